@@ -403,6 +403,26 @@ def cpu_baseline(threads):
                       "step takes 0.74x the reference modules' (profiles/r03_cpu_baseline_calibration.txt), i.e. this figure flatters the CPU by ~1.35x"}
 
 
+DUMP_SAMPLE = 1 << 21          # elements per dumped buffer: a dump is 3 x 8 MB of float32 (+ the loss)
+
+
+def dump_outputs(path, loss, engine):
+    """--dump-outputs: what the last timed step handed its caller -- the loss, the trainable parameters it updated (bf16 model
+    weights, the optimizer's fp32 master copy) and AdamW's first moment (the gradient's trace) -- as float32 .npy files.  A buffer
+    longer than DUMP_SAMPLE is sampled at fixed, seeded positions (sorted), the same on every run with the same arguments."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    opt = engine.optimizer
+    bufs = {"params": engine.flat.params, "master_params": opt.master, "exp_avg": opt.exp_avg}
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    for name, buf in bufs.items():
+        buf = buf.reshape(-1)
+        if buf.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, buf.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            buf = buf[idx.to(buf.device)]
+        np.save(os.path.join(path, f"{name}.npy"), buf.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -421,11 +441,16 @@ def main():
                          "all-reduces between them) with the eager step bit for bit on every rank; if it passes, four fenced steps of each mode "
                          "are timed and the faster one (slowest rank) runs; N = 1 runs eager.  MPV_GRAPH=1 / 0 in the environment mean "
                          "graph / eager when the flag is absent")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, a seeded sample of the updated parameters and "
+                         "of AdamW's first moment) to DIR/<name>.npy in float32 (rank 0)")
     ap.add_argument("--_test-cpu", dest="test_cpu", action="store_true", help=argparse.SUPPRESS)
     # TEST HOOK (tests/test_entrypoint_gpu.py): N ranks on ONE GPU over gloo on device tensors (RCCL refuses two ranks per device) -- the whole N > 1
     # flow (self-check, mode probe, fenced timed region, roofline steps on every rank) on real kernels where only 1-GPU boxes exist; the line says TEST
     ap.add_argument("--_test-one-gpu", dest="test_one_gpu", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     global _ON_CPU
     _ON_CPU = bool(args.test_cpu)
     if "MPV_BENCH_DEVICE" in os.environ:
@@ -607,6 +632,8 @@ def main():
     if sampler is not None:
         sampler.__exit__()
     final_loss = loss.item()                    # of the LAST TIMED step (under graph replay `loss` is a static buffer the extra launches below overwrite)
+    if args.dump_outputs and rank == 0:         # before the extra steps below move the parameters on
+        dump_outputs(args.dump_outputs, loss, engine)
     log(f"host enqueue time {t_enq / args.steps * 1e3:.1f} ms/step wall, {t_cpu / args.steps * 1e3:.1f} ms/step CPU (launch-bound if the CPU figure approaches the step time)" +
         (" [graph replay]" if use_graph else ""))
     # the same on an IDLE queue (nothing to wait for): what the host really spends to launch one step

@@ -3,6 +3,7 @@
 Usage (this container only; needs /root/reference):
     python -m oracle.gen_golden tiny        # full tensors, CONFIG_TINY, B=2, L=8 (ragged mask)
     python -m oracle.gen_golden configA     # BASELINE.json configs[0]: 1.3B dims, B=2, T=4, L=16
+    python -m oracle.gen_golden ref_modules_small randaugment_digests search_stub resize_embed   # reference records of CPU tests
 
 For each case the reference DistributedGPT3_Pretrain (models/distributed_gpt3.py:31-226) is
 run in eval() mode (dropout off -- SURVEY.md section 7 "Dropout parity") in fp32 ("intended
@@ -14,6 +15,7 @@ sample.  Weights and inputs are NOT stored: they are regenerated bit-identically
 """
 from __future__ import annotations
 
+import dataclasses
 import os
 import sys
 import time
@@ -385,9 +387,193 @@ def run_video(name: str = "video_tiny"):
     print("wrote", path, os.path.getsize(path) // 1024, "KiB")
 
 
+# ------------------------------------------------------------------------------ goldens of the CPU tests that once read the reference live
+# CONFIG_TINY's structure (two ViT blocks, two decoder layers, temporal attention, query tokens, ragged titles) at narrow, pairwise distinct
+# widths (tokens per frame 5, queries 6, ViT width 16 / head 8, decoder width 160 / head 80): every gradient of the reference fits a
+# small golden whole, in fp32
+CONFIG_REF_MODULES = dataclasses.replace(CONFIG_TINY, img_size=16, patch_size=8, vit_dim=16, vit_heads=2, num_frames=3, num_queries=6,
+                                         hidden=160, heads=2, ffn=224, vocab=112, max_pos=64)
+REF_MODULE_CASES = {   # name: (connect_ln, weight_seed, input_seed, gradients recorded whole: None = every trainable one); B=3, L=10 ragged
+    "plain": (False, 5, 11, None),
+    "connect_ln": (True, 6, 12, ["visual_norm.weight", "visual_norm.bias", "visual_fc.weight", "learnable_queries",
+                                 "visual_encoder.blocks.0.attn.qkv.weight"]),
+}
+
+
+def run_ref_modules(name: str = "ref_modules_small"):
+    """The reference DistributedGPT3_Pretrain on CONFIG_REF_MODULES, plain and with visual_cfg['connect_ln'] (models/distributed_gpt3.py:112-115,136),
+    fp32, eval(): logits, last hidden state, the named gradients whole, and the state-dict layout (key -> shape)."""
+    rec = {"meta": dict(case=name, batch=3, text_len=10, ragged=True, config=dataclasses.asdict(CONFIG_REF_MODULES), torch=str(torch.__version__))}
+    for case, (connect_ln, wseed, iseed, keys) in REF_MODULE_CASES.items():
+        cfg = dataclasses.replace(CONFIG_REF_MODULES, connect_ln=connect_ln)
+        model, sd = build_reference_model(cfg, wseed)
+        video, ids, mask = make_inputs(cfg, 3, 10, seed=iseed, ragged=True)
+        loss, out, _ = reference_forward(model, video, ids, mask)
+        loss.backward()
+        params = dict(model.named_parameters())
+        keys = keys or [n for n, p in params.items() if p.grad is not None]
+        rec[case] = {"weight_seed": wseed, "input_seed": iseed, "connect_ln": connect_ln, "loss": loss.detach().clone(),
+                     "logits": out.logits.detach().clone(), "last_hidden_state": out.last_hidden_state.detach().clone(),
+                     "grad": {n: params[n].grad.detach().clone() for n in keys}, "visual_norm_type": type(model.visual_norm).__name__,
+                     "state_dict_shapes": {k: tuple(v.shape) for k, v in model.state_dict().items()}}
+        print(f"[{name}/{case}] loss={loss.item():.6f}, {len(keys)} gradients", flush=True)
+        del model, sd
+    path = os.path.join(GOLDEN_DIR, f"{name}.pt")
+    torch.save(rec, path)
+    print("wrote", path, os.path.getsize(path) // 1024, "KiB")
+
+
+RANDAUG_LEVELS, RANDAUG_MS, RANDAUG_SEEDS = (0, 3, 5, 10), (5, 3, 10), range(8)
+
+
+def randaug_frames():
+    import numpy as np
+    return np.random.default_rng(0).integers(0, 256, size=(4, 48, 56, 3), dtype=np.uint8)
+
+
+def array_digest(a) -> str:
+    """SHA-256 over dtype, shape and bytes: two arrays have the same digest exactly when they have the same dtype, shape and contents"""
+    import hashlib
+    import numpy as np
+    a = np.ascontiguousarray(a)
+    h = hashlib.sha256(f"{a.dtype.str}{a.shape}".encode())
+    h.update(a.tobytes())
+    return h.hexdigest()
+
+
+def run_randaugment(name: str = "randaugment_digests"):
+    """The reference's dataset/video_utils/randaugment_video.py with oracle/cv2_shim.py standing in for opencv: whole clips through
+    TemporalConsistentRandomAugment(N=2, M) after np.random.seed(seed), and every op's arguments and output on one frame per level.
+    The tests only ask for equality, so each output array is recorded by its array_digest."""
+    import importlib.util
+    import numpy as np
+    from . import augment as A, cv2_shim
+    from .ref_loader import REF_ROOT
+    cv2_shim.install()
+    spec = importlib.util.spec_from_file_location("ref_randaugment_video", os.path.join(REF_ROOT, "dataset", "video_utils", "randaugment_video.py"))
+    ref = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ref)
+    frames = randaug_frames()
+    rec = {"meta": dict(case=name, augs=list(A.DEFAULT_AUGS), torch=str(torch.__version__)), "clips": {}, "args": {}, "ops": {}}
+    for M in RANDAUG_MS:
+        for seed in RANDAUG_SEEDS:
+            np.random.seed(seed)
+            rec["clips"][(M, seed)] = array_digest(ref.TemporalConsistentRandomAugment(N=2, M=M, augs=A.DEFAULT_AUGS)(torch.from_numpy(frames)).numpy())
+    for op in A.DEFAULT_AUGS:
+        for level in RANDAUG_LEVELS:
+            args = ref.arg_dict[op](level)
+            rec["args"][(op, level)] = args
+            rec["ops"][(op, level)] = array_digest(ref.func_dict[op](frames[1], *args))
+    path = os.path.join(GOLDEN_DIR, f"{name}.pt")
+    torch.save(rec, path)
+    print("wrote", path, os.path.getsize(path) // 1024, "KiB")
+
+
+class StubLogits:
+    """Deterministic logits as a function of a sequence's token prefix, so the reference's search loops and ours can be
+    driven from the SAME source (the search logic is discrete: it must agree token for token)."""
+
+    def __init__(self, vocab, stop, seed=0):
+        self.vocab, self.stop, self.seed = vocab, stop, seed
+
+    def row(self, prefix):
+        g = torch.Generator().manual_seed((hash(tuple(int(t) for t in prefix)) ^ self.seed) & 0x7FFFFFFF)
+        lg = torch.randn(self.vocab, generator=g) * 2.0
+        lg[self.stop] += 1.0 + 0.35 * len(prefix)          # the stop token becomes likely as the sequence grows
+        return lg
+
+
+# the search cases of tests/test_host_cpu.py: (stub vocab, stub seed, config, prompt tokens, prompt lengths or None, query slots)
+BEAM_CASES = {(seed, Q): (37, seed, dict(tokens_to_generate=9, eod_id=7, max_position_embeddings=64), [[5, 11, 3, 7, 7]], None, Q)
+              for seed in (1, 2, 3, 4) for Q in (0, 3)}
+SAMPLE_CASES = {Q: (29, 9, dict(tokens_to_generate=8, eod_id=7, max_position_embeddings=40), [[5, 11, 3, 2], [4, 9, 7, 7], [6, 6, 6, 1]],
+                    [4, 2, 3], Q) for Q in (0, 2)}
+
+
+def reference_search(kind, stub, tokens, query_embeds, cfg_over, **kw):
+    """Runs the reference's own DistributedGPT3.beam_search / .sample (models/modeling_distributed_gpt3.py:1620-1873) on a
+    stand-in `self` whose forward returns the stub logits; token prefixes ride in the InferenceParams KV dict so that
+    swap_key_value_dict re-orders them exactly as it re-orders a real cache."""
+    import types
+    from .ref_loader import cpu_generation_patches, import_reference
+    vt, mg, dg = import_reference()
+    import addict                                                       # oracle/shims (on sys.path after import_reference)
+
+    class Fake:
+        config = types.SimpleNamespace(tokens_to_generate=cfg_over["tokens_to_generate"], eod_id=cfg_over["eod_id"], top_k=1, top_p=0.0,
+                                       max_position_embeddings=cfg_over["max_position_embeddings"], vocab_size=stub.vocab)
+        inference_params = None
+
+        def __call__(self, tokens=None, query_embeds=None, attention_mask=None, position_ids=None):
+            d = self.inference_params.key_value_memory_dict
+            new = tokens.t().contiguous()                               # [n, beams]
+            pre = torch.cat([d[1][0], new], dim=0) if 1 in d else new
+            d[1] = (pre, pre)
+            B, n = tokens.shape
+            lg = torch.zeros(B, max(n, 1) + (0 if query_embeds is None else query_embeds.size(1)), stub.vocab)
+            for b in range(B):
+                lg[b, -1] = stub.row(pre[:, b].tolist())
+            return addict.Dict(logits=lg)
+
+    fake = Fake()
+    with torch.no_grad(), cpu_generation_patches():
+        if kind == "beam":
+            return mg.DistributedGPT3.beam_search(fake, tokens, query_embeds=query_embeds, **kw)
+        return mg.DistributedGPT3.sample(fake, tokens, query_embeds=query_embeds, **kw)
+
+
+def run_search(name: str = "search_stub"):
+    """The reference's beam search (beam 4, 3 returned, prompt length 3) and greedy sample (ragged prompt lengths) on the stub logits."""
+    rec = {"meta": dict(case=name, torch=str(torch.__version__)), "beam": {}, "sample": {}}
+    for key, (vocab, seed, cfgd, tokens, _, Q) in BEAM_CASES.items():
+        qe = torch.zeros(1, Q, 4) if Q else None
+        r = reference_search("beam", StubLogits(vocab, 7, seed), torch.tensor(tokens), qe, cfgd, beam_size=4, num_return_gen=3,
+                             prompt_length=torch.tensor(3))
+        rec["beam"][key] = {"sequences": r.sequences.clone(), "scores": r.scores.float().view(-1).clone()}
+    for key, (vocab, seed, cfgd, tokens, lengths, Q) in SAMPLE_CASES.items():
+        qe = torch.zeros(len(tokens), Q, 4) if Q else None
+        rec["sample"][key] = reference_search("sample", StubLogits(vocab, 7, seed), torch.tensor(tokens), qe, cfgd,
+                                              prompt_length=torch.tensor(lengths)).clone()
+    path = os.path.join(GOLDEN_DIR, f"{name}.pt")
+    torch.save(rec, path)
+    print("wrote", path, os.path.getsize(path) // 1024, "KiB")
+
+
+def resize_inputs():
+    g = torch.Generator().manual_seed(3)
+    return torch.randn(1, 1 + 14 * 14, 32, generator=g), torch.randn(1, 4, 32, generator=g)
+
+
+def resize_ckpt():
+    return {"blocks.0.attn.qkv.bias": torch.arange(9.0), "head.weight": torch.zeros(2), "blocks.0.attn.qkv.weight": torch.ones(3)}
+
+
+def run_resize(name: str = "resize_embed"):
+    """models/vision_transformer.py's resize_pos_embed (14^2 -> 16^2 grid), resize_temporal_embed (4 -> 8 frames) and
+    _convert_pretrained_vit on the seeded tensors of tests/test_engine_cpu.py::test_resize_pos_and_temporal_embed."""
+    from .ref_loader import import_reference
+    vt, _, _ = import_reference()
+    pos, tmp = resize_inputs()
+    rec = {"meta": dict(case=name, torch=str(torch.__version__)),
+           "pos_257": vt.resize_pos_embed(pos, torch.zeros(1, 257, 32)).clone(),
+           "temporal_8": vt.resize_temporal_embed(tmp, torch.zeros(1, 8, 32)).clone(),
+           "converted": {k: v.clone() for k, v in vt._convert_pretrained_vit(resize_ckpt()).items()}}
+    path = os.path.join(GOLDEN_DIR, f"{name}.pt")
+    torch.save(rec, path)
+    print("wrote", path, os.path.getsize(path) // 1024, "KiB")
+
+
 if __name__ == "__main__":
     for c in (sys.argv[1:] or ["tiny"]):
-        if c.startswith("retrieval"):
+        if c == "ref_modules_small":
+            run_ref_modules(c)
+        elif c == "randaugment_digests":
+            run_randaugment(c)
+        elif c == "search_stub":
+            run_search(c)
+        elif c == "resize_embed":
+            run_resize(c)
+        elif c.startswith("retrieval"):
             run_retrieval(c)
         elif c in ("itm", "cls"):
             run_gencls(c)

@@ -524,11 +524,14 @@ NAMES = ["ln_stream_fwd", "ln_stream_bwd", "LnDparamBatch", "accum_f32", "f32_to
 
 
 def install(monkeypatch):
-    """Replace the device wrappers of youku_mplug_amd.ops by the stand-ins above for the duration of a test."""
+    """Replace the device wrappers of youku_mplug_amd.ops by the stand-ins above for the duration of a test.  The stand-ins compute on
+    host tensors, so the code that picks its device or process-group backend from torch.cuda.is_available() (the entry points,
+    engine.init_process_group_for_dp) is shown a machine without a GPU, also where one is present."""
     import youku_mplug_amd  # noqa: F401
     from youku_mplug_amd import ops
     g = globals()
     for n in NAMES:
         monkeypatch.setattr(ops, n, g[n])
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
     from youku_mplug_amd import generation
     monkeypatch.setattr(generation.DecodeState, "step", decode_step)

@@ -134,7 +134,7 @@ def _data(n=8, dim=24):
     return torch.randn(n, dim, generator=g), torch.randn(n, 5, generator=g)
 
 
-def _engine_worker(rank, world, port, q, zero=0, ckpt_dir=None):
+def _engine_worker(rank, world, port, q, received, zero=0, ckpt_dir=None):
     import torch.distributed as dist
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -177,6 +177,7 @@ def _engine_worker(rank, world, port, q, zero=0, ckpt_dir=None):
         extra = (files, torch.equal(before[0], engine.flat.params) and torch.equal(before[1], opt.exp_avg) and opt.step_count == before[2],
                  (opt.lo, opt.hi), gathers[0], engine.flat.numel)
     q.put((rank, p0, engine.flat.params.clone(), list(engine.flat.stage_slices.items()), launched[:6], opt._global_grad_norm, extra))
+    received.wait(timeout=300)  # the parent takes the tensors over from this process: stay alive until it has them
     dist.barrier()
     dist.destroy_process_group()
 
@@ -187,12 +188,13 @@ def test_real_engine_world2_gloo(monkeypatch):
     batch (mean gradient, clip on the reduced gradient, 1/world folded into AdamW)."""
     import torch.multiprocessing as mp
     ctx = mp.get_context("spawn")
-    q = ctx.Queue()
+    q, received = ctx.Queue(), ctx.Event()
     port = 23000 + os.getpid() % 3000
-    procs = [ctx.Process(target=_engine_worker, args=(r, 2, port, q)) for r in range(2)]
+    procs = [ctx.Process(target=_engine_worker, args=(r, 2, port, q, received)) for r in range(2)]
     for p in procs:
         p.start()
     res = {r[0]: r[1:] for r in (q.get(timeout=180) for _ in range(2))}
+    received.set()
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0
@@ -228,14 +230,15 @@ def test_zero_stage1_world2_gloo_matches_replicated_optimizer(tmp_path):
     ctx = mp.get_context("spawn")
     results = {}
     for zero in (0, 1):
-        q = ctx.Queue()
+        q, received = ctx.Queue(), ctx.Event()
         port = 26000 + (os.getpid() + 17 * zero) % 3000
         d = str(tmp_path / f"ck{zero}")
         os.makedirs(d, exist_ok=True)
-        procs = [ctx.Process(target=_engine_worker, args=(r, 2, port, q, zero, d)) for r in range(2)]
+        procs = [ctx.Process(target=_engine_worker, args=(r, 2, port, q, received, zero, d)) for r in range(2)]
         for p in procs:
             p.start()
         res = {r[0]: r[1:] for r in (q.get(timeout=180) for _ in range(2))}
+        received.set()
         for p in procs:
             p.join(timeout=60)
         results[zero] = res
@@ -403,26 +406,23 @@ def test_pretrained_ckpt_initialises_vision_tower(tmp_path, monkeypatch):
 
 
 def test_resize_pos_and_temporal_embed():
+    from oracle.gen_golden import resize_ckpt, resize_inputs
     from youku_mplug_amd.vision import resize_pos_embed, resize_temporal_embed
-    g = torch.Generator().manual_seed(3)
-    pos = torch.randn(1, 1 + 14 * 14, 32, generator=g)
+    pos, tmp = resize_inputs()
     new = resize_pos_embed(pos, torch.zeros(1, 1 + 16 * 16, 32))
     assert new.shape == (1, 257, 32) and torch.equal(new[:, 0], pos[:, 0])
     assert torch.equal(resize_pos_embed(pos, torch.zeros(1, 197, 32)), pos)         # same grid: identity
-    tmp = torch.randn(1, 4, 32, generator=g)
     t8 = resize_temporal_embed(tmp, torch.zeros(1, 8, 32))
     assert t8.shape == (1, 8, 32) and torch.allclose(t8[:, 0], tmp[:, 0]) and torch.allclose(t8[:, -1], tmp[:, -1])
     pad = resize_temporal_embed(tmp, torch.zeros(1, 6, 32), mode="padding")
     assert torch.equal(pad[:, :4], tmp) and pad[:, 4:].abs().sum() == 0
-    from oracle import ref_loader
-    if ref_loader.reference_available():      # the reference's own functions (build container only), same tensors
-        vt, _, _ = ref_loader.import_reference()
-        assert torch.equal(vt.resize_pos_embed(pos, torch.zeros(1, 257, 32)), new)
-        assert torch.equal(vt.resize_temporal_embed(tmp, torch.zeros(1, 8, 32)), t8)
-        w = {"blocks.0.attn.qkv.bias": torch.arange(9.0), "head.weight": torch.zeros(2), "blocks.0.attn.qkv.weight": torch.ones(3)}
-        from youku_mplug_amd.vision import convert_pretrained_vit
-        a, b = convert_pretrained_vit(dict(w)), vt._convert_pretrained_vit(dict(w))
-        assert set(a) == set(b) and all(torch.equal(a[k], b[k]) for k in a)
+    # the reference's own functions on the same tensors (tests/golden/resize_embed.pt, oracle/gen_golden.py:run_resize)
+    ref = torch.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "resize_embed.pt"))
+    assert torch.equal(ref["pos_257"], new)
+    assert torch.equal(ref["temporal_8"], t8)
+    from youku_mplug_amd.vision import convert_pretrained_vit
+    a, b = convert_pretrained_vit(resize_ckpt()), ref["converted"]
+    assert set(a) == set(b) and all(torch.equal(a[k], b[k]) for k in a)
 
 
 def test_load_checkpoint_resizes_visual_embeds(monkeypatch, tmp_path):
@@ -446,7 +446,7 @@ def test_load_checkpoint_resizes_visual_embeds(monkeypatch, tmp_path):
 
 
 # ------------------------------------------------------------------------------ wire dtype of the gradient sum, world 8
-def _sum_worker(rank, world, port, q, comm):
+def _sum_worker(rank, world, port, q, received, comm):
     import torch.distributed as dist
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -463,6 +463,7 @@ def _sum_worker(rank, world, port, q, comm):
     red.finish()
     if rank == 0:
         q.put(flat.grads.float().clone())
+        received.wait(timeout=300)  # the parent takes the tensors over from this process: stay alive until it has them
     dist.barrier()
     dist.destroy_process_group()
 
@@ -475,12 +476,13 @@ def test_bf16_bucket_sum_error_world8_gloo(comm):
     import torch.multiprocessing as mp
     world, n = 8, 4096 * 3
     ctx = mp.get_context("spawn")
-    q = ctx.Queue()
+    q, received = ctx.Queue(), ctx.Event()
     port = 28000 + os.getpid() % 1500 + (7 if comm == "fp32" else 0)
-    procs = [ctx.Process(target=_sum_worker, args=(r, world, port, q, comm)) for r in range(world)]
+    procs = [ctx.Process(target=_sum_worker, args=(r, world, port, q, received, comm)) for r in range(world)]
     for p in procs:
         p.start()
     got = q.get(timeout=300)
+    received.set()
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0
@@ -495,7 +497,7 @@ def test_bf16_bucket_sum_error_world8_gloo(comm):
 
 
 # ------------------------------------------------------------------ graph segments: the reducer's cut / issue / drain protocol, world 2
-def _cut_worker(rank, world, port, q):
+def _cut_worker(rank, world, port, q, received):
     import torch.distributed as dist
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -540,6 +542,7 @@ def _cut_worker(rank, world, port, q):
         out.append((replayed, flat.grads.float().clone()))
     if rank == 0:
         q.put(out)
+        received.wait(timeout=300)  # the parent takes the tensors over from this process: stay alive until it has them
     dist.barrier()
     dist.destroy_process_group()
 
@@ -550,12 +553,13 @@ def test_reducer_cut_issue_drain_protocol_world2_gloo():
     bucket once, in announcement order, then the wait; replaying it sums the ranks' gradients exactly as the eager protocol does."""
     import torch.multiprocessing as mp
     ctx = mp.get_context("spawn")
-    q = ctx.Queue()
+    q, received = ctx.Queue(), ctx.Event()
     port = 26500 + os.getpid() % 1500
-    procs = [ctx.Process(target=_cut_worker, args=(r, 2, port, q)) for r in range(2)]
+    procs = [ctx.Process(target=_cut_worker, args=(r, 2, port, q, received)) for r in range(2)]
     for p in procs:
         p.start()
     out = q.get(timeout=300)
+    received.set()
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0

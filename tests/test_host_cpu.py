@@ -75,86 +75,84 @@ def test_restatement_matches_goldens_tiny():
         assert abs(sd[n].grad.norm().item() - gn) <= 1e-4 * gn + 1e-9, n
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/models"), reason="reference tree only exists in the build container")
 def test_restatement_matches_reference_modules_live():
+    """The restatement against the reference's own DistributedGPT3_Pretrain (CONFIG_REF_MODULES: CONFIG_TINY's structure at narrow
+    widths; weight seed 5, B=3, L=10 ragged): logits, last hidden state and every gradient, and the state-dict drop-in layout
+    (tests/golden/ref_modules_small.pt, written from the reference modules by oracle/gen_golden.py)."""
+    import dataclasses
     from oracle import restate
-    from oracle.ref_loader import build_reference_model, reference_forward
-    from oracle.weights import CONFIG_TINY, make_inputs
-    model, sd = build_reference_model(CONFIG_TINY, 5)
-    video, ids, mask = make_inputs(CONFIG_TINY, 3, 10, seed=11, ragged=True)
-    loss, out, _ = reference_forward(model, video, ids, mask)
-    loss.backward()
-    sdd = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
-    r = restate.pretrain_forward(video, ids, mask, sdd, CONFIG_TINY)
+    from oracle.gen_golden import CONFIG_REF_MODULES as cfg
+    from oracle.weights import make_inputs, make_state_dict
+    gold = torch.load(os.path.join(GOLD, "ref_modules_small.pt"))
+    assert gold["meta"]["config"] == dataclasses.asdict(cfg)
+    g = gold["plain"]
+    video, ids, mask = make_inputs(cfg, 3, 10, seed=g["input_seed"], ragged=True)
+    sdd = {k: v.clone().requires_grad_(True) for k, v in make_state_dict(cfg, g["weight_seed"]).items()}
+    r = restate.pretrain_forward(video, ids, mask, sdd, cfg)
     r["loss"].backward()
-    assert rel(r["logits"], out.logits) < 1e-5 and rel(r["last_hidden_state"], out.last_hidden_state) < 1e-5
-    for n, p in model.named_parameters():
-        if p.grad is not None:
-            assert rel(sdd[n].grad, p.grad) < 1e-4, n
+    assert rel(r["logits"], g["logits"]) < 1e-5 and rel(r["last_hidden_state"], g["last_hidden_state"]) < 1e-5
+    assert len(g["grad"]) > 0
+    for n, ref_grad in g["grad"].items():
+        assert rel(sdd[n].grad, ref_grad) < 1e-4, n
     # state-dict drop-in: identical keys and shapes
     from youku_mplug_amd.pretrain import synthetic_model
-    mine = synthetic_model(CONFIG_TINY, device="cpu").state_dict()
-    ref = model.state_dict()
+    mine = synthetic_model(cfg, device="cpu").state_dict()
+    ref = g["state_dict_shapes"]
     assert list(sorted(mine)) == list(sorted(ref))
     for k in ref:
-        assert tuple(mine[k].shape) == tuple(ref[k].shape), k
+        assert tuple(mine[k].shape) == tuple(ref[k]), k
 
 
 def test_connect_ln_restatement_matches_reference_modules_live():
     """visual_cfg['connect_ln'] (models/distributed_gpt3.py:112-115,136): LayerNormWithForceFP32 behind visual_fc.  The restatement
-    against the reference's own module built with the flag, and the product's state-dict layout against the reference's."""
+    against the reference's own module built with the flag, and the product's state-dict layout against the reference's
+    (tests/golden/ref_modules_small.pt, written from the reference modules by oracle/gen_golden.py)."""
     import dataclasses
     from oracle import restate
-    from oracle.ref_loader import build_reference_model, reference_forward
-    from oracle.weights import CONFIG_TINY, make_inputs
-    cfg = dataclasses.replace(CONFIG_TINY, connect_ln=True)
-    model, sd = build_reference_model(cfg, 6)
-    assert "visual_norm.weight" in sd and type(model.visual_norm).__name__ != "Identity"
-    video, ids, mask = make_inputs(cfg, 3, 10, seed=12, ragged=True)
-    loss, out, _ = reference_forward(model, video, ids, mask)
-    loss.backward()
-    sdd = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
+    from oracle.gen_golden import CONFIG_REF_MODULES
+    from oracle.weights import make_inputs, make_state_dict
+    gold = torch.load(os.path.join(GOLD, "ref_modules_small.pt"))
+    assert gold["meta"]["config"] == dataclasses.asdict(CONFIG_REF_MODULES)
+    g = gold["connect_ln"]
+    cfg = dataclasses.replace(CONFIG_REF_MODULES, connect_ln=True)
+    ref = g["state_dict_shapes"]
+    assert "visual_norm.weight" in ref and g["visual_norm_type"] != "Identity"
+    video, ids, mask = make_inputs(cfg, 3, 10, seed=g["input_seed"], ragged=True)
+    sdd = {k: v.clone().requires_grad_(True) for k, v in make_state_dict(cfg, g["weight_seed"]).items()}
     r = restate.pretrain_forward(video, ids, mask, sdd, cfg)
     r["loss"].backward()
-    assert rel(r["logits"], out.logits) < 1e-5 and rel(r["last_hidden_state"], out.last_hidden_state) < 1e-5
+    assert rel(r["logits"], g["logits"]) < 1e-5 and rel(r["last_hidden_state"], g["last_hidden_state"]) < 1e-5
     for n in ("visual_norm.weight", "visual_norm.bias", "visual_fc.weight", "learnable_queries", "visual_encoder.blocks.0.attn.qkv.weight"):
-        assert rel(sdd[n].grad, dict(model.named_parameters())[n].grad) < 1e-4, n
+        assert rel(sdd[n].grad, g["grad"][n]) < 1e-4, n
     from youku_mplug_amd.pretrain import synthetic_model
     mine = synthetic_model(cfg, device="cpu").state_dict()
-    ref = model.state_dict()
     assert list(sorted(mine)) == list(sorted(ref))
-    assert tuple(mine["visual_norm.weight"].shape) == tuple(ref["visual_norm.weight"].shape)
+    assert tuple(mine["visual_norm.weight"].shape) == tuple(ref["visual_norm.weight"])
 
 
 def test_randaugment_restatement_vs_reference_module_through_cv2_shim():
     """oracle/augment.py against the reference's dataset/video_utils/randaugment_video.py, imported with oracle/cv2_shim.py standing
     in for opencv (not installed): the class-level draw logic (ops per clip, apply mask, level -> arguments), the numpy ops and the
     code around the cv2 calls are the reference's own; the cv2 calls themselves land in the oracle's restatement of opencv
-    ("parity unpinned" at that boundary, see oracle/augment.py)."""
-    import importlib.util
+    ("parity unpinned" at that boundary, see oracle/augment.py).  The reference's outputs are recorded in
+    tests/golden/randaugment_digests.pt, written through the same shim by oracle/gen_golden.py, by their digest over dtype, shape and
+    contents (oracle/gen_golden.py:array_digest): equal digests are equal dtype and equal arrays."""
     import numpy as np
-    ref_file = "/root/reference/dataset/video_utils/randaugment_video.py"
-    if not os.path.isfile(ref_file):
-        pytest.skip("reference not present")
-    from oracle import augment as A, cv2_shim
-    cv2_shim.install()
-    spec = importlib.util.spec_from_file_location("ref_randaugment_video", ref_file)
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
-    rng = np.random.default_rng(0)
-    frames = rng.integers(0, 256, size=(4, 48, 56, 3), dtype=np.uint8)
-    for M in (5, 3, 10):
-        for seed in range(8):
-            np.random.seed(seed)
-            r = ref.TemporalConsistentRandomAugment(N=2, M=M, augs=A.DEFAULT_AUGS)(torch.from_numpy(frames)).numpy()
+    from oracle import augment as A
+    from oracle.gen_golden import RANDAUG_LEVELS, RANDAUG_MS, RANDAUG_SEEDS, array_digest, randaug_frames
+    g = torch.load(os.path.join(GOLD, "randaugment_digests.pt"))
+    assert g["meta"]["augs"] == list(A.DEFAULT_AUGS)
+    frames = randaug_frames()
+    for M in RANDAUG_MS:
+        for seed in RANDAUG_SEEDS:
             np.random.seed(seed)
             o = A.TemporalConsistentRandomAugment(N=2, M=M, augs=A.DEFAULT_AUGS)(frames)
-            assert r.dtype == o.dtype and np.array_equal(r, o), (M, seed)
+            assert array_digest(o) == g["clips"][(M, seed)], (M, seed, o.dtype)
     for name in A.DEFAULT_AUGS:
-        for level in (0, 3, 5, 10):
-            assert ref.arg_dict[name](level) == A.level_to_args(name, level), (name, level)
-            got, want = A.FUNC[name](frames[1], *A.level_to_args(name, level)), ref.func_dict[name](frames[1], *ref.arg_dict[name](level))
-            assert np.array_equal(got, want), (name, level)
+        for level in RANDAUG_LEVELS:
+            assert g["args"][(name, level)] == A.level_to_args(name, level), (name, level)
+            got = A.FUNC[name](frames[1], *A.level_to_args(name, level))
+            assert array_digest(got) == g["ops"][(name, level)], (name, level, got.dtype)
     # restated opencv pieces: properties that do not need opencv to check
     img = frames[0]
     assert np.array_equal(A.warp_affine_linear(img, np.float32([[1, 0, 0], [0, 1, 0]]), (128, 128, 128)), img)
@@ -223,7 +221,7 @@ def test_flat_params_views_and_stages():
     assert (tg != 255).sum().item() >= used // eng.TILE
 
 
-def _dp_worker(rank, world, port, q):
+def _dp_worker(rank, world, port, q, received):
     import torch.distributed as dist
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -247,6 +245,7 @@ def _dp_worker(rank, world, port, q):
     red.finish()
     avg = flat.grads / world
     q.put((rank, avg.clone()))
+    received.wait(timeout=300)  # the parent takes the tensors over from this process: stay alive until it has them
     dist.barrier()
     dist.destroy_process_group()
 
@@ -255,12 +254,13 @@ def test_dp_gloo_world2_matches_single_process():
     """N>1 path on CPU: mean of per-rank gradients == gradient of the mean of per-rank losses."""
     import torch.multiprocessing as mp
     ctx = mp.get_context("spawn")
-    q = ctx.Queue()
+    q, received = ctx.Queue(), ctx.Event()
     port = 29500 + os.getpid() % 2000
-    procs = [ctx.Process(target=_dp_worker, args=(r, 2, port, q)) for r in range(2)]
+    procs = [ctx.Process(target=_dp_worker, args=(r, 2, port, q, received)) for r in range(2)]
     for p in procs:
         p.start()
     res = dict(q.get(timeout=120) for _ in range(2))
+    received.set()
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0
@@ -305,7 +305,7 @@ def test_retrieval_state_dict_layout():
     assert id(model.learnable_queries) in unused and id(model.vision_proj.weight) not in unused
 
 
-def _itc_worker(rank, world, port, q):
+def _itc_worker(rank, world, port, q, received):
     import torch.distributed as dist
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -321,6 +321,7 @@ def _itc_worker(rank, world, port, q):
     w_r = torch.randn(world * 4, 8, generator=torch.Generator().manual_seed(100 + rank))
     d_mine = reduce_scatter_sum(w_r * allf)
     q.put((rank, allf.clone(), ids.clone(), d_mine.clone()))
+    received.wait(timeout=300)  # the parent takes the tensors over from this process: stay alive until it has them
     dist.barrier()
     dist.destroy_process_group()
 
@@ -329,12 +330,13 @@ def test_itc_collectives_gloo_world2():
     """all-gather forward / reduce-scatter backward of the ITC features (models/distributed_utils.py:285-311)."""
     import torch.multiprocessing as mp
     ctx = mp.get_context("spawn")
-    q = ctx.Queue()
+    q, received = ctx.Queue(), ctx.Event()
     port = 31500 + os.getpid() % 2000
-    procs = [ctx.Process(target=_itc_worker, args=(r, 2, port, q)) for r in range(2)]
+    procs = [ctx.Process(target=_itc_worker, args=(r, 2, port, q, received)) for r in range(2)]
     for p in procs:
         p.start()
     res = {r: (a, i, d) for r, a, i, d in (q.get(timeout=120) for _ in range(2))}
+    received.set()
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0
@@ -391,51 +393,9 @@ def test_restatement_eva_image_model_vs_golden():
 
 
 # ------------------------------------------------------------------------------ generation host logic
-class _StubLogits:
-    """Deterministic logits as a function of a sequence's token prefix, so the reference's search loops and ours can be
-    driven from the SAME source (the search logic is discrete: it must agree token for token)."""
-
-    def __init__(self, vocab, stop, seed=0):
-        self.vocab, self.stop, self.seed = vocab, stop, seed
-
-    def row(self, prefix):
-        g = torch.Generator().manual_seed((hash(tuple(int(t) for t in prefix)) ^ self.seed) & 0x7FFFFFFF)
-        lg = torch.randn(self.vocab, generator=g) * 2.0
-        lg[self.stop] += 1.0 + 0.35 * len(prefix)          # the stop token becomes likely as the sequence grows
-        return lg
-
-
-def _reference_search(kind, stub, tokens, query_embeds, cfg_over, **kw):
-    """Runs the reference's own DistributedGPT3.beam_search / .sample (models/modeling_distributed_gpt3.py:1620-1873) on a
-    stand-in `self` whose forward returns the stub logits; token prefixes ride in the InferenceParams KV dict so that
-    swap_key_value_dict re-orders them exactly as it re-orders a real cache."""
-    from oracle.ref_loader import cpu_generation_patches, import_reference
-    vt, mg, dg = import_reference()
-    import addict                                                       # oracle/shims (on sys.path after import_reference)
-
-    class Fake:
-        config = types.SimpleNamespace(tokens_to_generate=cfg_over["tokens_to_generate"], eod_id=cfg_over["eod_id"], top_k=1, top_p=0.0,
-                                       max_position_embeddings=cfg_over["max_position_embeddings"], vocab_size=stub.vocab)
-        inference_params = None
-
-        def __call__(self, tokens=None, query_embeds=None, attention_mask=None, position_ids=None):
-            d = self.inference_params.key_value_memory_dict
-            new = tokens.t().contiguous()                               # [n, beams]
-            pre = torch.cat([d[1][0], new], dim=0) if 1 in d else new
-            d[1] = (pre, pre)
-            B, n = tokens.shape
-            lg = torch.zeros(B, max(n, 1) + (0 if query_embeds is None else query_embeds.size(1)), stub.vocab)
-            for b in range(B):
-                lg[b, -1] = stub.row(pre[:, b].tolist())
-            return addict.Dict(logits=lg)
-
-    fake = Fake()
-    with torch.no_grad(), cpu_generation_patches():
-        if kind == "beam":
-            return mg.DistributedGPT3.beam_search(fake, tokens, query_embeds=query_embeds, **kw)
-        return mg.DistributedGPT3.sample(fake, tokens, query_embeds=query_embeds, **kw)
-
-
+# The search loops are driven by oracle/gen_golden.py's StubLogits (deterministic logits as a function of a sequence's token prefix); the
+# reference's own DistributedGPT3.beam_search / .sample (models/modeling_distributed_gpt3.py:1620-1873) driven by the same stub wrote
+# tests/golden/search_stub.pt (oracle/gen_golden.py:run_search).  The search logic is discrete: it must agree token for token.
 class _StubState:
     def __init__(self, stub, batch, max_len):
         self.stub, self.prefix, self.q = stub, None, 0
@@ -463,31 +423,32 @@ def _torch_topk(logits, k, add):
 def test_beam_search_host_logic_matches_reference(seed, Q):
     """generation.beam_search_loop == the reference's beam_search (same hypotheses bookkeeping, stop-token handling,
     done test, beam re-ordering, final ranking) when both are fed the same logits -- sequences and scores exact."""
+    from oracle.gen_golden import BEAM_CASES, StubLogits
     from youku_mplug_amd import generation
-    stub = _StubLogits(vocab=37, stop=7, seed=seed)
-    cfgd = dict(tokens_to_generate=9, eod_id=7, max_position_embeddings=64)
-    tokens = torch.tensor([[5, 11, 3, 7, 7]])
+    vocab, stub_seed, cfgd, tokens, _, _ = BEAM_CASES[(seed, Q)]
+    stub = StubLogits(vocab=vocab, stop=7, seed=stub_seed)
+    tokens = torch.tensor(tokens)
     qe = torch.zeros(1, Q, 4) if Q else None
-    ref = _reference_search("beam", stub, tokens.clone(), qe, cfgd, beam_size=4, num_return_gen=3, prompt_length=torch.tensor(3))
+    ref = torch.load(os.path.join(GOLD, "search_stub.pt"))["beam"][(seed, Q)]
     cfg = types.SimpleNamespace(**cfgd, top_k=1, top_p=0.0, vocab_size=stub.vocab)
     out = generation.beam_search_loop(cfg, lambda b, m: _StubState(stub, b, m), tokens.clone(), query_embeds=qe, beam_size=4,
                                       num_return_gen=3, prompt_length=3, topk_fn=_torch_topk)
-    assert out.sequences.shape == ref.sequences.shape
-    assert torch.equal(out.sequences, ref.sequences), (out.sequences.tolist(), ref.sequences.tolist())
-    assert torch.allclose(out.scores, ref.scores.float().view(-1), atol=1e-5)
+    assert out.sequences.shape == ref["sequences"].shape
+    assert torch.equal(out.sequences, ref["sequences"]), (out.sequences.tolist(), ref["sequences"].tolist())
+    assert torch.allclose(out.scores, ref["scores"], atol=1e-5)
 
 
 @pytest.mark.parametrize("Q", [0, 2])
 def test_greedy_sample_host_logic_matches_reference(Q):
     """generation.sample_loop (top_k = 1) == the reference's sample(): ragged prompt lengths, teacher-forced prompt
     tokens until `started`, termination bookkeeping and the returned slice."""
+    from oracle.gen_golden import SAMPLE_CASES, StubLogits
     from youku_mplug_amd import generation
-    stub = _StubLogits(vocab=29, stop=7, seed=9)
-    cfgd = dict(tokens_to_generate=8, eod_id=7, max_position_embeddings=40)
-    tokens = torch.tensor([[5, 11, 3, 2], [4, 9, 7, 7], [6, 6, 6, 1]])
-    lengths = torch.tensor([4, 2, 3])
+    vocab, stub_seed, cfgd, tokens, lengths, _ = SAMPLE_CASES[Q]
+    stub = StubLogits(vocab=vocab, stop=7, seed=stub_seed)
+    tokens, lengths = torch.tensor(tokens), torch.tensor(lengths)
     qe = torch.zeros(3, Q, 4) if Q else None
-    ref = _reference_search("sample", stub, tokens.clone(), qe, cfgd, prompt_length=lengths.clone())
+    ref = torch.load(os.path.join(GOLD, "search_stub.pt"))["sample"][Q]
     cfg = types.SimpleNamespace(**cfgd, top_k=1, top_p=0.0, vocab_size=stub.vocab)
     import youku_mplug_amd.generation as G
     orig = G.sample_token

@@ -180,6 +180,9 @@ def test_loss_window_is_exact_on_standins(monkeypatch):
 def _on_cpu(monkeypatch):
     standin_ops.install(monkeypatch)
     monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+    import torch.distributed as dist
+    if dist.is_initialized():      # left by a GPU test earlier in this process (NCCL): the entry points would reuse it for host tensors
+        dist.destroy_process_group()
     return torch.device("cpu")
 
 
@@ -234,7 +237,7 @@ def _dp_setup(seed, mp=None):
     return engine, video.to(torch.bfloat16), ids, mask
 
 
-def _dp_worker(rank, world, port, q):
+def _dp_worker(rank, world, port, q, received):
     import torch.distributed as dist
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -252,6 +255,7 @@ def _dp_worker(rank, world, port, q):
     first = list(launched)
     engine.reducer.finish()
     q.put((rank, p0, engine.flat.grads.clone(), first, loss.item()))
+    received.wait(timeout=300)  # the parent takes the tensors over from this process: stay alive until it has them
     dist.barrier()
     dist.destroy_process_group()
 
@@ -263,12 +267,13 @@ def test_real_model_data_parallel_world2_gloo(monkeypatch):
     to the gradient of the whole batch in one process (run_pretrain_distributed_gpt3.py:263-274, DeepSpeed's averaged all-reduce)."""
     import torch.multiprocessing as mp
     ctx = mp.get_context("spawn")
-    q = ctx.Queue()
+    q, received = ctx.Queue(), ctx.Event()
     port = 26000 + os.getpid() % 3000
-    procs = [ctx.Process(target=_dp_worker, args=(r, 2, port, q)) for r in range(2)]
+    procs = [ctx.Process(target=_dp_worker, args=(r, 2, port, q, received)) for r in range(2)]
     for p in procs:
         p.start()
     res = {r[0]: r[1:] for r in (q.get(timeout=300) for _ in range(2))}
+    received.set()
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0
@@ -390,7 +395,7 @@ def test_finetune_host_pieces_on_cpu():
     t.test_caption_metrics_known_answers()
 
 
-def _entry_world2_worker(rank, world, port, d, which, q):
+def _entry_world2_worker(rank, world, port, d, which, q, received):
     """one rank of a two-process run of an entry point on the stand-ins (gloo); reports the final flat parameters and statistics"""
     import json
     import sys
@@ -428,6 +433,7 @@ def _entry_world2_worker(rank, world, port, d, which, q):
     stats = entry.main(args, config)
     e = seen["engine"]
     q.put((rank, e.flat.params.clone(), e.zero_shards, {k: v for k, v in stats.items() if isinstance(v, (int, float))}))
+    received.wait(timeout=300)  # the parent takes the tensors over from this process: stay alive until it has them
     import torch.distributed as dist
     dist.barrier()
     dist.destroy_process_group()
@@ -451,9 +457,9 @@ def test_entrypoints_world2_gloo_zero1(tmp_path, which):
     cfg.update(hidden_dropout=0.0, attention_dropout=0.0)              # the stand-ins do not model the hash dropout
     json.dump(cfg, open(os.path.join(d, "txt.json"), "w"))
     ctx = mp.get_context("spawn")
-    q = ctx.Queue()
+    q, received = ctx.Queue(), ctx.Event()
     port = 36000 + os.getpid() % 3000 + (7 if which == "itm" else 0)
-    procs = [ctx.Process(target=_entry_world2_worker, args=(r, 2, port, d, which, q)) for r in range(2)]
+    procs = [ctx.Process(target=_entry_world2_worker, args=(r, 2, port, d, which, q, received)) for r in range(2)]
     for p in procs:
         p.start()
     res = {}
@@ -466,6 +472,7 @@ def test_entrypoints_world2_gloo_zero1(tmp_path, which):
                 break
         if len(res) == 2:
             break
+    received.set()
     for p in procs:
         p.join(timeout=120 if len(res) == 2 else 5)
         if p.is_alive():                                                # its peer died: it would wait in a collective for ever
