@@ -390,6 +390,24 @@ int mpv_video_u8_normalize(const uint8_t* frames, int T, int H, int W, const flo
  * dsim (bf16, optional) = (softmax - targets) * scale; dts[i] (optional) = sum_j dsim[i][j] * sim[i][j]. */
 int mpv_soft_target_ce(const float* sim, const int64_t* row_ids, const int64_t* col_ids, float scale, float* losses,
                        void* dsim, float* dts, int64_t rows, int64_t cols, mpv_stream_t stream);
+/* Image-text contrastive head of the pre-train model (use_contrastive, models/distributed_gpt3.py:168-212): the similarity of a
+ * clip and a title is the MAX over the clip's Q query features.
+ * mpv_maxsim_fwd: A bf16 [R][Q][E], T bf16 [C][E] (both L2-normalised rows, E % 8 == 0, 16-byte aligned);
+ *   sim fp32 = alpha * max_q <A[r][q], T[c]> (the max is taken before the scale; alpha = *alpha_dev, or 1 when NULL) and
+ *   arg int32 = that q, ties to the lowest q (deterministic).  trans = 0: sim / arg are [R][C]; trans = 1: [C][R].
+ *   i2t: A = v [B][Q][E], T = t_all [WB][E]; t2i: A = v_all [WB][Q][E], T = t [B][E], trans = 1 (sim_t2i [B][WB]).
+ * mpv_maxsim_route: the max's backward as a dense operand: G bf16 [R*Q][C], G[r*Q + q][c] = dsim(r, c) * [arg(r, c) == q], with
+ *   dsim bf16 and arg in mpv_maxsim_fwd's layout (trans as there); C % 8 == 0.  Every element written once, no atomics.
+ *   dA = alpha G T and dT = alpha G^T A are then plain mpv_gemm_bf16 products.
+ * mpv_smoothed_ce: F.cross_entropy(sim, target, label_smoothing=eps) per row over fp32 sim[rows][cols], int64 target[rows]:
+ *   targets[i][j] = (1 - eps) [j == target[i]] + eps / cols; losses[i] = -sum_j log_softmax(sim_i)[j] targets[i][j];
+ *   dsim (bf16, optional) = (softmax - targets) * scale; dts[i] (optional) = sum_j dsim[i][j] * sim[i][j] (the temp gradient,
+ *   as in mpv_soft_target_ce). */
+int mpv_maxsim_fwd(const void* A, const void* T, const float* alpha_dev, float* sim, int* arg, int64_t R, int64_t Q, int64_t C,
+                   int64_t E, int trans, mpv_stream_t stream);
+int mpv_maxsim_route(const void* dsim, const int* arg, void* G, int64_t R, int64_t Q, int64_t C, int trans, mpv_stream_t stream);
+int mpv_smoothed_ce(const float* sim, const int64_t* target, float eps, float scale, float* losses, void* dsim, float* dts,
+                    int64_t rows, int64_t cols, mpv_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Optimizer (DeepSpeed FusedAdam + global-norm clip, run_pretrain_distributed_gpt3.py:137;

@@ -81,6 +81,11 @@ def train_one_epoch(model, tokenizer, data_loader, optimizer, device, epoch, num
     # step and keeps the eager step)
     use_graph = os.environ.get("MPV_GRAPH", "0") == "1" and update_freq == 1 and device.type == "cuda" and \
         (world == 1 or getattr(model, "zero_shards", None) is None)
+    contrastive = getattr(getattr(model, "module", model), "use_contrastive", False)
+    if use_graph and contrastive and world > 1:
+        log("MPV_GRAPH=1: use_contrastive on more than one rank runs the eager step (its feature all-gather sits inside the forward; "
+            "the segmented replay only cuts at gradient buckets)")
+        use_graph = False
     for data_iter_step, (video, text) in enumerate(data_loader):
         t0 = time.time()
         step = data_iter_step // update_freq
@@ -114,7 +119,11 @@ def train_one_epoch(model, tokenizer, data_loader, optimizer, device, epoch, num
             # MPV_GRAPH=1: forward + backward + optimizer step as ONE replayed HIP graph (engine.graph_step).  The loss is known
             # only after the step it belongs to has been applied; a non-finite one is handled as below (reload the last checkpoint
             # or stop), which discards that step either way.
-            loss_caption, loss_ita = model.graph_step(video, text), torch.zeros((), device=device)
+            total = model.graph_step(video, text)
+            if contrastive:      # forward_backward leaves both parts in the step's (replayed) buffers
+                loss_caption, loss_ita = model.module.loss_caption, model.module.loss_contrastive
+            else:
+                loss_caption, loss_ita = total, torch.zeros((), device=device)
         else:
             loss_caption, loss_ita = model(video, text)
         loss = loss_caption + loss_ita

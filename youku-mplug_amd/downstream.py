@@ -43,6 +43,7 @@ class _GenClsFn(torch.autograd.Function):
 
 class _GenCls(DistributedGPT3_Pretrain):
     ITM = False
+    CONTRASTIVE = "ignore"          # the reference's Cls / Retrieval_Cls never read use_contrastive: no head is built
 
     def __init__(self, config: Optional[dict] = None, tokenizer=None, *, visual_cfg: Optional[dict] = None,
                  text_cfg: Optional[GPT3Config] = None, device="cuda"):

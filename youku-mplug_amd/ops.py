@@ -557,3 +557,34 @@ def soft_target_ce(sim, row_ids, col_ids, scale, rows, cols, want_grad=True):
     check(_lib.lib().mpv_soft_target_ce(sim.data_ptr(), row_ids.data_ptr(), col_ids.data_ptr(), scale, losses.data_ptr(), _p(dsim),
                                         _p(dts), rows, cols, _stream()), "mpv_soft_target_ce")
     return losses, dsim, dts
+
+
+def maxsim_fwd(a, t, R, Q, C, E, *, alpha_dev=None, trans=False):
+    """-> (sim fp32, arg int32): alpha * max_q <a[r,q], t[c]> and its argmax (ties to the lowest q), [R,C] or [C,R] with trans.
+    a bf16 [R*Q, E], t bf16 [C, E]; alpha_dev fp32 device scalar (include/mpv.h: mpv_maxsim_fwd)."""
+    _need_cuda(a, t)
+    shape = (C, R) if trans else (R, C)
+    sim = torch.empty(shape, dtype=torch.float32, device=a.device)
+    arg = torch.empty(shape, dtype=torch.int32, device=a.device)
+    check(_lib.lib().mpv_maxsim_fwd(a.data_ptr(), t.data_ptr(), _p(alpha_dev), sim.data_ptr(), arg.data_ptr(), R, Q, C, E,
+                                    int(trans), _stream()), "mpv_maxsim_fwd")
+    return sim, arg
+
+
+def maxsim_route(dsim, arg, R, Q, C, *, trans=False):
+    """-> G bf16 [R*Q, C] = dsim(r, c) where arg(r, c) == q, else 0 (include/mpv.h: mpv_maxsim_route)"""
+    _need_cuda(dsim, arg)
+    g = torch.empty((R * Q, C), dtype=torch.bfloat16, device=dsim.device)
+    check(_lib.lib().mpv_maxsim_route(dsim.data_ptr(), arg.data_ptr(), g.data_ptr(), R, Q, C, int(trans), _stream()), "mpv_maxsim_route")
+    return g
+
+
+def smoothed_ce(sim, target, eps, scale, rows, cols, want_grad=True):
+    """-> (losses fp32 [rows], dsim bf16 [rows, cols], dts fp32 [rows]): cross-entropy with label smoothing eps (include/mpv.h)"""
+    _need_cuda(sim, target)
+    losses = torch.empty(rows, dtype=torch.float32, device=sim.device)
+    dsim = torch.empty((rows, cols), dtype=torch.bfloat16, device=sim.device) if want_grad else None
+    dts = torch.empty(rows, dtype=torch.float32, device=sim.device) if want_grad else None
+    check(_lib.lib().mpv_smoothed_ce(sim.data_ptr(), target.data_ptr(), eps, scale, losses.data_ptr(), _p(dsim), _p(dts), rows, cols,
+                                     _stream()), "mpv_smoothed_ce")
+    return losses, dsim, dts

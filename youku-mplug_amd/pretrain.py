@@ -22,22 +22,29 @@ from .vision import AttentionPool, Linear, TimeSformer, _param, convert_pretrain
 
 
 class _StepFn(torch.autograd.Function):
-    """Bridges the explicit forward/backward pipeline into autograd (one node per step)."""
+    """Bridges the explicit forward/backward pipeline into autograd (one node per step).  Outputs: loss_caption, and with the
+    contrastive head on a second one, loss_contrastive."""
 
     @staticmethod
     def forward(ctx, anchor, model, video, ids, mask, prompt_lengths=None):
         loss, tape = model._forward_pipeline(video, ids, mask, prompt_lengths=prompt_lengths)
         ctx.model, ctx.tape = model, tape
-        return loss
+        return (loss, tape["loss_ita"]) if "loss_ita" in tape else loss
 
     @staticmethod
-    def backward(ctx, grad_loss):
-        ctx.model._backward_pipeline(ctx.tape, grad_loss.contiguous().float())
+    def backward(ctx, grad_loss, grad_ita=None):
+        # (an output that took no part in the loss arrives as a zero tensor: autograd materialises missing gradients)
+        g_ita = None if grad_ita is None else grad_ita.contiguous().float()
+        ctx.model._backward_pipeline(ctx.tape, grad_loss.contiguous().float(), g_ita)
         ctx.tape = None
         return torch.zeros(1, device=grad_loss.device), None, None, None, None, None
 
 
 class DistributedGPT3_Pretrain(nn.Module):
+    # what a subclass does with config['use_contrastive']: "build" the ITC head, "refuse" it, or "ignore" the key as the
+    # reference's generation / classification models do (they never read it)
+    CONTRASTIVE = "build"
+
     def __init__(self, config: Optional[dict] = None, tokenizer=None, *, visual_cfg: Optional[dict] = None,
                  text_cfg: Optional[GPT3Config] = None, device="cuda"):
         super().__init__()
@@ -71,9 +78,15 @@ class DistributedGPT3_Pretrain(nn.Module):
         if visual_cfg.get("connect_ln", False):                                           # :112-115
             from .vision import LayerNormWithForceFP32
             self.visual_norm = LayerNormWithForceFP32(self.text_width, eps=1e-6, device=device)
-        self.use_contrastive = config.get("use_contrastive", False)
-        if self.use_contrastive:
-            raise NotImplementedError("use_contrastive is false in the pre-train recipe (…yaml:26); ITC lives in the retrieval model")
+        self.use_contrastive = bool(config.get("use_contrastive", False)) and self.CONTRASTIVE != "ignore"
+        if self.use_contrastive:                                                          # :122-127
+            self._check_contrastive_supported(config)
+            E = config.get("contrastive_embed_dim", 256)      # the reference reads this key; the YAML's `embed_dim` is not used
+            if E % 8:
+                raise ValueError(f"contrastive_embed_dim ({E}) must be a multiple of 8")
+            self.vision_proj = Linear(self.vision_width, E, device=device)
+            self.text_proj = Linear(self.text_width, E, device=device)
+            self.temp = nn.Parameter(torch.ones([], dtype=torch.bfloat16, device=device) * config.get("temp", 0.07))
         self.prompt = config.get("prompt", "")
         self._anchor = torch.zeros(1, device=device, requires_grad=True)
         self.on_stage_grads_ready = None      # engine hook(stage_name)
@@ -109,6 +122,74 @@ class DistributedGPT3_Pretrain(nn.Module):
     def no_weight_decay(self):
         return {"visual_encoder.pos_embed", "visual_encoder.cls_token", "visual_encoder.temporal_embed"}       # :224-226
 
+    def _check_contrastive_supported(self, config):
+        """use_contrastive is built for this class with the frozen decoder (every shipped recipe); refuse the rest loudly."""
+        if self.CONTRASTIVE != "build":
+            raise NotImplementedError(f"use_contrastive is implemented for DistributedGPT3_Pretrain only, not {type(self).__name__} "
+                                      "(the image model pools the caption pass's hidden states instead, models/distributed_gpt3.py:378-382)")
+        if not config.get("freeze_text_decoder", True):
+            raise NotImplementedError("use_contrastive with freeze_text_decoder: false would need a backward through the text-only "
+                                      "decoder pass; the gfx950 path implements the frozen-decoder recipe")
+
+    # ---------------------------------------------------------------- contrastive head (models/distributed_gpt3.py:168-212)
+    def _contrastive_forward(self, tape, ids, mask):
+        """query-max ITC: loss_ita (fp32 scalar, device) into the tape; no host synchronisation anywhere."""
+        from .retrieval import gather_cat
+        B, L = ids.shape
+        Q, D, Hh, E = self.num_learnable_token, self.vision_width, self.text_width, self.vision_proj.out_features
+        if B % 8:
+            raise ValueError(f"use_contrastive: the per-rank batch ({B}) must be a multiple of 8 (operand rule of the head's GEMMs)")
+        # text-only pass of the frozen decoder (:169-176): hidden states after the final LayerNorm; its LM head / CE are unused in
+        # the reference and skipped here.  pass_index 1: its dropout masks are not the caption pass's.
+        out = self.text_decoder.forward_lm(None, ids, None, None, {}, hidden_only=True, pass_index=1)
+        rows = torch.arange(B, device=ids.device) * L + (mask.sum(dim=-1) - 1)                                  # :181
+        pooled = ops.gather_rows(out["last_hidden_state"].reshape(B * L, Hh), rows.contiguous(), B, Hh)
+        iq = tape["image_query"]
+        vp = ops.gemm(iq, self.vision_proj.weight, B * Q, E, D, bias=self.vision_proj.bias)                    # :178
+        vf, vn = ops.l2norm_fwd(vp, B * Q, E)
+        tp = ops.gemm(pooled, self.text_proj.weight, B, E, Hh, bias=self.text_proj.bias)                       # :182
+        tf, tn = ops.l2norm_fwd(tp, B, E)
+        g = getattr(self, "process_group", None)
+        v_all, t_all = gather_cat(vf, g), gather_cat(tf, g)                                                    # :184-185
+        WB = t_all.shape[0]
+        rank = torch.distributed.get_rank(g) if WB > B else 0
+        inv_temp = (1.0 / self.temp.detach().float()).reshape(1)
+        sim_i2t, arg1 = ops.maxsim_fwd(vf, t_all, B, Q, WB, E, alpha_dev=inv_temp)                             # :187-195
+        sim_t2i, arg2 = ops.maxsim_fwd(v_all, tf, WB, Q, B, E, alpha_dev=inv_temp, trans=True)                 # :197-204
+        target = torch.arange(rank * B, rank * B + B, device=ids.device)                                       # :206-208
+        scale = 0.5 / B                                                                                        # (mean + mean) / 2
+        l1, ds1, dt1 = ops.smoothed_ce(sim_i2t, target, 0.1, scale, B, WB)                                     # :211-212
+        l2, ds2, dt2 = ops.smoothed_ce(sim_t2i, target, 0.1, scale, B, WB)
+        tape["loss_ita"] = (l1.sum() + l2.sum()) * scale
+        tape["itc"] = dict(B=B, WB=WB, E=E, pooled=pooled, vp=vp, vn=vn, vf=vf, tp=tp, tn=tn, tf=tf, v_all=v_all, t_all=t_all,
+                           arg1=arg1, arg2=arg2, ds1=ds1, ds2=ds2, dts=dt1.sum() + dt2.sum(), inv_temp=inv_temp)
+
+    def _contrastive_backward(self, tape, grad_ita):
+        """gradients of the head (projections, temp) and d image_query [B*Q, D]; the text tower below `pooled` is frozen."""
+        from .retrieval import reduce_scatter_sum
+        c = tape["itc"]
+        B, WB, E = c["B"], c["WB"], c["E"]
+        Q, D, Hh = self.num_learnable_token, self.vision_width, self.text_width
+        g = getattr(self, "process_group", None)
+        coef = (c["inv_temp"] * grad_ita.reshape(1)).contiguous()
+        G1 = ops.maxsim_route(c["ds1"], c["arg1"], B, Q, WB)                       # d sim_i2t / d <v[i,q], t_all[j]>   [B*Q, WB]
+        G2 = ops.maxsim_route(c["ds2"], c["arg2"], WB, Q, B, trans=True)           # d sim_t2i / d <t[i], v_all[j,q]>   [WB*Q, B]
+        dv = ops.gemm(G1, c["t_all"], B * Q, E, WB, trans_b=True, alpha_dev=coef)
+        dt_all = ops.gemm(G1, c["vf"], WB, E, B * Q, trans_a=True, trans_b=True, alpha_dev=coef)
+        dt = ops.gemm(G2, c["v_all"], B, E, WB * Q, trans_a=True, trans_b=True, alpha_dev=coef)
+        dv_all = ops.gemm(G2, c["tf"], WB * Q, E, B, trans_b=True, alpha_dev=coef)
+        dv = ops.add(dv, reduce_scatter_sum(dv_all, g))                            # all_gather backward
+        dt = ops.add(dt, reduce_scatter_sum(dt_all, g))
+        # d temp: sim = raw / temp  ->  dL/dtemp = -(1/temp) * sum(dsim * sim)
+        grad_of(self.temp).copy_((-(c["dts"]) * c["inv_temp"][0] * grad_ita.reshape(())).to(torch.bfloat16))
+        dtp = ops.l2norm_bwd(dt, c["tp"], c["tn"], B, E)
+        ops.colsum(dtp, B, E, out=grad_of(self.text_proj.bias))
+        ops.gemm(dtp, c["pooled"], E, Hh, B, trans_a=True, trans_b=True, out=grad_of(self.text_proj.weight))
+        dvp = ops.l2norm_bwd(dv, c["vp"], c["vn"], B * Q, E)
+        ops.colsum(dvp, B * Q, E, out=grad_of(self.vision_proj.bias))
+        ops.gemm(dvp, tape["image_query"], E, D, B * Q, trans_a=True, trans_b=True, out=grad_of(self.vision_proj.weight))
+        return ops.gemm(dvp, self.vision_proj.weight, B * Q, D, E, trans_b=True)
+
     # ---------------------------------------------------------------- pipeline
     def _forward_pipeline(self, video, ids, mask, want_logits=False, prompt_lengths=None):
         B = video.shape[0]
@@ -130,6 +211,8 @@ class DistributedGPT3_Pretrain(nn.Module):
             out = self.text_decoder.forward_lm(qf, ids, None, None, tape["gpt"], loss_window=(Q, ids.shape[1]),
                                                window_targets=ops.caption_targets(ids, mask, pl))
             tape["out"] = out
+            if self.use_contrastive:
+                self._contrastive_forward(tape, ids, mask)
             return out["loss"], tape
         # targets / loss mask exactly as :142-159 (filler id 100 is always masked)
         targets = torch.cat([ids[:, 1:], ids[:, 1:2]], dim=1)
@@ -146,9 +229,12 @@ class DistributedGPT3_Pretrain(nn.Module):
         tape["out"] = out
         return out["loss"], tape
 
-    def _backward_pipeline(self, tape, grad_loss):
+    def _backward_pipeline(self, tape, grad_loss, grad_ita=None):
         B = tape["vit"]["B"]
         Q, Hh, D = self.num_learnable_token, self.text_width, self.vision_width
+        diq_itc = None
+        if "itc" in tape:               # every head gradient is complete before the "head" bucket is reported below
+            diq_itc = self._contrastive_backward(tape, grad_ita if grad_ita is not None else torch.zeros((), device=grad_loss.device))
         dqf = self.text_decoder.backward_lm(tape["gpt"], grad_loss)
         iq = tape["image_query"]
         if "qf_raw" in tape:
@@ -158,6 +244,8 @@ class DistributedGPT3_Pretrain(nn.Module):
         ops.colsum(dqf, B * Q, Hh, out=grad_of(self.visual_fc.bias))
         ops.gemm(dqf, iq, Hh, D, B * Q, trans_a=True, trans_b=True, out=grad_of(self.visual_fc.weight))
         diq = ops.gemm(dqf, self.visual_fc.weight, B * Q, D, Hh, trans_b=True)
+        if diq_itc is not None:
+            diq = ops.add(diq, diq_itc)
         demb = self.attn_pool.backward_pool(diq, self.learnable_queries, tape["pool"])
         if self.on_stage_grads_ready is not None:
             self.on_stage_grads_ready("head")
@@ -167,20 +255,31 @@ class DistributedGPT3_Pretrain(nn.Module):
     def forward(self, image, text):
         ids, mask = text.input_ids, text.attention_mask
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            loss = _StepFn.apply(self._anchor, self, image, ids, mask)
+            out = _StepFn.apply(self._anchor, self, image, ids, mask)
+            loss, lita = out if isinstance(out, tuple) else (out, None)
         else:
-            loss, _ = self._forward_pipeline(image, ids, mask)
-        return loss, torch.zeros((), device=loss.device)                                   # :218-221
+            loss, tape = self._forward_pipeline(image, ids, mask)
+            lita = tape.get("loss_ita")
+        if not self.use_contrastive:
+            return loss, torch.zeros((), device=loss.device)                               # :218-219
+        return loss, lita                                                                  # :221
 
     @torch.no_grad()
     def forward_backward(self, image, text):
         """forward + backward of one micro-batch WITHOUT autograd: what `loss, _ = model(image, text); loss.backward()` does, as two
         direct calls of the explicit pipeline.  Gradients land in the same .grad views.  This is the form a HIP graph can capture
         (engine.graph_step): under autograd the anchor's AccumulateGrad node runs on the stream the anchor was created on, not
-        on the capturing stream."""
+        on the capturing stream.
+        With use_contrastive the step's loss is loss_caption + loss_contrastive; both parts stay readable afterwards (also after a
+        graph replay, which rewrites the same buffers) as `self.loss_caption` / `self.loss_contrastive`."""
         loss, tape = self._forward_pipeline(image, text.input_ids, text.attention_mask, prompt_lengths=getattr(text, "prompt_lengths", None))
-        self._backward_pipeline(tape, torch.ones((), dtype=torch.float32, device=loss.device))
-        return loss
+        one = torch.ones((), dtype=torch.float32, device=loss.device)
+        if "itc" not in tape:
+            self._backward_pipeline(tape, one)
+            return loss
+        self._backward_pipeline(tape, one, one)
+        self.loss_caption, self.loss_contrastive = loss, tape["loss_ita"]
+        return loss + tape["loss_ita"]
 
     @torch.no_grad()
     def forward_outputs(self, image, text):
@@ -192,7 +291,8 @@ class DistributedGPT3_Pretrain(nn.Module):
 class DistributedGPT3_Pretrain_Image(DistributedGPT3_Pretrain):
     """models/distributed_gpt3.py:229-427 with use_eva_g: the EVA-ViT-g image encoder in front of the same abstractor and
     frozen decoder; forward(image [B,3,H,W], text) -> (loss_caption, loss_contrastive); `text.prompt_lengths`, when
-    present, is masked out of the caption loss (:348-351)."""
+    present, is masked out of the caption loss (:348-351).  use_contrastive is refused (its head differs, :378-382)."""
+    CONTRASTIVE = "refuse"
 
     def _build_visual_encoder(self, config, visual_cfg, device):
         from .eva_vit import create_eva_vit_g
@@ -227,14 +327,16 @@ def synthetic_image_model(shapes, device="cuda", **eva) -> "DistributedGPT3_Pret
                                           visual_cfg=vis, text_cfg=txt, device=device)
 
 
-def synthetic_model(shapes, device="cuda", num_frames=None) -> DistributedGPT3_Pretrain:
+def synthetic_model(shapes, device="cuda", num_frames=None, use_contrastive=False, temp=0.07) -> DistributedGPT3_Pretrain:
     """Random-init model from a shapes object with the fields of oracle.weights.PathConfig (the
-    product never imports oracle/: tests pass the dataclass in)."""
+    product never imports oracle/: tests pass the dataclass in).  use_contrastive / temp: the ITC head of the recipe keys."""
     vis = dict(img_size=shapes.img_size, patch_size=shapes.patch_size, depth=shapes.vit_depth,
                num_frames=num_frames or shapes.num_frames, embed_dim=shapes.vit_dim, num_heads=shapes.vit_heads,
                mlp_ratio=shapes.vit_mlp_ratio, clip_model=True, connect_ln=bool(getattr(shapes, "connect_ln", False)))
     txt = GPT3Config(vocab_size=shapes.vocab, hidden_size=shapes.hidden, ffn_hidden_size=shapes.ffn,
                      num_hidden_layers=shapes.layers, num_attention_heads=shapes.heads, max_position_embeddings=shapes.max_pos,
                      layernorm_epsilon=shapes.gpt_ln_eps)
-    return DistributedGPT3_Pretrain({"num_learnable_token": shapes.num_queries, "_synthetic": True}, visual_cfg=vis,
-                                    text_cfg=txt, device=device)
+    config = {"num_learnable_token": shapes.num_queries, "_synthetic": True}
+    if use_contrastive:
+        config.update(use_contrastive=True, temp=temp)
+    return DistributedGPT3_Pretrain(config, visual_cfg=vis, text_cfg=txt, device=device)
