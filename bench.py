@@ -1,6 +1,6 @@
 """bench.py -- whole-job throughput of the mPLUG-Video pre-train step on N MI355X GPUs.
 
-    python bench.py --gpus 1 --steps 50 --warmup 5
+    python bench.py --gpus 1 --steps 50 --warmup 5 [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -8,9 +8,14 @@ Workload = BASELINE.json configs[1]: mPLUG-Video GPT3-1.3B pre-train step (freez
 TimeSformer/CLIP-B16 vision tower -- SURVEY.md R4), per-GPU batch 32 x 8 frames x 224^2 + 32-token
 titles, bf16, synthetic data, random-init weights.  A step = forward + backward + DP gradient
 all-reduce (overlapped) + global-norm clip + AdamW, dropout live (train mode).  One JSON line is
-printed by rank 0 (contract in the task statement) with `roofline` (bf16 MFMA GEMM family, timed
-live with HIP events on the launch stream) and `cpu_baseline` (the oracle restatement of the
-reference path timed on the host cores; reported, not the target).
+printed by rank 0 (contract in the task statement).
+
+A plain run does only what that line's headline needs: set-up, warm-up, the timed steps, --dump-outputs if
+given, the line.  `--full` adds everything else the benchmark measures, after the timed region: `roofline`
+(bf16 MFMA GEMM family, timed live with HIP events on the launch stream, with the clock / power of the
+timed region), the host's launch cost on an idle queue and of the other step mode, and `cpu_baseline` (the
+oracle restatement of the reference path timed on the host cores; reported, not the target).  Without
+`--full` those fields are null.
 """
 import argparse
 import json
@@ -434,8 +439,11 @@ def main():
     ap.add_argument("--batch", type=int, default=None)
     ap.add_argument("--frames", type=int, default=None)
     ap.add_argument("--text-len", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure what the headline does not need: roofline (+ clock / power of the timed "
+                         "region), the host's launch cost on an idle queue and of the other step mode, and (N = 1) the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: leave the roofline steps out")
     ap.add_argument("--step-mode", choices=["auto", "eager", "graph"], default=None,
                     help="auto (default): on N > 1 ranks a start-up self-check compares the replayed step (a chain of HIP-graph segments, "
                          "all-reduces between them) with the eager step bit for bit on every rank; if it passes, four fenced steps of each mode "
@@ -455,6 +463,9 @@ def main():
     _ON_CPU = bool(args.test_cpu)
     if "MPV_BENCH_DEVICE" in os.environ:
         sys.exit("bench.py: MPV_BENCH_DEVICE is no longer read (round 6): the stand-in run of the CPU suite is the --_test-cpu flag; unset the variable")
+    want_roof = args.full and not args.no_roofline
+    if os.environ.get("MPV_BENCH_BY_SHAPE") and not want_roof:
+        ap.error("MPV_BENCH_BY_SHAPE is written from the roofline steps: run with --full (and without --no-roofline)")
 
     t_start = time.perf_counter()
     import torch.distributed as dist
@@ -615,7 +626,7 @@ def main():
     # per-step HIP events on the launch stream (torch's current stream is the stream every kernel of the step is launched
     # on) give the distribution; the reported value is the whole timed region between two fences (the contract)
     marks = [_event() for _ in range(args.steps + 1)]
-    sampler = ClockPowerSampler(local) if (rank == 0 and not _ON_CPU) else None
+    sampler = ClockPowerSampler(local) if (want_roof and rank == 0 and not _ON_CPU) else None      # (its figures go into `roofline`)
     fence()
     if sampler is not None:
         sampler.__enter__()                     # a host thread reading gpu_metrics at 10 Hz: nothing is enqueued on the device
@@ -636,22 +647,23 @@ def main():
         dump_outputs(args.dump_outputs, loss, engine)
     log(f"host enqueue time {t_enq / args.steps * 1e3:.1f} ms/step wall, {t_cpu / args.steps * 1e3:.1f} ms/step CPU (launch-bound if the CPU figure approaches the step time)" +
         (" [graph replay]" if use_graph else ""))
-    # the same on an IDLE queue (nothing to wait for): what the host really spends to launch one step
-    t_idle = []
-    for i in range(3):
-        _sync()
-        t1, c1 = time.perf_counter(), time.thread_time()
-        step(total - 1)
-        t_idle.append((time.perf_counter() - t1, time.thread_time() - c1))
-    _sync()
-    log(f"host time to launch one step on an idle queue: {min(t[0] for t in t_idle) * 1e3:.1f} ms wall, {min(t[1] for t in t_idle) * 1e3:.1f} ms CPU")
     host = {"mode": step_mode, "cpu_ms_per_step": round(t_cpu / args.steps * 1e3, 2), "enqueue_wall_ms_per_step": round(t_enq / args.steps * 1e3, 2),
-            "idle_queue_launch_ms": round(min(t[0] for t in t_idle) * 1e3, 2), "graph_self_check": self_check,
-            "mode_probe_ms_per_step": mode_probe}
-    # the OTHER mode's host cost, for the record (every rank: the steps carry the collectives): the CPU time this thread spends enqueueing
-    # eight steps back to back (a filling queue, as in the timed region)
+            "idle_queue_launch_ms": None, "graph_self_check": self_check, "mode_probe_ms_per_step": mode_probe}
+    if args.full:
+        # the same on an IDLE queue (nothing to wait for): what the host really spends to launch one step
+        t_idle = []
+        for i in range(3):
+            _sync()
+            t1, c1 = time.perf_counter(), time.thread_time()
+            step(total - 1)
+            t_idle.append((time.perf_counter() - t1, time.thread_time() - c1))
+        _sync()
+        log(f"host time to launch one step on an idle queue: {min(t[0] for t in t_idle) * 1e3:.1f} ms wall, {min(t[1] for t in t_idle) * 1e3:.1f} ms CPU")
+        host["idle_queue_launch_ms"] = round(min(t[0] for t in t_idle) * 1e3, 2)
+    # (--full) the OTHER mode's host cost, for the record (every rank: the steps carry the collectives): the CPU time this thread spends
+    # enqueueing eight steps back to back (a filling queue, as in the timed region)
     other = None
-    if self_check is not None and self_check["passed"]:
+    if args.full and self_check is not None and self_check["passed"]:
         other_eager = use_graph
         nother = max(2, min(8, args.steps))
         c1 = time.thread_time()
@@ -661,7 +673,7 @@ def main():
         _sync()
         engine._graph_inflight.clear()
     host["cpu_ms_per_step_eager"] = host["cpu_ms_per_step"] if not use_graph else other
-    host["cpu_ms_per_step_graph"] = host["cpu_ms_per_step"] if use_graph else other      # None: the replay never ran (N = 1 default, failed self-check, --step-mode eager)
+    host["cpu_ms_per_step_graph"] = host["cpu_ms_per_step"] if use_graph else other      # None: the replay never ran (N = 1 default, failed self-check, --step-mode eager) or no --full
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     if dist_on:
         dist.all_reduce(dt, op=dist.ReduceOp.MAX)
@@ -673,7 +685,7 @@ def main():
     assert math.isfinite(final_loss), "non-finite loss in the timed region"
 
     roof = None
-    if not args.no_roofline:
+    if want_roof:
         # EVERY rank runs these extra steps (each holds the step's gradient all-reduces: a rank that stepped alone would leave its
         # peers' next collective unmatched); only rank 0's launch timings go into the line
         nroof = min(args.steps, 3)
@@ -692,7 +704,7 @@ def main():
             gt.by_shape(os.environ["MPV_BENCH_BY_SHAPE"], nroof)
         if lane is not None:
             lane.on = lane_on
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and want_roof:
         fl = sum(v[0] for v in tot.values())
         tt = sum(v[1] for v in tot.values())
         n = sum(v[2] for v in tot.values())
@@ -724,7 +736,7 @@ def main():
         from youku_mplug_amd import ops as _ops
         print(f"[bench] mpv_gemm_bf16 calls in this process: {_ops.gemm_calls}", file=sys.stderr)
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             ncores = host_cores()
             log(f"cpu baseline on {ncores} cores ...")
             cpu = cpu_baseline(ncores)

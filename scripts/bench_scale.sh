@@ -13,7 +13,7 @@ for N in 1 2 4 8; do
   [ "$N" -le "$NG" ] || { echo "only $NG GPUs: skipping N=$N"; continue; }
   PORT=$((29600 + N))
   if [ "$N" -eq 1 ]; then LAUNCH="python"; else LAUNCH="python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $PORT"; fi
-  $LAUNCH "$R/bench.py" --gpus $N --steps $STEPS --warmup $WARM --no-cpu-baseline > "$OUT/bench_n$N.json" 2> "$OUT/bench_n$N.err"
+  $LAUNCH "$R/bench.py" --gpus $N --steps $STEPS --warmup $WARM --full --no-cpu-baseline > "$OUT/bench_n$N.json" 2> "$OUT/bench_n$N.err"
   tail -1 "$OUT/bench_n$N.json" | cut -c1-300
   if [ "$N" -ge 2 ]; then
     # the launcher runs under the profiler: one database per rank, the first one found is analysed

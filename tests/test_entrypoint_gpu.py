@@ -437,7 +437,7 @@ def test_bench_contract_line_forced_distributed_path():
     env = dict(os.environ, MPV_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(25000 + os.getpid() % 2000))
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=600, env=env, stdin=subprocess.DEVNULL)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -463,6 +463,30 @@ def test_bench_contract_line_forced_distributed_path():
     assert 30.0 < rec["ms_per_step"] < 400.0
 
 
+def test_bench_plain_run_is_lean():
+    """bench.py without --full, exactly as the driver runs it: the contract's line with the --full measurements null, and at most
+    30 s of the whole process's wall time spent outside its warm-up and timed steps."""
+    import subprocess
+    import time
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MPV_BENCH_FORCE_DIST", "MPV_BENCH_BY_SHAPE", "MPV_GRAPH"):
+        env.pop(k, None)
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1"],
+                       capture_output=True, text=True, timeout=600, env=env, stdin=subprocess.DEVNULL)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    rec = json.loads(lines[0])
+    assert rec["metric"] == "video-text samples/sec/node, mPLUG-Video 1.3B pretrain step" and rec["unit"] == "samples/s"
+    assert rec["higher_is_better"] is True and rec["dtype"] == "bf16" and rec["data"] == "synthetic" and rec["step_mode"] == "eager"
+    assert rec["value"] == pytest.approx(32 * 3 / (rec["ms_per_step"] * 3e-3), rel=1e-3) and 30.0 < rec["ms_per_step"] < 400.0
+    assert rec["roofline"] is None and rec["cpu_baseline"] is None and rec["host"]["idle_queue_launch_ms"] is None
+    outside = wall - (3 + 1) * rec["ms_per_step"] * 1e-3
+    assert outside < 30.0, f"{outside:.1f} s outside the steps"
+
+
 def test_bench_two_ranks_on_one_gpu():
     """bench.py launched as the driver launches it for N = 2 (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment, `--gpus 2`), both
     ranks on this box's one GPU over gloo on device tensors (`--_test-one-gpu`: RCCL refuses two ranks per device; the line is stamped TEST):
@@ -479,7 +503,7 @@ def test_bench_two_ranks_on_one_gpu():
     worker.write("import sys\nsys.path.insert(0, %r)\nimport bench\nS = bench.Shapes\n"
                  "S.img_size, S.patch_size, S.vit_dim, S.vit_depth, S.vit_heads, S.num_queries = 64, 16, 192, 2, 2, 32\n"
                  "S.hidden, S.layers, S.heads, S.ffn, S.vocab, S.max_pos = 256, 2, 4, 1024, 1024, 256\n"
-                 "sys.argv = ['bench.py', '--gpus', '2', '--steps', '3', '--warmup', '1', '--batch', '4', '--frames', '4', '--text-len', '8', '--no-cpu-baseline', '--_test-one-gpu']\n"
+                 "sys.argv = ['bench.py', '--gpus', '2', '--steps', '3', '--warmup', '1', '--batch', '4', '--frames', '4', '--text-len', '8', '--full', '--no-cpu-baseline', '--_test-one-gpu']\n"
                  "bench.main()\n" % ROOT)
     worker.close()
     for r in range(2):

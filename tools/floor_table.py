@@ -4,7 +4,7 @@ main loop reaches on random data at the clock the power cap allows, DESIGN secti
 
     python tools/floor_table.py profiles/r05_final2_gemm_in_step_by_shape.md profiles/r05_final2_kernel_trace.md 7 > profiles/r06_floor_table.md
 
-Inputs: the in-step GEMM table (bench.py, MPV_BENCH_BY_SHAPE) and the kernel trace summary (tools/rocpd_stats.py) of the same tree; the
+Inputs: the in-step GEMM table (bench.py --full, MPV_BENCH_BY_SHAPE) and the kernel trace summary (tools/rocpd_stats.py) of the same tree; the
 third argument is the number of steps the trace covers.  Algorithmic bytes of the non-GEMM families are written out below for config B
 (R = 32 x 8 x 197 = 50432 ViT rows of 768, 5120 decoder rows of 2048, 130.0 M trainable parameters)."""
 import re
