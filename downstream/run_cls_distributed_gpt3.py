@@ -40,8 +40,10 @@ def topk_accuracy(output, target, topk=(1,)):
 
 
 @torch.no_grad()
-def evaluation(model, data_loader, tokenizer, device, config, max_length):
-    """-> {gen_top1_accuracy, gen_top5_accuracy[, cls_top1_accuracy, cls_top5_accuracy]} (:205-247)"""
+def evaluation(model, data_loader, tokenizer, device, config, max_length, shared_prefix=False):
+    """-> {gen_top1_accuracy, gen_top5_accuracy[, cls_top1_accuracy, cls_top5_accuracy]} (:205-247).  shared_prefix
+    (--eval_shared_prefix): each video batch is encoded once and scored through score_shared_prefix -- the same scores, with the
+    prompt rows all class names of a video share run once."""
     module = getattr(model, "module", model)
     module.eval()
     class_names = [data_loader.dataset.idx2label[i] for i in range(config["num_classes"])]
@@ -52,7 +54,11 @@ def evaluation(model, data_loader, tokenizer, device, config, max_length):
         input_text = [[PROMPT.format(t[:max_length - 15]), c] for t in text for c in class_names]
         text_input = tokenizer(input_text, padding="max_length", truncation=True, max_length=max_length, return_tensors="pt").to(device)
         prompt_text_input = tokenizer(list(text), padding="max_length", truncation=True, max_length=max_length, return_tensors="pt").to(device)
-        generation_logits, cls_logits = module(video, text_input, prompt_text_input, train=False)
+        if shared_prefix:
+            generation_logits, cls_logits = module.score_shared_prefix(text_input, prompt_text_input,
+                                                                       query_features=module.encode_video(video))
+        else:
+            generation_logits, cls_logits = module(video, text_input, prompt_text_input, train=False)
         n = video.shape[0]
         acc = dict(zip(("gen_top1_accuracy", "gen_top5_accuracy"), topk_accuracy(generation_logits.float().cpu(), labels, (1, 5))))
         if cls_logits is not None:
@@ -107,9 +113,9 @@ def main(args, config):
         return {"loss_generation": loss_generation, "loss_cls": loss_cls}
 
     def evaluate_both():
-        val = evaluation(s.model, val_loader, s.tokenizer, s.device, config, args.max_length)
+        val = evaluation(s.model, val_loader, s.tokenizer, s.device, config, args.max_length, args.eval_shared_prefix)
         print("Validation Performance:", val)
-        test = evaluation(s.model, test_loader, s.tokenizer, s.device, config, args.max_length)
+        test = evaluation(s.model, test_loader, s.tokenizer, s.device, config, args.max_length, args.eval_shared_prefix)
         print("Test Performance:", test)
         return {**{f"val_{k}": v for k, v in val.items()}, **{f"test_{k}": v for k, v in test.items()}}
 
@@ -121,7 +127,9 @@ def main(args, config):
 
 
 def get_args(argv=None):
-    return ft.get_args(argv)
+    return ft.get_args(argv, extra=lambda p: p.add_argument(
+        "--eval_shared_prefix", action="store_true", default=False,
+        help="evaluation: encode each video batch once and score through score_shared_prefix"))
 
 
 if __name__ == "__main__":

@@ -66,8 +66,10 @@ def make_training_batch(video, text, idx, tokenizer, device, max_length):
 
 
 @torch.no_grad()
-def evaluation(model, data_loader, tokenizer, device, config, max_length):
-    """-> (gen_v2t, gen_t2v, cls_v2t, cls_t2v) numpy score matrices (:228-286)."""
+def evaluation(model, data_loader, tokenizer, device, config, max_length, text_bs=TEXT_BS, shared_prefix=False):
+    """-> (gen_v2t, gen_t2v, cls_v2t, cls_t2v) numpy score matrices (:228-286).  Titles are scored text_bs at a time (the reference's
+    chunk is 8).  shared_prefix (--eval_shared_prefix): each video batch is encoded once and every chunk is scored through
+    score_shared_prefix -- the same scores, with the rows all titles of a video share run once."""
     module = getattr(model, "module", model)
     module.eval()
     texts = data_loader.dataset.text
@@ -79,14 +81,18 @@ def evaluation(model, data_loader, tokenizer, device, config, max_length):
     for b, (video, _vid) in enumerate(data_loader):
         if b % world == rank:
             video = video.to(device).bfloat16()
+            qf = module.encode_video(video) if shared_prefix else None
             gens, clss = [], []
-            for i in range(0, num_text, TEXT_BS):
-                chunk = texts[i:i + TEXT_BS]
+            for i in range(0, num_text, text_bs):
+                chunk = texts[i:i + text_bs]
                 input_text = [[QUESTION.format(t[:max_length - 20]), ANSWER[1]] for _ in range(len(video)) for t in chunk]
                 prompt_text = list(chunk) * len(video)
                 text_input = tokenizer(input_text, padding="max_length", truncation=True, max_length=max_length, return_tensors="pt").to(device)
                 prompt_text_input = tokenizer(prompt_text, padding="max_length", truncation=True, max_length=max_length, return_tensors="pt").to(device)
-                g, c = module(video, text_input, prompt_text_input, train=False)
+                if shared_prefix:
+                    g, c = module.score_shared_prefix(text_input, prompt_text_input, query_features=qf)
+                else:
+                    g, c = module(video, text_input, prompt_text_input, train=False)
                 gens.append(g.float())
                 clss.append(c.float())
             gen[start:start + len(video)] = torch.cat(gens, dim=1)
@@ -137,7 +143,8 @@ def main(args, config):
         return {"loss_generation": loss_generation, "loss_cls": loss_cls}
 
     def evaluate(loader, name):
-        gen_v2t, gen_t2v, cls_v2t, cls_t2v = evaluation(s.model, loader, s.tokenizer, s.device, config, args.max_length)
+        gen_v2t, gen_t2v, cls_v2t, cls_t2v = evaluation(s.model, loader, s.tokenizer, s.device, config, args.max_length,
+                                                        text_bs=args.eval_text_bs, shared_prefix=args.eval_shared_prefix)
         ds = loader.dataset
         stats = {f"gen_{k}": v for k, v in itm_eval(gen_v2t, gen_t2v, ds.txt2vid, ds.vid2txt).items()}
         stats.update({f"cls_{k}": v for k, v in itm_eval(cls_v2t, cls_t2v, ds.txt2vid, ds.vid2txt).items()})
@@ -155,9 +162,15 @@ def main(args, config):
     return ft.epoch_loop(args, s, step_fn, after_epoch)
 
 
+def _extra_args(p):
+    p.add_argument("--eval_freq", default=11, type=int, help="evaluate every N epochs (:510)")
+    p.add_argument("--eval_text_bs", default=TEXT_BS, type=int, help="titles per scoring call of the evaluation (:241)")
+    p.add_argument("--eval_shared_prefix", action="store_true", default=False,
+                   help="evaluation: encode each video batch once and score through score_shared_prefix")
+
+
 def get_args(argv=None):
-    return ft.get_args(argv, extra=lambda p: p.add_argument("--eval_freq", default=11, type=int, help="evaluate every N epochs (:510)"),
-                       config_defaults={"num_classes": 2})
+    return ft.get_args(argv, extra=_extra_args, config_defaults={"num_classes": 2})
 
 
 if __name__ == "__main__":

@@ -202,6 +202,26 @@ int mpv_attn_fwd(const mpv_attn_desc* d, mpv_stream_t stream);
 int mpv_attn_bwd(const mpv_attn_desc* d, const void* dO, void* dq, void* dk, void* dv, float* delta,
                  mpv_stream_t stream);
 
+/* Causal attention of continuations against a shared, already computed prefix (evaluation of the ITM / category scoring
+ * heads: every candidate of one video shares the query features and the common token prefix, models/distributed_gpt3.py:
+ * 1160-1218, 598-657).  n_cont continuations of cont_len rows; continuation c belongs to prefix group c / group_size
+ * (n_groups = ceil(n_cont / group_size)).  Query row i of continuation c sits at absolute position prefix_len + i and attends
+ * to the prefix_len keys of its group's prefix and to its own keys j <= i: softmax(scale * q.k) with fp32 scores and softmax,
+ * no dropout.  Element (c,h,i,d) of q/k/v/o lives at X + c*x_cs + h*x_hs + i*x_rs + d; element (g,h,j,d) of pk/pv at
+ * X + g*x_gs + h*x_hs + j*x_rs + d (the prefix pass's qkv rows at column offsets head_dim / 2*head_dim).  head_dim 64 or
+ * 80 (anything else: MPV_E_SHAPE).  o is bf16. */
+typedef struct mpv_attn_prefix_desc {
+  const void *q, *k, *v;     /* continuations */
+  const void *pk, *pv;       /* prefixes (may be NULL when prefix_len == 0) */
+  void* o;
+  int64_t q_cs, q_hs, q_rs, k_cs, k_hs, k_rs, v_cs, v_hs, v_rs;
+  int64_t pk_gs, pk_hs, pk_rs, pv_gs, pv_hs, pv_rs;
+  int64_t o_cs, o_hs, o_rs;
+  int n_cont, group_size, n_groups, heads, cont_len, prefix_len, head_dim;
+  float scale;
+} mpv_attn_prefix_desc;
+int mpv_attn_prefix_fwd(const mpv_attn_prefix_desc* d, mpv_stream_t stream);
+
 /* Divided space-time "temporal" attention: T<=16 tokens per (b,n) sequence, many tiny
  * problems (models/vision_transformer.py:247-248 with Attention :169-207).  qkv is the packed
  * [rows][3*D] projection in stream layout; sequence (o,i) (o<n_outer, i<n_inner) has its token

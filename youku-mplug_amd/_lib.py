@@ -42,6 +42,20 @@ class AttnDesc(C.Structure):
     ]
 
 
+class AttnPrefixDesc(C.Structure):
+    _fields_ = [
+        ("q", c_void_p), ("k", c_void_p), ("v", c_void_p), ("pk", c_void_p), ("pv", c_void_p), ("o", c_void_p),
+        ("q_cs", c_int64), ("q_hs", c_int64), ("q_rs", c_int64),
+        ("k_cs", c_int64), ("k_hs", c_int64), ("k_rs", c_int64),
+        ("v_cs", c_int64), ("v_hs", c_int64), ("v_rs", c_int64),
+        ("pk_gs", c_int64), ("pk_hs", c_int64), ("pk_rs", c_int64),
+        ("pv_gs", c_int64), ("pv_hs", c_int64), ("pv_rs", c_int64),
+        ("o_cs", c_int64), ("o_hs", c_int64), ("o_rs", c_int64),
+        ("n_cont", c_int), ("group_size", c_int), ("n_groups", c_int), ("heads", c_int), ("cont_len", c_int),
+        ("prefix_len", c_int), ("head_dim", c_int), ("scale", c_float),
+    ]
+
+
 _RM = [c_int, c_int, c_int]
 _SIGS = {
     "mpv_version": (c_int, []),
@@ -63,6 +77,7 @@ _SIGS = {
     "mpv_ln_stream_bwd": (c_int, [c_void_p] * 8 + [c_float, c_uint64, c_uint64] + [c_int64] * 4 + _RM + _RM + [c_void_p]),
     "mpv_attn_fwd": (c_int, [C.POINTER(AttnDesc), c_void_p]),
     "mpv_attn_bwd": (c_int, [C.POINTER(AttnDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mpv_attn_prefix_fwd": (c_int, [C.POINTER(AttnPrefixDesc), c_void_p]),
     "mpv_temporal_attn_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int64, c_int64, c_int, c_int, c_int,
                                       c_float, c_void_p]),
     "mpv_temporal_attn_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int64, c_int64, c_int,

@@ -27,6 +27,26 @@ from .vision import Linear, grad_of
 _PAD = 8   # GEMM / cross-entropy column granule: the class dimension is padded to it
 
 
+def shared_prefix_split(ids: torch.Tensor, first_out: torch.Tensor, last_out: torch.Tensor, group_size: int, Q: int):
+    """The split rule of shared-prefix scoring.  ids [n, L] (n = groups * group_size; the rows of one group share a video);
+    first_out / last_out [n]: token position j of the first / last output of each row (the hidden row at Q + j is read: a scored
+    position or a pooled row), first_out = L and last_out = -1 for a row without outputs.  -> (P, Lc):
+      P = Q + t with t the longest common token prefix of every group's rows, capped so that no output lies inside the prefix
+      (t <= first_out of every row) and at least one token is left to the continuations (t <= L - 1); one P for the call, the
+      minimum over groups;
+      Lc = rows from P to the last output of the chunk (trailing rows only ever follow every output of a causal decoder), >= 1."""
+    n, L = ids.shape
+    assert n % group_size == 0 and L >= 1
+    g = ids.view(n // group_size, group_size, L)
+    same = (g == g[:, :1]).all(dim=1).to(torch.int32)                        # [groups, L]: column shared by every row of the group
+    common = same.cumprod(dim=1).sum(dim=1)                                  # longest common prefix per group
+    cap = first_out.view(n // group_size, group_size).min(dim=1).values
+    t, last = torch.stack([torch.minimum(common, cap).min().clamp(max=L - 1), last_out.max().to(common.dtype)]).tolist()   # one host sync
+    P = Q + t
+    Lc = max(last + Q + 1 - P, 1)
+    return P, Lc
+
+
 class _GenClsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, model, args):
@@ -96,11 +116,18 @@ class _GenCls(DistributedGPT3_Pretrain):
     def _cls_logits(self, qf_rows, p_ids, p_mask, tape):
         """prompt pass -> pooled last valid hidden state -> cls_head logits (class dim padded to 8 with -1e30 bias)."""
         n, Lp = p_ids.shape
-        Q, H, C = self.num_learnable_token, self.text_width, self.num_classes
+        Q, H = self.num_learnable_token, self.text_width
         S = Q + Lp
         out = self.text_decoder.forward_lm(qf_rows, p_ids, None, None, tape["gpt2"], hidden_only=True, pass_index=1)
         rows = (torch.arange(n, device=p_ids.device) * S + Q + p_mask.sum(dim=-1) - 1).contiguous()      # :1149-1150
         pooled = ops.gather_rows(out["last_hidden_state"].reshape(n * S, H), rows, n, H)
+        logits, (z, a, w2, Cp) = self._cls_head_logits(pooled)
+        tape.update(rows=rows, pooled=pooled, z=z, a=a, w2=w2, Cp=Cp, n2=n, S2=S)
+        return logits
+
+    def _cls_head_logits(self, pooled):
+        """cls_head = Linear-ReLU-Linear on pooled [n, H] -> (logits [n, Cp], (z, a, w2, Cp) for the backward)."""
+        n, H, C = pooled.shape[0], self.text_width, self.num_classes
         l0, l2 = self.cls_head[0], self.cls_head[2]
         z = torch.empty((n, H), dtype=torch.bfloat16, device=pooled.device)
         a = ops.gemm(pooled, l0.weight, n, H, H, bias=l0.bias, act=ACT_RELU, preact_out=z)
@@ -110,8 +137,7 @@ class _GenCls(DistributedGPT3_Pretrain):
         w2[:C].copy_(l2.weight.detach())
         b2[:C].copy_(l2.bias.detach())
         logits = ops.gemm(a, w2, n, Cp, H, bias=b2)
-        tape.update(rows=rows, pooled=pooled, z=z, a=a, w2=w2, Cp=Cp, n2=n, S2=S)
-        return logits
+        return logits, (z, a, w2, Cp)
 
     # ------------------------------------------------------------------ pipelines
     def _forward_pipeline(self, video, ids, mask, prompt_lengths, p_ids, p_mask, negative_indices, labels):
@@ -195,6 +221,77 @@ class _GenCls(DistributedGPT3_Pretrain):
             logits = self._cls_logits(qf if per_video else qf_rep, prompt_text.input_ids, prompt_text.attention_mask, tape)
             logits = logits[:, :self.num_classes].float()
             cls = torch.softmax(logits, dim=-1)[:, 1].view(Bv, t) if self.ITM else logits
+        return (gen if self.ITM else torch.softmax(gen, dim=-1)), cls
+
+    # ------------------------------------------------------------------ shared-prefix scoring (evaluation)
+    @torch.no_grad()
+    def encode_video(self, video):
+        """query features [B * Q, H] of a video batch: run once, then score any number of text chunks against them
+        (score_shared_prefix(..., query_features=...))."""
+        return self._query_features(video, {"vit": {}, "pool": {}})
+
+    def _shared_prefix_pass(self, qf, ids, group_size, first_out, last_out, out_rows, loss_mask=None, targets=None):
+        """Prefix pass over the groups' shared rows + continuation pass over each row's own rows.  out_rows [n]: hidden row
+        (absolute position) to pool, or None; loss_mask / targets [n, S-1] / [n, S]: the scored positions.  -> (losses per row
+        [n] summed over its scored positions, pooled hidden [n, H])."""
+        Q = self.num_learnable_token
+        n, L = ids.shape
+        dec = self.text_decoder
+        P, Lc = shared_prefix_split(ids, first_out, last_out, group_size, Q)
+        t = P - Q
+        assert n % group_size == 0 and qf.shape[0] == (n // group_size) * Q, \
+            f"{n} rows in groups of {group_size} need the query features of {n // group_size} videos, got {qf.shape[0] // Q}"
+        prefix = dec.forward_prefix(qf, ids[::group_size, :t].contiguous())
+        assert prefix["P"] == P and prefix["B"] == n // group_size
+        cont = ids[:, t:t + Lc].contiguous()
+        kw, sel = {}, None
+        if loss_mask is not None:
+            lm = torch.zeros((n, P + Lc), dtype=loss_mask.dtype, device=ids.device)
+            w = min(loss_mask.shape[1], P + Lc)
+            lm[:, :w] = loss_mask[:, :w]
+            sel = lm[:, P:].nonzero()                                                       # (row, i) of every scored position
+            kw.update(loss_rows=(sel[:, 0] * Lc + sel[:, 1]).contiguous(), labels=targets[sel[:, 0], P + sel[:, 1]].contiguous())
+        if out_rows is not None:
+            kw.update(hidden_rows=(torch.arange(n, device=ids.device) * Lc + out_rows - P).contiguous())
+        out = dec.forward_continuation(prefix, cont, group_size, **kw)
+        losses = None
+        if sel is not None:
+            losses = torch.zeros(n, dtype=torch.float32, device=ids.device).index_add_(0, sel[:, 0], out["losses"])
+        return losses, out.get("hidden")
+
+    @torch.no_grad()
+    def score_shared_prefix(self, text, prompt_text, *, video=None, query_features=None):
+        """What forward(..., train=False) returns (the same shapes and post-processing), computed with every video's shared rows
+        -- its query features and the tokens all its candidates share -- run once (gpt3.DistributedGPT3.forward_prefix) and
+        each candidate's own rows against them (forward_continuation, ops.attn_prefix_fwd).  Exact up to bf16 summation order."""
+        assert (video is None) != (query_features is None), "pass exactly one of video / query_features"
+        qf = self.encode_video(video) if query_features is None else query_features
+        Q = self.num_learnable_token
+        Bv = qf.shape[0] // Q
+        ids, mask = text.input_ids, text.attention_mask
+        n, L = ids.shape
+        if qf.shape[0] != Bv * Q or Bv == 0 or n % Bv != 0:
+            raise ValueError(f"query features of {qf.shape[0] / Q:g} videos ({qf.shape[0]} rows of Q = {Q}) do not divide the {n} "
+                             f"text rows into equal groups: pass the features of the video batch the texts were built for")
+        t = n // Bv
+        targets, loss_mask = self._gen_targets(ids, mask, text.prompt_lengths, Q)
+        scored = loss_mask[:, Q:] != 0                                                       # [n, L-1]: hidden row Q + j scored
+        j = torch.arange(scored.shape[1], device=ids.device)
+        first = torch.where(scored, j, L).min(dim=1).values if scored.shape[1] else torch.full((n,), L, device=ids.device)
+        last = torch.where(scored, j, -1).max(dim=1).values if scored.shape[1] else torch.full((n,), -1, device=ids.device)
+        losses, _ = self._shared_prefix_pass(qf, ids, t, first, last, None, loss_mask=loss_mask, targets=targets)
+        gen = (-losses).view(Bv, t)
+        cls = None
+        if self.use_cls:
+            if self.ITM:
+                p_ids, p_mask = prompt_text.input_ids, prompt_text.attention_mask
+                pj = p_mask.sum(dim=-1) - 1                                                  # pooled token (:1149-1150)
+                _, pooled = self._shared_prefix_pass(qf, p_ids, t, pj, pj, Q + pj)
+                logits, _ = self._cls_head_logits(pooled)
+                cls = torch.softmax(logits[:, :self.num_classes].float(), dim=-1)[:, 1].view(Bv, t)
+            else:                                                                            # one prompt per video (:622-647)
+                tape = {"gpt2": {}}
+                cls = self._cls_logits(qf, prompt_text.input_ids, prompt_text.attention_mask, tape)[:, :self.num_classes].float()
         return (gen if self.ITM else torch.softmax(gen, dim=-1)), cls
 
     def _run(self, image, text, prompt_text, negative_indices, labels, train):

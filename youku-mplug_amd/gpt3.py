@@ -321,6 +321,90 @@ class DistributedGPT3(nn.Module):
             out["logits"] = keep_logits.view(B, S, V)
         return out
 
+    @torch.no_grad()
+    def forward_prefix(self, query_features: Optional[torch.Tensor], ids: torch.Tensor) -> dict:
+        """Prefix pass of shared-prefix scoring: forward_lm over the n_groups prefix sequences (query features + the shared
+        tokens, ids [n_groups, t]).  -> the tape forward_continuation reads: every layer's packed qkv rows [n_groups * P, 3H]
+        (both residual-stream modes keep them)."""
+        assert not self.training, "shared-prefix scoring is an evaluation path (no dropout)"
+        tape = {}
+        self.forward_lm(query_features, ids, None, None, tape, hidden_only=True)
+        return dict(B=tape["B"], P=tape["S"], qkv=[ent["qkv"] for ent in tape["layers"]])
+
+    @torch.no_grad()
+    def forward_continuation(self, prefix: dict, ids: torch.Tensor, group_size: int, *, loss_rows: Optional[torch.Tensor] = None,
+                             labels: Optional[torch.Tensor] = None, hidden_rows: Optional[torch.Tensor] = None) -> dict:
+        """Continuation pass: ids [n_cont, Lc] continue the prefixes of forward_prefix, continuation c that of group
+        c // group_size, at absolute positions P .. P + Lc - 1.  Per layer the kernel sequence of forward_lm on the continuation
+        rows only (in whichever residual-stream mode forward_lm runs), with the attention against [prefix | own causal] keys
+        (ops.attn_prefix_fwd).  Outputs, on the rows asked for (row r = c * Lc + i of the flattened continuations):
+        loss_rows + labels -> losses fp32 [len(loss_rows)], the per-token CE of the tied LM head run on those rows only;
+        hidden_rows -> hidden bf16 [len(hidden_rows), H], the final LayerNorm's output there."""
+        assert not self.training, "shared-prefix scoring is an evaluation path (no dropout)"
+        cfg = self.config
+        lm = self.dist_model.language_model
+        n, Lc = ids.shape
+        P, ng = prefix["P"], prefix["B"]
+        assert Lc > 0 and ng == (n + group_size - 1) // group_size
+        H, np_, hn, V = cfg.hidden_size, cfg.num_attention_heads, cfg.kv_channels, cfg.vocab_size
+        R = n * Lc
+        wpe = lm.embedding.position_embeddings.weight
+        if P + Lc > wpe.shape[0]:
+            raise ops._lib.MpvError(f"sequence of {P + Lc} positions exceeds max_position_embeddings = {wpe.shape[0]}")
+        h = ops.gpt_embed_fwd(None, ids.contiguous(), lm.embedding.word_embeddings.weight, wpe[P:], n, 0, Lc, H)   # positions from P
+        st3 = (Lc * 3 * H, 3 * hn, 3 * H)
+        lay = ops.AttnLayout(st3, st3, st3, (Lc * H, hn, H))
+        pst = (P * 3 * H, 3 * hn, 3 * H)
+        scale = 1.0 / math.sqrt(hn)
+
+        def attention(qkv, li):
+            ctx = torch.empty((R, H), dtype=torch.bfloat16, device=h.device)
+            pq = prefix["qkv"][li]
+            ops.attn_prefix_fwd(qkv, qkv[:, hn:], qkv[:, 2 * hn:], pq[:, hn:], pq[:, 2 * hn:], ctx, lay, (pst, pst), n, group_size, np_, Lc,
+                                P, hn, scale=scale)
+            return ctx
+
+        if FP32_STREAM:
+            stream, pending = h, None
+            for li, layer in enumerate(lm.encoder.layers):
+                att, mlp = layer.self_attention, layer.mlp
+                l1, l2 = layer.input_layernorm, layer.post_attention_layernorm
+                x1, nxt, _, _ = ops.ln_stream_fwd(stream, pending, l1.weight, l1.bias, l1.eps, R, H)
+                stream = nxt if nxt is not None else stream
+                qkv = ops.gemm(x1, att.query_key_value.weight, R, 3 * H, H, bias=att.query_key_value.bias, keep_output=True)
+                a1 = ops.gemm(attention(qkv, li), att.dense.weight, R, H, H, bias=att.dense.bias)
+                x2, stream, _, _ = ops.ln_stream_fwd(stream, a1, l2.weight, l2.bias, l2.eps, R, H)
+                F4 = mlp.dense_h_to_4h.out_features
+                g = ops.gemm(x2, mlp.dense_h_to_4h.weight, R, F4, H, bias=mlp.dense_h_to_4h.bias, act=ACT_GELU_TANH)
+                pending = ops.gemm(g, mlp.dense_4h_to_h.weight, R, H, F4, bias=mlp.dense_4h_to_h.bias)
+            fl = lm.encoder.final_layernorm
+            xf, _, _, _ = ops.ln_stream_fwd(stream, pending, fl.weight, fl.bias, fl.eps, R, H)
+        else:
+            for li, layer in enumerate(lm.encoder.layers):
+                att, mlp = layer.self_attention, layer.mlp
+                l1, l2 = layer.input_layernorm, layer.post_attention_layernorm
+                x1, _, _ = ops.layernorm_fwd(h, l1.weight, l1.bias, l1.eps, R, H, want_stats=False)
+                qkv = ops.gemm(x1, att.query_key_value.weight, R, 3 * H, H, bias=att.query_key_value.bias, keep_output=True)
+                h1 = ops.gemm(attention(qkv, li), att.dense.weight, R, H, H, bias=att.dense.bias, residual=h)
+                x2, _, _ = ops.layernorm_fwd(h1, l2.weight, l2.bias, l2.eps, R, H, want_stats=False)
+                F4 = mlp.dense_h_to_4h.out_features
+                g = ops.gemm(x2, mlp.dense_h_to_4h.weight, R, F4, H, bias=mlp.dense_h_to_4h.bias, act=ACT_GELU_TANH)
+                h = ops.gemm(g, mlp.dense_4h_to_h.weight, R, H, F4, bias=mlp.dense_4h_to_h.bias, residual=h1)
+            fl = lm.encoder.final_layernorm
+            xf, _, _ = ops.layernorm_fwd(h, fl.weight, fl.bias, fl.eps, R, H, want_stats=False)
+        out = {}
+        if loss_rows is not None and loss_rows.numel() > 0:
+            nr = loss_rows.numel()
+            xs = ops.gather_rows(xf, loss_rows.contiguous(), nr, H)
+            logits = ops.gemm(xs, lm.embedding.word_embeddings.weight, nr, V, H)      # tied LM head (:1348-1350), scored rows only
+            ones = torch.ones(nr, dtype=torch.float32, device=xf.device)
+            out["losses"], _ = ops.cross_entropy(logits, labels.contiguous().view(-1), ones, nr, V)
+        elif loss_rows is not None:
+            out["losses"] = torch.zeros(0, dtype=torch.float32, device=xf.device)
+        if hidden_rows is not None:
+            out["hidden"] = ops.gather_rows(xf, hidden_rows.contiguous(), hidden_rows.numel(), H)
+        return out
+
     def _layers_bf16_stream(self, h, lay, scale, window, layers, seed, p_h, p_a, B, S, R, H, np_, hn, keep_inputs=False):
         """The layer stack with the reference's bf16 residual stream (residual adds in the GEMM epilogues): MPV_DECODER_STREAM=bf16,
         and always for a trainable decoder (keep_inputs: x1 / x2 / gelu(z) stay on the tape for the weight gradients, and the top layer

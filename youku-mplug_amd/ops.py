@@ -272,6 +272,26 @@ def attn_bwd(q, k, v, o, lse, do, dq, dk, dv, lay: AttnLayout, batch, heads, sq,
                                   _stream()), "mpv_attn_bwd")
 
 
+def attn_prefix_fwd(q, k, v, pk, pv, o, lay: AttnLayout, prefix_lay: Tuple[Tuple[int, int, int], Tuple[int, int, int]], n_cont,
+                    group_size, heads, cont_len, prefix_len, hd, *, scale=1.0):
+    """Causal attention of n_cont continuations (cont_len rows each; q/k/v/o strided (continuation, head, row) by `lay`) against
+    the prefix_len-row prefix of their group c // group_size (pk/pv strided (group, head, row) by prefix_lay = (k strides,
+    v strides)): query row i sees every prefix key and its own keys j <= i.  include/mpv.h: mpv_attn_prefix_fwd."""
+    _need_cuda(q, k, v, o, pk, pv)
+    d = _lib.AttnPrefixDesc()
+    d.q, d.k, d.v, d.o = q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr()
+    d.pk, d.pv = (_p(pk), _p(pv)) if prefix_len > 0 else (None, None)      # no prefix: nothing of pk / pv is read
+    d.q_cs, d.q_hs, d.q_rs = lay.q
+    d.k_cs, d.k_hs, d.k_rs = lay.k
+    d.v_cs, d.v_hs, d.v_rs = lay.v
+    d.o_cs, d.o_hs, d.o_rs = lay.o
+    (d.pk_gs, d.pk_hs, d.pk_rs), (d.pv_gs, d.pv_hs, d.pv_rs) = prefix_lay
+    d.n_cont, d.group_size, d.n_groups = n_cont, group_size, (n_cont + group_size - 1) // group_size
+    d.heads, d.cont_len, d.prefix_len, d.head_dim, d.scale = heads, cont_len, prefix_len, hd, scale
+    check(_lib.lib().mpv_attn_prefix_fwd(C.byref(d), _stream()), "mpv_attn_prefix_fwd")
+    return o
+
+
 def temporal_attn_fwd(qkv, out, n_outer, outer_stride, n_inner, inner_offset, t_stride, T, heads, hd, scale):
     _need_cuda(qkv, out)
     check(_lib.lib().mpv_temporal_attn_fwd(qkv.data_ptr(), out.data_ptr(), n_outer, outer_stride, n_inner, inner_offset,
