@@ -9,6 +9,8 @@ Kept from the reference because downstream tooling depends on it:
   * evaluation (:245-293): text features of the whole split in chunks of 32 titles padded to max(64, max_length), video features
     batch by batch, the two similarity matrices as numpy arrays;
   * itm_eval (:296-339): recall@1/5/10 both ways from the similarity matrices and the dataset's txt2vid / vid2txt tables;
+  * `--eval_on_device` (not in the reference, default off): evaluation_on_device / recall_from_ranks replace the two score
+    matrices and the host argsort by RetrievalIndex.rank (DESIGN.md section 11); evaluation / itm_eval are untouched;
   * main (:342-520): `--resume` of a pre-training checkpoint ('model' or 'module' key) with the position / temporal embeddings
     refitted to this run's resolution and frame count (:402-420), `--evaluate_only`, one DeepSpeed-layout checkpoint, one
     evaluation pass over val and test and one log.txt line per epoch.
@@ -176,6 +178,68 @@ def itm_eval(scores_i2t, scores_t2i, txt2img, img2txt):
             "vid_r_mean": ir_mean, "r_mean": (tr_mean + ir_mean) / 2}
 
 
+def _targets(lists, rows, device):
+    """ragged index lists -> int64 [rows, widest] padded with -1 (a scalar entry is a list of one)"""
+    lists = [list(l) if isinstance(l, (list, tuple)) else [int(l)] for l in (lists[i] for i in rows)]
+    width = max(len(l) for l in lists)
+    return torch.tensor([l + [-1] * (width - len(l)) for l in lists], dtype=torch.long, device=device).reshape(len(lists), width)
+
+
+@torch.no_grad()
+def evaluation_on_device(model, data_loader, tokenizer, device, config):
+    """-> (ranks_v2t int32 [videos], ranks_t2v int32 [texts]) as numpy arrays: `--eval_on_device`.  The features are those of
+    `evaluation` (same towers, same chunking); they go into a text index and a video index and every query is ranked against the
+    full gallery on the device (RetrievalIndex.rank) -- no score matrix on the device or the host.  Under a process group each
+    rank ranks its share of the queries and the rank vectors are all-gathered."""
+    from youku_mplug_amd.retrieval import RetrievalIndex
+    module = getattr(model, "module", model)
+    module.eval()
+    t0 = time.time()
+    ds = data_loader.dataset
+    texts = ds.text
+    text_index = video_index = None
+    for i in range(0, len(texts), 32):
+        text_input = tokenizer(texts[i:i + 32], padding="max_length", truncation=True, max_length=max(64, config["max_length"]),
+                               return_tensors="pt").to(device)
+        feat = module.extract_text_feature(text_input)
+        text_index = text_index or RetrievalIndex(feat.shape[1], device=device)
+        text_index.add(feat)
+    for video, _vid in data_loader:
+        feat = module.extract_vision_feature(video.to(device).bfloat16())
+        video_index = video_index or RetrievalIndex(feat.shape[1], device=device)
+        video_index.add(feat)
+    world, rank = (dist.get_world_size(), dist.get_rank()) if dist.is_available() and dist.is_initialized() else (1, 0)
+
+    def ranks_of(queries, gallery, lists):
+        n = len(queries)
+        per = (n + world - 1) // world
+        lo, hi = min(n, rank * per), min(n, (rank + 1) * per)
+        out = torch.full((per,), -1, dtype=torch.int32, device=device)
+        if hi > lo:
+            out[:hi - lo] = gallery.rank(queries.features[lo:hi], _targets(lists, range(lo, hi), device))
+        if world > 1:
+            parts = [torch.empty_like(out) for _ in range(world)]
+            dist.all_gather(parts, out)
+            out = torch.cat(parts)
+        return out[:n].cpu().numpy()
+
+    ranks_v2t = ranks_of(video_index, text_index, ds.vid2txt)
+    ranks_t2v = ranks_of(text_index, video_index, ds.txt2vid)
+    print("Evaluation time {}".format(str(datetime.timedelta(seconds=int(time.time() - t0)))))
+    return ranks_v2t, ranks_t2v
+
+
+def recall_from_ranks(ranks_v2t, ranks_t2v):
+    """itm_eval's dict from the rank vectors of evaluation_on_device (rank 0 = the wanted row came first)."""
+    ranks = np.asarray(ranks_v2t)
+    tr1, tr5, tr10 = (100.0 * len(np.where(ranks < k)[0]) / len(ranks) for k in (1, 5, 10))
+    ranks = np.asarray(ranks_t2v)
+    ir1, ir5, ir10 = (100.0 * len(np.where(ranks < k)[0]) / len(ranks) for k in (1, 5, 10))
+    tr_mean, ir_mean = (tr1 + tr5 + tr10) / 3, (ir1 + ir5 + ir10) / 3
+    return {"txt_r1": tr1, "txt_r5": tr5, "txt_r10": tr10, "txt_r_mean": tr_mean, "vid_r1": ir1, "vid_r5": ir5, "vid_r10": ir10,
+            "vid_r_mean": ir_mean, "r_mean": (tr_mean + ir_mean) / 2}
+
+
 def load_resume_state(model, path):
     """`--resume` (:402-420): a pre-training checkpoint under key 'model' (.pth) or 'module' (DeepSpeed layout); position and
     temporal embeddings are refitted to this model's patch grid / frame count; strict=False (the ITC heads are new)."""
@@ -232,8 +296,12 @@ def main(args, config):
     wd_values = mpv_engine.cosine_scheduler(args.weight_decay, args.weight_decay, args.epochs, steps_per_epoch)
 
     def evaluate(loader, name):
-        v2t, t2v = evaluation(model, loader, tokenizer, device, config)
-        stats = {"sim_{}".format(k): v for k, v in itm_eval(v2t, t2v, loader.dataset.txt2vid, loader.dataset.vid2txt).items()}
+        if getattr(args, "eval_on_device", False):
+            result = recall_from_ranks(*evaluation_on_device(model, loader, tokenizer, device, config))
+        else:
+            v2t, t2v = evaluation(model, loader, tokenizer, device, config)
+            result = itm_eval(v2t, t2v, loader.dataset.txt2vid, loader.dataset.vid2txt)
+        stats = {"sim_{}".format(k): v for k, v in result.items()}
         print(f"{name} Performance:", stats)
         return stats
 
@@ -279,6 +347,11 @@ def get_args(argv=None):
     p.add_argument("--enable_deepspeed", action="store_true", default=False)
     p.add_argument("--zero_stage", default=1, type=int)
     p.add_argument("--evaluate_only", action="store_true", default=False)
+    p.add_argument("--eval_on_device", action="store_true", default=False,
+                   help="rank every query against the full gallery on the GPU (fused similarity + rank kernel, no score matrix) "
+                        "instead of building both fp32 score matrices and argsorting them on the host.  The towers emit bf16 "
+                        "features, so the default path's .float() copies are exact and both paths score identical inputs; "
+                        "ties are ranked by the lower gallery index")
     p.add_argument("--synthetic_steps", default=0, type=int, help="run on N synthetic batches per epoch instead of the dataset")
     args, _ = p.parse_known_args(argv)
     config = yaml.load(open(args.config, "r"), Loader=_ConfigLoader)

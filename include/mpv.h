@@ -430,6 +430,34 @@ int mpv_smoothed_ce(const float* sim, const int64_t* target, float eps, float sc
                     int64_t rows, int64_t cols, mpv_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Retrieval search (evaluation / serving of the ITC model: downstream/run_retrieval_distributed_gpt3.py:245-339 builds both full
+ * score matrices and argsorts every row on the host; these calls return the k best rows, or the rank of the wanted rows,
+ * without the matrix).  queries bf16 [nq][dim], gallery bf16 [ng][dim], row strides q_rs / g_rs in elements (multiples of 8,
+ * base pointers 16-byte aligned); dim a multiple of 32 in [32, 1024]; nq <= 65535 * 32; ng <= 2^31 - 1.  Scores are
+ * <q, g> in fp32 (bf16 MFMA, fp32 accumulation).
+ * Order rule (both calls): row g comes before row h iff s(g) > s(h), or s(g) == s(h) and g < h -- a total order, so results do
+ * not depend on `slices` (gallery slices per query tile, each a workgroup; 0 = choose so that a single query fills the chip).
+ * NaN scores are ordered after everything and never returned.
+ * mpv_sim_topk: vals fp32 [nq][k], idx int64 [nq][k], k in [1, 32]: the k first rows by the rule with s = scale * <q, g>
+ *   (scale = 1.0f for the plain product), in that order; when ng < k the tail is (-inf, -1).
+ * mpv_sim_rank: target int64 [nq][n_targets] (n_targets in [1, 32]; an entry outside [0, ng) is an unused slot); rank int32 [nq] =
+ *   min over the query's targets t of #{g : g comes before t} (ng when the query has no target); scale is not applied.
+ *   The target scores come from the code path that scores the stream, so s(g) > s(t) compares like with like.
+ * Workspaces: *_workspace_size(d[, n_targets]) bytes (0 for a descriptor the call would refuse), 4-byte aligned. */
+typedef struct mpv_sim_search_desc {
+  const void *queries, *gallery;
+  int64_t q_rs, g_rs;
+  int64_t nq, ng;
+  int dim, k, slices;
+  float scale;
+} mpv_sim_search_desc;
+size_t mpv_sim_topk_workspace_size(const mpv_sim_search_desc* d);
+int mpv_sim_topk(const mpv_sim_search_desc* d, float* vals, int64_t* idx, void* workspace, size_t workspace_bytes, mpv_stream_t stream);
+size_t mpv_sim_rank_workspace_size(const mpv_sim_search_desc* d, int n_targets);
+int mpv_sim_rank(const mpv_sim_search_desc* d, const int64_t* target, int n_targets, int32_t* rank, void* workspace,
+                 size_t workspace_bytes, mpv_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Optimizer (DeepSpeed FusedAdam + global-norm clip, run_pretrain_distributed_gpt3.py:137;
  * math of optim/adamw.py:66-115; torch.nn.utils.clip_grad_norm_ semantics, utils.py:308).
  * sumsq (fp32 scalar, pre-zeroed) += sum g^2 over n bf16 gradients -- BIT-REPRODUCIBLE since round 6: per-workgroup partial sums in

@@ -56,6 +56,13 @@ class AttnPrefixDesc(C.Structure):
     ]
 
 
+class SimSearchDesc(C.Structure):
+    _fields_ = [
+        ("queries", c_void_p), ("gallery", c_void_p), ("q_rs", c_int64), ("g_rs", c_int64), ("nq", c_int64), ("ng", c_int64),
+        ("dim", c_int), ("k", c_int), ("slices", c_int), ("scale", c_float),
+    ]
+
+
 _RM = [c_int, c_int, c_int]
 _SIGS = {
     "mpv_version": (c_int, []),
@@ -126,6 +133,10 @@ _SIGS = {
     "mpv_maxsim_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p]),
     "mpv_maxsim_route": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p]),
     "mpv_smoothed_ce": (c_int, [c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    "mpv_sim_topk_workspace_size": (c_size_t, [C.POINTER(SimSearchDesc)]),
+    "mpv_sim_topk": (c_int, [C.POINTER(SimSearchDesc), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mpv_sim_rank_workspace_size": (c_size_t, [C.POINTER(SimSearchDesc), c_int]),
+    "mpv_sim_rank": (c_int, [C.POINTER(SimSearchDesc), c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mpv_grad_sumsq_workspace_size": (c_size_t, []),
     "mpv_grad_sumsq": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mpv_adamw_step": (c_int, [c_void_p] * 5 + [c_int64] + [c_float] * 5 + [c_int, c_float, c_void_p, c_float, c_void_p]),

@@ -608,3 +608,55 @@ def smoothed_ce(sim, target, eps, scale, rows, cols, want_grad=True):
     check(_lib.lib().mpv_smoothed_ce(sim.data_ptr(), target.data_ptr(), eps, scale, losses.data_ptr(), _p(dsim), _p(dts), rows, cols,
                                      _stream()), "mpv_smoothed_ce")
     return losses, dsim, dts
+
+
+def _sim_desc(q, g, k, scale, slices):
+    """mpv_sim_search_desc over bf16 feature rows q [Nq, D], g [Ng, D] (rows contiguous; a row stride is allowed)"""
+    _need_cuda(q, g)
+    for name, t in (("queries", q), ("gallery", g)):
+        if t.dtype != torch.bfloat16:
+            raise _lib.MpvError(f"sim search: {name} must be bfloat16 (got {t.dtype})")
+        if t.dim() != 2 or t.shape[0] == 0:
+            raise _lib.MpvError(f"sim search: {name} must be a non-empty [rows, dim] matrix (got {tuple(t.shape)})")
+        if t.stride(1) != 1:
+            raise _lib.MpvError(f"sim search: {name} rows must be contiguous (strides {t.stride()})")
+    if q.shape[1] != g.shape[1]:
+        raise _lib.MpvError(f"sim search: feature widths differ ({q.shape[1]} vs {g.shape[1]})")
+    d = _lib.SimSearchDesc()
+    d.queries, d.gallery = q.data_ptr(), g.data_ptr()
+    d.q_rs, d.g_rs = q.stride(0) if q.shape[0] > 1 else q.shape[1], g.stride(0) if g.shape[0] > 1 else g.shape[1]
+    d.nq, d.ng, d.dim, d.k, d.slices = q.shape[0], g.shape[0], q.shape[1], k, slices
+    d.scale = 1.0 if scale is None else float(scale)
+    return d
+
+
+def sim_topk(q, g, k, scale=None, slices=0):
+    """-> (vals fp32 [Nq, k], idx int64 [Nq, k]): the k largest scale * <q_i, g_j> per query, descending, ties to the lower j,
+    (-inf, -1) beyond Ng; `slices` gallery slices per query tile (0 = choose), the result does not depend on it
+    (include/mpv.h: mpv_sim_topk)."""
+    d = _sim_desc(q, g, k, scale, slices)
+    vals = torch.empty((q.shape[0], k), dtype=torch.float32, device=q.device)
+    idx = torch.empty((q.shape[0], k), dtype=torch.int64, device=q.device)
+    need = _lib.lib().mpv_sim_topk_workspace_size(C.byref(d))
+    ws = workspace(max(need, 1), q.device)
+    check(_lib.lib().mpv_sim_topk(C.byref(d), vals.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "mpv_sim_topk")
+    return vals, idx
+
+
+def sim_rank(q, g, target, slices=0):
+    """-> rank int32 [Nq]: the best rank among the query's target rows (target int64 [Nq] or [Nq, n_t], -1 = unused slot); the rank of
+    row t is the number of rows j with <q, g_j> > <q, g_t>, or equal and j < t (include/mpv.h: mpv_sim_rank)."""
+    d = _sim_desc(q, g, 0, None, slices)
+    _need_cuda(target)
+    if target.dtype != torch.int64:
+        raise _lib.MpvError(f"sim_rank: target must be int64 (got {target.dtype})")
+    target = target.reshape(target.shape[0], -1).contiguous()
+    if target.shape[0] != q.shape[0]:
+        raise _lib.MpvError(f"sim_rank: {target.shape[0]} target rows for {q.shape[0]} queries")
+    n_t = target.shape[1]
+    rank = torch.empty(q.shape[0], dtype=torch.int32, device=q.device)
+    need = _lib.lib().mpv_sim_rank_workspace_size(C.byref(d), n_t)
+    ws = workspace(max(need, 1), q.device)
+    check(_lib.lib().mpv_sim_rank(C.byref(d), target.data_ptr(), n_t, rank.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+          "mpv_sim_rank")
+    return rank

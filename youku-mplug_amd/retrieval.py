@@ -144,6 +144,17 @@ class DistributedGPT3_Retrieval(nn.Module):
     def extract_text_feature(self, text):
         return self._text_tower(text.input_ids, text.attention_mask, {})
 
+    # ------------------------------------------------------------------ search
+    @torch.no_grad()
+    def search_videos(self, text, index: "RetrievalIndex", k: int):
+        """-> (scores fp32 [B, k], indices int64 [B, k]): the k best rows of a video-feature index for each tokenised title"""
+        return index.search(self.extract_text_feature(text), k)
+
+    @torch.no_grad()
+    def search_texts(self, video, index: "RetrievalIndex", k: int):
+        """-> (scores, indices): the k best rows of a text-feature index for each clip"""
+        return index.search(self.extract_vision_feature(video), k)
+
     # ------------------------------------------------------------------ pipelines
     def _forward_pipeline(self, video, ids, mask, idx):
         tape = {"vit": {}}
@@ -218,3 +229,68 @@ def synthetic_retrieval_model(shapes, device="cuda", num_frames=None, embed_dim=
                      layernorm_epsilon=shapes.gpt_ln_eps)
     return DistributedGPT3_Retrieval({"num_learnable_token": shapes.num_queries, "_synthetic": True, "contrastive_embed_dim": embed_dim,
                                       "num_frames": num_frames or shapes.num_frames}, visual_cfg=vis, text_cfg=txt, device=device)
+
+
+class RetrievalIndex:
+    """Gallery of L2-normalised bf16 feature rows (what extract_vision_feature / extract_text_feature return) searched on the
+    device by ops.sim_topk / ops.sim_rank: the [queries, gallery] score matrix is never built.  Rows keep the order they were
+    added in; row i of the index is the i-th feature ever added.  Storage grows geometrically, so `add` does not re-allocate
+    per call.  Order rule of both searches: higher score first, equal scores by the lower row index (include/mpv.h)."""
+
+    def __init__(self, dim: int, device="cuda", capacity: int = 1024):
+        if dim % 32 != 0 or not 32 <= dim <= 1024:
+            raise ops._lib.MpvError(f"RetrievalIndex: dim ({dim}) must be a multiple of 32 in [32, 1024]")
+        self.dim, self.device, self.size = dim, torch.device(device), 0
+        self._rows = torch.empty((max(int(capacity), 1), dim), dtype=torch.bfloat16, device=self.device)
+
+    def __len__(self):
+        return self.size
+
+    @property
+    def capacity(self):
+        return self._rows.shape[0]
+
+    @property
+    def features(self):
+        """the rows added so far: a view of the storage, bf16 [size, dim]"""
+        return self._rows[:self.size]
+
+    def _check(self, feats, what):
+        if not torch.is_tensor(feats) or feats.dtype != torch.bfloat16:
+            raise ops._lib.MpvError(f"RetrievalIndex.{what}: features must be a bfloat16 tensor (the towers emit bf16; got "
+                                    f"{getattr(feats, 'dtype', type(feats))})")
+        if feats.dim() != 2 or feats.shape[1] != self.dim:
+            raise ops._lib.MpvError(f"RetrievalIndex.{what}: features must be [rows, {self.dim}] (got {tuple(feats.shape)})")
+
+    def add(self, features):
+        """append rows; -> the index of the first one"""
+        self._check(features, "add")
+        n, first = features.shape[0], self.size
+        if first + n > self.capacity:
+            grown = torch.empty((max(2 * self.capacity, first + n), self.dim), dtype=torch.bfloat16, device=self.device)
+            grown[:first].copy_(self._rows[:first])
+            self._rows = grown
+        self._rows[first:first + n].copy_(features)
+        self.size = first + n
+        return first
+
+    def search(self, query_features, k: int, scale=None):
+        """-> (scores fp32 [Nq, k], indices int64 [Nq, k]), best first; (-inf, -1) beyond the index size"""
+        self._check(query_features, "search")
+        if not 1 <= int(k) <= 32:
+            raise ops._lib.MpvError(f"RetrievalIndex.search: k ({k}) must be in [1, 32]")
+        if self.size == 0:
+            raise ops._lib.MpvError("RetrievalIndex.search: the index is empty")
+        return ops.sim_topk(query_features.contiguous(), self.features, int(k), scale=scale)
+
+    def rank(self, query_features, target):
+        """-> int32 [Nq]: the best rank (0 = first) among each query's target rows; target int64 [Nq] or [Nq, n_t], -1 = unused"""
+        self._check(query_features, "rank")
+        if self.size == 0:
+            raise ops._lib.MpvError("RetrievalIndex.rank: the index is empty")
+        target = torch.as_tensor(target, dtype=torch.int64, device=query_features.device)
+        target = target.reshape(query_features.shape[0], -1)
+        if target.numel() and (int(target.max()) >= self.size or int(target.min()) < -1):
+            raise ops._lib.MpvError(f"RetrievalIndex.rank: target rows must be in [-1, {self.size}) "
+                                    f"(got {int(target.min())} .. {int(target.max())})")
+        return ops.sim_rank(query_features.contiguous(), self.features, target)
