@@ -14,33 +14,13 @@ from torch import nn
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import youku_mplug_amd  # noqa: E402,F401
 
 
 # ------------------------------------------------------------------------------ kernel-call stubs (arithmetic of optim/adamw.py:66-115)
 def _stub_optimizer_kernels(monkeypatch_target):
-    from youku_mplug_amd import engine as eng
-
-    def grad_sumsq(g, out):
-        out.add_(g.float().pow(2).sum())
-
-    def adamw_step_grouped(p16, master, m, v, g16, tile_group, lrs, wds, beta1, beta2, eps, step, grad_scale=1.0, sumsq=None,
-                           max_norm=0.0):
-        g = g16.float() * grad_scale
-        if max_norm > 0:
-            norm = math.sqrt(float(sumsq)) * grad_scale
-            g = g * min(1.0, max_norm / (norm + 1e-6))
-        tg = tile_group.long().repeat_interleave(eng.TILE)
-        for gi, (lr, wd) in enumerate(zip(lrs, wds)):
-            sel = tg == gi
-            if not sel.any():
-                continue
-            master[sel] *= 1.0 - lr * wd
-            m[sel] = beta1 * m[sel] + (1 - beta1) * g[sel]
-            v[sel] = beta2 * v[sel] + (1 - beta2) * g[sel] ** 2
-            denom = (v[sel].sqrt() / math.sqrt(1 - beta2 ** step)) + eps
-            master[sel] -= (lr / (1 - beta1 ** step)) * m[sel] / denom
-        p16.copy_(master.to(p16.dtype))
+    from standin_optim import adamw_step_grouped, grad_sumsq      # tests/standin_optim.py: their arithmetic in torch
 
     def add(a, b, out=None):
         out = out if out is not None else torch.empty_like(a)
