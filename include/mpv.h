@@ -458,6 +458,45 @@ int mpv_sim_rank(const mpv_sim_search_desc* d, const int64_t* target, int n_targ
                  size_t workspace_bytes, mpv_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Query-max retrieval search (zero-shot evaluation / serving of the pre-train model's contrastive head, use_contrastive,
+ * models/distributed_gpt3.py:178-202): mpv_sim_topk / mpv_sim_rank over ITEMS that are groups of rows.  Neither the
+ * [nq][ng][group] products nor an [nq][ng] matrix reach memory.
+ * queries / gallery: bf16 rows, L2-normalised by the caller, base pointers 16-byte aligned, row strides q_rs / g_rs in elements
+ *   (multiples of 8, at least dim).  nq / ng count ITEMS: item i of a side is its rows i * group .. i * group + group - 1.
+ * Score: s(i, j) = max over the rows a of query item i and the rows b of gallery item j of <a, b> (bf16 MFMA, fp32 accumulation);
+ *   the max is taken before any scale, as in mpv_maxsim_fwd.
+ * Groups: q_group and g_group are in [1, 1024], no multiple of anything, and at most ONE of them exceeds 1 (title -> clip:
+ *   g_group = Q; clip -> title: q_group = Q; both 1: mpv_sim_topk / mpv_sim_rank bit for bit).
+ * dim: a multiple of 32 in [32, 1024].  k in [1, 32], n_targets in [1, 32]; nq * q_group and ng * g_group <= 2^31 - 1.
+ * Order rule, ties, slices: those of mpv_sim_topk / mpv_sim_rank, over items, not rows: item g comes before item h iff
+ *   s(g) > s(h), or s(g) == s(h) and g < h -- a total order; `slices` (0 = choose) only cuts the work and the outputs are
+ *   bit-identical for every value of it.
+ * NaN: a NaN product never wins a max over finite ones; an item whose score is NaN (all its products are) is never returned,
+ *   beats nothing, and as a target counts as no target.
+ * mpv_maxsim_topk: vals fp32 [nq][k], idx int64 [nq][k]: the k first items by the rule with s = scale * s(i, j), in that order;
+ *   when ng < k the tail is (-inf, -1).  No atomics.
+ * mpv_maxsim_rank: target int64 [nq][n_targets] (an entry outside [0, ng) is an unused slot); rank int32 [nq] = min over the
+ *   query item's targets t of #{g : g comes before t}, ng when it has no valid target; scale is not applied.  The target scores
+ *   come from the staging and MFMA path that scores the stream (a max over bit-identical products is bit-identical), so
+ *   s(g) > s(t) compares like with like.  Counts are added with integer atomics (order-independent).
+ * Refusals: a descriptor the call would refuse makes *_workspace_size return 0 and the call return a negative code before any
+ *   launch; a workspace that is too small is MPV_E_ARG.  Workspaces are 4-byte aligned. */
+typedef struct mpv_maxsim_search_desc {
+  const void *queries, *gallery;
+  int64_t q_rs, g_rs;
+  int64_t nq, ng;
+  int q_group, g_group;
+  int dim, k, slices;
+  float scale;
+} mpv_maxsim_search_desc;
+size_t mpv_maxsim_topk_workspace_size(const mpv_maxsim_search_desc* d);
+int mpv_maxsim_topk(const mpv_maxsim_search_desc* d, float* vals, int64_t* idx, void* workspace, size_t workspace_bytes,
+                    mpv_stream_t stream);
+size_t mpv_maxsim_rank_workspace_size(const mpv_maxsim_search_desc* d, int n_targets);
+int mpv_maxsim_rank(const mpv_maxsim_search_desc* d, const int64_t* target, int n_targets, int32_t* rank, void* workspace,
+                    size_t workspace_bytes, mpv_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Optimizer (DeepSpeed FusedAdam + global-norm clip, run_pretrain_distributed_gpt3.py:137;
  * math of optim/adamw.py:66-115; torch.nn.utils.clip_grad_norm_ semantics, utils.py:308).
  * sumsq (fp32 scalar, pre-zeroed) += sum g^2 over n bf16 gradients -- BIT-REPRODUCIBLE since round 6: per-workgroup partial sums in

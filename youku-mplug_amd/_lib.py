@@ -63,6 +63,13 @@ class SimSearchDesc(C.Structure):
     ]
 
 
+class MaxSimSearchDesc(C.Structure):
+    _fields_ = [
+        ("queries", c_void_p), ("gallery", c_void_p), ("q_rs", c_int64), ("g_rs", c_int64), ("nq", c_int64), ("ng", c_int64),
+        ("q_group", c_int), ("g_group", c_int), ("dim", c_int), ("k", c_int), ("slices", c_int), ("scale", c_float),
+    ]
+
+
 _RM = [c_int, c_int, c_int]
 _SIGS = {
     "mpv_version": (c_int, []),
@@ -137,6 +144,10 @@ _SIGS = {
     "mpv_sim_topk": (c_int, [C.POINTER(SimSearchDesc), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mpv_sim_rank_workspace_size": (c_size_t, [C.POINTER(SimSearchDesc), c_int]),
     "mpv_sim_rank": (c_int, [C.POINTER(SimSearchDesc), c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mpv_maxsim_topk_workspace_size": (c_size_t, [C.POINTER(MaxSimSearchDesc)]),
+    "mpv_maxsim_topk": (c_int, [C.POINTER(MaxSimSearchDesc), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mpv_maxsim_rank_workspace_size": (c_size_t, [C.POINTER(MaxSimSearchDesc), c_int]),
+    "mpv_maxsim_rank": (c_int, [C.POINTER(MaxSimSearchDesc), c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mpv_grad_sumsq_workspace_size": (c_size_t, []),
     "mpv_grad_sumsq": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mpv_adamw_step": (c_int, [c_void_p] * 5 + [c_int64] + [c_float] * 5 + [c_int, c_float, c_void_p, c_float, c_void_p]),

@@ -660,3 +660,65 @@ def sim_rank(q, g, target, slices=0):
     check(_lib.lib().mpv_sim_rank(C.byref(d), target.data_ptr(), n_t, rank.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
           "mpv_sim_rank")
     return rank
+
+
+def _maxsim_side(name, t):
+    """-> (rows per item, row stride in elements) of bf16 features [n, dim] (one row per item) or [n, group, dim]"""
+    if t.dtype != torch.bfloat16:
+        raise _lib.MpvError(f"maxsim search: {name} must be bfloat16 (got {t.dtype})")
+    if t.dim() not in (2, 3) or t.shape[0] == 0 or t.shape[-2] == 0:
+        raise _lib.MpvError(f"maxsim search: {name} must be a non-empty [items, dim] or [items, group, dim] tensor (got {tuple(t.shape)})")
+    if t.stride(-1) != 1:
+        raise _lib.MpvError(f"maxsim search: {name} rows must be contiguous (strides {t.stride()})")
+    if t.dim() == 2:
+        return 1, (t.stride(0) if t.shape[0] > 1 else t.shape[1])
+    rs = t.stride(1) if t.shape[1] > 1 else (t.stride(0) if t.shape[0] > 1 else t.shape[2])
+    if t.shape[0] > 1 and t.stride(0) != t.shape[1] * rs:
+        raise _lib.MpvError(f"maxsim search: the rows of {name} must be evenly spaced across items (strides {t.stride()})")
+    return t.shape[1], rs
+
+
+def _maxsim_desc(q, g, k, scale, slices):
+    """mpv_maxsim_search_desc over bf16 features; each side is [items, dim] or [items, group, dim], at most one side grouped > 1"""
+    _need_cuda(q, g)
+    (qg, q_rs), (gg, g_rs) = _maxsim_side("queries", q), _maxsim_side("gallery", g)
+    if q.shape[-1] != g.shape[-1]:
+        raise _lib.MpvError(f"maxsim search: feature widths differ ({q.shape[-1]} vs {g.shape[-1]})")
+    d = _lib.MaxSimSearchDesc()
+    d.queries, d.gallery, d.q_rs, d.g_rs = q.data_ptr(), g.data_ptr(), q_rs, g_rs
+    d.nq, d.ng, d.q_group, d.g_group, d.dim, d.k, d.slices = q.shape[0], g.shape[0], qg, gg, q.shape[-1], k, slices
+    d.scale = 1.0 if scale is None else float(scale)
+    return d
+
+
+def maxsim_topk(q, g, k, scale=None, slices=0):
+    """-> (vals fp32 [Nq, k], idx int64 [Nq, k]): the k gallery items with the largest scale * max over the group's rows of <a, b>
+    per query item, descending, ties to the lower item, (-inf, -1) beyond Ng.  q, g: bf16 [items, dim] or [items, group, dim], at
+    most one of them with group > 1; the result does not depend on `slices` (include/mpv.h: mpv_maxsim_topk)."""
+    d = _maxsim_desc(q, g, k, scale, slices)
+    vals = torch.empty((q.shape[0], k), dtype=torch.float32, device=q.device)
+    idx = torch.empty((q.shape[0], k), dtype=torch.int64, device=q.device)
+    need = _lib.lib().mpv_maxsim_topk_workspace_size(C.byref(d))
+    ws = workspace(max(need, 1), q.device)
+    check(_lib.lib().mpv_maxsim_topk(C.byref(d), vals.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+          "mpv_maxsim_topk")
+    return vals, idx
+
+
+def maxsim_rank(q, g, target, slices=0):
+    """-> rank int32 [Nq]: the best rank among the query item's target items (target int64 [Nq] or [Nq, n_t], -1 = unused slot) under
+    the query-max score and the order rule of maxsim_topk; Ng for a query with no valid target (include/mpv.h: mpv_maxsim_rank)."""
+    d = _maxsim_desc(q, g, 0, None, slices)
+    _need_cuda(target)
+    if target.dtype != torch.int64:
+        raise _lib.MpvError(f"maxsim_rank: target must be int64 (got {target.dtype})")
+    target = target.reshape(target.shape[0], -1).contiguous()
+    if target.shape[0] != q.shape[0]:
+        raise _lib.MpvError(f"maxsim_rank: {target.shape[0]} target rows for {q.shape[0]} query items")
+    n_t = target.shape[1]
+    rank = torch.empty(q.shape[0], dtype=torch.int32, device=q.device)
+    need = _lib.lib().mpv_maxsim_rank_workspace_size(C.byref(d), n_t)
+    ws = workspace(max(need, 1), q.device)
+    check(_lib.lib().mpv_maxsim_rank(C.byref(d), target.data_ptr(), n_t, rank.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+          "mpv_maxsim_rank")
+    return rank

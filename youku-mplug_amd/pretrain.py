@@ -139,16 +139,9 @@ class DistributedGPT3_Pretrain(nn.Module):
         Q, D, Hh, E = self.num_learnable_token, self.vision_width, self.text_width, self.vision_proj.out_features
         if B % 8:
             raise ValueError(f"use_contrastive: the per-rank batch ({B}) must be a multiple of 8 (operand rule of the head's GEMMs)")
-        # text-only pass of the frozen decoder (:169-176): hidden states after the final LayerNorm; its LM head / CE are unused in
-        # the reference and skipped here.  pass_index 1: its dropout masks are not the caption pass's.
-        out = self.text_decoder.forward_lm(None, ids, None, None, {}, hidden_only=True, pass_index=1)
-        rows = torch.arange(B, device=ids.device) * L + (mask.sum(dim=-1) - 1)                                  # :181
-        pooled = ops.gather_rows(out["last_hidden_state"].reshape(B * L, Hh), rows.contiguous(), B, Hh)
+        pooled, tp, tf, tn = self._itc_text_features(ids, mask)
         iq = tape["image_query"]
-        vp = ops.gemm(iq, self.vision_proj.weight, B * Q, E, D, bias=self.vision_proj.bias)                    # :178
-        vf, vn = ops.l2norm_fwd(vp, B * Q, E)
-        tp = ops.gemm(pooled, self.text_proj.weight, B, E, Hh, bias=self.text_proj.bias)                       # :182
-        tf, tn = ops.l2norm_fwd(tp, B, E)
+        vp, vf, vn = self._itc_vision_features(iq, B)
         g = getattr(self, "process_group", None)
         v_all, t_all = gather_cat(vf, g), gather_cat(tf, g)                                                    # :184-185
         WB = t_all.shape[0]
@@ -163,6 +156,57 @@ class DistributedGPT3_Pretrain(nn.Module):
         tape["loss_ita"] = (l1.sum() + l2.sum()) * scale
         tape["itc"] = dict(B=B, WB=WB, E=E, pooled=pooled, vp=vp, vn=vn, vf=vf, tp=tp, tn=tn, tf=tf, v_all=v_all, t_all=t_all,
                            arg1=arg1, arg2=arg2, ds1=ds1, ds2=ds2, dts=dt1.sum() + dt2.sum(), inv_temp=inv_temp)
+
+    def _itc_text_features(self, ids, mask):
+        """-> (pooled [B, Hh], tp [B, E], tf = tp / |tp| bf16, tn): the title side of the head, shared by the loss and extract_text_feature"""
+        B, L = ids.shape
+        Hh, E = self.text_width, self.vision_proj.out_features
+        # text-only pass of the frozen decoder (:169-176): hidden states after the final LayerNorm; its LM head / CE are unused in
+        # the reference and skipped here.  pass_index 1: its dropout masks are not the caption pass's.
+        out = self.text_decoder.forward_lm(None, ids, None, None, {}, hidden_only=True, pass_index=1)
+        rows = torch.arange(B, device=ids.device) * L + (mask.sum(dim=-1) - 1)                                  # :181
+        pooled = ops.gather_rows(out["last_hidden_state"].reshape(B * L, Hh), rows.contiguous(), B, Hh)
+        tp = ops.gemm(pooled, self.text_proj.weight, B, E, Hh, bias=self.text_proj.bias)                       # :182
+        tf, tn = ops.l2norm_fwd(tp, B, E)
+        return pooled, tp, tf, tn
+
+    def _itc_vision_features(self, image_query, B):
+        """-> (vp [B*Q, E], vf = vp / |vp| bf16, vn): the clip side of the head, shared by the loss and extract_vision_feature"""
+        Q, D, E = self.num_learnable_token, self.vision_width, self.vision_proj.out_features
+        vp = ops.gemm(image_query, self.vision_proj.weight, B * Q, E, D, bias=self.vision_proj.bias)           # :178
+        vf, vn = ops.l2norm_fwd(vp, B * Q, E)
+        return vp, vf, vn
+
+    # ---------------------------------------------------------------- zero-shot retrieval with the contrastive head
+    def _need_contrastive(self, what):
+        if not self.use_contrastive:
+            raise RuntimeError(f"{type(self).__name__}.{what} needs the contrastive head: build the model with use_contrastive: true "
+                               "(vision_proj / text_proj / temp do not exist otherwise)")
+
+    @torch.no_grad()
+    def extract_vision_feature(self, video):
+        """video [B, 3, T, H, W] -> bf16 [B, Q, E], unit rows: the `vf` operand of the query-max loss for this batch, bit for bit"""
+        self._need_contrastive("extract_vision_feature")
+        B = video.shape[0]
+        emb = self.visual_encoder.forward_features(video.to(torch.bfloat16), {})
+        image_query = self.attn_pool.forward_pool(self.learnable_queries, emb, B, emb.shape[0] // B, {})
+        return self._itc_vision_features(image_query, B)[1].view(B, self.num_learnable_token, -1)
+
+    @torch.no_grad()
+    def extract_text_feature(self, text):
+        """text (input_ids, attention_mask [B, L]) -> bf16 [B, E], unit rows: the `tf` operand of the loss for this batch, bit for bit"""
+        self._need_contrastive("extract_text_feature")
+        return self._itc_text_features(text.input_ids, text.attention_mask)[2]
+
+    @torch.no_grad()
+    def search_videos(self, text, index, k):
+        """the k best clips of a retrieval.MaxSimIndex of clip features ([n, Q, E]) per title: (scores / temp, indices), best first"""
+        return index.search(self.extract_text_feature(text), k, scale=1.0 / float(self.temp))
+
+    @torch.no_grad()
+    def search_texts(self, video, index, k):
+        """the k best titles of a retrieval.MaxSimIndex of title features ([n, E]) per clip: (scores / temp, indices), best first"""
+        return index.search(self.extract_vision_feature(video), k, scale=1.0 / float(self.temp))
 
     def _contrastive_backward(self, tape, grad_ita):
         """gradients of the head (projections, temp) and d image_query [B*Q, D]; the text tower below `pooled` is frozen."""

@@ -294,3 +294,77 @@ class RetrievalIndex:
             raise ops._lib.MpvError(f"RetrievalIndex.rank: target rows must be in [-1, {self.size}) "
                                     f"(got {int(target.min())} .. {int(target.max())})")
         return ops.sim_rank(query_features.contiguous(), self.features, target)
+
+
+class MaxSimIndex:
+    """Gallery of ITEMS that are groups of `group` L2-normalised bf16 rows (the pre-train model's extract_vision_feature returns
+    [B, Q, E]: group = Q; its extract_text_feature returns [B, E]: group = 1), searched on the device by ops.maxsim_topk /
+    ops.maxsim_rank under the query-max score: s(query, item) = max over the rows of both of <a, b>.  A grouped index takes
+    single-row queries [nq, dim]; a group == 1 index takes single-row queries or grouped ones [nq, Q, dim].  Neither the row
+    products nor a [queries, items] matrix are built.  Surface, growth and order rule of RetrievalIndex."""
+
+    def __init__(self, dim: int, group: int = 1, device="cuda", capacity: int = 1024):
+        if dim % 32 != 0 or not 32 <= dim <= 1024:
+            raise ops._lib.MpvError(f"MaxSimIndex: dim ({dim}) must be a multiple of 32 in [32, 1024]")
+        if not 1 <= int(group) <= 1024:
+            raise ops._lib.MpvError(f"MaxSimIndex: group ({group}) must be in [1, 1024]")
+        self.dim, self.group, self.device, self.size = dim, int(group), torch.device(device), 0
+        self._rows = torch.empty((max(int(capacity), 1), self.group, dim), dtype=torch.bfloat16, device=self.device)
+
+    def __len__(self):
+        return self.size
+
+    @property
+    def capacity(self):
+        return self._rows.shape[0]
+
+    @property
+    def features(self):
+        """the items added so far: a view of the storage, bf16 [size, group, dim]"""
+        return self._rows[:self.size]
+
+    def _check(self, feats, what, groups):
+        if not torch.is_tensor(feats) or feats.dtype != torch.bfloat16:
+            raise ops._lib.MpvError(f"MaxSimIndex.{what}: features must be a bfloat16 tensor (the towers emit bf16; got "
+                                    f"{getattr(feats, 'dtype', type(feats))})")
+        if feats.dim() == 2 and 1 in groups and feats.shape[1] == self.dim:
+            return feats[:, None, :]
+        if feats.dim() == 3 and feats.shape[2] == self.dim and (groups is any or feats.shape[1] in groups) and feats.shape[1] >= 1:
+            return feats
+        raise ops._lib.MpvError(f"MaxSimIndex.{what}: features of shape {tuple(feats.shape)} do not fit an index of group {self.group}, "
+                                f"dim {self.dim}")
+
+    def add(self, features):
+        """append items [n, group, dim] ([n, dim] when group == 1); -> the index of the first one"""
+        features = self._check(features, "add", (self.group,))
+        n, first = features.shape[0], self.size
+        if first + n > self.capacity:
+            grown = torch.empty((max(2 * self.capacity, first + n), self.group, self.dim), dtype=torch.bfloat16, device=self.device)
+            grown[:first].copy_(self._rows[:first])
+            self._rows = grown
+        self._rows[first:first + n].copy_(features)
+        self.size = first + n
+        return first
+
+    def _query(self, query_features, what):
+        # a grouped index is searched with one row per query; an index of single rows with single rows or with groups of any size
+        q = self._check(query_features, what, (1,) if self.group > 1 else any)
+        if self.size == 0:
+            raise ops._lib.MpvError(f"MaxSimIndex.{what}: the index is empty")
+        return q.contiguous()
+
+    def search(self, query_features, k: int, scale=None):
+        """-> (scores fp32 [Nq, k], indices int64 [Nq, k]), best first; (-inf, -1) beyond the index size"""
+        q = self._query(query_features, "search")
+        if not 1 <= int(k) <= 32:
+            raise ops._lib.MpvError(f"MaxSimIndex.search: k ({k}) must be in [1, 32]")
+        return ops.maxsim_topk(q, self.features, int(k), scale=scale)
+
+    def rank(self, query_features, target):
+        """-> int32 [Nq]: the best rank (0 = first) among each query's target items; target int64 [Nq] or [Nq, n_t], -1 = unused"""
+        q = self._query(query_features, "rank")
+        target = torch.as_tensor(target, dtype=torch.int64, device=q.device).reshape(q.shape[0], -1)
+        if target.numel() and (int(target.max()) >= self.size or int(target.min()) < -1):
+            raise ops._lib.MpvError(f"MaxSimIndex.rank: target items must be in [-1, {self.size}) "
+                                    f"(got {int(target.min())} .. {int(target.max())})")
+        return ops.maxsim_rank(q, self.features, target)
