@@ -244,3 +244,23 @@ def test_requests_of_a_block_go_out_together(kernels):
     for i in range(1, len(seq) - 1):
         if seq[i] == "w0" and seq[i + 1] == "|":
             assert "S" not in seq[:i], seq
+
+
+def test_search_kernels_keep_their_occupancy_tier(kernels):
+    """The fused search kernels (csrc/retrieval_search.hip and maxsim_search.hip, built on csrc/search_common.h): no scratch, and every
+    kernel within the occupancy tier -- 128 / 168 / 256 / 512 unified registers = 4 / 3 / 2 / 1 waves per SIMD -- of the register
+    count it had while the two files each carried their own copy of the shared pieces (the numbers below; the rank finish kernel was
+    10 registers, its query-max twin mxs_rank_finish_kernel, whose NaN test it took over, 13).  The slice merge exists once."""
+    ks, _ = kernels
+    before = {"17sim_stream_kernelILi0ELi4EE": 144, "17sim_stream_kernelILi0ELi16EE": 192, "17sim_stream_kernelILi0ELi32EE": 260,
+              "17sim_stream_kernelILi1ELi1EE": 144, "17sim_target_kernel": 100, "21sim_topk_merge_kernel": 44,
+              "22sim_rank_finish_kernel": 10, "18mxs_gallery_kernelILi0ELi4EE": 168, "18mxs_gallery_kernelILi0ELi16EE": 224,
+              "18mxs_gallery_kernelILi0ELi32EE": 276, "18mxs_gallery_kernelILi1ELi1EE": 148, "15mxs_item_kernelILi0EE": 136,
+              "15mxs_item_kernelILi1EE": 116, "15mxs_item_kernelILi2EE": 108, "15mxs_item_kernelILi3EE": 108}
+    tier = lambda v: next(t for t in (128, 168, 256, 512) if v <= t)
+    mine = {n: k for n, k in ks.items() if re.search(r"\d+(sim|mxs)_\w+_kernel", n)}
+    assert len(mine) == len(before), sorted(mine)
+    for n, k in mine.items():
+        frag = next(f for f in before if f in n)
+        assert k["scratch"] == 0 and k["vgpr"] <= tier(before[frag]), (n, k, tier(before[frag]))
+    assert len(_sel(ks, "sim_topk_merge_kernel")) == 1 and not [n for n in ks if "mxs_merge_kernel" in n]

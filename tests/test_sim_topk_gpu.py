@@ -3,14 +3,11 @@
 import pytest
 import torch
 
+from standin_search import order as _order       # gallery indices per row by (-score, index)
+
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
 SLICES = (0, 1, 3, 17)
-
-
-def _order(scores):
-    """gallery indices per row by (-score, index): a stable sort of the negated scores"""
-    return torch.sort(-scores, dim=1, stable=True).indices
 
 
 def _ints(n, d, dev, seed):

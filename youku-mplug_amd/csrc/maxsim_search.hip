@@ -8,13 +8,14 @@
 //
 // Both kernels keep one side RESIDENT in LDS (32 rows, the MFMA's B operand: a lane owns resident row lane & 31) and STREAM the
 // other (32 rows x 128 k chunks per wave through registers and a 272-byte-pitch LDS stage, one step ahead, the MFMA's A operand)
-// -- the staging and MFMA functions are those of retrieval_search.hip, copied.  The grouped side is always the streamed one, so the
-// max over a group is a max over accumulator ROWS, which a lane holds itself: no cross-lane reduction beyond the two lane halves.
+// -- through sc_stage_* / sc_tile_mma / sc_load_resident of search_common.h, the one definition that retrieval_search.hip uses
+// too.  The grouped side is always the streamed one, so the max over a group is a max over accumulator ROWS, which a lane holds
+// itself: no cross-lane reduction beyond the two lane halves.
 //   gallery grouped (title -> clip, and group == 1): mxs_gallery_kernel.  A workgroup owns 32 queries; every wave walks its own
 //     contiguous run of gallery items.  Groups straddle the 32-row tiles, so a lane carries a running max; the item boundaries
 //     are wave-uniform.  Per tile the 32 row scores of a lane's query are put in row order (one exchange between the lane
 //     halves), scanned by a segmented running max, and the scores of the items that END in the tile are offered to the lane's
-//     sorted list (RsList of retrieval_search.hip) or compared with the query's targets.
+//     sorted list (TopList of search_common.h) or compared with the query's targets.
 //   queries grouped (clip -> title): mxs_item_kernel.  A wave owns ONE query item and streams its rows against every resident
 //     tile of 32 titles (shared by the workgroup's 4 waves); after the item's last row lane l holds s(item, title 32 t + l).  The
 //     item's list lives across the wave (slot j in lane j): the lanes that beat the k-th slot are found with a ballot and
@@ -24,71 +25,21 @@
 // its A row, its B column and the accumulator only, and a max does not depend on the order of its operands, so no result
 // depends on how the work was cut.  The running max starts at NaN and takes any operand over a NaN, so a NaN product never
 // wins over a finite one and an item is NaN only when all its products are; such an item beats nothing.
-// Target scores of mpv_maxsim_rank come from mxs_item_kernel's target modes: the same rs-style staging, chunk order (128 k
+// Target scores of mpv_maxsim_rank come from mxs_item_kernel's target modes: the same staging functions, chunk order (128 k
 // ascending, 16 per MFMA), operand roles and accumulator reset as the stream that later meets the same rows, hence bit-identical
-// products, and a max over bit-identical elements is bit-identical.
-#include "mpv_common.h"
+// products, and a max over bit-identical elements is bit-identical.  With both groups 1 the products are those of
+// retrieval_search.hip's kernels for the same reason -- one definition of the tile walk -- and the max is over one element, so
+// mpv_maxsim_* equals mpv_sim_* bit for bit.  The slices are merged by sim_topk_merge_kernel and the ranks finished by
+// sim_rank_finish_kernel (retrieval_search.hip), which both files launch.
+#include "search_common.h"
 #include "../../include/mpv.h"
 
 namespace {
 
-constexpr int MX_RT = 32;               // resident rows per workgroup
-constexpr int MX_WAVES = 4;
-constexpr int MX_ST = 32;               // streamed rows per wave and step
-constexpr int MX_KC = 128;              // k per staged chunk
-constexpr int MX_PITCH = MX_KC + 8;     // bf16 elements: 272 bytes, rows 4 banks apart
-constexpr int MX_UNITS = MX_ST * MX_KC / 8 / 64;
-constexpr int MX_NONE = 0x7fffffff;
-constexpr int MX_MAX_K = 32, MX_MAX_T = 32, MX_MAX_SLICES = 4096, MX_MAX_GROUP = 1024;
-constexpr int MX_MERGE_CACHE = 6144;
+constexpr int MX_MAX_GROUP = 1024;
 
-__device__ __forceinline__ bool mx_better(float v, int g, float bv, int bg) { return v > bv || (v == bv && g < bg); }
 // running max that starts at NaN: any operand replaces a NaN, a NaN operand replaces nothing
 __device__ __forceinline__ float mx_nanmax(float run, float x) { return (x > run || run != run) ? x : run; }
-
-struct MxStage {
-  bf16x8 r[MX_UNITS];
-};
-
-template <class RowFn>
-__device__ __forceinline__ void mx_stage_load(MxStage& st, const bf16* __restrict__ S, long long s_rs, int k0, int D, RowFn row_of,
-                                              int lane) {
-#pragma unroll
-  for (int j = 0; j < MX_UNITS; ++j) {
-    const int u = j * 64 + lane, row = u >> 4, k = k0 + (u & 15) * 8;
-    const long long gr = row_of(row);
-    bf16x8 v = {};
-    if (gr >= 0 && k < D) v = *(const bf16x8*)(S + gr * s_rs + k);
-    st.r[j] = v;
-  }
-}
-__device__ __forceinline__ void mx_stage_store(const MxStage& st, bf16* buf, int lane) {
-#pragma unroll
-  for (int j = 0; j < MX_UNITS; ++j) {
-    const int u = j * 64 + lane;
-    *(bf16x8*)(buf + (u >> 4) * MX_PITCH + (u & 15) * 8) = st.r[j];
-  }
-}
-// acc[i] += <staged row 8 (i / 4) + 4 (lane / 32) + i % 4, resident row lane & 31> over `ksteps` 16-wide steps
-__device__ __forceinline__ void mx_tile_mma(f32x16& acc, const bf16* sbuf, const bf16* rrow, int ksteps, int lane) {
-  const bf16* ap = sbuf + (lane & 31) * MX_PITCH + 8 * (lane >> 5);
-  const bf16* bp = rrow + 8 * (lane >> 5);
-  for (int kk = 0; kk < ksteps; ++kk)
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const bf16x8*)(ap + kk * 16), *(const bf16x8*)(bp + kk * 16), acc, 0, 0, 0);
-}
-// 32 resident rows (row_of(j), or zeros when < 0) -> LDS at pitch D + 8
-template <class RowFn>
-__device__ __forceinline__ void mx_load_resident(bf16* rbuf, const bf16* __restrict__ R, long long r_rs, int D, RowFn row_of, int tid,
-                                                 int nthreads) {
-  const int upr = D >> 3;
-  for (int u = tid; u < MX_RT * upr; u += nthreads) {
-    const int row = u / upr, c = (u - row * upr) * 8;
-    const long long gr = row_of(row);
-    bf16x8 v = {};
-    if (gr >= 0) v = *(const bf16x8*)(R + gr * r_rs + c);
-    *(bf16x8*)(rbuf + row * (D + 8) + c) = v;
-  }
-}
 
 struct MxArgs {
   const bf16 *S, *R;         // streamed (grouped) rows, resident rows
@@ -106,94 +57,54 @@ struct MxArgs {
   int* counts;               // rank: [nq][n_t], zeroed
 };
 
-// retrieval_search.hip's per-lane sorted list: the k <= KMAX best (value, item) pairs in the LAST k slots, static indices only
-template <int KMAX>
-struct MxList {
-  float v[KMAX];
-  int g[KMAX];
-  __device__ __forceinline__ void init(int k) {
-#pragma unroll
-    for (int j = 0; j < KMAX; ++j) {
-      v[j] = j < KMAX - k ? INFINITY : -INFINITY;
-      g[j] = j < KMAX - k ? -1 : MX_NONE;
-    }
-  }
-  __device__ __forceinline__ bool beats(float cv, int cg) const { return mx_better(cv, cg, v[KMAX - 1], g[KMAX - 1]); }
-  __device__ __forceinline__ void insert(float cv, int cg) {
-    bool below = true;
-#pragma unroll
-    for (int j = KMAX - 1; j > 0; --j) {
-      const bool up = mx_better(cv, cg, v[j - 1], g[j - 1]);
-      v[j] = up ? v[j - 1] : (below ? cv : v[j]);
-      g[j] = up ? g[j - 1] : (below ? cg : g[j]);
-      below = up;
-    }
-    v[0] = below ? cv : v[0];
-    g[0] = below ? cg : g[0];
-  }
-};
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // Gallery grouped (or no group at all).  grid (query tiles, slices); wave w of slice s is unit 4 s + w and owns the items
 // unit * per_unit .. + per_unit - 1, i.e. a contiguous run of rows that starts on an item boundary.
 template <int MODE, int KMAX>        // MODE 0: top-k (k <= KMAX), 1: rank counts
-__global__ __launch_bounds__(64 * MX_WAVES) void mxs_gallery_kernel(MxArgs a) {
+__global__ __launch_bounds__(64 * SC_WAVES) void mxs_gallery_kernel(MxArgs a) {
   extern __shared__ __attribute__((aligned(16))) char mx_smem[];
   const int tid = threadIdx.x, lane = tid & 63, l32 = lane & 31, half = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int D = a.D, rpitch = D + 8, G = a.G;
   bf16* rbuf = (bf16*)mx_smem;
-  bf16* sbuf = rbuf + MX_RT * rpitch + wave * (MX_ST * MX_PITCH);
-  char* tail = mx_smem + (size_t)(MX_RT * rpitch + MX_WAVES * MX_ST * MX_PITCH) * sizeof(bf16);
-  const int q0 = blockIdx.x * MX_RT, slice = blockIdx.y;
-  long long it_lo = ((long long)slice * MX_WAVES + wave) * a.per_unit;
+  bf16* sbuf = rbuf + SC_TILE * rpitch + wave * (SC_TILE * SC_PITCH);
+  char* tail = mx_smem + (size_t)(SC_TILE * rpitch + SC_WAVES * SC_TILE * SC_PITCH) * sizeof(bf16);
+  const int q0 = blockIdx.x * SC_TILE, slice = blockIdx.y;
+  long long it_lo = ((long long)slice * SC_WAVES + wave) * a.per_unit;
   if (it_lo > a.ns) it_lo = a.ns;
   long long it_hi = it_lo + a.per_unit;
   if (it_hi > a.ns) it_hi = a.ns;
   const long long row_lo = it_lo * G, row_hi = it_hi * G;
 
-  MxList<KMAX> top;          // top-k: this lane's list for query lane & 31 (both lane halves keep the same list)
-  float* tv = nullptr;       // rank: target scores [32][n_t], target items, counts, in LDS
-  int *ti = nullptr, *cnt = nullptr;
-  if (MODE == 0) {
+  TopList<KMAX> top;         // top-k: this lane's list for query lane & 31 (both lane halves keep the same list)
+  ScRankLds rk = {};         // rank: target scores [32][n_t], target items, counts, in LDS
+  if (MODE == 0)
     top.init(a.k);
-  } else {
-    tv = (float*)tail;
-    ti = (int*)(tv + MX_RT * a.n_t);
-    cnt = ti + MX_RT * a.n_t;
-    for (int j = tid; j < MX_RT * a.n_t; j += 64 * MX_WAVES) {
-      const int q = q0 + j / a.n_t;
-      long long t = -1;
-      if (q < a.nr) t = a.target[(long long)q * a.n_t + (j % a.n_t)];
-      const bool ok = t >= 0 && t < a.ns;
-      ti[j] = ok ? (int)t : -1;
-      tv[j] = ok ? a.tscore[(long long)q * a.n_t + (j % a.n_t)] : 0.f;
-      cnt[j] = 0;
-    }
-  }
-  mx_load_resident(rbuf, a.R, a.r_rs, D, [&](int j) -> long long { return q0 + j < a.nr ? q0 + j : -1; }, tid, 64 * MX_WAVES);
+  else
+    rk = sc_rank_park(tail, a.target, a.tscore, q0, a.nr, a.ns, a.n_t, tid, 64 * SC_WAVES);
+  sc_load_resident(rbuf, a.R, a.r_rs, D, [&](int j) -> long long { return q0 + j < a.nr ? q0 + j : -1; }, tid, 64 * SC_WAVES);
 
-  const int nk = (D + MX_KC - 1) / MX_KC;
+  const int nk = (D + SC_KC - 1) / SC_KC;
   const int nsteps = a.tiles * nk;                     // the same for every wave: the barriers below are uniform
   const bf16* rrow = rbuf + l32 * rpitch;
-  MxStage st;
+  ScStage st;
   long long trow = row_lo;                             // first row of the tile in flight
   auto rows = [&](long long r0) { return [=](int j) -> long long { return r0 + j < row_hi ? r0 + j : -1; }; };
-  mx_stage_load(st, a.S, a.s_rs, 0, D, rows(trow), lane);
+  sc_stage_load(st, a.S, a.s_rs, 0, D, rows(trow), lane);
   f32x16 acc = {};
   float run = __builtin_nanf("");                      // max over the rows seen so far of the item in progress
   int item = (int)it_lo, pos = 0;                      // that item, and how many of its rows have been seen
   int kc = 0;
   for (int s = 0; s < nsteps; ++s) {
-    mx_stage_store(st, sbuf, lane);
+    sc_stage_store(st, sbuf, lane);
     __syncthreads();
     if (s + 1 < nsteps) {
       const bool wrap = kc + 1 == nk;
-      mx_stage_load(st, a.S, a.s_rs, wrap ? 0 : (kc + 1) * MX_KC, D, rows(wrap ? trow + MX_ST : trow), lane);
+      sc_stage_load(st, a.S, a.s_rs, wrap ? 0 : (kc + 1) * SC_KC, D, rows(wrap ? trow + SC_TILE : trow), lane);
     }
     if (kc == 0) acc = f32x16{};
-    const int kleft = D - kc * MX_KC;
-    mx_tile_mma(acc, sbuf, rrow + kc * MX_KC, (kleft < MX_KC ? kleft : MX_KC) >> 4, lane);
+    const int kleft = D - kc * SC_KC;
+    sc_tile_mma(acc, sbuf, rrow + kc * SC_KC, (kleft < SC_KC ? kleft : SC_KC) >> 4, lane);
     if (kc + 1 == nk) {
       // r[j] = score of tile row j: acc[i] of the lane with half h is row 8 (i / 4) + 4 h + i % 4
       float r[32];
@@ -236,20 +147,20 @@ __global__ __launch_bounds__(64 * MX_WAVES) void mxs_gallery_kernel(MxArgs a) {
         }
       } else {
         for (int t = 0; t < a.n_t; ++t) {
-          const int tg = ti[l32 * a.n_t + t];
-          const float ts = tv[l32 * a.n_t + t];
+          const int tg = rk.ti[l32 * a.n_t + t];
+          const float ts = rk.tv[l32 * a.n_t + t];
           int c = 0;
 #pragma unroll
           for (int j = 0; j < 32; ++j) {
             const int g = item + __builtin_popcount(ends & ((1u << j) - 1u));
-            c += ((ends >> j & 1u) && mx_better(r[j], g, ts, tg)) ? 1 : 0;
+            c += ((ends >> j & 1u) && sc_better(r[j], g, ts, tg)) ? 1 : 0;
           }
-          if (half == 0 && tg >= 0 && c > 0) atomicAdd(&cnt[l32 * a.n_t + t], c);
+          if (half == 0 && tg >= 0 && c > 0) atomicAdd(&rk.cnt[l32 * a.n_t + t], c);
         }
       }
       item += __builtin_popcount(ends);
       kc = 0;
-      trow += MX_ST;
+      trow += SC_TILE;
     } else {
       ++kc;
     }
@@ -260,7 +171,7 @@ __global__ __launch_bounds__(64 * MX_WAVES) void mxs_gallery_kernel(MxArgs a) {
     // 4 lists per query (one per wave; the two lane halves hold the same one) -> 1 through LDS ([wave][k][32])
     const int k = a.k;
     float* lv = (float*)tail;
-    int* li = (int*)(lv + MX_WAVES * k * 32);
+    int* li = (int*)(lv + SC_WAVES * k * 32);
     if (half == 0 && wave > 0) {
 #pragma unroll
       for (int j = 0; j < KMAX; ++j)
@@ -271,11 +182,11 @@ __global__ __launch_bounds__(64 * MX_WAVES) void mxs_gallery_kernel(MxArgs a) {
     }
     __syncthreads();
     if (wave == 0 && half == 0) {
-      for (int w = 1; w < MX_WAVES; ++w)
+      for (int w = 1; w < SC_WAVES; ++w)
         for (int j = 0; j < k; ++j) {
           const float cv = lv[(w * k + j) * 32 + l32];
           const int cg = li[(w * k + j) * 32 + l32];
-          if (cg == MX_NONE || !top.beats(cv, cg)) break;
+          if (cg == SC_NONE || !top.beats(cv, cg)) break;
           top.insert(cv, cg);
         }
       if (q0 + l32 < a.nr) {
@@ -289,10 +200,7 @@ __global__ __launch_bounds__(64 * MX_WAVES) void mxs_gallery_kernel(MxArgs a) {
       }
     }
   } else {
-    for (int j = tid; j < MX_RT * a.n_t; j += 64 * MX_WAVES) {
-      const int q = q0 + j / a.n_t;
-      if (q < a.nr && cnt[j] > 0) atomicAdd(&a.counts[(long long)q * a.n_t + (j % a.n_t)], cnt[j]);
-    }
+    sc_rank_flush(rk.cnt, a.counts, q0, a.nr, a.n_t, tid, 64 * SC_WAVES);
   }
 }
 
@@ -302,14 +210,14 @@ __global__ __launch_bounds__(64 * MX_WAVES) void mxs_gallery_kernel(MxArgs a) {
 //   2: queries grouped -- streamed item = query item blockIdx.x, resident row j = its target title j;  tscore[item][j].
 //   3: gallery grouped -- streamed item = target (blockIdx.y) of query blockIdx.x, resident row 0 = that query; tscore[q][t].
 template <int MODE>
-__global__ __launch_bounds__(64 * MX_WAVES) void mxs_item_kernel(MxArgs a, float* __restrict__ tscore_out) {
+__global__ __launch_bounds__(64 * SC_WAVES) void mxs_item_kernel(MxArgs a, float* __restrict__ tscore_out) {
   extern __shared__ __attribute__((aligned(16))) char mx_smem[];
   const int tid = threadIdx.x, lane = tid & 63, l32 = lane & 31, half = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nthreads = blockDim.x, nwaves = nthreads >> 6;
   const int D = a.D, rpitch = D + 8, G = a.G;
   bf16* rbuf = (bf16*)mx_smem;
-  bf16* sbuf = rbuf + MX_RT * rpitch + wave * (MX_ST * MX_PITCH);
-  const int n_tt = (a.nr + MX_RT - 1) / MX_RT;
+  bf16* sbuf = rbuf + SC_TILE * rpitch + wave * (SC_TILE * SC_PITCH);
+  const int n_tt = (a.nr + SC_TILE - 1) / SC_TILE;
 
   long long sit;             // the streamed item of this wave, < 0: none (the wave still takes part in the barriers)
   int tt_lo = 0, tt_hi = 1;
@@ -327,45 +235,45 @@ __global__ __launch_bounds__(64 * MX_WAVES) void mxs_item_kernel(MxArgs a, float
   const long long srow0 = sit * G;
 
   float lv = -INFINITY;      // MODE 0: slot `lane` of the item's sorted list (lanes 0 .. k - 1)
-  int lg = MX_NONE;
-  const int nk = (D + MX_KC - 1) / MX_KC;
+  int lg = SC_NONE;
+  const int nk = (D + SC_KC - 1) / SC_KC;
   const int nsteps = a.tiles * nk;
   const bf16* rrow = rbuf + l32 * rpitch;
-  auto rows = [&](int tl) { return [=](int j) -> long long { return sit >= 0 && tl * MX_ST + j < G ? srow0 + tl * MX_ST + j : -1; }; };
+  auto rows = [&](int tl) { return [=](int j) -> long long { return sit >= 0 && tl * SC_TILE + j < G ? srow0 + tl * SC_TILE + j : -1; }; };
 
   for (int tt = tt_lo; tt < tt_hi; ++tt) {
     // the last barrier of the previous tile's loop has passed: nobody reads the resident tile any more
     if (MODE <= 1) {
-      mx_load_resident(rbuf, a.R, a.r_rs, D, [&](int j) -> long long { return tt * MX_RT + j < a.nr ? (long long)tt * MX_RT + j : -1; },
+      sc_load_resident(rbuf, a.R, a.r_rs, D, [&](int j) -> long long { return tt * SC_TILE + j < a.nr ? (long long)tt * SC_TILE + j : -1; },
                        tid, nthreads);
     } else if (MODE == 2) {
-      mx_load_resident(rbuf, a.R, a.r_rs, D, [&](int j) -> long long {
+      sc_load_resident(rbuf, a.R, a.r_rs, D, [&](int j) -> long long {
         if (j >= a.n_t) return -1;
         const long long t = a.target[sit * a.n_t + j];
         return t >= 0 && t < a.nr ? t : -1;
       }, tid, nthreads);
     } else {
-      mx_load_resident(rbuf, a.R, a.r_rs, D, [&](int j) -> long long { return j == 0 ? (long long)blockIdx.x : -1; }, tid, nthreads);
+      sc_load_resident(rbuf, a.R, a.r_rs, D, [&](int j) -> long long { return j == 0 ? (long long)blockIdx.x : -1; }, tid, nthreads);
     }
-    MxStage st;
-    mx_stage_load(st, a.S, a.s_rs, 0, D, rows(0), lane);
+    ScStage st;
+    sc_stage_load(st, a.S, a.s_rs, 0, D, rows(0), lane);
     f32x16 acc = {};
     float run = __builtin_nanf("");
     int kc = 0, tl = 0;
     for (int s = 0; s < nsteps; ++s) {
-      mx_stage_store(st, sbuf, lane);
+      sc_stage_store(st, sbuf, lane);
       __syncthreads();                                 // stage and resident tile visible
       if (s + 1 < nsteps) {
         const bool wrap = kc + 1 == nk;
-        mx_stage_load(st, a.S, a.s_rs, wrap ? 0 : (kc + 1) * MX_KC, D, rows(wrap ? tl + 1 : tl), lane);
+        sc_stage_load(st, a.S, a.s_rs, wrap ? 0 : (kc + 1) * SC_KC, D, rows(wrap ? tl + 1 : tl), lane);
       }
       if (kc == 0) acc = f32x16{};
-      const int kleft = D - kc * MX_KC;
-      mx_tile_mma(acc, sbuf, rrow + kc * MX_KC, (kleft < MX_KC ? kleft : MX_KC) >> 4, lane);
+      const int kleft = D - kc * SC_KC;
+      sc_tile_mma(acc, sbuf, rrow + kc * SC_KC, (kleft < SC_KC ? kleft : SC_KC) >> 4, lane);
       if (kc + 1 == nk) {
 #pragma unroll
         for (int i = 0; i < 16; ++i)
-          if (tl * MX_ST + 8 * (i >> 2) + 4 * half + (i & 3) < G) run = mx_nanmax(run, acc[i]);
+          if (tl * SC_TILE + 8 * (i >> 2) + 4 * half + (i & 3) < G) run = mx_nanmax(run, acc[i]);
         kc = 0;
         ++tl;
       } else {
@@ -374,22 +282,22 @@ __global__ __launch_bounds__(64 * MX_WAVES) void mxs_item_kernel(MxArgs a, float
       __syncthreads();                                 // every wave is done with its stage and, at the end, the resident tile
     }
     const float score = mx_nanmax(run, __shfl_xor(run, 32, 64));    // s(item, resident row lane & 31)
-    const int title = tt * MX_RT + l32;
+    const int title = tt * SC_TILE + l32;
     const bool valid = half == 0 && sit >= 0 && title < a.nr;
     if (MODE == 0) {
       const float v = score * a.scale;
       float kv = __shfl(lv, a.k - 1, 64);
       int kg = __shfl(lg, a.k - 1, 64);
-      unsigned long long m = __ballot(valid && mx_better(v, title, kv, kg));
+      unsigned long long m = __ballot(valid && sc_better(v, title, kv, kg));
       while (m) {                                      // wave-uniform
         const int b = __builtin_ctzll(m);
         m &= m - 1;
         const float cv = __shfl(v, b, 64);
-        const int cg = tt * MX_RT + b;
-        if (mx_better(cv, cg, kv, kg)) {
+        const int cg = tt * SC_TILE + b;
+        if (sc_better(cv, cg, kv, kg)) {
           const float pv = __shfl_up(lv, 1, 64);
           const int pg = __shfl_up(lg, 1, 64);
-          const bool up = lane > 0 && mx_better(cv, cg, pv, pg), here = mx_better(cv, cg, lv, lg);
+          const bool up = lane > 0 && sc_better(cv, cg, pv, pg), here = sc_better(cv, cg, lv, lg);
           lv = up ? pv : (here ? cv : lv);
           lg = up ? pg : (here ? cg : lg);
           kv = __shfl(lv, a.k - 1, 64);
@@ -405,7 +313,7 @@ __global__ __launch_bounds__(64 * MX_WAVES) void mxs_item_kernel(MxArgs a, float
           ts = a.tscore[sit * a.n_t + t];
         }
         const bool ok = tg >= 0 && tg < a.nr;
-        const int c = __builtin_popcountll(__ballot(valid && ok && mx_better(score, title, ts, (int)tg)));
+        const int c = __builtin_popcountll(__ballot(valid && ok && sc_better(score, title, ts, (int)tg)));
         if (lane == 0 && ok && c > 0) atomicAdd(&a.counts[sit * a.n_t + t], c);
       }
     } else if (MODE == 2) {
@@ -419,92 +327,6 @@ __global__ __launch_bounds__(64 * MX_WAVES) void mxs_item_kernel(MxArgs a, float
     a.ws_val[o] = lv;
     a.ws_idx[o] = lg;
   }
-}
-
-// retrieval_search.hip's slice merge: one workgroup per query item, k rounds of "the best entry that the last one written beats"
-__global__ __launch_bounds__(256) void mxs_merge_kernel(const float* __restrict__ ws_val, const int* __restrict__ ws_idx,
-                                                        float* __restrict__ vals, int64_t* __restrict__ idx, int nq, int k, int slices) {
-  __shared__ float c_v[MX_MERGE_CACHE];
-  __shared__ int c_g[MX_MERGE_CACHE];
-  __shared__ float r_v[2][4];
-  __shared__ int r_g[2][4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int q = blockIdx.x;
-  const int n = slices * k;
-  const bool cached = n <= MX_MERGE_CACHE;
-  auto entry = [&](int e) { return ((long long)(e / k) * nq + q) * k + (e % k); };
-  if (cached)
-    for (int e = tid; e < n; e += 256) {
-      c_v[e] = ws_val[entry(e)];
-      c_g[e] = ws_idx[entry(e)];
-    }
-  __syncthreads();
-  float pv = INFINITY;
-  int pg = -1;
-  for (int j = 0; j < k; ++j) {
-    float bv = -INFINITY;
-    int bg = MX_NONE;
-    for (int e = tid; e < n; e += 256) {
-      const float v = cached ? c_v[e] : ws_val[entry(e)];
-      const int g = cached ? c_g[e] : ws_idx[entry(e)];
-      if (g != MX_NONE && mx_better(pv, pg, v, g) && mx_better(v, g, bv, bg)) {
-        bv = v;
-        bg = g;
-      }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const float ov = __shfl_xor(bv, off, 64);
-      const int og = __shfl_xor(bg, off, 64);
-      if (mx_better(ov, og, bv, bg)) {
-        bv = ov;
-        bg = og;
-      }
-    }
-    if (lane == 0) {
-      r_v[j & 1][wave] = bv;
-      r_g[j & 1][wave] = bg;
-    }
-    __syncthreads();
-    bv = r_v[j & 1][0];
-    bg = r_g[j & 1][0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w)
-      if (mx_better(r_v[j & 1][w], r_g[j & 1][w], bv, bg)) {
-        bv = r_v[j & 1][w];
-        bg = r_g[j & 1][w];
-      }
-    if (tid == 0) {
-      vals[(long long)q * k + j] = bg == MX_NONE ? -INFINITY : bv;
-      idx[(long long)q * k + j] = bg == MX_NONE ? -1 : bg;
-    }
-    if (bg == MX_NONE) {
-      for (int r = j + 1 + tid; r < k; r += 256) {
-        vals[(long long)q * k + r] = -INFINITY;
-        idx[(long long)q * k + r] = -1;
-      }
-      break;
-    }
-    pv = bv;
-    pg = bg;
-  }
-}
-
-// rank = the smallest count among the valid targets whose score is not NaN (a NaN item is ordered after everything: it is no
-// target to be found), ng when there is none
-__global__ __launch_bounds__(256) void mxs_rank_finish_kernel(const int64_t* __restrict__ target, const float* __restrict__ tscore,
-                                                              const int* __restrict__ counts, int* __restrict__ rank, int nq, int n_t,
-                                                              int ng) {
-  const int q = blockIdx.x * 256 + threadIdx.x;
-  if (q >= nq) return;
-  int best = ng;
-  for (int t = 0; t < n_t; ++t) {
-    const long long g = target[(long long)q * n_t + t];
-    const int c = counts[(long long)q * n_t + t];
-    const float s = tscore[(long long)q * n_t + t];
-    if (g >= 0 && g < ng && s == s && c < best) best = c;
-  }
-  rank[q] = best;
 }
 
 struct MxPlan {
@@ -521,44 +343,38 @@ int mx_plan(const mpv_maxsim_search_desc* d, MxPlan* p, const char* what, int to
   MPV_REQUIRE(d->nq > 0 && d->ng > 0 && d->nq <= 0x7fffffffll / d->q_group && d->ng <= 0x7fffffffll / d->g_group, MPV_E_SHAPE,
               "%s: bad shape nq=%lld x %d ng=%lld x %d (rows per side <= 2^31 - 1)", what, (long long)d->nq, d->q_group, (long long)d->ng,
               d->g_group);
-  MPV_REQUIRE(d->dim >= 32 && d->dim <= 1024 && d->dim % 32 == 0, MPV_E_SHAPE, "%s: dim (%d) must be a multiple of 32 in [32, 1024]",
-              what, d->dim);
-  MPV_REQUIRE(d->q_rs >= d->dim && d->g_rs >= d->dim && d->q_rs % 8 == 0 && d->g_rs % 8 == 0, MPV_E_ALIGN,
-              "%s: row strides (%lld, %lld) must be multiples of 8 and at least dim", what, (long long)d->q_rs, (long long)d->g_rs);
-  MPV_REQUIRE((((uintptr_t)d->queries | (uintptr_t)d->gallery) & 15) == 0, MPV_E_ALIGN, "%s: queries and gallery must be 16-byte aligned",
-              what);
-  MPV_REQUIRE(d->slices >= 0 && d->slices <= MX_MAX_SLICES, MPV_E_ARG, "%s: slices (%d) must be in [0, %d]", what, d->slices,
-              MX_MAX_SLICES);
+  const int rc = sc_check_desc(what, d->queries, d->gallery, d->dim, d->q_rs, d->g_rs, d->slices);
+  if (rc != MPV_OK) return rc;
   p->by_item = d->q_group > 1;
   long long s = d->slices;
   if (!p->by_item) {
     // units of work are waves: slices * 4 of them share the gallery's items.  0 = choose: 3 workgroups per CU over the 256 CUs,
     // at least 512 gallery rows per workgroup
-    const long long qtiles = (d->nq + MX_RT - 1) / MX_RT, rows = d->ng * d->g_group;
-    const long long max_s = (d->ng + MX_WAVES - 1) / MX_WAVES;
+    const long long qtiles = (d->nq + SC_TILE - 1) / SC_TILE, rows = d->ng * d->g_group;
+    const long long max_s = (d->ng + SC_WAVES - 1) / SC_WAVES;
     if (s == 0) {
       s = (768 + qtiles - 1) / qtiles;
       if (s > (rows + 511) / 512) s = (rows + 511) / 512;
       if (topk_k > 0 && s > 512) s = 512;
-      if (topk_k > 0 && s > MX_MERGE_CACHE / topk_k) s = MX_MERGE_CACHE / topk_k;
+      if (topk_k > 0 && s > SC_MERGE_CACHE / topk_k) s = SC_MERGE_CACHE / topk_k;
     }
     if (s > max_s) s = max_s;
     if (s < 1) s = 1;
-    const long long per = (d->ng + s * MX_WAVES - 1) / (s * MX_WAVES);
+    const long long per = (d->ng + s * SC_WAVES - 1) / (s * SC_WAVES);
     p->per_unit = (int)per;
-    p->slices = (int)((d->ng + per * MX_WAVES - 1) / (per * MX_WAVES));      // no empty slice
-    p->tiles = (int)((per * d->g_group + MX_ST - 1) / MX_ST);
+    p->slices = (int)((d->ng + per * SC_WAVES - 1) / (per * SC_WAVES));      // no empty slice
+    p->tiles = (int)((per * d->g_group + SC_TILE - 1) / SC_TILE);
   } else {
-    const long long groups = (d->nq + MX_WAVES - 1) / MX_WAVES, n_tt = (d->ng + MX_RT - 1) / MX_RT;
+    const long long groups = (d->nq + SC_WAVES - 1) / SC_WAVES, n_tt = (d->ng + SC_TILE - 1) / SC_TILE;
     if (s == 0) {
       s = (768 + groups - 1) / groups;
-      if (topk_k > 0 && s > MX_MERGE_CACHE / topk_k) s = MX_MERGE_CACHE / topk_k;
+      if (topk_k > 0 && s > SC_MERGE_CACHE / topk_k) s = SC_MERGE_CACHE / topk_k;
     }
     if (s > n_tt) s = n_tt;
     if (s < 1) s = 1;
     p->per_unit = (int)((n_tt + s - 1) / s);
     p->slices = (int)((n_tt + p->per_unit - 1) / p->per_unit);
-    p->tiles = (d->q_group + MX_ST - 1) / MX_ST;
+    p->tiles = (d->q_group + SC_TILE - 1) / SC_TILE;
   }
   return MPV_OK;
 }
@@ -580,109 +396,96 @@ MxArgs mx_args(const mpv_maxsim_search_desc* d, const MxPlan& p) {
   return a;
 }
 
-size_t mx_lds(int D, int waves, size_t tail) { return (size_t)(MX_RT * (D + 8) + waves * MX_ST * MX_PITCH) * sizeof(bf16) + tail; }
-size_t mx_align(size_t n) { return (n + 255) & ~(size_t)255; }
-
-template <class K>
-void mx_allow_lds(K kern, size_t lds) {
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-}
-
 }  // namespace
 
 extern "C" size_t mpv_maxsim_topk_workspace_size(const mpv_maxsim_search_desc* d) {
   MxPlan p;
-  if (!d || d->k < 1 || d->k > MX_MAX_K || mx_plan(d, &p, "mpv_maxsim_topk_workspace_size", d->k) != MPV_OK) return 0;
-  return 2 * mx_align((size_t)p.slices * (size_t)d->nq * d->k * 4);
+  if (!d || d->k < 1 || d->k > SC_MAX_K || mx_plan(d, &p, "mpv_maxsim_topk_workspace_size", d->k) != MPV_OK) return 0;
+  return sc_ws_bytes((size_t)p.slices * (size_t)d->nq * d->k);
 }
 
 extern "C" int mpv_maxsim_topk(const mpv_maxsim_search_desc* d, float* vals, int64_t* idx, void* workspace, size_t workspace_bytes,
                                hipStream_t stream) {
   MxPlan p;
   MPV_REQUIRE(d, MPV_E_ARG, "mpv_maxsim_topk: null descriptor");
-  MPV_REQUIRE(d->k >= 1 && d->k <= MX_MAX_K, MPV_E_ARG, "mpv_maxsim_topk: k (%d) must be in [1, %d]", d->k, MX_MAX_K);
-  const int rc = mx_plan(d, &p, "mpv_maxsim_topk", d->k);
+  MPV_REQUIRE(d->k >= 1 && d->k <= SC_MAX_K, MPV_E_ARG, "mpv_maxsim_topk: k (%d) must be in [1, %d]", d->k, SC_MAX_K);
+  int rc = mx_plan(d, &p, "mpv_maxsim_topk", d->k);
   if (rc != MPV_OK) return rc;
   MPV_REQUIRE(vals && idx && workspace, MPV_E_ARG, "mpv_maxsim_topk: null pointer");
-  const size_t half = mx_align((size_t)p.slices * (size_t)d->nq * d->k * 4);
-  MPV_REQUIRE(workspace_bytes >= 2 * half, MPV_E_ARG, "mpv_maxsim_topk: workspace of %zu bytes, %zu needed", workspace_bytes, 2 * half);
-  MPV_REQUIRE(((uintptr_t)workspace & 3) == 0, MPV_E_ALIGN, "mpv_maxsim_topk: workspace must be 4-byte aligned");
+  const size_t n = (size_t)p.slices * (size_t)d->nq * d->k;
+  rc = sc_ws_check("mpv_maxsim_topk", workspace, workspace_bytes, n);
+  if (rc != MPV_OK) return rc;
   MxArgs a = mx_args(d, p);
   a.k = d->k;
   a.scale = d->scale;
   a.ws_val = (float*)workspace;
-  a.ws_idx = (int*)((char*)workspace + half);
+  a.ws_idx = (int*)sc_ws_upper(workspace, n);
   if (p.by_item) {
-    const size_t lds = mx_lds(d->dim, MX_WAVES, 0);
-    mx_allow_lds(mxs_item_kernel<0>, lds);
-    hipLaunchKernelGGL(mxs_item_kernel<0>, dim3((unsigned)((d->nq + MX_WAVES - 1) / MX_WAVES), (unsigned)p.slices), dim3(64 * MX_WAVES),
+    const size_t lds = sc_stream_lds(d->dim, SC_WAVES, 0);
+    sc_allow_lds((const void*)mxs_item_kernel<0>, lds);
+    hipLaunchKernelGGL(mxs_item_kernel<0>, dim3((unsigned)((d->nq + SC_WAVES - 1) / SC_WAVES), (unsigned)p.slices), dim3(64 * SC_WAVES),
                        lds, stream, a, (float*)nullptr);
   } else {
-    const size_t lds = mx_lds(d->dim, MX_WAVES, (size_t)MX_WAVES * d->k * 32 * 8);
+    const size_t lds = sc_stream_lds(d->dim, SC_WAVES, (size_t)SC_WAVES * d->k * 32 * 8);
     auto kern = d->k <= 4 ? mxs_gallery_kernel<0, 4> : d->k <= 16 ? mxs_gallery_kernel<0, 16> : mxs_gallery_kernel<0, 32>;
-    mx_allow_lds(kern, lds);
-    hipLaunchKernelGGL(kern, dim3((unsigned)((d->nq + MX_RT - 1) / MX_RT), (unsigned)p.slices), dim3(64 * MX_WAVES), lds, stream, a);
+    sc_allow_lds((const void*)kern, lds);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((d->nq + SC_TILE - 1) / SC_TILE), (unsigned)p.slices), dim3(64 * SC_WAVES), lds, stream, a);
   }
-  int lrc = mpv_check_launch("mpv_maxsim_topk");
-  if (lrc != MPV_OK) return lrc;
-  hipLaunchKernelGGL(mxs_merge_kernel, dim3((unsigned)d->nq), dim3(256), 0, stream, a.ws_val, a.ws_idx, vals, idx, (int)d->nq, a.k,
-                     p.slices);
-  return mpv_check_launch("mpv_maxsim_topk (merge)");
+  rc = mpv_check_launch("mpv_maxsim_topk");
+  if (rc != MPV_OK) return rc;
+  return sc_merge_slices("mpv_maxsim_topk (merge)", a.ws_val, a.ws_idx, vals, idx, (int)d->nq, a.k, p.slices, stream);
 }
 
 extern "C" size_t mpv_maxsim_rank_workspace_size(const mpv_maxsim_search_desc* d, int n_targets) {
   MxPlan p;
-  if (!d || n_targets < 1 || n_targets > MX_MAX_T || mx_plan(d, &p, "mpv_maxsim_rank_workspace_size") != MPV_OK) return 0;
-  return 2 * mx_align((size_t)d->nq * n_targets * 4);
+  if (!d || n_targets < 1 || n_targets > SC_MAX_T || mx_plan(d, &p, "mpv_maxsim_rank_workspace_size") != MPV_OK) return 0;
+  return sc_ws_bytes((size_t)d->nq * n_targets);
 }
 
 extern "C" int mpv_maxsim_rank(const mpv_maxsim_search_desc* d, const int64_t* target, int n_targets, int32_t* rank, void* workspace,
                                size_t workspace_bytes, hipStream_t stream) {
   MxPlan p;
-  const int rc = mx_plan(d, &p, "mpv_maxsim_rank");
+  int rc = mx_plan(d, &p, "mpv_maxsim_rank");
   if (rc != MPV_OK) return rc;
   MPV_REQUIRE(target && rank && workspace, MPV_E_ARG, "mpv_maxsim_rank: null pointer");
-  MPV_REQUIRE(n_targets >= 1 && n_targets <= MX_MAX_T, MPV_E_ARG, "mpv_maxsim_rank: n_targets (%d) must be in [1, %d]", n_targets,
-              MX_MAX_T);
-  const size_t half = mx_align((size_t)d->nq * n_targets * 4);
-  MPV_REQUIRE(workspace_bytes >= 2 * half, MPV_E_ARG, "mpv_maxsim_rank: workspace of %zu bytes, %zu needed", workspace_bytes, 2 * half);
-  MPV_REQUIRE(((uintptr_t)workspace & 3) == 0, MPV_E_ALIGN, "mpv_maxsim_rank: workspace must be 4-byte aligned");
+  MPV_REQUIRE(n_targets >= 1 && n_targets <= SC_MAX_T, MPV_E_ARG, "mpv_maxsim_rank: n_targets (%d) must be in [1, %d]", n_targets,
+              SC_MAX_T);
+  const size_t n = (size_t)d->nq * n_targets;
+  rc = sc_ws_check("mpv_maxsim_rank", workspace, workspace_bytes, n);
+  if (rc != MPV_OK) return rc;
   MxArgs a = mx_args(d, p);
   a.n_t = n_targets;
   a.target = target;
   float* tscore = (float*)workspace;
   a.tscore = tscore;
-  a.counts = (int*)((char*)workspace + half);
-  if (hipMemsetAsync(a.counts, 0, (size_t)d->nq * n_targets * 4, stream) != hipSuccess) {
+  a.counts = (int*)sc_ws_upper(workspace, n);
+  if (hipMemsetAsync(a.counts, 0, n * 4, stream) != hipSuccess) {
     mpv_set_error("mpv_maxsim_rank: hipMemsetAsync failed");
     return MPV_E_HIP;
   }
-  const size_t lds_t = mx_lds(d->dim, 1, 0);
-  int lrc;
+  const size_t lds_t = sc_stream_lds(d->dim, 1, 0);
   if (p.by_item) {
-    mx_allow_lds(mxs_item_kernel<2>, lds_t);
+    sc_allow_lds((const void*)mxs_item_kernel<2>, lds_t);
     hipLaunchKernelGGL(mxs_item_kernel<2>, dim3((unsigned)d->nq), dim3(64), lds_t, stream, a, tscore);
-    lrc = mpv_check_launch("mpv_maxsim_rank (target scores)");
-    if (lrc != MPV_OK) return lrc;
-    const size_t lds = mx_lds(d->dim, MX_WAVES, 0);
-    mx_allow_lds(mxs_item_kernel<1>, lds);
-    hipLaunchKernelGGL(mxs_item_kernel<1>, dim3((unsigned)((d->nq + MX_WAVES - 1) / MX_WAVES), (unsigned)p.slices), dim3(64 * MX_WAVES),
+    rc = mpv_check_launch("mpv_maxsim_rank (target scores)");
+    if (rc != MPV_OK) return rc;
+    const size_t lds = sc_stream_lds(d->dim, SC_WAVES, 0);
+    sc_allow_lds((const void*)mxs_item_kernel<1>, lds);
+    hipLaunchKernelGGL(mxs_item_kernel<1>, dim3((unsigned)((d->nq + SC_WAVES - 1) / SC_WAVES), (unsigned)p.slices), dim3(64 * SC_WAVES),
                        lds, stream, a, (float*)nullptr);
   } else {
     MxArgs ta = a;                                    // one wave per (query, target): the target item's rows against that query
-    ta.tiles = (d->g_group + MX_ST - 1) / MX_ST;
-    mx_allow_lds(mxs_item_kernel<3>, lds_t);
+    ta.tiles = (d->g_group + SC_TILE - 1) / SC_TILE;
+    sc_allow_lds((const void*)mxs_item_kernel<3>, lds_t);
     hipLaunchKernelGGL(mxs_item_kernel<3>, dim3((unsigned)d->nq, (unsigned)n_targets), dim3(64), lds_t, stream, ta, tscore);
-    lrc = mpv_check_launch("mpv_maxsim_rank (target scores)");
-    if (lrc != MPV_OK) return lrc;
-    const size_t lds = mx_lds(d->dim, MX_WAVES, (size_t)MX_RT * n_targets * 12);
-    mx_allow_lds(mxs_gallery_kernel<1, 1>, lds);
-    hipLaunchKernelGGL((mxs_gallery_kernel<1, 1>), dim3((unsigned)((d->nq + MX_RT - 1) / MX_RT), (unsigned)p.slices), dim3(64 * MX_WAVES),
+    rc = mpv_check_launch("mpv_maxsim_rank (target scores)");
+    if (rc != MPV_OK) return rc;
+    const size_t lds = sc_stream_lds(d->dim, SC_WAVES, (size_t)SC_TILE * n_targets * 12);
+    sc_allow_lds((const void*)mxs_gallery_kernel<1, 1>, lds);
+    hipLaunchKernelGGL((mxs_gallery_kernel<1, 1>), dim3((unsigned)((d->nq + SC_TILE - 1) / SC_TILE), (unsigned)p.slices), dim3(64 * SC_WAVES),
                        lds, stream, a);
   }
-  lrc = mpv_check_launch("mpv_maxsim_rank");
-  if (lrc != MPV_OK) return lrc;
-  hipLaunchKernelGGL(mxs_rank_finish_kernel, dim3((unsigned)((d->nq + 255) / 256)), dim3(256), 0, stream, target, tscore, a.counts, rank,
-                     (int)d->nq, n_targets, (int)d->ng);
-  return mpv_check_launch("mpv_maxsim_rank (finish)");
+  rc = mpv_check_launch("mpv_maxsim_rank");
+  if (rc != MPV_OK) return rc;
+  return sc_rank_finish("mpv_maxsim_rank (finish)", target, tscore, a.counts, rank, (int)d->nq, n_targets, (int)d->ng, stream);
 }

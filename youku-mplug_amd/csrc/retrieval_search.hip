@@ -9,7 +9,7 @@
 // each wave copies its 32 rows x 128 k chunk with coalesced 16-byte loads into registers one step ahead (the loads of step
 // s + 1 are in flight while step s computes), parks it in its own LDS stage (272-byte pitch: conflict-free ds_read_b128) and
 // runs v_mfma_f32_32x32x16_bf16 with A = gallery rows, B = queries: a lane ends up with 16 scores of ONE query (lane & 31).
-//   top-k: every lane keeps a sorted list of the k best (value, index) pairs it has seen, in registers (RsList: unrolled and
+//   top-k: every lane keeps a sorted list of the k best (value, index) pairs it has seen, in registers (TopList: unrolled and
 //     predicated, no dynamic indexing).  A score only touches the list when it beats the k-th entry: expected k ln(N / k)
 //     insertions per list over a stream of N rows, 3 VALU ops per slot each.  The 8 lists of a query (4 waves x 2 lane
 //     halves) are merged at the end, the slice's list goes to the workspace and the merge kernel (one workgroup per query, k
@@ -20,70 +20,22 @@
 // order and the result cannot depend on the slice count, the wave that saw a row, or the order of the merges.  NaN scores
 // beat nothing and are never returned.
 //
+// The tile walk (sc_stage_*, sc_tile_mma, sc_load_resident), the order rule, TopList and the rank bookkeeping are defined once,
+// in search_common.h, for this file and maxsim_search.hip; the common host checks are in search_common.hip.  The slice merge
+// (sim_topk_merge_kernel) and the rank finish (sim_rank_finish_kernel) below serve both files through sc_merge_slices /
+// sc_rank_finish.
+//
 // Self-consistency of s(g) > s(t) in mpv_sim_rank: the target scores are produced by sim_target_kernel, which stages the 32
-// target rows of a query tile through the same rs_stage_* / rs_tile_mma functions as the stream -- same operand roles, same
-// k order (chunks of 128 ascending, 16 per MFMA), same instruction, accumulator zeroed at the same point -- and reads the
-// diagonal of the 32 x 32 tile.  An MFMA output element is a function of its A row, its B column and the accumulator only,
-// so the score of target row t is bit-identical to the score the stream computes when it meets row t.
-#include "mpv_common.h"
+// target rows of a query tile through the stream's own sc_stage_* / sc_tile_mma -- same operand roles, same k order (chunks
+// of 128 ascending, 16 per MFMA), same instruction, accumulator zeroed at the same point -- and reads the diagonal of the
+// 32 x 32 tile.  An MFMA output element is a function of its A row, its B column and the accumulator only, so the score of
+// target row t is bit-identical to the score the stream computes when it meets row t.
+#include "search_common.h"
 #include "../../include/mpv.h"
 
 namespace {
 
-constexpr int RS_QT = 32;               // queries per workgroup
-constexpr int RS_WAVES = 4;
-constexpr int RS_GT = 32;               // gallery rows per wave and step
-constexpr int RS_SUPER = RS_WAVES * RS_GT;
-constexpr int RS_KC = 128;              // k per staged chunk
-constexpr int RS_PITCH = RS_KC + 8;     // bf16 elements: 272 bytes, rows 4 banks apart
-constexpr int RS_UNITS = RS_GT * RS_KC / 8 / 64;   // 16-byte units per lane and chunk (8)
-constexpr int RS_NONE = 0x7fffffff;     // index of an empty list entry (ng <= 2^31 - 1, so no row has it)
-constexpr int RS_MAX_K = 32, RS_MAX_T = 32, RS_MAX_SLICES = 4096;
-
-__device__ __forceinline__ bool rs_better(float v, int g, float bv, int bg) { return v > bv || (v == bv && g < bg); }
-
-struct RsStage {
-  bf16x8 r[RS_UNITS];
-};
-
-// 32 rows x 128 k of the gallery -> registers.  row_of(j) is the gallery row staged as tile row j, or < 0 for a row of zeros.
-template <class RowFn>
-__device__ __forceinline__ void rs_stage_load(RsStage& st, const bf16* __restrict__ G, long long g_rs, int k0, int D, RowFn row_of,
-                                              int lane) {
-#pragma unroll
-  for (int j = 0; j < RS_UNITS; ++j) {
-    const int u = j * 64 + lane, row = u >> 4, k = k0 + (u & 15) * 8;
-    const long long gr = row_of(row);
-    bf16x8 v = {};
-    if (gr >= 0 && k < D) v = *(const bf16x8*)(G + gr * g_rs + k);
-    st.r[j] = v;
-  }
-}
-__device__ __forceinline__ void rs_stage_store(const RsStage& st, bf16* buf, int lane) {
-#pragma unroll
-  for (int j = 0; j < RS_UNITS; ++j) {
-    const int u = j * 64 + lane;
-    *(bf16x8*)(buf + (u >> 4) * RS_PITCH + (u & 15) * 8) = st.r[j];
-  }
-}
-// acc[i] += <staged row 8 (i / 4) + 4 (lane / 32) + i % 4, query lane & 31> over `ksteps` 16-wide steps
-__device__ __forceinline__ void rs_tile_mma(f32x16& acc, const bf16* gbuf, const bf16* qrow, int ksteps, int lane) {
-  const bf16* ap = gbuf + (lane & 31) * RS_PITCH + 8 * (lane >> 5);
-  const bf16* bp = qrow + 8 * (lane >> 5);
-  for (int kk = 0; kk < ksteps; ++kk)
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const bf16x8*)(ap + kk * 16), *(const bf16x8*)(bp + kk * 16), acc, 0, 0, 0);
-}
-// the query tile (rows q0 .. q0 + 31, zeros beyond nq) -> LDS at pitch D + 8
-__device__ __forceinline__ void rs_load_queries(bf16* qbuf, const bf16* __restrict__ Q, long long q_rs, int q0, int nq, int D,
-                                                int tid, int nthreads) {
-  const int upr = D >> 3;
-  for (int u = tid; u < RS_QT * upr; u += nthreads) {
-    const int row = u / upr, c = (u - row * upr) * 8;
-    bf16x8 v = {};
-    if (q0 + row < nq) v = *(const bf16x8*)(Q + (long long)(q0 + row) * q_rs + c);
-    *(bf16x8*)(qbuf + row * (D + 8) + c) = v;
-  }
-}
+constexpr int RS_SUPER = SC_WAVES * SC_TILE;      // gallery rows per workgroup and step
 
 struct RsArgs {
   const bf16 *Q, *G;
@@ -98,92 +50,48 @@ struct RsArgs {
   int* counts;               // rank: [nq][n_t], zeroed
 };
 
-// Sorted (descending) list of the k <= KMAX best (value, row) pairs seen by one lane, in registers.  The list sits in the LAST k
-// slots, so the k-th entry -- what a candidate has to beat -- is always slot KMAX - 1; the slots before it hold (+inf, -1), which
-// nothing beats.  Every loop is unrolled over KMAX with static indices (no scratch); an insertion is 3 VALU ops per slot.
-template <int KMAX>
-struct RsList {
-  float v[KMAX];
-  int g[KMAX];
-  __device__ __forceinline__ void init(int k) {
-#pragma unroll
-    for (int j = 0; j < KMAX; ++j) {
-      v[j] = j < KMAX - k ? INFINITY : -INFINITY;
-      g[j] = j < KMAX - k ? -1 : RS_NONE;
-    }
-  }
-  __device__ __forceinline__ bool beats(float cv, int cg) const { return rs_better(cv, cg, v[KMAX - 1], g[KMAX - 1]); }
-  // precondition: beats(cv, cg).  Slot j takes its upper neighbour when the candidate belongs above that, the candidate when
-  // it belongs exactly here, and stays otherwise; walking up the list, "candidate beats slot j" is the previous step's `up`.
-  __device__ __forceinline__ void insert(float cv, int cg) {
-    bool below = true;
-#pragma unroll
-    for (int j = KMAX - 1; j > 0; --j) {
-      const bool up = rs_better(cv, cg, v[j - 1], g[j - 1]);
-      v[j] = up ? v[j - 1] : (below ? cv : v[j]);
-      g[j] = up ? g[j - 1] : (below ? cg : g[j]);
-      below = up;
-    }
-    v[0] = below ? cv : v[0];
-    g[0] = below ? cg : g[0];
-  }
-};
-
 template <int MODE, int KMAX>        // MODE 0: top-k (k <= KMAX), 1: rank counts
-__global__ __launch_bounds__(64 * RS_WAVES) void sim_stream_kernel(RsArgs a) {
+__global__ __launch_bounds__(64 * SC_WAVES) void sim_stream_kernel(RsArgs a) {
   extern __shared__ __attribute__((aligned(16))) char rs_smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l32 = lane & 31, half = lane >> 5;
   const int D = a.D, qpitch = D + 8;
   bf16* qbuf = (bf16*)rs_smem;
-  bf16* gbuf = qbuf + RS_QT * qpitch + wave * (RS_GT * RS_PITCH);
-  char* tail = rs_smem + (size_t)(RS_QT * qpitch + RS_WAVES * RS_GT * RS_PITCH) * sizeof(bf16);
-  const int q0 = blockIdx.y * RS_QT, slice = blockIdx.x;
+  bf16* gbuf = qbuf + SC_TILE * qpitch + wave * (SC_TILE * SC_PITCH);
+  char* tail = rs_smem + (size_t)(SC_TILE * qpitch + SC_WAVES * SC_TILE * SC_PITCH) * sizeof(bf16);
+  const int q0 = blockIdx.y * SC_TILE, slice = blockIdx.x;
   const long long s_row0 = (long long)slice * a.per_slice * RS_SUPER;
   long long s_end = s_row0 + (long long)a.per_slice * RS_SUPER;
   if (s_end > a.ng) s_end = a.ng;
   const unsigned uend = (unsigned)s_end;
   const int n_super = s_row0 < s_end ? (int)((s_end - s_row0 + RS_SUPER - 1) / RS_SUPER) : 0;
 
-  RsList<KMAX> top;          // top-k: this lane's list (its query is lane & 31; lanes l and l ^ 32 see different rows of it)
-  float* tv = nullptr;       // rank: target scores [32][n_t], target rows, counts, in LDS
-  int *ti = nullptr, *cnt = nullptr;
-  if (MODE == 0) {
+  TopList<KMAX> top;         // top-k: this lane's list (its query is lane & 31; lanes l and l ^ 32 see different rows of it)
+  ScRankLds rk = {};         // rank: target scores [32][n_t], target rows, counts, in LDS
+  if (MODE == 0)
     top.init(a.k);
-  } else {
-    tv = (float*)tail;
-    ti = (int*)(tv + RS_QT * a.n_t);
-    cnt = ti + RS_QT * a.n_t;
-    for (int j = tid; j < RS_QT * a.n_t; j += 64 * RS_WAVES) {
-      const int q = q0 + j / a.n_t;
-      long long t = -1;
-      if (q < a.nq) t = a.target[(long long)q * a.n_t + (j % a.n_t)];
-      const bool ok = t >= 0 && t < a.ng;
-      ti[j] = ok ? (int)t : -1;
-      tv[j] = ok ? a.tscore[(long long)q * a.n_t + (j % a.n_t)] : 0.f;
-      cnt[j] = 0;
-    }
-  }
-  rs_load_queries(qbuf, a.Q, a.q_rs, q0, a.nq, D, tid, 64 * RS_WAVES);
+  else
+    rk = sc_rank_park(tail, a.target, a.tscore, q0, a.nq, a.ng, a.n_t, tid, 64 * SC_WAVES);
+  sc_load_resident(qbuf, a.Q, a.q_rs, D, [&](int j) -> long long { return q0 + j < a.nq ? q0 + j : -1; }, tid, 64 * SC_WAVES);
 
-  const int nk = (D + RS_KC - 1) / RS_KC;
+  const int nk = (D + SC_KC - 1) / SC_KC;
   const int nsteps = n_super * nk;
   const bf16* qrow = qbuf + l32 * qpitch;
-  RsStage st;
-  long long row0 = s_row0 + wave * RS_GT;
+  ScStage st;
+  long long row0 = s_row0 + wave * SC_TILE;
   auto rows = [&](long long r0) { return [=](int j) -> long long { return r0 + j < s_end ? r0 + j : -1; }; };
-  if (nsteps > 0) rs_stage_load(st, a.G, a.g_rs, 0, D, rows(row0), lane);
+  if (nsteps > 0) sc_stage_load(st, a.G, a.g_rs, 0, D, rows(row0), lane);
   f32x16 acc = {};
   int kc = 0;
   for (int s = 0; s < nsteps; ++s) {
-    rs_stage_store(st, gbuf, lane);
+    sc_stage_store(st, gbuf, lane);
     __syncthreads();                                 // stage (and, first time round, queries / targets) visible
     if (s + 1 < nsteps) {                            // next step's rows fly while this one computes
       const bool wrap = kc + 1 == nk;
-      rs_stage_load(st, a.G, a.g_rs, wrap ? 0 : (kc + 1) * RS_KC, D, rows(wrap ? row0 + RS_SUPER : row0), lane);
+      sc_stage_load(st, a.G, a.g_rs, wrap ? 0 : (kc + 1) * SC_KC, D, rows(wrap ? row0 + RS_SUPER : row0), lane);
     }
     if (kc == 0) acc = f32x16{};
-    const int kleft = D - kc * RS_KC;
-    rs_tile_mma(acc, gbuf, qrow + kc * RS_KC, (kleft < RS_KC ? kleft : RS_KC) >> 4, lane);
+    const int kleft = D - kc * SC_KC;
+    sc_tile_mma(acc, gbuf, qrow + kc * SC_KC, (kleft < SC_KC ? kleft : SC_KC) >> 4, lane);
     if (kc + 1 == nk) {
       // acc[i] is gallery row base + 8 (i / 4) + i % 4.  Unsigned: the last super-tile of a gallery of 2^31 - 1 rows runs
       // past INT_MAX; such rows fail g < uend and are never used as an index.
@@ -208,15 +116,15 @@ __global__ __launch_bounds__(64 * RS_WAVES) void sim_stream_kernel(RsArgs a) {
         }
       } else {
         for (int t = 0; t < a.n_t; ++t) {
-          const int tg = ti[l32 * a.n_t + t];
-          const float ts = tv[l32 * a.n_t + t];
+          const int tg = rk.ti[l32 * a.n_t + t];
+          const float ts = rk.tv[l32 * a.n_t + t];
           int c = 0;
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
             const unsigned g = base + 8 * (i >> 2) + (i & 3);
-            c += (g < uend && rs_better(acc[i], (int)g, ts, tg)) ? 1 : 0;
+            c += (g < uend && sc_better(acc[i], (int)g, ts, tg)) ? 1 : 0;
           }
-          if (tg >= 0 && c > 0) atomicAdd(&cnt[l32 * a.n_t + t], c);
+          if (tg >= 0 && c > 0) atomicAdd(&rk.cnt[l32 * a.n_t + t], c);
         }
       }
       kc = 0;
@@ -230,10 +138,10 @@ __global__ __launch_bounds__(64 * RS_WAVES) void sim_stream_kernel(RsArgs a) {
   if (MODE == 0) {
     // 8 lists per query (4 waves x 2 halves) -> 1, through LDS ([wave][k][32]) in two rounds: the upper half of each wave hands
     // its list to the lower half, then waves 1-3 hand theirs to wave 0.  A sorted list stops contributing at its first entry
-    // that fails.
+    // that fails.  (The write-out loops stay in the kernel body: search_common.h, TopList.)
     const int k = a.k;
     float* lv = (float*)tail;
-    int* li = (int*)(lv + RS_WAVES * k * 32);
+    int* li = (int*)(lv + SC_WAVES * k * 32);
     auto put = [&]() {
 #pragma unroll
       for (int j = 0; j < KMAX; ++j)
@@ -246,7 +154,7 @@ __global__ __launch_bounds__(64 * RS_WAVES) void sim_stream_kernel(RsArgs a) {
       for (int j = 0; j < k; ++j) {
         const float cv = lv[(w * k + j) * 32 + l32];
         const int cg = li[(w * k + j) * 32 + l32];
-        if (cg == RS_NONE || !top.beats(cv, cg)) break;
+        if (cg == SC_NONE || !top.beats(cv, cg)) break;
         top.insert(cv, cg);
       }
     };
@@ -257,7 +165,7 @@ __global__ __launch_bounds__(64 * RS_WAVES) void sim_stream_kernel(RsArgs a) {
     if (half == 0 && wave > 0) put();
     __syncthreads();
     if (wave == 0 && half == 0) {
-      for (int w = 1; w < RS_WAVES; ++w) absorb(w);
+      for (int w = 1; w < SC_WAVES; ++w) absorb(w);
       if (q0 + l32 < a.nq) {
         const long long o = ((long long)slice * a.nq + q0 + l32) * k;
 #pragma unroll
@@ -269,29 +177,58 @@ __global__ __launch_bounds__(64 * RS_WAVES) void sim_stream_kernel(RsArgs a) {
       }
     }
   } else {
-    for (int j = tid; j < RS_QT * a.n_t; j += 64 * RS_WAVES) {
-      const int q = q0 + j / a.n_t;
-      if (q < a.nq && cnt[j] > 0) atomicAdd(&a.counts[(long long)q * a.n_t + (j % a.n_t)], cnt[j]);
-    }
+    sc_rank_flush(rk.cnt, a.counts, q0, a.nq, a.n_t, tid, 64 * SC_WAVES);
   }
 }
 
-// One workgroup per query: k rounds; round j writes the best workspace entry that the entry written in round j - 1 beats.  The
-// slices * k entries are copied to LDS first when they fit (RS_MERGE_CACHE; the host's slice choice keeps them fitting), so a
-// round is a scan of LDS plus a workgroup reduction by the order rule -- the same answer whichever thread holds which entry.
-constexpr int RS_MERGE_CACHE = 6144;
+// Scores of the target rows, through the stream's staging and MFMA functions: one wave = 32 queries x target slot t, tile row j
+// is the target row of query j, the score is the tile's diagonal.
+__global__ __launch_bounds__(64) void sim_target_kernel(RsArgs a, float* __restrict__ tscore) {
+  extern __shared__ __attribute__((aligned(16))) char rs_smem[];
+  const int lane = threadIdx.x, l32 = lane & 31, half = lane >> 5;
+  const int D = a.D, qpitch = D + 8;
+  bf16* qbuf = (bf16*)rs_smem;
+  bf16* gbuf = qbuf + SC_TILE * qpitch;
+  const int q0 = blockIdx.y * SC_TILE, t = blockIdx.x;
+  sc_load_resident(qbuf, a.Q, a.q_rs, D, [&](int j) -> long long { return q0 + j < a.nq ? q0 + j : -1; }, lane, 64);
+  auto rows = [&](int j) -> long long {
+    if (q0 + j >= a.nq) return -1;
+    const long long g = a.target[(long long)(q0 + j) * a.n_t + t];
+    return g >= 0 && g < a.ng ? g : -1;
+  };
+  const int nk = (D + SC_KC - 1) / SC_KC;
+  f32x16 acc = {};
+  ScStage st;
+  for (int kc = 0; kc < nk; ++kc) {
+    sc_stage_load(st, a.G, a.g_rs, kc * SC_KC, D, rows, lane);
+    __syncthreads();                                 // the previous chunk has been consumed
+    sc_stage_store(st, gbuf, lane);
+    __syncthreads();
+    const int kleft = D - kc * SC_KC;
+    sc_tile_mma(acc, gbuf, qbuf + l32 * qpitch + kc * SC_KC, (kleft < SC_KC ? kleft : SC_KC) >> 4, lane);
+  }
+  // tile row l32 sits in acc[4 (l32 / 8) + l32 % 4] of the lane with half == (l32 / 4) % 2
+  const int want = 4 * (l32 >> 3) + (l32 & 3);
+  float v = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) v = i == want ? acc[i] : v;
+  if (half == ((l32 >> 2) & 1) && q0 + l32 < a.nq) tscore[(long long)(q0 + l32) * a.n_t + t] = v;
+}
 
+// One workgroup per query: k rounds; round j writes the best workspace entry that the entry written in round j - 1 beats.  The
+// slices * k entries are copied to LDS first when they fit (SC_MERGE_CACHE; the host's slice choice keeps them fitting), so a
+// round is a scan of LDS plus a workgroup reduction by the order rule -- the same answer whichever thread holds which entry.
 __global__ __launch_bounds__(256) void sim_topk_merge_kernel(const float* __restrict__ ws_val, const int* __restrict__ ws_idx,
                                                              float* __restrict__ vals, int64_t* __restrict__ idx, int nq, int k,
                                                              int slices) {
-  __shared__ float c_v[RS_MERGE_CACHE];
-  __shared__ int c_g[RS_MERGE_CACHE];
+  __shared__ float c_v[SC_MERGE_CACHE];
+  __shared__ int c_g[SC_MERGE_CACHE];
   __shared__ float r_v[2][4];
   __shared__ int r_g[2][4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int q = blockIdx.x;
   const int n = slices * k;
-  const bool cached = n <= RS_MERGE_CACHE;
+  const bool cached = n <= SC_MERGE_CACHE;
   auto entry = [&](int e) { return ((long long)(e / k) * nq + q) * k + (e % k); };
   if (cached)
     for (int e = tid; e < n; e += 256) {
@@ -303,11 +240,11 @@ __global__ __launch_bounds__(256) void sim_topk_merge_kernel(const float* __rest
   int pg = -1;
   for (int j = 0; j < k; ++j) {
     float bv = -INFINITY;
-    int bg = RS_NONE;
+    int bg = SC_NONE;
     for (int e = tid; e < n; e += 256) {
       const float v = cached ? c_v[e] : ws_val[entry(e)];
       const int g = cached ? c_g[e] : ws_idx[entry(e)];
-      if (g != RS_NONE && rs_better(pv, pg, v, g) && rs_better(v, g, bv, bg)) {
+      if (g != SC_NONE && sc_better(pv, pg, v, g) && sc_better(v, g, bv, bg)) {
         bv = v;
         bg = g;
       }
@@ -316,7 +253,7 @@ __global__ __launch_bounds__(256) void sim_topk_merge_kernel(const float* __rest
     for (int off = 32; off > 0; off >>= 1) {
       const float ov = __shfl_xor(bv, off, 64);
       const int og = __shfl_xor(bg, off, 64);
-      if (rs_better(ov, og, bv, bg)) {
+      if (sc_better(ov, og, bv, bg)) {
         bv = ov;
         bg = og;
       }
@@ -330,15 +267,15 @@ __global__ __launch_bounds__(256) void sim_topk_merge_kernel(const float* __rest
     bg = r_g[j & 1][0];
 #pragma unroll
     for (int w = 1; w < 4; ++w)
-      if (rs_better(r_v[j & 1][w], r_g[j & 1][w], bv, bg)) {
+      if (sc_better(r_v[j & 1][w], r_g[j & 1][w], bv, bg)) {
         bv = r_v[j & 1][w];
         bg = r_g[j & 1][w];
       }
     if (tid == 0) {
-      vals[(long long)q * k + j] = bg == RS_NONE ? -INFINITY : bv;
-      idx[(long long)q * k + j] = bg == RS_NONE ? -1 : bg;
+      vals[(long long)q * k + j] = bg == SC_NONE ? -INFINITY : bv;
+      idx[(long long)q * k + j] = bg == SC_NONE ? -1 : bg;
     }
-    if (bg == RS_NONE) {                              // fewer than k rows in the gallery: the rest is filler (uniform exit)
+    if (bg == SC_NONE) {                              // fewer than k rows in the gallery: the rest is filler (uniform exit)
       for (int r = j + 1 + tid; r < k; r += 256) {
         vals[(long long)q * k + r] = -INFINITY;
         idx[(long long)q * k + r] = -1;
@@ -350,49 +287,17 @@ __global__ __launch_bounds__(256) void sim_topk_merge_kernel(const float* __rest
   }
 }
 
-// Scores of the target rows, through the stream's staging and MFMA functions: one wave = 32 queries x target slot t, tile row j
-// is the target row of query j, the score is the tile's diagonal.
-__global__ __launch_bounds__(64) void sim_target_kernel(RsArgs a, float* __restrict__ tscore) {
-  extern __shared__ __attribute__((aligned(16))) char rs_smem[];
-  const int lane = threadIdx.x, l32 = lane & 31, half = lane >> 5;
-  const int D = a.D, qpitch = D + 8;
-  bf16* qbuf = (bf16*)rs_smem;
-  bf16* gbuf = qbuf + RS_QT * qpitch;
-  const int q0 = blockIdx.y * RS_QT, t = blockIdx.x;
-  rs_load_queries(qbuf, a.Q, a.q_rs, q0, a.nq, D, lane, 64);
-  auto rows = [&](int j) -> long long {
-    if (q0 + j >= a.nq) return -1;
-    const long long g = a.target[(long long)(q0 + j) * a.n_t + t];
-    return g >= 0 && g < a.ng ? g : -1;
-  };
-  const int nk = (D + RS_KC - 1) / RS_KC;
-  f32x16 acc = {};
-  RsStage st;
-  for (int kc = 0; kc < nk; ++kc) {
-    rs_stage_load(st, a.G, a.g_rs, kc * RS_KC, D, rows, lane);
-    __syncthreads();                                 // the previous chunk has been consumed
-    rs_stage_store(st, gbuf, lane);
-    __syncthreads();
-    const int kleft = D - kc * RS_KC;
-    rs_tile_mma(acc, gbuf, qbuf + l32 * qpitch + kc * RS_KC, (kleft < RS_KC ? kleft : RS_KC) >> 4, lane);
-  }
-  // tile row l32 sits in acc[4 (l32 / 8) + l32 % 4] of the lane with half == (l32 / 4) % 2
-  const int want = 4 * (l32 >> 3) + (l32 & 3);
-  float v = 0.f;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) v = i == want ? acc[i] : v;
-  if (half == ((l32 >> 2) & 1) && q0 + l32 < a.nq) tscore[(long long)(q0 + l32) * a.n_t + t] = v;
-}
-
-__global__ __launch_bounds__(256) void sim_rank_finish_kernel(const int64_t* __restrict__ target, const int* __restrict__ counts,
-                                                              int* __restrict__ rank, int nq, int n_t, int ng) {
+__global__ __launch_bounds__(256) void sim_rank_finish_kernel(const int64_t* __restrict__ target, const float* __restrict__ tscore,
+                                                              const int* __restrict__ counts, int* __restrict__ rank, int nq, int n_t,
+                                                              int ng) {
   const int q = blockIdx.x * 256 + threadIdx.x;
   if (q >= nq) return;
   int best = ng;                                      // no target: worse than every real rank
   for (int t = 0; t < n_t; ++t) {
     const long long g = target[(long long)q * n_t + t];
     const int c = counts[(long long)q * n_t + t];
-    if (g >= 0 && g < ng && c < best) best = c;
+    const float s = tscore ? tscore[(long long)q * n_t + t] : 0.f;
+    if (g >= 0 && g < ng && s == s && c < best) best = c;      // a NaN item is ordered after everything: no target to be found
   }
   rank[q] = best;
 }
@@ -403,27 +308,21 @@ struct RsPlan {
 
 int rs_plan(const mpv_sim_search_desc* d, RsPlan* p, const char* what, int topk_k = 0) {
   MPV_REQUIRE(d && d->queries && d->gallery, MPV_E_ARG, "%s: null pointer", what);
-  MPV_REQUIRE(d->nq > 0 && d->ng > 0 && d->nq <= 65535ll * RS_QT /* grid.y */ && d->ng <= 0x7fffffffll, MPV_E_SHAPE,
+  MPV_REQUIRE(d->nq > 0 && d->ng > 0 && d->nq <= 65535ll * SC_TILE /* grid.y */ && d->ng <= 0x7fffffffll, MPV_E_SHAPE,
               "%s: bad shape nq=%lld ng=%lld", what, (long long)d->nq, (long long)d->ng);
-  MPV_REQUIRE(d->dim >= 32 && d->dim <= 1024 && d->dim % 32 == 0, MPV_E_SHAPE, "%s: dim (%d) must be a multiple of 32 in [32, 1024]",
-              what, d->dim);
-  MPV_REQUIRE(d->q_rs >= d->dim && d->g_rs >= d->dim && d->q_rs % 8 == 0 && d->g_rs % 8 == 0, MPV_E_ALIGN,
-              "%s: row strides (%lld, %lld) must be multiples of 8 and at least dim", what, (long long)d->q_rs, (long long)d->g_rs);
-  MPV_REQUIRE((((uintptr_t)d->queries | (uintptr_t)d->gallery) & 15) == 0, MPV_E_ALIGN, "%s: queries and gallery must be 16-byte aligned",
-              what);
-  MPV_REQUIRE(d->slices >= 0 && d->slices <= RS_MAX_SLICES, MPV_E_ARG, "%s: slices (%d) must be in [0, %d]", what, d->slices,
-              RS_MAX_SLICES);
+  const int rc = sc_check_desc(what, d->queries, d->gallery, d->dim, d->q_rs, d->g_rs, d->slices);
+  if (rc != MPV_OK) return rc;
   const long long supers = (d->ng + RS_SUPER - 1) / RS_SUPER;
-  p->qtiles = (int)((d->nq + RS_QT - 1) / RS_QT);
+  p->qtiles = (int)((d->nq + SC_TILE - 1) / SC_TILE);
   // 0 = choose: 3 workgroups per CU over the 256 CUs, at least 4 super-tiles (512 rows) each
   long long s = d->slices;
   if (s == 0) {
     s = (768 + p->qtiles - 1) / p->qtiles;
     if (s > (supers + 3) / 4) s = (supers + 3) / 4;
     // top-k: two workgroups fit a CU (registers), so no more than 512 -- a 513th would run alone in a second round -- and no
-    // more than the merge kernel caches (RS_MERGE_CACHE entries, k per slice)
+    // more than the merge kernel caches (SC_MERGE_CACHE entries, k per slice)
     if (topk_k > 0 && s > 512) s = 512;
-    if (topk_k > 0 && s > RS_MERGE_CACHE / topk_k) s = RS_MERGE_CACHE / topk_k;
+    if (topk_k > 0 && s > SC_MERGE_CACHE / topk_k) s = SC_MERGE_CACHE / topk_k;
   }
   if (s > supers) s = supers;
   if (s < 1) s = 1;
@@ -446,81 +345,88 @@ RsArgs rs_args(const mpv_sim_search_desc* d, const RsPlan& p) {
   return a;
 }
 
-size_t rs_stream_lds(int D, size_t tail) { return (size_t)(RS_QT * (D + 8) + RS_WAVES * RS_GT * RS_PITCH) * sizeof(bf16) + tail; }
-
-size_t rs_align(size_t n) { return (n + 255) & ~(size_t)255; }
-
 }  // namespace
+
+// the launchers of the two kernels above, for this file and maxsim_search.hip (declared in search_common.h)
+int sc_merge_slices(const char* what, const float* ws_val, const int* ws_idx, float* vals, int64_t* idx, int nq, int k, int slices,
+                    hipStream_t stream) {
+  hipLaunchKernelGGL(sim_topk_merge_kernel, dim3((unsigned)nq), dim3(256), 0, stream, ws_val, ws_idx, vals, idx, nq, k, slices);
+  return mpv_check_launch(what);
+}
+
+int sc_rank_finish(const char* what, const int64_t* target, const float* tscore, const int* counts, int* rank, int nq, int n_t, int ng,
+                   hipStream_t stream) {
+  hipLaunchKernelGGL(sim_rank_finish_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream, target, tscore, counts, rank, nq,
+                     n_t, ng);
+  return mpv_check_launch(what);
+}
 
 extern "C" size_t mpv_sim_topk_workspace_size(const mpv_sim_search_desc* d) {
   RsPlan p;
-  if (!d || d->k < 1 || d->k > RS_MAX_K || rs_plan(d, &p, "mpv_sim_topk_workspace_size", d->k) != MPV_OK) return 0;
-  return 2 * rs_align((size_t)p.slices * (size_t)d->nq * d->k * 4);
+  if (!d || d->k < 1 || d->k > SC_MAX_K || rs_plan(d, &p, "mpv_sim_topk_workspace_size", d->k) != MPV_OK) return 0;
+  return sc_ws_bytes((size_t)p.slices * (size_t)d->nq * d->k);
 }
 
 extern "C" int mpv_sim_topk(const mpv_sim_search_desc* d, float* vals, int64_t* idx, void* workspace, size_t workspace_bytes,
                             hipStream_t stream) {
   RsPlan p;
   MPV_REQUIRE(d, MPV_E_ARG, "mpv_sim_topk: null descriptor");
-  MPV_REQUIRE(d->k >= 1 && d->k <= RS_MAX_K, MPV_E_ARG, "mpv_sim_topk: k (%d) must be in [1, %d]", d->k, RS_MAX_K);
-  const int rc = rs_plan(d, &p, "mpv_sim_topk", d->k);
+  MPV_REQUIRE(d->k >= 1 && d->k <= SC_MAX_K, MPV_E_ARG, "mpv_sim_topk: k (%d) must be in [1, %d]", d->k, SC_MAX_K);
+  int rc = rs_plan(d, &p, "mpv_sim_topk", d->k);
   if (rc != MPV_OK) return rc;
   MPV_REQUIRE(vals && idx && workspace, MPV_E_ARG, "mpv_sim_topk: null pointer");
-  const size_t half = rs_align((size_t)p.slices * (size_t)d->nq * d->k * 4);
-  MPV_REQUIRE(workspace_bytes >= 2 * half, MPV_E_ARG, "mpv_sim_topk: workspace of %zu bytes, %zu needed", workspace_bytes, 2 * half);
-  MPV_REQUIRE(((uintptr_t)workspace & 3) == 0, MPV_E_ALIGN, "mpv_sim_topk: workspace must be 4-byte aligned");
+  const size_t n = (size_t)p.slices * (size_t)d->nq * d->k;
+  rc = sc_ws_check("mpv_sim_topk", workspace, workspace_bytes, n);
+  if (rc != MPV_OK) return rc;
   RsArgs a = rs_args(d, p);
   a.k = d->k;
   a.scale = d->scale;
   a.ws_val = (float*)workspace;
-  a.ws_idx = (int*)((char*)workspace + half);
-  const size_t lds = rs_stream_lds(d->dim, (size_t)RS_WAVES * d->k * 32 * 8);
+  a.ws_idx = (int*)sc_ws_upper(workspace, n);
+  const size_t lds = sc_stream_lds(d->dim, SC_WAVES, (size_t)SC_WAVES * d->k * 32 * 8);
   auto kern = d->k <= 4 ? sim_stream_kernel<0, 4> : d->k <= 16 ? sim_stream_kernel<0, 16> : sim_stream_kernel<0, 32>;
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(kern, dim3((unsigned)p.slices, (unsigned)p.qtiles), dim3(64 * RS_WAVES), lds, stream, a);
-  int lrc = mpv_check_launch("mpv_sim_topk");
-  if (lrc != MPV_OK) return lrc;
-  hipLaunchKernelGGL(sim_topk_merge_kernel, dim3((unsigned)d->nq), dim3(256), 0, stream, a.ws_val, a.ws_idx, vals, idx,
-                     a.nq, a.k, p.slices);
-  return mpv_check_launch("mpv_sim_topk (merge)");
+  sc_allow_lds((const void*)kern, lds);
+  hipLaunchKernelGGL(kern, dim3((unsigned)p.slices, (unsigned)p.qtiles), dim3(64 * SC_WAVES), lds, stream, a);
+  rc = mpv_check_launch("mpv_sim_topk");
+  if (rc != MPV_OK) return rc;
+  return sc_merge_slices("mpv_sim_topk (merge)", a.ws_val, a.ws_idx, vals, idx, a.nq, a.k, p.slices, stream);
 }
 
 extern "C" size_t mpv_sim_rank_workspace_size(const mpv_sim_search_desc* d, int n_targets) {
-  if (!d || d->nq <= 0 || n_targets < 1 || n_targets > RS_MAX_T) return 0;
-  return 2 * rs_align((size_t)d->nq * n_targets * 4);
+  if (!d || d->nq <= 0 || n_targets < 1 || n_targets > SC_MAX_T) return 0;
+  return sc_ws_bytes((size_t)d->nq * n_targets);
 }
 
 extern "C" int mpv_sim_rank(const mpv_sim_search_desc* d, const int64_t* target, int n_targets, int32_t* rank, void* workspace,
                             size_t workspace_bytes, hipStream_t stream) {
   RsPlan p;
-  const int rc = rs_plan(d, &p, "mpv_sim_rank");
+  int rc = rs_plan(d, &p, "mpv_sim_rank");
   if (rc != MPV_OK) return rc;
   MPV_REQUIRE(target && rank && workspace, MPV_E_ARG, "mpv_sim_rank: null pointer");
-  MPV_REQUIRE(n_targets >= 1 && n_targets <= RS_MAX_T, MPV_E_ARG, "mpv_sim_rank: n_targets (%d) must be in [1, %d]", n_targets, RS_MAX_T);
-  const size_t half = rs_align((size_t)d->nq * n_targets * 4);
-  MPV_REQUIRE(workspace_bytes >= 2 * half, MPV_E_ARG, "mpv_sim_rank: workspace of %zu bytes, %zu needed", workspace_bytes, 2 * half);
-  MPV_REQUIRE(((uintptr_t)workspace & 3) == 0, MPV_E_ALIGN, "mpv_sim_rank: workspace must be 4-byte aligned");
+  MPV_REQUIRE(n_targets >= 1 && n_targets <= SC_MAX_T, MPV_E_ARG, "mpv_sim_rank: n_targets (%d) must be in [1, %d]", n_targets, SC_MAX_T);
+  const size_t n = (size_t)d->nq * n_targets;
+  rc = sc_ws_check("mpv_sim_rank", workspace, workspace_bytes, n);
+  if (rc != MPV_OK) return rc;
   RsArgs a = rs_args(d, p);
   a.n_t = n_targets;
   a.target = target;
   float* tscore = (float*)workspace;
   a.tscore = tscore;
-  a.counts = (int*)((char*)workspace + half);
-  if (hipMemsetAsync(a.counts, 0, (size_t)d->nq * n_targets * 4, stream) != hipSuccess) {
+  a.counts = (int*)sc_ws_upper(workspace, n);
+  if (hipMemsetAsync(a.counts, 0, n * 4, stream) != hipSuccess) {
     mpv_set_error("mpv_sim_rank: hipMemsetAsync failed");
     return MPV_E_HIP;
   }
-  const size_t lds_t = (size_t)(RS_QT * (d->dim + 8) + RS_GT * RS_PITCH) * sizeof(bf16);
-  if (lds_t > 48 * 1024) (void)hipFuncSetAttribute((const void*)sim_target_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t);
+  const size_t lds_t = sc_stream_lds(d->dim, 1, 0);
+  sc_allow_lds((const void*)sim_target_kernel, lds_t);
   hipLaunchKernelGGL(sim_target_kernel, dim3((unsigned)n_targets, (unsigned)p.qtiles), dim3(64), lds_t, stream, a, tscore);
-  int lrc = mpv_check_launch("mpv_sim_rank (target scores)");
-  if (lrc != MPV_OK) return lrc;
-  const size_t lds = rs_stream_lds(d->dim, (size_t)RS_QT * n_targets * 12);
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)sim_stream_kernel<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((sim_stream_kernel<1, 1>), dim3((unsigned)p.slices, (unsigned)p.qtiles), dim3(64 * RS_WAVES), lds, stream, a);
-  lrc = mpv_check_launch("mpv_sim_rank");
-  if (lrc != MPV_OK) return lrc;
-  hipLaunchKernelGGL(sim_rank_finish_kernel, dim3((unsigned)((d->nq + 255) / 256)), dim3(256), 0, stream, target, a.counts, rank, a.nq,
-                     n_targets, a.ng);
-  return mpv_check_launch("mpv_sim_rank (finish)");
+  rc = mpv_check_launch("mpv_sim_rank (target scores)");
+  if (rc != MPV_OK) return rc;
+  const size_t lds = sc_stream_lds(d->dim, SC_WAVES, (size_t)SC_TILE * n_targets * 12);
+  sc_allow_lds((const void*)sim_stream_kernel<1, 1>, lds);
+  hipLaunchKernelGGL((sim_stream_kernel<1, 1>), dim3((unsigned)p.slices, (unsigned)p.qtiles), dim3(64 * SC_WAVES), lds, stream, a);
+  rc = mpv_check_launch("mpv_sim_rank");
+  if (rc != MPV_OK) return rc;
+  // no target scores: a target whose score is NaN still counts as a target here (mpv_maxsim_rank skips it)
+  return sc_rank_finish("mpv_sim_rank (finish)", target, nullptr, a.counts, rank, a.nq, n_targets, a.ng, stream);
 }

@@ -630,36 +630,44 @@ def _sim_desc(q, g, k, scale, slices):
     return d
 
 
+def _search_topk(name, d, q, k):
+    """vals / idx [Nq, k] filled by mpv_<name> on descriptor d, with the workspace mpv_<name>_workspace_size asks for"""
+    vals = torch.empty((q.shape[0], k), dtype=torch.float32, device=q.device)
+    idx = torch.empty((q.shape[0], k), dtype=torch.int64, device=q.device)
+    lib = _lib.lib()
+    ws = workspace(max(getattr(lib, f"mpv_{name}_workspace_size")(C.byref(d)), 1), q.device)
+    check(getattr(lib, f"mpv_{name}")(C.byref(d), vals.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), f"mpv_{name}")
+    return vals, idx
+
+
+def _search_rank(name, d, q, target, queries="queries"):
+    """rank [Nq] filled by mpv_<name> on descriptor d for target int64 [Nq] or [Nq, n_t]"""
+    _need_cuda(target)
+    if target.dtype != torch.int64:
+        raise _lib.MpvError(f"{name}: target must be int64 (got {target.dtype})")
+    target = target.reshape(target.shape[0], -1).contiguous()
+    if target.shape[0] != q.shape[0]:
+        raise _lib.MpvError(f"{name}: {target.shape[0]} target rows for {q.shape[0]} {queries}")
+    n_t = target.shape[1]
+    rank = torch.empty(q.shape[0], dtype=torch.int32, device=q.device)
+    lib = _lib.lib()
+    ws = workspace(max(getattr(lib, f"mpv_{name}_workspace_size")(C.byref(d), n_t), 1), q.device)
+    check(getattr(lib, f"mpv_{name}")(C.byref(d), target.data_ptr(), n_t, rank.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+          f"mpv_{name}")
+    return rank
+
+
 def sim_topk(q, g, k, scale=None, slices=0):
     """-> (vals fp32 [Nq, k], idx int64 [Nq, k]): the k largest scale * <q_i, g_j> per query, descending, ties to the lower j,
     (-inf, -1) beyond Ng; `slices` gallery slices per query tile (0 = choose), the result does not depend on it
     (include/mpv.h: mpv_sim_topk)."""
-    d = _sim_desc(q, g, k, scale, slices)
-    vals = torch.empty((q.shape[0], k), dtype=torch.float32, device=q.device)
-    idx = torch.empty((q.shape[0], k), dtype=torch.int64, device=q.device)
-    need = _lib.lib().mpv_sim_topk_workspace_size(C.byref(d))
-    ws = workspace(max(need, 1), q.device)
-    check(_lib.lib().mpv_sim_topk(C.byref(d), vals.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "mpv_sim_topk")
-    return vals, idx
+    return _search_topk("sim_topk", _sim_desc(q, g, k, scale, slices), q, k)
 
 
 def sim_rank(q, g, target, slices=0):
     """-> rank int32 [Nq]: the best rank among the query's target rows (target int64 [Nq] or [Nq, n_t], -1 = unused slot); the rank of
     row t is the number of rows j with <q, g_j> > <q, g_t>, or equal and j < t (include/mpv.h: mpv_sim_rank)."""
-    d = _sim_desc(q, g, 0, None, slices)
-    _need_cuda(target)
-    if target.dtype != torch.int64:
-        raise _lib.MpvError(f"sim_rank: target must be int64 (got {target.dtype})")
-    target = target.reshape(target.shape[0], -1).contiguous()
-    if target.shape[0] != q.shape[0]:
-        raise _lib.MpvError(f"sim_rank: {target.shape[0]} target rows for {q.shape[0]} queries")
-    n_t = target.shape[1]
-    rank = torch.empty(q.shape[0], dtype=torch.int32, device=q.device)
-    need = _lib.lib().mpv_sim_rank_workspace_size(C.byref(d), n_t)
-    ws = workspace(max(need, 1), q.device)
-    check(_lib.lib().mpv_sim_rank(C.byref(d), target.data_ptr(), n_t, rank.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
-          "mpv_sim_rank")
-    return rank
+    return _search_rank("sim_rank", _sim_desc(q, g, 0, None, slices), q, target)
 
 
 def _maxsim_side(name, t):
@@ -695,30 +703,10 @@ def maxsim_topk(q, g, k, scale=None, slices=0):
     """-> (vals fp32 [Nq, k], idx int64 [Nq, k]): the k gallery items with the largest scale * max over the group's rows of <a, b>
     per query item, descending, ties to the lower item, (-inf, -1) beyond Ng.  q, g: bf16 [items, dim] or [items, group, dim], at
     most one of them with group > 1; the result does not depend on `slices` (include/mpv.h: mpv_maxsim_topk)."""
-    d = _maxsim_desc(q, g, k, scale, slices)
-    vals = torch.empty((q.shape[0], k), dtype=torch.float32, device=q.device)
-    idx = torch.empty((q.shape[0], k), dtype=torch.int64, device=q.device)
-    need = _lib.lib().mpv_maxsim_topk_workspace_size(C.byref(d))
-    ws = workspace(max(need, 1), q.device)
-    check(_lib.lib().mpv_maxsim_topk(C.byref(d), vals.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
-          "mpv_maxsim_topk")
-    return vals, idx
+    return _search_topk("maxsim_topk", _maxsim_desc(q, g, k, scale, slices), q, k)
 
 
 def maxsim_rank(q, g, target, slices=0):
     """-> rank int32 [Nq]: the best rank among the query item's target items (target int64 [Nq] or [Nq, n_t], -1 = unused slot) under
     the query-max score and the order rule of maxsim_topk; Ng for a query with no valid target (include/mpv.h: mpv_maxsim_rank)."""
-    d = _maxsim_desc(q, g, 0, None, slices)
-    _need_cuda(target)
-    if target.dtype != torch.int64:
-        raise _lib.MpvError(f"maxsim_rank: target must be int64 (got {target.dtype})")
-    target = target.reshape(target.shape[0], -1).contiguous()
-    if target.shape[0] != q.shape[0]:
-        raise _lib.MpvError(f"maxsim_rank: {target.shape[0]} target rows for {q.shape[0]} query items")
-    n_t = target.shape[1]
-    rank = torch.empty(q.shape[0], dtype=torch.int32, device=q.device)
-    need = _lib.lib().mpv_maxsim_rank_workspace_size(C.byref(d), n_t)
-    ws = workspace(max(need, 1), q.device)
-    check(_lib.lib().mpv_maxsim_rank(C.byref(d), target.data_ptr(), n_t, rank.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
-          "mpv_maxsim_rank")
-    return rank
+    return _search_rank("maxsim_rank", _maxsim_desc(q, g, 0, None, slices), q, target, queries="query items")

@@ -231,17 +231,12 @@ def synthetic_retrieval_model(shapes, device="cuda", num_frames=None, embed_dim=
                                       "num_frames": num_frames or shapes.num_frames}, visual_cfg=vis, text_cfg=txt, device=device)
 
 
-class RetrievalIndex:
-    """Gallery of L2-normalised bf16 feature rows (what extract_vision_feature / extract_text_feature return) searched on the
-    device by ops.sim_topk / ops.sim_rank: the [queries, gallery] score matrix is never built.  Rows keep the order they were
-    added in; row i of the index is the i-th feature ever added.  Storage grows geometrically, so `add` does not re-allocate
-    per call.  Order rule of both searches: higher score first, equal scores by the lower row index (include/mpv.h)."""
+class _FeatureIndex:
+    """Storage shared by the two indexes: items of shape `_item` appended in order into a buffer that grows geometrically."""
 
-    def __init__(self, dim: int, device="cuda", capacity: int = 1024):
-        if dim % 32 != 0 or not 32 <= dim <= 1024:
-            raise ops._lib.MpvError(f"RetrievalIndex: dim ({dim}) must be a multiple of 32 in [32, 1024]")
-        self.dim, self.device, self.size = dim, torch.device(device), 0
-        self._rows = torch.empty((max(int(capacity), 1), dim), dtype=torch.bfloat16, device=self.device)
+    def _init_storage(self, item, device, capacity):
+        self._item, self.device, self.size = tuple(item), torch.device(device), 0
+        self._rows = torch.empty((max(int(capacity), 1),) + self._item, dtype=torch.bfloat16, device=self.device)
 
     def __len__(self):
         return self.size
@@ -252,8 +247,39 @@ class RetrievalIndex:
 
     @property
     def features(self):
-        """the rows added so far: a view of the storage, bf16 [size, dim]"""
+        """the items added so far: a view of the storage, bf16 [size, *item shape]"""
         return self._rows[:self.size]
+
+    def _append(self, features):
+        n, first = features.shape[0], self.size
+        if first + n > self.capacity:
+            grown = torch.empty((max(2 * self.capacity, first + n),) + self._item, dtype=torch.bfloat16, device=self.device)
+            grown[:first].copy_(self._rows[:first])
+            self._rows = grown
+        self._rows[first:first + n].copy_(features)
+        self.size = first + n
+        return first
+
+    def _targets(self, target, q, noun):
+        """target -> int64 [Nq, n_t] on the queries' device, every entry in [-1, size)"""
+        target = torch.as_tensor(target, dtype=torch.int64, device=q.device).reshape(q.shape[0], -1)
+        if target.numel() and (int(target.max()) >= self.size or int(target.min()) < -1):
+            raise ops._lib.MpvError(f"{type(self).__name__}.rank: target {noun} must be in [-1, {self.size}) "
+                                    f"(got {int(target.min())} .. {int(target.max())})")
+        return target
+
+
+class RetrievalIndex(_FeatureIndex):
+    """Gallery of L2-normalised bf16 feature rows (what extract_vision_feature / extract_text_feature return) searched on the
+    device by ops.sim_topk / ops.sim_rank: the [queries, gallery] score matrix is never built.  Rows keep the order they were
+    added in; row i of the index is the i-th feature ever added.  Storage grows geometrically, so `add` does not re-allocate
+    per call.  Order rule of both searches: higher score first, equal scores by the lower row index (include/mpv.h)."""
+
+    def __init__(self, dim: int, device="cuda", capacity: int = 1024):
+        if dim % 32 != 0 or not 32 <= dim <= 1024:
+            raise ops._lib.MpvError(f"RetrievalIndex: dim ({dim}) must be a multiple of 32 in [32, 1024]")
+        self.dim = dim
+        self._init_storage((dim,), device, capacity)
 
     def _check(self, feats, what):
         if not torch.is_tensor(feats) or feats.dtype != torch.bfloat16:
@@ -265,14 +291,7 @@ class RetrievalIndex:
     def add(self, features):
         """append rows; -> the index of the first one"""
         self._check(features, "add")
-        n, first = features.shape[0], self.size
-        if first + n > self.capacity:
-            grown = torch.empty((max(2 * self.capacity, first + n), self.dim), dtype=torch.bfloat16, device=self.device)
-            grown[:first].copy_(self._rows[:first])
-            self._rows = grown
-        self._rows[first:first + n].copy_(features)
-        self.size = first + n
-        return first
+        return self._append(features)
 
     def search(self, query_features, k: int, scale=None):
         """-> (scores fp32 [Nq, k], indices int64 [Nq, k]), best first; (-inf, -1) beyond the index size"""
@@ -288,15 +307,10 @@ class RetrievalIndex:
         self._check(query_features, "rank")
         if self.size == 0:
             raise ops._lib.MpvError("RetrievalIndex.rank: the index is empty")
-        target = torch.as_tensor(target, dtype=torch.int64, device=query_features.device)
-        target = target.reshape(query_features.shape[0], -1)
-        if target.numel() and (int(target.max()) >= self.size or int(target.min()) < -1):
-            raise ops._lib.MpvError(f"RetrievalIndex.rank: target rows must be in [-1, {self.size}) "
-                                    f"(got {int(target.min())} .. {int(target.max())})")
-        return ops.sim_rank(query_features.contiguous(), self.features, target)
+        return ops.sim_rank(query_features.contiguous(), self.features, self._targets(target, query_features, "rows"))
 
 
-class MaxSimIndex:
+class MaxSimIndex(_FeatureIndex):
     """Gallery of ITEMS that are groups of `group` L2-normalised bf16 rows (the pre-train model's extract_vision_feature returns
     [B, Q, E]: group = Q; its extract_text_feature returns [B, E]: group = 1), searched on the device by ops.maxsim_topk /
     ops.maxsim_rank under the query-max score: s(query, item) = max over the rows of both of <a, b>.  A grouped index takes
@@ -308,20 +322,8 @@ class MaxSimIndex:
             raise ops._lib.MpvError(f"MaxSimIndex: dim ({dim}) must be a multiple of 32 in [32, 1024]")
         if not 1 <= int(group) <= 1024:
             raise ops._lib.MpvError(f"MaxSimIndex: group ({group}) must be in [1, 1024]")
-        self.dim, self.group, self.device, self.size = dim, int(group), torch.device(device), 0
-        self._rows = torch.empty((max(int(capacity), 1), self.group, dim), dtype=torch.bfloat16, device=self.device)
-
-    def __len__(self):
-        return self.size
-
-    @property
-    def capacity(self):
-        return self._rows.shape[0]
-
-    @property
-    def features(self):
-        """the items added so far: a view of the storage, bf16 [size, group, dim]"""
-        return self._rows[:self.size]
+        self.dim, self.group = dim, int(group)
+        self._init_storage((self.group, dim), device, capacity)
 
     def _check(self, feats, what, groups):
         if not torch.is_tensor(feats) or feats.dtype != torch.bfloat16:
@@ -336,15 +338,7 @@ class MaxSimIndex:
 
     def add(self, features):
         """append items [n, group, dim] ([n, dim] when group == 1); -> the index of the first one"""
-        features = self._check(features, "add", (self.group,))
-        n, first = features.shape[0], self.size
-        if first + n > self.capacity:
-            grown = torch.empty((max(2 * self.capacity, first + n), self.group, self.dim), dtype=torch.bfloat16, device=self.device)
-            grown[:first].copy_(self._rows[:first])
-            self._rows = grown
-        self._rows[first:first + n].copy_(features)
-        self.size = first + n
-        return first
+        return self._append(self._check(features, "add", (self.group,)))
 
     def _query(self, query_features, what):
         # a grouped index is searched with one row per query; an index of single rows with single rows or with groups of any size
@@ -363,8 +357,4 @@ class MaxSimIndex:
     def rank(self, query_features, target):
         """-> int32 [Nq]: the best rank (0 = first) among each query's target items; target int64 [Nq] or [Nq, n_t], -1 = unused"""
         q = self._query(query_features, "rank")
-        target = torch.as_tensor(target, dtype=torch.int64, device=q.device).reshape(q.shape[0], -1)
-        if target.numel() and (int(target.max()) >= self.size or int(target.min()) < -1):
-            raise ops._lib.MpvError(f"MaxSimIndex.rank: target items must be in [-1, {self.size}) "
-                                    f"(got {int(target.min())} .. {int(target.max())})")
-        return ops.maxsim_rank(q, self.features, target)
+        return ops.maxsim_rank(q, self.features, self._targets(target, q, "items"))
