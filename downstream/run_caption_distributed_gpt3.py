@@ -8,6 +8,8 @@ What this entry point adds to downstream/finetune_common.py:
     `model(video, text)` -> loss_generation;
   * evaluation (:208-238): the prompt alone (padded to 20 tokens) + the clip's query features -> `model.generate` (one beam search
     per clip), decoded, blanks removed, the prompt cut off -> [{video_id, pred_caption, gold_caption}];
+  * `--eval_batched_beam` (not in the reference, default off): `model.generate(..., batched=True)` searches the clips of a batch in
+    lockstep (`--clips_per_search` at a time, generation.beam_search_batched_loop); same result files;
   * save_result (dataset/utils.py:114-160): one JSON per rank, merged by rank 0; cal_metric (:240-298): predictions and references
     reduced to their CJK characters, one token per character, scored by pycocoevalcap's COCOEvalCap when that package is importable.
     It is not on this image: then BLEU-1..4 (corpus level, closest-reference brevity penalty) and ROUGE-L (beta 1.2, best reference)
@@ -36,8 +38,8 @@ def make_training_batch(video, text, prompt, tokenizer, device, max_length):
 
 
 @torch.no_grad()
-def evaluation(model, data_loader, tokenizer, device, config):
-    """-> [{video_id, pred_caption, gold_caption}] (:208-238)"""
+def evaluation(model, data_loader, tokenizer, device, config, batched=False, clips_per_search=32):
+    """-> [{video_id, pred_caption, gold_caption}] (:208-238); batched: `--eval_batched_beam`"""
     module = getattr(model, "module", model)
     module.eval()
     result = []
@@ -45,7 +47,7 @@ def evaluation(model, data_loader, tokenizer, device, config):
         video = video.to(device, non_blocking=True).bfloat16()
         text = [config["prompt"] for _ in range(video.shape[0])]
         text_input = tokenizer(text, padding="max_length", truncation=True, max_length=20, return_tensors="pt").to(device)
-        res = module.generate(video, text_input)
+        res = module.generate(video, text_input, batched=True, clips_per_search=clips_per_search) if batched else module.generate(video, text_input)
         for video_id, r, gold in zip(video_ids, res, gold_caption):
             ans = tokenizer.decode(r.tolist()[0]).replace(" ", "").strip()
             if config["prompt"] != "":
@@ -197,7 +199,8 @@ def main(args, config):
         return {"loss_generation": s.model(*make_training_batch(video, text, config["prompt"], s.tokenizer, s.device, args.max_length))}
 
     if args.evaluate_only:
-        result = evaluation(s.model, val_loader, s.tokenizer, s.device, config)
+        result = evaluation(s.model, val_loader, s.tokenizer, s.device, config, batched=getattr(args, "eval_batched_beam", False),
+                            clips_per_search=getattr(args, "clips_per_search", 32))
         val_stats = cal_metric(save_result(result, args.result_dir, "val_caption_result"))
         print("* Validation Stats:", val_stats)
         log_stats = {**{f"val_{k}": v for k, v in val_stats.items()}, "n_parameters": s.n_parameters}
@@ -207,7 +210,13 @@ def main(args, config):
 
 
 def get_args(argv=None):
-    args, config = ft.get_args(argv, extra=lambda p: p.add_argument("--no_zero_shot", action="store_true"))
+    def extra(p):
+        p.add_argument("--no_zero_shot", action="store_true")
+        p.add_argument("--eval_batched_beam", action="store_true", default=False,
+                       help="evaluation: beam-search the clips of a batch in lockstep (model.generate(batched=True)) instead of one by one")
+        p.add_argument("--clips_per_search", type=int, default=32,
+                       help="--eval_batched_beam: clips per lockstep search (KV memory: clips x beams x 2 cache copies)")
+    args, config = ft.get_args(argv, extra=extra)
     config.setdefault("prompt", "")
     args.result_dir = os.path.join(args.output_dir, "result")
     os.makedirs(args.result_dir, exist_ok=True)

@@ -377,6 +377,47 @@ int mpv_gpt_decode_step(const mpv_gpt_weights* w, void* const* kv_cache, int bat
 int mpv_kv_reorder(void* const* src, void* const* dst, int layers, const int64_t* idx, int batch, int max_len, int rows,
                    int hidden, mpv_stream_t stream);
 /* ------------------------------------------------------------------------------------------
+ * Lockstep beam search over a batch of clips (caption evaluation, generation.beam_search_batched_loop): ONE launch advances the
+ * beam state of `batch` clips x `beams` (K) beams by one position, doing per clip exactly what one iteration of the reference's
+ * beam_search does on the host (models/modeling_distributed_gpt3.py:1793-1840 with BeamHypotheses.add / is_done, :1908-1960).
+ * Input: cand_val fp32 / cand_idx int64 [batch*K][2K] -- what mpv_logprob_topk writes for k = 2K with add = scores (row b*K + j
+ *   is beam j of clip b) -- the state below, `pos` (the token column this step fills), `cur_len` (positions generated so far,
+ *   this one included: the done test's length) and `first` (non-zero: only beam 0 of every clip is read, :1793-1795).
+ * State (device arrays, struct of arrays): tokens_in / tokens_out int64 [batch][K][row_len], two different tables that the caller
+ *   swaps after every call; scores fp32 [batch][K]; the hypothesis store hyp_score fp64 [batch][K], hyp_order int32 [batch][K]
+ *   (insertion counter), hyp_tokens int64 [batch][K][row_len], hyp_count / hyp_next int32 [batch], worst fp64 [batch] (initially
+ *   1e9), done int32 [batch].
+ * Output: src_row int64 [batch*K] = b*K + source beam (never leaves the clip: it feeds the KV re-order as it is) and next_tok
+ *   int64 [batch*K].
+ * Per clip: the candidates are ordered by value descending, then beam * vocab + token ascending, and the first 2K are walked.
+ *   The stop token at rank >= K is skipped; at rank < K it adds tokens_in[beam] (the whole row) to the store with the score
+ *   double(value) / row_len (length penalty 1.0 over the ROW length, sic): added when count < K or score > worst; then the lowest
+ *   score goes, ties to the earliest inserted, and worst becomes the lowest that stays.  Any other token becomes the next beam
+ *   until there are K.  Done test: count == K && worst >= double(best candidate value) / cur_len.  Otherwise tokens_out[j] =
+ *   tokens_in[source beam of j] with the new token at `pos`, scores[j] = its value.  fp64 arithmetic on the fp32 inputs: the
+ *   scores are those of the host loop's Python floats bit for bit.
+ * A clip that is done, or becomes done in this call, is frozen: tokens_out gets its tokens_in rows unchanged, src_row is the
+ *   identity, next_tok the stop token, scores stay; once done, nothing else of its state is written again.
+ * Limits: beams in [1, 8], row_len in [1, 2048], 0 <= pos < row_len; a descriptor outside them is refused with a negative code
+ *   before any launch.  One wave per clip, no atomics; a clip's result depends neither on `batch` nor on its place in it. */
+typedef struct mpv_beam_advance_desc {
+  const float* cand_val;
+  const int64_t* cand_idx;
+  const int64_t* tokens_in;
+  int64_t* tokens_out;
+  float* scores;
+  double* hyp_score;
+  int32_t* hyp_order;
+  int64_t* hyp_tokens;
+  int32_t *hyp_count, *hyp_next;
+  double* worst;
+  int32_t* done;
+  int64_t *src_row, *next_tok;
+  int batch, beams, row_len, vocab, pos, cur_len, first;
+  int64_t stop_token;
+} mpv_beam_advance_desc;
+int mpv_beam_advance(const mpv_beam_advance_desc* d, mpv_stream_t stream);
+/* ------------------------------------------------------------------------------------------
  * Device-side video input transform (configs' video_pretrain/train/test transforms,
  * dataset/__init__.py:60-85): the decoder's uint8 clip [T][H][W][3] -> crop (i, j, h, w) ->
  * torch.nn.functional.interpolate to out_h x out_w (mode 0 nearest / 1 bilinear / 2 bicubic, align_corners=False:

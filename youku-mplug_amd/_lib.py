@@ -70,6 +70,12 @@ class MaxSimSearchDesc(C.Structure):
     ]
 
 
+class BeamAdvanceDesc(C.Structure):
+    _fields_ = [(n, c_void_p) for n in ("cand_val", "cand_idx", "tokens_in", "tokens_out", "scores", "hyp_score", "hyp_order", "hyp_tokens",
+                                        "hyp_count", "hyp_next", "worst", "done", "src_row", "next_tok")] + \
+               [(n, c_int) for n in ("batch", "beams", "row_len", "vocab", "pos", "cur_len", "first")] + [("stop_token", c_int64)]
+
+
 _RM = [c_int, c_int, c_int]
 _SIGS = {
     "mpv_version": (c_int, []),
@@ -136,6 +142,7 @@ _SIGS = {
     "mpv_gather_rows_ld": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p]),
     "mpv_logprob_topk_workspace_size": (c_size_t, [c_int64, c_int]),
     "mpv_logprob_topk": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mpv_beam_advance": (c_int, [C.POINTER(BeamAdvanceDesc), c_void_p]),
     "mpv_soft_target_ce": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     "mpv_maxsim_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p]),
     "mpv_maxsim_route": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p]),

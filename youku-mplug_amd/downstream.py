@@ -330,8 +330,14 @@ class DistributedGPT3_Caption(_GenCls):
         return self._run(image, text, None, None, None, True)[0]                              # :768-789 returns loss_caption only
 
     @torch.no_grad()
-    def generate(self, image, text, termination_id=None, **kw):
-        """One beam search per sample (:790-809): prompt = text.input_ids[i, :mask.sum()-1], prefix = its query features."""
+    def generate(self, image, text, termination_id=None, batched=False, clips_per_search=32, **kw):
+        """One beam search per sample (:790-809): prompt = text.input_ids[i, :mask.sum()-1], prefix = its query features.
+        batched=True (not in the reference, default off): the clips are grouped by prompt length and every group is searched in
+        lockstep, `clips_per_search` clips at a time (generation.beam_search_batched_loop: the decoder's weights are read once per
+        generated position of a chunk, not once per clip; the prefill runs once per clip).  Same return value: one [n, Lt] tensor
+        per clip, in input order.  KV memory is what bounds clips_per_search: a chunk holds clips_per_search x beam_size sequences
+        in both copies of the cache -- at 1.3B dims 88 MB per sequence of 300 positions, so 32 clips x 5 beams x 2 copies is about
+        28 GB; halve clips_per_search to halve it."""
         Bv = image.shape[0]
         Q, Hh = self.num_learnable_token, self.text_width
         was = self.training
@@ -341,8 +347,23 @@ class DistributedGPT3_Caption(_GenCls):
             if termination_id is None:
                 tok = getattr(self, "tokenizer", None)
                 termination_id = tok.tokenizer.eos if tok is not None else None
+            n = text.input_ids.shape[0]
+            if batched:
+                if int(clips_per_search) < 1:
+                    raise ValueError(f"clips_per_search must be at least 1 (got {clips_per_search})")
+                lengths = (text.attention_mask.sum(-1) - 1).tolist()
+                res = [None] * n
+                for pl in sorted(set(lengths)):
+                    group = [i for i in range(n) if lengths[i] == pl]
+                    for c in range(0, len(group), int(clips_per_search)):
+                        sel = torch.as_tensor(group[c:c + int(clips_per_search)], dtype=torch.long, device=qf.device)
+                        outs = self.text_decoder.beam_search_batched(text.input_ids[sel], query_embeds=qf[sel].contiguous(),
+                                                                     stop_token=termination_id, prompt_length=int(pl), **kw)
+                        for i, out in zip(sel.tolist(), outs):
+                            res[i] = out.sequences.cpu()
+                return res
             res = []
-            for i in range(text.input_ids.shape[0]):
+            for i in range(n):
                 out = self.text_decoder.generate(text.input_ids[i:i + 1], query_embeds=qf[i:i + 1], termination_id=termination_id,
                                                  do_sample=False, prompt_length=int(text.attention_mask.sum(-1)[i]) - 1, **kw)
                 res.append(out.sequences.cpu())

@@ -8,7 +8,8 @@ the fused attention reads K/V from it with (batch, head, row) strides; nothing i
 keeps [max_s, b, np, hn] K and V tensors and copies into them, :905-915).  A step processes the n new positions of
 every sequence (prefill: the visual prefix + prompt; afterwards one token), attends causally over the cached rows and
 runs the LM head on the last position only.  Beam re-ordering (swap_key_value_dict) is one strided row gather per
-layer into the twin buffer.  The search logic itself stays on the host, as in the reference.
+layer into the twin buffer.  The search logic of the per-clip loops stays on the host, as in the reference; the lockstep
+search over a batch of clips (beam_search_batched_loop) keeps it on the device (ops.beam_advance, csrc/beam_search.hip).
 """
 from __future__ import annotations
 
@@ -108,19 +109,49 @@ class DecodeState:
         self.pos += Q + L
         return logits
 
-    def reorder(self, batch_idx: torch.Tensor, shared_prefix: int = 0):
-        """swap_key_value_dict(:1459-1473): sequence j continues from the cache of sequence batch_idx[j].  The layers
-        are one allocation, so the whole re-order is a single strided row gather over (layer, sequence) rows.
-        `shared_prefix`: the caller's promise that the first `shared_prefix` cached positions are the same in every
-        sequence (beam search: the visual prefix and the prompt, 264 of ~290 positions at the caption shapes).  Once both
-        copies of the cache hold them they are not moved again: the gather starts at that position (round 4: 122 -> 9 us
-        per step)."""
-        first = self.twin is None
-        if first:
+    def _ensure_twin(self):
+        if self.twin is None:
             self.twin = torch.empty_like(self.cache)
             self._twin_ptrs = self._ptrs(self.twin)
             self._layer_base = torch.arange(self.nl, device=self.cache.device, dtype=torch.int64)[:, None] * self.batch
             self._twin_shared = 0                    # leading positions known to be identical in cache AND twin
+
+    def prefill_fan_out(self, tokens: Optional[torch.Tensor], query_embeds: Optional[torch.Tensor], fan: int) -> torch.Tensor:
+        """Prefill ONCE per clip, then fan out: tokens [G, n_tok] / query_embeds [G, Q, H] with G = batch // fan clips are run as
+        one step of batch G (they fill the cache rows of sequences 0 .. G-1), then sequence j of the `batch` sequences takes the
+        cached rows of clip j // fan -- one gather_rows_ld per copy of the cache (into the twin with index j // fan, and back, so
+        that both copies hold the prefix).  That is the first gather of the shared_prefix bookkeeping: a later
+        reorder(idx, shared_prefix=n) with n <= the prefilled length moves generated rows only.
+        -> logits [batch, V]: row j is clip j // fan's.  (beam_search_loop instead repeats the clip `fan` times and prefills
+        identical rows `fan` times.)"""
+        assert self.pos == 0 and fan >= 1 and self.batch % fan == 0, (self.pos, self.batch, fan)
+        full, G = self.batch, self.batch // fan
+        assert (tokens is None or tokens.shape[0] == G) and (query_embeds is None or query_embeds.shape[0] == G)
+        self.batch = G                               # a step over the first G sequences' cache rows
+        try:
+            logits = self.step(tokens, query_embeds)
+        finally:
+            self.batch = full
+        self._ensure_twin()
+        dev = self.cache.device
+        seq = torch.arange(full, device=dev, dtype=torch.int64)
+        pitch, cols = self.max_len * 3 * self.H, self.pos * 3 * self.H
+        for idx, src, dst in (((self._layer_base + (seq // fan)[None]).reshape(-1), self.cache, self.twin),
+                              ((self._layer_base + seq[None]).reshape(-1), self.twin, self.cache)):
+            ops.gather_rows_ld(src.view(-1), idx.contiguous(), dst.view(-1), self.nl * full, cols, pitch, pitch)
+        self._twin_shared = self.pos                 # both copies hold the prefilled positions of every sequence
+        return logits.repeat_interleave(fan, dim=0)
+
+    def reorder(self, batch_idx: torch.Tensor, shared_prefix: int = 0):
+        """swap_key_value_dict(:1459-1473): sequence j continues from the cache of sequence batch_idx[j].  The layers
+        are one allocation, so the whole re-order is a single strided row gather over (layer, sequence) rows.
+        `shared_prefix`: the caller's promise that the first `shared_prefix` cached positions of sequence j and of sequence
+        batch_idx[j] are the same for every j -- beam search over one clip: the visual prefix and the prompt are the same in
+        every sequence (264 of ~290 positions at the caption shapes); beam search over a batch of clips: they are identical
+        within each group of K consecutive sequences, and batch_idx never leaves the group (ops.beam_advance's src_row).  Once
+        both copies of the cache hold them they are not moved again: the gather starts at that position (round 4: 122 -> 9 us
+        per step)."""
+        self._ensure_twin()
         B, nl = self.batch, self.nl
         shared_prefix = min(int(shared_prefix), self.pos)
         lo = shared_prefix if shared_prefix <= self._twin_shared else 0
@@ -254,6 +285,83 @@ def beam_search_loop(cfg, make_state: Callable[[int, int], object], tokens: torc
                            scores=torch.tensor([ranked[i][0] for i in range(num_return_gen)], dtype=torch.float32))
 
 
+class BeamState:
+    """The search state of beam_search_batched_loop for B clips x K beams, as device tensors (struct of arrays; the contract of
+    include/mpv.h: mpv_beam_advance).  `tokens` is the current token table, `tokens_alt` the one the next advance writes;
+    ops.beam_advance swaps them."""
+
+    def __init__(self, tokens: torch.Tensor, beams: int):
+        B, Lt = tokens.shape
+        dev = tokens.device
+        self.batch, self.beams, self.row_len = B, beams, Lt
+        self.tokens = tokens.to(torch.int64)[:, None, :].repeat(1, beams, 1).contiguous()
+        self.tokens_alt = torch.empty_like(self.tokens)
+        self.scores = torch.zeros((B, beams), dtype=torch.float32, device=dev)
+        self.hyp_score = torch.zeros((B, beams), dtype=torch.float64, device=dev)
+        self.hyp_order = torch.zeros((B, beams), dtype=torch.int32, device=dev)
+        self.hyp_tokens = torch.zeros((B, beams, Lt), dtype=torch.int64, device=dev)
+        self.hyp_count = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.hyp_next = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.worst = torch.full((B,), 1e9, dtype=torch.float64, device=dev)
+        self.done = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.src_row = torch.arange(B * beams, dtype=torch.int64, device=dev)
+        self.next_tok = torch.zeros(B * beams, dtype=torch.int64, device=dev)
+
+    ARRAYS = ("tokens", "scores", "hyp_score", "hyp_order", "hyp_tokens", "hyp_count", "hyp_next", "worst", "done", "src_row", "next_tok")
+
+
+def beam_search_batched_loop(cfg, make_state: Callable[[int, int], object], tokens: torch.Tensor, query_embeds=None, beam_size=5,
+                             num_return_gen=1, stop_token=None, prompt_length: Optional[int] = None, topk_fn=None, advance_fn=None):
+    """beam_search_loop for B clips in lockstep: tokens [B, L], query_embeds [B, Q, H], ONE prompt length for all clips of the call.
+    Every decode step advances B x beam_size sequences, so the decoder's weights are read once per generated position instead of
+    once per clip and position, the prefill runs once per clip (state.prefill_fan_out) and the bookkeeping of a step is one kernel.
+    A step issues state.step, topk_fn(logits, 2 * beam_size, scores), advance_fn (ops.beam_advance: per clip what one iteration of
+    beam_search_loop does; it fills bs.src_row / bs.next_tok and swaps the token tables) and state.reorder(src_row, shared_prefix);
+    nothing goes to the host except the read that tells whether every clip is done.
+    Finished clips are NOT compacted away: a clip that is done is frozen by advance_fn and keeps stepping as padding rows (stop
+    token, identity re-order) until every clip is done or the length is exhausted.
+    After the loop the state is downloaded once; the final flush of the unfinished clips and the stable ranking run on the host
+    through BeamHypotheses, as in beam_search_loop.  -> a list of B namespaces (sequences [n, Lt], scores [n]), clip by clip what
+    beam_search_loop returns for it.  `make_state(batch, max_len)` -> an object with prefill_fan_out / step / reorder
+    (DecodeState); make_state, topk_fn and advance_fn are injectable as in beam_search_loop."""
+    B, dev, K = tokens.size(0), tokens.device, int(beam_size)
+    prompt_length = int(prompt_length) if prompt_length is not None else tokens.size(1)
+    stop_token = cfg.eod_id if stop_token is None else int(stop_token)
+    tokens = torch.cat((tokens, torch.full((B, cfg.tokens_to_generate), stop_token, dtype=torch.long, device=dev)), dim=-1)
+    final_len = min(tokens.size(1), cfg.max_position_embeddings)
+    if prompt_length >= final_len:
+        raise ValueError("context length + tokens_to_generate too large")
+    Q = 0 if query_embeds is None else query_embeds.size(1)
+    state = make_state(B * K, final_len + Q)
+    bs = BeamState(tokens, K)
+    total_prompt, total_final = prompt_length + Q, final_len + Q
+    for n, context_length in enumerate(range(total_prompt, total_final)):
+        if n == 0:
+            logits = state.prefill_fan_out(tokens[:, :prompt_length].contiguous(), query_embeds, K)
+        else:
+            logits = state.step(bs.next_tok.view(-1, 1))
+        vals, idxs = topk_fn(logits, 2 * K, bs.scores.view(-1))                             # log_softmax + scores (:1790-1791)
+        advance_fn(vals, idxs, bs, vocab=logits.size(-1), pos=context_length - Q, cur_len=n + 1, first=n == 0, stop_token=stop_token)
+        if bool(bs.done.all()):                                                              # the step's one host read
+            break
+        state.reorder(bs.src_row, shared_prefix=total_prompt)
+    h = SimpleNamespace(**{k: getattr(bs, k).cpu() for k in BeamState.ARRAYS})              # one download
+    out = []
+    for b in range(B):
+        hyp = BeamHypotheses(K)
+        for s in sorted(range(int(h.hyp_count[b])), key=lambda s: int(h.hyp_order[b, s])):  # insertion order
+            hyp.beams.append((float(h.hyp_score[b, s]), h.hyp_tokens[b, s].clone(), None))
+        hyp.worst_score = float(h.worst[b])
+        if not bool(h.done[b]):
+            for k in range(K):
+                hyp.add(h.tokens[b, k].clone(), float(h.scores[b, k]))
+        ranked = sorted(hyp.beams, key=lambda x: x[0], reverse=True)
+        n_ret = min(num_return_gen, len(ranked))
+        out.append(SimpleNamespace(sequences=torch.stack([ranked[i][1] for i in range(n_ret)], dim=0).to(dev),
+                                   scores=torch.tensor([ranked[i][0] for i in range(n_ret)], dtype=torch.float32)))
+    return out
+
+
 def sample_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None, temperature=1.0, use_eod_token_for_early_termination=True,
                 stop_on_double_eol=False, stop_on_eol=False, termination_id=None, prompt_length=None, generator=None):
     """models/modeling_distributed_gpt3.py:1620-1735."""
@@ -292,7 +400,7 @@ def sample_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None, temper
 
 
 def install(gpt_cls):
-    """Adds sample / beam_search / generate to DistributedGPT3 (same signatures as the reference methods)."""
+    """Adds sample / beam_search / generate to DistributedGPT3 (same signatures as the reference methods), and beam_search_batched."""
 
     def _make_state(self):
         return lambda batch, max_len: DecodeState(self, batch, max_len)
@@ -304,6 +412,12 @@ def install(gpt_cls):
         return beam_search_loop(_gen_config(self), _make_state(self), tokens, query_embeds=query_embeds, beam_size=beam_size,
                                 num_return_gen=num_return_gen, stop_token=stop_token, prompt_length=kw.pop("prompt_length", None),
                                 topk_fn=lambda lg, k, add: ops.logprob_topk(lg, k, add=add))
+
+    def beam_search_batched(self, tokens, query_embeds=None, beam_size=5, num_return_gen=1, stop_token=None, **kw):
+        """beam_search for tokens [B, L] / query_embeds [B, Q, H] with one prompt length, B clips in lockstep -> a list of B results"""
+        return beam_search_batched_loop(_gen_config(self), _make_state(self), tokens, query_embeds=query_embeds, beam_size=beam_size,
+                                        num_return_gen=num_return_gen, stop_token=stop_token, prompt_length=kw.pop("prompt_length", None),
+                                        topk_fn=lambda lg, k, add: ops.logprob_topk(lg, k, add=add), advance_fn=ops.beam_advance)
 
     @torch.no_grad()
     def generate(self, tokens, do_sample=True, termination_id=None, *args, **kw):                # :1875-1880
@@ -317,3 +431,4 @@ def install(gpt_cls):
             self.train(was)
 
     gpt_cls.sample, gpt_cls.beam_search, gpt_cls.generate = sample, beam_search, generate
+    gpt_cls.beam_search_batched = beam_search_batched
