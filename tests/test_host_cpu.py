@@ -528,7 +528,7 @@ def test_ctypes_struct_layouts_match_the_header(tmp_path):
         pytest.skip("no gcc")
     hdr = open(os.path.join(ROOT, "include", "mpv.h")).read()
     pairs = [("mpv_gemm_epilogue", _lib.GemmEpilogue), ("mpv_attn_desc", _lib.AttnDesc), ("mpv_gpt_layer_weights", _lib.GptLayerWeights),
-             ("mpv_gpt_weights", _lib.GptWeights)]
+             ("mpv_gpt_weights", _lib.GptWeights), ("mpv_attn_plan_info", _lib.AttnPlanInfo)]
     prog = ['#include <stdio.h>', '#include <stddef.h>', '#include "mpv.h"', 'int main(void) {']
     for cname, ct in pairs:
         body = re.search(r"typedef struct " + cname + r" \{(.*?)\} " + cname + ";", hdr, re.S).group(1)

@@ -222,8 +222,9 @@ ATTN_CASES = [  # B, H, Sq, Sk, hd, causal, scale_q_bf16
     (1, 2, 33, 33, 96, True, False),
     (2, 3, 257, 257, 88, False, True),      # EVA-ViT-g spatial attention (models/eva_vit.py:413-427: 1408 / 16 heads)
     (2, 2, 32, 258, 88, False, False),      # its abstractor: 257 keys + bias_kv
-    # more (batch, head) items than CUs: the persistent double-buffered kernels (csrc/attention.hip, attn_*_pres_kernel), 2-3 items
-    # per workgroup, the second operand set and the register prefetch of the next item in use
+    # more (batch, head) items than CUs.  The ViT shape runs the persistent double-buffered forward (csrc/attention.hip,
+    # attn_fwd_pres_kernel: 2 items per workgroup, the second operand set and the register prefetch of the next item in use); the
+    # decoder shapes have no persistent instance and fill the CUs with several one-shot / paired items each (ATTN_FAMILIES below)
     (34, 8, 197, 197, 96, False, True),     # ViT-B/16 spatial attention: lean 7-tile forward instance
     (40, 16, 160, 160, 64, True, False),    # decoder at config B (S = 128 + 32)
     (20, 16, 208, 208, 64, True, False),    # decoder at the YAML-as-shipped geometry (S = 128 + 80)
@@ -245,6 +246,31 @@ ATTN_CASES = [  # B, H, Sq, Sk, hd, causal, scale_q_bf16
 ]
 
 
+# The kernel family the comments above promise per case, per role (forward, dQ, dK/dV): asserted on the plan (csrc/attention.hip:
+# attn_plan through mpv_attn_plan_describe), so a dispatch that stops routing a shape to its family fails here, not only in speed.
+ATTN_FAMILIES = {
+    (34, 8, 197, 197, 96, False, True): ("attn_fwd_pres_kernel<96, 7, 8, 512, 1, true>", "attn_bwd_dq_duo96_kernel<256>", "attn_bwd_dkv_duo96_kernel<256>"),
+    (40, 16, 160, 160, 64, True, False): ("attn_fwd_pair64_kernel<5, 192, 3>", "attn_bwd_dq_pair64_kernel<192, 3>", "attn_bwd_dkv_res_kernel<64, 320, 3>"),
+    (20, 16, 208, 208, 64, True, False): ("attn_fwd_pair64_kernel<7, 256, 2>", "attn_bwd_dq_pair64_kernel<256, 3>", "attn_bwd_dkv_pair64_kernel<256, 3>"),
+    (36, 8, 100, 100, 64, False, False): ("attn_fwd_res_kernel<64, 0, 5, 320, 3>", "attn_bwd_dq_res_kernel<64, 0, 320, 3>", "attn_bwd_dkv_res_kernel<64, 320, 3>"),
+    (2, 4, 160, 160, 64, True, False): ("attn_fwd_pair64_kernel<5, 192, 3>", "attn_bwd_dq_pair64_kernel<192, 3>", "attn_bwd_dkv_res_kernel<64, 320, 3>"),
+    (3, 4, 33, 33, 64, True, False): ("attn_fwd_pair64_kernel<5, 192, 3>", "attn_bwd_dq_pair64_kernel<192, 3>", "attn_bwd_dkv_res_kernel<64, 320, 3>"),
+    (5, 2, 100, 100, 64, True, False): ("attn_fwd_pair64_kernel<5, 192, 3>", "attn_bwd_dq_pair64_kernel<192, 3>", "attn_bwd_dkv_res_kernel<64, 320, 3>"),
+    (2, 2, 8, 8, 64, True, False): ("attn_fwd_pair64_kernel<5, 192, 3>", "attn_bwd_dq_pair64_kernel<192, 3>", "attn_bwd_dkv_res_kernel<64, 320, 3>"),
+    (9, 4, 224, 224, 64, True, False): ("attn_fwd_pair64_kernel<7, 256, 2>", "attn_bwd_dq_pair64_kernel<256, 3>", "attn_bwd_dkv_pair64_kernel<256, 3>"),
+    (2, 2, 129, 129, 64, True, True): ("attn_fwd_pair64_kernel<5, 192, 3>", "attn_bwd_dq_pair64_kernel<192, 3>", "attn_bwd_dkv_res_kernel<64, 320, 3>"),
+    (33, 32, 160, 160, 64, True, False): ("attn_fwd_pair64_kernel<5, 192, 3>", "attn_bwd_dq_pair64_kernel<192, 3>", "attn_bwd_dkv_res_kernel<64, 320, 3>"),
+    (5, 4, 197, 197, 96, False, False): ("attn_fwd_res_kernel<96, 7>", "attn_bwd_dq_duo96_kernel<256>", "attn_bwd_dkv_duo96_kernel<256>"),
+    (2, 2, 193, 193, 96, False, True): ("attn_fwd_res_kernel<96, 7>", "attn_bwd_dq_duo96_kernel<256>", "attn_bwd_dkv_duo96_kernel<256>"),
+    (2, 2, 224, 224, 96, False, False): ("attn_fwd_res_kernel<96, 7>", "attn_bwd_dq_duo96_kernel<256>", "attn_bwd_dkv_duo96_kernel<256>"),
+}
+
+
+def planned(ops, *args, **kw):
+    """The kernel instances the forward, the dQ and the dK/dV launch of these attn_fwd / attn_bwd arguments go to."""
+    return tuple(ops.attn_plan(role, *args, **kw)["variant"] for role in (0, 1, 2))
+
+
 @pytest.mark.parametrize("B,H,Sq,Sk,hd,causal,sqb", ATTN_CASES)
 def test_attention_fwd_bwd(dev, B, H, Sq, Sk, hd, causal, sqb):
     from youku_mplug_amd import ops
@@ -253,6 +279,8 @@ def test_attention_fwd_bwd(dev, B, H, Sq, Sk, hd, causal, sqb):
     o = torch.empty_like(q)
     scale = hd ** -0.5
     lay = ops.AttnLayout((Sq * H * hd, hd, H * hd), (Sk * H * hd, hd, H * hd), (Sk * H * hd, hd, H * hd), (Sq * H * hd, hd, H * hd))
+    if (B, H, Sq, Sk, hd, causal, sqb) in ATTN_FAMILIES:
+        assert planned(ops, q, k, v, o, lay, B, H, Sq, Sk, hd, causal=causal, scale=scale, scale_q_bf16=sqb) == ATTN_FAMILIES[(B, H, Sq, Sk, hd, causal, sqb)]
     lse = ops.attn_fwd(q, k, v, o, lay, B, H, Sq, Sk, hd, causal=causal, scale=scale, scale_q_bf16=sqb)
     qt, kt, vt = (t.permute(0, 2, 1, 3) for t in (q, k, v))
     qr, kr, vr = (t.float().requires_grad_(True) for t in (qt, kt, vt))
@@ -327,7 +355,20 @@ def test_gemm_colscale_epilogue(dev):
         ops.gemm(a, w, M, N, K, bias=b, residual=plain, colscale=(ncols, sc))
 
 
-@pytest.mark.parametrize("B", [2, 80])      # 80 x 4 heads = 320 items: the persistent kernels
+def test_attention_plan_on_the_device_names_the_persistent_forward(dev):
+    """mpv_attn_plan_describe with the real CU count: 34 x 8 ViT-B/16 items (40 x 8 = 320 with the batch padded to groups of 8) are more
+    than the CUs, so the forward is the lean persistent instance, one workgroup per CU; nothing is launched."""
+    from youku_mplug_amd import ops
+    B, H, S, hd = 34, 8, 197, 96
+    t = torch.empty(1, dtype=torch.bfloat16, device=dev)
+    ncu = torch.cuda.get_device_properties(dev).multi_processor_count // 8 * 8
+    st = (S * H * hd, hd, H * hd)
+    plan = ops.attn_plan(0, t, t, t, t, ops.AttnLayout(st, st, st, st), B, H, S, S, hd, scale=hd ** -0.5, scale_q_bf16=True)
+    assert plan["variant"] == "attn_fwd_pres_kernel<96, 7, 8, 512, 1, true>", plan
+    assert plan["grid"] == (min(320, ncu), 1) and plan["block"] == 448 and plan["lds_bytes"] <= plan["lds_limit"] <= 160 * 1024, plan
+
+
+@pytest.mark.parametrize("B", [2, 80])      # 80 x 4 heads = 320 items
 def test_attention_packed_gpt_layout_and_dropout(dev, B):
     """GPT layout: qkv [B,S,np,3*hn] head-interleaved (modeling_distributed_gpt3.py:895-902)."""
     from youku_mplug_amd import ops
@@ -339,6 +380,10 @@ def test_attention_packed_gpt_layout_and_dropout(dev, B):
     lay = ops.AttnLayout(st, st, st, (S * Hh, hn, Hh))
     q, k, v = qkv[..., :hn], qkv[..., hn:2 * hn], qkv[..., 2 * hn:]
     ops.attn_fwd(q, k, v, o, lay, B, np_, S, S, hn, causal=True, scale=hn ** -0.5)
+    # 96 rows = 3 blocks of the causal head_dim-64 shape: the paired forward and dQ, the <64, 320, 3> one-shot dK/dV, with and without dropout
+    for p in (0.0, 0.1):
+        assert planned(ops, q, k, v, o, lay, B, np_, S, S, hn, causal=True, scale=hn ** -0.5, dropout_p=p) == \
+            ("attn_fwd_pair64_kernel<5, 192, 3>", "attn_bwd_dq_pair64_kernel<192, 3>", "attn_bwd_dkv_res_kernel<64, 320, 3>")
     ref, _ = ref_attention(q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3), v.permute(0, 2, 1, 3), True, hn ** -0.5, False)
     close(o.view(B, S, np_, hn).permute(0, 2, 1, 3), ref, 1.5e-2, "packed layout")
     # dropout: deterministic in (seed, offset); mean preserved; backward consistent with forward mask
@@ -367,7 +412,7 @@ def test_attention_packed_gpt_layout_and_dropout(dev, B):
     assert abs(lhs - rhs) <= 1e-4 * do.float().norm().item() * o3.float().norm().item(), (lhs, rhs)
 
 
-@pytest.mark.parametrize("B,H", [(1, 2), (40, 8)])      # (40, 8): 320 items -> the persistent kernels
+@pytest.mark.parametrize("B,H", [(1, 2), (40, 8)])      # (40, 8): 320 items, more than one per CU (the plan is asserted below)
 def test_attention_dropout_masks_forward_vs_dkv(dev, B, H):
     """The masks the forward and the dK/dV kernels draw, recovered element by element (q = k = 0 -> uniform
     probabilities, one-hot V and dO): identical, and the keep rate is 1 - p."""
@@ -383,6 +428,9 @@ def test_attention_dropout_masks_forward_vs_dkv(dev, B, H):
         do[:] = eye
         o, dq, dk, dv = (torch.empty_like(q) for _ in range(4))
         kw = dict(causal=causal, scale=hd ** -0.5, dropout_p=0.25, seed=5, offset=9)
+        assert planned(ops, q, k, v, o, lay, B, H, S, S, hd, causal=causal, scale=hd ** -0.5, dropout_p=0.25) == (
+            ("attn_fwd_pair64_kernel<5, 192, 3>", "attn_bwd_dq_pair64_kernel<192, 3>", "attn_bwd_dkv_res_kernel<64, 320, 3>") if causal else
+            ("attn_fwd_res_kernel<64, 0, 5, 320, 3>", "attn_bwd_dq_res_kernel<64, 0, 320, 3>", "attn_bwd_dkv_res_kernel<64, 320, 3>"))
         lse = ops.attn_fwd(q, k, v, o, lay, B, H, S, S, hd, **kw)
         ops.attn_bwd(q, k, v, o, lse, do, dq, dk, dv, lay, B, H, S, S, hd, **kw)
         fwd_mask = o.float().permute(0, 2, 1, 3) > 0                          # [B,H,q,key]
@@ -394,7 +442,7 @@ def test_attention_dropout_masks_forward_vs_dkv(dev, B, H):
         assert abs(rate - 0.75) < 0.02, rate
 
 
-@pytest.mark.parametrize("B,H", [(1, 2), (40, 8)])      # (40, 8): 320 items -> the persistent kernels
+@pytest.mark.parametrize("B,H", [(1, 2), (40, 8)])      # (40, 8): 320 items, more than one per CU (the plan is asserted below)
 def test_attention_dropout_backward_vs_reference_with_recovered_mask(dev, B, H):
     """dQ / dK / dV under probability dropout against autograd through the SAME mask: the mask is a function of (seed, offset,
     row, key) only, so it is first recovered from a forward with q = k = 0 and one-hot V, then applied in a torch reference."""
@@ -407,6 +455,8 @@ def test_attention_dropout_backward_vs_reference_with_recovered_mask(dev, B, H):
     eye = z.clone()
     eye[:] = torch.eye(S, hd, dtype=torch.bfloat16, device=dev).view(1, S, 1, hd)
     o = torch.empty_like(z)
+    assert planned(ops, z, z, eye, o, lay, B, H, S, S, hd, causal=True, scale=hd ** -0.5, dropout_p=pdrop) == \
+        ("attn_fwd_pair64_kernel<5, 192, 3>", "attn_bwd_dq_pair64_kernel<192, 3>", "attn_bwd_dkv_res_kernel<64, 320, 3>")
     ops.attn_fwd(z, z, eye, o, lay, B, H, S, S, hd, **kw)
     mask = (o.float().permute(0, 2, 1, 3) > 0).float()                       # [B,H,q,key] keep mask (visible part)
     q, k, v, do = (rn(B, S, H, hd, dev=dev, seed=50 + i) for i in range(4))
@@ -604,6 +654,8 @@ def test_attention_decode_step(dev, B, H, Sk, hd, sqb):
     o = torch.empty_like(q)
     scale = hd ** -0.5
     lay = ops.AttnLayout((H * hd, hd, H * hd), (Sk * H * hd, hd, H * hd), (Sk * H * hd, hd, H * hd), (H * hd, hd, H * hd))
+    assert ops.attn_plan(0, q, k, v, o, lay, B, H, 1, Sk, hd, causal=True, scale=scale, scale_q_bf16=sqb)["variant"] == \
+        ("attn_decode_kernel<8>" if hd <= 64 else "attn_decode_kernel<16>")
     lse = ops.attn_fwd(q, k, v, o, lay, B, H, 1, Sk, hd, causal=True, scale=scale, scale_q_bf16=sqb)
     qf = (q * scale).float() if sqb else q.float() * scale
     s = torch.einsum("bqhd,bkhd->bhqk", qf, k.float())

@@ -42,6 +42,11 @@ class AttnDesc(C.Structure):
     ]
 
 
+class AttnPlanInfo(C.Structure):
+    _fields_ = [("variant", C.c_char_p), ("grid_x", C.c_uint), ("grid_y", C.c_uint), ("block", c_int), ("lds_bytes", c_int),
+                ("lds_limit", c_int)]
+
+
 class AttnPrefixDesc(C.Structure):
     _fields_ = [
         ("q", c_void_p), ("k", c_void_p), ("v", c_void_p), ("pk", c_void_p), ("pv", c_void_p), ("o", c_void_p),
@@ -97,6 +102,8 @@ _SIGS = {
     "mpv_ln_stream_bwd": (c_int, [c_void_p] * 8 + [c_float, c_uint64, c_uint64] + [c_int64] * 4 + _RM + _RM + [c_void_p]),
     "mpv_attn_fwd": (c_int, [C.POINTER(AttnDesc), c_void_p]),
     "mpv_attn_bwd": (c_int, [C.POINTER(AttnDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mpv_attn_plan_describe": (c_int, [C.POINTER(AttnDesc), c_int, C.POINTER(AttnPlanInfo)]),
+    "mpv_temporal_attn_plan_describe": (c_int, [c_int] * 6 + [C.POINTER(AttnPlanInfo)]),
     "mpv_attn_prefix_fwd": (c_int, [C.POINTER(AttnPrefixDesc), c_void_p]),
     "mpv_temporal_attn_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int64, c_int64, c_int, c_int, c_int,
                                       c_float, c_void_p]),

@@ -23,12 +23,14 @@
 #include <type_traits>
 
 #include "mpv_common.h"
+#include "attention_layout.h"
 #include "../../include/mpv.h"
+
+using namespace attn_layout;      // ROWB and every LDS region / size function: one definition for kernels and host
 
 namespace {
 
 constexpr int CH = 64;          // rows per LDS chunk
-constexpr int ROWB = 208;       // LDS row pitch in bytes (96 bf16 + 16 pad: conflict-free ds_read_b128)
 constexpr int CHUNK_BYTES = CH * ROWB;
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 // a wave's DS ops retire in order; wait for them and stop the compiler from moving LDS traffic across
@@ -694,8 +696,6 @@ __device__ __forceinline__ void dma_rows(const __amdgpu_buffer_rsrc_t src, char*
     __builtin_amdgcn_raw_ptr_buffer_load_lds(src, (lds_void_t*)(lds + i * 1024), 16, off, 0, 0, 0);
   }
 }
-// bytes of one LDS region of `rows` rows padded to whole tiles (device twin of the host's res_region)
-__device__ __forceinline__ int region_bytes(int rows, int pitch) { return (((rows + 31) / 32 * 32) * pitch + 1023) / 1024 * 1024; }
 
 // NTC > 0: non-causal with exactly NTC key tiles for every wave, known at compile time -- the tile loops become
 // straight-line code (no per-tile branch), so the scheduler can hoist the next tile's LDS reads and MFMA chain above the
@@ -715,7 +715,7 @@ __global__ __launch_bounds__(THREADS, WPE) void attn_fwd_res_kernel(const AttnAr
   if (!decode_bh(p, b, h)) return;
   const int bh = b * p.heads + h;
   char* vl = rsm;                                                         // [sk][208 B]
-  char* kl = rsm + region_bytes(p.sk, ROWB);                               // [sk][208 B]; both regions hold whole zero-padded tiles
+  char* kl = rsm + tile_region(p.sk, ROWB);                               // [sk][208 B]; both regions hold whole zero-padded tiles
   const bf16* qb = p.q + b * p.q_bs + h * p.q_hs;
   const __amdgpu_buffer_rsrc_t ksrc = make_rsrc(p.k + b * p.k_bs + h * p.k_hs, (uint32_t)(((long long)(p.sk - 1) * p.k_rs + p.hd) * 2));
   const __amdgpu_buffer_rsrc_t vsrc = make_rsrc(p.v + b * p.v_bs + h * p.v_hs, (uint32_t)(((long long)(p.sk - 1) * p.v_rs + p.hd) * 2));
@@ -843,7 +843,7 @@ __global__ __launch_bounds__(THREADS, WPE) void attn_bwd_dq_res_kernel(const Att
   if (!decode_bh(p, b, h)) return;
   const int bh = b * p.heads + h;
   char* vl = rsm;                                                         // [sk][208 B]
-  char* kl = rsm + region_bytes(p.sk, ROWB);                               // [sk][208 B]; both regions hold whole zero-padded tiles
+  char* kl = rsm + tile_region(p.sk, ROWB);                               // [sk][208 B]; both regions hold whole zero-padded tiles
   const __amdgpu_buffer_rsrc_t ksrc = make_rsrc(p.k + b * p.k_bs + h * p.k_hs, (uint32_t)(((long long)(p.sk - 1) * p.k_rs + p.hd) * 2));
   const __amdgpu_buffer_rsrc_t vsrc = make_rsrc(p.v + b * p.v_bs + h * p.v_hs, (uint32_t)(((long long)(p.sk - 1) * p.v_rs + p.hd) * 2));
   dma_rows<HD, ROWB>(ksrc, kl, p.sk, p.k_rs, wave, nwaves, lane, p.hd);
@@ -976,9 +976,9 @@ __global__ __launch_bounds__(THREADS, WPE) void attn_bwd_dkv_res_kernel(const At
   // (hardware returns 0 for out-of-range LDS reads); the fp32 stats sit in front so no bf16 fragment read
   // can ever interpret them as (possibly Inf/NaN) bf16.
   float* sl = (float*)rsm;                                                  // [lse*log2e | delta] x qrows
-  char* vl = rsm + ((2 * qrows * 4 + 1023) / 1024) * 1024;                  // V  [sk][208 B] (head_dim > 64 only: zero bytes otherwise)
-  char* dl = vl + (HD > 64 ? region_bytes(p.sk, ROWB) : 0);                  // dO [sq][208 B]
-  char* ql = dl + region_bytes(p.sq, ROWB);                                  // Q  [sq][208 B]
+  char* vl = rsm + stat_bytes(qrows);                                         // V  [sk][208 B] (head_dim > 64 only: zero bytes otherwise)
+  char* dl = vl + res_dkv_v_region(p.sk, HD);                                // dO [sq][208 B]
+  char* ql = dl + tile_region(p.sq, ROWB);                                   // Q  [sq][208 B]
   const __amdgpu_buffer_rsrc_t qsrc = make_rsrc(p.q + b * p.q_bs + h * p.q_hs, (uint32_t)(((long long)(p.sq - 1) * p.q_rs + p.hd) * 2));
   const __amdgpu_buffer_rsrc_t dosrc = make_rsrc(p.dO + b * p.o_bs + h * p.o_hs, (uint32_t)(((long long)(p.sq - 1) * p.o_rs + p.hd) * 2));
   // The wave's K rows and the thread's first pair of statistics are requested BEFORE the LDS-DMA of the images: the compiler puts
@@ -1143,12 +1143,6 @@ __global__ __launch_bounds__(THREADS, WPE) void attn_bwd_dkv_res_kernel(const At
 // piece is zero-filled): a 32-row tile read past the last row lands in the next region, which always holds finite data of
 // some item (or, past the allocation, reads as zero) -- every product with such a row is masked by a select or multiplied
 // by an exact zero probability.
-template <int HD>
-struct PresPitch {
-  static constexpr int R = HD * 2 + 16;                     // row-fragment (ds_read_b128) images: conflict-free at 144 / 176 / 208 B
-  static constexpr int C = HD > 80 ? HD * 2 : HD * 2 + 16;  // images that only serve transposing column reads: 192 B at head_dim 96
-};
-__device__ __forceinline__ int pres_region(int rows, int pitch) { return (rows * pitch + 1023) / 1024 * 1024; }
 __device__ __forceinline__ i32x4 pres_rsrc(const void* ptr, uint32_t bytes) {
   const uint64_t a = (uint64_t)ptr;
   return i32x4{(int)(uint32_t)a, (int)((uint32_t)(a >> 32) & 0xffffu), (int)bytes, 0x00020000};
@@ -1225,11 +1219,11 @@ template <int HD, int NTC = 0, int NTMAX = 8, int THREADS = 512, int WPE = 1, bo
 __global__ __launch_bounds__(THREADS, WPE) void attn_fwd_pres_kernel(const AttnArgs p, const int nitems) {
   constexpr int NS = HD / 16;
   constexpr int NDT = (HD + 31) / 32;
-  constexpr int KP = PresPitch<HD>::R, VP = PresPitch<HD>::C;
+  constexpr int KP = pres_pitch_r(HD), VP = pres_pitch_c(HD);
   extern __shared__ __attribute__((aligned(1024))) char rsm[];
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nwaves = blockDim.x >> 6;
-  const int vbytes = pres_region(p.sk, VP), setb = vbytes + pres_region(p.sk, KP);      // set = [V | K]
+  const int vbytes = packed_region(p.sk, VP), setb = pres_set(p.sk, HD);      // set = [V | K]
   const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_void_t*)rsm;
   const int step = gridDim.x;
   const int q0 = wave * 32;
@@ -1414,8 +1408,7 @@ __global__ __launch_bounds__(256) void temporal_attn_kernel(const TempArgs p) {
   extern __shared__ __attribute__((aligned(16))) float tsm[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int T = TC ? TC : p.T, hd = HDC ? HDC : p.hd, ld = hd + 4, D = p.heads * hd, H4 = hd / 4;
-  const int per_wave = (BWD ? 4 : 3) * T * ld + (BWD ? 2 : 1) * T * (T + 1);
-  float* qs = tsm + wave * ((per_wave + 3) & ~3);
+  float* qs = tsm + wave * temporal_f32_wave_floats(BWD, T, hd);
   float* ks = qs + T * ld;
   float* vs = ks + T * ld;
   float* dos = vs + T * ld;                         // BWD only: dO [T][ld]
@@ -1727,263 +1720,6 @@ int check_desc(const mpv_attn_desc* d, const char* who) {
 
 }  // namespace
 
-constexpr int RES_MAX_ROWS = 256;
-// whole zero-filled 32-row tiles per region (one workgroup per CU is register-bound anyway: 90 KiB at S = 197 costs nothing)
-static size_t res_region(int rows, int pitch) { return ((size_t)((rows + 31) / 32 * 32) * pitch + 1023) / 1024 * 1024; }
-static size_t res_lds_bytes(int rows, bool stats) {
-  const int padded = (rows + 31) / 32 * 32;
-  return 2 * res_region(rows, ROWB) + (stats ? (2 * (size_t)padded * sizeof(float) + 1023) / 1024 * 1024 : 0);
-}
-template <typename K>
-static void allow_lds(K kernel, int bytes = 120 * 1024) {
-  (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-}
-// ---- persistent variants: host side ----
-constexpr size_t PRES_LDS_MAX = 160 * 1024;
-static size_t pres_region_h(int rows, int pitch) { return ((size_t)rows * pitch + 1023) / 1024 * 1024; }
-static int pres_pitch_r(int hdc) { return hdc * 2 + 16; }
-static int pres_pitch_c(int hdc) { return hdc > 80 ? hdc * 2 : hdc * 2 + 16; }
-static int attn_ncu() {
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-    ncu = ncu / 8 * 8 > 0 ? ncu / 8 * 8 : 8;      // whole XCD groups: item i and workgroup i % grid then share i % 8
-  }
-  return ncu;
-}
-// MPV_ATTN_PERSIST (measurement knob, read once): 0 = the one-shot resident kernels only; 1 (default) = the persistent
-// double-buffered kernels where a workgroup gets more than one (batch, head) item; 2 = also for a single item per workgroup
-static int pres_mode() {
-  static int mode = -1;
-  if (mode < 0) {
-    const char* e = getenv("MPV_ATTN_PERSIST");
-    mode = e ? atoi(e) : 1;
-  }
-  return mode;
-}
-// the persistent kernels address every operand with 32-bit element offsets from its base pointer
-static bool pres_offsets_ok(const mpv_attn_desc* d) {
-  auto fits = [&](int64_t bs, int64_t hs, int64_t rs, int rows) {
-    return bs >= 0 && hs >= 0 && rs > 0 && rs < (1 << 20) &&
-           (int64_t)(d->batch + 7) * bs + (int64_t)d->heads * hs + (int64_t)(rows + 32) * rs + 128 < (1LL << 31) / 2;
-  };
-  return fits(d->q_bs, d->q_hs, d->q_rs, d->sq) && fits(d->k_bs, d->k_hs, d->k_rs, d->sk) && fits(d->v_bs, d->v_hs, d->v_rs, d->sk) &&
-         fits(d->o_bs, d->o_hs, d->o_rs, d->sq) && (int64_t)(d->batch + 7) * d->heads * d->sq < (1LL << 30);
-}
-static bool pres_wanted(int nitems) { return pres_mode() >= 2 || (pres_mode() == 1 && nitems > attn_ncu()); }
-static void pres_attr_once() {
-  static bool done = false;
-  if (done) return;
-  const int L = (int)PRES_LDS_MAX;
-  allow_lds(attn_fwd_pres_kernel<96, 7>, L); allow_lds(attn_fwd_pres_kernel<96, 7, 8, 512, 1, true>, L);
-  done = true;
-}
-// Instances exist where the structure measured faster than the one-shot kernels and the item loop fits the register file
-// without scratch (a scratch reload sits behind an s_waitcnt vmcnt(0), which would drain the next item's DMA in the middle of
-// the current one): the 7-tile non-causal head_dim-96 forward (ViT-B/16 spatial attention).
-static bool pres_fwd_has(int hdc, const mpv_attn_desc* d) {
-  return hdc == 96 && !d->causal && d->dropout_p == 0.f && (d->sk + 31) / 32 == 7;
-}
-
-static void res_attr_once() {
-  static bool done = false;
-  if (done) return;
-  allow_lds(attn_fwd_res_kernel<64>); allow_lds(attn_fwd_res_kernel<64, 0, 5, 320, 3>); allow_lds(attn_fwd_res_kernel<80>); allow_lds(attn_fwd_res_kernel<96>); allow_lds(attn_fwd_res_kernel<96, 7>);
-  allow_lds(attn_bwd_dq_res_kernel<64>); allow_lds(attn_bwd_dq_res_kernel<64, 0, 320, 3>); allow_lds(attn_bwd_dq_res_kernel<80>); allow_lds(attn_bwd_dq_res_kernel<96>); allow_lds(attn_bwd_dq_res_kernel<96, 7>);
-  allow_lds(attn_bwd_dkv_res_kernel<64, 512>); allow_lds(attn_bwd_dkv_res_kernel<64, 320, 3>); allow_lds(attn_bwd_dkv_res_kernel<80, 512>); allow_lds(attn_bwd_dkv_res_kernel<96, 512>);
-  done = true;
-}
-
-// ---- paired-block causal kernels (attention_pair.inc): host side ----
-// MPV_ATTN_PAIR (measurement knob, read once): 0 = the one-shot resident kernels; 1 (default) = the paired forward and dQ kernels, the
-// paired dK/dV kernel above 5 blocks; 2 = the paired dK/dV kernel everywhere
-static int pair_mode() {
-  static int mode = -1;
-  if (mode < 0) {
-    const char* e = getenv("MPV_ATTN_PAIR");
-    mode = e ? atoi(e) : 1;
-  }
-  return mode;
-}
-// MPV_ATTN_DUO (measurement knob, read once): 0 = the one-shot 7-wave backward kernels of the ViT shape; 1 = dQ as two 4-wave items
-// per CU; 2 (default) = dQ and dK/dV
-static int duo_mode() {
-  static int mode = -1;
-  if (mode < 0) {
-    const char* e = getenv("MPV_ATTN_DUO");
-    mode = e ? atoi(e) : 2;
-  }
-  return mode;
-}
-constexpr int PAIR_MAX_ROWS = 224;
-static bool pair_ok(const mpv_attn_desc* d) {
-  return pair_mode() > 0 && d->head_dim == 64 && d->causal && d->sq == d->sk && d->sk <= PAIR_MAX_ROWS;
-}
-static size_t pair_lds(int rows) { return 2 * (size_t)((rows + 31) / 32) * 32 * 128; }      // two images of whole 32-row tiles (z_region)
-
-extern "C" int mpv_attn_fwd(const mpv_attn_desc* d, hipStream_t stream) {
-  int rc = check_desc(d, "mpv_attn_fwd");
-  if (rc) return rc;
-  AttnArgs a = {};
-  fill_args(a, d);
-  if (d->sq == 1 && d->dropout_p == 0.f && d->sk <= DEC_MAX_SK && (d->o_hs % 8) == 0 && ((uintptr_t)d->o & 15) == 0) {      // decode step of KV-cache generation
-    const dim3 dg((unsigned)(d->batch * d->heads));
-    if (d->head_dim <= 64) hipLaunchKernelGGL(attn_decode_kernel<8>, dg, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL(attn_decode_kernel<16>, dg, dim3(256), 0, stream, a);
-    return mpv_check_launch("mpv_attn_fwd");
-  }
-  if (d->sk <= RES_MAX_ROWS) {
-    res_attr_once();
-    const int nw = waves_for(d->sq);
-    const int gy = (d->batch + 7) / 8 * 8 * d->heads;   // decode_bh() needs whole groups of 8 sequences
-    dim3 grid((d->sq + 32 * nw - 1) / (32 * nw), gy), block(64 * nw);
-    if (pair_ok(d)) {
-      const int nb = (d->sk + 31) / 32;
-      const dim3 pg(1, gy), pb(64 * ((nb + 1) / 2));
-      if (nb <= 5) hipLaunchKernelGGL((attn_fwd_pair64_kernel<5, 192, 3>), pg, pb, pair_lds(d->sk), stream, a);
-      else hipLaunchKernelGGL((attn_fwd_pair64_kernel<7, 256, 2>), pg, pb, pair_lds(d->sk), stream, a);
-      return mpv_check_launch("mpv_attn_fwd");
-    }
-    const int hdc = d->head_dim <= 64 ? 64 : d->head_dim <= 80 ? 80 : 96;
-    const size_t plds = 2 * (pres_region_h(d->sk, pres_pitch_r(hdc)) + pres_region_h(d->sk, pres_pitch_c(hdc)));
-    if (grid.x == 1 && plds <= PRES_LDS_MAX && pres_wanted(gy) && pres_offsets_ok(d) && pres_fwd_has(hdc, d)) {
-      pres_attr_once();
-      const dim3 pg((unsigned)(gy < attn_ncu() ? gy : attn_ncu()));
-      if (d->sk <= 200) {
-        hipLaunchKernelGGL((attn_fwd_pres_kernel<96, 7, 8, 512, 1, true>), pg, block, plds, stream, a, gy);   // ViT-B/16: 197 keys
-      } else {
-        hipLaunchKernelGGL((attn_fwd_pres_kernel<96, 7>), pg, block, plds, stream, a, gy);
-      }
-      return mpv_check_launch("mpv_attn_fwd");
-    }
-    const size_t lds = res_lds_bytes(d->sk, false);
-    switch (d->head_dim <= 64 ? 64 : d->head_dim <= 80 ? 80 : 96) {
-      case 64:
-        if (d->sk <= 160 && nw <= 5) hipLaunchKernelGGL((attn_fwd_res_kernel<64, 0, 5, 320, 3>), grid, block, lds, stream, a);
-        else hipLaunchKernelGGL((attn_fwd_res_kernel<64>), grid, block, lds, stream, a);
-        break;
-      case 80: hipLaunchKernelGGL((attn_fwd_res_kernel<80>), grid, block, lds, stream, a); break;
-      default:
-        if (!d->causal && d->dropout_p == 0.f && (d->sk + 31) / 32 == 7) hipLaunchKernelGGL((attn_fwd_res_kernel<96, 7>), grid, block, lds, stream, a);   // ViT-B/16 spatial: 197 keys
-        else hipLaunchKernelGGL((attn_fwd_res_kernel<96>), grid, block, lds, stream, a);
-        break;
-    }
-    return mpv_check_launch("mpv_attn_fwd");
-  }
-  const int nw = waves_for(d->sq);
-  dim3 grid((d->sq + 32 * nw - 1) / (32 * nw), d->batch * d->heads), block(64 * nw);
-  switch (d->head_dim <= 64 ? 64 : d->head_dim <= 80 ? 80 : 96) {
-    case 64: hipLaunchKernelGGL((attn_fwd_kernel<64>), grid, block, 0, stream, a); break;
-    case 80: hipLaunchKernelGGL((attn_fwd_kernel<80>), grid, block, 0, stream, a); break;
-    default: hipLaunchKernelGGL((attn_fwd_kernel<96>), grid, block, 0, stream, a); break;
-  }
-  return mpv_check_launch("mpv_attn_fwd");
-}
-
-extern "C" int mpv_attn_bwd(const mpv_attn_desc* d, const void* dO, void* dq, void* dk, void* dv, float* delta,
-                            hipStream_t stream) {
-  int rc = check_desc(d, "mpv_attn_bwd");
-  if (rc) return rc;
-  MPV_REQUIRE(dO && dq && dk && dv && delta && d->lse, MPV_E_ARG, "mpv_attn_bwd: null pointer");
-  AttnArgs a = {};
-  fill_args(a, d);
-  a.dO = (const bf16*)dO;
-  a.dq = (bf16*)dq;
-  a.dk = (bf16*)dk;
-  a.dv = (bf16*)dv;
-  a.delta = delta;
-  // delta = rowsum(dO * O) is produced by the dQ kernel (row_delta) and read by the dK/dV kernel launched after it
-  if (d->sk <= RES_MAX_ROWS && d->sq <= RES_MAX_ROWS) {
-    res_attr_once();
-    const int nw = waves_for(d->sq);
-    const int gy = (d->batch + 7) / 8 * 8 * d->heads;
-    const int nwk = waves_for(d->sk);
-    dim3 gq((d->sq + 32 * nw - 1) / (32 * nw), gy), gk((d->sk + 32 * nwk - 1) / (32 * nwk), gy);
-    const size_t lq = res_lds_bytes(d->sk, false), lk = res_lds_bytes(d->sq, true) + (d->head_dim > 64 ? res_region(d->sk, ROWB) : 0);
-    const int hdc = d->head_dim <= 64 ? 64 : d->head_dim <= 80 ? 80 : 96;
-    const bool small64 = hdc == 64 && d->sk <= 160 && d->sq <= 160 && nw <= 5 && nwk <= 5;     // two workgroups per CU (see attn_fwd_res_kernel)
-    const bool vit7 = hdc == 96 && !d->causal && d->dropout_p == 0.f && (d->sk + 31) / 32 == 7;
-    // dQ first: it also stores delta = rowsum(dO * O), which the dK/dV kernel reads
-    if (pair_ok(d)) {      // paired-block dQ role (attention_pair.inc); the dK/dV role stays with the one-shot kernel below
-      const int nb = (d->sk + 31) / 32;
-      const dim3 pg(1, gy), pb(64 * ((nb + 1) / 2));
-      if (nb <= 5) hipLaunchKernelGGL((attn_bwd_dq_pair64_kernel<192, 3>), pg, pb, pair_lds(d->sk), stream, a);
-      else hipLaunchKernelGGL((attn_bwd_dq_pair64_kernel<256, 3>), pg, pb, pair_lds(d->sk), stream, a);
-    } else {
-      switch (hdc) {
-        case 64:
-          if (small64) hipLaunchKernelGGL((attn_bwd_dq_res_kernel<64, 0, 320, 3>), gq, dim3(64 * nw), lq, stream, a);
-          else hipLaunchKernelGGL((attn_bwd_dq_res_kernel<64>), gq, dim3(64 * nw), lq, stream, a);
-          break;
-        case 80: hipLaunchKernelGGL((attn_bwd_dq_res_kernel<80>), gq, dim3(64 * nw), lq, stream, a); break;
-        default:
-          if (vit7 && duo_mode() && d->sq == d->sk && d->head_dim == 96) {      // two 4-wave items per CU (attention_duo.inc)
-            static bool attr = false;
-            if (!attr) {
-              allow_lds(attn_bwd_dq_duo96_kernel<256>, 80 * 1024);
-              attr = true;
-            }
-            const size_t dl = (((size_t)d->sk * 208 + 1023) / 1024 + ((size_t)d->sk * 192 + 1023) / 1024) * 1024;
-            hipLaunchKernelGGL((attn_bwd_dq_duo96_kernel<256>), dim3(1, gy), dim3(256), dl, stream, a);
-          } else if (vit7) hipLaunchKernelGGL((attn_bwd_dq_res_kernel<96, 7>), gq, dim3(64 * nw), lq, stream, a);
-          else hipLaunchKernelGGL((attn_bwd_dq_res_kernel<96>), gq, dim3(64 * nw), lq, stream, a);
-          break;
-      }
-    }
-    // the dK/dV role paired too where it measured faster: above 5 blocks (S = 208: 4 waves and two items per CU instead of one
-    // 7-wave workgroup, backward 120.8 -> 99.4 us per layer); at S = 160 (three items per CU instead of two 5-wave ones) it is a
-    // tie, 76.4 vs 75.7 us, and the one-shot kernel stays (MPV_ATTN_PAIR=2 forces the paired one) -- profiles/r03_c19_dkv_pair_ab.log
-    if (pair_ok(d) && (pair_mode() >= 2 || (d->sk + 31) / 32 >= 6)) {
-      const int nb = (d->sk + 31) / 32;
-      const size_t pl = pair_lds(d->sk) + ((size_t)(2 * nb * 32 * 4) + 1023) / 1024 * 1024;
-      const dim3 pg(1, gy), pb(64 * ((nb + 1) / 2));
-      if (nb <= 5) hipLaunchKernelGGL((attn_bwd_dkv_pair64_kernel<192, 3>), pg, pb, pl, stream, a);
-      else hipLaunchKernelGGL((attn_bwd_dkv_pair64_kernel<256, 3>), pg, pb, pl, stream, a);
-    } else {
-      switch (hdc) {
-        case 64:
-          if (small64) hipLaunchKernelGGL((attn_bwd_dkv_res_kernel<64, 320, 3>), gk, dim3(64 * nwk), lk, stream, a);
-          else hipLaunchKernelGGL((attn_bwd_dkv_res_kernel<64, 512>), gk, dim3(64 * nwk), lk, stream, a);
-          break;
-        case 80: hipLaunchKernelGGL((attn_bwd_dkv_res_kernel<80, 512>), gk, dim3(64 * nwk), lk, stream, a); break;
-        default:
-          if (vit7 && duo_mode() >= 2 && d->sq == d->sk && d->head_dim == 96) {      // two 4-wave items per CU (attention_duo.inc)
-            static bool attr = false;
-            if (!attr) {
-              allow_lds(attn_bwd_dkv_duo96_kernel<256>, 80 * 1024);
-              attr = true;
-            }
-            const int qr = (d->sq + 31) / 32 * 32;
-            const size_t dl = ((size_t)(2 * qr * 4 + 1023) / 1024 + 2 * (((size_t)d->sq * 192 + 1023) / 1024)) * 1024;
-            hipLaunchKernelGGL((attn_bwd_dkv_duo96_kernel<256>), dim3(1, gy), dim3(256), dl, stream, a);
-          } else hipLaunchKernelGGL((attn_bwd_dkv_res_kernel<96, 512>), gk, dim3(64 * nwk), lk, stream, a);
-          break;
-      }
-    }
-    return mpv_check_launch("mpv_attn_bwd");
-  }
-  const int nwq = waves_for(d->sq), nwk = 4;   // dK/dV keeps 4 waves (its accumulators need > 256 VGPRs at 8)
-  dim3 gq((d->sq + 32 * nwq - 1) / (32 * nwq), d->batch * d->heads), gk((d->sk + 32 * nwk - 1) / (32 * nwk), d->batch * d->heads);
-  dim3 bq(64 * nwq), bk(64 * nwk);
-  switch (d->head_dim <= 64 ? 64 : d->head_dim <= 80 ? 80 : 96) {
-    case 64:
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<64>), gq, bq, 0, stream, a);
-      hipLaunchKernelGGL((attn_bwd_dkv_kernel<64>), gk, bk, 0, stream, a);
-      break;
-    case 80:
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<80>), gq, bq, 0, stream, a);
-      hipLaunchKernelGGL((attn_bwd_dkv_kernel<80>), gk, bk, 0, stream, a);
-      break;
-    default:
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<96>), gq, bq, 0, stream, a);
-      hipLaunchKernelGGL((attn_bwd_dkv_kernel<96>), gk, bk, 0, stream, a);
-      break;
-  }
-  return mpv_check_launch("mpv_attn_bwd");
-}
-
 // ---- the same problem with its rows in LDS as bf16 (round 4; measured stand-alone in round 3: tools/probe/temporal_bf16_probe.hip,
 // profiles/r03_c26_temporal_bf16_probe.log).  The rows ARE bf16 values (q * scale is rounded to bf16 by the reference itself, :179),
 // so bf16 rows at the conflict-free 208-byte pitch hold the same numbers in half the LDS bytes -- LDS is what limits this kernel's
@@ -1999,17 +1735,12 @@ __device__ __forceinline__ void tdot8(bf16x8 a, bf16x8 b, float& c0, float& c1) 
 }
 
 template <bool BWD, int T, int HD>
-constexpr int temporal_b16_wave_lds() {
-  return ((BWD ? 4 : 3) * T * (HD + 8) * 2 + (BWD ? 2 : 1) * T * (T + 1) * 4 + 15) & ~15;
-}
-
-template <bool BWD, int T, int HD>
 __global__ __launch_bounds__(256) void temporal_attn_b16_kernel(const TempArgs p) {
   extern __shared__ __attribute__((aligned(16))) float tsm[];
   constexpr int LDB = HD + 8;                          // bf16 row pitch: 208 bytes at head_dim 96
   constexpr int H4 = HD / 4, H8 = HD / 8;
   constexpr int ROWS = (BWD ? 4 : 3) * T * LDB * 2;    // bytes of the bf16 images
-  constexpr int PER_WAVE = temporal_b16_wave_lds<BWD, T, HD>();
+  constexpr int PER_WAVE = temporal_b16_wave_lds(BWD, T, HD);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwv = (int)(blockDim.x >> 6);
   const int D = p.heads * HD;
   char* base = (char*)tsm + wave * PER_WAVE;
@@ -2139,63 +1870,285 @@ static int temporal_common(TempArgs& t, int n_outer, int64_t outer_stride, int n
   return MPV_OK;
 }
 
-// Waves (one problem each) per workgroup: 4 unless fewer waves per workgroup put more waves on a CU (LDS is what limits the
-// occupancy of this kernel: 160 KiB per CU, a wave's rows are 10 KiB at 8 frames -- 4 x 4 waves either way -- but 20 / 28 KiB at
-// 16 frames, where 4-wave workgroups would leave one workgroup = 4 waves per CU and 1- / 2-wave ones fit 7 / 5).
-static int temporal_waves_per_workgroup(size_t wave_lds) {
-  const size_t cu = 160 * 1024;
-  int best = 4, best_waves = (int)(cu / (4 * wave_lds)) * 4;
-  for (int n = 3; n >= 1; --n) {
-    const int waves = (int)(cu / (n * wave_lds)) * n;
-    if (waves > best_waves) best = n, best_waves = waves;
-  }
-  return best;
+// =========================================================================== host side: knobs, plan, variant table, entry points
+// DESIGN.md "Attention dispatch".  attn_plan / temporal_plan decide (pure functions of the shape, the knobs and the CU count);
+// the variant table names every launched instance once, with its launcher and the most dynamic LDS it can be asked for; the
+// entry points check, fill the arguments, plan and launch the row.
+constexpr int RES_MAX_ROWS = 256;       // resident kernels: the whole streamed side of one (batch, head) in LDS
+constexpr int PAIR_MAX_ROWS = 224;      // paired-block causal kernels (attention_pair.inc)
+constexpr int SMALL64_MAX_ROWS = 160;   // head_dim 64, <= 5 waves: the <.., 320, 3> instances, two workgroups per CU
+constexpr int VIT7_MIN_ROWS = 193, VIT7_MAX_ROWS = 224, PRES_LEAN_MAX_ROWS = 200;      // exactly 7 key tiles; LEAN: <= 8 keys in the last one
+
+enum AttnRole { ROLE_FWD = 0, ROLE_DQ = 1, ROLE_DKV = 2 };
+
+struct AttnPlan {
+  int variant;
+  unsigned gx, gy;
+  int block, lds;
+  int nitems;      // persistent kernels: (batch, head) items walked by the grid
+};
+
+// ---- knobs (measurement only) and the CU count: read once per process, handed to the plan functions as values
+struct AttnKnobs {
+  int persist;         // MPV_ATTN_PERSIST: 0 = one-shot resident kernels only; 1 (default) = the persistent double-buffered forward where a
+                       // workgroup gets more than one (batch, head) item; 2 = also for a single item per workgroup
+  int pair;            // MPV_ATTN_PAIR: 0 = one-shot resident kernels; 1 (default) = paired forward and dQ, paired dK/dV above 5 blocks; 2 = paired dK/dV everywhere
+  int duo;             // MPV_ATTN_DUO: 0 = one-shot 7-wave backward of the ViT shape; 1 = dQ as two 4-wave items per CU; 2 (default) = dQ and dK/dV
+  bool temporal_bf16;  // MPV_TEMPORAL_ROWS=fp32 keeps the fp32-row temporal kernel (same-box A/B); default: the bf16-row instances
+  int ncu;             // whole XCD groups of CUs: item i and workgroup i % grid then share i % 8
+};
+static int attn_ncu() {
+  int dev = 0, ncu = 0;
+  (void)hipGetDevice(&dev);
+  if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
+  return ncu / 8 * 8 > 0 ? ncu / 8 * 8 : 8;
 }
-static void temporal_set_attributes() {
-  static bool done = false;
-  if (done) return;
-  const int lim = 150 * 1024;
-  (void)hipFuncSetAttribute((const void*)temporal_attn_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-  (void)hipFuncSetAttribute((const void*)temporal_attn_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-  (void)hipFuncSetAttribute((const void*)temporal_attn_kernel<false, 8, 96>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-  (void)hipFuncSetAttribute((const void*)temporal_attn_kernel<true, 8, 96>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-  (void)hipFuncSetAttribute((const void*)temporal_attn_kernel<false, 16, 96>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-  (void)hipFuncSetAttribute((const void*)temporal_attn_kernel<true, 16, 96>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-  (void)hipFuncSetAttribute((const void*)temporal_attn_kernel<false, 4, 96>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-  (void)hipFuncSetAttribute((const void*)temporal_attn_kernel<true, 4, 96>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-  done = true;
+static const AttnKnobs& attn_knobs() {
+  static const AttnKnobs k = [] {
+    const auto env = [](const char* name, int dflt) {
+      const char* e = getenv(name);
+      return e ? atoi(e) : dflt;
+    };
+    const char* rows = getenv("MPV_TEMPORAL_ROWS");
+    return AttnKnobs{env("MPV_ATTN_PERSIST", 1), env("MPV_ATTN_PAIR", 1), env("MPV_ATTN_DUO", 2), !(rows && !strcmp(rows, "fp32")), attn_ncu()};
+  }();
+  return k;
 }
 
-// bf16-row instances (head_dim 96; 4 / 8 / 16 frames): the default; MPV_TEMPORAL_ROWS=fp32 keeps the fp32-row kernel (same-box A/B).
-static bool temporal_rows_bf16() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("MPV_TEMPORAL_ROWS");
-    v = (e && !strcmp(e, "fp32")) ? 0 : 1;
-  }
-  return v == 1;
+// ---- variant table: X(enumerator, argument kind, LDS limit, kernel as written).  The limit is the layout function of the role at
+// the largest shape the plan can send to the instance.  Kinds: A = (AttnArgs), P = (AttnArgs, nitems), T = (TempArgs).
+constexpr int pres_fwd_limit(int sk_max) {      // (the plan also refuses what does not fit a CU: two 7-tile sets do not at every length)
+  int m = 0;
+  for (int sk = VIT7_MIN_ROWS; sk <= sk_max; ++sk)
+    if (pres_fwd_lds(sk, 96) <= CU_LDS && pres_fwd_lds(sk, 96) > m) m = pres_fwd_lds(sk, 96);
+  return m;
 }
-template <bool BWD, int T>
-static void temporal_b16_launch(const TempArgs& t, hipStream_t stream) {
-  constexpr int NWV = 2;                               // measured best (or tied) at 8 and at 16 frames in both directions
-  constexpr size_t lds = (size_t)NWV * temporal_b16_wave_lds<BWD, T, 96>();
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)temporal_attn_b16_kernel<BWD, T, 96>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    attr = true;
-  }
-  const long long nprob = (long long)t.n_outer * t.n_inner * t.heads;
-  const int grid = (int)((nprob + NWV - 1) / NWV < 16384 ? (nprob + NWV - 1) / NWV : 16384);
-  hipLaunchKernelGGL((temporal_attn_b16_kernel<BWD, T, 96>), dim3(grid), dim3(64 * NWV), lds, stream, t);
+constexpr int temporal_f32_limit(bool bwd) {    // run-time T <= 16, head_dim <= 96 (temporal_common)
+  int m = 0;
+  for (int T = 1; T <= 16; ++T)
+    for (int hd = 4; hd <= 96; hd += 4)
+      if (temporal_f32_lds(bwd, T, hd) > m) m = temporal_f32_lds(bwd, T, hd);
+  return m;
 }
-template <bool BWD>
-static bool temporal_b16_dispatch(const TempArgs& t, hipStream_t stream) {
-  if (t.hd != 96 || !temporal_rows_bf16()) return false;
-  if (t.T == 8) temporal_b16_launch<BWD, 8>(t, stream);
-  else if (t.T == 16) temporal_b16_launch<BWD, 16>(t, stream);
-  else if (t.T == 4) temporal_b16_launch<BWD, 4>(t, stream);
-  else return false;
-  return true;
+#define ATTN_VARIANTS(X)                                                                                                \
+  X(FWD_DECODE_8, A, 0, attn_decode_kernel<8>)                                                                          \
+  X(FWD_DECODE_16, A, 0, attn_decode_kernel<16>)                                                                        \
+  X(FWD_STREAM_64, A, 0, attn_fwd_kernel<64>)                                                                           \
+  X(FWD_STREAM_80, A, 0, attn_fwd_kernel<80>)                                                                           \
+  X(FWD_STREAM_96, A, 0, attn_fwd_kernel<96>)                                                                           \
+  X(DQ_STREAM_64, A, 0, attn_bwd_dq_kernel<64>)                                                                         \
+  X(DQ_STREAM_80, A, 0, attn_bwd_dq_kernel<80>)                                                                         \
+  X(DQ_STREAM_96, A, 0, attn_bwd_dq_kernel<96>)                                                                         \
+  X(DKV_STREAM_64, A, 0, attn_bwd_dkv_kernel<64>)                                                                       \
+  X(DKV_STREAM_80, A, 0, attn_bwd_dkv_kernel<80>)                                                                       \
+  X(DKV_STREAM_96, A, 0, attn_bwd_dkv_kernel<96>)                                                                       \
+  X(FWD_RES_64, A, res_fwd_lds(RES_MAX_ROWS), attn_fwd_res_kernel<64>)                                                  \
+  X(FWD_RES_80, A, res_fwd_lds(RES_MAX_ROWS), attn_fwd_res_kernel<80>)                                                  \
+  X(FWD_RES_96, A, res_fwd_lds(RES_MAX_ROWS), attn_fwd_res_kernel<96>)                                                  \
+  X(FWD_RES_64_SMALL, A, res_fwd_lds(SMALL64_MAX_ROWS), attn_fwd_res_kernel<64, 0, 5, 320, 3>)                          \
+  X(FWD_RES_96_VIT7, A, res_fwd_lds(VIT7_MAX_ROWS), attn_fwd_res_kernel<96, 7>)                                         \
+  X(DQ_RES_64, A, res_dq_lds(RES_MAX_ROWS), attn_bwd_dq_res_kernel<64>)                                                 \
+  X(DQ_RES_80, A, res_dq_lds(RES_MAX_ROWS), attn_bwd_dq_res_kernel<80>)                                                 \
+  X(DQ_RES_96, A, res_dq_lds(RES_MAX_ROWS), attn_bwd_dq_res_kernel<96>)                                                 \
+  X(DQ_RES_64_SMALL, A, res_dq_lds(SMALL64_MAX_ROWS), attn_bwd_dq_res_kernel<64, 0, 320, 3>)                            \
+  X(DQ_RES_96_VIT7, A, res_dq_lds(VIT7_MAX_ROWS), attn_bwd_dq_res_kernel<96, 7>)                                        \
+  X(DKV_RES_64, A, res_dkv_lds(RES_MAX_ROWS, RES_MAX_ROWS, 64), attn_bwd_dkv_res_kernel<64, 512>)                       \
+  X(DKV_RES_80, A, res_dkv_lds(RES_MAX_ROWS, RES_MAX_ROWS, 80), attn_bwd_dkv_res_kernel<80, 512>)                       \
+  X(DKV_RES_96, A, res_dkv_lds(RES_MAX_ROWS, RES_MAX_ROWS, 96), attn_bwd_dkv_res_kernel<96, 512>)                       \
+  X(DKV_RES_64_SMALL, A, res_dkv_lds(SMALL64_MAX_ROWS, SMALL64_MAX_ROWS, 64), attn_bwd_dkv_res_kernel<64, 320, 3>)      \
+  X(FWD_PRES_LEAN, P, pres_fwd_limit(PRES_LEAN_MAX_ROWS), attn_fwd_pres_kernel<96, 7, 8, 512, 1, true>)                 \
+  X(FWD_PRES, P, pres_fwd_limit(VIT7_MAX_ROWS), attn_fwd_pres_kernel<96, 7>)                                            \
+  X(FWD_PAIR_5, A, pair_fwd_lds(5 * 32), attn_fwd_pair64_kernel<5, 192, 3>)                                             \
+  X(FWD_PAIR_7, A, pair_fwd_lds(PAIR_MAX_ROWS), attn_fwd_pair64_kernel<7, 256, 2>)                                      \
+  X(DQ_PAIR_5, A, pair_dq_lds(5 * 32), attn_bwd_dq_pair64_kernel<192, 3>)                                               \
+  X(DQ_PAIR_7, A, pair_dq_lds(PAIR_MAX_ROWS), attn_bwd_dq_pair64_kernel<256, 3>)                                        \
+  X(DKV_PAIR_5, A, pair_dkv_lds(5 * 32), attn_bwd_dkv_pair64_kernel<192, 3>)                                            \
+  X(DKV_PAIR_7, A, pair_dkv_lds(PAIR_MAX_ROWS), attn_bwd_dkv_pair64_kernel<256, 3>)                                     \
+  X(DQ_DUO, A, duo_dq_lds(VIT7_MAX_ROWS), attn_bwd_dq_duo96_kernel<256>)                                                \
+  X(DKV_DUO, A, duo_dkv_lds(VIT7_MAX_ROWS), attn_bwd_dkv_duo96_kernel<256>)                                             \
+  X(TEMPORAL_F32_FWD, T, temporal_f32_limit(false), temporal_attn_kernel<false>)                                        \
+  X(TEMPORAL_F32_FWD_4, T, temporal_f32_lds(false, 4, 96), temporal_attn_kernel<false, 4, 96>)                          \
+  X(TEMPORAL_F32_FWD_8, T, temporal_f32_lds(false, 8, 96), temporal_attn_kernel<false, 8, 96>)                          \
+  X(TEMPORAL_F32_FWD_16, T, temporal_f32_lds(false, 16, 96), temporal_attn_kernel<false, 16, 96>)                       \
+  X(TEMPORAL_F32_BWD, T, temporal_f32_limit(true), temporal_attn_kernel<true>)                                          \
+  X(TEMPORAL_F32_BWD_4, T, temporal_f32_lds(true, 4, 96), temporal_attn_kernel<true, 4, 96>)                            \
+  X(TEMPORAL_F32_BWD_8, T, temporal_f32_lds(true, 8, 96), temporal_attn_kernel<true, 8, 96>)                            \
+  X(TEMPORAL_F32_BWD_16, T, temporal_f32_lds(true, 16, 96), temporal_attn_kernel<true, 16, 96>)                         \
+  X(TEMPORAL_B16_FWD_4, T, temporal_b16_lds(false, 4, 96), temporal_attn_b16_kernel<false, 4, 96>)                      \
+  X(TEMPORAL_B16_FWD_8, T, temporal_b16_lds(false, 8, 96), temporal_attn_b16_kernel<false, 8, 96>)                      \
+  X(TEMPORAL_B16_FWD_16, T, temporal_b16_lds(false, 16, 96), temporal_attn_b16_kernel<false, 16, 96>)                   \
+  X(TEMPORAL_B16_BWD_4, T, temporal_b16_lds(true, 4, 96), temporal_attn_b16_kernel<true, 4, 96>)                        \
+  X(TEMPORAL_B16_BWD_8, T, temporal_b16_lds(true, 8, 96), temporal_attn_b16_kernel<true, 8, 96>)                        \
+  X(TEMPORAL_B16_BWD_16, T, temporal_b16_lds(true, 16, 96), temporal_attn_b16_kernel<true, 16, 96>)
+
+enum AttnVariantId {
+#define X(id, kind, limit, ...) id,
+  ATTN_VARIANTS(X)
+#undef X
+};
+
+template <auto K>
+static void launch_A(const AttnPlan& pl, const void* args, hipStream_t stream) {
+  hipLaunchKernelGGL(K, dim3(pl.gx, pl.gy), dim3(pl.block), pl.lds, stream, *(const AttnArgs*)args);
+}
+template <auto K>
+static void launch_P(const AttnPlan& pl, const void* args, hipStream_t stream) {
+  hipLaunchKernelGGL(K, dim3(pl.gx, pl.gy), dim3(pl.block), pl.lds, stream, *(const AttnArgs*)args, pl.nitems);
+}
+template <auto K>
+static void launch_T(const AttnPlan& pl, const void* args, hipStream_t stream) {
+  hipLaunchKernelGGL(K, dim3(pl.gx, pl.gy), dim3(pl.block), pl.lds, stream, *(const TempArgs*)args);
+}
+struct AttnVariant {
+  const char* name;
+  const void* kernel;
+  void (*launch)(const AttnPlan&, const void* args, hipStream_t);
+  int lds_limit;
+};
+static const AttnVariant ATTN_VARIANT_TABLE[] = {
+#define X(id, kind, limit, ...) {#__VA_ARGS__, (const void*)__VA_ARGS__, launch_##kind<__VA_ARGS__>, limit},
+    ATTN_VARIANTS(X)
+#undef X
+};
+#define X(id, kind, limit, ...) static_assert((limit) <= CU_LDS, #id ": LDS limit above a CU's LDS");
+ATTN_VARIANTS(X)
+#undef X
+
+// Dynamic LDS above the 64 KiB default needs an opt-in per kernel: one walk over the table, at the first launch.
+static void attn_launch(const AttnPlan& pl, const void* args, hipStream_t stream) {
+  static const bool opted_in = [] {
+    for (const AttnVariant& v : ATTN_VARIANT_TABLE)
+      if (v.lds_limit > 64 * 1024) (void)hipFuncSetAttribute(v.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds_limit);
+    return true;
+  }();
+  (void)opted_in;
+  ATTN_VARIANT_TABLE[pl.variant].launch(pl, args, stream);
+}
+
+// ---- shape facts shared by the three roles
+struct AttnShape {
+  int hdc;            // instantiated head_dim: 64 / 80 / 96
+  int nwq, nwk;       // waves per workgroup over the query / key rows
+  int gy;             // (batch, head) items with the batch padded to whole groups of 8 (decode_bh)
+  int nb;             // 32-row key blocks
+  bool decode;        // single-row step of KV-cache generation
+  bool vit7;          // ViT spatial shape: head_dim class 96, no mask, no dropout, exactly 7 key tiles
+  bool small64;       // head_dim class 64 and <= 160 rows on both sides
+  bool pair;          // paired-block causal shape
+  bool offsets32;     // every operand addressable with 32-bit element offsets from its base (persistent kernels)
+};
+static AttnShape attn_shape(const mpv_attn_desc* d) {
+  AttnShape s;
+  s.hdc = d->head_dim <= 64 ? 64 : d->head_dim <= 80 ? 80 : 96;
+  s.nwq = waves_for(d->sq);
+  s.nwk = waves_for(d->sk);
+  s.gy = (d->batch + 7) / 8 * 8 * d->heads;
+  s.nb = (d->sk + 31) / 32;
+  s.decode = d->sq == 1 && d->dropout_p == 0.f && d->sk <= DEC_MAX_SK && (d->o_hs % 8) == 0 && ((uintptr_t)d->o & 15) == 0;
+  s.vit7 = s.hdc == 96 && !d->causal && d->dropout_p == 0.f && s.nb == 7;
+  s.small64 = s.hdc == 64 && d->sk <= SMALL64_MAX_ROWS && d->sq <= SMALL64_MAX_ROWS;
+  s.pair = d->head_dim == 64 && d->causal && d->sq == d->sk && d->sk <= PAIR_MAX_ROWS;
+  const auto fits = [&](int64_t bs, int64_t hs, int64_t rs, int rows) {
+    return bs >= 0 && hs >= 0 && rs > 0 && rs < (1 << 20) &&
+           (int64_t)(d->batch + 7) * bs + (int64_t)d->heads * hs + (int64_t)(rows + 32) * rs + 128 < (1LL << 31) / 2;
+  };
+  s.offsets32 = fits(d->q_bs, d->q_hs, d->q_rs, d->sq) && fits(d->k_bs, d->k_hs, d->k_rs, d->sk) && fits(d->v_bs, d->v_hs, d->v_rs, d->sk) &&
+                fits(d->o_bs, d->o_hs, d->o_rs, d->sq) && (int64_t)(d->batch + 7) * d->heads * d->sq < (1LL << 30);
+  return s;
+}
+
+// Which instance runs role `role` of problem `d`, and how it is launched.  Calls no HIP function.
+static AttnPlan attn_plan(const mpv_attn_desc* d, int role, const AttnKnobs& kn) {
+  const AttnShape s = attn_shape(d);
+  const int sq = d->sq, sk = d->sk;
+  const auto by_hd = [&](int v64) { return v64 + (s.hdc == 64 ? 0 : s.hdc == 80 ? 1 : 2); };      // rows .._64, .._80, .._96 are adjacent
+  const auto by_role = [&](int fwd, int dq, int dkv) { return role == ROLE_FWD ? fwd : role == ROLE_DQ ? dq : dkv; };
+  const auto cdiv = [](int a, int b) { return (unsigned)((a + b - 1) / b); };
+  if (role == ROLE_FWD && s.decode) return {d->head_dim <= 64 ? FWD_DECODE_8 : FWD_DECODE_16, (unsigned)(d->batch * d->heads), 1, 256, 0, 0};
+  // the forward streams K / V only; the backward pair also Q / dO (delta goes from the dQ kernel to the dK/dV kernel either way)
+  if (sk > RES_MAX_ROWS || (role != ROLE_FWD && sq > RES_MAX_ROWS)) {
+    const int nw = role == ROLE_DKV ? 4 : s.nwq;      // dK/dV keeps 4 waves (its accumulators need > 256 VGPRs at 8)
+    return {by_hd(by_role(FWD_STREAM_64, DQ_STREAM_64, DKV_STREAM_64)), cdiv(role == ROLE_DKV ? sk : sq, 32 * nw),
+            (unsigned)(d->batch * d->heads), 64 * nw, 0, 0};
+  }
+  const unsigned gy = (unsigned)s.gy;
+  // Paired-block causal kernels.  The dK/dV role only where it measured faster: above 5 blocks (S = 208: 4 waves and two items per CU
+  // instead of one 7-wave workgroup, backward 120.8 -> 99.4 us per layer); at S = 160 (three items per CU instead of two 5-wave ones)
+  // it is a tie, 76.4 vs 75.7 us, and the one-shot kernel stays -- profiles/r03_c19_dkv_pair_ab.log
+  if (s.pair && kn.pair > 0 && (role != ROLE_DKV || kn.pair >= 2 || s.nb >= 6)) {
+    const int small = s.nb <= 5 ? 0 : 1;
+    return {by_role(FWD_PAIR_5, DQ_PAIR_5, DKV_PAIR_5) + small, 1, gy, 64 * ((s.nb + 1) / 2),
+            by_role(pair_fwd_lds(sk), pair_dq_lds(sk), pair_dkv_lds(sk)), 0};
+  }
+  // Persistent forward: instances exist where the structure measured faster than the one-shot kernels and the item loop fits the
+  // register file without scratch (a scratch reload sits behind an s_waitcnt vmcnt(0), which would drain the next item's DMA in the
+  // middle of the current one): the 7-tile non-causal head_dim-96 forward (ViT-B/16 spatial attention, 197 keys: LEAN).
+  if (role == ROLE_FWD && s.vit7 && sq <= 32 * s.nwq && pres_fwd_lds(sk, 96) <= CU_LDS && s.offsets32 &&
+      (kn.persist >= 2 || (kn.persist == 1 && s.gy > kn.ncu)))
+    return {sk <= PRES_LEAN_MAX_ROWS ? FWD_PRES_LEAN : FWD_PRES, (unsigned)(s.gy < kn.ncu ? s.gy : kn.ncu), 1, 64 * s.nwq, pres_fwd_lds(sk, 96), s.gy};
+  // Duo backward of the ViT shape: two 4-wave items per CU (attention_duo.inc)
+  if (role != ROLE_FWD && s.vit7 && sq == sk && d->head_dim == 96 && (role == ROLE_DQ ? kn.duo != 0 : kn.duo >= 2))
+    return {by_role(-1, DQ_DUO, DKV_DUO), 1, gy, 256, by_role(0, duo_dq_lds(sk), duo_dkv_lds(sq)), 0};
+  // One-shot resident kernels
+  if (role == ROLE_DKV)
+    return {s.small64 ? DKV_RES_64_SMALL : by_hd(DKV_RES_64), cdiv(sk, 32 * s.nwk), gy, 64 * s.nwk, res_dkv_lds(sq, sk, s.hdc), 0};
+  const int variant = s.small64 ? by_role(FWD_RES_64_SMALL, DQ_RES_64_SMALL, -1)
+                      : s.vit7  ? by_role(FWD_RES_96_VIT7, DQ_RES_96_VIT7, -1)
+                                : by_hd(by_role(FWD_RES_64, DQ_RES_64, -1));
+  return {variant, cdiv(sq, 32 * s.nwq), gy, 64 * s.nwq, by_role(res_fwd_lds(sk), res_dq_lds(sk), 0), 0};
+}
+static_assert(FWD_STREAM_96 == FWD_STREAM_64 + 2 && DQ_STREAM_96 == DQ_STREAM_64 + 2 && DKV_STREAM_96 == DKV_STREAM_64 + 2 &&
+                  FWD_RES_96 == FWD_RES_64 + 2 && DQ_RES_96 == DQ_RES_64 + 2 && DKV_RES_96 == DKV_RES_64 + 2 && FWD_PAIR_7 == FWD_PAIR_5 + 1 &&
+                  DQ_PAIR_7 == DQ_PAIR_5 + 1 && DKV_PAIR_7 == DKV_PAIR_5 + 1,
+              "attn_plan indexes adjacent table rows");
+
+// Temporal pair: the compile-time instances (head_dim 96; 4 / 8 / 16 frames) with bf16 rows by default, fp32 rows on request;
+// every other shape on the run-time fp32-row kernel.  One problem per wave, the grid capped (the kernels stride over the problems).
+static AttnPlan temporal_plan(bool bwd, int T, int hd, long long nprob, const AttnKnobs& kn) {
+  const int inst = hd != 96 ? 0 : T == 4 ? 1 : T == 8 ? 2 : T == 16 ? 3 : 0;      // row offset from the run-time instance
+  const bool b16 = inst && kn.temporal_bf16;
+  const int nwv = b16 ? TEMPORAL_B16_WAVES : temporal_f32_waves(temporal_f32_wave_lds(bwd, T, hd));
+  const long long wgs = (nprob + nwv - 1) / nwv;
+  return {b16 ? (bwd ? TEMPORAL_B16_BWD_4 : TEMPORAL_B16_FWD_4) + inst - 1 : (bwd ? TEMPORAL_F32_BWD : TEMPORAL_F32_FWD) + inst,
+          (unsigned)(wgs < 16384 ? wgs : 16384), 1, 64 * nwv, b16 ? temporal_b16_lds(bwd, T, hd) : temporal_f32_lds(bwd, T, hd), 0};
+}
+static_assert(TEMPORAL_F32_FWD_16 == TEMPORAL_F32_FWD + 3 && TEMPORAL_F32_BWD_16 == TEMPORAL_F32_BWD + 3 &&
+                  TEMPORAL_B16_FWD_16 == TEMPORAL_B16_FWD_4 + 2 && TEMPORAL_B16_BWD_16 == TEMPORAL_B16_BWD_4 + 2,
+              "temporal_plan indexes adjacent table rows");
+
+extern "C" int mpv_attn_fwd(const mpv_attn_desc* d, hipStream_t stream) {
+  int rc = check_desc(d, "mpv_attn_fwd");
+  if (rc) return rc;
+  AttnArgs a = {};
+  fill_args(a, d);
+  attn_launch(attn_plan(d, ROLE_FWD, attn_knobs()), &a, stream);
+  return mpv_check_launch("mpv_attn_fwd");
+}
+
+extern "C" int mpv_attn_bwd(const mpv_attn_desc* d, const void* dO, void* dq, void* dk, void* dv, float* delta,
+                            hipStream_t stream) {
+  int rc = check_desc(d, "mpv_attn_bwd");
+  if (rc) return rc;
+  MPV_REQUIRE(dO && dq && dk && dv && delta && d->lse, MPV_E_ARG, "mpv_attn_bwd: null pointer");
+  AttnArgs a = {};
+  fill_args(a, d);
+  a.dO = (const bf16*)dO;
+  a.dq = (bf16*)dq;
+  a.dk = (bf16*)dk;
+  a.dv = (bf16*)dv;
+  a.delta = delta;
+  // dQ first: it also stores delta = rowsum(dO * O) (row_delta), which the dK/dV kernel reads
+  attn_launch(attn_plan(d, ROLE_DQ, attn_knobs()), &a, stream);
+  attn_launch(attn_plan(d, ROLE_DKV, attn_knobs()), &a, stream);
+  return mpv_check_launch("mpv_attn_bwd");
+}
+
+static int temporal_launch(bool bwd, TempArgs& t, int n_outer, int64_t outer_stride, int n_inner, int64_t inner_offset, int64_t t_stride,
+                           int T, int heads, int head_dim, float scale, hipStream_t stream, const char* who) {
+  int rc = temporal_common(t, n_outer, outer_stride, n_inner, inner_offset, t_stride, T, heads, head_dim, scale, who);
+  if (rc) return rc;
+  attn_launch(temporal_plan(bwd, T, head_dim, (long long)n_outer * n_inner * heads, attn_knobs()), &t, stream);
+  return mpv_check_launch(who);
 }
 
 extern "C" int mpv_temporal_attn_fwd(const void* qkv, void* out, int n_outer, int64_t outer_stride, int n_inner,
@@ -2203,23 +2156,9 @@ extern "C" int mpv_temporal_attn_fwd(const void* qkv, void* out, int n_outer, in
                                      float scale, hipStream_t stream) {
   MPV_REQUIRE(qkv && out, MPV_E_ARG, "mpv_temporal_attn_fwd: null pointer");
   TempArgs t = {};
-  int rc = temporal_common(t, n_outer, outer_stride, n_inner, inner_offset, t_stride, T, heads, head_dim, scale,
-                           "mpv_temporal_attn_fwd");
-  if (rc) return rc;
   t.qkv = (const bf16*)qkv;
   t.out = (bf16*)out;
-  if (temporal_b16_dispatch<false>(t, stream)) return mpv_check_launch("mpv_temporal_attn_fwd");
-  const size_t wave_lds = sizeof(float) * (size_t)(((3 * T * (head_dim + 4) + T * (T + 1)) + 3) & ~3);
-  const int nwv = temporal_waves_per_workgroup(wave_lds);
-  const size_t lds = nwv * wave_lds;
-  const long long nprob = (long long)n_outer * n_inner * heads;
-  const int grid = (int)((nprob + nwv - 1) / nwv < 16384 ? (nprob + nwv - 1) / nwv : 16384);
-  temporal_set_attributes();
-  if (T == 8 && head_dim == 96) hipLaunchKernelGGL((temporal_attn_kernel<false, 8, 96>), dim3(grid), dim3(64 * nwv), lds, stream, t);
-  else if (T == 16 && head_dim == 96) hipLaunchKernelGGL((temporal_attn_kernel<false, 16, 96>), dim3(grid), dim3(64 * nwv), lds, stream, t);
-  else if (T == 4 && head_dim == 96) hipLaunchKernelGGL((temporal_attn_kernel<false, 4, 96>), dim3(grid), dim3(64 * nwv), lds, stream, t);
-  else hipLaunchKernelGGL((temporal_attn_kernel<false>), dim3(grid), dim3(64 * nwv), lds, stream, t);
-  return mpv_check_launch("mpv_temporal_attn_fwd");
+  return temporal_launch(false, t, n_outer, outer_stride, n_inner, inner_offset, t_stride, T, heads, head_dim, scale, stream, "mpv_temporal_attn_fwd");
 }
 
 extern "C" int mpv_temporal_attn_bwd(const void* qkv, const void* dout, void* dqkv, int n_outer, int64_t outer_stride,
@@ -2227,24 +2166,31 @@ extern "C" int mpv_temporal_attn_bwd(const void* qkv, const void* dout, void* dq
                                      int head_dim, float scale, hipStream_t stream) {
   MPV_REQUIRE(qkv && dout && dqkv, MPV_E_ARG, "mpv_temporal_attn_bwd: null pointer");
   TempArgs t = {};
-  int rc = temporal_common(t, n_outer, outer_stride, n_inner, inner_offset, t_stride, T, heads, head_dim, scale,
-                           "mpv_temporal_attn_bwd");
-  if (rc) return rc;
   t.qkv = (const bf16*)qkv;
   t.dout = (const bf16*)dout;
   t.dqkv = (bf16*)dqkv;
-  if (temporal_b16_dispatch<true>(t, stream)) return mpv_check_launch("mpv_temporal_attn_bwd");
-  const size_t wave_lds = sizeof(float) * (size_t)(((4 * T * (head_dim + 4) + 2 * T * (T + 1)) + 3) & ~3);
-  const int nwv = temporal_waves_per_workgroup(wave_lds);
-  const size_t lds = nwv * wave_lds;
-  const long long nprob = (long long)n_outer * n_inner * heads;
-  const int grid = (int)((nprob + nwv - 1) / nwv < 16384 ? (nprob + nwv - 1) / nwv : 16384);
-  temporal_set_attributes();
-  if (T == 8 && head_dim == 96) hipLaunchKernelGGL((temporal_attn_kernel<true, 8, 96>), dim3(grid), dim3(64 * nwv), lds, stream, t);
-  else if (T == 16 && head_dim == 96) hipLaunchKernelGGL((temporal_attn_kernel<true, 16, 96>), dim3(grid), dim3(64 * nwv), lds, stream, t);
-  else if (T == 4 && head_dim == 96) hipLaunchKernelGGL((temporal_attn_kernel<true, 4, 96>), dim3(grid), dim3(64 * nwv), lds, stream, t);
-  else hipLaunchKernelGGL((temporal_attn_kernel<true>), dim3(grid), dim3(64 * nwv), lds, stream, t);
-  return mpv_check_launch("mpv_temporal_attn_bwd");
+  return temporal_launch(true, t, n_outer, outer_stride, n_inner, inner_offset, t_stride, T, heads, head_dim, scale, stream, "mpv_temporal_attn_bwd");
+}
+
+// ---- read-only queries (tests, tools): what the entry points above would launch.  Host only; nothing on the hot path calls them.
+static int describe_plan(const AttnPlan& pl, mpv_attn_plan_info* out) {
+  const AttnVariant& v = ATTN_VARIANT_TABLE[pl.variant];
+  *out = mpv_attn_plan_info{v.name, pl.gx, pl.gy, pl.block, pl.lds, v.lds_limit};
+  return MPV_OK;
+}
+extern "C" int mpv_attn_plan_describe(const mpv_attn_desc* d, int role, mpv_attn_plan_info* out) {
+  MPV_REQUIRE(out, MPV_E_ARG, "mpv_attn_plan_describe: null pointer");
+  MPV_REQUIRE(role >= ROLE_FWD && role <= ROLE_DKV, MPV_E_ARG, "mpv_attn_plan_describe: role %d is none of 0 (forward), 1 (dQ), 2 (dK/dV)", role);
+  int rc = check_desc(d, "mpv_attn_plan_describe");
+  if (rc) return rc;
+  return describe_plan(attn_plan(d, role, attn_knobs()), out);
+}
+extern "C" int mpv_temporal_attn_plan_describe(int n_outer, int n_inner, int T, int heads, int head_dim, int bwd, mpv_attn_plan_info* out) {
+  MPV_REQUIRE(out, MPV_E_ARG, "mpv_temporal_attn_plan_describe: null pointer");
+  TempArgs t = {};
+  int rc = temporal_common(t, n_outer, 0, n_inner, 0, 0, T, heads, head_dim, 0.f, "mpv_temporal_attn_plan_describe");
+  if (rc) return rc;
+  return describe_plan(temporal_plan(bwd != 0, T, head_dim, (long long)n_outer * n_inner * heads, attn_knobs()), out);
 }
 
 #ifdef MPV_ATTN_TIMING

@@ -24,9 +24,7 @@
 // item per CU; q, k, v, dO leave HBM once instead of twice: 930 -> 620 MB per layer): 321 us against 292 us for the two
 // two-item launches (profiles/r03_c18_fused_ab.log) -- two co-resident items hide more than a third less traffic saves.
 
-constexpr int DUO_KP = 208, DUO_VP = 192;
-__device__ __forceinline__ int duo_region(int rows, int pitch) { return (rows * pitch + 1023) / 1024 * 1024; }
-
+// (DUO_KP / DUO_VP, the image pitches, and packed_region / duo_*_lds: attention_layout.h)
 // DMA of the two dQ-role images: K [S][208 B] at kl (13 chunks per row: 12 + the zero-filled pad chunk), V [S][192 B] at vl with the
 // chunk at LDS position pos of row r = source chunk (pos - ((r >> 2) & 3)) mod 12
 __device__ __forceinline__ void duo_dma_kv(const AttnArgs& p, int b, int h, char* kl, char* vl, int S, int wave, int nwaves, int lane) {
@@ -184,7 +182,7 @@ __global__ __launch_bounds__(THREADS, 2) void attn_bwd_dq_duo96_kernel(const Att
   int b, h;
   if (!decode_bh(p, b, h)) return;
   const int S = p.sk;
-  const int kreg = duo_region(S, DUO_KP);
+  const int kreg = packed_region(S, DUO_KP);
   duo_dma_kv(p, b, h, rsm, rsm + kreg, S, wave, nwaves, lane);      // [K | V]
   duo_dq_role<true>(p, (const lds_char*)rsm, 0, kreg, b, h, b * p.heads + h, S, lane, wave);
 }
@@ -373,7 +371,7 @@ __global__ __launch_bounds__(THREADS, 2) void attn_bwd_dkv_duo96_kernel(const At
   const int bh = b * p.heads + h;
   const int S = p.sq;                                   // == p.sk (host-checked)
   const int qrows = ((S + 31) >> 5) * 32;
-  const int sreg = ((2 * qrows * 4 + 1023) / 1024) * 1024, ireg = duo_region(S, DUO_VP);
+  const int sreg = stat_bytes(qrows), ireg = packed_region(S, DUO_VP);
   float* sl = (float*)rsm;                              // [lse * log2e | delta] x qrows (fp32: in front, never read as bf16)
   char* dl = rsm + sreg;                                // dO [S][192 B] rotated: reads past the end land in Q (finite)
   char* ql = dl + ireg;                                 // Q  [S][192 B] rotated

@@ -32,7 +32,7 @@
 // of the XCD's whole L2 per workgroup on this part: `buffer_wbl2 sc1`.)  The loop is VALU-bound either way: ~550 VALU
 // instructions per tile, half of them the dropout hash, which in this orientation cannot be shared by the two keys of a pair.
 
-constexpr int ZP = 128;      // Z-image row pitch in bytes
+// (ZP, the Z-image row pitch, and z_region / pair_*_lds: attention_layout.h)
 __device__ __host__ __forceinline__ int zkey(int r) {
   const int x = (r >> 1) & 7;
   return ((x & 1) << 2) | (x & 2) | (x >> 2);
@@ -40,7 +40,6 @@ __device__ __host__ __forceinline__ int zkey(int r) {
 // An image holds whole 32-row tiles, the rows past the sequence end zero-filled by the DMA (out-of-range source): a tile read
 // never leaves defined data (the slack between a workgroup's LDS request and its allocation granule holds stale bytes of
 // earlier workgroups -- a NaN there times an exactly-zero probability would still be a NaN in the accumulator).
-__device__ __forceinline__ int z_region(int rows) { return ((rows + 31) >> 5) * 32 * ZP; }
 __device__ __forceinline__ void z_dma_rows(const __amdgpu_buffer_rsrc_t src, char* lds, int nrows, long long rs, int wave, int nwaves, int lane) {
   const int ninstr = ((nrows + 31) >> 5) * 4;      // 1 KiB = 8 rows per instruction, 4 instructions per tile
   for (int i = wave; i < ninstr; i += nwaves) {
@@ -353,7 +352,7 @@ __global__ __launch_bounds__(THREADS, WPE) void attn_bwd_dkv_pair64_kernel(const
   if (!decode_bh(p, b, h)) return;
   const int bh = b * p.heads + h;
   const int S = p.sk, NB = (S + 31) >> 5, qrows = NB * 32;
-  const int reg = z_region(S), sreg = ((2 * qrows * 4 + 1023) / 1024) * 1024;
+  const int reg = z_region(S), sreg = stat_bytes(qrows);
   float* sl = (float*)rsm;                     // fp32 statistics in front: no bf16 fragment read can ever land on them
   const int dimg = sreg, qimg = sreg + reg;
   const lds_char* sm = (const lds_char*)rsm;

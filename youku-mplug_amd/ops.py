@@ -272,6 +272,16 @@ def attn_bwd(q, k, v, o, lse, do, dq, dk, dv, lay: AttnLayout, batch, heads, sq,
                                   _stream()), "mpv_attn_bwd")
 
 
+def attn_plan(role, q, k, v, o, lay: AttnLayout, batch, heads, sq, sk, hd, *, causal=False, scale=1.0, scale_q_bf16=False, dropout_p=0.0):
+    """What attn_fwd (role 0) / attn_bwd (role 1: dQ, 2: dK/dV) would launch for these arguments (include/mpv.h:
+    mpv_attn_plan_describe): dict(variant, grid, block, lds_bytes, lds_limit).  Launches nothing; for tests and tools."""
+    d = _attn_desc(q, k, v, o, o, lay, batch, heads, sq, sk, hd, causal, scale, scale_q_bf16, dropout_p, 0, 0)
+    info = _lib.AttnPlanInfo()
+    check(_lib.lib().mpv_attn_plan_describe(C.byref(d), role, C.byref(info)), "mpv_attn_plan_describe")
+    return dict(variant=info.variant.decode(), grid=(info.grid_x, info.grid_y), block=info.block, lds_bytes=info.lds_bytes,
+                lds_limit=info.lds_limit)
+
+
 def attn_prefix_fwd(q, k, v, pk, pv, o, lay: AttnLayout, prefix_lay: Tuple[Tuple[int, int, int], Tuple[int, int, int]], n_cont,
                     group_size, heads, cont_len, prefix_len, hd, *, scale=1.0):
     """Causal attention of n_cont continuations (cont_len rows each; q/k/v/o strided (continuation, head, row) by `lay`) against
