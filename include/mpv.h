@@ -233,11 +233,22 @@ int mpv_temporal_attn_bwd(const void* qkv, const void* dout, void* dqkv, int n_o
                           int n_inner, int64_t inner_offset, int64_t t_stride, int T, int heads, int head_dim,
                           float scale, mpv_stream_t stream);
 
+/* The same problem for clips of up to 64 frames, on the matrix cores: 1 <= T <= 64 (T <= 32 runs the 32-token instance, longer
+ * clips the 64-token one), head_dim a multiple of 16 up to 96, every operand 16-byte aligned.  Arguments, addressing and numerics
+ * as above; token rows t >= T are neither read nor written.  mpv_temporal_attn_fwd / _bwd keep their T <= 16. */
+int mpv_temporal_attn_long_fwd(const void* qkv, void* out, int n_outer, int64_t outer_stride, int n_inner,
+                               int64_t inner_offset, int64_t t_stride, int T, int heads, int head_dim, float scale,
+                               mpv_stream_t stream);
+int mpv_temporal_attn_long_bwd(const void* qkv, const void* dout, void* dqkv, int n_outer, int64_t outer_stride,
+                               int n_inner, int64_t inner_offset, int64_t t_stride, int T, int heads, int head_dim,
+                               float scale, mpv_stream_t stream);
+
 /* What mpv_attn_fwd (role 0) / mpv_attn_bwd (role 1: its dQ launch, 2: its dK/dV launch) would launch for `d`, without
  * launching: the kernel instance as written in csrc/attention.hip, its grid, block and dynamic LDS bytes, and the most LDS
  * that instance is ever asked for (its opt-in limit).  Host only -- no device needed, nothing is dereferenced but `d` and
  * `out`; the refusals of mpv_attn_fwd apply.  For tests and tools: the launch paths do not go through it.
- * mpv_temporal_attn_plan_describe: the same for mpv_temporal_attn_fwd (bwd = 0) / _bwd (bwd = 1). */
+ * mpv_temporal_attn_plan_describe: the same for mpv_temporal_attn_fwd (bwd = 0) / _bwd (bwd = 1);
+ * mpv_temporal_attn_long_plan_describe: for mpv_temporal_attn_long_fwd / _bwd. */
 typedef struct mpv_attn_plan_info {
   const char* variant;   /* static storage */
   unsigned grid_x, grid_y;
@@ -246,6 +257,7 @@ typedef struct mpv_attn_plan_info {
 } mpv_attn_plan_info;
 int mpv_attn_plan_describe(const mpv_attn_desc* d, int role, mpv_attn_plan_info* out);
 int mpv_temporal_attn_plan_describe(int n_outer, int n_inner, int T, int heads, int head_dim, int bwd, mpv_attn_plan_info* out);
+int mpv_temporal_attn_long_plan_describe(int n_outer, int n_inner, int T, int heads, int head_dim, int bwd, mpv_attn_plan_info* out);
 
 /* ------------------------------------------------------------------------------------------
  * Patch-embed fold: video [B,3,T,H,W] bf16 -> im2col rows (b,t,ph,pw) x (c,i,j) padded to kpad

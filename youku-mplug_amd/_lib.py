@@ -109,6 +109,11 @@ _SIGS = {
                                       c_float, c_void_p]),
     "mpv_temporal_attn_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int64, c_int64, c_int,
                                       c_int, c_int, c_float, c_void_p]),
+    "mpv_temporal_attn_long_plan_describe": (c_int, [c_int] * 6 + [C.POINTER(AttnPlanInfo)]),
+    "mpv_temporal_attn_long_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int64, c_int64, c_int, c_int, c_int,
+                                           c_float, c_void_p]),
+    "mpv_temporal_attn_long_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int64, c_int64, c_int,
+                                           c_int, c_int, c_float, c_void_p]),
     "mpv_im2col_patches": (c_int, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p]),
     "mpv_vit_embed_assemble_fwd": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
     "mpv_vit_embed_assemble_bwd": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),

@@ -5,7 +5,8 @@
 //   ViT spatial attention       (Sq=Sk=197,  head_dim 96, q pre-scaled in bf16)
 //   AttentionPool cross-attn    (Sq=128, Sk=1+T*196+1, head_dim 96)
 // plus a VALU kernel pair for the divided space-time *temporal* attention (T<=16 tokens,
-// hundreds of thousands of tiny problems, HBM-bound).
+// hundreds of thousands of tiny problems, HBM-bound) and a matrix-core family for the same attention at 17..64
+// tokens (attention_temporal_long.inc).
 //
 // Layout of the MFMA kernels: a workgroup = 4 waves = 128 query rows (forward, dQ) or 128
 // key rows (dK/dV) of one (batch, head); every wave owns a 32-row tile whose operand
@@ -1668,6 +1669,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const AttnArgs p) {
 
 #include "attention_pair.inc"
 #include "attention_duo.inc"
+#include "attention_temporal_long.inc"
 
 // waves per workgroup: cover a whole sequence with one workgroup when it has <= 256 rows (no idle
 // waves: 160 rows -> 5 waves, 197 -> 7), otherwise 8 waves = 256 rows per workgroup
@@ -1979,7 +1981,11 @@ constexpr int temporal_f32_limit(bool bwd) {    // run-time T <= 16, head_dim <=
   X(TEMPORAL_B16_FWD_16, T, temporal_b16_lds(false, 16, 96), temporal_attn_b16_kernel<false, 16, 96>)                   \
   X(TEMPORAL_B16_BWD_4, T, temporal_b16_lds(true, 4, 96), temporal_attn_b16_kernel<true, 4, 96>)                        \
   X(TEMPORAL_B16_BWD_8, T, temporal_b16_lds(true, 8, 96), temporal_attn_b16_kernel<true, 8, 96>)                        \
-  X(TEMPORAL_B16_BWD_16, T, temporal_b16_lds(true, 16, 96), temporal_attn_b16_kernel<true, 16, 96>)
+  X(TEMPORAL_B16_BWD_16, T, temporal_b16_lds(true, 16, 96), temporal_attn_b16_kernel<true, 16, 96>)                     \
+  X(TEMPORAL_MFMA_FWD_32, T, temporal_mfma_lds(false, 32), temporal_attn_mfma_kernel<false, 32>)                        \
+  X(TEMPORAL_MFMA_FWD_64, T, temporal_mfma_lds(false, 64), temporal_attn_mfma_kernel<false, 64>)                        \
+  X(TEMPORAL_MFMA_BWD_32, T, temporal_mfma_lds(true, 32), temporal_attn_mfma_kernel<true, 32>)                          \
+  X(TEMPORAL_MFMA_BWD_64, T, temporal_mfma_lds(true, 64), temporal_attn_mfma_kernel<true, 64>)
 
 enum AttnVariantId {
 #define X(id, kind, limit, ...) id,
@@ -2116,6 +2122,18 @@ static_assert(TEMPORAL_F32_FWD_16 == TEMPORAL_F32_FWD + 3 && TEMPORAL_F32_BWD_16
                   TEMPORAL_B16_FWD_16 == TEMPORAL_B16_FWD_4 + 2 && TEMPORAL_B16_BWD_16 == TEMPORAL_B16_BWD_4 + 2,
               "temporal_plan indexes adjacent table rows");
 
+// Long clips (17..64 frames; the entry points take 1..64): the matrix-core instances, TT = 32 up to 32 frames, TT = 64 above.  One
+// problem per wave, TEMPORAL_MFMA_WAVES waves per workgroup, the grid capped as above.
+constexpr int TEMPORAL_GRID_CAP = 16384;
+static AttnPlan temporal_long_plan(bool bwd, int T, long long nprob) {
+  const int tt = T <= 32 ? 32 : 64;
+  const long long wgs = (nprob + TEMPORAL_MFMA_WAVES - 1) / TEMPORAL_MFMA_WAVES;
+  return {(bwd ? TEMPORAL_MFMA_BWD_32 : TEMPORAL_MFMA_FWD_32) + (tt == 64), (unsigned)(wgs < TEMPORAL_GRID_CAP ? wgs : TEMPORAL_GRID_CAP), 1,
+          64 * TEMPORAL_MFMA_WAVES, temporal_mfma_lds(bwd, tt), 0};
+}
+static_assert(TEMPORAL_MFMA_FWD_64 == TEMPORAL_MFMA_FWD_32 + 1 && TEMPORAL_MFMA_BWD_64 == TEMPORAL_MFMA_BWD_32 + 1,
+              "temporal_long_plan indexes adjacent table rows");
+
 extern "C" int mpv_attn_fwd(const mpv_attn_desc* d, hipStream_t stream) {
   int rc = check_desc(d, "mpv_attn_fwd");
   if (rc) return rc;
@@ -2172,6 +2190,56 @@ extern "C" int mpv_temporal_attn_bwd(const void* qkv, const void* dout, void* dq
   return temporal_launch(true, t, n_outer, outer_stride, n_inner, inner_offset, t_stride, T, heads, head_dim, scale, stream, "mpv_temporal_attn_bwd");
 }
 
+static int temporal_long_common(TempArgs& t, int n_outer, int64_t outer_stride, int n_inner, int64_t inner_offset, int64_t t_stride,
+                                int T, int heads, int head_dim, float scale, const char* who) {
+  MPV_REQUIRE(T >= 1 && T <= 64, MPV_E_SHAPE, "%s: T=%d must be in [1,64]", who, T);
+  MPV_REQUIRE(head_dim >= 16 && head_dim % 16 == 0 && head_dim <= 96, MPV_E_SHAPE, "%s: head_dim=%d must be a multiple of 16 in [16,96]", who,
+              head_dim);
+  MPV_REQUIRE(n_outer > 0 && n_inner > 0 && heads > 0, MPV_E_SHAPE, "%s: empty problem", who);
+  t.n_outer = n_outer;
+  t.n_inner = n_inner;
+  t.outer_stride = outer_stride;
+  t.inner_offset = inner_offset;
+  t.t_stride = t_stride;
+  t.T = T;
+  t.heads = heads;
+  t.hd = head_dim;
+  t.scale = scale;
+  return MPV_OK;
+}
+static int temporal_long_launch(bool bwd, TempArgs& t, int n_outer, int64_t outer_stride, int n_inner, int64_t inner_offset, int64_t t_stride,
+                                int T, int heads, int head_dim, float scale, hipStream_t stream, const char* who) {
+  int rc = temporal_long_common(t, n_outer, outer_stride, n_inner, inner_offset, t_stride, T, heads, head_dim, scale, who);
+  if (rc) return rc;
+  MPV_REQUIRE((((uintptr_t)t.qkv | (uintptr_t)t.dout | (uintptr_t)t.out | (uintptr_t)t.dqkv) & 15) == 0, MPV_E_ALIGN,
+              "%s: operands must be 16-byte aligned", who);
+  attn_launch(temporal_long_plan(bwd, T, (long long)n_outer * n_inner * heads), &t, stream);
+  return mpv_check_launch(who);
+}
+
+extern "C" int mpv_temporal_attn_long_fwd(const void* qkv, void* out, int n_outer, int64_t outer_stride, int n_inner,
+                                          int64_t inner_offset, int64_t t_stride, int T, int heads, int head_dim,
+                                          float scale, hipStream_t stream) {
+  MPV_REQUIRE(qkv && out, MPV_E_ARG, "mpv_temporal_attn_long_fwd: null pointer");
+  TempArgs t = {};
+  t.qkv = (const bf16*)qkv;
+  t.out = (bf16*)out;
+  return temporal_long_launch(false, t, n_outer, outer_stride, n_inner, inner_offset, t_stride, T, heads, head_dim, scale, stream,
+                              "mpv_temporal_attn_long_fwd");
+}
+
+extern "C" int mpv_temporal_attn_long_bwd(const void* qkv, const void* dout, void* dqkv, int n_outer, int64_t outer_stride,
+                                          int n_inner, int64_t inner_offset, int64_t t_stride, int T, int heads,
+                                          int head_dim, float scale, hipStream_t stream) {
+  MPV_REQUIRE(qkv && dout && dqkv, MPV_E_ARG, "mpv_temporal_attn_long_bwd: null pointer");
+  TempArgs t = {};
+  t.qkv = (const bf16*)qkv;
+  t.dout = (const bf16*)dout;
+  t.dqkv = (bf16*)dqkv;
+  return temporal_long_launch(true, t, n_outer, outer_stride, n_inner, inner_offset, t_stride, T, heads, head_dim, scale, stream,
+                              "mpv_temporal_attn_long_bwd");
+}
+
 // ---- read-only queries (tests, tools): what the entry points above would launch.  Host only; nothing on the hot path calls them.
 static int describe_plan(const AttnPlan& pl, mpv_attn_plan_info* out) {
   const AttnVariant& v = ATTN_VARIANT_TABLE[pl.variant];
@@ -2191,6 +2259,14 @@ extern "C" int mpv_temporal_attn_plan_describe(int n_outer, int n_inner, int T, 
   int rc = temporal_common(t, n_outer, 0, n_inner, 0, 0, T, heads, head_dim, 0.f, "mpv_temporal_attn_plan_describe");
   if (rc) return rc;
   return describe_plan(temporal_plan(bwd != 0, T, head_dim, (long long)n_outer * n_inner * heads, attn_knobs()), out);
+}
+
+extern "C" int mpv_temporal_attn_long_plan_describe(int n_outer, int n_inner, int T, int heads, int head_dim, int bwd, mpv_attn_plan_info* out) {
+  MPV_REQUIRE(out, MPV_E_ARG, "mpv_temporal_attn_long_plan_describe: null pointer");
+  TempArgs t = {};
+  int rc = temporal_long_common(t, n_outer, 0, n_inner, 0, 0, T, heads, head_dim, 0.f, "mpv_temporal_attn_long_plan_describe");
+  if (rc) return rc;
+  return describe_plan(temporal_long_plan(bwd != 0, T, (long long)n_outer * n_inner * heads), out);
 }
 
 #ifdef MPV_ATTN_TIMING

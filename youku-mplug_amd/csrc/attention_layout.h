@@ -73,4 +73,12 @@ __host__ __device__ constexpr int temporal_f32_lds(bool bwd, int T, int hd) {
 }
 __host__ __device__ constexpr int temporal_b16_lds(bool bwd, int T, int hd) { return TEMPORAL_B16_WAVES * temporal_b16_wave_lds(bwd, T, hd); }
 
+// ---- temporal attention on the matrix cores (attention_temporal_long.inc; TT = 32 / 64 padded tokens): one problem per wave, one
+// per-wave image of 32-row tiles at the ROWB pitch.  Forward: V, TT rows.  Backward: K (TT rows), then a [Q | dO] tile pair --
+// 64 rows either way --, followed by the per-query fp32 (lse, delta) pairs.
+constexpr int TEMPORAL_MFMA_PITCH = ROWB;
+constexpr int TEMPORAL_MFMA_WAVES = 4;
+__host__ __device__ constexpr int temporal_mfma_wave_lds(bool bwd, int tt) { return bwd ? 64 * TEMPORAL_MFMA_PITCH + tt * 8 : tt * TEMPORAL_MFMA_PITCH; }
+__host__ __device__ constexpr int temporal_mfma_lds(bool bwd, int tt) { return TEMPORAL_MFMA_WAVES * temporal_mfma_wave_lds(bwd, tt); }
+
 }  // namespace attn_layout

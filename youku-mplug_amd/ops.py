@@ -302,16 +302,39 @@ def attn_prefix_fwd(q, k, v, pk, pv, o, lay: AttnLayout, prefix_lay: Tuple[Tuple
     return o
 
 
+TEMPORAL_SHORT_MAX_T = 16      # mpv_temporal_attn_fwd / _bwd: the VALU kernels
+TEMPORAL_MAX_T = 64            # mpv_temporal_attn_long_fwd / _bwd: the matrix-core kernels (one or four 32 x 32 score tiles)
+
+
+def _temporal_entry(T, short, long):
+    """The entry point for a clip of T frames: the short family up to 16 frames (unchanged), the long one for 17..64."""
+    if T > TEMPORAL_MAX_T:
+        raise ValueError(f"temporal attention supports at most {TEMPORAL_MAX_T} frames per clip, got T={T}")
+    return short if T <= TEMPORAL_SHORT_MAX_T else long
+
+
 def temporal_attn_fwd(qkv, out, n_outer, outer_stride, n_inner, inner_offset, t_stride, T, heads, hd, scale):
+    name = _temporal_entry(T, "mpv_temporal_attn_fwd", "mpv_temporal_attn_long_fwd")
     _need_cuda(qkv, out)
-    check(_lib.lib().mpv_temporal_attn_fwd(qkv.data_ptr(), out.data_ptr(), n_outer, outer_stride, n_inner, inner_offset,
-                                           t_stride, T, heads, hd, scale, _stream()), "mpv_temporal_attn_fwd")
+    check(getattr(_lib.lib(), name)(qkv.data_ptr(), out.data_ptr(), n_outer, outer_stride, n_inner, inner_offset,
+                                    t_stride, T, heads, hd, scale, _stream()), name)
 
 
 def temporal_attn_bwd(qkv, dout, dqkv, n_outer, outer_stride, n_inner, inner_offset, t_stride, T, heads, hd, scale):
+    name = _temporal_entry(T, "mpv_temporal_attn_bwd", "mpv_temporal_attn_long_bwd")
     _need_cuda(qkv, dout, dqkv)
-    check(_lib.lib().mpv_temporal_attn_bwd(qkv.data_ptr(), dout.data_ptr(), dqkv.data_ptr(), n_outer, outer_stride, n_inner,
-                                           inner_offset, t_stride, T, heads, hd, scale, _stream()), "mpv_temporal_attn_bwd")
+    check(getattr(_lib.lib(), name)(qkv.data_ptr(), dout.data_ptr(), dqkv.data_ptr(), n_outer, outer_stride, n_inner,
+                                    inner_offset, t_stride, T, heads, hd, scale, _stream()), name)
+
+
+def temporal_attn_long_plan(n_outer, n_inner, T, heads, hd, bwd=False):
+    """What mpv_temporal_attn_long_fwd (bwd=False) / _bwd would launch (include/mpv.h: mpv_temporal_attn_long_plan_describe):
+    dict(variant, grid, block, lds_bytes, lds_limit).  Launches nothing; for tests and tools."""
+    info = _lib.AttnPlanInfo()
+    check(_lib.lib().mpv_temporal_attn_long_plan_describe(n_outer, n_inner, T, heads, hd, int(bool(bwd)), C.byref(info)),
+          "mpv_temporal_attn_long_plan_describe")
+    return dict(variant=info.variant.decode(), grid=(info.grid_x, info.grid_y), block=info.block, lds_bytes=info.lds_bytes,
+                lds_limit=info.lds_limit)
 
 
 def im2col_patches(video, B, Cc, T, H, W, P, kpad):

@@ -259,6 +259,10 @@ class TimeSformer(nn.Module):
         super().__init__()
         D = embed_dim
         assert (D // num_heads) % 8 == 0 and D // num_heads <= 96, "fused attention kernels take head_dim = multiple of 8, <= 96"
+        if not 1 <= num_frames <= ops.TEMPORAL_MAX_T:
+            raise ValueError(f"num_frames={num_frames}: temporal attention supports 1..{ops.TEMPORAL_MAX_T} frames per clip")
+        if num_frames > ops.TEMPORAL_SHORT_MAX_T and (D // num_heads) % 16:
+            raise ValueError(f"num_frames={num_frames} > {ops.TEMPORAL_SHORT_MAX_T} needs head_dim = multiple of 16, got {D // num_heads}")
         self.embed_dim = self.num_features = D
         self.num_frames, self.num_heads, self.depth = num_frames, num_heads, depth
         self.patch_embed = PatchEmbed(img_size, patch_size, in_chans, D, bias=not clip_model, std=init_std, device=device)
