@@ -10,6 +10,8 @@ What this entry point adds to downstream/finetune_common.py:
     per clip), decoded, blanks removed, the prompt cut off -> [{video_id, pred_caption, gold_caption}];
   * `--eval_batched_beam` (not in the reference, default off): `model.generate(..., batched=True)` searches the clips of a batch in
     lockstep (`--clips_per_search` at a time, generation.beam_search_batched_loop); same result files;
+  * `--eval_sample N` (not in the reference, default off): N sampled captions per clip next to the beam caption, as
+    "sampled_captions" in the result file (`model.generate(..., do_sample=True, num_samples=N)`: the sampler on the device);
   * save_result (dataset/utils.py:114-160): one JSON per rank, merged by rank 0; cal_metric (:240-298): predictions and references
     reduced to their CJK characters, one token per character, scored by pycocoevalcap's COCOEvalCap when that package is importable.
     It is not on this image: then BLEU-1..4 (corpus level, closest-reference brevity penalty) and ROUGE-L (beta 1.2, best reference)
@@ -38,8 +40,8 @@ def make_training_batch(video, text, prompt, tokenizer, device, max_length):
 
 
 @torch.no_grad()
-def evaluation(model, data_loader, tokenizer, device, config, batched=False, clips_per_search=32):
-    """-> [{video_id, pred_caption, gold_caption}] (:208-238); batched: `--eval_batched_beam`"""
+def evaluation(model, data_loader, tokenizer, device, config, batched=False, clips_per_search=32, eval_sample=0, seed=0):
+    """-> [{video_id, pred_caption, gold_caption}] (:208-238); batched: `--eval_batched_beam`; eval_sample: `--eval_sample`"""
     module = getattr(model, "module", model)
     module.eval()
     result = []
@@ -48,11 +50,15 @@ def evaluation(model, data_loader, tokenizer, device, config, batched=False, cli
         text = [config["prompt"] for _ in range(video.shape[0])]
         text_input = tokenizer(text, padding="max_length", truncation=True, max_length=20, return_tensors="pt").to(device)
         res = module.generate(video, text_input, batched=True, clips_per_search=clips_per_search) if batched else module.generate(video, text_input)
+        def caption(ids):
+            ans = tokenizer.decode(ids).replace(" ", "").strip()
+            return ans.split(config["prompt"])[-1].strip() if config["prompt"] != "" else ans
         for video_id, r, gold in zip(video_ids, res, gold_caption):
-            ans = tokenizer.decode(r.tolist()[0]).replace(" ", "").strip()
-            if config["prompt"] != "":
-                ans = ans.split(config["prompt"])[-1].strip()
-            result.append({"video_id": video_id, "pred_caption": ans, "gold_caption": list(gold)})
+            result.append({"video_id": video_id, "pred_caption": caption(r.tolist()[0]), "gold_caption": list(gold)})
+        if eval_sample:
+            sampled = module.generate(video, text_input, do_sample=True, num_samples=eval_sample, seed=seed + n, clips_per_search=clips_per_search)
+            for rec, rows in zip(result[-len(sampled):], sampled):
+                rec["sampled_captions"] = [caption(row) for row in rows.tolist()]
         if n == 0:
             print(result)
     return result
@@ -200,7 +206,8 @@ def main(args, config):
 
     if args.evaluate_only:
         result = evaluation(s.model, val_loader, s.tokenizer, s.device, config, batched=getattr(args, "eval_batched_beam", False),
-                            clips_per_search=getattr(args, "clips_per_search", 32))
+                            clips_per_search=getattr(args, "clips_per_search", 32), eval_sample=getattr(args, "eval_sample", 0),
+                            seed=getattr(args, "seed", 0) or 0)
         val_stats = cal_metric(save_result(result, args.result_dir, "val_caption_result"))
         print("* Validation Stats:", val_stats)
         log_stats = {**{f"val_{k}": v for k, v in val_stats.items()}, "n_parameters": s.n_parameters}
@@ -216,6 +223,8 @@ def get_args(argv=None):
                        help="evaluation: beam-search the clips of a batch in lockstep (model.generate(batched=True)) instead of one by one")
         p.add_argument("--clips_per_search", type=int, default=32,
                        help="--eval_batched_beam: clips per lockstep search (KV memory: clips x beams x 2 cache copies)")
+        p.add_argument("--eval_sample", type=int, default=0,
+                       help="evaluation: also write N sampled captions per clip (model.generate(do_sample=True, num_samples=N))")
     args, config = ft.get_args(argv, extra=extra)
     config.setdefault("prompt", "")
     args.result_dir = os.path.join(args.output_dir, "result")

@@ -444,6 +444,60 @@ typedef struct mpv_beam_advance_desc {
 } mpv_beam_advance_desc;
 int mpv_beam_advance(const mpv_beam_advance_desc* d, mpv_stream_t stream);
 /* ------------------------------------------------------------------------------------------
+ * Sampled generation in lockstep (generation.sample_batched_loop): ONE launch draws the next token of `rows` sequences and does the
+ * bookkeeping of one iteration of the reference's sample loop (models/modeling_distributed_gpt3.py:1689-1728).  The filters follow
+ * :1369-1441; the tie order that the reference leaves to an unstable sort is fixed here.  One sampling step of row r:
+ * Input: logits row r of a bf16 [rows][ld] matrix, first `vocab` columns; temperature T > 0; exactly one of plain (top_k == 0,
+ *   top_p == 0), greedy (top_k == 1), top-k (top_k > 1), top-p (0 < top_p <= 1).  NaN logits are not supported.
+ * Probabilities: z_i = float(l_i) / T, p_i proportional to exp(z_i - max z), fp32.  A logit of -inf has probability 0 and is never
+ *   a member of the kept set (it is not counted in out_kept and cannot be drawn).  -0 and +0 are one value.
+ * Greedy: the arg-max, lowest index among ties (the rule of mpv_logprob_topk).
+ * Top-k (k > 1): every i with l_i >= the k-th largest logit stays; ties with the k-th value all stay (the reference's
+ *   `logits < kth` mask).
+ * Top-p: order by (logit descending, index ascending); with c_j the inclusive cumulative probability in that order, entry j stays
+ *   iff j == 0 or c_{j-1} <= top_p (the reference's right-shifted `cumulative > top_p` mask).  top_p == 1 keeps everything.
+ * Draw: u in [0, 1); the token is the smallest index i, in VOCABULARY-INDEX order, of the kept set with
+ *   sum_{kept j <= i} p_j > u * sum_{kept} p_j; if no index qualifies, the last kept index.  (Index order: a plain prefix scan,
+ *   independent of any sort.)
+ * The uniform: u = (h >> 8) * 2^-24 with h the 32-bit hash mpv_rand_pair of csrc/mpv_common.h for the seed `seed` and the counter
+ *   (uint64(pos) << 32) | uint32(stream_id[r]); stream_id is a per-row int64 array of the caller's choice, NULL = the row index.  A
+ *   row's token depends on (its logits, T, the filter, seed, pos, stream_id[r]) only -- neither on `rows` nor on the row's place in
+ *   the launch.  u_override (fp32 [rows], optional) replaces the hash; the generation loop does not use it.
+ * Clamp: with vocab_size > 0 the token is clamped to [0, vocab_size - 1] (the reference's padded-vocabulary clamp); 0 = no clamp.
+ * A row whose every logit is -inf yields token 0, kept count 0, kept mass 0.
+ * Bookkeeping, per row: started = prompt_len[r] <= pos; if started, tokens[r][pos] = token, otherwise the prompt token stays
+ *   (teacher forcing); next_tok[r] = tokens[r][pos] after that; done[r] |= started && terminated(token), with termination_mode
+ *   0: token == termination_id; 1 (stop_on_eol): token is 628 or 198; 2 (stop_on_double_eol): 628, or 198 with tokens[r][pos - 1]
+ *   == 198 (pos == 0 has no previous token).  n_done (one int32) receives the number of rows whose done flag is set after the call.
+ *   tokens is int64 [rows][row_len], updated in place: a row writes only its own column `pos`.
+ * Optional outputs (NULL = not wanted): out_kept int32 [rows] the size of the kept set, out_mass fp32 [rows] its mass as a fraction
+ *   of the total, out_token int64 [rows] the (clamped) sampled token before the started / teacher-forcing logic.
+ * Refused with a negative code before any launch: vocab not a multiple of 8 or outside [8, 65536]; ld < vocab or ld % 8 != 0;
+ *   logits not 16-byte aligned; T <= 0 or not finite; top_k > 1 or top_k == 1 together with top_p > 0; top_k < 0 or > vocab;
+ *   top_p < 0 or > 1; pos outside [0, row_len); a termination_mode other than 0, 1, 2; a NULL logits / tokens / prompt_len / done /
+ *   next_tok / n_done.
+ * One workgroup per row, the row read once; fixed-order reductions and no floating-point atomics: the same inputs give the same
+ *   outputs, bit for bit, on every run. */
+typedef struct mpv_sample_advance_desc {
+  const void* logits;
+  const int64_t* stream_id;
+  const float* u_override;
+  const int64_t* prompt_len;
+  int64_t* tokens;
+  int32_t* done;
+  int64_t* next_tok;
+  int32_t* n_done;
+  int32_t* out_kept;
+  float* out_mass;
+  int64_t* out_token;
+  int64_t ld;
+  uint64_t seed;
+  int64_t termination_id;
+  int rows, vocab, row_len, pos, top_k, vocab_size, termination_mode;
+  float temperature, top_p;
+} mpv_sample_advance_desc;
+int mpv_sample_advance(const mpv_sample_advance_desc* d, mpv_stream_t stream);
+/* ------------------------------------------------------------------------------------------
  * Device-side video input transform (configs' video_pretrain/train/test transforms,
  * dataset/__init__.py:60-85): the decoder's uint8 clip [T][H][W][3] -> crop (i, j, h, w) ->
  * torch.nn.functional.interpolate to out_h x out_w (mode 0 nearest / 1 bilinear / 2 bicubic, align_corners=False:

@@ -81,6 +81,14 @@ class BeamAdvanceDesc(C.Structure):
                [(n, c_int) for n in ("batch", "beams", "row_len", "vocab", "pos", "cur_len", "first")] + [("stop_token", c_int64)]
 
 
+class SampleAdvanceDesc(C.Structure):
+    _fields_ = [(n, c_void_p) for n in ("logits", "stream_id", "u_override", "prompt_len", "tokens", "done", "next_tok", "n_done", "out_kept",
+                                        "out_mass", "out_token")] + \
+               [("ld", c_int64), ("seed", c_uint64), ("termination_id", c_int64)] + \
+               [(n, c_int) for n in ("rows", "vocab", "row_len", "pos", "top_k", "vocab_size", "termination_mode")] + \
+               [("temperature", c_float), ("top_p", c_float)]
+
+
 _RM = [c_int, c_int, c_int]
 _SIGS = {
     "mpv_version": (c_int, []),
@@ -155,6 +163,7 @@ _SIGS = {
     "mpv_logprob_topk_workspace_size": (c_size_t, [c_int64, c_int]),
     "mpv_logprob_topk": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mpv_beam_advance": (c_int, [C.POINTER(BeamAdvanceDesc), c_void_p]),
+    "mpv_sample_advance": (c_int, [C.POINTER(SampleAdvanceDesc), c_void_p]),
     "mpv_soft_target_ce": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     "mpv_maxsim_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p]),
     "mpv_maxsim_route": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p]),

@@ -330,14 +330,23 @@ class DistributedGPT3_Caption(_GenCls):
         return self._run(image, text, None, None, None, True)[0]                              # :768-789 returns loss_caption only
 
     @torch.no_grad()
-    def generate(self, image, text, termination_id=None, batched=False, clips_per_search=32, **kw):
+    def generate(self, image, text, termination_id=None, batched=False, clips_per_search=32, do_sample=False, num_samples=1, temperature=1.0,
+                 top_k=None, top_p=None, seed=0, **kw):
         """One beam search per sample (:790-809): prompt = text.input_ids[i, :mask.sum()-1], prefix = its query features.
         batched=True (not in the reference, default off): the clips are grouped by prompt length and every group is searched in
         lockstep, `clips_per_search` clips at a time (generation.beam_search_batched_loop: the decoder's weights are read once per
         generated position of a chunk, not once per clip; the prefill runs once per clip).  Same return value: one [n, Lt] tensor
         per clip, in input order.  KV memory is what bounds clips_per_search: a chunk holds clips_per_search x beam_size sequences
         in both copies of the cache -- at 1.3B dims 88 MB per sequence of 300 positions, so 32 clips x 5 beams x 2 copies is about
-        28 GB; halve clips_per_search to halve it."""
+        28 GB; halve clips_per_search to halve it.
+        do_sample=True (not in the reference, default off): `num_samples` SAMPLED captions per clip instead of the beam search, with
+        the sampler on the device (generation.sample_batched_loop; temperature, top_k / top_p -- None: the decoder's configuration --
+        and seed as there).  The clips are grouped and chunked as with batched=True; sample s of clip i (its index in this call) draws
+        from stream i * num_samples + s, so a clip's samples depend neither on clips_per_search nor on the other clips of the call.
+        A chunk stops when all of its sequences have terminated, and a terminated sequence goes on drawing until then (as in the
+        reference's sample): every row is therefore cut behind its first termination token and padded with that token to the full
+        width Lt = prompt columns + tokens_to_generate, which is what makes the result independent of the chunking.
+        -> per clip one [num_samples, Lt] tensor, in input order."""
         Bv = image.shape[0]
         Q, Hh = self.num_learnable_token, self.text_width
         was = self.training
@@ -348,6 +357,29 @@ class DistributedGPT3_Caption(_GenCls):
                 tok = getattr(self, "tokenizer", None)
                 termination_id = tok.tokenizer.eos if tok is not None else None
             n = text.input_ids.shape[0]
+            if do_sample:
+                from . import generation
+                N = int(num_samples)
+                if int(clips_per_search) < 1 or N < 1:
+                    raise ValueError(f"clips_per_search and num_samples must be at least 1 (got {clips_per_search}, {num_samples})")
+                lengths = (text.attention_mask.sum(-1) - 1).tolist()
+                gc = generation._gen_config(self.text_decoder)
+                term = gc.eod_id if termination_id is None else int(termination_id)
+                width = min(text.input_ids.shape[1] + gc.tokens_to_generate, gc.max_position_embeddings)
+                res = [None] * n
+                for pl in sorted(set(lengths)):
+                    group = [i for i in range(n) if lengths[i] == pl]
+                    for c in range(0, len(group), int(clips_per_search)):
+                        sel = torch.as_tensor(group[c:c + int(clips_per_search)], dtype=torch.long, device=qf.device)
+                        streams = (sel[:, None] * N + torch.arange(N, device=qf.device)[None]).reshape(-1)
+                        out = self.text_decoder.sample_batched(text.input_ids[sel], query_embeds=qf[sel].contiguous(), temperature=temperature,
+                                                               num_samples=N, seed=seed, streams=streams, top_k=top_k, top_p=top_p,
+                                                               termination_id=termination_id,
+                                                               prompt_length=torch.full((len(sel),), int(pl), device=qf.device), **kw)
+                        out = generation.pad_after_termination(out, int(pl), term, width, term).cpu()
+                        for j, i in enumerate(sel.tolist()):
+                            res[i] = out[j * N:(j + 1) * N]
+                return res
             if batched:
                 if int(clips_per_search) < 1:
                     raise ValueError(f"clips_per_search must be at least 1 (got {clips_per_search})")

@@ -9,7 +9,8 @@ keeps [max_s, b, np, hn] K and V tensors and copies into them, :905-915).  A ste
 every sequence (prefill: the visual prefix + prompt; afterwards one token), attends causally over the cached rows and
 runs the LM head on the last position only.  Beam re-ordering (swap_key_value_dict) is one strided row gather per
 layer into the twin buffer.  The search logic of the per-clip loops stays on the host, as in the reference; the lockstep
-search over a batch of clips (beam_search_batched_loop) keeps it on the device (ops.beam_advance, csrc/beam_search.hip).
+search over a batch of clips (beam_search_batched_loop) keeps it on the device (ops.beam_advance, csrc/beam_search.hip), and so does
+sampled generation in lockstep (sample_batched_loop: ops.sample_advance, csrc/sampling.hip).
 """
 from __future__ import annotations
 
@@ -399,8 +400,85 @@ def sample_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None, temper
     return tokens[:, :context_length + 1]      # (sic) the reference slices with the prefix-inclusive length (:1733)
 
 
+class SampleState:
+    """The state of sample_batched_loop for `rows` sequences, as device tensors (struct of arrays; the contract of include/mpv.h:
+    mpv_sample_advance): the token table, the prompt lengths, the done flags, the tokens the next decode step consumes, the stream
+    number that keys every row's uniforms, and the count of done rows (the loop's one host read per step)."""
+
+    def __init__(self, tokens: torch.Tensor, prompt_len: torch.Tensor, streams: Optional[torch.Tensor] = None):
+        R, Lt = tokens.shape
+        dev = tokens.device
+        self.rows, self.row_len = R, Lt
+        self.tokens = tokens.to(torch.int64).contiguous().clone()
+        self.prompt_len = prompt_len.to(device=dev, dtype=torch.int64).reshape(-1).expand(R).contiguous().clone()
+        self.done = torch.zeros(R, dtype=torch.int32, device=dev)
+        self.next_tok = torch.zeros(R, dtype=torch.int64, device=dev)
+        self.stream = (torch.arange(R, dtype=torch.int64, device=dev) if streams is None
+                       else torch.as_tensor(streams, device=dev).to(torch.int64).reshape(-1).contiguous().clone())
+        assert self.stream.numel() == R, (self.stream.numel(), R)
+        self.n_done = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    ARRAYS = ("tokens", "prompt_len", "done", "next_tok", "stream", "n_done")
+
+
+def sample_batched_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None, temperature=1.0, use_eod_token_for_early_termination=True,
+                        stop_on_double_eol=False, stop_on_eol=False, termination_id=None, prompt_length=None, num_samples=1, seed=0,
+                        streams=None, advance_fn=None):
+    """sample_loop with the whole of a step's sampling and bookkeeping in one launch, for B clips x num_samples sequences in lockstep:
+    tokens [B, L], query_embeds [B, Q, H], prompt_length [B] (ragged lengths are allowed) or None.  Sequence j belongs to clip
+    j // num_samples.  The prefill runs once per clip over the shortest prompt (state.prefill_fan_out) and fans out to the clip's
+    samples; afterwards a step is state.step(next_tok) and advance_fn (ops.sample_advance: filter, draw, teacher forcing behind the
+    prefill, termination; include/mpv.h states the semantics).  Samples never swap KV caches, so nothing is re-ordered, and the host
+    reads four bytes per step (the count of done rows).  Row j draws from the stream streams[j] (default j) of `seed`: its tokens do
+    not depend on the other rows of the call.  cfg.top_k / cfg.top_p choose the filter as in sample_loop.  -> tokens [B * num_samples,
+    n] with sample_loop's (prefix-inclusive, sic) slice.  make_state and advance_fn are injectable as in beam_search_batched_loop."""
+    B, dev, N = tokens.size(0), tokens.device, int(num_samples)
+    if N < 1:
+        raise ValueError(f"num_samples must be at least 1 (got {num_samples})")
+    lengths = prompt_length if prompt_length is not None else torch.tensor([tokens.size(1)], device=dev)
+    lengths = torch.as_tensor(lengths, device=dev).view(-1).expand(B)
+    tokens = torch.cat((tokens, torch.full((B, cfg.tokens_to_generate), cfg.eod_id, dtype=torch.long, device=dev)), dim=-1)
+    min_prompt = int(lengths.min().item())
+    max_len = min(tokens.size(1), cfg.max_position_embeddings)
+    if min_prompt >= max_len:
+        raise ValueError("context length + tokens_to_generate too large")
+    Q = 0 if query_embeds is None else query_embeds.size(1)
+    R = B * N
+    state = make_state(R, max_len + Q)
+    st = SampleState(tokens.repeat_interleave(N, dim=0), lengths.repeat_interleave(N), streams=streams)
+    termination_id = cfg.eod_id if termination_id is None else int(termination_id)
+    mode = 2 if stop_on_double_eol else 1 if stop_on_eol else 0
+    total_min, total_max = min_prompt + Q, max_len + Q
+    context_length = total_min
+    for context_length in range(total_min, total_max):
+        if context_length == total_min:
+            logits = state.prefill_fan_out(tokens[:, :min_prompt].contiguous(), query_embeds, N)
+        else:
+            logits = state.step(st.next_tok.view(-1, 1))
+        advance_fn(logits, st, pos=context_length - Q, temperature=temperature, top_k=cfg.top_k, top_p=cfg.top_p, seed=seed,
+                   vocab_size=cfg.vocab_size, termination_mode=mode, termination_id=termination_id)
+        if use_eod_token_for_early_termination and int(st.n_done.item()) == R:       # the step's one host read: 4 bytes
+            break
+    return st.tokens[:, :context_length + 1]      # (sic) as sample_loop
+
+
+def pad_after_termination(tokens: torch.Tensor, prompt_len: int, termination_id: int, width: int, fill: int) -> torch.Tensor:
+    """tokens [R, n] (what sample_batched_loop returns) -> [R, width]: every row keeps its columns up to and including the first
+    `termination_id` at or behind column `prompt_len`; what follows (tokens drawn while other rows were still running, and the
+    columns the loop never reached) is `fill`."""
+    R, n = tokens.shape
+    out = torch.full((R, width), int(fill), dtype=tokens.dtype, device=tokens.device)
+    out[:, :min(n, width)] = tokens[:, :width]
+    col = torch.arange(width, device=tokens.device)[None]
+    hit = (out == int(termination_id)) & (col >= int(prompt_len))
+    first = torch.where(hit.any(dim=1), hit.int().argmax(dim=1), torch.full((R,), width, device=tokens.device))
+    out[col > first[:, None]] = int(fill)
+    return out
+
+
 def install(gpt_cls):
-    """Adds sample / beam_search / generate to DistributedGPT3 (same signatures as the reference methods), and beam_search_batched."""
+    """Adds sample / beam_search / generate to DistributedGPT3 (same signatures as the reference methods), and beam_search_batched /
+    sample_batched."""
 
     def _make_state(self):
         return lambda batch, max_len: DecodeState(self, batch, max_len)
@@ -419,11 +497,26 @@ def install(gpt_cls):
                                         num_return_gen=num_return_gen, stop_token=stop_token, prompt_length=kw.pop("prompt_length", None),
                                         topk_fn=lambda lg, k, add: ops.logprob_topk(lg, k, add=add), advance_fn=ops.beam_advance)
 
+    def sample_batched(self, tokens, query_embeds=None, temperature=1.0, num_samples=1, seed=0, streams=None, top_k=None, top_p=None, **kw):
+        """sample with the sampler on the device (sample_batched_loop): tokens [B, L] -> [B * num_samples, n]; top_k / top_p override
+        the configuration's values; the draws are those of (seed, position, streams[row]) -- not torch's generator"""
+        cfg = _gen_config(self)
+        if top_k is not None or top_p is not None:
+            cfg.top_k, cfg.top_p = int(top_k or 0), float(top_p or 0.0)
+        return sample_batched_loop(cfg, _make_state(self), tokens, query_embeds=query_embeds, temperature=temperature, num_samples=num_samples,
+                                   seed=seed, streams=streams, advance_fn=ops.sample_advance, **kw)
+
     @torch.no_grad()
     def generate(self, tokens, do_sample=True, termination_id=None, *args, **kw):                # :1875-1880
+        """sampler="device" (keyword; not in the reference, default "torch"): do_sample=True runs sample_batched"""
+        sampler = kw.pop("sampler", "torch")
+        if sampler not in ("torch", "device"):
+            raise ValueError(f"sampler must be 'torch' or 'device' (got {sampler!r})")
         was = self.training
         self.eval()
         try:
+            if do_sample and sampler == "device":
+                return self.sample_batched(tokens, termination_id=termination_id, *args, **kw)
             if do_sample:
                 return self.sample(tokens, termination_id=termination_id, *args, **kw)
             return self.beam_search(tokens, stop_token=termination_id, *args, **kw)
@@ -431,4 +524,4 @@ def install(gpt_cls):
             self.train(was)
 
     gpt_cls.sample, gpt_cls.beam_search, gpt_cls.generate = sample, beam_search, generate
-    gpt_cls.beam_search_batched = beam_search_batched
+    gpt_cls.beam_search_batched, gpt_cls.sample_batched = beam_search_batched, sample_batched

@@ -624,6 +624,58 @@ def beam_advance(cand_val, cand_idx, st, *, vocab, pos, cur_len, first, stop_tok
     return st.src_row, st.next_tok
 
 
+TERMINATION_ID, TERMINATION_EOL, TERMINATION_DOUBLE_EOL = 0, 1, 2      # mpv_sample_advance_desc.termination_mode
+
+
+def sample_advance_desc(logits, st, *, pos, temperature=1.0, top_k=0, top_p=0.0, seed=0, vocab_size=None, termination_mode=TERMINATION_ID,
+                        termination_id=0, u_override=None, out_kept=None, out_mass=None, out_token=None, vocab=None, ld=None):
+    """The descriptor of one mpv_sample_advance call (include/mpv.h) for logits bf16 [rows, ld] and a generation.SampleState."""
+    d = _lib.SampleAdvanceDesc()
+    d.logits, d.stream_id, d.u_override, d.prompt_len = _p(logits), _p(st.stream), _p(u_override), _p(st.prompt_len)
+    d.tokens, d.done, d.next_tok, d.n_done = _p(st.tokens), _p(st.done), _p(st.next_tok), _p(st.n_done)
+    d.out_kept, d.out_mass, d.out_token = _p(out_kept), _p(out_mass), _p(out_token)
+    d.ld = int(ld) if ld is not None else (logits.stride(0) if logits is not None else 0)
+    d.seed, d.termination_id = int(seed) & 0xFFFFFFFFFFFFFFFF, int(termination_id)
+    d.rows, d.row_len, d.pos = st.rows, st.row_len, int(pos)
+    d.vocab = int(vocab) if vocab is not None else (logits.shape[-1] if logits is not None else 0)
+    d.top_k, d.vocab_size, d.termination_mode = int(top_k), int(vocab_size or 0), int(termination_mode)
+    d.temperature, d.top_p = float(temperature), float(top_p)
+    return d
+
+
+def sample_advance(logits, st, *, pos, temperature=1.0, top_k=0, top_p=0.0, seed=0, vocab_size=None, termination_mode=TERMINATION_ID,
+                   termination_id=0, u_override=None, out_kept=None, out_mass=None, out_token=None, vocab=None, ld=None):
+    """One position of sampled generation for st.rows sequences in one launch (include/mpv.h: mpv_sample_advance; st is a
+    generation.SampleState): temperature, the top-k / top-p filter, the draw with the counter-based uniform of (seed, pos, st.stream),
+    the write into st.tokens[:, pos] behind the prompt, st.next_tok, st.done and st.n_done.  logits bf16 [rows, ld], the first `vocab`
+    columns are read.  u_override fp32 [rows] replaces the uniform; out_kept int32 / out_mass fp32 / out_token int64 [rows] are optional
+    diagnostics.  -> st.next_tok"""
+    _need_cuda(logits, st.tokens, u_override, out_kept, out_mass, out_token)
+    if logits.dtype != torch.bfloat16 or logits.ndim != 2 or logits.shape[0] < st.rows or logits.stride(1) != 1:
+        raise _lib.MpvError(f"sample_advance: logits must be bf16 [{st.rows}, ld] with unit column stride (got {logits.dtype} {tuple(logits.shape)})")
+    for name, t, dt in (("u_override", u_override, torch.float32), ("out_kept", out_kept, torch.int32), ("out_mass", out_mass, torch.float32),
+                        ("out_token", out_token, torch.int64)):
+        if t is not None and (t.dtype != dt or t.numel() < st.rows or not t.is_contiguous()):
+            raise _lib.MpvError(f"sample_advance: {name} must be contiguous {dt} [{st.rows}]")
+    d = sample_advance_desc(logits, st, pos=pos, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, vocab_size=vocab_size,
+                            termination_mode=termination_mode, termination_id=termination_id, u_override=u_override, out_kept=out_kept,
+                            out_mass=out_mass, out_token=out_token, vocab=vocab, ld=ld)
+    check(_lib.lib().mpv_sample_advance(C.byref(d), _stream()), "mpv_sample_advance")
+    return st.next_tok
+
+
+def sample_tokens(logits, *, temperature=1.0, top_k=0, top_p=0.0, seed=0, streams=None, vocab_size=None, vocab=None):
+    """One-off draw: -> int64 [rows], the token sample_advance draws at pos 0 for every row of logits bf16 [rows, ld] (no prompt, no
+    termination; vary `seed` or `streams` for another draw)."""
+    from .generation import SampleState
+    rows = logits.shape[0]
+    st = SampleState(torch.zeros((rows, 1), dtype=torch.int64, device=logits.device), torch.zeros(rows, dtype=torch.int64, device=logits.device),
+                     streams=streams)
+    sample_advance(logits, st, pos=0, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, vocab_size=vocab_size, termination_id=-1,
+                   vocab=vocab)
+    return st.tokens.view(-1)
+
+
 def soft_target_ce(sim, row_ids, col_ids, scale, rows, cols, want_grad=True):
     losses = torch.empty(rows, dtype=torch.float32, device=sim.device)
     dsim = torch.empty((rows, cols), dtype=torch.bfloat16, device=sim.device) if want_grad else None
