@@ -12,6 +12,8 @@ What this entry point adds to downstream/finetune_common.py:
     lockstep (`--clips_per_search` at a time, generation.beam_search_batched_loop); same result files;
   * `--eval_sample N` (not in the reference, default off): N sampled captions per clip next to the beam caption, as
     "sampled_captions" in the result file (`model.generate(..., do_sample=True, num_samples=N)`: the sampler on the device);
+  * `--eval_shared_kv` (not in the reference, default off): `--eval_batched_beam` and `--eval_sample` cache the query slots and the
+    prompt once per clip instead of once per beam or sample (`model.generate(..., kv_cache="shared_prefix")`); same result files;
   * save_result (dataset/utils.py:114-160): one JSON per rank, merged by rank 0; cal_metric (:240-298): predictions and references
     reduced to their CJK characters, one token per character, scored by pycocoevalcap's COCOEvalCap when that package is importable.
     It is not on this image: then BLEU-1..4 (corpus level, closest-reference brevity penalty) and ROUGE-L (beta 1.2, best reference)
@@ -40,23 +42,26 @@ def make_training_batch(video, text, prompt, tokenizer, device, max_length):
 
 
 @torch.no_grad()
-def evaluation(model, data_loader, tokenizer, device, config, batched=False, clips_per_search=32, eval_sample=0, seed=0):
-    """-> [{video_id, pred_caption, gold_caption}] (:208-238); batched: `--eval_batched_beam`; eval_sample: `--eval_sample`"""
+def evaluation(model, data_loader, tokenizer, device, config, batched=False, clips_per_search=32, eval_sample=0, seed=0, shared_kv=False):
+    """-> [{video_id, pred_caption, gold_caption}] (:208-238); batched: `--eval_batched_beam`; eval_sample: `--eval_sample`;
+    shared_kv: `--eval_shared_kv` (the lockstep calls only)"""
     module = getattr(model, "module", model)
     module.eval()
+    kvkw = {"kv_cache": "shared_prefix"} if shared_kv else {}                # flag absent: the calls below are unchanged
     result = []
     for n, (video, video_ids, gold_caption) in enumerate(data_loader):
         video = video.to(device, non_blocking=True).bfloat16()
         text = [config["prompt"] for _ in range(video.shape[0])]
         text_input = tokenizer(text, padding="max_length", truncation=True, max_length=20, return_tensors="pt").to(device)
-        res = module.generate(video, text_input, batched=True, clips_per_search=clips_per_search) if batched else module.generate(video, text_input)
+        res = module.generate(video, text_input, batched=True, clips_per_search=clips_per_search, **kvkw) if batched else module.generate(video, text_input)
         def caption(ids):
             ans = tokenizer.decode(ids).replace(" ", "").strip()
             return ans.split(config["prompt"])[-1].strip() if config["prompt"] != "" else ans
         for video_id, r, gold in zip(video_ids, res, gold_caption):
             result.append({"video_id": video_id, "pred_caption": caption(r.tolist()[0]), "gold_caption": list(gold)})
         if eval_sample:
-            sampled = module.generate(video, text_input, do_sample=True, num_samples=eval_sample, seed=seed + n, clips_per_search=clips_per_search)
+            sampled = module.generate(video, text_input, do_sample=True, num_samples=eval_sample, seed=seed + n, clips_per_search=clips_per_search,
+                                      **kvkw)
             for rec, rows in zip(result[-len(sampled):], sampled):
                 rec["sampled_captions"] = [caption(row) for row in rows.tolist()]
         if n == 0:
@@ -207,7 +212,7 @@ def main(args, config):
     if args.evaluate_only:
         result = evaluation(s.model, val_loader, s.tokenizer, s.device, config, batched=getattr(args, "eval_batched_beam", False),
                             clips_per_search=getattr(args, "clips_per_search", 32), eval_sample=getattr(args, "eval_sample", 0),
-                            seed=getattr(args, "seed", 0) or 0)
+                            seed=getattr(args, "seed", 0) or 0, shared_kv=getattr(args, "eval_shared_kv", False))
         val_stats = cal_metric(save_result(result, args.result_dir, "val_caption_result"))
         print("* Validation Stats:", val_stats)
         log_stats = {**{f"val_{k}": v for k, v in val_stats.items()}, "n_parameters": s.n_parameters}
@@ -225,6 +230,9 @@ def get_args(argv=None):
                        help="--eval_batched_beam: clips per lockstep search (KV memory: clips x beams x 2 cache copies)")
         p.add_argument("--eval_sample", type=int, default=0,
                        help="evaluation: also write N sampled captions per clip (model.generate(do_sample=True, num_samples=N))")
+        p.add_argument("--eval_shared_kv", action="store_true", default=False,
+                       help="--eval_batched_beam / --eval_sample: cache the query slots and the prompt once per clip "
+                            "(model.generate(kv_cache='shared_prefix')) instead of once per beam or sample")
     args, config = ft.get_args(argv, extra=extra)
     config.setdefault("prompt", "")
     args.result_dir = os.path.join(args.output_dir, "result")

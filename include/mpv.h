@@ -222,6 +222,30 @@ typedef struct mpv_attn_prefix_desc {
 } mpv_attn_prefix_desc;
 int mpv_attn_prefix_fwd(const mpv_attn_prefix_desc* d, mpv_stream_t stream);
 
+/* One decode step's attention for sequences that share a per-group prefix KV cache (lockstep beam search / sampling: the K
+ * beams or samples of a clip share the visual prefix and the prompt).  n_seq sequences in groups of group_size consecutive
+ * ones: sequence s belongs to group s / group_size (n_groups = ceil(n_seq / group_size); the last group may be short).  Every
+ * sequence has ONE query row.  It attends, in this order, to the prefix_len keys of its group's prefix (pk / pv) and to its own
+ * own_len keys (k / v; the last of them is the current position's; own_len is the same for every sequence): ONE softmax over
+ * the concatenation, softmax(scale * q.k) with fp32 scores and statistics (scale multiplies the fp32 scores; q is not
+ * pre-scaled), probabilities rounded to bf16 for the PV product.  Element (s,h,d) of q / o lives at X + s*x_ss + h*x_hs + d,
+ * element (s,h,j,d) of k / v at X + s*x_ss + h*x_hs + j*x_rs + d, element (g,h,j,d) of pk / pv at X + g*x_gs + h*x_hs + j*x_rs
+ * + d.  Rows of k / v at and beyond own_len are never read.  o is bf16; nothing else is written.  The output of a sequence is a
+ * function of its group's prefix and its own rows only, bit for bit: not of n_groups, the group's place or the sequence's place
+ * in its group.  head_dim 64 or 80, prefix_len >= 1, 1 <= own_len <= 2048, group_size >= 1 (rows go in tiles of 32); q / k / v /
+ * pk / pv rows 16-byte aligned, o rows 8-byte aligned.  Anything else: a negative code before any launch. */
+typedef struct mpv_attn_decode_shared_desc {
+  const void *q, *k, *v;     /* per sequence */
+  const void *pk, *pv;       /* per group */
+  void* o;
+  int64_t q_ss, q_hs, k_ss, k_hs, k_rs, v_ss, v_hs, v_rs;
+  int64_t pk_gs, pk_hs, pk_rs, pv_gs, pv_hs, pv_rs;
+  int64_t o_ss, o_hs;
+  int n_seq, group_size, n_groups, heads, prefix_len, own_len, head_dim;
+  float scale;
+} mpv_attn_decode_shared_desc;
+int mpv_attn_decode_shared_fwd(const mpv_attn_decode_shared_desc* d, mpv_stream_t stream);
+
 /* Divided space-time "temporal" attention: T<=16 tokens per (b,n) sequence, many tiny
  * problems (models/vision_transformer.py:247-248 with Attention :169-207).  qkv is the packed
  * [rows][3*D] projection in stream layout; sequence (o,i) (o<n_outer, i<n_inner) has its token
@@ -399,6 +423,17 @@ size_t mpv_gpt_decode_workspace_size(const mpv_gpt_weights* w, int batch, int n_
 int mpv_gpt_decode_step(const mpv_gpt_weights* w, void* const* kv_cache, int batch, int max_len, int pos0, const void* query,
                         int Q, const int64_t* tokens, int L, void* workspace, size_t workspace_bytes, void* logits,
                         mpv_stream_t stream);
+/* mpv_gpt_decode_step for ONE new token per sequence against a per-group shared prefix: n_seq = n_groups * fan sequences,
+ * sequence s continues the prefix of group s / fan.  prefix_cache[l] = [n_groups][prefix_len][3*hidden] (what a prefill through
+ * mpv_gpt_decode_step at batch n_groups, max_len = prefix_len, pos0 = 0 leaves), suffix_cache[l] = [n_seq][suffix_max][3*hidden],
+ * both in the decoder's q|k|v row format.  The token sits at suffix position t (absolute position prefix_len + t, which must
+ * lie inside the position embedding): its qkv row is written to suffix row s*suffix_max + t, the attention is
+ * mpv_attn_decode_shared_fwd with own_len = t + 1, the rest of the layer and the LM head are those of mpv_gpt_decode_step.
+ * logits [n_seq][vocab] bf16.  The workspace is that of a batch n_seq, one-position step. */
+size_t mpv_gpt_decode_shared_workspace_size(const mpv_gpt_weights* w, int n_seq);
+int mpv_gpt_decode_step_shared(const mpv_gpt_weights* w, void* const* prefix_cache, void* const* suffix_cache, int n_groups, int fan,
+                               int prefix_len, int suffix_max, int t, const int64_t* tokens, void* workspace,
+                               size_t workspace_bytes, void* logits, mpv_stream_t stream);
 /* beam re-order of all layers: dst[l][j] = src[l][idx[j]] for the first `rows` cached positions */
 int mpv_kv_reorder(void* const* src, void* const* dst, int layers, const int64_t* idx, int batch, int max_len, int rows,
                    int hidden, mpv_stream_t stream);

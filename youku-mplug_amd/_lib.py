@@ -61,6 +61,20 @@ class AttnPrefixDesc(C.Structure):
     ]
 
 
+class AttnDecodeSharedDesc(C.Structure):
+    _fields_ = [
+        ("q", c_void_p), ("k", c_void_p), ("v", c_void_p), ("pk", c_void_p), ("pv", c_void_p), ("o", c_void_p),
+        ("q_ss", c_int64), ("q_hs", c_int64),
+        ("k_ss", c_int64), ("k_hs", c_int64), ("k_rs", c_int64),
+        ("v_ss", c_int64), ("v_hs", c_int64), ("v_rs", c_int64),
+        ("pk_gs", c_int64), ("pk_hs", c_int64), ("pk_rs", c_int64),
+        ("pv_gs", c_int64), ("pv_hs", c_int64), ("pv_rs", c_int64),
+        ("o_ss", c_int64), ("o_hs", c_int64),
+        ("n_seq", c_int), ("group_size", c_int), ("n_groups", c_int), ("heads", c_int), ("prefix_len", c_int),
+        ("own_len", c_int), ("head_dim", c_int), ("scale", c_float),
+    ]
+
+
 class SimSearchDesc(C.Structure):
     _fields_ = [
         ("queries", c_void_p), ("gallery", c_void_p), ("q_rs", c_int64), ("g_rs", c_int64), ("nq", c_int64), ("ng", c_int64),
@@ -113,6 +127,7 @@ _SIGS = {
     "mpv_attn_plan_describe": (c_int, [C.POINTER(AttnDesc), c_int, C.POINTER(AttnPlanInfo)]),
     "mpv_temporal_attn_plan_describe": (c_int, [c_int] * 6 + [C.POINTER(AttnPlanInfo)]),
     "mpv_attn_prefix_fwd": (c_int, [C.POINTER(AttnPrefixDesc), c_void_p]),
+    "mpv_attn_decode_shared_fwd": (c_int, [C.POINTER(AttnDecodeSharedDesc), c_void_p]),
     "mpv_temporal_attn_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int64, c_int64, c_int, c_int, c_int,
                                       c_float, c_void_p]),
     "mpv_temporal_attn_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int64, c_int64, c_int,
@@ -201,6 +216,9 @@ _SIGS.update({
     "mpv_gpt_decode_step": (c_int, [C.POINTER(GptWeights), C.POINTER(c_void_p), c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
                                     c_void_p, c_size_t, c_void_p, c_void_p]),
     "mpv_kv_reorder": (c_int, [C.POINTER(c_void_p), C.POINTER(c_void_p), c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "mpv_gpt_decode_shared_workspace_size": (c_size_t, [C.POINTER(GptWeights), c_int]),
+    "mpv_gpt_decode_step_shared": (c_int, [C.POINTER(GptWeights), C.POINTER(c_void_p), C.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int,
+                                           c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
 })
 
 EXPORTS = tuple(_SIGS)

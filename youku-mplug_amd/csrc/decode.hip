@@ -20,6 +20,35 @@ extern "C" size_t mpv_gpt_decode_workspace_size(const mpv_gpt_weights* w, int ba
          mpv_gemm_workspace_size(R, w->ffn, w->hidden, 0, 0);
 }
 
+// what follows the attention in a layer: dense + residual, LN2, fc1 + GELU, fc2 + residual (the layer output lands in h)
+static int layer_tail(const mpv_gpt_weights* w, const mpv_gpt_layer_weights* lw, int64_t R, void* h, void* x, void* ctx, void* h1,
+                      void* g, void* gws, size_t gws_bytes, hipStream_t stream) {
+  const int H = w->hidden, F4 = w->ffn;
+  mpv_gemm_epilogue e1 = {};
+  e1.bias = lw->dense_b; e1.residual = h; e1.ldr = H;
+  int rc = mpv_gemm_bf16(ctx, lw->dense_w, h1, R, H, H, H, H, H, 0, 0, &e1, gws, gws_bytes, stream);
+  if (rc) return rc;
+  rc = mpv_layernorm_fwd(h1, lw->ln2_w, lw->ln2_b, x, nullptr, nullptr, R, H, H, H, w->ln_eps, 0, 0, 0, 0, 0, 0, stream);
+  if (rc) return rc;
+  mpv_gemm_epilogue e2 = {};
+  e2.bias = lw->fc1_b; e2.act = MPV_ACT_GELU_TANH;
+  rc = mpv_gemm_bf16(x, lw->fc1_w, g, R, F4, H, H, H, F4, 0, 0, &e2, gws, gws_bytes, stream);
+  if (rc) return rc;
+  mpv_gemm_epilogue e3 = {};
+  e3.bias = lw->fc2_b; e3.residual = h1; e3.ldr = H;
+  // the layer input `h` was last read by the dense GEMM (as its residual): its buffer takes the layer output
+  return mpv_gemm_bf16(g, lw->fc2_w, h, R, H, F4, F4, F4, H, 0, 0, &e3, gws, gws_bytes, stream);
+}
+
+// final LN + tied LM head on one row per sequence
+static int lm_head(const mpv_gpt_weights* w, const void* lastrow, void* xf, int batch, void* logits, void* gws, size_t gws_bytes,
+                   hipStream_t stream) {
+  const int H = w->hidden;
+  const int rc = mpv_layernorm_fwd(lastrow, w->lnf_w, w->lnf_b, xf, nullptr, nullptr, batch, H, H, H, w->ln_eps, 0, 0, 0, 0, 0, 0, stream);
+  if (rc) return rc;
+  return mpv_gemm_bf16(xf, w->wte, logits, batch, w->vocab, H, H, H, w->vocab, 0, 0, nullptr, gws, gws_bytes, stream);
+}
+
 extern "C" int mpv_gpt_decode_step(const mpv_gpt_weights* w, void* const* kv_cache, int batch, int max_len, int pos0,
                                    const void* query, int Q, const int64_t* tokens, int L, void* workspace,
                                    size_t workspace_bytes, void* logits, hipStream_t stream) {
@@ -67,20 +96,7 @@ extern "C" int mpv_gpt_decode_step(const mpv_gpt_weights* w, void* const* kv_cac
     d.scale = 1.0f / sqrtf((float)hn);
     rc = mpv_attn_fwd(&d, stream);
     if (rc) return rc;
-    mpv_gemm_epilogue e1 = {};
-    e1.bias = lw->dense_b; e1.residual = h; e1.ldr = H;
-    rc = mpv_gemm_bf16(ctx, lw->dense_w, h1, R, H, H, H, H, H, 0, 0, &e1, gws, gws_bytes, stream);
-    if (rc) return rc;
-    rc = mpv_layernorm_fwd(h1, lw->ln2_w, lw->ln2_b, x, nullptr, nullptr, R, H, H, H, w->ln_eps, 0, 0, 0, 0, 0, 0, stream);
-    if (rc) return rc;
-    mpv_gemm_epilogue e2 = {};
-    e2.bias = lw->fc1_b; e2.act = MPV_ACT_GELU_TANH;
-    rc = mpv_gemm_bf16(x, lw->fc1_w, g, R, F4, H, H, H, F4, 0, 0, &e2, gws, gws_bytes, stream);
-    if (rc) return rc;
-    mpv_gemm_epilogue e3 = {};
-    e3.bias = lw->fc2_b; e3.residual = h1; e3.ldr = H;
-    // the layer input `h` was last read by the dense GEMM (as its residual): its buffer takes the layer output
-    rc = mpv_gemm_bf16(g, lw->fc2_w, h, R, H, F4, F4, F4, H, 0, 0, &e3, gws, gws_bytes, stream);
+    rc = layer_tail(w, lw, R, h, x, ctx, h1, g, gws, gws_bytes, stream);
     if (rc) return rc;
   }
   const void* lastrow = h;
@@ -89,9 +105,73 @@ extern "C" int mpv_gpt_decode_step(const mpv_gpt_weights* w, void* const* kv_cac
     if (rc) return rc;
     lastrow = last;
   }
-  rc = mpv_layernorm_fwd(lastrow, w->lnf_w, w->lnf_b, xf, nullptr, nullptr, batch, H, H, H, w->ln_eps, 0, 0, 0, 0, 0, 0, stream);
+  return lm_head(w, lastrow, xf, batch, logits, gws, gws_bytes, stream);
+}
+
+// mpv_gpt_decode_step for one token per sequence against a per-group shared prefix cache (include/mpv.h states the contract)
+extern "C" size_t mpv_gpt_decode_shared_workspace_size(const mpv_gpt_weights* w, int n_seq) {
+  return mpv_gpt_decode_workspace_size(w, n_seq, 1);
+}
+
+extern "C" int mpv_gpt_decode_step_shared(const mpv_gpt_weights* w, void* const* prefix_cache, void* const* suffix_cache, int n_groups,
+                                          int fan, int prefix_len, int suffix_max, int t, const int64_t* tokens, void* workspace,
+                                          size_t workspace_bytes, void* logits, hipStream_t stream) {
+  MPV_REQUIRE(w && prefix_cache && suffix_cache && tokens && workspace && logits, MPV_E_ARG, "mpv_gpt_decode_step_shared: null pointer");
+  MPV_REQUIRE(n_groups > 0 && fan > 0 && (int64_t)n_groups * fan < (1ll << 31) && prefix_len > 0, MPV_E_SHAPE,
+              "mpv_gpt_decode_step_shared: empty problem (n_groups %d, fan %d, prefix_len %d)", n_groups, fan, prefix_len);
+  MPV_REQUIRE(t >= 0 && t < suffix_max && t < 2048, MPV_E_SHAPE,
+              "mpv_gpt_decode_step_shared: suffix position %d does not fit suffix_max %d (and the attention's 2048 own rows)", t, suffix_max);
+  MPV_REQUIRE(w->max_positions <= 0 || prefix_len + t < w->max_positions, MPV_E_SHAPE,
+              "mpv_gpt_decode_step_shared: position %d runs past the %d rows of the position embedding", prefix_len + t, w->max_positions);
+  const int n_seq = n_groups * fan, H = w->hidden, np = w->heads, hn = H / np, F4 = w->ffn;
+  MPV_REQUIRE(workspace_bytes >= mpv_gpt_decode_shared_workspace_size(w, n_seq), MPV_E_ARG,
+              "mpv_gpt_decode_step_shared: workspace too small");
+  const int64_t R = n_seq;
+  char* p = (char*)workspace;
+  void* h = carve(p, R * H * 2);
+  void* x = carve(p, R * H * 2);
+  void* ctx = carve(p, R * H * 2);
+  void* h1 = carve(p, R * H * 2);
+  void* g = carve(p, R * F4 * 2);
+  carve(p, (size_t)n_seq * H * 2);                       // (the `last` rows of the general step: one position needs no copy)
+  void* xf = carve(p, (size_t)n_seq * H * 2);
+  void* gws = p;
+  const size_t gws_bytes = workspace_bytes - (size_t)(p - (char*)workspace);
+  int rc = mpv_gpt_embed_fwd(nullptr, tokens, w->wte, (const char*)w->wpe + (size_t)(prefix_len + t) * H * 2, h, n_seq, 0, 1, H, 0.f, 0, 0,
+                             stream);
   if (rc) return rc;
-  return mpv_gemm_bf16(xf, w->wte, logits, batch, w->vocab, H, H, H, w->vocab, 0, 0, nullptr, gws, gws_bytes, stream);
+  for (int li = 0; li < w->layers; ++li) {
+    const mpv_gpt_layer_weights* lw = &w->layer[li];
+    char* pc = (char*)prefix_cache[li];
+    char* sc = (char*)suffix_cache[li];
+    rc = mpv_layernorm_fwd(h, lw->ln1_w, lw->ln1_b, x, nullptr, nullptr, R, H, H, H, w->ln_eps, 0, 0, 0, 0, 0, 0, stream);
+    if (rc) return rc;
+    mpv_gemm_epilogue ep = {};
+    ep.bias = lw->qkv_b;
+    ep.c_group = 1; ep.c_stride = suffix_max; ep.c_offset = t;                // row s lands at suffix row s*suffix_max + t
+    rc = mpv_gemm_bf16(x, lw->qkv_w, sc, R, 3 * H, H, H, H, 3 * H, 0, 0, &ep, gws, gws_bytes, stream);
+    if (rc) return rc;
+    mpv_attn_decode_shared_desc d = {};
+    d.q = sc + (size_t)t * 3 * H * 2;
+    d.k = sc + (size_t)hn * 2;
+    d.v = sc + (size_t)2 * hn * 2;
+    d.pk = pc + (size_t)hn * 2;
+    d.pv = pc + (size_t)2 * hn * 2;
+    d.o = ctx;
+    d.q_ss = d.k_ss = d.v_ss = (int64_t)suffix_max * 3 * H;
+    d.pk_gs = d.pv_gs = (int64_t)prefix_len * 3 * H;
+    d.q_hs = d.k_hs = d.v_hs = d.pk_hs = d.pv_hs = 3 * hn;
+    d.k_rs = d.v_rs = d.pk_rs = d.pv_rs = 3 * H;
+    d.o_ss = H; d.o_hs = hn;
+    d.n_seq = n_seq; d.group_size = fan; d.n_groups = n_groups; d.heads = np;
+    d.prefix_len = prefix_len; d.own_len = t + 1; d.head_dim = hn;
+    d.scale = 1.0f / sqrtf((float)hn);
+    rc = mpv_attn_decode_shared_fwd(&d, stream);
+    if (rc) return rc;
+    rc = layer_tail(w, lw, R, h, x, ctx, h1, g, gws, gws_bytes, stream);
+    if (rc) return rc;
+  }
+  return lm_head(w, h, xf, n_seq, logits, gws, gws_bytes, stream);
 }
 
 // InferenceParams.swap_key_value_dict (:1459-1473) for every layer: dst[l][j] = src[l][idx[j]], first `rows` positions

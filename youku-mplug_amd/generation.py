@@ -10,7 +10,9 @@ every sequence (prefill: the visual prefix + prompt; afterwards one token), atte
 runs the LM head on the last position only.  Beam re-ordering (swap_key_value_dict) is one strided row gather per
 layer into the twin buffer.  The search logic of the per-clip loops stays on the host, as in the reference; the lockstep
 search over a batch of clips (beam_search_batched_loop) keeps it on the device (ops.beam_advance, csrc/beam_search.hip), and so does
-sampled generation in lockstep (sample_batched_loop: ops.sample_advance, csrc/sampling.hip).
+sampled generation in lockstep (sample_batched_loop: ops.sample_advance, csrc/sampling.hip).  The lockstep loops can also keep
+the positions all sequences of a clip share (visual prefix + prompt) once per clip: SharedPrefixDecodeState (kv="shared_prefix";
+mpv_gpt_decode_step_shared, csrc/decode_shared_attention.hip).
 """
 from __future__ import annotations
 
@@ -164,6 +166,112 @@ class DecodeState:
         self._twin_shared = shared_prefix            # after a gather from 0 the twin holds them too; the source did already
         self.cache, self.twin = self.twin, self.cache
         self._cache_ptrs, self._twin_ptrs = self._twin_ptrs, self._cache_ptrs
+
+    def kv_bytes(self) -> int:
+        """bytes of the cache and twin allocations"""
+        return sum(t.numel() * t.element_size() for t in (self.cache, self.twin) if t is not None)
+
+
+class SharedPrefixDecodeState:
+    """DecodeState for the lockstep loops with the prefix every sequence of a clip shares stored ONCE per clip: a prefix cache
+    [nl, G * P, 3H] (P = Q + prompt positions; it is the cache of a DecodeState of batch G and max_len P, filled by the ordinary
+    prefill) and a suffix cache [nl, batch * S, 3H] (S = max_len - P) for the positions the sequences generate.  A step is ONE
+    call into the C ABI (mpv_gpt_decode_step_shared): its attention reads a clip's prefix once per head for all of the clip's
+    sequences (mpv_attn_decode_shared_fwd).  A re-order gathers suffix rows only; the prefix is never copied or moved.
+    Resident KV: nl * (G * P + (1 or 2) * batch * S) * 3H * 2 bytes (the twin exists once a re-order has moved rows) against
+    nl * 2 * batch * (P + S) * 3H * 2 of DecodeState."""
+
+    def __init__(self, gpt, batch: int, max_len: int):
+        self.gpt, self.batch, self.max_len = gpt, batch, max_len
+        self.prefix = None                    # the DecodeState of the prefill: its cache is the prefix cache
+        self.suffix = self.twin = None
+        self.fan = self.P = self.S = 0
+        self.t = 0                            # suffix rows cached so far (per sequence)
+
+    @property
+    def pos(self) -> int:
+        return self.P + self.t
+
+    def prefill_fan_out(self, tokens: Optional[torch.Tensor], query_embeds: Optional[torch.Tensor], fan: int) -> torch.Tensor:
+        """tokens [G, n_tok] / query_embeds [G, Q, H], G = batch // fan: the prefill runs once per clip into the prefix cache and
+        nothing is copied.  -> logits [batch, V]: row j is clip j // fan's."""
+        assert self.prefix is None and fan >= 1 and self.batch % fan == 0, (self.batch, fan)
+        G = self.batch // fan
+        assert (tokens is None or tokens.shape[0] == G) and (query_embeds is None or query_embeds.shape[0] == G)
+        P = (0 if query_embeds is None else query_embeds.shape[1]) + (0 if tokens is None else tokens.shape[1])
+        if not 0 < P < self.max_len:
+            raise ValueError(f"a shared prefix of {P} positions leaves no room in max_len {self.max_len}")
+        self.prefix = DecodeState(self.gpt, G, P)
+        logits = self.prefix.step(tokens, query_embeds)
+        self.fan, self.P, self.S = fan, P, self.max_len - P
+        st = self.prefix
+        self.nl, self.H = st.nl, st.H
+        self.suffix = torch.zeros((st.nl, self.batch * self.S, 3 * st.H), dtype=torch.bfloat16, device=st.cache.device)
+        self._suffix_ptrs = st._ptrs(self.suffix)
+        return logits.repeat_interleave(fan, dim=0)
+
+    def step(self, tokens: torch.Tensor, query_embeds: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """tokens [batch, 1] int64 -> the logits of the new position: [batch, V] bf16"""
+        if self.prefix is None:
+            raise ValueError("SharedPrefixDecodeState.step: prefill_fan_out comes first")
+        if query_embeds is not None or tokens is None or tokens.dim() != 2 or tokens.shape[1] != 1:
+            raise ValueError("SharedPrefixDecodeState.step takes ONE token per sequence and no query_embeds after the prefill")
+        if tokens.shape[0] != self.batch:
+            raise ValueError(f"SharedPrefixDecodeState.step: {tokens.shape[0]} rows for {self.batch} sequences")
+        if self.t >= self.S:
+            raise ValueError(f"SharedPrefixDecodeState.step: the suffix cache of {self.S} positions is full")
+        logits = self._shared_step(tokens.contiguous())
+        self.t += 1
+        return logits
+
+    def _shared_step(self, tokens: torch.Tensor) -> torch.Tensor:
+        import ctypes as C
+        from . import _lib
+        st, dev = self.prefix, self.suffix.device
+        wsn = _lib.lib().mpv_gpt_decode_shared_workspace_size(C.byref(st._w), self.batch)
+        ws = ops.workspace(wsn, dev)
+        logits = torch.empty((self.batch, st.V), dtype=torch.bfloat16, device=dev)
+        ops.check(_lib.lib().mpv_gpt_decode_step_shared(C.byref(st._w), st._cache_ptrs, self._suffix_ptrs, self.batch // self.fan, self.fan,
+                                                        self.P, self.S, self.t, tokens.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                        logits.data_ptr(), ops._stream()), "mpv_gpt_decode_step_shared")
+        return logits
+
+    def reorder(self, batch_idx: torch.Tensor, shared_prefix: Optional[int] = None):
+        """sequence j continues from the suffix rows of sequence batch_idx[j] (which must belong to the same clip): one strided
+        row gather of the t cached suffix rows over (layer, sequence) into the twin.  `shared_prefix` (default: the prefilled
+        length) must cover the prefilled positions -- they are shared by construction."""
+        if self.prefix is None:
+            raise ValueError("SharedPrefixDecodeState.reorder: prefill_fan_out comes first")
+        if shared_prefix is not None and int(shared_prefix) < self.P:
+            raise ValueError(f"shared_prefix {int(shared_prefix)} is smaller than the {self.P} prefilled positions, which are stored once per clip")
+        if self.t == 0:
+            return                                   # nothing generated yet: nothing to move
+        if self.twin is None:
+            self.twin = torch.empty_like(self.suffix)
+            self._twin_ptrs = self.prefix._ptrs(self.twin)
+            self._layer_base = torch.arange(self.nl, device=self.suffix.device, dtype=torch.int64)[:, None] * self.batch
+        idx = (self._layer_base + batch_idx.to(torch.int64)[None]).reshape(-1)
+        pitch = self.S * 3 * self.H
+        ops.gather_rows_ld(self.suffix.view(-1), idx, self.twin.view(-1), self.nl * self.batch, self.t * 3 * self.H, pitch, pitch)
+        self.suffix, self.twin = self.twin, self.suffix
+        self._suffix_ptrs, self._twin_ptrs = self._twin_ptrs, self._suffix_ptrs
+
+    def kv_bytes(self) -> int:
+        """bytes of the prefix, suffix and twin allocations"""
+        return sum(t.numel() * t.element_size() for t in (None if self.prefix is None else self.prefix.cache, self.suffix, self.twin)
+                   if t is not None)
+
+
+KV_MODES = ("per_sequence", "shared_prefix")
+
+
+def make_state_fn(gpt, kv: str = "per_sequence"):
+    """The make_state of the loops for the keyword `kv`: "per_sequence" (DecodeState: every sequence owns a full cache) or
+    "shared_prefix" (SharedPrefixDecodeState; the lockstep loops only)."""
+    if kv not in KV_MODES:
+        raise ValueError(f"kv must be one of {KV_MODES} (got {kv!r})")
+    cls = DecodeState if kv == "per_sequence" else SharedPrefixDecodeState
+    return lambda batch, max_len: cls(gpt, batch, max_len)
 
 
 # ---------------------------------------------------------------------------------------------- sampling helpers
@@ -480,38 +588,44 @@ def install(gpt_cls):
     """Adds sample / beam_search / generate to DistributedGPT3 (same signatures as the reference methods), and beam_search_batched /
     sample_batched."""
 
-    def _make_state(self):
-        return lambda batch, max_len: DecodeState(self, batch, max_len)
-
     def sample(self, tokens, query_embeds=None, temperature=1.0, **kw):
-        return sample_loop(_gen_config(self), _make_state(self), tokens, query_embeds=query_embeds, temperature=temperature, **kw)
+        return sample_loop(_gen_config(self), make_state_fn(self), tokens, query_embeds=query_embeds, temperature=temperature, **kw)
 
     def beam_search(self, tokens, query_embeds=None, beam_size=5, num_return_gen=1, stop_token=None, **kw):
-        return beam_search_loop(_gen_config(self), _make_state(self), tokens, query_embeds=query_embeds, beam_size=beam_size,
+        return beam_search_loop(_gen_config(self), make_state_fn(self), tokens, query_embeds=query_embeds, beam_size=beam_size,
                                 num_return_gen=num_return_gen, stop_token=stop_token, prompt_length=kw.pop("prompt_length", None),
                                 topk_fn=lambda lg, k, add: ops.logprob_topk(lg, k, add=add))
 
-    def beam_search_batched(self, tokens, query_embeds=None, beam_size=5, num_return_gen=1, stop_token=None, **kw):
-        """beam_search for tokens [B, L] / query_embeds [B, Q, H] with one prompt length, B clips in lockstep -> a list of B results"""
-        return beam_search_batched_loop(_gen_config(self), _make_state(self), tokens, query_embeds=query_embeds, beam_size=beam_size,
+    def beam_search_batched(self, tokens, query_embeds=None, beam_size=5, num_return_gen=1, stop_token=None, kv="per_sequence", **kw):
+        """beam_search for tokens [B, L] / query_embeds [B, Q, H] with one prompt length, B clips in lockstep -> a list of B results;
+        kv="shared_prefix" keeps the visual prefix and the prompt once per clip (SharedPrefixDecodeState)"""
+        return beam_search_batched_loop(_gen_config(self), make_state_fn(self, kv), tokens, query_embeds=query_embeds, beam_size=beam_size,
                                         num_return_gen=num_return_gen, stop_token=stop_token, prompt_length=kw.pop("prompt_length", None),
                                         topk_fn=lambda lg, k, add: ops.logprob_topk(lg, k, add=add), advance_fn=ops.beam_advance)
 
-    def sample_batched(self, tokens, query_embeds=None, temperature=1.0, num_samples=1, seed=0, streams=None, top_k=None, top_p=None, **kw):
+    def sample_batched(self, tokens, query_embeds=None, temperature=1.0, num_samples=1, seed=0, streams=None, top_k=None, top_p=None,
+                       kv="per_sequence", **kw):
         """sample with the sampler on the device (sample_batched_loop): tokens [B, L] -> [B * num_samples, n]; top_k / top_p override
-        the configuration's values; the draws are those of (seed, position, streams[row]) -- not torch's generator"""
+        the configuration's values; the draws are those of (seed, position, streams[row]) -- not torch's generator;
+        kv="shared_prefix" keeps the visual prefix and the shortest prompt once per clip (SharedPrefixDecodeState)"""
+        make_state = make_state_fn(self, kv)
         cfg = _gen_config(self)
         if top_k is not None or top_p is not None:
             cfg.top_k, cfg.top_p = int(top_k or 0), float(top_p or 0.0)
-        return sample_batched_loop(cfg, _make_state(self), tokens, query_embeds=query_embeds, temperature=temperature, num_samples=num_samples,
+        return sample_batched_loop(cfg, make_state, tokens, query_embeds=query_embeds, temperature=temperature, num_samples=num_samples,
                                    seed=seed, streams=streams, advance_fn=ops.sample_advance, **kw)
 
     @torch.no_grad()
     def generate(self, tokens, do_sample=True, termination_id=None, *args, **kw):                # :1875-1880
-        """sampler="device" (keyword; not in the reference, default "torch"): do_sample=True runs sample_batched"""
+        """sampler="device" (keyword; not in the reference, default "torch"): do_sample=True runs sample_batched, which takes
+        kv="per_sequence" | "shared_prefix" (the per-clip loops keep a cache per sequence)"""
         sampler = kw.pop("sampler", "torch")
         if sampler not in ("torch", "device"):
             raise ValueError(f"sampler must be 'torch' or 'device' (got {sampler!r})")
+        if kw.get("kv", "per_sequence") not in KV_MODES:
+            raise ValueError(f"kv must be one of {KV_MODES} (got {kw['kv']!r})")
+        if not (do_sample and sampler == "device") and kw.pop("kv", "per_sequence") != "per_sequence":
+            raise ValueError('kv="shared_prefix" needs a lockstep loop: do_sample=True with sampler="device", or beam_search_batched')
         was = self.training
         self.eval()
         try:

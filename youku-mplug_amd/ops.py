@@ -302,7 +302,27 @@ def attn_prefix_fwd(q, k, v, pk, pv, o, lay: AttnLayout, prefix_lay: Tuple[Tuple
     return o
 
 
-TEMPORAL_SHORT_MAX_T = 16      # mpv_temporal_attn_fwd / _bwd: the VALU kernels
+def attn_decode_shared_fwd(q, k, v, pk, pv, o, lay: AttnLayout, prefix_lay: Tuple[Tuple[int, int, int], Tuple[int, int, int]], n_seq,
+                           group_size, heads, prefix_len, own_len, hd, *, scale=1.0):
+    """One decode step's attention of n_seq sequences (ONE query row each; q/k/v/o strided (sequence, head, row) by `lay`, the row
+    stride of q and o is not used) against the prefix_len-row prefix of their group s // group_size (pk/pv strided (group, head,
+    row) by prefix_lay = (k strides, v strides)) and their own own_len rows of k/v: one softmax over both key sets.
+    include/mpv.h: mpv_attn_decode_shared_fwd."""
+    _need_cuda(q, k, v, o, pk, pv)
+    d = _lib.AttnDecodeSharedDesc()
+    d.q, d.k, d.v, d.o, d.pk, d.pv = q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), pk.data_ptr(), pv.data_ptr()
+    d.q_ss, d.q_hs = lay.q[:2]
+    d.k_ss, d.k_hs, d.k_rs = lay.k
+    d.v_ss, d.v_hs, d.v_rs = lay.v
+    d.o_ss, d.o_hs = lay.o[:2]
+    (d.pk_gs, d.pk_hs, d.pk_rs), (d.pv_gs, d.pv_hs, d.pv_rs) = prefix_lay
+    d.n_seq, d.group_size, d.n_groups = n_seq, group_size, (n_seq + group_size - 1) // max(group_size, 1)
+    d.heads, d.prefix_len, d.own_len, d.head_dim, d.scale = heads, prefix_len, own_len, hd, scale
+    check(_lib.lib().mpv_attn_decode_shared_fwd(C.byref(d), _stream()), "mpv_attn_decode_shared_fwd")
+    return o
+
+
+TEMPORAL_SHORT_MAX_T = 16     # mpv_temporal_attn_fwd / _bwd: the VALU kernels
 TEMPORAL_MAX_T = 64            # mpv_temporal_attn_long_fwd / _bwd: the matrix-core kernels (one or four 32 x 32 score tiles)
 
 
