@@ -14,6 +14,10 @@ What this entry point adds to downstream/finetune_common.py:
     "sampled_captions" in the result file (`model.generate(..., do_sample=True, num_samples=N)`: the sampler on the device);
   * `--eval_shared_kv` (not in the reference, default off): `--eval_batched_beam` and `--eval_sample` cache the query slots and the
     prompt once per clip instead of once per beam or sample (`model.generate(..., kv_cache="shared_prefix")`); same result files;
+  * `--eval_repetition_penalty F`, `--eval_no_repeat_ngram N`, `--eval_min_new_tokens N` (not in the reference, defaults off): the
+    `--eval_batched_beam` and `--eval_sample` calls penalise repeated tokens, never repeat an n-gram of N tokens and do not end a
+    caption before N tokens, on the device (`model.generate(..., repetition_penalty=F, no_repeat_ngram_size=N, min_new_tokens=N)`);
+    without one of those two flags they are an error;
   * save_result (dataset/utils.py:114-160): one JSON per rank, merged by rank 0; cal_metric (:240-298): predictions and references
     reduced to their CJK characters, one token per character, scored by pycocoevalcap's COCOEvalCap when that package is importable.
     It is not on this image: then BLEU-1..4 (corpus level, closest-reference brevity penalty) and ROUGE-L (beta 1.2, best reference)
@@ -42,12 +46,15 @@ def make_training_batch(video, text, prompt, tokenizer, device, max_length):
 
 
 @torch.no_grad()
-def evaluation(model, data_loader, tokenizer, device, config, batched=False, clips_per_search=32, eval_sample=0, seed=0, shared_kv=False):
+def evaluation(model, data_loader, tokenizer, device, config, batched=False, clips_per_search=32, eval_sample=0, seed=0, shared_kv=False,
+               constraints=None):
     """-> [{video_id, pred_caption, gold_caption}] (:208-238); batched: `--eval_batched_beam`; eval_sample: `--eval_sample`;
-    shared_kv: `--eval_shared_kv` (the lockstep calls only)"""
+    shared_kv: `--eval_shared_kv`, constraints: the keywords of `--eval_repetition_penalty` / `--eval_no_repeat_ngram` /
+    `--eval_min_new_tokens` (the lockstep calls only)"""
     module = getattr(model, "module", model)
     module.eval()
     kvkw = {"kv_cache": "shared_prefix"} if shared_kv else {}                # flag absent: the calls below are unchanged
+    kvkw.update(constraints or {})
     result = []
     for n, (video, video_ids, gold_caption) in enumerate(data_loader):
         video = video.to(device, non_blocking=True).bfloat16()
@@ -212,13 +219,29 @@ def main(args, config):
     if args.evaluate_only:
         result = evaluation(s.model, val_loader, s.tokenizer, s.device, config, batched=getattr(args, "eval_batched_beam", False),
                             clips_per_search=getattr(args, "clips_per_search", 32), eval_sample=getattr(args, "eval_sample", 0),
-                            seed=getattr(args, "seed", 0) or 0, shared_kv=getattr(args, "eval_shared_kv", False))
+                            seed=getattr(args, "seed", 0) or 0, shared_kv=getattr(args, "eval_shared_kv", False),
+                            constraints=constraint_keywords(args))
         val_stats = cal_metric(save_result(result, args.result_dir, "val_caption_result"))
         print("* Validation Stats:", val_stats)
         log_stats = {**{f"val_{k}": v for k, v in val_stats.items()}, "n_parameters": s.n_parameters}
         ft.write_log(args, log_stats)
         return log_stats
     return ft.epoch_loop(args, s, step_fn, lambda epoch: {})
+
+
+def constraint_keywords(args):
+    """the model.generate keywords of --eval_repetition_penalty / --eval_no_repeat_ngram / --eval_min_new_tokens; {} when all are off"""
+    kw = {}
+    if getattr(args, "eval_repetition_penalty", None) is not None:
+        kw["repetition_penalty"] = args.eval_repetition_penalty
+    if getattr(args, "eval_no_repeat_ngram", 0):
+        kw["no_repeat_ngram_size"] = args.eval_no_repeat_ngram
+    if getattr(args, "eval_min_new_tokens", 0):
+        kw["min_new_tokens"] = args.eval_min_new_tokens
+    if kw and not (getattr(args, "eval_batched_beam", False) or getattr(args, "eval_sample", 0)):
+        raise ValueError(f"--eval_repetition_penalty / --eval_no_repeat_ngram / --eval_min_new_tokens ({kw}) need --eval_batched_beam or "
+                         "--eval_sample: the per-clip beam search has no constraints")
+    return kw
 
 
 def get_args(argv=None):
@@ -233,7 +256,14 @@ def get_args(argv=None):
         p.add_argument("--eval_shared_kv", action="store_true", default=False,
                        help="--eval_batched_beam / --eval_sample: cache the query slots and the prompt once per clip "
                             "(model.generate(kv_cache='shared_prefix')) instead of once per beam or sample")
+        p.add_argument("--eval_repetition_penalty", type=float, default=None,
+                       help="--eval_batched_beam / --eval_sample: CTRL repetition penalty on the tokens generated so far (model.generate(repetition_penalty=F))")
+        p.add_argument("--eval_no_repeat_ngram", type=int, default=0,
+                       help="--eval_batched_beam / --eval_sample: no n-gram of N tokens is generated twice (model.generate(no_repeat_ngram_size=N))")
+        p.add_argument("--eval_min_new_tokens", type=int, default=0,
+                       help="--eval_batched_beam / --eval_sample: no termination token before N generated tokens (model.generate(min_new_tokens=N))")
     args, config = ft.get_args(argv, extra=extra)
+    constraint_keywords(args)                                               # refuses the flags without a lockstep mode
     config.setdefault("prompt", "")
     args.result_dir = os.path.join(args.output_dir, "result")
     os.makedirs(args.result_dir, exist_ok=True)

@@ -533,6 +533,52 @@ typedef struct mpv_sample_advance_desc {
 } mpv_sample_advance_desc;
 int mpv_sample_advance(const mpv_sample_advance_desc* d, mpv_stream_t stream);
 /* ------------------------------------------------------------------------------------------
+ * Generation constraints in lockstep (generation.LogitsConstraints): ONE launch edits one step's logits in place, before
+ * mpv_sample_advance or mpv_logprob_topk reads them, from the loop's own device token table -- the CTRL repetition penalty, the
+ * no-repeat n-gram ban, the minimum length and a list of banned ids.  They act on the RAW logits (before temperature, filter and
+ * log_softmax).
+ * Input: logits bf16 [rows][ld], 16-byte aligned, the first `vocab` columns are the row; tokens int64 [rows][row_len] (the token
+ *   table of mpv_sample_advance, or the one of mpv_beam_advance seen as [batch*K][row_len]); prompt_len int64 [rows], or NULL: then
+ *   every row has the prompt length prompt_len_all; eos_ids int64 [n_eos], n_eos in [0, 8]; banned_ids int64 [n_banned], n_banned
+ *   in [0, 1024] (both device arrays); pos, the token column this step fills; penalty > 0 (1 = off); ngram 0 (off) or 1 .. 8;
+ *   min_new_tokens >= 0; include_prompt 0 / 1; ban_value, -inf or finite and negative, stored rounded to bf16.
+ * Row r: with prompt_len[r] > pos the row is teacher-forced and is left untouched, bit for bit.  Otherwise the history is
+ *   h = tokens[r][start : pos], start = include_prompt ? 0 : prompt_len[r], of length m, and g = pos - prompt_len[r] tokens have
+ *   been generated.  History tokens outside [0, vocab) are ignored everywhere (they never form an address), except that they take
+ *   part in the n-gram comparison like any other value.
+ * 1. Repetition penalty (penalty != 1): every DISTINCT in-range token v of h is penalised once, however often it occurs:
+ *   x = float(logits[v]) becomes bf16_rne(x < 0 ? x * penalty : x / penalty), one fp32 multiply or IEEE-correct divide.
+ * 2. No-repeat n-gram: ngram == 1 bans every token of h.  ngram = n >= 2, when m >= n: with s = h[m-n+1 : m], for every i in
+ *   [0, m-n] with h[i : i+n-1] == s the token h[i+n-1] is banned, if it is in range.
+ * 3. Minimum length: while g < min_new_tokens every in-range id of eos_ids is banned.
+ * 4. Every in-range id of banned_ids is banned, always.
+ * A banned logit becomes ban_value; the ban wins over the penalty.  No other logit is read or written: not the columns >= vocab,
+ *   not the bf16 next to an edited one (2-byte stores).  A row's result depends on its own logits, its history and the scalars only
+ *   -- neither on `rows` nor on the row's place in the launch -- and every edited logit has one writer rule: the result does not
+ *   depend on thread timing.  If every logit of a row ends up banned, the readers' own rules apply (mpv_sample_advance: token 0).
+ * ban_value: mpv_sample_advance defines -inf as probability 0, never kept: the value for sampling.  mpv_logprob_topk takes
+ *   exp(v - max) per vocabulary slice, and a slice that is -inf throughout is exp(NaN): beam search passes the lowest finite bf16
+ *   (-0x1.fep127) instead, which goes through both of its kernels as an exact zero probability.
+ * Refused with a negative code before any launch, logits untouched: a NULL logits / tokens; vocab not a multiple of 8 or outside
+ *   [8, 65536]; ld < vocab or ld % 8 != 0; logits not 16-byte aligned; rows < 1; row_len outside [1, 2048]; pos outside [0, row_len);
+ *   penalty <= 0 or not finite; ngram outside [0, 8]; min_new_tokens < 0; include_prompt other than 0 / 1; n_eos or n_banned outside
+ *   its range, or positive with a NULL array; a ban_value that is NaN, +inf or >= 0.  A descriptor with everything off (penalty 1,
+ *   ngram 0, no banned id, min_new_tokens 0 or no eos id) launches nothing and returns 0.
+ * One workgroup per row, the history in LDS; the work follows the history (O(m n) + the O(m^2) first-occurrence test + distinct
+ *   tokens x listed ids), never the vocabulary.  No atomics, no floating-point reductions. */
+typedef struct mpv_logits_constrain_desc {
+  void* logits;
+  const int64_t* tokens;
+  const int64_t* prompt_len;
+  const int64_t* eos_ids;
+  const int64_t* banned_ids;
+  int64_t ld;
+  int64_t prompt_len_all;
+  int rows, vocab, row_len, pos, n_eos, n_banned, ngram, min_new_tokens, include_prompt;
+  float penalty, ban_value;
+} mpv_logits_constrain_desc;
+int mpv_logits_constrain(const mpv_logits_constrain_desc* d, mpv_stream_t stream);
+/* ------------------------------------------------------------------------------------------
  * Device-side video input transform (configs' video_pretrain/train/test transforms,
  * dataset/__init__.py:60-85): the decoder's uint8 clip [T][H][W][3] -> crop (i, j, h, w) ->
  * torch.nn.functional.interpolate to out_h x out_w (mode 0 nearest / 1 bilinear / 2 bicubic, align_corners=False:

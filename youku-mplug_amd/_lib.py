@@ -103,6 +103,13 @@ class SampleAdvanceDesc(C.Structure):
                [("temperature", c_float), ("top_p", c_float)]
 
 
+class LogitsConstrainDesc(C.Structure):
+    _fields_ = [(n, c_void_p) for n in ("logits", "tokens", "prompt_len", "eos_ids", "banned_ids")] + \
+               [("ld", c_int64), ("prompt_len_all", c_int64)] + \
+               [(n, c_int) for n in ("rows", "vocab", "row_len", "pos", "n_eos", "n_banned", "ngram", "min_new_tokens", "include_prompt")] + \
+               [("penalty", c_float), ("ban_value", c_float)]
+
+
 _RM = [c_int, c_int, c_int]
 _SIGS = {
     "mpv_version": (c_int, []),
@@ -179,6 +186,7 @@ _SIGS = {
     "mpv_logprob_topk": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mpv_beam_advance": (c_int, [C.POINTER(BeamAdvanceDesc), c_void_p]),
     "mpv_sample_advance": (c_int, [C.POINTER(SampleAdvanceDesc), c_void_p]),
+    "mpv_logits_constrain": (c_int, [C.POINTER(LogitsConstrainDesc), c_void_p]),
     "mpv_soft_target_ce": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     "mpv_maxsim_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p]),
     "mpv_maxsim_route": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p]),

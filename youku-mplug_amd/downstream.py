@@ -331,7 +331,8 @@ class DistributedGPT3_Caption(_GenCls):
 
     @torch.no_grad()
     def generate(self, image, text, termination_id=None, batched=False, clips_per_search=32, do_sample=False, num_samples=1, temperature=1.0,
-                 top_k=None, top_p=None, seed=0, kv_cache="per_sequence", **kw):
+                 top_k=None, top_p=None, seed=0, kv_cache="per_sequence", repetition_penalty=None, no_repeat_ngram_size=0, min_new_tokens=0,
+                 banned_token_ids=None, constrain_prompt=False, **kw):
         """One beam search per sample (:790-809): prompt = text.input_ids[i, :mask.sum()-1], prefix = its query features.
         batched=True (not in the reference, default off): the clips are grouped by prompt length and every group is searched in
         lockstep, `clips_per_search` clips at a time (generation.beam_search_batched_loop: the decoder's weights are read once per
@@ -351,7 +352,12 @@ class DistributedGPT3_Caption(_GenCls):
         A chunk stops when all of its sequences have terminated, and a terminated sequence goes on drawing until then (as in the
         reference's sample): every row is therefore cut behind its first termination token and padded with that token to the full
         width Lt = prompt columns + tokens_to_generate, which is what makes the result independent of the chunking.
-        -> per clip one [num_samples, Lt] tensor, in input order."""
+        -> per clip one [num_samples, Lt] tensor, in input order.
+        repetition_penalty / no_repeat_ngram_size / min_new_tokens / banned_token_ids / constrain_prompt (batched=True and do_sample=True
+        only; defaults off): a generation.LogitsConstraints applied to every step's raw logits on the device (one launch,
+        ops.logits_constrain) -- the CTRL penalty on tokens already generated, no n-gram of that size twice, no termination token
+        before min_new_tokens tokens, ids that are never produced; constrain_prompt=True lets the penalty and the n-grams see the
+        prompt too.  They combine with kv_cache="shared_prefix"."""
         Bv = image.shape[0]
         Q, Hh = self.num_learnable_token, self.text_width
         was = self.training
@@ -369,6 +375,15 @@ class DistributedGPT3_Caption(_GenCls):
                 if not (do_sample or batched):
                     raise ValueError('kv_cache="shared_prefix" needs batched=True or do_sample=True (the per-clip search keeps a cache per beam)')
                 kw = dict(kw, kv=kv_cache)                               # absent keyword: the calls below are today's
+            if repetition_penalty is not None or no_repeat_ngram_size or min_new_tokens or banned_token_ids or constrain_prompt:
+                if not (do_sample or batched):
+                    raise ValueError("repetition_penalty / no_repeat_ngram_size / min_new_tokens / banned_token_ids / constrain_prompt need "
+                                     f"batched=True or do_sample=True (got repetition_penalty={repetition_penalty!r}, no_repeat_ngram_size="
+                                     f"{no_repeat_ngram_size!r}, min_new_tokens={min_new_tokens!r}, banned_token_ids={banned_token_ids!r}, "
+                                     f"constrain_prompt={constrain_prompt!r}): the per-clip search has no constraints")
+                kw = dict(kw, constraints=generation.LogitsConstraints(
+                    repetition_penalty=1.0 if repetition_penalty is None else repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                    min_new_tokens=min_new_tokens, banned_token_ids=tuple(banned_token_ids or ()), include_prompt=constrain_prompt))
             if do_sample:
                 N = int(num_samples)
                 if int(clips_per_search) < 1 or N < 1:

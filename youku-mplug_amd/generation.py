@@ -16,6 +16,7 @@ mpv_gpt_decode_step_shared, csrc/decode_shared_attention.hip).
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 from types import SimpleNamespace
 from typing import Callable, List, Optional
@@ -420,7 +421,8 @@ class BeamState:
 
 
 def beam_search_batched_loop(cfg, make_state: Callable[[int, int], object], tokens: torch.Tensor, query_embeds=None, beam_size=5,
-                             num_return_gen=1, stop_token=None, prompt_length: Optional[int] = None, topk_fn=None, advance_fn=None):
+                             num_return_gen=1, stop_token=None, prompt_length: Optional[int] = None, topk_fn=None, advance_fn=None,
+                             constraints: Optional["LogitsConstraints"] = None, constrain_fn=None):
     """beam_search_loop for B clips in lockstep: tokens [B, L], query_embeds [B, Q, H], ONE prompt length for all clips of the call.
     Every decode step advances B x beam_size sequences, so the decoder's weights are read once per generated position instead of
     once per clip and position, the prefill runs once per clip (state.prefill_fan_out) and the bookkeeping of a step is one kernel.
@@ -432,8 +434,13 @@ def beam_search_batched_loop(cfg, make_state: Callable[[int, int], object], toke
     After the loop the state is downloaded once; the final flush of the unfinished clips and the stable ranking run on the host
     through BeamHypotheses, as in beam_search_loop.  -> a list of B namespaces (sequences [n, Lt], scores [n]), clip by clip what
     beam_search_loop returns for it.  `make_state(batch, max_len)` -> an object with prefill_fan_out / step / reorder
-    (DecodeState); make_state, topk_fn and advance_fn are injectable as in beam_search_loop."""
+    (DecodeState); make_state, topk_fn and advance_fn are injectable as in beam_search_loop.
+    `constraints` (a LogitsConstraints; None or inactive: no call and no launch is added): before topk_fn every step edits the raw
+    logits of all B x beam_size rows -- the first step's and those of frozen clips too, which advance_fn ignores -- through
+    constrain_fn (ops.logits_constrain) on the beams' token table, with the stop token as the termination id of min_new_tokens and
+    the lowest finite bf16 as the ban value (include/mpv.h says why it is not -inf here)."""
     B, dev, K = tokens.size(0), tokens.device, int(beam_size)
+    constraints = _active_constraints(constraints, constrain_fn)
     prompt_length = int(prompt_length) if prompt_length is not None else tokens.size(1)
     stop_token = cfg.eod_id if stop_token is None else int(stop_token)
     tokens = torch.cat((tokens, torch.full((B, cfg.tokens_to_generate), stop_token, dtype=torch.long, device=dev)), dim=-1)
@@ -449,6 +456,9 @@ def beam_search_batched_loop(cfg, make_state: Callable[[int, int], object], toke
             logits = state.prefill_fan_out(tokens[:, :prompt_length].contiguous(), query_embeds, K)
         else:
             logits = state.step(bs.next_tok.view(-1, 1))
+        if constraints is not None:
+            constrain_fn(logits, bs.tokens.view(B * K, -1), pos=context_length - Q, constraints=constraints, prompt_len_all=prompt_length,
+                         eos_ids=[stop_token], ban_value=BAN_BEAM)
         vals, idxs = topk_fn(logits, 2 * K, bs.scores.view(-1))                             # log_softmax + scores (:1790-1791)
         advance_fn(vals, idxs, bs, vocab=logits.size(-1), pos=context_length - Q, cur_len=n + 1, first=n == 0, stop_token=stop_token)
         if bool(bs.done.all()):                                                              # the step's one host read
@@ -469,6 +479,55 @@ def beam_search_batched_loop(cfg, make_state: Callable[[int, int], object], toke
         out.append(SimpleNamespace(sequences=torch.stack([ranked[i][1] for i in range(n_ret)], dim=0).to(dev),
                                    scores=torch.tensor([ranked[i][0] for i in range(n_ret)], dtype=torch.float32)))
     return out
+
+
+BAN_SAMPLING = float("-inf")                 # mpv_sample_advance: probability 0, never in the kept set
+BAN_BEAM = -float.fromhex("0x1.fep127")      # the lowest finite bf16: mpv_logprob_topk would take exp(-inf + inf) on a slice of -inf only
+
+
+@dataclasses.dataclass
+class LogitsConstraints:
+    """What the lockstep loops may forbid or discourage (include/mpv.h: mpv_logits_constrain; ops.logits_constrain applies it to one
+    step's logits on the device): the CTRL repetition penalty (1.0 = off), the no-repeat n-gram size (0 = off, at most 8),
+    min_new_tokens (the termination tokens stay banned until that many tokens are generated), banned_token_ids (at most 1024 single
+    tokens) and include_prompt (the penalty and the n-grams also see the prompt; default: the generated tokens only).
+    The constraints act on the RAW logits -- before temperature, the top-k / top-p filter and log_softmax -- in sampling and in beam
+    search alike.  (Hugging Face's beam search applies its processors to the log-probabilities instead, so a penalised beam score
+    differs from theirs; for sampling the two orders agree with their processors run before their warpers.)"""
+    repetition_penalty: float = 1.0
+    no_repeat_ngram_size: int = 0
+    min_new_tokens: int = 0
+    banned_token_ids: tuple = ()
+    include_prompt: bool = False
+
+    def __post_init__(self):
+        p = self.repetition_penalty
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not math.isfinite(p) or p <= 0:
+            raise ValueError(f"repetition_penalty must be a finite number above 0 (got {p!r})")
+        for name, hi in (("no_repeat_ngram_size", 8), ("min_new_tokens", None)):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0 or (hi is not None and v > hi):
+                raise ValueError(f"{name} must be an integer in [0, {hi}] (got {v!r})" if hi else f"{name} must be a non-negative integer (got {v!r})")
+        ids = tuple(self.banned_token_ids)
+        for t in ids:
+            if isinstance(t, bool) or not isinstance(t, int):
+                raise ValueError(f"banned_token_ids must be integers (got {t!r})")
+        if len(ids) > 1024:
+            raise ValueError(f"at most 1024 banned_token_ids (got {len(ids)})")
+        self.repetition_penalty, self.banned_token_ids, self.include_prompt = float(p), ids, bool(self.include_prompt)
+        self._device_ids = {}                    # ops.logits_constrain: the device copies of the id lists, made once
+
+    @property
+    def active(self) -> bool:
+        return self.repetition_penalty != 1.0 or self.no_repeat_ngram_size > 0 or self.min_new_tokens > 0 or len(self.banned_token_ids) > 0
+
+
+def _active_constraints(constraints, constrain_fn):
+    if constraints is None or not constraints.active:
+        return None
+    if constrain_fn is None:
+        raise ValueError("active constraints need a constrain_fn (ops.logits_constrain)")
+    return constraints
 
 
 def sample_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None, temperature=1.0, use_eod_token_for_early_termination=True,
@@ -531,7 +590,7 @@ class SampleState:
 
 def sample_batched_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None, temperature=1.0, use_eod_token_for_early_termination=True,
                         stop_on_double_eol=False, stop_on_eol=False, termination_id=None, prompt_length=None, num_samples=1, seed=0,
-                        streams=None, advance_fn=None):
+                        streams=None, advance_fn=None, constraints: Optional["LogitsConstraints"] = None, constrain_fn=None):
     """sample_loop with the whole of a step's sampling and bookkeeping in one launch, for B clips x num_samples sequences in lockstep:
     tokens [B, L], query_embeds [B, Q, H], prompt_length [B] (ragged lengths are allowed) or None.  Sequence j belongs to clip
     j // num_samples.  The prefill runs once per clip over the shortest prompt (state.prefill_fan_out) and fans out to the clip's
@@ -539,10 +598,18 @@ def sample_batched_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None
     prefill, termination; include/mpv.h states the semantics).  Samples never swap KV caches, so nothing is re-ordered, and the host
     reads four bytes per step (the count of done rows).  Row j draws from the stream streams[j] (default j) of `seed`: its tokens do
     not depend on the other rows of the call.  cfg.top_k / cfg.top_p choose the filter as in sample_loop.  -> tokens [B * num_samples,
-    n] with sample_loop's (prefix-inclusive, sic) slice.  make_state and advance_fn are injectable as in beam_search_batched_loop."""
+    n] with sample_loop's (prefix-inclusive, sic) slice.  make_state and advance_fn are injectable as in beam_search_batched_loop.
+    `constraints` (a LogitsConstraints; None or inactive: no call and no launch is added): between the step and advance_fn every
+    step, the prefill's included, edits the raw logits through constrain_fn (ops.logits_constrain) on st.tokens / st.prompt_len; rows
+    still inside their prompt are left alone.  The termination ids of min_new_tokens are [termination_id], or [628, 198] under
+    stop_on_eol; a banned logit is -inf, the sampler's "never drawn".  min_new_tokens with stop_on_double_eol is refused (a pair of
+    tokens ends the row there, which a per-token ban cannot express)."""
     B, dev, N = tokens.size(0), tokens.device, int(num_samples)
     if N < 1:
         raise ValueError(f"num_samples must be at least 1 (got {num_samples})")
+    constraints = _active_constraints(constraints, constrain_fn)
+    if constraints is not None and constraints.min_new_tokens > 0 and stop_on_double_eol:
+        raise ValueError(f"min_new_tokens ({constraints.min_new_tokens}) cannot be combined with stop_on_double_eol")
     lengths = prompt_length if prompt_length is not None else torch.tensor([tokens.size(1)], device=dev)
     lengths = torch.as_tensor(lengths, device=dev).view(-1).expand(B)
     tokens = torch.cat((tokens, torch.full((B, cfg.tokens_to_generate), cfg.eod_id, dtype=torch.long, device=dev)), dim=-1)
@@ -556,6 +623,7 @@ def sample_batched_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None
     st = SampleState(tokens.repeat_interleave(N, dim=0), lengths.repeat_interleave(N), streams=streams)
     termination_id = cfg.eod_id if termination_id is None else int(termination_id)
     mode = 2 if stop_on_double_eol else 1 if stop_on_eol else 0
+    eos_ids = [628, 198] if mode else [termination_id]
     total_min, total_max = min_prompt + Q, max_len + Q
     context_length = total_min
     for context_length in range(total_min, total_max):
@@ -563,6 +631,9 @@ def sample_batched_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None
             logits = state.prefill_fan_out(tokens[:, :min_prompt].contiguous(), query_embeds, N)
         else:
             logits = state.step(st.next_tok.view(-1, 1))
+        if constraints is not None:
+            constrain_fn(logits, st.tokens, pos=context_length - Q, constraints=constraints, prompt_len=st.prompt_len, eos_ids=eos_ids,
+                         ban_value=BAN_SAMPLING)
         advance_fn(logits, st, pos=context_length - Q, temperature=temperature, top_k=cfg.top_k, top_p=cfg.top_p, seed=seed,
                    vocab_size=cfg.vocab_size, termination_mode=mode, termination_id=termination_id)
         if use_eod_token_for_early_termination and int(st.n_done.item()) == R:       # the step's one host read: 4 bytes
@@ -596,29 +667,35 @@ def install(gpt_cls):
                                 num_return_gen=num_return_gen, stop_token=stop_token, prompt_length=kw.pop("prompt_length", None),
                                 topk_fn=lambda lg, k, add: ops.logprob_topk(lg, k, add=add))
 
-    def beam_search_batched(self, tokens, query_embeds=None, beam_size=5, num_return_gen=1, stop_token=None, kv="per_sequence", **kw):
+    def beam_search_batched(self, tokens, query_embeds=None, beam_size=5, num_return_gen=1, stop_token=None, kv="per_sequence",
+                            constraints=None, **kw):
         """beam_search for tokens [B, L] / query_embeds [B, Q, H] with one prompt length, B clips in lockstep -> a list of B results;
-        kv="shared_prefix" keeps the visual prefix and the prompt once per clip (SharedPrefixDecodeState)"""
+        kv="shared_prefix" keeps the visual prefix and the prompt once per clip (SharedPrefixDecodeState); constraints: a
+        LogitsConstraints, applied on the device every step"""
         return beam_search_batched_loop(_gen_config(self), make_state_fn(self, kv), tokens, query_embeds=query_embeds, beam_size=beam_size,
                                         num_return_gen=num_return_gen, stop_token=stop_token, prompt_length=kw.pop("prompt_length", None),
-                                        topk_fn=lambda lg, k, add: ops.logprob_topk(lg, k, add=add), advance_fn=ops.beam_advance)
+                                        topk_fn=lambda lg, k, add: ops.logprob_topk(lg, k, add=add), advance_fn=ops.beam_advance,
+                                        constraints=constraints, constrain_fn=ops.logits_constrain)
 
     def sample_batched(self, tokens, query_embeds=None, temperature=1.0, num_samples=1, seed=0, streams=None, top_k=None, top_p=None,
-                       kv="per_sequence", **kw):
+                       kv="per_sequence", constraints=None, **kw):
         """sample with the sampler on the device (sample_batched_loop): tokens [B, L] -> [B * num_samples, n]; top_k / top_p override
         the configuration's values; the draws are those of (seed, position, streams[row]) -- not torch's generator;
-        kv="shared_prefix" keeps the visual prefix and the shortest prompt once per clip (SharedPrefixDecodeState)"""
+        kv="shared_prefix" keeps the visual prefix and the shortest prompt once per clip (SharedPrefixDecodeState); constraints: a
+        LogitsConstraints, applied on the device every step"""
         make_state = make_state_fn(self, kv)
         cfg = _gen_config(self)
         if top_k is not None or top_p is not None:
             cfg.top_k, cfg.top_p = int(top_k or 0), float(top_p or 0.0)
         return sample_batched_loop(cfg, make_state, tokens, query_embeds=query_embeds, temperature=temperature, num_samples=num_samples,
-                                   seed=seed, streams=streams, advance_fn=ops.sample_advance, **kw)
+                                   seed=seed, streams=streams, advance_fn=ops.sample_advance, constraints=constraints,
+                                   constrain_fn=ops.logits_constrain, **kw)
 
     @torch.no_grad()
     def generate(self, tokens, do_sample=True, termination_id=None, *args, **kw):                # :1875-1880
         """sampler="device" (keyword; not in the reference, default "torch"): do_sample=True runs sample_batched, which takes
-        kv="per_sequence" | "shared_prefix" (the per-clip loops keep a cache per sequence)"""
+        kv="per_sequence" | "shared_prefix" (the per-clip loops keep a cache per sequence) and constraints= (a LogitsConstraints; the
+        per-clip loops have none)"""
         sampler = kw.pop("sampler", "torch")
         if sampler not in ("torch", "device"):
             raise ValueError(f"sampler must be 'torch' or 'device' (got {sampler!r})")
@@ -626,6 +703,8 @@ def install(gpt_cls):
             raise ValueError(f"kv must be one of {KV_MODES} (got {kw['kv']!r})")
         if not (do_sample and sampler == "device") and kw.pop("kv", "per_sequence") != "per_sequence":
             raise ValueError('kv="shared_prefix" needs a lockstep loop: do_sample=True with sampler="device", or beam_search_batched')
+        if not (do_sample and sampler == "device") and kw.pop("constraints", None) is not None:
+            raise ValueError('constraints need a lockstep loop: do_sample=True with sampler="device", or beam_search_batched')
         was = self.training
         self.eval()
         try:

@@ -684,6 +684,43 @@ def sample_advance(logits, st, *, pos, temperature=1.0, top_k=0, top_p=0.0, seed
     return st.next_tok
 
 
+def _constraint_ids(constraints, device, eos_ids):
+    """(eos, banned) int64 device arrays of a generation.LogitsConstraints, made once per (device, eos_ids) and kept on the object"""
+    key = (str(device), tuple(int(t) for t in eos_ids))
+    hit = constraints._device_ids.get(key)
+    if hit is None:
+        hit = (torch.tensor(key[1], dtype=torch.int64, device=device), torch.tensor(constraints.banned_token_ids, dtype=torch.int64, device=device))
+        constraints._device_ids[key] = hit
+    return hit
+
+
+def logits_constrain(logits, tokens, *, pos, constraints, prompt_len=None, prompt_len_all=0, eos_ids=(), ban_value=float("-inf"), vocab=None,
+                     ld=None):
+    """One step's generation constraints, in place and in one launch (include/mpv.h: mpv_logits_constrain; constraints is a
+    generation.LogitsConstraints): repetition penalty, no-repeat n-gram, min_new_tokens (bans eos_ids while fewer tokens are generated)
+    and the banned ids, on logits bf16 [rows, ld] (the first `vocab` columns) from the histories in tokens int64 [rows, row_len] below
+    column `pos`.  prompt_len int64 [rows] (rows with prompt_len > pos are left alone), or None: prompt_len_all for every row.  A
+    banned logit becomes ban_value (-inf for the sampler, the lowest finite bf16 in front of logprob_topk).  -> logits"""
+    _need_cuda(logits, tokens, prompt_len)
+    if logits.dtype != torch.bfloat16 or logits.ndim != 2 or logits.stride(1) != 1:
+        raise _lib.MpvError(f"logits_constrain: logits must be bf16 [rows, ld] with unit column stride (got {logits.dtype} {tuple(logits.shape)})")
+    rows = logits.shape[0]
+    if tokens.dtype != torch.int64 or tokens.ndim != 2 or tokens.shape[0] != rows or not tokens.is_contiguous():
+        raise _lib.MpvError(f"logits_constrain: tokens must be contiguous int64 [{rows}, row_len] (got {tokens.dtype} {tuple(tokens.shape)})")
+    if prompt_len is not None and (prompt_len.dtype != torch.int64 or prompt_len.numel() != rows or not prompt_len.is_contiguous()):
+        raise _lib.MpvError(f"logits_constrain: prompt_len must be contiguous int64 [{rows}]")
+    eos, banned = _constraint_ids(constraints, logits.device, eos_ids)
+    d = _lib.LogitsConstrainDesc()
+    d.logits, d.tokens, d.prompt_len = _p(logits), _p(tokens), _p(prompt_len)
+    d.eos_ids, d.banned_ids = (_p(eos) if eos.numel() else None), (_p(banned) if banned.numel() else None)
+    d.ld, d.prompt_len_all = int(ld) if ld is not None else logits.stride(0), int(prompt_len_all)
+    d.rows, d.vocab, d.row_len, d.pos = rows, int(vocab) if vocab is not None else logits.shape[-1], tokens.shape[1], int(pos)
+    d.n_eos, d.n_banned, d.ngram, d.min_new_tokens = eos.numel(), banned.numel(), constraints.no_repeat_ngram_size, constraints.min_new_tokens
+    d.include_prompt, d.penalty, d.ban_value = int(constraints.include_prompt), constraints.repetition_penalty, float(ban_value)
+    check(_lib.lib().mpv_logits_constrain(C.byref(d), _stream()), "mpv_logits_constrain")
+    return logits
+
+
 def sample_tokens(logits, *, temperature=1.0, top_k=0, top_p=0.0, seed=0, streams=None, vocab_size=None, vocab=None):
     """One-off draw: -> int64 [rows], the token sample_advance draws at pos 0 for every row of logits bf16 [rows, ld] (no prompt, no
     termination; vary `seed` or `streams` for another draw)."""
