@@ -17,7 +17,11 @@ What this entry point adds to downstream/finetune_common.py:
   * `--eval_repetition_penalty F`, `--eval_no_repeat_ngram N`, `--eval_min_new_tokens N` (not in the reference, defaults off): the
     `--eval_batched_beam` and `--eval_sample` calls penalise repeated tokens, never repeat an n-gram of N tokens and do not end a
     caption before N tokens, on the device (`model.generate(..., repetition_penalty=F, no_repeat_ngram_size=N, min_new_tokens=N)`);
-    without one of those two flags they are an error;
+    without one of those two flags (or `--eval_sample_best_of`) they are an error;
+  * `--eval_sample_best_of N` (not in the reference, default 0 = off): the caption of a clip is the most likely of N sampled ones
+    instead of the beam search's (`model.generate(..., do_sample=True, num_samples=N, best_of=True)`: the model's log-probability per
+    token, recorded on the device while sampling), written as "pred_caption" through the same result path, so the metrics below run
+    on it; it combines with `--eval_shared_kv` and the constraint flags;
   * save_result (dataset/utils.py:114-160): one JSON per rank, merged by rank 0; cal_metric (:240-298): predictions and references
     reduced to their CJK characters, one token per character, scored by pycocoevalcap's COCOEvalCap when that package is importable.
     It is not on this image: then BLEU-1..4 (corpus level, closest-reference brevity penalty) and ROUGE-L (beta 1.2, best reference)
@@ -47,10 +51,11 @@ def make_training_batch(video, text, prompt, tokenizer, device, max_length):
 
 @torch.no_grad()
 def evaluation(model, data_loader, tokenizer, device, config, batched=False, clips_per_search=32, eval_sample=0, seed=0, shared_kv=False,
-               constraints=None):
+               constraints=None, best_of=0):
     """-> [{video_id, pred_caption, gold_caption}] (:208-238); batched: `--eval_batched_beam`; eval_sample: `--eval_sample`;
     shared_kv: `--eval_shared_kv`, constraints: the keywords of `--eval_repetition_penalty` / `--eval_no_repeat_ngram` /
-    `--eval_min_new_tokens` (the lockstep calls only)"""
+    `--eval_min_new_tokens` (the lockstep calls only); best_of: `--eval_sample_best_of` (the prediction is the best of that many
+    samples instead of the beam search's)"""
     module = getattr(model, "module", model)
     module.eval()
     kvkw = {"kv_cache": "shared_prefix"} if shared_kv else {}                # flag absent: the calls below are unchanged
@@ -60,7 +65,11 @@ def evaluation(model, data_loader, tokenizer, device, config, batched=False, cli
         video = video.to(device, non_blocking=True).bfloat16()
         text = [config["prompt"] for _ in range(video.shape[0])]
         text_input = tokenizer(text, padding="max_length", truncation=True, max_length=20, return_tensors="pt").to(device)
-        res = module.generate(video, text_input, batched=True, clips_per_search=clips_per_search, **kvkw) if batched else module.generate(video, text_input)
+        if best_of:
+            res = module.generate(video, text_input, do_sample=True, num_samples=best_of, best_of=True, seed=seed + n,
+                                  clips_per_search=clips_per_search, **kvkw)
+        else:
+            res = module.generate(video, text_input, batched=True, clips_per_search=clips_per_search, **kvkw) if batched else module.generate(video, text_input)
         def caption(ids):
             ans = tokenizer.decode(ids).replace(" ", "").strip()
             return ans.split(config["prompt"])[-1].strip() if config["prompt"] != "" else ans
@@ -220,7 +229,7 @@ def main(args, config):
         result = evaluation(s.model, val_loader, s.tokenizer, s.device, config, batched=getattr(args, "eval_batched_beam", False),
                             clips_per_search=getattr(args, "clips_per_search", 32), eval_sample=getattr(args, "eval_sample", 0),
                             seed=getattr(args, "seed", 0) or 0, shared_kv=getattr(args, "eval_shared_kv", False),
-                            constraints=constraint_keywords(args))
+                            constraints=constraint_keywords(args), best_of=getattr(args, "eval_sample_best_of", 0))
         val_stats = cal_metric(save_result(result, args.result_dir, "val_caption_result"))
         print("* Validation Stats:", val_stats)
         log_stats = {**{f"val_{k}": v for k, v in val_stats.items()}, "n_parameters": s.n_parameters}
@@ -238,9 +247,9 @@ def constraint_keywords(args):
         kw["no_repeat_ngram_size"] = args.eval_no_repeat_ngram
     if getattr(args, "eval_min_new_tokens", 0):
         kw["min_new_tokens"] = args.eval_min_new_tokens
-    if kw and not (getattr(args, "eval_batched_beam", False) or getattr(args, "eval_sample", 0)):
+    if kw and not (getattr(args, "eval_batched_beam", False) or getattr(args, "eval_sample", 0) or getattr(args, "eval_sample_best_of", 0)):
         raise ValueError(f"--eval_repetition_penalty / --eval_no_repeat_ngram / --eval_min_new_tokens ({kw}) need --eval_batched_beam or "
-                         "--eval_sample: the per-clip beam search has no constraints")
+                         "--eval_sample (or --eval_sample_best_of): the per-clip beam search has no constraints")
     return kw
 
 
@@ -262,7 +271,12 @@ def get_args(argv=None):
                        help="--eval_batched_beam / --eval_sample: no n-gram of N tokens is generated twice (model.generate(no_repeat_ngram_size=N))")
         p.add_argument("--eval_min_new_tokens", type=int, default=0,
                        help="--eval_batched_beam / --eval_sample: no termination token before N generated tokens (model.generate(min_new_tokens=N))")
+        p.add_argument("--eval_sample_best_of", type=int, default=0,
+                       help="evaluation: the caption of a clip is the most likely of N sampled ones, not the beam search's "
+                            "(model.generate(do_sample=True, num_samples=N, best_of=True)); 0 = off")
     args, config = ft.get_args(argv, extra=extra)
+    if args.eval_sample_best_of < 0:
+        raise ValueError(f"--eval_sample_best_of must not be negative (got {args.eval_sample_best_of})")
     constraint_keywords(args)                                               # refuses the flags without a lockstep mode
     config.setdefault("prompt", "")
     args.result_dir = os.path.join(args.output_dir, "result")

@@ -579,6 +579,41 @@ typedef struct mpv_logits_constrain_desc {
 } mpv_logits_constrain_desc;
 int mpv_logits_constrain(const mpv_logits_constrain_desc* d, mpv_stream_t stream);
 /* ------------------------------------------------------------------------------------------
+ * Sequence scores of sampled generation in lockstep (generation.SampleScores): ONE launch, right after mpv_sample_advance, records
+ * the model's log-probability of the token that call wrote into column `pos` -- log_softmax of the RAW logits the sampler read
+ * (after mpv_logits_constrain edited them, if it did).  Temperature, top-k and top-p are ignored by design: the score is the
+ * model's under the constraints, not the proposal's.
+ * Input: logits bf16 [rows][ld], 16-byte aligned, the first `vocab` columns are the row, exactly what mpv_sample_advance read this
+ *   step; tokens int64 [rows][row_len] AFTER mpv_sample_advance wrote column pos; prompt_len int64 [rows]; done int32 [rows], the
+ *   sampler's flags AFTER its call.  State, owned by the scoring: live int32 [rows] (initially 1), token_logprob fp32
+ *   [rows][row_len] (initially 0), sum_logprob fp32 [rows] (initially 0), count int32 [rows] (initially 0).
+ * Row r: with prompt_len[r] > pos (teacher-forced) or live[r] == 0 (terminated in an earlier call: the sampler lets such a row go
+ *   on drawing until the chunk ends) nothing of the row is read except those two words, and nothing is written.  Otherwise, with
+ *   t = tokens[r][pos], x_i = float(logits[r][i]) for i < vocab, m = max x_i and S = sum exp(x_i - m) in fp32, where a logit of
+ *   -inf contributes 0:  lp = x_t - (m + log S).  If x_t is -inf, lp = -inf explicitly, whatever the rest of the row is (the
+ *   all-banned row, where the sampler emits token 0, included): never NaN.  If t is outside [0, vocab), lp = NaN (the loop cannot
+ *   produce that; it makes misuse loud).  Then, by one thread: token_logprob[r][pos] = lp; sum_logprob[r] += lp; count[r] += 1;
+ *   live[r] = done[r] ? 0 : 1.  The terminating token itself is scored, every position behind it is not.
+ * NaN and +inf logits are not supported, as in mpv_sample_advance.  Columns at and beyond vocab are never read.
+ * A row's result depends on its own logits, its token and its own state only -- neither on `rows` nor on the row's place in the
+ *   launch.  The reductions run in a fixed order, without floating-point atomics: the same inputs give the same bits on every run.
+ * Refused with a negative code before any launch, every output untouched: a NULL pointer; vocab not a multiple of 8 or outside
+ *   [8, 65536]; ld < vocab or ld % 8 != 0; logits not 16-byte aligned; rows < 1; row_len outside [1, 2048]; pos outside [0, row_len).
+ * One workgroup per row, the row read once with 16-byte loads and held in registers (max, then sum); no scratch. */
+typedef struct mpv_sample_score_desc {
+  const void* logits;
+  const int64_t* tokens;
+  const int64_t* prompt_len;
+  const int32_t* done;
+  int32_t* live;
+  float* token_logprob;
+  float* sum_logprob;
+  int32_t* count;
+  int64_t ld;
+  int rows, vocab, row_len, pos;
+} mpv_sample_score_desc;
+int mpv_sample_score(const mpv_sample_score_desc* d, mpv_stream_t stream);
+/* ------------------------------------------------------------------------------------------
  * Device-side video input transform (configs' video_pretrain/train/test transforms,
  * dataset/__init__.py:60-85): the decoder's uint8 clip [T][H][W][3] -> crop (i, j, h, w) ->
  * torch.nn.functional.interpolate to out_h x out_w (mode 0 nearest / 1 bilinear / 2 bicubic, align_corners=False:

@@ -110,6 +110,11 @@ class LogitsConstrainDesc(C.Structure):
                [("penalty", c_float), ("ban_value", c_float)]
 
 
+class SampleScoreDesc(C.Structure):
+    _fields_ = [(n, c_void_p) for n in ("logits", "tokens", "prompt_len", "done", "live", "token_logprob", "sum_logprob", "count")] + \
+               [("ld", c_int64)] + [(n, c_int) for n in ("rows", "vocab", "row_len", "pos")]
+
+
 _RM = [c_int, c_int, c_int]
 _SIGS = {
     "mpv_version": (c_int, []),
@@ -187,6 +192,7 @@ _SIGS = {
     "mpv_beam_advance": (c_int, [C.POINTER(BeamAdvanceDesc), c_void_p]),
     "mpv_sample_advance": (c_int, [C.POINTER(SampleAdvanceDesc), c_void_p]),
     "mpv_logits_constrain": (c_int, [C.POINTER(LogitsConstrainDesc), c_void_p]),
+    "mpv_sample_score": (c_int, [C.POINTER(SampleScoreDesc), c_void_p]),
     "mpv_soft_target_ce": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     "mpv_maxsim_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p]),
     "mpv_maxsim_route": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p]),

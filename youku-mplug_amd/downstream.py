@@ -13,6 +13,7 @@ B + len(negative_indices) rows.  forward(..., train=False) returns the scores th
 """
 from __future__ import annotations
 
+import math
 from typing import Optional, Sequence
 
 import torch
@@ -332,7 +333,7 @@ class DistributedGPT3_Caption(_GenCls):
     @torch.no_grad()
     def generate(self, image, text, termination_id=None, batched=False, clips_per_search=32, do_sample=False, num_samples=1, temperature=1.0,
                  top_k=None, top_p=None, seed=0, kv_cache="per_sequence", repetition_penalty=None, no_repeat_ngram_size=0, min_new_tokens=0,
-                 banned_token_ids=None, constrain_prompt=False, **kw):
+                 banned_token_ids=None, constrain_prompt=False, return_scores=False, best_of=False, length_penalty=1.0, **kw):
         """One beam search per sample (:790-809): prompt = text.input_ids[i, :mask.sum()-1], prefix = its query features.
         batched=True (not in the reference, default off): the clips are grouped by prompt length and every group is searched in
         lockstep, `clips_per_search` clips at a time (generation.beam_search_batched_loop: the decoder's weights are read once per
@@ -357,7 +358,20 @@ class DistributedGPT3_Caption(_GenCls):
         only; defaults off): a generation.LogitsConstraints applied to every step's raw logits on the device (one launch,
         ops.logits_constrain) -- the CTRL penalty on tokens already generated, no n-gram of that size twice, no termination token
         before min_new_tokens tokens, ids that are never produced; constrain_prompt=True lets the penalty and the n-grams see the
-        prompt too.  They combine with kv_cache="shared_prefix"."""
+        prompt too.  They combine with kv_cache="shared_prefix".
+        return_scores=True (do_sample=True only; default off): -> (res, scores); scores[i] is a dict of CPU tensors for clip i, in input
+        order: sum_logprob [N] fp32 (the model's log-probability of sample s: the sum over its generated tokens up to and including the
+        terminating one), count [N] int32 (how many tokens that is) and token_logprob [N, Lt] fp32 (0 at prompt positions, behind the
+        termination and in the columns the chunk never reached: the table is padded like the tokens).  The scores are recorded on the
+        device, one launch per step (ops.sample_score), from the RAW logits under the constraints: temperature, top_k and top_p shape
+        the proposal, not the score.
+        best_of=True (do_sample=True only; default off): one [1, Lt] tensor per clip, sample argmax_s sum_logprob[s] / count[s] **
+        length_penalty of the clip's num_samples samples (fp64 on the host, once per chunk, from the chunk's one download; a tie goes to
+        the lowest sample index; a sample with count 0 scores -inf); with return_scores the dict holds the chosen sample's entries
+        ([1], [1], [1, Lt]) and `index`, its number.
+        A clip's TOKENS stay independent of clips_per_search and of its neighbours.  Its SCORES are bit-identical only at an equal row
+        count: the decode step's GEMM dispatch depends on the number of rows (DESIGN.md sections 13, 17, 18), which moves the logits in
+        their last bf16 digit.  A near-tie in best_of may therefore resolve differently under another chunking."""
         Bv = image.shape[0]
         Q, Hh = self.num_learnable_token, self.text_width
         was = self.training
@@ -369,6 +383,9 @@ class DistributedGPT3_Caption(_GenCls):
                 termination_id = tok.tokenizer.eos if tok is not None else None
             n = text.input_ids.shape[0]
             from . import generation
+            if (return_scores or best_of) and not do_sample:
+                raise ValueError(f"return_scores / best_of need do_sample=True (got return_scores={return_scores!r}, best_of={best_of!r}): "
+                                 "beam hypotheses carry their own scores")
             if kv_cache not in generation.KV_MODES:
                 raise ValueError(f"kv_cache must be one of {generation.KV_MODES} (got {kv_cache!r})")
             if kv_cache != "per_sequence":
@@ -393,6 +410,10 @@ class DistributedGPT3_Caption(_GenCls):
                 term = gc.eod_id if termination_id is None else int(termination_id)
                 width = min(text.input_ids.shape[1] + gc.tokens_to_generate, gc.max_position_embeddings)
                 res = [None] * n
+                scored = bool(return_scores or best_of)
+                scores = [None] * n
+                if scored:
+                    kw = dict(kw, return_scores=True)                    # absent keyword: the calls below are today's
                 for pl in sorted(set(lengths)):
                     group = [i for i in range(n) if lengths[i] == pl]
                     for c in range(0, len(group), int(clips_per_search)):
@@ -402,10 +423,24 @@ class DistributedGPT3_Caption(_GenCls):
                                                                num_samples=N, seed=seed, streams=streams, top_k=top_k, top_p=top_p,
                                                                termination_id=termination_id,
                                                                prompt_length=torch.full((len(sel),), int(pl), device=qf.device), **kw)
-                        out = generation.pad_after_termination(out, int(pl), term, width, term).cpu()
+                        if not scored:
+                            out = generation.pad_after_termination(out, int(pl), term, width, term).cpu()
+                            for j, i in enumerate(sel.tolist()):
+                                res[i] = out[j * N:(j + 1) * N]
+                            continue
+                        out, sc = out
+                        out, tlp, slp, cnt = _download_scored(generation.pad_after_termination(out, int(pl), term, width, term), sc, width)
                         for j, i in enumerate(sel.tolist()):
-                            res[i] = out[j * N:(j + 1) * N]
-                return res
+                            rows = slice(j * N, (j + 1) * N)
+                            entry = dict(sum_logprob=slp[rows], count=cnt[rows], token_logprob=tlp[rows])
+                            if best_of:
+                                b = best_sample(entry["sum_logprob"], entry["count"], length_penalty)
+                                entry = dict({k: v[b:b + 1] for k, v in entry.items()}, index=b)
+                                res[i] = out[rows][b:b + 1]
+                            else:
+                                res[i] = out[rows]
+                            scores[i] = entry
+                return (res, scores) if return_scores else res
             if batched:
                 if int(clips_per_search) < 1:
                     raise ValueError(f"clips_per_search must be at least 1 (got {clips_per_search})")
@@ -428,6 +463,33 @@ class DistributedGPT3_Caption(_GenCls):
             return res
         finally:
             self.train(was)
+
+
+def best_sample(sum_logprob, count, length_penalty: float = 1.0) -> int:
+    """argmax_s sum_logprob[s] / count[s] ** length_penalty in fp64; a tie goes to the lowest index, a sample with count 0 scores -inf"""
+    best, best_score = 0, -math.inf
+    for s, (lp, c) in enumerate(zip(sum_logprob.tolist(), count.tolist())):
+        score = float(lp) / float(c) ** float(length_penalty) if c > 0 else -math.inf
+        if score > best_score:
+            best, best_score = s, score
+    return best
+
+
+def _download_scored(tokens, sc, width: int):
+    """tokens int64 [R, width] (padded) and a generation.SampleScores -> CPU (tokens, token_logprob [R, width] padded with 0,
+    sum_logprob [R], count [R]) in ONE device-to-host copy: the rows are packed byte-wise side by side."""
+    R = tokens.shape[0]
+    tlp = torch.zeros((R, width), dtype=torch.float32, device=tokens.device)
+    w = min(width, sc.token_logprob.shape[1])
+    tlp[:, :w] = sc.token_logprob[:, :w]
+    parts = (tokens.contiguous(), tlp, sc.sum_logprob.view(R, 1), sc.count.view(R, 1))
+    packed = torch.cat([p.contiguous().view(torch.uint8).view(R, -1) for p in parts], dim=1).cpu()
+    out, at = [], 0
+    for p in parts:
+        nb = p.shape[1] * p.element_size()
+        out.append(packed[:, at:at + nb].contiguous().view(p.dtype).view(R, p.shape[1]))
+        at += nb
+    return out[0], out[1], out[2].view(R), out[3].view(R)
 
 
 def synthetic_gencls_model(shapes, kind: str, num_classes: int = 2, device="cuda", num_frames=None):

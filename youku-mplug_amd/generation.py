@@ -10,7 +10,8 @@ every sequence (prefill: the visual prefix + prompt; afterwards one token), atte
 runs the LM head on the last position only.  Beam re-ordering (swap_key_value_dict) is one strided row gather per
 layer into the twin buffer.  The search logic of the per-clip loops stays on the host, as in the reference; the lockstep
 search over a batch of clips (beam_search_batched_loop) keeps it on the device (ops.beam_advance, csrc/beam_search.hip), and so does
-sampled generation in lockstep (sample_batched_loop: ops.sample_advance, csrc/sampling.hip).  The lockstep loops can also keep
+sampled generation in lockstep (sample_batched_loop: ops.sample_advance, csrc/sampling.hip; with return_scores ops.sample_score,
+csrc/sample_score.hip, records every drawn token's log-probability).  The lockstep loops can also keep
 the positions all sequences of a clip share (visual prefix + prompt) once per clip: SharedPrefixDecodeState (kv="shared_prefix";
 mpv_gpt_decode_step_shared, csrc/decode_shared_attention.hip).
 """
@@ -324,11 +325,19 @@ def _gen_config(gpt):
 StepFn = Callable[[Optional[torch.Tensor], Optional[torch.Tensor]], torch.Tensor]
 
 
+def _no_sample_scores(return_scores, who):
+    if return_scores:
+        raise ValueError(f"return_scores=True needs the lockstep sampling loop (sample_batched / generate(sampler=\"device\")): {who} "
+                         "has no per-sample scores")
+
+
 def beam_search_loop(cfg, make_state: Callable[[int, int], object], tokens: torch.Tensor, query_embeds=None, beam_size=5,
-                     num_return_gen=1, stop_token=None, prompt_length=None, topk_fn=None):
+                     num_return_gen=1, stop_token=None, prompt_length=None, topk_fn=None, return_scores=False):
     """models/modeling_distributed_gpt3.py:1737-1873.  `make_state(batch, max_len)` returns an object with
     .step(tokens, query_embeds) -> logits [beams, V] and .reorder(batch_idx, shared_prefix=n); `topk_fn(logits, k, add)` ->
-    (values, indices) of log_softmax + add.  Both are injectable so the host logic can be driven from any logits source."""
+    (values, indices) of log_softmax + add.  Both are injectable so the host logic can be driven from any logits source.
+    return_scores=True is refused: the hypotheses carry their scores already (SampleScores belong to sample_batched_loop)."""
+    _no_sample_scores(return_scores, "beam_search_loop")
     assert tokens.size(0) == 1
     dev = tokens.device
     prompt_length = int(prompt_length) if prompt_length is not None else tokens.size(1)
@@ -422,7 +431,7 @@ class BeamState:
 
 def beam_search_batched_loop(cfg, make_state: Callable[[int, int], object], tokens: torch.Tensor, query_embeds=None, beam_size=5,
                              num_return_gen=1, stop_token=None, prompt_length: Optional[int] = None, topk_fn=None, advance_fn=None,
-                             constraints: Optional["LogitsConstraints"] = None, constrain_fn=None):
+                             constraints: Optional["LogitsConstraints"] = None, constrain_fn=None, return_scores=False):
     """beam_search_loop for B clips in lockstep: tokens [B, L], query_embeds [B, Q, H], ONE prompt length for all clips of the call.
     Every decode step advances B x beam_size sequences, so the decoder's weights are read once per generated position instead of
     once per clip and position, the prefill runs once per clip (state.prefill_fan_out) and the bookkeeping of a step is one kernel.
@@ -438,7 +447,9 @@ def beam_search_batched_loop(cfg, make_state: Callable[[int, int], object], toke
     `constraints` (a LogitsConstraints; None or inactive: no call and no launch is added): before topk_fn every step edits the raw
     logits of all B x beam_size rows -- the first step's and those of frozen clips too, which advance_fn ignores -- through
     constrain_fn (ops.logits_constrain) on the beams' token table, with the stop token as the termination id of min_new_tokens and
-    the lowest finite bf16 as the ban value (include/mpv.h says why it is not -inf here)."""
+    the lowest finite bf16 as the ban value (include/mpv.h says why it is not -inf here).
+    return_scores=True is refused, as in beam_search_loop."""
+    _no_sample_scores(return_scores, "beam_search_batched_loop")
     B, dev, K = tokens.size(0), tokens.device, int(beam_size)
     constraints = _active_constraints(constraints, constrain_fn)
     prompt_length = int(prompt_length) if prompt_length is not None else tokens.size(1)
@@ -531,8 +542,9 @@ def _active_constraints(constraints, constrain_fn):
 
 
 def sample_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None, temperature=1.0, use_eod_token_for_early_termination=True,
-                stop_on_double_eol=False, stop_on_eol=False, termination_id=None, prompt_length=None, generator=None):
-    """models/modeling_distributed_gpt3.py:1620-1735."""
+                stop_on_double_eol=False, stop_on_eol=False, termination_id=None, prompt_length=None, generator=None, return_scores=False):
+    """models/modeling_distributed_gpt3.py:1620-1735.  return_scores=True is refused: the scores are sample_batched_loop's."""
+    _no_sample_scores(return_scores, "sample_loop")
     B, dev = tokens.size(0), tokens.device
     lengths = prompt_length if prompt_length is not None else torch.tensor([tokens.size(1)], device=dev)
     lengths = torch.as_tensor(lengths, device=dev).view(-1)
@@ -588,9 +600,26 @@ class SampleState:
     ARRAYS = ("tokens", "prompt_len", "done", "next_tok", "stream", "n_done")
 
 
+class SampleScores:
+    """The sequence scores of sample_batched_loop for `rows` sequences, as device tensors (struct of arrays; the contract of
+    include/mpv.h: mpv_sample_score): live (1 until the row's terminating token has been scored), token_logprob (the model's
+    log-probability of every generated token up to and including the terminating one; 0 at prompt positions and behind the
+    termination), sum_logprob (their sum, added in position order) and count (their number)."""
+
+    def __init__(self, rows: int, row_len: int, device):
+        self.rows, self.row_len = int(rows), int(row_len)
+        self.live = torch.ones(self.rows, dtype=torch.int32, device=device)
+        self.token_logprob = torch.zeros((self.rows, self.row_len), dtype=torch.float32, device=device)
+        self.sum_logprob = torch.zeros(self.rows, dtype=torch.float32, device=device)
+        self.count = torch.zeros(self.rows, dtype=torch.int32, device=device)
+
+    ARRAYS = ("live", "token_logprob", "sum_logprob", "count")
+
+
 def sample_batched_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None, temperature=1.0, use_eod_token_for_early_termination=True,
                         stop_on_double_eol=False, stop_on_eol=False, termination_id=None, prompt_length=None, num_samples=1, seed=0,
-                        streams=None, advance_fn=None, constraints: Optional["LogitsConstraints"] = None, constrain_fn=None):
+                        streams=None, advance_fn=None, constraints: Optional["LogitsConstraints"] = None, constrain_fn=None,
+                        return_scores=False, score_fn=None):
     """sample_loop with the whole of a step's sampling and bookkeeping in one launch, for B clips x num_samples sequences in lockstep:
     tokens [B, L], query_embeds [B, Q, H], prompt_length [B] (ragged lengths are allowed) or None.  Sequence j belongs to clip
     j // num_samples.  The prefill runs once per clip over the shortest prompt (state.prefill_fan_out) and fans out to the clip's
@@ -603,10 +632,17 @@ def sample_batched_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None
     step, the prefill's included, edits the raw logits through constrain_fn (ops.logits_constrain) on st.tokens / st.prompt_len; rows
     still inside their prompt are left alone.  The termination ids of min_new_tokens are [termination_id], or [628, 198] under
     stop_on_eol; a banned logit is -inf, the sampler's "never drawn".  min_new_tokens with stop_on_double_eol is refused (a pair of
-    tokens ends the row there, which a per-token ban cannot express)."""
+    tokens ends the row there, which a per-token ban cannot express).
+    `return_scores` (default False: no call, no launch and no allocation is added, and the return value is the tensor alone): right
+    after advance_fn every step, the prefill's included, score_fn (ops.sample_score) records the model's log-probability of the token
+    just written, from the logits advance_fn read (the constrained ones) -- rows still inside their prompt and rows that terminated
+    in an earlier step are not scored; the terminating token is.  -> (tokens, scores): a SampleScores whose token_logprob is cut to
+    the columns of `tokens`.  The host still reads only the count of done rows."""
     B, dev, N = tokens.size(0), tokens.device, int(num_samples)
     if N < 1:
         raise ValueError(f"num_samples must be at least 1 (got {num_samples})")
+    if return_scores and score_fn is None:
+        raise ValueError("return_scores=True needs a score_fn (ops.sample_score)")
     constraints = _active_constraints(constraints, constrain_fn)
     if constraints is not None and constraints.min_new_tokens > 0 and stop_on_double_eol:
         raise ValueError(f"min_new_tokens ({constraints.min_new_tokens}) cannot be combined with stop_on_double_eol")
@@ -621,6 +657,7 @@ def sample_batched_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None
     R = B * N
     state = make_state(R, max_len + Q)
     st = SampleState(tokens.repeat_interleave(N, dim=0), lengths.repeat_interleave(N), streams=streams)
+    sc = SampleScores(R, st.row_len, dev) if return_scores else None
     termination_id = cfg.eod_id if termination_id is None else int(termination_id)
     mode = 2 if stop_on_double_eol else 1 if stop_on_eol else 0
     eos_ids = [628, 198] if mode else [termination_id]
@@ -636,8 +673,13 @@ def sample_batched_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None
                          ban_value=BAN_SAMPLING)
         advance_fn(logits, st, pos=context_length - Q, temperature=temperature, top_k=cfg.top_k, top_p=cfg.top_p, seed=seed,
                    vocab_size=cfg.vocab_size, termination_mode=mode, termination_id=termination_id)
+        if sc is not None:
+            score_fn(logits, st, sc, pos=context_length - Q)
         if use_eod_token_for_early_termination and int(st.n_done.item()) == R:       # the step's one host read: 4 bytes
             break
+    if sc is not None:
+        sc.token_logprob = sc.token_logprob[:, :context_length + 1]
+        return st.tokens[:, :context_length + 1], sc
     return st.tokens[:, :context_length + 1]      # (sic) as sample_loop
 
 
@@ -660,9 +702,11 @@ def install(gpt_cls):
     sample_batched."""
 
     def sample(self, tokens, query_embeds=None, temperature=1.0, **kw):
+        _no_sample_scores(kw.pop("return_scores", False), "sample")
         return sample_loop(_gen_config(self), make_state_fn(self), tokens, query_embeds=query_embeds, temperature=temperature, **kw)
 
     def beam_search(self, tokens, query_embeds=None, beam_size=5, num_return_gen=1, stop_token=None, **kw):
+        _no_sample_scores(kw.pop("return_scores", False), "beam_search")
         return beam_search_loop(_gen_config(self), make_state_fn(self), tokens, query_embeds=query_embeds, beam_size=beam_size,
                                 num_return_gen=num_return_gen, stop_token=stop_token, prompt_length=kw.pop("prompt_length", None),
                                 topk_fn=lambda lg, k, add: ops.logprob_topk(lg, k, add=add))
@@ -672,30 +716,33 @@ def install(gpt_cls):
         """beam_search for tokens [B, L] / query_embeds [B, Q, H] with one prompt length, B clips in lockstep -> a list of B results;
         kv="shared_prefix" keeps the visual prefix and the prompt once per clip (SharedPrefixDecodeState); constraints: a
         LogitsConstraints, applied on the device every step"""
+        _no_sample_scores(kw.pop("return_scores", False), "beam_search_batched")
         return beam_search_batched_loop(_gen_config(self), make_state_fn(self, kv), tokens, query_embeds=query_embeds, beam_size=beam_size,
                                         num_return_gen=num_return_gen, stop_token=stop_token, prompt_length=kw.pop("prompt_length", None),
                                         topk_fn=lambda lg, k, add: ops.logprob_topk(lg, k, add=add), advance_fn=ops.beam_advance,
                                         constraints=constraints, constrain_fn=ops.logits_constrain)
 
     def sample_batched(self, tokens, query_embeds=None, temperature=1.0, num_samples=1, seed=0, streams=None, top_k=None, top_p=None,
-                       kv="per_sequence", constraints=None, **kw):
+                       kv="per_sequence", constraints=None, return_scores=False, **kw):
         """sample with the sampler on the device (sample_batched_loop): tokens [B, L] -> [B * num_samples, n]; top_k / top_p override
         the configuration's values; the draws are those of (seed, position, streams[row]) -- not torch's generator;
         kv="shared_prefix" keeps the visual prefix and the shortest prompt once per clip (SharedPrefixDecodeState); constraints: a
-        LogitsConstraints, applied on the device every step"""
+        LogitsConstraints, applied on the device every step; return_scores=True: -> (tokens, SampleScores), the model's
+        log-probability of every generated token, recorded on the device every step (ops.sample_score)"""
         make_state = make_state_fn(self, kv)
         cfg = _gen_config(self)
         if top_k is not None or top_p is not None:
             cfg.top_k, cfg.top_p = int(top_k or 0), float(top_p or 0.0)
         return sample_batched_loop(cfg, make_state, tokens, query_embeds=query_embeds, temperature=temperature, num_samples=num_samples,
                                    seed=seed, streams=streams, advance_fn=ops.sample_advance, constraints=constraints,
-                                   constrain_fn=ops.logits_constrain, **kw)
+                                   constrain_fn=ops.logits_constrain, **(dict(return_scores=True, score_fn=ops.sample_score) if return_scores else {}),
+                                   **kw)
 
     @torch.no_grad()
     def generate(self, tokens, do_sample=True, termination_id=None, *args, **kw):                # :1875-1880
         """sampler="device" (keyword; not in the reference, default "torch"): do_sample=True runs sample_batched, which takes
         kv="per_sequence" | "shared_prefix" (the per-clip loops keep a cache per sequence) and constraints= (a LogitsConstraints; the
-        per-clip loops have none)"""
+        per-clip loops have none) and return_scores=True (-> (tokens, SampleScores); refused everywhere else)"""
         sampler = kw.pop("sampler", "torch")
         if sampler not in ("torch", "device"):
             raise ValueError(f"sampler must be 'torch' or 'device' (got {sampler!r})")
@@ -705,6 +752,8 @@ def install(gpt_cls):
             raise ValueError('kv="shared_prefix" needs a lockstep loop: do_sample=True with sampler="device", or beam_search_batched')
         if not (do_sample and sampler == "device") and kw.pop("constraints", None) is not None:
             raise ValueError('constraints need a lockstep loop: do_sample=True with sampler="device", or beam_search_batched')
+        if not (do_sample and sampler == "device"):
+            _no_sample_scores(kw.pop("return_scores", False), "generate without do_sample=True and sampler=\"device\"")
         was = self.training
         self.eval()
         try:

@@ -721,6 +721,30 @@ def logits_constrain(logits, tokens, *, pos, constraints, prompt_len=None, promp
     return logits
 
 
+def sample_score(logits, st, sc, *, pos, vocab=None, ld=None):
+    """The model's log-probability of the token sample_advance has just written into st.tokens[:, pos], for st.rows sequences in one
+    launch on the current stream (include/mpv.h: mpv_sample_score; st is the loop's generation.SampleState, sc a
+    generation.SampleScores): log_softmax of logits bf16 [rows, ld] (the first `vocab` columns, what sample_advance read), into
+    sc.token_logprob[:, pos], sc.sum_logprob and sc.count.  Rows with st.prompt_len > pos and rows whose sc.live is 0 are skipped;
+    sc.live follows st.done.  -> sc"""
+    _need_cuda(logits, st.tokens, sc.token_logprob)
+    if logits.dtype != torch.bfloat16 or logits.ndim != 2 or logits.shape[0] < st.rows or logits.stride(1) != 1:
+        raise _lib.MpvError(f"sample_score: logits must be bf16 [{st.rows}, ld] with unit column stride (got {logits.dtype} {tuple(logits.shape)})")
+    if sc.rows != st.rows or sc.row_len != st.row_len:
+        raise _lib.MpvError(f"sample_score: scores of [{sc.rows}, {sc.row_len}] for a state of [{st.rows}, {st.row_len}]")
+    for name, t, dt, shape in (("live", sc.live, torch.int32, (st.rows,)), ("token_logprob", sc.token_logprob, torch.float32, (st.rows, st.row_len)),
+                               ("sum_logprob", sc.sum_logprob, torch.float32, (st.rows,)), ("count", sc.count, torch.int32, (st.rows,))):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != logits.device:
+            raise _lib.MpvError(f"sample_score: {name} must be contiguous {dt} {list(shape)} on {logits.device}")
+    d = _lib.SampleScoreDesc()
+    d.logits, d.tokens, d.prompt_len, d.done = _p(logits), _p(st.tokens), _p(st.prompt_len), _p(st.done)
+    d.live, d.token_logprob, d.sum_logprob, d.count = _p(sc.live), _p(sc.token_logprob), _p(sc.sum_logprob), _p(sc.count)
+    d.ld = int(ld) if ld is not None else logits.stride(0)
+    d.rows, d.vocab, d.row_len, d.pos = st.rows, int(vocab) if vocab is not None else logits.shape[-1], st.row_len, int(pos)
+    check(_lib.lib().mpv_sample_score(C.byref(d), _stream()), "mpv_sample_score")
+    return sc
+
+
 def sample_tokens(logits, *, temperature=1.0, top_k=0, top_p=0.0, seed=0, streams=None, vocab_size=None, vocab=None):
     """One-off draw: -> int64 [rows], the token sample_advance draws at pos 0 for every row of logits bf16 [rows, ld] (no prompt, no
     termination; vary `seed` or `streams` for another draw)."""
