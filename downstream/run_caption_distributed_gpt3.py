@@ -22,6 +22,10 @@ What this entry point adds to downstream/finetune_common.py:
     instead of the beam search's (`model.generate(..., do_sample=True, num_samples=N, best_of=True)`: the model's log-probability per
     token, recorded on the device while sampling), written as "pred_caption" through the same result path, so the metrics below run
     on it; it combines with `--eval_shared_kv` and the constraint flags;
+  * `--eval_score_gold` (not in the reference, default off): evaluation also scores every clip's `gold_caption` list, teacher-forced,
+    against the query features computed once for that clip (`model.score_captions(..., query_features=)`: one packed pass per batch,
+    no padding rows), adds "gold_logprob" / "gold_tokens" lists to the result entries and logs the corpus per-token NLL and perplexity;
+    it combines with every flag above, and without it the run is the one described above;
   * save_result (dataset/utils.py:114-160): one JSON per rank, merged by rank 0; cal_metric (:240-298): predictions and references
     reduced to their CJK characters, one token per character, scored by pycocoevalcap's COCOEvalCap when that package is importable.
     It is not on this image: then BLEU-1..4 (corpus level, closest-reference brevity penalty) and ROUGE-L (beta 1.2, best reference)
@@ -51,11 +55,12 @@ def make_training_batch(video, text, prompt, tokenizer, device, max_length):
 
 @torch.no_grad()
 def evaluation(model, data_loader, tokenizer, device, config, batched=False, clips_per_search=32, eval_sample=0, seed=0, shared_kv=False,
-               constraints=None, best_of=0):
+               constraints=None, best_of=0, score_gold=False, max_length=None):
     """-> [{video_id, pred_caption, gold_caption}] (:208-238); batched: `--eval_batched_beam`; eval_sample: `--eval_sample`;
     shared_kv: `--eval_shared_kv`, constraints: the keywords of `--eval_repetition_penalty` / `--eval_no_repeat_ngram` /
     `--eval_min_new_tokens` (the lockstep calls only); best_of: `--eval_sample_best_of` (the prediction is the best of that many
-    samples instead of the beam search's)"""
+    samples instead of the beam search's); score_gold: `--eval_score_gold` (the clip's query features are computed once and serve the
+    generation and the scoring of its gold captions, tokenized as the training pairs are, at most max_length tokens)"""
     module = getattr(model, "module", model)
     module.eval()
     kvkw = {"kv_cache": "shared_prefix"} if shared_kv else {}                # flag absent: the calls below are unchanged
@@ -65,11 +70,15 @@ def evaluation(model, data_loader, tokenizer, device, config, batched=False, cli
         video = video.to(device, non_blocking=True).bfloat16()
         text = [config["prompt"] for _ in range(video.shape[0])]
         text_input = tokenizer(text, padding="max_length", truncation=True, max_length=20, return_tensors="pt").to(device)
+        qkw = {}                                                                 # flag absent: the calls below are unchanged
+        if score_gold:
+            qf = module.encode_video(video)
+            qkw = {"query_features": qf}
         if best_of:
             res = module.generate(video, text_input, do_sample=True, num_samples=best_of, best_of=True, seed=seed + n,
-                                  clips_per_search=clips_per_search, **kvkw)
+                                  clips_per_search=clips_per_search, **kvkw, **qkw)
         else:
-            res = module.generate(video, text_input, batched=True, clips_per_search=clips_per_search, **kvkw) if batched else module.generate(video, text_input)
+            res = module.generate(video, text_input, batched=True, clips_per_search=clips_per_search, **kvkw, **qkw) if batched else module.generate(video, text_input, **qkw)
         def caption(ids):
             ans = tokenizer.decode(ids).replace(" ", "").strip()
             return ans.split(config["prompt"])[-1].strip() if config["prompt"] != "" else ans
@@ -77,12 +86,41 @@ def evaluation(model, data_loader, tokenizer, device, config, batched=False, cli
             result.append({"video_id": video_id, "pred_caption": caption(r.tolist()[0]), "gold_caption": list(gold)})
         if eval_sample:
             sampled = module.generate(video, text_input, do_sample=True, num_samples=eval_sample, seed=seed + n, clips_per_search=clips_per_search,
-                                      **kvkw)
+                                      **kvkw, **qkw)
             for rec, rows in zip(result[-len(sampled):], sampled):
                 rec["sampled_captions"] = [caption(row) for row in rows.tolist()]
+        if score_gold:
+            scores = module.score_captions(None, text_input, [gold_tokens(tokenizer, config["prompt"], g, max_length) for g in gold_caption],
+                                           query_features=qf, clips_per_pass=clips_per_search)
+            for rec, sc in zip(result[-len(scores):], scores):
+                rec["gold_logprob"] = [float(x) for x in sc["sum_logprob"].tolist()]
+                rec["gold_tokens"] = [int(x) for x in sc["count"].tolist()]
         if n == 0:
             print(result)
     return result
+
+
+def gold_tokens(tokenizer, prompt, captions, max_length):
+    """the caption tokens of a clip's gold captions as the training pairs hold them ([prompt, caption] -> bos + prompt + caption + eos,
+    make_training_batch): what lies between the prompt and the closing eos"""
+    if not len(captions):
+        return []
+    enc = tokenizer([[prompt, c] for c in captions], padding="max_length", truncation=True, max_length=max_length, return_tensors="pt")
+    eos = tokenizer.tokenizer.eos
+    out = []
+    for row, mask, pl in zip(enc["input_ids"].tolist(), enc["attention_mask"].tolist(), enc["prompt_lengths"].tolist()):
+        n = sum(mask)
+        end = n - 1 if n > 0 and row[n - 1] == eos else n
+        out.append(row[1 + int(pl):end])
+    return out
+
+
+def gold_perplexity(result):
+    """corpus per-token NLL and perplexity of the gold captions of `--eval_score_gold` result entries (terminators included)"""
+    lp = sum(x for r in result for x in r.get("gold_logprob", []))
+    nt = sum(x for r in result for x in r.get("gold_tokens", []))
+    nll = -lp / max(nt, 1)
+    return {"gold_nll": nll, "gold_ppl": math.exp(min(nll, 700.0)), "gold_scored_tokens": nt}
 
 
 def save_result(result, result_dir, filename):
@@ -229,8 +267,12 @@ def main(args, config):
         result = evaluation(s.model, val_loader, s.tokenizer, s.device, config, batched=getattr(args, "eval_batched_beam", False),
                             clips_per_search=getattr(args, "clips_per_search", 32), eval_sample=getattr(args, "eval_sample", 0),
                             seed=getattr(args, "seed", 0) or 0, shared_kv=getattr(args, "eval_shared_kv", False),
-                            constraints=constraint_keywords(args), best_of=getattr(args, "eval_sample_best_of", 0))
-        val_stats = cal_metric(save_result(result, args.result_dir, "val_caption_result"))
+                            constraints=constraint_keywords(args), best_of=getattr(args, "eval_sample_best_of", 0),
+                            **({"score_gold": True, "max_length": args.max_length} if getattr(args, "eval_score_gold", False) else {}))
+        final = save_result(result, args.result_dir, "val_caption_result")
+        val_stats = cal_metric(final)
+        if getattr(args, "eval_score_gold", False):
+            val_stats = {**val_stats, **gold_perplexity(json.load(open(final, "r")))}        # the merged file: every rank's clips
         print("* Validation Stats:", val_stats)
         log_stats = {**{f"val_{k}": v for k, v in val_stats.items()}, "n_parameters": s.n_parameters}
         ft.write_log(args, log_stats)
@@ -274,6 +316,9 @@ def get_args(argv=None):
         p.add_argument("--eval_sample_best_of", type=int, default=0,
                        help="evaluation: the caption of a clip is the most likely of N sampled ones, not the beam search's "
                             "(model.generate(do_sample=True, num_samples=N, best_of=True)); 0 = off")
+        p.add_argument("--eval_score_gold", action="store_true", default=False,
+                       help="evaluation: also score every clip's gold captions against its query features (model.score_captions): "
+                            "gold_logprob / gold_tokens in the result file, per-token NLL and perplexity in the log")
     args, config = ft.get_args(argv, extra=extra)
     if args.eval_sample_best_of < 0:
         raise ValueError(f"--eval_sample_best_of must not be negative (got {args.eval_sample_best_of})")

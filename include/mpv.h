@@ -222,6 +222,40 @@ typedef struct mpv_attn_prefix_desc {
 } mpv_attn_prefix_desc;
 int mpv_attn_prefix_fwd(const mpv_attn_prefix_desc* d, mpv_stream_t stream);
 
+/* The same attention for PACKED, ragged continuations (scoring given captions: reference captions have a few to 40 tokens each and
+ * every clip its own number of them).  All continuation rows lie end to end in one [rows] array, the continuations of one group
+ * next to each other, so a group is one contiguous row range: packed row r, head h, element d of q/k/v/o at X + r*x_rs + h*x_hs +
+ * d; element (g,h,j,d) of pk/pv at X + g*x_gs + h*x_hs + j*x_rs + d as above (NULL allowed when prefix_len == 0).
+ *   seg_start (device, int32 [rows])          packed index of the first row of the continuation row r belongs to, seg_start[r] <= r
+ *   group_row (device, int32 [n_groups + 1])  group g owns rows group_row[g] .. group_row[g+1]-1; group_row[0] == 0,
+ *                                             group_row[n_groups] == rows; a continuation never spans two groups
+ *   max_group_rows (host)                     the largest group's row count: it sizes the grid, nothing is read back from the device
+ * Query row r attends to the prefix_len prefix keys of its group and to its own keys kr with seg_start[r] <= kr <= r: ONE softmax
+ * over both sets, fp32 scores and statistics, probabilities rounded to bf16 for the PV product, no dropout, o bf16.  Nothing but
+ * o[0 .. rows) is written and nothing behind row `rows` is read.  A row's output is a function of its group's prefix and of its own
+ * continuation only, bit for bit (masked keys have probability exactly 0 and stay out of the running max).
+ * Refused with a negative code before any launch: NULL pointers; head_dim not 64 or 80; rows, n_groups or heads < 1; prefix_len <
+ * 0; max_group_rows outside [1, rows]; rows >= 2^30, n_groups > 65535 or heads > 65535 (the grid's y / z limits: MPV_E_SHAPE, "problem
+ * too large", as mpv_attn_prefix_fwd); q/k/v/pk/pv rows not 16-byte or o rows not 8-byte aligned; scale <= 0.  The contents of the
+ * two index arrays are the caller's promise: build them with mpv_attn_prefix_packed_layout. */
+typedef struct mpv_attn_prefix_packed_desc {
+  const void *q, *k, *v;     /* packed continuation rows */
+  const void *pk, *pv;       /* prefixes (may be NULL when prefix_len == 0) */
+  void* o;
+  const int32_t *seg_start, *group_row;
+  int64_t q_rs, q_hs, k_rs, k_hs, v_rs, v_hs, o_rs, o_hs;
+  int64_t pk_gs, pk_hs, pk_rs, pv_gs, pv_hs, pv_rs;
+  int rows, n_groups, heads, prefix_len, head_dim, max_group_rows;
+  float scale;
+} mpv_attn_prefix_packed_desc;
+int mpv_attn_prefix_packed_fwd(const mpv_attn_prefix_packed_desc* d, mpv_stream_t stream);
+/* Host only (no device needed): the two index arrays of the packed layout from the continuation lengths cont_len[n_cont] and the
+ * number of continuations of every group conts_per_group[n_groups], in packed order.  seg_start_out has room for sum(cont_len)
+ * entries, group_row_out for n_groups + 1.  Refused (MPV_E_SHAPE): a length < 1, a group without a continuation, counts that do not
+ * sum to n_cont, 2^30 rows or more. */
+int mpv_attn_prefix_packed_layout(const int32_t* cont_len, int n_cont, const int32_t* conts_per_group, int n_groups,
+                                  int32_t* seg_start_out, int32_t* group_row_out, int* rows_out, int* max_group_rows_out);
+
 /* One decode step's attention for sequences that share a per-group prefix KV cache (lockstep beam search / sampling: the K
  * beams or samples of a clip share the visual prefix and the prompt).  n_seq sequences in groups of group_size consecutive
  * ones: sequence s belongs to group s / group_size (n_groups = ceil(n_seq / group_size); the last group may be short).  Every
@@ -360,6 +394,13 @@ int mpv_caption_targets(const int64_t* ids, const int64_t* attention_mask, const
  * dropout (models/distributed_gpt3.py:155-156; models/modeling_distributed_gpt3.py:640-666). */
 int mpv_gpt_embed_fwd(const void* query, const int64_t* ids, const void* wte, const void* wpe, void* h, int B,
                       int Q, int L, int H, float dropout_p, uint64_t seed, uint64_t offset, mpv_stream_t stream);
+/* Packed rows of the same front in evaluation (no dropout, no query rows): out[r,:] = wte[ids[r],:] + wpe[pos[r],:], one bf16
+ * rounding as above.  ids int64 [rows], pos int32 [rows] (device); wpe has max_positions rows and 0 <= pos[r] < max_positions is the
+ * caller's promise (the host knows the positions and checks them: ops.gpt_embed_rows_fwd).  The kernel keeps that promise from
+ * becoming a read outside wpe: a position outside the table reads its nearest row instead.  Refused: rows < 1, H not a multiple of
+ * 8, max_positions < 1, NULL pointers. */
+int mpv_gpt_embed_rows_fwd(const int64_t* ids, const int32_t* pos, const void* wte, const void* wpe, void* out, int rows, int H,
+                           int max_positions, mpv_stream_t stream);
 /* dquery[b,q,:] = dh[b,q,:] * keepmask/(1-p) */
 int mpv_gpt_embed_bwd(const void* dh, void* dquery, int B, int Q, int L, int H, float dropout_p, uint64_t seed,
                       uint64_t offset, mpv_stream_t stream);

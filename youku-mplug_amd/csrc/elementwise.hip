@@ -304,6 +304,19 @@ __global__ void gpt_embed_fwd_kernel(const bf16* __restrict__ query, const int64
     *(bf16x8*)(h + row * H + c8 * 8) = cvt8(v);
   }
 }
+// packed rows of the evaluation front: out[r] = wte[ids[r]] + wpe[pos[r]] (the rounding of gpt_embed_fwd_kernel without dropout)
+__global__ void gpt_embed_rows_fwd_kernel(const int64_t* __restrict__ ids, const int32_t* __restrict__ pos, const bf16* __restrict__ wte,
+                                          const bf16* __restrict__ wpe, bf16* __restrict__ out, int rows, int H, int max_positions) {
+  const int H8 = H / 8;
+  const long long total = (long long)rows * H8;
+  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+    const int c8 = (int)(idx % H8);
+    const long long row = idx / H8;
+    const f32x8 v = cvt8(*(const bf16x8*)(wte + ids[row] * (long long)H + c8 * 8)) +
+                    cvt8(*(const bf16x8*)(wpe + (long long)min(max(pos[row], 0), max_positions - 1) * H + c8 * 8));   // never outside wpe
+    *(bf16x8*)(out + row * H + c8 * 8) = cvt8(v);
+  }
+}
 __global__ void gpt_embed_bwd_kernel(const bf16* __restrict__ dh, bf16* __restrict__ dquery, int B, int Q, int L, int H,
                                      float drop_scale, uint32_t thr, uint64_t seed, uint64_t offset) {
   const int H8 = H / 8, S = Q + L;
@@ -839,6 +852,17 @@ extern "C" int mpv_gpt_embed_fwd(const void* query, const int64_t* ids, const vo
                      (const bf16*)wpe, (bf16*)h, B, Q, L, H, 1.0f / (1.0f - dropout_p),
                      dropout_p > 0.f ? mpv_drop_threshold(dropout_p) : 0u, seed, offset);
   return mpv_check_launch("mpv_gpt_embed_fwd");
+}
+
+extern "C" int mpv_gpt_embed_rows_fwd(const int64_t* ids, const int32_t* pos, const void* wte, const void* wpe, void* out, int rows,
+                                      int H, int max_positions, hipStream_t stream) {
+  MPV_REQUIRE(ids && pos && wte && wpe && out, MPV_E_ARG, "mpv_gpt_embed_rows_fwd: null pointer");
+  MPV_REQUIRE(rows >= 1 && H > 0 && H % 8 == 0 && max_positions >= 1, MPV_E_SHAPE,
+              "mpv_gpt_embed_rows_fwd: bad shape (rows %d, H %d, max_positions %d)", rows, H, max_positions);
+  const long long total = (long long)rows * (H / 8);
+  hipLaunchKernelGGL(gpt_embed_rows_fwd_kernel, dim3(ew_grid(total)), dim3(256), 0, stream, ids, pos, (const bf16*)wte,
+                     (const bf16*)wpe, (bf16*)out, rows, H, max_positions);
+  return mpv_check_launch("mpv_gpt_embed_rows_fwd");
 }
 
 extern "C" int mpv_gpt_embed_bwd(const void* dh, void* dquery, int B, int Q, int L, int H, float dropout_p, uint64_t seed,

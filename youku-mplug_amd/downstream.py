@@ -333,7 +333,8 @@ class DistributedGPT3_Caption(_GenCls):
     @torch.no_grad()
     def generate(self, image, text, termination_id=None, batched=False, clips_per_search=32, do_sample=False, num_samples=1, temperature=1.0,
                  top_k=None, top_p=None, seed=0, kv_cache="per_sequence", repetition_penalty=None, no_repeat_ngram_size=0, min_new_tokens=0,
-                 banned_token_ids=None, constrain_prompt=False, return_scores=False, best_of=False, length_penalty=1.0, **kw):
+                 banned_token_ids=None, constrain_prompt=False, return_scores=False, best_of=False, length_penalty=1.0, query_features=None,
+                 **kw):
         """One beam search per sample (:790-809): prompt = text.input_ids[i, :mask.sum()-1], prefix = its query features.
         batched=True (not in the reference, default off): the clips are grouped by prompt length and every group is searched in
         lockstep, `clips_per_search` clips at a time (generation.beam_search_batched_loop: the decoder's weights are read once per
@@ -371,13 +372,15 @@ class DistributedGPT3_Caption(_GenCls):
         ([1], [1], [1, Lt]) and `index`, its number.
         A clip's TOKENS stay independent of clips_per_search and of its neighbours.  Its SCORES are bit-identical only at an equal row
         count: the decode step's GEMM dispatch depends on the number of rows (DESIGN.md sections 13, 17, 18), which moves the logits in
-        their last bf16 digit.  A near-tie in best_of may therefore resolve differently under another chunking."""
-        Bv = image.shape[0]
+        their last bf16 digit.  A near-tie in best_of may therefore resolve differently under another chunking.
+        query_features (default None: computed from `image` here): the clips' encode_video() output, for a caller that also needs it
+        elsewhere (score_captions); `image` is then not consulted."""
         Q, Hh = self.num_learnable_token, self.text_width
+        Bv = image.shape[0] if query_features is None else query_features.shape[0] // Q
         was = self.training
         self.eval()
         try:
-            qf = self._query_features(image, {"vit": {}, "pool": {}}).view(Bv, Q, Hh)
+            qf = (self._query_features(image, {"vit": {}, "pool": {}}) if query_features is None else query_features).view(Bv, Q, Hh)
             if termination_id is None:
                 tok = getattr(self, "tokenizer", None)
                 termination_id = tok.tokenizer.eos if tok is not None else None
@@ -460,6 +463,107 @@ class DistributedGPT3_Caption(_GenCls):
                 out = self.text_decoder.generate(text.input_ids[i:i + 1], query_embeds=qf[i:i + 1], termination_id=termination_id,
                                                  do_sample=False, prompt_length=int(text.attention_mask.sum(-1)[i]) - 1, **kw)
                 res.append(out.sequences.cpu())
+            return res
+        finally:
+            self.train(was)
+
+
+    @torch.no_grad()
+    def score_captions(self, image, text, candidates, *, query_features=None, termination_id=None, score_termination=True,
+                       clips_per_pass=32, length_penalty=1.0):
+        """The model's log-likelihood of GIVEN captions (not in the reference): per-token NLL / perplexity of reference captions,
+        ranking of candidate answers, re-scoring of captions from elsewhere.  text: the prompts as in generate (the prompt of clip i is
+        text.input_ids[i, :mask.sum()-1]; at least one token); candidates[i]: a list, possibly empty, of caption token sequences for
+        clip i (1-D int64 tensors or lists; caption tokens only: no prompt, no terminator, no padding).  Pass exactly one of image and
+        query_features (encode_video's output: many candidate sets can be scored against one ViT pass).
+        The clips are grouped by prompt length and chunked by clips_per_pass as generate does.  Per chunk: one prefix pass over the
+        query slots and prompt[:-1] (text_decoder.forward_prefix), then ONE packed continuation pass (forward_continuation_packed,
+        ops.attn_prefix_packed_fwd) in which candidate c is the rows [last prompt token, c_0 .. c_{n-1}] with the targets [c_0 ..
+        c_{n-1}, termination]: the candidates lie end to end at their own lengths, so no padding row goes through the decoder or the
+        LM head.  score_termination=False drops the last row (the terminator is not scored; an empty candidate is then an error).  One
+        download per chunk; a candidate's sum is taken on the host in fp64, in position order, and stored as fp32.
+        -> one dict per clip, in input order, of CPU tensors shaped like generate(..., return_scores=True)'s entries: sum_logprob [C_i]
+        fp32, count [C_i] int32, token_logprob [C_i, Lmax_i] fp32 (zero-padded behind each candidate's count), and best =
+        best_sample(sum_logprob, count, length_penalty), None for a clip without candidates.  The quantity is the one SampleScores
+        records: the log-probability of every token up to and including the terminating one, from the raw logits, without constraints.
+        A candidate's scores are bit-identical only at an equal row count of the pass: the GEMM dispatch depends on the number of rows
+        (DESIGN.md sections 13, 17, 18, 20), which moves the logits in their last bf16 digit -- as for generate's scores."""
+        if (image is None) == (query_features is None):
+            raise ValueError("pass exactly one of image / query_features")
+        if int(clips_per_pass) < 1:
+            raise ValueError(f"clips_per_pass must be at least 1 (got {clips_per_pass})")
+        Q, Hh = self.num_learnable_token, self.text_width
+        ids_all, mask = text.input_ids, text.attention_mask
+        n = ids_all.shape[0]
+        if len(candidates) != n:
+            raise ValueError(f"{len(candidates)} candidate lists for {n} clips")
+        lengths = (mask.sum(-1) - 1).tolist()
+        if any(pl < 1 for pl in lengths):
+            raise ValueError(f"every clip needs a prompt of at least one token (prompt lengths {lengths})")
+        cands = [[[int(t) for t in (c.tolist() if torch.is_tensor(c) else c)] for c in cl] for cl in candidates]
+        if not score_termination and any(len(c) == 0 for cl in cands for c in cl):
+            raise ValueError("an empty candidate has nothing to score with score_termination=False")
+        was = self.training
+        self.eval()
+        try:
+            qf = self._query_features(image, {"vit": {}, "pool": {}}) if query_features is None else query_features
+            if qf.shape[0] != n * Q:
+                raise ValueError(f"query features of {qf.shape[0] / Q:g} clips ({qf.shape[0]} rows of Q = {Q}) for {n} prompts")
+            qf = qf.view(n, Q, Hh)
+            if termination_id is None:
+                tok = getattr(self, "tokenizer", None)
+                termination_id = tok.tokenizer.eos if tok is not None else None
+            if termination_id is None:
+                from . import generation
+                termination_id = generation._gen_config(self.text_decoder).eod_id
+            term = int(termination_id)
+            host_ids = ids_all.tolist()                                          # the prompts' last tokens, on the host
+            res = [None] * n
+            for i in range(n):
+                if not cands[i]:
+                    res[i] = dict(sum_logprob=torch.zeros(0, dtype=torch.float32), count=torch.zeros(0, dtype=torch.int32),
+                                  token_logprob=torch.zeros((0, 0), dtype=torch.float32), best=None)
+            for pl in sorted(set(lengths)):
+                group = [i for i in range(n) if lengths[i] == pl]
+                for c0 in range(0, len(group), int(clips_per_pass)):
+                    clips = [i for i in group[c0:c0 + int(clips_per_pass)] if cands[i]]
+                    if not clips:
+                        continue
+                    rows_in, rows_tgt, cont_len = [], [], []
+                    for i in clips:
+                        for c in cands[i]:
+                            seq_in, seq_tgt = [host_ids[i][pl - 1]] + c, c + [term]
+                            if not score_termination:
+                                seq_in, seq_tgt = seq_in[:-1], seq_tgt[:-1]
+                            rows_in += seq_in
+                            rows_tgt += seq_tgt
+                            cont_len.append(len(seq_in))
+                    dev = qf.device
+                    layout = ops.PackedLayout(cont_len, [len(cands[i]) for i in clips], device=dev)
+                    sel = torch.as_tensor(clips, dtype=torch.long, device=dev)
+                    prefix = self.text_decoder.forward_prefix(qf[sel].reshape(-1, Hh).contiguous(), ids_all[sel, :pl - 1].contiguous())
+                    both = torch.tensor([rows_in, rows_tgt], dtype=torch.long).to(dev)                       # one upload
+                    out = self.text_decoder.forward_continuation_packed(prefix, both[0], layout, labels=both[1])
+                    tlp = out["token_logprob"].cpu()                                                          # the chunk's one download
+                    at, k = 0, 0
+                    for i in clips:
+                        C_i = len(cands[i])
+                        lens = cont_len[k:k + C_i]
+                        table = torch.zeros((C_i, max(lens)), dtype=torch.float32)
+                        sums = []
+                        for j, ln in enumerate(lens):
+                            row = tlp[at:at + ln]
+                            table[j, :ln] = row
+                            acc = 0.0
+                            for x in row.tolist():                               # fp64, in position order
+                                acc += x
+                            sums.append(acc)
+                            at += ln
+                        k += C_i
+                        entry = dict(sum_logprob=torch.tensor(sums, dtype=torch.float64).to(torch.float32),
+                                     count=torch.tensor(lens, dtype=torch.int32), token_logprob=table)
+                        entry["best"] = best_sample(entry["sum_logprob"], entry["count"], length_penalty)
+                        res[i] = entry
             return res
         finally:
             self.train(was)

@@ -364,6 +364,27 @@ class DistributedGPT3(nn.Module):
                                 P, hn, scale=scale)
             return ctx
 
+        xf = self._continuation_layers(h, R, attention)
+        out = {}
+        if loss_rows is not None and loss_rows.numel() > 0:
+            nr = loss_rows.numel()
+            xs = ops.gather_rows(xf, loss_rows.contiguous(), nr, H)
+            logits = ops.gemm(xs, lm.embedding.word_embeddings.weight, nr, V, H)      # tied LM head (:1348-1350), scored rows only
+            ones = torch.ones(nr, dtype=torch.float32, device=xf.device)
+            out["losses"], _ = ops.cross_entropy(logits, labels.contiguous().view(-1), ones, nr, V)
+        elif loss_rows is not None:
+            out["losses"] = torch.zeros(0, dtype=torch.float32, device=xf.device)
+        if hidden_rows is not None:
+            out["hidden"] = ops.gather_rows(xf, hidden_rows.contiguous(), hidden_rows.numel(), H)
+        return out
+
+    def _continuation_layers(self, h, R, attention):
+        """The layer stack of a continuation pass on the R embedded rows h (forward_continuation: [n_cont * Lc, H]; forward_continuation_
+        packed: the packed rows), in whichever residual-stream mode forward_lm runs; attention(qkv, li) -> ctx [R, H] is the pass's
+        own attention against [prefix | own causal] keys.  -> the final LayerNorm's output [R, H]."""
+        cfg = self.config
+        lm = self.dist_model.language_model
+        H = cfg.hidden_size
         if FP32_STREAM:
             stream, pending = h, None
             for li, layer in enumerate(lm.encoder.layers):
@@ -392,18 +413,45 @@ class DistributedGPT3(nn.Module):
                 h = ops.gemm(g, mlp.dense_4h_to_h.weight, R, H, F4, bias=mlp.dense_4h_to_h.bias, residual=h1)
             fl = lm.encoder.final_layernorm
             xf, _, _ = ops.layernorm_fwd(h, fl.weight, fl.bias, fl.eps, R, H, want_stats=False)
-        out = {}
-        if loss_rows is not None and loss_rows.numel() > 0:
-            nr = loss_rows.numel()
-            xs = ops.gather_rows(xf, loss_rows.contiguous(), nr, H)
-            logits = ops.gemm(xs, lm.embedding.word_embeddings.weight, nr, V, H)      # tied LM head (:1348-1350), scored rows only
-            ones = torch.ones(nr, dtype=torch.float32, device=xf.device)
-            out["losses"], _ = ops.cross_entropy(logits, labels.contiguous().view(-1), ones, nr, V)
-        elif loss_rows is not None:
-            out["losses"] = torch.zeros(0, dtype=torch.float32, device=xf.device)
-        if hidden_rows is not None:
-            out["hidden"] = ops.gather_rows(xf, hidden_rows.contiguous(), hidden_rows.numel(), H)
-        return out
+        return xf
+
+    @torch.no_grad()
+    def forward_continuation_packed(self, prefix: dict, ids: torch.Tensor, layout, *, labels: torch.Tensor) -> dict:
+        """The packed twin of forward_continuation: ids int64 [rows] are the rows of ragged continuations laid end to end as `layout`
+        (an ops.PackedLayout with its device arrays) says -- continuation c has layout.cont_len[c] rows, group g (the prefix sequence g
+        of forward_prefix) layout.conts_per_group[g] consecutive continuations -- so no padding row exists anywhere in the pass.
+        Packed row r sits at absolute position P + (r - seg_start[r]).  Per layer the kernel sequence of forward_continuation on
+        [rows, H], with the attention of ops.attn_prefix_packed_fwd; the tied LM head runs on ALL rows (every packed row is a scored
+        row) and labels int64 [rows] are their targets.  -> dict(token_logprob fp32 [rows]): log softmax(logits[r])[labels[r]], the
+        negated per-row loss of mpv_cross_entropy."""
+        assert not self.training, "shared-prefix scoring is an evaluation path (no dropout)"
+        cfg = self.config
+        lm = self.dist_model.language_model
+        P, ng = prefix["P"], prefix["B"]
+        R = layout.rows
+        assert ids.numel() == R and labels.numel() == R and layout.n_groups == ng, \
+            f"{ids.numel()} ids / {labels.numel()} labels for {R} packed rows; {layout.n_groups} groups for {ng} prefixes"
+        H, np_, hn, V = cfg.hidden_size, cfg.num_attention_heads, cfg.kv_channels, cfg.vocab_size
+        wpe = lm.embedding.position_embeddings.weight
+        pos_host = [P + i for i in layout.pos_in_cont]
+        pos = (torch.arange(R, dtype=torch.int32, device=ids.device) - layout.seg_start) + P
+        h = ops.gpt_embed_rows_fwd(ids.contiguous(), pos, pos_host, lm.embedding.word_embeddings.weight, wpe, R, H)   # checks pos_host
+        st = ((3 * H, 3 * hn),) * 3 + ((H, hn),)
+        pst = (P * 3 * H, 3 * hn, 3 * H)
+        scale = 1.0 / math.sqrt(hn)
+
+        def attention(qkv, li):
+            ctx = torch.empty((R, H), dtype=torch.bfloat16, device=h.device)
+            pq = prefix["qkv"][li]
+            ops.attn_prefix_packed_fwd(qkv, qkv[:, hn:], qkv[:, 2 * hn:], pq[:, hn:], pq[:, 2 * hn:], ctx, st, (pst, pst), layout, np_, P,
+                                       hn, scale=scale)
+            return ctx
+
+        xf = self._continuation_layers(h, R, attention)
+        logits = ops.gemm(xf, lm.embedding.word_embeddings.weight, R, V, H)      # tied LM head (:1348-1350), every packed row
+        ones = torch.ones(R, dtype=torch.float32, device=xf.device)
+        losses, _ = ops.cross_entropy(logits, labels.contiguous().view(-1), ones, R, V)
+        return dict(token_logprob=-losses)
 
     def _layers_bf16_stream(self, h, lay, scale, window, layers, seed, p_h, p_a, B, S, R, H, np_, hn, keep_inputs=False):
         """The layer stack with the reference's bf16 residual stream (residual adds in the GEMM epilogues): MPV_DECODER_STREAM=bf16,

@@ -302,6 +302,54 @@ def attn_prefix_fwd(q, k, v, pk, pv, o, lay: AttnLayout, prefix_lay: Tuple[Tuple
     return o
 
 
+class PackedLayout:
+    """The packed layout of ragged continuations (include/mpv.h: mpv_attn_prefix_packed_layout), built once per pass: cont_len[c] rows
+    for continuation c, conts_per_group[g] consecutive continuations for group g.  Host side: cont_len, conts_per_group, seg_start_host,
+    group_row_host, rows, max_group_rows and pos_in_cont[r] = r - seg_start[r]; with a device, the two index arrays as int32 device
+    tensors seg_start and group_row (two views of one upload; None without a device)."""
+
+    def __init__(self, cont_len, conts_per_group, device=None):
+        self.cont_len = [int(x) for x in cont_len]
+        self.conts_per_group = [int(x) for x in conts_per_group]
+        nc, ng = len(self.cont_len), len(self.conts_per_group)
+        cl = (C.c_int32 * max(nc, 1))(*self.cont_len)
+        cg = (C.c_int32 * max(ng, 1))(*self.conts_per_group)
+        total = sum(self.cont_len)
+        # the function validates before it writes: what it will refuse (a length < 1, 2^30 rows or more) gets no buffer to speak of
+        seg = (C.c_int32 * (total if nc and min(self.cont_len) >= 1 and total < (1 << 30) else 1))()
+        grp = (C.c_int32 * (ng + 1))()
+        rows, mgr = C.c_int(0), C.c_int(0)
+        check(_lib.lib().mpv_attn_prefix_packed_layout(cl, nc, cg, ng, seg, grp, C.byref(rows), C.byref(mgr)),
+              "mpv_attn_prefix_packed_layout")
+        self.rows, self.max_group_rows, self.n_groups, self.n_cont = rows.value, mgr.value, ng, nc
+        self.seg_start_host = list(seg[:self.rows])
+        self.group_row_host = list(grp)
+        self.pos_in_cont = [r - s for r, s in enumerate(self.seg_start_host)]
+        self.seg_start = self.group_row = None
+        if device is not None:
+            both = torch.tensor(self.seg_start_host + self.group_row_host, dtype=torch.int32).to(device)      # one copy
+            self.seg_start, self.group_row = both[:self.rows], both[self.rows:]
+
+
+def attn_prefix_packed_fwd(q, k, v, pk, pv, o, row_strides, prefix_lay: Tuple[Tuple[int, int, int], Tuple[int, int, int]],
+                           layout: PackedLayout, heads, prefix_len, hd, *, scale=1.0):
+    """Causal attention of the packed, ragged continuations of `layout` (packed row r of q/k/v/o strided (row, head) by row_strides
+    = (q, k, v, o) pairs) against the prefix_len-row prefix of their group (pk/pv strided (group, head, row) by prefix_lay = (k
+    strides, v strides)): query row r sees every prefix key of its group and its own keys seg_start[r] <= kr <= r.
+    include/mpv.h: mpv_attn_prefix_packed_fwd."""
+    _need_cuda(q, k, v, o, pk, pv, layout.seg_start, layout.group_row)
+    d = _lib.AttnPrefixPackedDesc()
+    d.q, d.k, d.v, d.o = q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr()
+    d.pk, d.pv = (_p(pk), _p(pv)) if prefix_len > 0 else (None, None)      # no prefix: nothing of pk / pv is read
+    d.seg_start, d.group_row = _p(layout.seg_start), _p(layout.group_row)
+    (d.q_rs, d.q_hs), (d.k_rs, d.k_hs), (d.v_rs, d.v_hs), (d.o_rs, d.o_hs) = row_strides
+    (d.pk_gs, d.pk_hs, d.pk_rs), (d.pv_gs, d.pv_hs, d.pv_rs) = prefix_lay
+    d.rows, d.n_groups, d.max_group_rows = layout.rows, layout.n_groups, layout.max_group_rows
+    d.heads, d.prefix_len, d.head_dim, d.scale = heads, prefix_len, hd, scale
+    check(_lib.lib().mpv_attn_prefix_packed_fwd(C.byref(d), _stream()), "mpv_attn_prefix_packed_fwd")
+    return o
+
+
 def attn_decode_shared_fwd(q, k, v, pk, pv, o, lay: AttnLayout, prefix_lay: Tuple[Tuple[int, int, int], Tuple[int, int, int]], n_seq,
                            group_size, heads, prefix_len, own_len, hd, *, scale=1.0):
     """One decode step's attention of n_seq sequences (ONE query row each; q/k/v/o strided (sequence, head, row) by `lay`, the row
@@ -506,6 +554,20 @@ def gpt_embed_fwd(query, ids, wte, wpe, B, Q, L, H, dropout_p=0.0, seed=0, offse
     check(_lib.lib().mpv_gpt_embed_fwd(_p(query), ids.data_ptr(), wte.data_ptr(), wpe.data_ptr(), h.data_ptr(), B, Q, L, H,
                                        dropout_p, seed, offset, _stream()), "mpv_gpt_embed_fwd")
     return h
+
+
+def gpt_embed_rows_fwd(ids, pos, pos_host, wte, wpe, rows, H):
+    """out[r] = wte[ids[r]] + wpe[pos[r]] for packed rows (ids int64 [rows], pos int32 [rows] on the device; include/mpv.h:
+    mpv_gpt_embed_rows_fwd).  pos_host: the same positions as a host list -- they are checked against wpe here, without a sync."""
+    if len(pos_host) != rows or min(pos_host) < 0:
+        raise _lib.MpvError(f"{len(pos_host)} host positions (smallest {min(pos_host, default=0)}) for {rows} rows")
+    if max(pos_host) >= wpe.shape[0]:      # nn.Embedding would raise on the position ids
+        raise _lib.MpvError(f"sequence of {max(pos_host) + 1} positions exceeds max_position_embeddings = {wpe.shape[0]}")
+    _need_cuda(ids, pos, wte, wpe)
+    out = torch.empty((rows, H), dtype=torch.bfloat16, device=wte.device)
+    check(_lib.lib().mpv_gpt_embed_rows_fwd(ids.data_ptr(), pos.data_ptr(), wte.data_ptr(), wpe.data_ptr(), out.data_ptr(), rows, H,
+                                            wpe.shape[0], _stream()), "mpv_gpt_embed_rows_fwd")
+    return out
 
 
 def gpt_embed_bwd_full(dh, rows, H, dropout_p=0.0, seed=0, offset=0):
