@@ -22,6 +22,11 @@ What this entry point adds to downstream/finetune_common.py:
     instead of the beam search's (`model.generate(..., do_sample=True, num_samples=N, best_of=True)`: the model's log-probability per
     token, recorded on the device while sampling), written as "pred_caption" through the same result path, so the metrics below run
     on it; it combines with `--eval_shared_kv` and the constraint flags;
+  * `--eval_beam_groups G` with `--eval_diversity_penalty F` (not in the reference, default 1 = off): diverse (group) beam search in
+    lockstep, G groups of min(5, 16 // G) beams each, a later group penalised by F for every token an earlier group chose at the same
+    step (`model.generate(..., batched=True, beam_groups=G, diversity_penalty=F, rerank_by_logprob=True)`); every hypothesis of every
+    group is re-scored by the model's own log-probability per token: "pred_caption" is the best, "pred_candidates" lists all of them in
+    that order; it implies the batched path and combines with `--eval_shared_kv` and the constraint flags;
   * `--eval_score_gold` (not in the reference, default off): evaluation also scores every clip's `gold_caption` list, teacher-forced,
     against the query features computed once for that clip (`model.score_captions(..., query_features=)`: one packed pass per batch,
     no padding rows), adds "gold_logprob" / "gold_tokens" lists to the result entries and logs the corpus per-token NLL and perplexity;
@@ -55,12 +60,14 @@ def make_training_batch(video, text, prompt, tokenizer, device, max_length):
 
 @torch.no_grad()
 def evaluation(model, data_loader, tokenizer, device, config, batched=False, clips_per_search=32, eval_sample=0, seed=0, shared_kv=False,
-               constraints=None, best_of=0, score_gold=False, max_length=None):
+               constraints=None, best_of=0, score_gold=False, max_length=None, beam_groups=1, diversity_penalty=0.0):
     """-> [{video_id, pred_caption, gold_caption}] (:208-238); batched: `--eval_batched_beam`; eval_sample: `--eval_sample`;
     shared_kv: `--eval_shared_kv`, constraints: the keywords of `--eval_repetition_penalty` / `--eval_no_repeat_ngram` /
     `--eval_min_new_tokens` (the lockstep calls only); best_of: `--eval_sample_best_of` (the prediction is the best of that many
     samples instead of the beam search's); score_gold: `--eval_score_gold` (the clip's query features are computed once and serve the
-    generation and the scoring of its gold captions, tokenized as the training pairs are, at most max_length tokens)"""
+    generation and the scoring of its gold captions, tokenized as the training pairs are, at most max_length tokens); beam_groups /
+    diversity_penalty: `--eval_beam_groups` / `--eval_diversity_penalty` (the prediction is the most likely hypothesis of a diverse beam
+    search, all of them in "pred_candidates")"""
     module = getattr(model, "module", model)
     module.eval()
     kvkw = {"kv_cache": "shared_prefix"} if shared_kv else {}                # flag absent: the calls below are unchanged
@@ -74,7 +81,14 @@ def evaluation(model, data_loader, tokenizer, device, config, batched=False, cli
         if score_gold:
             qf = module.encode_video(video)
             qkw = {"query_features": qf}
-        if best_of:
+        candidates = None
+        if beam_groups > 1:
+            per_group = min(5, 16 // beam_groups)
+            candidates, _ = module.generate(video, text_input, batched=True, clips_per_search=clips_per_search, beam_groups=beam_groups,
+                                            diversity_penalty=diversity_penalty, beam_size=per_group, num_return_gen=beam_groups * per_group,
+                                            rerank_by_logprob=True, **kvkw, **qkw)
+            res = [c[:1] for c in candidates]
+        elif best_of:
             res = module.generate(video, text_input, do_sample=True, num_samples=best_of, best_of=True, seed=seed + n,
                                   clips_per_search=clips_per_search, **kvkw, **qkw)
         else:
@@ -84,6 +98,9 @@ def evaluation(model, data_loader, tokenizer, device, config, batched=False, cli
             return ans.split(config["prompt"])[-1].strip() if config["prompt"] != "" else ans
         for video_id, r, gold in zip(video_ids, res, gold_caption):
             result.append({"video_id": video_id, "pred_caption": caption(r.tolist()[0]), "gold_caption": list(gold)})
+        if candidates is not None:
+            for rec, rows in zip(result[-len(candidates):], candidates):
+                rec["pred_candidates"] = [caption(row) for row in rows.tolist()]
         if eval_sample:
             sampled = module.generate(video, text_input, do_sample=True, num_samples=eval_sample, seed=seed + n, clips_per_search=clips_per_search,
                                       **kvkw, **qkw)
@@ -268,6 +285,8 @@ def main(args, config):
                             clips_per_search=getattr(args, "clips_per_search", 32), eval_sample=getattr(args, "eval_sample", 0),
                             seed=getattr(args, "seed", 0) or 0, shared_kv=getattr(args, "eval_shared_kv", False),
                             constraints=constraint_keywords(args), best_of=getattr(args, "eval_sample_best_of", 0),
+                            **({"beam_groups": args.eval_beam_groups, "diversity_penalty": args.eval_diversity_penalty}
+                               if getattr(args, "eval_beam_groups", 1) > 1 else {}),
                             **({"score_gold": True, "max_length": args.max_length} if getattr(args, "eval_score_gold", False) else {}))
         final = save_result(result, args.result_dir, "val_caption_result")
         val_stats = cal_metric(final)
@@ -289,7 +308,8 @@ def constraint_keywords(args):
         kw["no_repeat_ngram_size"] = args.eval_no_repeat_ngram
     if getattr(args, "eval_min_new_tokens", 0):
         kw["min_new_tokens"] = args.eval_min_new_tokens
-    if kw and not (getattr(args, "eval_batched_beam", False) or getattr(args, "eval_sample", 0) or getattr(args, "eval_sample_best_of", 0)):
+    if kw and not (getattr(args, "eval_batched_beam", False) or getattr(args, "eval_sample", 0) or getattr(args, "eval_sample_best_of", 0) or
+                   getattr(args, "eval_beam_groups", 1) > 1):
         raise ValueError(f"--eval_repetition_penalty / --eval_no_repeat_ngram / --eval_min_new_tokens ({kw}) need --eval_batched_beam or "
                          "--eval_sample (or --eval_sample_best_of): the per-clip beam search has no constraints")
     return kw
@@ -316,12 +336,25 @@ def get_args(argv=None):
         p.add_argument("--eval_sample_best_of", type=int, default=0,
                        help="evaluation: the caption of a clip is the most likely of N sampled ones, not the beam search's "
                             "(model.generate(do_sample=True, num_samples=N, best_of=True)); 0 = off")
+        p.add_argument("--eval_beam_groups", type=int, default=1,
+                       help="evaluation: diverse beam search in lockstep, G groups of min(5, 16 // G) beams, the hypotheses re-ranked by the "
+                            "model's log-probability per token (model.generate(batched=True, beam_groups=G, rerank_by_logprob=True)); 1 = off")
+        p.add_argument("--eval_diversity_penalty", type=float, default=0.0,
+                       help="--eval_beam_groups: what a later group pays for a token an earlier group chose at the same step "
+                            "(model.generate(diversity_penalty=F))")
         p.add_argument("--eval_score_gold", action="store_true", default=False,
                        help="evaluation: also score every clip's gold captions against its query features (model.score_captions): "
                             "gold_logprob / gold_tokens in the result file, per-token NLL and perplexity in the log")
     args, config = ft.get_args(argv, extra=extra)
     if args.eval_sample_best_of < 0:
         raise ValueError(f"--eval_sample_best_of must not be negative (got {args.eval_sample_best_of})")
+    if not 1 <= args.eval_beam_groups <= 8:
+        raise ValueError(f"--eval_beam_groups must be in [1, 8] (got {args.eval_beam_groups})")
+    if not (math.isfinite(args.eval_diversity_penalty) and args.eval_diversity_penalty >= 0) or \
+            (args.eval_diversity_penalty and args.eval_beam_groups == 1):
+        raise ValueError(f"--eval_diversity_penalty must be finite, not negative and needs --eval_beam_groups above 1 (got {args.eval_diversity_penalty})")
+    if args.eval_beam_groups > 1 and args.eval_sample_best_of:
+        raise ValueError("--eval_beam_groups and --eval_sample_best_of both choose the prediction: pass one of them")
     constraint_keywords(args)                                               # refuses the flags without a lockstep mode
     config.setdefault("prompt", "")
     args.result_dir = os.path.join(args.output_dir, "result")

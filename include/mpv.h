@@ -520,6 +520,55 @@ typedef struct mpv_beam_advance_desc {
 } mpv_beam_advance_desc;
 int mpv_beam_advance(const mpv_beam_advance_desc* d, mpv_stream_t stream);
 /* ------------------------------------------------------------------------------------------
+ * Diverse (group) beam search in lockstep (generation.beam_search_batched_loop with beam_groups > 1; Vijayakumar et al., "Diverse
+ * Beam Search"): ONE launch advances `batch` clips x `groups` (G) groups x `beams` (K', the beams PER GROUP) by one position.  A
+ * (clip, group) pair is a clip of mpv_beam_advance: every state array is the one described there with batch * G pseudo-clips,
+ * pseudo-clip b*G + g being group g of clip b -- tokens_in / tokens_out int64 [batch][G][K'][row_len], scores fp32 [batch][G][K'],
+ * hyp_score fp64 / hyp_order int32 [batch][G][K'], hyp_tokens int64 [batch][G][K'][row_len], hyp_count / hyp_next int32, worst
+ * fp64 and done int32 [batch][G]; src_row / next_tok int64 [batch*G*K'].
+ * Input: cand_val fp32 / cand_idx int64 [batch*G*K'][m] with m = 2K' + (G-1)K' -- what mpv_logprob_topk writes for k = m with
+ *   add = scores -- and pos, cur_len, first, stop_token as in mpv_beam_advance; diversity_penalty (lambda, fp32).
+ * Per clip the groups are processed in the order g = 0 .. G-1:
+ *   A group whose done flag is set is frozen exactly as a done clip of mpv_beam_advance: rows copied to tokens_out, identity
+ *   src_row, the stop token, nothing else written; it contributes nothing to the groups after it.
+ *   Otherwise let c(t) be the number of next beams emitted in THIS call by the groups < g of this clip whose new token is t: only
+ *   real next-beam slots count (not a slot left over with the stop token), a frozen group and one that becomes done in this call
+ *   do not count, and two beams with the same token count twice.  Every candidate value v becomes v' = v - lambda * c(token), two
+ *   separately rounded fp32 operations (fp32 product, then fp32 difference: no contraction); with c = 0, v' is v bit for bit.
+ *   Group g then runs exactly one iteration of mpv_beam_advance's contract on its K' beams with the values v': order by v'
+ *   descending, then (beam in group) * vocab + token ascending, the first 2K' walked; the stop token at rank >= K' skipped, at
+ *   rank < K' added to the group's store with the score double(v') / row_len; eviction and worst as there; done test count == K'
+ *   && worst >= double(best v') / cur_len; `first` reads beam 0 of the group only.  scores receive the penalised values v' (the
+ *   usual definition): from the second group on the search score is not a model likelihood.  src_row = row0 + source beam with
+ *   row0 the first row of the (clip, group): it never leaves the group, so it feeds the KV re-order as it is.
+ * The definition is over the whole vocabulary: with every row's full log-probability vector penalised and sorted the result is the
+ *   same, because at most (G-1)K' distinct tokens are penalised, lambda >= 0 and the rounding is monotone, so a row's penalised
+ *   first 2K' lie inside its unpenalised first 2K' + (G-1)K' under the common tie rule, lower token first.
+ * With groups = 1 every state array and output equals mpv_beam_advance's on the same input, bit for bit, whatever lambda is.
+ * Limits: beams in [1, 8], groups in [1, 8], groups * beams <= 16, diversity_penalty finite and >= 0, and everything
+ *   mpv_beam_advance refuses (row_len in [1, 2048], 0 <= pos < row_len, batch / vocab / cur_len >= 1, a NULL pointer, tokens_in ==
+ *   tokens_out); a descriptor outside them is refused with a negative code before any launch, the outputs untouched.
+ * One wave per clip, the clip's groups one after the other inside it, the tokens of the earlier groups in LDS; no atomics; a
+ *   clip's result depends neither on `batch` nor on its place in it. */
+typedef struct mpv_beam_advance_groups_desc {
+  const float* cand_val;
+  const int64_t* cand_idx;
+  const int64_t* tokens_in;
+  int64_t* tokens_out;
+  float* scores;
+  double* hyp_score;
+  int32_t* hyp_order;
+  int64_t* hyp_tokens;
+  int32_t *hyp_count, *hyp_next;
+  double* worst;
+  int32_t* done;
+  int64_t *src_row, *next_tok;
+  int batch, beams, row_len, vocab, pos, cur_len, first, groups;
+  float diversity_penalty;
+  int64_t stop_token;
+} mpv_beam_advance_groups_desc;
+int mpv_beam_advance_groups(const mpv_beam_advance_groups_desc* d, mpv_stream_t stream);
+/* ------------------------------------------------------------------------------------------
  * Sampled generation in lockstep (generation.sample_batched_loop): ONE launch draws the next token of `rows` sequences and does the
  * bookkeeping of one iteration of the reference's sample loop (models/modeling_distributed_gpt3.py:1689-1728).  The filters follow
  * :1369-1441; the tie order that the reference leaves to an unstable sort is fixed here.  One sampling step of row r:

@@ -108,6 +108,13 @@ class BeamAdvanceDesc(C.Structure):
                [(n, c_int) for n in ("batch", "beams", "row_len", "vocab", "pos", "cur_len", "first")] + [("stop_token", c_int64)]
 
 
+class BeamAdvanceGroupsDesc(C.Structure):
+    _fields_ = [(n, c_void_p) for n in ("cand_val", "cand_idx", "tokens_in", "tokens_out", "scores", "hyp_score", "hyp_order", "hyp_tokens",
+                                        "hyp_count", "hyp_next", "worst", "done", "src_row", "next_tok")] + \
+               [(n, c_int) for n in ("batch", "beams", "row_len", "vocab", "pos", "cur_len", "first", "groups")] + \
+               [("diversity_penalty", c_float), ("stop_token", c_int64)]
+
+
 class SampleAdvanceDesc(C.Structure):
     _fields_ = [(n, c_void_p) for n in ("logits", "stream_id", "u_override", "prompt_len", "tokens", "done", "next_tok", "n_done", "out_kept",
                                         "out_mass", "out_token")] + \
@@ -207,6 +214,7 @@ _SIGS = {
     "mpv_logprob_topk_workspace_size": (c_size_t, [c_int64, c_int]),
     "mpv_logprob_topk": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mpv_beam_advance": (c_int, [C.POINTER(BeamAdvanceDesc), c_void_p]),
+    "mpv_beam_advance_groups": (c_int, [C.POINTER(BeamAdvanceGroupsDesc), c_void_p]),
     "mpv_sample_advance": (c_int, [C.POINTER(SampleAdvanceDesc), c_void_p]),
     "mpv_logits_constrain": (c_int, [C.POINTER(LogitsConstrainDesc), c_void_p]),
     "mpv_sample_score": (c_int, [C.POINTER(SampleScoreDesc), c_void_p]),

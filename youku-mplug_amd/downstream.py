@@ -334,7 +334,7 @@ class DistributedGPT3_Caption(_GenCls):
     def generate(self, image, text, termination_id=None, batched=False, clips_per_search=32, do_sample=False, num_samples=1, temperature=1.0,
                  top_k=None, top_p=None, seed=0, kv_cache="per_sequence", repetition_penalty=None, no_repeat_ngram_size=0, min_new_tokens=0,
                  banned_token_ids=None, constrain_prompt=False, return_scores=False, best_of=False, length_penalty=1.0, query_features=None,
-                 **kw):
+                 beam_groups=1, diversity_penalty=0.0, rerank_by_logprob=False, **kw):
         """One beam search per sample (:790-809): prompt = text.input_ids[i, :mask.sum()-1], prefix = its query features.
         batched=True (not in the reference, default off): the clips are grouped by prompt length and every group is searched in
         lockstep, `clips_per_search` clips at a time (generation.beam_search_batched_loop: the decoder's weights are read once per
@@ -374,8 +374,27 @@ class DistributedGPT3_Caption(_GenCls):
         count: the decode step's GEMM dispatch depends on the number of rows (DESIGN.md sections 13, 17, 18), which moves the logits in
         their last bf16 digit.  A near-tie in best_of may therefore resolve differently under another chunking.
         query_features (default None: computed from `image` here): the clips' encode_video() output, for a caller that also needs it
-        elsewhere (score_captions); `image` is then not consulted."""
+        elsewhere (score_captions); `image` is then not consulted.
+        beam_groups = G > 1 (batched=True only; default 1): diverse (group) beam search -- `beam_size` beams PER GROUP, G * beam_size at
+        most 16, a later group penalised by diversity_penalty for every beam of an earlier group that chose the same token at the same
+        step (generation.beam_search_batched_loop, ops.beam_advance_groups).  -> per clip one [n, Lt] tensor, n <= num_return_gen (a
+        multiple of G): group 0's best num_return_gen // G rows first, then group 1's, ...  It combines with kv_cache and the constraints.
+        rerank_by_logprob=True (batched=True only; default off): -> (res, scores).  Each clip's n candidates -- the tokens between the
+        prompt and the first termination token, possibly none -- are scored by score_captions on this call's query features (no second
+        ViT pass; a beam's search score is length-normalised over the whole row and, in a later group, penalised: it is no likelihood),
+        and the clip's rows are reordered by sum_logprob / count ** length_penalty descending, ties in search order: row 0 is
+        best_sample's choice.  A hypothesis that fills its row without a termination token is scored whole, terminator included: one
+        position more than the search fed, at most the LAST row of the position table (the search generates up to column final_len - 1
+        and never feeds it; the scoring does) -- never outside it.  scores[i] is score_captions' dict in the new order (best = 0) plus group [n] int64, the group every row
+        came from (zeros without groups)."""
         Q, Hh = self.num_learnable_token, self.text_width
+        G = int(beam_groups)
+        if G != 1 and (do_sample or not batched):
+            raise ValueError(f"beam_groups={beam_groups!r} needs batched=True without do_sample: the per-clip search and the samplers have no groups")
+        if rerank_by_logprob and (do_sample or not batched):
+            raise ValueError("rerank_by_logprob needs batched=True without do_sample (sampled captions: best_of=True)")
+        if G != 1:
+            kw = dict(kw, beam_groups=G, diversity_penalty=diversity_penalty)      # absent keyword: the calls below are today's
         Bv = image.shape[0] if query_features is None else query_features.shape[0] // Q
         was = self.training
         self.eval()
@@ -449,6 +468,7 @@ class DistributedGPT3_Caption(_GenCls):
                     raise ValueError(f"clips_per_search must be at least 1 (got {clips_per_search})")
                 lengths = (text.attention_mask.sum(-1) - 1).tolist()
                 res = [None] * n
+                groups_of = [None] * n
                 for pl in sorted(set(lengths)):
                     group = [i for i in range(n) if lengths[i] == pl]
                     for c in range(0, len(group), int(clips_per_search)):
@@ -457,7 +477,26 @@ class DistributedGPT3_Caption(_GenCls):
                                                                      stop_token=termination_id, prompt_length=int(pl), **kw)
                         for i, out in zip(sel.tolist(), outs):
                             res[i] = out.sequences.cpu()
-                return res
+                            groups_of[i] = getattr(out, "group", None)
+                if not rerank_by_logprob:
+                    return res
+                term = generation._gen_config(self.text_decoder).eod_id if termination_id is None else int(termination_id)
+                cands = []
+                for i in range(n):
+                    rows = res[i][:, lengths[i]:].tolist()
+                    cands.append([row[:row.index(term)] if term in row else row for row in rows])
+                scores = self.score_captions(None, text, cands, query_features=qf.reshape(Bv * Q, Hh), termination_id=term,
+                                             clips_per_pass=clips_per_search, length_penalty=length_penalty)
+                for i in range(n):
+                    sc = scores[i]
+                    norm = [float(lp) / float(c) ** float(length_penalty) if c > 0 else -math.inf
+                            for lp, c in zip(sc["sum_logprob"].tolist(), sc["count"].tolist())]
+                    order = sorted(range(len(norm)), key=lambda s: -norm[s])             # stable: ties keep the search order
+                    grp = groups_of[i] if groups_of[i] is not None else torch.zeros(len(norm), dtype=torch.int64)
+                    res[i] = res[i][order]
+                    scores[i] = dict(sum_logprob=sc["sum_logprob"][order], count=sc["count"][order], token_logprob=sc["token_logprob"][order],
+                                     group=grp[order], best=0)
+                return res, scores
             res = []
             for i in range(n):
                 out = self.text_decoder.generate(text.input_ids[i:i + 1], query_embeds=qf[i:i + 1], termination_id=termination_id,

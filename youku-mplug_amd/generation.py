@@ -431,7 +431,8 @@ class BeamState:
 
 def beam_search_batched_loop(cfg, make_state: Callable[[int, int], object], tokens: torch.Tensor, query_embeds=None, beam_size=5,
                              num_return_gen=1, stop_token=None, prompt_length: Optional[int] = None, topk_fn=None, advance_fn=None,
-                             constraints: Optional["LogitsConstraints"] = None, constrain_fn=None, return_scores=False):
+                             constraints: Optional["LogitsConstraints"] = None, constrain_fn=None, return_scores=False, beam_groups=1,
+                             diversity_penalty=0.0, group_advance_fn=None):
     """beam_search_loop for B clips in lockstep: tokens [B, L], query_embeds [B, Q, H], ONE prompt length for all clips of the call.
     Every decode step advances B x beam_size sequences, so the decoder's weights are read once per generated position instead of
     once per clip and position, the prefill runs once per clip (state.prefill_fan_out) and the bookkeeping of a step is one kernel.
@@ -448,9 +449,31 @@ def beam_search_batched_loop(cfg, make_state: Callable[[int, int], object], toke
     logits of all B x beam_size rows -- the first step's and those of frozen clips too, which advance_fn ignores -- through
     constrain_fn (ops.logits_constrain) on the beams' token table, with the stop token as the termination id of min_new_tokens and
     the lowest finite bf16 as the ban value (include/mpv.h says why it is not -inf here).
-    return_scores=True is refused, as in beam_search_loop."""
+    return_scores=True is refused, as in beam_search_loop.
+    beam_groups = G > 1 (default 1: the calls above, nothing added): diverse (group) beam search.  beam_size is then K', the beams PER
+    GROUP; the state holds B x G x K' sequences, a (clip, group) pair being a clip of the BeamState; the prefill fans out to G * K'; a
+    step asks topk_fn for m = 2K' + (G-1)K' candidates per row and calls group_advance_fn (ops.beam_advance_groups: per clip, group
+    after group, one iteration on the values lowered by diversity_penalty times the number of next beams that the groups before chose
+    with the candidate's token at this step).  The re-order stays inside the (clip, group), so both KV states work as they are.  The
+    host finish is the one above, per (clip, group): -> per clip a namespace (sequences [n, Lt], scores [n], group [n] int64), group
+    0's best r = num_return_gen // G rows first, then group 1's, ...; a group with fewer hypotheses yields fewer rows.  From the second
+    group on the scores are penalised search scores, not model likelihoods.  num_return_gen must be a multiple of G with r <= K'."""
     _no_sample_scores(return_scores, "beam_search_batched_loop")
     B, dev, K = tokens.size(0), tokens.device, int(beam_size)
+    G = int(beam_groups)
+    if G != 1:
+        if G < 1 or isinstance(beam_groups, bool):
+            raise ValueError(f"beam_groups must be a positive integer (got {beam_groups!r})")
+        lam = float(diversity_penalty)
+        if not (math.isfinite(lam) and lam >= 0.0):
+            raise ValueError(f"diversity_penalty must be finite and not negative (got {diversity_penalty!r})")
+        if int(num_return_gen) % G or int(num_return_gen) // G > K or int(num_return_gen) < G:
+            raise ValueError(f"num_return_gen ({num_return_gen}) must be a multiple of beam_groups ({G}) with at most beam_size ({K}) "
+                             "rows per group")
+        if group_advance_fn is None:
+            raise ValueError("beam_groups > 1 needs a group_advance_fn (ops.beam_advance_groups)")
+        return _beam_search_groups_loop(cfg, make_state, tokens, query_embeds, K, G, lam, int(num_return_gen) // G, stop_token, prompt_length,
+                                        topk_fn, group_advance_fn, _active_constraints(constraints, constrain_fn), constrain_fn)
     constraints = _active_constraints(constraints, constrain_fn)
     prompt_length = int(prompt_length) if prompt_length is not None else tokens.size(1)
     stop_token = cfg.eod_id if stop_token is None else int(stop_token)
@@ -478,17 +501,65 @@ def beam_search_batched_loop(cfg, make_state: Callable[[int, int], object], toke
     h = SimpleNamespace(**{k: getattr(bs, k).cpu() for k in BeamState.ARRAYS})              # one download
     out = []
     for b in range(B):
-        hyp = BeamHypotheses(K)
-        for s in sorted(range(int(h.hyp_count[b])), key=lambda s: int(h.hyp_order[b, s])):  # insertion order
-            hyp.beams.append((float(h.hyp_score[b, s]), h.hyp_tokens[b, s].clone(), None))
-        hyp.worst_score = float(h.worst[b])
-        if not bool(h.done[b]):
-            for k in range(K):
-                hyp.add(h.tokens[b, k].clone(), float(h.scores[b, k]))
-        ranked = sorted(hyp.beams, key=lambda x: x[0], reverse=True)
+        ranked = _ranked_hypotheses(h, b, K)
         n_ret = min(num_return_gen, len(ranked))
         out.append(SimpleNamespace(sequences=torch.stack([ranked[i][1] for i in range(n_ret)], dim=0).to(dev),
                                    scores=torch.tensor([ranked[i][0] for i in range(n_ret)], dtype=torch.float32)))
+    return out
+
+
+def _ranked_hypotheses(h, b, K):
+    """the host finish of the lockstep searches for pseudo-clip b of the downloaded BeamState arrays `h`: its stored hypotheses in
+    insertion order, the final flush of its K beams unless it is done, and the stable ranking -- as beam_search_loop ends"""
+    hyp = BeamHypotheses(K)
+    for s in sorted(range(int(h.hyp_count[b])), key=lambda s: int(h.hyp_order[b, s])):      # insertion order
+        hyp.beams.append((float(h.hyp_score[b, s]), h.hyp_tokens[b, s].clone(), None))
+    hyp.worst_score = float(h.worst[b])
+    if not bool(h.done[b]):
+        for k in range(K):
+            hyp.add(h.tokens[b, k].clone(), float(h.scores[b, k]))
+    return sorted(hyp.beams, key=lambda x: x[0], reverse=True)
+
+
+def _beam_search_groups_loop(cfg, make_state, tokens, query_embeds, K, G, lam, per_group, stop_token, prompt_length, topk_fn, advance_fn,
+                             constraints, constrain_fn):
+    """beam_search_batched_loop with beam_groups = G > 1 (its docstring has the contract): the same loop over B * G pseudo-clips"""
+    B, dev = tokens.size(0), tokens.device
+    prompt_length = int(prompt_length) if prompt_length is not None else tokens.size(1)
+    stop_token = cfg.eod_id if stop_token is None else int(stop_token)
+    tokens = torch.cat((tokens, torch.full((B, cfg.tokens_to_generate), stop_token, dtype=torch.long, device=dev)), dim=-1)
+    final_len = min(tokens.size(1), cfg.max_position_embeddings)
+    if prompt_length >= final_len:
+        raise ValueError("context length + tokens_to_generate too large")
+    Q = 0 if query_embeds is None else query_embeds.size(1)
+    state = make_state(B * G * K, final_len + Q)
+    bs = BeamState(tokens.repeat_interleave(G, 0), K)                                      # pseudo-clip b * G + g: group g of clip b
+    total_prompt, total_final, m = prompt_length + Q, final_len + Q, 2 * K + (G - 1) * K
+    for n, context_length in enumerate(range(total_prompt, total_final)):
+        if n == 0:
+            logits = state.prefill_fan_out(tokens[:, :prompt_length].contiguous(), query_embeds, G * K)
+        else:
+            logits = state.step(bs.next_tok.view(-1, 1))
+        if constraints is not None:
+            constrain_fn(logits, bs.tokens.view(B * G * K, -1), pos=context_length - Q, constraints=constraints, prompt_len_all=prompt_length,
+                         eos_ids=[stop_token], ban_value=BAN_BEAM)
+        vals, idxs = topk_fn(logits, m, bs.scores.view(-1))
+        advance_fn(vals, idxs, bs, groups=G, diversity_penalty=lam, vocab=logits.size(-1), pos=context_length - Q, cur_len=n + 1, first=n == 0,
+                   stop_token=stop_token)
+        if bool(bs.done.all()):                                                              # the step's one host read
+            break
+        state.reorder(bs.src_row, shared_prefix=total_prompt)
+    h = SimpleNamespace(**{k: getattr(bs, k).cpu() for k in BeamState.ARRAYS})              # one download
+    out = []
+    for clip in range(B):
+        seqs, scores, group = [], [], []
+        for g in range(G):
+            ranked = _ranked_hypotheses(h, clip * G + g, K)[:per_group]
+            seqs += [r[1] for r in ranked]
+            scores += [r[0] for r in ranked]
+            group += [g] * len(ranked)
+        out.append(SimpleNamespace(sequences=torch.stack(seqs, dim=0).to(dev), scores=torch.tensor(scores, dtype=torch.float32),
+                                   group=torch.tensor(group, dtype=torch.int64)))
     return out
 
 
@@ -712,15 +783,18 @@ def install(gpt_cls):
                                 topk_fn=lambda lg, k, add: ops.logprob_topk(lg, k, add=add))
 
     def beam_search_batched(self, tokens, query_embeds=None, beam_size=5, num_return_gen=1, stop_token=None, kv="per_sequence",
-                            constraints=None, **kw):
+                            constraints=None, beam_groups=1, diversity_penalty=0.0, **kw):
         """beam_search for tokens [B, L] / query_embeds [B, Q, H] with one prompt length, B clips in lockstep -> a list of B results;
         kv="shared_prefix" keeps the visual prefix and the prompt once per clip (SharedPrefixDecodeState); constraints: a
-        LogitsConstraints, applied on the device every step"""
+        LogitsConstraints, applied on the device every step; beam_groups = G > 1: diverse beam search, G groups of beam_size beams
+        each with diversity_penalty between them (beam_search_batched_loop; ops.beam_advance_groups)"""
         _no_sample_scores(kw.pop("return_scores", False), "beam_search_batched")
+        groups = {} if int(beam_groups) == 1 else dict(beam_groups=beam_groups, diversity_penalty=diversity_penalty,
+                                                       group_advance_fn=ops.beam_advance_groups)      # one group: today's call
         return beam_search_batched_loop(_gen_config(self), make_state_fn(self, kv), tokens, query_embeds=query_embeds, beam_size=beam_size,
                                         num_return_gen=num_return_gen, stop_token=stop_token, prompt_length=kw.pop("prompt_length", None),
                                         topk_fn=lambda lg, k, add: ops.logprob_topk(lg, k, add=add), advance_fn=ops.beam_advance,
-                                        constraints=constraints, constrain_fn=ops.logits_constrain)
+                                        constraints=constraints, constrain_fn=ops.logits_constrain, **groups)
 
     def sample_batched(self, tokens, query_embeds=None, temperature=1.0, num_samples=1, seed=0, streams=None, top_k=None, top_p=None,
                        kv="per_sequence", constraints=None, return_scores=False, **kw):

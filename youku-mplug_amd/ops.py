@@ -706,6 +706,31 @@ def beam_advance(cand_val, cand_idx, st, *, vocab, pos, cur_len, first, stop_tok
     return st.src_row, st.next_tok
 
 
+def beam_advance_groups(cand_val, cand_idx, st, *, groups, diversity_penalty, vocab, pos, cur_len, first, stop_token):
+    """One position of the lockstep GROUP beam search (include/mpv.h: mpv_beam_advance_groups): st is a generation.BeamState whose
+    st.batch pseudo-clips are (clip, group) pairs, `groups` consecutive ones per clip, of st.beams beams each.  cand_val fp32 /
+    cand_idx int64 [st.batch * st.beams, m], m = (groups + 1) * st.beams: logprob_topk(logits, m, add=st.scores).  Updates the state
+    in place, fills st.src_row / st.next_tok and swaps st.tokens with st.tokens_alt, as beam_advance does."""
+    _need_cuda(cand_val, cand_idx, st.tokens)
+    groups = int(groups)
+    if groups < 1 or st.batch % groups:
+        raise _lib.MpvError(f"beam_advance_groups: the state's {st.batch} (clip, group) pairs are no multiple of groups = {groups}")
+    rows, m = st.batch * st.beams, (groups + 1) * st.beams
+    if (cand_val.dtype, cand_idx.dtype) != (torch.float32, torch.int64) or tuple(cand_val.shape) != (rows, m) or \
+            tuple(cand_idx.shape) != (rows, m) or not (cand_val.is_contiguous() and cand_idx.is_contiguous()):
+        raise _lib.MpvError(f"beam_advance_groups: candidates must be contiguous fp32 / int64 [{rows}, {m}] "
+                            f"(got {cand_val.dtype} {tuple(cand_val.shape)}, {cand_idx.dtype} {tuple(cand_idx.shape)})")
+    d = _lib.BeamAdvanceGroupsDesc()
+    d.cand_val, d.cand_idx, d.tokens_in, d.tokens_out = cand_val.data_ptr(), cand_idx.data_ptr(), st.tokens.data_ptr(), st.tokens_alt.data_ptr()
+    for n in ("scores", "hyp_score", "hyp_order", "hyp_tokens", "hyp_count", "hyp_next", "worst", "done", "src_row", "next_tok"):
+        setattr(d, n, getattr(st, n).data_ptr())
+    d.batch, d.beams, d.row_len, d.vocab, d.pos, d.cur_len, d.first = st.batch // groups, st.beams, st.row_len, int(vocab), int(pos), int(cur_len), int(bool(first))
+    d.groups, d.diversity_penalty, d.stop_token = groups, float(diversity_penalty), int(stop_token)
+    check(_lib.lib().mpv_beam_advance_groups(C.byref(d), _stream()), "mpv_beam_advance_groups")
+    st.tokens, st.tokens_alt = st.tokens_alt, st.tokens
+    return st.src_row, st.next_tok
+
+
 TERMINATION_ID, TERMINATION_EOL, TERMINATION_DOUBLE_EOL = 0, 1, 2      # mpv_sample_advance_desc.termination_mode
 
 
