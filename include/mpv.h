@@ -544,7 +544,8 @@ int mpv_beam_advance(const mpv_beam_advance_desc* d, mpv_stream_t stream);
  * The definition is over the whole vocabulary: with every row's full log-probability vector penalised and sorted the result is the
  *   same, because at most (G-1)K' distinct tokens are penalised, lambda >= 0 and the rounding is monotone, so a row's penalised
  *   first 2K' lie inside its unpenalised first 2K' + (G-1)K' under the common tie rule, lower token first.
- * With groups = 1 every state array and output equals mpv_beam_advance's on the same input, bit for bit, whatever lambda is.
+ * With groups = 1 every state array and output equals mpv_beam_advance's on the same input, bit for bit, whatever lambda is:
+ * mpv_beam_advance is the groups = 1 case of one kernel.
  * Limits: beams in [1, 8], groups in [1, 8], groups * beams <= 16, diversity_penalty finite and >= 0, and everything
  *   mpv_beam_advance refuses (row_len in [1, 2048], 0 <= pos < row_len, batch / vocab / cur_len >= 1, a NULL pointer, tokens_in ==
  *   tokens_out); a descriptor outside them is refused with a negative code before any launch, the outputs untouched.

@@ -1,6 +1,7 @@
-"""Lockstep beam search over a batch of clips, on the GPU: mpv_beam_advance (csrc/beam_search.hip) against its restatement
-tests/standin_beam.py bit for bit, its refusals, the stub-driven search of tests/test_beam_batched_cpu.py on the real kernel against
-the reference's golden, DistributedGPT3_Caption.generate(batched=True) on the tiny model, and DecodeState.prefill_fan_out."""
+"""Lockstep beam search over a batch of clips, on the GPU: mpv_beam_advance (csrc/beam_search.hip: the groups = 1 case of the kernel it
+shares with mpv_beam_advance_groups) against its restatement tests/standin_beam.py bit for bit, its refusals, the stub-driven search
+of tests/test_beam_batched_cpu.py on the real kernel against the reference's golden, DistributedGPT3_Caption.generate(batched=True) on
+the tiny model, and DecodeState.prefill_fan_out."""
 import os
 import re
 import types
@@ -73,6 +74,34 @@ def test_kernel_equals_the_standin_bit_for_bit(dev, K):
         assert torch.equal(ref.src_row // K, torch.arange(B * K) // K)          # a source row never leaves its clip
     assert int(ref.done[1]) == 1 and int(ref.done[0]) == 0 and int(ref.done[2]) == 0          # only the clip that was made done
     assert added > 2 * min(K, 6) and int(ref.hyp_count[0]) == min(K, 6)                        # additions, and evictions where K < 6
+
+
+@pytest.mark.parametrize("K", [1, 8])
+@pytest.mark.parametrize("B", [1, 33])
+def test_plain_entry_equals_the_standin_at_the_row_copy_and_rank_edges(dev, K, B):
+    """mpv_beam_advance runs the kernel it shares with mpv_beam_advance_groups (groups = 1); tests/standin_beam.py shares no code with
+    it.  row_len 63 / 64 / 65 / 130 lie below, at, one over and two passes over the 64-lane row copies, K = 8 ranks 128 candidates,
+    B = 33 is more than one workgroup and an odd count.  4 steps from `first`, one clip made done before step 2 where B > 1; every
+    state array and tokens_alt bit for bit after every step (no tolerance: both sides are exact)."""
+    from youku_mplug_amd import ops
+    from youku_mplug_amd.generation import BeamState
+    V, P = 37, 3
+    for Lt in (63, 64, 65, 130):
+        g = torch.Generator().manual_seed(1000 * K + 10 * B + Lt)
+        prompt = torch.randint(0, V, (B, Lt), generator=g)
+        ref, mine = BeamState(prompt, K), BeamState(prompt.to(dev), K)
+        for step in range(4):
+            if step == 2 and B > 1:
+                ref.done[1] = 1
+                mine.done[1] = 1
+            val, tok = _candidates(g, B, K, V, step)
+            kw = dict(vocab=V, pos=P + step, cur_len=step + 1, first=step == 0, stop_token=STOP)
+            standin_beam.beam_advance(val, tok, ref, **kw)
+            ops.beam_advance(val.to(dev), tok.to(dev), mine, **kw)
+            for n in BeamState.ARRAYS + ("tokens_alt",):
+                a, b = getattr(mine, n).cpu(), getattr(ref, n)
+                assert a.dtype == b.dtype and torch.equal(a, b), (K, B, Lt, step, n)
+        assert int(ref.hyp_next.sum()) >= B and int(ref.done.sum()) == (1 if B > 1 else 0)      # hypotheses were added; only the clip made done is
 
 
 @pytest.mark.parametrize("K,Lt", [(9, 12), (4, 4096)])

@@ -1,5 +1,5 @@
-"""Diverse (group) beam search in lockstep, on the GPU: mpv_beam_advance_groups (csrc/beam_search_groups.hip) against its restatement
-tests/standin_beam_groups.py bit for bit on every state array, against mpv_beam_advance at one group, its refusals, the stub-driven
+"""Diverse (group) beam search in lockstep, on the GPU: mpv_beam_advance_groups (csrc/beam_search.hip, the kernel it shares with
+mpv_beam_advance) against its restatement tests/standin_beam_groups.py bit for bit on every state array, against mpv_beam_advance at one group, its refusals, the stub-driven
 search of tests/test_beam_groups_cpu.py on the real kernel against the reference's golden, the exact statements that hold on the tiny
 model in both KV modes, and the re-ranked scores of DistributedGPT3_Caption.generate(rerank_by_logprob=True) against the fp32
 restatement under section 20's gate."""

@@ -436,32 +436,30 @@ class DistributedGPT3_Caption(_GenCls):
                 scores = [None] * n
                 if scored:
                     kw = dict(kw, return_scores=True)                    # absent keyword: the calls below are today's
-                for pl in sorted(set(lengths)):
-                    group = [i for i in range(n) if lengths[i] == pl]
-                    for c in range(0, len(group), int(clips_per_search)):
-                        sel = torch.as_tensor(group[c:c + int(clips_per_search)], dtype=torch.long, device=qf.device)
-                        streams = (sel[:, None] * N + torch.arange(N, device=qf.device)[None]).reshape(-1)
-                        out = self.text_decoder.sample_batched(text.input_ids[sel], query_embeds=qf[sel].contiguous(), temperature=temperature,
-                                                               num_samples=N, seed=seed, streams=streams, top_k=top_k, top_p=top_p,
-                                                               termination_id=termination_id,
-                                                               prompt_length=torch.full((len(sel),), int(pl), device=qf.device), **kw)
-                        if not scored:
-                            out = generation.pad_after_termination(out, int(pl), term, width, term).cpu()
-                            for j, i in enumerate(sel.tolist()):
-                                res[i] = out[j * N:(j + 1) * N]
-                            continue
-                        out, sc = out
-                        out, tlp, slp, cnt = _download_scored(generation.pad_after_termination(out, int(pl), term, width, term), sc, width)
+                for pl, chunk in _prompt_length_chunks(lengths, clips_per_search):
+                    sel = torch.as_tensor(chunk, dtype=torch.long, device=qf.device)
+                    streams = (sel[:, None] * N + torch.arange(N, device=qf.device)[None]).reshape(-1)
+                    out = self.text_decoder.sample_batched(text.input_ids[sel], query_embeds=qf[sel].contiguous(), temperature=temperature,
+                                                           num_samples=N, seed=seed, streams=streams, top_k=top_k, top_p=top_p,
+                                                           termination_id=termination_id,
+                                                           prompt_length=torch.full((len(sel),), int(pl), device=qf.device), **kw)
+                    if not scored:
+                        out = generation.pad_after_termination(out, int(pl), term, width, term).cpu()
                         for j, i in enumerate(sel.tolist()):
-                            rows = slice(j * N, (j + 1) * N)
-                            entry = dict(sum_logprob=slp[rows], count=cnt[rows], token_logprob=tlp[rows])
-                            if best_of:
-                                b = best_sample(entry["sum_logprob"], entry["count"], length_penalty)
-                                entry = dict({k: v[b:b + 1] for k, v in entry.items()}, index=b)
-                                res[i] = out[rows][b:b + 1]
-                            else:
-                                res[i] = out[rows]
-                            scores[i] = entry
+                            res[i] = out[j * N:(j + 1) * N]
+                        continue
+                    out, sc = out
+                    out, tlp, slp, cnt = _download_scored(generation.pad_after_termination(out, int(pl), term, width, term), sc, width)
+                    for j, i in enumerate(sel.tolist()):
+                        rows = slice(j * N, (j + 1) * N)
+                        entry = dict(sum_logprob=slp[rows], count=cnt[rows], token_logprob=tlp[rows])
+                        if best_of:
+                            b = best_sample(entry["sum_logprob"], entry["count"], length_penalty)
+                            entry = dict({k: v[b:b + 1] for k, v in entry.items()}, index=b)
+                            res[i] = out[rows][b:b + 1]
+                        else:
+                            res[i] = out[rows]
+                        scores[i] = entry
                 return (res, scores) if return_scores else res
             if batched:
                 if int(clips_per_search) < 1:
@@ -469,15 +467,13 @@ class DistributedGPT3_Caption(_GenCls):
                 lengths = (text.attention_mask.sum(-1) - 1).tolist()
                 res = [None] * n
                 groups_of = [None] * n
-                for pl in sorted(set(lengths)):
-                    group = [i for i in range(n) if lengths[i] == pl]
-                    for c in range(0, len(group), int(clips_per_search)):
-                        sel = torch.as_tensor(group[c:c + int(clips_per_search)], dtype=torch.long, device=qf.device)
-                        outs = self.text_decoder.beam_search_batched(text.input_ids[sel], query_embeds=qf[sel].contiguous(),
-                                                                     stop_token=termination_id, prompt_length=int(pl), **kw)
-                        for i, out in zip(sel.tolist(), outs):
-                            res[i] = out.sequences.cpu()
-                            groups_of[i] = getattr(out, "group", None)
+                for pl, chunk in _prompt_length_chunks(lengths, clips_per_search):
+                    sel = torch.as_tensor(chunk, dtype=torch.long, device=qf.device)
+                    outs = self.text_decoder.beam_search_batched(text.input_ids[sel], query_embeds=qf[sel].contiguous(),
+                                                                 stop_token=termination_id, prompt_length=int(pl), **kw)
+                    for i, out in zip(sel.tolist(), outs):
+                        res[i] = out.sequences.cpu()
+                        groups_of[i] = getattr(out, "group", None)
                 if not rerank_by_logprob:
                     return res
                 term = generation._gen_config(self.text_decoder).eod_id if termination_id is None else int(termination_id)
@@ -562,50 +558,57 @@ class DistributedGPT3_Caption(_GenCls):
                 if not cands[i]:
                     res[i] = dict(sum_logprob=torch.zeros(0, dtype=torch.float32), count=torch.zeros(0, dtype=torch.int32),
                                   token_logprob=torch.zeros((0, 0), dtype=torch.float32), best=None)
-            for pl in sorted(set(lengths)):
-                group = [i for i in range(n) if lengths[i] == pl]
-                for c0 in range(0, len(group), int(clips_per_pass)):
-                    clips = [i for i in group[c0:c0 + int(clips_per_pass)] if cands[i]]
-                    if not clips:
-                        continue
-                    rows_in, rows_tgt, cont_len = [], [], []
-                    for i in clips:
-                        for c in cands[i]:
-                            seq_in, seq_tgt = [host_ids[i][pl - 1]] + c, c + [term]
-                            if not score_termination:
-                                seq_in, seq_tgt = seq_in[:-1], seq_tgt[:-1]
-                            rows_in += seq_in
-                            rows_tgt += seq_tgt
-                            cont_len.append(len(seq_in))
-                    dev = qf.device
-                    layout = ops.PackedLayout(cont_len, [len(cands[i]) for i in clips], device=dev)
-                    sel = torch.as_tensor(clips, dtype=torch.long, device=dev)
-                    prefix = self.text_decoder.forward_prefix(qf[sel].reshape(-1, Hh).contiguous(), ids_all[sel, :pl - 1].contiguous())
-                    both = torch.tensor([rows_in, rows_tgt], dtype=torch.long).to(dev)                       # one upload
-                    out = self.text_decoder.forward_continuation_packed(prefix, both[0], layout, labels=both[1])
-                    tlp = out["token_logprob"].cpu()                                                          # the chunk's one download
-                    at, k = 0, 0
-                    for i in clips:
-                        C_i = len(cands[i])
-                        lens = cont_len[k:k + C_i]
-                        table = torch.zeros((C_i, max(lens)), dtype=torch.float32)
-                        sums = []
-                        for j, ln in enumerate(lens):
-                            row = tlp[at:at + ln]
-                            table[j, :ln] = row
-                            acc = 0.0
-                            for x in row.tolist():                               # fp64, in position order
-                                acc += x
-                            sums.append(acc)
-                            at += ln
-                        k += C_i
-                        entry = dict(sum_logprob=torch.tensor(sums, dtype=torch.float64).to(torch.float32),
-                                     count=torch.tensor(lens, dtype=torch.int32), token_logprob=table)
-                        entry["best"] = best_sample(entry["sum_logprob"], entry["count"], length_penalty)
-                        res[i] = entry
+            for pl, chunk in _prompt_length_chunks(lengths, clips_per_pass):
+                clips = [i for i in chunk if cands[i]]
+                if not clips:
+                    continue
+                rows_in, rows_tgt, cont_len = [], [], []
+                for i in clips:
+                    for c in cands[i]:
+                        seq_in, seq_tgt = [host_ids[i][pl - 1]] + c, c + [term]
+                        if not score_termination:
+                            seq_in, seq_tgt = seq_in[:-1], seq_tgt[:-1]
+                        rows_in += seq_in
+                        rows_tgt += seq_tgt
+                        cont_len.append(len(seq_in))
+                dev = qf.device
+                layout = ops.PackedLayout(cont_len, [len(cands[i]) for i in clips], device=dev)
+                sel = torch.as_tensor(clips, dtype=torch.long, device=dev)
+                prefix = self.text_decoder.forward_prefix(qf[sel].reshape(-1, Hh).contiguous(), ids_all[sel, :pl - 1].contiguous())
+                both = torch.tensor([rows_in, rows_tgt], dtype=torch.long).to(dev)                       # one upload
+                out = self.text_decoder.forward_continuation_packed(prefix, both[0], layout, labels=both[1])
+                tlp = out["token_logprob"].cpu()                                                          # the chunk's one download
+                at, k = 0, 0
+                for i in clips:
+                    C_i = len(cands[i])
+                    lens = cont_len[k:k + C_i]
+                    table = torch.zeros((C_i, max(lens)), dtype=torch.float32)
+                    sums = []
+                    for j, ln in enumerate(lens):
+                        row = tlp[at:at + ln]
+                        table[j, :ln] = row
+                        acc = 0.0
+                        for x in row.tolist():                               # fp64, in position order
+                            acc += x
+                        sums.append(acc)
+                        at += ln
+                    k += C_i
+                    entry = dict(sum_logprob=torch.tensor(sums, dtype=torch.float64).to(torch.float32),
+                                 count=torch.tensor(lens, dtype=torch.int32), token_logprob=table)
+                    entry["best"] = best_sample(entry["sum_logprob"], entry["count"], length_penalty)
+                    res[i] = entry
             return res
         finally:
             self.train(was)
+
+
+def _prompt_length_chunks(lengths, per_chunk):
+    """the clips grouped by prompt length (ascending), each group cut into chunks of at most per_chunk clips in input order
+    -> (prompt length, clip indices) per chunk: one lockstep search, or one scoring pass"""
+    for pl in sorted(set(lengths)):
+        group = [i for i, x in enumerate(lengths) if x == pl]
+        for c in range(0, len(group), int(per_chunk)):
+            yield pl, group[c:c + int(per_chunk)]
 
 
 def best_sample(sum_logprob, count, length_penalty: float = 1.0) -> int:

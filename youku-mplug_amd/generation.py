@@ -9,9 +9,9 @@ keeps [max_s, b, np, hn] K and V tensors and copies into them, :905-915).  A ste
 every sequence (prefill: the visual prefix + prompt; afterwards one token), attends causally over the cached rows and
 runs the LM head on the last position only.  Beam re-ordering (swap_key_value_dict) is one strided row gather per
 layer into the twin buffer.  The search logic of the per-clip loops stays on the host, as in the reference; the lockstep
-search over a batch of clips (beam_search_batched_loop) keeps it on the device (ops.beam_advance, csrc/beam_search.hip), and so does
-sampled generation in lockstep (sample_batched_loop: ops.sample_advance, csrc/sampling.hip; with return_scores ops.sample_score,
-csrc/sample_score.hip, records every drawn token's log-probability).  The lockstep loops can also keep
+search over a batch of clips (beam_search_batched_loop) keeps it on the device (ops.beam_advance / ops.beam_advance_groups: one kernel,
+csrc/beam_search.hip), and so does sampled generation in lockstep (sample_batched_loop: ops.sample_advance, csrc/sampling.hip; with
+return_scores ops.sample_score, csrc/sample_score.hip, records every drawn token's log-probability).  The lockstep loops can also keep
 the positions all sequences of a clip share (visual prefix + prompt) once per clip: SharedPrefixDecodeState (kv="shared_prefix";
 mpv_gpt_decode_step_shared, csrc/decode_shared_attention.hip).
 """
@@ -331,6 +331,16 @@ def _no_sample_scores(return_scores, who):
                          "has no per-sample scores")
 
 
+def _pad_for_generation(cfg, tokens, fill, prompt_length, query_embeds):
+    """the prelude of every loop: the token table grows by tokens_to_generate columns of `fill` -> (tokens, final_len, Q), final_len
+    clamped to max_position_embeddings and above prompt_length (the shortest prompt of the call), Q the number of query slots"""
+    tokens = torch.cat((tokens, torch.full((tokens.size(0), cfg.tokens_to_generate), fill, dtype=torch.long, device=tokens.device)), dim=-1)
+    final_len = min(tokens.size(1), cfg.max_position_embeddings)
+    if prompt_length >= final_len:
+        raise ValueError("context length + tokens_to_generate too large")
+    return tokens, final_len, 0 if query_embeds is None else query_embeds.size(1)
+
+
 def beam_search_loop(cfg, make_state: Callable[[int, int], object], tokens: torch.Tensor, query_embeds=None, beam_size=5,
                      num_return_gen=1, stop_token=None, prompt_length=None, topk_fn=None, return_scores=False):
     """models/modeling_distributed_gpt3.py:1737-1873.  `make_state(batch, max_len)` returns an object with
@@ -342,11 +352,7 @@ def beam_search_loop(cfg, make_state: Callable[[int, int], object], tokens: torc
     dev = tokens.device
     prompt_length = int(prompt_length) if prompt_length is not None else tokens.size(1)
     stop_token = cfg.eod_id if stop_token is None else int(stop_token)
-    tokens = torch.cat((tokens, torch.full((1, cfg.tokens_to_generate), stop_token, dtype=torch.long, device=dev)), dim=-1)
-    final_len = min(tokens.size(1), cfg.max_position_embeddings)
-    if prompt_length >= final_len:
-        raise ValueError("context length + tokens_to_generate too large")
-    Q = 0 if query_embeds is None else query_embeds.size(1)
+    tokens, final_len, Q = _pad_for_generation(cfg, tokens, stop_token, prompt_length, query_embeds)
     state = make_state(beam_size, final_len + Q)
     hyp = BeamHypotheses(beam_size)
     done = False
@@ -450,14 +456,16 @@ def beam_search_batched_loop(cfg, make_state: Callable[[int, int], object], toke
     constrain_fn (ops.logits_constrain) on the beams' token table, with the stop token as the termination id of min_new_tokens and
     the lowest finite bf16 as the ban value (include/mpv.h says why it is not -inf here).
     return_scores=True is refused, as in beam_search_loop.
-    beam_groups = G > 1 (default 1: the calls above, nothing added): diverse (group) beam search.  beam_size is then K', the beams PER
-    GROUP; the state holds B x G x K' sequences, a (clip, group) pair being a clip of the BeamState; the prefill fans out to G * K'; a
-    step asks topk_fn for m = 2K' + (G-1)K' candidates per row and calls group_advance_fn (ops.beam_advance_groups: per clip, group
-    after group, one iteration on the values lowered by diversity_penalty times the number of next beams that the groups before chose
-    with the candidate's token at this step).  The re-order stays inside the (clip, group), so both KV states work as they are.  The
-    host finish is the one above, per (clip, group): -> per clip a namespace (sequences [n, Lt], scores [n], group [n] int64), group
-    0's best r = num_return_gen // G rows first, then group 1's, ...; a group with fewer hypotheses yields fewer rows.  From the second
-    group on the scores are penalised search scores, not model likelihoods.  num_return_gen must be a multiple of G with r <= K'."""
+    beam_groups = G > 1 (default 1: the calls above with exactly those keywords, group_advance_fn untouched, no `group` in the result):
+    diverse (group) beam search in the same loop.  beam_size is then K', the beams PER GROUP; the state holds B x G x K' sequences, a
+    (clip, group) pair being a clip of the BeamState; the prefill fans out to G * K'; a step asks topk_fn for m = 2K' + (G-1)K'
+    candidates per row and calls group_advance_fn in advance_fn's place, with groups= and diversity_penalty= added
+    (ops.beam_advance_groups: per clip, group after group, one iteration on the values lowered by diversity_penalty times the number
+    of next beams that the groups before chose with the candidate's token at this step).  The re-order stays inside the (clip,
+    group), so both KV states work as they are.  The host finish runs per (clip, group): -> per clip a namespace (sequences [n, Lt],
+    scores [n], group [n] int64), group 0's best r = num_return_gen // G rows first, then group 1's, ...; a group with fewer
+    hypotheses yields fewer rows.  From the second group on the scores are penalised search scores, not model likelihoods.
+    num_return_gen must be a multiple of G with r <= K'."""
     _no_sample_scores(return_scores, "beam_search_batched_loop")
     B, dev, K = tokens.size(0), tokens.device, int(beam_size)
     G = int(beam_groups)
@@ -472,39 +480,38 @@ def beam_search_batched_loop(cfg, make_state: Callable[[int, int], object], toke
                              "rows per group")
         if group_advance_fn is None:
             raise ValueError("beam_groups > 1 needs a group_advance_fn (ops.beam_advance_groups)")
-        return _beam_search_groups_loop(cfg, make_state, tokens, query_embeds, K, G, lam, int(num_return_gen) // G, stop_token, prompt_length,
-                                        topk_fn, group_advance_fn, _active_constraints(constraints, constrain_fn), constrain_fn)
+        advance, more, per_group = group_advance_fn, dict(groups=G, diversity_penalty=lam), int(num_return_gen) // G
+    else:
+        advance, more, per_group = advance_fn, {}, num_return_gen
     constraints = _active_constraints(constraints, constrain_fn)
     prompt_length = int(prompt_length) if prompt_length is not None else tokens.size(1)
     stop_token = cfg.eod_id if stop_token is None else int(stop_token)
-    tokens = torch.cat((tokens, torch.full((B, cfg.tokens_to_generate), stop_token, dtype=torch.long, device=dev)), dim=-1)
-    final_len = min(tokens.size(1), cfg.max_position_embeddings)
-    if prompt_length >= final_len:
-        raise ValueError("context length + tokens_to_generate too large")
-    Q = 0 if query_embeds is None else query_embeds.size(1)
-    state = make_state(B * K, final_len + Q)
-    bs = BeamState(tokens, K)
-    total_prompt, total_final = prompt_length + Q, final_len + Q
+    tokens, final_len, Q = _pad_for_generation(cfg, tokens, stop_token, prompt_length, query_embeds)
+    state = make_state(B * G * K, final_len + Q)
+    bs = BeamState(tokens if G == 1 else tokens.repeat_interleave(G, 0), K)                # pseudo-clip b * G + g: group g of clip b
+    total_prompt, total_final, m = prompt_length + Q, final_len + Q, 2 * K + (G - 1) * K
     for n, context_length in enumerate(range(total_prompt, total_final)):
         if n == 0:
-            logits = state.prefill_fan_out(tokens[:, :prompt_length].contiguous(), query_embeds, K)
+            logits = state.prefill_fan_out(tokens[:, :prompt_length].contiguous(), query_embeds, G * K)
         else:
             logits = state.step(bs.next_tok.view(-1, 1))
         if constraints is not None:
-            constrain_fn(logits, bs.tokens.view(B * K, -1), pos=context_length - Q, constraints=constraints, prompt_len_all=prompt_length,
+            constrain_fn(logits, bs.tokens.view(B * G * K, -1), pos=context_length - Q, constraints=constraints, prompt_len_all=prompt_length,
                          eos_ids=[stop_token], ban_value=BAN_BEAM)
-        vals, idxs = topk_fn(logits, 2 * K, bs.scores.view(-1))                             # log_softmax + scores (:1790-1791)
-        advance_fn(vals, idxs, bs, vocab=logits.size(-1), pos=context_length - Q, cur_len=n + 1, first=n == 0, stop_token=stop_token)
+        vals, idxs = topk_fn(logits, m, bs.scores.view(-1))                                  # log_softmax + scores (:1790-1791)
+        advance(vals, idxs, bs, vocab=logits.size(-1), pos=context_length - Q, cur_len=n + 1, first=n == 0, stop_token=stop_token, **more)
         if bool(bs.done.all()):                                                              # the step's one host read
             break
         state.reorder(bs.src_row, shared_prefix=total_prompt)
     h = SimpleNamespace(**{k: getattr(bs, k).cpu() for k in BeamState.ARRAYS})              # one download
     out = []
-    for b in range(B):
-        ranked = _ranked_hypotheses(h, b, K)
-        n_ret = min(num_return_gen, len(ranked))
-        out.append(SimpleNamespace(sequences=torch.stack([ranked[i][1] for i in range(n_ret)], dim=0).to(dev),
-                                   scores=torch.tensor([ranked[i][0] for i in range(n_ret)], dtype=torch.float32)))
+    for clip in range(B):
+        ranked = [_ranked_hypotheses(h, clip * G + g, K)[:per_group] for g in range(G)]
+        res = SimpleNamespace(sequences=torch.stack([r[1] for rg in ranked for r in rg], dim=0).to(dev),
+                              scores=torch.tensor([r[0] for rg in ranked for r in rg], dtype=torch.float32))
+        if G > 1:
+            res.group = torch.tensor([g for g, rg in enumerate(ranked) for _ in rg], dtype=torch.int64)
+        out.append(res)
     return out
 
 
@@ -519,48 +526,6 @@ def _ranked_hypotheses(h, b, K):
         for k in range(K):
             hyp.add(h.tokens[b, k].clone(), float(h.scores[b, k]))
     return sorted(hyp.beams, key=lambda x: x[0], reverse=True)
-
-
-def _beam_search_groups_loop(cfg, make_state, tokens, query_embeds, K, G, lam, per_group, stop_token, prompt_length, topk_fn, advance_fn,
-                             constraints, constrain_fn):
-    """beam_search_batched_loop with beam_groups = G > 1 (its docstring has the contract): the same loop over B * G pseudo-clips"""
-    B, dev = tokens.size(0), tokens.device
-    prompt_length = int(prompt_length) if prompt_length is not None else tokens.size(1)
-    stop_token = cfg.eod_id if stop_token is None else int(stop_token)
-    tokens = torch.cat((tokens, torch.full((B, cfg.tokens_to_generate), stop_token, dtype=torch.long, device=dev)), dim=-1)
-    final_len = min(tokens.size(1), cfg.max_position_embeddings)
-    if prompt_length >= final_len:
-        raise ValueError("context length + tokens_to_generate too large")
-    Q = 0 if query_embeds is None else query_embeds.size(1)
-    state = make_state(B * G * K, final_len + Q)
-    bs = BeamState(tokens.repeat_interleave(G, 0), K)                                      # pseudo-clip b * G + g: group g of clip b
-    total_prompt, total_final, m = prompt_length + Q, final_len + Q, 2 * K + (G - 1) * K
-    for n, context_length in enumerate(range(total_prompt, total_final)):
-        if n == 0:
-            logits = state.prefill_fan_out(tokens[:, :prompt_length].contiguous(), query_embeds, G * K)
-        else:
-            logits = state.step(bs.next_tok.view(-1, 1))
-        if constraints is not None:
-            constrain_fn(logits, bs.tokens.view(B * G * K, -1), pos=context_length - Q, constraints=constraints, prompt_len_all=prompt_length,
-                         eos_ids=[stop_token], ban_value=BAN_BEAM)
-        vals, idxs = topk_fn(logits, m, bs.scores.view(-1))
-        advance_fn(vals, idxs, bs, groups=G, diversity_penalty=lam, vocab=logits.size(-1), pos=context_length - Q, cur_len=n + 1, first=n == 0,
-                   stop_token=stop_token)
-        if bool(bs.done.all()):                                                              # the step's one host read
-            break
-        state.reorder(bs.src_row, shared_prefix=total_prompt)
-    h = SimpleNamespace(**{k: getattr(bs, k).cpu() for k in BeamState.ARRAYS})              # one download
-    out = []
-    for clip in range(B):
-        seqs, scores, group = [], [], []
-        for g in range(G):
-            ranked = _ranked_hypotheses(h, clip * G + g, K)[:per_group]
-            seqs += [r[1] for r in ranked]
-            scores += [r[0] for r in ranked]
-            group += [g] * len(ranked)
-        out.append(SimpleNamespace(sequences=torch.stack(seqs, dim=0).to(dev), scores=torch.tensor(scores, dtype=torch.float32),
-                                   group=torch.tensor(group, dtype=torch.int64)))
-    return out
 
 
 BAN_SAMPLING = float("-inf")                 # mpv_sample_advance: probability 0, never in the kept set
@@ -619,12 +584,8 @@ def sample_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None, temper
     B, dev = tokens.size(0), tokens.device
     lengths = prompt_length if prompt_length is not None else torch.tensor([tokens.size(1)], device=dev)
     lengths = torch.as_tensor(lengths, device=dev).view(-1)
-    tokens = torch.cat((tokens, torch.full((B, cfg.tokens_to_generate), cfg.eod_id, dtype=torch.long, device=dev)), dim=-1)
     min_prompt = int(lengths.min().item())
-    max_len = min(tokens.size(1), cfg.max_position_embeddings)
-    if min_prompt >= max_len:
-        raise ValueError("context length + tokens_to_generate too large")
-    Q = 0 if query_embeds is None else query_embeds.size(1)
+    tokens, max_len, Q = _pad_for_generation(cfg, tokens, cfg.eod_id, min_prompt, query_embeds)
     state = make_state(B, max_len + Q)
     termination_id = cfg.eod_id if termination_id is None else int(termination_id)
     is_done = torch.zeros(B, dtype=torch.bool, device=dev)
@@ -719,12 +680,8 @@ def sample_batched_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None
         raise ValueError(f"min_new_tokens ({constraints.min_new_tokens}) cannot be combined with stop_on_double_eol")
     lengths = prompt_length if prompt_length is not None else torch.tensor([tokens.size(1)], device=dev)
     lengths = torch.as_tensor(lengths, device=dev).view(-1).expand(B)
-    tokens = torch.cat((tokens, torch.full((B, cfg.tokens_to_generate), cfg.eod_id, dtype=torch.long, device=dev)), dim=-1)
     min_prompt = int(lengths.min().item())
-    max_len = min(tokens.size(1), cfg.max_position_embeddings)
-    if min_prompt >= max_len:
-        raise ValueError("context length + tokens_to_generate too large")
-    Q = 0 if query_embeds is None else query_embeds.size(1)
+    tokens, max_len, Q = _pad_for_generation(cfg, tokens, cfg.eod_id, min_prompt, query_embeds)
     R = B * N
     state = make_state(R, max_len + Q)
     st = SampleState(tokens.repeat_interleave(N, dim=0), lengths.repeat_interleave(N), streams=streams)

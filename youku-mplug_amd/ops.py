@@ -685,25 +685,30 @@ def logprob_topk(logits, k, add=None, rows=None, vocab=None, ld=None):
     return val, idx
 
 
+def _beam_advance(who, d, m, cand_val, cand_idx, st, vocab, pos, cur_len, first, stop_token):
+    """beam_advance / beam_advance_groups on the descriptor d (batch, and what the entry adds, are set): checks the candidates against
+    [rows, m], fills d from the state and the step, calls mpv_<who> and swaps the token tables"""
+    rows = st.batch * st.beams
+    if (cand_val.dtype, cand_idx.dtype) != (torch.float32, torch.int64) or tuple(cand_val.shape) != (rows, m) or \
+            tuple(cand_idx.shape) != (rows, m) or not (cand_val.is_contiguous() and cand_idx.is_contiguous()):
+        raise _lib.MpvError(f"{who}: candidates must be contiguous fp32 / int64 [{rows}, {m}] "
+                            f"(got {cand_val.dtype} {tuple(cand_val.shape)}, {cand_idx.dtype} {tuple(cand_idx.shape)})")
+    d.cand_val, d.cand_idx, d.tokens_in, d.tokens_out = cand_val.data_ptr(), cand_idx.data_ptr(), st.tokens.data_ptr(), st.tokens_alt.data_ptr()
+    for n in ("scores", "hyp_score", "hyp_order", "hyp_tokens", "hyp_count", "hyp_next", "worst", "done", "src_row", "next_tok"):
+        setattr(d, n, getattr(st, n).data_ptr())
+    d.beams, d.row_len, d.vocab, d.pos, d.cur_len, d.first, d.stop_token = st.beams, st.row_len, int(vocab), int(pos), int(cur_len), int(bool(first)), int(stop_token)
+    check(getattr(_lib.lib(), "mpv_" + who)(C.byref(d), _stream()), "mpv_" + who)
+    st.tokens, st.tokens_alt = st.tokens_alt, st.tokens
+    return st.src_row, st.next_tok
+
+
 def beam_advance(cand_val, cand_idx, st, *, vocab, pos, cur_len, first, stop_token):
     """One position of the lockstep beam search over st.batch clips x st.beams beams (include/mpv.h: mpv_beam_advance; st is a
     generation.BeamState).  cand_val fp32 / cand_idx int64 [batch * beams, 2 * beams]: logprob_topk(logits, 2 * beams, add=st.scores).
     Updates the state in place, fills st.src_row / st.next_tok and swaps st.tokens with st.tokens_alt."""
     _need_cuda(cand_val, cand_idx, st.tokens)
-    rows, k2 = st.batch * st.beams, 2 * st.beams
-    if (cand_val.dtype, cand_idx.dtype) != (torch.float32, torch.int64) or tuple(cand_val.shape) != (rows, k2) or \
-            tuple(cand_idx.shape) != (rows, k2) or not (cand_val.is_contiguous() and cand_idx.is_contiguous()):
-        raise _lib.MpvError(f"beam_advance: candidates must be contiguous fp32 / int64 [{rows}, {k2}] "
-                            f"(got {cand_val.dtype} {tuple(cand_val.shape)}, {cand_idx.dtype} {tuple(cand_idx.shape)})")
-    d = _lib.BeamAdvanceDesc()
-    d.cand_val, d.cand_idx, d.tokens_in, d.tokens_out = cand_val.data_ptr(), cand_idx.data_ptr(), st.tokens.data_ptr(), st.tokens_alt.data_ptr()
-    for n in ("scores", "hyp_score", "hyp_order", "hyp_tokens", "hyp_count", "hyp_next", "worst", "done", "src_row", "next_tok"):
-        setattr(d, n, getattr(st, n).data_ptr())
-    d.batch, d.beams, d.row_len, d.vocab, d.pos, d.cur_len, d.first = st.batch, st.beams, st.row_len, int(vocab), int(pos), int(cur_len), int(bool(first))
-    d.stop_token = int(stop_token)
-    check(_lib.lib().mpv_beam_advance(C.byref(d), _stream()), "mpv_beam_advance")
-    st.tokens, st.tokens_alt = st.tokens_alt, st.tokens
-    return st.src_row, st.next_tok
+    return _beam_advance("beam_advance", _lib.BeamAdvanceDesc(batch=st.batch), 2 * st.beams, cand_val, cand_idx, st, vocab, pos, cur_len, first,
+                         stop_token)
 
 
 def beam_advance_groups(cand_val, cand_idx, st, *, groups, diversity_penalty, vocab, pos, cur_len, first, stop_token):
@@ -715,20 +720,8 @@ def beam_advance_groups(cand_val, cand_idx, st, *, groups, diversity_penalty, vo
     groups = int(groups)
     if groups < 1 or st.batch % groups:
         raise _lib.MpvError(f"beam_advance_groups: the state's {st.batch} (clip, group) pairs are no multiple of groups = {groups}")
-    rows, m = st.batch * st.beams, (groups + 1) * st.beams
-    if (cand_val.dtype, cand_idx.dtype) != (torch.float32, torch.int64) or tuple(cand_val.shape) != (rows, m) or \
-            tuple(cand_idx.shape) != (rows, m) or not (cand_val.is_contiguous() and cand_idx.is_contiguous()):
-        raise _lib.MpvError(f"beam_advance_groups: candidates must be contiguous fp32 / int64 [{rows}, {m}] "
-                            f"(got {cand_val.dtype} {tuple(cand_val.shape)}, {cand_idx.dtype} {tuple(cand_idx.shape)})")
-    d = _lib.BeamAdvanceGroupsDesc()
-    d.cand_val, d.cand_idx, d.tokens_in, d.tokens_out = cand_val.data_ptr(), cand_idx.data_ptr(), st.tokens.data_ptr(), st.tokens_alt.data_ptr()
-    for n in ("scores", "hyp_score", "hyp_order", "hyp_tokens", "hyp_count", "hyp_next", "worst", "done", "src_row", "next_tok"):
-        setattr(d, n, getattr(st, n).data_ptr())
-    d.batch, d.beams, d.row_len, d.vocab, d.pos, d.cur_len, d.first = st.batch // groups, st.beams, st.row_len, int(vocab), int(pos), int(cur_len), int(bool(first))
-    d.groups, d.diversity_penalty, d.stop_token = groups, float(diversity_penalty), int(stop_token)
-    check(_lib.lib().mpv_beam_advance_groups(C.byref(d), _stream()), "mpv_beam_advance_groups")
-    st.tokens, st.tokens_alt = st.tokens_alt, st.tokens
-    return st.src_row, st.next_tok
+    d = _lib.BeamAdvanceGroupsDesc(batch=st.batch // groups, groups=groups, diversity_penalty=float(diversity_penalty))
+    return _beam_advance("beam_advance_groups", d, (groups + 1) * st.beams, cand_val, cand_idx, st, vocab, pos, cur_len, first, stop_token)
 
 
 TERMINATION_ID, TERMINATION_EOL, TERMINATION_DOUBLE_EOL = 0, 1, 2      # mpv_sample_advance_desc.termination_mode
