@@ -139,9 +139,11 @@ def test_ctypes_descriptor_layout_matches_the_header(tmp_path):
 
 
 def test_packed_attention_kernel_has_no_scratch_and_fits_two_workgroups_per_cu():
-    """attn_prefix_packed_fwd_kernel<64> / <80> in the gfx950 code object: two 256-thread workgroups per CU = two
-    waves per SIMD, so at most 256 registers (launch_bounds(256, 2)); no scratch; 52 KiB of LDS (two buffers of 64-row K and V chunks at a
-    208-byte pitch), of which two fit the CU's 160 KiB.  Register, LDS and scratch figures only, read the way tests/test_isa_cpu.py reads
+    """attn_prefix_fwd_kernel<64 / 80, uniform / packed> in the gfx950 code object ("Merged"): the one kernel body behind
+    mpv_attn_prefix_fwd and mpv_attn_prefix_packed_fwd, four instances and no second prefix kernel.  No scratch; 52 KiB of LDS (two buffers
+    of 64-row K and V chunks at a 208-byte pitch), of which two fit the CU's 160 KiB; each instance inside the register tier it had before
+    the two kernels became one: at most 168 registers (three waves per SIMD) for both hd-64 instances and packed hd-80, at most 256 (two
+    waves, launch_bounds(256, 2)) for uniform hd-80.  Register, LDS and scratch figures only, read the way tests/test_isa_cpu.py reads
     them."""
     import tempfile
     import test_isa_cpu as isa
@@ -155,14 +157,18 @@ def test_packed_attention_kernel_has_no_scratch_and_fits_two_workgroups_per_cu()
             txt = subprocess.run([os.path.join(isa.LLVM, "llvm-readelf"), "--notes", f], capture_output=True, text=True).stdout
             for blk in txt.split("- .agpr_count:")[1:]:
                 name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-                if "attn_prefix_packed_fwd_kernel" in name:
+                if "attn_prefix" in name:
                     g = lambda key: int(re.search(r"\." + key + r":\s+(\d+)", blk).group(1))
                     found[name] = dict(vgpr=g("vgpr_count"), agpr=int(blk.split()[0]), scratch=g("private_segment_fixed_size"),
                                        lds=g("group_segment_fixed_size"), threads=g("max_flat_workgroup_size"))
-    assert len(found) == 2, sorted(found)                                    # head_dim 64 and 80
+    # template arguments as the Itanium mangling spells them: Li<head_dim>E, Lb<packed>E
+    tier = {"attn_prefix_fwd_kernelILi64ELb0EE": 168, "attn_prefix_fwd_kernelILi64ELb1EE": 168, "attn_prefix_fwd_kernelILi80ELb1EE": 168,
+            "attn_prefix_fwd_kernelILi80ELb0EE": 256}
+    assert len(found) == 4 and all(sum(t in n for n in found) == 1 for t in tier), sorted(found)   # every prefix kernel is one of the four
     for n, k in found.items():
         print(f"    {n}: {k}")
-        assert k["scratch"] == 0 and k["vgpr"] + k["agpr"] <= 256 and k["lds"] == 4 * 64 * 208 and 2 * k["lds"] <= 160 * 1024 and k["threads"] == 256, (n, k)
+        regs = next(v for t, v in tier.items() if t in n)
+        assert k["scratch"] == 0 and k["vgpr"] + k["agpr"] <= regs and k["lds"] == 4 * 64 * 208 and 2 * k["lds"] <= 160 * 1024 and k["threads"] == 256, (n, k)
 
 
 # ------------------------------------------------------------------------------ the host pipeline on the stand-ins

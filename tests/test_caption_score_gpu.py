@@ -1,4 +1,4 @@
-"""Scoring of given captions on the GPU: mpv_attn_prefix_packed_fwd (csrc/prefix_packed_attention.hip) against an
+"""Scoring of given captions on the GPU: mpv_attn_prefix_packed_fwd (csrc/prefix_attention.hip) against an
 fp32 torch softmax over every continuation's concatenated keys and against the decoder's own mpv_attn_fwd on that concatenation (the
 gate of tests/test_prefix_attention_gpu.py), against mpv_attn_prefix_fwd at uniform lengths, and its bit-for-bit properties;
 mpv_gpt_embed_rows_fwd against mpv_gpt_embed_fwd; DistributedGPT3_Caption.score_captions on the tiny model against three yardsticks; the
@@ -101,24 +101,32 @@ def test_packed_attention_sweep_vs_fp32_and_the_decoder_kernel(dev, hd, heads):
 @gpu
 @pytest.mark.parametrize("hd", [64, 80])
 def test_packed_attention_at_uniform_lengths_vs_the_uniform_kernel(dev, hd):
-    """the same data through mpv_attn_prefix_fwd: both inside the gate above, their difference at most twice the older kernel's own error"""
+    """the same data through mpv_attn_prefix_fwd: both inside the gate above, their difference at most twice the older kernel's own error
+    -- and in fact none: the two entries run one kernel body that cuts a group into the same tiles, so on a uniform layout they agree bit
+    for bit.  (G, Lc, groups, P, continuations short in the last group): prefix phase skipped / a partial chunk / several chunks, the
+    segment division on and off, a continuation across the 128-row tile edge (5 x 33 rows: the second tile's key stream starts inside
+    the first), a short last group, workgroups that leave early."""
     from youku_mplug_amd import ops
     heads = 3
-    for G, Lc, ng, P in ((8, 5, 3, 137), (3, 41, 2, 264), (45, 7, 2, 33), (1, 130, 2, 0)):
-        lay = ([Lc] * (G * ng), [G] * ng)
+    for G, Lc, ng, P, short in ((8, 5, 3, 137, 0), (3, 41, 2, 264, 0), (45, 7, 2, 33, 0), (1, 130, 2, 0, 0), (8, 5, 3, 65, 1), (5, 33, 2, 31, 0)):
+        n_cont = G * ng - short
+        lay = ([Lc] * n_cont, [G] * (ng - 1) + [G - short])
         cq, pq, H = _problem(dev, hd, heads, lay, P, seed=hd + G * 7 + Lc)
-        mine = _run_packed(cq, pq, ops.PackedLayout(*lay, device=dev), P, heads, hd).float()
-        o = torch.empty((G * ng * Lc, H), dtype=BF, device=dev)
+        mine_bf = _run_packed(cq, pq, ops.PackedLayout(*lay, device=dev), P, heads, hd)
+        mine = mine_bf.float()
+        o = torch.empty((n_cont * Lc, H), dtype=BF, device=dev)
         st3 = (Lc * 3 * H, 3 * hd, 3 * H)
         pst = (P * 3 * H, 3 * hd, 3 * H)
         ops.attn_prefix_fwd(cq, cq[:, hd:], cq[:, 2 * hd:], pq[:, hd:], pq[:, 2 * hd:], o, ops.AttnLayout(st3, st3, st3, (Lc * H, hd, H)), (pst, pst),
-                            G * ng, G, heads, Lc, P, hd, scale=1.0 / math.sqrt(hd))
+                            n_cont, G, heads, Lc, P, hd, scale=1.0 / math.sqrt(hd))
         torch.cuda.synchronize()
         ref, base = _references(cq, pq, lay, P, heads, hd)
         e_new, e_uni, e_old = (mine - ref).abs().max().item(), (o.float() - ref).abs().max().item(), (base - ref).abs().max().item()
         diff = (mine - o.float()).abs().max().item()
-        print(f"    hd {hd} G {G} Lc {Lc} P {P}: e_packed {e_new:.3e} e_uniform {e_uni:.3e} e_attn_fwd {e_old:.3e} |packed - uniform| {diff:.3e}")
+        print(f"    hd {hd} G {G} Lc {Lc} P {P} n_cont {n_cont}: e_packed {e_new:.3e} e_uniform {e_uni:.3e} e_attn_fwd {e_old:.3e} "
+              f"|packed - uniform| {diff:.3e}")
         assert e_new <= 1.5 * e_old + 1e-6 and e_uni <= 1.5 * e_old + 1e-6 and diff <= 2 * e_uni, (G, Lc, P, e_new, e_uni, e_old, diff)
+        assert torch.equal(mine_bf, o), (G, Lc, P, n_cont, diff)
 
 
 @gpu

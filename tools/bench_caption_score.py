@@ -2,7 +2,9 @@
 
 (a) The attention alone at 1.3B dims (32 heads x 64): P = 264 prefix rows, 32 groups x 8 candidates, lengths drawn once from a seeded
     uniform 6..40 plus the prompt token: ops.attn_prefix_packed_fwd on the packed rows against ops.attn_prefix_fwd padded to the longest;
-    the same at the uniform length 41.  HIP events, 3 warm-up + 20 timed launches per kernel, alternated launch by launch.
+    the same at the uniform length 41; both again at head_dim 80 (32 heads x 80); then the category-scoring shape (8 groups x 45
+    continuations of 5 rows, the uniform entry only) at both head dims.  HIP events, 3 warm-up + 20 timed launches per kernel, alternated
+    launch by launch.
 (b) End to end on the 1.3B decoder, the same candidates three ways, alternated --rounds times in one process: every (clip, candidate)
     pair as its own Q + L sequence (forward_lm: what _GenCls._scores does), the padded forward_continuation, and the packed pass
     (forward_continuation_packed); pairs/s and decoder rows of each.  Then the padded and the packed pass again at the uniform length
@@ -25,6 +27,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STEP_SECONDS = {"attention": 240, "end_to_end": 420}
 GROUPS, PER_GROUP, LEN_LO, LEN_HI, UNIFORM = 32, 8, 6, 40, 41
+CAT_GROUPS, CAT_PER_GROUP, CAT_LEN = 8, 45, 5        # the attention step's category-scoring rows
 PAIR_CHUNK = 8            # clips per forward_lm call of the pair-by-pair way (its tape holds every layer of Q + L rows per pair)
 
 
@@ -57,46 +60,67 @@ def attention_rows(dev, sampler_cls):
     import torch
     from bench_sampling import HEADS, HIDDEN
     from youku_mplug_amd import ops
-    hd, H, P = HIDDEN // HEADS, HIDDEN, 264
+    P = 264
     out = []
     g = torch.Generator().manual_seed(1)
-    for uniform in (False, True):
-        lens = _lengths(uniform)
-        layout = ops.PackedLayout(lens, [PER_GROUP] * GROUPS, device=dev)
-        Lc, n = max(lens), len(lens)
-        cq = (torch.randn(layout.rows, 3 * H, generator=g) * 1.5).to(torch.bfloat16).to(dev)
-        pq = (torch.randn(GROUPS * P, 3 * H, generator=g) * 1.5).to(torch.bfloat16).to(dev)
-        pad = torch.zeros((n, Lc, 3 * H), dtype=torch.bfloat16, device=dev)
-        at = 0
-        for c, ln in enumerate(lens):
-            pad[c, :ln] = cq[at:at + ln]
-            at += ln
-        pad = pad.view(n * Lc, 3 * H)
-        o1 = torch.empty((layout.rows, H), dtype=torch.bfloat16, device=dev)
-        o2 = torch.empty((n * Lc, H), dtype=torch.bfloat16, device=dev)
-        st = ((3 * H, 3 * hd),) * 3 + ((H, hd),)
+
+    def uniform_entry(x, pq, o, n, per_group, Lc, hd):
+        H = HEADS * hd
         st3 = (Lc * 3 * H, 3 * hd, 3 * H)
-        lay = ops.AttnLayout(st3, st3, st3, (Lc * H, hd, H))
         pst = (P * 3 * H, 3 * hd, 3 * H)
-        sc = 1.0 / math.sqrt(hd)
-        fns = {"packed": lambda: ops.attn_prefix_packed_fwd(cq, cq[:, hd:], cq[:, 2 * hd:], pq[:, hd:], pq[:, 2 * hd:], o1, st, (pst, pst), layout,
-                                                            HEADS, P, hd, scale=sc),
-               "padded": lambda: ops.attn_prefix_fwd(pad, pad[:, hd:], pad[:, 2 * hd:], pq[:, hd:], pq[:, 2 * hd:], o2, lay, (pst, pst), n, PER_GROUP,
-                                                     HEADS, Lc, P, hd, scale=sc)}
+        lay = ops.AttnLayout(st3, st3, st3, (Lc * H, hd, H))
+        return lambda: ops.attn_prefix_fwd(x, x[:, hd:], x[:, 2 * hd:], pq[:, hd:], pq[:, 2 * hd:], o, lay, (pst, pst), n, per_group, HEADS, Lc, P, hd,
+                                           scale=1.0 / math.sqrt(hd))
+
+    for hd in (HIDDEN // HEADS, 80):                        # 64: the 1.3B decoder; 80: the 2.7B decoder's heads
+        H = HEADS * hd
+        for uniform in (False, True):
+            lens = _lengths(uniform)
+            layout = ops.PackedLayout(lens, [PER_GROUP] * GROUPS, device=dev)
+            Lc, n = max(lens), len(lens)
+            cq = (torch.randn(layout.rows, 3 * H, generator=g) * 1.5).to(torch.bfloat16).to(dev)
+            pq = (torch.randn(GROUPS * P, 3 * H, generator=g) * 1.5).to(torch.bfloat16).to(dev)
+            pad = torch.zeros((n, Lc, 3 * H), dtype=torch.bfloat16, device=dev)
+            at = 0
+            for c, ln in enumerate(lens):
+                pad[c, :ln] = cq[at:at + ln]
+                at += ln
+            pad = pad.view(n * Lc, 3 * H)
+            o1 = torch.empty((layout.rows, H), dtype=torch.bfloat16, device=dev)
+            o2 = torch.empty((n * Lc, H), dtype=torch.bfloat16, device=dev)
+            st = ((3 * H, 3 * hd),) * 3 + ((H, hd),)
+            pst = (P * 3 * H, 3 * hd, 3 * H)
+            sc = 1.0 / math.sqrt(hd)
+            fns = {"packed": lambda: ops.attn_prefix_packed_fwd(cq, cq[:, hd:], cq[:, 2 * hd:], pq[:, hd:], pq[:, 2 * hd:], o1, st, (pst, pst), layout,
+                                                                HEADS, P, hd, scale=sc),
+                   "padded": uniform_entry(pad, pq, o2, n, PER_GROUP, Lc, hd)}
+            with sampler_cls(0) as sampler:
+                t = _timeit_alternated(fns)
+            tel = sampler.summary()
+            at, worst = 0, 0.0                                  # the two kernels agree on the real rows
+            o2v = o2.view(n, Lc, H)
+            for c, ln in enumerate(lens):
+                worst = max(worst, (o1[at:at + ln].float() - o2v[c, :ln].float()).abs().max().item())
+                at += ln
+            row = dict(lengths="uniform 41" if uniform else f"uniform random {LEN_LO}..{LEN_HI} + 1 (seed 0)", prefix_len=P, groups=GROUPS, per_group=PER_GROUP,
+                       heads=HEADS, head_dim=hd, packed_rows=layout.rows, padded_rows=n * Lc, rows_ratio=round(n * Lc / layout.rows, 3), packed=t["packed"],
+                       padded=t["padded"], padded_over_packed=round(t["padded"]["median_us"] / t["packed"]["median_us"], 3),
+                       max_abs_difference_on_real_rows=worst, sclk_mhz=tel["sclk_mhz"], power_w=tel["power_w"], clock_power_source=tel["clock_power_source"])
+            print(f"attention hd {hd} {row['lengths']}: packed {t['packed']['median_us']} us ({layout.rows} rows), padded {t['padded']['median_us']} us "
+                  f"({n * Lc} rows)", file=sys.stderr, flush=True)
+            out.append(row)
+    # category scoring, the shape the uniform entry was written for: many short continuations per clip (the uniform entry only)
+    for hd in (HIDDEN // HEADS, 80):
+        H = HEADS * hd
+        x = (torch.randn(CAT_GROUPS * CAT_PER_GROUP * CAT_LEN, 3 * H, generator=g) * 1.5).to(torch.bfloat16).to(dev)
+        pq = (torch.randn(CAT_GROUPS * P, 3 * H, generator=g) * 1.5).to(torch.bfloat16).to(dev)
+        o = torch.empty((x.shape[0], H), dtype=torch.bfloat16, device=dev)
         with sampler_cls(0) as sampler:
-            t = _timeit_alternated(fns)
+            t = _timeit_alternated({"padded": uniform_entry(x, pq, o, CAT_GROUPS * CAT_PER_GROUP, CAT_PER_GROUP, CAT_LEN, hd)})
         tel = sampler.summary()
-        at, worst = 0, 0.0                                  # the two kernels agree on the real rows
-        o2v = o2.view(n, Lc, H)
-        for c, ln in enumerate(lens):
-            worst = max(worst, (o1[at:at + ln].float() - o2v[c, :ln].float()).abs().max().item())
-            at += ln
-        row = dict(lengths="uniform 41" if uniform else f"uniform random {LEN_LO}..{LEN_HI} + 1 (seed 0)", prefix_len=P, groups=GROUPS, per_group=PER_GROUP,
-                   heads=HEADS, head_dim=hd, packed_rows=layout.rows, padded_rows=n * Lc, rows_ratio=round(n * Lc / layout.rows, 3), packed=t["packed"],
-                   padded=t["padded"], padded_over_packed=round(t["padded"]["median_us"] / t["packed"]["median_us"], 3),
-                   max_abs_difference_on_real_rows=worst, sclk_mhz=tel["sclk_mhz"], power_w=tel["power_w"], clock_power_source=tel["clock_power_source"])
-        print(f"attention {row['lengths']}: packed {t['packed']['median_us']} us ({layout.rows} rows), padded {t['padded']['median_us']} us "
-              f"({n * Lc} rows)", file=sys.stderr, flush=True)
+        row = dict(lengths=f"categories: uniform {CAT_LEN}", prefix_len=P, groups=CAT_GROUPS, per_group=CAT_PER_GROUP, heads=HEADS, head_dim=hd,
+                   padded_rows=x.shape[0], padded=t["padded"], sclk_mhz=tel["sclk_mhz"], power_w=tel["power_w"], clock_power_source=tel["clock_power_source"])
+        print(f"attention hd {hd} {row['lengths']}: padded {t['padded']['median_us']} us ({x.shape[0]} rows)", file=sys.stderr, flush=True)
         out.append(row)
     return out
 

@@ -1,10 +1,8 @@
-// prefix_tile.h -- the 32-key score / online-softmax / PV tile of decode_shared_attention.hip: K/V streamed through LDS against 32
-// query rows held in registers.  It restates the tile of prefix_attention.hip's attn_prefix_fwd_kernel (same fragment helpers, same
-// arithmetic, in the same order) as a function of the softmax state, because the decode kernel keeps two states per wave.  That
-// kernel keeps its own copy: calling this function from it gave the same arithmetic but another register allocation (SGPRs spilled
-// to lanes), and its code is to stay as it is.  Conventions of attention.hip's forward kernel: S^T = K Q^T so a lane owns one query
-// row of the 32x32 score tile, the probabilities feed the PV MFMA as its B operand from registers, V^T fragments come from the
-// transposing LDS read.
+// prefix_tile.h -- the 32-key score / online-softmax / PV tile of the shared-prefix attention kernels (prefix_attention.hip's
+// attn_prefix_fwd_kernel, decode_shared_attention.hip's attn_decode_shared_kernel): K/V streamed through LDS against 32 query rows
+// held in registers.  The tile is a function of the softmax state because the decode kernel keeps two states per wave.  Conventions
+// of attention.hip's forward kernel: S^T = K Q^T so a lane owns one query row of the 32x32 score tile, the probabilities feed the PV
+// MFMA as its B operand from registers, V^T fragments come from the transposing LDS read.
 #pragma once
 
 #include "mpv_common.h"
