@@ -27,6 +27,9 @@ What this entry point adds to downstream/finetune_common.py:
     step (`model.generate(..., batched=True, beam_groups=G, diversity_penalty=F, rerank_by_logprob=True)`); every hypothesis of every
     group is re-scored by the model's own log-probability per token: "pred_caption" is the best, "pred_candidates" lists all of them in
     that order; it implies the batched path and combines with `--eval_shared_kv` and the constraint flags;
+  * `--eval_fp8_decode` (not in the reference, default off): every generation call of the evaluation runs its decode steps on e4m3
+    codes of the decoder's weights (`model.generate(..., decode_weights="fp8")`: quantised on the device, once; the bf16 weights stay
+    and serve the prefill of many rows and the scoring); it combines with every other flag;
   * `--eval_score_gold` (not in the reference, default off): evaluation also scores every clip's `gold_caption` list, teacher-forced,
     against the query features computed once for that clip (`model.score_captions(..., query_features=)`: one packed pass per batch,
     no padding rows), adds "gold_logprob" / "gold_tokens" lists to the result entries and logs the corpus per-token NLL and perplexity;
@@ -60,14 +63,14 @@ def make_training_batch(video, text, prompt, tokenizer, device, max_length):
 
 @torch.no_grad()
 def evaluation(model, data_loader, tokenizer, device, config, batched=False, clips_per_search=32, eval_sample=0, seed=0, shared_kv=False,
-               constraints=None, best_of=0, score_gold=False, max_length=None, beam_groups=1, diversity_penalty=0.0):
+               constraints=None, best_of=0, score_gold=False, max_length=None, beam_groups=1, diversity_penalty=0.0, fp8_decode=False):
     """-> [{video_id, pred_caption, gold_caption}] (:208-238); batched: `--eval_batched_beam`; eval_sample: `--eval_sample`;
     shared_kv: `--eval_shared_kv`, constraints: the keywords of `--eval_repetition_penalty` / `--eval_no_repeat_ngram` /
     `--eval_min_new_tokens` (the lockstep calls only); best_of: `--eval_sample_best_of` (the prediction is the best of that many
     samples instead of the beam search's); score_gold: `--eval_score_gold` (the clip's query features are computed once and serve the
     generation and the scoring of its gold captions, tokenized as the training pairs are, at most max_length tokens); beam_groups /
     diversity_penalty: `--eval_beam_groups` / `--eval_diversity_penalty` (the prediction is the most likely hypothesis of a diverse beam
-    search, all of them in "pred_candidates")"""
+    search, all of them in "pred_candidates"); fp8_decode: `--eval_fp8_decode`"""
     module = getattr(model, "module", model)
     module.eval()
     kvkw = {"kv_cache": "shared_prefix"} if shared_kv else {}                # flag absent: the calls below are unchanged
@@ -77,10 +80,10 @@ def evaluation(model, data_loader, tokenizer, device, config, batched=False, cli
         video = video.to(device, non_blocking=True).bfloat16()
         text = [config["prompt"] for _ in range(video.shape[0])]
         text_input = tokenizer(text, padding="max_length", truncation=True, max_length=20, return_tensors="pt").to(device)
-        qkw = {}                                                                 # flag absent: the calls below are unchanged
+        qkw = {"decode_weights": "fp8"} if fp8_decode else {}                    # flag absent: the calls below are unchanged
         if score_gold:
             qf = module.encode_video(video)
-            qkw = {"query_features": qf}
+            qkw = dict(qkw, query_features=qf)
         candidates = None
         if beam_groups > 1:
             per_group = min(5, 16 // beam_groups)
@@ -287,7 +290,8 @@ def main(args, config):
                             constraints=constraint_keywords(args), best_of=getattr(args, "eval_sample_best_of", 0),
                             **({"beam_groups": args.eval_beam_groups, "diversity_penalty": args.eval_diversity_penalty}
                                if getattr(args, "eval_beam_groups", 1) > 1 else {}),
-                            **({"score_gold": True, "max_length": args.max_length} if getattr(args, "eval_score_gold", False) else {}))
+                            **({"score_gold": True, "max_length": args.max_length} if getattr(args, "eval_score_gold", False) else {}),
+                            **({"fp8_decode": True} if getattr(args, "eval_fp8_decode", False) else {}))
         final = save_result(result, args.result_dir, "val_caption_result")
         val_stats = cal_metric(final)
         if getattr(args, "eval_score_gold", False):
@@ -342,6 +346,9 @@ def get_args(argv=None):
         p.add_argument("--eval_diversity_penalty", type=float, default=0.0,
                        help="--eval_beam_groups: what a later group pays for a token an earlier group chose at the same step "
                             "(model.generate(diversity_penalty=F))")
+        p.add_argument("--eval_fp8_decode", action="store_true", default=False,
+                       help="evaluation: the decode steps of every generation call run on e4m3 codes of the decoder's weights "
+                            "(model.generate(decode_weights='fp8'))")
         p.add_argument("--eval_score_gold", action="store_true", default=False,
                        help="evaluation: also score every clip's gold captions against its query features (model.score_captions): "
                             "gold_logprob / gold_tokens in the result file, per-token NLL and perplexity in the log")

@@ -479,6 +479,55 @@ int mpv_gpt_decode_step_shared(const mpv_gpt_weights* w, void* const* prefix_cac
 int mpv_kv_reorder(void* const* src, void* const* dst, int layers, const int64_t* idx, int batch, int max_len, int rows,
                    int hidden, mpv_stream_t stream);
 /* ------------------------------------------------------------------------------------------
+ * FP8 decoder weights (weight-only, opt-in, the decode steps of the frozen decoder; csrc/gemm_w8.hip).  Numeric contract:
+ *   format   OCP e4m3fn (gfx950's native FP8, not fnuz), one fp32 scale per output row of a [N, K] nn.Linear weight (bf16 in).
+ *   scale    row n: amax = max_k |w[n,k]|; e = the smallest integer with amax <= 448 * 2^e -- from frexp(amax) = (f, x):
+ *            e = x - 9 if f <= 0.875, else x - 8; a zero row has e = 0 (e is never below -126); scale[n] = 2^e.
+ *   codes    code[n,k] = RNE_e4m3(w[n,k] * 2^-e).  Nothing saturates and no NaN code is produced (finite weights).
+ *   product  C[m,n] = bf16(epi(scale[n] * sum_k A[m,k] * deq(code[n,k]))), A bf16, fp32 accumulation; deq is exact for all 254
+ *            finite codes, subnormals included.  epi: bias, GELU-tanh on the bf16-rounded pre-activation, residual with ldr, the
+ *            output row map c_group / c_stride / c_offset; any other epilogue field set: MPV_E_ARG.
+ * The scales are powers of two, so deq(code) * scale is a bf16 number: the quantised decoder IS a bf16 model, the one with those
+ * weights loaded, and the FP8 entries compute its function -- kernel error and quantisation error are separate questions.  (The
+ * rounding of a weight to e4m3 is about 2.7 % relative L2 noise per product, computed on the CPU for Gaussian rows; the bf16
+ * gates of this project are 1e-2.  What that costs in caption quality has NOT been measured -- no trained checkpoint exists
+ * here; running the unchanged bf16 stack on DistributedGPT3.dequantized_state_dict() measures exactly that.)
+ *
+ * mpv_quantize_rows_e4m3: codes [N][K] uint8 (dense), scale [N] fp32 from w [N][ldw] bf16.  K % 16 == 0, ldw % 8 == 0.
+ * mpv_gemm_w8: 1 <= M <= 512, N % 8 == 0, K % 16 == 0 (a 16-byte chunk is 16 codes), anything else MPV_E_SHAPE with C untouched.
+ *   The codes are streamed once per product straight into registers, turned into bf16 MFMA operands there, and multiplied into
+ *   16-row blocks of A held by the same workgroup (A is re-read from L2: from a few dozen rows on that traffic, not the weight, is
+ *   what the product costs).  Shapes with K >= 4096 and N <= 4096 split K over 16 waves whose registers hold 8 row blocks: such a
+ *   product goes out in launches of 128 rows.  The K-summation order of an
+ *   output element depends on (N, K) only: row m of a 160-row call is bit-identical to the same row computed alone.  No atomics.
+ * mpv_gpt_embed_w8_fwd: mpv_gpt_embed_fwd (no dropout) of the bf16 model above -- token rows are deq(code) * scale of the tied
+ *   embedding's codes, query rows are copied, the position rows are added in fp32. */
+int mpv_quantize_rows_e4m3(const void* w, int64_t N, int64_t K, int64_t ldw, void* codes, float* scale, mpv_stream_t stream);
+int mpv_gemm_w8(const void* A, const void* codes, const float* scale, void* C, int64_t M, int64_t N, int64_t K, int64_t lda,
+                int64_t ldw, int64_t ldc, const mpv_gemm_epilogue* ep, mpv_stream_t stream);
+int mpv_gpt_embed_w8_fwd(const void* query, const int64_t* ids, const void* wte_codes, const float* wte_scale, const void* wpe, void* h,
+                         int B, int Q, int L, int H, mpv_stream_t stream);
+/* The decode steps on FP8 weights: mpv_gpt_decode_step / mpv_gpt_decode_step_shared with every weight product of at most
+ * MPV_W8_MAX_ROWS rows going to mpv_gemm_w8 on q8's codes (a larger one -- a many-clip prefill -- goes to mpv_gemm_bf16 on w's bf16
+ * weights) and the token embedding read from the tied embedding's codes.  Everything else (norms, attention, biases, position
+ * embedding, workspace) is w's.  q8->layers must equal w->layers. */
+#define MPV_W8_MAX_ROWS 96 /* measured (profiles/decode_w8.json): the largest row count at which the FP8 product is not slower than
+                              mpv_gemm_bf16 on most of the 1.3B decoder's four layer shapes */
+typedef struct mpv_gpt_layer_weights_q8 {
+  const void *qkv_q, *qkv_s, *dense_q, *dense_s, *fc1_q, *fc1_s, *fc2_q, *fc2_s; /* codes uint8 [N][K], scales fp32 [N] */
+} mpv_gpt_layer_weights_q8;
+typedef struct mpv_gpt_weights_q8 {
+  int layers;
+  const mpv_gpt_layer_weights_q8* layer;
+  const void *wte_q, *wte_s; /* the tied embedding / LM head: codes [vocab][hidden], scales [vocab] */
+} mpv_gpt_weights_q8;
+int mpv_gpt_decode_step_q8(const mpv_gpt_weights* w, const mpv_gpt_weights_q8* q8, void* const* kv_cache, int batch, int max_len,
+                           int pos0, const void* query, int Q, const int64_t* tokens, int L, void* workspace, size_t workspace_bytes,
+                           void* logits, mpv_stream_t stream);
+int mpv_gpt_decode_step_shared_q8(const mpv_gpt_weights* w, const mpv_gpt_weights_q8* q8, void* const* prefix_cache,
+                                  void* const* suffix_cache, int n_groups, int fan, int prefix_len, int suffix_max, int t,
+                                  const int64_t* tokens, void* workspace, size_t workspace_bytes, void* logits, mpv_stream_t stream);
+/* ------------------------------------------------------------------------------------------
  * Lockstep beam search over a batch of clips (caption evaluation, generation.beam_search_batched_loop): ONE launch advances the
  * beam state of `batch` clips x `beams` (K) beams by one position, doing per clip exactly what one iteration of the reference's
  * beam_search does on the host (models/modeling_distributed_gpt3.py:1793-1840 with BeamHypotheses.add / is_done, :1908-1960).

@@ -250,6 +250,16 @@ class GptWeights(C.Structure):
                 ("max_positions", c_int)]
 
 
+class GptLayerWeightsQ8(C.Structure):
+    _fields_ = [(n, c_void_p) for n in ("qkv_q", "qkv_s", "dense_q", "dense_s", "fc1_q", "fc1_s", "fc2_q", "fc2_s")]
+
+
+class GptWeightsQ8(C.Structure):
+    _fields_ = [("layers", c_int), ("layer", C.POINTER(GptLayerWeightsQ8)), ("wte_q", c_void_p), ("wte_s", c_void_p)]
+
+
+W8_MAX_ROWS = 96       # include/mpv.h MPV_W8_MAX_ROWS
+
 _SIGS.update({
     "mpv_gpt_decode_workspace_size": (c_size_t, [C.POINTER(GptWeights), c_int, c_int]),
     "mpv_gpt_decode_step": (c_int, [C.POINTER(GptWeights), C.POINTER(c_void_p), c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
@@ -258,6 +268,14 @@ _SIGS.update({
     "mpv_gpt_decode_shared_workspace_size": (c_size_t, [C.POINTER(GptWeights), c_int]),
     "mpv_gpt_decode_step_shared": (c_int, [C.POINTER(GptWeights), C.POINTER(c_void_p), C.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int,
                                            c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "mpv_quantize_rows_e4m3": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "mpv_gemm_w8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64,
+                            C.POINTER(GemmEpilogue), c_void_p]),
+    "mpv_gpt_embed_w8_fwd": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p]),
+    "mpv_gpt_decode_step_q8": (c_int, [C.POINTER(GptWeights), C.POINTER(GptWeightsQ8), C.POINTER(c_void_p), c_int, c_int, c_int, c_void_p,
+                                       c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "mpv_gpt_decode_step_shared_q8": (c_int, [C.POINTER(GptWeights), C.POINTER(GptWeightsQ8), C.POINTER(c_void_p), C.POINTER(c_void_p), c_int,
+                                              c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
 })
 
 EXPORTS = tuple(_SIGS)

@@ -20,38 +20,75 @@ extern "C" size_t mpv_gpt_decode_workspace_size(const mpv_gpt_weights* w, int ba
          mpv_gemm_workspace_size(R, w->ffn, w->hidden, 0, 0);
 }
 
+// One weight product of a step, C[M, N] = epi(A[M, K] W[N, K]^T) with dense operands: on the bf16 weight, or -- in the _q8 entries
+// (codes != nullptr) for at most MPV_W8_MAX_ROWS rows -- on its e4m3 codes (include/mpv.h, "FP8 decoder weights").
+struct Products {
+  void* gws;
+  size_t gws_bytes;
+  hipStream_t stream;
+  int operator()(const void* A, const void* w_bf16, const void* codes, const void* scale, void* C, int64_t M, int64_t N, int64_t K,
+                 const mpv_gemm_epilogue* ep) const {
+    if (codes && M <= MPV_W8_MAX_ROWS) return mpv_gemm_w8(A, codes, (const float*)scale, C, M, N, K, K, K, N, ep, stream);
+    return mpv_gemm_bf16(A, w_bf16, C, M, N, K, K, K, N, 0, 0, ep, gws, gws_bytes, stream);
+  }
+};
+static const mpv_gpt_layer_weights_q8 NO_Q8_LAYER = {};
+
 // what follows the attention in a layer: dense + residual, LN2, fc1 + GELU, fc2 + residual (the layer output lands in h)
-static int layer_tail(const mpv_gpt_weights* w, const mpv_gpt_layer_weights* lw, int64_t R, void* h, void* x, void* ctx, void* h1,
-                      void* g, void* gws, size_t gws_bytes, hipStream_t stream) {
+static int layer_tail(const mpv_gpt_weights* w, const mpv_gpt_layer_weights* lw, const mpv_gpt_layer_weights_q8* lq, int64_t R, void* h,
+                      void* x, void* ctx, void* h1, void* g, const Products& product) {
   const int H = w->hidden, F4 = w->ffn;
+  hipStream_t stream = product.stream;
   mpv_gemm_epilogue e1 = {};
   e1.bias = lw->dense_b; e1.residual = h; e1.ldr = H;
-  int rc = mpv_gemm_bf16(ctx, lw->dense_w, h1, R, H, H, H, H, H, 0, 0, &e1, gws, gws_bytes, stream);
+  int rc = product(ctx, lw->dense_w, lq->dense_q, lq->dense_s, h1, R, H, H, &e1);
   if (rc) return rc;
   rc = mpv_layernorm_fwd(h1, lw->ln2_w, lw->ln2_b, x, nullptr, nullptr, R, H, H, H, w->ln_eps, 0, 0, 0, 0, 0, 0, stream);
   if (rc) return rc;
   mpv_gemm_epilogue e2 = {};
   e2.bias = lw->fc1_b; e2.act = MPV_ACT_GELU_TANH;
-  rc = mpv_gemm_bf16(x, lw->fc1_w, g, R, F4, H, H, H, F4, 0, 0, &e2, gws, gws_bytes, stream);
+  rc = product(x, lw->fc1_w, lq->fc1_q, lq->fc1_s, g, R, F4, H, &e2);
   if (rc) return rc;
   mpv_gemm_epilogue e3 = {};
   e3.bias = lw->fc2_b; e3.residual = h1; e3.ldr = H;
   // the layer input `h` was last read by the dense GEMM (as its residual): its buffer takes the layer output
-  return mpv_gemm_bf16(g, lw->fc2_w, h, R, H, F4, F4, F4, H, 0, 0, &e3, gws, gws_bytes, stream);
+  return product(g, lw->fc2_w, lq->fc2_q, lq->fc2_s, h, R, H, F4, &e3);
 }
 
 // final LN + tied LM head on one row per sequence
-static int lm_head(const mpv_gpt_weights* w, const void* lastrow, void* xf, int batch, void* logits, void* gws, size_t gws_bytes,
-                   hipStream_t stream) {
+static int lm_head(const mpv_gpt_weights* w, const mpv_gpt_weights_q8* q8, const void* lastrow, void* xf, int batch, void* logits,
+                   const Products& product) {
   const int H = w->hidden;
-  const int rc = mpv_layernorm_fwd(lastrow, w->lnf_w, w->lnf_b, xf, nullptr, nullptr, batch, H, H, H, w->ln_eps, 0, 0, 0, 0, 0, 0, stream);
+  const int rc = mpv_layernorm_fwd(lastrow, w->lnf_w, w->lnf_b, xf, nullptr, nullptr, batch, H, H, H, w->ln_eps, 0, 0, 0, 0, 0, 0,
+                                   product.stream);
   if (rc) return rc;
-  return mpv_gemm_bf16(xf, w->wte, logits, batch, w->vocab, H, H, H, w->vocab, 0, 0, nullptr, gws, gws_bytes, stream);
+  return product(xf, w->wte, q8 ? q8->wte_q : nullptr, q8 ? q8->wte_s : nullptr, logits, batch, w->vocab, H, nullptr);
 }
 
-extern "C" int mpv_gpt_decode_step(const mpv_gpt_weights* w, void* const* kv_cache, int batch, int max_len, int pos0,
-                                   const void* query, int Q, const int64_t* tokens, int L, void* workspace,
-                                   size_t workspace_bytes, void* logits, hipStream_t stream) {
+// the token / query rows of a step plus their position rows: from the bf16 embedding, or from the tied embedding's codes
+static int embed(const mpv_gpt_weights* w, const mpv_gpt_weights_q8* q8, const void* query, const int64_t* tokens, int pos0, void* h,
+                 int batch, int Q, int L, hipStream_t stream) {
+  const void* wpe = (const char*)w->wpe + (size_t)pos0 * w->hidden * 2;
+  if (q8) return mpv_gpt_embed_w8_fwd(query, tokens, q8->wte_q, (const float*)q8->wte_s, wpe, h, batch, Q, L, w->hidden, stream);
+  return mpv_gpt_embed_fwd(query, tokens, w->wte, wpe, h, batch, Q, L, w->hidden, 0.f, 0, 0, stream);
+}
+
+static int check_q8(const mpv_gpt_weights* w, const mpv_gpt_weights_q8* q8, const char* who) {
+  MPV_REQUIRE(w && q8, MPV_E_ARG, "%s: null pointer", who);
+  MPV_REQUIRE(q8->layers == w->layers && q8->layer && q8->wte_q && q8->wte_s, MPV_E_ARG, "%s: the FP8 table has %d layers, the decoder %d",
+              who, q8->layers, w->layers);
+  for (int li = 0; li < w->layers; ++li) {
+    const mpv_gpt_layer_weights_q8* l = &q8->layer[li];
+    MPV_REQUIRE(l->qkv_q && l->qkv_s && l->dense_q && l->dense_s && l->fc1_q && l->fc1_s && l->fc2_q && l->fc2_s, MPV_E_ARG,
+                "%s: null codes or scales in layer %d", who, li);
+  }
+  return MPV_OK;
+}
+
+// the body of mpv_gpt_decode_step and mpv_gpt_decode_step_q8 (q8 == nullptr: the bf16 step)
+static int decode_step(const mpv_gpt_weights* w, const mpv_gpt_weights_q8* q8, void* const* kv_cache, int batch, int max_len, int pos0,
+                       const void* query, int Q, const int64_t* tokens, int L, void* workspace, size_t workspace_bytes, void* logits,
+                       hipStream_t stream) {
   MPV_REQUIRE(w && kv_cache && workspace && logits, MPV_E_ARG, "mpv_gpt_decode_step: null pointer");
   const int n = Q + L, H = w->hidden, np = w->heads, hn = H / np, F4 = w->ffn;
   MPV_REQUIRE(batch > 0 && n > 0 && pos0 >= 0 && pos0 + n <= max_len, MPV_E_SHAPE,
@@ -68,19 +105,19 @@ extern "C" int mpv_gpt_decode_step(const mpv_gpt_weights* w, void* const* kv_cac
   void* g = carve(p, R * F4 * 2);
   void* last = carve(p, (size_t)batch * H * 2);
   void* xf = carve(p, (size_t)batch * H * 2);
-  void* gws = p;
-  const size_t gws_bytes = workspace_bytes - (size_t)(p - (char*)workspace);
-  int rc = mpv_gpt_embed_fwd(query, tokens, w->wte, (const char*)w->wpe + (size_t)pos0 * H * 2, h, batch, Q, L, H, 0.f, 0, 0, stream);
+  const Products product = {p, workspace_bytes - (size_t)(p - (char*)workspace), stream};
+  int rc = embed(w, q8, query, tokens, pos0, h, batch, Q, L, stream);
   if (rc) return rc;
   for (int li = 0; li < w->layers; ++li) {
     const mpv_gpt_layer_weights* lw = &w->layer[li];
+    const mpv_gpt_layer_weights_q8* lq = q8 ? &q8->layer[li] : &NO_Q8_LAYER;
     char* c = (char*)kv_cache[li];
     rc = mpv_layernorm_fwd(h, lw->ln1_w, lw->ln1_b, x, nullptr, nullptr, R, H, H, H, w->ln_eps, 0, 0, 0, 0, 0, 0, stream);
     if (rc) return rc;
     mpv_gemm_epilogue ep = {};
     ep.bias = lw->qkv_b;
     ep.c_group = n; ep.c_stride = max_len; ep.c_offset = pos0;                 // the new rows land in the cache
-    rc = mpv_gemm_bf16(x, lw->qkv_w, c, R, 3 * H, H, H, H, 3 * H, 0, 0, &ep, gws, gws_bytes, stream);
+    rc = product(x, lw->qkv_w, lq->qkv_q, lq->qkv_s, c, R, 3 * H, H, &ep);
     if (rc) return rc;
     mpv_attn_desc d = {};
     d.q = c + (size_t)pos0 * 3 * H * 2;
@@ -96,7 +133,7 @@ extern "C" int mpv_gpt_decode_step(const mpv_gpt_weights* w, void* const* kv_cac
     d.scale = 1.0f / sqrtf((float)hn);
     rc = mpv_attn_fwd(&d, stream);
     if (rc) return rc;
-    rc = layer_tail(w, lw, R, h, x, ctx, h1, g, gws, gws_bytes, stream);
+    rc = layer_tail(w, lw, lq, R, h, x, ctx, h1, g, product);
     if (rc) return rc;
   }
   const void* lastrow = h;
@@ -105,7 +142,21 @@ extern "C" int mpv_gpt_decode_step(const mpv_gpt_weights* w, void* const* kv_cac
     if (rc) return rc;
     lastrow = last;
   }
-  return lm_head(w, lastrow, xf, batch, logits, gws, gws_bytes, stream);
+  return lm_head(w, q8, lastrow, xf, batch, logits, product);
+}
+
+extern "C" int mpv_gpt_decode_step(const mpv_gpt_weights* w, void* const* kv_cache, int batch, int max_len, int pos0,
+                                   const void* query, int Q, const int64_t* tokens, int L, void* workspace,
+                                   size_t workspace_bytes, void* logits, hipStream_t stream) {
+  return decode_step(w, nullptr, kv_cache, batch, max_len, pos0, query, Q, tokens, L, workspace, workspace_bytes, logits, stream);
+}
+
+extern "C" int mpv_gpt_decode_step_q8(const mpv_gpt_weights* w, const mpv_gpt_weights_q8* q8, void* const* kv_cache, int batch,
+                                      int max_len, int pos0, const void* query, int Q, const int64_t* tokens, int L, void* workspace,
+                                      size_t workspace_bytes, void* logits, hipStream_t stream) {
+  const int rc = check_q8(w, q8, "mpv_gpt_decode_step_q8");
+  if (rc) return rc;
+  return decode_step(w, q8, kv_cache, batch, max_len, pos0, query, Q, tokens, L, workspace, workspace_bytes, logits, stream);
 }
 
 // mpv_gpt_decode_step for one token per sequence against a per-group shared prefix cache (include/mpv.h states the contract)
@@ -113,9 +164,10 @@ extern "C" size_t mpv_gpt_decode_shared_workspace_size(const mpv_gpt_weights* w,
   return mpv_gpt_decode_workspace_size(w, n_seq, 1);
 }
 
-extern "C" int mpv_gpt_decode_step_shared(const mpv_gpt_weights* w, void* const* prefix_cache, void* const* suffix_cache, int n_groups,
-                                          int fan, int prefix_len, int suffix_max, int t, const int64_t* tokens, void* workspace,
-                                          size_t workspace_bytes, void* logits, hipStream_t stream) {
+// the body of mpv_gpt_decode_step_shared and mpv_gpt_decode_step_shared_q8 (q8 == nullptr: the bf16 step)
+static int decode_step_shared(const mpv_gpt_weights* w, const mpv_gpt_weights_q8* q8, void* const* prefix_cache, void* const* suffix_cache,
+                              int n_groups, int fan, int prefix_len, int suffix_max, int t, const int64_t* tokens, void* workspace,
+                              size_t workspace_bytes, void* logits, hipStream_t stream) {
   MPV_REQUIRE(w && prefix_cache && suffix_cache && tokens && workspace && logits, MPV_E_ARG, "mpv_gpt_decode_step_shared: null pointer");
   MPV_REQUIRE(n_groups > 0 && fan > 0 && (int64_t)n_groups * fan < (1ll << 31) && prefix_len > 0, MPV_E_SHAPE,
               "mpv_gpt_decode_step_shared: empty problem (n_groups %d, fan %d, prefix_len %d)", n_groups, fan, prefix_len);
@@ -135,13 +187,12 @@ extern "C" int mpv_gpt_decode_step_shared(const mpv_gpt_weights* w, void* const*
   void* g = carve(p, R * F4 * 2);
   carve(p, (size_t)n_seq * H * 2);                       // (the `last` rows of the general step: one position needs no copy)
   void* xf = carve(p, (size_t)n_seq * H * 2);
-  void* gws = p;
-  const size_t gws_bytes = workspace_bytes - (size_t)(p - (char*)workspace);
-  int rc = mpv_gpt_embed_fwd(nullptr, tokens, w->wte, (const char*)w->wpe + (size_t)(prefix_len + t) * H * 2, h, n_seq, 0, 1, H, 0.f, 0, 0,
-                             stream);
+  const Products product = {p, workspace_bytes - (size_t)(p - (char*)workspace), stream};
+  int rc = embed(w, q8, nullptr, tokens, prefix_len + t, h, n_seq, 0, 1, stream);
   if (rc) return rc;
   for (int li = 0; li < w->layers; ++li) {
     const mpv_gpt_layer_weights* lw = &w->layer[li];
+    const mpv_gpt_layer_weights_q8* lq = q8 ? &q8->layer[li] : &NO_Q8_LAYER;
     char* pc = (char*)prefix_cache[li];
     char* sc = (char*)suffix_cache[li];
     rc = mpv_layernorm_fwd(h, lw->ln1_w, lw->ln1_b, x, nullptr, nullptr, R, H, H, H, w->ln_eps, 0, 0, 0, 0, 0, 0, stream);
@@ -149,7 +200,7 @@ extern "C" int mpv_gpt_decode_step_shared(const mpv_gpt_weights* w, void* const*
     mpv_gemm_epilogue ep = {};
     ep.bias = lw->qkv_b;
     ep.c_group = 1; ep.c_stride = suffix_max; ep.c_offset = t;                // row s lands at suffix row s*suffix_max + t
-    rc = mpv_gemm_bf16(x, lw->qkv_w, sc, R, 3 * H, H, H, H, 3 * H, 0, 0, &ep, gws, gws_bytes, stream);
+    rc = product(x, lw->qkv_w, lq->qkv_q, lq->qkv_s, sc, R, 3 * H, H, &ep);
     if (rc) return rc;
     mpv_attn_decode_shared_desc d = {};
     d.q = sc + (size_t)t * 3 * H * 2;
@@ -168,10 +219,27 @@ extern "C" int mpv_gpt_decode_step_shared(const mpv_gpt_weights* w, void* const*
     d.scale = 1.0f / sqrtf((float)hn);
     rc = mpv_attn_decode_shared_fwd(&d, stream);
     if (rc) return rc;
-    rc = layer_tail(w, lw, R, h, x, ctx, h1, g, gws, gws_bytes, stream);
+    rc = layer_tail(w, lw, lq, R, h, x, ctx, h1, g, product);
     if (rc) return rc;
   }
-  return lm_head(w, h, xf, n_seq, logits, gws, gws_bytes, stream);
+  return lm_head(w, q8, h, xf, n_seq, logits, product);
+}
+
+extern "C" int mpv_gpt_decode_step_shared(const mpv_gpt_weights* w, void* const* prefix_cache, void* const* suffix_cache, int n_groups,
+                                          int fan, int prefix_len, int suffix_max, int t, const int64_t* tokens, void* workspace,
+                                          size_t workspace_bytes, void* logits, hipStream_t stream) {
+  return decode_step_shared(w, nullptr, prefix_cache, suffix_cache, n_groups, fan, prefix_len, suffix_max, t, tokens, workspace,
+                            workspace_bytes, logits, stream);
+}
+
+extern "C" int mpv_gpt_decode_step_shared_q8(const mpv_gpt_weights* w, const mpv_gpt_weights_q8* q8, void* const* prefix_cache,
+                                             void* const* suffix_cache, int n_groups, int fan, int prefix_len, int suffix_max, int t,
+                                             const int64_t* tokens, void* workspace, size_t workspace_bytes, void* logits,
+                                             hipStream_t stream) {
+  const int rc = check_q8(w, q8, "mpv_gpt_decode_step_shared_q8");
+  if (rc) return rc;
+  return decode_step_shared(w, q8, prefix_cache, suffix_cache, n_groups, fan, prefix_len, suffix_max, t, tokens, workspace, workspace_bytes,
+                            logits, stream);
 }
 
 // InferenceParams.swap_key_value_dict (:1459-1473) for every layer: dst[l][j] = src[l][idx[j]], first `rows` positions

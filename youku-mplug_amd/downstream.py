@@ -334,7 +334,7 @@ class DistributedGPT3_Caption(_GenCls):
     def generate(self, image, text, termination_id=None, batched=False, clips_per_search=32, do_sample=False, num_samples=1, temperature=1.0,
                  top_k=None, top_p=None, seed=0, kv_cache="per_sequence", repetition_penalty=None, no_repeat_ngram_size=0, min_new_tokens=0,
                  banned_token_ids=None, constrain_prompt=False, return_scores=False, best_of=False, length_penalty=1.0, query_features=None,
-                 beam_groups=1, diversity_penalty=0.0, rerank_by_logprob=False, **kw):
+                 beam_groups=1, diversity_penalty=0.0, rerank_by_logprob=False, decode_weights="bf16", **kw):
         """One beam search per sample (:790-809): prompt = text.input_ids[i, :mask.sum()-1], prefix = its query features.
         batched=True (not in the reference, default off): the clips are grouped by prompt length and every group is searched in
         lockstep, `clips_per_search` clips at a time (generation.beam_search_batched_loop: the decoder's weights are read once per
@@ -386,9 +386,16 @@ class DistributedGPT3_Caption(_GenCls):
         best_sample's choice.  A hypothesis that fills its row without a termination token is scored whole, terminator included: one
         position more than the search fed, at most the LAST row of the position table (the search generates up to column final_len - 1
         and never feeds it; the scoring does) -- never outside it.  scores[i] is score_captions' dict in the new order (best = 0) plus group [n] int64, the group every row
-        came from (zeros without groups)."""
+        came from (zeros without groups).
+        decode_weights="fp8" (every path; default "bf16"): the decode steps run on e4m3 codes of the decoder's weights, quantised on the
+        device on first use (generation.DecodeWeightsQ8; the scoring of rerank_by_logprob stays on the bf16 weights).  It combines with
+        kv_cache, the constraints, the scores and the groups."""
         Q, Hh = self.num_learnable_token, self.text_width
         G = int(beam_groups)
+        from . import generation as _gen
+        _gen._check_weight_mode(decode_weights)
+        if decode_weights != "bf16":
+            kw = dict(kw, decode_weights=decode_weights)                 # absent keyword: the calls below are today's
         if G != 1 and (do_sample or not batched):
             raise ValueError(f"beam_groups={beam_groups!r} needs batched=True without do_sample: the per-clip search and the samplers have no groups")
         if rerank_by_logprob and (do_sample or not batched):

@@ -13,7 +13,8 @@ search over a batch of clips (beam_search_batched_loop) keeps it on the device (
 csrc/beam_search.hip), and so does sampled generation in lockstep (sample_batched_loop: ops.sample_advance, csrc/sampling.hip; with
 return_scores ops.sample_score, csrc/sample_score.hip, records every drawn token's log-probability).  The lockstep loops can also keep
 the positions all sequences of a clip share (visual prefix + prompt) once per clip: SharedPrefixDecodeState (kv="shared_prefix";
-mpv_gpt_decode_step_shared, csrc/decode_shared_attention.hip).
+mpv_gpt_decode_step_shared, csrc/decode_shared_attention.hip).  decode_weights="fp8" (default "bf16") runs the steps of any of these
+loops on e4m3 codes of the decoder's weights (DecodeWeightsQ8; mpv_gpt_decode_step_q8 / _shared_q8, csrc/gemm_w8.hip).
 """
 from __future__ import annotations
 
@@ -57,15 +58,75 @@ class BeamHypotheses:
         return self.worst_score >= best_sum_logprobs / cur_len ** self.length_penalty        # :1958-1960
 
 
+WEIGHT_MODES = ("bf16", "fp8")
+
+
+def _check_weight_mode(weights):
+    if weights not in WEIGHT_MODES:
+        raise ValueError(f"decode_weights must be one of {WEIGHT_MODES} (got {weights!r})")
+
+
+class DecodeWeightsQ8:
+    """Weight-only FP8 copy of a frozen decoder for the decode steps (include/mpv.h, "FP8 decoder weights"): e4m3fn codes and one
+    power-of-two fp32 scale per output row of every layer's qkv / dense / fc1 / fc2 weight and of the tied embedding (the LM head),
+    quantised on the device, once (DistributedGPT3.quantize_decode_weights).  The bf16 parameters stay where they are -- this is an
+    extra 0.5 x of the quantised tensors.  deq(code) * scale is a bf16 number, so the FP8 steps compute exactly the function of
+    the bf16 decoder with dequantized() loaded.  The rounding to e4m3 itself is about 2.7 % relative L2 noise per product (computed
+    on the CPU for Gaussian rows; the bf16 gates of this project are 1e-2).  What it costs in caption quality on a trained
+    checkpoint has NOT been measured -- no checkpoint exists here; running the unchanged bf16 stack with
+    DistributedGPT3.dequantized_state_dict() loaded measures exactly that cost.
+    Every source parameter's _version (and storage address) is recorded: stale() is True once any of them has been written to, or
+    moved, since."""
+
+    SITES = (("qkv", lambda l: l.self_attention.query_key_value), ("dense", lambda l: l.self_attention.dense),
+             ("fc1", lambda l: l.mlp.dense_h_to_4h), ("fc2", lambda l: l.mlp.dense_4h_to_h))
+
+    def __init__(self, gpt):
+        lm = gpt.dist_model.language_model
+        self.sources = [site(layer).weight for layer in lm.encoder.layers for _, site in self.SITES] + [lm.embedding.word_embeddings.weight]
+        for p in self.sources:
+            if p.dtype != torch.bfloat16 or p.dim() != 2 or not p.is_contiguous():
+                raise ValueError("quantize_decode_weights takes contiguous 2-D bf16 weights")
+        self.tensors = [ops.quantize_rows_e4m3(p.detach()) for p in self.sources]       # (codes uint8 [N, K], scale fp32 [N]) per source
+        self.versions = [(p._version, p.data_ptr()) for p in self.sources]
+
+    def stale(self) -> bool:
+        return any((p._version, p.data_ptr()) != v for p, v in zip(self.sources, self.versions))
+
+    def table(self):
+        """-> (_lib.GptWeightsQ8, what it points into): the C table of the step entries"""
+        from . import _lib
+        nl = len(self.tensors) // len(self.SITES)
+        layers = (_lib.GptLayerWeightsQ8 * nl)()
+        for i in range(nl):
+            for j, (name, _) in enumerate(self.SITES):
+                codes, scale = self.tensors[i * len(self.SITES) + j]
+                setattr(layers[i], name + "_q", codes.data_ptr())
+                setattr(layers[i], name + "_s", scale.data_ptr())
+        return _lib.GptWeightsQ8(nl, layers, self.tensors[-1][0].data_ptr(), self.tensors[-1][1].data_ptr()), layers
+
+    def dequantized(self):
+        """-> the bf16 tensors deq(code) * scale, in the order of self.sources"""
+        return [(codes.view(torch.float8_e4m3fn).float() * scale[:, None]).to(torch.bfloat16) for codes, scale in self.tensors]
+
+    def nbytes(self) -> int:
+        return sum(c.numel() + 4 * s.numel() for c, s in self.tensors)
+
+
 class DecodeState:
     """Per-generation KV caches of a DistributedGPT3 (the InferenceParams of :1444-1473).  A step is ONE call into the
     C ABI (mpv_gpt_decode_step issues every launch of the incremental forward; the step is launch-bound otherwise)."""
 
-    def __init__(self, gpt, batch: int, max_len: int):
+    def __init__(self, gpt, batch: int, max_len: int, weights: str = "bf16"):
         import ctypes as C
         from . import _lib
+        _check_weight_mode(weights)
         cfg = gpt.config
         self.gpt, self.batch, self.max_len = gpt, batch, max_len
+        self.q8 = None                        # weights="fp8": the decoder's DecodeWeightsQ8 (re-quantised if a weight has moved)
+        if weights == "fp8":
+            self.q8 = gpt.decode_weights_q8()
+            self._q8, self._q8_layers = self.q8.table()
         self.H, self.np_, self.hn, self.V = cfg.hidden_size, cfg.num_attention_heads, cfg.kv_channels, cfg.vocab_size
         assert self.V % 8 == 0, "vocab_size must be a multiple of 8"
         lm = gpt.dist_model.language_model
@@ -109,8 +170,12 @@ class DecodeState:
         wsn = _lib.lib().mpv_gpt_decode_workspace_size(C.byref(self._w), B, Q + L)
         ws = ops.workspace(wsn, self.cache.device)
         logits = torch.empty((B, self.V), dtype=torch.bfloat16, device=self.cache.device)
-        ops.check(_lib.lib().mpv_gpt_decode_step(C.byref(self._w), self._cache_ptrs, B, self.max_len, self.pos, ops._p(qf), Q, ops._p(ids), L,
-                                                 ws.data_ptr(), ws.numel(), logits.data_ptr(), ops._stream()), "mpv_gpt_decode_step")
+        tail = (self._cache_ptrs, B, self.max_len, self.pos, ops._p(qf), Q, ops._p(ids), L, ws.data_ptr(), ws.numel(), logits.data_ptr(),
+                ops._stream())
+        if self.q8 is None:
+            ops.check(_lib.lib().mpv_gpt_decode_step(C.byref(self._w), *tail), "mpv_gpt_decode_step")
+        else:
+            ops.check(_lib.lib().mpv_gpt_decode_step_q8(C.byref(self._w), C.byref(self._q8), *tail), "mpv_gpt_decode_step_q8")
         self.pos += Q + L
         return logits
 
@@ -183,8 +248,9 @@ class SharedPrefixDecodeState:
     Resident KV: nl * (G * P + (1 or 2) * batch * S) * 3H * 2 bytes (the twin exists once a re-order has moved rows) against
     nl * 2 * batch * (P + S) * 3H * 2 of DecodeState."""
 
-    def __init__(self, gpt, batch: int, max_len: int):
-        self.gpt, self.batch, self.max_len = gpt, batch, max_len
+    def __init__(self, gpt, batch: int, max_len: int, weights: str = "bf16"):
+        _check_weight_mode(weights)
+        self.gpt, self.batch, self.max_len, self.weights = gpt, batch, max_len, weights
         self.prefix = None                    # the DecodeState of the prefill: its cache is the prefix cache
         self.suffix = self.twin = None
         self.fan = self.P = self.S = 0
@@ -203,7 +269,7 @@ class SharedPrefixDecodeState:
         P = (0 if query_embeds is None else query_embeds.shape[1]) + (0 if tokens is None else tokens.shape[1])
         if not 0 < P < self.max_len:
             raise ValueError(f"a shared prefix of {P} positions leaves no room in max_len {self.max_len}")
-        self.prefix = DecodeState(self.gpt, G, P)
+        self.prefix = DecodeState(self.gpt, G, P, self.weights)
         logits = self.prefix.step(tokens, query_embeds)
         self.fan, self.P, self.S = fan, P, self.max_len - P
         st = self.prefix
@@ -233,9 +299,12 @@ class SharedPrefixDecodeState:
         wsn = _lib.lib().mpv_gpt_decode_shared_workspace_size(C.byref(st._w), self.batch)
         ws = ops.workspace(wsn, dev)
         logits = torch.empty((self.batch, st.V), dtype=torch.bfloat16, device=dev)
-        ops.check(_lib.lib().mpv_gpt_decode_step_shared(C.byref(st._w), st._cache_ptrs, self._suffix_ptrs, self.batch // self.fan, self.fan,
-                                                        self.P, self.S, self.t, tokens.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                        logits.data_ptr(), ops._stream()), "mpv_gpt_decode_step_shared")
+        tail = (st._cache_ptrs, self._suffix_ptrs, self.batch // self.fan, self.fan, self.P, self.S, self.t, tokens.data_ptr(), ws.data_ptr(),
+                ws.numel(), logits.data_ptr(), ops._stream())
+        if st.q8 is None:
+            ops.check(_lib.lib().mpv_gpt_decode_step_shared(C.byref(st._w), *tail), "mpv_gpt_decode_step_shared")
+        else:
+            ops.check(_lib.lib().mpv_gpt_decode_step_shared_q8(C.byref(st._w), C.byref(st._q8), *tail), "mpv_gpt_decode_step_shared_q8")
         return logits
 
     def reorder(self, batch_idx: torch.Tensor, shared_prefix: Optional[int] = None):
@@ -267,13 +336,17 @@ class SharedPrefixDecodeState:
 KV_MODES = ("per_sequence", "shared_prefix")
 
 
-def make_state_fn(gpt, kv: str = "per_sequence"):
+def make_state_fn(gpt, kv: str = "per_sequence", weights: str = "bf16"):
     """The make_state of the loops for the keyword `kv`: "per_sequence" (DecodeState: every sequence owns a full cache) or
-    "shared_prefix" (SharedPrefixDecodeState; the lockstep loops only)."""
+    "shared_prefix" (SharedPrefixDecodeState; the lockstep loops only), and for `weights`: "bf16", or "fp8" (the steps run on the
+    decoder's DecodeWeightsQ8, which the first such state quantises)."""
     if kv not in KV_MODES:
         raise ValueError(f"kv must be one of {KV_MODES} (got {kv!r})")
+    _check_weight_mode(weights)
     cls = DecodeState if kv == "per_sequence" else SharedPrefixDecodeState
-    return lambda batch, max_len: cls(gpt, batch, max_len)
+    if weights == "bf16":
+        return lambda batch, max_len: cls(gpt, batch, max_len)
+    return lambda batch, max_len: cls(gpt, batch, max_len, weights)
 
 
 # ---------------------------------------------------------------------------------------------- sampling helpers
@@ -729,38 +802,40 @@ def install(gpt_cls):
     """Adds sample / beam_search / generate to DistributedGPT3 (same signatures as the reference methods), and beam_search_batched /
     sample_batched."""
 
-    def sample(self, tokens, query_embeds=None, temperature=1.0, **kw):
+    def sample(self, tokens, query_embeds=None, temperature=1.0, decode_weights="bf16", **kw):
         _no_sample_scores(kw.pop("return_scores", False), "sample")
-        return sample_loop(_gen_config(self), make_state_fn(self), tokens, query_embeds=query_embeds, temperature=temperature, **kw)
+        return sample_loop(_gen_config(self), make_state_fn(self, weights=decode_weights), tokens, query_embeds=query_embeds, temperature=temperature, **kw)
 
-    def beam_search(self, tokens, query_embeds=None, beam_size=5, num_return_gen=1, stop_token=None, **kw):
+    def beam_search(self, tokens, query_embeds=None, beam_size=5, num_return_gen=1, stop_token=None, decode_weights="bf16", **kw):
         _no_sample_scores(kw.pop("return_scores", False), "beam_search")
-        return beam_search_loop(_gen_config(self), make_state_fn(self), tokens, query_embeds=query_embeds, beam_size=beam_size,
+        return beam_search_loop(_gen_config(self), make_state_fn(self, weights=decode_weights), tokens, query_embeds=query_embeds, beam_size=beam_size,
                                 num_return_gen=num_return_gen, stop_token=stop_token, prompt_length=kw.pop("prompt_length", None),
                                 topk_fn=lambda lg, k, add: ops.logprob_topk(lg, k, add=add))
 
     def beam_search_batched(self, tokens, query_embeds=None, beam_size=5, num_return_gen=1, stop_token=None, kv="per_sequence",
-                            constraints=None, beam_groups=1, diversity_penalty=0.0, **kw):
+                            constraints=None, beam_groups=1, diversity_penalty=0.0, decode_weights="bf16", **kw):
         """beam_search for tokens [B, L] / query_embeds [B, Q, H] with one prompt length, B clips in lockstep -> a list of B results;
         kv="shared_prefix" keeps the visual prefix and the prompt once per clip (SharedPrefixDecodeState); constraints: a
         LogitsConstraints, applied on the device every step; beam_groups = G > 1: diverse beam search, G groups of beam_size beams
-        each with diversity_penalty between them (beam_search_batched_loop; ops.beam_advance_groups)"""
+        each with diversity_penalty between them (beam_search_batched_loop; ops.beam_advance_groups); decode_weights="fp8": the steps
+        run on the decoder's e4m3 codes (DecodeWeightsQ8)"""
         _no_sample_scores(kw.pop("return_scores", False), "beam_search_batched")
         groups = {} if int(beam_groups) == 1 else dict(beam_groups=beam_groups, diversity_penalty=diversity_penalty,
                                                        group_advance_fn=ops.beam_advance_groups)      # one group: today's call
-        return beam_search_batched_loop(_gen_config(self), make_state_fn(self, kv), tokens, query_embeds=query_embeds, beam_size=beam_size,
+        return beam_search_batched_loop(_gen_config(self), make_state_fn(self, kv, decode_weights), tokens, query_embeds=query_embeds, beam_size=beam_size,
                                         num_return_gen=num_return_gen, stop_token=stop_token, prompt_length=kw.pop("prompt_length", None),
                                         topk_fn=lambda lg, k, add: ops.logprob_topk(lg, k, add=add), advance_fn=ops.beam_advance,
                                         constraints=constraints, constrain_fn=ops.logits_constrain, **groups)
 
     def sample_batched(self, tokens, query_embeds=None, temperature=1.0, num_samples=1, seed=0, streams=None, top_k=None, top_p=None,
-                       kv="per_sequence", constraints=None, return_scores=False, **kw):
+                       kv="per_sequence", constraints=None, return_scores=False, decode_weights="bf16", **kw):
         """sample with the sampler on the device (sample_batched_loop): tokens [B, L] -> [B * num_samples, n]; top_k / top_p override
         the configuration's values; the draws are those of (seed, position, streams[row]) -- not torch's generator;
         kv="shared_prefix" keeps the visual prefix and the shortest prompt once per clip (SharedPrefixDecodeState); constraints: a
         LogitsConstraints, applied on the device every step; return_scores=True: -> (tokens, SampleScores), the model's
-        log-probability of every generated token, recorded on the device every step (ops.sample_score)"""
-        make_state = make_state_fn(self, kv)
+        log-probability of every generated token, recorded on the device every step (ops.sample_score); decode_weights="fp8": the
+        steps run on the decoder's e4m3 codes (DecodeWeightsQ8)"""
+        make_state = make_state_fn(self, kv, decode_weights)
         cfg = _gen_config(self)
         if top_k is not None or top_p is not None:
             cfg.top_k, cfg.top_p = int(top_k or 0), float(top_p or 0.0)
@@ -773,8 +848,10 @@ def install(gpt_cls):
     def generate(self, tokens, do_sample=True, termination_id=None, *args, **kw):                # :1875-1880
         """sampler="device" (keyword; not in the reference, default "torch"): do_sample=True runs sample_batched, which takes
         kv="per_sequence" | "shared_prefix" (the per-clip loops keep a cache per sequence) and constraints= (a LogitsConstraints; the
-        per-clip loops have none) and return_scores=True (-> (tokens, SampleScores); refused everywhere else)"""
+        per-clip loops have none) and return_scores=True (-> (tokens, SampleScores); refused everywhere else).
+        decode_weights="fp8" (every loop; default "bf16"): the decode steps run on e4m3 codes of the weights (DecodeWeightsQ8)"""
         sampler = kw.pop("sampler", "torch")
+        _check_weight_mode(kw.get("decode_weights", "bf16"))
         if sampler not in ("torch", "device"):
             raise ValueError(f"sampler must be 'torch' or 'device' (got {sampler!r})")
         if kw.get("kv", "per_sequence") not in KV_MODES:

@@ -184,6 +184,32 @@ class DistributedGPT3(nn.Module):
         self.step_seed = 0        # bumped by the engine every step -> fresh dropout masks
         self.seed_dev = None      # engine.enable_device_step_state(): int64[4] device tensor, seed of decoder pass k of this step
 
+    # -------------------------------------------------------------- FP8 weights of the decode steps (generation.DecodeWeightsQ8)
+    def quantize_decode_weights(self):
+        """Quantises the layer products' weights and the tied embedding to e4m3 codes with per-row power-of-two scales, on the
+        device, once, and keeps the result on the decoder (decode_weights="fp8" does this on first use, and again when a source
+        parameter has been written to since).  -> the generation.DecodeWeightsQ8."""
+        self._decode_weights_q8 = _generation.DecodeWeightsQ8(self)
+        return self._decode_weights_q8
+
+    def clear_decode_weights(self):
+        """Drops the FP8 copy (the attribute too)."""
+        if "_decode_weights_q8" in self.__dict__:
+            del self._decode_weights_q8
+
+    def decode_weights_q8(self):
+        """The current FP8 copy: quantised now if there is none or a source parameter's _version has moved."""
+        q8 = self.__dict__.get("_decode_weights_q8")
+        return self.quantize_decode_weights() if q8 is None or q8.stale() else q8
+
+    def dequantized_state_dict(self) -> dict:
+        """The bf16 tensors deq(code) * scale of the FP8 copy under the parameters' own state-dict keys (the quantised tensors only:
+        load with strict=False).  The unchanged bf16 stack with these loaded computes what decode_weights="fp8" computes -- for
+        tests, and for measuring the quality cost of the quantisation through any existing path."""
+        q8 = self.decode_weights_q8()
+        names = {id(p): n for n, p in self.named_parameters()}
+        return {names[id(p)]: t for p, t in zip(q8.sources, q8.dequantized())}
+
     @property
     def trainable(self) -> bool:
         """freeze_text_decoder: false (models/distributed_gpt3.py:91-93): the decoder's own parameters receive gradients"""

@@ -668,6 +668,39 @@ def scatter_rows(src, idx, dst, rows, cols, ld=None):
     return dst
 
 
+def quantize_rows_e4m3(w: torch.Tensor, N: Optional[int] = None, K: Optional[int] = None, ldw: Optional[int] = None):
+    """include/mpv.h mpv_quantize_rows_e4m3: w [N, K] bf16 (row pitch ldw) -> (codes uint8 [N, K], scale fp32 [N]); e4m3fn codes of
+    w / scale with scale the power of two of the contract ("FP8 decoder weights")."""
+    _need_cuda(w)
+    N = w.shape[0] if N is None else N
+    K = w.shape[1] if K is None else K
+    ldw = (w.stride(0) if w.dim() == 2 else K) if ldw is None else ldw
+    codes = torch.empty((N, K), dtype=torch.uint8, device=w.device)
+    scale = torch.empty((N,), dtype=torch.float32, device=w.device)
+    check(_lib.lib().mpv_quantize_rows_e4m3(w.data_ptr(), N, K, ldw, codes.data_ptr(), scale.data_ptr(), _stream()), "mpv_quantize_rows_e4m3")
+    return codes, scale
+
+
+def gemm_w8(a: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor, M: int, N: int, K: int, *, out: Optional[torch.Tensor] = None,
+            lda: Optional[int] = None, ldw: Optional[int] = None, ldc: Optional[int] = None, bias=None, act: int = 0, residual=None,
+            ldr: int = 0, cmap: RowMap = IDENT, out_rows: Optional[int] = None, **other) -> torch.Tensor:
+    """include/mpv.h mpv_gemm_w8: C[M, N] = epi(scale[n] * sum_k A[m, k] deq(codes[n, k])), 1 <= M <= 512, the decode step's
+    epilogues only (bias, act = ACT_GELU_TANH, residual / ldr, cmap).  `other`: further GemmEpilogue fields by name -- the library
+    refuses every one of them."""
+    _need_cuda(a, codes, scale)
+    ldc = ldc if ldc is not None else N
+    if out is None:
+        out = torch.empty((out_rows if out_rows is not None else M, ldc), dtype=torch.bfloat16, device=a.device)
+    ep = GemmEpilogue()
+    ep.c_group, ep.c_stride, ep.c_offset = cmap
+    ep.bias, ep.act, ep.residual, ep.ldr = _p(bias), act, _p(residual), ldr
+    for k, v in other.items():
+        setattr(ep, k, v)
+    check(_lib.lib().mpv_gemm_w8(a.data_ptr(), codes.data_ptr(), scale.data_ptr(), out.data_ptr(), M, N, K, lda if lda is not None else K,
+                                 ldw if ldw is not None else K, ldc, C.byref(ep), _stream()), "mpv_gemm_w8")
+    return out
+
+
 def gather_rows_ld(src, idx, dst, rows, cols, lds, ldd):
     check(_lib.lib().mpv_gather_rows_ld(src.data_ptr(), idx.data_ptr(), dst.data_ptr(), rows, cols, lds, ldd, _stream()), "mpv_gather_rows_ld")
     return dst
