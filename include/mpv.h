@@ -500,19 +500,34 @@ int mpv_kv_reorder(void* const* src, void* const* dst, int layers, const int64_t
  *   what the product costs).  Shapes with K >= 4096 and N <= 4096 split K over 16 waves whose registers hold 8 row blocks: such a
  *   product goes out in launches of 128 rows.  The K-summation order of an
  *   output element depends on (N, K) only: row m of a 160-row call is bit-identical to the same row computed alone.  No atomics.
+ * mpv_gemm_w8_tiled: the same contract, shapes, epilogues and refusals, built for 97-512 rows (any M in [1, 512] is computed).  A
+ *   workgroup owns up to 128 rows x 64 columns over all of K: it stages its A tile through LDS in K-steps of 128 (coalesced
+ *   16-byte loads, shared by its four waves), each wave keeps the codes of its own 16 columns in registers, four K-steps of
+ *   loads are in flight.  An output element is one accumulator chain over ascending k: row m of a 512-row call is bit-identical to that row in
+ *   a 97-row or a 1-row call of this entry (NOT to mpv_gemm_w8, whose order differs; both are within the 1e-2 gate of the fp32
+ *   product).  K is not split over workgroups, so the workspace (which may be null) is not used and cannot change a result.
  * mpv_gpt_embed_w8_fwd: mpv_gpt_embed_fwd (no dropout) of the bf16 model above -- token rows are deq(code) * scale of the tied
  *   embedding's codes, query rows are copied, the position rows are added in fp32. */
 int mpv_quantize_rows_e4m3(const void* w, int64_t N, int64_t K, int64_t ldw, void* codes, float* scale, mpv_stream_t stream);
 int mpv_gemm_w8(const void* A, const void* codes, const float* scale, void* C, int64_t M, int64_t N, int64_t K, int64_t lda,
                 int64_t ldw, int64_t ldc, const mpv_gemm_epilogue* ep, mpv_stream_t stream);
+int mpv_gemm_w8_tiled(const void* A, const void* codes, const float* scale, void* C, int64_t M, int64_t N, int64_t K, int64_t lda,
+                      int64_t ldw, int64_t ldc, const mpv_gemm_epilogue* ep, void* workspace, size_t workspace_bytes, mpv_stream_t stream);
 int mpv_gpt_embed_w8_fwd(const void* query, const int64_t* ids, const void* wte_codes, const float* wte_scale, const void* wpe, void* h,
                          int B, int Q, int L, int H, mpv_stream_t stream);
-/* The decode steps on FP8 weights: mpv_gpt_decode_step / mpv_gpt_decode_step_shared with every weight product of at most
- * MPV_W8_MAX_ROWS rows going to mpv_gemm_w8 on q8's codes (a larger one -- a many-clip prefill -- goes to mpv_gemm_bf16 on w's bf16
- * weights) and the token embedding read from the tied embedding's codes.  Everything else (norms, attention, biases, position
- * embedding, workspace) is w's.  q8->layers must equal w->layers. */
+/* The decode steps on FP8 weights: mpv_gpt_decode_step / mpv_gpt_decode_step_shared with the token embedding read from the tied
+ * embedding's codes and every weight product of
+ *   at most MPV_W8_MAX_ROWS rows                          going to mpv_gemm_w8 on q8's codes,
+ *   MPV_W8_MAX_ROWS + 1 .. MPV_W8_TILED_MAX_ROWS rows     going to mpv_gemm_w8_tiled on q8's codes (the lockstep steps: 32 x 5 rows),
+ *   more rows (a many-clip prefill)                       going to mpv_gemm_bf16 on w's ORIGINAL bf16 weights.
+ * So "the quantised decoder is exactly the bf16 model dequantized_state_dict() returns" holds for a state whose products all stay
+ * within MPV_W8_TILED_MAX_ROWS rows; a larger prefill runs the original weights behind the dequantised embedding, which no single
+ * state dict reproduces.  Everything else (norms, attention, biases, position embedding, workspace) is w's.  q8->layers must
+ * equal w->layers. */
 #define MPV_W8_MAX_ROWS 96 /* measured (profiles/decode_w8.json): the largest row count at which the FP8 product is not slower than
                               mpv_gemm_bf16 on most of the 1.3B decoder's four layer shapes */
+#define MPV_W8_TILED_MAX_ROWS 512 /* measured (profiles/decode_w8.json): the largest of 128, 160, 256, 384, 512 rows up to which the
+                                     1.3B decoder's step sum on the codes is below the bf16 one by more than the run-to-run spread */
 typedef struct mpv_gpt_layer_weights_q8 {
   const void *qkv_q, *qkv_s, *dense_q, *dense_s, *fc1_q, *fc1_s, *fc2_q, *fc2_s; /* codes uint8 [N][K], scales fp32 [N] */
 } mpv_gpt_layer_weights_q8;

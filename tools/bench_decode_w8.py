@@ -2,10 +2,13 @@
 
     python tools/bench_decode_w8.py [--out profiles/decode_w8.json] [--rounds 3] [--positions 24] [--sections a,b] [--rows 1,5,...]
 
-(a) per product: the 1.3B decoder's five weight products at M = 1, 5, 16, 40, 96, 160, 512 rows, ops.gemm_w8 on the codes beside ops.gemm
-    on the bf16 weight (the baseline is the existing bf16 product, never an earlier version of the new kernel), alternated in one
-    process, the weights rotated through a set three times the size of the MALL so that none is cache-resident: time and weight
-    bytes / s of both, and the run-to-run spread of the pair.
+(a) per product: the 1.3B decoder's five weight products at M = 1, 5, 16, 40, 96, 128, 160, 256, 384, 512 rows, ops.gemm_w8 (the
+    streaming kernel) and ops.gemm_w8_tiled (the many-row kernel) on the codes beside ops.gemm on the bf16 weight (the baseline is
+    the existing bf16 product, never an earlier version of a new kernel), alternated in one process, the weights rotated through a
+    set three times the size of the MALL so that none is cache-resident: time and weight bytes / s of each, and the run-to-run
+    spread.  Per row count the step sum 24 * (qkv + dense + fc1 + fc2) + lm_head of the bf16 products and of the products the
+    FP8 step runs (streaming up to MPV_W8_MAX_ROWS rows, tiled above), and from them the row limit of the tiled kernel by the
+    rule of DESIGN section 22.
 (b) end to end: tools/bench_caption_batched.py's decoder and constants, decode_weights "bf16" / "fp8" alternated: the per-clip beam
     search (beam 5), the lockstep search of 32 clips x 5 beams in both KV modes, 32 clips x 16 samples on the shared prefix."""
 import argparse
@@ -22,7 +25,8 @@ sys.path.insert(0, ROOT)
 from tools.bench_caption_batched import BEAMS, FFN, HEADS, HIDDEN, LAYERS, LN_EPS, MAX_POS, PROMPT, Q, STOP, VOCAB  # noqa: E402
 
 PRODUCTS = [("qkv", 3 * HIDDEN, HIDDEN), ("dense", HIDDEN, HIDDEN), ("fc1", FFN, HIDDEN), ("fc2", HIDDEN, FFN), ("lm_head", VOCAB, HIDDEN)]
-ROWS = [1, 5, 16, 40, 96, 160, 512]
+ROWS = [1, 5, 16, 40, 96, 128, 160, 256, 384, 512]
+TILED_CANDIDATES = [128, 160, 256, 384, 512]      # the row counts MPV_W8_TILED_MAX_ROWS is chosen from
 ROTATE_BYTES = 768 << 20          # of codes per shape: three times the 256 MiB MALL (the bf16 set is twice that)
 
 
@@ -34,7 +38,8 @@ def section_a(dev, rounds, rows=ROWS):
     from tools.bench_kernels import timeit
     from youku_mplug_amd import ops
     out = []
-    print(f"{'product':>8} {'M':>4} {'bf16 us':>9} {'fp8 us':>9} {'bf16 TB/s':>10} {'fp8 TB/s':>9} {'fp8/bf16':>9} {'spread':>7}")
+    print(f"{'product':>8} {'M':>4} {'bf16 us':>9} {'fp8 us':>9} {'tiled us':>9} {'bf16 TB/s':>10} {'fp8 TB/s':>9} {'tiled TB/s':>10} "
+          f"{'fp8/bf16':>9} {'tiled/bf16':>10} {'spread':>7}")
     for name, N, K in PRODUCTS:
         n = max(8, -(-ROTATE_BYTES // (N * K)))
         ws = [(torch.randn(N, K, device=dev) * 0.02).bfloat16() for _ in range(n)]
@@ -51,21 +56,60 @@ def section_a(dev, rounds, rows=ROWS):
             def fp8():
                 i[0] = (i[0] + 1) % n
                 ops.gemm_w8(a, qs[i[0]][0], qs[i[0]][1], M, N, K, out=c)
-            t = {"bf16": [], "fp8": []}
+
+            def tiled():
+                i[0] = (i[0] + 1) % n
+                ops.gemm_w8_tiled(a, qs[i[0]][0], qs[i[0]][1], M, N, K, out=c)
+            t = {"bf16": [], "fp8": [], "tiled": []}
             for _ in range(rounds):
-                for fn in (bf16, fp8):
+                for fn in (bf16, fp8, tiled):
                     t[fn.__name__].append(timeit(fn, iters=max(20, n)))
             med = {k: _median(v) for k, v in t.items()}
             spread = max((max(v) - min(v)) / med[k] for k, v in t.items())
             rec = {"product": name, "M": M, "N": N, "K": K, "rotated_weights": n, "seconds": t, "median_s": med,
-                   "weight_bytes_per_s": {"bf16": N * K * 2 / med["bf16"], "fp8": N * K / med["fp8"]},
-                   "fp8_over_bf16_time": med["fp8"] / med["bf16"], "pair_spread": spread}
+                   "weight_bytes_per_s": {"bf16": N * K * 2 / med["bf16"], "fp8": N * K / med["fp8"], "tiled": N * K / med["tiled"]},
+                   "fp8_over_bf16_time": med["fp8"] / med["bf16"], "tiled_over_bf16_time": med["tiled"] / med["bf16"], "pair_spread": spread}
             out.append(rec)
-            print(f"{name:>8} {M:>4} {med['bf16'] * 1e6:9.1f} {med['fp8'] * 1e6:9.1f} {rec['weight_bytes_per_s']['bf16'] / 1e12:10.2f} "
-                  f"{rec['weight_bytes_per_s']['fp8'] / 1e12:9.2f} {rec['fp8_over_bf16_time']:9.2f} {spread:7.3f}", flush=True)
+            bw = rec["weight_bytes_per_s"]
+            print(f"{name:>8} {M:>4} {med['bf16'] * 1e6:9.1f} {med['fp8'] * 1e6:9.1f} {med['tiled'] * 1e6:9.1f} {bw['bf16'] / 1e12:10.2f} "
+                  f"{bw['fp8'] / 1e12:9.2f} {bw['tiled'] / 1e12:10.2f} {rec['fp8_over_bf16_time']:9.2f} {rec['tiled_over_bf16_time']:10.2f} "
+                  f"{spread:7.3f}", flush=True)
         del ws, qs
         torch.cuda.empty_cache()
     return out
+
+
+def step_sums(per_product, w8_max_rows):
+    """per row count: 24 * (qkv + dense + fc1 + fc2) + lm_head per round -> median and run-to-run spread, for the bf16 products and for
+    the FP8 step's (streaming up to w8_max_rows rows, tiled above), and whether FP8 is below bf16 by more than the larger spread"""
+    out = []
+    for M in sorted({r["M"] for r in per_product}):
+        by = {r["product"]: r["seconds"] for r in per_product if r["M"] == M}
+        if set(by) != {name for name, _, _ in PRODUCTS}:
+            continue
+        kernel = "fp8" if M <= w8_max_rows else "tiled"
+        rec = {"M": M, "fp8_kernel": kernel}
+        for key, col in (("bf16", "bf16"), ("fp8", kernel)):
+            sums = [LAYERS * sum(by[p][col][i] for p in ("qkv", "dense", "fc1", "fc2")) + by["lm_head"][col][i] for i in range(len(by["qkv"][col]))]
+            rec[key + "_s"] = _median(sums)
+            rec[key + "_spread"] = (max(sums) - min(sums)) / _median(sums)
+        rec["fp8_over_bf16_time"] = rec["fp8_s"] / rec["bf16_s"]
+        rec["fp8_wins"] = rec["fp8_s"] < rec["bf16_s"] * (1 - max(rec["bf16_spread"], rec["fp8_spread"]))
+        out.append(rec)
+    return out
+
+
+def tiled_limit_by_rule(sums, w8_max_rows):
+    """the largest of TILED_CANDIDATES such that FP8 wins there and at every smaller measured row count above w8_max_rows
+    (None: not even the smallest, or a candidate was not measured)"""
+    measured = {r["M"]: r["fp8_wins"] for r in sums if r["M"] > w8_max_rows}
+    best = None
+    for M in sorted(measured):
+        if not measured[M]:
+            break
+        if M in TILED_CANDIDATES:
+            best = M
+    return best
 
 
 def section_b(dev, rounds, positions):
@@ -128,12 +172,20 @@ def main():
     import youku_mplug_amd  # noqa: F401
     from youku_mplug_amd import _lib
     dev = torch.device("cuda:0")
-    rec = {"device": torch.cuda.get_device_name(0), "rounds": args.rounds, "w8_max_rows": _lib.W8_MAX_ROWS}
+    rec = {"device": torch.cuda.get_device_name(0), "rounds": args.rounds, "w8_max_rows": _lib.W8_MAX_ROWS,
+           "w8_tiled_max_rows": _lib.W8_TILED_MAX_ROWS}
     if os.path.isfile(args.out):                               # a run of one section keeps the other
         with open(args.out) as f:
             rec = dict(json.load(f), **rec)
     if "a" in args.sections.split(","):
         rec["per_product"] = section_a(dev, args.rounds, [int(m) for m in args.rows.split(",")])
+        rec["step_sums"] = step_sums(rec["per_product"], _lib.W8_MAX_ROWS)
+        rec["w8_tiled_max_rows_by_rule"] = tiled_limit_by_rule(rec["step_sums"], _lib.W8_MAX_ROWS)
+        print(f"{'M':>4} {'bf16 step us':>13} {'fp8 step us':>12} {'kernel':>7} {'fp8/bf16':>9} {'spreads':>15} wins")
+        for r in rec["step_sums"]:
+            print(f"{r['M']:>4} {r['bf16_s'] * 1e6:13.1f} {r['fp8_s'] * 1e6:12.1f} {r['fp8_kernel']:>7} {r['fp8_over_bf16_time']:9.3f} "
+                  f"{r['bf16_spread']:7.3f} {r['fp8_spread']:7.3f} {r['fp8_wins']}")
+        print("tiled row limit by the rule:", rec["w8_tiled_max_rows_by_rule"], "-- built with", _lib.W8_TILED_MAX_ROWS)
     if "b" in args.sections.split(","):
         rec["end_to_end"] = section_b(dev, args.rounds, args.positions)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -259,6 +259,7 @@ class GptWeightsQ8(C.Structure):
 
 
 W8_MAX_ROWS = 96       # include/mpv.h MPV_W8_MAX_ROWS
+W8_TILED_MAX_ROWS = 512  # include/mpv.h MPV_W8_TILED_MAX_ROWS
 
 _SIGS.update({
     "mpv_gpt_decode_workspace_size": (c_size_t, [C.POINTER(GptWeights), c_int, c_int]),
@@ -271,6 +272,8 @@ _SIGS.update({
     "mpv_quantize_rows_e4m3": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "mpv_gemm_w8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64,
                             C.POINTER(GemmEpilogue), c_void_p]),
+    "mpv_gemm_w8_tiled": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64,
+                                  C.POINTER(GemmEpilogue), c_void_p, c_size_t, c_void_p]),
     "mpv_gpt_embed_w8_fwd": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p]),
     "mpv_gpt_decode_step_q8": (c_int, [C.POINTER(GptWeights), C.POINTER(GptWeightsQ8), C.POINTER(c_void_p), c_int, c_int, c_int, c_void_p,
                                        c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),

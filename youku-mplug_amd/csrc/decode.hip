@@ -21,7 +21,7 @@ extern "C" size_t mpv_gpt_decode_workspace_size(const mpv_gpt_weights* w, int ba
 }
 
 // One weight product of a step, C[M, N] = epi(A[M, K] W[N, K]^T) with dense operands: on the bf16 weight, or -- in the _q8 entries
-// (codes != nullptr) for at most MPV_W8_MAX_ROWS rows -- on its e4m3 codes (include/mpv.h, "FP8 decoder weights").
+// (codes != nullptr) for at most MPV_W8_TILED_MAX_ROWS rows -- on its e4m3 codes (include/mpv.h, "FP8 decoder weights").
 struct Products {
   void* gws;
   size_t gws_bytes;
@@ -29,6 +29,8 @@ struct Products {
   int operator()(const void* A, const void* w_bf16, const void* codes, const void* scale, void* C, int64_t M, int64_t N, int64_t K,
                  const mpv_gemm_epilogue* ep) const {
     if (codes && M <= MPV_W8_MAX_ROWS) return mpv_gemm_w8(A, codes, (const float*)scale, C, M, N, K, K, K, N, ep, stream);
+    if (codes && M <= MPV_W8_TILED_MAX_ROWS)
+      return mpv_gemm_w8_tiled(A, codes, (const float*)scale, C, M, N, K, K, K, N, ep, gws, gws_bytes, stream);
     return mpv_gemm_bf16(A, w_bf16, C, M, N, K, K, K, N, 0, 0, ep, gws, gws_bytes, stream);
   }
 };

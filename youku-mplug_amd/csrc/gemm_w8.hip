@@ -3,6 +3,7 @@
 //   mpv_quantize_rows_e4m3  row amax -> exponent -> codes, one workgroup per weight row
 //   mpv_gemm_w8             C[M,N] = epi(scale[n] * sum_k A[m,k] deq(code[n,k])) for 1 <= M <= 512 rows: the weight-streaming kernel
 //                           of gemm.hip (gemm_small_m_kernel) with an 8-bit weight and up to 32 row blocks of 16 rows per workgroup
+//   mpv_gemm_w8_tiled       the same product for 97-512 rows: tiles of up to 128 rows x 64 columns, A staged through LDS
 //   mpv_gpt_embed_w8_fwd    mpv_gpt_embed_fwd with the token rows taken from the codes (the quantised decoder IS a bf16 model whose
 //                           tied embedding holds deq(code) * scale: the rows are looked up in that bf16 table without storing it)
 #include "../../include/mpv.h"
@@ -165,6 +166,148 @@ __global__ __launch_bounds__(64 * NW) void gemm_w8_kernel(const W8Args p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// The many-row product (mpv_gemm_w8_tiled).  A workgroup of four waves owns a tile of RB 16-row blocks (1..8, chosen on the host) x
+// 64 columns and walks all of K in stages of 128: wave w owns the 16 columns n0 + 16 w .. and every row block of the tile, so an
+// output element is ONE MFMA accumulator chain over ascending k -- no cross-wave reduce, no K split, and the order is the same for
+// every M, RB and tile position.  Per stage the workgroup brings its A tile (rows x 256 bytes) into LDS with coalesced 16-byte loads
+// (a row's 16 chunks by 16 consecutive lanes) and every wave reads its fragments from there; a lane's codes (16 per 64-wide
+// K-block, the layout of gemm_w8_kernel) stay in registers.  The loads of stage s + PD are issued right after the MFMAs of stage s
+// and wait in registers: PD = 4 stages are in flight per workgroup (the product is bound by load latency, not by MFMA or LDS time:
+// two stages behind a wait for every load took 1.4-2.4 times as long at 160 rows), and the steady-state loop has no branch around a load, so that the
+// compiler's vmcnt waits leave the younger stages in flight.  Registers: at most 248, two workgroups per CU.
+// LDS image of a stage: 16-byte chunk c (k = 8 c ..) of tile row m at unit 16 m + (c ^ (m & 15)): the ds_write_b128 of 16
+// consecutive chunks of a row and the ds_read_b128 of chunks {2g, 2g + 1} + 8 q by lane (r, g) are both free of bank conflicts.
+// Tile rows past M repeat row M - 1 (computed, never stored); chunks past K are zero on both operands.
+constexpr int TILED_RB = 8;                                     // the most 16-row blocks a workgroup holds (32 KiB of LDS per stage)
+constexpr int TILED_RB2 = 4;                                    // ... with two column groups
+template <int RB, int CG>
+struct TiledStage {
+  i32x4 a[RB];                                                  // this thread's chunk of tile rows i * 16 + (tid >> 4)
+  i32x4 c[CG][2];                                               // this lane's codes of the stage's two 64-wide K-blocks, per column group
+  bool aok, cok[2];                                             // whether they lie inside K
+};
+
+// CG = 2: a workgroup owns two groups of 64 columns (wave w: columns 16 w .. of each), which halves the A bytes per output.  Built for
+// RB <= 4 only: taller tiles of 128 columns need more than 256 registers, and with one workgroup per CU they were SLOWER than 64
+// columns (measured at 512 rows: qkv 35.6 against 32.3 us, the LM head 259 against 227).
+template <int RB, int CG>
+__global__ __launch_bounds__(256, 2) void gemm_w8_tiled_kernel(const W8Args p) {
+  static_assert(CG == 1 || RB <= TILED_RB2, "two column groups: at most TILED_RB2 row blocks");
+  constexpr int PD = 4;                                         // stages in flight (even: the LDS buffer of a stage is static)
+  __shared__ i32x4 lds[2][RB * 16 * 16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 15, g = lane >> 4;
+  const int row0 = blockIdx.y * RB * 16;                        // first row of the tile
+  const int n0 = blockIdx.x * (64 * CG) + wave * 16 + r;        // this lane's column of group cg: n0 + 64 cg
+  const uint8_t* wrow[CG];
+#pragma unroll
+  for (int cg = 0; cg < CG; ++cg) wrow[cg] = p.W + (long long)min(n0 + 64 * cg, p.N - 1) * p.ldw + g * 16;
+  // staging role: chunk ac of tile rows am, am + 16, ...
+  const int ac = tid & 15, am = tid >> 4;
+  const bf16* arow[RB];
+#pragma unroll
+  for (int i = 0; i < RB; ++i) arow[i] = p.A + (long long)min(row0 + i * 16 + am, p.M - 1) * p.lda + ac * 8;
+  const int wunit = am * 16 + (ac ^ am);
+  const int nst = (p.K + 127) >> 7;
+  f32x4 acc[RB][CG];
+#pragma unroll
+  for (int b = 0; b < RB; ++b)
+#pragma unroll
+    for (int cg = 0; cg < CG; ++cg) acc[b][cg] = f32x4{0.f, 0.f, 0.f, 0.f};
+  TiledStage<RB, CG> st[PD];
+  const i32x4 zero = {0, 0, 0, 0};
+  // no branch around a load, and nothing reads a loaded register before the stage's turn (either would make the wait for one stage
+  // a wait for all): a chunk past K is read at k = 0 and zeroed when the stage is used
+  auto load = [&](int s, TiledStage<RB, CG>& t) {
+    const int k0 = s * 128;
+    t.aok = k0 + ac * 8 < p.K;                                  // K % 16 == 0: a chunk is all-in or all-out
+#pragma unroll
+    for (int i = 0; i < RB; ++i) t.a[i] = *(const i32x4*)(arow[i] + (t.aok ? k0 : 0));
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      t.cok[q] = k0 + q * 64 + g * 16 < p.K;
+#pragma unroll
+      for (int cg = 0; cg < CG; ++cg) t.c[cg][q] = *(const i32x4*)(wrow[cg] + (t.cok[q] ? k0 + q * 64 : 0));
+    }
+  };
+  auto step = [&](i32x4* buf, const TiledStage<RB, CG>& t) {
+    __builtin_amdgcn_sched_barrier(0);                          // (a later stage's conversions hoisted to here would wait for its loads)
+#pragma unroll
+    for (int i = 0; i < RB; ++i) buf[i * 256 + wunit] = t.aok ? t.a[i] : zero;
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      Frag w0[CG], w1[CG];
+#pragma unroll
+      for (int cg = 0; cg < CG; ++cg) deq_chunk(t.cok[q] ? t.c[cg][q] : zero, w0[cg], w1[cg]);
+#pragma unroll
+      for (int b = 0; b < RB; ++b) {
+        Frag a0, a1;
+        const i32x4* row = buf + (b * 16 + r) * 16;
+        a0.i = row[(8 * q + 2 * g) ^ r];
+        a1.i = row[(8 * q + 2 * g + 1) ^ r];
+#pragma unroll
+        for (int cg = 0; cg < CG; ++cg) {
+          acc[b][cg] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0.b, w0[cg].b, acc[b][cg], 0, 0, 0);
+          acc[b][cg] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1.b, w1[cg].b, acc[b][cg], 0, 0, 0);
+        }
+      }
+    }
+  };
+  // One barrier per stage is enough with two LDS buffers: stage s writes the buffer stage s - 2 read, and every wave passed the
+  // barrier of stage s - 1 after those reads.
+#pragma unroll
+  for (int j = 0; j < PD; ++j) load(min(j, nst - 1), st[j]);    // (a stage past the end repeats the last one: loaded, never used)
+  int s = 0;
+  for (; s + 2 * PD <= nst; s += PD) {                          // steady state: stage s + j + PD exists for every j
+#pragma unroll
+    for (int j = 0; j < PD; ++j) {
+      step(lds[j & 1], st[j]);
+      load(s + j + PD, st[j]);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 2 * PD - 1; ++j) {                        // the last nst - s < 2 PD stages
+    if (s + j < nst) {
+      step(lds[j & 1], st[j % PD]);
+      if (s + j + PD < nst) load(s + j + PD, st[j % PD]);
+    }
+  }
+  // D layout: lane -> column n = lane & 15, rows 4 * (lane >> 4) + i of the block
+#pragma unroll
+  for (int cg = 0; cg < CG; ++cg) {
+    const int n = n0 + 64 * cg;
+    if (n < p.N) {
+      const float sc = p.scale[n];
+      const float bias = p.bias ? bf2f(p.bias[n]) : 0.f;
+#pragma unroll
+      for (int b = 0; b < RB; ++b) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int m = row0 + b * 16 + 4 * g + i;
+          if (m < p.M) {
+            float v = acc[b][cg][i] * sc + bias;
+            if (p.act) v = gelu_tanh_f(bf2f(f2bf(v)));
+            const long long crow = map_row(p.cmap, p.m0 + m);
+            if (p.residual) v += bf2f(p.residual[crow * p.ldr + n]);
+            p.C[crow * p.ldc + n] = f2bf(v);
+          }
+        }
+      }
+    }
+  }
+}
+
+template <int RB, int CG>
+void launch_w8_tiled(const W8Args& a, int rb, hipStream_t stream) {
+  if constexpr (RB > 1) {
+    if (rb < RB) return launch_w8_tiled<RB - 1, CG>(a, rb, stream);
+  }
+  const dim3 grid((unsigned)((a.N + 64 * CG - 1) / (64 * CG)), (unsigned)(((a.M + 15) / 16 + RB - 1) / RB));
+  hipLaunchKernelGGL((gemm_w8_tiled_kernel<RB, CG>), grid, dim3(256), 0, stream, a);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // one workgroup per weight row: amax, the exponent of the contract, then the codes (v_cvt_pk_fp8_f32: round to nearest even, OCP
 // e4m3fn on gfx950; |w * 2^-e| <= 448, so its saturation never acts)
 __global__ __launch_bounds__(256) void quantize_rows_e4m3_kernel(const bf16* __restrict__ w, int K, long long ldw, uint8_t* __restrict__ codes,
@@ -263,18 +406,19 @@ extern "C" int mpv_quantize_rows_e4m3(const void* w, int64_t N, int64_t K, int64
   return mpv_check_launch("mpv_quantize_rows_e4m3");
 }
 
-extern "C" int mpv_gemm_w8(const void* A, const void* codes, const float* scale, void* C, int64_t M, int64_t N, int64_t K, int64_t lda,
-                           int64_t ldw, int64_t ldc, const mpv_gemm_epilogue* ep, hipStream_t stream) {
-  MPV_REQUIRE(A && codes && scale && C, MPV_E_ARG, "mpv_gemm_w8: null pointer");
-  MPV_REQUIRE(M >= 1 && M <= 512, MPV_E_SHAPE, "mpv_gemm_w8: M (%lld) must be in [1, 512]", (long long)M);
+// the host-side checks of both product entries and the kernel arguments they share (a.M, a.m0 and the row range are the caller's)
+static int w8_args(const char* who, const void* A, const void* codes, const float* scale, void* C, int64_t M, int64_t N, int64_t K, int64_t lda,
+                   int64_t ldw, int64_t ldc, const mpv_gemm_epilogue* ep, W8Args& a) {
+  MPV_REQUIRE(A && codes && scale && C, MPV_E_ARG, "%s: null pointer", who);
+  MPV_REQUIRE(M >= 1 && M <= 512, MPV_E_SHAPE, "%s: M (%lld) must be in [1, 512]", who, (long long)M);
   MPV_REQUIRE(N > 0 && N % 8 == 0 && K > 0 && K % 16 == 0 && N < (1ll << 31) && K < (1ll << 31), MPV_E_SHAPE,
-              "mpv_gemm_w8: N (%lld) must be a positive multiple of 8 and K (%lld) of 16", (long long)N, (long long)K);
-  MPV_REQUIRE(lda >= K && ldw >= K && ldc >= N, MPV_E_SHAPE, "mpv_gemm_w8: leading dimension shorter than its row (lda=%lld ldw=%lld ldc=%lld)",
+              "%s: N (%lld) must be a positive multiple of 8 and K (%lld) of 16", who, (long long)N, (long long)K);
+  MPV_REQUIRE(lda >= K && ldw >= K && ldc >= N, MPV_E_SHAPE, "%s: leading dimension shorter than its row (lda=%lld ldw=%lld ldc=%lld)", who,
               (long long)lda, (long long)ldw, (long long)ldc);
   MPV_REQUIRE(lda % 8 == 0 && ldw % 16 == 0 && (((uintptr_t)A | (uintptr_t)codes) & 15) == 0 && ((uintptr_t)C & 1) == 0 &&
                   ((uintptr_t)scale & 3) == 0,
-              MPV_E_ALIGN, "mpv_gemm_w8: lda must be a multiple of 8, ldw of 16, A and codes 16-byte aligned");
-  W8Args a = {};
+              MPV_E_ALIGN, "%s: lda must be a multiple of 8, ldw of 16, A and codes 16-byte aligned", who);
+  a = W8Args{};
   a.A = (const bf16*)A; a.W = (const uint8_t*)codes; a.scale = scale; a.C = (bf16*)C;
   a.N = (int)N; a.K = (int)K;
   a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.ldr = ldc;
@@ -285,16 +429,24 @@ extern "C" int mpv_gemm_w8(const void* A, const void* codes, const float* scale,
                     !(ep->alpha != 0.f) && !ep->out_f32 && !ep->accumulate && !ep->colsum_out && !ep->tile_hint && !ep->row_tap_out &&
                     !ep->row_tap_group && !ep->split_hint && !ep->gm_hint && !ep->preact_deriv && !ep->keep_output && !(ep->colscale != 0.f) &&
                     !ep->colscale_cols,
-                MPV_E_ARG, "mpv_gemm_w8: the epilogue takes bias, act = MPV_ACT_GELU_TANH, residual / ldr and the C row map only");
-    MPV_REQUIRE(ep->act == MPV_ACT_NONE || ep->act == MPV_ACT_GELU_TANH, MPV_E_ARG, "mpv_gemm_w8: act (%d) must be none or GELU-tanh", ep->act);
+                MPV_E_ARG, "%s: the epilogue takes bias, act = MPV_ACT_GELU_TANH, residual / ldr and the C row map only", who);
+    MPV_REQUIRE(ep->act == MPV_ACT_NONE || ep->act == MPV_ACT_GELU_TANH, MPV_E_ARG, "%s: act (%d) must be none or GELU-tanh", who, ep->act);
     MPV_REQUIRE(ep->c_group >= 0 && ep->ldr >= 0 && (ep->ldr == 0 || ep->ldr >= N) && (ep->residual || ep->ldr == 0), MPV_E_ARG,
-                "mpv_gemm_w8: bad c_group (%d) or ldr (%lld)", ep->c_group, (long long)ep->ldr);
+                "%s: bad c_group (%d) or ldr (%lld)", who, ep->c_group, (long long)ep->ldr);
     a.cmap = RowMap{ep->c_group, ep->c_stride, ep->c_offset};
     a.bias = (const bf16*)ep->bias;
     a.residual = (const bf16*)ep->residual;
     if (ep->ldr) a.ldr = ep->ldr;
     a.act = ep->act;
   }
+  return MPV_OK;
+}
+
+extern "C" int mpv_gemm_w8(const void* A, const void* codes, const float* scale, void* C, int64_t M, int64_t N, int64_t K, int64_t lda,
+                           int64_t ldw, int64_t ldc, const mpv_gemm_epilogue* ep, hipStream_t stream) {
+  W8Args a;
+  const int rc = w8_args("mpv_gemm_w8", A, codes, scale, C, M, N, K, lda, ldw, ldc, ep, a);
+  if (rc) return rc;
   const bool full = N % 16 == 0 && K % 64 == 0;
   // the K split is a function of (N, K) only (row invariance): 16 waves for a long reduction with few workgroups, as gemm.hip does
   const bool long_k = full && K >= 4096 && N / 16 <= 256;
@@ -312,6 +464,40 @@ extern "C" int mpv_gemm_w8(const void* A, const void* codes, const float* scale,
     else launch_w8<false, 4, 16>(s, stream);
   }
   return mpv_check_launch("mpv_gemm_w8");
+}
+
+// The tile of the tiled product: a workgroup reads rb * 16 rows of A (2 bytes an element) and cg * 64 rows of codes over all of K, and
+// the 256 CUs take the workgroups in rounds -- the (rb, cg) with the least bytes on the busiest CU; on a tie the larger rb, then one
+// column group.  It shapes the launch only: the summation order of an element does not depend on it.
+static void tiled_tile(int64_t M, int64_t N, int& rb_out, int& cg_out) {
+  const int64_t nrb = (M + 15) / 16;
+  int64_t best_cost = 0;
+  rb_out = 0;
+  for (int cg = 2; cg >= 1; --cg) {
+    const int64_t ct = (N + 64 * cg - 1) / (64 * cg);
+    for (int rb = 1; rb <= (cg == 2 ? TILED_RB2 : TILED_RB); ++rb) {
+      const int64_t wgs = ct * ((nrb + rb - 1) / rb);
+      const int64_t cost = ((wgs + 255) / 256) * (rb * 32 + cg * 64);
+      if (!rb_out || cost <= best_cost) rb_out = rb, cg_out = cg, best_cost = cost;
+    }
+  }
+}
+
+extern "C" int mpv_gemm_w8_tiled(const void* A, const void* codes, const float* scale, void* C, int64_t M, int64_t N, int64_t K, int64_t lda,
+                                 int64_t ldw, int64_t ldc, const mpv_gemm_epilogue* ep, void* workspace, size_t workspace_bytes,
+                                 hipStream_t stream) {
+  W8Args a;
+  const int rc = w8_args("mpv_gemm_w8_tiled", A, codes, scale, C, M, N, K, lda, ldw, ldc, ep, a);
+  if (rc) return rc;
+  // no variant of this kernel splits K over workgroups: the workspace is not used, so the result cannot depend on it
+  (void)workspace;
+  (void)workspace_bytes;
+  a.M = (int)M;
+  int rb, cg;
+  tiled_tile(M, N, rb, cg);
+  if (cg == 2) launch_w8_tiled<TILED_RB2, 2>(a, rb, stream);
+  else launch_w8_tiled<TILED_RB, 1>(a, rb, stream);
+  return mpv_check_launch("mpv_gemm_w8_tiled");
 }
 
 extern "C" int mpv_gpt_embed_w8_fwd(const void* query, const int64_t* ids, const void* wte_codes, const float* wte_scale, const void* wpe,

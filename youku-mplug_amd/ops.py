@@ -681,12 +681,7 @@ def quantize_rows_e4m3(w: torch.Tensor, N: Optional[int] = None, K: Optional[int
     return codes, scale
 
 
-def gemm_w8(a: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor, M: int, N: int, K: int, *, out: Optional[torch.Tensor] = None,
-            lda: Optional[int] = None, ldw: Optional[int] = None, ldc: Optional[int] = None, bias=None, act: int = 0, residual=None,
-            ldr: int = 0, cmap: RowMap = IDENT, out_rows: Optional[int] = None, **other) -> torch.Tensor:
-    """include/mpv.h mpv_gemm_w8: C[M, N] = epi(scale[n] * sum_k A[m, k] deq(codes[n, k])), 1 <= M <= 512, the decode step's
-    epilogues only (bias, act = ACT_GELU_TANH, residual / ldr, cmap).  `other`: further GemmEpilogue fields by name -- the library
-    refuses every one of them."""
+def _gemm_w8(entry, a, codes, scale, M, N, K, out, lda, ldw, ldc, bias, act, residual, ldr, cmap, out_rows, other, tail=()):
     _need_cuda(a, codes, scale)
     ldc = ldc if ldc is not None else N
     if out is None:
@@ -696,9 +691,28 @@ def gemm_w8(a: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor, M: int, N
     ep.bias, ep.act, ep.residual, ep.ldr = _p(bias), act, _p(residual), ldr
     for k, v in other.items():
         setattr(ep, k, v)
-    check(_lib.lib().mpv_gemm_w8(a.data_ptr(), codes.data_ptr(), scale.data_ptr(), out.data_ptr(), M, N, K, lda if lda is not None else K,
-                                 ldw if ldw is not None else K, ldc, C.byref(ep), _stream()), "mpv_gemm_w8")
+    check(getattr(_lib.lib(), entry)(a.data_ptr(), codes.data_ptr(), scale.data_ptr(), out.data_ptr(), M, N, K, lda if lda is not None else K,
+                                     ldw if ldw is not None else K, ldc, C.byref(ep), *tail, _stream()), entry)
     return out
+
+
+def gemm_w8(a: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor, M: int, N: int, K: int, *, out: Optional[torch.Tensor] = None,
+            lda: Optional[int] = None, ldw: Optional[int] = None, ldc: Optional[int] = None, bias=None, act: int = 0, residual=None,
+            ldr: int = 0, cmap: RowMap = IDENT, out_rows: Optional[int] = None, **other) -> torch.Tensor:
+    """include/mpv.h mpv_gemm_w8: C[M, N] = epi(scale[n] * sum_k A[m, k] deq(codes[n, k])), 1 <= M <= 512, the decode step's
+    epilogues only (bias, act = ACT_GELU_TANH, residual / ldr, cmap).  `other`: further GemmEpilogue fields by name -- the library
+    refuses every one of them."""
+    return _gemm_w8("mpv_gemm_w8", a, codes, scale, M, N, K, out, lda, ldw, ldc, bias, act, residual, ldr, cmap, out_rows, other)
+
+
+def gemm_w8_tiled(a: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor, M: int, N: int, K: int, *, out: Optional[torch.Tensor] = None,
+                  lda: Optional[int] = None, ldw: Optional[int] = None, ldc: Optional[int] = None, bias=None, act: int = 0, residual=None,
+                  ldr: int = 0, cmap: RowMap = IDENT, out_rows: Optional[int] = None, use_workspace: bool = True, **other) -> torch.Tensor:
+    """include/mpv.h mpv_gemm_w8_tiled: gemm_w8's product, keywords and refusals on the kernel built for 97-512 rows.
+    use_workspace=False passes a null workspace (the result is the same bits)."""
+    ws = workspace(1, a.device) if use_workspace and a.is_cuda else None
+    return _gemm_w8("mpv_gemm_w8_tiled", a, codes, scale, M, N, K, out, lda, ldw, ldc, bias, act, residual, ldr, cmap, out_rows, other,
+                    (_p(ws), ws.numel() if ws is not None else 0))
 
 
 def gather_rows_ld(src, idx, dst, rows, cols, lds, ldd):
