@@ -3,7 +3,8 @@ ONLY: they let the real host pipelines (vision.py / gpt3.py / pretrain.py: row m
 composed temporal-projection backward) run on CPU inside `-m "not gpu"` tests and be checked against the reference goldens.
 Each function restates the contract of its C entry point in include/mpv.h (same arguments as the ops.py wrapper, bf16
 storage, fp32 arithmetic, bf16 rounding at the points the kernels round) with plain indexing -- no attempt at speed, tiny
-shapes only.  Dropout is not modelled (the counter-hash masks live in the kernels): every stand-in asserts dropout_p == 0.
+shapes only.  Dropout is not modelled (the counter-hash masks live in the kernels): every stand-in asserts dropout_p == 0, except the
+LayerNorm entry points, which take their mask from the host replica of the hash in tests/ref_norm.py (_hash_dropout).
 Nothing in the product imports this file; tests install it with `install(monkeypatch)`."""
 import math
 
@@ -122,6 +123,16 @@ def gemm(a, b, M, N, K, *, out=None, trans_a=False, trans_b=False, lda=None, ldb
     return out
 
 
+def _hash_dropout(v, rows, cols, p, seed, offset):
+    """The counter-hash dropout of the LayerNorm entry points only (the other stand-ins still assert dropout_p == 0): v [n, cols]
+    fp32, element index offset + rows[i] * cols + column; v * fp32(1 / (1 - p)) where tests/ref_norm.py keep_mask keeps, +0 elsewhere."""
+    if p == 0.0:
+        return v
+    import ref_norm
+    keep = ref_norm.keep_mask(seed, offset, int(rows.max()) + 1, cols, p)[rows]
+    return torch.where(keep, v * torch.tensor(ref_norm.drop_scale(p), dtype=torch.float32), torch.zeros_like(v))
+
+
 def layernorm_fwd(x, gamma, beta, eps, rows, cols, *, out=None, xmap=IDENT, ymap=IDENT, out_rows=None, ldx=None, ldy=None,
                   want_stats=True):
     ldx, ldy = ldx or cols, ldy or cols
@@ -153,7 +164,6 @@ class LnDparamBatch:
 def layernorm_bwd(dy, x, gamma, mean, rstd, rows, cols, *, dres=None, dx=None, dx_drop=None, dropout_p=0.0, seed=0, offset=0,
                   dgamma=None, dbeta=None, accumulate_dparams=False, xmap=IDENT, ymap=IDENT, ldx=None, ldy=None, dx_rows=None,
                   defer=None):
-    assert dropout_p == 0.0
     ldx, ldy = ldx or cols, ldy or cols
     if dx is None:
         dx = torch.zeros((dx_rows if dx_rows is not None else rows, ldx), dtype=BF, device=x.device)
@@ -167,7 +177,7 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, rows, cols, *, dres=None, dx=None, d
         o = o + _rd(dres, xr, ldx, cols)
     _wr(dx, xr, ldx, o)
     if dx_drop is not None:
-        _wr(dx_drop, xr, ldx, _r16(o))
+        _wr(dx_drop, xr, ldx, _hash_dropout(_r16(o), torch.arange(rows), cols, dropout_p, seed, offset))
     if dgamma is not None and defer is not None:       # MPV_LN_DPARAM_DEFER: nothing is written until the batch's finish()
         defer._pending.append(((dv * xh).sum(0), dv.sum(0), dgamma, dbeta, bool(accumulate_dparams)))
     elif dgamma is not None:
@@ -181,13 +191,13 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, rows, cols, *, dres=None, dx=None, d
 
 def ln_stream_fwd(h_in, add, gamma, beta, eps, rows, cols, *, add_dropout_p=0.0, seed=0, offset=0, h_out=None, out=None, hmap=IDENT, amap=IDENT, ymap=IDENT, out_rows=None,
                   h_rows=None):
-    assert add_dropout_p == 0.0, "stand-ins do not model the hash dropout"
     if out is None:
         out = torch.zeros((out_rows if out_rows is not None else rows, cols), dtype=BF)
     hr = _rows(hmap, rows)
     v = _rd(h_in, hr, cols, cols)                      # fp32 (or bf16 for the first LayerNorm) -> fp32
     if add is not None:
-        v = v + _rd(add, _rows(amap, rows), cols, cols)
+        ar = _rows(amap, rows)
+        v = v + _r16(_hash_dropout(_rd(add, ar, cols, cols), ar, cols, add_dropout_p, seed, offset))      # (the index uses the row of `add`)
         if h_out is None:
             h_out = torch.zeros((h_rows if h_rows is not None else h_in.shape[0], cols), dtype=torch.float32)
         _wr(h_out, hr, cols, v)
