@@ -30,6 +30,9 @@ What this entry point adds to downstream/finetune_common.py:
   * `--eval_fp8_decode` (not in the reference, default off): every generation call of the evaluation runs its decode steps on e4m3
     codes of the decoder's weights (`model.generate(..., decode_weights="fp8")`: quantised on the device, once; the bf16 weights stay
     and serve the prefill of many rows and the scoring); it combines with every other flag;
+  * `--eval_mixed_prompts` (not in the reference, default off; implies nothing else): the lockstep beam searches (`--eval_batched_beam`,
+    `--eval_beam_groups`) take the clips of a batch in input order, `--clips_per_search` at a time, whatever their prompt lengths,
+    instead of one search per distinct length (`model.generate(..., mixed_prompts=True)`; needs `--eval_shared_kv`); same result files;
   * `--eval_score_gold` (not in the reference, default off): evaluation also scores every clip's `gold_caption` list, teacher-forced,
     against the query features computed once for that clip (`model.score_captions(..., query_features=)`: one packed pass per batch,
     no padding rows), adds "gold_logprob" / "gold_tokens" lists to the result entries and logs the corpus per-token NLL and perplexity;
@@ -63,18 +66,23 @@ def make_training_batch(video, text, prompt, tokenizer, device, max_length):
 
 @torch.no_grad()
 def evaluation(model, data_loader, tokenizer, device, config, batched=False, clips_per_search=32, eval_sample=0, seed=0, shared_kv=False,
-               constraints=None, best_of=0, score_gold=False, max_length=None, beam_groups=1, diversity_penalty=0.0, fp8_decode=False):
+               constraints=None, best_of=0, score_gold=False, max_length=None, beam_groups=1, diversity_penalty=0.0, fp8_decode=False,
+               mixed_prompts=False):
     """-> [{video_id, pred_caption, gold_caption}] (:208-238); batched: `--eval_batched_beam`; eval_sample: `--eval_sample`;
     shared_kv: `--eval_shared_kv`, constraints: the keywords of `--eval_repetition_penalty` / `--eval_no_repeat_ngram` /
     `--eval_min_new_tokens` (the lockstep calls only); best_of: `--eval_sample_best_of` (the prediction is the best of that many
     samples instead of the beam search's); score_gold: `--eval_score_gold` (the clip's query features are computed once and serve the
     generation and the scoring of its gold captions, tokenized as the training pairs are, at most max_length tokens); beam_groups /
     diversity_penalty: `--eval_beam_groups` / `--eval_diversity_penalty` (the prediction is the most likely hypothesis of a diverse beam
-    search, all of them in "pred_candidates"); fp8_decode: `--eval_fp8_decode`"""
+    search, all of them in "pred_candidates"); fp8_decode: `--eval_fp8_decode`; mixed_prompts: `--eval_mixed_prompts` (the
+    lockstep beam-search calls only)"""
     module = getattr(model, "module", model)
     module.eval()
     kvkw = {"kv_cache": "shared_prefix"} if shared_kv else {}                # flag absent: the calls below are unchanged
     kvkw.update(constraints or {})
+    if mixed_prompts and not (batched or beam_groups > 1):
+        raise ValueError("--eval_mixed_prompts needs --eval_batched_beam or --eval_beam_groups: the per-clip search has one prompt per call")
+    mixkw = {"mixed_prompts": True} if mixed_prompts else {}                 # flag absent: the calls below are unchanged
     result = []
     for n, (video, video_ids, gold_caption) in enumerate(data_loader):
         video = video.to(device, non_blocking=True).bfloat16()
@@ -89,13 +97,13 @@ def evaluation(model, data_loader, tokenizer, device, config, batched=False, cli
             per_group = min(5, 16 // beam_groups)
             candidates, _ = module.generate(video, text_input, batched=True, clips_per_search=clips_per_search, beam_groups=beam_groups,
                                             diversity_penalty=diversity_penalty, beam_size=per_group, num_return_gen=beam_groups * per_group,
-                                            rerank_by_logprob=True, **kvkw, **qkw)
+                                            rerank_by_logprob=True, **kvkw, **qkw, **mixkw)
             res = [c[:1] for c in candidates]
         elif best_of:
             res = module.generate(video, text_input, do_sample=True, num_samples=best_of, best_of=True, seed=seed + n,
                                   clips_per_search=clips_per_search, **kvkw, **qkw)
         else:
-            res = module.generate(video, text_input, batched=True, clips_per_search=clips_per_search, **kvkw, **qkw) if batched else module.generate(video, text_input, **qkw)
+            res = module.generate(video, text_input, batched=True, clips_per_search=clips_per_search, **kvkw, **qkw, **mixkw) if batched else module.generate(video, text_input, **qkw)
         def caption(ids):
             ans = tokenizer.decode(ids).replace(" ", "").strip()
             return ans.split(config["prompt"])[-1].strip() if config["prompt"] != "" else ans
@@ -291,7 +299,8 @@ def main(args, config):
                             **({"beam_groups": args.eval_beam_groups, "diversity_penalty": args.eval_diversity_penalty}
                                if getattr(args, "eval_beam_groups", 1) > 1 else {}),
                             **({"score_gold": True, "max_length": args.max_length} if getattr(args, "eval_score_gold", False) else {}),
-                            **({"fp8_decode": True} if getattr(args, "eval_fp8_decode", False) else {}))
+                            **({"fp8_decode": True} if getattr(args, "eval_fp8_decode", False) else {}),
+                            **({"mixed_prompts": True} if getattr(args, "eval_mixed_prompts", False) else {}))
         final = save_result(result, args.result_dir, "val_caption_result")
         val_stats = cal_metric(final)
         if getattr(args, "eval_score_gold", False):
@@ -349,6 +358,9 @@ def get_args(argv=None):
         p.add_argument("--eval_fp8_decode", action="store_true", default=False,
                        help="evaluation: the decode steps of every generation call run on e4m3 codes of the decoder's weights "
                             "(model.generate(decode_weights='fp8'))")
+        p.add_argument("--eval_mixed_prompts", action="store_true", default=False,
+                       help="--eval_batched_beam / --eval_beam_groups with --eval_shared_kv: one lockstep search per chunk of clips whatever "
+                            "their prompt lengths (model.generate(mixed_prompts=True)) instead of one per distinct length")
         p.add_argument("--eval_score_gold", action="store_true", default=False,
                        help="evaluation: also score every clip's gold captions against its query features (model.score_captions): "
                             "gold_logprob / gold_tokens in the result file, per-token NLL and perplexity in the log")

@@ -279,6 +279,16 @@ typedef struct mpv_attn_decode_shared_desc {
   float scale;
 } mpv_attn_decode_shared_desc;
 int mpv_attn_decode_shared_fwd(const mpv_attn_decode_shared_desc* d, mpv_stream_t stream);
+/* The same step for groups whose prefixes differ in length (one lockstep search over prompts of different lengths): group g attends
+ * to the first group_prefix_len[g] rows of its prefix (pk / pv + g*x_gs) and to its own_len own rows.  group_prefix_len is a DEVICE
+ * array of int32 [n_groups]; d->prefix_len is the host-side upper bound (at most the rows between two groups' prefixes), and
+ * 1 <= group_prefix_len[g] <= d->prefix_len is the caller's promise: the kernel clamps into that range, so a bad value cannot leave
+ * the group's rows (as mpv_gpt_embed_rows_fwd keeps its positions inside wpe).  Prefix rows at and beyond a group's length are never
+ * read.  One kernel body serves both entries (the uniform one passes no array), with the prefix length a per-workgroup value:
+ *   with every length equal to d->prefix_len the output is mpv_attn_decode_shared_fwd's, bit for bit;
+ *   a group's output is, bit for bit, that of mpv_attn_decode_shared_fwd run on that group alone with prefix_len = its length.
+ * Refused: what mpv_attn_decode_shared_fwd refuses, and a NULL array.  Nothing is read back from the device. */
+int mpv_attn_decode_shared_ragged_fwd(const mpv_attn_decode_shared_desc* d, const int32_t* group_prefix_len, mpv_stream_t stream);
 
 /* Divided space-time "temporal" attention: T<=16 tokens per (b,n) sequence, many tiny
  * problems (models/vision_transformer.py:247-248 with Attention :169-207).  qkv is the packed
@@ -475,6 +485,23 @@ size_t mpv_gpt_decode_shared_workspace_size(const mpv_gpt_weights* w, int n_seq)
 int mpv_gpt_decode_step_shared(const mpv_gpt_weights* w, void* const* prefix_cache, void* const* suffix_cache, int n_groups, int fan,
                                int prefix_len, int suffix_max, int t, const int64_t* tokens, void* workspace,
                                size_t workspace_bytes, void* logits, mpv_stream_t stream);
+/* mpv_gpt_decode_step_shared over groups whose prefixes differ in length: prefix_cache[l] = [n_groups][prefix_stride][3*hidden],
+ * group g's prefix being its first group_prefix_len[g] rows (DEVICE int32 [n_groups], 1 <= length <= max_prefix_len <= prefix_stride:
+ * the caller's promise, clamped on the device); max_prefix_len (host) serves the position-table check max_prefix_len + t <
+ * max_positions.  Sequence s sits at absolute position group_prefix_len[s / fan] + t: the driver forms these positions on the
+ * device inside its workspace, embeds through mpv_gpt_embed_rows_fwd and attends through mpv_attn_decode_shared_ragged_fwd;
+ * everything else -- suffix cache, workspace, the rest of the layer, the LM head, logits -- is mpv_gpt_decode_step_shared's. */
+int mpv_gpt_decode_step_shared_ragged(const mpv_gpt_weights* w, void* const* prefix_cache, void* const* suffix_cache, int n_groups, int fan,
+                                      int prefix_stride, const int32_t* group_prefix_len, int max_prefix_len, int suffix_max, int t,
+                                      const int64_t* tokens, void* workspace, size_t workspace_bytes, void* logits, mpv_stream_t stream);
+/* mpv_gpt_decode_step at pos0 = 0 (a prefill) for prompts of different lengths, right-padded to L tokens behind their real ones:
+ * the LM head runs on row last_row[b] (DEVICE int64 [batch], an index inside sequence b's n = Q + L new rows, clamped into them) of
+ * every sequence, fetched through mpv_gather_rows, instead of on row n - 1.  Causal attention leaves the rows up to last_row[b]
+ * exactly those of a prefill of the unpadded prompt; the pad rows' KV is written to the cache and is for the caller never to read
+ * (mpv_gpt_decode_step_shared_ragged does not).  Refused: what mpv_gpt_decode_step refuses, and a NULL last_row. */
+int mpv_gpt_prefill_ragged(const mpv_gpt_weights* w, void* const* kv_cache, int batch, int max_len, const void* query, int Q,
+                           const int64_t* tokens, int L, const int64_t* last_row, void* workspace, size_t workspace_bytes, void* logits,
+                           mpv_stream_t stream);
 /* beam re-order of all layers: dst[l][j] = src[l][idx[j]] for the first `rows` cached positions */
 int mpv_kv_reorder(void* const* src, void* const* dst, int layers, const int64_t* idx, int batch, int max_len, int rows,
                    int hidden, mpv_stream_t stream);
@@ -515,6 +542,10 @@ int mpv_gemm_w8_tiled(const void* A, const void* codes, const float* scale, void
                       int64_t ldw, int64_t ldc, const mpv_gemm_epilogue* ep, void* workspace, size_t workspace_bytes, mpv_stream_t stream);
 int mpv_gpt_embed_w8_fwd(const void* query, const int64_t* ids, const void* wte_codes, const float* wte_scale, const void* wpe, void* h,
                          int B, int Q, int L, int H, mpv_stream_t stream);
+/* mpv_gpt_embed_rows_fwd (per-row positions, clamped into wpe's max_positions rows; same refusals) with the token rows read as
+ * deq(code) * scale from the tied embedding's codes: mpv_gpt_embed_w8_fwd's conversion, bit for bit. */
+int mpv_gpt_embed_rows_w8_fwd(const int64_t* ids, const int32_t* pos, const void* wte_codes, const float* wte_scale, const void* wpe,
+                              void* out, int rows, int H, int max_positions, mpv_stream_t stream);
 /* The decode steps on FP8 weights: mpv_gpt_decode_step / mpv_gpt_decode_step_shared with the token embedding read from the tied
  * embedding's codes and every weight product of
  *   at most MPV_W8_MAX_ROWS rows                          going to mpv_gemm_w8 on q8's codes,
@@ -542,6 +573,14 @@ int mpv_gpt_decode_step_q8(const mpv_gpt_weights* w, const mpv_gpt_weights_q8* q
 int mpv_gpt_decode_step_shared_q8(const mpv_gpt_weights* w, const mpv_gpt_weights_q8* q8, void* const* prefix_cache,
                                   void* const* suffix_cache, int n_groups, int fan, int prefix_len, int suffix_max, int t,
                                   const int64_t* tokens, void* workspace, size_t workspace_bytes, void* logits, mpv_stream_t stream);
+/* The ragged step and prefill on FP8 weights: the row-count dispatch above, the token rows through mpv_gpt_embed_rows_w8_fwd. */
+int mpv_gpt_decode_step_shared_ragged_q8(const mpv_gpt_weights* w, const mpv_gpt_weights_q8* q8, void* const* prefix_cache,
+                                         void* const* suffix_cache, int n_groups, int fan, int prefix_stride,
+                                         const int32_t* group_prefix_len, int max_prefix_len, int suffix_max, int t, const int64_t* tokens,
+                                         void* workspace, size_t workspace_bytes, void* logits, mpv_stream_t stream);
+int mpv_gpt_prefill_ragged_q8(const mpv_gpt_weights* w, const mpv_gpt_weights_q8* q8, void* const* kv_cache, int batch, int max_len,
+                              const void* query, int Q, const int64_t* tokens, int L, const int64_t* last_row, void* workspace,
+                              size_t workspace_bytes, void* logits, mpv_stream_t stream);
 /* ------------------------------------------------------------------------------------------
  * Lockstep beam search over a batch of clips (caption evaluation, generation.beam_search_batched_loop): ONE launch advances the
  * beam state of `batch` clips x `beams` (K) beams by one position, doing per clip exactly what one iteration of the reference's

@@ -279,6 +279,17 @@ _SIGS.update({
                                        c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     "mpv_gpt_decode_step_shared_q8": (c_int, [C.POINTER(GptWeights), C.POINTER(GptWeightsQ8), C.POINTER(c_void_p), C.POINTER(c_void_p), c_int,
                                               c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "mpv_attn_decode_shared_ragged_fwd": (c_int, [C.POINTER(AttnDecodeSharedDesc), c_void_p, c_void_p]),
+    "mpv_gpt_embed_rows_w8_fwd": (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_void_p]),
+    "mpv_gpt_decode_step_shared_ragged": (c_int, [C.POINTER(GptWeights), C.POINTER(c_void_p), C.POINTER(c_void_p), c_int, c_int, c_int,
+                                                  c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "mpv_gpt_decode_step_shared_ragged_q8": (c_int, [C.POINTER(GptWeights), C.POINTER(GptWeightsQ8), C.POINTER(c_void_p), C.POINTER(c_void_p),
+                                                     c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t,
+                                                     c_void_p, c_void_p]),
+    "mpv_gpt_prefill_ragged": (c_int, [C.POINTER(GptWeights), C.POINTER(c_void_p), c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                       c_void_p, c_size_t, c_void_p, c_void_p]),
+    "mpv_gpt_prefill_ragged_q8": (c_int, [C.POINTER(GptWeights), C.POINTER(GptWeightsQ8), C.POINTER(c_void_p), c_int, c_int, c_void_p, c_int,
+                                          c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
 })
 
 EXPORTS = tuple(_SIGS)

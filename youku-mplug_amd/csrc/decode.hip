@@ -8,6 +8,18 @@
 #include "../../include/mpv.h"
 #include "mpv_common.h"
 
+// The two index vectors the ragged entries form on the device (nothing is read back):
+//   positions  pos[s] = clamp(group_prefix_len[s / fan], 1, max_prefix_len) + t      the position row of sequence s' new token
+//   last rows  idx[b] = b * n + clamp(last_row[b], 0, n - 1)                         the row of sequence b the LM head runs on
+__global__ void ragged_positions_kernel(const int32_t* __restrict__ glen, int32_t* __restrict__ pos, int n_seq, int fan, int max_plen, int t) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s < n_seq) pos[s] = min(max(glen[s / fan], 1), max_plen) + t;
+}
+__global__ void ragged_last_rows_kernel(const int64_t* __restrict__ last_row, int64_t* __restrict__ idx, int batch, int n) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < batch) idx[b] = (int64_t)b * n + min(max(last_row[b], (int64_t)0), (int64_t)(n - 1));
+}
+
 static inline char* carve(char*& p, size_t bytes) {
   char* r = p;
   p += (bytes + 255) / 256 * 256;
@@ -87,17 +99,19 @@ static int check_q8(const mpv_gpt_weights* w, const mpv_gpt_weights_q8* q8, cons
   return MPV_OK;
 }
 
-// the body of mpv_gpt_decode_step and mpv_gpt_decode_step_q8 (q8 == nullptr: the bf16 step)
-static int decode_step(const mpv_gpt_weights* w, const mpv_gpt_weights_q8* q8, void* const* kv_cache, int batch, int max_len, int pos0,
+// the body of mpv_gpt_decode_step, mpv_gpt_decode_step_q8 (q8 == nullptr: the bf16 step) and of the ragged prefills (last_row !=
+// nullptr: the LM head runs on row last_row[b] of sequence b's n new rows instead of on row n - 1)
+static int decode_step(const char* who,
+                       const mpv_gpt_weights* w, const mpv_gpt_weights_q8* q8, void* const* kv_cache, int batch, int max_len, int pos0,
                        const void* query, int Q, const int64_t* tokens, int L, void* workspace, size_t workspace_bytes, void* logits,
-                       hipStream_t stream) {
-  MPV_REQUIRE(w && kv_cache && workspace && logits, MPV_E_ARG, "mpv_gpt_decode_step: null pointer");
+                       hipStream_t stream, const int64_t* last_row = nullptr) {
+  MPV_REQUIRE(w && kv_cache && workspace && logits, MPV_E_ARG, "%s: null pointer", who);
   const int n = Q + L, H = w->hidden, np = w->heads, hn = H / np, F4 = w->ffn;
   MPV_REQUIRE(batch > 0 && n > 0 && pos0 >= 0 && pos0 + n <= max_len, MPV_E_SHAPE,
-              "mpv_gpt_decode_step: positions [%d, %d) do not fit max_len %d", pos0, pos0 + n, max_len);
+              "%s: positions [%d, %d) do not fit max_len %d", who, pos0, pos0 + n, max_len);
   MPV_REQUIRE(w->max_positions <= 0 || pos0 + n <= w->max_positions, MPV_E_SHAPE,
-              "mpv_gpt_decode_step: positions [%d, %d) run past the %d rows of the position embedding", pos0, pos0 + n, w->max_positions);
-  MPV_REQUIRE(workspace_bytes >= mpv_gpt_decode_workspace_size(w, batch, n), MPV_E_ARG, "mpv_gpt_decode_step: workspace too small");
+              "%s: positions [%d, %d) run past the %d rows of the position embedding", who, pos0, pos0 + n, w->max_positions);
+  MPV_REQUIRE(workspace_bytes >= mpv_gpt_decode_workspace_size(w, batch, n), MPV_E_ARG, "%s: workspace too small", who);
   const int64_t R = (int64_t)batch * n;
   char* p = (char*)workspace;
   void* h = carve(p, R * H * 2);
@@ -139,7 +153,14 @@ static int decode_step(const mpv_gpt_weights* w, const mpv_gpt_weights_q8* q8, v
     if (rc) return rc;
   }
   const void* lastrow = h;
-  if (n > 1) {   // LM head on the last position of every sequence only
+  if (last_row) {   // LM head on the caller's row of every sequence; x is free behind the last layer and takes the row indices
+    hipLaunchKernelGGL(ragged_last_rows_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, stream, last_row, (int64_t*)x, batch, n);
+    rc = mpv_check_launch(who);
+    if (rc) return rc;
+    rc = mpv_gather_rows(h, (const int64_t*)x, last, batch, H, H, stream);
+    if (rc) return rc;
+    lastrow = last;
+  } else if (n > 1) {   // LM head on the last position of every sequence only
     rc = mpv_copy_rows(h, last, batch, H, H, H, 1, n, n - 1, 0, 0, 0, stream);
     if (rc) return rc;
     lastrow = last;
@@ -150,7 +171,8 @@ static int decode_step(const mpv_gpt_weights* w, const mpv_gpt_weights_q8* q8, v
 extern "C" int mpv_gpt_decode_step(const mpv_gpt_weights* w, void* const* kv_cache, int batch, int max_len, int pos0,
                                    const void* query, int Q, const int64_t* tokens, int L, void* workspace,
                                    size_t workspace_bytes, void* logits, hipStream_t stream) {
-  return decode_step(w, nullptr, kv_cache, batch, max_len, pos0, query, Q, tokens, L, workspace, workspace_bytes, logits, stream);
+  return decode_step("mpv_gpt_decode_step",
+                     w, nullptr, kv_cache, batch, max_len, pos0, query, Q, tokens, L, workspace, workspace_bytes, logits, stream);
 }
 
 extern "C" int mpv_gpt_decode_step_q8(const mpv_gpt_weights* w, const mpv_gpt_weights_q8* q8, void* const* kv_cache, int batch,
@@ -158,7 +180,27 @@ extern "C" int mpv_gpt_decode_step_q8(const mpv_gpt_weights* w, const mpv_gpt_we
                                       size_t workspace_bytes, void* logits, hipStream_t stream) {
   const int rc = check_q8(w, q8, "mpv_gpt_decode_step_q8");
   if (rc) return rc;
-  return decode_step(w, q8, kv_cache, batch, max_len, pos0, query, Q, tokens, L, workspace, workspace_bytes, logits, stream);
+  return decode_step("mpv_gpt_decode_step_q8",
+                     w, q8, kv_cache, batch, max_len, pos0, query, Q, tokens, L, workspace, workspace_bytes, logits, stream);
+}
+
+// the prefill of prompts of different lengths (include/mpv.h states the contract)
+extern "C" int mpv_gpt_prefill_ragged(const mpv_gpt_weights* w, void* const* kv_cache, int batch, int max_len, const void* query, int Q,
+                                      const int64_t* tokens, int L, const int64_t* last_row, void* workspace, size_t workspace_bytes,
+                                      void* logits, hipStream_t stream) {
+  MPV_REQUIRE(last_row, MPV_E_ARG, "mpv_gpt_prefill_ragged: null last_row");
+  return decode_step("mpv_gpt_prefill_ragged",
+                     w, nullptr, kv_cache, batch, max_len, 0, query, Q, tokens, L, workspace, workspace_bytes, logits, stream, last_row);
+}
+
+extern "C" int mpv_gpt_prefill_ragged_q8(const mpv_gpt_weights* w, const mpv_gpt_weights_q8* q8, void* const* kv_cache, int batch,
+                                         int max_len, const void* query, int Q, const int64_t* tokens, int L, const int64_t* last_row,
+                                         void* workspace, size_t workspace_bytes, void* logits, hipStream_t stream) {
+  MPV_REQUIRE(last_row, MPV_E_ARG, "mpv_gpt_prefill_ragged_q8: null last_row");
+  const int rc = check_q8(w, q8, "mpv_gpt_prefill_ragged_q8");
+  if (rc) return rc;
+  return decode_step("mpv_gpt_prefill_ragged_q8",
+                     w, q8, kv_cache, batch, max_len, 0, query, Q, tokens, L, workspace, workspace_bytes, logits, stream, last_row);
 }
 
 // mpv_gpt_decode_step for one token per sequence against a per-group shared prefix cache (include/mpv.h states the contract)
@@ -166,20 +208,27 @@ extern "C" size_t mpv_gpt_decode_shared_workspace_size(const mpv_gpt_weights* w,
   return mpv_gpt_decode_workspace_size(w, n_seq, 1);
 }
 
-// the body of mpv_gpt_decode_step_shared and mpv_gpt_decode_step_shared_q8 (q8 == nullptr: the bf16 step)
-static int decode_step_shared(const mpv_gpt_weights* w, const mpv_gpt_weights_q8* q8, void* const* prefix_cache, void* const* suffix_cache,
+// the body of mpv_gpt_decode_step_shared, mpv_gpt_decode_step_shared_q8 (q8 == nullptr: the bf16 step) and of the two ragged steps
+// (ragged: group g's prefix is glen[g] <= prefix_len rows long inside its prefix_stride rows; otherwise prefix_stride == prefix_len)
+static int decode_step_shared(const char* who,
+                              const mpv_gpt_weights* w, const mpv_gpt_weights_q8* q8, void* const* prefix_cache, void* const* suffix_cache,
                               int n_groups, int fan, int prefix_len, int suffix_max, int t, const int64_t* tokens, void* workspace,
-                              size_t workspace_bytes, void* logits, hipStream_t stream) {
-  MPV_REQUIRE(w && prefix_cache && suffix_cache && tokens && workspace && logits, MPV_E_ARG, "mpv_gpt_decode_step_shared: null pointer");
+                              size_t workspace_bytes, void* logits, hipStream_t stream, bool ragged = false, const int32_t* glen = nullptr,
+                              int prefix_stride = 0) {
+  if (!ragged) prefix_stride = prefix_len;
+  MPV_REQUIRE(!ragged || glen, MPV_E_ARG, "%s: null group_prefix_len", who);
+  MPV_REQUIRE(prefix_stride >= prefix_len, MPV_E_SHAPE, "%s: max_prefix_len %d exceeds the prefix_stride %d", who,
+              prefix_len, prefix_stride);
+  MPV_REQUIRE(w && prefix_cache && suffix_cache && tokens && workspace && logits, MPV_E_ARG, "%s: null pointer", who);
   MPV_REQUIRE(n_groups > 0 && fan > 0 && (int64_t)n_groups * fan < (1ll << 31) && prefix_len > 0, MPV_E_SHAPE,
-              "mpv_gpt_decode_step_shared: empty problem (n_groups %d, fan %d, prefix_len %d)", n_groups, fan, prefix_len);
+              "%s: empty problem (n_groups %d, fan %d, prefix_len %d)", who, n_groups, fan, prefix_len);
   MPV_REQUIRE(t >= 0 && t < suffix_max && t < 2048, MPV_E_SHAPE,
-              "mpv_gpt_decode_step_shared: suffix position %d does not fit suffix_max %d (and the attention's 2048 own rows)", t, suffix_max);
+              "%s: suffix position %d does not fit suffix_max %d (and the attention's 2048 own rows)", who, t, suffix_max);
   MPV_REQUIRE(w->max_positions <= 0 || prefix_len + t < w->max_positions, MPV_E_SHAPE,
-              "mpv_gpt_decode_step_shared: position %d runs past the %d rows of the position embedding", prefix_len + t, w->max_positions);
+              "%s: position %d runs past the %d rows of the position embedding", who, prefix_len + t, w->max_positions);
   const int n_seq = n_groups * fan, H = w->hidden, np = w->heads, hn = H / np, F4 = w->ffn;
   MPV_REQUIRE(workspace_bytes >= mpv_gpt_decode_shared_workspace_size(w, n_seq), MPV_E_ARG,
-              "mpv_gpt_decode_step_shared: workspace too small");
+              "%s: workspace too small", who);
   const int64_t R = n_seq;
   char* p = (char*)workspace;
   void* h = carve(p, R * H * 2);
@@ -187,10 +236,22 @@ static int decode_step_shared(const mpv_gpt_weights* w, const mpv_gpt_weights_q8
   void* ctx = carve(p, R * H * 2);
   void* h1 = carve(p, R * H * 2);
   void* g = carve(p, R * F4 * 2);
-  carve(p, (size_t)n_seq * H * 2);                       // (the `last` rows of the general step: one position needs no copy)
+  void* pos = carve(p, (size_t)n_seq * H * 2);           // (the `last` rows of the general step: one position needs no copy; the
+                                                         // ragged step keeps its n_seq int32 positions there)
   void* xf = carve(p, (size_t)n_seq * H * 2);
   const Products product = {p, workspace_bytes - (size_t)(p - (char*)workspace), stream};
-  int rc = embed(w, q8, nullptr, tokens, prefix_len + t, h, n_seq, 0, 1, stream);
+  int rc;
+  if (ragged) {
+    hipLaunchKernelGGL(ragged_positions_kernel, dim3((unsigned)((n_seq + 255) / 256)), dim3(256), 0, stream, glen, (int32_t*)pos, n_seq, fan,
+                       prefix_len, t);
+    rc = mpv_check_launch(who);
+    if (rc) return rc;
+    const int rows_wpe = w->max_positions > 0 ? w->max_positions : prefix_len + t + 1;
+    rc = q8 ? mpv_gpt_embed_rows_w8_fwd(tokens, (const int32_t*)pos, q8->wte_q, (const float*)q8->wte_s, w->wpe, h, n_seq, H, rows_wpe, stream)
+            : mpv_gpt_embed_rows_fwd(tokens, (const int32_t*)pos, w->wte, w->wpe, h, n_seq, H, rows_wpe, stream);
+  } else {
+    rc = embed(w, q8, nullptr, tokens, prefix_len + t, h, n_seq, 0, 1, stream);
+  }
   if (rc) return rc;
   for (int li = 0; li < w->layers; ++li) {
     const mpv_gpt_layer_weights* lw = &w->layer[li];
@@ -212,14 +273,14 @@ static int decode_step_shared(const mpv_gpt_weights* w, const mpv_gpt_weights_q8
     d.pv = pc + (size_t)2 * hn * 2;
     d.o = ctx;
     d.q_ss = d.k_ss = d.v_ss = (int64_t)suffix_max * 3 * H;
-    d.pk_gs = d.pv_gs = (int64_t)prefix_len * 3 * H;
+    d.pk_gs = d.pv_gs = (int64_t)prefix_stride * 3 * H;
     d.q_hs = d.k_hs = d.v_hs = d.pk_hs = d.pv_hs = 3 * hn;
     d.k_rs = d.v_rs = d.pk_rs = d.pv_rs = 3 * H;
     d.o_ss = H; d.o_hs = hn;
     d.n_seq = n_seq; d.group_size = fan; d.n_groups = n_groups; d.heads = np;
     d.prefix_len = prefix_len; d.own_len = t + 1; d.head_dim = hn;
     d.scale = 1.0f / sqrtf((float)hn);
-    rc = mpv_attn_decode_shared_fwd(&d, stream);
+    rc = ragged ? mpv_attn_decode_shared_ragged_fwd(&d, glen, stream) : mpv_attn_decode_shared_fwd(&d, stream);
     if (rc) return rc;
     rc = layer_tail(w, lw, lq, R, h, x, ctx, h1, g, product);
     if (rc) return rc;
@@ -230,7 +291,8 @@ static int decode_step_shared(const mpv_gpt_weights* w, const mpv_gpt_weights_q8
 extern "C" int mpv_gpt_decode_step_shared(const mpv_gpt_weights* w, void* const* prefix_cache, void* const* suffix_cache, int n_groups,
                                           int fan, int prefix_len, int suffix_max, int t, const int64_t* tokens, void* workspace,
                                           size_t workspace_bytes, void* logits, hipStream_t stream) {
-  return decode_step_shared(w, nullptr, prefix_cache, suffix_cache, n_groups, fan, prefix_len, suffix_max, t, tokens, workspace,
+  return decode_step_shared("mpv_gpt_decode_step_shared",
+                            w, nullptr, prefix_cache, suffix_cache, n_groups, fan, prefix_len, suffix_max, t, tokens, workspace,
                             workspace_bytes, logits, stream);
 }
 
@@ -240,8 +302,30 @@ extern "C" int mpv_gpt_decode_step_shared_q8(const mpv_gpt_weights* w, const mpv
                                              hipStream_t stream) {
   const int rc = check_q8(w, q8, "mpv_gpt_decode_step_shared_q8");
   if (rc) return rc;
-  return decode_step_shared(w, q8, prefix_cache, suffix_cache, n_groups, fan, prefix_len, suffix_max, t, tokens, workspace, workspace_bytes,
-                            logits, stream);
+  return decode_step_shared("mpv_gpt_decode_step_shared_q8",
+                            w, q8, prefix_cache, suffix_cache, n_groups, fan, prefix_len, suffix_max, t, tokens, workspace,
+                            workspace_bytes, logits, stream);
+}
+
+extern "C" int mpv_gpt_decode_step_shared_ragged(const mpv_gpt_weights* w, void* const* prefix_cache, void* const* suffix_cache, int n_groups,
+                                                 int fan, int prefix_stride, const int32_t* group_prefix_len, int max_prefix_len,
+                                                 int suffix_max, int t, const int64_t* tokens, void* workspace, size_t workspace_bytes,
+                                                 void* logits, hipStream_t stream) {
+  return decode_step_shared("mpv_gpt_decode_step_shared_ragged",
+                            w, nullptr, prefix_cache, suffix_cache, n_groups, fan, max_prefix_len, suffix_max, t, tokens, workspace,
+                            workspace_bytes, logits, stream, true, group_prefix_len, prefix_stride);
+}
+
+extern "C" int mpv_gpt_decode_step_shared_ragged_q8(const mpv_gpt_weights* w, const mpv_gpt_weights_q8* q8, void* const* prefix_cache,
+                                                    void* const* suffix_cache, int n_groups, int fan, int prefix_stride,
+                                                    const int32_t* group_prefix_len, int max_prefix_len, int suffix_max, int t,
+                                                    const int64_t* tokens, void* workspace, size_t workspace_bytes, void* logits,
+                                                    hipStream_t stream) {
+  const int rc = check_q8(w, q8, "mpv_gpt_decode_step_shared_ragged_q8");
+  if (rc) return rc;
+  return decode_step_shared("mpv_gpt_decode_step_shared_ragged_q8",
+                            w, q8, prefix_cache, suffix_cache, n_groups, fan, max_prefix_len, suffix_max, t, tokens, workspace,
+                            workspace_bytes, logits, stream, true, group_prefix_len, prefix_stride);
 }
 
 // InferenceParams.swap_key_value_dict (:1459-1473) for every layer: dst[l][j] = src[l][idx[j]], first `rows` positions

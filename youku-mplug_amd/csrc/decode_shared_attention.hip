@@ -15,6 +15,10 @@
 // result therefore depends on the prefix, on its own keys and on nothing else: not on its place in the group, not on the group's
 // place in the launch.  Tile arithmetic: prefix_tile.h (S^T = K Q^T on mfma_f32_32x32x16_bf16, online softmax in fp32,
 // probabilities rounded to bf16 for the PV product).  No atomics, no stores outside o.
+//
+// The ragged entry (mpv_attn_decode_shared_ragged_fwd: prompts of different lengths in one lockstep search) is the same kernel with
+// a per-group prefix length: plen, the prefix tile count pt and with it the (pt + r) % 4 wave assignment are per-workgroup values,
+// read once (a workgroup serves one group).  A group's arithmetic is that of the uniform entry at its length, bit for bit.
 #include <string.h>
 
 #include "mpv_common.h"
@@ -31,6 +35,7 @@ constexpr int DS_MAX_OWN = 2048;
 
 struct SharedArgs {
   const bf16 *q, *k, *v, *pk, *pv;
+  const int* glen;                                // per-group prefix lengths (device), or nullptr: plen for every group
   bf16* o;
   long long q_ss, q_hs, k_ss, k_hs, k_rs, v_ss, v_hs, v_rs;
   long long pk_gs, pk_hs, pk_rs, pv_gs, pv_hs, pv_rs, o_ss, o_hs;
@@ -58,7 +63,7 @@ struct SharedStage {
 
   // tile T of the stream: prefix tile (T < pt) or own tile (T - pt) % nt of tile-local row (T - pt) / nt
   __device__ __forceinline__ void issue(const SharedArgs& p, const bf16* pkb, const bf16* pvb, const bf16* kb, const bf16* vb, int tid,
-                                        int chunk, int pt, int nt, int nrows) {
+                                        int chunk, int plen, int pt, int nt, int nrows) {
 #pragma unroll
     for (int i = 0; i < NLOAD; ++i) {
       const int c = tid + DS_THREADS * i;
@@ -68,7 +73,7 @@ struct SharedStage {
       if (cc * 8 < p.hd) {
         if (T < pt) {
           const int key = T * 32 + kr;
-          if (key < p.plen) {
+          if (key < plen) {
             xk = *(const i32x4*)(pkb + (long long)key * p.pk_rs + cc * 8);
             xv = *(const i32x4*)(pvb + (long long)key * p.pv_rs + cc * 8);
           }
@@ -109,7 +114,9 @@ __global__ __launch_bounds__(DS_THREADS, 2) void attn_decode_shared_kernel(const
   const int nrows = min(32, min(p.group_size, p.n_seq - g * p.group_size) - (int)blockIdx.x * 32);
   if (nrows <= 0) return;                                                  // (a short last group): uniform over the workgroup
   const int rr = lane & 31;                                                // this lane's query row inside the tile
-  const int pt = (p.plen + 31) >> 5, nt = (p.own + 31) >> 5;               // prefix tiles, own tiles per row
+  // the group's prefix length: the ragged entry's is clamped into [1, p.plen], so a bad value cannot leave the group's rows
+  const int plen = p.glen ? min(max(p.glen[g], 1), p.plen) : p.plen;
+  const int pt = (plen + 31) >> 5, nt = (p.own + 31) >> 5;                 // prefix tiles, own tiles per row
   const int ntiles = pt + nrows * nt;
   const int nchunk = (ntiles + DS_WAVES - 1) / DS_WAVES;
 
@@ -139,14 +146,14 @@ __global__ __launch_bounds__(DS_THREADS, 2) void attn_decode_shared_kernel(const
   const bf16* vb = p.v + (long long)s0 * p.v_ss + (long long)h * p.v_hs;
 
   SharedStage<HD> st;
-  st.issue(p, pkb, pvb, kb, vb, tid, 0, pt, nt, nrows);
+  st.issue(p, pkb, pvb, kb, vb, tid, 0, plen, pt, nt, nrows);
   st.commit(smem, tid);
   __syncthreads();
   // head_dim 64 keeps the next chunk's loads in flight (in registers) under the tiles of this one; head_dim 80 has 16 more
   // accumulator registers per triple and 16 more staging registers, and would spill: it loads between the two barriers
   constexpr bool PREFETCH = HD == 64;
   for (int c = 0; c < nchunk; ++c) {
-    if (PREFETCH && c + 1 < nchunk) st.issue(p, pkb, pvb, kb, vb, tid, c + 1, pt, nt, nrows);
+    if (PREFETCH && c + 1 < nchunk) st.issue(p, pkb, pvb, kb, vb, tid, c + 1, plen, pt, nt, nrows);
 #pragma unroll 1
     for (int s = 0; s < DS_WAVES; ++s) {
       const int T = c * DS_WAVES + s;
@@ -154,7 +161,7 @@ __global__ __launch_bounds__(DS_THREADS, 2) void attn_decode_shared_kernel(const
       if (T < pt) {
         if (s != wave) continue;
         const int key0 = T * 32;
-        ptile_update<HD>(smem, smem + DS_KV, s, key0, qf, sc, pm, pl, pacc, lane, [&](int key) { return key < p.plen; });
+        ptile_update<HD>(smem, smem + DS_KV, s, key0, qf, sc, pm, pl, pacc, lane, [&](int key) { return key < plen; });
       } else {
         const int tt = T - pt;
         const int r = nt == 1 ? tt : tt / nt;
@@ -165,7 +172,7 @@ __global__ __launch_bounds__(DS_THREADS, 2) void attn_decode_shared_kernel(const
     }
     __syncthreads();                                                       // every wave is done with the chunk
     if (c + 1 < nchunk) {
-      if (!PREFETCH) st.issue(p, pkb, pvb, kb, vb, tid, c + 1, pt, nt, nrows);
+      if (!PREFETCH) st.issue(p, pkb, pvb, kb, vb, tid, c + 1, plen, pt, nt, nrows);
       st.commit(smem, tid);
       __syncthreads();
     }
@@ -224,35 +231,38 @@ __global__ __launch_bounds__(DS_THREADS, 2) void attn_decode_shared_kernel(const
 
 }  // namespace
 
-extern "C" int mpv_attn_decode_shared_fwd(const mpv_attn_decode_shared_desc* d, hipStream_t stream) {
-  MPV_REQUIRE(d && d->q && d->k && d->v && d->pk && d->pv && d->o, MPV_E_ARG, "mpv_attn_decode_shared_fwd: null pointer");
+// the body of both entries (glen == nullptr: the uniform one); `who` names the entry in the messages
+static int launch_shared(const mpv_attn_decode_shared_desc* d, const int32_t* glen, bool ragged, const char* who, hipStream_t stream) {
+  MPV_REQUIRE(d && d->q && d->k && d->v && d->pk && d->pv && d->o, MPV_E_ARG, "%s: null pointer", who);
+  MPV_REQUIRE(!ragged || glen, MPV_E_ARG, "%s: null group_prefix_len", who);
   MPV_REQUIRE(d->head_dim == 64 || d->head_dim == 80, MPV_E_SHAPE,
-              "mpv_attn_decode_shared_fwd: head_dim %d is not supported (64: the 1.3B decoder, 80: 2.7B)", d->head_dim);
+              "%s: head_dim %d is not supported (64: the 1.3B decoder, 80: 2.7B)", who, d->head_dim);
   MPV_REQUIRE(d->n_seq > 0 && d->group_size > 0 && d->heads > 0, MPV_E_SHAPE,
-              "mpv_attn_decode_shared_fwd: empty problem (n_seq %d, group_size %d, heads %d)", d->n_seq, d->group_size, d->heads);
+              "%s: empty problem (n_seq %d, group_size %d, heads %d)", who, d->n_seq, d->group_size, d->heads);
   MPV_REQUIRE(d->prefix_len >= 1 && d->prefix_len < (1 << 24), MPV_E_SHAPE,
-              "mpv_attn_decode_shared_fwd: prefix_len %d must lie in [1, 2^24)", d->prefix_len);
-  MPV_REQUIRE(d->own_len >= 1 && d->own_len <= DS_MAX_OWN, MPV_E_SHAPE, "mpv_attn_decode_shared_fwd: own_len %d must lie in [1, %d]",
+              "%s: prefix_len %d must lie in [1, 2^24)", who, d->prefix_len);
+  MPV_REQUIRE(d->own_len >= 1 && d->own_len <= DS_MAX_OWN, MPV_E_SHAPE, "%s: own_len %d must lie in [1, %d]", who,
               d->own_len, DS_MAX_OWN);
   MPV_REQUIRE(d->n_groups == (d->n_seq + d->group_size - 1) / d->group_size, MPV_E_SHAPE,
-              "mpv_attn_decode_shared_fwd: n_groups %d must be ceil(n_seq %d / group_size %d)", d->n_groups, d->n_seq, d->group_size);
-  MPV_REQUIRE(d->n_groups <= 65535 && d->heads <= 65535, MPV_E_SHAPE, "mpv_attn_decode_shared_fwd: problem too large");
+              "%s: n_groups %d must be ceil(n_seq %d / group_size %d)", who, d->n_groups, d->n_seq, d->group_size);
+  MPV_REQUIRE(d->n_groups <= 65535 && d->heads <= 65535, MPV_E_SHAPE, "%s: problem too large", who);
   const int64_t st[] = {d->q_ss, d->q_hs, d->k_ss, d->k_hs, d->k_rs, d->v_ss, d->v_hs, d->v_rs,
                         d->pk_gs, d->pk_hs, d->pk_rs, d->pv_gs, d->pv_hs, d->pv_rs};
   bool al = true;
   for (int64_t s : st) al = al && (s % 8 == 0);
   MPV_REQUIRE(al && d->o_ss % 4 == 0 && d->o_hs % 4 == 0, MPV_E_ALIGN,
-              "mpv_attn_decode_shared_fwd: strides must keep q/k/v/pk/pv rows 16-byte and o rows 8-byte aligned");
+              "%s: strides must keep q/k/v/pk/pv rows 16-byte and o rows 8-byte aligned", who);
   MPV_REQUIRE((((uintptr_t)d->q | (uintptr_t)d->k | (uintptr_t)d->v | (uintptr_t)d->pk | (uintptr_t)d->pv) & 15) == 0 &&
                   ((uintptr_t)d->o & 7) == 0,
-              MPV_E_ALIGN, "mpv_attn_decode_shared_fwd: q/k/v/pk/pv must be 16-byte aligned, o 8-byte aligned");
-  MPV_REQUIRE(d->scale > 0.f, MPV_E_ARG, "mpv_attn_decode_shared_fwd: scale must be positive");
+              MPV_E_ALIGN, "%s: q/k/v/pk/pv must be 16-byte aligned, o 8-byte aligned", who);
+  MPV_REQUIRE(d->scale > 0.f, MPV_E_ARG, "%s: scale must be positive", who);
   SharedArgs a;
   a.q = (const bf16*)d->q;
   a.k = (const bf16*)d->k;
   a.v = (const bf16*)d->v;
   a.pk = (const bf16*)d->pk;
   a.pv = (const bf16*)d->pv;
+  a.glen = glen;
   a.o = (bf16*)d->o;
   a.q_ss = d->q_ss; a.q_hs = d->q_hs;
   a.k_ss = d->k_ss; a.k_hs = d->k_hs; a.k_rs = d->k_rs;
@@ -271,5 +281,14 @@ extern "C" int mpv_attn_decode_shared_fwd(const mpv_attn_decode_shared_desc* d, 
     hipLaunchKernelGGL(attn_decode_shared_kernel<64>, grid, dim3(DS_THREADS), 0, stream, a);
   else
     hipLaunchKernelGGL(attn_decode_shared_kernel<80>, grid, dim3(DS_THREADS), 0, stream, a);
-  return mpv_check_launch("mpv_attn_decode_shared_fwd");
+  return mpv_check_launch(who);
+}
+
+extern "C" int mpv_attn_decode_shared_fwd(const mpv_attn_decode_shared_desc* d, hipStream_t stream) {
+  return launch_shared(d, nullptr, false, "mpv_attn_decode_shared_fwd", stream);
+}
+
+extern "C" int mpv_attn_decode_shared_ragged_fwd(const mpv_attn_decode_shared_desc* d, const int32_t* group_prefix_len,
+                                                 hipStream_t stream) {
+  return launch_shared(d, group_prefix_len, true, "mpv_attn_decode_shared_ragged_fwd", stream);
 }

@@ -345,6 +345,15 @@ __global__ __launch_bounds__(256) void quantize_rows_e4m3_kernel(const bf16* __r
   }
 }
 
+// eight columns of the tied embedding's row `id` as deq(code) * scale: the one conversion of both embedding kernels below
+__device__ __forceinline__ f32x8 deq_row8(const uint8_t* __restrict__ codes, const float* __restrict__ scale, int64_t id, int H, int c8) {
+  const i32x2 c = *(const i32x2*)(codes + id * (long long)H + c8 * 8);
+  const float sc = scale[id];
+  const f32x2 f0 = __builtin_amdgcn_cvt_pk_f32_fp8(c[0], false), f1 = __builtin_amdgcn_cvt_pk_f32_fp8(c[0], true);
+  const f32x2 f2 = __builtin_amdgcn_cvt_pk_f32_fp8(c[1], false), f3 = __builtin_amdgcn_cvt_pk_f32_fp8(c[1], true);
+  return f32x8{f0[0], f0[1], f1[0], f1[1], f2[0], f2[1], f3[0], f3[1]} * sc;        // exact: a bf16 value
+}
+
 // gpt_embed_fwd_kernel (elementwise.hip) without dropout, the token rows being deq(code) * scale
 __global__ void gpt_embed_w8_fwd_kernel(const bf16* __restrict__ query, const int64_t* __restrict__ ids, const uint8_t* __restrict__ codes,
                                         const float* __restrict__ scale, const bf16* __restrict__ wpe, bf16* __restrict__ h, int B, int Q,
@@ -361,14 +370,25 @@ __global__ void gpt_embed_w8_fwd_kernel(const bf16* __restrict__ query, const in
       v = cvt8(*(const bf16x8*)(query + (b * Q + s) * (long long)H + c8 * 8));
     } else {
       const int64_t id = ids[b * L + (s - Q)];
-      const i32x2 c = *(const i32x2*)(codes + id * (long long)H + c8 * 8);
-      const float sc = scale[id];
-      const f32x2 f0 = __builtin_amdgcn_cvt_pk_f32_fp8(c[0], false), f1 = __builtin_amdgcn_cvt_pk_f32_fp8(c[0], true);
-      const f32x2 f2 = __builtin_amdgcn_cvt_pk_f32_fp8(c[1], false), f3 = __builtin_amdgcn_cvt_pk_f32_fp8(c[1], true);
-      v = f32x8{f0[0], f0[1], f1[0], f1[1], f2[0], f2[1], f3[0], f3[1]} * sc;        // exact: a bf16 value
+      v = deq_row8(codes, scale, id, H, c8);
     }
     v += cvt8(*(const bf16x8*)(wpe + (long long)s * H + c8 * 8));
     *(bf16x8*)(h + row * H + c8 * 8) = cvt8(v);
+  }
+}
+
+// gpt_embed_rows_fwd_kernel (elementwise.hip: per-row positions, no query rows), the token rows being deq(code) * scale
+__global__ void gpt_embed_rows_w8_fwd_kernel(const int64_t* __restrict__ ids, const int32_t* __restrict__ pos, const uint8_t* __restrict__ codes,
+                                             const float* __restrict__ scale, const bf16* __restrict__ wpe, bf16* __restrict__ out, int rows,
+                                             int H, int max_positions) {
+  const int H8 = H / 8;
+  const long long total = (long long)rows * H8;
+  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+    const int c8 = (int)(idx % H8);
+    const long long row = idx / H8;
+    f32x8 v = deq_row8(codes, scale, ids[row], H, c8);
+    v += cvt8(*(const bf16x8*)(wpe + (long long)min(max(pos[row], 0), max_positions - 1) * H + c8 * 8));   // never outside wpe
+    *(bf16x8*)(out + row * H + c8 * 8) = cvt8(v);
   }
 }
 
@@ -509,4 +529,16 @@ extern "C" int mpv_gpt_embed_w8_fwd(const void* query, const int64_t* ids, const
   hipLaunchKernelGGL(gpt_embed_w8_fwd_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, stream, (const bf16*)query, ids,
                      (const uint8_t*)wte_codes, wte_scale, (const bf16*)wpe, (bf16*)h, B, Q, L, H);
   return mpv_check_launch("mpv_gpt_embed_w8_fwd");
+}
+
+extern "C" int mpv_gpt_embed_rows_w8_fwd(const int64_t* ids, const int32_t* pos, const void* wte_codes, const float* wte_scale, const void* wpe,
+                                         void* out, int rows, int H, int max_positions, hipStream_t stream) {
+  MPV_REQUIRE(ids && pos && wte_codes && wte_scale && wpe && out, MPV_E_ARG, "mpv_gpt_embed_rows_w8_fwd: null pointer");
+  MPV_REQUIRE(rows > 0 && H > 0 && H % 8 == 0 && max_positions > 0, MPV_E_SHAPE,
+              "mpv_gpt_embed_rows_w8_fwd: bad shape (rows %d, H %d, max_positions %d)", rows, H, max_positions);
+  const long long total = (long long)rows * (H / 8);
+  const long long blocks = (total + 255) / 256;
+  hipLaunchKernelGGL(gpt_embed_rows_w8_fwd_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, stream, ids, pos,
+                     (const uint8_t*)wte_codes, wte_scale, (const bf16*)wpe, (bf16*)out, rows, H, max_positions);
+  return mpv_check_launch("mpv_gpt_embed_rows_w8_fwd");
 }

@@ -334,7 +334,7 @@ class DistributedGPT3_Caption(_GenCls):
     def generate(self, image, text, termination_id=None, batched=False, clips_per_search=32, do_sample=False, num_samples=1, temperature=1.0,
                  top_k=None, top_p=None, seed=0, kv_cache="per_sequence", repetition_penalty=None, no_repeat_ngram_size=0, min_new_tokens=0,
                  banned_token_ids=None, constrain_prompt=False, return_scores=False, best_of=False, length_penalty=1.0, query_features=None,
-                 beam_groups=1, diversity_penalty=0.0, rerank_by_logprob=False, decode_weights="bf16", **kw):
+                 beam_groups=1, diversity_penalty=0.0, rerank_by_logprob=False, decode_weights="bf16", mixed_prompts=False, **kw):
         """One beam search per sample (:790-809): prompt = text.input_ids[i, :mask.sum()-1], prefix = its query features.
         batched=True (not in the reference, default off): the clips are grouped by prompt length and every group is searched in
         lockstep, `clips_per_search` clips at a time (generation.beam_search_batched_loop: the decoder's weights are read once per
@@ -389,7 +389,14 @@ class DistributedGPT3_Caption(_GenCls):
         came from (zeros without groups).
         decode_weights="fp8" (every path; default "bf16"): the decode steps run on e4m3 codes of the decoder's weights, quantised on the
         device on first use (generation.DecodeWeightsQ8; the scoring of rerank_by_logprob stays on the bf16 weights).  It combines with
-        kv_cache, the constraints, the scores and the groups."""
+        kv_cache, the constraints, the scores and the groups.
+        mixed_prompts=True (batched=True with kv_cache="shared_prefix" only; default off): the clips are NOT grouped by prompt length.
+        They are chunked by clips_per_search in input order and every chunk is ONE lockstep search over its prompts, whatever their
+        lengths (generation.beam_search_batched_loop's mixed mode: a per-clip prefix length in the decode steps, the beams' token
+        table left-padded, every clip with the budget of positions its own length leaves).  Prompts that carry per-video text (a
+        title, a question) then cost one search per chunk instead of one per distinct length.  Same return value; a clip's rows are
+        those of the grouped call.  It combines with beam_groups, the constraints, rerank_by_logprob and decode_weights; do_sample,
+        kv_cache="per_sequence" and constrain_prompt=True are refused (DESIGN.md section 23 says why)."""
         Q, Hh = self.num_learnable_token, self.text_width
         G = int(beam_groups)
         from . import generation as _gen
@@ -402,6 +409,18 @@ class DistributedGPT3_Caption(_GenCls):
             raise ValueError("rerank_by_logprob needs batched=True without do_sample (sampled captions: best_of=True)")
         if G != 1:
             kw = dict(kw, beam_groups=G, diversity_penalty=diversity_penalty)      # absent keyword: the calls below are today's
+        if mixed_prompts:
+            if do_sample:
+                raise ValueError("mixed_prompts does not combine with do_sample: a sampled token is a function of its table column, "
+                                 "which the left padding would make depend on the longest prompt of the chunk")
+            if not batched:
+                raise ValueError("mixed_prompts needs batched=True: the per-clip search has one prompt per call")
+            if kv_cache != "shared_prefix":
+                raise ValueError(f'mixed_prompts needs kv_cache="shared_prefix" (got {kv_cache!r}): only the shared-prefix decode step '
+                                 "takes a prefix length per clip")
+            if constrain_prompt:
+                raise ValueError("mixed_prompts does not combine with constrain_prompt=True: the left padding of the token table would "
+                                 "count as prompt")
         Bv = image.shape[0] if query_features is None else query_features.shape[0] // Q
         was = self.training
         self.eval()
@@ -474,10 +493,16 @@ class DistributedGPT3_Caption(_GenCls):
                 lengths = (text.attention_mask.sum(-1) - 1).tolist()
                 res = [None] * n
                 groups_of = [None] * n
-                for pl, chunk in _prompt_length_chunks(lengths, clips_per_search):
+                if mixed_prompts:                                        # input order, no grouping: one search per chunk with its lengths
+                    per = int(clips_per_search)
+                    chunks = [list(range(c, min(c + per, n))) for c in range(0, n, per)]
+                    chunks = [([int(lengths[i]) for i in chunk], chunk) for chunk in chunks]
+                else:
+                    chunks = [(int(pl), chunk) for pl, chunk in _prompt_length_chunks(lengths, clips_per_search)]
+                for pl, chunk in chunks:
                     sel = torch.as_tensor(chunk, dtype=torch.long, device=qf.device)
                     outs = self.text_decoder.beam_search_batched(text.input_ids[sel], query_embeds=qf[sel].contiguous(),
-                                                                 stop_token=termination_id, prompt_length=int(pl), **kw)
+                                                                 stop_token=termination_id, prompt_length=pl, **kw)
                     for i, out in zip(sel.tolist(), outs):
                         res[i] = out.sequences.cpu()
                         groups_of[i] = getattr(out, "group", None)

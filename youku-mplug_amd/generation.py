@@ -13,7 +13,8 @@ search over a batch of clips (beam_search_batched_loop) keeps it on the device (
 csrc/beam_search.hip), and so does sampled generation in lockstep (sample_batched_loop: ops.sample_advance, csrc/sampling.hip; with
 return_scores ops.sample_score, csrc/sample_score.hip, records every drawn token's log-probability).  The lockstep loops can also keep
 the positions all sequences of a clip share (visual prefix + prompt) once per clip: SharedPrefixDecodeState (kv="shared_prefix";
-mpv_gpt_decode_step_shared, csrc/decode_shared_attention.hip).  decode_weights="fp8" (default "bf16") runs the steps of any of these
+mpv_gpt_decode_step_shared, csrc/decode_shared_attention.hip), and with it the lockstep beam search takes clips whose prompts differ in
+length in ONE search (prompt_length = a sequence: mpv_gpt_prefill_ragged, mpv_gpt_decode_step_shared_ragged).  decode_weights="fp8" (default "bf16") runs the steps of any of these
 loops on e4m3 codes of the decoder's weights (DecodeWeightsQ8; mpv_gpt_decode_step_q8 / _shared_q8, csrc/gemm_w8.hip).
 """
 from __future__ import annotations
@@ -246,7 +247,11 @@ class SharedPrefixDecodeState:
     call into the C ABI (mpv_gpt_decode_step_shared): its attention reads a clip's prefix once per head for all of the clip's
     sequences (mpv_attn_decode_shared_fwd).  A re-order gathers suffix rows only; the prefix is never copied or moved.
     Resident KV: nl * (G * P + (1 or 2) * batch * S) * 3H * 2 bytes (the twin exists once a re-order has moved rows) against
-    nl * 2 * batch * (P + S) * 3H * 2 of DecodeState."""
+    nl * 2 * batch * (P + S) * 3H * 2 of DecodeState.
+    prefill_fan_out(..., prompt_len=[G lengths]) makes the state ragged: the prompts are right-padded to one width, P = Q + the
+    longest prompt is the pitch of a clip's prefix rows, and a device array group_prefix_len = Q + prompt_len says how many of them
+    are real (mpv_gpt_prefill_ragged, mpv_gpt_decode_step_shared_ragged: clip g's sequences sit at position group_prefix_len[g] + t).
+    The pad rows behind a clip's prompt are written by the prefill and never read."""
 
     def __init__(self, gpt, batch: int, max_len: int, weights: str = "bf16"):
         _check_weight_mode(weights)
@@ -255,14 +260,18 @@ class SharedPrefixDecodeState:
         self.suffix = self.twin = None
         self.fan = self.P = self.S = 0
         self.t = 0                            # suffix rows cached so far (per sequence)
+        self.group_prefix_len = None          # ragged: int32 [G] on the device, Q + prompt_len
 
     @property
     def pos(self) -> int:
         return self.P + self.t
 
-    def prefill_fan_out(self, tokens: Optional[torch.Tensor], query_embeds: Optional[torch.Tensor], fan: int) -> torch.Tensor:
+    def prefill_fan_out(self, tokens: Optional[torch.Tensor], query_embeds: Optional[torch.Tensor], fan: int,
+                        prompt_len: Optional[torch.Tensor] = None) -> torch.Tensor:
         """tokens [G, n_tok] / query_embeds [G, Q, H], G = batch // fan: the prefill runs once per clip into the prefix cache and
-        nothing is copied.  -> logits [batch, V]: row j is clip j // fan's."""
+        nothing is copied.  -> logits [batch, V]: row j is clip j // fan's.
+        prompt_len (int64 [G], 1 <= prompt_len[g] <= n_tok; default None: every prompt is n_tok long, today's calls): clip g's prompt
+        is tokens[g, :prompt_len[g]], the rest of its row padding; the logits are those of each clip's own last prompt row."""
         assert self.prefix is None and fan >= 1 and self.batch % fan == 0, (self.batch, fan)
         G = self.batch // fan
         assert (tokens is None or tokens.shape[0] == G) and (query_embeds is None or query_embeds.shape[0] == G)
@@ -270,13 +279,44 @@ class SharedPrefixDecodeState:
         if not 0 < P < self.max_len:
             raise ValueError(f"a shared prefix of {P} positions leaves no room in max_len {self.max_len}")
         self.prefix = DecodeState(self.gpt, G, P, self.weights)
-        logits = self.prefix.step(tokens, query_embeds)
+        if prompt_len is None:
+            logits = self.prefix.step(tokens, query_embeds)
+        else:
+            logits = self._ragged_prefill(tokens, query_embeds, prompt_len)
         self.fan, self.P, self.S = fan, P, self.max_len - P
         st = self.prefix
         self.nl, self.H = st.nl, st.H
         self.suffix = torch.zeros((st.nl, self.batch * self.S, 3 * st.H), dtype=torch.bfloat16, device=st.cache.device)
         self._suffix_ptrs = st._ptrs(self.suffix)
         return logits.repeat_interleave(fan, dim=0)
+
+    def _ragged_prefill(self, tokens, query_embeds, prompt_len) -> torch.Tensor:
+        import ctypes as C
+        from . import _lib
+        st = self.prefix
+        G, H, dev = st.batch, st.H, st.cache.device
+        if tokens is None or tokens.dim() != 2:
+            raise ValueError("prefill_fan_out(prompt_len=...) needs the right-padded prompts: tokens [G, n_tok]")
+        L = tokens.shape[1]
+        lens = [int(x) for x in (prompt_len.tolist() if torch.is_tensor(prompt_len) else prompt_len)]   # host values: the caller's
+        if len(lens) != G or min(lens) < 1 or max(lens) > L:
+            raise ValueError(f"prompt_len must hold {G} lengths in [1, {L}] (got {lens})")
+        qf = None if query_embeds is None else query_embeds.reshape(-1, H).to(torch.bfloat16).contiguous()
+        Q = 0 if qf is None else qf.shape[0] // G
+        plen = torch.as_tensor(lens, dtype=torch.int64).to(dev)
+        self.group_prefix_len = (plen + Q).to(torch.int32)
+        last_row = (plen + (Q - 1)).contiguous()
+        ids = tokens.contiguous()
+        ws = ops.workspace(_lib.lib().mpv_gpt_decode_workspace_size(C.byref(st._w), G, Q + L), dev)
+        logits = torch.empty((G, st.V), dtype=torch.bfloat16, device=dev)
+        tail = (st._cache_ptrs, G, st.max_len, ops._p(qf), Q, ids.data_ptr(), L, last_row.data_ptr(), ws.data_ptr(), ws.numel(),
+                logits.data_ptr(), ops._stream())
+        if st.q8 is None:
+            ops.check(_lib.lib().mpv_gpt_prefill_ragged(C.byref(st._w), *tail), "mpv_gpt_prefill_ragged")
+        else:
+            ops.check(_lib.lib().mpv_gpt_prefill_ragged_q8(C.byref(st._w), C.byref(st._q8), *tail), "mpv_gpt_prefill_ragged_q8")
+        st.pos += Q + L
+        return logits
 
     def step(self, tokens: torch.Tensor, query_embeds: Optional[torch.Tensor] = None) -> torch.Tensor:
         """tokens [batch, 1] int64 -> the logits of the new position: [batch, V] bf16"""
@@ -301,7 +341,14 @@ class SharedPrefixDecodeState:
         logits = torch.empty((self.batch, st.V), dtype=torch.bfloat16, device=dev)
         tail = (st._cache_ptrs, self._suffix_ptrs, self.batch // self.fan, self.fan, self.P, self.S, self.t, tokens.data_ptr(), ws.data_ptr(),
                 ws.numel(), logits.data_ptr(), ops._stream())
-        if st.q8 is None:
+        if self.group_prefix_len is not None:        # prefix_stride = max_prefix_len = P: the pitch is the longest prefix
+            tail = tail[:5] + (self.group_prefix_len.data_ptr(),) + tail[4:]
+            if st.q8 is None:
+                ops.check(_lib.lib().mpv_gpt_decode_step_shared_ragged(C.byref(st._w), *tail), "mpv_gpt_decode_step_shared_ragged")
+            else:
+                ops.check(_lib.lib().mpv_gpt_decode_step_shared_ragged_q8(C.byref(st._w), C.byref(st._q8), *tail),
+                          "mpv_gpt_decode_step_shared_ragged_q8")
+        elif st.q8 is None:
             ops.check(_lib.lib().mpv_gpt_decode_step_shared(C.byref(st._w), *tail), "mpv_gpt_decode_step_shared")
         else:
             ops.check(_lib.lib().mpv_gpt_decode_step_shared_q8(C.byref(st._w), C.byref(st._q8), *tail), "mpv_gpt_decode_step_shared_q8")
@@ -538,7 +585,27 @@ def beam_search_batched_loop(cfg, make_state: Callable[[int, int], object], toke
     group), so both KV states work as they are.  The host finish runs per (clip, group): -> per clip a namespace (sequences [n, Lt],
     scores [n], group [n] int64), group 0's best r = num_return_gen // G rows first, then group 1's, ...; a group with fewer
     hypotheses yields fewer rows.  From the second group on the scores are penalised search scores, not model likelihoods.
-    num_return_gen must be a multiple of G with r <= K'."""
+    num_return_gen must be a multiple of G with r <= K'.
+    prompt_length = a sequence of B lengths (an int, or None: everything above, call for call): the MIXED mode, ONE lockstep search
+    over clips whose prompts differ in length; clip c's prompt is tokens[c, :prompt_length[c]].  make_state's state must take
+    prefill_fan_out(..., prompt_len=) (SharedPrefixDecodeState: it gets the prompts right-padded with the stop token, and the
+    lengths); a DecodeState does not.  The beams' token table is LEFT-padded with the stop token so that every prompt ends at column
+    P_max = max(prompt_length): topk_fn, advance / group_advance_fn and constrain_fn run unchanged with prompt_len_all = P_max and
+    pos = P_max + n, so a generated token sits n columns behind every clip's prompt.  Budget: clip c generates at most final_len -
+    prompt_length[c] positions, as a search over clips of its own length would; the loop runs until the shortest prompt's budget
+    ends.  The host knows at which step a longer prompt's budget ends: there it sets the clip's bs.done on the device (advance then
+    freezes it: tokens and scores stay, include/mpv.h mpv_beam_advance) after saving which of these clips were not done -- no host
+    read is added -- and the finish flushes the beams of exactly those, as it does for a clip the loop's end leaves unfinished.
+    All sequences step until then, the frozen ones as padding rows, so Q + P_max + final_len - P_min - 2 must be a row of the position
+    table (a ValueError before the first launch otherwise).
+    Row length: advance scores a hypothesis by value / row_len and tests worst >= best / cur_len, so the search depends on the
+    table's width.  The padded table is 2 * Lt wide (Lt = L + tokens_to_generate, the width of the uniform table; P_max - P_min +
+    final_len <= 2 * Lt always) and cur_len is 2 * (n + 1): both sides of every comparison are then exactly half of what the Lt-wide
+    table gives (a division by two is exact), so the clip's search is step for step the one of the uniform loop over clips of its
+    length, and the stored scores are doubled -- exactly -- at the finish.  2 * Lt must fit the advance kernels' 2048 columns.
+    Returned rows: left padding stripped, Lt wide like the uniform loop's (behind the generated tokens they hold what that loop's
+    rows hold: the rest of the clip's input row, then the stop token).  LogitsConstraints(include_prompt=True) is refused: the pad
+    columns would count as prompt."""
     _no_sample_scores(return_scores, "beam_search_batched_loop")
     B, dev, K = tokens.size(0), tokens.device, int(beam_size)
     G = int(beam_groups)
@@ -557,14 +624,49 @@ def beam_search_batched_loop(cfg, make_state: Callable[[int, int], object], toke
     else:
         advance, more, per_group = advance_fn, {}, num_return_gen
     constraints = _active_constraints(constraints, constrain_fn)
-    prompt_length = int(prompt_length) if prompt_length is not None else tokens.size(1)
+    lens = _mixed_prompt_lengths(prompt_length, B, tokens.size(1))                         # None: one prompt length, today's path
     stop_token = cfg.eod_id if stop_token is None else int(stop_token)
-    tokens, final_len, Q = _pad_for_generation(cfg, tokens, stop_token, prompt_length, query_embeds)
-    state = make_state(B * G * K, final_len + Q)
-    bs = BeamState(tokens if G == 1 else tokens.repeat_interleave(G, 0), K)                # pseudo-clip b * G + g: group g of clip b
-    total_prompt, total_final, m = prompt_length + Q, final_len + Q, 2 * K + (G - 1) * K
+    if lens is None:
+        prompt_length = int(prompt_length) if prompt_length is not None else tokens.size(1)
+        tokens, final_len, Q = _pad_for_generation(cfg, tokens, stop_token, prompt_length, query_embeds)
+        state = make_state(B * G * K, final_len + Q)
+        table, total_final, len_scale = tokens, final_len + Q, 1
+    else:
+        if constraints is not None and constraints.include_prompt:
+            raise ValueError("LogitsConstraints(include_prompt=True) does not combine with prompts of different lengths: the "
+                             "left padding of the token table would count as prompt")
+        prompt_length, shortest = max(lens), min(lens)
+        tokens, final_len, Q = _pad_for_generation(cfg, tokens, stop_token, prompt_length, query_embeds)
+        Lt, len_scale = tokens.size(1), 2
+        if len_scale * Lt > 2048:
+            raise ValueError(f"prompts of different lengths need a token table of {len_scale * Lt} columns; the advance kernels take 2048")
+        total_final = Q + prompt_length + final_len - shortest
+        if total_final - 2 >= cfg.max_position_embeddings:        # the last step's position of the longest prefix (frozen by then, but fed)
+            raise ValueError(f"prompts of {shortest} .. {prompt_length} tokens behind {Q} query slots step up to position {total_final - 2}; "
+                             f"the position table has {cfg.max_position_embeddings} rows")
+        state = make_state(B * G * K, total_final)
+        if not _takes_prompt_len(state):
+            raise ValueError('prompts of different lengths need a state with prefill_fan_out(..., prompt_len=): kv="shared_prefix" '
+                             f"(got a {type(state).__name__})")
+        lens_d = torch.as_tensor(lens, dtype=torch.long).to(dev)
+        left = prompt_length - lens_d                                                      # clip c's columns start at left[c]
+        src = torch.arange(len_scale * Lt, device=dev)[None] - left[:, None]
+        table = torch.where((src >= 0) & (src < Lt), tokens.gather(1, src.clamp(0, Lt - 1)), torch.full_like(src, stop_token))
+        prompts = torch.where(torch.arange(prompt_length, device=dev)[None] < lens_d[:, None], tokens[:, :prompt_length],
+                              torch.full_like(tokens[:, :prompt_length], stop_token))
+        # the step after which a clip's budget ends -> its pseudo-clips (the shortest prompts end with the loop itself)
+        ends = {}
+        for c, pl in enumerate(lens):
+            if pl != shortest:
+                ends.setdefault(final_len - pl, []).extend(range(c * G, (c + 1) * G))
+        ends = {k: torch.as_tensor(v, dtype=torch.long).to(dev) for k, v in ends.items()}
+        flush = torch.zeros(B * G, dtype=torch.int32, device=dev)                          # budget ended before the clip was done
+    bs = BeamState(table if G == 1 else table.repeat_interleave(G, 0), K)                  # pseudo-clip b * G + g: group g of clip b
+    total_prompt, m = prompt_length + Q, 2 * K + (G - 1) * K
     for n, context_length in enumerate(range(total_prompt, total_final)):
-        if n == 0:
+        if n == 0 and lens is not None:
+            logits = state.prefill_fan_out(prompts.contiguous(), query_embeds, G * K, prompt_len=lens)
+        elif n == 0:
             logits = state.prefill_fan_out(tokens[:, :prompt_length].contiguous(), query_embeds, G * K)
         else:
             logits = state.step(bs.next_tok.view(-1, 1))
@@ -572,11 +674,20 @@ def beam_search_batched_loop(cfg, make_state: Callable[[int, int], object], toke
             constrain_fn(logits, bs.tokens.view(B * G * K, -1), pos=context_length - Q, constraints=constraints, prompt_len_all=prompt_length,
                          eos_ids=[stop_token], ban_value=BAN_BEAM)
         vals, idxs = topk_fn(logits, m, bs.scores.view(-1))                                  # log_softmax + scores (:1790-1791)
-        advance(vals, idxs, bs, vocab=logits.size(-1), pos=context_length - Q, cur_len=n + 1, first=n == 0, stop_token=stop_token, **more)
+        advance(vals, idxs, bs, vocab=logits.size(-1), pos=context_length - Q, cur_len=len_scale * (n + 1), first=n == 0,
+                stop_token=stop_token, **more)
+        if lens is not None and n + 1 in ends:                                               # these clips' budgets end here: freeze them
+            flush[ends[n + 1]] = 1 - bs.done[ends[n + 1]]
+            bs.done[ends[n + 1]] = 1
         if bool(bs.done.all()):                                                              # the step's one host read
             break
         state.reorder(bs.src_row, shared_prefix=total_prompt)
     h = SimpleNamespace(**{k: getattr(bs, k).cpu() for k in BeamState.ARRAYS})              # one download
+    if lens is not None:                       # the uniform loop's view of every clip: its Lt columns, scores over Lt, budget flushes
+        flush, cols = flush.cpu(), (torch.arange(Lt)[None] + (prompt_length - torch.as_tensor(lens))[:, None]).repeat_interleave(G, 0)
+        h.tokens = h.tokens.gather(2, cols[:, None, :].expand(-1, K, -1))
+        h.hyp_tokens = h.hyp_tokens.gather(2, cols[:, None, :].expand(-1, K, -1))
+        h.hyp_score, h.worst, h.done = h.hyp_score * len_scale, h.worst * len_scale, h.done * (1 - flush)
     out = []
     for clip in range(B):
         ranked = [_ranked_hypotheses(h, clip * G + g, K)[:per_group] for g in range(G)]
@@ -586,6 +697,23 @@ def beam_search_batched_loop(cfg, make_state: Callable[[int, int], object], toke
             res.group = torch.tensor([g for g, rg in enumerate(ranked) for _ in rg], dtype=torch.int64)
         out.append(res)
     return out
+
+
+def _mixed_prompt_lengths(prompt_length, B, L):
+    """beam_search_batched_loop's prompt_length: None or an int -> None (one prompt length); a sequence or tensor of B lengths -> them
+    as a list of ints in [1, L]"""
+    if prompt_length is None or not hasattr(prompt_length, "__len__") or (torch.is_tensor(prompt_length) and prompt_length.dim() == 0):
+        return None
+    lens = [int(x) for x in (prompt_length.tolist() if torch.is_tensor(prompt_length) else prompt_length)]
+    if len(lens) != B or min(lens) < 1 or max(lens) > L:
+        raise ValueError(f"prompt_length must be an int or {B} lengths in [1, {L}] (got {lens})")
+    return lens
+
+
+def _takes_prompt_len(state) -> bool:
+    import inspect
+    fn = getattr(state, "prefill_fan_out", None)
+    return fn is not None and "prompt_len" in inspect.signature(fn).parameters
 
 
 def _ranked_hypotheses(h, b, K):
@@ -814,7 +942,8 @@ def install(gpt_cls):
 
     def beam_search_batched(self, tokens, query_embeds=None, beam_size=5, num_return_gen=1, stop_token=None, kv="per_sequence",
                             constraints=None, beam_groups=1, diversity_penalty=0.0, decode_weights="bf16", **kw):
-        """beam_search for tokens [B, L] / query_embeds [B, Q, H] with one prompt length, B clips in lockstep -> a list of B results;
+        """beam_search for tokens [B, L] / query_embeds [B, Q, H] with one prompt length (prompt_length an int) or one per clip
+        (a sequence of B lengths: beam_search_batched_loop's mixed mode, kv="shared_prefix" only), B clips in lockstep -> a list of B results;
         kv="shared_prefix" keeps the visual prefix and the prompt once per clip (SharedPrefixDecodeState); constraints: a
         LogitsConstraints, applied on the device every step; beam_groups = G > 1: diverse beam search, G groups of beam_size beams
         each with diversity_penalty between them (beam_search_batched_loop; ops.beam_advance_groups); decode_weights="fp8": the steps

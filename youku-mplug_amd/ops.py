@@ -356,6 +356,23 @@ def attn_decode_shared_fwd(q, k, v, pk, pv, o, lay: AttnLayout, prefix_lay: Tupl
     stride of q and o is not used) against the prefix_len-row prefix of their group s // group_size (pk/pv strided (group, head,
     row) by prefix_lay = (k strides, v strides)) and their own own_len rows of k/v: one softmax over both key sets.
     include/mpv.h: mpv_attn_decode_shared_fwd."""
+    return _attn_decode_shared(q, k, v, pk, pv, o, lay, prefix_lay, n_seq, group_size, heads, prefix_len, own_len, hd, scale, None, False)
+
+
+def attn_decode_shared_ragged_fwd(q, k, v, pk, pv, o, lay: AttnLayout, prefix_lay, n_seq, group_size, heads, prefix_len, group_prefix_len,
+                                  own_len, hd, *, scale=1.0):
+    """attn_decode_shared_fwd with a prefix length per group: group_prefix_len int32 [n_groups] on the device, every entry in
+    [1, prefix_len] (the caller's promise; prefix_len is the upper bound).  include/mpv.h: mpv_attn_decode_shared_ragged_fwd."""
+    if group_prefix_len is not None:
+        _need_cuda(group_prefix_len)
+        n_groups = (n_seq + group_size - 1) // max(group_size, 1)
+        if group_prefix_len.dtype != torch.int32 or not group_prefix_len.is_contiguous() or group_prefix_len.numel() < n_groups:
+            raise ValueError(f"group_prefix_len must be a contiguous int32 tensor of {n_groups} lengths")
+    return _attn_decode_shared(q, k, v, pk, pv, o, lay, prefix_lay, n_seq, group_size, heads, prefix_len, own_len, hd, scale,
+                               group_prefix_len, True)
+
+
+def _attn_decode_shared(q, k, v, pk, pv, o, lay, prefix_lay, n_seq, group_size, heads, prefix_len, own_len, hd, scale, glen, ragged):
     _need_cuda(q, k, v, o, pk, pv)
     d = _lib.AttnDecodeSharedDesc()
     d.q, d.k, d.v, d.o, d.pk, d.pv = q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), pk.data_ptr(), pv.data_ptr()
@@ -366,7 +383,10 @@ def attn_decode_shared_fwd(q, k, v, pk, pv, o, lay: AttnLayout, prefix_lay: Tupl
     (d.pk_gs, d.pk_hs, d.pk_rs), (d.pv_gs, d.pv_hs, d.pv_rs) = prefix_lay
     d.n_seq, d.group_size, d.n_groups = n_seq, group_size, (n_seq + group_size - 1) // max(group_size, 1)
     d.heads, d.prefix_len, d.own_len, d.head_dim, d.scale = heads, prefix_len, own_len, hd, scale
-    check(_lib.lib().mpv_attn_decode_shared_fwd(C.byref(d), _stream()), "mpv_attn_decode_shared_fwd")
+    if ragged:
+        check(_lib.lib().mpv_attn_decode_shared_ragged_fwd(C.byref(d), _p(glen), _stream()), "mpv_attn_decode_shared_ragged_fwd")
+    else:
+        check(_lib.lib().mpv_attn_decode_shared_fwd(C.byref(d), _stream()), "mpv_attn_decode_shared_fwd")
     return o
 
 
@@ -679,6 +699,20 @@ def quantize_rows_e4m3(w: torch.Tensor, N: Optional[int] = None, K: Optional[int
     scale = torch.empty((N,), dtype=torch.float32, device=w.device)
     check(_lib.lib().mpv_quantize_rows_e4m3(w.data_ptr(), N, K, ldw, codes.data_ptr(), scale.data_ptr(), _stream()), "mpv_quantize_rows_e4m3")
     return codes, scale
+
+
+def gpt_embed_rows_w8_fwd(ids, pos, pos_host, codes, scale, wpe, rows, H):
+    """gpt_embed_rows_fwd with the token rows read as deq(code) * scale from the tied embedding's codes (uint8 [vocab, H]) and scales
+    (fp32 [vocab]); include/mpv.h: mpv_gpt_embed_rows_w8_fwd.  pos_host is checked against wpe as there."""
+    if len(pos_host) != rows or min(pos_host) < 0:
+        raise _lib.MpvError(f"{len(pos_host)} host positions (smallest {min(pos_host, default=0)}) for {rows} rows")
+    if max(pos_host) >= wpe.shape[0]:
+        raise _lib.MpvError(f"sequence of {max(pos_host) + 1} positions exceeds max_position_embeddings = {wpe.shape[0]}")
+    _need_cuda(ids, pos, codes, scale, wpe)
+    out = torch.empty((rows, H), dtype=torch.bfloat16, device=wpe.device)
+    check(_lib.lib().mpv_gpt_embed_rows_w8_fwd(ids.data_ptr(), pos.data_ptr(), codes.data_ptr(), scale.data_ptr(), wpe.data_ptr(),
+                                               out.data_ptr(), rows, H, wpe.shape[0], _stream()), "mpv_gpt_embed_rows_w8_fwd")
+    return out
 
 
 def _gemm_w8(entry, a, codes, scale, M, N, K, out, lda, ldw, ldc, bias, act, residual, ldr, cmap, out_rows, other, tail=()):
