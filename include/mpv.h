@@ -726,6 +726,23 @@ typedef struct mpv_sample_advance_desc {
   float temperature, top_p;
 } mpv_sample_advance_desc;
 int mpv_sample_advance(const mpv_sample_advance_desc* d, mpv_stream_t stream);
+/* The same step for rows whose prompts differ in length (one lockstep loop over prompts of different lengths, the table
+ * left-aligned: row r's prompt sits at columns [0, prompt_len[r])).  The descriptor is the same; d->pos is the generation STEP
+ * t >= 0, not a column, and row r works on its own column c_r = clamp(prompt_len[r], 0, row_len) + t, a per-workgroup value that
+ * the row's workgroup reads once.  One kernel body serves both entries.
+ * Row r with c_r < row_len is started (there is no teacher forcing here: c_r lies behind the prompt): it draws with the counter
+ *   (uint64(c_r) << 32) | uint32(stream_id[r]), writes tokens[r][c_r] and next_tok[r]; termination mode 2 looks at tokens[r][c_r - 1]
+ *   (c_r == 0 has no previous token).
+ * Row r with c_r >= row_len is FROZEN (its budget has ended, or its length was bad): no logit is read, no token is written,
+ *   done[r] = 1 (the row counts in n_done), next_tok[r] = tokens[r][row_len - 1], and the optional outputs get token 0, kept 0, mass 0.
+ * Invariants:
+ *   a row's result depends on its own logits, tokens[r][c_r - 1], done[r], prompt_len[r], t and the scalars only -- neither on
+ *     `rows` nor on the row's place in the launch;
+ *   a row of a ragged launch equals, bit for bit, mpv_sample_advance run on that row alone at pos = c_r (with a prompt_len <= c_r);
+ *     with every prompt_len equal to p the launch equals mpv_sample_advance at pos = p + t, n_done included;
+ *   a bad prompt_len[r] (negative: taken as 0; beyond row_len: frozen) touches only row r.
+ * Refused: what mpv_sample_advance refuses (prompt_len must not be NULL), and t outside [0, row_len). */
+int mpv_sample_advance_ragged(const mpv_sample_advance_desc* d, mpv_stream_t stream);
 /* ------------------------------------------------------------------------------------------
  * Generation constraints in lockstep (generation.LogitsConstraints): ONE launch edits one step's logits in place, before
  * mpv_sample_advance or mpv_logprob_topk reads them, from the loop's own device token table -- the CTRL repetition penalty, the
@@ -772,6 +789,17 @@ typedef struct mpv_logits_constrain_desc {
   float penalty, ban_value;
 } mpv_logits_constrain_desc;
 int mpv_logits_constrain(const mpv_logits_constrain_desc* d, mpv_stream_t stream);
+/* The same edit for rows whose prompts differ in length (the left-aligned table of mpv_sample_advance_ragged).  The descriptor is
+ * the same; d->pos is the generation STEP t >= 0, prompt_len must not be NULL (prompt_len_all is ignored), and row r works on its
+ * own column c_r = clamp(prompt_len[r], 0, row_len) + t, a per-workgroup value read once.  One kernel body serves both entries.
+ * Row r with c_r < row_len: the history is tokens[r][start : c_r], start = include_prompt ? 0 : prompt_len[r], and g = t tokens
+ *   have been generated.  The table has no padding, so include_prompt = 1 sees exactly the row's prompt.
+ * Row r with c_r >= row_len is frozen: its logits stay untouched, bit for bit.
+ * Invariants: a row's result depends on its own logits, its history, prompt_len[r], t and the scalars only -- neither on `rows`
+ *   nor on the row's place in the launch; a row of a ragged launch equals, bit for bit, mpv_logits_constrain run on that row alone
+ *   at pos = c_r with that prompt_len; a bad prompt_len[r] (negative: 0; beyond row_len: frozen) touches only row r.
+ * Refused: what mpv_logits_constrain refuses, a NULL prompt_len, and t outside [0, row_len). */
+int mpv_logits_constrain_ragged(const mpv_logits_constrain_desc* d, mpv_stream_t stream);
 /* ------------------------------------------------------------------------------------------
  * Sequence scores of sampled generation in lockstep (generation.SampleScores): ONE launch, right after mpv_sample_advance, records
  * the model's log-probability of the token that call wrote into column `pos` -- log_softmax of the RAW logits the sampler read
@@ -807,6 +835,15 @@ typedef struct mpv_sample_score_desc {
   int rows, vocab, row_len, pos;
 } mpv_sample_score_desc;
 int mpv_sample_score(const mpv_sample_score_desc* d, mpv_stream_t stream);
+/* The same record for rows whose prompts differ in length, right after mpv_sample_advance_ragged.  The descriptor is the same;
+ * d->pos is the generation STEP t >= 0 and row r scores the token at its own column c_r = clamp(prompt_len[r], 0, row_len) + t
+ * (a per-workgroup value read once) into token_logprob[r][c_r].  One kernel body serves both entries.
+ * A row with c_r >= row_len (frozen) or live[r] == 0 (dead) reads nothing else and writes nothing: logits and state stay bit for bit.
+ * Invariants: a row's result depends on its own logits, its token, its state, prompt_len[r] and t only -- neither on `rows` nor on
+ *   the row's place in the launch; a row of a ragged launch equals, bit for bit, mpv_sample_score run on that row alone at
+ *   pos = c_r; a bad prompt_len[r] (negative: 0; beyond row_len: frozen) touches only row r.
+ * Refused: what mpv_sample_score refuses (prompt_len must not be NULL), and t outside [0, row_len). */
+int mpv_sample_score_ragged(const mpv_sample_score_desc* d, mpv_stream_t stream);
 /* ------------------------------------------------------------------------------------------
  * Device-side video input transform (configs' video_pretrain/train/test transforms,
  * dataset/__init__.py:60-85): the decoder's uint8 clip [T][H][W][3] -> crop (i, j, h, w) ->

@@ -218,6 +218,9 @@ _SIGS = {
     "mpv_sample_advance": (c_int, [C.POINTER(SampleAdvanceDesc), c_void_p]),
     "mpv_logits_constrain": (c_int, [C.POINTER(LogitsConstrainDesc), c_void_p]),
     "mpv_sample_score": (c_int, [C.POINTER(SampleScoreDesc), c_void_p]),
+    "mpv_sample_advance_ragged": (c_int, [C.POINTER(SampleAdvanceDesc), c_void_p]),
+    "mpv_logits_constrain_ragged": (c_int, [C.POINTER(LogitsConstrainDesc), c_void_p]),
+    "mpv_sample_score_ragged": (c_int, [C.POINTER(SampleScoreDesc), c_void_p]),
     "mpv_soft_target_ce": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     "mpv_maxsim_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p]),
     "mpv_maxsim_route": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p]),

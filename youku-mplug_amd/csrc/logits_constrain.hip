@@ -13,27 +13,48 @@
 //      it.  The threads of the listed ids store ban_value too: an id that is also in the history gets the same bits from both.
 // No address is read by one thread and written by another, and no address receives two different values: the result does not
 // depend on thread timing.  No scratch, no atomics, no floating-point reduction.
+//
+// The ragged entry (mpv_logits_constrain_ragged) is the same kernel body with the token column a per-workgroup value,
+// c_r = clamp(prompt_len[r], 0, row_len) + step; a row whose column lies behind the table is frozen and left as it is.
 #include "mpv_common.h"
 #include "../../include/mpv.h"
 
 #include <math.h>
 #include <string.h>
+#include <type_traits>
 
 namespace {
 
 constexpr int LC_THREADS = 1024, LC_MAX_ROW = 2048, LC_MAX_EOS = 8, LC_MAX_BANNED = 1024, LC_MAX_NGRAM = 8, LC_MAX_VOCAB = 65536;
 
-__global__ __launch_bounds__(LC_THREADS) void logits_constrain_kernel(mpv_logits_constrain_desc d, unsigned ban_bits) {
+// The kernel is a template over an entry tag.  The uniform entry's tag carries the kernel's name of old, so that its symbol still
+// contains it (the resource checks and profiles look the uniform kernel up by that name) and the ragged one's does not.
+struct logits_constrain_kernel {};    // mpv_logits_constrain: every row at column d.pos
+struct lc_ragged_entry {};            // mpv_logits_constrain_ragged: row r at its own column
+
+template <class Entry>
+__global__ __launch_bounds__(LC_THREADS) void lc_rows(mpv_logits_constrain_desc d, unsigned ban_bits) {
+  constexpr bool RAGGED = std::is_same<Entry, lc_ragged_entry>::value;
   __shared__ long long hist[LC_MAX_ROW];                       // 16 KiB
   __shared__ long long listed[LC_MAX_BANNED + LC_MAX_EOS];     // 8 KiB
   __shared__ unsigned char hit[LC_MAX_ROW];                    // 2 KiB
   const int tid = threadIdx.x;
   const long long row = blockIdx.x;
-  const long long pl = d.prompt_len ? d.prompt_len[row] : d.prompt_len_all;
-  if (pl > d.pos) return;                                      // block-uniform: a teacher-forced row stays as it is
+  long long pl;
+  int pos;
+  if (RAGGED) {                                                // the row's own column: its prompt length + the step d.pos
+    pl = d.prompt_len[row];
+    pl = pl < 0 ? 0 : pl > d.row_len ? d.row_len : pl;
+    if (pl + d.pos >= d.row_len) return;                       // block-uniform: a frozen row stays as it is
+    pos = (int)pl + d.pos;
+  } else {
+    pl = d.prompt_len ? d.prompt_len[row] : d.prompt_len_all;
+    if (pl > d.pos) return;                                    // block-uniform: a teacher-forced row stays as it is
+    pos = d.pos;
+  }
   const int start = d.include_prompt || pl < 0 ? 0 : (int)pl;  // 0 <= start <= pos < row_len <= 2048
-  const int m = d.pos - start, n = d.ngram, vocab = d.vocab;
-  const int n_list = d.n_banned + ((long long)d.pos - pl < d.min_new_tokens ? d.n_eos : 0);
+  const int m = pos - start, n = d.ngram, vocab = d.vocab;
+  const int n_list = d.n_banned + ((long long)pos - pl < d.min_new_tokens ? d.n_eos : 0);
 
   // ---- 1. the history and the id lists
   const int64_t* trow = d.tokens + row * d.row_len + start;
@@ -89,28 +110,41 @@ unsigned lc_bf16_bits(float v) {
 
 }  // namespace
 
-extern "C" int mpv_logits_constrain(const mpv_logits_constrain_desc* d, hipStream_t stream) {
-  MPV_REQUIRE(d, MPV_E_ARG, "mpv_logits_constrain: null descriptor");
-  MPV_REQUIRE(d->logits && d->tokens, MPV_E_ARG, "mpv_logits_constrain: null logits or tokens");
-  MPV_REQUIRE(d->rows >= 1, MPV_E_SHAPE, "mpv_logits_constrain: rows (%d) must be positive", d->rows);
-  MPV_REQUIRE(d->vocab >= 8 && d->vocab <= LC_MAX_VOCAB && d->vocab % 8 == 0, MPV_E_SHAPE,
-              "mpv_logits_constrain: vocab (%d) must be a multiple of 8 in [8, %d]", d->vocab, LC_MAX_VOCAB);
-  MPV_REQUIRE(d->ld >= d->vocab && d->ld % 8 == 0, MPV_E_SHAPE, "mpv_logits_constrain: ld (%lld) must be a multiple of 8 and at least vocab (%d)",
+// the body of both entries; `who` names the entry in the messages
+static int launch_logits_constrain(const mpv_logits_constrain_desc* d, bool ragged, const char* who, hipStream_t stream) {
+  MPV_REQUIRE(d, MPV_E_ARG, "%s: null descriptor", who);
+  MPV_REQUIRE(d->logits && d->tokens, MPV_E_ARG, "%s: null logits or tokens", who);
+  MPV_REQUIRE(!ragged || d->prompt_len, MPV_E_ARG, "%s: null prompt_len", who);
+  MPV_REQUIRE(d->rows >= 1, MPV_E_SHAPE, "%s: rows (%d) must be positive", who, d->rows);
+  MPV_REQUIRE(d->vocab >= 8 && d->vocab <= LC_MAX_VOCAB && d->vocab % 8 == 0, MPV_E_SHAPE, "%s: vocab (%d) must be a multiple of 8 in [8, %d]", who,
+              d->vocab, LC_MAX_VOCAB);
+  MPV_REQUIRE(d->ld >= d->vocab && d->ld % 8 == 0, MPV_E_SHAPE, "%s: ld (%lld) must be a multiple of 8 and at least vocab (%d)", who,
               (long long)d->ld, d->vocab);
-  MPV_REQUIRE(((uintptr_t)d->logits & 15) == 0, MPV_E_ALIGN, "mpv_logits_constrain: logits must be 16-byte aligned");
-  MPV_REQUIRE(d->row_len >= 1 && d->row_len <= LC_MAX_ROW, MPV_E_SHAPE, "mpv_logits_constrain: row_len (%d) must be in [1, %d]", d->row_len, LC_MAX_ROW);
-  MPV_REQUIRE(d->pos >= 0 && d->pos < d->row_len, MPV_E_SHAPE, "mpv_logits_constrain: pos (%d) must be in [0, row_len = %d)", d->pos, d->row_len);
-  MPV_REQUIRE(isfinite(d->penalty) && d->penalty > 0.f, MPV_E_ARG, "mpv_logits_constrain: penalty (%g) must be finite and positive", (double)d->penalty);
-  MPV_REQUIRE(d->ngram >= 0 && d->ngram <= LC_MAX_NGRAM, MPV_E_ARG, "mpv_logits_constrain: ngram (%d) must be in [0, %d]", d->ngram, LC_MAX_NGRAM);
-  MPV_REQUIRE(d->min_new_tokens >= 0, MPV_E_ARG, "mpv_logits_constrain: min_new_tokens (%d) must not be negative", d->min_new_tokens);
-  MPV_REQUIRE(d->include_prompt == 0 || d->include_prompt == 1, MPV_E_ARG, "mpv_logits_constrain: include_prompt (%d) must be 0 or 1", d->include_prompt);
+  MPV_REQUIRE(((uintptr_t)d->logits & 15) == 0, MPV_E_ALIGN, "%s: logits must be 16-byte aligned", who);
+  MPV_REQUIRE(d->row_len >= 1 && d->row_len <= LC_MAX_ROW, MPV_E_SHAPE, "%s: row_len (%d) must be in [1, %d]", who, d->row_len, LC_MAX_ROW);
+  MPV_REQUIRE(d->pos >= 0 && d->pos < d->row_len, MPV_E_SHAPE, "%s: %s (%d) must be in [0, row_len = %d)", who, ragged ? "step" : "pos", d->pos,
+              d->row_len);
+  MPV_REQUIRE(isfinite(d->penalty) && d->penalty > 0.f, MPV_E_ARG, "%s: penalty (%g) must be finite and positive", who, (double)d->penalty);
+  MPV_REQUIRE(d->ngram >= 0 && d->ngram <= LC_MAX_NGRAM, MPV_E_ARG, "%s: ngram (%d) must be in [0, %d]", who, d->ngram, LC_MAX_NGRAM);
+  MPV_REQUIRE(d->min_new_tokens >= 0, MPV_E_ARG, "%s: min_new_tokens (%d) must not be negative", who, d->min_new_tokens);
+  MPV_REQUIRE(d->include_prompt == 0 || d->include_prompt == 1, MPV_E_ARG, "%s: include_prompt (%d) must be 0 or 1", who, d->include_prompt);
   MPV_REQUIRE(d->n_eos >= 0 && d->n_eos <= LC_MAX_EOS && (d->n_eos == 0 || d->eos_ids), MPV_E_ARG,
-              "mpv_logits_constrain: n_eos (%d) must be in [0, %d], with an array when positive", d->n_eos, LC_MAX_EOS);
+              "%s: n_eos (%d) must be in [0, %d], with an array when positive", who, d->n_eos, LC_MAX_EOS);
   MPV_REQUIRE(d->n_banned >= 0 && d->n_banned <= LC_MAX_BANNED && (d->n_banned == 0 || d->banned_ids), MPV_E_ARG,
-              "mpv_logits_constrain: n_banned (%d) must be in [0, %d], with an array when positive", d->n_banned, LC_MAX_BANNED);
-  MPV_REQUIRE(!isnan(d->ban_value) && d->ban_value < 0.f, MPV_E_ARG, "mpv_logits_constrain: ban_value (%g) must be -inf or a finite negative number",
+              "%s: n_banned (%d) must be in [0, %d], with an array when positive", who, d->n_banned, LC_MAX_BANNED);
+  MPV_REQUIRE(!isnan(d->ban_value) && d->ban_value < 0.f, MPV_E_ARG, "%s: ban_value (%g) must be -inf or a finite negative number", who,
               (double)d->ban_value);
   if (d->penalty == 1.f && d->ngram == 0 && d->n_banned == 0 && (d->min_new_tokens == 0 || d->n_eos == 0)) return MPV_OK;      // everything off
-  hipLaunchKernelGGL(logits_constrain_kernel, dim3((unsigned)d->rows), dim3(LC_THREADS), 0, stream, *d, lc_bf16_bits(d->ban_value));
-  return mpv_check_launch("mpv_logits_constrain");
+  const unsigned ban_bits = lc_bf16_bits(d->ban_value);
+  if (ragged) hipLaunchKernelGGL(lc_rows<lc_ragged_entry>, dim3((unsigned)d->rows), dim3(LC_THREADS), 0, stream, *d, ban_bits);
+  else hipLaunchKernelGGL(lc_rows<logits_constrain_kernel>, dim3((unsigned)d->rows), dim3(LC_THREADS), 0, stream, *d, ban_bits);
+  return mpv_check_launch(who);
+}
+
+extern "C" int mpv_logits_constrain(const mpv_logits_constrain_desc* d, hipStream_t stream) {
+  return launch_logits_constrain(d, false, "mpv_logits_constrain", stream);
+}
+
+extern "C" int mpv_logits_constrain_ragged(const mpv_logits_constrain_desc* d, hipStream_t stream) {
+  return launch_logits_constrain(d, true, "mpv_logits_constrain_ragged", stream);
 }

@@ -12,10 +12,14 @@
 //      wave partials through LDS, added in wave order by thread 0.
 // Thread 0 then reads the token and its logit (one 2-byte load), forms lp = x_t - (m + log S) and does the bookkeeping.  Every sum runs
 // in a fixed order and there is no atomic: the outputs are bit-reproducible.  No scratch.
+//
+// The ragged entry (mpv_sample_score_ragged) is the same kernel body with the token column a per-workgroup value,
+// c_r = clamp(prompt_len[r], 0, row_len) + step; a row whose column lies behind the table is frozen and returns like a dead one.
 #include "mpv_common.h"
 #include "../../include/mpv.h"
 
 #include <math.h>
+#include <type_traits>
 
 namespace {
 
@@ -23,11 +27,26 @@ constexpr int SS_THREADS = 1024, SS_WAVES = SS_THREADS / 64, SS_SLOTS = 8;
 constexpr int SS_MAX_VOCAB = SS_THREADS * SS_SLOTS * 8, SS_MAX_ROW = 2048;
 constexpr unsigned SS_NEG_INF_PAIR = 0xff80ff80u;        // two bf16 -inf: what a vector slot past the vocabulary holds
 
-__global__ __launch_bounds__(SS_THREADS) void sample_score_kernel(mpv_sample_score_desc d) {
+// The kernel is a template over an entry tag.  The uniform entry's tag carries the kernel's name of old, so that its symbol still
+// contains it (the resource checks and profiles look the uniform kernel up by that name) and the ragged one's does not.
+struct sample_score_kernel {};        // mpv_sample_score: every row at column d.pos
+struct ss_ragged_entry {};            // mpv_sample_score_ragged: row r at its own column
+
+template <class Entry>
+__global__ __launch_bounds__(SS_THREADS) void ss_rows(mpv_sample_score_desc d) {
+  constexpr bool RAGGED = std::is_same<Entry, ss_ragged_entry>::value;
   __shared__ float wave_m[SS_WAVES], wave_s[SS_WAVES];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long long row = blockIdx.x;
-  if (d.prompt_len[row] > d.pos || d.live[row] == 0) return;   // block-uniform (live is rewritten behind the last barrier only)
+  int pos = d.pos;
+  if (RAGGED) {                                                // the row's own column: its prompt length + the step d.pos
+    long long pl = d.prompt_len[row];
+    pl = pl < 0 ? 0 : pl > d.row_len ? d.row_len : pl;
+    if (pl + d.pos >= d.row_len || d.live[row] == 0) return;   // block-uniform: frozen, or scored to its end already
+    pos = (int)pl + d.pos;
+  } else if (d.prompt_len[row] > d.pos || d.live[row] == 0) {
+    return;                                                    // block-uniform (live is rewritten behind the last barrier only)
+  }
   const int vocab = d.vocab;
   const float ninf = -INFINITY;
 
@@ -77,7 +96,7 @@ __global__ __launch_bounds__(SS_THREADS) void sample_score_kernel(mpv_sample_sco
     float S = 0.f;
 #pragma unroll
     for (int w = 0; w < SS_WAVES; ++w) S += wave_s[w];
-    const long long at = row * d.row_len + d.pos;
+    const long long at = row * d.row_len + pos;
     const long long t = d.tokens[at];
     float lp = __builtin_nanf("");                       // a token outside [0, vocab): misuse, made loud
     if (t >= 0 && t < vocab) {
@@ -93,18 +112,29 @@ __global__ __launch_bounds__(SS_THREADS) void sample_score_kernel(mpv_sample_sco
 
 }  // namespace
 
-extern "C" int mpv_sample_score(const mpv_sample_score_desc* d, hipStream_t stream) {
-  MPV_REQUIRE(d, MPV_E_ARG, "mpv_sample_score: null descriptor");
+// the body of both entries; `who` names the entry in the messages
+static int launch_sample_score(const mpv_sample_score_desc* d, bool ragged, const char* who, hipStream_t stream) {
+  MPV_REQUIRE(d, MPV_E_ARG, "%s: null descriptor", who);
   MPV_REQUIRE(d->logits && d->tokens && d->prompt_len && d->done && d->live && d->token_logprob && d->sum_logprob && d->count, MPV_E_ARG,
-              "mpv_sample_score: null pointer");
-  MPV_REQUIRE(d->rows >= 1, MPV_E_SHAPE, "mpv_sample_score: rows (%d) must be positive", d->rows);
-  MPV_REQUIRE(d->vocab >= 8 && d->vocab <= SS_MAX_VOCAB && d->vocab % 8 == 0, MPV_E_SHAPE,
-              "mpv_sample_score: vocab (%d) must be a multiple of 8 in [8, %d]", d->vocab, SS_MAX_VOCAB);
-  MPV_REQUIRE(d->ld >= d->vocab && d->ld % 8 == 0, MPV_E_SHAPE, "mpv_sample_score: ld (%lld) must be a multiple of 8 and at least vocab (%d)",
+              "%s: null pointer", who);
+  MPV_REQUIRE(d->rows >= 1, MPV_E_SHAPE, "%s: rows (%d) must be positive", who, d->rows);
+  MPV_REQUIRE(d->vocab >= 8 && d->vocab <= SS_MAX_VOCAB && d->vocab % 8 == 0, MPV_E_SHAPE, "%s: vocab (%d) must be a multiple of 8 in [8, %d]", who,
+              d->vocab, SS_MAX_VOCAB);
+  MPV_REQUIRE(d->ld >= d->vocab && d->ld % 8 == 0, MPV_E_SHAPE, "%s: ld (%lld) must be a multiple of 8 and at least vocab (%d)", who,
               (long long)d->ld, d->vocab);
-  MPV_REQUIRE(((uintptr_t)d->logits & 15) == 0, MPV_E_ALIGN, "mpv_sample_score: logits must be 16-byte aligned");
-  MPV_REQUIRE(d->row_len >= 1 && d->row_len <= SS_MAX_ROW, MPV_E_SHAPE, "mpv_sample_score: row_len (%d) must be in [1, %d]", d->row_len, SS_MAX_ROW);
-  MPV_REQUIRE(d->pos >= 0 && d->pos < d->row_len, MPV_E_SHAPE, "mpv_sample_score: pos (%d) must be in [0, row_len = %d)", d->pos, d->row_len);
-  hipLaunchKernelGGL(sample_score_kernel, dim3((unsigned)d->rows), dim3(SS_THREADS), 0, stream, *d);
-  return mpv_check_launch("mpv_sample_score");
+  MPV_REQUIRE(((uintptr_t)d->logits & 15) == 0, MPV_E_ALIGN, "%s: logits must be 16-byte aligned", who);
+  MPV_REQUIRE(d->row_len >= 1 && d->row_len <= SS_MAX_ROW, MPV_E_SHAPE, "%s: row_len (%d) must be in [1, %d]", who, d->row_len, SS_MAX_ROW);
+  MPV_REQUIRE(d->pos >= 0 && d->pos < d->row_len, MPV_E_SHAPE, "%s: %s (%d) must be in [0, row_len = %d)", who, ragged ? "step" : "pos", d->pos,
+              d->row_len);
+  if (ragged) hipLaunchKernelGGL(ss_rows<ss_ragged_entry>, dim3((unsigned)d->rows), dim3(SS_THREADS), 0, stream, *d);
+  else hipLaunchKernelGGL(ss_rows<sample_score_kernel>, dim3((unsigned)d->rows), dim3(SS_THREADS), 0, stream, *d);
+  return mpv_check_launch(who);
+}
+
+extern "C" int mpv_sample_score(const mpv_sample_score_desc* d, hipStream_t stream) {
+  return launch_sample_score(d, false, "mpv_sample_score", stream);
+}
+
+extern "C" int mpv_sample_score_ragged(const mpv_sample_score_desc* d, hipStream_t stream) {
+  return launch_sample_score(d, true, "mpv_sample_score_ragged", stream);
 }

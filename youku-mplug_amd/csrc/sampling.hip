@@ -18,11 +18,18 @@
 // Every sum runs in a fixed order (lane-local in element order, xor butterfly / Hillis-Steele across the lanes of a wave, wave
 // partials through LDS in wave order); there is no floating-point atomic anywhere, so the outputs are bit-reproducible.  The one
 // atomic is the integer add that counts the done rows.
+//
+// The ragged entry (mpv_sample_advance_ragged: prompts of different lengths in one lockstep loop) is the same kernel body with the
+// token column a per-workgroup value, c_r = clamp(prompt_len[r], 0, row_len) + step, read once by the row's workgroup; a row whose
+// column lies behind the table is frozen and leaves before the first barrier.  The column is a template parameter's business: the
+// uniform instantiation (sa_rows<sample_advance_kernel>) reads d.pos as before and contains nothing of the ragged one
+// (sa_rows<sa_ragged_entry>).
 #include "mpv_common.h"
 #include "../../include/mpv.h"
 
 #include <limits.h>
 #include <math.h>
+#include <type_traits>
 
 namespace {
 
@@ -136,7 +143,14 @@ __device__ __forceinline__ void sa_seg_scan_f(const float* x, float* ex, float* 
   in[2 * lane + 1] = incl;
 }
 
-__global__ __launch_bounds__(SA_THREADS) void sample_advance_kernel(mpv_sample_advance_desc d, float exp_scale) {
+// The kernel is a template over an entry tag.  The uniform entry's tag carries the kernel's name of old, so that its symbol still
+// contains it (the resource checks and profiles look the uniform kernel up by that name) and the ragged one's does not.
+struct sample_advance_kernel {};      // mpv_sample_advance: every row at column d.pos
+struct sa_ragged_entry {};            // mpv_sample_advance_ragged: row r at its own column
+
+template <class Entry>
+__global__ __launch_bounds__(SA_THREADS) void sa_rows(mpv_sample_advance_desc d, float exp_scale) {
+  constexpr bool RAGGED = std::is_same<Entry, sa_ragged_entry>::value;
   __shared__ uint4 row_keys[SA_SLOTS * SA_THREADS];      // 128 KiB: slot c of thread t at [c * 1024 + t]; a thread reads only what it wrote
   __shared__ int red_buf[2 * SA_WAVES];
   __shared__ int seg_cnt[SA_SEGS], seg_cnt_ex[SA_SEGS];
@@ -147,6 +161,25 @@ __global__ __launch_bounds__(SA_THREADS) void sample_advance_kernel(mpv_sample_a
   const long long row = blockIdx.x;
   const int vocab = d.vocab;
   SaReduce red{red_buf, 0};
+
+  // ---- the token column of this row: d.pos, or (ragged) the row's own prompt length + the step d.pos
+  int pos = d.pos;
+  if (RAGGED) {
+    const long long pl = d.prompt_len[row];
+    const long long col = (pl < 0 ? 0 : pl > d.row_len ? d.row_len : pl) + d.pos;
+    if (col >= d.row_len) {                              // block-uniform: frozen (the budget has ended, or a bad length); no logits read
+      if (tid == 0) {
+        if (d.out_token) d.out_token[row] = 0;
+        if (d.out_kept) d.out_kept[row] = 0;
+        if (d.out_mass) d.out_mass[row] = 0.f;
+        d.next_tok[row] = d.tokens[row * d.row_len + d.row_len - 1];
+        d.done[row] = 1;
+        atomicAdd(d.n_done, 1);
+      }
+      return;
+    }
+    pos = (int)col;
+  }
 
   if (tid < SA_SEGS) seg_cnt[tid] = 0, seg_mass[tid] = 0.f;
   if (tid == 0) pick_seg = -1, pick_tok = 0;
@@ -296,7 +329,7 @@ __global__ __launch_bounds__(SA_THREADS) void sample_advance_kernel(mpv_sample_a
       u = d.u_override[row];
     } else {
       const long long sid = d.stream_id ? d.stream_id[row] : row;
-      u = (float)(mpv_rand_pair(d.seed, ((uint64_t)(uint32_t)d.pos << 32) | (uint32_t)sid) >> 8) * 0x1p-24f;
+      u = (float)(mpv_rand_pair(d.seed, ((uint64_t)(uint32_t)pos << 32) | (uint32_t)sid) >> 8) * 0x1p-24f;
     }
     if (wave == 0) {
       sa_seg_scan_f(seg_mass, seg_mass_ex, seg_mass_in, lane);
@@ -351,11 +384,11 @@ __global__ __launch_bounds__(SA_THREADS) void sample_advance_kernel(mpv_sample_a
     if (d.out_kept) d.out_kept[row] = n_kept;
     if (d.out_mass) d.out_mass[row] = mass;
     int64_t* trow = d.tokens + row * d.row_len;
-    const bool started = d.prompt_len[row] <= d.pos;
-    if (started) trow[d.pos] = tok;
-    d.next_tok[row] = trow[d.pos];
+    const bool started = RAGGED || d.prompt_len[row] <= pos;      // ragged: no teacher forcing, the column lies behind the prompt
+    if (started) trow[pos] = tok;
+    d.next_tok[row] = trow[pos];
     bool term;
-    if (d.termination_mode == 2) term = tok == 628 || (tok == 198 && d.pos > 0 && trow[d.pos - 1] == 198);
+    if (d.termination_mode == 2) term = tok == 628 || (tok == 198 && pos > 0 && trow[pos - 1] == 198);
     else if (d.termination_mode == 1) term = tok == 628 || tok == 198;
     else term = tok == d.termination_id;
     const int done = (d.done[row] != 0 || (started && term)) ? 1 : 0;
@@ -366,30 +399,40 @@ __global__ __launch_bounds__(SA_THREADS) void sample_advance_kernel(mpv_sample_a
 
 }  // namespace
 
-extern "C" int mpv_sample_advance(const mpv_sample_advance_desc* d, hipStream_t stream) {
-  MPV_REQUIRE(d, MPV_E_ARG, "mpv_sample_advance: null descriptor");
-  MPV_REQUIRE(d->logits && d->tokens && d->prompt_len && d->done && d->next_tok && d->n_done, MPV_E_ARG, "mpv_sample_advance: null pointer");
-  MPV_REQUIRE(d->rows >= 1, MPV_E_SHAPE, "mpv_sample_advance: rows (%d) must be positive", d->rows);
-  MPV_REQUIRE(d->vocab >= 8 && d->vocab <= SA_MAX_VOCAB && d->vocab % 8 == 0, MPV_E_SHAPE,
-              "mpv_sample_advance: vocab (%d) must be a multiple of 8 in [8, %d]", d->vocab, SA_MAX_VOCAB);
-  MPV_REQUIRE(d->ld >= d->vocab && d->ld % 8 == 0, MPV_E_SHAPE, "mpv_sample_advance: ld (%lld) must be a multiple of 8 and at least vocab (%d)",
+// the body of both entries; `who` names the entry in the messages
+static int launch_sample_advance(const mpv_sample_advance_desc* d, bool ragged, const char* who, hipStream_t stream) {
+  MPV_REQUIRE(d, MPV_E_ARG, "%s: null descriptor", who);
+  MPV_REQUIRE(d->logits && d->tokens && d->prompt_len && d->done && d->next_tok && d->n_done, MPV_E_ARG, "%s: null pointer", who);
+  MPV_REQUIRE(d->rows >= 1, MPV_E_SHAPE, "%s: rows (%d) must be positive", who, d->rows);
+  MPV_REQUIRE(d->vocab >= 8 && d->vocab <= SA_MAX_VOCAB && d->vocab % 8 == 0, MPV_E_SHAPE, "%s: vocab (%d) must be a multiple of 8 in [8, %d]", who,
+              d->vocab, SA_MAX_VOCAB);
+  MPV_REQUIRE(d->ld >= d->vocab && d->ld % 8 == 0, MPV_E_SHAPE, "%s: ld (%lld) must be a multiple of 8 and at least vocab (%d)", who,
               (long long)d->ld, d->vocab);
-  MPV_REQUIRE(((uintptr_t)d->logits & 15) == 0, MPV_E_ALIGN, "mpv_sample_advance: logits must be 16-byte aligned");
-  MPV_REQUIRE(isfinite(d->temperature) && d->temperature > 0.f, MPV_E_ARG, "mpv_sample_advance: temperature (%g) must be finite and positive",
+  MPV_REQUIRE(((uintptr_t)d->logits & 15) == 0, MPV_E_ALIGN, "%s: logits must be 16-byte aligned", who);
+  MPV_REQUIRE(isfinite(d->temperature) && d->temperature > 0.f, MPV_E_ARG, "%s: temperature (%g) must be finite and positive", who,
               (double)d->temperature);
-  MPV_REQUIRE(d->top_k >= 0 && d->top_k <= d->vocab, MPV_E_ARG, "mpv_sample_advance: top_k (%d) must be in [0, vocab = %d]", d->top_k, d->vocab);
-  MPV_REQUIRE(d->top_p >= 0.f && d->top_p <= 1.f, MPV_E_ARG, "mpv_sample_advance: top_p (%g) must be in [0, 1]", (double)d->top_p);
-  MPV_REQUIRE(!(d->top_k > 1 && d->top_p > 0.f), MPV_E_ARG, "mpv_sample_advance: cannot set both top-k and top-p samplings");
-  MPV_REQUIRE(!(d->top_k == 1 && d->top_p > 0.f), MPV_E_ARG, "mpv_sample_advance: cannot set both greedy and top-p samplings");
-  MPV_REQUIRE(d->row_len >= 1 && d->pos >= 0 && d->pos < d->row_len, MPV_E_SHAPE, "mpv_sample_advance: pos (%d) must be in [0, row_len = %d)", d->pos,
-              d->row_len);
+  MPV_REQUIRE(d->top_k >= 0 && d->top_k <= d->vocab, MPV_E_ARG, "%s: top_k (%d) must be in [0, vocab = %d]", who, d->top_k, d->vocab);
+  MPV_REQUIRE(d->top_p >= 0.f && d->top_p <= 1.f, MPV_E_ARG, "%s: top_p (%g) must be in [0, 1]", who, (double)d->top_p);
+  MPV_REQUIRE(!(d->top_k > 1 && d->top_p > 0.f), MPV_E_ARG, "%s: cannot set both top-k and top-p samplings", who);
+  MPV_REQUIRE(!(d->top_k == 1 && d->top_p > 0.f), MPV_E_ARG, "%s: cannot set both greedy and top-p samplings", who);
+  MPV_REQUIRE(d->row_len >= 1 && d->pos >= 0 && d->pos < d->row_len, MPV_E_SHAPE, "%s: %s (%d) must be in [0, row_len = %d)", who,
+              ragged ? "step" : "pos", d->pos, d->row_len);
   MPV_REQUIRE(d->termination_mode >= 0 && d->termination_mode <= 2 && d->vocab_size >= 0, MPV_E_ARG,
-              "mpv_sample_advance: termination_mode (%d) must be 0, 1 or 2 and vocab_size (%d) non-negative", d->termination_mode, d->vocab_size);
+              "%s: termination_mode (%d) must be 0, 1 or 2 and vocab_size (%d) non-negative", who, d->termination_mode, d->vocab_size);
   if (hipMemsetAsync(d->n_done, 0, sizeof(int32_t), stream) != hipSuccess) {
-    mpv_set_error("mpv_sample_advance: clearing n_done failed: %s", hipGetErrorString(hipGetLastError()));
+    mpv_set_error("%s: clearing n_done failed: %s", who, hipGetErrorString(hipGetLastError()));
     return MPV_E_HIP;
   }
   const float exp_scale = (float)(1.4426950408889634 / (double)d->temperature);
-  hipLaunchKernelGGL(sample_advance_kernel, dim3((unsigned)d->rows), dim3(SA_THREADS), 0, stream, *d, exp_scale);
-  return mpv_check_launch("mpv_sample_advance");
+  if (ragged) hipLaunchKernelGGL(sa_rows<sa_ragged_entry>, dim3((unsigned)d->rows), dim3(SA_THREADS), 0, stream, *d, exp_scale);
+  else hipLaunchKernelGGL(sa_rows<sample_advance_kernel>, dim3((unsigned)d->rows), dim3(SA_THREADS), 0, stream, *d, exp_scale);
+  return mpv_check_launch(who);
+}
+
+extern "C" int mpv_sample_advance(const mpv_sample_advance_desc* d, hipStream_t stream) {
+  return launch_sample_advance(d, false, "mpv_sample_advance", stream);
+}
+
+extern "C" int mpv_sample_advance_ragged(const mpv_sample_advance_desc* d, hipStream_t stream) {
+  return launch_sample_advance(d, true, "mpv_sample_advance_ragged", stream);
 }

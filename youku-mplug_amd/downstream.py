@@ -334,7 +334,8 @@ class DistributedGPT3_Caption(_GenCls):
     def generate(self, image, text, termination_id=None, batched=False, clips_per_search=32, do_sample=False, num_samples=1, temperature=1.0,
                  top_k=None, top_p=None, seed=0, kv_cache="per_sequence", repetition_penalty=None, no_repeat_ngram_size=0, min_new_tokens=0,
                  banned_token_ids=None, constrain_prompt=False, return_scores=False, best_of=False, length_penalty=1.0, query_features=None,
-                 beam_groups=1, diversity_penalty=0.0, rerank_by_logprob=False, decode_weights="bf16", mixed_prompts=False, **kw):
+                 beam_groups=1, diversity_penalty=0.0, rerank_by_logprob=False, decode_weights="bf16", mixed_prompts=False, sample_mixed_prompts=False,
+                 **kw):
         """One beam search per sample (:790-809): prompt = text.input_ids[i, :mask.sum()-1], prefix = its query features.
         batched=True (not in the reference, default off): the clips are grouped by prompt length and every group is searched in
         lockstep, `clips_per_search` clips at a time (generation.beam_search_batched_loop: the decoder's weights are read once per
@@ -396,7 +397,15 @@ class DistributedGPT3_Caption(_GenCls):
         table left-padded, every clip with the budget of positions its own length leaves).  Prompts that carry per-video text (a
         title, a question) then cost one search per chunk instead of one per distinct length.  Same return value; a clip's rows are
         those of the grouped call.  It combines with beam_groups, the constraints, rerank_by_logprob and decode_weights; do_sample,
-        kv_cache="per_sequence" and constrain_prompt=True are refused (DESIGN.md section 23 says why)."""
+        kv_cache="per_sequence" and constrain_prompt=True are refused (DESIGN.md section 23 says why).
+        sample_mixed_prompts=True (do_sample=True with kv_cache="shared_prefix" only; default off): the same for the SAMPLED captions.
+        The clips are chunked by clips_per_search in input order and every chunk is ONE lockstep loop over its prompts, whatever their
+        lengths (generation.sample_batched_loop's mixed mode: the token table stays left-aligned and every row draws, is constrained and
+        is scored at its own column, so a clip's samples still depend neither on clips_per_search nor on its neighbours; a clip whose
+        columns run out before the chunk ends is frozen on the device).  Streams, return value, scores and best_of are those of the
+        grouped call.  It combines with num_samples, temperature, top_k / top_p, seed, return_scores, best_of, decode_weights and the
+        constraints, constrain_prompt=True included (this table has no padding); use without do_sample=True and
+        kv_cache="per_sequence" are refused."""
         Q, Hh = self.num_learnable_token, self.text_width
         G = int(beam_groups)
         from . import generation as _gen
@@ -412,7 +421,8 @@ class DistributedGPT3_Caption(_GenCls):
         if mixed_prompts:
             if do_sample:
                 raise ValueError("mixed_prompts does not combine with do_sample: a sampled token is a function of its table column, "
-                                 "which the left padding would make depend on the longest prompt of the chunk")
+                                 "which the left padding would make depend on the longest prompt of the chunk (sampled captions over "
+                                 "prompts of different lengths: sample_mixed_prompts=True)")
             if not batched:
                 raise ValueError("mixed_prompts needs batched=True: the per-clip search has one prompt per call")
             if kv_cache != "shared_prefix":
@@ -421,6 +431,13 @@ class DistributedGPT3_Caption(_GenCls):
             if constrain_prompt:
                 raise ValueError("mixed_prompts does not combine with constrain_prompt=True: the left padding of the token table would "
                                  "count as prompt")
+        if sample_mixed_prompts:
+            if not do_sample:
+                raise ValueError("sample_mixed_prompts needs do_sample=True (the beam search over prompts of different lengths: "
+                                 "mixed_prompts=True)")
+            if kv_cache != "shared_prefix":
+                raise ValueError(f'sample_mixed_prompts needs kv_cache="shared_prefix" (got {kv_cache!r}): only the shared-prefix decode '
+                                 "step takes a prefix length per clip")
         Bv = image.shape[0] if query_features is None else query_features.shape[0] // Q
         was = self.training
         self.eval()
@@ -462,20 +479,30 @@ class DistributedGPT3_Caption(_GenCls):
                 scores = [None] * n
                 if scored:
                     kw = dict(kw, return_scores=True)                    # absent keyword: the calls below are today's
-                for pl, chunk in _prompt_length_chunks(lengths, clips_per_search):
+                if sample_mixed_prompts:                                 # input order, no grouping: one loop per chunk with its lengths
+                    per = int(clips_per_search)
+                    chunks = [list(range(c, min(c + per, n))) for c in range(0, n, per)]
+                    chunks = [([int(lengths[i]) for i in chunk], chunk) for chunk in chunks]
+                    kw = dict(kw, mixed_prompts=True)
+                else:
+                    chunks = [(int(pl), chunk) for pl, chunk in _prompt_length_chunks(lengths, clips_per_search)]
+                for pl, chunk in chunks:
                     sel = torch.as_tensor(chunk, dtype=torch.long, device=qf.device)
                     streams = (sel[:, None] * N + torch.arange(N, device=qf.device)[None]).reshape(-1)
                     out = self.text_decoder.sample_batched(text.input_ids[sel], query_embeds=qf[sel].contiguous(), temperature=temperature,
                                                            num_samples=N, seed=seed, streams=streams, top_k=top_k, top_p=top_p,
                                                            termination_id=termination_id,
-                                                           prompt_length=torch.full((len(sel),), int(pl), device=qf.device), **kw)
+                                                           prompt_length=(pl if sample_mixed_prompts
+                                                                          else torch.full((len(sel),), pl, device=qf.device)), **kw)
+                    if sample_mixed_prompts:                             # pad_after_termination: one prompt length per row
+                        pl = [x for x in pl for _ in range(N)]
                     if not scored:
-                        out = generation.pad_after_termination(out, int(pl), term, width, term).cpu()
+                        out = generation.pad_after_termination(out, pl, term, width, term).cpu()
                         for j, i in enumerate(sel.tolist()):
                             res[i] = out[j * N:(j + 1) * N]
                         continue
                     out, sc = out
-                    out, tlp, slp, cnt = _download_scored(generation.pad_after_termination(out, int(pl), term, width, term), sc, width)
+                    out, tlp, slp, cnt = _download_scored(generation.pad_after_termination(out, pl, term, width, term), sc, width)
                     for j, i in enumerate(sel.tolist()):
                         rows = slice(j * N, (j + 1) * N)
                         entry = dict(sum_logprob=slp[rows], count=cnt[rows], token_logprob=tlp[rows])

@@ -14,7 +14,9 @@ csrc/beam_search.hip), and so does sampled generation in lockstep (sample_batche
 return_scores ops.sample_score, csrc/sample_score.hip, records every drawn token's log-probability).  The lockstep loops can also keep
 the positions all sequences of a clip share (visual prefix + prompt) once per clip: SharedPrefixDecodeState (kv="shared_prefix";
 mpv_gpt_decode_step_shared, csrc/decode_shared_attention.hip), and with it the lockstep beam search takes clips whose prompts differ in
-length in ONE search (prompt_length = a sequence: mpv_gpt_prefill_ragged, mpv_gpt_decode_step_shared_ragged).  decode_weights="fp8" (default "bf16") runs the steps of any of these
+length in ONE search (prompt_length = a sequence: mpv_gpt_prefill_ragged, mpv_gpt_decode_step_shared_ragged), and so does the lockstep
+sampling loop (mixed_prompts=True: a left-aligned table and a token column per row, ops.sample_advance_ragged / logits_constrain_ragged /
+sample_score_ragged).  decode_weights="fp8" (default "bf16") runs the steps of any of these
 loops on e4m3 codes of the decoder's weights (DecodeWeightsQ8; mpv_gpt_decode_step_q8 / _shared_q8, csrc/gemm_w8.hip).
 """
 from __future__ import annotations
@@ -852,7 +854,7 @@ class SampleScores:
 def sample_batched_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None, temperature=1.0, use_eod_token_for_early_termination=True,
                         stop_on_double_eol=False, stop_on_eol=False, termination_id=None, prompt_length=None, num_samples=1, seed=0,
                         streams=None, advance_fn=None, constraints: Optional["LogitsConstraints"] = None, constrain_fn=None,
-                        return_scores=False, score_fn=None):
+                        return_scores=False, score_fn=None, mixed_prompts=False):
     """sample_loop with the whole of a step's sampling and bookkeeping in one launch, for B clips x num_samples sequences in lockstep:
     tokens [B, L], query_embeds [B, Q, H], prompt_length [B] (ragged lengths are allowed) or None.  Sequence j belongs to clip
     j // num_samples.  The prefill runs once per clip over the shortest prompt (state.prefill_fan_out) and fans out to the clip's
@@ -870,7 +872,18 @@ def sample_batched_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None
     after advance_fn every step, the prefill's included, score_fn (ops.sample_score) records the model's log-probability of the token
     just written, from the logits advance_fn read (the constrained ones) -- rows still inside their prompt and rows that terminated
     in an earlier step are not scored; the terminating token is.  -> (tokens, scores): a SampleScores whose token_logprob is cut to
-    the columns of `tokens`.  The host still reads only the count of done rows."""
+    the columns of `tokens`.  The host still reads only the count of done rows.
+    mixed_prompts=True (default False: everything above, launch for launch) with prompt_length = B lengths: ONE lockstep loop over
+    clips whose prompts differ in length WITHOUT teacher forcing.  The table stays LEFT-aligned (clip c's prompt at columns
+    [0, prompt_length[c]), final_len wide): a draw is a function of (seed, column, stream), so a clip's samples must not move with its
+    neighbours' prompts.  The prefill is the ragged one (state.prefill_fan_out(..., prompt_len=): SharedPrefixDecodeState; any other
+    state is refused), and advance_fn / constrain_fn / score_fn are the RAGGED entries (ops.sample_advance_ragged,
+    ops.logits_constrain_ragged, ops.sample_score_ragged), called with step=t in place of pos=: row r works on column
+    prompt_length[r] + t.  The loop ends when every row is done or after final_len - P_min steps; a clip with a longer prompt runs out
+    of columns earlier and is frozen by the kernels (done, counted in n_done), with no host bookkeeping; it keeps stepping as
+    padding rows, so Q + P_max + final_len - P_min - 2 must be a row of the position table (a ValueError before the first launch
+    otherwise).  -> tokens [B * num_samples, n], n covering every written column; a row holds its prompt, its generated tokens and,
+    behind them, the rest of its input row."""
     B, dev, N = tokens.size(0), tokens.device, int(num_samples)
     if N < 1:
         raise ValueError(f"num_samples must be at least 1 (got {num_samples})")
@@ -879,6 +892,46 @@ def sample_batched_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None
     constraints = _active_constraints(constraints, constrain_fn)
     if constraints is not None and constraints.min_new_tokens > 0 and stop_on_double_eol:
         raise ValueError(f"min_new_tokens ({constraints.min_new_tokens}) cannot be combined with stop_on_double_eol")
+    if mixed_prompts:
+        lens = _mixed_prompt_lengths(prompt_length, B, tokens.size(1))
+        if lens is None:
+            raise ValueError(f"mixed_prompts=True needs prompt_length = {B} lengths, one per clip (got {prompt_length!r})")
+        longest, shortest = max(lens), min(lens)
+        tokens, final_len, Q = _pad_for_generation(cfg, tokens, cfg.eod_id, longest, query_embeds)
+        R = B * N
+        total_final = Q + longest + final_len - shortest
+        if total_final - 2 >= cfg.max_position_embeddings:        # the last step's position of the longest prefix (frozen by then, but fed)
+            raise ValueError(f"prompts of {shortest} .. {longest} tokens behind {Q} query slots step up to position {total_final - 2}; "
+                             f"the position table has {cfg.max_position_embeddings} rows")
+        state = make_state(R, total_final)
+        if not _takes_prompt_len(state):
+            raise ValueError('mixed_prompts=True needs a state with prefill_fan_out(..., prompt_len=): kv="shared_prefix" '
+                             f"(got a {type(state).__name__})")
+        st = SampleState(tokens[:, :final_len].repeat_interleave(N, dim=0), torch.as_tensor(lens, dtype=torch.long).to(dev).repeat_interleave(N),
+                         streams=streams)
+        sc = SampleScores(R, st.row_len, dev) if return_scores else None
+        termination_id = cfg.eod_id if termination_id is None else int(termination_id)
+        mode = 2 if stop_on_double_eol else 1 if stop_on_eol else 0
+        eos_ids = [628, 198] if mode else [termination_id]
+        t = 0
+        for t in range(final_len - shortest):
+            if t == 0:
+                logits = state.prefill_fan_out(tokens[:, :longest].contiguous(), query_embeds, N, prompt_len=lens)
+            else:
+                logits = state.step(st.next_tok.view(-1, 1))
+            if constraints is not None:
+                constrain_fn(logits, st.tokens, step=t, constraints=constraints, prompt_len=st.prompt_len, eos_ids=eos_ids, ban_value=BAN_SAMPLING)
+            advance_fn(logits, st, step=t, temperature=temperature, top_k=cfg.top_k, top_p=cfg.top_p, seed=seed, vocab_size=cfg.vocab_size,
+                       termination_mode=mode, termination_id=termination_id)
+            if sc is not None:
+                score_fn(logits, st, sc, step=t)
+            if use_eod_token_for_early_termination and int(st.n_done.item()) == R:   # the step's one host read: 4 bytes
+                break
+        n = min(longest + t + Q + 1, final_len)                   # with equal lengths: the uniform loop's (prefix-inclusive, sic) slice
+        if sc is not None:
+            sc.token_logprob = sc.token_logprob[:, :n]
+            return st.tokens[:, :n], sc
+        return st.tokens[:, :n]
     lengths = prompt_length if prompt_length is not None else torch.tensor([tokens.size(1)], device=dev)
     lengths = torch.as_tensor(lengths, device=dev).view(-1).expand(B)
     min_prompt = int(lengths.min().item())
@@ -912,15 +965,19 @@ def sample_batched_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None
     return st.tokens[:, :context_length + 1]      # (sic) as sample_loop
 
 
-def pad_after_termination(tokens: torch.Tensor, prompt_len: int, termination_id: int, width: int, fill: int) -> torch.Tensor:
+def pad_after_termination(tokens: torch.Tensor, prompt_len, termination_id: int, width: int, fill: int) -> torch.Tensor:
     """tokens [R, n] (what sample_batched_loop returns) -> [R, width]: every row keeps its columns up to and including the first
     `termination_id` at or behind column `prompt_len`; what follows (tokens drawn while other rows were still running, and the
-    columns the loop never reached) is `fill`."""
+    columns the loop never reached) is `fill`.  prompt_len: an int, or R lengths (a sequence or tensor: one per row, the mixed loop)."""
     R, n = tokens.shape
     out = torch.full((R, width), int(fill), dtype=tokens.dtype, device=tokens.device)
     out[:, :min(n, width)] = tokens[:, :width]
     col = torch.arange(width, device=tokens.device)[None]
-    hit = (out == int(termination_id)) & (col >= int(prompt_len))
+    if hasattr(prompt_len, "__len__") and not (torch.is_tensor(prompt_len) and prompt_len.dim() == 0):
+        prompt_len = torch.as_tensor(prompt_len, dtype=torch.long).to(tokens.device).view(R, 1)
+    else:
+        prompt_len = int(prompt_len)
+    hit = (out == int(termination_id)) & (col >= prompt_len)
     first = torch.where(hit.any(dim=1), hit.int().argmax(dim=1), torch.full((R,), width, device=tokens.device))
     out[col > first[:, None]] = int(fill)
     return out
@@ -957,17 +1014,27 @@ def install(gpt_cls):
                                         constraints=constraints, constrain_fn=ops.logits_constrain, **groups)
 
     def sample_batched(self, tokens, query_embeds=None, temperature=1.0, num_samples=1, seed=0, streams=None, top_k=None, top_p=None,
-                       kv="per_sequence", constraints=None, return_scores=False, decode_weights="bf16", **kw):
+                       kv="per_sequence", constraints=None, return_scores=False, decode_weights="bf16", mixed_prompts=False, **kw):
         """sample with the sampler on the device (sample_batched_loop): tokens [B, L] -> [B * num_samples, n]; top_k / top_p override
         the configuration's values; the draws are those of (seed, position, streams[row]) -- not torch's generator;
         kv="shared_prefix" keeps the visual prefix and the shortest prompt once per clip (SharedPrefixDecodeState); constraints: a
         LogitsConstraints, applied on the device every step; return_scores=True: -> (tokens, SampleScores), the model's
         log-probability of every generated token, recorded on the device every step (ops.sample_score); decode_weights="fp8": the
-        steps run on the decoder's e4m3 codes (DecodeWeightsQ8)"""
+        steps run on the decoder's e4m3 codes (DecodeWeightsQ8); mixed_prompts=True with prompt_length = B lengths and
+        kv="shared_prefix": ONE loop over clips whose prompts differ in length, the table left-aligned and every row on its own
+        column (sample_batched_loop's mixed mode: ops.sample_advance_ragged / logits_constrain_ragged / sample_score_ragged)"""
         make_state = make_state_fn(self, kv, decode_weights)
         cfg = _gen_config(self)
         if top_k is not None or top_p is not None:
             cfg.top_k, cfg.top_p = int(top_k or 0), float(top_p or 0.0)
+        if mixed_prompts:
+            if kv != "shared_prefix":
+                raise ValueError(f'mixed_prompts=True needs kv="shared_prefix" (got {kv!r}): only the shared-prefix decode step takes a '
+                                 "prefix length per clip")
+            return sample_batched_loop(cfg, make_state, tokens, query_embeds=query_embeds, temperature=temperature, num_samples=num_samples,
+                                       seed=seed, streams=streams, advance_fn=ops.sample_advance_ragged, constraints=constraints,
+                                       constrain_fn=ops.logits_constrain_ragged, mixed_prompts=True,
+                                       **(dict(return_scores=True, score_fn=ops.sample_score_ragged) if return_scores else {}), **kw)
         return sample_batched_loop(cfg, make_state, tokens, query_embeds=query_embeds, temperature=temperature, num_samples=num_samples,
                                    seed=seed, streams=streams, advance_fn=ops.sample_advance, constraints=constraints,
                                    constrain_fn=ops.logits_constrain, **(dict(return_scores=True, score_fn=ops.sample_score) if return_scores else {}),

@@ -824,6 +824,23 @@ def sample_advance_desc(logits, st, *, pos, temperature=1.0, top_k=0, top_p=0.0,
     return d
 
 
+def _sample_advance(entry, logits, st, *, pos, temperature=1.0, top_k=0, top_p=0.0, seed=0, vocab_size=None, termination_mode=TERMINATION_ID,
+                    termination_id=0, u_override=None, out_kept=None, out_mass=None, out_token=None, vocab=None, ld=None):
+    """the body of sample_advance and sample_advance_ragged: `entry` is the C entry's name without the mpv_ prefix"""
+    _need_cuda(logits, st.tokens, u_override, out_kept, out_mass, out_token)
+    if logits.dtype != torch.bfloat16 or logits.ndim != 2 or logits.shape[0] < st.rows or logits.stride(1) != 1:
+        raise _lib.MpvError(f"{entry}: logits must be bf16 [{st.rows}, ld] with unit column stride (got {logits.dtype} {tuple(logits.shape)})")
+    for name, t, dt in (("u_override", u_override, torch.float32), ("out_kept", out_kept, torch.int32), ("out_mass", out_mass, torch.float32),
+                        ("out_token", out_token, torch.int64)):
+        if t is not None and (t.dtype != dt or t.numel() < st.rows or not t.is_contiguous()):
+            raise _lib.MpvError(f"{entry}: {name} must be contiguous {dt} [{st.rows}]")
+    d = sample_advance_desc(logits, st, pos=pos, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, vocab_size=vocab_size,
+                            termination_mode=termination_mode, termination_id=termination_id, u_override=u_override, out_kept=out_kept,
+                            out_mass=out_mass, out_token=out_token, vocab=vocab, ld=ld)
+    check(getattr(_lib.lib(), "mpv_" + entry)(C.byref(d), _stream()), "mpv_" + entry)
+    return st.next_tok
+
+
 def sample_advance(logits, st, *, pos, temperature=1.0, top_k=0, top_p=0.0, seed=0, vocab_size=None, termination_mode=TERMINATION_ID,
                    termination_id=0, u_override=None, out_kept=None, out_mass=None, out_token=None, vocab=None, ld=None):
     """One position of sampled generation for st.rows sequences in one launch (include/mpv.h: mpv_sample_advance; st is a
@@ -831,18 +848,20 @@ def sample_advance(logits, st, *, pos, temperature=1.0, top_k=0, top_p=0.0, seed
     the write into st.tokens[:, pos] behind the prompt, st.next_tok, st.done and st.n_done.  logits bf16 [rows, ld], the first `vocab`
     columns are read.  u_override fp32 [rows] replaces the uniform; out_kept int32 / out_mass fp32 / out_token int64 [rows] are optional
     diagnostics.  -> st.next_tok"""
-    _need_cuda(logits, st.tokens, u_override, out_kept, out_mass, out_token)
-    if logits.dtype != torch.bfloat16 or logits.ndim != 2 or logits.shape[0] < st.rows or logits.stride(1) != 1:
-        raise _lib.MpvError(f"sample_advance: logits must be bf16 [{st.rows}, ld] with unit column stride (got {logits.dtype} {tuple(logits.shape)})")
-    for name, t, dt in (("u_override", u_override, torch.float32), ("out_kept", out_kept, torch.int32), ("out_mass", out_mass, torch.float32),
-                        ("out_token", out_token, torch.int64)):
-        if t is not None and (t.dtype != dt or t.numel() < st.rows or not t.is_contiguous()):
-            raise _lib.MpvError(f"sample_advance: {name} must be contiguous {dt} [{st.rows}]")
-    d = sample_advance_desc(logits, st, pos=pos, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, vocab_size=vocab_size,
-                            termination_mode=termination_mode, termination_id=termination_id, u_override=u_override, out_kept=out_kept,
-                            out_mass=out_mass, out_token=out_token, vocab=vocab, ld=ld)
-    check(_lib.lib().mpv_sample_advance(C.byref(d), _stream()), "mpv_sample_advance")
-    return st.next_tok
+    return _sample_advance("sample_advance", logits, st, pos=pos, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, vocab_size=vocab_size,
+                           termination_mode=termination_mode, termination_id=termination_id, u_override=u_override, out_kept=out_kept,
+                           out_mass=out_mass, out_token=out_token, vocab=vocab, ld=ld)
+
+
+def sample_advance_ragged(logits, st, *, step, temperature=1.0, top_k=0, top_p=0.0, seed=0, vocab_size=None, termination_mode=TERMINATION_ID,
+                          termination_id=0, u_override=None, out_kept=None, out_mass=None, out_token=None, vocab=None, ld=None):
+    """sample_advance for a LEFT-ALIGNED table of prompts of different lengths (include/mpv.h: mpv_sample_advance_ragged): generation
+    step `step` >= 0; row r draws, with the counter of its own column st.prompt_len[r] + step, into st.tokens[r, that column].  A row
+    whose column lies behind the table is frozen: nothing read or written but st.done[r] = 1 and st.next_tok[r] = its last token.
+    -> st.next_tok"""
+    return _sample_advance("sample_advance_ragged", logits, st, pos=step, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
+                           vocab_size=vocab_size, termination_mode=termination_mode, termination_id=termination_id, u_override=u_override,
+                           out_kept=out_kept, out_mass=out_mass, out_token=out_token, vocab=vocab, ld=ld)
 
 
 def _constraint_ids(constraints, device, eos_ids):
@@ -855,21 +874,16 @@ def _constraint_ids(constraints, device, eos_ids):
     return hit
 
 
-def logits_constrain(logits, tokens, *, pos, constraints, prompt_len=None, prompt_len_all=0, eos_ids=(), ban_value=float("-inf"), vocab=None,
-                     ld=None):
-    """One step's generation constraints, in place and in one launch (include/mpv.h: mpv_logits_constrain; constraints is a
-    generation.LogitsConstraints): repetition penalty, no-repeat n-gram, min_new_tokens (bans eos_ids while fewer tokens are generated)
-    and the banned ids, on logits bf16 [rows, ld] (the first `vocab` columns) from the histories in tokens int64 [rows, row_len] below
-    column `pos`.  prompt_len int64 [rows] (rows with prompt_len > pos are left alone), or None: prompt_len_all for every row.  A
-    banned logit becomes ban_value (-inf for the sampler, the lowest finite bf16 in front of logprob_topk).  -> logits"""
+def _logits_constrain(entry, logits, tokens, *, pos, constraints, prompt_len, prompt_len_all, eos_ids, ban_value, vocab, ld):
+    """the body of logits_constrain and logits_constrain_ragged: `entry` is the C entry's name without the mpv_ prefix"""
     _need_cuda(logits, tokens, prompt_len)
     if logits.dtype != torch.bfloat16 or logits.ndim != 2 or logits.stride(1) != 1:
-        raise _lib.MpvError(f"logits_constrain: logits must be bf16 [rows, ld] with unit column stride (got {logits.dtype} {tuple(logits.shape)})")
+        raise _lib.MpvError(f"{entry}: logits must be bf16 [rows, ld] with unit column stride (got {logits.dtype} {tuple(logits.shape)})")
     rows = logits.shape[0]
     if tokens.dtype != torch.int64 or tokens.ndim != 2 or tokens.shape[0] != rows or not tokens.is_contiguous():
-        raise _lib.MpvError(f"logits_constrain: tokens must be contiguous int64 [{rows}, row_len] (got {tokens.dtype} {tuple(tokens.shape)})")
+        raise _lib.MpvError(f"{entry}: tokens must be contiguous int64 [{rows}, row_len] (got {tokens.dtype} {tuple(tokens.shape)})")
     if prompt_len is not None and (prompt_len.dtype != torch.int64 or prompt_len.numel() != rows or not prompt_len.is_contiguous()):
-        raise _lib.MpvError(f"logits_constrain: prompt_len must be contiguous int64 [{rows}]")
+        raise _lib.MpvError(f"{entry}: prompt_len must be contiguous int64 [{rows}]")
     eos, banned = _constraint_ids(constraints, logits.device, eos_ids)
     d = _lib.LogitsConstrainDesc()
     d.logits, d.tokens, d.prompt_len = _p(logits), _p(tokens), _p(prompt_len)
@@ -878,8 +892,50 @@ def logits_constrain(logits, tokens, *, pos, constraints, prompt_len=None, promp
     d.rows, d.vocab, d.row_len, d.pos = rows, int(vocab) if vocab is not None else logits.shape[-1], tokens.shape[1], int(pos)
     d.n_eos, d.n_banned, d.ngram, d.min_new_tokens = eos.numel(), banned.numel(), constraints.no_repeat_ngram_size, constraints.min_new_tokens
     d.include_prompt, d.penalty, d.ban_value = int(constraints.include_prompt), constraints.repetition_penalty, float(ban_value)
-    check(_lib.lib().mpv_logits_constrain(C.byref(d), _stream()), "mpv_logits_constrain")
+    check(getattr(_lib.lib(), "mpv_" + entry)(C.byref(d), _stream()), "mpv_" + entry)
     return logits
+
+
+def logits_constrain(logits, tokens, *, pos, constraints, prompt_len=None, prompt_len_all=0, eos_ids=(), ban_value=float("-inf"), vocab=None,
+                     ld=None):
+    """One step's generation constraints, in place and in one launch (include/mpv.h: mpv_logits_constrain; constraints is a
+    generation.LogitsConstraints): repetition penalty, no-repeat n-gram, min_new_tokens (bans eos_ids while fewer tokens are generated)
+    and the banned ids, on logits bf16 [rows, ld] (the first `vocab` columns) from the histories in tokens int64 [rows, row_len] below
+    column `pos`.  prompt_len int64 [rows] (rows with prompt_len > pos are left alone), or None: prompt_len_all for every row.  A
+    banned logit becomes ban_value (-inf for the sampler, the lowest finite bf16 in front of logprob_topk).  -> logits"""
+    return _logits_constrain("logits_constrain", logits, tokens, pos=pos, constraints=constraints, prompt_len=prompt_len,
+                             prompt_len_all=prompt_len_all, eos_ids=eos_ids, ban_value=ban_value, vocab=vocab, ld=ld)
+
+
+def logits_constrain_ragged(logits, tokens, *, step, constraints, prompt_len, eos_ids=(), ban_value=float("-inf"), vocab=None, ld=None):
+    """logits_constrain for a LEFT-ALIGNED table of prompts of different lengths (include/mpv.h: mpv_logits_constrain_ragged):
+    generation step `step` >= 0; row r's history is tokens[r, start : prompt_len[r] + step] with start = 0 under include_prompt and
+    prompt_len[r] otherwise, and `step` tokens count as generated.  prompt_len int64 [rows] is required.  A row whose column lies behind
+    the table is left alone.  -> logits"""
+    if prompt_len is None:
+        raise _lib.MpvError("logits_constrain_ragged: prompt_len int64 [rows] is required")
+    return _logits_constrain("logits_constrain_ragged", logits, tokens, pos=step, constraints=constraints, prompt_len=prompt_len,
+                             prompt_len_all=0, eos_ids=eos_ids, ban_value=ban_value, vocab=vocab, ld=ld)
+
+
+def _sample_score(entry, logits, st, sc, *, pos, vocab, ld):
+    """the body of sample_score and sample_score_ragged: `entry` is the C entry's name without the mpv_ prefix"""
+    _need_cuda(logits, st.tokens, sc.token_logprob)
+    if logits.dtype != torch.bfloat16 or logits.ndim != 2 or logits.shape[0] < st.rows or logits.stride(1) != 1:
+        raise _lib.MpvError(f"{entry}: logits must be bf16 [{st.rows}, ld] with unit column stride (got {logits.dtype} {tuple(logits.shape)})")
+    if sc.rows != st.rows or sc.row_len != st.row_len:
+        raise _lib.MpvError(f"{entry}: scores of [{sc.rows}, {sc.row_len}] for a state of [{st.rows}, {st.row_len}]")
+    for name, t, dt, shape in (("live", sc.live, torch.int32, (st.rows,)), ("token_logprob", sc.token_logprob, torch.float32, (st.rows, st.row_len)),
+                               ("sum_logprob", sc.sum_logprob, torch.float32, (st.rows,)), ("count", sc.count, torch.int32, (st.rows,))):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != logits.device:
+            raise _lib.MpvError(f"{entry}: {name} must be contiguous {dt} {list(shape)} on {logits.device}")
+    d = _lib.SampleScoreDesc()
+    d.logits, d.tokens, d.prompt_len, d.done = _p(logits), _p(st.tokens), _p(st.prompt_len), _p(st.done)
+    d.live, d.token_logprob, d.sum_logprob, d.count = _p(sc.live), _p(sc.token_logprob), _p(sc.sum_logprob), _p(sc.count)
+    d.ld = int(ld) if ld is not None else logits.stride(0)
+    d.rows, d.vocab, d.row_len, d.pos = st.rows, int(vocab) if vocab is not None else logits.shape[-1], st.row_len, int(pos)
+    check(getattr(_lib.lib(), "mpv_" + entry)(C.byref(d), _stream()), "mpv_" + entry)
+    return sc
 
 
 def sample_score(logits, st, sc, *, pos, vocab=None, ld=None):
@@ -888,22 +944,14 @@ def sample_score(logits, st, sc, *, pos, vocab=None, ld=None):
     generation.SampleScores): log_softmax of logits bf16 [rows, ld] (the first `vocab` columns, what sample_advance read), into
     sc.token_logprob[:, pos], sc.sum_logprob and sc.count.  Rows with st.prompt_len > pos and rows whose sc.live is 0 are skipped;
     sc.live follows st.done.  -> sc"""
-    _need_cuda(logits, st.tokens, sc.token_logprob)
-    if logits.dtype != torch.bfloat16 or logits.ndim != 2 or logits.shape[0] < st.rows or logits.stride(1) != 1:
-        raise _lib.MpvError(f"sample_score: logits must be bf16 [{st.rows}, ld] with unit column stride (got {logits.dtype} {tuple(logits.shape)})")
-    if sc.rows != st.rows or sc.row_len != st.row_len:
-        raise _lib.MpvError(f"sample_score: scores of [{sc.rows}, {sc.row_len}] for a state of [{st.rows}, {st.row_len}]")
-    for name, t, dt, shape in (("live", sc.live, torch.int32, (st.rows,)), ("token_logprob", sc.token_logprob, torch.float32, (st.rows, st.row_len)),
-                               ("sum_logprob", sc.sum_logprob, torch.float32, (st.rows,)), ("count", sc.count, torch.int32, (st.rows,))):
-        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != logits.device:
-            raise _lib.MpvError(f"sample_score: {name} must be contiguous {dt} {list(shape)} on {logits.device}")
-    d = _lib.SampleScoreDesc()
-    d.logits, d.tokens, d.prompt_len, d.done = _p(logits), _p(st.tokens), _p(st.prompt_len), _p(st.done)
-    d.live, d.token_logprob, d.sum_logprob, d.count = _p(sc.live), _p(sc.token_logprob), _p(sc.sum_logprob), _p(sc.count)
-    d.ld = int(ld) if ld is not None else logits.stride(0)
-    d.rows, d.vocab, d.row_len, d.pos = st.rows, int(vocab) if vocab is not None else logits.shape[-1], st.row_len, int(pos)
-    check(_lib.lib().mpv_sample_score(C.byref(d), _stream()), "mpv_sample_score")
-    return sc
+    return _sample_score("sample_score", logits, st, sc, pos=pos, vocab=vocab, ld=ld)
+
+
+def sample_score_ragged(logits, st, sc, *, step, vocab=None, ld=None):
+    """sample_score right after sample_advance_ragged (include/mpv.h: mpv_sample_score_ragged): generation step `step` >= 0; row r's
+    token at its own column st.prompt_len[r] + step is scored into sc.token_logprob[r, that column].  Frozen rows (the column lies
+    behind the table) and rows whose sc.live is 0 are skipped.  -> sc"""
+    return _sample_score("sample_score_ragged", logits, st, sc, pos=step, vocab=vocab, ld=ld)
 
 
 def sample_tokens(logits, *, temperature=1.0, top_k=0, top_p=0.0, seed=0, streams=None, vocab_size=None, vocab=None):
