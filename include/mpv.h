@@ -289,6 +289,19 @@ int mpv_attn_decode_shared_fwd(const mpv_attn_decode_shared_desc* d, mpv_stream_
  *   a group's output is, bit for bit, that of mpv_attn_decode_shared_fwd run on that group alone with prefix_len = its length.
  * Refused: what mpv_attn_decode_shared_fwd refuses, and a NULL array.  Nothing is read back from the device. */
 int mpv_attn_decode_shared_ragged_fwd(const mpv_attn_decode_shared_desc* d, const int32_t* group_prefix_len, mpv_stream_t stream);
+/* The same step for groups that ALSO differ in how many own rows they hold (clips that entered a running loop at different times:
+ * generation.sample_inflight_loop): group g attends to the first group_prefix_len[g] rows of its prefix and to the first
+ * group_own_len[g] own rows of each of its sequences.  group_own_len is a DEVICE array of int32 [n_groups]; d->own_len (1 .. 2048) is
+ * the host-side upper bound and the kernel clamps into [0, d->own_len].  A group of own length 0 is IDLE: its workgroups read no key,
+ * no q and no length but their own, and write zeros to the group's o rows.  Own rows at and beyond a group's length are never read.
+ * One kernel body serves all three entries, the own length a per-workgroup value next to the prefix length; the steps entry is its
+ * own kernel around that body, so the code of the two entries above is what it was:
+ *   with every own length equal to d->own_len the output is mpv_attn_decode_shared_ragged_fwd's, bit for bit;
+ *   a live group's output is, bit for bit, that of mpv_attn_decode_shared_fwd run on that group alone with its two lengths;
+ *   a bad length (negative: idle; beyond d->own_len: d->own_len) touches only its own group.
+ * Refused: what mpv_attn_decode_shared_ragged_fwd refuses, and a NULL group_own_len.  Nothing is read back from the device. */
+int mpv_attn_decode_shared_steps_fwd(const mpv_attn_decode_shared_desc* d, const int32_t* group_prefix_len, const int32_t* group_own_len,
+                                     mpv_stream_t stream);
 
 /* Divided space-time "temporal" attention: T<=16 tokens per (b,n) sequence, many tiny
  * problems (models/vision_transformer.py:247-248 with Attention :169-207).  qkv is the packed
@@ -494,6 +507,24 @@ int mpv_gpt_decode_step_shared(const mpv_gpt_weights* w, void* const* prefix_cac
 int mpv_gpt_decode_step_shared_ragged(const mpv_gpt_weights* w, void* const* prefix_cache, void* const* suffix_cache, int n_groups, int fan,
                                       int prefix_stride, const int32_t* group_prefix_len, int max_prefix_len, int suffix_max, int t,
                                       const int64_t* tokens, void* workspace, size_t workspace_bytes, void* logits, mpv_stream_t stream);
+/* mpv_gpt_decode_step_shared_ragged over groups that sit at different suffix positions (a finished clip's slot was given to the next
+ * clip while the others went on): group_t is a DEVICE int32 [n_groups] in place of the host t, max_t (host) the largest position any
+ * group may hold -- it serves the checks max_t < suffix_max, max_t < 2048 and max_prefix_len + max_t < max_positions.  Group g's
+ * sequences sit at suffix position group_t[g], absolute position group_prefix_len[g] + group_t[g] (formed on the device).  A group
+ * with group_t[g] < 0 (or beyond max_t: the caller's broken promise stays inside the group) is IDLE: its rows flow through the
+ * products as padding, embedded at position group_prefix_len[g]; its attention is the idle case of mpv_attn_decode_shared_steps_fwd;
+ * its logits are unspecified but finite for finite weights; NOTHING of it is written into the suffix cache.
+ * The qkv product writes dense rows into the workspace (through the identity row map: the product is the ragged step's in
+ * everything but its addresses, so the same kernel serves it), one launch per layer places row s at suffix row s*suffix_max +
+ * group_t[g], and q is read from the dense rows.  With every group_t[g] equal to t the logits and the suffix cache are
+ * mpv_gpt_decode_step_shared_ragged's at t, bit for bit; a live group's logits are those of the same group stepped where all groups
+ * sit at its position.  Workspace: mpv_gpt_decode_shared_steps_workspace_size (the shared step's plus the dense qkv rows).
+ * Refused: what mpv_gpt_decode_step_shared_ragged refuses (with max_t for t), a NULL group_t, hidden % 8 != 0. */
+size_t mpv_gpt_decode_shared_steps_workspace_size(const mpv_gpt_weights* w, int n_seq);
+int mpv_gpt_decode_step_shared_steps(const mpv_gpt_weights* w, void* const* prefix_cache, void* const* suffix_cache, int n_groups, int fan,
+                                     int prefix_stride, const int32_t* group_prefix_len, int max_prefix_len, int suffix_max,
+                                     const int32_t* group_t, int max_t, const int64_t* tokens, void* workspace, size_t workspace_bytes,
+                                     void* logits, mpv_stream_t stream);
 /* mpv_gpt_decode_step at pos0 = 0 (a prefill) for prompts of different lengths, right-padded to L tokens behind their real ones:
  * the LM head runs on row last_row[b] (DEVICE int64 [batch], an index inside sequence b's n = Q + L new rows, clamped into them) of
  * every sequence, fetched through mpv_gather_rows, instead of on row n - 1.  Causal attention leaves the rows up to last_row[b]
@@ -578,6 +609,10 @@ int mpv_gpt_decode_step_shared_ragged_q8(const mpv_gpt_weights* w, const mpv_gpt
                                          void* const* suffix_cache, int n_groups, int fan, int prefix_stride,
                                          const int32_t* group_prefix_len, int max_prefix_len, int suffix_max, int t, const int64_t* tokens,
                                          void* workspace, size_t workspace_bytes, void* logits, mpv_stream_t stream);
+int mpv_gpt_decode_step_shared_steps_q8(const mpv_gpt_weights* w, const mpv_gpt_weights_q8* q8, void* const* prefix_cache,
+                                        void* const* suffix_cache, int n_groups, int fan, int prefix_stride, const int32_t* group_prefix_len,
+                                        int max_prefix_len, int suffix_max, const int32_t* group_t, int max_t, const int64_t* tokens,
+                                        void* workspace, size_t workspace_bytes, void* logits, mpv_stream_t stream);
 int mpv_gpt_prefill_ragged_q8(const mpv_gpt_weights* w, const mpv_gpt_weights_q8* q8, void* const* kv_cache, int batch, int max_len,
                               const void* query, int Q, const int64_t* tokens, int L, const int64_t* last_row, void* workspace,
                               size_t workspace_bytes, void* logits, mpv_stream_t stream);
@@ -743,6 +778,13 @@ int mpv_sample_advance(const mpv_sample_advance_desc* d, mpv_stream_t stream);
  *   a bad prompt_len[r] (negative: taken as 0; beyond row_len: frozen) touches only row r.
  * Refused: what mpv_sample_advance refuses (prompt_len must not be NULL), and t outside [0, row_len). */
 int mpv_sample_advance_ragged(const mpv_sample_advance_desc* d, mpv_stream_t stream);
+/* The same step for rows that ALSO differ in their generation step (rows of clips that entered a running loop at different times).
+ * The descriptor is the same and d->pos is ignored; row_step is a DEVICE int32 [rows].  Row r works on column
+ * c_r = clamp(prompt_len[r], 0, row_len) + row_step[r].  A row with row_step[r] < 0 or c_r >= row_len is FROZEN exactly as above: no
+ * logit read, no token written, done[r] = 1, counted in n_done.  Bit for bit: with every row_step[r] == t the launch equals
+ * mpv_sample_advance_ragged at step t; a row equals mpv_sample_advance run on that row alone at pos = c_r.
+ * Refused: what mpv_sample_advance_ragged refuses except a d->pos out of range, and a NULL row_step. */
+int mpv_sample_advance_steps(const mpv_sample_advance_desc* d, const int32_t* row_step, mpv_stream_t stream);
 /* ------------------------------------------------------------------------------------------
  * Generation constraints in lockstep (generation.LogitsConstraints): ONE launch edits one step's logits in place, before
  * mpv_sample_advance or mpv_logprob_topk reads them, from the loop's own device token table -- the CTRL repetition penalty, the
@@ -800,6 +842,11 @@ int mpv_logits_constrain(const mpv_logits_constrain_desc* d, mpv_stream_t stream
  *   at pos = c_r with that prompt_len; a bad prompt_len[r] (negative: 0; beyond row_len: frozen) touches only row r.
  * Refused: what mpv_logits_constrain refuses, a NULL prompt_len, and t outside [0, row_len). */
 int mpv_logits_constrain_ragged(const mpv_logits_constrain_desc* d, mpv_stream_t stream);
+/* ... and for rows that also differ in their step (mpv_sample_advance_steps): d->pos is ignored, row r works on column
+ * c_r = clamp(prompt_len[r], 0, row_len) + row_step[r] (DEVICE int32 [rows]) with g = row_step[r] generated tokens.  A row with
+ * row_step[r] < 0 or c_r >= row_len is frozen: its logits stay untouched.  Bit for bit the ragged entry when every row_step[r] == t,
+ * and mpv_logits_constrain on that row alone at pos = c_r.  Refused: as the ragged entry except d->pos, and a NULL row_step. */
+int mpv_logits_constrain_steps(const mpv_logits_constrain_desc* d, const int32_t* row_step, mpv_stream_t stream);
 /* ------------------------------------------------------------------------------------------
  * Sequence scores of sampled generation in lockstep (generation.SampleScores): ONE launch, right after mpv_sample_advance, records
  * the model's log-probability of the token that call wrote into column `pos` -- log_softmax of the RAW logits the sampler read
@@ -844,6 +891,11 @@ int mpv_sample_score(const mpv_sample_score_desc* d, mpv_stream_t stream);
  *   pos = c_r; a bad prompt_len[r] (negative: 0; beyond row_len: frozen) touches only row r.
  * Refused: what mpv_sample_score refuses (prompt_len must not be NULL), and t outside [0, row_len). */
 int mpv_sample_score_ragged(const mpv_sample_score_desc* d, mpv_stream_t stream);
+/* ... and for rows that also differ in their step, right after mpv_sample_advance_steps: d->pos is ignored, row r scores the token at
+ * column c_r = clamp(prompt_len[r], 0, row_len) + row_step[r] (DEVICE int32 [rows]).  A row with row_step[r] < 0 or c_r >= row_len
+ * (frozen) or live[r] == 0 writes nothing.  Bit for bit the ragged entry when every row_step[r] == t, and mpv_sample_score on that
+ * row alone at pos = c_r.  Refused: as the ragged entry except d->pos, and a NULL row_step. */
+int mpv_sample_score_steps(const mpv_sample_score_desc* d, const int32_t* row_step, mpv_stream_t stream);
 /* ------------------------------------------------------------------------------------------
  * Device-side video input transform (configs' video_pretrain/train/test transforms,
  * dataset/__init__.py:60-85): the decoder's uint8 clip [T][H][W][3] -> crop (i, j, h, w) ->

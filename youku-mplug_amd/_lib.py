@@ -293,6 +293,16 @@ _SIGS.update({
                                        c_void_p, c_size_t, c_void_p, c_void_p]),
     "mpv_gpt_prefill_ragged_q8": (c_int, [C.POINTER(GptWeights), C.POINTER(GptWeightsQ8), C.POINTER(c_void_p), c_int, c_int, c_void_p, c_int,
                                           c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "mpv_attn_decode_shared_steps_fwd": (c_int, [C.POINTER(AttnDecodeSharedDesc), c_void_p, c_void_p, c_void_p]),
+    "mpv_gpt_decode_shared_steps_workspace_size": (c_size_t, [C.POINTER(GptWeights), c_int]),
+    "mpv_gpt_decode_step_shared_steps": (c_int, [C.POINTER(GptWeights), C.POINTER(c_void_p), C.POINTER(c_void_p), c_int, c_int, c_int,
+                                                 c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "mpv_gpt_decode_step_shared_steps_q8": (c_int, [C.POINTER(GptWeights), C.POINTER(GptWeightsQ8), C.POINTER(c_void_p), C.POINTER(c_void_p),
+                                                    c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t,
+                                                    c_void_p, c_void_p]),
+    "mpv_sample_advance_steps": (c_int, [C.POINTER(SampleAdvanceDesc), c_void_p, c_void_p]),
+    "mpv_logits_constrain_steps": (c_int, [C.POINTER(LogitsConstrainDesc), c_void_p, c_void_p]),
+    "mpv_sample_score_steps": (c_int, [C.POINTER(SampleScoreDesc), c_void_p, c_void_p]),
 })
 
 EXPORTS = tuple(_SIGS)

@@ -20,6 +20,28 @@ __global__ void ragged_last_rows_kernel(const int64_t* __restrict__ last_row, in
   if (b < batch) idx[b] = (int64_t)b * n + min(max(last_row[b], (int64_t)0), (int64_t)(n - 1));
 }
 
+// The steps entries (every group at its own suffix position group_t[g]; a group outside [0, max_t] is idle) form two vectors:
+//   positions  pos[s] = clamp(group_prefix_len[g], 1, max_prefix_len) + (live ? group_t[g] : 0)      g = s / fan; idle: a valid row
+//   own rows   own[g] = live ? group_t[g] + 1 : 0                                                     the attention's group_own_len
+// and place the dense qkv rows of a layer: row s goes to suffix row s * suffix_max + own[g] - 1, an idle group's rows nowhere.
+__global__ void steps_index_kernel(const int32_t* __restrict__ glen, const int32_t* __restrict__ group_t, int32_t* __restrict__ pos,
+                                   int32_t* __restrict__ own, int n_seq, int fan, int max_plen, int max_t) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n_seq) return;
+  const int g = s / fan, t = group_t[g];
+  const bool live = t >= 0 && t <= max_t;
+  pos[s] = min(max(glen[g], 1), max_plen) + (live ? t : 0);
+  if (s == g * fan) own[g] = live ? t + 1 : 0;
+}
+__global__ void steps_scatter_kernel(const uint4* __restrict__ qkv, const int32_t* __restrict__ own, uint4* __restrict__ suffix, long long n_seq,
+                                     int fan, long long suffix_max, int vecs) {      // vecs: 16-byte pieces of a 3H row
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_seq * vecs; i += (long long)gridDim.x * blockDim.x) {
+    const long long s = i / vecs;
+    const int o = own[s / fan];                                                      // 0 .. max_t + 1 <= suffix_max (steps_index_kernel)
+    if (o > 0) suffix[(s * suffix_max + (o - 1)) * vecs + (i - s * vecs)] = qkv[i];
+  }
+}
+
 static inline char* carve(char*& p, size_t bytes) {
   char* r = p;
   p += (bytes + 255) / 256 * 256;
@@ -207,16 +229,24 @@ extern "C" int mpv_gpt_prefill_ragged_q8(const mpv_gpt_weights* w, const mpv_gpt
 extern "C" size_t mpv_gpt_decode_shared_workspace_size(const mpv_gpt_weights* w, int n_seq) {
   return mpv_gpt_decode_workspace_size(w, n_seq, 1);
 }
+// ... of the steps entries: the dense qkv rows of a layer on top
+extern "C" size_t mpv_gpt_decode_shared_steps_workspace_size(const mpv_gpt_weights* w, int n_seq) {
+  return mpv_gpt_decode_workspace_size(w, n_seq, 1) + ((size_t)n_seq * 3 * w->hidden * 2 + 256);
+}
 
 // the body of mpv_gpt_decode_step_shared, mpv_gpt_decode_step_shared_q8 (q8 == nullptr: the bf16 step) and of the two ragged steps
 // (ragged: group g's prefix is glen[g] <= prefix_len rows long inside its prefix_stride rows; otherwise prefix_stride == prefix_len)
+// and of the two steps entries (group_t != nullptr, on top of ragged: group g sits at suffix position group_t[g]; `t` is then the
+// host bound max_t.  The qkv product writes dense rows -- through the identity row map, so that it is the ragged step's product
+// in everything but its addresses -- which steps_scatter_kernel places in the suffix cache; q is read from the dense rows)
 static int decode_step_shared(const char* who,
                               const mpv_gpt_weights* w, const mpv_gpt_weights_q8* q8, void* const* prefix_cache, void* const* suffix_cache,
                               int n_groups, int fan, int prefix_len, int suffix_max, int t, const int64_t* tokens, void* workspace,
                               size_t workspace_bytes, void* logits, hipStream_t stream, bool ragged = false, const int32_t* glen = nullptr,
-                              int prefix_stride = 0) {
+                              int prefix_stride = 0, bool steps = false, const int32_t* group_t = nullptr) {
   if (!ragged) prefix_stride = prefix_len;
   MPV_REQUIRE(!ragged || glen, MPV_E_ARG, "%s: null group_prefix_len", who);
+  MPV_REQUIRE(!steps || group_t, MPV_E_ARG, "%s: null group_t", who);
   MPV_REQUIRE(prefix_stride >= prefix_len, MPV_E_SHAPE, "%s: max_prefix_len %d exceeds the prefix_stride %d", who,
               prefix_len, prefix_stride);
   MPV_REQUIRE(w && prefix_cache && suffix_cache && tokens && workspace && logits, MPV_E_ARG, "%s: null pointer", who);
@@ -227,8 +257,9 @@ static int decode_step_shared(const char* who,
   MPV_REQUIRE(w->max_positions <= 0 || prefix_len + t < w->max_positions, MPV_E_SHAPE,
               "%s: position %d runs past the %d rows of the position embedding", who, prefix_len + t, w->max_positions);
   const int n_seq = n_groups * fan, H = w->hidden, np = w->heads, hn = H / np, F4 = w->ffn;
-  MPV_REQUIRE(workspace_bytes >= mpv_gpt_decode_shared_workspace_size(w, n_seq), MPV_E_ARG,
-              "%s: workspace too small", who);
+  MPV_REQUIRE(workspace_bytes >= (steps ? mpv_gpt_decode_shared_steps_workspace_size(w, n_seq) : mpv_gpt_decode_shared_workspace_size(w, n_seq)),
+              MPV_E_ARG, "%s: workspace too small", who);
+  MPV_REQUIRE(!steps || H % 8 == 0, MPV_E_SHAPE, "%s: hidden %d must be a multiple of 8", who, H);
   const int64_t R = n_seq;
   char* p = (char*)workspace;
   void* h = carve(p, R * H * 2);
@@ -239,11 +270,17 @@ static int decode_step_shared(const char* who,
   void* pos = carve(p, (size_t)n_seq * H * 2);           // (the `last` rows of the general step: one position needs no copy; the
                                                          // ragged step keeps its n_seq int32 positions there)
   void* xf = carve(p, (size_t)n_seq * H * 2);
+  char* qkv = steps ? carve(p, (size_t)n_seq * 3 * H * 2) : nullptr;                  // the steps entries' dense qkv rows
+  int32_t* own = (int32_t*)pos + n_seq;                                             // ... and their n_groups own lengths, behind the positions
   const Products product = {p, workspace_bytes - (size_t)(p - (char*)workspace), stream};
   int rc;
   if (ragged) {
-    hipLaunchKernelGGL(ragged_positions_kernel, dim3((unsigned)((n_seq + 255) / 256)), dim3(256), 0, stream, glen, (int32_t*)pos, n_seq, fan,
-                       prefix_len, t);
+    if (steps)
+      hipLaunchKernelGGL(steps_index_kernel, dim3((unsigned)((n_seq + 255) / 256)), dim3(256), 0, stream, glen, group_t, (int32_t*)pos, own, n_seq,
+                         fan, prefix_len, t);
+    else
+      hipLaunchKernelGGL(ragged_positions_kernel, dim3((unsigned)((n_seq + 255) / 256)), dim3(256), 0, stream, glen, (int32_t*)pos, n_seq, fan,
+                         prefix_len, t);
     rc = mpv_check_launch(who);
     if (rc) return rc;
     const int rows_wpe = w->max_positions > 0 ? w->max_positions : prefix_len + t + 1;
@@ -263,16 +300,26 @@ static int decode_step_shared(const char* who,
     mpv_gemm_epilogue ep = {};
     ep.bias = lw->qkv_b;
     ep.c_group = 1; ep.c_stride = suffix_max; ep.c_offset = t;                // row s lands at suffix row s*suffix_max + t
-    rc = product(x, lw->qkv_w, lq->qkv_q, lq->qkv_s, sc, R, 3 * H, H, &ep);
+    if (steps) ep.c_stride = 1, ep.c_offset = 0;                              // ... at dense row s: the identity, through the same row map
+    rc = product(x, lw->qkv_w, lq->qkv_q, lq->qkv_s, steps ? qkv : sc, R, 3 * H, H, &ep);
     if (rc) return rc;
+    if (steps) {
+      const int vecs = 3 * H / 8;
+      const long long blocks = ((long long)n_seq * vecs + 255) / 256;
+      hipLaunchKernelGGL(steps_scatter_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, stream, (const uint4*)qkv, own,
+                         (uint4*)sc, (long long)n_seq, fan, (long long)suffix_max, vecs);
+      rc = mpv_check_launch(who);
+      if (rc) return rc;
+    }
     mpv_attn_decode_shared_desc d = {};
-    d.q = sc + (size_t)t * 3 * H * 2;
+    d.q = steps ? qkv : sc + (size_t)t * 3 * H * 2;
     d.k = sc + (size_t)hn * 2;
     d.v = sc + (size_t)2 * hn * 2;
     d.pk = pc + (size_t)hn * 2;
     d.pv = pc + (size_t)2 * hn * 2;
     d.o = ctx;
     d.q_ss = d.k_ss = d.v_ss = (int64_t)suffix_max * 3 * H;
+    if (steps) d.q_ss = 3 * H;
     d.pk_gs = d.pv_gs = (int64_t)prefix_stride * 3 * H;
     d.q_hs = d.k_hs = d.v_hs = d.pk_hs = d.pv_hs = 3 * hn;
     d.k_rs = d.v_rs = d.pk_rs = d.pv_rs = 3 * H;
@@ -280,7 +327,9 @@ static int decode_step_shared(const char* who,
     d.n_seq = n_seq; d.group_size = fan; d.n_groups = n_groups; d.heads = np;
     d.prefix_len = prefix_len; d.own_len = t + 1; d.head_dim = hn;
     d.scale = 1.0f / sqrtf((float)hn);
-    rc = ragged ? mpv_attn_decode_shared_ragged_fwd(&d, glen, stream) : mpv_attn_decode_shared_fwd(&d, stream);
+    rc = steps    ? mpv_attn_decode_shared_steps_fwd(&d, glen, own, stream)
+         : ragged ? mpv_attn_decode_shared_ragged_fwd(&d, glen, stream)
+                  : mpv_attn_decode_shared_fwd(&d, stream);
     if (rc) return rc;
     rc = layer_tail(w, lw, lq, R, h, x, ctx, h1, g, product);
     if (rc) return rc;
@@ -326,6 +375,27 @@ extern "C" int mpv_gpt_decode_step_shared_ragged_q8(const mpv_gpt_weights* w, co
   return decode_step_shared("mpv_gpt_decode_step_shared_ragged_q8",
                             w, q8, prefix_cache, suffix_cache, n_groups, fan, max_prefix_len, suffix_max, t, tokens, workspace,
                             workspace_bytes, logits, stream, true, group_prefix_len, prefix_stride);
+}
+
+extern "C" int mpv_gpt_decode_step_shared_steps(const mpv_gpt_weights* w, void* const* prefix_cache, void* const* suffix_cache, int n_groups,
+                                                int fan, int prefix_stride, const int32_t* group_prefix_len, int max_prefix_len, int suffix_max,
+                                                const int32_t* group_t, int max_t, const int64_t* tokens, void* workspace,
+                                                size_t workspace_bytes, void* logits, hipStream_t stream) {
+  return decode_step_shared("mpv_gpt_decode_step_shared_steps",
+                            w, nullptr, prefix_cache, suffix_cache, n_groups, fan, max_prefix_len, suffix_max, max_t, tokens, workspace,
+                            workspace_bytes, logits, stream, true, group_prefix_len, prefix_stride, true, group_t);
+}
+
+extern "C" int mpv_gpt_decode_step_shared_steps_q8(const mpv_gpt_weights* w, const mpv_gpt_weights_q8* q8, void* const* prefix_cache,
+                                                   void* const* suffix_cache, int n_groups, int fan, int prefix_stride,
+                                                   const int32_t* group_prefix_len, int max_prefix_len, int suffix_max,
+                                                   const int32_t* group_t, int max_t, const int64_t* tokens, void* workspace,
+                                                   size_t workspace_bytes, void* logits, hipStream_t stream) {
+  const int rc = check_q8(w, q8, "mpv_gpt_decode_step_shared_steps_q8");
+  if (rc) return rc;
+  return decode_step_shared("mpv_gpt_decode_step_shared_steps_q8",
+                            w, q8, prefix_cache, suffix_cache, n_groups, fan, max_prefix_len, suffix_max, max_t, tokens, workspace,
+                            workspace_bytes, logits, stream, true, group_prefix_len, prefix_stride, true, group_t);
 }
 
 // InferenceParams.swap_key_value_dict (:1459-1473) for every layer: dst[l][j] = src[l][idx[j]], first `rows` positions

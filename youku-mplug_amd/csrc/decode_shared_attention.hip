@@ -19,6 +19,11 @@
 // The ragged entry (mpv_attn_decode_shared_ragged_fwd: prompts of different lengths in one lockstep search) is the same kernel with
 // a per-group prefix length: plen, the prefix tile count pt and with it the (pt + r) % 4 wave assignment are per-workgroup values,
 // read once (a workgroup serves one group).  A group's arithmetic is that of the uniform entry at its length, bit for bit.
+//
+// The steps entry (mpv_attn_decode_shared_steps_fwd: clips that entered a running loop at different times) adds a per-group OWN
+// length the same way: own and the own tile count nt are per-workgroup values too.  It is its own kernel
+// (attn_decode_shared_steps_kernel) around the one body, so the two entries above keep their code object; a group of own length 0
+// is idle: its workgroups read no key and store zeros.
 #include <string.h>
 
 #include "mpv_common.h"
@@ -41,6 +46,7 @@ struct SharedArgs {
   long long pk_gs, pk_hs, pk_rs, pv_gs, pv_hs, pv_rs, o_ss, o_hs;
   int n_seq, group_size, plen, own, hd;
   float scale;
+  const int* gown;                                // the steps entry: per-group own lengths (device); not read by the other two
 };
 
 template <int HD>
@@ -63,7 +69,7 @@ struct SharedStage {
 
   // tile T of the stream: prefix tile (T < pt) or own tile (T - pt) % nt of tile-local row (T - pt) / nt
   __device__ __forceinline__ void issue(const SharedArgs& p, const bf16* pkb, const bf16* pvb, const bf16* kb, const bf16* vb, int tid,
-                                        int chunk, int plen, int pt, int nt, int nrows) {
+                                        int chunk, int plen, int own, int pt, int nt, int nrows) {
 #pragma unroll
     for (int i = 0; i < NLOAD; ++i) {
       const int c = tid + DS_THREADS * i;
@@ -81,7 +87,7 @@ struct SharedStage {
           const int tt = T - pt;
           const int r = nt == 1 ? tt : tt / nt;
           const int key = (tt - r * nt) * 32 + kr;
-          if (r < nrows && key < p.own) {
+          if (r < nrows && key < own) {
             xk = *(const i32x4*)(kb + (long long)r * p.k_ss + (long long)key * p.k_rs + cc * 8);
             xv = *(const i32x4*)(vb + (long long)r * p.v_ss + (long long)key * p.v_rs + cc * 8);
           }
@@ -102,8 +108,9 @@ struct SharedStage {
   }
 };
 
-template <int HD>
-__global__ __launch_bounds__(DS_THREADS, 2) void attn_decode_shared_kernel(const SharedArgs p) {
+// the body of both kernels; STEPS: the own length is the group's (p.gown[g] clamped into [0, p.own]) instead of p.own
+template <int HD, bool STEPS>
+__device__ __forceinline__ void attn_decode_shared_body(const SharedArgs p) {      // (by value, as a kernel takes it: a reference costs hd 64 two registers)
   constexpr int NS = HD / 16;
   constexpr int NDT = (HD + 31) / 32;
   typedef DsLds<HD> L;
@@ -116,7 +123,22 @@ __global__ __launch_bounds__(DS_THREADS, 2) void attn_decode_shared_kernel(const
   const int rr = lane & 31;                                                // this lane's query row inside the tile
   // the group's prefix length: the ragged entry's is clamped into [1, p.plen], so a bad value cannot leave the group's rows
   const int plen = p.glen ? min(max(p.glen[g], 1), p.plen) : p.plen;
-  const int pt = (plen + 31) >> 5, nt = (p.own + 31) >> 5;                 // prefix tiles, own tiles per row
+  int own = p.own;
+  if (STEPS) {
+    own = min(max(p.gown[g], 0), p.own);                                   // a bad value cannot leave the group's rows either
+    if (own == 0) {                                                        // an idle group (uniform over the workgroup): zeros, no key read
+      if (rr < nrows) {
+        bf16* orow = p.o + (long long)(s0 + rr) * p.o_ss + (long long)h * p.o_hs;
+#pragma unroll
+        for (int d = 0; d < NDT; ++d) {
+          const int col = d * 32 + 8 * wave + 4 * (lane >> 5);             // the store pattern of the live case
+          if (col < p.hd) *(bf16x4*)(orow + col) = cvt4(f32x4{0.f, 0.f, 0.f, 0.f});
+        }
+      }
+      return;
+    }
+  }
+  const int pt = (plen + 31) >> 5, nt = (own + 31) >> 5;                   // prefix tiles, own tiles per row
   const int ntiles = pt + nrows * nt;
   const int nchunk = (ntiles + DS_WAVES - 1) / DS_WAVES;
 
@@ -146,14 +168,14 @@ __global__ __launch_bounds__(DS_THREADS, 2) void attn_decode_shared_kernel(const
   const bf16* vb = p.v + (long long)s0 * p.v_ss + (long long)h * p.v_hs;
 
   SharedStage<HD> st;
-  st.issue(p, pkb, pvb, kb, vb, tid, 0, plen, pt, nt, nrows);
+  st.issue(p, pkb, pvb, kb, vb, tid, 0, plen, own, pt, nt, nrows);
   st.commit(smem, tid);
   __syncthreads();
   // head_dim 64 keeps the next chunk's loads in flight (in registers) under the tiles of this one; head_dim 80 has 16 more
   // accumulator registers per triple and 16 more staging registers, and would spill: it loads between the two barriers
   constexpr bool PREFETCH = HD == 64;
   for (int c = 0; c < nchunk; ++c) {
-    if (PREFETCH && c + 1 < nchunk) st.issue(p, pkb, pvb, kb, vb, tid, c + 1, plen, pt, nt, nrows);
+    if (PREFETCH && c + 1 < nchunk) st.issue(p, pkb, pvb, kb, vb, tid, c + 1, plen, own, pt, nt, nrows);
 #pragma unroll 1
     for (int s = 0; s < DS_WAVES; ++s) {
       const int T = c * DS_WAVES + s;
@@ -167,12 +189,12 @@ __global__ __launch_bounds__(DS_THREADS, 2) void attn_decode_shared_kernel(const
         const int r = nt == 1 ? tt : tt / nt;
         if (((pt + r) & (DS_WAVES - 1)) != wave) continue;
         const int key0 = (tt - r * nt) * 32;
-        ptile_update<HD>(smem, smem + DS_KV, s, key0, qf, sc, om, ol, oacc, lane, [&](int key) { return rr == r && key < p.own; });
+        ptile_update<HD>(smem, smem + DS_KV, s, key0, qf, sc, om, ol, oacc, lane, [&](int key) { return rr == r && key < own; });
       }
     }
     __syncthreads();                                                       // every wave is done with the chunk
     if (c + 1 < nchunk) {
-      if (!PREFETCH) st.issue(p, pkb, pvb, kb, vb, tid, c + 1, plen, pt, nt, nrows);
+      if (!PREFETCH) st.issue(p, pkb, pvb, kb, vb, tid, c + 1, plen, own, pt, nt, nrows);
       st.commit(smem, tid);
       __syncthreads();
     }
@@ -229,12 +251,23 @@ __global__ __launch_bounds__(DS_THREADS, 2) void attn_decode_shared_kernel(const
   }
 }
 
+template <int HD>
+__global__ __launch_bounds__(DS_THREADS, 2) void attn_decode_shared_kernel(const SharedArgs p) {
+  attn_decode_shared_body<HD, false>(p);
+}
+template <int HD>
+__global__ __launch_bounds__(DS_THREADS, 2) void attn_decode_shared_steps_kernel(const SharedArgs p) {
+  attn_decode_shared_body<HD, true>(p);
+}
+
 }  // namespace
 
-// the body of both entries (glen == nullptr: the uniform one); `who` names the entry in the messages
-static int launch_shared(const mpv_attn_decode_shared_desc* d, const int32_t* glen, bool ragged, const char* who, hipStream_t stream) {
+// the body of the three entries (glen == nullptr: the uniform one; gown != nullptr: the steps one); `who` names the entry in the messages
+static int launch_shared(const mpv_attn_decode_shared_desc* d, const int32_t* glen, bool ragged, const char* who, hipStream_t stream,
+                         const int32_t* gown = nullptr, bool steps = false) {
   MPV_REQUIRE(d && d->q && d->k && d->v && d->pk && d->pv && d->o, MPV_E_ARG, "%s: null pointer", who);
   MPV_REQUIRE(!ragged || glen, MPV_E_ARG, "%s: null group_prefix_len", who);
+  MPV_REQUIRE(!steps || gown, MPV_E_ARG, "%s: null group_own_len", who);
   MPV_REQUIRE(d->head_dim == 64 || d->head_dim == 80, MPV_E_SHAPE,
               "%s: head_dim %d is not supported (64: the 1.3B decoder, 80: 2.7B)", who, d->head_dim);
   MPV_REQUIRE(d->n_seq > 0 && d->group_size > 0 && d->heads > 0, MPV_E_SHAPE,
@@ -263,6 +296,7 @@ static int launch_shared(const mpv_attn_decode_shared_desc* d, const int32_t* gl
   a.pk = (const bf16*)d->pk;
   a.pv = (const bf16*)d->pv;
   a.glen = glen;
+  a.gown = gown;
   a.o = (bf16*)d->o;
   a.q_ss = d->q_ss; a.q_hs = d->q_hs;
   a.k_ss = d->k_ss; a.k_hs = d->k_hs; a.k_rs = d->k_rs;
@@ -277,7 +311,11 @@ static int launch_shared(const mpv_attn_decode_shared_desc* d, const int32_t* gl
   a.hd = d->head_dim;
   a.scale = d->scale;
   const dim3 grid((unsigned)((d->group_size + 31) / 32), (unsigned)d->heads, (unsigned)d->n_groups);
-  if (d->head_dim == 64)
+  if (steps && d->head_dim == 64)
+    hipLaunchKernelGGL(attn_decode_shared_steps_kernel<64>, grid, dim3(DS_THREADS), 0, stream, a);
+  else if (steps)
+    hipLaunchKernelGGL(attn_decode_shared_steps_kernel<80>, grid, dim3(DS_THREADS), 0, stream, a);
+  else if (d->head_dim == 64)
     hipLaunchKernelGGL(attn_decode_shared_kernel<64>, grid, dim3(DS_THREADS), 0, stream, a);
   else
     hipLaunchKernelGGL(attn_decode_shared_kernel<80>, grid, dim3(DS_THREADS), 0, stream, a);
@@ -291,4 +329,9 @@ extern "C" int mpv_attn_decode_shared_fwd(const mpv_attn_decode_shared_desc* d, 
 extern "C" int mpv_attn_decode_shared_ragged_fwd(const mpv_attn_decode_shared_desc* d, const int32_t* group_prefix_len,
                                                  hipStream_t stream) {
   return launch_shared(d, group_prefix_len, true, "mpv_attn_decode_shared_ragged_fwd", stream);
+}
+
+extern "C" int mpv_attn_decode_shared_steps_fwd(const mpv_attn_decode_shared_desc* d, const int32_t* group_prefix_len,
+                                                const int32_t* group_own_len, hipStream_t stream) {
+  return launch_shared(d, group_prefix_len, true, "mpv_attn_decode_shared_steps_fwd", stream, group_own_len, true);
 }

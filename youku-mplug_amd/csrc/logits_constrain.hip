@@ -15,7 +15,9 @@
 // depend on thread timing.  No scratch, no atomics, no floating-point reduction.
 //
 // The ragged entry (mpv_logits_constrain_ragged) is the same kernel body with the token column a per-workgroup value,
-// c_r = clamp(prompt_len[r], 0, row_len) + step; a row whose column lies behind the table is frozen and left as it is.
+// c_r = clamp(prompt_len[r], 0, row_len) + step; a row whose column lies behind the table is frozen and left as it is.  The steps
+// entry (mpv_logits_constrain_steps: rows that entered a running loop at different times) reads the step per row as well, from
+// row_step[r]; a negative step freezes the row.
 #include "mpv_common.h"
 #include "../../include/mpv.h"
 
@@ -31,10 +33,12 @@ constexpr int LC_THREADS = 1024, LC_MAX_ROW = 2048, LC_MAX_EOS = 8, LC_MAX_BANNE
 // contains it (the resource checks and profiles look the uniform kernel up by that name) and the ragged one's does not.
 struct logits_constrain_kernel {};    // mpv_logits_constrain: every row at column d.pos
 struct lc_ragged_entry {};            // mpv_logits_constrain_ragged: row r at its own column
+struct lc_steps_entry {};             // mpv_logits_constrain_steps: row r at its own column AND its own step row_step[r]
 
 template <class Entry>
-__global__ __launch_bounds__(LC_THREADS) void lc_rows(mpv_logits_constrain_desc d, unsigned ban_bits) {
-  constexpr bool RAGGED = std::is_same<Entry, lc_ragged_entry>::value;
+__global__ __launch_bounds__(LC_THREADS) void lc_rows(mpv_logits_constrain_desc d, unsigned ban_bits, const int32_t* __restrict__ row_step) {
+  constexpr bool STEPS = std::is_same<Entry, lc_steps_entry>::value;       // (row_step is read by this instantiation only)
+  constexpr bool RAGGED = std::is_same<Entry, lc_ragged_entry>::value || STEPS;
   __shared__ long long hist[LC_MAX_ROW];                       // 16 KiB
   __shared__ long long listed[LC_MAX_BANNED + LC_MAX_EOS];     // 8 KiB
   __shared__ unsigned char hit[LC_MAX_ROW];                    // 2 KiB
@@ -45,8 +49,9 @@ __global__ __launch_bounds__(LC_THREADS) void lc_rows(mpv_logits_constrain_desc 
   if (RAGGED) {                                                // the row's own column: its prompt length + the step d.pos
     pl = d.prompt_len[row];
     pl = pl < 0 ? 0 : pl > d.row_len ? d.row_len : pl;
-    if (pl + d.pos >= d.row_len) return;                       // block-uniform: a frozen row stays as it is
-    pos = (int)pl + d.pos;
+    const int step = STEPS ? row_step[row] : d.pos;
+    if (pl + step >= d.row_len || (STEPS && step < 0)) return; // block-uniform: a frozen row stays as it is
+    pos = (int)pl + step;
   } else {
     pl = d.prompt_len ? d.prompt_len[row] : d.prompt_len_all;
     if (pl > d.pos) return;                                    // block-uniform: a teacher-forced row stays as it is
@@ -110,9 +115,11 @@ unsigned lc_bf16_bits(float v) {
 
 }  // namespace
 
-// the body of both entries; `who` names the entry in the messages
-static int launch_logits_constrain(const mpv_logits_constrain_desc* d, bool ragged, const char* who, hipStream_t stream) {
+// the body of the three entries (row_step != nullptr: the steps one, which ignores d->pos); `who` names the entry in the messages
+static int launch_logits_constrain(const mpv_logits_constrain_desc* d, bool ragged, const char* who, hipStream_t stream,
+                                   const int32_t* row_step = nullptr, bool steps = false) {
   MPV_REQUIRE(d, MPV_E_ARG, "%s: null descriptor", who);
+  MPV_REQUIRE(!steps || row_step, MPV_E_ARG, "%s: null row_step", who);
   MPV_REQUIRE(d->logits && d->tokens, MPV_E_ARG, "%s: null logits or tokens", who);
   MPV_REQUIRE(!ragged || d->prompt_len, MPV_E_ARG, "%s: null prompt_len", who);
   MPV_REQUIRE(d->rows >= 1, MPV_E_SHAPE, "%s: rows (%d) must be positive", who, d->rows);
@@ -122,8 +129,8 @@ static int launch_logits_constrain(const mpv_logits_constrain_desc* d, bool ragg
               (long long)d->ld, d->vocab);
   MPV_REQUIRE(((uintptr_t)d->logits & 15) == 0, MPV_E_ALIGN, "%s: logits must be 16-byte aligned", who);
   MPV_REQUIRE(d->row_len >= 1 && d->row_len <= LC_MAX_ROW, MPV_E_SHAPE, "%s: row_len (%d) must be in [1, %d]", who, d->row_len, LC_MAX_ROW);
-  MPV_REQUIRE(d->pos >= 0 && d->pos < d->row_len, MPV_E_SHAPE, "%s: %s (%d) must be in [0, row_len = %d)", who, ragged ? "step" : "pos", d->pos,
-              d->row_len);
+  MPV_REQUIRE(steps || (d->pos >= 0 && d->pos < d->row_len), MPV_E_SHAPE, "%s: %s (%d) must be in [0, row_len = %d)", who, ragged ? "step" : "pos",
+              d->pos, d->row_len);
   MPV_REQUIRE(isfinite(d->penalty) && d->penalty > 0.f, MPV_E_ARG, "%s: penalty (%g) must be finite and positive", who, (double)d->penalty);
   MPV_REQUIRE(d->ngram >= 0 && d->ngram <= LC_MAX_NGRAM, MPV_E_ARG, "%s: ngram (%d) must be in [0, %d]", who, d->ngram, LC_MAX_NGRAM);
   MPV_REQUIRE(d->min_new_tokens >= 0, MPV_E_ARG, "%s: min_new_tokens (%d) must not be negative", who, d->min_new_tokens);
@@ -136,9 +143,14 @@ static int launch_logits_constrain(const mpv_logits_constrain_desc* d, bool ragg
               (double)d->ban_value);
   if (d->penalty == 1.f && d->ngram == 0 && d->n_banned == 0 && (d->min_new_tokens == 0 || d->n_eos == 0)) return MPV_OK;      // everything off
   const unsigned ban_bits = lc_bf16_bits(d->ban_value);
-  if (ragged) hipLaunchKernelGGL(lc_rows<lc_ragged_entry>, dim3((unsigned)d->rows), dim3(LC_THREADS), 0, stream, *d, ban_bits);
-  else hipLaunchKernelGGL(lc_rows<logits_constrain_kernel>, dim3((unsigned)d->rows), dim3(LC_THREADS), 0, stream, *d, ban_bits);
+  if (steps) hipLaunchKernelGGL(lc_rows<lc_steps_entry>, dim3((unsigned)d->rows), dim3(LC_THREADS), 0, stream, *d, ban_bits, row_step);
+  else if (ragged) hipLaunchKernelGGL(lc_rows<lc_ragged_entry>, dim3((unsigned)d->rows), dim3(LC_THREADS), 0, stream, *d, ban_bits, nullptr);
+  else hipLaunchKernelGGL(lc_rows<logits_constrain_kernel>, dim3((unsigned)d->rows), dim3(LC_THREADS), 0, stream, *d, ban_bits, nullptr);
   return mpv_check_launch(who);
+}
+
+extern "C" int mpv_logits_constrain_steps(const mpv_logits_constrain_desc* d, const int32_t* row_step, hipStream_t stream) {
+  return launch_logits_constrain(d, true, "mpv_logits_constrain_steps", stream, row_step, true);
 }
 
 extern "C" int mpv_logits_constrain(const mpv_logits_constrain_desc* d, hipStream_t stream) {

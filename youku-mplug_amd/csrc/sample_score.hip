@@ -15,6 +15,7 @@
 //
 // The ragged entry (mpv_sample_score_ragged) is the same kernel body with the token column a per-workgroup value,
 // c_r = clamp(prompt_len[r], 0, row_len) + step; a row whose column lies behind the table is frozen and returns like a dead one.
+// The steps entry (mpv_sample_score_steps) reads the step per row as well, from row_step[r]; a negative step freezes the row.
 #include "mpv_common.h"
 #include "../../include/mpv.h"
 
@@ -31,10 +32,12 @@ constexpr unsigned SS_NEG_INF_PAIR = 0xff80ff80u;        // two bf16 -inf: what 
 // contains it (the resource checks and profiles look the uniform kernel up by that name) and the ragged one's does not.
 struct sample_score_kernel {};        // mpv_sample_score: every row at column d.pos
 struct ss_ragged_entry {};            // mpv_sample_score_ragged: row r at its own column
+struct ss_steps_entry {};             // mpv_sample_score_steps: row r at its own column AND its own step row_step[r]
 
 template <class Entry>
-__global__ __launch_bounds__(SS_THREADS) void ss_rows(mpv_sample_score_desc d) {
-  constexpr bool RAGGED = std::is_same<Entry, ss_ragged_entry>::value;
+__global__ __launch_bounds__(SS_THREADS) void ss_rows(mpv_sample_score_desc d, const int32_t* __restrict__ row_step) {
+  constexpr bool STEPS = std::is_same<Entry, ss_steps_entry>::value;       // (row_step is read by this instantiation only)
+  constexpr bool RAGGED = std::is_same<Entry, ss_ragged_entry>::value || STEPS;
   __shared__ float wave_m[SS_WAVES], wave_s[SS_WAVES];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long long row = blockIdx.x;
@@ -42,8 +45,9 @@ __global__ __launch_bounds__(SS_THREADS) void ss_rows(mpv_sample_score_desc d) {
   if (RAGGED) {                                                // the row's own column: its prompt length + the step d.pos
     long long pl = d.prompt_len[row];
     pl = pl < 0 ? 0 : pl > d.row_len ? d.row_len : pl;
-    if (pl + d.pos >= d.row_len || d.live[row] == 0) return;   // block-uniform: frozen, or scored to its end already
-    pos = (int)pl + d.pos;
+    const int step = STEPS ? row_step[row] : d.pos;
+    if (pl + step >= d.row_len || (STEPS && step < 0) || d.live[row] == 0) return;   // block-uniform: frozen, or scored to its end already
+    pos = (int)pl + step;
   } else if (d.prompt_len[row] > d.pos || d.live[row] == 0) {
     return;                                                    // block-uniform (live is rewritten behind the last barrier only)
   }
@@ -112,9 +116,11 @@ __global__ __launch_bounds__(SS_THREADS) void ss_rows(mpv_sample_score_desc d) {
 
 }  // namespace
 
-// the body of both entries; `who` names the entry in the messages
-static int launch_sample_score(const mpv_sample_score_desc* d, bool ragged, const char* who, hipStream_t stream) {
+// the body of the three entries (row_step != nullptr: the steps one, which ignores d->pos); `who` names the entry in the messages
+static int launch_sample_score(const mpv_sample_score_desc* d, bool ragged, const char* who, hipStream_t stream,
+                               const int32_t* row_step = nullptr, bool steps = false) {
   MPV_REQUIRE(d, MPV_E_ARG, "%s: null descriptor", who);
+  MPV_REQUIRE(!steps || row_step, MPV_E_ARG, "%s: null row_step", who);
   MPV_REQUIRE(d->logits && d->tokens && d->prompt_len && d->done && d->live && d->token_logprob && d->sum_logprob && d->count, MPV_E_ARG,
               "%s: null pointer", who);
   MPV_REQUIRE(d->rows >= 1, MPV_E_SHAPE, "%s: rows (%d) must be positive", who, d->rows);
@@ -124,11 +130,16 @@ static int launch_sample_score(const mpv_sample_score_desc* d, bool ragged, cons
               (long long)d->ld, d->vocab);
   MPV_REQUIRE(((uintptr_t)d->logits & 15) == 0, MPV_E_ALIGN, "%s: logits must be 16-byte aligned", who);
   MPV_REQUIRE(d->row_len >= 1 && d->row_len <= SS_MAX_ROW, MPV_E_SHAPE, "%s: row_len (%d) must be in [1, %d]", who, d->row_len, SS_MAX_ROW);
-  MPV_REQUIRE(d->pos >= 0 && d->pos < d->row_len, MPV_E_SHAPE, "%s: %s (%d) must be in [0, row_len = %d)", who, ragged ? "step" : "pos", d->pos,
-              d->row_len);
-  if (ragged) hipLaunchKernelGGL(ss_rows<ss_ragged_entry>, dim3((unsigned)d->rows), dim3(SS_THREADS), 0, stream, *d);
-  else hipLaunchKernelGGL(ss_rows<sample_score_kernel>, dim3((unsigned)d->rows), dim3(SS_THREADS), 0, stream, *d);
+  MPV_REQUIRE(steps || (d->pos >= 0 && d->pos < d->row_len), MPV_E_SHAPE, "%s: %s (%d) must be in [0, row_len = %d)", who, ragged ? "step" : "pos",
+              d->pos, d->row_len);
+  if (steps) hipLaunchKernelGGL(ss_rows<ss_steps_entry>, dim3((unsigned)d->rows), dim3(SS_THREADS), 0, stream, *d, row_step);
+  else if (ragged) hipLaunchKernelGGL(ss_rows<ss_ragged_entry>, dim3((unsigned)d->rows), dim3(SS_THREADS), 0, stream, *d, nullptr);
+  else hipLaunchKernelGGL(ss_rows<sample_score_kernel>, dim3((unsigned)d->rows), dim3(SS_THREADS), 0, stream, *d, nullptr);
   return mpv_check_launch(who);
+}
+
+extern "C" int mpv_sample_score_steps(const mpv_sample_score_desc* d, const int32_t* row_step, hipStream_t stream) {
+  return launch_sample_score(d, true, "mpv_sample_score_steps", stream, row_step, true);
 }
 
 extern "C" int mpv_sample_score(const mpv_sample_score_desc* d, hipStream_t stream) {

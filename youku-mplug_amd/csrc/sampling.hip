@@ -23,7 +23,8 @@
 // token column a per-workgroup value, c_r = clamp(prompt_len[r], 0, row_len) + step, read once by the row's workgroup; a row whose
 // column lies behind the table is frozen and leaves before the first barrier.  The column is a template parameter's business: the
 // uniform instantiation (sa_rows<sample_advance_kernel>) reads d.pos as before and contains nothing of the ragged one
-// (sa_rows<sa_ragged_entry>).
+// (sa_rows<sa_ragged_entry>).  The steps entry (mpv_sample_advance_steps: rows that entered a running loop at different times,
+// sa_rows<sa_steps_entry>) reads the step per row as well, from row_step[r]; a negative step freezes the row.
 #include "mpv_common.h"
 #include "../../include/mpv.h"
 
@@ -147,10 +148,12 @@ __device__ __forceinline__ void sa_seg_scan_f(const float* x, float* ex, float* 
 // contains it (the resource checks and profiles look the uniform kernel up by that name) and the ragged one's does not.
 struct sample_advance_kernel {};      // mpv_sample_advance: every row at column d.pos
 struct sa_ragged_entry {};            // mpv_sample_advance_ragged: row r at its own column
+struct sa_steps_entry {};             // mpv_sample_advance_steps: row r at its own column AND its own step row_step[r]
 
 template <class Entry>
-__global__ __launch_bounds__(SA_THREADS) void sa_rows(mpv_sample_advance_desc d, float exp_scale) {
-  constexpr bool RAGGED = std::is_same<Entry, sa_ragged_entry>::value;
+__global__ __launch_bounds__(SA_THREADS) void sa_rows(mpv_sample_advance_desc d, float exp_scale, const int32_t* __restrict__ row_step) {
+  constexpr bool STEPS = std::is_same<Entry, sa_steps_entry>::value;       // (row_step is read by this instantiation only)
+  constexpr bool RAGGED = std::is_same<Entry, sa_ragged_entry>::value || STEPS;
   __shared__ uint4 row_keys[SA_SLOTS * SA_THREADS];      // 128 KiB: slot c of thread t at [c * 1024 + t]; a thread reads only what it wrote
   __shared__ int red_buf[2 * SA_WAVES];
   __shared__ int seg_cnt[SA_SEGS], seg_cnt_ex[SA_SEGS];
@@ -166,8 +169,9 @@ __global__ __launch_bounds__(SA_THREADS) void sa_rows(mpv_sample_advance_desc d,
   int pos = d.pos;
   if (RAGGED) {
     const long long pl = d.prompt_len[row];
-    const long long col = (pl < 0 ? 0 : pl > d.row_len ? d.row_len : pl) + d.pos;
-    if (col >= d.row_len) {                              // block-uniform: frozen (the budget has ended, or a bad length); no logits read
+    const int step = STEPS ? row_step[row] : d.pos;
+    const long long col = (pl < 0 ? 0 : pl > d.row_len ? d.row_len : pl) + step;
+    if (col >= d.row_len || (STEPS && step < 0)) {       // block-uniform: frozen (the budget has ended, a bad length, an idle row); no logits read
       if (tid == 0) {
         if (d.out_token) d.out_token[row] = 0;
         if (d.out_kept) d.out_kept[row] = 0;
@@ -399,9 +403,11 @@ __global__ __launch_bounds__(SA_THREADS) void sa_rows(mpv_sample_advance_desc d,
 
 }  // namespace
 
-// the body of both entries; `who` names the entry in the messages
-static int launch_sample_advance(const mpv_sample_advance_desc* d, bool ragged, const char* who, hipStream_t stream) {
+// the body of the three entries (row_step != nullptr: the steps one, which ignores d->pos); `who` names the entry in the messages
+static int launch_sample_advance(const mpv_sample_advance_desc* d, bool ragged, const char* who, hipStream_t stream,
+                                 const int32_t* row_step = nullptr, bool steps = false) {
   MPV_REQUIRE(d, MPV_E_ARG, "%s: null descriptor", who);
+  MPV_REQUIRE(!steps || row_step, MPV_E_ARG, "%s: null row_step", who);
   MPV_REQUIRE(d->logits && d->tokens && d->prompt_len && d->done && d->next_tok && d->n_done, MPV_E_ARG, "%s: null pointer", who);
   MPV_REQUIRE(d->rows >= 1, MPV_E_SHAPE, "%s: rows (%d) must be positive", who, d->rows);
   MPV_REQUIRE(d->vocab >= 8 && d->vocab <= SA_MAX_VOCAB && d->vocab % 8 == 0, MPV_E_SHAPE, "%s: vocab (%d) must be a multiple of 8 in [8, %d]", who,
@@ -415,7 +421,7 @@ static int launch_sample_advance(const mpv_sample_advance_desc* d, bool ragged, 
   MPV_REQUIRE(d->top_p >= 0.f && d->top_p <= 1.f, MPV_E_ARG, "%s: top_p (%g) must be in [0, 1]", who, (double)d->top_p);
   MPV_REQUIRE(!(d->top_k > 1 && d->top_p > 0.f), MPV_E_ARG, "%s: cannot set both top-k and top-p samplings", who);
   MPV_REQUIRE(!(d->top_k == 1 && d->top_p > 0.f), MPV_E_ARG, "%s: cannot set both greedy and top-p samplings", who);
-  MPV_REQUIRE(d->row_len >= 1 && d->pos >= 0 && d->pos < d->row_len, MPV_E_SHAPE, "%s: %s (%d) must be in [0, row_len = %d)", who,
+  MPV_REQUIRE(d->row_len >= 1 && (steps || (d->pos >= 0 && d->pos < d->row_len)), MPV_E_SHAPE, "%s: %s (%d) must be in [0, row_len = %d)", who,
               ragged ? "step" : "pos", d->pos, d->row_len);
   MPV_REQUIRE(d->termination_mode >= 0 && d->termination_mode <= 2 && d->vocab_size >= 0, MPV_E_ARG,
               "%s: termination_mode (%d) must be 0, 1 or 2 and vocab_size (%d) non-negative", who, d->termination_mode, d->vocab_size);
@@ -424,9 +430,14 @@ static int launch_sample_advance(const mpv_sample_advance_desc* d, bool ragged, 
     return MPV_E_HIP;
   }
   const float exp_scale = (float)(1.4426950408889634 / (double)d->temperature);
-  if (ragged) hipLaunchKernelGGL(sa_rows<sa_ragged_entry>, dim3((unsigned)d->rows), dim3(SA_THREADS), 0, stream, *d, exp_scale);
-  else hipLaunchKernelGGL(sa_rows<sample_advance_kernel>, dim3((unsigned)d->rows), dim3(SA_THREADS), 0, stream, *d, exp_scale);
+  if (steps) hipLaunchKernelGGL(sa_rows<sa_steps_entry>, dim3((unsigned)d->rows), dim3(SA_THREADS), 0, stream, *d, exp_scale, row_step);
+  else if (ragged) hipLaunchKernelGGL(sa_rows<sa_ragged_entry>, dim3((unsigned)d->rows), dim3(SA_THREADS), 0, stream, *d, exp_scale, nullptr);
+  else hipLaunchKernelGGL(sa_rows<sample_advance_kernel>, dim3((unsigned)d->rows), dim3(SA_THREADS), 0, stream, *d, exp_scale, nullptr);
   return mpv_check_launch(who);
+}
+
+extern "C" int mpv_sample_advance_steps(const mpv_sample_advance_desc* d, const int32_t* row_step, hipStream_t stream) {
+  return launch_sample_advance(d, true, "mpv_sample_advance_steps", stream, row_step, true);
 }
 
 extern "C" int mpv_sample_advance(const mpv_sample_advance_desc* d, hipStream_t stream) {

@@ -335,7 +335,7 @@ class DistributedGPT3_Caption(_GenCls):
                  top_k=None, top_p=None, seed=0, kv_cache="per_sequence", repetition_penalty=None, no_repeat_ngram_size=0, min_new_tokens=0,
                  banned_token_ids=None, constrain_prompt=False, return_scores=False, best_of=False, length_penalty=1.0, query_features=None,
                  beam_groups=1, diversity_penalty=0.0, rerank_by_logprob=False, decode_weights="bf16", mixed_prompts=False, sample_mixed_prompts=False,
-                 **kw):
+                 inflight=False, max_new_tokens=None, refill_min=None, **kw):
         """One beam search per sample (:790-809): prompt = text.input_ids[i, :mask.sum()-1], prefix = its query features.
         batched=True (not in the reference, default off): the clips are grouped by prompt length and every group is searched in
         lockstep, `clips_per_search` clips at a time (generation.beam_search_batched_loop: the decoder's weights are read once per
@@ -405,7 +405,16 @@ class DistributedGPT3_Caption(_GenCls):
         columns run out before the chunk ends is frozen on the device).  Streams, return value, scores and best_of are those of the
         grouped call.  It combines with num_samples, temperature, top_k / top_p, seed, return_scores, best_of, decode_weights and the
         constraints, constrain_prompt=True included (this table has no padding); use without do_sample=True and
-        kv_cache="per_sequence" are refused."""
+        kv_cache="per_sequence" are refused.
+        inflight=True (do_sample=True with kv_cache="shared_prefix" only; default off): the sampled captions of ALL the clips in one
+        loop that keeps clips_per_search clips (slots) x num_samples sequences resident and gives a finished clip's slot to the next
+        clip while the others go on (generation.sample_inflight_loop: continuous batching; a suffix position per clip in the decode
+        step, a generation step per row in the sampler-side kernels).  A lockstep chunk is held until its slowest caption ends; here a
+        clip leaves when all its samples have terminated or after max_new_tokens tokens (None: tokens_to_generate; an int or one budget
+        per clip, capped by the table's columns), and refills wait for refill_min free slots.  Prompts may differ in length as with
+        sample_mixed_prompts, and streams, return value, return_scores and best_of are that call's: a clip's tokens depend neither on
+        its slot nor on when it entered.  top_k=1 makes it a greedy captioner.  Use without do_sample=True or with
+        kv_cache="per_sequence" is refused."""
         Q, Hh = self.num_learnable_token, self.text_width
         G = int(beam_groups)
         from . import generation as _gen
@@ -438,6 +447,15 @@ class DistributedGPT3_Caption(_GenCls):
             if kv_cache != "shared_prefix":
                 raise ValueError(f'sample_mixed_prompts needs kv_cache="shared_prefix" (got {kv_cache!r}): only the shared-prefix decode '
                                  "step takes a prefix length per clip")
+        if inflight:
+            if not do_sample:
+                raise ValueError("inflight needs do_sample=True: beam search in flight would need a step per clip in the beam kernels "
+                                 "(greedy captions: do_sample=True with top_k=1)")
+            if kv_cache != "shared_prefix":
+                raise ValueError(f'inflight needs kv_cache="shared_prefix" (got {kv_cache!r}): only the shared-prefix decode step takes a '
+                                 "suffix position per clip")
+        elif max_new_tokens is not None or refill_min is not None:
+            raise ValueError("max_new_tokens / refill_min belong to inflight=True")
         Bv = image.shape[0] if query_features is None else query_features.shape[0] // Q
         was = self.training
         self.eval()
@@ -479,6 +497,32 @@ class DistributedGPT3_Caption(_GenCls):
                 scores = [None] * n
                 if scored:
                     kw = dict(kw, return_scores=True)                    # absent keyword: the calls below are today's
+                if inflight:                                             # ONE loop over all clips, clips_per_search slots resident
+                    more = {k: v for k, v in kw.items() if k != "kv"}
+                    out = self.text_decoder.sample_inflight(text.input_ids, query_embeds=qf.contiguous(), temperature=temperature, num_samples=N,
+                                                            slots=int(clips_per_search), seed=seed, top_k=top_k, top_p=top_p,
+                                                            termination_id=termination_id, prompt_length=[int(x) for x in lengths],
+                                                            max_new_tokens=max_new_tokens, refill_min=refill_min, **more)
+                    rows_pl = [int(x) for x in lengths for _ in range(N)]
+                    col = torch.arange(out.tokens.shape[1], device=out.tokens.device)[None]
+                    end = torch.as_tensor([w for w in out.written for _ in range(N)], dtype=torch.long).to(out.tokens.device)[:, None]
+                    toks = torch.where(col < end, out.tokens, torch.full_like(out.tokens, term))      # behind a clip's budget: padding
+                    toks = generation.pad_after_termination(toks, rows_pl, term, width, term)
+                    if not scored:
+                        toks = toks.cpu()
+                        return [toks[i * N:(i + 1) * N] for i in range(n)]
+                    toks, tlp, slp, cnt = _download_scored(toks, out.scores, width)
+                    for i in range(n):
+                        rows = slice(i * N, (i + 1) * N)
+                        entry = dict(sum_logprob=slp[rows], count=cnt[rows], token_logprob=tlp[rows])
+                        if best_of:
+                            b = best_sample(entry["sum_logprob"], entry["count"], length_penalty)
+                            entry = dict({k: v[b:b + 1] for k, v in entry.items()}, index=b)
+                            res[i] = toks[rows][b:b + 1]
+                        else:
+                            res[i] = toks[rows]
+                        scores[i] = entry
+                    return (res, scores) if return_scores else res
                 if sample_mixed_prompts:                                 # input order, no grouping: one loop per chunk with its lengths
                     per = int(clips_per_search)
                     chunks = [list(range(c, min(c + per, n))) for c in range(0, n, per)]

@@ -16,7 +16,9 @@ the positions all sequences of a clip share (visual prefix + prompt) once per cl
 mpv_gpt_decode_step_shared, csrc/decode_shared_attention.hip), and with it the lockstep beam search takes clips whose prompts differ in
 length in ONE search (prompt_length = a sequence: mpv_gpt_prefill_ragged, mpv_gpt_decode_step_shared_ragged), and so does the lockstep
 sampling loop (mixed_prompts=True: a left-aligned table and a token column per row, ops.sample_advance_ragged / logits_constrain_ragged /
-sample_score_ragged).  decode_weights="fp8" (default "bf16") runs the steps of any of these
+sample_score_ragged); sample_inflight_loop refills a finished clip's rows with the next clip of the data set while the others go on
+(InflightDecodeState: mpv_gpt_decode_step_shared_steps, a suffix position per clip; ops.sample_advance_steps / logits_constrain_steps /
+sample_score_steps, a step per row).  decode_weights="fp8" (default "bf16") runs the steps of any of these
 loops on e4m3 codes of the decoder's weights (DecodeWeightsQ8; mpv_gpt_decode_step_q8 / _shared_q8, csrc/gemm_w8.hip).
 """
 from __future__ import annotations
@@ -380,6 +382,88 @@ class SharedPrefixDecodeState:
         """bytes of the prefix, suffix and twin allocations"""
         return sum(t.numel() * t.element_size() for t in (None if self.prefix is None else self.prefix.cache, self.suffix, self.twin)
                    if t is not None)
+
+
+class InflightDecodeState:
+    """The shared-prefix state of sample_inflight_loop: `slots` clips x `fan` sequences stay resident and a finished clip's slot is
+    given to the next clip while the others go on.  The prefix cache is [nl, slots * P, 3H] with P = Q + the longest prompt of the
+    whole call (it is the cache of a DecodeState of batch `slots`, which also carries the weight tables), group_prefix_len int32
+    [slots] says how many of a slot's rows are real, and the suffix cache is [nl, slots * fan * S, 3H]; samples never swap caches, so
+    there is no twin.  install() prefills new clips on a small staging state (mpv_gpt_prefill_ragged) and copies their prefix rows
+    into their slots with ONE scatter over all layers; step() is ONE call into the C ABI (mpv_gpt_decode_step_shared_steps) with a
+    suffix position per slot, idle slots included."""
+
+    def __init__(self, gpt, slots: int, fan: int, prefix_rows: int, suffix_rows: int, weights: str = "bf16"):
+        _check_weight_mode(weights)
+        if slots < 1 or fan < 1 or prefix_rows < 1 or suffix_rows < 1:
+            raise ValueError(f"InflightDecodeState: slots {slots}, fan {fan}, prefix rows {prefix_rows} and suffix rows {suffix_rows} must be positive")
+        self.gpt, self.slots, self.fan, self.P, self.S, self.weights = gpt, int(slots), int(fan), int(prefix_rows), int(suffix_rows), weights
+        self.batch = self.slots * self.fan
+        self.prefix = st = DecodeState(gpt, self.slots, self.P, weights)
+        self.nl, self.H = st.nl, st.H
+        dev = st.cache.device
+        self.suffix = torch.zeros((st.nl, self.batch * self.S, 3 * st.H), dtype=torch.bfloat16, device=dev)
+        self._suffix_ptrs = st._ptrs(self.suffix)
+        self.group_prefix_len = torch.ones(self.slots, dtype=torch.int32, device=dev)       # a free slot: one (zero) prefix row, never used
+        self._layer_base = torch.arange(st.nl, device=dev, dtype=torch.int64)[:, None] * self.slots
+        self.prefills = self.steps = 0            # launches issued so far (the loop's report)
+
+    def install(self, slot_ids, tokens: torch.Tensor, query_embeds: Optional[torch.Tensor], prompt_len) -> torch.Tensor:
+        """prefills k new clips -- tokens [k, L] right-padded, query_embeds [k, Q, H], prompt_len k lengths in [1, L], Q + L == the
+        state's prefix rows -- into the slots slot_ids (k distinct slot numbers) -> their prefill logits [k, V]"""
+        slot_ids = [int(s) for s in slot_ids]
+        k = len(slot_ids)
+        Q = 0 if query_embeds is None else query_embeds.shape[1]
+        if k < 1 or tokens.shape[0] != k or len(set(slot_ids)) != k or min(slot_ids) < 0 or max(slot_ids) >= self.slots:
+            raise ValueError(f"install: {k} distinct slots in [0, {self.slots}) for {tokens.shape[0]} clips (got {slot_ids})")
+        if Q + tokens.shape[1] != self.P:
+            raise ValueError(f"install: {Q} query slots + {tokens.shape[1]} prompt columns are not the state's {self.P} prefix rows")
+        staging = SharedPrefixDecodeState(self.gpt, k, self.P + 1, self.weights)
+        logits = staging.prefill_fan_out(tokens, query_embeds, 1, prompt_len=prompt_len)
+        dev = self.suffix.device
+        idx = (self._layer_base + torch.as_tensor(slot_ids, dtype=torch.int64).to(dev)[None]).reshape(-1).contiguous()
+        row = self.P * 3 * self.H                 # a clip's prefix rows of one layer are one "row" of the scatter
+        ops.scatter_rows(staging.prefix.cache.view(-1), idx, self.prefix.cache.view(-1), self.nl * k, row, row)
+        self.group_prefix_len[torch.as_tensor(slot_ids, dtype=torch.long).to(dev)] = staging.group_prefix_len
+        self.prefills += 1
+        return logits
+
+    def step(self, tokens: torch.Tensor, group_t: torch.Tensor, max_t: int) -> torch.Tensor:
+        """tokens [slots * fan, 1] int64, group_t int32 [slots] on the device (slot g's suffix position; negative: idle), max_t the
+        largest of them (host) -> logits [slots * fan, V] bf16; an idle slot's rows are unspecified"""
+        if tokens is None or tokens.dim() != 2 or tokens.shape != (self.batch, 1):
+            raise ValueError(f"InflightDecodeState.step takes ONE token for each of the {self.batch} sequences")
+        if group_t.dtype != torch.int32 or group_t.numel() != self.slots or not group_t.is_contiguous():
+            raise ValueError(f"InflightDecodeState.step: group_t must be a contiguous int32 tensor of {self.slots} positions")
+        if not 0 <= int(max_t) < self.S:
+            raise ValueError(f"InflightDecodeState.step: suffix position {int(max_t)} does not fit the suffix cache of {self.S} positions")
+        self.steps += 1
+        return self._steps_step(tokens.contiguous(), group_t, int(max_t))
+
+    def _steps_step(self, tokens, group_t, max_t) -> torch.Tensor:
+        import ctypes as C
+        from . import _lib
+        st, dev = self.prefix, self.suffix.device
+        ws = ops.workspace(_lib.lib().mpv_gpt_decode_shared_steps_workspace_size(C.byref(st._w), self.batch), dev)
+        logits = torch.empty((self.batch, st.V), dtype=torch.bfloat16, device=dev)
+        tail = (st._cache_ptrs, self._suffix_ptrs, self.slots, self.fan, self.P, self.group_prefix_len.data_ptr(), self.P, self.S,
+                group_t.data_ptr(), max_t, tokens.data_ptr(), ws.data_ptr(), ws.numel(), logits.data_ptr(), ops._stream())
+        if st.q8 is None:
+            ops.check(_lib.lib().mpv_gpt_decode_step_shared_steps(C.byref(st._w), *tail), "mpv_gpt_decode_step_shared_steps")
+        else:
+            ops.check(_lib.lib().mpv_gpt_decode_step_shared_steps_q8(C.byref(st._w), C.byref(st._q8), *tail),
+                      "mpv_gpt_decode_step_shared_steps_q8")
+        return logits
+
+    def kv_bytes(self) -> int:
+        """bytes of the prefix and suffix allocations"""
+        return sum(t.numel() * t.element_size() for t in (self.prefix.cache, self.suffix))
+
+
+def make_inflight_state_fn(gpt, weights: str = "bf16"):
+    """The make_state of sample_inflight_loop: (slots, fan, prefix_rows, suffix_rows) -> an InflightDecodeState on `weights`"""
+    _check_weight_mode(weights)
+    return lambda slots, fan, prefix_rows, suffix_rows: InflightDecodeState(gpt, slots, fan, prefix_rows, suffix_rows, weights)
 
 
 KV_MODES = ("per_sequence", "shared_prefix")
@@ -965,6 +1049,149 @@ def sample_batched_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None
     return st.tokens[:, :context_length + 1]      # (sic) as sample_loop
 
 
+def refill_min_default(slots: int) -> int:
+    """sample_inflight_loop: the free slots a refill waits for, a quarter of the slots -- a staged prefill costs more than a decode step,
+    and at 32 slots a wait for 8 was the fastest of 1 / 4 / 8 / 16 on both row counts measured"""
+    return max(1, int(slots) // 4)
+
+
+def sample_inflight_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None, temperature=1.0, use_eod_token_for_early_termination=True,
+                         stop_on_double_eol=False, stop_on_eol=False, termination_id=None, prompt_length=None, num_samples=1, slots=32,
+                         max_new_tokens=None, refill_min=None, seed=0, streams=None, advance_fn=None,
+                         constraints: Optional["LogitsConstraints"] = None, constrain_fn=None, return_scores=False, score_fn=None):
+    """sample_batched_loop's mixed mode with the finished clips' rows REFILLED in flight (continuous batching): tokens [n, L],
+    query_embeds [n, Q, H], prompt_length n lengths; `slots` clips x num_samples sequences stay resident and the n clips of the
+    call pass through them in input order.  A lockstep chunk is held until its slowest sequence ends while a decode step costs the
+    same whatever the number of live rows; here a clip LEAVES when all its samples are done or its own budget is reached, and its
+    slot goes to the next clip.  The table is the mixed mode's (left-aligned, final_len wide) and a draw is a function of (seed,
+    column, stream), so a clip's rows do not depend on when, where or beside whom it runs: they are, on every column both wrote, those
+    of sample_batched_loop(mixed_prompts=True) on that clip alone with the same streams.
+    make_state(slots, fan, prefix_rows, suffix_rows) -> an InflightDecodeState (make_inflight_state_fn).  advance_fn / constrain_fn /
+    score_fn are the _steps entries (ops.sample_advance_steps, ops.logits_constrain_steps, ops.sample_score_steps), called with
+    row_step= (int32 [slots * num_samples] on the device: every row's own generation step, -1 for the rows of a free slot).
+    One iteration: (0) if at least refill_min slots are free (default refill_min_default(slots): a quarter of them; at most `slots`), or nothing runs, the next
+    clips are installed (ONE staged ragged prefill for all of them); (1) ONE decode step for the slots already running -- a slot just
+    installed is idle in it --, none if nothing runs; (2) the prefill logits overwrite the rows of the slots just installed; (3) one
+    constrain launch, one advance launch and one score launch, every row on its own step; (4) the host, which mirrors every slot's
+    step as Python ints, reads n_done (4 bytes) and -- only when that count is not the one it expects -- the done vector; clips that
+    are done (unless use_eod_token_for_early_termination is False) or have used their budget leave: their token and score rows are
+    gathered on the device into the result, in input order.
+    max_new_tokens: None (cfg.tokens_to_generate for every clip), an int, or n budgets; a clip's budget is capped by the columns its
+    prompt leaves in the table, and the last position it feeds, Q + prompt_length[c] + budget - 2, must be a row of the position
+    table (a ValueError before the first launch otherwise).  When the input runs out, free slots idle until the last clip ends.
+    -> SimpleNamespace(tokens [n * num_samples, final_len] (a row: its prompt, its generated tokens, behind them the rest of its
+    input row), written [n] (list: the columns of clip c that hold prompt or generated tokens), scores (a SampleScores over all rows,
+    or None), steps / prefills (decode steps and prefill passes issued))."""
+    n, dev, N, slots = tokens.size(0), tokens.device, int(num_samples), int(slots)
+    if N < 1 or slots < 1:
+        raise ValueError(f"num_samples and slots must be at least 1 (got {num_samples}, {slots})")
+    if return_scores and score_fn is None:
+        raise ValueError("return_scores=True needs a score_fn (ops.sample_score_steps)")
+    if advance_fn is None:
+        raise ValueError("sample_inflight_loop needs an advance_fn (ops.sample_advance_steps)")
+    constraints = _active_constraints(constraints, constrain_fn)
+    if constraints is not None and constraints.min_new_tokens > 0 and stop_on_double_eol:
+        raise ValueError(f"min_new_tokens ({constraints.min_new_tokens}) cannot be combined with stop_on_double_eol")
+    lens = _mixed_prompt_lengths(prompt_length, n, tokens.size(1))
+    if lens is None:
+        raise ValueError(f"sample_inflight_loop needs prompt_length = {n} lengths, one per clip (got {prompt_length!r})")
+    refill_min = min(slots, refill_min_default(slots) if refill_min is None else int(refill_min))
+    if refill_min < 1:
+        raise ValueError(f"refill_min must be at least 1 (got {refill_min})")
+    longest = max(lens)
+    table, final_len, Q = _pad_for_generation(cfg, tokens, cfg.eod_id, longest, query_embeds)
+    table = table[:, :final_len]
+    if max_new_tokens is None:
+        budgets = [int(cfg.tokens_to_generate)] * n
+    elif hasattr(max_new_tokens, "__len__") and not (torch.is_tensor(max_new_tokens) and max_new_tokens.dim() == 0):
+        budgets = [int(b) for b in (max_new_tokens.tolist() if torch.is_tensor(max_new_tokens) else max_new_tokens)]
+    else:
+        budgets = [int(max_new_tokens)] * n
+    if len(budgets) != n or min(budgets) < 1:
+        raise ValueError(f"max_new_tokens must be None, a positive int or {n} positive budgets (got {max_new_tokens!r})")
+    budgets = [min(b, final_len - pl) for b, pl in zip(budgets, lens)]                      # the table's columns behind the prompt
+    for c, (b, pl) in enumerate(zip(budgets, lens)):
+        if Q + pl + b - 2 >= cfg.max_position_embeddings:
+            raise ValueError(f"clip {c}: a prompt of {pl} tokens behind {Q} query slots with a budget of {b} feeds position {Q + pl + b - 2}; "
+                             f"the position table has {cfg.max_position_embeddings} rows")
+    R = slots * N
+    state = make_state(slots, N, Q + longest, max(max(budgets) - 1, 1))
+    streams = (torch.arange(n * N, dtype=torch.int64, device=dev) if streams is None
+               else torch.as_tensor(streams, device=dev).to(torch.int64).reshape(-1))
+    if streams.numel() != n * N:
+        raise ValueError(f"streams must hold {n * N} numbers, one per sample (got {streams.numel()})")
+    st = SampleState(table[:1].expand(R, -1), torch.zeros(1, dtype=torch.long, device=dev))
+    sc = SampleScores(R, st.row_len, dev) if return_scores else None
+    out_tokens = table.repeat_interleave(N, dim=0).contiguous()
+    out_sc = SampleScores(n * N, st.row_len, dev) if return_scores else None
+    written = list(lens)
+    termination_id = cfg.eod_id if termination_id is None else int(termination_id)
+    mode = 2 if stop_on_double_eol else 1 if stop_on_eol else 0
+    eos_ids = [628, 198] if mode else [termination_id]
+    lens_d = torch.as_tensor(lens, dtype=torch.long).to(dev)
+    within = torch.arange(N, device=dev)
+    logits = None
+    clip_of, step_of, known_done = [-1] * slots, [-1] * slots, [0] * slots            # the host's mirror: clip, next sampler step, done rows
+    next_clip = 0
+    while next_clip < n or any(c >= 0 for c in clip_of):
+        free = [s for s in range(slots) if clip_of[s] < 0]
+        fresh = []
+        if next_clip < n and free and (len(free) >= refill_min or len(free) == slots):     # (0) the refill
+            fresh = free[:n - next_clip]
+            clips = list(range(next_clip, next_clip + len(fresh)))
+            next_clip += len(fresh)
+            sel = torch.as_tensor(clips, dtype=torch.long).to(dev)
+            first = state.install(fresh, table[sel, :longest].contiguous(), None if query_embeds is None else query_embeds[sel].contiguous(),
+                                  [lens[c] for c in clips])
+            fresh_rows = (torch.as_tensor(fresh, dtype=torch.long).to(dev)[:, None] * N + within[None]).reshape(-1)
+            src = (sel[:, None] * N + within[None]).reshape(-1)
+            st.tokens[fresh_rows] = out_tokens[src]                                        # the slot's rows, reset for their new clip
+            st.prompt_len[fresh_rows] = lens_d[sel].repeat_interleave(N)
+            st.stream[fresh_rows] = streams[src]
+            st.done[fresh_rows] = 0
+            if sc is not None:
+                sc.live[fresh_rows], sc.sum_logprob[fresh_rows], sc.count[fresh_rows], sc.token_logprob[fresh_rows] = 1, 0.0, 0, 0.0
+            for s, c in zip(fresh, clips):
+                clip_of[s], step_of[s], known_done[s] = c, 0, 0
+        running = [s for s in range(slots) if clip_of[s] >= 0 and step_of[s] >= 1]
+        if running:                                                                        # (1) one decode step; fresh and free slots idle
+            group_t = torch.tensor([step_of[s] - 1 if clip_of[s] >= 0 else -1 for s in range(slots)], dtype=torch.int32).to(dev)
+            logits = state.step(st.next_tok.view(-1, 1), group_t, max(step_of[s] - 1 for s in running))
+        elif logits is None:
+            logits = torch.zeros((R, first.shape[1]), dtype=torch.bfloat16, device=dev)     # the first iteration; frozen rows read none of it
+        if fresh:                                                                          # (2) the prefill logits of the fresh slots
+            logits[fresh_rows] = first.repeat_interleave(N, dim=0)
+        row_step = torch.tensor([step_of[s] if clip_of[s] >= 0 else -1 for s in range(slots)], dtype=torch.int32).repeat_interleave(N).to(dev)
+        if constraints is not None:                                                        # (3) every row on its own step
+            constrain_fn(logits, st.tokens, row_step=row_step, constraints=constraints, prompt_len=st.prompt_len, eos_ids=eos_ids,
+                         ban_value=BAN_SAMPLING)
+        advance_fn(logits, st, row_step=row_step, temperature=temperature, top_k=cfg.top_k, top_p=cfg.top_p, seed=seed, vocab_size=cfg.vocab_size,
+                   termination_mode=mode, termination_id=termination_id)
+        if sc is not None:
+            score_fn(logits, st, sc, row_step=row_step)
+        active = [s for s in range(slots) if clip_of[s] >= 0]                              # (4) the bookkeeping
+        for s in active:
+            step_of[s] += 1
+        if use_eod_token_for_early_termination:
+            expected = sum(known_done[s] for s in active) + N * (slots - len(active))      # frozen rows count as done
+            if int(st.n_done.item()) != expected:                                          # the step's host read: 4 bytes; the vector on a change
+                done_h = st.done.view(slots, N).ne(0).sum(dim=1).tolist()
+                for s in active:
+                    known_done[s] = done_h[s]
+        leaving = [s for s in active if known_done[s] == N or step_of[s] >= budgets[clip_of[s]]]
+        if leaving:
+            rows = (torch.as_tensor(leaving, dtype=torch.long).to(dev)[:, None] * N + within[None]).reshape(-1)
+            dst = (torch.as_tensor([clip_of[s] for s in leaving], dtype=torch.long).to(dev)[:, None] * N + within[None]).reshape(-1)
+            out_tokens[dst] = st.tokens[rows]
+            if sc is not None:
+                out_sc.live[dst], out_sc.sum_logprob[dst], out_sc.count[dst] = sc.live[rows], sc.sum_logprob[rows], sc.count[rows]
+                out_sc.token_logprob[dst] = sc.token_logprob[rows]
+            for s in leaving:
+                written[clip_of[s]] = lens[clip_of[s]] + step_of[s]
+                clip_of[s], step_of[s], known_done[s] = -1, -1, 0
+    return SimpleNamespace(tokens=out_tokens, written=written, scores=out_sc, steps=state.steps, prefills=state.prefills)
+
+
 def pad_after_termination(tokens: torch.Tensor, prompt_len, termination_id: int, width: int, fill: int) -> torch.Tensor:
     """tokens [R, n] (what sample_batched_loop returns) -> [R, width]: every row keeps its columns up to and including the first
     `termination_id` at or behind column `prompt_len`; what follows (tokens drawn while other rows were still running, and the
@@ -1040,6 +1267,21 @@ def install(gpt_cls):
                                    constrain_fn=ops.logits_constrain, **(dict(return_scores=True, score_fn=ops.sample_score) if return_scores else {}),
                                    **kw)
 
+    def sample_inflight(self, tokens, query_embeds=None, temperature=1.0, num_samples=1, slots=32, seed=0, streams=None, top_k=None, top_p=None,
+                        constraints=None, return_scores=False, decode_weights="bf16", max_new_tokens=None, refill_min=None, **kw):
+        """sample_batched(mixed_prompts=True, kv="shared_prefix") over a whole data set with the finished clips' slots refilled in
+        flight (sample_inflight_loop: continuous batching): tokens [n, L], prompt_length n lengths; `slots` clips x num_samples
+        sequences stay resident; max_new_tokens: a budget per clip (None: tokens_to_generate); top_k=1 is a greedy captioner.
+        -> a namespace: tokens [n * num_samples, final_len], written [n], scores (SampleScores or None), steps, prefills"""
+        cfg = _gen_config(self)
+        if top_k is not None or top_p is not None:
+            cfg.top_k, cfg.top_p = int(top_k or 0), float(top_p or 0.0)
+        return sample_inflight_loop(cfg, make_inflight_state_fn(self, decode_weights), tokens, query_embeds=query_embeds, temperature=temperature,
+                                    num_samples=num_samples, slots=slots, seed=seed, streams=streams, max_new_tokens=max_new_tokens,
+                                    refill_min=refill_min, advance_fn=ops.sample_advance_steps, constraints=constraints,
+                                    constrain_fn=ops.logits_constrain_steps,
+                                    **(dict(return_scores=True, score_fn=ops.sample_score_steps) if return_scores else {}), **kw)
+
     @torch.no_grad()
     def generate(self, tokens, do_sample=True, termination_id=None, *args, **kw):                # :1875-1880
         """sampler="device" (keyword; not in the reference, default "torch"): do_sample=True runs sample_batched, which takes
@@ -1071,3 +1313,4 @@ def install(gpt_cls):
 
     gpt_cls.sample, gpt_cls.beam_search, gpt_cls.generate = sample, beam_search, generate
     gpt_cls.beam_search_batched, gpt_cls.sample_batched = beam_search_batched, sample_batched
+    gpt_cls.sample_inflight = torch.no_grad()(sample_inflight)

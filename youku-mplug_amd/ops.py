@@ -372,7 +372,23 @@ def attn_decode_shared_ragged_fwd(q, k, v, pk, pv, o, lay: AttnLayout, prefix_la
                                group_prefix_len, True)
 
 
-def _attn_decode_shared(q, k, v, pk, pv, o, lay, prefix_lay, n_seq, group_size, heads, prefix_len, own_len, hd, scale, glen, ragged):
+def attn_decode_shared_steps_fwd(q, k, v, pk, pv, o, lay: AttnLayout, prefix_lay, n_seq, group_size, heads, prefix_len, group_prefix_len,
+                                 own_len, group_own_len, hd, *, scale=1.0):
+    """attn_decode_shared_ragged_fwd with an own length per group as well: group_own_len int32 [n_groups] on the device, every entry in
+    [0, own_len] (own_len is the upper bound; 0: the group is idle and its o rows become zeros).
+    include/mpv.h: mpv_attn_decode_shared_steps_fwd."""
+    n_groups = (n_seq + group_size - 1) // max(group_size, 1)
+    for name, t in (("group_prefix_len", group_prefix_len), ("group_own_len", group_own_len)):
+        if t is not None:
+            _need_cuda(t)
+            if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < n_groups:
+                raise ValueError(f"{name} must be a contiguous int32 tensor of {n_groups} lengths")
+    return _attn_decode_shared(q, k, v, pk, pv, o, lay, prefix_lay, n_seq, group_size, heads, prefix_len, own_len, hd, scale,
+                               group_prefix_len, True, group_own_len, True)
+
+
+def _attn_decode_shared(q, k, v, pk, pv, o, lay, prefix_lay, n_seq, group_size, heads, prefix_len, own_len, hd, scale, glen, ragged,
+                        gown=None, steps=False):
     _need_cuda(q, k, v, o, pk, pv)
     d = _lib.AttnDecodeSharedDesc()
     d.q, d.k, d.v, d.o, d.pk, d.pv = q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), pk.data_ptr(), pv.data_ptr()
@@ -383,7 +399,9 @@ def _attn_decode_shared(q, k, v, pk, pv, o, lay, prefix_lay, n_seq, group_size, 
     (d.pk_gs, d.pk_hs, d.pk_rs), (d.pv_gs, d.pv_hs, d.pv_rs) = prefix_lay
     d.n_seq, d.group_size, d.n_groups = n_seq, group_size, (n_seq + group_size - 1) // max(group_size, 1)
     d.heads, d.prefix_len, d.own_len, d.head_dim, d.scale = heads, prefix_len, own_len, hd, scale
-    if ragged:
+    if steps:
+        check(_lib.lib().mpv_attn_decode_shared_steps_fwd(C.byref(d), _p(glen), _p(gown), _stream()), "mpv_attn_decode_shared_steps_fwd")
+    elif ragged:
         check(_lib.lib().mpv_attn_decode_shared_ragged_fwd(C.byref(d), _p(glen), _stream()), "mpv_attn_decode_shared_ragged_fwd")
     else:
         check(_lib.lib().mpv_attn_decode_shared_fwd(C.byref(d), _stream()), "mpv_attn_decode_shared_fwd")
@@ -825,9 +843,11 @@ def sample_advance_desc(logits, st, *, pos, temperature=1.0, top_k=0, top_p=0.0,
 
 
 def _sample_advance(entry, logits, st, *, pos, temperature=1.0, top_k=0, top_p=0.0, seed=0, vocab_size=None, termination_mode=TERMINATION_ID,
-                    termination_id=0, u_override=None, out_kept=None, out_mass=None, out_token=None, vocab=None, ld=None):
-    """the body of sample_advance and sample_advance_ragged: `entry` is the C entry's name without the mpv_ prefix"""
+                    termination_id=0, u_override=None, out_kept=None, out_mass=None, out_token=None, vocab=None, ld=None, row_step=None):
+    """the body of sample_advance, sample_advance_ragged and sample_advance_steps (row_step: its extra argument): `entry` is the C
+    entry's name without the mpv_ prefix"""
     _need_cuda(logits, st.tokens, u_override, out_kept, out_mass, out_token)
+    more = _row_step_arg(entry, row_step, st.rows)
     if logits.dtype != torch.bfloat16 or logits.ndim != 2 or logits.shape[0] < st.rows or logits.stride(1) != 1:
         raise _lib.MpvError(f"{entry}: logits must be bf16 [{st.rows}, ld] with unit column stride (got {logits.dtype} {tuple(logits.shape)})")
     for name, t, dt in (("u_override", u_override, torch.float32), ("out_kept", out_kept, torch.int32), ("out_mass", out_mass, torch.float32),
@@ -837,8 +857,18 @@ def _sample_advance(entry, logits, st, *, pos, temperature=1.0, top_k=0, top_p=0
     d = sample_advance_desc(logits, st, pos=pos, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, vocab_size=vocab_size,
                             termination_mode=termination_mode, termination_id=termination_id, u_override=u_override, out_kept=out_kept,
                             out_mass=out_mass, out_token=out_token, vocab=vocab, ld=ld)
-    check(getattr(_lib.lib(), "mpv_" + entry)(C.byref(d), _stream()), "mpv_" + entry)
+    check(getattr(_lib.lib(), "mpv_" + entry)(C.byref(d), *more, _stream()), "mpv_" + entry)
     return st.next_tok
+
+
+def _row_step_arg(entry, row_step, rows):
+    """() for the uniform and ragged entries, (pointer,) for the _steps ones: row_step int32 [rows] on the device"""
+    if not entry.endswith("_steps"):
+        return ()
+    if row_step is None or row_step.dtype != torch.int32 or row_step.numel() != rows or not row_step.is_contiguous():
+        raise _lib.MpvError(f"{entry}: row_step must be a contiguous int32 tensor of {rows} steps")
+    _need_cuda(row_step)
+    return (_p(row_step),)
 
 
 def sample_advance(logits, st, *, pos, temperature=1.0, top_k=0, top_p=0.0, seed=0, vocab_size=None, termination_mode=TERMINATION_ID,
@@ -864,6 +894,16 @@ def sample_advance_ragged(logits, st, *, step, temperature=1.0, top_k=0, top_p=0
                            out_kept=out_kept, out_mass=out_mass, out_token=out_token, vocab=vocab, ld=ld)
 
 
+def sample_advance_steps(logits, st, *, row_step, temperature=1.0, top_k=0, top_p=0.0, seed=0, vocab_size=None, termination_mode=TERMINATION_ID,
+                         termination_id=0, u_override=None, out_kept=None, out_mass=None, out_token=None, vocab=None, ld=None):
+    """sample_advance_ragged with a generation step per row (include/mpv.h: mpv_sample_advance_steps; rows of clips that entered a
+    running loop at different times): row_step int32 [rows] on the device; row r draws at column st.prompt_len[r] + row_step[r].  A
+    row with a negative step, or whose column lies behind the table, is frozen.  -> st.next_tok"""
+    return _sample_advance("sample_advance_steps", logits, st, pos=0, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
+                           vocab_size=vocab_size, termination_mode=termination_mode, termination_id=termination_id, u_override=u_override,
+                           out_kept=out_kept, out_mass=out_mass, out_token=out_token, vocab=vocab, ld=ld, row_step=row_step)
+
+
 def _constraint_ids(constraints, device, eos_ids):
     """(eos, banned) int64 device arrays of a generation.LogitsConstraints, made once per (device, eos_ids) and kept on the object"""
     key = (str(device), tuple(int(t) for t in eos_ids))
@@ -874,8 +914,9 @@ def _constraint_ids(constraints, device, eos_ids):
     return hit
 
 
-def _logits_constrain(entry, logits, tokens, *, pos, constraints, prompt_len, prompt_len_all, eos_ids, ban_value, vocab, ld):
-    """the body of logits_constrain and logits_constrain_ragged: `entry` is the C entry's name without the mpv_ prefix"""
+def _logits_constrain(entry, logits, tokens, *, pos, constraints, prompt_len, prompt_len_all, eos_ids, ban_value, vocab, ld, row_step=None):
+    """the body of logits_constrain, logits_constrain_ragged and logits_constrain_steps (row_step: its extra argument): `entry` is the C
+    entry's name without the mpv_ prefix"""
     _need_cuda(logits, tokens, prompt_len)
     if logits.dtype != torch.bfloat16 or logits.ndim != 2 or logits.stride(1) != 1:
         raise _lib.MpvError(f"{entry}: logits must be bf16 [rows, ld] with unit column stride (got {logits.dtype} {tuple(logits.shape)})")
@@ -892,7 +933,7 @@ def _logits_constrain(entry, logits, tokens, *, pos, constraints, prompt_len, pr
     d.rows, d.vocab, d.row_len, d.pos = rows, int(vocab) if vocab is not None else logits.shape[-1], tokens.shape[1], int(pos)
     d.n_eos, d.n_banned, d.ngram, d.min_new_tokens = eos.numel(), banned.numel(), constraints.no_repeat_ngram_size, constraints.min_new_tokens
     d.include_prompt, d.penalty, d.ban_value = int(constraints.include_prompt), constraints.repetition_penalty, float(ban_value)
-    check(getattr(_lib.lib(), "mpv_" + entry)(C.byref(d), _stream()), "mpv_" + entry)
+    check(getattr(_lib.lib(), "mpv_" + entry)(C.byref(d), *_row_step_arg(entry, row_step, rows), _stream()), "mpv_" + entry)
     return logits
 
 
@@ -918,8 +959,19 @@ def logits_constrain_ragged(logits, tokens, *, step, constraints, prompt_len, eo
                              prompt_len_all=0, eos_ids=eos_ids, ban_value=ban_value, vocab=vocab, ld=ld)
 
 
-def _sample_score(entry, logits, st, sc, *, pos, vocab, ld):
-    """the body of sample_score and sample_score_ragged: `entry` is the C entry's name without the mpv_ prefix"""
+def logits_constrain_steps(logits, tokens, *, row_step, constraints, prompt_len, eos_ids=(), ban_value=float("-inf"), vocab=None, ld=None):
+    """logits_constrain_ragged with a generation step per row (include/mpv.h: mpv_logits_constrain_steps): row_step int32 [rows] on the
+    device; row r's history ends in front of column prompt_len[r] + row_step[r] and row_step[r] tokens count as generated.  A row with
+    a negative step, or whose column lies behind the table, is left alone.  -> logits"""
+    if prompt_len is None:
+        raise _lib.MpvError("logits_constrain_steps: prompt_len int64 [rows] is required")
+    return _logits_constrain("logits_constrain_steps", logits, tokens, pos=0, constraints=constraints, prompt_len=prompt_len,
+                             prompt_len_all=0, eos_ids=eos_ids, ban_value=ban_value, vocab=vocab, ld=ld, row_step=row_step)
+
+
+def _sample_score(entry, logits, st, sc, *, pos, vocab, ld, row_step=None):
+    """the body of sample_score, sample_score_ragged and sample_score_steps (row_step: its extra argument): `entry` is the C entry's
+    name without the mpv_ prefix"""
     _need_cuda(logits, st.tokens, sc.token_logprob)
     if logits.dtype != torch.bfloat16 or logits.ndim != 2 or logits.shape[0] < st.rows or logits.stride(1) != 1:
         raise _lib.MpvError(f"{entry}: logits must be bf16 [{st.rows}, ld] with unit column stride (got {logits.dtype} {tuple(logits.shape)})")
@@ -934,7 +986,7 @@ def _sample_score(entry, logits, st, sc, *, pos, vocab, ld):
     d.live, d.token_logprob, d.sum_logprob, d.count = _p(sc.live), _p(sc.token_logprob), _p(sc.sum_logprob), _p(sc.count)
     d.ld = int(ld) if ld is not None else logits.stride(0)
     d.rows, d.vocab, d.row_len, d.pos = st.rows, int(vocab) if vocab is not None else logits.shape[-1], st.row_len, int(pos)
-    check(getattr(_lib.lib(), "mpv_" + entry)(C.byref(d), _stream()), "mpv_" + entry)
+    check(getattr(_lib.lib(), "mpv_" + entry)(C.byref(d), *_row_step_arg(entry, row_step, st.rows), _stream()), "mpv_" + entry)
     return sc
 
 
@@ -952,6 +1004,12 @@ def sample_score_ragged(logits, st, sc, *, step, vocab=None, ld=None):
     token at its own column st.prompt_len[r] + step is scored into sc.token_logprob[r, that column].  Frozen rows (the column lies
     behind the table) and rows whose sc.live is 0 are skipped.  -> sc"""
     return _sample_score("sample_score_ragged", logits, st, sc, pos=step, vocab=vocab, ld=ld)
+
+
+def sample_score_steps(logits, st, sc, *, row_step, vocab=None, ld=None):
+    """sample_score right after sample_advance_steps (include/mpv.h: mpv_sample_score_steps): row r's token at its own column
+    st.prompt_len[r] + row_step[r] is scored.  Frozen rows and rows whose sc.live is 0 are skipped.  -> sc"""
+    return _sample_score("sample_score_steps", logits, st, sc, pos=0, vocab=vocab, ld=ld, row_step=row_step)
 
 
 def sample_tokens(logits, *, temperature=1.0, top_k=0, top_p=0.0, seed=0, streams=None, vocab_size=None, vocab=None):
