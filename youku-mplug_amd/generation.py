@@ -23,6 +23,7 @@ loops on e4m3 codes of the decoder's weights (DecodeWeightsQ8; mpv_gpt_decode_st
 """
 from __future__ import annotations
 
+import ctypes as C
 import dataclasses
 import math
 from types import SimpleNamespace
@@ -30,7 +31,7 @@ from typing import Callable, List, Optional
 
 import torch
 
-from . import ops
+from . import _lib, ops
 
 
 class BeamHypotheses:
@@ -71,6 +72,16 @@ def _check_weight_mode(weights):
         raise ValueError(f"decode_weights must be one of {WEIGHT_MODES} (got {weights!r})")
 
 
+def _is_scalar(x) -> bool:
+    """the arguments that are "one number, or one per clip / row": None, an int and a 0-dim tensor are scalars"""
+    return x is None or not hasattr(x, "__len__") or (torch.is_tensor(x) and x.dim() == 0)
+
+
+def _int_list(x):
+    """a sequence or tensor of numbers -> them as a list of ints (a tensor on the device is read); a scalar -> None"""
+    return None if _is_scalar(x) else [int(v) for v in (x.tolist() if torch.is_tensor(x) else x)]
+
+
 class DecodeWeightsQ8:
     """Weight-only FP8 copy of a frozen decoder for the decode steps (include/mpv.h, "FP8 decoder weights"): e4m3fn codes and one
     power-of-two fp32 scale per output row of every layer's qkv / dense / fc1 / fc2 weight and of the tied embedding (the LM head),
@@ -100,7 +111,6 @@ class DecodeWeightsQ8:
 
     def table(self):
         """-> (_lib.GptWeightsQ8, what it points into): the C table of the step entries"""
-        from . import _lib
         nl = len(self.tensors) // len(self.SITES)
         layers = (_lib.GptLayerWeightsQ8 * nl)()
         for i in range(nl):
@@ -123,8 +133,6 @@ class DecodeState:
     C ABI (mpv_gpt_decode_step issues every launch of the incremental forward; the step is launch-bound otherwise)."""
 
     def __init__(self, gpt, batch: int, max_len: int, weights: str = "bf16"):
-        import ctypes as C
-        from . import _lib
         _check_weight_mode(weights)
         cfg = gpt.config
         self.gpt, self.batch, self.max_len = gpt, batch, max_len
@@ -163,26 +171,36 @@ class DecodeState:
     def step(self, tokens: Optional[torch.Tensor], query_embeds: Optional[torch.Tensor] = None) -> torch.Tensor:
         """tokens [B, n_tok] int64, query_embeds [B, Q, H] for the first call.  Appends Q + n_tok positions per
         sequence and returns the logits of the last one: [B, V] bf16."""
-        import ctypes as C
-        from . import _lib
-        B, H = self.batch, self.H
-        qf = None if query_embeds is None else query_embeds.reshape(-1, H).to(torch.bfloat16).contiguous()
+        B = self.batch
+        qf, Q = self._query_rows(query_embeds)
         if query_embeds is not None and self.twin is not None:
             self._twin_shared = 0                    # a new visual prefix: the twin's copy of the shared positions is stale (reorder re-gathers from 0)
-        Q = 0 if qf is None else qf.shape[0] // B
         L = 0 if tokens is None else tokens.shape[1]
         ids = tokens.contiguous() if L else None
-        wsn = _lib.lib().mpv_gpt_decode_workspace_size(C.byref(self._w), B, Q + L)
-        ws = ops.workspace(wsn, self.cache.device)
-        logits = torch.empty((B, self.V), dtype=torch.bfloat16, device=self.cache.device)
-        tail = (self._cache_ptrs, B, self.max_len, self.pos, ops._p(qf), Q, ops._p(ids), L, ws.data_ptr(), ws.numel(), logits.data_ptr(),
-                ops._stream())
-        if self.q8 is None:
-            ops.check(_lib.lib().mpv_gpt_decode_step(C.byref(self._w), *tail), "mpv_gpt_decode_step")
-        else:
-            ops.check(_lib.lib().mpv_gpt_decode_step_q8(C.byref(self._w), C.byref(self._q8), *tail), "mpv_gpt_decode_step_q8")
+        ws, logits = self._scratch("mpv_gpt_decode_workspace_size", B, Q + L)
+        self._call("mpv_gpt_decode_step", self._cache_ptrs, B, self.max_len, self.pos, ops._p(qf), Q, ops._p(ids), L, ws.data_ptr(), ws.numel(),
+                   logits.data_ptr(), ops._stream())
         self.pos += Q + L
         return logits
+
+    def _call(self, name: str, *tail):
+        """The seam to the C step entries, also for the states built on a DecodeState: name(&weights, *tail), or, when the state holds
+        an FP8 table, name_q8(&weights, &fp8 table, *tail) -- every step entry of include/mpv.h has both forms with the same tail."""
+        head = (C.byref(self._w),)
+        if self.q8 is not None:
+            name, head = name + "_q8", head + (C.byref(self._q8),)
+        ops.check(getattr(_lib.lib(), name)(*head, *tail), name)
+
+    def _scratch(self, size_entry: str, rows: int, *more):
+        """-> (the workspace size_entry(&weights, rows, *more) asks for, logits [rows, V] bf16 to be written) for one _call"""
+        dev = self.cache.device
+        ws = ops.workspace(getattr(_lib.lib(), size_entry)(C.byref(self._w), rows, *more), dev)
+        return ws, torch.empty((rows, self.V), dtype=torch.bfloat16, device=dev)
+
+    def _query_rows(self, query_embeds):
+        """query_embeds [batch, Q, H] or None -> (the contiguous bf16 rows [batch * Q, H] or None, Q)"""
+        qf = None if query_embeds is None else query_embeds.reshape(-1, self.H).to(torch.bfloat16).contiguous()
+        return qf, 0 if qf is None else qf.shape[0] // self.batch
 
     def _ensure_twin(self):
         if self.twin is None:
@@ -244,7 +262,48 @@ class DecodeState:
         return sum(t.numel() * t.element_size() for t in (self.cache, self.twin) if t is not None)
 
 
-class SharedPrefixDecodeState:
+class _PrefixSuffixCaches:
+    """What SharedPrefixDecodeState and InflightDecodeState have in common: `prefix`, a DecodeState of one sequence per clip whose
+    cache [nl, clips * P, 3H] IS the prefix cache (it also carries the weight tables); `suffix` [nl, batch * S, 3H] for the positions
+    the batch = clips * fan sequences generate, with its pointer table; and the ONE call of the three shared-prefix step entries."""
+    prefix = suffix = twin = None
+
+    def _attach_suffix(self, prefix: "DecodeState", fan: int, P: int, S: int):
+        self.prefix, self.fan, self.P, self.S = prefix, fan, P, S
+        self.nl, self.H = prefix.nl, prefix.H
+        self.suffix = torch.zeros((prefix.nl, self.batch * S, 3 * prefix.H), dtype=torch.bfloat16, device=prefix.cache.device)
+        self._suffix_ptrs = prefix._ptrs(self.suffix)
+
+    def _layer_rows(self, per_layer: int) -> torch.Tensor:
+        """int64 [nl, 1]: the first of layer l's `per_layer` rows when all layers' rows are numbered through (a gather / scatter index base)"""
+        return torch.arange(self.nl, device=self.suffix.device, dtype=torch.int64)[:, None] * per_layer
+
+    def _step_call(self, tokens: torch.Tensor, group_t: Optional[torch.Tensor] = None, max_t: Optional[int] = None) -> torch.Tensor:
+        """tokens [batch, 1] int64 -> logits [batch, V] bf16 through ONE step entry, chosen by what the state and the caller hold:
+        (group_t, max_t) given -- a suffix position per clip (int32 [clips] on the device, negative: idle) and the largest of them:
+        mpv_gpt_decode_step_shared_steps; else a group_prefix_len (a prefix length per clip): mpv_gpt_decode_step_shared_ragged at the
+        suffix position self.t; else mpv_gpt_decode_step_shared at self.t.  With prefix lengths both prefix_stride and max_prefix_len
+        are P: the pitch of a clip's prefix rows is the longest prefix."""
+        st = self.prefix
+        steps = group_t is not None
+        ws, logits = st._scratch("mpv_gpt_decode_shared_steps_workspace_size" if steps else "mpv_gpt_decode_shared_workspace_size", self.batch)
+        caches = (st._cache_ptrs, self._suffix_ptrs, self.batch // self.fan, self.fan, self.P)
+        io = (tokens.data_ptr(), ws.data_ptr(), ws.numel(), logits.data_ptr(), ops._stream())
+        if steps:
+            st._call("mpv_gpt_decode_step_shared_steps", *caches, self.group_prefix_len.data_ptr(), self.P, self.S, group_t.data_ptr(), max_t, *io)
+        elif self.group_prefix_len is not None:
+            st._call("mpv_gpt_decode_step_shared_ragged", *caches, self.group_prefix_len.data_ptr(), self.P, self.S, self.t, *io)
+        else:
+            st._call("mpv_gpt_decode_step_shared", *caches, self.S, self.t, *io)
+        return logits
+
+    def kv_bytes(self) -> int:
+        """bytes of the prefix, suffix and twin allocations that exist"""
+        return sum(t.numel() * t.element_size() for t in (None if self.prefix is None else self.prefix.cache, self.suffix, self.twin)
+                   if t is not None)
+
+
+class SharedPrefixDecodeState(_PrefixSuffixCaches):
     """DecodeState for the lockstep loops with the prefix every sequence of a clip shares stored ONCE per clip: a prefix cache
     [nl, G * P, 3H] (P = Q + prompt positions; it is the cache of a DecodeState of batch G and max_len P, filled by the ordinary
     prefill) and a suffix cache [nl, batch * S, 3H] (S = max_len - P) for the positions the sequences generate.  A step is ONE
@@ -260,9 +319,7 @@ class SharedPrefixDecodeState:
     def __init__(self, gpt, batch: int, max_len: int, weights: str = "bf16"):
         _check_weight_mode(weights)
         self.gpt, self.batch, self.max_len, self.weights = gpt, batch, max_len, weights
-        self.prefix = None                    # the DecodeState of the prefill: its cache is the prefix cache
-        self.suffix = self.twin = None
-        self.fan = self.P = self.S = 0
+        self.fan = self.P = self.S = 0        # set, with prefix (the DecodeState of the prefill) and suffix, by prefill_fan_out
         self.t = 0                            # suffix rows cached so far (per sequence)
         self.group_prefix_len = None          # ragged: int32 [G] on the device, Q + prompt_len
 
@@ -274,8 +331,8 @@ class SharedPrefixDecodeState:
                         prompt_len: Optional[torch.Tensor] = None) -> torch.Tensor:
         """tokens [G, n_tok] / query_embeds [G, Q, H], G = batch // fan: the prefill runs once per clip into the prefix cache and
         nothing is copied.  -> logits [batch, V]: row j is clip j // fan's.
-        prompt_len (int64 [G], 1 <= prompt_len[g] <= n_tok; default None: every prompt is n_tok long, today's calls): clip g's prompt
-        is tokens[g, :prompt_len[g]], the rest of its row padding; the logits are those of each clip's own last prompt row."""
+        prompt_len (G lengths, 1 <= prompt_len[g] <= n_tok; default None: every prompt is n_tok long): clip g's prompt is
+        tokens[g, :prompt_len[g]], the rest of its row padding; the logits are those of each clip's own last prompt row."""
         assert self.prefix is None and fan >= 1 and self.batch % fan == 0, (self.batch, fan)
         G = self.batch // fan
         assert (tokens is None or tokens.shape[0] == G) and (query_embeds is None or query_embeds.shape[0] == G)
@@ -287,38 +344,26 @@ class SharedPrefixDecodeState:
             logits = self.prefix.step(tokens, query_embeds)
         else:
             logits = self._ragged_prefill(tokens, query_embeds, prompt_len)
-        self.fan, self.P, self.S = fan, P, self.max_len - P
-        st = self.prefix
-        self.nl, self.H = st.nl, st.H
-        self.suffix = torch.zeros((st.nl, self.batch * self.S, 3 * st.H), dtype=torch.bfloat16, device=st.cache.device)
-        self._suffix_ptrs = st._ptrs(self.suffix)
+        self._attach_suffix(self.prefix, fan, P, self.max_len - P)
         return logits.repeat_interleave(fan, dim=0)
 
     def _ragged_prefill(self, tokens, query_embeds, prompt_len) -> torch.Tensor:
-        import ctypes as C
-        from . import _lib
         st = self.prefix
-        G, H, dev = st.batch, st.H, st.cache.device
+        G, dev = st.batch, st.cache.device
         if tokens is None or tokens.dim() != 2:
             raise ValueError("prefill_fan_out(prompt_len=...) needs the right-padded prompts: tokens [G, n_tok]")
         L = tokens.shape[1]
-        lens = [int(x) for x in (prompt_len.tolist() if torch.is_tensor(prompt_len) else prompt_len)]   # host values: the caller's
-        if len(lens) != G or min(lens) < 1 or max(lens) > L:
+        lens = _int_list(prompt_len)                 # host values: the caller's
+        if lens is None or len(lens) != G or min(lens) < 1 or max(lens) > L:
             raise ValueError(f"prompt_len must hold {G} lengths in [1, {L}] (got {lens})")
-        qf = None if query_embeds is None else query_embeds.reshape(-1, H).to(torch.bfloat16).contiguous()
-        Q = 0 if qf is None else qf.shape[0] // G
+        qf, Q = st._query_rows(query_embeds)
         plen = torch.as_tensor(lens, dtype=torch.int64).to(dev)
         self.group_prefix_len = (plen + Q).to(torch.int32)
         last_row = (plen + (Q - 1)).contiguous()
         ids = tokens.contiguous()
-        ws = ops.workspace(_lib.lib().mpv_gpt_decode_workspace_size(C.byref(st._w), G, Q + L), dev)
-        logits = torch.empty((G, st.V), dtype=torch.bfloat16, device=dev)
-        tail = (st._cache_ptrs, G, st.max_len, ops._p(qf), Q, ids.data_ptr(), L, last_row.data_ptr(), ws.data_ptr(), ws.numel(),
-                logits.data_ptr(), ops._stream())
-        if st.q8 is None:
-            ops.check(_lib.lib().mpv_gpt_prefill_ragged(C.byref(st._w), *tail), "mpv_gpt_prefill_ragged")
-        else:
-            ops.check(_lib.lib().mpv_gpt_prefill_ragged_q8(C.byref(st._w), C.byref(st._q8), *tail), "mpv_gpt_prefill_ragged_q8")
+        ws, logits = st._scratch("mpv_gpt_decode_workspace_size", G, Q + L)
+        st._call("mpv_gpt_prefill_ragged", st._cache_ptrs, G, st.max_len, ops._p(qf), Q, ids.data_ptr(), L, last_row.data_ptr(), ws.data_ptr(),
+                 ws.numel(), logits.data_ptr(), ops._stream())
         st.pos += Q + L
         return logits
 
@@ -337,26 +382,7 @@ class SharedPrefixDecodeState:
         return logits
 
     def _shared_step(self, tokens: torch.Tensor) -> torch.Tensor:
-        import ctypes as C
-        from . import _lib
-        st, dev = self.prefix, self.suffix.device
-        wsn = _lib.lib().mpv_gpt_decode_shared_workspace_size(C.byref(st._w), self.batch)
-        ws = ops.workspace(wsn, dev)
-        logits = torch.empty((self.batch, st.V), dtype=torch.bfloat16, device=dev)
-        tail = (st._cache_ptrs, self._suffix_ptrs, self.batch // self.fan, self.fan, self.P, self.S, self.t, tokens.data_ptr(), ws.data_ptr(),
-                ws.numel(), logits.data_ptr(), ops._stream())
-        if self.group_prefix_len is not None:        # prefix_stride = max_prefix_len = P: the pitch is the longest prefix
-            tail = tail[:5] + (self.group_prefix_len.data_ptr(),) + tail[4:]
-            if st.q8 is None:
-                ops.check(_lib.lib().mpv_gpt_decode_step_shared_ragged(C.byref(st._w), *tail), "mpv_gpt_decode_step_shared_ragged")
-            else:
-                ops.check(_lib.lib().mpv_gpt_decode_step_shared_ragged_q8(C.byref(st._w), C.byref(st._q8), *tail),
-                          "mpv_gpt_decode_step_shared_ragged_q8")
-        elif st.q8 is None:
-            ops.check(_lib.lib().mpv_gpt_decode_step_shared(C.byref(st._w), *tail), "mpv_gpt_decode_step_shared")
-        else:
-            ops.check(_lib.lib().mpv_gpt_decode_step_shared_q8(C.byref(st._w), C.byref(st._q8), *tail), "mpv_gpt_decode_step_shared_q8")
-        return logits
+        return self._step_call(tokens)
 
     def reorder(self, batch_idx: torch.Tensor, shared_prefix: Optional[int] = None):
         """sequence j continues from the suffix rows of sequence batch_idx[j] (which must belong to the same clip): one strided
@@ -371,20 +397,15 @@ class SharedPrefixDecodeState:
         if self.twin is None:
             self.twin = torch.empty_like(self.suffix)
             self._twin_ptrs = self.prefix._ptrs(self.twin)
-            self._layer_base = torch.arange(self.nl, device=self.suffix.device, dtype=torch.int64)[:, None] * self.batch
+            self._layer_base = self._layer_rows(self.batch)
         idx = (self._layer_base + batch_idx.to(torch.int64)[None]).reshape(-1)
         pitch = self.S * 3 * self.H
         ops.gather_rows_ld(self.suffix.view(-1), idx, self.twin.view(-1), self.nl * self.batch, self.t * 3 * self.H, pitch, pitch)
         self.suffix, self.twin = self.twin, self.suffix
         self._suffix_ptrs, self._twin_ptrs = self._twin_ptrs, self._suffix_ptrs
 
-    def kv_bytes(self) -> int:
-        """bytes of the prefix, suffix and twin allocations"""
-        return sum(t.numel() * t.element_size() for t in (None if self.prefix is None else self.prefix.cache, self.suffix, self.twin)
-                   if t is not None)
 
-
-class InflightDecodeState:
+class InflightDecodeState(_PrefixSuffixCaches):
     """The shared-prefix state of sample_inflight_loop: `slots` clips x `fan` sequences stay resident and a finished clip's slot is
     given to the next clip while the others go on.  The prefix cache is [nl, slots * P, 3H] with P = Q + the longest prompt of the
     whole call (it is the cache of a DecodeState of batch `slots`, which also carries the weight tables), group_prefix_len int32
@@ -397,15 +418,11 @@ class InflightDecodeState:
         _check_weight_mode(weights)
         if slots < 1 or fan < 1 or prefix_rows < 1 or suffix_rows < 1:
             raise ValueError(f"InflightDecodeState: slots {slots}, fan {fan}, prefix rows {prefix_rows} and suffix rows {suffix_rows} must be positive")
-        self.gpt, self.slots, self.fan, self.P, self.S, self.weights = gpt, int(slots), int(fan), int(prefix_rows), int(suffix_rows), weights
-        self.batch = self.slots * self.fan
-        self.prefix = st = DecodeState(gpt, self.slots, self.P, weights)
-        self.nl, self.H = st.nl, st.H
-        dev = st.cache.device
-        self.suffix = torch.zeros((st.nl, self.batch * self.S, 3 * st.H), dtype=torch.bfloat16, device=dev)
-        self._suffix_ptrs = st._ptrs(self.suffix)
-        self.group_prefix_len = torch.ones(self.slots, dtype=torch.int32, device=dev)       # a free slot: one (zero) prefix row, never used
-        self._layer_base = torch.arange(st.nl, device=dev, dtype=torch.int64)[:, None] * self.slots
+        self.gpt, self.slots, self.weights = gpt, int(slots), weights
+        self.batch = self.slots * int(fan)
+        self._attach_suffix(DecodeState(gpt, self.slots, int(prefix_rows), weights), int(fan), int(prefix_rows), int(suffix_rows))
+        self.group_prefix_len = torch.ones(self.slots, dtype=torch.int32, device=self.suffix.device)   # a free slot: one (zero) prefix row, never used
+        self._layer_base = self._layer_rows(self.slots)
         self.prefills = self.steps = 0            # launches issued so far (the loop's report)
 
     def install(self, slot_ids, tokens: torch.Tensor, query_embeds: Optional[torch.Tensor], prompt_len) -> torch.Tensor:
@@ -441,23 +458,7 @@ class InflightDecodeState:
         return self._steps_step(tokens.contiguous(), group_t, int(max_t))
 
     def _steps_step(self, tokens, group_t, max_t) -> torch.Tensor:
-        import ctypes as C
-        from . import _lib
-        st, dev = self.prefix, self.suffix.device
-        ws = ops.workspace(_lib.lib().mpv_gpt_decode_shared_steps_workspace_size(C.byref(st._w), self.batch), dev)
-        logits = torch.empty((self.batch, st.V), dtype=torch.bfloat16, device=dev)
-        tail = (st._cache_ptrs, self._suffix_ptrs, self.slots, self.fan, self.P, self.group_prefix_len.data_ptr(), self.P, self.S,
-                group_t.data_ptr(), max_t, tokens.data_ptr(), ws.data_ptr(), ws.numel(), logits.data_ptr(), ops._stream())
-        if st.q8 is None:
-            ops.check(_lib.lib().mpv_gpt_decode_step_shared_steps(C.byref(st._w), *tail), "mpv_gpt_decode_step_shared_steps")
-        else:
-            ops.check(_lib.lib().mpv_gpt_decode_step_shared_steps_q8(C.byref(st._w), C.byref(st._q8), *tail),
-                      "mpv_gpt_decode_step_shared_steps_q8")
-        return logits
-
-    def kv_bytes(self) -> int:
-        """bytes of the prefix and suffix allocations"""
-        return sum(t.numel() * t.element_size() for t in (self.prefix.cache, self.suffix))
+        return self._step_call(tokens, group_t, max_t)
 
 
 def make_inflight_state_fn(gpt, weights: str = "bf16"):
@@ -645,53 +646,40 @@ def beam_search_batched_loop(cfg, make_state: Callable[[int, int], object], toke
                              num_return_gen=1, stop_token=None, prompt_length: Optional[int] = None, topk_fn=None, advance_fn=None,
                              constraints: Optional["LogitsConstraints"] = None, constrain_fn=None, return_scores=False, beam_groups=1,
                              diversity_penalty=0.0, group_advance_fn=None):
-    """beam_search_loop for B clips in lockstep: tokens [B, L], query_embeds [B, Q, H], ONE prompt length for all clips of the call.
-    Every decode step advances B x beam_size sequences, so the decoder's weights are read once per generated position instead of
-    once per clip and position, the prefill runs once per clip (state.prefill_fan_out) and the bookkeeping of a step is one kernel.
-    A step issues state.step, topk_fn(logits, 2 * beam_size, scores), advance_fn (ops.beam_advance: per clip what one iteration of
-    beam_search_loop does; it fills bs.src_row / bs.next_tok and swaps the token tables) and state.reorder(src_row, shared_prefix);
-    nothing goes to the host except the read that tells whether every clip is done.
-    Finished clips are NOT compacted away: a clip that is done is frozen by advance_fn and keeps stepping as padding rows (stop
-    token, identity re-order) until every clip is done or the length is exhausted.
-    After the loop the state is downloaded once; the final flush of the unfinished clips and the stable ranking run on the host
-    through BeamHypotheses, as in beam_search_loop.  -> a list of B namespaces (sequences [n, Lt], scores [n]), clip by clip what
-    beam_search_loop returns for it.  `make_state(batch, max_len)` -> an object with prefill_fan_out / step / reorder
-    (DecodeState); make_state, topk_fn and advance_fn are injectable as in beam_search_loop.
+    """Beam search for B clips in lockstep, the search state on the device: tokens [B, L], query_embeds [B, Q, H].  Every decode step
+    advances all the clips' beams, so the decoder's weights are read once per generated position instead of once per clip and
+    position, the prefill runs once per clip and the bookkeeping of a step is one kernel.  `make_state(batch, max_len)` -> an object
+    with prefill_fan_out / step / reorder (DecodeState, SharedPrefixDecodeState); make_state and the *_fn are injectable as in
+    beam_search_loop, and return_scores=True is refused as there.
+    A step issues state.prefill_fan_out(prompts, query_embeds, fan) (the first) or state.step(bs.next_tok); constrain_fn; topk_fn(logits,
+    m, bs.scores); the advance (per clip what one iteration of beam_search_loop does; it fills bs.src_row / bs.next_tok and swaps the
+    token tables); the read that tells whether every clip is done -- nothing else goes to the host --; state.reorder(bs.src_row,
+    shared_prefix=Q + prompt).  Finished clips are NOT compacted away: a clip that is done is frozen by the advance and keeps stepping
+    as padding rows (stop token, identity re-order) until every clip is done or the length is exhausted.  After the loop the state is
+    downloaded once; the final flush of the unfinished clips and the stable ranking run on the host (_ranked_hypotheses).
     `constraints` (a LogitsConstraints; None or inactive: no call and no launch is added): before topk_fn every step edits the raw
-    logits of all B x beam_size rows -- the first step's and those of frozen clips too, which advance_fn ignores -- through
-    constrain_fn (ops.logits_constrain) on the beams' token table, with the stop token as the termination id of min_new_tokens and
-    the lowest finite bf16 as the ban value (include/mpv.h says why it is not -inf here).
-    return_scores=True is refused, as in beam_search_loop.
-    beam_groups = G > 1 (default 1: the calls above with exactly those keywords, group_advance_fn untouched, no `group` in the result):
-    diverse (group) beam search in the same loop.  beam_size is then K', the beams PER GROUP; the state holds B x G x K' sequences, a
-    (clip, group) pair being a clip of the BeamState; the prefill fans out to G * K'; a step asks topk_fn for m = 2K' + (G-1)K'
-    candidates per row and calls group_advance_fn in advance_fn's place, with groups= and diversity_penalty= added
-    (ops.beam_advance_groups: per clip, group after group, one iteration on the values lowered by diversity_penalty times the number
-    of next beams that the groups before chose with the candidate's token at this step).  The re-order stays inside the (clip,
-    group), so both KV states work as they are.  The host finish runs per (clip, group): -> per clip a namespace (sequences [n, Lt],
-    scores [n], group [n] int64), group 0's best r = num_return_gen // G rows first, then group 1's, ...; a group with fewer
-    hypotheses yields fewer rows.  From the second group on the scores are penalised search scores, not model likelihoods.
-    num_return_gen must be a multiple of G with r <= K'.
-    prompt_length = a sequence of B lengths (an int, or None: everything above, call for call): the MIXED mode, ONE lockstep search
-    over clips whose prompts differ in length; clip c's prompt is tokens[c, :prompt_length[c]].  make_state's state must take
-    prefill_fan_out(..., prompt_len=) (SharedPrefixDecodeState: it gets the prompts right-padded with the stop token, and the
-    lengths); a DecodeState does not.  The beams' token table is LEFT-padded with the stop token so that every prompt ends at column
-    P_max = max(prompt_length): topk_fn, advance / group_advance_fn and constrain_fn run unchanged with prompt_len_all = P_max and
-    pos = P_max + n, so a generated token sits n columns behind every clip's prompt.  Budget: clip c generates at most final_len -
-    prompt_length[c] positions, as a search over clips of its own length would; the loop runs until the shortest prompt's budget
-    ends.  The host knows at which step a longer prompt's budget ends: there it sets the clip's bs.done on the device (advance then
-    freezes it: tokens and scores stay, include/mpv.h mpv_beam_advance) after saving which of these clips were not done -- no host
-    read is added -- and the finish flushes the beams of exactly those, as it does for a clip the loop's end leaves unfinished.
-    All sequences step until then, the frozen ones as padding rows, so Q + P_max + final_len - P_min - 2 must be a row of the position
-    table (a ValueError before the first launch otherwise).
-    Row length: advance scores a hypothesis by value / row_len and tests worst >= best / cur_len, so the search depends on the
-    table's width.  The padded table is 2 * Lt wide (Lt = L + tokens_to_generate, the width of the uniform table; P_max - P_min +
-    final_len <= 2 * Lt always) and cur_len is 2 * (n + 1): both sides of every comparison are then exactly half of what the Lt-wide
-    table gives (a division by two is exact), so the clip's search is step for step the one of the uniform loop over clips of its
-    length, and the stored scores are doubled -- exactly -- at the finish.  2 * Lt must fit the advance kernels' 2048 columns.
-    Returned rows: left padding stripped, Lt wide like the uniform loop's (behind the generated tokens they hold what that loop's
-    rows hold: the rest of the clip's input row, then the stop token).  LogitsConstraints(include_prompt=True) is refused: the pad
-    columns would count as prompt."""
+    logits of all rows -- the first step's and those of frozen clips too, which the advance ignores -- through constrain_fn
+    (ops.logits_constrain) on the beams' token table, with the stop token as the termination id of min_new_tokens and the lowest
+    finite bf16 as the ban value (include/mpv.h says why it is not -inf here).
+    One prompt length, one group (prompt_length an int or None, beam_groups 1): fan = beam_size, m = 2 * beam_size, the advance is
+    advance_fn (ops.beam_advance) with pos = prompt + n and cur_len = n + 1.  -> a list of B namespaces (sequences [n, Lt], scores
+    [n]), clip by clip what beam_search_loop returns for it.
+    beam_groups = G > 1: diverse (group) beam search.  beam_size is then K', the beams PER GROUP; the state holds B x G x K'
+    sequences, a (clip, group) pair being a clip of the BeamState; fan = G * K'; m = 2K' + (G-1)K'; the advance is group_advance_fn
+    with groups= and diversity_penalty= added (ops.beam_advance_groups: per clip, group after group, one iteration on the values
+    lowered by diversity_penalty times the number of next beams that the groups before chose with the candidate's token at this
+    step).  The re-order stays inside the (clip, group), so both KV states work as they are.  The host finish runs per (clip, group):
+    -> per clip a namespace (sequences [n, Lt], scores [n], group [n] int64), group 0's best r = num_return_gen // G rows first, then
+    group 1's, ...; a group with fewer hypotheses yields fewer rows.  From the second group on the scores are penalised search scores,
+    not model likelihoods.  num_return_gen must be a multiple of G with r <= K'.
+    prompt_length = a sequence of B lengths (either number of groups): ONE search over clips whose prompts differ in length; clip c's
+    prompt is tokens[c, :prompt_length[c]].  The state gets the prompts right-padded and the lengths (prefill_fan_out(..., prompt_len=):
+    SharedPrefixDecodeState; a DecodeState is refused); the beams' table is the left-padded one of _left_padded_table, which says why
+    cur_len = 2 * (n + 1) then reproduces each clip's own search exactly; pos = P_max + n.  The loop runs until the shortest prompt's
+    budget ends; where a longer prompt's budget ends the host sets the clip's bs.done on the device (the advance then freezes it:
+    tokens and scores stay, include/mpv.h mpv_beam_advance) after saving which of these clips were not done -- no host read is added
+    -- and _strip_left_padding flushes the beams of exactly those.  Raised before the first launch: include_prompt=True constraints
+    (the pad columns would count as prompt), 2 * Lt > 2048 columns (the advance kernels' limit), what _mixed_prompt_state refuses."""
     _no_sample_scores(return_scores, "beam_search_batched_loop")
     B, dev, K = tokens.size(0), tokens.device, int(beam_size)
     G = int(beam_groups)
@@ -710,50 +698,29 @@ def beam_search_batched_loop(cfg, make_state: Callable[[int, int], object], toke
     else:
         advance, more, per_group = advance_fn, {}, num_return_gen
     constraints = _active_constraints(constraints, constrain_fn)
-    lens = _mixed_prompt_lengths(prompt_length, B, tokens.size(1))                         # None: one prompt length, today's path
+    lens = _mixed_prompt_lengths(prompt_length, B, tokens.size(1))                         # None: one prompt length
     stop_token = cfg.eod_id if stop_token is None else int(stop_token)
     if lens is None:
         prompt_length = int(prompt_length) if prompt_length is not None else tokens.size(1)
         tokens, final_len, Q = _pad_for_generation(cfg, tokens, stop_token, prompt_length, query_embeds)
-        state = make_state(B * G * K, final_len + Q)
-        table, total_final, len_scale = tokens, final_len + Q, 1
+        state, total_final = make_state(B * G * K, final_len + Q), final_len + Q
+        table, prompts, prefill_more, ends, len_scale = tokens, tokens[:, :prompt_length], {}, {}, 1
     else:
         if constraints is not None and constraints.include_prompt:
             raise ValueError("LogitsConstraints(include_prompt=True) does not combine with prompts of different lengths: the "
                              "left padding of the token table would count as prompt")
-        prompt_length, shortest = max(lens), min(lens)
+        prompt_length = max(lens)
         tokens, final_len, Q = _pad_for_generation(cfg, tokens, stop_token, prompt_length, query_embeds)
-        Lt, len_scale = tokens.size(1), 2
-        if len_scale * Lt > 2048:
-            raise ValueError(f"prompts of different lengths need a token table of {len_scale * Lt} columns; the advance kernels take 2048")
-        total_final = Q + prompt_length + final_len - shortest
-        if total_final - 2 >= cfg.max_position_embeddings:        # the last step's position of the longest prefix (frozen by then, but fed)
-            raise ValueError(f"prompts of {shortest} .. {prompt_length} tokens behind {Q} query slots step up to position {total_final - 2}; "
-                             f"the position table has {cfg.max_position_embeddings} rows")
-        state = make_state(B * G * K, total_final)
-        if not _takes_prompt_len(state):
-            raise ValueError('prompts of different lengths need a state with prefill_fan_out(..., prompt_len=): kv="shared_prefix" '
-                             f"(got a {type(state).__name__})")
-        lens_d = torch.as_tensor(lens, dtype=torch.long).to(dev)
-        left = prompt_length - lens_d                                                      # clip c's columns start at left[c]
-        src = torch.arange(len_scale * Lt, device=dev)[None] - left[:, None]
-        table = torch.where((src >= 0) & (src < Lt), tokens.gather(1, src.clamp(0, Lt - 1)), torch.full_like(src, stop_token))
-        prompts = torch.where(torch.arange(prompt_length, device=dev)[None] < lens_d[:, None], tokens[:, :prompt_length],
-                              torch.full_like(tokens[:, :prompt_length], stop_token))
-        # the step after which a clip's budget ends -> its pseudo-clips (the shortest prompts end with the loop itself)
-        ends = {}
-        for c, pl in enumerate(lens):
-            if pl != shortest:
-                ends.setdefault(final_len - pl, []).extend(range(c * G, (c + 1) * G))
-        ends = {k: torch.as_tensor(v, dtype=torch.long).to(dev) for k, v in ends.items()}
-        flush = torch.zeros(B * G, dtype=torch.int32, device=dev)                          # budget ended before the clip was done
+        if 2 * tokens.size(1) > 2048:
+            raise ValueError(f"prompts of different lengths need a token table of {2 * tokens.size(1)} columns; the advance kernels take 2048")
+        state, total_final = _mixed_prompt_state(cfg, make_state, B * G * K, Q, lens, final_len, "prompts of different lengths need")
+        table, prompts, ends, flush, len_scale = _left_padded_table(tokens, lens, G, stop_token, final_len)
+        prefill_more = dict(prompt_len=lens)
     bs = BeamState(table if G == 1 else table.repeat_interleave(G, 0), K)                  # pseudo-clip b * G + g: group g of clip b
     total_prompt, m = prompt_length + Q, 2 * K + (G - 1) * K
     for n, context_length in enumerate(range(total_prompt, total_final)):
-        if n == 0 and lens is not None:
-            logits = state.prefill_fan_out(prompts.contiguous(), query_embeds, G * K, prompt_len=lens)
-        elif n == 0:
-            logits = state.prefill_fan_out(tokens[:, :prompt_length].contiguous(), query_embeds, G * K)
+        if n == 0:
+            logits = state.prefill_fan_out(prompts.contiguous(), query_embeds, G * K, **prefill_more)
         else:
             logits = state.step(bs.next_tok.view(-1, 1))
         if constraints is not None:
@@ -762,18 +729,15 @@ def beam_search_batched_loop(cfg, make_state: Callable[[int, int], object], toke
         vals, idxs = topk_fn(logits, m, bs.scores.view(-1))                                  # log_softmax + scores (:1790-1791)
         advance(vals, idxs, bs, vocab=logits.size(-1), pos=context_length - Q, cur_len=len_scale * (n + 1), first=n == 0,
                 stop_token=stop_token, **more)
-        if lens is not None and n + 1 in ends:                                               # these clips' budgets end here: freeze them
+        if n + 1 in ends:                                                                    # these clips' budgets end here: freeze them
             flush[ends[n + 1]] = 1 - bs.done[ends[n + 1]]
             bs.done[ends[n + 1]] = 1
         if bool(bs.done.all()):                                                              # the step's one host read
             break
         state.reorder(bs.src_row, shared_prefix=total_prompt)
     h = SimpleNamespace(**{k: getattr(bs, k).cpu() for k in BeamState.ARRAYS})              # one download
-    if lens is not None:                       # the uniform loop's view of every clip: its Lt columns, scores over Lt, budget flushes
-        flush, cols = flush.cpu(), (torch.arange(Lt)[None] + (prompt_length - torch.as_tensor(lens))[:, None]).repeat_interleave(G, 0)
-        h.tokens = h.tokens.gather(2, cols[:, None, :].expand(-1, K, -1))
-        h.hyp_tokens = h.hyp_tokens.gather(2, cols[:, None, :].expand(-1, K, -1))
-        h.hyp_score, h.worst, h.done = h.hyp_score * len_scale, h.worst * len_scale, h.done * (1 - flush)
+    if lens is not None:
+        _strip_left_padding(h, lens, flush, len_scale)
     out = []
     for clip in range(B):
         ranked = [_ranked_hypotheses(h, clip * G + g, K)[:per_group] for g in range(G)]
@@ -785,15 +749,73 @@ def beam_search_batched_loop(cfg, make_state: Callable[[int, int], object], toke
     return out
 
 
-def _mixed_prompt_lengths(prompt_length, B, L):
-    """beam_search_batched_loop's prompt_length: None or an int -> None (one prompt length); a sequence or tensor of B lengths -> them
-    as a list of ints in [1, L]"""
-    if prompt_length is None or not hasattr(prompt_length, "__len__") or (torch.is_tensor(prompt_length) and prompt_length.dim() == 0):
-        return None
-    lens = [int(x) for x in (prompt_length.tolist() if torch.is_tensor(prompt_length) else prompt_length)]
-    if len(lens) != B or min(lens) < 1 or max(lens) > L:
+def _left_padded_table(tokens, lens, G, stop_token, final_len):
+    """The token table of the lockstep beam search over prompts of `lens` tokens (tokens [B, Lt]: the padded input rows; G groups per
+    clip) -> (table [B, 2 * Lt], prompts [B, P_max], ends, flush, len_scale = 2).
+    The table is LEFT-padded with the stop token so that every prompt ends at column P_max = max(lens): topk_fn, the advance and
+    constrain_fn then run as for one prompt length, with prompt_len_all = P_max and pos = P_max + n, and a generated token sits n
+    columns behind every clip's prompt.  `prompts` are the prompts RIGHT-padded with the stop token, what the ragged prefill takes.
+    Row length: the advance scores a hypothesis by value / row_len and tests worst >= best / cur_len, so the search depends on the
+    table's width.  The padded table is 2 * Lt wide (Lt = L + tokens_to_generate, the width of the table of one prompt length;
+    P_max - P_min + final_len <= 2 * Lt always) and the loop passes cur_len = len_scale * (n + 1): both sides of every comparison are
+    then exactly half of what the Lt-wide table gives (a division by two is exact), so a clip's search is step for step the one of a
+    loop over clips of its own length, and the stored scores are doubled -- exactly -- by _strip_left_padding.
+    Budget: clip c generates at most final_len - lens[c] positions, as a search over clips of its length would: ends[step] holds the
+    pseudo-clips (clip * G + group) to freeze after that step, and the loop notes in flush (int32 [B * G]) which were not done."""
+    B, Lt, dev = tokens.size(0), tokens.size(1), tokens.device
+    longest, shortest = max(lens), min(lens)
+    lens_d = torch.as_tensor(lens, dtype=torch.long).to(dev)
+    left = longest - lens_d                                                                # clip c's columns start at left[c]
+    src = torch.arange(2 * Lt, device=dev)[None] - left[:, None]
+    table = torch.where((src >= 0) & (src < Lt), tokens.gather(1, src.clamp(0, Lt - 1)), torch.full_like(src, stop_token))
+    prompts = torch.where(torch.arange(longest, device=dev)[None] < lens_d[:, None], tokens[:, :longest],
+                          torch.full_like(tokens[:, :longest], stop_token))
+    ends = {}
+    for c, pl in enumerate(lens):
+        if pl != shortest:
+            ends.setdefault(final_len - pl, []).extend(range(c * G, (c + 1) * G))
+    ends = {k: torch.as_tensor(v, dtype=torch.long).to(dev) for k, v in ends.items()}
+    return table, prompts, ends, torch.zeros(B * G, dtype=torch.int32, device=dev), 2
+
+
+def _strip_left_padding(h, lens, flush, len_scale):
+    """The finish of the search over _left_padded_table, on the downloaded BeamState arrays `h` (in place): every clip as a search over
+    clips of its own length leaves it.  The rows lose their left padding and are Lt wide again (behind the generated tokens they hold
+    the rest of the clip's input row, then the stop token); the hypothesis scores and the worst score, stored over the 2 * Lt wide
+    table, are multiplied by len_scale (exact); and a pseudo-clip whose budget ended before it was done (flush) counts as not done, so
+    that the host flushes its beams as it does for a clip the loop's end leaves unfinished."""
+    K, Lt = h.tokens.size(1), h.tokens.size(2) // len_scale
+    groups = h.tokens.size(0) // len(lens)
+    cols = (torch.arange(Lt)[None] + (max(lens) - torch.as_tensor(lens))[:, None]).repeat_interleave(groups, 0)
+    h.tokens = h.tokens.gather(2, cols[:, None, :].expand(-1, K, -1))
+    h.hyp_tokens = h.hyp_tokens.gather(2, cols[:, None, :].expand(-1, K, -1))
+    h.hyp_score, h.worst, h.done = h.hyp_score * len_scale, h.worst * len_scale, h.done * (1 - flush.cpu())
+
+
+def _mixed_prompt_lengths(prompt_length, B, L, needed_by=None):
+    """A loop's prompt_length: None or an int -> None (one prompt length; refused for the caller `needed_by`); a sequence or tensor of
+    B lengths -> them as a list of ints in [1, L]"""
+    lens = _int_list(prompt_length)
+    if lens is None and needed_by:
+        raise ValueError(f"{needed_by} needs prompt_length = {B} lengths, one per clip (got {prompt_length!r})")
+    if lens is not None and (len(lens) != B or min(lens) < 1 or max(lens) > L):
         raise ValueError(f"prompt_length must be an int or {B} lengths in [1, {L}] (got {lens})")
     return lens
+
+
+def _mixed_prompt_state(cfg, make_state, rows, Q, lens, final_len, who):
+    """The decode state of a lockstep loop over clips whose prompts hold `lens` tokens -> (state, the positions it holds).  Every
+    sequence steps until the shortest prompt's budget ends, the longer ones as padding rows by then, so Q + P_max + final_len - P_min -
+    2 must be a row of the position table, and the state must take the prompt lengths: both are checked before the first launch."""
+    longest, shortest = max(lens), min(lens)
+    total_final = Q + longest + final_len - shortest
+    if total_final - 2 >= cfg.max_position_embeddings:        # the last step's position of the longest prefix (frozen by then, but fed)
+        raise ValueError(f"prompts of {shortest} .. {longest} tokens behind {Q} query slots step up to position {total_final - 2}; "
+                         f"the position table has {cfg.max_position_embeddings} rows")
+    state = make_state(rows, total_final)
+    if not _takes_prompt_len(state):
+        raise ValueError(f'{who} a state with prefill_fan_out(..., prompt_len=): kv="shared_prefix" (got a {type(state).__name__})')
+    return state, total_final
 
 
 def _takes_prompt_len(state) -> bool:
@@ -939,114 +961,102 @@ def sample_batched_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None
                         stop_on_double_eol=False, stop_on_eol=False, termination_id=None, prompt_length=None, num_samples=1, seed=0,
                         streams=None, advance_fn=None, constraints: Optional["LogitsConstraints"] = None, constrain_fn=None,
                         return_scores=False, score_fn=None, mixed_prompts=False):
-    """sample_loop with the whole of a step's sampling and bookkeeping in one launch, for B clips x num_samples sequences in lockstep:
-    tokens [B, L], query_embeds [B, Q, H], prompt_length [B] (ragged lengths are allowed) or None.  Sequence j belongs to clip
-    j // num_samples.  The prefill runs once per clip over the shortest prompt (state.prefill_fan_out) and fans out to the clip's
-    samples; afterwards a step is state.step(next_tok) and advance_fn (ops.sample_advance: filter, draw, teacher forcing behind the
-    prefill, termination; include/mpv.h states the semantics).  Samples never swap KV caches, so nothing is re-ordered, and the host
-    reads four bytes per step (the count of done rows).  Row j draws from the stream streams[j] (default j) of `seed`: its tokens do
-    not depend on the other rows of the call.  cfg.top_k / cfg.top_p choose the filter as in sample_loop.  -> tokens [B * num_samples,
-    n] with sample_loop's (prefix-inclusive, sic) slice.  make_state and advance_fn are injectable as in beam_search_batched_loop.
+    """Sampled generation for B clips x num_samples sequences in lockstep, the whole of a step's sampling and bookkeeping in one
+    launch: tokens [B, L], query_embeds [B, Q, H]; sequence j belongs to clip j // num_samples.  The prefill runs once per clip
+    (state.prefill_fan_out) and fans out to the clip's samples; afterwards a step is state.step(st.next_tok) and _Sampler.step:
+    constrain_fn, advance_fn (filter, draw, write, termination; include/mpv.h states the semantics), score_fn.  Samples never swap KV
+    caches, so nothing is re-ordered, and the host reads four bytes per step (the count of done rows).  Row j draws from the stream
+    streams[j] (default j) of `seed`: its tokens do not depend on the other rows of the call.  cfg.top_k / cfg.top_p choose the
+    filter as in sample_loop.  make_state and the *_fn are injectable as in beam_search_batched_loop.
     `constraints` (a LogitsConstraints; None or inactive: no call and no launch is added): between the step and advance_fn every
-    step, the prefill's included, edits the raw logits through constrain_fn (ops.logits_constrain) on st.tokens / st.prompt_len; rows
-    still inside their prompt are left alone.  The termination ids of min_new_tokens are [termination_id], or [628, 198] under
-    stop_on_eol; a banned logit is -inf, the sampler's "never drawn".  min_new_tokens with stop_on_double_eol is refused (a pair of
-    tokens ends the row there, which a per-token ban cannot express).
+    step, the prefill's included, edits the raw logits through constrain_fn on st.tokens / st.prompt_len; rows still inside their
+    prompt are left alone.  The termination ids of min_new_tokens are [termination_id], or [628, 198] under stop_on_eol; a banned
+    logit is -inf, the sampler's "never drawn".  min_new_tokens with stop_on_double_eol is refused (a pair of tokens ends the row
+    there, which a per-token ban cannot express).
     `return_scores` (default False: no call, no launch and no allocation is added, and the return value is the tensor alone): right
-    after advance_fn every step, the prefill's included, score_fn (ops.sample_score) records the model's log-probability of the token
-    just written, from the logits advance_fn read (the constrained ones) -- rows still inside their prompt and rows that terminated
-    in an earlier step are not scored; the terminating token is.  -> (tokens, scores): a SampleScores whose token_logprob is cut to
-    the columns of `tokens`.  The host still reads only the count of done rows.
-    mixed_prompts=True (default False: everything above, launch for launch) with prompt_length = B lengths: ONE lockstep loop over
-    clips whose prompts differ in length WITHOUT teacher forcing.  The table stays LEFT-aligned (clip c's prompt at columns
-    [0, prompt_length[c]), final_len wide): a draw is a function of (seed, column, stream), so a clip's samples must not move with its
-    neighbours' prompts.  The prefill is the ragged one (state.prefill_fan_out(..., prompt_len=): SharedPrefixDecodeState; any other
-    state is refused), and advance_fn / constrain_fn / score_fn are the RAGGED entries (ops.sample_advance_ragged,
-    ops.logits_constrain_ragged, ops.sample_score_ragged), called with step=t in place of pos=: row r works on column
-    prompt_length[r] + t.  The loop ends when every row is done or after final_len - P_min steps; a clip with a longer prompt runs out
-    of columns earlier and is frozen by the kernels (done, counted in n_done), with no host bookkeeping; it keeps stepping as
-    padding rows, so Q + P_max + final_len - P_min - 2 must be a row of the position table (a ValueError before the first launch
-    otherwise).  -> tokens [B * num_samples, n], n covering every written column; a row holds its prompt, its generated tokens and,
-    behind them, the rest of its input row."""
+    after advance_fn every step, the prefill's included, score_fn records the model's log-probability of the token just written,
+    from the logits advance_fn read (the constrained ones) -- rows still inside their prompt and rows that terminated in an earlier
+    step are not scored; the terminating token is.  -> (tokens, scores): a SampleScores whose token_logprob is cut to the columns of
+    `tokens`.
+    mixed_prompts=False: prompt_length [B] (ragged lengths are allowed) or None.  The prefill covers the shortest prompt P_min, and
+    the entries are the uniform ones (ops.sample_advance, ops.logits_constrain, ops.sample_score), called with pos = P_min + t: all
+    rows work on one column, and advance_fn teacher-forces the rows whose prompt reaches further.  -> tokens [B * num_samples, n]
+    with sample_loop's (prefix-inclusive, sic) slice n = Q + P_min + t + 1.
+    mixed_prompts=True with prompt_length = B lengths: ONE loop over clips whose prompts differ in length WITHOUT teacher forcing.
+    The table stays LEFT-aligned (clip c's prompt at columns [0, prompt_length[c]), final_len wide): a draw is a function of (seed,
+    column, stream), so a clip's samples must not move with its neighbours' prompts.  The prefill is the ragged one
+    (state.prefill_fan_out(..., prompt_len=): SharedPrefixDecodeState; any other state is refused), and the entries are the RAGGED
+    ones (ops.sample_advance_ragged, ops.logits_constrain_ragged, ops.sample_score_ragged), called with step = t: row r works on
+    column prompt_length[r] + t.  The loop ends when every row is done or after final_len - P_min steps; a clip with a longer prompt
+    runs out of columns earlier and is frozen by the kernels (done, counted in n_done), with no host bookkeeping; it keeps stepping as
+    padding rows, which _mixed_prompt_state checks against the position table before the first launch.  -> tokens [B * num_samples,
+    n], n covering every written column; a row holds its prompt, its generated tokens and, behind them, the rest of its input row."""
     B, dev, N = tokens.size(0), tokens.device, int(num_samples)
-    if N < 1:
-        raise ValueError(f"num_samples must be at least 1 (got {num_samples})")
-    if return_scores and score_fn is None:
-        raise ValueError("return_scores=True needs a score_fn (ops.sample_score)")
-    constraints = _active_constraints(constraints, constrain_fn)
-    if constraints is not None and constraints.min_new_tokens > 0 and stop_on_double_eol:
-        raise ValueError(f"min_new_tokens ({constraints.min_new_tokens}) cannot be combined with stop_on_double_eol")
-    if mixed_prompts:
-        lens = _mixed_prompt_lengths(prompt_length, B, tokens.size(1))
-        if lens is None:
-            raise ValueError(f"mixed_prompts=True needs prompt_length = {B} lengths, one per clip (got {prompt_length!r})")
-        longest, shortest = max(lens), min(lens)
-        tokens, final_len, Q = _pad_for_generation(cfg, tokens, cfg.eod_id, longest, query_embeds)
-        R = B * N
-        total_final = Q + longest + final_len - shortest
-        if total_final - 2 >= cfg.max_position_embeddings:        # the last step's position of the longest prefix (frozen by then, but fed)
-            raise ValueError(f"prompts of {shortest} .. {longest} tokens behind {Q} query slots step up to position {total_final - 2}; "
-                             f"the position table has {cfg.max_position_embeddings} rows")
-        state = make_state(R, total_final)
-        if not _takes_prompt_len(state):
-            raise ValueError('mixed_prompts=True needs a state with prefill_fan_out(..., prompt_len=): kv="shared_prefix" '
-                             f"(got a {type(state).__name__})")
-        st = SampleState(tokens[:, :final_len].repeat_interleave(N, dim=0), torch.as_tensor(lens, dtype=torch.long).to(dev).repeat_interleave(N),
-                         streams=streams)
-        sc = SampleScores(R, st.row_len, dev) if return_scores else None
-        termination_id = cfg.eod_id if termination_id is None else int(termination_id)
-        mode = 2 if stop_on_double_eol else 1 if stop_on_eol else 0
-        eos_ids = [628, 198] if mode else [termination_id]
-        t = 0
-        for t in range(final_len - shortest):
-            if t == 0:
-                logits = state.prefill_fan_out(tokens[:, :longest].contiguous(), query_embeds, N, prompt_len=lens)
-            else:
-                logits = state.step(st.next_tok.view(-1, 1))
-            if constraints is not None:
-                constrain_fn(logits, st.tokens, step=t, constraints=constraints, prompt_len=st.prompt_len, eos_ids=eos_ids, ban_value=BAN_SAMPLING)
-            advance_fn(logits, st, step=t, temperature=temperature, top_k=cfg.top_k, top_p=cfg.top_p, seed=seed, vocab_size=cfg.vocab_size,
-                       termination_mode=mode, termination_id=termination_id)
-            if sc is not None:
-                score_fn(logits, st, sc, step=t)
-            if use_eod_token_for_early_termination and int(st.n_done.item()) == R:   # the step's one host read: 4 bytes
-                break
-        n = min(longest + t + Q + 1, final_len)                   # with equal lengths: the uniform loop's (prefix-inclusive, sic) slice
-        if sc is not None:
-            sc.token_logprob = sc.token_logprob[:, :n]
-            return st.tokens[:, :n], sc
-        return st.tokens[:, :n]
-    lengths = prompt_length if prompt_length is not None else torch.tensor([tokens.size(1)], device=dev)
-    lengths = torch.as_tensor(lengths, device=dev).view(-1).expand(B)
-    min_prompt = int(lengths.min().item())
-    tokens, max_len, Q = _pad_for_generation(cfg, tokens, cfg.eod_id, min_prompt, query_embeds)
+    sampler = _Sampler(cfg, dict(num_samples=num_samples), temperature, seed, termination_id, stop_on_double_eol, stop_on_eol, advance_fn,
+                       constraints, constrain_fn, return_scores, score_fn, "sample_score")
     R = B * N
-    state = make_state(R, max_len + Q)
-    st = SampleState(tokens.repeat_interleave(N, dim=0), lengths.repeat_interleave(N), streams=streams)
+    if mixed_prompts:
+        lens = _mixed_prompt_lengths(prompt_length, B, tokens.size(1), "mixed_prompts=True")
+        prompt = max(lens)                                        # the prefill's columns: the longest prompt, right-padded
+        tokens, final_len, Q = _pad_for_generation(cfg, tokens, cfg.eod_id, prompt, query_embeds)
+        state, _ = _mixed_prompt_state(cfg, make_state, R, Q, lens, final_len, "mixed_prompts=True needs")
+        table, lengths = tokens[:, :final_len], torch.as_tensor(lens, dtype=torch.long).to(dev)
+        prefill_more, steps, where, first = dict(prompt_len=lens), final_len - min(lens), "step", 0
+    else:
+        lengths = prompt_length if prompt_length is not None else torch.tensor([tokens.size(1)], device=dev)
+        lengths = torch.as_tensor(lengths, device=dev).view(-1).expand(B)
+        prompt = int(lengths.min().item())                        # the prefill's columns: the shortest prompt
+        tokens, max_len, Q = _pad_for_generation(cfg, tokens, cfg.eod_id, prompt, query_embeds)
+        state = make_state(R, max_len + Q)
+        table = tokens
+        prefill_more, steps, where, first = {}, max_len - prompt, "pos", prompt
+    st = SampleState(table.repeat_interleave(N, dim=0), lengths.repeat_interleave(N), streams=streams)
     sc = SampleScores(R, st.row_len, dev) if return_scores else None
-    termination_id = cfg.eod_id if termination_id is None else int(termination_id)
-    mode = 2 if stop_on_double_eol else 1 if stop_on_eol else 0
-    eos_ids = [628, 198] if mode else [termination_id]
-    total_min, total_max = min_prompt + Q, max_len + Q
-    context_length = total_min
-    for context_length in range(total_min, total_max):
-        if context_length == total_min:
-            logits = state.prefill_fan_out(tokens[:, :min_prompt].contiguous(), query_embeds, N)
+    t = 0
+    for t in range(steps):
+        if t == 0:
+            logits = state.prefill_fan_out(tokens[:, :prompt].contiguous(), query_embeds, N, **prefill_more)
         else:
             logits = state.step(st.next_tok.view(-1, 1))
-        if constraints is not None:
-            constrain_fn(logits, st.tokens, pos=context_length - Q, constraints=constraints, prompt_len=st.prompt_len, eos_ids=eos_ids,
-                         ban_value=BAN_SAMPLING)
-        advance_fn(logits, st, pos=context_length - Q, temperature=temperature, top_k=cfg.top_k, top_p=cfg.top_p, seed=seed,
-                   vocab_size=cfg.vocab_size, termination_mode=mode, termination_id=termination_id)
-        if sc is not None:
-            score_fn(logits, st, sc, pos=context_length - Q)
+        sampler.step(logits, st, sc, **{where: first + t})
         if use_eod_token_for_early_termination and int(st.n_done.item()) == R:       # the step's one host read: 4 bytes
             break
+    n = min(Q + prompt + t + 1, st.row_len)          # (sic) sample_loop slices with the prefix-inclusive length; the table may end before it
     if sc is not None:
-        sc.token_logprob = sc.token_logprob[:, :context_length + 1]
-        return st.tokens[:, :context_length + 1], sc
-    return st.tokens[:, :context_length + 1]      # (sic) as sample_loop
+        sc.token_logprob = sc.token_logprob[:, :n]
+        return st.tokens[:, :n], sc
+    return st.tokens[:, :n]
+
+
+class _Sampler:
+    """What sample_batched_loop and sample_inflight_loop do alike, built once per call: the checks of their common arguments, the
+    termination triple (termination_id, termination_mode, the eos ids of min_new_tokens) and the three calls of a step."""
+
+    def __init__(self, cfg, at_least_one: dict, temperature, seed, termination_id, stop_on_double_eol, stop_on_eol, advance_fn, constraints,
+                 constrain_fn, return_scores, score_fn, score_name: str):
+        if any(int(v) < 1 for v in at_least_one.values()):
+            raise ValueError(f"{' and '.join(at_least_one)} must be at least 1 (got {', '.join(str(v) for v in at_least_one.values())})")
+        if return_scores and score_fn is None:
+            raise ValueError(f"return_scores=True needs a score_fn (ops.{score_name})")
+        self.constraints = _active_constraints(constraints, constrain_fn)
+        if self.constraints is not None and self.constraints.min_new_tokens > 0 and stop_on_double_eol:
+            raise ValueError(f"min_new_tokens ({self.constraints.min_new_tokens}) cannot be combined with stop_on_double_eol")
+        self.termination_id = cfg.eod_id if termination_id is None else int(termination_id)
+        self.mode = 2 if stop_on_double_eol else 1 if stop_on_eol else 0
+        self.eos_ids = [628, 198] if self.mode else [self.termination_id]
+        self.advance_fn, self.constrain_fn, self.score_fn = advance_fn, constrain_fn, score_fn
+        self.draw = dict(temperature=temperature, top_k=cfg.top_k, top_p=cfg.top_p, seed=seed, vocab_size=cfg.vocab_size,
+                         termination_mode=self.mode, termination_id=self.termination_id)
+
+    def step(self, logits, st: "SampleState", sc: Optional["SampleScores"], **where):
+        """constrain (active constraints only), advance, score (sc given) on one step's logits; `where` is the entries' own keyword for
+        the column a row works on: pos= (one for all), step= (the row's prompt length + step) or row_step= (a step per row)"""
+        if self.constraints is not None:
+            self.constrain_fn(logits, st.tokens, constraints=self.constraints, prompt_len=st.prompt_len, eos_ids=self.eos_ids,
+                              ban_value=BAN_SAMPLING, **where)
+        self.advance_fn(logits, st, **where, **self.draw)
+        if sc is not None:
+            self.score_fn(logits, st, sc, **where)
 
 
 def refill_min_default(slots: int) -> int:
@@ -1069,10 +1079,12 @@ def sample_inflight_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=Non
     make_state(slots, fan, prefix_rows, suffix_rows) -> an InflightDecodeState (make_inflight_state_fn).  advance_fn / constrain_fn /
     score_fn are the _steps entries (ops.sample_advance_steps, ops.logits_constrain_steps, ops.sample_score_steps), called with
     row_step= (int32 [slots * num_samples] on the device: every row's own generation step, -1 for the rows of a free slot).
-    One iteration: (0) if at least refill_min slots are free (default refill_min_default(slots): a quarter of them; at most `slots`), or nothing runs, the next
-    clips are installed (ONE staged ragged prefill for all of them); (1) ONE decode step for the slots already running -- a slot just
-    installed is idle in it --, none if nothing runs; (2) the prefill logits overwrite the rows of the slots just installed; (3) one
-    constrain launch, one advance launch and one score launch, every row on its own step; (4) the host, which mirrors every slot's
+    The argument checks, the termination rule, constraints and return_scores are sample_batched_loop's (_Sampler).
+    One iteration: (0) if at least refill_min slots are free (default refill_min_default(slots): a quarter of them; at most `slots`),
+    or nothing runs, the next clips are installed (state.install: ONE staged ragged prefill for all of them); (1) ONE decode step
+    (state.step(st.next_tok, group_t, max_t)) for the slots already running -- a slot just installed is idle in it --, none if
+    nothing runs; (2) the prefill logits overwrite the rows of the slots just installed; (3) the sampler's step: one constrain
+    launch, one advance launch and one score launch, every row on its own step; (4) the host, which mirrors every slot's
     step as Python ints, reads n_done (4 bytes) and -- only when that count is not the one it expects -- the done vector; clips that
     are done (unless use_eod_token_for_early_termination is False) or have used their budget leave: their token and score rows are
     gathered on the device into the result, in input order.
@@ -1083,30 +1095,20 @@ def sample_inflight_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=Non
     input row), written [n] (list: the columns of clip c that hold prompt or generated tokens), scores (a SampleScores over all rows,
     or None), steps / prefills (decode steps and prefill passes issued))."""
     n, dev, N, slots = tokens.size(0), tokens.device, int(num_samples), int(slots)
-    if N < 1 or slots < 1:
-        raise ValueError(f"num_samples and slots must be at least 1 (got {num_samples}, {slots})")
-    if return_scores and score_fn is None:
-        raise ValueError("return_scores=True needs a score_fn (ops.sample_score_steps)")
     if advance_fn is None:
         raise ValueError("sample_inflight_loop needs an advance_fn (ops.sample_advance_steps)")
-    constraints = _active_constraints(constraints, constrain_fn)
-    if constraints is not None and constraints.min_new_tokens > 0 and stop_on_double_eol:
-        raise ValueError(f"min_new_tokens ({constraints.min_new_tokens}) cannot be combined with stop_on_double_eol")
-    lens = _mixed_prompt_lengths(prompt_length, n, tokens.size(1))
-    if lens is None:
-        raise ValueError(f"sample_inflight_loop needs prompt_length = {n} lengths, one per clip (got {prompt_length!r})")
+    sampler = _Sampler(cfg, dict(num_samples=num_samples, slots=slots), temperature, seed, termination_id, stop_on_double_eol, stop_on_eol,
+                       advance_fn, constraints, constrain_fn, return_scores, score_fn, "sample_score_steps")
+    lens = _mixed_prompt_lengths(prompt_length, n, tokens.size(1), "sample_inflight_loop")
     refill_min = min(slots, refill_min_default(slots) if refill_min is None else int(refill_min))
     if refill_min < 1:
         raise ValueError(f"refill_min must be at least 1 (got {refill_min})")
     longest = max(lens)
     table, final_len, Q = _pad_for_generation(cfg, tokens, cfg.eod_id, longest, query_embeds)
     table = table[:, :final_len]
-    if max_new_tokens is None:
-        budgets = [int(cfg.tokens_to_generate)] * n
-    elif hasattr(max_new_tokens, "__len__") and not (torch.is_tensor(max_new_tokens) and max_new_tokens.dim() == 0):
-        budgets = [int(b) for b in (max_new_tokens.tolist() if torch.is_tensor(max_new_tokens) else max_new_tokens)]
-    else:
-        budgets = [int(max_new_tokens)] * n
+    budgets = _int_list(max_new_tokens)
+    if budgets is None:
+        budgets = [int(cfg.tokens_to_generate if max_new_tokens is None else max_new_tokens)] * n
     if len(budgets) != n or min(budgets) < 1:
         raise ValueError(f"max_new_tokens must be None, a positive int or {n} positive budgets (got {max_new_tokens!r})")
     budgets = [min(b, final_len - pl) for b, pl in zip(budgets, lens)]                      # the table's columns behind the prompt
@@ -1125,11 +1127,9 @@ def sample_inflight_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=Non
     out_tokens = table.repeat_interleave(N, dim=0).contiguous()
     out_sc = SampleScores(n * N, st.row_len, dev) if return_scores else None
     written = list(lens)
-    termination_id = cfg.eod_id if termination_id is None else int(termination_id)
-    mode = 2 if stop_on_double_eol else 1 if stop_on_eol else 0
-    eos_ids = [628, 198] if mode else [termination_id]
     lens_d = torch.as_tensor(lens, dtype=torch.long).to(dev)
     within = torch.arange(N, device=dev)
+    rows_of = lambda ids: (torch.as_tensor(ids, dtype=torch.long).to(dev)[:, None] * N + within[None]).reshape(-1)   # the N rows of each slot / clip
     logits = None
     clip_of, step_of, known_done = [-1] * slots, [-1] * slots, [0] * slots            # the host's mirror: clip, next sampler step, done rows
     next_clip = 0
@@ -1143,8 +1143,8 @@ def sample_inflight_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=Non
             sel = torch.as_tensor(clips, dtype=torch.long).to(dev)
             first = state.install(fresh, table[sel, :longest].contiguous(), None if query_embeds is None else query_embeds[sel].contiguous(),
                                   [lens[c] for c in clips])
-            fresh_rows = (torch.as_tensor(fresh, dtype=torch.long).to(dev)[:, None] * N + within[None]).reshape(-1)
-            src = (sel[:, None] * N + within[None]).reshape(-1)
+            fresh_rows = rows_of(fresh)
+            src = rows_of(sel)
             st.tokens[fresh_rows] = out_tokens[src]                                        # the slot's rows, reset for their new clip
             st.prompt_len[fresh_rows] = lens_d[sel].repeat_interleave(N)
             st.stream[fresh_rows] = streams[src]
@@ -1162,13 +1162,7 @@ def sample_inflight_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=Non
         if fresh:                                                                          # (2) the prefill logits of the fresh slots
             logits[fresh_rows] = first.repeat_interleave(N, dim=0)
         row_step = torch.tensor([step_of[s] if clip_of[s] >= 0 else -1 for s in range(slots)], dtype=torch.int32).repeat_interleave(N).to(dev)
-        if constraints is not None:                                                        # (3) every row on its own step
-            constrain_fn(logits, st.tokens, row_step=row_step, constraints=constraints, prompt_len=st.prompt_len, eos_ids=eos_ids,
-                         ban_value=BAN_SAMPLING)
-        advance_fn(logits, st, row_step=row_step, temperature=temperature, top_k=cfg.top_k, top_p=cfg.top_p, seed=seed, vocab_size=cfg.vocab_size,
-                   termination_mode=mode, termination_id=termination_id)
-        if sc is not None:
-            score_fn(logits, st, sc, row_step=row_step)
+        sampler.step(logits, st, sc, row_step=row_step)                                    # (3) every row on its own step
         active = [s for s in range(slots) if clip_of[s] >= 0]                              # (4) the bookkeeping
         for s in active:
             step_of[s] += 1
@@ -1180,8 +1174,8 @@ def sample_inflight_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=Non
                     known_done[s] = done_h[s]
         leaving = [s for s in active if known_done[s] == N or step_of[s] >= budgets[clip_of[s]]]
         if leaving:
-            rows = (torch.as_tensor(leaving, dtype=torch.long).to(dev)[:, None] * N + within[None]).reshape(-1)
-            dst = (torch.as_tensor([clip_of[s] for s in leaving], dtype=torch.long).to(dev)[:, None] * N + within[None]).reshape(-1)
+            rows = rows_of(leaving)
+            dst = rows_of([clip_of[s] for s in leaving])
             out_tokens[dst] = st.tokens[rows]
             if sc is not None:
                 out_sc.live[dst], out_sc.sum_logprob[dst], out_sc.count[dst] = sc.live[rows], sc.sum_logprob[rows], sc.count[rows]
@@ -1200,14 +1194,31 @@ def pad_after_termination(tokens: torch.Tensor, prompt_len, termination_id: int,
     out = torch.full((R, width), int(fill), dtype=tokens.dtype, device=tokens.device)
     out[:, :min(n, width)] = tokens[:, :width]
     col = torch.arange(width, device=tokens.device)[None]
-    if hasattr(prompt_len, "__len__") and not (torch.is_tensor(prompt_len) and prompt_len.dim() == 0):
-        prompt_len = torch.as_tensor(prompt_len, dtype=torch.long).to(tokens.device).view(R, 1)
-    else:
-        prompt_len = int(prompt_len)
+    prompt_len = int(prompt_len) if _is_scalar(prompt_len) else torch.as_tensor(prompt_len, dtype=torch.long).to(tokens.device).view(R, 1)
     hit = (out == int(termination_id)) & (col >= prompt_len)
     first = torch.where(hit.any(dim=1), hit.int().argmax(dim=1), torch.full((R,), width, device=tokens.device))
     out[col > first[:, None]] = int(fill)
     return out
+
+
+def _sampler_config(gpt, top_k=None, top_p=None):
+    """_gen_config with the filter overridden: giving either of top_k / top_p replaces both (the other one is then off)"""
+    cfg = _gen_config(gpt)
+    if top_k is not None or top_p is not None:
+        cfg.top_k, cfg.top_p = int(top_k or 0), float(top_p or 0.0)
+    return cfg
+
+
+# sampler mode -> the names in `ops` of its (advance, constrain, score) functions; they say where a row works by pos=, step=, row_step=
+SAMPLER_OPS = {"uniform": ("sample_advance", "logits_constrain", "sample_score"),
+               "ragged": ("sample_advance_ragged", "logits_constrain_ragged", "sample_score_ragged"),
+               "steps": ("sample_advance_steps", "logits_constrain_steps", "sample_score_steps")}
+
+
+def _sampler_fns(mode: str, return_scores) -> dict:
+    """a sampler mode's advance_fn / constrain_fn keywords (with return_scores also the score keywords), looked up in `ops` at the call"""
+    advance, constrain, score = (getattr(ops, name) for name in SAMPLER_OPS[mode])
+    return dict(advance_fn=advance, constrain_fn=constrain, **(dict(return_scores=True, score_fn=score) if return_scores else {}))
 
 
 def install(gpt_cls):
@@ -1234,7 +1245,7 @@ def install(gpt_cls):
         run on the decoder's e4m3 codes (DecodeWeightsQ8)"""
         _no_sample_scores(kw.pop("return_scores", False), "beam_search_batched")
         groups = {} if int(beam_groups) == 1 else dict(beam_groups=beam_groups, diversity_penalty=diversity_penalty,
-                                                       group_advance_fn=ops.beam_advance_groups)      # one group: today's call
+                                                       group_advance_fn=ops.beam_advance_groups)      # one group: none of the three keywords
         return beam_search_batched_loop(_gen_config(self), make_state_fn(self, kv, decode_weights), tokens, query_embeds=query_embeds, beam_size=beam_size,
                                         num_return_gen=num_return_gen, stop_token=stop_token, prompt_length=kw.pop("prompt_length", None),
                                         topk_fn=lambda lg, k, add: ops.logprob_topk(lg, k, add=add), advance_fn=ops.beam_advance,
@@ -1251,21 +1262,12 @@ def install(gpt_cls):
         kv="shared_prefix": ONE loop over clips whose prompts differ in length, the table left-aligned and every row on its own
         column (sample_batched_loop's mixed mode: ops.sample_advance_ragged / logits_constrain_ragged / sample_score_ragged)"""
         make_state = make_state_fn(self, kv, decode_weights)
-        cfg = _gen_config(self)
-        if top_k is not None or top_p is not None:
-            cfg.top_k, cfg.top_p = int(top_k or 0), float(top_p or 0.0)
-        if mixed_prompts:
-            if kv != "shared_prefix":
-                raise ValueError(f'mixed_prompts=True needs kv="shared_prefix" (got {kv!r}): only the shared-prefix decode step takes a '
-                                 "prefix length per clip")
-            return sample_batched_loop(cfg, make_state, tokens, query_embeds=query_embeds, temperature=temperature, num_samples=num_samples,
-                                       seed=seed, streams=streams, advance_fn=ops.sample_advance_ragged, constraints=constraints,
-                                       constrain_fn=ops.logits_constrain_ragged, mixed_prompts=True,
-                                       **(dict(return_scores=True, score_fn=ops.sample_score_ragged) if return_scores else {}), **kw)
-        return sample_batched_loop(cfg, make_state, tokens, query_embeds=query_embeds, temperature=temperature, num_samples=num_samples,
-                                   seed=seed, streams=streams, advance_fn=ops.sample_advance, constraints=constraints,
-                                   constrain_fn=ops.logits_constrain, **(dict(return_scores=True, score_fn=ops.sample_score) if return_scores else {}),
-                                   **kw)
+        if mixed_prompts and kv != "shared_prefix":
+            raise ValueError(f'mixed_prompts=True needs kv="shared_prefix" (got {kv!r}): only the shared-prefix decode step takes a '
+                             "prefix length per clip")
+        return sample_batched_loop(_sampler_config(self, top_k, top_p), make_state, tokens, query_embeds=query_embeds, temperature=temperature,
+                                   num_samples=num_samples, seed=seed, streams=streams, constraints=constraints,
+                                   mixed_prompts=bool(mixed_prompts), **_sampler_fns("ragged" if mixed_prompts else "uniform", return_scores), **kw)
 
     def sample_inflight(self, tokens, query_embeds=None, temperature=1.0, num_samples=1, slots=32, seed=0, streams=None, top_k=None, top_p=None,
                         constraints=None, return_scores=False, decode_weights="bf16", max_new_tokens=None, refill_min=None, **kw):
@@ -1273,14 +1275,10 @@ def install(gpt_cls):
         flight (sample_inflight_loop: continuous batching): tokens [n, L], prompt_length n lengths; `slots` clips x num_samples
         sequences stay resident; max_new_tokens: a budget per clip (None: tokens_to_generate); top_k=1 is a greedy captioner.
         -> a namespace: tokens [n * num_samples, final_len], written [n], scores (SampleScores or None), steps, prefills"""
-        cfg = _gen_config(self)
-        if top_k is not None or top_p is not None:
-            cfg.top_k, cfg.top_p = int(top_k or 0), float(top_p or 0.0)
-        return sample_inflight_loop(cfg, make_inflight_state_fn(self, decode_weights), tokens, query_embeds=query_embeds, temperature=temperature,
-                                    num_samples=num_samples, slots=slots, seed=seed, streams=streams, max_new_tokens=max_new_tokens,
-                                    refill_min=refill_min, advance_fn=ops.sample_advance_steps, constraints=constraints,
-                                    constrain_fn=ops.logits_constrain_steps,
-                                    **(dict(return_scores=True, score_fn=ops.sample_score_steps) if return_scores else {}), **kw)
+        return sample_inflight_loop(_sampler_config(self, top_k, top_p), make_inflight_state_fn(self, decode_weights), tokens,
+                                    query_embeds=query_embeds, temperature=temperature, num_samples=num_samples, slots=slots, seed=seed,
+                                    streams=streams, max_new_tokens=max_new_tokens, refill_min=refill_min, constraints=constraints,
+                                    **_sampler_fns("steps", return_scores), **kw)
 
     @torch.no_grad()
     def generate(self, tokens, do_sample=True, termination_id=None, *args, **kw):                # :1875-1880
@@ -1294,16 +1292,17 @@ def install(gpt_cls):
             raise ValueError(f"sampler must be 'torch' or 'device' (got {sampler!r})")
         if kw.get("kv", "per_sequence") not in KV_MODES:
             raise ValueError(f"kv must be one of {KV_MODES} (got {kw['kv']!r})")
-        if not (do_sample and sampler == "device") and kw.pop("kv", "per_sequence") != "per_sequence":
-            raise ValueError('kv="shared_prefix" needs a lockstep loop: do_sample=True with sampler="device", or beam_search_batched')
-        if not (do_sample and sampler == "device") and kw.pop("constraints", None) is not None:
-            raise ValueError('constraints need a lockstep loop: do_sample=True with sampler="device", or beam_search_batched')
-        if not (do_sample and sampler == "device"):
+        lockstep = do_sample and sampler == "device"
+        if not lockstep:                                       # the per-clip loops: what only the lockstep loops take is refused
+            if kw.pop("kv", "per_sequence") != "per_sequence":
+                raise ValueError('kv="shared_prefix" needs a lockstep loop: do_sample=True with sampler="device", or beam_search_batched')
+            if kw.pop("constraints", None) is not None:
+                raise ValueError('constraints need a lockstep loop: do_sample=True with sampler="device", or beam_search_batched')
             _no_sample_scores(kw.pop("return_scores", False), "generate without do_sample=True and sampler=\"device\"")
         was = self.training
         self.eval()
         try:
-            if do_sample and sampler == "device":
+            if lockstep:
                 return self.sample_batched(tokens, termination_id=termination_id, *args, **kw)
             if do_sample:
                 return self.sample(tokens, termination_id=termination_id, *args, **kw)

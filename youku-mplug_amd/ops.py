@@ -842,33 +842,33 @@ def sample_advance_desc(logits, st, *, pos, temperature=1.0, top_k=0, top_p=0.0,
     return d
 
 
-def _sample_advance(entry, logits, st, *, pos, temperature=1.0, top_k=0, top_p=0.0, seed=0, vocab_size=None, termination_mode=TERMINATION_ID,
-                    termination_id=0, u_override=None, out_kept=None, out_mass=None, out_token=None, vocab=None, ld=None, row_step=None):
-    """the body of sample_advance, sample_advance_ragged and sample_advance_steps (row_step: its extra argument): `entry` is the C
-    entry's name without the mpv_ prefix"""
+def _where(entry, rows, pos, step, row_step):
+    """How the three forms of a sampler entry say on which column a row works -> (the descriptor's pos, the arguments behind the
+    descriptor): the uniform form a column `pos` for all rows; the ragged form a generation `step` in the descriptor's pos (row r:
+    column prompt_len[r] + step); the steps form, neither given, row_step int32 [rows] on the device behind the descriptor"""
+    if pos is not None or step is not None:
+        return int(step if pos is None else pos), ()
+    if row_step is None or row_step.dtype != torch.int32 or row_step.numel() != rows or not row_step.is_contiguous():
+        raise _lib.MpvError(f"{entry}: row_step must be a contiguous int32 tensor of {rows} steps")
+    _need_cuda(row_step)
+    return 0, (_p(row_step),)
+
+
+def _sample_advance(entry, logits, st, *, pos=None, step=None, row_step=None, u_override=None, out_kept=None, out_mass=None, out_token=None,
+                    **desc):
+    """the body of sample_advance, sample_advance_ragged and sample_advance_steps, which pass all their arguments on: `entry` is the C
+    entry's name without the mpv_ prefix, `desc` what sample_advance_desc takes besides"""
     _need_cuda(logits, st.tokens, u_override, out_kept, out_mass, out_token)
-    more = _row_step_arg(entry, row_step, st.rows)
+    pos, more = _where(entry, st.rows, pos, step, row_step)
     if logits.dtype != torch.bfloat16 or logits.ndim != 2 or logits.shape[0] < st.rows or logits.stride(1) != 1:
         raise _lib.MpvError(f"{entry}: logits must be bf16 [{st.rows}, ld] with unit column stride (got {logits.dtype} {tuple(logits.shape)})")
     for name, t, dt in (("u_override", u_override, torch.float32), ("out_kept", out_kept, torch.int32), ("out_mass", out_mass, torch.float32),
                         ("out_token", out_token, torch.int64)):
         if t is not None and (t.dtype != dt or t.numel() < st.rows or not t.is_contiguous()):
             raise _lib.MpvError(f"{entry}: {name} must be contiguous {dt} [{st.rows}]")
-    d = sample_advance_desc(logits, st, pos=pos, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, vocab_size=vocab_size,
-                            termination_mode=termination_mode, termination_id=termination_id, u_override=u_override, out_kept=out_kept,
-                            out_mass=out_mass, out_token=out_token, vocab=vocab, ld=ld)
+    d = sample_advance_desc(logits, st, pos=pos, u_override=u_override, out_kept=out_kept, out_mass=out_mass, out_token=out_token, **desc)
     check(getattr(_lib.lib(), "mpv_" + entry)(C.byref(d), *more, _stream()), "mpv_" + entry)
     return st.next_tok
-
-
-def _row_step_arg(entry, row_step, rows):
-    """() for the uniform and ragged entries, (pointer,) for the _steps ones: row_step int32 [rows] on the device"""
-    if not entry.endswith("_steps"):
-        return ()
-    if row_step is None or row_step.dtype != torch.int32 or row_step.numel() != rows or not row_step.is_contiguous():
-        raise _lib.MpvError(f"{entry}: row_step must be a contiguous int32 tensor of {rows} steps")
-    _need_cuda(row_step)
-    return (_p(row_step),)
 
 
 def sample_advance(logits, st, *, pos, temperature=1.0, top_k=0, top_p=0.0, seed=0, vocab_size=None, termination_mode=TERMINATION_ID,
@@ -878,9 +878,7 @@ def sample_advance(logits, st, *, pos, temperature=1.0, top_k=0, top_p=0.0, seed
     the write into st.tokens[:, pos] behind the prompt, st.next_tok, st.done and st.n_done.  logits bf16 [rows, ld], the first `vocab`
     columns are read.  u_override fp32 [rows] replaces the uniform; out_kept int32 / out_mass fp32 / out_token int64 [rows] are optional
     diagnostics.  -> st.next_tok"""
-    return _sample_advance("sample_advance", logits, st, pos=pos, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, vocab_size=vocab_size,
-                           termination_mode=termination_mode, termination_id=termination_id, u_override=u_override, out_kept=out_kept,
-                           out_mass=out_mass, out_token=out_token, vocab=vocab, ld=ld)
+    return _sample_advance("sample_advance", **locals())
 
 
 def sample_advance_ragged(logits, st, *, step, temperature=1.0, top_k=0, top_p=0.0, seed=0, vocab_size=None, termination_mode=TERMINATION_ID,
@@ -889,9 +887,7 @@ def sample_advance_ragged(logits, st, *, step, temperature=1.0, top_k=0, top_p=0
     step `step` >= 0; row r draws, with the counter of its own column st.prompt_len[r] + step, into st.tokens[r, that column].  A row
     whose column lies behind the table is frozen: nothing read or written but st.done[r] = 1 and st.next_tok[r] = its last token.
     -> st.next_tok"""
-    return _sample_advance("sample_advance_ragged", logits, st, pos=step, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
-                           vocab_size=vocab_size, termination_mode=termination_mode, termination_id=termination_id, u_override=u_override,
-                           out_kept=out_kept, out_mass=out_mass, out_token=out_token, vocab=vocab, ld=ld)
+    return _sample_advance("sample_advance_ragged", **locals())
 
 
 def sample_advance_steps(logits, st, *, row_step, temperature=1.0, top_k=0, top_p=0.0, seed=0, vocab_size=None, termination_mode=TERMINATION_ID,
@@ -899,9 +895,7 @@ def sample_advance_steps(logits, st, *, row_step, temperature=1.0, top_k=0, top_
     """sample_advance_ragged with a generation step per row (include/mpv.h: mpv_sample_advance_steps; rows of clips that entered a
     running loop at different times): row_step int32 [rows] on the device; row r draws at column st.prompt_len[r] + row_step[r].  A
     row with a negative step, or whose column lies behind the table, is frozen.  -> st.next_tok"""
-    return _sample_advance("sample_advance_steps", logits, st, pos=0, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
-                           vocab_size=vocab_size, termination_mode=termination_mode, termination_id=termination_id, u_override=u_override,
-                           out_kept=out_kept, out_mass=out_mass, out_token=out_token, vocab=vocab, ld=ld, row_step=row_step)
+    return _sample_advance("sample_advance_steps", **locals())
 
 
 def _constraint_ids(constraints, device, eos_ids):
@@ -914,9 +908,12 @@ def _constraint_ids(constraints, device, eos_ids):
     return hit
 
 
-def _logits_constrain(entry, logits, tokens, *, pos, constraints, prompt_len, prompt_len_all, eos_ids, ban_value, vocab, ld, row_step=None):
-    """the body of logits_constrain, logits_constrain_ragged and logits_constrain_steps (row_step: its extra argument): `entry` is the C
-    entry's name without the mpv_ prefix"""
+def _logits_constrain(entry, logits, tokens, *, pos=None, step=None, row_step=None, constraints, prompt_len, prompt_len_all=0, eos_ids, ban_value,
+                      vocab, ld):
+    """the body of logits_constrain, logits_constrain_ragged and logits_constrain_steps, which pass all their arguments on: `entry` is
+    the C entry's name without the mpv_ prefix"""
+    if pos is None and prompt_len is None:                # a column per row is counted from the row's prompt length
+        raise _lib.MpvError(f"{entry}: prompt_len int64 [rows] is required")
     _need_cuda(logits, tokens, prompt_len)
     if logits.dtype != torch.bfloat16 or logits.ndim != 2 or logits.stride(1) != 1:
         raise _lib.MpvError(f"{entry}: logits must be bf16 [rows, ld] with unit column stride (got {logits.dtype} {tuple(logits.shape)})")
@@ -926,6 +923,7 @@ def _logits_constrain(entry, logits, tokens, *, pos, constraints, prompt_len, pr
     if prompt_len is not None and (prompt_len.dtype != torch.int64 or prompt_len.numel() != rows or not prompt_len.is_contiguous()):
         raise _lib.MpvError(f"{entry}: prompt_len must be contiguous int64 [{rows}]")
     eos, banned = _constraint_ids(constraints, logits.device, eos_ids)
+    pos, more = _where(entry, rows, pos, step, row_step)
     d = _lib.LogitsConstrainDesc()
     d.logits, d.tokens, d.prompt_len = _p(logits), _p(tokens), _p(prompt_len)
     d.eos_ids, d.banned_ids = (_p(eos) if eos.numel() else None), (_p(banned) if banned.numel() else None)
@@ -933,7 +931,7 @@ def _logits_constrain(entry, logits, tokens, *, pos, constraints, prompt_len, pr
     d.rows, d.vocab, d.row_len, d.pos = rows, int(vocab) if vocab is not None else logits.shape[-1], tokens.shape[1], int(pos)
     d.n_eos, d.n_banned, d.ngram, d.min_new_tokens = eos.numel(), banned.numel(), constraints.no_repeat_ngram_size, constraints.min_new_tokens
     d.include_prompt, d.penalty, d.ban_value = int(constraints.include_prompt), constraints.repetition_penalty, float(ban_value)
-    check(getattr(_lib.lib(), "mpv_" + entry)(C.byref(d), *_row_step_arg(entry, row_step, rows), _stream()), "mpv_" + entry)
+    check(getattr(_lib.lib(), "mpv_" + entry)(C.byref(d), *more, _stream()), "mpv_" + entry)
     return logits
 
 
@@ -944,8 +942,7 @@ def logits_constrain(logits, tokens, *, pos, constraints, prompt_len=None, promp
     and the banned ids, on logits bf16 [rows, ld] (the first `vocab` columns) from the histories in tokens int64 [rows, row_len] below
     column `pos`.  prompt_len int64 [rows] (rows with prompt_len > pos are left alone), or None: prompt_len_all for every row.  A
     banned logit becomes ban_value (-inf for the sampler, the lowest finite bf16 in front of logprob_topk).  -> logits"""
-    return _logits_constrain("logits_constrain", logits, tokens, pos=pos, constraints=constraints, prompt_len=prompt_len,
-                             prompt_len_all=prompt_len_all, eos_ids=eos_ids, ban_value=ban_value, vocab=vocab, ld=ld)
+    return _logits_constrain("logits_constrain", **locals())
 
 
 def logits_constrain_ragged(logits, tokens, *, step, constraints, prompt_len, eos_ids=(), ban_value=float("-inf"), vocab=None, ld=None):
@@ -953,25 +950,19 @@ def logits_constrain_ragged(logits, tokens, *, step, constraints, prompt_len, eo
     generation step `step` >= 0; row r's history is tokens[r, start : prompt_len[r] + step] with start = 0 under include_prompt and
     prompt_len[r] otherwise, and `step` tokens count as generated.  prompt_len int64 [rows] is required.  A row whose column lies behind
     the table is left alone.  -> logits"""
-    if prompt_len is None:
-        raise _lib.MpvError("logits_constrain_ragged: prompt_len int64 [rows] is required")
-    return _logits_constrain("logits_constrain_ragged", logits, tokens, pos=step, constraints=constraints, prompt_len=prompt_len,
-                             prompt_len_all=0, eos_ids=eos_ids, ban_value=ban_value, vocab=vocab, ld=ld)
+    return _logits_constrain("logits_constrain_ragged", **locals())
 
 
 def logits_constrain_steps(logits, tokens, *, row_step, constraints, prompt_len, eos_ids=(), ban_value=float("-inf"), vocab=None, ld=None):
     """logits_constrain_ragged with a generation step per row (include/mpv.h: mpv_logits_constrain_steps): row_step int32 [rows] on the
     device; row r's history ends in front of column prompt_len[r] + row_step[r] and row_step[r] tokens count as generated.  A row with
     a negative step, or whose column lies behind the table, is left alone.  -> logits"""
-    if prompt_len is None:
-        raise _lib.MpvError("logits_constrain_steps: prompt_len int64 [rows] is required")
-    return _logits_constrain("logits_constrain_steps", logits, tokens, pos=0, constraints=constraints, prompt_len=prompt_len,
-                             prompt_len_all=0, eos_ids=eos_ids, ban_value=ban_value, vocab=vocab, ld=ld, row_step=row_step)
+    return _logits_constrain("logits_constrain_steps", **locals())
 
 
-def _sample_score(entry, logits, st, sc, *, pos, vocab, ld, row_step=None):
-    """the body of sample_score, sample_score_ragged and sample_score_steps (row_step: its extra argument): `entry` is the C entry's
-    name without the mpv_ prefix"""
+def _sample_score(entry, logits, st, sc, *, pos=None, step=None, row_step=None, vocab, ld):
+    """the body of sample_score, sample_score_ragged and sample_score_steps, which pass all their arguments on: `entry` is the C
+    entry's name without the mpv_ prefix"""
     _need_cuda(logits, st.tokens, sc.token_logprob)
     if logits.dtype != torch.bfloat16 or logits.ndim != 2 or logits.shape[0] < st.rows or logits.stride(1) != 1:
         raise _lib.MpvError(f"{entry}: logits must be bf16 [{st.rows}, ld] with unit column stride (got {logits.dtype} {tuple(logits.shape)})")
@@ -981,12 +972,13 @@ def _sample_score(entry, logits, st, sc, *, pos, vocab, ld, row_step=None):
                                ("sum_logprob", sc.sum_logprob, torch.float32, (st.rows,)), ("count", sc.count, torch.int32, (st.rows,))):
         if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != logits.device:
             raise _lib.MpvError(f"{entry}: {name} must be contiguous {dt} {list(shape)} on {logits.device}")
+    pos, more = _where(entry, st.rows, pos, step, row_step)
     d = _lib.SampleScoreDesc()
     d.logits, d.tokens, d.prompt_len, d.done = _p(logits), _p(st.tokens), _p(st.prompt_len), _p(st.done)
     d.live, d.token_logprob, d.sum_logprob, d.count = _p(sc.live), _p(sc.token_logprob), _p(sc.sum_logprob), _p(sc.count)
     d.ld = int(ld) if ld is not None else logits.stride(0)
     d.rows, d.vocab, d.row_len, d.pos = st.rows, int(vocab) if vocab is not None else logits.shape[-1], st.row_len, int(pos)
-    check(getattr(_lib.lib(), "mpv_" + entry)(C.byref(d), *_row_step_arg(entry, row_step, st.rows), _stream()), "mpv_" + entry)
+    check(getattr(_lib.lib(), "mpv_" + entry)(C.byref(d), *more, _stream()), "mpv_" + entry)
     return sc
 
 
@@ -996,20 +988,20 @@ def sample_score(logits, st, sc, *, pos, vocab=None, ld=None):
     generation.SampleScores): log_softmax of logits bf16 [rows, ld] (the first `vocab` columns, what sample_advance read), into
     sc.token_logprob[:, pos], sc.sum_logprob and sc.count.  Rows with st.prompt_len > pos and rows whose sc.live is 0 are skipped;
     sc.live follows st.done.  -> sc"""
-    return _sample_score("sample_score", logits, st, sc, pos=pos, vocab=vocab, ld=ld)
+    return _sample_score("sample_score", **locals())
 
 
 def sample_score_ragged(logits, st, sc, *, step, vocab=None, ld=None):
     """sample_score right after sample_advance_ragged (include/mpv.h: mpv_sample_score_ragged): generation step `step` >= 0; row r's
     token at its own column st.prompt_len[r] + step is scored into sc.token_logprob[r, that column].  Frozen rows (the column lies
     behind the table) and rows whose sc.live is 0 are skipped.  -> sc"""
-    return _sample_score("sample_score_ragged", logits, st, sc, pos=step, vocab=vocab, ld=ld)
+    return _sample_score("sample_score_ragged", **locals())
 
 
 def sample_score_steps(logits, st, sc, *, row_step, vocab=None, ld=None):
     """sample_score right after sample_advance_steps (include/mpv.h: mpv_sample_score_steps): row r's token at its own column
     st.prompt_len[r] + row_step[r] is scored.  Frozen rows and rows whose sc.live is 0 are skipped.  -> sc"""
-    return _sample_score("sample_score_steps", logits, st, sc, pos=0, vocab=vocab, ld=ld, row_step=row_step)
+    return _sample_score("sample_score_steps", **locals())
 
 
 def sample_tokens(logits, *, temperature=1.0, top_k=0, top_p=0.0, seed=0, streams=None, vocab_size=None, vocab=None):
