@@ -66,6 +66,7 @@ int mpv_check_arch_name(const char* gcn_arch_name);
  * GEMM: C[M,N] = epilogue(sum_k A(m,k) B(n,k)), bf16 in, fp32 accumulate (v_mfma_f32_16x16x32_bf16 in the 256x256 kernel, 32x32x16 in the 128x128 fallback).
  * transA=0: A is [M][K] (lda); transA=1: A is [K][M].  transB=0: B is [N][K] (nn.Linear
  * weight); transB=1: B is [K][N].  (0,0)=forward, (0,1)=dgrad, (1,1)=wgrad (split-K inside).
+ * N, the leading dimensions and the contiguous extent of A (K, or M when transA) are multiples of 8; a wgrad's K is ANY length >= 1, odd included.
  * Replaces: F.linear / nn.Linear (models/vision_transformer.py:104,108,175,205,250),
  * nn.MultiheadAttention projections (:353), visual_fc (models/distributed_gpt3.py:111,136),
  * mpu.Column/RowParallelLinear + LM head (models/modeling_distributed_gpt3.py:562,573,843,852,
@@ -78,7 +79,9 @@ typedef struct mpv_gemm_epilogue {
                                       LDS-DMA; any other alignment is taken by the 128x128 kernel) */
   int act;                         /* MPV_ACT_*: y = act(bf16(acc + bias))                    */
   void* preact_out;                /* optional bf16 copy of (acc + bias) before act (ldc)     */
-  const void* residual;            /* optional bf16 [.,N] added last (leading dim ldr)        */
+  const void* residual;            /* optional bf16 [.,N] added last (leading dim ldr): C = bf16(v + residual) with v the epilogue's value
+                                      so far -- bf16(acc + bias) without an activation.  EXCEPT the small-M forward kernel (M <= 16, the
+                                      decode steps): without an activation it adds the residual to the fp32 (acc + bias) and rounds once */
   int64_t ldr;
   const void* act_bwd_z; /* optional bf16 z [M][ldz]: multiply by act'(z) (GELU backward)    */
   int64_t ldz;
@@ -88,13 +91,14 @@ typedef struct mpv_gemm_epilogue {
   const float* alpha_dev; /* optional device scalar multiplier                                */
   float alpha;            /* host scalar multiplier (0 -> 1)                                  */
   int out_f32;            /* C is fp32 (no epilogue besides alpha / accumulate)               */
-  int accumulate;         /* C += result                                                      */
+  int accumulate;         /* C += result: bf16(bf16(result) + C_old) for a bf16 C on every path, the split-K reduce included */
   void* colsum_out;       /* wgrad only: bf16 [M] = column sums of A over the (mapped) reduction rows,
                              i.e. the bias gradient that goes with dW = dY^T X, fused into the same pass */
   int tile_hint;          /* 0: the library picks the tile kernel per problem; 128 / 256 pin the 128x128 or the
                              256x256 eight-phase kernel where it applies, 192 / 160 its 192- and 160-row tile variants
                              (tests and measurements)                                                          */
-  void* row_tap_out;      /* optional bf16 [ceil(M / row_tap_group)][N]: rows m with m % row_tap_group == 0 ALSO store
+  void* row_tap_out;      /* optional bf16 [ceil(M / row_tap_group)][N] (forward / dgrad on the tile kernels; with any epilogue, a
+                             bias-only one included): rows m with m % row_tap_group == 0 ALSO store
                              bf16(acc * alpha + bias) -- before activation / dropout / residual -- at row m / group.
                              The ViT block uses it to take the per-frame cls rows of the spatial projection out of the
                              GEMM whose residual epilogue writes x + proj(.) for all rows (vision_transformer.py:263-270) */

@@ -3,7 +3,7 @@ ONLY: they let the real host pipelines (vision.py / gpt3.py / pretrain.py: row m
 composed temporal-projection backward) run on CPU inside `-m "not gpu"` tests and be checked against the reference goldens.
 Each function restates the contract of its C entry point in include/mpv.h (same arguments as the ops.py wrapper, bf16
 storage, fp32 arithmetic, bf16 rounding at the points the kernels round) with plain indexing -- no attempt at speed, tiny
-shapes only.  Dropout is not modelled (the counter-hash masks live in the kernels): every stand-in asserts dropout_p == 0, except the
+shapes only.  Dropout is not modelled (the counter-hash masks live in the kernels): every stand-in asserts dropout_p == 0, except gemm and the
 LayerNorm entry points, which take their mask from the host replica of the hash in tests/ref_norm.py (_hash_dropout).
 Nothing in the product imports this file; tests install it with `install(monkeypatch)`."""
 import math
@@ -44,8 +44,16 @@ def _r16(x):
     return x.to(BF).float()
 
 
-ACT_NONE, ACT_GELU_ERF, ACT_GELU_TANH, ACT_RELU = 0, 1, 2, 3
+ACT_NONE, ACT_GELU_ERF, ACT_GELU_TANH, ACT_RELU, ACT_DERIV = 0, 1, 2, 3, 4
 IDENT = (0, 0, 0)
+# tests/test_gemm_refs_cpu.py only: a named defect injected into gemm() to show that the gates of tests/gemm_cases.py reject it --
+# "bf16_partials" | "act_unrounded" | "drop_last_k" | "alpha_after_bias"; None everywhere else
+GEMM_MUTATION = None
+# tests/test_gemm_refs_cpu.py only: gemm() to the letter of include/mpv.h where it goes through gates measured on the kernels -- the fp32
+# accumulator holds the correctly rounded sum (formed in fp64: no summation order of the host's BLAS in the result), and the small-M
+# forward kernel's documented exception (residual added to the unrounded sum) is modelled.  False everywhere else: the host pipelines'
+# recorded traces and goldens were made without either
+GEMM_STRICT = False
 
 
 def _act(v, kind):
@@ -74,7 +82,6 @@ def gemm(a, b, M, N, K, *, out=None, trans_a=False, trans_b=False, lda=None, ldb
     switches (ops.gemm): preact_out receives bf16(act'(zb)) and the dgrad multiplies by that tensor (MPV_ACT_DERIV)."""
     from youku_mplug_amd import ops as _ops
     deriv_on = _ops.GELU_DERIV_FWD
-    assert dropout_p == 0.0, "stand-ins do not model the hash dropout"
     assert not (trans_a and not trans_b)
     lda = lda if lda is not None else (M if trans_a else K)
     ldb = ldb if ldb is not None else (N if trans_b else K)
@@ -84,12 +91,19 @@ def gemm(a, b, M, N, K, *, out=None, trans_a=False, trans_b=False, lda=None, ldb
     kr = _rows(kmap, K)
     A = _rd(a, kr, lda, M).t() if trans_a else _rd(a, _rows(amap, M), lda, K)          # [M, K]
     Bm = _rd(b, kr, ldb, N) if trans_b else _rd(b, torch.arange(N), ldb, K).t()        # [K, N]
-    acc = A @ Bm
+    if GEMM_MUTATION == "drop_last_k":
+        A, Bm = A[:, :-1], Bm[:-1]
+    if GEMM_MUTATION == "bf16_partials":          # the running sum rounded to bf16 between K-tiles of 64
+        acc = torch.zeros(M, N)
+        for k0 in range(0, A.shape[1], 64):
+            acc = _r16(acc + A[:, k0:k0 + 64] @ Bm[k0:k0 + 64])
+    else:
+        acc = (A.double() @ Bm.double()).float() if GEMM_STRICT else A @ Bm
     al = (alpha if alpha != 0.0 else 1.0) * (float(alpha_dev.float().item()) if alpha_dev is not None else 1.0)
     crow = _rows(cmap, M)
     if colsum_out is not None:
         assert trans_a and trans_b and not out_f32
-        _flat(colsum_out)[:M] = A.sum(1).to(BF)
+        _flat(colsum_out)[:M] = (A.double() if GEMM_STRICT else A).sum(1).to(BF)
     if out_f32:
         v = acc * al
         if accumulate:
@@ -98,13 +112,20 @@ def gemm(a, b, M, N, K, *, out=None, trans_a=False, trans_b=False, lda=None, ldb
         return out
     z = acc * al
     if bias is not None:
-        z = z + _flat(bias)[:N].float()[None, :]
-    zb = _r16(z)
+        z = (acc + _flat(bias)[:N].float()[None, :]) * al if GEMM_MUTATION == "alpha_after_bias" else z + _flat(bias)[:N].float()[None, :]
+    zb = z if GEMM_MUTATION == "act_unrounded" else _r16(z)
     if colscale is not None:          # mpv.h colscale: columns below ncols are rounded, scaled, rounded again
         assert not (act or act_bwd or residual is not None or preact_out is not None or accumulate or row_tap_out is not None)
         zb = zb.clone()
         zb[:, :colscale[0]] = _r16(zb[:, :colscale[0]] * colscale[1])
     v = zb
+    # mpv.h, residual: the small-M forward kernel (the decode branch of mpv_gemm_bf16) without an activation adds the residual to the
+    # unrounded sum
+    decode = (not trans_a and not trans_b and M <= 16 and not accumulate and dropout_p == 0.0 and not (act_bwd_z is not None and act_bwd)
+              and preact_out is None and alpha_dev is None and row_tap_out is None and colscale is None and alpha in (0.0, 1.0)
+              and amap[0] == 0 and colsum_out is None)
+    if GEMM_STRICT and decode and not act and residual is not None:
+        v = z
     if row_tap_out is not None:
         sel = torch.arange(0, M, row_tap_group)
         _wr(row_tap_out, torch.arange(len(sel)), N, zb[sel])
@@ -114,7 +135,8 @@ def gemm(a, b, M, N, K, *, out=None, trans_a=False, trans_b=False, lda=None, ldb
         v = _act(v, act)
     if act_bwd_z is not None and act_bwd:
         zz = _rd(act_bwd_z, torch.arange(M), ldz if ldz else N, N)
-        v = v * (zz if (z_is_deriv and deriv_on) else _act_grad(zz, act_bwd))
+        v = v * (zz if ((z_is_deriv and deriv_on) or act_bwd == ACT_DERIV) else _act_grad(zz, act_bwd))
+    v = _hash_dropout(v, torch.arange(M), N, dropout_p, seed, offset)          # (index: the row NUMBER, not the mapped row)
     if residual is not None:
         v = v + _rd(residual, crow, ldr if ldr else ldc, N)
     if accumulate:
@@ -124,7 +146,7 @@ def gemm(a, b, M, N, K, *, out=None, trans_a=False, trans_b=False, lda=None, ldb
 
 
 def _hash_dropout(v, rows, cols, p, seed, offset):
-    """The counter-hash dropout of the LayerNorm entry points only (the other stand-ins still assert dropout_p == 0): v [n, cols]
+    """The counter-hash dropout of gemm and the LayerNorm entry points only (the other stand-ins still assert dropout_p == 0): v [n, cols]
     fp32, element index offset + rows[i] * cols + column; v * fp32(1 / (1 - p)) where tests/ref_norm.py keep_mask keeps, +0 elsewhere."""
     if p == 0.0:
         return v

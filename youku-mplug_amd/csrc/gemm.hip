@@ -317,7 +317,8 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const GemmArgs p, con
   // Plain epilogue (bias only, bf16 out: the qkv / projection GEMMs and every plain dgrad): add the bias in the MFMA
   // layout, round to bf16 in registers and stage the WHOLE tile once as bf16 (pitch 136 elements) -- half the LDS
   // traffic and one barrier pair instead of two; the stores stay 16-byte row-contiguous.
-  if (parts == 1 && !p.out_f32 && !p.act && !p.act_bwd && !p.residual && !p.drop_thr && !p.accumulate && !p.preact) {
+  // (row_tap_out is stored by the general epilogue below: with a bias-only epilogue this path used to return without writing it)
+  if (parts == 1 && !p.out_f32 && !p.act && !p.act_bwd && !p.residual && !p.drop_thr && !p.accumulate && !p.preact && !p.tap_out) {
     constexpr int BP = 136;
     bf16* cb = (bf16*)smem;
 #pragma unroll
@@ -535,7 +536,7 @@ __global__ void splitk_reduce_kernel(const float* part, bf16* out, long long MN,
     s = cvt4(cvt4(s));                                                            // the unsplit epilogue drops bf16(acc + bias)
     s = mpv_dropout_vec<f32x4, 4>(s, mpv_resolve_seed(epi.seed), epi.drop_offset + (uint64_t)i, epi.drop_thr, epi.drop_scale);
   }
-  if (accumulate) s += cvt4(*(const bf16x4*)(out + i));
+  if (accumulate) s = cvt4(cvt4(s)) + cvt4(*(const bf16x4*)(out + i));      // C += bf16(result), as the unsplit epilogues accumulate
   *(bf16x4*)(out + i) = cvt4(s);
 }
 
@@ -649,6 +650,8 @@ __global__ __launch_bounds__(64 * NW) void gemm_small_m_kernel(const SmallMArgs 
       v = p.act == 1 ? gelu_erf_f(z) : p.act == 2 ? gelu_tanh_f(z) : fmaxf(z, 0.f);
     }
     const long long crow = map_row(p.cmap, m);
+    // NOTE (include/mpv.h, residual): without an activation this kernel adds the residual to the fp32 sum and rounds ONCE; the tile
+    // kernels round the product to bf16 first.  Kept: the decode steps' sampled tokens are pinned by tests on these bits.
     if (p.residual) v += bf2f(p.residual[crow * p.ldr + n]);
     p.C[crow * p.ldc + n] = f2bf(v);
   }
