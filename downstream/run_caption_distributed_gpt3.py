@@ -42,6 +42,11 @@ What this entry point adds to downstream/finetune_common.py:
     clip's rows go to the next clip while the others continue (`model.generate(..., do_sample=True, inflight=True)`: continuous
     batching; needs one of those two flags and `--eval_shared_kv`; it replaces `--eval_sample_mixed_prompts`, which it is refused
     with); the beam-search calls are not touched; same result files;
+  * `--eval_beam_inflight` (not in the reference, default off; implies nothing else): the lockstep beam search (`--eval_batched_beam`,
+    with or without `--eval_beam_groups`) runs ONE loop over all the clips of a batch in which `--clips_per_search` clips stay resident
+    and a finished clip's beams go to the next clip while the others continue (`model.generate(..., batched=True, beam_inflight=True)`;
+    needs `--eval_batched_beam` and `--eval_shared_kv`; refused with `--eval_mixed_prompts` and with the sampling flags); same result
+    files;
   * `--eval_score_gold` (not in the reference, default off): evaluation also scores every clip's `gold_caption` list, teacher-forced,
     against the query features computed once for that clip (`model.score_captions(..., query_features=)`: one packed pass per batch,
     no padding rows), adds "gold_logprob" / "gold_tokens" lists to the result entries and logs the corpus per-token NLL and perplexity;
@@ -76,7 +81,7 @@ def make_training_batch(video, text, prompt, tokenizer, device, max_length):
 @torch.no_grad()
 def evaluation(model, data_loader, tokenizer, device, config, batched=False, clips_per_search=32, eval_sample=0, seed=0, shared_kv=False,
                constraints=None, best_of=0, score_gold=False, max_length=None, beam_groups=1, diversity_penalty=0.0, fp8_decode=False,
-               mixed_prompts=False, sample_mixed_prompts=False, sample_inflight=False):
+               mixed_prompts=False, sample_mixed_prompts=False, sample_inflight=False, beam_inflight=False):
     """-> [{video_id, pred_caption, gold_caption}] (:208-238); batched: `--eval_batched_beam`; eval_sample: `--eval_sample`;
     shared_kv: `--eval_shared_kv`, constraints: the keywords of `--eval_repetition_penalty` / `--eval_no_repeat_ngram` /
     `--eval_min_new_tokens` (the lockstep calls only); best_of: `--eval_sample_best_of` (the prediction is the best of that many
@@ -85,7 +90,7 @@ def evaluation(model, data_loader, tokenizer, device, config, batched=False, cli
     diversity_penalty: `--eval_beam_groups` / `--eval_diversity_penalty` (the prediction is the most likely hypothesis of a diverse beam
     search, all of them in "pred_candidates"); fp8_decode: `--eval_fp8_decode`; mixed_prompts: `--eval_mixed_prompts` (the
     lockstep beam-search calls only); sample_mixed_prompts: `--eval_sample_mixed_prompts` (the sampling calls only); sample_inflight:
-    `--eval_sample_inflight` (the sampling calls only)"""
+    `--eval_sample_inflight` (the sampling calls only); beam_inflight: `--eval_beam_inflight` (the lockstep beam-search calls only)"""
     module = getattr(model, "module", model)
     module.eval()
     kvkw = {"kv_cache": "shared_prefix"} if shared_kv else {}                # flag absent: the calls below are unchanged
@@ -101,6 +106,9 @@ def evaluation(model, data_loader, tokenizer, device, config, batched=False, cli
                          "--eval_sample_mixed_prompts")
     if sample_inflight:
         smixkw = {"inflight": True}
+    if beam_inflight:
+        _check_beam_inflight(batched, shared_kv, mixed_prompts, eval_sample or best_of or sample_mixed_prompts or sample_inflight)
+        mixkw = {"beam_inflight": True}
     result = []
     for n, (video, video_ids, gold_caption) in enumerate(data_loader):
         video = video.to(device, non_blocking=True).bfloat16()
@@ -144,6 +152,12 @@ def evaluation(model, data_loader, tokenizer, device, config, batched=False, cli
         if n == 0:
             print(result)
     return result
+
+
+def _check_beam_inflight(batched, shared_kv, mixed_prompts, sampling):
+    if not (batched and shared_kv) or mixed_prompts or sampling:
+        raise ValueError("--eval_beam_inflight needs --eval_batched_beam and --eval_shared_kv, without --eval_mixed_prompts and without "
+                         "the sampling flags (--eval_sample, --eval_sample_best_of, --eval_sample_mixed_prompts, --eval_sample_inflight)")
 
 
 def gold_tokens(tokenizer, prompt, captions, max_length):
@@ -320,7 +334,8 @@ def main(args, config):
                             **({"fp8_decode": True} if getattr(args, "eval_fp8_decode", False) else {}),
                             **({"mixed_prompts": True} if getattr(args, "eval_mixed_prompts", False) else {}),
                             **({"sample_mixed_prompts": True} if getattr(args, "eval_sample_mixed_prompts", False) else {}),
-                            **({"sample_inflight": True} if getattr(args, "eval_sample_inflight", False) else {}))
+                            **({"sample_inflight": True} if getattr(args, "eval_sample_inflight", False) else {}),
+                            **({"beam_inflight": True} if getattr(args, "eval_beam_inflight", False) else {}))
         final = save_result(result, args.result_dir, "val_caption_result")
         val_stats = cal_metric(final)
         if getattr(args, "eval_score_gold", False):
@@ -389,6 +404,9 @@ def get_args(argv=None):
                        help="--eval_sample / --eval_sample_best_of with --eval_shared_kv: one sampling loop over all clips of a batch with "
                             "--clips_per_search clips resident, a finished clip's rows refilled with the next clip "
                             "(model.generate(do_sample=True, inflight=True))")
+        p.add_argument("--eval_beam_inflight", action="store_true", default=False,
+                       help="--eval_batched_beam with --eval_shared_kv: one beam search over all clips of a batch with --clips_per_search "
+                            "clips resident, a finished clip's beams refilled with the next clip (model.generate(batched=True, beam_inflight=True))")
         p.add_argument("--eval_score_gold", action="store_true", default=False,
                        help="evaluation: also score every clip's gold captions against its query features (model.score_captions): "
                             "gold_logprob / gold_tokens in the result file, per-token NLL and perplexity in the log")
@@ -407,6 +425,9 @@ def get_args(argv=None):
     if args.eval_sample_inflight and (args.eval_sample_mixed_prompts or not ((args.eval_sample or args.eval_sample_best_of) and args.eval_shared_kv)):
         raise ValueError("--eval_sample_inflight needs --eval_sample N or --eval_sample_best_of N, and --eval_shared_kv, without "
                          "--eval_sample_mixed_prompts")
+    if args.eval_beam_inflight:
+        _check_beam_inflight(args.eval_batched_beam, args.eval_shared_kv, args.eval_mixed_prompts,
+                             args.eval_sample or args.eval_sample_best_of or args.eval_sample_mixed_prompts or args.eval_sample_inflight)
     constraint_keywords(args)                                               # refuses the flags without a lockstep mode
     config.setdefault("prompt", "")
     args.result_dir = os.path.join(args.output_dir, "result")

@@ -540,6 +540,16 @@ int mpv_gpt_prefill_ragged(const mpv_gpt_weights* w, void* const* kv_cache, int 
 /* beam re-order of all layers: dst[l][j] = src[l][idx[j]] for the first `rows` cached positions */
 int mpv_kv_reorder(void* const* src, void* const* dst, int layers, const int64_t* idx, int batch, int max_len, int rows,
                    int hidden, mpv_stream_t stream);
+/* beam re-order of the suffix cache of the steps entries, where every clip has written its own number of suffix rows: src and dst
+ * are two caches [layers][n_groups * fan * suffix_max][3 * hidden] bf16 (contiguous, 16-byte aligned, different), and ONE launch
+ * over all layers does, for sequence j of clip g = j / fan,  dst[l][j][0:r) = src[l][idx[j]][0:r)  with r = clamp(group_rows[g], 0,
+ * max_rows).  idx is DEVICE int64 [n_groups * fan] (mpv_beam_advance_steps' src_row: it never leaves the clip; an entry outside
+ * [0, n_groups * fan) moves nothing), group_rows DEVICE int32 [n_groups], max_rows (host) the largest count any clip may hold.
+ * Copies are 16 bytes wide.  A clip with r = 0 (a free slot, or one installed in this iteration) moves nothing; rows at or behind r
+ * are not written.  With every count equal to t the written region is mpv_gather_rows_ld's over (layer, sequence) with t rows.
+ * Refused: a NULL pointer, src == dst, hidden % 8 != 0, max_rows outside [0, suffix_max], a misaligned cache, layers > 65535. */
+int mpv_kv_suffix_reorder_steps(const void* src, void* dst, int layers, int n_groups, int fan, int suffix_max, const int64_t* idx,
+                                const int32_t* group_rows, int max_rows, int hidden, mpv_stream_t stream);
 /* ------------------------------------------------------------------------------------------
  * FP8 decoder weights (weight-only, opt-in, the decode steps of the frozen decoder; csrc/gemm_w8.hip).  Numeric contract:
  *   format   OCP e4m3fn (gfx950's native FP8, not fnuz), one fp32 scale per output row of a [N, K] nn.Linear weight (bf16 in).
@@ -711,6 +721,21 @@ typedef struct mpv_beam_advance_groups_desc {
   int64_t stop_token;
 } mpv_beam_advance_groups_desc;
 int mpv_beam_advance_groups(const mpv_beam_advance_groups_desc* d, mpv_stream_t stream);
+/* mpv_beam_advance_groups (groups = 1: mpv_beam_advance) for clips that sit at different generation steps -- a finished clip's slot
+ * was given to the next clip while the others went on (generation.beam_inflight_loop).  clip_prompt_len and clip_step are DEVICE
+ * int32 [d->batch], one value per real clip (not per (clip, group)); the token table is LEFT-aligned, clip c's prompt in columns
+ * [0, clip_prompt_len[c]).  For clip c with s = clip_step[c] the call uses pos = clamp(clip_prompt_len[c], 0, row_len) + s,
+ * cur_len = s + 1 and first = (s == 0) for all of the clip's groups; d->pos, d->cur_len and d->first are ignored and not checked.
+ * A clip with s < 0 (a free slot) or pos >= row_len is FROZEN with all its groups: rows copied to tokens_out, identity src_row, the
+ * stop token in next_tok; nothing else is written -- done included -- and neither a candidate nor the done flag is read.
+ * Contract: a clip at step s is, bit for bit in every state array and output, the uniform entry (mpv_beam_advance_groups, or
+ * mpv_beam_advance at groups = 1) on that clip alone with pos = prompt_len + s, cur_len = s + 1, first = (s == 0); with one common
+ * step the call is the uniform entry on the whole batch.  The same kernel body, compiled with one more flag; a workgroup reads its
+ * clip's two values once (they are wave-uniform).  One entry serves the plain and the group search.
+ * Refused before any launch, the outputs untouched: what mpv_beam_advance_groups refuses except the pos / cur_len checks, and a NULL
+ * clip_prompt_len or clip_step. */
+int mpv_beam_advance_steps(const mpv_beam_advance_groups_desc* d, const int32_t* clip_prompt_len, const int32_t* clip_step,
+                           mpv_stream_t stream);
 /* ------------------------------------------------------------------------------------------
  * Sampled generation in lockstep (generation.sample_batched_loop): ONE launch draws the next token of `rows` sequences and does the
  * bookkeeping of one iteration of the reference's sample loop (models/modeling_distributed_gpt3.py:1689-1728).  The filters follow

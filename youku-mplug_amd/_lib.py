@@ -303,6 +303,8 @@ _SIGS.update({
     "mpv_sample_advance_steps": (c_int, [C.POINTER(SampleAdvanceDesc), c_void_p, c_void_p]),
     "mpv_logits_constrain_steps": (c_int, [C.POINTER(LogitsConstrainDesc), c_void_p, c_void_p]),
     "mpv_sample_score_steps": (c_int, [C.POINTER(SampleScoreDesc), c_void_p, c_void_p]),
+    "mpv_beam_advance_steps": (c_int, [C.POINTER(BeamAdvanceGroupsDesc), c_void_p, c_void_p, c_void_p]),
+    "mpv_kv_suffix_reorder_steps": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
 })
 
 EXPORTS = tuple(_SIGS)

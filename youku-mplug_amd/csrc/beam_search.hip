@@ -9,6 +9,8 @@
 // mpv_beam_advance is the G = 1 case: it fills a groups descriptor with groups = 1, diversity_penalty = 0 and goes through the same
 // check-and-launch.  The kernel body is written once and compiled twice, beam_advance_kernel<192, true> for G > 1 and <128, false>
 // for G = 1 ("Merged", has the measurement that asked for the second instantiation).
+// mpv_beam_advance_steps is both with a generation step per clip (clips that entered a running search at different times, DESIGN.md
+// section 27): the third template flag, STEPS, compiled into two more instantiations; the two above are compiled with STEPS = false.
 //
 // One workgroup of one wave per clip; nothing is shared between clips, so a clip's result depends neither on the batch size nor
 // on its place in the batch.  The clip's groups are walked one after the other inside the wave; per group, on a candidate list of
@@ -47,9 +49,14 @@ __device__ __forceinline__ bool ba_before(float va, long long ka, int ia, float 
   return va > vb || (va == vb && (ka < kb || (ka == kb && ia < ib)));
 }
 
-// GROUPS = false is the body at G = 1 with the group loop, the penalty and the emitted-token list compiled away
-template <int MAX_CAND, bool GROUPS>
-__global__ __launch_bounds__(64) void beam_advance_kernel(mpv_beam_advance_groups_desc d) {
+// GROUPS = false is the body at G = 1 with the group loop, the penalty and the emitted-token list compiled away.
+// STEPS = true (mpv_beam_advance_steps) is the body with a generation step per clip: the workgroup reads clip_prompt_len[clip] and
+// clip_step[clip] once (one address for the whole wave, so the three values below are wave-uniform) in place of d.pos / d.cur_len /
+// d.first; a clip with a negative step, or whose column lies behind the table, takes the frozen path with all its groups and reads
+// neither a candidate nor its done flag.  With STEPS = false the two arrays are not touched (the callers pass null).
+template <int MAX_CAND, bool GROUPS, bool STEPS>
+__global__ __launch_bounds__(64) void beam_advance_kernel(mpv_beam_advance_groups_desc d, const int32_t* __restrict__ clip_prompt_len,
+                                                          const int32_t* __restrict__ clip_step) {
   __shared__ float c_val[MAX_CAND];
   __shared__ long long c_key[MAX_CAND];
   __shared__ long long c_tok[MAX_CAND];
@@ -63,6 +70,13 @@ __global__ __launch_bounds__(64) void beam_advance_kernel(mpv_beam_advance_group
   const int lane = threadIdx.x, K = d.beams, K2 = 2 * K, G = GROUPS ? d.groups : 1, M = K2 + (G - 1) * K, Lt = d.row_len;
   const float lambda = d.diversity_penalty;
   int n_emit = 0;                                        // wave-uniform
+  int pos = d.pos, cur_len = d.cur_len;
+  bool first = d.first != 0, idle = false;
+  if constexpr (STEPS) {
+    const int s = clip_step[blockIdx.x], pl = min(max(clip_prompt_len[blockIdx.x], 0), Lt);
+    idle = s < 0 || s >= Lt - pl;                        // pl + s >= Lt without the sum (s may be anything)
+    pos = idle ? 0 : pl + s, cur_len = idle ? 1 : s + 1, first = s == 0;
+  }
 
   for (int g = 0; g < G; ++g) {
     __syncthreads();                                     // the LDS of the group before: e_tok written, c_* / s_* / n_* read
@@ -70,7 +84,7 @@ __global__ __launch_bounds__(64) void beam_advance_kernel(mpv_beam_advance_group
     const int64_t* tin = d.tokens_in + row0 * Lt;
     int64_t* tout = d.tokens_out + row0 * Lt;
 
-    if (d.done[b]) {                                     // frozen: wave-uniform
+    if ((STEPS && idle) || d.done[b]) {                  // frozen: wave-uniform
       for (int j = 0; j < K; ++j)
         for (int t = lane; t < Lt; t += 64) tout[(long long)j * Lt + t] = tin[(long long)j * Lt + t];
       if (lane < K) {
@@ -81,7 +95,7 @@ __global__ __launch_bounds__(64) void beam_advance_kernel(mpv_beam_advance_group
     }
 
     // ---- 1. penalise and rank
-    const int n_cand = d.first ? M : K * M;              // the first step reads beam 0 of the group only (:1793-1795)
+    const int n_cand = first ? M : K * M;                // the first step reads beam 0 of the group only (:1793-1795)
     for (int i = lane; i < n_cand; i += 64) {
       const long long tok = d.cand_idx[row0 * M + i];
       const float v = d.cand_val[row0 * M + i];
@@ -159,7 +173,7 @@ __global__ __launch_bounds__(64) void beam_advance_kernel(mpv_beam_advance_group
     }
 
     // ---- 3. finish
-    const bool now_done = count == K && worst >= (double)s_val[0] / (double)d.cur_len;      // is_done (:1946-1960)
+    const bool now_done = count == K && worst >= (double)s_val[0] / (double)cur_len;        // is_done (:1946-1960)
     if (lane == 0) {
 #pragma unroll
       for (int j = 0; j < BA_MAX_K; ++j)
@@ -187,7 +201,7 @@ __global__ __launch_bounds__(64) void beam_advance_kernel(mpv_beam_advance_group
       const bool have = j < n_next;
       const int beam = have ? n_beam[j] : j;
       const long long tok = have ? n_tok[j] : d.stop_token;
-      for (int t = lane; t < Lt; t += 64) tout[(long long)j * Lt + t] = t == d.pos ? tok : tin[(long long)beam * Lt + t];
+      for (int t = lane; t < Lt; t += 64) tout[(long long)j * Lt + t] = t == pos ? tok : tin[(long long)beam * Lt + t];
       if (lane == 0) {
         d.scores[row0 + j] = have ? n_val[j] : -INFINITY;
         d.src_row[row0 + j] = row0 + beam;
@@ -201,19 +215,45 @@ __global__ __launch_bounds__(64) void beam_advance_kernel(mpv_beam_advance_group
 }
 
 // the refusals both entry points share, then the launch; `who` names the entry point in the messages
-int beam_advance_launch(const mpv_beam_advance_groups_desc& d, const char* who, hipStream_t stream) {
+// steps = true (mpv_beam_advance_steps): pos / cur_len / first come per clip from the two device arrays, the descriptor's are not looked at
+int beam_advance_launch(const mpv_beam_advance_groups_desc& d, const char* who, hipStream_t stream, bool steps = false,
+                        const int32_t* clip_prompt_len = nullptr, const int32_t* clip_step = nullptr) {
   MPV_REQUIRE(d.row_len >= 1 && d.row_len <= BA_MAX_LT, MPV_E_SHAPE, "%s: row_len (%d) must be in [1, %d]", who, d.row_len, BA_MAX_LT);
-  MPV_REQUIRE(d.batch >= 1 && d.vocab >= 1 && d.cur_len >= 1 && d.pos >= 0 && d.pos < d.row_len, MPV_E_SHAPE,
-              "%s: bad shape batch=%d vocab=%d cur_len=%d pos=%d (row_len %d)", who, d.batch, d.vocab, d.cur_len, d.pos, d.row_len);
+  if (steps) {
+    MPV_REQUIRE(d.batch >= 1 && d.vocab >= 1, MPV_E_SHAPE, "%s: bad shape batch=%d vocab=%d", who, d.batch, d.vocab);
+    MPV_REQUIRE(clip_prompt_len, MPV_E_ARG, "%s: null clip_prompt_len", who);
+    MPV_REQUIRE(clip_step, MPV_E_ARG, "%s: null clip_step", who);
+  } else {
+    MPV_REQUIRE(d.batch >= 1 && d.vocab >= 1 && d.cur_len >= 1 && d.pos >= 0 && d.pos < d.row_len, MPV_E_SHAPE,
+                "%s: bad shape batch=%d vocab=%d cur_len=%d pos=%d (row_len %d)", who, d.batch, d.vocab, d.cur_len, d.pos, d.row_len);
+  }
   MPV_REQUIRE(d.cand_val && d.cand_idx && d.tokens_in && d.tokens_out && d.scores && d.hyp_score && d.hyp_order && d.hyp_tokens &&
                   d.hyp_count && d.hyp_next && d.worst && d.done && d.src_row && d.next_tok,
               MPV_E_ARG, "%s: null pointer", who);
   MPV_REQUIRE(d.tokens_in != d.tokens_out, MPV_E_ARG, "%s: tokens_in and tokens_out must be different tables", who);
-  if (d.groups == 1)
-    hipLaunchKernelGGL((beam_advance_kernel<BA_MAX_CAND_PLAIN, false>), dim3((unsigned)d.batch), dim3(64), 0, stream, d);
+  const dim3 grid((unsigned)d.batch), block(64);
+  const int32_t* none = nullptr;
+  if (steps && d.groups == 1)
+    hipLaunchKernelGGL((beam_advance_kernel<BA_MAX_CAND_PLAIN, false, true>), grid, block, 0, stream, d, clip_prompt_len, clip_step);
+  else if (steps)
+    hipLaunchKernelGGL((beam_advance_kernel<BA_MAX_CAND, true, true>), grid, block, 0, stream, d, clip_prompt_len, clip_step);
+  else if (d.groups == 1)
+    hipLaunchKernelGGL((beam_advance_kernel<BA_MAX_CAND_PLAIN, false, false>), grid, block, 0, stream, d, none, none);
   else
-    hipLaunchKernelGGL((beam_advance_kernel<BA_MAX_CAND, true>), dim3((unsigned)d.batch), dim3(64), 0, stream, d);
+    hipLaunchKernelGGL((beam_advance_kernel<BA_MAX_CAND, true, false>), grid, block, 0, stream, d, none, none);
   return mpv_check_launch(who);
+}
+
+// what mpv_beam_advance_groups and mpv_beam_advance_steps refuse about the groups of a descriptor
+int beam_groups_check(const mpv_beam_advance_groups_desc* d, const char* who) {
+  MPV_REQUIRE(d, MPV_E_ARG, "%s: null descriptor", who);
+  MPV_REQUIRE(d->beams >= 1 && d->beams <= BA_MAX_K, MPV_E_SHAPE, "%s: beams per group (%d) must be in [1, %d]", who, d->beams, BA_MAX_K);
+  MPV_REQUIRE(d->groups >= 1 && d->groups <= BA_MAX_G, MPV_E_SHAPE, "%s: groups (%d) must be in [1, %d]", who, d->groups, BA_MAX_G);
+  MPV_REQUIRE(d->groups * d->beams <= BA_MAX_SEQ, MPV_E_SHAPE, "%s: groups * beams (%d x %d) must be at most %d", who, d->groups, d->beams,
+              BA_MAX_SEQ);
+  MPV_REQUIRE(d->diversity_penalty >= 0.f && d->diversity_penalty <= 3.402823466e+38f, MPV_E_ARG,
+              "%s: diversity_penalty (%g) must be finite and not negative", who, (double)d->diversity_penalty);
+  return MPV_OK;
 }
 
 }  // namespace
@@ -233,14 +273,12 @@ extern "C" int mpv_beam_advance(const mpv_beam_advance_desc* d, hipStream_t stre
 }
 
 extern "C" int mpv_beam_advance_groups(const mpv_beam_advance_groups_desc* d, hipStream_t stream) {
-  MPV_REQUIRE(d, MPV_E_ARG, "mpv_beam_advance_groups: null descriptor");
-  MPV_REQUIRE(d->beams >= 1 && d->beams <= BA_MAX_K, MPV_E_SHAPE, "mpv_beam_advance_groups: beams per group (%d) must be in [1, %d]",
-              d->beams, BA_MAX_K);
-  MPV_REQUIRE(d->groups >= 1 && d->groups <= BA_MAX_G, MPV_E_SHAPE, "mpv_beam_advance_groups: groups (%d) must be in [1, %d]", d->groups,
-              BA_MAX_G);
-  MPV_REQUIRE(d->groups * d->beams <= BA_MAX_SEQ, MPV_E_SHAPE, "mpv_beam_advance_groups: groups * beams (%d x %d) must be at most %d",
-              d->groups, d->beams, BA_MAX_SEQ);
-  MPV_REQUIRE(d->diversity_penalty >= 0.f && d->diversity_penalty <= 3.402823466e+38f, MPV_E_ARG,
-              "mpv_beam_advance_groups: diversity_penalty (%g) must be finite and not negative", (double)d->diversity_penalty);
-  return beam_advance_launch(*d, "mpv_beam_advance_groups", stream);
+  const int rc = beam_groups_check(d, "mpv_beam_advance_groups");
+  return rc ? rc : beam_advance_launch(*d, "mpv_beam_advance_groups", stream);
+}
+
+extern "C" int mpv_beam_advance_steps(const mpv_beam_advance_groups_desc* d, const int32_t* clip_prompt_len, const int32_t* clip_step,
+                                      hipStream_t stream) {
+  const int rc = beam_groups_check(d, "mpv_beam_advance_steps");
+  return rc ? rc : beam_advance_launch(*d, "mpv_beam_advance_steps", stream, true, clip_prompt_len, clip_step);
 }

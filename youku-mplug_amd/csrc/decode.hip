@@ -42,6 +42,39 @@ __global__ void steps_scatter_kernel(const uint4* __restrict__ qkv, const int32_
   }
 }
 
+// The beam re-order of the steps entries' suffix cache, all layers in one launch: sequence j of clip g = j / fan continues from the
+// first r = clamp(group_rows[g], 0, max_rows) suffix rows of sequence idx[j]; rows at or behind r, and all rows of a clip with r = 0,
+// are not written.  An idx[j] outside [0, n_seq) moves nothing (the advance never produces one).
+__global__ void steps_reorder_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, const int64_t* __restrict__ idx,
+                                     const int32_t* __restrict__ group_rows, long long n_seq, int fan, long long suffix_max, int max_rows,
+                                     int vecs) {                                        // vecs: 16-byte pieces of a 3H row
+  const long long j = blockIdx.x, l = blockIdx.y, from = idx[j];                        // one workgroup per (sequence, layer)
+  const int r = min(max(group_rows[j / fan], 0), max_rows);                            // max_rows <= suffix_max (the entry's check)
+  if (r == 0 || from < 0 || from >= n_seq) return;
+  const uint4* s = src + (l * n_seq + from) * suffix_max * vecs;
+  uint4* d = dst + (l * n_seq + j) * suffix_max * vecs;
+  for (int i = threadIdx.x; i < r * vecs; i += blockDim.x) d[i] = s[i];
+}
+
+extern "C" int mpv_kv_suffix_reorder_steps(const void* src, void* dst, int layers, int n_groups, int fan, int suffix_max, const int64_t* idx,
+                                           const int32_t* group_rows, int max_rows, int hidden, hipStream_t stream) {
+  const char* who = "mpv_kv_suffix_reorder_steps";
+  MPV_REQUIRE(src && dst && idx && group_rows, MPV_E_ARG, "%s: null pointer", who);
+  MPV_REQUIRE(src != dst, MPV_E_ARG, "%s: src and dst must be different caches", who);
+  MPV_REQUIRE(layers >= 1 && n_groups >= 1 && fan >= 1 && suffix_max >= 1 && hidden >= 8 && hidden % 8 == 0, MPV_E_SHAPE,
+              "%s: bad shape layers=%d n_groups=%d fan=%d suffix_max=%d hidden=%d (hidden %% 8 == 0)", who, layers, n_groups, fan, suffix_max, hidden);
+  MPV_REQUIRE(max_rows >= 0 && max_rows <= suffix_max, MPV_E_SHAPE, "%s: max_rows (%d) must be in [0, suffix_max = %d]", who, max_rows, suffix_max);
+  MPV_REQUIRE((uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0, MPV_E_ARG, "%s: the caches must be 16-byte aligned", who);
+  if (max_rows == 0) return MPV_OK;
+  const int vecs = 3 * hidden / 8;
+  const long long n_seq = (long long)n_groups * fan;
+  MPV_REQUIRE(layers <= 65535 && n_seq <= 0x7fffffffLL && (long long)max_rows * vecs <= 0x7fffffffLL, MPV_E_SHAPE,
+              "%s: layers=%d, %lld sequences or %d rows of %d hidden exceed the launch", who, layers, n_seq, max_rows, hidden);
+  hipLaunchKernelGGL(steps_reorder_kernel, dim3((unsigned)n_seq, (unsigned)layers), dim3(256), 0, stream, (const uint4*)src, (uint4*)dst, idx,
+                     group_rows, n_seq, fan, (long long)suffix_max, max_rows, vecs);
+  return mpv_check_launch(who);
+}
+
 static inline char* carve(char*& p, size_t bytes) {
   char* r = p;
   p += (bytes + 255) / 256 * 256;

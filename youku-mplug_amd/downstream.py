@@ -335,7 +335,7 @@ class DistributedGPT3_Caption(_GenCls):
                  top_k=None, top_p=None, seed=0, kv_cache="per_sequence", repetition_penalty=None, no_repeat_ngram_size=0, min_new_tokens=0,
                  banned_token_ids=None, constrain_prompt=False, return_scores=False, best_of=False, length_penalty=1.0, query_features=None,
                  beam_groups=1, diversity_penalty=0.0, rerank_by_logprob=False, decode_weights="bf16", mixed_prompts=False, sample_mixed_prompts=False,
-                 inflight=False, max_new_tokens=None, refill_min=None, **kw):
+                 inflight=False, max_new_tokens=None, refill_min=None, beam_inflight=False, **kw):
         """One beam search per sample (:790-809): prompt = text.input_ids[i, :mask.sum()-1], prefix = its query features.
         batched=True (not in the reference, default off): the clips are grouped by prompt length and every group is searched in
         lockstep, `clips_per_search` clips at a time (generation.beam_search_batched_loop: the decoder's weights are read once per
@@ -414,7 +414,15 @@ class DistributedGPT3_Caption(_GenCls):
         per clip, capped by the table's columns), and refills wait for refill_min free slots.  Prompts may differ in length as with
         sample_mixed_prompts, and streams, return value, return_scores and best_of are that call's: a clip's tokens depend neither on
         its slot nor on when it entered.  top_k=1 makes it a greedy captioner.  Use without do_sample=True or with
-        kv_cache="per_sequence" is refused."""
+        kv_cache="per_sequence" is refused.
+        beam_inflight=True (batched=True with kv_cache="shared_prefix" only; default off): the same for the BEAM search -- ONE loop over
+        all the clips, prompt lengths from the attention mask, that keeps clips_per_search clips (slots) x beam_groups * beam_size
+        sequences resident; a clip leaves when all its groups are done or after max_new_tokens positions (None: up to the end of the
+        table, the lockstep search's budget; an int or one budget per clip), and refills wait for refill_min free slots
+        (generation.beam_inflight_loop: a generation step per clip in the advance kernel, a row count per clip in the suffix
+        re-order).  The return value is the batched call's.  It combines with beam_groups, diversity_penalty, rerank_by_logprob,
+        decode_weights and the constraints, constrain_prompt=True included (this table has no padding).  Refused with do_sample, without
+        batched=True, with kv_cache="per_sequence" and together with mixed_prompts=True."""
         Q, Hh = self.num_learnable_token, self.text_width
         G = int(beam_groups)
         from . import generation as _gen
@@ -449,13 +457,24 @@ class DistributedGPT3_Caption(_GenCls):
                                  "step takes a prefix length per clip")
         if inflight:
             if not do_sample:
-                raise ValueError("inflight needs do_sample=True: beam search in flight would need a step per clip in the beam kernels "
-                                 "(greedy captions: do_sample=True with top_k=1)")
+                raise ValueError("inflight needs do_sample=True (beam search in flight: batched=True with beam_inflight=True; greedy "
+                                 "captions: do_sample=True with top_k=1)")
             if kv_cache != "shared_prefix":
                 raise ValueError(f'inflight needs kv_cache="shared_prefix" (got {kv_cache!r}): only the shared-prefix decode step takes a '
                                  "suffix position per clip")
-        elif max_new_tokens is not None or refill_min is not None:
-            raise ValueError("max_new_tokens / refill_min belong to inflight=True")
+        if beam_inflight:
+            if do_sample:
+                raise ValueError("beam_inflight does not combine with do_sample (sampled captions in flight: inflight=True)")
+            if not batched:
+                raise ValueError("beam_inflight needs batched=True: the per-clip search has one clip per call")
+            if kv_cache != "shared_prefix":
+                raise ValueError(f'beam_inflight needs kv_cache="shared_prefix" (got {kv_cache!r}): only the shared-prefix decode step takes '
+                                 "a suffix position per clip")
+            if mixed_prompts:
+                raise ValueError("beam_inflight does not combine with mixed_prompts=True: the in-flight search takes prompts of different "
+                                 "lengths as it is")
+        if not (inflight or beam_inflight) and (max_new_tokens is not None or refill_min is not None):
+            raise ValueError("max_new_tokens / refill_min belong to inflight=True (sampled captions) or beam_inflight=True (beam search)")
         Bv = image.shape[0] if query_features is None else query_features.shape[0] // Q
         was = self.training
         self.eval()
@@ -564,7 +583,16 @@ class DistributedGPT3_Caption(_GenCls):
                 lengths = (text.attention_mask.sum(-1) - 1).tolist()
                 res = [None] * n
                 groups_of = [None] * n
-                if mixed_prompts:                                        # input order, no grouping: one search per chunk with its lengths
+                if beam_inflight:                                        # ONE loop over all clips, clips_per_search slots resident
+                    more = {k: v for k, v in kw.items() if k != "kv"}
+                    outs = self.text_decoder.beam_search_inflight(text.input_ids, query_embeds=qf.contiguous(), stop_token=termination_id,
+                                                                  prompt_length=[int(x) for x in lengths], slots=int(clips_per_search),
+                                                                  max_new_tokens=max_new_tokens, refill_min=refill_min, **more).results
+                    for i, out in enumerate(outs):
+                        res[i] = out.sequences.cpu()
+                        groups_of[i] = getattr(out, "group", None)
+                    chunks = []
+                elif mixed_prompts:                                      # input order, no grouping: one search per chunk with its lengths
                     per = int(clips_per_search)
                     chunks = [list(range(c, min(c + per, n))) for c in range(0, n, per)]
                     chunks = [([int(lengths[i]) for i in chunk], chunk) for chunk in chunks]

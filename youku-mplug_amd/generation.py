@@ -460,6 +460,25 @@ class InflightDecodeState(_PrefixSuffixCaches):
     def _steps_step(self, tokens, group_t, max_t) -> torch.Tensor:
         return self._step_call(tokens, group_t, max_t)
 
+    def reorder(self, batch_idx: torch.Tensor, group_rows: torch.Tensor, max_rows: int):
+        """beam search only: sequence j continues from the suffix rows of sequence batch_idx[j] (int64 [slots * fan], inside j's slot),
+        of which slot g has written group_rows[g] (int32 [slots] on the device; 0: nothing of the slot moves), at most max_rows (host):
+        ONE launch over all layers into the twin (ops.kv_suffix_reorder_steps), which the first call allocates -- a sampling call
+        never does -- and which then becomes the suffix cache."""
+        if group_rows.dtype != torch.int32 or group_rows.numel() != self.slots or not group_rows.is_contiguous():
+            raise ValueError(f"InflightDecodeState.reorder: group_rows must be a contiguous int32 tensor of {self.slots} counts")
+        if not 0 <= int(max_rows) <= self.S:
+            raise ValueError(f"InflightDecodeState.reorder: {int(max_rows)} rows do not fit the suffix cache of {self.S} positions")
+        if int(max_rows) == 0:
+            return                                   # nothing generated yet: nothing to move
+        if self.twin is None:
+            self.twin = torch.zeros_like(self.suffix)
+            self._twin_ptrs = self.prefix._ptrs(self.twin)
+        ops.kv_suffix_reorder_steps(self.suffix, self.twin, batch_idx.contiguous(), group_rows, fan=self.fan, suffix_rows=self.S,
+                                    max_rows=int(max_rows))
+        self.suffix, self.twin = self.twin, self.suffix
+        self._suffix_ptrs, self._twin_ptrs = self._twin_ptrs, self._suffix_ptrs
+
 
 def make_inflight_state_fn(gpt, weights: str = "bf16"):
     """The make_state of sample_inflight_loop: (slots, fan, prefix_rows, suffix_rows) -> an InflightDecodeState on `weights`"""
@@ -682,21 +701,13 @@ def beam_search_batched_loop(cfg, make_state: Callable[[int, int], object], toke
     (the pad columns would count as prompt), 2 * Lt > 2048 columns (the advance kernels' limit), what _mixed_prompt_state refuses."""
     _no_sample_scores(return_scores, "beam_search_batched_loop")
     B, dev, K = tokens.size(0), tokens.device, int(beam_size)
-    G = int(beam_groups)
+    G, lam, per_group = _beam_groups(beam_groups, diversity_penalty, num_return_gen, K)
     if G != 1:
-        if G < 1 or isinstance(beam_groups, bool):
-            raise ValueError(f"beam_groups must be a positive integer (got {beam_groups!r})")
-        lam = float(diversity_penalty)
-        if not (math.isfinite(lam) and lam >= 0.0):
-            raise ValueError(f"diversity_penalty must be finite and not negative (got {diversity_penalty!r})")
-        if int(num_return_gen) % G or int(num_return_gen) // G > K or int(num_return_gen) < G:
-            raise ValueError(f"num_return_gen ({num_return_gen}) must be a multiple of beam_groups ({G}) with at most beam_size ({K}) "
-                             "rows per group")
         if group_advance_fn is None:
             raise ValueError("beam_groups > 1 needs a group_advance_fn (ops.beam_advance_groups)")
-        advance, more, per_group = group_advance_fn, dict(groups=G, diversity_penalty=lam), int(num_return_gen) // G
+        advance, more = group_advance_fn, dict(groups=G, diversity_penalty=lam)
     else:
-        advance, more, per_group = advance_fn, {}, num_return_gen
+        advance, more = advance_fn, {}
     constraints = _active_constraints(constraints, constrain_fn)
     lens = _mixed_prompt_lengths(prompt_length, B, tokens.size(1))                         # None: one prompt length
     stop_token = cfg.eod_id if stop_token is None else int(stop_token)
@@ -738,6 +749,27 @@ def beam_search_batched_loop(cfg, make_state: Callable[[int, int], object], toke
     h = SimpleNamespace(**{k: getattr(bs, k).cpu() for k in BeamState.ARRAYS})              # one download
     if lens is not None:
         _strip_left_padding(h, lens, flush, len_scale)
+    return _beam_results(h, B, G, K, per_group, dev)
+
+
+def _beam_groups(beam_groups, diversity_penalty, num_return_gen, K):
+    """the checks of a beam loop's group arguments -> (G, lambda, rows returned per group); one group: (1, 0.0, num_return_gen)"""
+    G = int(beam_groups)
+    if G == 1:
+        return 1, 0.0, num_return_gen
+    if G < 1 or isinstance(beam_groups, bool):
+        raise ValueError(f"beam_groups must be a positive integer (got {beam_groups!r})")
+    lam = float(diversity_penalty)
+    if not (math.isfinite(lam) and lam >= 0.0):
+        raise ValueError(f"diversity_penalty must be finite and not negative (got {diversity_penalty!r})")
+    if int(num_return_gen) % G or int(num_return_gen) // G > K or int(num_return_gen) < G:
+        raise ValueError(f"num_return_gen ({num_return_gen}) must be a multiple of beam_groups ({G}) with at most beam_size ({K}) "
+                         "rows per group")
+    return G, lam, int(num_return_gen) // G
+
+
+def _beam_results(h, B, G, K, per_group, dev):
+    """the downloaded BeamState arrays `h` of B clips x G groups -> the list of B result namespaces of the lockstep beam loops"""
     out = []
     for clip in range(B):
         ranked = [_ranked_hypotheses(h, clip * G + g, K)[:per_group] for g in range(G)]
@@ -1065,6 +1097,76 @@ def refill_min_default(slots: int) -> int:
     return max(1, int(slots) // 4)
 
 
+class _Slots:
+    """The refill bookkeeping of the in-flight loops (sample_inflight_loop, beam_inflight_loop), the host's mirror as Python ints: per
+    slot the clip it holds (-1: free) and the generation step its next advance works on; the n clips pass through in input order."""
+
+    def __init__(self, n: int, slots: int, refill_min, budgets):
+        self.n, self.slots, self.budgets = int(n), int(slots), budgets
+        self.refill_min = min(self.slots, refill_min_default(self.slots) if refill_min is None else int(refill_min))
+        if self.refill_min < 1:
+            raise ValueError(f"refill_min must be at least 1 (got {self.refill_min})")
+        self.clip_of, self.step_of, self.next_clip = [-1] * self.slots, [-1] * self.slots, 0
+
+    def busy(self) -> bool:
+        return self.next_clip < self.n or any(c >= 0 for c in self.clip_of)
+
+    def refill(self):
+        """-> (the slots that take a new clip now, their clips): all free slots (as far as clips are left) once refill_min are free, or
+        when nothing runs; both empty otherwise"""
+        free = [s for s in range(self.slots) if self.clip_of[s] < 0]
+        if not (self.next_clip < self.n and free and (len(free) >= self.refill_min or len(free) == self.slots)):
+            return [], []
+        fresh = free[:self.n - self.next_clip]
+        clips = list(range(self.next_clip, self.next_clip + len(fresh)))
+        self.next_clip += len(fresh)
+        for s, c in zip(fresh, clips):
+            self.clip_of[s], self.step_of[s] = c, 0
+        return fresh, clips
+
+    def running(self):
+        """the slots a decode step serves: those whose clip has advanced at least once"""
+        return [s for s in range(self.slots) if self.clip_of[s] >= 0 and self.step_of[s] >= 1]
+
+    def group_t(self):
+        """per slot the suffix position of the decode step: step - 1, negative (idle) for a fresh and for a free slot"""
+        return [self.step_of[s] - 1 if self.clip_of[s] >= 0 else -1 for s in range(self.slots)]
+
+    def steps(self):
+        """per slot the generation step of the advance; -1 for a free slot"""
+        return [self.step_of[s] if self.clip_of[s] >= 0 else -1 for s in range(self.slots)]
+
+    def advanced(self):
+        """after the advance: every occupied slot is one step further -> the occupied slots"""
+        active = [s for s in range(self.slots) if self.clip_of[s] >= 0]
+        for s in active:
+            self.step_of[s] += 1
+        return active
+
+    def spent(self, s) -> bool:
+        return self.step_of[s] >= self.budgets[self.clip_of[s]]
+
+    def release(self, s):
+        self.clip_of[s], self.step_of[s] = -1, -1
+
+
+def _inflight_budgets(cfg, max_new_tokens, default, lens, final_len, Q):
+    """max_new_tokens (None: `default`, one budget per clip; an int; or one budget per clip) -> the clips' budgets, capped by the
+    columns each prompt leaves in the table; the last position a clip feeds must be a row of the position table"""
+    n = len(lens)
+    budgets = _int_list(max_new_tokens)
+    if budgets is None:
+        budgets = list(default) if max_new_tokens is None else [int(max_new_tokens)] * n
+    if len(budgets) != n or min(budgets) < 1:
+        raise ValueError(f"max_new_tokens must be None, a positive int or {n} positive budgets (got {max_new_tokens!r})")
+    budgets = [min(b, final_len - pl) for b, pl in zip(budgets, lens)]                      # the table's columns behind the prompt
+    for c, (b, pl) in enumerate(zip(budgets, lens)):
+        if Q + pl + b - 2 >= cfg.max_position_embeddings:
+            raise ValueError(f"clip {c}: a prompt of {pl} tokens behind {Q} query slots with a budget of {b} feeds position {Q + pl + b - 2}; "
+                             f"the position table has {cfg.max_position_embeddings} rows")
+    return budgets
+
+
 def sample_inflight_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None, temperature=1.0, use_eod_token_for_early_termination=True,
                          stop_on_double_eol=False, stop_on_eol=False, termination_id=None, prompt_length=None, num_samples=1, slots=32,
                          max_new_tokens=None, refill_min=None, seed=0, streams=None, advance_fn=None,
@@ -1100,22 +1202,11 @@ def sample_inflight_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=Non
     sampler = _Sampler(cfg, dict(num_samples=num_samples, slots=slots), temperature, seed, termination_id, stop_on_double_eol, stop_on_eol,
                        advance_fn, constraints, constrain_fn, return_scores, score_fn, "sample_score_steps")
     lens = _mixed_prompt_lengths(prompt_length, n, tokens.size(1), "sample_inflight_loop")
-    refill_min = min(slots, refill_min_default(slots) if refill_min is None else int(refill_min))
-    if refill_min < 1:
-        raise ValueError(f"refill_min must be at least 1 (got {refill_min})")
+    sl = _Slots(n, slots, refill_min, None)
     longest = max(lens)
     table, final_len, Q = _pad_for_generation(cfg, tokens, cfg.eod_id, longest, query_embeds)
     table = table[:, :final_len]
-    budgets = _int_list(max_new_tokens)
-    if budgets is None:
-        budgets = [int(cfg.tokens_to_generate if max_new_tokens is None else max_new_tokens)] * n
-    if len(budgets) != n or min(budgets) < 1:
-        raise ValueError(f"max_new_tokens must be None, a positive int or {n} positive budgets (got {max_new_tokens!r})")
-    budgets = [min(b, final_len - pl) for b, pl in zip(budgets, lens)]                      # the table's columns behind the prompt
-    for c, (b, pl) in enumerate(zip(budgets, lens)):
-        if Q + pl + b - 2 >= cfg.max_position_embeddings:
-            raise ValueError(f"clip {c}: a prompt of {pl} tokens behind {Q} query slots with a budget of {b} feeds position {Q + pl + b - 2}; "
-                             f"the position table has {cfg.max_position_embeddings} rows")
+    budgets = sl.budgets = _inflight_budgets(cfg, max_new_tokens, [int(cfg.tokens_to_generate)] * n, lens, final_len, Q)
     R = slots * N
     state = make_state(slots, N, Q + longest, max(max(budgets) - 1, 1))
     streams = (torch.arange(n * N, dtype=torch.int64, device=dev) if streams is None
@@ -1131,15 +1222,10 @@ def sample_inflight_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=Non
     within = torch.arange(N, device=dev)
     rows_of = lambda ids: (torch.as_tensor(ids, dtype=torch.long).to(dev)[:, None] * N + within[None]).reshape(-1)   # the N rows of each slot / clip
     logits = None
-    clip_of, step_of, known_done = [-1] * slots, [-1] * slots, [0] * slots            # the host's mirror: clip, next sampler step, done rows
-    next_clip = 0
-    while next_clip < n or any(c >= 0 for c in clip_of):
-        free = [s for s in range(slots) if clip_of[s] < 0]
-        fresh = []
-        if next_clip < n and free and (len(free) >= refill_min or len(free) == slots):     # (0) the refill
-            fresh = free[:n - next_clip]
-            clips = list(range(next_clip, next_clip + len(fresh)))
-            next_clip += len(fresh)
+    clip_of, step_of, known_done = sl.clip_of, sl.step_of, [0] * slots                # the host's mirror (_Slots), and the done rows per slot
+    while sl.busy():
+        fresh, clips = sl.refill()
+        if fresh:                                                                          # (0) the refill
             sel = torch.as_tensor(clips, dtype=torch.long).to(dev)
             first = state.install(fresh, table[sel, :longest].contiguous(), None if query_embeds is None else query_embeds[sel].contiguous(),
                                   [lens[c] for c in clips])
@@ -1151,28 +1237,26 @@ def sample_inflight_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=Non
             st.done[fresh_rows] = 0
             if sc is not None:
                 sc.live[fresh_rows], sc.sum_logprob[fresh_rows], sc.count[fresh_rows], sc.token_logprob[fresh_rows] = 1, 0.0, 0, 0.0
-            for s, c in zip(fresh, clips):
-                clip_of[s], step_of[s], known_done[s] = c, 0, 0
-        running = [s for s in range(slots) if clip_of[s] >= 0 and step_of[s] >= 1]
+            for s in fresh:
+                known_done[s] = 0
+        running = sl.running()
         if running:                                                                        # (1) one decode step; fresh and free slots idle
-            group_t = torch.tensor([step_of[s] - 1 if clip_of[s] >= 0 else -1 for s in range(slots)], dtype=torch.int32).to(dev)
+            group_t = torch.tensor(sl.group_t(), dtype=torch.int32).to(dev)
             logits = state.step(st.next_tok.view(-1, 1), group_t, max(step_of[s] - 1 for s in running))
         elif logits is None:
             logits = torch.zeros((R, first.shape[1]), dtype=torch.bfloat16, device=dev)     # the first iteration; frozen rows read none of it
         if fresh:                                                                          # (2) the prefill logits of the fresh slots
             logits[fresh_rows] = first.repeat_interleave(N, dim=0)
-        row_step = torch.tensor([step_of[s] if clip_of[s] >= 0 else -1 for s in range(slots)], dtype=torch.int32).repeat_interleave(N).to(dev)
+        row_step = torch.tensor(sl.steps(), dtype=torch.int32).repeat_interleave(N).to(dev)
         sampler.step(logits, st, sc, row_step=row_step)                                    # (3) every row on its own step
-        active = [s for s in range(slots) if clip_of[s] >= 0]                              # (4) the bookkeeping
-        for s in active:
-            step_of[s] += 1
+        active = sl.advanced()                                                             # (4) the bookkeeping
         if use_eod_token_for_early_termination:
             expected = sum(known_done[s] for s in active) + N * (slots - len(active))      # frozen rows count as done
             if int(st.n_done.item()) != expected:                                          # the step's host read: 4 bytes; the vector on a change
                 done_h = st.done.view(slots, N).ne(0).sum(dim=1).tolist()
                 for s in active:
                     known_done[s] = done_h[s]
-        leaving = [s for s in active if known_done[s] == N or step_of[s] >= budgets[clip_of[s]]]
+        leaving = [s for s in active if known_done[s] == N or sl.spent(s)]
         if leaving:
             rows = rows_of(leaving)
             dst = rows_of([clip_of[s] for s in leaving])
@@ -1182,8 +1266,115 @@ def sample_inflight_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=Non
                 out_sc.token_logprob[dst] = sc.token_logprob[rows]
             for s in leaving:
                 written[clip_of[s]] = lens[clip_of[s]] + step_of[s]
-                clip_of[s], step_of[s], known_done[s] = -1, -1, 0
+                sl.release(s)
+                known_done[s] = 0
     return SimpleNamespace(tokens=out_tokens, written=written, scores=out_sc, steps=state.steps, prefills=state.prefills)
+
+
+BEAM_RESULT_ARRAYS = ("tokens", "scores", "hyp_score", "hyp_order", "hyp_tokens", "hyp_count", "hyp_next", "worst", "done")
+
+
+def beam_inflight_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None, beam_size=5, num_return_gen=1, stop_token=None,
+                       prompt_length=None, slots=32, max_new_tokens=None, refill_min=None, topk_fn=None, advance_fn=None,
+                       constraints: Optional["LogitsConstraints"] = None, constrain_fn=None, return_scores=False, beam_groups=1,
+                       diversity_penalty=0.0):
+    """beam_search_batched_loop with the finished clips' slots REFILLED in flight, as sample_inflight_loop does for samples: tokens
+    [n, L], query_embeds [n, Q, H], prompt_length n lengths; `slots` clips x G * K sequences stay resident (K = beam_size beams per
+    group, G = beam_groups) and the n clips of the call pass through them in input order.  A clip LEAVES when all its groups are done
+    or its budget is reached; its slot goes to the next clip (the refill rule, refill_min and their default are sample_inflight_loop's:
+    _Slots).
+    The token table is LEFT-aligned and Lt = L + tokens_to_generate wide, row_len = Lt for every clip: the table of the one-length
+    lockstep search.  A hypothesis scores value / row_len, so clip c's search is the one beam_search_batched_loop(prompt_length=
+    prompt_length[c]) runs on it -- no left padding, no len_scale -- and LogitsConstraints(include_prompt=True), which the mixed
+    lockstep search has to refuse, is allowed here.
+    make_state(slots, fan, prefix_rows, suffix_rows) -> an InflightDecodeState (make_inflight_state_fn), fan = G * K.  advance_fn is
+    the _steps advance (ops.beam_advance_steps: one entry for one group and for several), constrain_fn the _steps constraint
+    (ops.logits_constrain_steps), topk_fn as in beam_search_batched_loop; the group arguments are checked as there.  The search state
+    is a BeamState of slots * G pseudo-clips; a free slot has done = 1 on the device and step -1.
+    One iteration: (0) the refill (state.install); the fresh slots' rows of the CURRENT token table are reset to their clips' input
+    rows and their search state is cleared (scores 0, hyp_count 0, hyp_next 0, worst 1e9, done 0); (1) ONE decode step
+    (state.step(bs.next_tok, group_t, max_t)) for the slots already running, fresh and free slots idle in it; (2) the prefill logits
+    overwrite the fresh slots' rows; (3) constrain_fn(..., row_step=, prompt_len=) with the stop token as termination id and BAN_BEAM
+    (only with active constraints), topk_fn(logits, m, bs.scores), advance_fn(..., clip_prompt_len=, clip_step=), then the read of
+    bs.done, int32 [slots * G]: the step's one host read; (4) the host mirrors every slot's step as Python ints: a clip whose G groups
+    are all done, or whose budget is reached, leaves -- its BeamState rows are gathered ON THE DEVICE into the result arrays, in input
+    order and with `done` as it stood, then the slot's done is set to 1; (5) state.reorder(bs.src_row, group_rows, max_rows) with
+    group_rows[g] = group_t[g] + 1 for a slot that took part in this iteration's decode step and 0 otherwise.
+    After the loop the result arrays are downloaded ONCE and every (clip, group) is finished by _ranked_hypotheses; a clip that left
+    on its budget is not done, so its beams are flushed there as at the end of the lockstep loop.
+    max_new_tokens: None, an int, or n budgets.  None gives final_len - prompt_length[c], the LOCKSTEP SEARCH's budget (NOT
+    sample_inflight_loop's default of tokens_to_generate); budgets are capped by the table and the last position a clip feeds, Q +
+    prompt_length[c] + budget - 2, must be a row of the position table (a ValueError before the first launch otherwise).
+    -> a SimpleNamespace(results: the list of n namespaces beam_search_batched_loop returns (sequences, scores, group for G > 1),
+    advances [n]: the positions every clip was advanced by before it left, steps / prefills: decode steps and prefill passes issued)."""
+    _no_sample_scores(return_scores, "beam_inflight_loop")
+    n, dev, K, slots = tokens.size(0), tokens.device, int(beam_size), int(slots)
+    if advance_fn is None or topk_fn is None:
+        raise ValueError("beam_inflight_loop needs a topk_fn (ops.logprob_topk) and an advance_fn (ops.beam_advance_steps)")
+    if slots < 1 or K < 1:
+        raise ValueError(f"slots and beam_size must be at least 1 (got {slots}, {K})")
+    G, lam, per_group = _beam_groups(beam_groups, diversity_penalty, num_return_gen, K)
+    constraints = _active_constraints(constraints, constrain_fn)
+    lens = _mixed_prompt_lengths(prompt_length, n, tokens.size(1), "beam_inflight_loop")
+    sl = _Slots(n, slots, refill_min, None)
+    stop_token = cfg.eod_id if stop_token is None else int(stop_token)
+    longest = max(lens)
+    table, final_len, Q = _pad_for_generation(cfg, tokens, stop_token, longest, query_embeds)
+    sl.budgets = _inflight_budgets(cfg, max_new_tokens, [final_len - pl for pl in lens], lens, final_len, Q)
+    if table.size(1) > 2048:
+        raise ValueError(f"a token table of {table.size(1)} columns; the advance kernels take 2048")
+    fan, m = G * K, 2 * K + (G - 1) * K
+    state = make_state(slots, fan, Q + longest, max(max(sl.budgets) - 1, 1))
+    bs = BeamState(table[:1].expand(slots * G, -1), K)
+    bs.done.fill_(1)                                                                       # free slots: frozen by the advance
+    out = {k: torch.zeros((n * G,) + tuple(getattr(bs, k).shape[1:]), dtype=getattr(bs, k).dtype, device=dev) for k in BEAM_RESULT_ARRAYS}
+    row_prompt_len = torch.zeros(slots * fan, dtype=torch.int64, device=dev)               # constrain_fn's, per sequence
+    clip_prompt_len = torch.zeros(slots, dtype=torch.int32, device=dev)                    # advance_fn's, per slot
+    lens_d = torch.as_tensor(lens, dtype=torch.long).to(dev)
+    within = torch.arange(G, device=dev)
+    pseudo = lambda ids: (torch.as_tensor(ids, dtype=torch.long).to(dev)[:, None] * G + within[None]).reshape(-1)   # the G pseudo-clips of each
+    logits, advances = None, [0] * n
+    while sl.busy():
+        fresh, clips = sl.refill()
+        if fresh:                                                                          # (0) the refill
+            sel = torch.as_tensor(clips, dtype=torch.long).to(dev)
+            first = state.install(fresh, table[sel, :longest].contiguous(), None if query_embeds is None else query_embeds[sel].contiguous(),
+                                  [lens[c] for c in clips])
+            rows, fresh_d = pseudo(fresh), torch.as_tensor(fresh, dtype=torch.long).to(dev)
+            bs.tokens[rows] = table[sel].repeat_interleave(G, dim=0)[:, None, :]
+            bs.scores[rows], bs.hyp_count[rows], bs.hyp_next[rows], bs.worst[rows], bs.done[rows] = 0.0, 0, 0, 1e9, 0
+            clip_prompt_len[fresh_d] = lens_d[sel].to(torch.int32)
+            row_prompt_len.view(slots, fan)[fresh_d] = lens_d[sel][:, None]
+        running = sl.running()
+        where = torch.tensor([sl.group_t(), sl.steps()], dtype=torch.int32).to(dev)        # one upload: suffix positions, generation steps
+        group_t, clip_step = where[0], where[1]
+        if running:                                                                        # (1) one decode step; fresh and free slots idle
+            max_t = max(sl.step_of[s] - 1 for s in running)
+            logits = state.step(bs.next_tok.view(-1, 1), group_t, max_t)
+        elif logits is None:
+            logits = torch.zeros((slots * fan, first.shape[1]), dtype=torch.bfloat16, device=dev)   # the first iteration; frozen rows read none of it
+        if fresh:                                                                          # (2) the prefill logits of the fresh slots
+            logits.view(slots, fan, -1)[fresh_d] = first[:, None, :]
+        if constraints is not None:                                                        # (3) every clip on its own step
+            constrain_fn(logits, bs.tokens.view(slots * fan, -1), row_step=clip_step.repeat_interleave(fan), constraints=constraints,
+                         prompt_len=row_prompt_len, eos_ids=[stop_token], ban_value=BAN_BEAM)
+        vals, idxs = topk_fn(logits, m, bs.scores.view(-1))
+        advance_fn(vals, idxs, bs, groups=G, diversity_penalty=lam, vocab=logits.size(-1), clip_prompt_len=clip_prompt_len, clip_step=clip_step,
+                   stop_token=stop_token)
+        done_h = bs.done.view(slots, G).tolist()                                           # the step's one host read
+        leaving = [s for s in sl.advanced() if all(done_h[s]) or sl.spent(s)]              # (4) the bookkeeping
+        if leaving:
+            rows, dst = pseudo(leaving), pseudo([sl.clip_of[s] for s in leaving])
+            for k in BEAM_RESULT_ARRAYS:
+                out[k][dst] = getattr(bs, k)[rows]
+            bs.done[rows] = 1
+            for s in leaving:
+                advances[sl.clip_of[s]] = sl.step_of[s]
+                sl.release(s)
+        if running and sl.busy():                                                          # (5) the suffix rows follow their beams
+            state.reorder(bs.src_row, (group_t + 1).clamp_(min=0), max_t + 1)
+    h = SimpleNamespace(**{k: v.cpu() for k, v in out.items()})                            # one download
+    return SimpleNamespace(results=_beam_results(h, n, G, K, per_group, dev), advances=advances, steps=state.steps, prefills=state.prefills)
 
 
 def pad_after_termination(tokens: torch.Tensor, prompt_len, termination_id: int, width: int, fill: int) -> torch.Tensor:
@@ -1280,6 +1471,20 @@ def install(gpt_cls):
                                     streams=streams, max_new_tokens=max_new_tokens, refill_min=refill_min, constraints=constraints,
                                     **_sampler_fns("steps", return_scores), **kw)
 
+    def beam_search_inflight(self, tokens, query_embeds=None, beam_size=5, num_return_gen=1, stop_token=None, prompt_length=None, slots=32,
+                             max_new_tokens=None, refill_min=None, beam_groups=1, diversity_penalty=0.0, constraints=None,
+                             decode_weights="bf16", **kw):
+        """beam_search_batched(kv="shared_prefix") over a whole data set with the finished clips' slots refilled in flight
+        (beam_inflight_loop): tokens [n, L], prompt_length n lengths; `slots` clips x beam_groups * beam_size sequences stay resident;
+        max_new_tokens: a budget per clip (None: the lockstep search's, up to the end of the table).  -> a namespace: results (the
+        list of n results of beam_search_batched), steps, prefills"""
+        return beam_inflight_loop(_gen_config(self), make_inflight_state_fn(self, decode_weights), tokens, query_embeds=query_embeds,
+                                  beam_size=beam_size, num_return_gen=num_return_gen, stop_token=stop_token, prompt_length=prompt_length,
+                                  slots=slots, max_new_tokens=max_new_tokens, refill_min=refill_min, beam_groups=beam_groups,
+                                  diversity_penalty=diversity_penalty, constraints=constraints,
+                                  topk_fn=lambda lg, k, add: ops.logprob_topk(lg, k, add=add), advance_fn=ops.beam_advance_steps,
+                                  constrain_fn=ops.logits_constrain_steps, **kw)
+
     @torch.no_grad()
     def generate(self, tokens, do_sample=True, termination_id=None, *args, **kw):                # :1875-1880
         """sampler="device" (keyword; not in the reference, default "torch"): do_sample=True runs sample_batched, which takes
@@ -1313,3 +1518,4 @@ def install(gpt_cls):
     gpt_cls.sample, gpt_cls.beam_search, gpt_cls.generate = sample, beam_search, generate
     gpt_cls.beam_search_batched, gpt_cls.sample_batched = beam_search_batched, sample_batched
     gpt_cls.sample_inflight = torch.no_grad()(sample_inflight)
+    gpt_cls.beam_search_inflight = torch.no_grad()(beam_search_inflight)

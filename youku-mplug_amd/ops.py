@@ -784,9 +784,10 @@ def logprob_topk(logits, k, add=None, rows=None, vocab=None, ld=None):
     return val, idx
 
 
-def _beam_advance(who, d, m, cand_val, cand_idx, st, vocab, pos, cur_len, first, stop_token):
-    """beam_advance / beam_advance_groups on the descriptor d (batch, and what the entry adds, are set): checks the candidates against
-    [rows, m], fills d from the state and the step, calls mpv_<who> and swaps the token tables"""
+def _beam_advance(who, d, m, cand_val, cand_idx, st, vocab, pos, cur_len, first, stop_token, more=()):
+    """beam_advance / beam_advance_groups / beam_advance_steps on the descriptor d (batch, and what the entry adds, are set): checks the
+    candidates against [rows, m], fills d from the state and the step, calls mpv_<who> (`more`: the arguments behind the descriptor)
+    and swaps the token tables"""
     rows = st.batch * st.beams
     if (cand_val.dtype, cand_idx.dtype) != (torch.float32, torch.int64) or tuple(cand_val.shape) != (rows, m) or \
             tuple(cand_idx.shape) != (rows, m) or not (cand_val.is_contiguous() and cand_idx.is_contiguous()):
@@ -796,7 +797,7 @@ def _beam_advance(who, d, m, cand_val, cand_idx, st, vocab, pos, cur_len, first,
     for n in ("scores", "hyp_score", "hyp_order", "hyp_tokens", "hyp_count", "hyp_next", "worst", "done", "src_row", "next_tok"):
         setattr(d, n, getattr(st, n).data_ptr())
     d.beams, d.row_len, d.vocab, d.pos, d.cur_len, d.first, d.stop_token = st.beams, st.row_len, int(vocab), int(pos), int(cur_len), int(bool(first)), int(stop_token)
-    check(getattr(_lib.lib(), "mpv_" + who)(C.byref(d), _stream()), "mpv_" + who)
+    check(getattr(_lib.lib(), "mpv_" + who)(C.byref(d), *more, _stream()), "mpv_" + who)
     st.tokens, st.tokens_alt = st.tokens_alt, st.tokens
     return st.src_row, st.next_tok
 
@@ -823,7 +824,44 @@ def beam_advance_groups(cand_val, cand_idx, st, *, groups, diversity_penalty, vo
     return _beam_advance("beam_advance_groups", d, (groups + 1) * st.beams, cand_val, cand_idx, st, vocab, pos, cur_len, first, stop_token)
 
 
-TERMINATION_ID, TERMINATION_EOL, TERMINATION_DOUBLE_EOL = 0, 1, 2      # mpv_sample_advance_desc.termination_mode
+def beam_advance_steps(cand_val, cand_idx, st, *, groups=1, diversity_penalty=0.0, vocab, clip_prompt_len, clip_step, stop_token):
+    """beam_advance (groups = 1) / beam_advance_groups with a generation step per clip (include/mpv.h: mpv_beam_advance_steps; clips
+    that entered a running search at different times): clip_prompt_len / clip_step int32 [st.batch // groups] on the device, one value
+    per real clip; the table is left-aligned and clip c works on column clip_prompt_len[c] + clip_step[c] with cur_len =
+    clip_step[c] + 1.  A clip with a negative step, or whose column lies behind the table, is frozen with all its groups."""
+    _need_cuda(cand_val, cand_idx, st.tokens, clip_prompt_len, clip_step)
+    groups = int(groups)
+    if groups < 1 or st.batch % groups:
+        raise _lib.MpvError(f"beam_advance_steps: the state's {st.batch} (clip, group) pairs are no multiple of groups = {groups}")
+    clips = st.batch // groups
+    for name, t in (("clip_prompt_len", clip_prompt_len), ("clip_step", clip_step)):
+        if t is not None and (t.dtype != torch.int32 or t.numel() != clips or not t.is_contiguous()):
+            raise _lib.MpvError(f"beam_advance_steps: {name} must be a contiguous int32 tensor of {clips} values")
+    d = _lib.BeamAdvanceGroupsDesc(batch=clips, groups=groups, diversity_penalty=float(diversity_penalty))
+    return _beam_advance("beam_advance_steps", d, (groups + 1) * st.beams, cand_val, cand_idx, st, vocab, 0, 0, False, stop_token,
+                         (_p(clip_prompt_len), _p(clip_step)))
+
+
+def kv_suffix_reorder_steps(src, dst, idx, group_rows, *, fan, suffix_rows, max_rows):
+    """The beam re-order of the in-flight suffix cache in one launch over all layers (include/mpv.h: mpv_kv_suffix_reorder_steps): src /
+    dst bf16 [nl, n_groups * fan * suffix_rows, 3H]; sequence j of clip g = j // fan gets the first clamp(group_rows[g], 0, max_rows)
+    suffix rows of sequence idx[j] (int64 [n_groups * fan], inside the clip); group_rows int32 [n_groups].  -> dst"""
+    _need_cuda(src, dst, idx, group_rows)
+    ok = src is not None and dst is not None and src.dtype == dst.dtype == torch.bfloat16 and src.dim() == 3 and src.shape == dst.shape and \
+        src.is_contiguous() and dst.is_contiguous() and src.shape[2] % 3 == 0 and src.shape[1] % (int(fan) * int(suffix_rows)) == 0
+    if not ok:
+        raise _lib.MpvError(f"kv_suffix_reorder_steps: src and dst must be contiguous bf16 [nl, n_groups * {fan} * {suffix_rows}, 3H] of one shape")
+    nl, n_groups, hidden = src.shape[0], src.shape[1] // (int(fan) * int(suffix_rows)), src.shape[2] // 3
+    if idx is not None and (idx.dtype != torch.int64 or idx.numel() != n_groups * int(fan) or not idx.is_contiguous()):
+        raise _lib.MpvError(f"kv_suffix_reorder_steps: idx must be a contiguous int64 tensor of {n_groups * int(fan)} rows")
+    if group_rows is not None and (group_rows.dtype != torch.int32 or group_rows.numel() != n_groups or not group_rows.is_contiguous()):
+        raise _lib.MpvError(f"kv_suffix_reorder_steps: group_rows must be a contiguous int32 tensor of {n_groups} counts")
+    check(_lib.lib().mpv_kv_suffix_reorder_steps(src.data_ptr(), dst.data_ptr(), nl, n_groups, int(fan), int(suffix_rows), _p(idx), _p(group_rows),
+                                                 int(max_rows), hidden, _stream()), "mpv_kv_suffix_reorder_steps")
+    return dst
+
+
+TERMINATION_ID, TERMINATION_EOL, TERMINATION_DOUBLE_EOL = 0, 1, 2     # mpv_sample_advance_desc.termination_mode
 
 
 def sample_advance_desc(logits, st, *, pos, temperature=1.0, top_k=0, top_p=0.0, seed=0, vocab_size=None, termination_mode=TERMINATION_ID,
