@@ -47,6 +47,12 @@ What this entry point adds to downstream/finetune_common.py:
     and a finished clip's beams go to the next clip while the others continue (`model.generate(..., batched=True, beam_inflight=True)`;
     needs `--eval_batched_beam` and `--eval_shared_kv`; refused with `--eval_mixed_prompts` and with the sampling flags); same result
     files;
+  * `--eval_allowed_phrases FILE` (not in the reference, default off): a closed vocabulary, one phrase per line (blank lines are
+    skipped).  The lockstep beam search is constrained to the trie of the phrases (`model.generate(..., batched=True,
+    allowed_phrases=)`: one mask launch per step, a cost that does not grow with the number of phrases): "pred_caption" is the best
+    phrase, "pred_candidates" lists the up to 5 best as {"caption", "phrase_index", "score"}, the score renormalised over the allowed
+    tokens; needs `--eval_batched_beam`, combines with `--eval_shared_kv`, `--eval_fp8_decode`, `--eval_mixed_prompts` and
+    `--eval_beam_inflight`, and is refused with `--eval_beam_groups`, `--eval_sample_best_of` and `--eval_min_new_tokens`;
   * `--eval_score_gold` (not in the reference, default off): evaluation also scores every clip's `gold_caption` list, teacher-forced,
     against the query features computed once for that clip (`model.score_captions(..., query_features=)`: one packed pass per batch,
     no padding rows), adds "gold_logprob" / "gold_tokens" lists to the result entries and logs the corpus per-token NLL and perplexity;
@@ -81,7 +87,7 @@ def make_training_batch(video, text, prompt, tokenizer, device, max_length):
 @torch.no_grad()
 def evaluation(model, data_loader, tokenizer, device, config, batched=False, clips_per_search=32, eval_sample=0, seed=0, shared_kv=False,
                constraints=None, best_of=0, score_gold=False, max_length=None, beam_groups=1, diversity_penalty=0.0, fp8_decode=False,
-               mixed_prompts=False, sample_mixed_prompts=False, sample_inflight=False, beam_inflight=False):
+               mixed_prompts=False, sample_mixed_prompts=False, sample_inflight=False, beam_inflight=False, allowed_phrases=None):
     """-> [{video_id, pred_caption, gold_caption}] (:208-238); batched: `--eval_batched_beam`; eval_sample: `--eval_sample`;
     shared_kv: `--eval_shared_kv`, constraints: the keywords of `--eval_repetition_penalty` / `--eval_no_repeat_ngram` /
     `--eval_min_new_tokens` (the lockstep calls only); best_of: `--eval_sample_best_of` (the prediction is the best of that many
@@ -90,9 +96,18 @@ def evaluation(model, data_loader, tokenizer, device, config, batched=False, cli
     diversity_penalty: `--eval_beam_groups` / `--eval_diversity_penalty` (the prediction is the most likely hypothesis of a diverse beam
     search, all of them in "pred_candidates"); fp8_decode: `--eval_fp8_decode`; mixed_prompts: `--eval_mixed_prompts` (the
     lockstep beam-search calls only); sample_mixed_prompts: `--eval_sample_mixed_prompts` (the sampling calls only); sample_inflight:
-    `--eval_sample_inflight` (the sampling calls only); beam_inflight: `--eval_beam_inflight` (the lockstep beam-search calls only)"""
+    `--eval_sample_inflight` (the sampling calls only); beam_inflight: `--eval_beam_inflight` (the lockstep beam-search calls only);
+    allowed_phrases: the strings of `--eval_allowed_phrases` (the lockstep beam search only; tokenised once, here)"""
     module = getattr(model, "module", model)
     module.eval()
+    trie = None
+    if allowed_phrases:
+        if not batched or beam_groups > 1 or best_of:
+            raise ValueError("--eval_allowed_phrases needs --eval_batched_beam, without --eval_beam_groups and --eval_sample_best_of")
+        from youku_mplug_amd import generation
+        from youku_mplug_amd.downstream import _encode_phrase
+        trie = generation.as_phrase_trie(list(allowed_phrases), generation._gen_config(module.text_decoder).vocab_size,
+                                         lambda s: _encode_phrase(tokenizer, s))
     kvkw = {"kv_cache": "shared_prefix"} if shared_kv else {}                # flag absent: the calls below are unchanged
     kvkw.update(constraints or {})
     if mixed_prompts and not (batched or beam_groups > 1):
@@ -128,6 +143,9 @@ def evaluation(model, data_loader, tokenizer, device, config, batched=False, cli
         elif best_of:
             res = module.generate(video, text_input, do_sample=True, num_samples=best_of, best_of=True, seed=seed + n,
                                   clips_per_search=clips_per_search, **kvkw, **qkw, **smixkw)
+        elif trie is not None:
+            res, phrase_info = module.generate(video, text_input, batched=True, clips_per_search=clips_per_search, allowed_phrases=trie,
+                                               num_return_gen=min(5, trie.n_phrases), **kvkw, **qkw, **mixkw)
         else:
             res = module.generate(video, text_input, batched=True, clips_per_search=clips_per_search, **kvkw, **qkw, **mixkw) if batched else module.generate(video, text_input, **qkw)
         def caption(ids):
@@ -135,6 +153,11 @@ def evaluation(model, data_loader, tokenizer, device, config, batched=False, cli
             return ans.split(config["prompt"])[-1].strip() if config["prompt"] != "" else ans
         for video_id, r, gold in zip(video_ids, res, gold_caption):
             result.append({"video_id": video_id, "pred_caption": caption(r.tolist()[0]), "gold_caption": list(gold)})
+        if trie is not None:
+            for rec, info in zip(result[-len(res):], phrase_info):
+                rec["pred_candidates"] = [{"caption": allowed_phrases[i], "phrase_index": i, "score": float(sc)}
+                                          for i, sc in zip(info["phrase_index"].tolist(), info["scores"].tolist())]
+                rec["pred_caption"] = rec["pred_candidates"][0]["caption"] if rec["pred_candidates"] else ""
         if candidates is not None:
             for rec, rows in zip(result[-len(candidates):], candidates):
                 rec["pred_candidates"] = [caption(row) for row in rows.tolist()]
@@ -335,7 +358,8 @@ def main(args, config):
                             **({"mixed_prompts": True} if getattr(args, "eval_mixed_prompts", False) else {}),
                             **({"sample_mixed_prompts": True} if getattr(args, "eval_sample_mixed_prompts", False) else {}),
                             **({"sample_inflight": True} if getattr(args, "eval_sample_inflight", False) else {}),
-                            **({"beam_inflight": True} if getattr(args, "eval_beam_inflight", False) else {}))
+                            **({"beam_inflight": True} if getattr(args, "eval_beam_inflight", False) else {}),
+                            **({"allowed_phrases": read_phrases(args.eval_allowed_phrases)} if getattr(args, "eval_allowed_phrases", None) else {}))
         final = save_result(result, args.result_dir, "val_caption_result")
         val_stats = cal_metric(final)
         if getattr(args, "eval_score_gold", False):
@@ -345,6 +369,15 @@ def main(args, config):
         ft.write_log(args, log_stats)
         return log_stats
     return ft.epoch_loop(args, s, step_fn, lambda epoch: {})
+
+
+def read_phrases(path):
+    """the phrases of an --eval_allowed_phrases file: one per line, surrounding blanks and blank lines dropped"""
+    phrases = [line.strip() for line in open(path, "r", encoding="utf-8")]
+    phrases = [p for p in phrases if p]
+    if not phrases:
+        raise ValueError(f"--eval_allowed_phrases: {path} holds no phrase")
+    return phrases
 
 
 def constraint_keywords(args):
@@ -407,6 +440,9 @@ def get_args(argv=None):
         p.add_argument("--eval_beam_inflight", action="store_true", default=False,
                        help="--eval_batched_beam with --eval_shared_kv: one beam search over all clips of a batch with --clips_per_search "
                             "clips resident, a finished clip's beams refilled with the next clip (model.generate(batched=True, beam_inflight=True))")
+        p.add_argument("--eval_allowed_phrases", type=str, default=None, metavar="FILE",
+                       help="--eval_batched_beam: the captions are phrases of FILE (one per line), found by a beam search along their trie "
+                            "(model.generate(batched=True, allowed_phrases=...)); pred_candidates lists the best with their scores")
         p.add_argument("--eval_score_gold", action="store_true", default=False,
                        help="evaluation: also score every clip's gold captions against its query features (model.score_captions): "
                             "gold_logprob / gold_tokens in the result file, per-token NLL and perplexity in the log")
@@ -428,6 +464,10 @@ def get_args(argv=None):
     if args.eval_beam_inflight:
         _check_beam_inflight(args.eval_batched_beam, args.eval_shared_kv, args.eval_mixed_prompts,
                              args.eval_sample or args.eval_sample_best_of or args.eval_sample_mixed_prompts or args.eval_sample_inflight)
+    if args.eval_allowed_phrases and (not args.eval_batched_beam or args.eval_beam_groups > 1 or args.eval_sample_best_of or
+                                      args.eval_min_new_tokens):
+        raise ValueError("--eval_allowed_phrases needs --eval_batched_beam, without --eval_beam_groups, --eval_sample_best_of and "
+                         "--eval_min_new_tokens")
     constraint_keywords(args)                                               # refuses the flags without a lockstep mode
     config.setdefault("prompt", "")
     args.result_dir = os.path.join(args.output_dir, "result")

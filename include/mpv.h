@@ -877,6 +877,59 @@ int mpv_logits_constrain_ragged(const mpv_logits_constrain_desc* d, mpv_stream_t
  * and mpv_logits_constrain on that row alone at pos = c_r.  Refused: as the ragged entry except d->pos, and a NULL row_step. */
 int mpv_logits_constrain_steps(const mpv_logits_constrain_desc* d, const int32_t* row_step, mpv_stream_t stream);
 /* ------------------------------------------------------------------------------------------
+ * Closed-vocabulary generation (generation.PhraseTrie, LogitsConstraints.allowed_phrases): ONE launch keeps, in one step's logits,
+ * only the tokens that continue the row's generated history along a trie of allowed phrases, after mpv_logits_constrain (a ban
+ * still wins) and before mpv_sample_advance or mpv_logprob_topk reads them.  The state of the walk is the loop's own token table.
+ * The trie is four DEVICE arrays in CSR form, node 0 the root: child_begin int32 [n_nodes + 1]; child_tok int32 [n_edges], strictly
+ *   ascending inside each node's run [child_begin[u], child_begin[u + 1]); child_node int32 [n_edges], the node an edge leads to;
+ *   terminal int32 [n_nodes], the index of the phrase that ends at the node, or -1.
+ * Input: logits bf16 [rows][ld], 16-byte aligned, the first `vocab` columns are the row; tokens int64 [rows][row_len]; prompt_len
+ *   int64 [rows], or NULL: then every row has the prompt length prompt_len_all; eos_ids int64 [n_eos] (device), 1 <= n_eos <= 8;
+ *   pos, the token column this step fills; ban_value, -inf or finite and negative, stored rounded to bf16; node_out int32 [rows]
+ *   (device) or NULL.
+ * Row r at column c = pos:
+ * 1. prompt_len[r] > c (teacher-forced): the row is left untouched, bit for bit, and node_out[r] = -2.
+ * 2. Otherwise the history is tokens[r][prompt_len[r] : c], the generated tokens only (a negative prompt_len counts as 0).  The walk
+ *   starts at the root; every token must be a child of the current node.  A token that is not a child makes the row DEAD: an
+ *   out-of-range token, a termination id (no phrase holds one) and anything behind a termination id.
+ * 3. A live row at node u allows the child tokens of u and, when terminal[u] >= 0, every in-range id of eos_ids.
+ * 4. A dead row allows the in-range ids of eos_ids only: a row that left the trie ends at once.
+ * 5. Every column in [0, vocab) that is not allowed becomes ban_value; every allowed column keeps its bits; columns >= vocab are
+ *   neither read nor written.  node_out[r] = u for a live row, -1 for a dead one.
+ * Invariants: a row's result depends on its own logits, its history, its lengths and the scalars only -- neither on `rows` nor on
+ *   the row's place in the launch; every column has one writer; the result does not depend on thread timing; no atomics.
+ * ban_value: -inf for mpv_sample_advance, the lowest finite bf16 in front of mpv_logprob_topk, as for mpv_logits_constrain.
+ * Refused with a negative code before any launch, logits untouched: what mpv_logits_constrain refuses about logits / vocab / ld /
+ *   rows / row_len / pos; n_eos outside [1, 8] or a NULL eos_ids; a NULL trie array; n_nodes < 1; a ban_value that is NaN or >= 0.
+ * One workgroup per row: the history goes through LDS, a wave walks it with a 64-ary search of every node's sorted child run, and
+ *   the row is written once in 16-byte chunks; a chunk is loaded only when the child run says it holds an allowed token.  Indices read
+ *   from the trie arrays are checked against n_nodes / n_edges before they become addresses. */
+typedef struct mpv_logits_trie_desc {
+  void* logits;
+  const int64_t* tokens;
+  const int64_t* prompt_len;
+  const int64_t* eos_ids;
+  const int32_t* child_begin;
+  const int32_t* child_tok;
+  const int32_t* child_node;
+  const int32_t* terminal;
+  int32_t* node_out;
+  int64_t ld;
+  int64_t prompt_len_all;
+  int rows, vocab, row_len, pos, n_eos, n_nodes, n_edges;
+  float ban_value;
+} mpv_logits_trie_desc;
+int mpv_logits_trie_mask(const mpv_logits_trie_desc* d, mpv_stream_t stream);
+/* The same mask for a LEFT-ALIGNED table of prompts of different lengths: d->pos is the generation STEP t >= 0, prompt_len must not
+ * be NULL, and row r works on its own column c_r = clamp(prompt_len[r], 0, row_len) + t.  A row with c_r >= row_len is frozen: its
+ * logits stay untouched and node_out[r] = -2.  A row equals, bit for bit, mpv_logits_trie_mask on that row alone at pos = c_r.
+ * Refused: what mpv_logits_trie_mask refuses, a NULL prompt_len, and t outside [0, row_len). */
+int mpv_logits_trie_mask_ragged(const mpv_logits_trie_desc* d, mpv_stream_t stream);
+/* ... and for rows that also differ in their step: d->pos is ignored, row r works on column c_r = clamp(prompt_len[r], 0, row_len) +
+ * row_step[r] (DEVICE int32 [rows]).  A row with row_step[r] < 0 or c_r >= row_len is frozen.  Bit for bit the ragged entry when every
+ * row_step[r] == t.  Refused: as the ragged entry except d->pos, and a NULL row_step. */
+int mpv_logits_trie_mask_steps(const mpv_logits_trie_desc* d, const int32_t* row_step, mpv_stream_t stream);
+/* ------------------------------------------------------------------------------------------
  * Sequence scores of sampled generation in lockstep (generation.SampleScores): ONE launch, right after mpv_sample_advance, records
  * the model's log-probability of the token that call wrote into column `pos` -- log_softmax of the RAW logits the sampler read
  * (after mpv_logits_constrain edited them, if it did).  Temperature, top-k and top-p are ignored by design: the score is the

@@ -130,6 +130,12 @@ class LogitsConstrainDesc(C.Structure):
                [("penalty", c_float), ("ban_value", c_float)]
 
 
+class LogitsTrieDesc(C.Structure):
+    _fields_ = [(n, c_void_p) for n in ("logits", "tokens", "prompt_len", "eos_ids", "child_begin", "child_tok", "child_node", "terminal", "node_out")] + \
+               [("ld", c_int64), ("prompt_len_all", c_int64)] + \
+               [(n, c_int) for n in ("rows", "vocab", "row_len", "pos", "n_eos", "n_nodes", "n_edges")] + [("ban_value", c_float)]
+
+
 class SampleScoreDesc(C.Structure):
     _fields_ = [(n, c_void_p) for n in ("logits", "tokens", "prompt_len", "done", "live", "token_logprob", "sum_logprob", "count")] + \
                [("ld", c_int64)] + [(n, c_int) for n in ("rows", "vocab", "row_len", "pos")]
@@ -305,6 +311,9 @@ _SIGS.update({
     "mpv_sample_score_steps": (c_int, [C.POINTER(SampleScoreDesc), c_void_p, c_void_p]),
     "mpv_beam_advance_steps": (c_int, [C.POINTER(BeamAdvanceGroupsDesc), c_void_p, c_void_p, c_void_p]),
     "mpv_kv_suffix_reorder_steps": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "mpv_logits_trie_mask": (c_int, [C.POINTER(LogitsTrieDesc), c_void_p]),
+    "mpv_logits_trie_mask_ragged": (c_int, [C.POINTER(LogitsTrieDesc), c_void_p]),
+    "mpv_logits_trie_mask_steps": (c_int, [C.POINTER(LogitsTrieDesc), c_void_p, c_void_p]),
 })
 
 EXPORTS = tuple(_SIGS)

@@ -13,6 +13,7 @@ B + len(negative_indices) rows.  forward(..., train=False) returns the scores th
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 from typing import Optional, Sequence
 
@@ -335,7 +336,7 @@ class DistributedGPT3_Caption(_GenCls):
                  top_k=None, top_p=None, seed=0, kv_cache="per_sequence", repetition_penalty=None, no_repeat_ngram_size=0, min_new_tokens=0,
                  banned_token_ids=None, constrain_prompt=False, return_scores=False, best_of=False, length_penalty=1.0, query_features=None,
                  beam_groups=1, diversity_penalty=0.0, rerank_by_logprob=False, decode_weights="bf16", mixed_prompts=False, sample_mixed_prompts=False,
-                 inflight=False, max_new_tokens=None, refill_min=None, beam_inflight=False, **kw):
+                 inflight=False, max_new_tokens=None, refill_min=None, beam_inflight=False, allowed_phrases=None, **kw):
         """One beam search per sample (:790-809): prompt = text.input_ids[i, :mask.sum()-1], prefix = its query features.
         batched=True (not in the reference, default off): the clips are grouped by prompt length and every group is searched in
         lockstep, `clips_per_search` clips at a time (generation.beam_search_batched_loop: the decoder's weights are read once per
@@ -422,7 +423,17 @@ class DistributedGPT3_Caption(_GenCls):
         (generation.beam_inflight_loop: a generation step per clip in the advance kernel, a row count per clip in the suffix
         re-order).  The return value is the batched call's.  It combines with beam_groups, diversity_penalty, rerank_by_logprob,
         decode_weights and the constraints, constrain_prompt=True included (this table has no padding).  Refused with do_sample, without
-        batched=True, with kv_cache="per_sequence" and together with mixed_prompts=True."""
+        batched=True, with kv_cache="per_sequence" and together with mixed_prompts=True.
+        allowed_phrases (batched=True and do_sample=True only; default None: no call and no launch is added): a closed vocabulary --
+        a generation.PhraseTrie, a list of token lists, or a list of strings tokenised with the model's tokenizer.  Every caption is
+        then one of the phrases followed by the termination id: each step keeps only the tokens that continue a sequence along the
+        trie (generation.LogitsConstraints(allowed_phrases=), ops.logits_trie_mask*; one launch per step, a cost independent of the
+        number of phrases -- DESIGN.md section 28).  The tensors keep their shapes.  batched=True: -> (res, info); info[i] is a dict of
+        CPU tensors for clip i: phrase_index [n] int64 (the index of row r's phrase in the list) and scores [n] fp32, the search's
+        scores; a clip returns the best min(num_return_gen, phrases the search reached) rows.  do_sample=True: with return_scores the
+        clip's dict also holds phrase_index [N].  All these scores are RENORMALISED over the allowed tokens, not the model's
+        likelihoods over the vocabulary.  It combines with kv_cache, decode_weights, beam_groups, the mixed and in-flight modes and the
+        other constraints except min_new_tokens; rerank_by_logprob is refused (score the phrases with score_captions instead)."""
         Q, Hh = self.num_learnable_token, self.text_width
         G = int(beam_groups)
         from . import generation as _gen
@@ -503,6 +514,16 @@ class DistributedGPT3_Caption(_GenCls):
                 kw = dict(kw, constraints=generation.LogitsConstraints(
                     repetition_penalty=1.0 if repetition_penalty is None else repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
                     min_new_tokens=min_new_tokens, banned_token_ids=tuple(banned_token_ids or ()), include_prompt=constrain_prompt))
+            trie = None
+            if allowed_phrases is not None:
+                if not (do_sample or batched):
+                    raise ValueError("allowed_phrases need batched=True or do_sample=True: the per-clip search has no constraints")
+                if rerank_by_logprob:
+                    raise ValueError("allowed_phrases do not combine with rerank_by_logprob: score the phrases with score_captions")
+                tok = getattr(self, "tokenizer", None)
+                trie = generation.as_phrase_trie(allowed_phrases, generation._gen_config(self.text_decoder).vocab_size,
+                                                 None if tok is None else (lambda s: _encode_phrase(tok, s)))
+                kw = dict(kw, constraints=dataclasses.replace(kw.get("constraints") or generation.LogitsConstraints(), allowed_phrases=trie))
             if do_sample:
                 N = int(num_samples)
                 if int(clips_per_search) < 1 or N < 1:
@@ -540,7 +561,7 @@ class DistributedGPT3_Caption(_GenCls):
                             res[i] = toks[rows][b:b + 1]
                         else:
                             res[i] = toks[rows]
-                        scores[i] = entry
+                        scores[i] = _with_phrase_index(entry, trie, res[i], lengths[i], term)
                     return (res, scores) if return_scores else res
                 if sample_mixed_prompts:                                 # input order, no grouping: one loop per chunk with its lengths
                     per = int(clips_per_search)
@@ -575,7 +596,7 @@ class DistributedGPT3_Caption(_GenCls):
                             res[i] = out[rows][b:b + 1]
                         else:
                             res[i] = out[rows]
-                        scores[i] = entry
+                        scores[i] = _with_phrase_index(entry, trie, res[i], lengths[i], term)
                 return (res, scores) if return_scores else res
             if batched:
                 if int(clips_per_search) < 1:
@@ -583,6 +604,7 @@ class DistributedGPT3_Caption(_GenCls):
                 lengths = (text.attention_mask.sum(-1) - 1).tolist()
                 res = [None] * n
                 groups_of = [None] * n
+                info = [None] * n
                 if beam_inflight:                                        # ONE loop over all clips, clips_per_search slots resident
                     more = {k: v for k, v in kw.items() if k != "kv"}
                     outs = self.text_decoder.beam_search_inflight(text.input_ids, query_embeds=qf.contiguous(), stop_token=termination_id,
@@ -591,6 +613,7 @@ class DistributedGPT3_Caption(_GenCls):
                     for i, out in enumerate(outs):
                         res[i] = out.sequences.cpu()
                         groups_of[i] = getattr(out, "group", None)
+                        info[i] = dict(phrase_index=getattr(out, "phrase_index", None), scores=out.scores)
                     chunks = []
                 elif mixed_prompts:                                      # input order, no grouping: one search per chunk with its lengths
                     per = int(clips_per_search)
@@ -605,6 +628,9 @@ class DistributedGPT3_Caption(_GenCls):
                     for i, out in zip(sel.tolist(), outs):
                         res[i] = out.sequences.cpu()
                         groups_of[i] = getattr(out, "group", None)
+                        info[i] = dict(phrase_index=getattr(out, "phrase_index", None), scores=out.scores)
+                if trie is not None:
+                    return res, info
                 if not rerank_by_logprob:
                     return res
                 term = generation._gen_config(self.text_decoder).eod_id if termination_id is None else int(termination_id)
@@ -731,6 +757,26 @@ class DistributedGPT3_Caption(_GenCls):
             return res
         finally:
             self.train(was)
+
+
+def _encode_phrase(tok, s):
+    """the tokens of the string `s` alone: what the tokenizer makes of it without the opening and the closing token"""
+    enc = tok([s], padding="longest", truncation=False, return_tensors="pt")
+    ids = enc["input_ids"][0, :int(enc["attention_mask"][0].sum())].tolist()
+    if ids and ids[0] == tok.tokenizer.bos:
+        ids = ids[1:]
+    if ids and ids[-1] == tok.tokenizer.eos:
+        ids = ids[:-1]
+    return ids
+
+
+def _with_phrase_index(entry, trie, rows, prompt_len, term):
+    """generate(allowed_phrases=, return_scores=True): the clip's score dict with phrase_index [rows] int64 (-1: no phrase)"""
+    if trie is None:
+        return entry
+    from . import generation
+    return dict(entry, phrase_index=torch.tensor([trie.lookup(generation.generated_part(r, prompt_len, term)) for r in rows.tolist()],
+                                                 dtype=torch.int64))
 
 
 def _prompt_length_chunks(lengths, per_chunk):

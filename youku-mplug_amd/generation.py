@@ -20,6 +20,8 @@ sample_score_ragged); sample_inflight_loop refills a finished clip's rows with t
 (InflightDecodeState: mpv_gpt_decode_step_shared_steps, a suffix position per clip; ops.sample_advance_steps / logits_constrain_steps /
 sample_score_steps, a step per row).  decode_weights="fp8" (default "bf16") runs the steps of any of these
 loops on e4m3 codes of the decoder's weights (DecodeWeightsQ8; mpv_gpt_decode_step_q8 / _shared_q8, csrc/gemm_w8.hip).
+LogitsConstraints(allowed_phrases=PhraseTrie) makes the lockstep and in-flight loops produce members of a closed set of phrases only:
+one more launch per step keeps the tokens that continue a row along the trie (ops.logits_trie_mask*, csrc/logits_trie.hip).
 """
 from __future__ import annotations
 
@@ -664,7 +666,7 @@ class BeamState:
 def beam_search_batched_loop(cfg, make_state: Callable[[int, int], object], tokens: torch.Tensor, query_embeds=None, beam_size=5,
                              num_return_gen=1, stop_token=None, prompt_length: Optional[int] = None, topk_fn=None, advance_fn=None,
                              constraints: Optional["LogitsConstraints"] = None, constrain_fn=None, return_scores=False, beam_groups=1,
-                             diversity_penalty=0.0, group_advance_fn=None):
+                             diversity_penalty=0.0, group_advance_fn=None, trie_fn=None):
     """Beam search for B clips in lockstep, the search state on the device: tokens [B, L], query_embeds [B, Q, H].  Every decode step
     advances all the clips' beams, so the decoder's weights are read once per generated position instead of once per clip and
     position, the prefill runs once per clip and the bookkeeping of a step is one kernel.  `make_state(batch, max_len)` -> an object
@@ -698,7 +700,14 @@ def beam_search_batched_loop(cfg, make_state: Callable[[int, int], object], toke
     budget ends; where a longer prompt's budget ends the host sets the clip's bs.done on the device (the advance then freezes it:
     tokens and scores stay, include/mpv.h mpv_beam_advance) after saving which of these clips were not done -- no host read is added
     -- and _strip_left_padding flushes the beams of exactly those.  Raised before the first launch: include_prompt=True constraints
-    (the pad columns would count as prompt), 2 * Lt > 2048 columns (the advance kernels' limit), what _mixed_prompt_state refuses."""
+    (the pad columns would count as prompt), 2 * Lt > 2048 columns (the advance kernels' limit), what _mixed_prompt_state refuses.
+    constraints.allowed_phrases (a PhraseTrie): after constrain_fn and before topk_fn every step keeps only the tokens that continue a
+    row along the trie, through trie_fn (ops.logits_trie_mask) on the same table, column, termination id and ban value.  The scores are
+    then renormalised over the allowed tokens.  With fewer allowed tokens than 2K the candidates include banned ones at BAN_BEAM-sized
+    values; they rank behind every allowed one, die at the next step and may reach the hypothesis store, so the host finish drops every
+    hypothesis whose generated part is not a phrase (trie.lookup: exact, no score threshold) and a clip may return fewer than
+    num_return_gen rows; every result carries phrase_index [n] int64.  The columns behind every prompt are set to the stop token in the
+    loop's table.  Raised before the first launch: what _active_trie refuses (min_new_tokens, a phrase with the stop token)."""
     _no_sample_scores(return_scores, "beam_search_batched_loop")
     B, dev, K = tokens.size(0), tokens.device, int(beam_size)
     G, lam, per_group = _beam_groups(beam_groups, diversity_penalty, num_return_gen, K)
@@ -708,9 +717,12 @@ def beam_search_batched_loop(cfg, make_state: Callable[[int, int], object], toke
         advance, more = group_advance_fn, dict(groups=G, diversity_penalty=lam)
     else:
         advance, more = advance_fn, {}
-    constraints = _active_constraints(constraints, constrain_fn)
+    constraints_given, constraints = constraints, _active_constraints(constraints, constrain_fn)
     lens = _mixed_prompt_lengths(prompt_length, B, tokens.size(1))                         # None: one prompt length
     stop_token = cfg.eod_id if stop_token is None else int(stop_token)
+    trie = _active_trie(constraints_given, trie_fn, [stop_token])
+    if trie is not None:
+        tokens = _stop_behind_prompts(tokens, lens if lens is not None else tokens.size(1) if prompt_length is None else int(prompt_length), stop_token)
     if lens is None:
         prompt_length = int(prompt_length) if prompt_length is not None else tokens.size(1)
         tokens, final_len, Q = _pad_for_generation(cfg, tokens, stop_token, prompt_length, query_embeds)
@@ -737,6 +749,9 @@ def beam_search_batched_loop(cfg, make_state: Callable[[int, int], object], toke
         if constraints is not None:
             constrain_fn(logits, bs.tokens.view(B * G * K, -1), pos=context_length - Q, constraints=constraints, prompt_len_all=prompt_length,
                          eos_ids=[stop_token], ban_value=BAN_BEAM)
+        if trie is not None:
+            trie_fn(logits, bs.tokens.view(B * G * K, -1), pos=context_length - Q, trie=trie, prompt_len_all=prompt_length, eos_ids=[stop_token],
+                    ban_value=BAN_BEAM)
         vals, idxs = topk_fn(logits, m, bs.scores.view(-1))                                  # log_softmax + scores (:1790-1791)
         advance(vals, idxs, bs, vocab=logits.size(-1), pos=context_length - Q, cur_len=len_scale * (n + 1), first=n == 0,
                 stop_token=stop_token, **more)
@@ -749,7 +764,7 @@ def beam_search_batched_loop(cfg, make_state: Callable[[int, int], object], toke
     h = SimpleNamespace(**{k: getattr(bs, k).cpu() for k in BeamState.ARRAYS})              # one download
     if lens is not None:
         _strip_left_padding(h, lens, flush, len_scale)
-    return _beam_results(h, B, G, K, per_group, dev)
+    return _beam_results(h, B, G, K, per_group, dev, trie, lens if lens is not None else [prompt_length] * B, stop_token)
 
 
 def _beam_groups(beam_groups, diversity_penalty, num_return_gen, K):
@@ -768,13 +783,30 @@ def _beam_groups(beam_groups, diversity_penalty, num_return_gen, K):
     return G, lam, int(num_return_gen) // G
 
 
-def _beam_results(h, B, G, K, per_group, dev):
-    """the downloaded BeamState arrays `h` of B clips x G groups -> the list of B result namespaces of the lockstep beam loops"""
+def _beam_results(h, B, G, K, per_group, dev, trie=None, prompt_lens=None, stop_token=None):
+    """the downloaded BeamState arrays `h` of B clips x G groups -> the list of B result namespaces of the lockstep beam loops.
+    trie (a PhraseTrie; prompt_lens: the clips' prompt lengths in the left-aligned rows of `h`): a hypothesis stays only if its
+    generated part is a phrase, and the namespaces carry phrase_index [n] int64"""
     out = []
     for clip in range(B):
-        ranked = [_ranked_hypotheses(h, clip * G + g, K)[:per_group] for g in range(G)]
-        res = SimpleNamespace(sequences=torch.stack([r[1] for rg in ranked for r in rg], dim=0).to(dev),
+        ranked = [_ranked_hypotheses(h, clip * G + g, K) for g in range(G)]
+        if trie is not None:                                                                 # best first, until per_group phrases are found
+            kept = []
+            for rg in ranked:
+                kept.append([])
+                for r in rg:
+                    if len(kept[-1]) == per_group:
+                        break
+                    idx = trie.lookup(generated_part(r[1], prompt_lens[clip], stop_token))
+                    if idx >= 0:
+                        kept[-1].append(r + (idx,))
+            ranked = kept
+        ranked = [rg[:per_group] for rg in ranked]
+        rows = [r[1] for rg in ranked for r in rg]
+        res = SimpleNamespace(sequences=(torch.stack(rows, dim=0) if rows else h.tokens.new_zeros((0, h.tokens.size(-1)))).to(dev),
                               scores=torch.tensor([r[0] for rg in ranked for r in rg], dtype=torch.float32))
+        if trie is not None:
+            res.phrase_index = torch.tensor([r[-1] for rg in ranked for r in rg], dtype=torch.int64)
         if G > 1:
             res.group = torch.tensor([g for g, rg in enumerate(ranked) for _ in rg], dtype=torch.int64)
         out.append(res)
@@ -873,6 +905,101 @@ BAN_SAMPLING = float("-inf")                 # mpv_sample_advance: probability 0
 BAN_BEAM = -float.fromhex("0x1.fep127")      # the lowest finite bf16: mpv_logprob_topk would take exp(-inf + inf) on a slice of -inf only
 
 
+class PhraseTrie:
+    """A closed vocabulary of multi-token phrases as a trie, for LogitsConstraints(allowed_phrases=): the lockstep and in-flight loops
+    then produce only members of the set, each followed by the termination id (include/mpv.h: mpv_logits_trie_mask; DESIGN.md section
+    28).  phrases: non-empty sequences of token ids in [0, vocab) (lists or 1-D tensors), at most 255 tokens each.  Shared prefixes are
+    merged; a phrase given twice is one terminal node that keeps the LOWEST phrase index.  The trie is flattened to four int32 arrays in
+    CSR form, node 0 the root: child_begin [n_nodes + 1], child_tok [n_edges] (strictly ascending inside each node's run),
+    child_node [n_edges], terminal [n_nodes] (the phrase index, or -1 where no phrase ends).
+    .max_len: the longest phrase; .n_phrases: len(phrases), duplicates included; .lookup(seq) -> the phrase index of exactly `seq`, or
+    -1 (on the host, exact); .arrays(device) -> the four arrays on `device`, built once per device.  Whether a phrase holds a
+    termination id is checked by the loops, which know the ids (.contains(token))."""
+    MAX_PHRASE_LEN, MAX_EDGES = 255, 2 ** 31 - 1
+
+    def __init__(self, phrases, vocab: int):
+        vocab = int(vocab)
+        phrases = list(phrases)
+        if not phrases:
+            raise ValueError("PhraseTrie needs at least one phrase")
+        children, terminal, n_edges, self.max_len = [{}], [-1], 0, 0
+        for idx, ph in enumerate(phrases):
+            seq = [int(t) for t in (ph.tolist() if torch.is_tensor(ph) else ph)]
+            if not seq:
+                raise ValueError(f"phrase {idx} is empty")
+            if len(seq) > self.MAX_PHRASE_LEN:
+                raise ValueError(f"phrase {idx} has {len(seq)} tokens; at most {self.MAX_PHRASE_LEN}")
+            u = 0
+            for t in seq:
+                if not 0 <= t < vocab:
+                    raise ValueError(f"phrase {idx}: token {t} is outside [0, {vocab})")
+                v = children[u].get(t)
+                if v is None:
+                    n_edges += 1
+                    if n_edges > self.MAX_EDGES:
+                        raise ValueError(f"the trie has more than {self.MAX_EDGES} edges")
+                    v = children[u][t] = len(children)
+                    children.append({})
+                    terminal.append(-1)
+                u = v
+            if terminal[u] < 0:
+                terminal[u] = idx
+            self.max_len = max(self.max_len, len(seq))
+        self.vocab, self.n_phrases, self.n_nodes, self.n_edges = vocab, len(phrases), len(children), n_edges
+        self.child_begin, self.child_tok, self.child_node, self.terminal = [0], [], [], terminal
+        for kids in children:
+            for t in sorted(kids):
+                self.child_tok.append(t)
+                self.child_node.append(kids[t])
+            self.child_begin.append(len(self.child_tok))
+        self._tokens = frozenset(self.child_tok)
+        self._device = {}
+
+    def contains(self, token: int) -> bool:
+        """does any phrase hold `token`?"""
+        return int(token) in self._tokens
+
+    def lookup(self, seq) -> int:
+        """-> the index of the phrase that is exactly `seq` (the lowest, if it was given more than once), or -1"""
+        import bisect
+        u = 0
+        for t in (seq.tolist() if torch.is_tensor(seq) else seq):
+            b, e = self.child_begin[u], self.child_begin[u + 1]
+            j = bisect.bisect_left(self.child_tok, int(t), b, e)
+            if j == e or self.child_tok[j] != int(t):
+                return -1
+            u = self.child_node[j]
+        return self.terminal[u] if u else -1
+
+    def arrays(self, device):
+        """-> (child_begin, child_tok, child_node, terminal) as int32 tensors on `device`, made once per device"""
+        key = str(torch.device(device))
+        hit = self._device.get(key)
+        if hit is None:
+            hit = self._device[key] = tuple(torch.tensor(a, dtype=torch.int32).to(device)
+                                            for a in (self.child_begin, self.child_tok, self.child_node, self.terminal))
+        return hit
+
+
+def as_phrase_trie(phrases, vocab: int, encode=None) -> "PhraseTrie":
+    """a PhraseTrie as it is; a list of token lists (or tensors); or a list of strings, each tokenised by `encode` (str -> ids)"""
+    if isinstance(phrases, PhraseTrie):
+        return phrases
+    phrases = list(phrases)
+    if any(isinstance(p, str) for p in phrases):
+        if encode is None:
+            raise ValueError("allowed_phrases given as strings need a tokenizer")
+        phrases = [list(encode(p)) if isinstance(p, str) else p for p in phrases]
+    return PhraseTrie(phrases, vocab)
+
+
+def generated_part(row, prompt_len: int, termination_id: int) -> list:
+    """a result row (a list or 1-D tensor: prompt, generated tokens, padding) -> the tokens between the prompt and the first
+    termination id behind it"""
+    gen = (row.tolist() if torch.is_tensor(row) else list(row))[int(prompt_len):]
+    return gen[:gen.index(int(termination_id))] if int(termination_id) in gen else gen
+
+
 @dataclasses.dataclass
 class LogitsConstraints:
     """What the lockstep loops may forbid or discourage (include/mpv.h: mpv_logits_constrain; ops.logits_constrain applies it to one
@@ -881,12 +1008,17 @@ class LogitsConstraints:
     tokens) and include_prompt (the penalty and the n-grams also see the prompt; default: the generated tokens only).
     The constraints act on the RAW logits -- before temperature, the top-k / top-p filter and log_softmax -- in sampling and in beam
     search alike.  (Hugging Face's beam search applies its processors to the log-probabilities instead, so a penalised beam score
-    differs from theirs; for sampling the two orders agree with their processors run before their warpers.)"""
+    differs from theirs; for sampling the two orders agree with their processors run before their warpers.)
+    allowed_phrases (a PhraseTrie; default None): what the loops REQUIRE -- every sequence is a phrase of the trie followed by the
+    termination id.  After the edits above (a ban still wins) every step keeps only the tokens that continue the row's generated
+    tokens along the trie (ops.logits_trie_mask*, include/mpv.h: mpv_logits_trie_mask).  The scores of such a call -- beam scores and
+    sample log-probabilities alike -- are RENORMALISED ones: log_softmax runs over the allowed tokens only."""
     repetition_penalty: float = 1.0
     no_repeat_ngram_size: int = 0
     min_new_tokens: int = 0
     banned_token_ids: tuple = ()
     include_prompt: bool = False
+    allowed_phrases: Optional[PhraseTrie] = None
 
     def __post_init__(self):
         p = self.repetition_penalty
@@ -902,20 +1034,53 @@ class LogitsConstraints:
                 raise ValueError(f"banned_token_ids must be integers (got {t!r})")
         if len(ids) > 1024:
             raise ValueError(f"at most 1024 banned_token_ids (got {len(ids)})")
+        if self.allowed_phrases is not None and not isinstance(self.allowed_phrases, PhraseTrie):
+            raise ValueError(f"allowed_phrases must be a PhraseTrie or None (got a {type(self.allowed_phrases).__name__})")
         self.repetition_penalty, self.banned_token_ids, self.include_prompt = float(p), ids, bool(self.include_prompt)
         self._device_ids = {}                    # ops.logits_constrain: the device copies of the id lists, made once
 
     @property
-    def active(self) -> bool:
+    def edits(self) -> bool:
+        """is any of the edits of ops.logits_constrain on?"""
         return self.repetition_penalty != 1.0 or self.no_repeat_ngram_size > 0 or self.min_new_tokens > 0 or len(self.banned_token_ids) > 0
+
+    @property
+    def active(self) -> bool:
+        return self.edits or self.allowed_phrases is not None
 
 
 def _active_constraints(constraints, constrain_fn):
-    if constraints is None or not constraints.active:
+    """-> the constraints if constrain_fn has something to do (the edits; the trie is _active_trie's), else None"""
+    if constraints is None or not constraints.edits:
         return None
     if constrain_fn is None:
         raise ValueError("active constraints need a constrain_fn (ops.logits_constrain)")
     return constraints
+
+
+def _active_trie(constraints, trie_fn, eos_ids, eol_stop=False):
+    """-> constraints.allowed_phrases, or None; with a trie, everything that cannot work is raised here, before the first launch"""
+    trie = None if constraints is None else constraints.allowed_phrases
+    if trie is None:
+        return None
+    if trie_fn is None:
+        raise ValueError("allowed_phrases need a trie_fn (ops.logits_trie_mask)")
+    if constraints.min_new_tokens > 0:
+        raise ValueError(f"min_new_tokens ({constraints.min_new_tokens}) cannot be combined with allowed_phrases: a phrase ends with the "
+                         "termination id that the minimum length bans")
+    if eol_stop:
+        raise ValueError("allowed_phrases cannot be combined with stop_on_eol / stop_on_double_eol: a phrase ends with one termination id")
+    for t in eos_ids:
+        if trie.contains(t):
+            raise ValueError(f"an allowed phrase contains the termination id {int(t)}")
+    return trie
+
+
+def _stop_behind_prompts(tokens, prompt_lens, stop_token):
+    """tokens [B, L] -> a copy with the stop token in every column at and behind the clip's prompt length: a beam hypothesis is stored
+    as its whole row, so with this its generated part is what generated_part() reads, whatever padding the caller's rows carried"""
+    lens = torch.as_tensor(prompt_lens, dtype=torch.long).to(tokens.device).reshape(-1, 1)
+    return torch.where(torch.arange(tokens.size(1), device=tokens.device)[None] < lens, tokens, torch.full_like(tokens, stop_token))
 
 
 def sample_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None, temperature=1.0, use_eod_token_for_early_termination=True,
@@ -992,7 +1157,7 @@ class SampleScores:
 def sample_batched_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None, temperature=1.0, use_eod_token_for_early_termination=True,
                         stop_on_double_eol=False, stop_on_eol=False, termination_id=None, prompt_length=None, num_samples=1, seed=0,
                         streams=None, advance_fn=None, constraints: Optional["LogitsConstraints"] = None, constrain_fn=None,
-                        return_scores=False, score_fn=None, mixed_prompts=False):
+                        return_scores=False, score_fn=None, mixed_prompts=False, trie_fn=None):
     """Sampled generation for B clips x num_samples sequences in lockstep, the whole of a step's sampling and bookkeeping in one
     launch: tokens [B, L], query_embeds [B, Q, H]; sequence j belongs to clip j // num_samples.  The prefill runs once per clip
     (state.prefill_fan_out) and fans out to the clip's samples; afterwards a step is state.step(st.next_tok) and _Sampler.step:
@@ -1022,10 +1187,15 @@ def sample_batched_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None
     column prompt_length[r] + t.  The loop ends when every row is done or after final_len - P_min steps; a clip with a longer prompt
     runs out of columns earlier and is frozen by the kernels (done, counted in n_done), with no host bookkeeping; it keeps stepping as
     padding rows, which _mixed_prompt_state checks against the position table before the first launch.  -> tokens [B * num_samples,
-    n], n covering every written column; a row holds its prompt, its generated tokens and, behind them, the rest of its input row."""
+    n], n covering every written column; a row holds its prompt, its generated tokens and, behind them, the rest of its input row.
+    constraints.allowed_phrases (a PhraseTrie): between constrain_fn and advance_fn every step keeps only the tokens that continue a row
+    along the trie, through trie_fn (the ops.logits_trie_mask* of the mode) with the same table, lengths, column, termination id and
+    -inf: a banned token is never drawn, so every row is a phrase followed by the termination id (and then draws that id until the
+    loop ends).  score_fn then records log-probabilities RENORMALISED over the allowed tokens.  Raised before the first launch: what
+    _active_trie refuses (min_new_tokens, stop_on_eol / stop_on_double_eol, a phrase with the termination id)."""
     B, dev, N = tokens.size(0), tokens.device, int(num_samples)
     sampler = _Sampler(cfg, dict(num_samples=num_samples), temperature, seed, termination_id, stop_on_double_eol, stop_on_eol, advance_fn,
-                       constraints, constrain_fn, return_scores, score_fn, "sample_score")
+                       constraints, constrain_fn, return_scores, score_fn, "sample_score", trie_fn)
     R = B * N
     if mixed_prompts:
         lens = _mixed_prompt_lengths(prompt_length, B, tokens.size(1), "mixed_prompts=True")
@@ -1065,7 +1235,7 @@ class _Sampler:
     termination triple (termination_id, termination_mode, the eos ids of min_new_tokens) and the three calls of a step."""
 
     def __init__(self, cfg, at_least_one: dict, temperature, seed, termination_id, stop_on_double_eol, stop_on_eol, advance_fn, constraints,
-                 constrain_fn, return_scores, score_fn, score_name: str):
+                 constrain_fn, return_scores, score_fn, score_name: str, trie_fn=None):
         if any(int(v) < 1 for v in at_least_one.values()):
             raise ValueError(f"{' and '.join(at_least_one)} must be at least 1 (got {', '.join(str(v) for v in at_least_one.values())})")
         if return_scores and score_fn is None:
@@ -1076,16 +1246,19 @@ class _Sampler:
         self.termination_id = cfg.eod_id if termination_id is None else int(termination_id)
         self.mode = 2 if stop_on_double_eol else 1 if stop_on_eol else 0
         self.eos_ids = [628, 198] if self.mode else [self.termination_id]
-        self.advance_fn, self.constrain_fn, self.score_fn = advance_fn, constrain_fn, score_fn
+        self.trie = _active_trie(constraints, trie_fn, self.eos_ids, eol_stop=self.mode != 0)
+        self.advance_fn, self.constrain_fn, self.score_fn, self.trie_fn = advance_fn, constrain_fn, score_fn, trie_fn
         self.draw = dict(temperature=temperature, top_k=cfg.top_k, top_p=cfg.top_p, seed=seed, vocab_size=cfg.vocab_size,
                          termination_mode=self.mode, termination_id=self.termination_id)
 
     def step(self, logits, st: "SampleState", sc: Optional["SampleScores"], **where):
-        """constrain (active constraints only), advance, score (sc given) on one step's logits; `where` is the entries' own keyword for
+        """constrain (active constraints only), the trie mask (allowed_phrases only), advance, score (sc given) on one step's logits; `where` is the entries' own keyword for
         the column a row works on: pos= (one for all), step= (the row's prompt length + step) or row_step= (a step per row)"""
         if self.constraints is not None:
             self.constrain_fn(logits, st.tokens, constraints=self.constraints, prompt_len=st.prompt_len, eos_ids=self.eos_ids,
                               ban_value=BAN_SAMPLING, **where)
+        if self.trie is not None:
+            self.trie_fn(logits, st.tokens, trie=self.trie, prompt_len=st.prompt_len, eos_ids=self.eos_ids, ban_value=BAN_SAMPLING, **where)
         self.advance_fn(logits, st, **where, **self.draw)
         if sc is not None:
             self.score_fn(logits, st, sc, **where)
@@ -1170,7 +1343,7 @@ def _inflight_budgets(cfg, max_new_tokens, default, lens, final_len, Q):
 def sample_inflight_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None, temperature=1.0, use_eod_token_for_early_termination=True,
                          stop_on_double_eol=False, stop_on_eol=False, termination_id=None, prompt_length=None, num_samples=1, slots=32,
                          max_new_tokens=None, refill_min=None, seed=0, streams=None, advance_fn=None,
-                         constraints: Optional["LogitsConstraints"] = None, constrain_fn=None, return_scores=False, score_fn=None):
+                         constraints: Optional["LogitsConstraints"] = None, constrain_fn=None, return_scores=False, score_fn=None, trie_fn=None):
     """sample_batched_loop's mixed mode with the finished clips' rows REFILLED in flight (continuous batching): tokens [n, L],
     query_embeds [n, Q, H], prompt_length n lengths; `slots` clips x num_samples sequences stay resident and the n clips of the
     call pass through them in input order.  A lockstep chunk is held until its slowest sequence ends while a decode step costs the
@@ -1195,18 +1368,21 @@ def sample_inflight_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=Non
     table (a ValueError before the first launch otherwise).  When the input runs out, free slots idle until the last clip ends.
     -> SimpleNamespace(tokens [n * num_samples, final_len] (a row: its prompt, its generated tokens, behind them the rest of its
     input row), written [n] (list: the columns of clip c that hold prompt or generated tokens), scores (a SampleScores over all rows,
-    or None), steps / prefills (decode steps and prefill passes issued))."""
+    or None), steps / prefills (decode steps and prefill passes issued)).
+    constraints.allowed_phrases (a PhraseTrie) with trie_fn (ops.logits_trie_mask_steps): as in sample_batched_loop, every row on its
+    own step; the default budget is then min(tokens_to_generate, trie.max_len + 1), the longest phrase and its termination id."""
     n, dev, N, slots = tokens.size(0), tokens.device, int(num_samples), int(slots)
     if advance_fn is None:
         raise ValueError("sample_inflight_loop needs an advance_fn (ops.sample_advance_steps)")
     sampler = _Sampler(cfg, dict(num_samples=num_samples, slots=slots), temperature, seed, termination_id, stop_on_double_eol, stop_on_eol,
-                       advance_fn, constraints, constrain_fn, return_scores, score_fn, "sample_score_steps")
+                       advance_fn, constraints, constrain_fn, return_scores, score_fn, "sample_score_steps", trie_fn)
     lens = _mixed_prompt_lengths(prompt_length, n, tokens.size(1), "sample_inflight_loop")
     sl = _Slots(n, slots, refill_min, None)
     longest = max(lens)
     table, final_len, Q = _pad_for_generation(cfg, tokens, cfg.eod_id, longest, query_embeds)
     table = table[:, :final_len]
-    budgets = sl.budgets = _inflight_budgets(cfg, max_new_tokens, [int(cfg.tokens_to_generate)] * n, lens, final_len, Q)
+    default = int(cfg.tokens_to_generate) if sampler.trie is None else min(int(cfg.tokens_to_generate), sampler.trie.max_len + 1)
+    budgets = sl.budgets = _inflight_budgets(cfg, max_new_tokens, [default] * n, lens, final_len, Q)
     R = slots * N
     state = make_state(slots, N, Q + longest, max(max(budgets) - 1, 1))
     streams = (torch.arange(n * N, dtype=torch.int64, device=dev) if streams is None
@@ -1277,7 +1453,7 @@ BEAM_RESULT_ARRAYS = ("tokens", "scores", "hyp_score", "hyp_order", "hyp_tokens"
 def beam_inflight_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None, beam_size=5, num_return_gen=1, stop_token=None,
                        prompt_length=None, slots=32, max_new_tokens=None, refill_min=None, topk_fn=None, advance_fn=None,
                        constraints: Optional["LogitsConstraints"] = None, constrain_fn=None, return_scores=False, beam_groups=1,
-                       diversity_penalty=0.0):
+                       diversity_penalty=0.0, trie_fn=None):
     """beam_search_batched_loop with the finished clips' slots REFILLED in flight, as sample_inflight_loop does for samples: tokens
     [n, L], query_embeds [n, Q, H], prompt_length n lengths; `slots` clips x G * K sequences stay resident (K = beam_size beams per
     group, G = beam_groups) and the n clips of the call pass through them in input order.  A clip LEAVES when all its groups are done
@@ -1306,7 +1482,10 @@ def beam_inflight_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None,
     sample_inflight_loop's default of tokens_to_generate); budgets are capped by the table and the last position a clip feeds, Q +
     prompt_length[c] + budget - 2, must be a row of the position table (a ValueError before the first launch otherwise).
     -> a SimpleNamespace(results: the list of n namespaces beam_search_batched_loop returns (sequences, scores, group for G > 1),
-    advances [n]: the positions every clip was advanced by before it left, steps / prefills: decode steps and prefill passes issued)."""
+    advances [n]: the positions every clip was advanced by before it left, steps / prefills: decode steps and prefill passes issued).
+    constraints.allowed_phrases (a PhraseTrie) with trie_fn (ops.logits_trie_mask_steps): as in beam_search_batched_loop, between
+    constrain_fn and topk_fn, every clip on its own step; the host finish drops the hypotheses that are no phrase and the results carry
+    phrase_index.  The default budget is then min(final_len - prompt_length[c], trie.max_len + 1)."""
     _no_sample_scores(return_scores, "beam_inflight_loop")
     n, dev, K, slots = tokens.size(0), tokens.device, int(beam_size), int(slots)
     if advance_fn is None or topk_fn is None:
@@ -1314,13 +1493,17 @@ def beam_inflight_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None,
     if slots < 1 or K < 1:
         raise ValueError(f"slots and beam_size must be at least 1 (got {slots}, {K})")
     G, lam, per_group = _beam_groups(beam_groups, diversity_penalty, num_return_gen, K)
-    constraints = _active_constraints(constraints, constrain_fn)
+    constraints_given, constraints = constraints, _active_constraints(constraints, constrain_fn)
     lens = _mixed_prompt_lengths(prompt_length, n, tokens.size(1), "beam_inflight_loop")
     sl = _Slots(n, slots, refill_min, None)
     stop_token = cfg.eod_id if stop_token is None else int(stop_token)
+    trie = _active_trie(constraints_given, trie_fn, [stop_token])
+    if trie is not None:
+        tokens = _stop_behind_prompts(tokens, lens, stop_token)
     longest = max(lens)
     table, final_len, Q = _pad_for_generation(cfg, tokens, stop_token, longest, query_embeds)
-    sl.budgets = _inflight_budgets(cfg, max_new_tokens, [final_len - pl for pl in lens], lens, final_len, Q)
+    sl.budgets = _inflight_budgets(cfg, max_new_tokens, [final_len - pl if trie is None else min(final_len - pl, trie.max_len + 1) for pl in lens],
+                                   lens, final_len, Q)
     if table.size(1) > 2048:
         raise ValueError(f"a token table of {table.size(1)} columns; the advance kernels take 2048")
     fan, m = G * K, 2 * K + (G - 1) * K
@@ -1355,9 +1538,14 @@ def beam_inflight_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None,
             logits = torch.zeros((slots * fan, first.shape[1]), dtype=torch.bfloat16, device=dev)   # the first iteration; frozen rows read none of it
         if fresh:                                                                          # (2) the prefill logits of the fresh slots
             logits.view(slots, fan, -1)[fresh_d] = first[:, None, :]
-        if constraints is not None:                                                        # (3) every clip on its own step
-            constrain_fn(logits, bs.tokens.view(slots * fan, -1), row_step=clip_step.repeat_interleave(fan), constraints=constraints,
+        if constraints is not None or trie is not None:                                    # (3) every clip on its own step
+            row_step = clip_step.repeat_interleave(fan)
+        if constraints is not None:
+            constrain_fn(logits, bs.tokens.view(slots * fan, -1), row_step=row_step, constraints=constraints,
                          prompt_len=row_prompt_len, eos_ids=[stop_token], ban_value=BAN_BEAM)
+        if trie is not None:
+            trie_fn(logits, bs.tokens.view(slots * fan, -1), row_step=row_step, trie=trie, prompt_len=row_prompt_len, eos_ids=[stop_token],
+                    ban_value=BAN_BEAM)
         vals, idxs = topk_fn(logits, m, bs.scores.view(-1))
         advance_fn(vals, idxs, bs, groups=G, diversity_penalty=lam, vocab=logits.size(-1), clip_prompt_len=clip_prompt_len, clip_step=clip_step,
                    stop_token=stop_token)
@@ -1374,7 +1562,7 @@ def beam_inflight_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None,
         if running and sl.busy():                                                          # (5) the suffix rows follow their beams
             state.reorder(bs.src_row, (group_t + 1).clamp_(min=0), max_t + 1)
     h = SimpleNamespace(**{k: v.cpu() for k, v in out.items()})                            # one download
-    return SimpleNamespace(results=_beam_results(h, n, G, K, per_group, dev), advances=advances, steps=state.steps, prefills=state.prefills)
+    return SimpleNamespace(results=_beam_results(h, n, G, K, per_group, dev, trie, lens, stop_token), advances=advances, steps=state.steps, prefills=state.prefills)
 
 
 def pad_after_termination(tokens: torch.Tensor, prompt_len, termination_id: int, width: int, fill: int) -> torch.Tensor:
@@ -1406,6 +1594,16 @@ SAMPLER_OPS = {"uniform": ("sample_advance", "logits_constrain", "sample_score")
                "steps": ("sample_advance_steps", "logits_constrain_steps", "sample_score_steps")}
 
 
+TRIE_OPS = {"uniform": "logits_trie_mask", "ragged": "logits_trie_mask_ragged", "steps": "logits_trie_mask_steps"}
+
+
+def _trie_fn(mode: str, constraints) -> dict:
+    """the trie_fn keyword of a loop for constraints with allowed_phrases, looked up in `ops` at the call; nothing without them"""
+    if constraints is None or constraints.allowed_phrases is None:
+        return {}
+    return dict(trie_fn=getattr(ops, TRIE_OPS[mode]))
+
+
 def _sampler_fns(mode: str, return_scores) -> dict:
     """a sampler mode's advance_fn / constrain_fn keywords (with return_scores also the score keywords), looked up in `ops` at the call"""
     advance, constrain, score = (getattr(ops, name) for name in SAMPLER_OPS[mode])
@@ -1431,7 +1629,8 @@ def install(gpt_cls):
         """beam_search for tokens [B, L] / query_embeds [B, Q, H] with one prompt length (prompt_length an int) or one per clip
         (a sequence of B lengths: beam_search_batched_loop's mixed mode, kv="shared_prefix" only), B clips in lockstep -> a list of B results;
         kv="shared_prefix" keeps the visual prefix and the prompt once per clip (SharedPrefixDecodeState); constraints: a
-        LogitsConstraints, applied on the device every step; beam_groups = G > 1: diverse beam search, G groups of beam_size beams
+        LogitsConstraints, applied on the device every step (with allowed_phrases: a closed set of phrases, the results carry
+        phrase_index and renormalised scores); beam_groups = G > 1: diverse beam search, G groups of beam_size beams
         each with diversity_penalty between them (beam_search_batched_loop; ops.beam_advance_groups); decode_weights="fp8": the steps
         run on the decoder's e4m3 codes (DecodeWeightsQ8)"""
         _no_sample_scores(kw.pop("return_scores", False), "beam_search_batched")
@@ -1440,14 +1639,15 @@ def install(gpt_cls):
         return beam_search_batched_loop(_gen_config(self), make_state_fn(self, kv, decode_weights), tokens, query_embeds=query_embeds, beam_size=beam_size,
                                         num_return_gen=num_return_gen, stop_token=stop_token, prompt_length=kw.pop("prompt_length", None),
                                         topk_fn=lambda lg, k, add: ops.logprob_topk(lg, k, add=add), advance_fn=ops.beam_advance,
-                                        constraints=constraints, constrain_fn=ops.logits_constrain, **groups)
+                                        constraints=constraints, constrain_fn=ops.logits_constrain, **groups, **_trie_fn("uniform", constraints))
 
     def sample_batched(self, tokens, query_embeds=None, temperature=1.0, num_samples=1, seed=0, streams=None, top_k=None, top_p=None,
                        kv="per_sequence", constraints=None, return_scores=False, decode_weights="bf16", mixed_prompts=False, **kw):
         """sample with the sampler on the device (sample_batched_loop): tokens [B, L] -> [B * num_samples, n]; top_k / top_p override
         the configuration's values; the draws are those of (seed, position, streams[row]) -- not torch's generator;
         kv="shared_prefix" keeps the visual prefix and the shortest prompt once per clip (SharedPrefixDecodeState); constraints: a
-        LogitsConstraints, applied on the device every step; return_scores=True: -> (tokens, SampleScores), the model's
+        LogitsConstraints, applied on the device every step (with allowed_phrases: every row is a phrase of the trie and the scores
+        are renormalised over the allowed tokens); return_scores=True: -> (tokens, SampleScores), the model's
         log-probability of every generated token, recorded on the device every step (ops.sample_score); decode_weights="fp8": the
         steps run on the decoder's e4m3 codes (DecodeWeightsQ8); mixed_prompts=True with prompt_length = B lengths and
         kv="shared_prefix": ONE loop over clips whose prompts differ in length, the table left-aligned and every row on its own
@@ -1458,7 +1658,8 @@ def install(gpt_cls):
                              "prefix length per clip")
         return sample_batched_loop(_sampler_config(self, top_k, top_p), make_state, tokens, query_embeds=query_embeds, temperature=temperature,
                                    num_samples=num_samples, seed=seed, streams=streams, constraints=constraints,
-                                   mixed_prompts=bool(mixed_prompts), **_sampler_fns("ragged" if mixed_prompts else "uniform", return_scores), **kw)
+                                   mixed_prompts=bool(mixed_prompts), **_sampler_fns("ragged" if mixed_prompts else "uniform", return_scores),
+                                   **_trie_fn("ragged" if mixed_prompts else "uniform", constraints), **kw)
 
     def sample_inflight(self, tokens, query_embeds=None, temperature=1.0, num_samples=1, slots=32, seed=0, streams=None, top_k=None, top_p=None,
                         constraints=None, return_scores=False, decode_weights="bf16", max_new_tokens=None, refill_min=None, **kw):
@@ -1469,7 +1670,7 @@ def install(gpt_cls):
         return sample_inflight_loop(_sampler_config(self, top_k, top_p), make_inflight_state_fn(self, decode_weights), tokens,
                                     query_embeds=query_embeds, temperature=temperature, num_samples=num_samples, slots=slots, seed=seed,
                                     streams=streams, max_new_tokens=max_new_tokens, refill_min=refill_min, constraints=constraints,
-                                    **_sampler_fns("steps", return_scores), **kw)
+                                    **_sampler_fns("steps", return_scores), **_trie_fn("steps", constraints), **kw)
 
     def beam_search_inflight(self, tokens, query_embeds=None, beam_size=5, num_return_gen=1, stop_token=None, prompt_length=None, slots=32,
                              max_new_tokens=None, refill_min=None, beam_groups=1, diversity_penalty=0.0, constraints=None,
@@ -1483,7 +1684,7 @@ def install(gpt_cls):
                                   slots=slots, max_new_tokens=max_new_tokens, refill_min=refill_min, beam_groups=beam_groups,
                                   diversity_penalty=diversity_penalty, constraints=constraints,
                                   topk_fn=lambda lg, k, add: ops.logprob_topk(lg, k, add=add), advance_fn=ops.beam_advance_steps,
-                                  constrain_fn=ops.logits_constrain_steps, **kw)
+                                  constrain_fn=ops.logits_constrain_steps, **_trie_fn("steps", constraints), **kw)
 
     @torch.no_grad()
     def generate(self, tokens, do_sample=True, termination_id=None, *args, **kw):                # :1875-1880

@@ -998,6 +998,60 @@ def logits_constrain_steps(logits, tokens, *, row_step, constraints, prompt_len,
     return _logits_constrain("logits_constrain_steps", **locals())
 
 
+def _logits_trie_mask(entry, logits, tokens, *, pos=None, step=None, row_step=None, trie, prompt_len, prompt_len_all=0, eos_ids, ban_value,
+                      node_out, vocab, ld):
+    """the body of logits_trie_mask, logits_trie_mask_ragged and logits_trie_mask_steps, which pass all their arguments on: `entry` is
+    the C entry's name without the mpv_ prefix"""
+    if pos is None and prompt_len is None:                # a column per row is counted from the row's prompt length
+        raise _lib.MpvError(f"{entry}: prompt_len int64 [rows] is required")
+    _need_cuda(logits, tokens, prompt_len, node_out)
+    if logits.dtype != torch.bfloat16 or logits.ndim != 2 or logits.stride(1) != 1:
+        raise _lib.MpvError(f"{entry}: logits must be bf16 [rows, ld] with unit column stride (got {logits.dtype} {tuple(logits.shape)})")
+    rows = logits.shape[0]
+    if tokens.dtype != torch.int64 or tokens.ndim != 2 or tokens.shape[0] != rows or not tokens.is_contiguous():
+        raise _lib.MpvError(f"{entry}: tokens must be contiguous int64 [{rows}, row_len] (got {tokens.dtype} {tuple(tokens.shape)})")
+    if prompt_len is not None and (prompt_len.dtype != torch.int64 or prompt_len.numel() != rows or not prompt_len.is_contiguous()):
+        raise _lib.MpvError(f"{entry}: prompt_len must be contiguous int64 [{rows}]")
+    if node_out is not None and (node_out.dtype != torch.int32 or node_out.numel() != rows or not node_out.is_contiguous()):
+        raise _lib.MpvError(f"{entry}: node_out must be contiguous int32 [{rows}]")
+    key = (str(logits.device), tuple(int(t) for t in eos_ids))
+    eos = trie._device.get(key)                           # the termination ids on the device, made once per (device, ids) and kept on the trie
+    if eos is None:
+        eos = trie._device[key] = torch.tensor(key[1], dtype=torch.int64, device=logits.device)
+    arrays = trie.arrays(logits.device)
+    pos, more = _where(entry, rows, pos, step, row_step)
+    d = _lib.LogitsTrieDesc()
+    d.logits, d.tokens, d.prompt_len, d.eos_ids, d.node_out = _p(logits), _p(tokens), _p(prompt_len), (_p(eos) if eos.numel() else None), _p(node_out)
+    d.child_begin, d.child_tok, d.child_node, d.terminal = (_p(a) for a in arrays)
+    d.ld, d.prompt_len_all = int(ld) if ld is not None else logits.stride(0), int(prompt_len_all)
+    d.rows, d.vocab, d.row_len, d.pos = rows, int(vocab) if vocab is not None else logits.shape[-1], tokens.shape[1], int(pos)
+    d.n_eos, d.n_nodes, d.n_edges, d.ban_value = eos.numel(), trie.n_nodes, trie.n_edges, float(ban_value)
+    check(getattr(_lib.lib(), "mpv_" + entry)(C.byref(d), *more, _stream()), "mpv_" + entry)
+    return logits
+
+
+def logits_trie_mask(logits, tokens, *, pos, trie, prompt_len=None, prompt_len_all=0, eos_ids, ban_value=float("-inf"), node_out=None, vocab=None,
+                     ld=None):
+    """One step's closed-vocabulary mask, in place and in one launch (include/mpv.h: mpv_logits_trie_mask; trie is a
+    generation.PhraseTrie): in logits bf16 [rows, ld] (the first `vocab` columns) only the tokens that continue tokens[r, prompt_len[r] :
+    pos] along the trie keep their bits -- and eos_ids where a phrase ends, or alone once the row has left the trie -- every other column
+    becomes ban_value.  prompt_len int64 [rows] (rows with prompt_len > pos are left alone), or None: prompt_len_all for every row.
+    node_out int32 [rows] (optional): the node every row stands on, -1 dead, -2 untouched.  -> logits"""
+    return _logits_trie_mask("logits_trie_mask", **locals())
+
+
+def logits_trie_mask_ragged(logits, tokens, *, step, trie, prompt_len, eos_ids, ban_value=float("-inf"), node_out=None, vocab=None, ld=None):
+    """logits_trie_mask for a LEFT-ALIGNED table of prompts of different lengths (include/mpv.h: mpv_logits_trie_mask_ragged): row r
+    works on column prompt_len[r] + step; a row whose column lies behind the table is left alone.  -> logits"""
+    return _logits_trie_mask("logits_trie_mask_ragged", **locals())
+
+
+def logits_trie_mask_steps(logits, tokens, *, row_step, trie, prompt_len, eos_ids, ban_value=float("-inf"), node_out=None, vocab=None, ld=None):
+    """logits_trie_mask_ragged with a generation step per row (include/mpv.h: mpv_logits_trie_mask_steps): row_step int32 [rows] on the
+    device; a row with a negative step, or whose column lies behind the table, is left alone.  -> logits"""
+    return _logits_trie_mask("logits_trie_mask_steps", **locals())
+
+
 def _sample_score(entry, logits, st, sc, *, pos=None, step=None, row_step=None, vocab, ld):
     """the body of sample_score, sample_score_ragged and sample_score_steps, which pass all their arguments on: `entry` is the C
     entry's name without the mpv_ prefix"""
