@@ -53,6 +53,12 @@ What this entry point adds to downstream/finetune_common.py:
     phrase, "pred_candidates" lists the up to 5 best as {"caption", "phrase_index", "score"}, the score renormalised over the allowed
     tokens; needs `--eval_batched_beam`, combines with `--eval_shared_kv`, `--eval_fp8_decode`, `--eval_mixed_prompts` and
     `--eval_beam_inflight`, and is refused with `--eval_beam_groups`, `--eval_sample_best_of` and `--eval_min_new_tokens`;
+  * `--eval_sample_consensus N` with `--eval_consensus_metric rouge_l|ngram_f` (not in the reference, default 0 = off): the caption of
+    a clip is the CONSENSUS (minimum-Bayes-risk) choice among N sampled ones instead of the beam search's -- the sample with the
+    largest mean ROUGE-L (beta 1.2; the default) or mean clipped-n-gram F against all N samples, counted over token ids on the device
+    (`model.generate(..., do_sample=True, num_samples=N, consensus=METRIC)`); the chosen caption goes through the result path and the
+    metrics above like `--eval_sample_best_of`'s, with which (as with `--eval_beam_groups` and `--eval_allowed_phrases`) it is
+    refused; it combines with `--eval_shared_kv`, the constraints, `--eval_sample_mixed_prompts` and `--eval_sample_inflight`;
   * `--eval_score_gold` (not in the reference, default off): evaluation also scores every clip's `gold_caption` list, teacher-forced,
     against the query features computed once for that clip (`model.score_captions(..., query_features=)`: one packed pass per batch,
     no padding rows), adds "gold_logprob" / "gold_tokens" lists to the result entries and logs the corpus per-token NLL and perplexity;
@@ -87,7 +93,8 @@ def make_training_batch(video, text, prompt, tokenizer, device, max_length):
 @torch.no_grad()
 def evaluation(model, data_loader, tokenizer, device, config, batched=False, clips_per_search=32, eval_sample=0, seed=0, shared_kv=False,
                constraints=None, best_of=0, score_gold=False, max_length=None, beam_groups=1, diversity_penalty=0.0, fp8_decode=False,
-               mixed_prompts=False, sample_mixed_prompts=False, sample_inflight=False, beam_inflight=False, allowed_phrases=None):
+               mixed_prompts=False, sample_mixed_prompts=False, sample_inflight=False, beam_inflight=False, allowed_phrases=None,
+               consensus=0, consensus_metric="rouge_l"):
     """-> [{video_id, pred_caption, gold_caption}] (:208-238); batched: `--eval_batched_beam`; eval_sample: `--eval_sample`;
     shared_kv: `--eval_shared_kv`, constraints: the keywords of `--eval_repetition_penalty` / `--eval_no_repeat_ngram` /
     `--eval_min_new_tokens` (the lockstep calls only); best_of: `--eval_sample_best_of` (the prediction is the best of that many
@@ -97,7 +104,9 @@ def evaluation(model, data_loader, tokenizer, device, config, batched=False, cli
     search, all of them in "pred_candidates"); fp8_decode: `--eval_fp8_decode`; mixed_prompts: `--eval_mixed_prompts` (the
     lockstep beam-search calls only); sample_mixed_prompts: `--eval_sample_mixed_prompts` (the sampling calls only); sample_inflight:
     `--eval_sample_inflight` (the sampling calls only); beam_inflight: `--eval_beam_inflight` (the lockstep beam-search calls only);
-    allowed_phrases: the strings of `--eval_allowed_phrases` (the lockstep beam search only; tokenised once, here)"""
+    allowed_phrases: the strings of `--eval_allowed_phrases` (the lockstep beam search only; tokenised once, here); consensus /
+    consensus_metric: `--eval_sample_consensus` / `--eval_consensus_metric` (the prediction is the consensus choice among that many
+    samples instead of the beam search's)"""
     module = getattr(model, "module", model)
     module.eval()
     trie = None
@@ -113,16 +122,19 @@ def evaluation(model, data_loader, tokenizer, device, config, batched=False, cli
     if mixed_prompts and not (batched or beam_groups > 1):
         raise ValueError("--eval_mixed_prompts needs --eval_batched_beam or --eval_beam_groups: the per-clip search has one prompt per call")
     mixkw = {"mixed_prompts": True} if mixed_prompts else {}                 # flag absent: the calls below are unchanged
-    if sample_mixed_prompts and not ((eval_sample or best_of) and shared_kv):
+    if consensus and (best_of or beam_groups > 1 or allowed_phrases):
+        raise ValueError("--eval_sample_consensus, --eval_sample_best_of, --eval_beam_groups and --eval_allowed_phrases all choose the "
+                         "prediction: pass one of them")
+    if sample_mixed_prompts and not ((eval_sample or best_of or consensus) and shared_kv):
         raise ValueError("--eval_sample_mixed_prompts needs --eval_sample or --eval_sample_best_of, and --eval_shared_kv")
     smixkw = {"sample_mixed_prompts": True} if sample_mixed_prompts else {}  # flag absent: the calls below are unchanged
-    if sample_inflight and (sample_mixed_prompts or not ((eval_sample or best_of) and shared_kv)):
+    if sample_inflight and (sample_mixed_prompts or not ((eval_sample or best_of or consensus) and shared_kv)):
         raise ValueError("--eval_sample_inflight needs --eval_sample or --eval_sample_best_of, and --eval_shared_kv, without "
                          "--eval_sample_mixed_prompts")
     if sample_inflight:
         smixkw = {"inflight": True}
     if beam_inflight:
-        _check_beam_inflight(batched, shared_kv, mixed_prompts, eval_sample or best_of or sample_mixed_prompts or sample_inflight)
+        _check_beam_inflight(batched, shared_kv, mixed_prompts, eval_sample or best_of or consensus or sample_mixed_prompts or sample_inflight)
         mixkw = {"beam_inflight": True}
     result = []
     for n, (video, video_ids, gold_caption) in enumerate(data_loader):
@@ -142,6 +154,9 @@ def evaluation(model, data_loader, tokenizer, device, config, batched=False, cli
             res = [c[:1] for c in candidates]
         elif best_of:
             res = module.generate(video, text_input, do_sample=True, num_samples=best_of, best_of=True, seed=seed + n,
+                                  clips_per_search=clips_per_search, **kvkw, **qkw, **smixkw)
+        elif consensus:
+            res = module.generate(video, text_input, do_sample=True, num_samples=consensus, consensus=consensus_metric, seed=seed + n,
                                   clips_per_search=clips_per_search, **kvkw, **qkw, **smixkw)
         elif trie is not None:
             res, phrase_info = module.generate(video, text_input, batched=True, clips_per_search=clips_per_search, allowed_phrases=trie,
@@ -359,6 +374,8 @@ def main(args, config):
                             **({"sample_mixed_prompts": True} if getattr(args, "eval_sample_mixed_prompts", False) else {}),
                             **({"sample_inflight": True} if getattr(args, "eval_sample_inflight", False) else {}),
                             **({"beam_inflight": True} if getattr(args, "eval_beam_inflight", False) else {}),
+                            **({"consensus": args.eval_sample_consensus, "consensus_metric": args.eval_consensus_metric or "rouge_l"}
+                               if getattr(args, "eval_sample_consensus", 0) else {}),
                             **({"allowed_phrases": read_phrases(args.eval_allowed_phrases)} if getattr(args, "eval_allowed_phrases", None) else {}))
         final = save_result(result, args.result_dir, "val_caption_result")
         val_stats = cal_metric(final)
@@ -390,7 +407,7 @@ def constraint_keywords(args):
     if getattr(args, "eval_min_new_tokens", 0):
         kw["min_new_tokens"] = args.eval_min_new_tokens
     if kw and not (getattr(args, "eval_batched_beam", False) or getattr(args, "eval_sample", 0) or getattr(args, "eval_sample_best_of", 0) or
-                   getattr(args, "eval_beam_groups", 1) > 1):
+                   getattr(args, "eval_sample_consensus", 0) or getattr(args, "eval_beam_groups", 1) > 1):
         raise ValueError(f"--eval_repetition_penalty / --eval_no_repeat_ngram / --eval_min_new_tokens ({kw}) need --eval_batched_beam or "
                          "--eval_sample (or --eval_sample_best_of): the per-clip beam search has no constraints")
     return kw
@@ -417,6 +434,13 @@ def get_args(argv=None):
         p.add_argument("--eval_sample_best_of", type=int, default=0,
                        help="evaluation: the caption of a clip is the most likely of N sampled ones, not the beam search's "
                             "(model.generate(do_sample=True, num_samples=N, best_of=True)); 0 = off")
+        p.add_argument("--eval_sample_consensus", type=int, default=0,
+                       help="evaluation: the caption of a clip is the consensus (minimum-Bayes-risk) choice among N sampled ones, the "
+                            "sample that agrees most with the others, not the beam search's "
+                            "(model.generate(do_sample=True, num_samples=N, consensus=METRIC)); 0 = off")
+        p.add_argument("--eval_consensus_metric", type=str, default=None, choices=("rouge_l", "ngram_f"),
+                       help="--eval_sample_consensus: the agreement, over token ids -- ROUGE-L (beta 1.2; the default) or the mean F of the "
+                            "clipped 1..4-gram matches")
         p.add_argument("--eval_beam_groups", type=int, default=1,
                        help="evaluation: diverse beam search in lockstep, G groups of min(5, 16 // G) beams, the hypotheses re-ranked by the "
                             "model's log-probability per token (model.generate(batched=True, beam_groups=G, rerank_by_logprob=True)); 1 = off")
@@ -449,6 +473,13 @@ def get_args(argv=None):
     args, config = ft.get_args(argv, extra=extra)
     if args.eval_sample_best_of < 0:
         raise ValueError(f"--eval_sample_best_of must not be negative (got {args.eval_sample_best_of})")
+    if args.eval_sample_consensus < 0:
+        raise ValueError(f"--eval_sample_consensus must not be negative (got {args.eval_sample_consensus})")
+    if args.eval_consensus_metric is not None and not args.eval_sample_consensus:
+        raise ValueError("--eval_consensus_metric needs --eval_sample_consensus N")
+    if args.eval_sample_consensus and (args.eval_sample_best_of or args.eval_beam_groups > 1 or args.eval_allowed_phrases):
+        raise ValueError("--eval_sample_consensus, --eval_sample_best_of, --eval_beam_groups and --eval_allowed_phrases all choose the "
+                         "prediction: pass one of them")
     if not 1 <= args.eval_beam_groups <= 8:
         raise ValueError(f"--eval_beam_groups must be in [1, 8] (got {args.eval_beam_groups})")
     if not (math.isfinite(args.eval_diversity_penalty) and args.eval_diversity_penalty >= 0) or \
@@ -456,14 +487,16 @@ def get_args(argv=None):
         raise ValueError(f"--eval_diversity_penalty must be finite, not negative and needs --eval_beam_groups above 1 (got {args.eval_diversity_penalty})")
     if args.eval_beam_groups > 1 and args.eval_sample_best_of:
         raise ValueError("--eval_beam_groups and --eval_sample_best_of both choose the prediction: pass one of them")
-    if args.eval_sample_mixed_prompts and not ((args.eval_sample or args.eval_sample_best_of) and args.eval_shared_kv):
+    if args.eval_sample_mixed_prompts and not ((args.eval_sample or args.eval_sample_best_of or args.eval_sample_consensus) and args.eval_shared_kv):
         raise ValueError("--eval_sample_mixed_prompts needs --eval_sample N or --eval_sample_best_of N, and --eval_shared_kv")
-    if args.eval_sample_inflight and (args.eval_sample_mixed_prompts or not ((args.eval_sample or args.eval_sample_best_of) and args.eval_shared_kv)):
+    if args.eval_sample_inflight and (args.eval_sample_mixed_prompts or
+                                      not ((args.eval_sample or args.eval_sample_best_of or args.eval_sample_consensus) and args.eval_shared_kv)):
         raise ValueError("--eval_sample_inflight needs --eval_sample N or --eval_sample_best_of N, and --eval_shared_kv, without "
                          "--eval_sample_mixed_prompts")
     if args.eval_beam_inflight:
         _check_beam_inflight(args.eval_batched_beam, args.eval_shared_kv, args.eval_mixed_prompts,
-                             args.eval_sample or args.eval_sample_best_of or args.eval_sample_mixed_prompts or args.eval_sample_inflight)
+                             args.eval_sample or args.eval_sample_best_of or args.eval_sample_consensus or args.eval_sample_mixed_prompts or
+                             args.eval_sample_inflight)
     if args.eval_allowed_phrases and (not args.eval_batched_beam or args.eval_beam_groups > 1 or args.eval_sample_best_of or
                                       args.eval_min_new_tokens):
         raise ValueError("--eval_allowed_phrases needs --eval_batched_beam, without --eval_beam_groups, --eval_sample_best_of and "

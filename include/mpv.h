@@ -930,6 +930,57 @@ int mpv_logits_trie_mask_ragged(const mpv_logits_trie_desc* d, mpv_stream_t stre
  * row_step[r] == t.  Refused: as the ragged entry except d->pos, and a NULL row_step. */
 int mpv_logits_trie_mask_steps(const mpv_logits_trie_desc* d, const int32_t* row_step, mpv_stream_t stream);
 /* ------------------------------------------------------------------------------------------
+ * Pairwise overlap counts between caption candidates (generation.consensus_utility / consensus_choice: the consensus, or
+ * minimum-Bayes-risk, choice among a clip's samples or beams): for every ordered pair of every group, the length of the longest
+ * common subsequence and the clipped n-gram matches of the orders 1 .. 4, over TOKEN IDS.
+ * Tables: tok_a int64 [rows_a][ld_a] and tok_b int64 [rows_b][ld_b] (device), of which the first width_a / width_b columns are the
+ *   row (ld >= width).  The same table may be passed twice (a clip's samples against each other); two tables serve "candidates
+ *   against references".  start_x int32 [rows_x] (device): the first generated column of the row, in [0, width_x]; rows of one call
+ *   may differ in it.  begin_x int32 [groups + 1] (device): CSR, group g holds the rows [begin_x[g], begin_x[g + 1]) of side x,
+ *   begin_x[0] = 0, begin_x[groups] = rows_x, non-decreasing: a group may have 0 rows on either side.
+ * Candidate: row r's candidate is tok[r][start[r] : e], e the column of the first `term` at or behind start[r], or width when there
+ *   is none.  A `term` in front of start[r] (inside the prompt) does not end it.  Its length is at most
+ *   MPV_CAPTION_OVERLAP_MAX_LEN: a row with width - start[r] above that is refused.
+ * Outputs (device): len_a int32 [rows_a], len_b int32 [rows_b], the candidates' lengths; counts int32 [pairs][5] with pairs =
+ *   sum_g nA_g * nB_g: group g's nA_g x nB_g pairs row-major (a outer, b inner) from row pair_begin[g] on.  pair_begin int64
+ *   [groups + 1] (device) holds the running sums, pair_begin[0] = 0.  counts[p] = { LCS(a, b), m1, m2, m3, m4 }, m_n = sum over the
+ *   distinct n-grams g of min(count_a(g), count_b(g)); an order longer than either candidate gives 0.  All five are symmetric in
+ *   (a, b).
+ * Host copies: host_start_a / host_start_b / host_begin_a / host_begin_b / host_pair_begin are the same five arrays in HOST memory;
+ *   the refusals below are decided on them, so that nothing is launched over a bad layout.  The kernels read the device arrays and
+ *   clamp what they read, so that even arrays that differ from the host copies cannot make them read outside the tables or hang.
+ * Invariants: a pair has one writer; no atomics; the outputs depend on the pair's two candidates only and not on thread timing;
+ *   no column at or beyond width_x is read.  No limit on the rows of a group or on the number of groups (pairs / 64 < 2^31).
+ * When tok_b, start_b, len_b, ld_b, width_b and rows_b equal side a's, the lengths are computed once.
+ * Refused with a negative code before any launch: a NULL descriptor or pointer (MPV_E_ARG); groups < 1, negative rows or widths,
+ *   ld < width (MPV_E_SHAPE); a begin that does not start at 0, end at rows or is not monotone, a start outside [0, width], a
+ *   pair_begin that is not the running sum of nA_g * nB_g (MPV_E_ARG); width - start above MPV_CAPTION_OVERLAP_MAX_LEN
+ *   (MPV_E_SHAPE). */
+#define MPV_CAPTION_OVERLAP_MAX_LEN 255
+#define MPV_CAPTION_OVERLAP_COUNTS 5
+typedef struct mpv_caption_overlap_desc {
+  const int64_t* tok_a;
+  const int64_t* tok_b;
+  const int32_t* start_a;
+  const int32_t* start_b;
+  const int32_t* begin_a;
+  const int32_t* begin_b;
+  const int64_t* pair_begin;
+  int32_t* len_a;
+  int32_t* len_b;
+  int32_t* counts;
+  const int32_t* host_start_a;
+  const int32_t* host_start_b;
+  const int32_t* host_begin_a;
+  const int32_t* host_begin_b;
+  const int64_t* host_pair_begin;
+  int64_t ld_a;
+  int64_t ld_b;
+  int64_t term;
+  int rows_a, rows_b, width_a, width_b, groups;
+} mpv_caption_overlap_desc;
+int mpv_caption_overlap(const mpv_caption_overlap_desc* d, mpv_stream_t stream);
+/* ------------------------------------------------------------------------------------------
  * Sequence scores of sampled generation in lockstep (generation.SampleScores): ONE launch, right after mpv_sample_advance, records
  * the model's log-probability of the token that call wrote into column `pos` -- log_softmax of the RAW logits the sampler read
  * (after mpv_logits_constrain edited them, if it did).  Temperature, top-k and top-p are ignored by design: the score is the

@@ -141,6 +141,15 @@ class SampleScoreDesc(C.Structure):
                [("ld", c_int64)] + [(n, c_int) for n in ("rows", "vocab", "row_len", "pos")]
 
 
+class CaptionOverlapDesc(C.Structure):
+    _fields_ = [(n, c_void_p) for n in ("tok_a", "tok_b", "start_a", "start_b", "begin_a", "begin_b", "pair_begin", "len_a", "len_b", "counts",
+                                        "host_start_a", "host_start_b", "host_begin_a", "host_begin_b", "host_pair_begin")] + \
+               [("ld_a", c_int64), ("ld_b", c_int64), ("term", c_int64)] + \
+               [(n, c_int) for n in ("rows_a", "rows_b", "width_a", "width_b", "groups")]
+
+
+CAPTION_OVERLAP_MAX_LEN = 255   # include/mpv.h MPV_CAPTION_OVERLAP_MAX_LEN
+
 _RM = [c_int, c_int, c_int]
 _SIGS = {
     "mpv_version": (c_int, []),
@@ -314,6 +323,7 @@ _SIGS.update({
     "mpv_logits_trie_mask": (c_int, [C.POINTER(LogitsTrieDesc), c_void_p]),
     "mpv_logits_trie_mask_ragged": (c_int, [C.POINTER(LogitsTrieDesc), c_void_p]),
     "mpv_logits_trie_mask_steps": (c_int, [C.POINTER(LogitsTrieDesc), c_void_p, c_void_p]),
+    "mpv_caption_overlap": (c_int, [C.POINTER(CaptionOverlapDesc), c_void_p]),
 })
 
 EXPORTS = tuple(_SIGS)

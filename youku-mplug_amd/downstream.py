@@ -336,7 +336,8 @@ class DistributedGPT3_Caption(_GenCls):
                  top_k=None, top_p=None, seed=0, kv_cache="per_sequence", repetition_penalty=None, no_repeat_ngram_size=0, min_new_tokens=0,
                  banned_token_ids=None, constrain_prompt=False, return_scores=False, best_of=False, length_penalty=1.0, query_features=None,
                  beam_groups=1, diversity_penalty=0.0, rerank_by_logprob=False, decode_weights="bf16", mixed_prompts=False, sample_mixed_prompts=False,
-                 inflight=False, max_new_tokens=None, refill_min=None, beam_inflight=False, allowed_phrases=None, **kw):
+                 inflight=False, max_new_tokens=None, refill_min=None, beam_inflight=False, allowed_phrases=None, consensus=None,
+                 rerank_by_consensus=None, **kw):
         """One beam search per sample (:790-809): prompt = text.input_ids[i, :mask.sum()-1], prefix = its query features.
         batched=True (not in the reference, default off): the clips are grouped by prompt length and every group is searched in
         lockstep, `clips_per_search` clips at a time (generation.beam_search_batched_loop: the decoder's weights are read once per
@@ -433,11 +434,43 @@ class DistributedGPT3_Caption(_GenCls):
         scores; a clip returns the best min(num_return_gen, phrases the search reached) rows.  do_sample=True: with return_scores the
         clip's dict also holds phrase_index [N].  All these scores are RENORMALISED over the allowed tokens, not the model's
         likelihoods over the vocabulary.  It combines with kv_cache, decode_weights, beam_groups, the mixed and in-flight modes and the
-        other constraints except min_new_tokens; rerank_by_logprob is refused (score the phrases with score_captions instead)."""
+        other constraints except min_new_tokens; rerank_by_logprob is refused (score the phrases with score_captions instead).
+        consensus="rouge_l" | "ngram_f" (do_sample=True only; default None: no call and no launch is added): one [1, Lt] tensor per
+        clip, the CONSENSUS (minimum-Bayes-risk) choice among its num_samples samples: the sample h with the largest mean utility
+        U[h] = mean_r u(h, r) over all the clip's samples r, itself included (generation.consensus_utility / consensus_choice: ROUGE-L
+        with beta 1.2, or the mean F of the clipped 1..4-gram matches; a tie goes to the lowest sample index).  Likelihood prefers
+        short, generic captions; this prefers the caption the other samples agree with.  The pairwise overlap counts are taken on the
+        device from the padded token table the call has built anyway (ops.caption_overlap: one launch set per chunk) and come down in
+        the chunk's one download beside the tokens and scores; the utilities are fp64 on the host.  The utilities are over TOKEN IDS,
+        the entry point's corpus metrics over CJK characters.  A candidate holds at most 255 tokens: a table with more generated
+        columns than that is refused before anything runs.  With return_scores the clip's dict holds the chosen sample's entries and
+        `index` as with best_of, plus consensus [N] fp64, U of every sample.  It works in the grouped, sample_mixed_prompts and
+        inflight modes; together with best_of it is refused.
+        rerank_by_consensus="rouge_l" | "ngram_f" (batched=True only; default None): -> (res, info).  Each clip's returned hypotheses
+        are reordered by U descending, ties in search order (one ops.caption_overlap call over all the clips' rows: the clips may
+        return different numbers of rows); info[i] holds consensus [n] fp64 and group [n] int64 in the new order.  Refused together
+        with rerank_by_logprob and with allowed_phrases."""
         Q, Hh = self.num_learnable_token, self.text_width
         G = int(beam_groups)
         from . import generation as _gen
         _gen._check_weight_mode(decode_weights)
+        for name, metric in (("consensus", consensus), ("rerank_by_consensus", rerank_by_consensus)):
+            if metric is not None and metric not in _gen.CONSENSUS_METRICS:
+                raise ValueError(f"{name} must be one of {_gen.CONSENSUS_METRICS} or None (got {metric!r})")
+        if consensus is not None:
+            if not do_sample:
+                raise ValueError("consensus needs do_sample=True (beam hypotheses: batched=True with rerank_by_consensus=)")
+            if best_of:
+                raise ValueError(f"consensus={consensus!r} does not combine with best_of=True: both choose the clip's one caption")
+        if rerank_by_consensus is not None:
+            if do_sample or not batched:
+                raise ValueError("rerank_by_consensus needs batched=True without do_sample (sampled captions: consensus=)")
+            if rerank_by_logprob:
+                raise ValueError(f"rerank_by_consensus={rerank_by_consensus!r} does not combine with rerank_by_logprob=True: both order the "
+                                 "clip's hypotheses")
+            if allowed_phrases is not None:
+                raise ValueError("rerank_by_consensus does not combine with allowed_phrases: the phrases of a closed vocabulary are "
+                                 "alternatives, not paraphrases")
         if decode_weights != "bf16":
             kw = dict(kw, decode_weights=decode_weights)                 # absent keyword: the calls below are today's
         if G != 1 and (do_sample or not batched):
@@ -537,6 +570,21 @@ class DistributedGPT3_Caption(_GenCls):
                 scores = [None] * n
                 if scored:
                     kw = dict(kw, return_scores=True)                    # absent keyword: the calls below are today's
+                if consensus is not None and lengths and width - int(min(lengths)) > ops._lib.CAPTION_OVERLAP_MAX_LEN:
+                    raise ValueError(f"consensus: a row of {width} columns behind a prompt of {int(min(lengths))} tokens can hold a candidate "
+                                     f"of more than {ops._lib.CAPTION_OVERLAP_MAX_LEN} tokens")
+
+                def choose(toks, sc, starts, clips):
+                    """consensus: the chunk's padded device table (N rows per clip of `clips`, generated part from starts[row] on)
+                    -> res / scores of its clips, from ONE download that carries the overlap counts beside the tokens and scores"""
+                    toks, tlp, slp, cnt, picks = _consensus_samples(toks, sc, starts, N, term, width, consensus)
+                    for j, i in enumerate(clips):
+                        rows, (U, b) = slice(j * N, (j + 1) * N), picks[j]
+                        res[i] = toks[rows][b:b + 1]
+                        if scored:
+                            entry = dict(sum_logprob=slp[rows][b:b + 1], count=cnt[rows][b:b + 1], token_logprob=tlp[rows][b:b + 1], index=b,
+                                         consensus=U)
+                            scores[i] = _with_phrase_index(entry, trie, res[i], lengths[i], term)
                 if inflight:                                             # ONE loop over all clips, clips_per_search slots resident
                     more = {k: v for k, v in kw.items() if k != "kv"}
                     out = self.text_decoder.sample_inflight(text.input_ids, query_embeds=qf.contiguous(), temperature=temperature, num_samples=N,
@@ -548,6 +596,9 @@ class DistributedGPT3_Caption(_GenCls):
                     end = torch.as_tensor([w for w in out.written for _ in range(N)], dtype=torch.long).to(out.tokens.device)[:, None]
                     toks = torch.where(col < end, out.tokens, torch.full_like(out.tokens, term))      # behind a clip's budget: padding
                     toks = generation.pad_after_termination(toks, rows_pl, term, width, term)
+                    if consensus is not None:
+                        choose(toks, out.scores if scored else None, rows_pl, range(n))
+                        return (res, scores) if return_scores else res
                     if not scored:
                         toks = toks.cpu()
                         return [toks[i * N:(i + 1) * N] for i in range(n)]
@@ -580,6 +631,11 @@ class DistributedGPT3_Caption(_GenCls):
                                                                           else torch.full((len(sel),), pl, device=qf.device)), **kw)
                     if sample_mixed_prompts:                             # pad_after_termination: one prompt length per row
                         pl = [x for x in pl for _ in range(N)]
+                    if consensus is not None:
+                        toks, sc = out if scored else (out, None)
+                        choose(generation.pad_after_termination(toks, pl, term, width, term), sc,
+                               pl if sample_mixed_prompts else [pl] * (len(chunk) * N), sel.tolist())
+                        continue
                     if not scored:
                         out = generation.pad_after_termination(out, pl, term, width, term).cpu()
                         for j, i in enumerate(sel.tolist()):
@@ -630,6 +686,16 @@ class DistributedGPT3_Caption(_GenCls):
                         groups_of[i] = getattr(out, "group", None)
                         info[i] = dict(phrase_index=getattr(out, "phrase_index", None), scores=out.scores)
                 if trie is not None:
+                    return res, info
+                if rerank_by_consensus is not None:
+                    term = generation._gen_config(self.text_decoder).eod_id if termination_id is None else int(termination_id)
+                    picks = _consensus_rows(res, lengths, term, rerank_by_consensus, qf.device)
+                    for i in range(n):
+                        U = picks[i][0]
+                        order = generation.consensus_order(U)                                # ties keep the search order
+                        grp = groups_of[i] if groups_of[i] is not None else torch.zeros(U.numel(), dtype=torch.int64)
+                        res[i] = res[i][order]
+                        info[i] = dict(consensus=U[order], group=grp[order])
                     return res, info
                 if not rerank_by_logprob:
                     return res
@@ -798,21 +864,81 @@ def best_sample(sum_logprob, count, length_penalty: float = 1.0) -> int:
     return best
 
 
-def _download_scored(tokens, sc, width: int):
-    """tokens int64 [R, width] (padded) and a generation.SampleScores -> CPU (tokens, token_logprob [R, width] padded with 0,
-    sum_logprob [R], count [R]) in ONE device-to-host copy: the rows are packed byte-wise side by side."""
-    R = tokens.shape[0]
-    tlp = torch.zeros((R, width), dtype=torch.float32, device=tokens.device)
-    w = min(width, sc.token_logprob.shape[1])
-    tlp[:, :w] = sc.token_logprob[:, :w]
-    parts = (tokens.contiguous(), tlp, sc.sum_logprob.view(R, 1), sc.count.view(R, 1))
+def _download_rows(parts):
+    """device tensors [R, c_k] of any dtypes -> their CPU copies in ONE device-to-host copy: the rows are packed byte-wise side by side"""
+    R = parts[0].shape[0]
     packed = torch.cat([p.contiguous().view(torch.uint8).view(R, -1) for p in parts], dim=1).cpu()
     out, at = [], 0
     for p in parts:
         nb = p.shape[1] * p.element_size()
         out.append(packed[:, at:at + nb].contiguous().view(p.dtype).view(R, p.shape[1]))
         at += nb
-    return out[0], out[1], out[2].view(R), out[3].view(R)
+    return out
+
+
+def _download_scored(tokens, sc, width: int, extra=()):
+    """tokens int64 [R, width] (padded) and a generation.SampleScores -> CPU (tokens, token_logprob [R, width] padded with 0,
+    sum_logprob [R], count [R]) in ONE device-to-host copy (_download_rows); extra: further [R, c] device tensors that ride along and
+    follow the four in the result"""
+    R = tokens.shape[0]
+    tlp = torch.zeros((R, width), dtype=torch.float32, device=tokens.device)
+    w = min(width, sc.token_logprob.shape[1])
+    tlp[:, :w] = sc.token_logprob[:, :w]
+    out = _download_rows((tokens.contiguous(), tlp, sc.sum_logprob.view(R, 1), sc.count.view(R, 1)) + tuple(extra))
+    return (out[0], out[1], out[2].view(R), out[3].view(R)) + tuple(out[4:])
+
+
+def _consensus_samples(toks, sc, starts, N: int, term: int, width: int, metric: str):
+    """generate(consensus=): toks int64 [R, width] on the device (padded; N rows per clip, the generated part of row r from column
+    starts[r] on), sc the chunk's generation.SampleScores or None -> CPU (tokens, token_logprob, sum_logprob, count -- None without
+    sc --, [(U [N] fp64, index) per clip]).  The overlap counts of every clip's N x N pairs are taken on the device
+    (ops.caption_overlap) and come down in the chunk's ONE download, N * 5 integers beside every row; the utilities and the choice are
+    fp64 on the host (generation.consensus_utility / consensus_choice)."""
+    from . import generation
+    R = toks.shape[0]
+    toks = toks.contiguous()
+    ln, _, counts = ops.caption_overlap(toks, [int(s) for s in starts], list(range(0, R + 1, N)), term=term)
+    extra = (ln.view(R, 1), counts.view(R, N * 5))         # clip j's pairs (a, b) row-major: row j * N + a holds its N pairs
+    if sc is None:
+        toks, ln, counts = _download_rows((toks,) + extra)
+        tlp = slp = cnt = None
+    else:
+        toks, tlp, slp, cnt, ln, counts = _download_scored(toks, sc, width, extra)
+    picks = []
+    for j in range(R // N):
+        rows = slice(j * N, (j + 1) * N)
+        u = generation.consensus_utility(counts[rows].reshape(N, N, 5), ln[rows].view(N), ln[rows].view(N), metric)
+        picks.append(generation.consensus_choice(u))
+    return toks, tlp, slp, cnt, picks
+
+
+def _consensus_rows(res, starts, term: int, metric: str, device):
+    """generate(rerank_by_consensus=): res[i] int64 [n_i, L_i] on the CPU (clip i's hypotheses, the generated part from column
+    starts[i] on) -> [(U [n_i] fp64, index) per clip].  ONE table of all the clips' rows (padded with `term` to the widest), one
+    upload, one ops.caption_overlap call over ragged groups with a start per row, one download."""
+    from . import generation
+    counts_of = [int(r.shape[0]) for r in res]
+    W = max([int(r.shape[1]) for r in res] + [1])
+    table = torch.full((sum(counts_of), W), int(term), dtype=torch.int64)
+    begin, row_start = [0], []
+    for r, s in zip(res, starts):
+        table[begin[-1]:begin[-1] + r.shape[0], :r.shape[1]] = r
+        begin.append(begin[-1] + int(r.shape[0]))
+        row_start += [int(s)] * int(r.shape[0])
+    if not table.shape[0]:
+        return [generation.consensus_choice(torch.zeros((0, 0), dtype=torch.float64)) for _ in res]
+    ln, _, counts = ops.caption_overlap(table.to(device), row_start, begin, term=term)
+    pair_begin = [0]
+    for c in counts_of:
+        pair_begin.append(pair_begin[-1] + c * c)
+    flat = torch.cat([ln.view(-1), counts.view(-1)]).cpu()            # one download
+    ln, counts = flat[:table.shape[0]], flat[table.shape[0]:].view(-1, 5)
+    picks = []
+    for i, c in enumerate(counts_of):
+        u = generation.consensus_utility(counts[pair_begin[i]:pair_begin[i + 1]].reshape(c, c, 5), ln[begin[i]:begin[i + 1]],
+                                         ln[begin[i]:begin[i + 1]], metric)
+        picks.append(generation.consensus_choice(u))
+    return picks
 
 
 def synthetic_gencls_model(shapes, kind: str, num_classes: int = 2, device="cuda", num_frames=None):

@@ -1580,6 +1580,81 @@ def pad_after_termination(tokens: torch.Tensor, prompt_len, termination_id: int,
     return out
 
 
+CONSENSUS_METRICS = ("rouge_l", "ngram_f")
+ROUGE_BETA = 1.2                                   # the caption entry point's rouge_l (pycocoevalcap's Rouge)
+
+
+def consensus_utility(counts, len_h, len_r, metric: str) -> torch.Tensor:
+    """The utility u[h, r] in fp64 of candidate h judged against candidate r, from the integer overlap counts of ops.caption_overlap
+    (include/mpv.h: mpv_caption_overlap) on the CPU: counts int [nA, nB, 5] or [nA * nB, 5] ([LCS, m1, m2, m3, m4] per pair, row-major),
+    len_h [nA] and len_r [nB] the candidates' lengths.  The units are TOKEN IDS -- the caption entry point's corpus metrics are over
+    CJK characters: the two agree in definition, not in unit.
+    metric="rouge_l": P = lcs / len_h, R = lcs / len_r, u = (1 + b^2) P R / (R + b^2 P) with b = 1.2 and 0 when lcs = 0 -- rouge_l of
+    the caption entry point for one reference; asymmetric, h is the candidate being judged.
+    metric="ngram_f": the mean over the orders n = 1 .. 4 with g_h + g_r > 0 of 2 m_n / (g_h + g_r), g_x = max(len_x - n + 1, 0).
+    Both: two empty candidates score 1, exactly one empty candidate scores 0."""
+    if metric not in CONSENSUS_METRICS:
+        raise ValueError(f"metric must be one of {CONSENSUS_METRICS} (got {metric!r})")
+    F64 = torch.float64
+    lh = torch.as_tensor(len_h).to("cpu", F64).reshape(-1, 1)
+    lr = torch.as_tensor(len_r).to("cpu", F64).reshape(1, -1)
+    nA, nB = lh.shape[0], lr.shape[1]
+    c = torch.as_tensor(counts).to("cpu", F64).reshape(nA, nB, 5)
+    both_empty = (lh == 0) & (lr == 0)
+    one = torch.ones((), dtype=F64)
+    if metric == "rouge_l":
+        lcs = c[..., 0]
+        p, r = lcs / torch.where(lh > 0, lh, one), lcs / torch.where(lr > 0, lr, one)
+        b2 = ROUGE_BETA ** 2
+        den = r + b2 * p
+        u = torch.where(lcs > 0, (1 + b2) * p * r / torch.where(den > 0, den, one), torch.zeros((), dtype=F64))
+    else:
+        total, orders = torch.zeros((nA, nB), dtype=F64), torch.zeros((nA, nB), dtype=F64)
+        for n in range(1, 5):
+            g = (lh - n + 1).clamp(min=0) + (lr - n + 1).clamp(min=0)
+            total = total + torch.where(g > 0, 2 * c[..., n] / torch.where(g > 0, g, one), torch.zeros((), dtype=F64))
+            orders = orders + (g > 0).to(F64)
+        u = total / torch.where(orders > 0, orders, one)
+    return torch.where(both_empty, one, u)
+
+
+def consensus_choice(u, weights=None):
+    """u [nA, nB] (consensus_utility) -> (U [nA] fp64, index): U[h] = sum_r w_r u[h, r] / sum_r w_r over ALL the columns, h's own
+    included -- every row is reduced in the same order (r ascending), so identical candidates get bit-identical U --, and index =
+    argmax U, a tie going to the lowest index (None without rows; U within CONSENSUS_TIE of each other are tied: consensus_order).
+    weights None: uniform, the Monte-Carlo estimate of the expected utility for samples."""
+    u = torch.as_tensor(u).to("cpu", torch.float64)
+    nA, nB = u.shape
+    w = torch.ones(nB, dtype=torch.float64) if weights is None else torch.as_tensor(weights).to("cpu", torch.float64).reshape(-1)
+    if w.numel() != nB:
+        raise ValueError(f"{w.numel()} weights for {nB} references")
+    acc, tot = torch.zeros(nA, dtype=torch.float64), 0.0
+    for r in range(nB):                                      # a fixed order, the same for every row
+        acc = acc + w[r] * u[:, r]
+        tot = tot + float(w[r])
+    U = acc / tot if nB and tot != 0.0 else acc
+    order = consensus_order(U)
+    return U, (order[0] if order else None)
+
+
+CONSENSUS_TIE = 1e-12
+
+
+def consensus_order(U) -> list:
+    """the indices of U (fp64, in [0, 1]) by U descending, ties in index order.  Two U within CONSENSUS_TIE of each other count as
+    TIED: the utilities are ratios of small integers, so different candidates often have exactly equal expected utilities (samples of
+    one length whose LCS sums agree), and their fp64 sums may differ in the last bits -- rounding must not decide between them.  The
+    order is built by selection: the lowest index among the remaining ones within the tie width of their maximum comes next."""
+    vals = torch.as_tensor(U).to(torch.float64).tolist()
+    left, order = list(range(len(vals))), []
+    while left:
+        top = max(vals[h] for h in left)
+        pick = next(h for h in left if vals[h] >= top - CONSENSUS_TIE)
+        order.append(pick)
+        left.remove(pick)
+    return order
+
+
 def _sampler_config(gpt, top_k=None, top_p=None):
     """_gen_config with the filter overridden: giving either of top_k / top_p replaces both (the other one is then off)"""
     cfg = _gen_config(gpt)

@@ -1096,6 +1096,69 @@ def sample_score_steps(logits, st, sc, *, row_step, vocab=None, ld=None):
     return _sample_score("sample_score_steps", **locals())
 
 
+def caption_overlap(tok_a, start_a, begin_a, tok_b=None, start_b=None, begin_b=None, *, term, width_a=None, width_b=None):
+    """Pairwise overlap counts between caption candidates on the current stream (include/mpv.h: mpv_caption_overlap).  tok_x: int64
+    [rows_x, >= width_x] on the device with unit column stride (the row stride may exceed the width; width_x defaults to the column
+    count); start_x: rows_x first generated columns and begin_x: the groups' CSR offsets [groups + 1], both HOST sequences or CPU
+    tensors.  Side b defaults to side a (a clip's candidates against each other).  -> (len_a [rows_a], len_b [rows_b], counts
+    [pairs, 5]) int32 on the device: the candidates' lengths and, group after group, its nA x nB pairs row-major with [LCS, m1, m2,
+    m3, m4] each.  Raises ValueError before any launch when a row could hold a candidate of more than 255 tokens."""
+    same = tok_b is None
+    if same:
+        if start_b is not None or begin_b is not None or width_b is not None:
+            raise ValueError("caption_overlap: start_b / begin_b / width_b without tok_b")
+        tok_b, start_b, begin_b, width_b = tok_a, start_a, begin_a, width_a
+    _need_cuda(tok_a, tok_b)
+    host, shape = [], []
+    for name, tok, start, begin, width in (("a", tok_a, start_a, begin_a, width_a), ("b", tok_b, start_b, begin_b, width_b)):
+        if tok.dtype != torch.int64 or tok.ndim != 2 or (tok.shape[0] > 1 and tok.shape[1] > 1 and tok.stride(1) != 1):
+            raise _lib.MpvError(f"caption_overlap: tok_{name} must be int64 [rows, width] with unit column stride (got {tok.dtype} {tuple(tok.shape)})")
+        width = tok.shape[1] if width is None else int(width)
+        if width > tok.shape[1]:
+            raise ValueError(f"caption_overlap: width_{name} = {width} for a table of {tok.shape[1]} columns")
+        start = torch.as_tensor(start, dtype=torch.int32, device="cpu").reshape(-1)
+        begin = torch.as_tensor(begin, dtype=torch.int32, device="cpu").reshape(-1)
+        if start.numel() != tok.shape[0]:
+            raise ValueError(f"caption_overlap: {start.numel()} start_{name} for {tok.shape[0]} rows")
+        if start.numel() and width - int(start.min()) > _lib.CAPTION_OVERLAP_MAX_LEN:
+            raise ValueError(f"caption_overlap: a row of table {name} can hold a candidate of {width - int(start.min())} tokens "
+                             f"(width {width}, start {int(start.min())}); at most {_lib.CAPTION_OVERLAP_MAX_LEN}")
+        host += [start, begin]
+        shape.append((tok.shape[0], width, tok.stride(0) if tok.shape[0] > 1 else max(width, 1)))
+    groups = host[1].numel() - 1
+    if groups != host[3].numel() - 1 or groups < 0:
+        raise ValueError(f"caption_overlap: begin_a / begin_b describe {groups} and {host[3].numel() - 1} groups")
+    dev = tok_a.device
+    na, nb = host[1].to(torch.int64).diff(), host[3].to(torch.int64).diff()
+    pair_begin = torch.cat([torch.zeros(1, dtype=torch.int64), (na * nb).cumsum(0)])
+    pairs = max(int(pair_begin[-1]), 0)
+    len_a = torch.empty(shape[0][0], dtype=torch.int32, device=dev)
+    len_b = len_a if same else torch.empty(shape[1][0], dtype=torch.int32, device=dev)
+    counts = torch.empty((pairs, 5), dtype=torch.int32, device=dev)
+    if groups == 0:
+        return len_a, len_b, counts
+    # ONE upload: the pair offsets (int64) first, then the four int32 arrays
+    packed = torch.cat([pair_begin.view(torch.uint8)] + [h.contiguous().view(torch.uint8) for h in host])
+    up = packed.to(dev)
+    at, dptr, hptr = 0, [], []
+    for h in [pair_begin] + host:
+        dptr.append(up.data_ptr() + at)
+        hptr.append(packed.data_ptr() + at)
+        at += h.numel() * h.element_size()
+    some = torch.zeros(2, dtype=torch.int64, device=dev)               # what a side without rows, or a call without pairs, points at
+    ptr = lambda t: t.data_ptr() if t.numel() else some.data_ptr()
+    d = _lib.CaptionOverlapDesc()
+    d.tok_a, d.tok_b, d.len_a, d.len_b, d.counts = ptr(tok_a), ptr(tok_b), ptr(len_a), ptr(len_b), ptr(counts)
+    d.pair_begin, d.start_a, d.begin_a, d.start_b, d.begin_b = dptr
+    d.host_pair_begin, d.host_start_a, d.host_begin_a, d.host_start_b, d.host_begin_b = hptr
+    (d.rows_a, d.width_a, d.ld_a), (d.rows_b, d.width_b, d.ld_b) = shape
+    d.term, d.groups = int(term), groups
+    if same:                                                            # one table: the library computes its lengths once
+        d.start_b, d.begin_b = d.start_a, d.begin_a
+    check(_lib.lib().mpv_caption_overlap(C.byref(d), _stream()), "mpv_caption_overlap")
+    return len_a, len_b, counts
+
+
 def sample_tokens(logits, *, temperature=1.0, top_k=0, top_p=0.0, seed=0, streams=None, vocab_size=None, vocab=None):
     """One-off draw: -> int64 [rows], the token sample_advance draws at pos 0 for every row of logits bf16 [rows, ld] (no prompt, no
     termination; vary `seed` or `streams` for another draw)."""
