@@ -198,7 +198,10 @@ typedef struct mpv_attn_desc {
   float scale;      /* softmax(scale * q.k)                            */
   int scale_q_bf16; /* 1: q' = bf16(q*scale) first (ViT numerics); 2: q IS that q' already (written by the qkv product's
                        colscale epilogue): scores use it as it is, dQ is still the gradient of the UNSCALED q (x scale)  */
-  float dropout_p;  /* on the probabilities                            */
+  float dropout_p;  /* on the probabilities.  The mask is attention's own convention: probability (b, h, row, key) has the element index
+                       offset + ((b * heads + h) * sq + row) * sk + key; its pair's counter (mpv_common.h, mpv_rand_pair) is the ROW's base
+                       index plus (key & ~1) -- pairs run along the key axis whatever the parity of the base --, key & 1 picks the low / high
+                       16 bits of the pair's word, and the element is kept iff that field >= the 16-bit threshold of dropout_p there */
   uint64_t seed, offset;
 } mpv_attn_desc;
 int mpv_attn_fwd(const mpv_attn_desc* d, mpv_stream_t stream);
@@ -310,7 +313,9 @@ int mpv_attn_decode_shared_steps_fwd(const mpv_attn_decode_shared_desc* d, const
 /* Divided space-time "temporal" attention: T<=16 tokens per (b,n) sequence, many tiny
  * problems (models/vision_transformer.py:247-248 with Attention :169-207).  qkv is the packed
  * [rows][3*D] projection in stream layout; sequence (o,i) (o<n_outer, i<n_inner) has its token
- * t at row o*outer_stride + inner_offset + i + t*t_stride.  out/dout are [rows][D]. */
+ * t at row o*outer_stride + inner_offset + i + t*t_stride.  out/dout are [rows][D].
+ * Numerics: every instance (fp32 rows, bf16 rows, the matrix-core ones below) scores with q' = bf16(q * scale), as the model it
+ * replaces does (:179); dq is the gradient of the unscaled q (x scale). */
 int mpv_temporal_attn_fwd(const void* qkv, void* out, int n_outer, int64_t outer_stride, int n_inner,
                           int64_t inner_offset, int64_t t_stride, int T, int heads, int head_dim, float scale,
                           mpv_stream_t stream);

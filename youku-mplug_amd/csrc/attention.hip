@@ -253,7 +253,7 @@ __global__ __launch_bounds__(512) void attn_fwd_kernel(const AttnArgs p) {
     sc = 1.0f;
   }
   // keys needed by this workgroup / by this wave (wave-uniform: tiles beyond it are skipped)
-  const int blk_last_q = min(p.sq - 1, blockIdx.x * rows_per_blk + rows_per_blk - 1);
+  const int blk_last_q = min(p.sq - 1, (int)blockIdx.x * rows_per_blk + rows_per_blk - 1);
   const int kmax = last_visible_key(p, blk_last_q);
   const int nchunk = kmax / CH + 1;
   const int my_last = last_visible_key(p, qrow);
@@ -432,7 +432,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(const AttnArgs p) {
   const float lse = qok ? p.lse[(long long)bh * p.sq + qrow] : INFINITY;
   const float dl = row_delta<HD>(dof, p.o + b * p.o_bs + h * p.o_hs, p.o_rs, qrow, p.sq, lane, p.hd);
   if (qok && lane < 32) p.delta[(long long)bh * p.sq + qrow] = dl;
-  const int blk_last_q = min(p.sq - 1, blockIdx.x * rows_per_blk + rows_per_blk - 1);
+  const int blk_last_q = min(p.sq - 1, (int)blockIdx.x * rows_per_blk + rows_per_blk - 1);
   const int nchunk = last_visible_key(p, blk_last_q) / CH + 1;
   const int my_last = last_visible_key(p, qrow);
   const int wave_last = q0 < p.sq ? last_visible_key(p, min(p.sq - 1, q0 + 31)) : -1;
@@ -538,7 +538,9 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnArgs p) {
   const bool kok = krow < p.sk;
 
   // query rows that can see any key of this workgroup: q >= first_key - (sk - sq) when causal
-  const int first_q = p.causal ? max(0, blockIdx.x * rows_per_blk - (p.sk - p.sq)) : 0;
+  // (in int: with the unsigned blockIdx.x the difference wraps where sk > sq and max() picks its double overload -- first_q then
+  // saturated to INT_MAX and a workgroup whose first key is below sk - sq walked no chunk at all: dK = dV = 0)
+  const int first_q = p.causal ? max(0, (int)blockIdx.x * rows_per_blk - (p.sk - p.sq)) : 0;
   // first query row that can see any key of THIS wave (wave-uniform); whole q-tiles before it are skipped
   const int wave_first_q = k0 >= p.sk ? p.sq : (p.causal ? max(0, k0 - (p.sk - p.sq)) : 0);
   const int c_begin = first_q / CH;
