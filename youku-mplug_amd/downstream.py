@@ -13,14 +13,16 @@ B + len(negative_indices) rows.  forward(..., train=False) returns the scores th
 """
 from __future__ import annotations
 
+import contextlib
 import dataclasses
 import math
+from types import SimpleNamespace
 from typing import Optional, Sequence
 
 import torch
 from torch import nn
 
-from . import ops
+from . import generation, ops
 from .ops import ACT_RELU
 from .pretrain import DistributedGPT3_Pretrain
 from .gpt3 import GPT3Config
@@ -450,280 +452,204 @@ class DistributedGPT3_Caption(_GenCls):
         are reordered by U descending, ties in search order (one ops.caption_overlap call over all the clips' rows: the clips may
         return different numbers of rows); info[i] holds consensus [n] fp64 and group [n] int64 in the new order.  Refused together
         with rerank_by_logprob and with allowed_phrases."""
+        o = self._generate_options(SimpleNamespace(**locals()))       # every refusal comes first: a refused call runs no ViT pass
         Q, Hh = self.num_learnable_token, self.text_width
-        G = int(beam_groups)
-        from . import generation as _gen
-        _gen._check_weight_mode(decode_weights)
-        for name, metric in (("consensus", consensus), ("rerank_by_consensus", rerank_by_consensus)):
-            if metric is not None and metric not in _gen.CONSENSUS_METRICS:
-                raise ValueError(f"{name} must be one of {_gen.CONSENSUS_METRICS} or None (got {metric!r})")
-        if consensus is not None:
-            if not do_sample:
-                raise ValueError("consensus needs do_sample=True (beam hypotheses: batched=True with rerank_by_consensus=)")
-            if best_of:
-                raise ValueError(f"consensus={consensus!r} does not combine with best_of=True: both choose the clip's one caption")
-        if rerank_by_consensus is not None:
-            if do_sample or not batched:
-                raise ValueError("rerank_by_consensus needs batched=True without do_sample (sampled captions: consensus=)")
-            if rerank_by_logprob:
-                raise ValueError(f"rerank_by_consensus={rerank_by_consensus!r} does not combine with rerank_by_logprob=True: both order the "
-                                 "clip's hypotheses")
-            if allowed_phrases is not None:
-                raise ValueError("rerank_by_consensus does not combine with allowed_phrases: the phrases of a closed vocabulary are "
-                                 "alternatives, not paraphrases")
-        if decode_weights != "bf16":
-            kw = dict(kw, decode_weights=decode_weights)                 # absent keyword: the calls below are today's
-        if G != 1 and (do_sample or not batched):
-            raise ValueError(f"beam_groups={beam_groups!r} needs batched=True without do_sample: the per-clip search and the samplers have no groups")
-        if rerank_by_logprob and (do_sample or not batched):
-            raise ValueError("rerank_by_logprob needs batched=True without do_sample (sampled captions: best_of=True)")
-        if G != 1:
-            kw = dict(kw, beam_groups=G, diversity_penalty=diversity_penalty)      # absent keyword: the calls below are today's
-        if mixed_prompts:
-            if do_sample:
-                raise ValueError("mixed_prompts does not combine with do_sample: a sampled token is a function of its table column, "
-                                 "which the left padding would make depend on the longest prompt of the chunk (sampled captions over "
-                                 "prompts of different lengths: sample_mixed_prompts=True)")
-            if not batched:
-                raise ValueError("mixed_prompts needs batched=True: the per-clip search has one prompt per call")
-            if kv_cache != "shared_prefix":
-                raise ValueError(f'mixed_prompts needs kv_cache="shared_prefix" (got {kv_cache!r}): only the shared-prefix decode step '
-                                 "takes a prefix length per clip")
-            if constrain_prompt:
-                raise ValueError("mixed_prompts does not combine with constrain_prompt=True: the left padding of the token table would "
-                                 "count as prompt")
-        if sample_mixed_prompts:
-            if not do_sample:
-                raise ValueError("sample_mixed_prompts needs do_sample=True (the beam search over prompts of different lengths: "
-                                 "mixed_prompts=True)")
-            if kv_cache != "shared_prefix":
-                raise ValueError(f'sample_mixed_prompts needs kv_cache="shared_prefix" (got {kv_cache!r}): only the shared-prefix decode '
-                                 "step takes a prefix length per clip")
-        if inflight:
-            if not do_sample:
-                raise ValueError("inflight needs do_sample=True (beam search in flight: batched=True with beam_inflight=True; greedy "
-                                 "captions: do_sample=True with top_k=1)")
-            if kv_cache != "shared_prefix":
-                raise ValueError(f'inflight needs kv_cache="shared_prefix" (got {kv_cache!r}): only the shared-prefix decode step takes a '
-                                 "suffix position per clip")
-        if beam_inflight:
-            if do_sample:
-                raise ValueError("beam_inflight does not combine with do_sample (sampled captions in flight: inflight=True)")
-            if not batched:
-                raise ValueError("beam_inflight needs batched=True: the per-clip search has one clip per call")
-            if kv_cache != "shared_prefix":
-                raise ValueError(f'beam_inflight needs kv_cache="shared_prefix" (got {kv_cache!r}): only the shared-prefix decode step takes '
-                                 "a suffix position per clip")
-            if mixed_prompts:
-                raise ValueError("beam_inflight does not combine with mixed_prompts=True: the in-flight search takes prompts of different "
-                                 "lengths as it is")
-        if not (inflight or beam_inflight) and (max_new_tokens is not None or refill_min is not None):
-            raise ValueError("max_new_tokens / refill_min belong to inflight=True (sampled captions) or beam_inflight=True (beam search)")
         Bv = image.shape[0] if query_features is None else query_features.shape[0] // Q
-        was = self.training
-        self.eval()
-        try:
+        with _eval_mode(self):
             qf = (self._query_features(image, {"vit": {}, "pool": {}}) if query_features is None else query_features).view(Bv, Q, Hh)
-            if termination_id is None:
-                tok = getattr(self, "tokenizer", None)
-                termination_id = tok.tokenizer.eos if tok is not None else None
-            n = text.input_ids.shape[0]
-            from . import generation
-            if (return_scores or best_of) and not do_sample:
-                raise ValueError(f"return_scores / best_of need do_sample=True (got return_scores={return_scores!r}, best_of={best_of!r}): "
-                                 "beam hypotheses carry their own scores")
-            if kv_cache not in generation.KV_MODES:
-                raise ValueError(f"kv_cache must be one of {generation.KV_MODES} (got {kv_cache!r})")
-            if kv_cache != "per_sequence":
-                if not (do_sample or batched):
-                    raise ValueError('kv_cache="shared_prefix" needs batched=True or do_sample=True (the per-clip search keeps a cache per beam)')
-                kw = dict(kw, kv=kv_cache)                               # absent keyword: the calls below are today's
-            if repetition_penalty is not None or no_repeat_ngram_size or min_new_tokens or banned_token_ids or constrain_prompt:
-                if not (do_sample or batched):
-                    raise ValueError("repetition_penalty / no_repeat_ngram_size / min_new_tokens / banned_token_ids / constrain_prompt need "
-                                     f"batched=True or do_sample=True (got repetition_penalty={repetition_penalty!r}, no_repeat_ngram_size="
-                                     f"{no_repeat_ngram_size!r}, min_new_tokens={min_new_tokens!r}, banned_token_ids={banned_token_ids!r}, "
-                                     f"constrain_prompt={constrain_prompt!r}): the per-clip search has no constraints")
-                kw = dict(kw, constraints=generation.LogitsConstraints(
-                    repetition_penalty=1.0 if repetition_penalty is None else repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
-                    min_new_tokens=min_new_tokens, banned_token_ids=tuple(banned_token_ids or ()), include_prompt=constrain_prompt))
-            trie = None
-            if allowed_phrases is not None:
-                if not (do_sample or batched):
-                    raise ValueError("allowed_phrases need batched=True or do_sample=True: the per-clip search has no constraints")
-                if rerank_by_logprob:
-                    raise ValueError("allowed_phrases do not combine with rerank_by_logprob: score the phrases with score_captions")
-                tok = getattr(self, "tokenizer", None)
-                trie = generation.as_phrase_trie(allowed_phrases, generation._gen_config(self.text_decoder).vocab_size,
-                                                 None if tok is None else (lambda s: _encode_phrase(tok, s)))
-                kw = dict(kw, constraints=dataclasses.replace(kw.get("constraints") or generation.LogitsConstraints(), allowed_phrases=trie))
             if do_sample:
-                N = int(num_samples)
-                if int(clips_per_search) < 1 or N < 1:
-                    raise ValueError(f"clips_per_search and num_samples must be at least 1 (got {clips_per_search}, {num_samples})")
-                lengths = (text.attention_mask.sum(-1) - 1).tolist()
-                gc = generation._gen_config(self.text_decoder)
-                term = gc.eod_id if termination_id is None else int(termination_id)
-                width = min(text.input_ids.shape[1] + gc.tokens_to_generate, gc.max_position_embeddings)
-                res = [None] * n
-                scored = bool(return_scores or best_of)
-                scores = [None] * n
-                if scored:
-                    kw = dict(kw, return_scores=True)                    # absent keyword: the calls below are today's
-                if consensus is not None and lengths and width - int(min(lengths)) > ops._lib.CAPTION_OVERLAP_MAX_LEN:
-                    raise ValueError(f"consensus: a row of {width} columns behind a prompt of {int(min(lengths))} tokens can hold a candidate "
-                                     f"of more than {ops._lib.CAPTION_OVERLAP_MAX_LEN} tokens")
-
-                def choose(toks, sc, starts, clips):
-                    """consensus: the chunk's padded device table (N rows per clip of `clips`, generated part from starts[row] on)
-                    -> res / scores of its clips, from ONE download that carries the overlap counts beside the tokens and scores"""
-                    toks, tlp, slp, cnt, picks = _consensus_samples(toks, sc, starts, N, term, width, consensus)
-                    for j, i in enumerate(clips):
-                        rows, (U, b) = slice(j * N, (j + 1) * N), picks[j]
-                        res[i] = toks[rows][b:b + 1]
-                        if scored:
-                            entry = dict(sum_logprob=slp[rows][b:b + 1], count=cnt[rows][b:b + 1], token_logprob=tlp[rows][b:b + 1], index=b,
-                                         consensus=U)
-                            scores[i] = _with_phrase_index(entry, trie, res[i], lengths[i], term)
-                if inflight:                                             # ONE loop over all clips, clips_per_search slots resident
-                    more = {k: v for k, v in kw.items() if k != "kv"}
-                    out = self.text_decoder.sample_inflight(text.input_ids, query_embeds=qf.contiguous(), temperature=temperature, num_samples=N,
-                                                            slots=int(clips_per_search), seed=seed, top_k=top_k, top_p=top_p,
-                                                            termination_id=termination_id, prompt_length=[int(x) for x in lengths],
-                                                            max_new_tokens=max_new_tokens, refill_min=refill_min, **more)
-                    rows_pl = [int(x) for x in lengths for _ in range(N)]
-                    col = torch.arange(out.tokens.shape[1], device=out.tokens.device)[None]
-                    end = torch.as_tensor([w for w in out.written for _ in range(N)], dtype=torch.long).to(out.tokens.device)[:, None]
-                    toks = torch.where(col < end, out.tokens, torch.full_like(out.tokens, term))      # behind a clip's budget: padding
-                    toks = generation.pad_after_termination(toks, rows_pl, term, width, term)
-                    if consensus is not None:
-                        choose(toks, out.scores if scored else None, rows_pl, range(n))
-                        return (res, scores) if return_scores else res
-                    if not scored:
-                        toks = toks.cpu()
-                        return [toks[i * N:(i + 1) * N] for i in range(n)]
-                    toks, tlp, slp, cnt = _download_scored(toks, out.scores, width)
-                    for i in range(n):
-                        rows = slice(i * N, (i + 1) * N)
-                        entry = dict(sum_logprob=slp[rows], count=cnt[rows], token_logprob=tlp[rows])
-                        if best_of:
-                            b = best_sample(entry["sum_logprob"], entry["count"], length_penalty)
-                            entry = dict({k: v[b:b + 1] for k, v in entry.items()}, index=b)
-                            res[i] = toks[rows][b:b + 1]
-                        else:
-                            res[i] = toks[rows]
-                        scores[i] = _with_phrase_index(entry, trie, res[i], lengths[i], term)
-                    return (res, scores) if return_scores else res
-                if sample_mixed_prompts:                                 # input order, no grouping: one loop per chunk with its lengths
-                    per = int(clips_per_search)
-                    chunks = [list(range(c, min(c + per, n))) for c in range(0, n, per)]
-                    chunks = [([int(lengths[i]) for i in chunk], chunk) for chunk in chunks]
-                    kw = dict(kw, mixed_prompts=True)
-                else:
-                    chunks = [(int(pl), chunk) for pl, chunk in _prompt_length_chunks(lengths, clips_per_search)]
-                for pl, chunk in chunks:
-                    sel = torch.as_tensor(chunk, dtype=torch.long, device=qf.device)
-                    streams = (sel[:, None] * N + torch.arange(N, device=qf.device)[None]).reshape(-1)
-                    out = self.text_decoder.sample_batched(text.input_ids[sel], query_embeds=qf[sel].contiguous(), temperature=temperature,
-                                                           num_samples=N, seed=seed, streams=streams, top_k=top_k, top_p=top_p,
-                                                           termination_id=termination_id,
-                                                           prompt_length=(pl if sample_mixed_prompts
-                                                                          else torch.full((len(sel),), pl, device=qf.device)), **kw)
-                    if sample_mixed_prompts:                             # pad_after_termination: one prompt length per row
-                        pl = [x for x in pl for _ in range(N)]
-                    if consensus is not None:
-                        toks, sc = out if scored else (out, None)
-                        choose(generation.pad_after_termination(toks, pl, term, width, term), sc,
-                               pl if sample_mixed_prompts else [pl] * (len(chunk) * N), sel.tolist())
-                        continue
-                    if not scored:
-                        out = generation.pad_after_termination(out, pl, term, width, term).cpu()
-                        for j, i in enumerate(sel.tolist()):
-                            res[i] = out[j * N:(j + 1) * N]
-                        continue
-                    out, sc = out
-                    out, tlp, slp, cnt = _download_scored(generation.pad_after_termination(out, pl, term, width, term), sc, width)
-                    for j, i in enumerate(sel.tolist()):
-                        rows = slice(j * N, (j + 1) * N)
-                        entry = dict(sum_logprob=slp[rows], count=cnt[rows], token_logprob=tlp[rows])
-                        if best_of:
-                            b = best_sample(entry["sum_logprob"], entry["count"], length_penalty)
-                            entry = dict({k: v[b:b + 1] for k, v in entry.items()}, index=b)
-                            res[i] = out[rows][b:b + 1]
-                        else:
-                            res[i] = out[rows]
-                        scores[i] = _with_phrase_index(entry, trie, res[i], lengths[i], term)
-                return (res, scores) if return_scores else res
+                return self._generate_samples(o, qf)
             if batched:
-                if int(clips_per_search) < 1:
-                    raise ValueError(f"clips_per_search must be at least 1 (got {clips_per_search})")
-                lengths = (text.attention_mask.sum(-1) - 1).tolist()
-                res = [None] * n
-                groups_of = [None] * n
-                info = [None] * n
-                if beam_inflight:                                        # ONE loop over all clips, clips_per_search slots resident
-                    more = {k: v for k, v in kw.items() if k != "kv"}
-                    outs = self.text_decoder.beam_search_inflight(text.input_ids, query_embeds=qf.contiguous(), stop_token=termination_id,
-                                                                  prompt_length=[int(x) for x in lengths], slots=int(clips_per_search),
-                                                                  max_new_tokens=max_new_tokens, refill_min=refill_min, **more).results
-                    for i, out in enumerate(outs):
-                        res[i] = out.sequences.cpu()
-                        groups_of[i] = getattr(out, "group", None)
-                        info[i] = dict(phrase_index=getattr(out, "phrase_index", None), scores=out.scores)
-                    chunks = []
-                elif mixed_prompts:                                      # input order, no grouping: one search per chunk with its lengths
-                    per = int(clips_per_search)
-                    chunks = [list(range(c, min(c + per, n))) for c in range(0, n, per)]
-                    chunks = [([int(lengths[i]) for i in chunk], chunk) for chunk in chunks]
-                else:
-                    chunks = [(int(pl), chunk) for pl, chunk in _prompt_length_chunks(lengths, clips_per_search)]
-                for pl, chunk in chunks:
-                    sel = torch.as_tensor(chunk, dtype=torch.long, device=qf.device)
-                    outs = self.text_decoder.beam_search_batched(text.input_ids[sel], query_embeds=qf[sel].contiguous(),
-                                                                 stop_token=termination_id, prompt_length=pl, **kw)
-                    for i, out in zip(sel.tolist(), outs):
-                        res[i] = out.sequences.cpu()
-                        groups_of[i] = getattr(out, "group", None)
-                        info[i] = dict(phrase_index=getattr(out, "phrase_index", None), scores=out.scores)
-                if trie is not None:
-                    return res, info
-                if rerank_by_consensus is not None:
-                    term = generation._gen_config(self.text_decoder).eod_id if termination_id is None else int(termination_id)
-                    picks = _consensus_rows(res, lengths, term, rerank_by_consensus, qf.device)
-                    for i in range(n):
-                        U = picks[i][0]
-                        order = generation.consensus_order(U)                                # ties keep the search order
-                        grp = groups_of[i] if groups_of[i] is not None else torch.zeros(U.numel(), dtype=torch.int64)
-                        res[i] = res[i][order]
-                        info[i] = dict(consensus=U[order], group=grp[order])
-                    return res, info
-                if not rerank_by_logprob:
-                    return res
-                term = generation._gen_config(self.text_decoder).eod_id if termination_id is None else int(termination_id)
-                cands = []
-                for i in range(n):
-                    rows = res[i][:, lengths[i]:].tolist()
-                    cands.append([row[:row.index(term)] if term in row else row for row in rows])
-                scores = self.score_captions(None, text, cands, query_features=qf.reshape(Bv * Q, Hh), termination_id=term,
-                                             clips_per_pass=clips_per_search, length_penalty=length_penalty)
-                for i in range(n):
-                    sc = scores[i]
-                    norm = [float(lp) / float(c) ** float(length_penalty) if c > 0 else -math.inf
-                            for lp, c in zip(sc["sum_logprob"].tolist(), sc["count"].tolist())]
-                    order = sorted(range(len(norm)), key=lambda s: -norm[s])             # stable: ties keep the search order
-                    grp = groups_of[i] if groups_of[i] is not None else torch.zeros(len(norm), dtype=torch.int64)
-                    res[i] = res[i][order]
-                    scores[i] = dict(sum_logprob=sc["sum_logprob"][order], count=sc["count"][order], token_logprob=sc["token_logprob"][order],
-                                     group=grp[order], best=0)
-                return res, scores
+                return self._generate_beams(o, qf)
             res = []
-            for i in range(n):
-                out = self.text_decoder.generate(text.input_ids[i:i + 1], query_embeds=qf[i:i + 1], termination_id=termination_id,
-                                                 do_sample=False, prompt_length=int(text.attention_mask.sum(-1)[i]) - 1, **kw)
+            for i in range(o.n):
+                out = self.text_decoder.generate(text.input_ids[i:i + 1], query_embeds=qf[i:i + 1], termination_id=o.termination_id,
+                                                 do_sample=False, prompt_length=o.lengths[i], **o.kw)
                 res.append(out.sequences.cpu())
             return res
-        finally:
-            self.train(was)
+
+    def _termination(self, termination_id):
+        """the termination_id of generate / score_captions -> (the id forwarded to the decoder: the caller's, else the tokenizer's eos,
+        else None; term: that id as an int, the decoder's eod_id where it is None -- what the decoder's loops make of it)"""
+        if termination_id is None:
+            tok = getattr(self, "tokenizer", None)
+            termination_id = tok.tokenizer.eos if tok is not None else None
+        return termination_id, generation._gen_config(self.text_decoder).eod_id if termination_id is None else int(termination_id)
+
+    def _generate_options(self, o):
+        """generate's arguments as a namespace -> the same namespace, checked and completed, before anything runs.  The refusals keep
+        one order: the keyword combinations (_refuse_keyword_combinations), then what the per-clip search cannot do, then the sizes of
+        the mode.  kw becomes what is forwarded to the decoder: a keyword is there only when its feature is on (absent keyword: the
+        call is the one made before the feature existed), and the in-flight calls take no kv.  Added for the routines below:
+        termination_id / term (_termination), trie, n, lengths (the prompts' token counts) and, for the samplers, N, scored and width"""
+        _refuse_keyword_combinations(o)
+        kw = dict(o.kw)
+        if o.decode_weights != "bf16":
+            kw["decode_weights"] = o.decode_weights
+        if int(o.beam_groups) != 1:
+            kw.update(beam_groups=int(o.beam_groups), diversity_penalty=o.diversity_penalty)
+        lockstep = o.do_sample or o.batched
+        if (o.return_scores or o.best_of) and not o.do_sample:
+            raise ValueError(f"return_scores / best_of need do_sample=True (got return_scores={o.return_scores!r}, best_of={o.best_of!r}): "
+                             "beam hypotheses carry their own scores")
+        if o.kv_cache not in generation.KV_MODES:
+            raise ValueError(f"kv_cache must be one of {generation.KV_MODES} (got {o.kv_cache!r})")
+        if o.kv_cache != "per_sequence":
+            if not lockstep:
+                raise ValueError('kv_cache="shared_prefix" needs batched=True or do_sample=True (the per-clip search keeps a cache per beam)')
+            kw["kv"] = o.kv_cache
+        if o.repetition_penalty is not None or o.no_repeat_ngram_size or o.min_new_tokens or o.banned_token_ids or o.constrain_prompt:
+            if not lockstep:
+                raise ValueError("repetition_penalty / no_repeat_ngram_size / min_new_tokens / banned_token_ids / constrain_prompt need "
+                                 f"batched=True or do_sample=True (got repetition_penalty={o.repetition_penalty!r}, no_repeat_ngram_size="
+                                 f"{o.no_repeat_ngram_size!r}, min_new_tokens={o.min_new_tokens!r}, banned_token_ids={o.banned_token_ids!r}, "
+                                 f"constrain_prompt={o.constrain_prompt!r}): the per-clip search has no constraints")
+            kw["constraints"] = generation.LogitsConstraints(
+                repetition_penalty=1.0 if o.repetition_penalty is None else o.repetition_penalty, no_repeat_ngram_size=o.no_repeat_ngram_size,
+                min_new_tokens=o.min_new_tokens, banned_token_ids=tuple(o.banned_token_ids or ()), include_prompt=o.constrain_prompt)
+        o.trie = None
+        if o.allowed_phrases is not None:
+            if not lockstep:
+                raise ValueError("allowed_phrases need batched=True or do_sample=True: the per-clip search has no constraints")
+            if o.rerank_by_logprob:
+                raise ValueError("allowed_phrases do not combine with rerank_by_logprob: score the phrases with score_captions")
+            tok = getattr(self, "tokenizer", None)
+            o.trie = generation.as_phrase_trie(o.allowed_phrases, generation._gen_config(self.text_decoder).vocab_size,
+                                               None if tok is None else (lambda s: _encode_phrase(tok, s)))
+            kw["constraints"] = dataclasses.replace(kw.get("constraints") or generation.LogitsConstraints(), allowed_phrases=o.trie)
+        o.termination_id, o.term = self._termination(o.termination_id)
+        o.n = o.text.input_ids.shape[0]
+        o.lengths = (o.text.attention_mask.sum(-1) - 1).tolist()
+        if o.do_sample:
+            o.N = int(o.num_samples)
+            if int(o.clips_per_search) < 1 or o.N < 1:
+                raise ValueError(f"clips_per_search and num_samples must be at least 1 (got {o.clips_per_search}, {o.num_samples})")
+            gc = generation._gen_config(self.text_decoder)
+            o.width = min(o.text.input_ids.shape[1] + gc.tokens_to_generate, gc.max_position_embeddings)
+            o.scored = bool(o.return_scores or o.best_of)
+            if o.scored:
+                kw["return_scores"] = True
+            if o.consensus is not None and o.lengths and o.width - int(min(o.lengths)) > ops._lib.CAPTION_OVERLAP_MAX_LEN:
+                raise ValueError(f"consensus: a row of {o.width} columns behind a prompt of {int(min(o.lengths))} tokens can hold a candidate "
+                                 f"of more than {ops._lib.CAPTION_OVERLAP_MAX_LEN} tokens")
+            if o.sample_mixed_prompts and not o.inflight:
+                kw["mixed_prompts"] = True
+        elif o.batched and int(o.clips_per_search) < 1:
+            raise ValueError(f"clips_per_search must be at least 1 (got {o.clips_per_search})")
+        if o.inflight or o.beam_inflight:
+            kw.pop("kv", None)
+        o.kw = kw
+        return o
+
+    # ------------------------------------------------------------------ the sampled family: three modes, one finish
+    def _generate_samples(self, o, qf):
+        """do_sample=True.  Each mode hands over (the padded device table [rows, width] with N rows per clip, its SampleScores or None,
+        the column at which every row's generated part starts, the clips it covers): the in-flight loop once for the whole call, the
+        lockstep loops once per chunk."""
+        res, scores = [None] * o.n, [None] * o.n
+        for toks, sc, starts, clips in (self._sampled_inflight(o, qf) if o.inflight else self._sampled_chunks(o, qf)):
+            self._finish_samples(o, toks, sc, starts, clips, res, scores)
+        return (res, scores) if o.return_scores else res
+
+    def _sampled_inflight(self, o, qf):
+        """inflight=True: ONE loop over all clips, clips_per_search slots resident"""
+        out = self.text_decoder.sample_inflight(o.text.input_ids, query_embeds=qf.contiguous(), temperature=o.temperature, num_samples=o.N,
+                                                slots=int(o.clips_per_search), seed=o.seed, top_k=o.top_k, top_p=o.top_p,
+                                                termination_id=o.termination_id, prompt_length=[int(x) for x in o.lengths],
+                                                max_new_tokens=o.max_new_tokens, refill_min=o.refill_min, **o.kw)
+        starts = [int(x) for x in o.lengths for _ in range(o.N)]
+        col = torch.arange(out.tokens.shape[1], device=out.tokens.device)[None]
+        end = torch.as_tensor([w for w in out.written for _ in range(o.N)], dtype=torch.long).to(out.tokens.device)[:, None]
+        toks = torch.where(col < end, out.tokens, torch.full_like(out.tokens, o.term))              # behind a clip's budget: padding
+        yield generation.pad_after_termination(toks, starts, o.term, o.width, o.term), out.scores if o.scored else None, starts, range(o.n)
+
+    def _sampled_chunks(self, o, qf):
+        """the lockstep loops: one per chunk of clips with one prompt length, or (sample_mixed_prompts) per chunk in input order with
+        its clips' lengths; sample s of clip i draws from stream i * N + s whatever the chunk"""
+        mixed, N = o.sample_mixed_prompts, o.N
+        for pl, chunk in _clip_chunks(o.lengths, o.clips_per_search, by_length=not mixed):
+            sel = torch.as_tensor(chunk, dtype=torch.long, device=qf.device)
+            streams = (sel[:, None] * N + torch.arange(N, device=qf.device)[None]).reshape(-1)
+            out = self.text_decoder.sample_batched(o.text.input_ids[sel], query_embeds=qf[sel].contiguous(), temperature=o.temperature,
+                                                   num_samples=N, seed=o.seed, streams=streams, top_k=o.top_k, top_p=o.top_p,
+                                                   termination_id=o.termination_id,
+                                                   prompt_length=pl if mixed else torch.full((len(sel),), pl, device=qf.device), **o.kw)
+            toks, sc = out if o.scored else (out, None)
+            starts = [x for x in pl for _ in range(N)] if mixed else [pl] * (len(chunk) * N)
+            yield generation.pad_after_termination(toks, starts if mixed else pl, o.term, o.width, o.term), sc, starts, chunk
+
+    def _finish_samples(self, o, toks, sc, starts, clips, res, scores):
+        """a mode's padded device table -> res / scores of its clips, from ONE download (_download_rows) that carries the scores and,
+        with consensus, the overlap counts beside the tokens; then the clip's one caption (consensus, best_of) and phrase_index"""
+        N, picks = o.N, None
+        if o.consensus is not None:
+            toks, tlp, slp, cnt, picks = _consensus_samples(toks, sc, starts, N, o.term, o.width, o.consensus)
+        elif sc is not None:
+            toks, tlp, slp, cnt = _download_scored(toks, sc, o.width)
+        else:
+            toks = toks.cpu()
+        for j, i in enumerate(clips):
+            rows = slice(j * N, (j + 1) * N)
+            res[i] = toks[rows]
+            entry = None if sc is None else dict(sum_logprob=slp[rows], count=cnt[rows], token_logprob=tlp[rows])
+            chosen = None
+            if picks is not None:
+                chosen = dict(index=picks[j][1], consensus=picks[j][0])
+            elif o.best_of:
+                chosen = dict(index=best_sample(entry["sum_logprob"], entry["count"], o.length_penalty))
+            if chosen is not None:
+                b = chosen["index"]
+                res[i] = res[i][b:b + 1]
+                if entry is not None:
+                    entry = dict({k: v[b:b + 1] for k, v in entry.items()}, **chosen)
+            if entry is not None:
+                scores[i] = _with_phrase_index(entry, o.trie, res[i], o.lengths[i], o.term)
+
+    # ------------------------------------------------------------------ the beam family: one collect, one reorder
+    def _generate_beams(self, o, qf):
+        """batched=True: the in-flight search over all clips or one lockstep search per chunk, then at most one re-rank"""
+        n, dec = o.n, self.text_decoder
+        res, groups_of, info = [None] * n, [None] * n, [None] * n
+
+        def collect(clips, outs):
+            for i, out in zip(clips, outs):
+                res[i] = out.sequences.cpu()
+                groups_of[i] = getattr(out, "group", None)
+                info[i] = dict(phrase_index=getattr(out, "phrase_index", None), scores=out.scores)
+        if o.beam_inflight:                                                  # ONE loop over all clips, clips_per_search slots resident
+            collect(range(n), dec.beam_search_inflight(o.text.input_ids, query_embeds=qf.contiguous(), stop_token=o.termination_id,
+                                                       prompt_length=[int(x) for x in o.lengths], slots=int(o.clips_per_search),
+                                                       max_new_tokens=o.max_new_tokens, refill_min=o.refill_min, **o.kw).results)
+        else:                               # grouped by prompt length, or (mixed_prompts) in input order with the chunk's lengths
+            for pl, chunk in _clip_chunks(o.lengths, o.clips_per_search, by_length=not o.mixed_prompts):
+                sel = torch.as_tensor(chunk, dtype=torch.long, device=qf.device)
+                collect(chunk, dec.beam_search_batched(o.text.input_ids[sel], query_embeds=qf[sel].contiguous(), stop_token=o.termination_id,
+                                                       prompt_length=pl, **o.kw))
+        if o.trie is not None:
+            return res, info
+        if o.rerank_by_consensus is not None:
+            picks = _consensus_rows(res, o.lengths, o.term, o.rerank_by_consensus, qf.device)
+            ranked, tail = [(generation.consensus_order(U), dict(consensus=U)) for U, _ in picks], {}   # ties keep the search order
+        elif o.rerank_by_logprob:
+            ranked, tail = self._rank_by_logprob(o, qf, res), dict(best=0)
+        else:
+            return res
+        for i, (order, columns) in enumerate(ranked):
+            grp = groups_of[i] if groups_of[i] is not None else torch.zeros(len(order), dtype=torch.int64)
+            res[i] = res[i][order]
+            info[i] = dict({k: v[order] for k, v in columns.items()}, group=grp[order], **tail)
+        return res, info
+
+    def _rank_by_logprob(self, o, qf, res):
+        """rerank_by_logprob: score every clip's hypotheses (the tokens between the prompt and the first termination token) with
+        score_captions on this call's query features -> (order, score columns) per clip, best first as best_sample ranks"""
+        cands = [[generation.generated_part(row, o.lengths[i], o.term) for row in res[i].tolist()] for i in range(o.n)]
+        scores = self.score_captions(None, o.text, cands, query_features=qf.reshape(-1, self.text_width), termination_id=o.term,
+                                     clips_per_pass=o.clips_per_search, length_penalty=o.length_penalty)
+        for sc in scores:
+            norm = [_normalised(lp, c, o.length_penalty) for lp, c in zip(sc["sum_logprob"].tolist(), sc["count"].tolist())]
+            order = sorted(range(len(norm)), key=lambda s: -norm[s])                         # stable: ties keep the search order
+            yield order, {k: sc[k] for k in ("sum_logprob", "count", "token_logprob")}
 
 
     @torch.no_grad()
@@ -761,20 +687,12 @@ class DistributedGPT3_Caption(_GenCls):
         cands = [[[int(t) for t in (c.tolist() if torch.is_tensor(c) else c)] for c in cl] for cl in candidates]
         if not score_termination and any(len(c) == 0 for cl in cands for c in cl):
             raise ValueError("an empty candidate has nothing to score with score_termination=False")
-        was = self.training
-        self.eval()
-        try:
+        with _eval_mode(self):
             qf = self._query_features(image, {"vit": {}, "pool": {}}) if query_features is None else query_features
             if qf.shape[0] != n * Q:
                 raise ValueError(f"query features of {qf.shape[0] / Q:g} clips ({qf.shape[0]} rows of Q = {Q}) for {n} prompts")
             qf = qf.view(n, Q, Hh)
-            if termination_id is None:
-                tok = getattr(self, "tokenizer", None)
-                termination_id = tok.tokenizer.eos if tok is not None else None
-            if termination_id is None:
-                from . import generation
-                termination_id = generation._gen_config(self.text_decoder).eod_id
-            term = int(termination_id)
+            _, term = self._termination(termination_id)
             host_ids = ids_all.tolist()                                          # the prompts' last tokens, on the host
             res = [None] * n
             for i in range(n):
@@ -821,8 +739,85 @@ class DistributedGPT3_Caption(_GenCls):
                     entry["best"] = best_sample(entry["sum_logprob"], entry["count"], length_penalty)
                     res[i] = entry
             return res
-        finally:
-            self.train(was)
+
+
+@contextlib.contextmanager
+def _eval_mode(model):
+    """the model in eval mode inside the block, back in the mode it was in behind it"""
+    was = model.training
+    model.eval()
+    try:
+        yield
+    finally:
+        model.train(was)
+
+
+def _refuse_keyword_combinations(o):
+    """generate's rules on which keywords go together, as functions of the keywords alone (o: a namespace of them), in one order: a
+    call that breaks several gets the first one's message"""
+    generation._check_weight_mode(o.decode_weights)
+    for name, metric in (("consensus", o.consensus), ("rerank_by_consensus", o.rerank_by_consensus)):
+        if metric is not None and metric not in generation.CONSENSUS_METRICS:
+            raise ValueError(f"{name} must be one of {generation.CONSENSUS_METRICS} or None (got {metric!r})")
+    beams = o.batched and not o.do_sample
+    if o.consensus is not None:
+        if not o.do_sample:
+            raise ValueError("consensus needs do_sample=True (beam hypotheses: batched=True with rerank_by_consensus=)")
+        if o.best_of:
+            raise ValueError(f"consensus={o.consensus!r} does not combine with best_of=True: both choose the clip's one caption")
+    if o.rerank_by_consensus is not None:
+        if not beams:
+            raise ValueError("rerank_by_consensus needs batched=True without do_sample (sampled captions: consensus=)")
+        if o.rerank_by_logprob:
+            raise ValueError(f"rerank_by_consensus={o.rerank_by_consensus!r} does not combine with rerank_by_logprob=True: both order the "
+                             "clip's hypotheses")
+        if o.allowed_phrases is not None:
+            raise ValueError("rerank_by_consensus does not combine with allowed_phrases: the phrases of a closed vocabulary are "
+                             "alternatives, not paraphrases")
+    if int(o.beam_groups) != 1 and not beams:
+        raise ValueError(f"beam_groups={o.beam_groups!r} needs batched=True without do_sample: the per-clip search and the samplers have no groups")
+    if o.rerank_by_logprob and not beams:
+        raise ValueError("rerank_by_logprob needs batched=True without do_sample (sampled captions: best_of=True)")
+    if o.mixed_prompts:
+        if o.do_sample:
+            raise ValueError("mixed_prompts does not combine with do_sample: a sampled token is a function of its table column, "
+                             "which the left padding would make depend on the longest prompt of the chunk (sampled captions over "
+                             "prompts of different lengths: sample_mixed_prompts=True)")
+        if not o.batched:
+            raise ValueError("mixed_prompts needs batched=True: the per-clip search has one prompt per call")
+        if o.kv_cache != "shared_prefix":
+            raise ValueError(f'mixed_prompts needs kv_cache="shared_prefix" (got {o.kv_cache!r}): only the shared-prefix decode step '
+                             "takes a prefix length per clip")
+        if o.constrain_prompt:
+            raise ValueError("mixed_prompts does not combine with constrain_prompt=True: the left padding of the token table would "
+                             "count as prompt")
+    if o.sample_mixed_prompts:
+        if not o.do_sample:
+            raise ValueError("sample_mixed_prompts needs do_sample=True (the beam search over prompts of different lengths: "
+                             "mixed_prompts=True)")
+        if o.kv_cache != "shared_prefix":
+            raise ValueError(f'sample_mixed_prompts needs kv_cache="shared_prefix" (got {o.kv_cache!r}): only the shared-prefix decode '
+                             "step takes a prefix length per clip")
+    if o.inflight:
+        if not o.do_sample:
+            raise ValueError("inflight needs do_sample=True (beam search in flight: batched=True with beam_inflight=True; greedy "
+                             "captions: do_sample=True with top_k=1)")
+        if o.kv_cache != "shared_prefix":
+            raise ValueError(f'inflight needs kv_cache="shared_prefix" (got {o.kv_cache!r}): only the shared-prefix decode step takes a '
+                             "suffix position per clip")
+    if o.beam_inflight:
+        if o.do_sample:
+            raise ValueError("beam_inflight does not combine with do_sample (sampled captions in flight: inflight=True)")
+        if not o.batched:
+            raise ValueError("beam_inflight needs batched=True: the per-clip search has one clip per call")
+        if o.kv_cache != "shared_prefix":
+            raise ValueError(f'beam_inflight needs kv_cache="shared_prefix" (got {o.kv_cache!r}): only the shared-prefix decode step takes '
+                             "a suffix position per clip")
+        if o.mixed_prompts:
+            raise ValueError("beam_inflight does not combine with mixed_prompts=True: the in-flight search takes prompts of different "
+                             "lengths as it is")
+    if not (o.inflight or o.beam_inflight) and (o.max_new_tokens is not None or o.refill_min is not None):
+        raise ValueError("max_new_tokens / refill_min belong to inflight=True (sampled captions) or beam_inflight=True (beam search)")
 
 
 def _encode_phrase(tok, s):
@@ -840,7 +835,6 @@ def _with_phrase_index(entry, trie, rows, prompt_len, term):
     """generate(allowed_phrases=, return_scores=True): the clip's score dict with phrase_index [rows] int64 (-1: no phrase)"""
     if trie is None:
         return entry
-    from . import generation
     return dict(entry, phrase_index=torch.tensor([trie.lookup(generation.generated_part(r, prompt_len, term)) for r in rows.tolist()],
                                                  dtype=torch.int64))
 
@@ -854,11 +848,28 @@ def _prompt_length_chunks(lengths, per_chunk):
             yield pl, group[c:c + int(per_chunk)]
 
 
+def _clip_chunks(lengths, per_chunk, by_length: bool):
+    """generate's lockstep chunks of at most per_chunk clips -> (prompt length, clip indices) per chunk, the clips grouped by prompt
+    length (_prompt_length_chunks); or, by_length=False, (the clips' prompt lengths, clip indices) in input order: the mixed modes"""
+    if by_length:
+        for pl, chunk in _prompt_length_chunks(lengths, per_chunk):
+            yield int(pl), chunk
+    else:
+        for c in range(0, len(lengths), int(per_chunk)):
+            chunk = list(range(c, min(c + int(per_chunk), len(lengths))))
+            yield [int(lengths[i]) for i in chunk], chunk
+
+
+def _normalised(sum_logprob, count, length_penalty) -> float:
+    """sum_logprob / count ** length_penalty in fp64; -inf for a sequence of no tokens"""
+    return float(sum_logprob) / float(count) ** float(length_penalty) if count > 0 else -math.inf
+
+
 def best_sample(sum_logprob, count, length_penalty: float = 1.0) -> int:
     """argmax_s sum_logprob[s] / count[s] ** length_penalty in fp64; a tie goes to the lowest index, a sample with count 0 scores -inf"""
     best, best_score = 0, -math.inf
     for s, (lp, c) in enumerate(zip(sum_logprob.tolist(), count.tolist())):
-        score = float(lp) / float(c) ** float(length_penalty) if c > 0 else -math.inf
+        score = _normalised(lp, c, length_penalty)
         if score > best_score:
             best, best_score = s, score
     return best
@@ -894,7 +905,6 @@ def _consensus_samples(toks, sc, starts, N: int, term: int, width: int, metric: 
     sc --, [(U [N] fp64, index) per clip]).  The overlap counts of every clip's N x N pairs are taken on the device
     (ops.caption_overlap) and come down in the chunk's ONE download, N * 5 integers beside every row; the utilities and the choice are
     fp64 on the host (generation.consensus_utility / consensus_choice)."""
-    from . import generation
     R = toks.shape[0]
     toks = toks.contiguous()
     ln, _, counts = ops.caption_overlap(toks, [int(s) for s in starts], list(range(0, R + 1, N)), term=term)
@@ -916,7 +926,6 @@ def _consensus_rows(res, starts, term: int, metric: str, device):
     """generate(rerank_by_consensus=): res[i] int64 [n_i, L_i] on the CPU (clip i's hypotheses, the generated part from column
     starts[i] on) -> [(U [n_i] fp64, index) per clip].  ONE table of all the clips' rows (padded with `term` to the widest), one
     upload, one ops.caption_overlap call over ragged groups with a start per row, one download."""
-    from . import generation
     counts_of = [int(r.shape[0]) for r in res]
     W = max([int(r.shape[1]) for r in res] + [1])
     table = torch.full((sum(counts_of), W), int(term), dtype=torch.int64)
