@@ -63,12 +63,25 @@ What this entry point adds to downstream/finetune_common.py:
     against the query features computed once for that clip (`model.score_captions(..., query_features=)`: one packed pass per batch,
     no padding rows), adds "gold_logprob" / "gold_tokens" lists to the result entries and logs the corpus per-token NLL and perplexity;
     it combines with every flag above, and without it the run is the one described above;
+  * `--scst` with `--scst_samples N`, `--scst_baseline mean_others|greedy`, `--scst_temperature F` and `--scst_stats FILE` (not in the
+    reference, all off by default: without `--scst` the loop is the one above): self-critical sequence training -- a step samples N
+    captions per clip from the model, rewards each with CIDEr over token ids against the clip's own caption(s) on the device and
+    weights its log-likelihood by reward minus baseline (`model.forward_scst`).  The corpus statistics are a
+    saved `generation.CiderStats` (FILE) or, by default, built at start-up from the training set's captions (with
+    `--synthetic_steps`, the synthetic ones); a step is one `forward_scst` call, and a batch whose prompts differ in length (the
+    tokenizer shortens the prompt of an over-long pair) is refused;
+  * corpus CIDEr in the evaluation's result dict ("CIDEr": the mean over clips of the scorer's 10 x mean-over-orders score): over the
+    same CJK-character units as BLEU / ROUGE-L, the units mapped to ids in order of first appearance, df from this evaluation's own
+    references as the reference project's scorer takes it, ONE `ops.caption_cider` call (`corpus_cider`).  Past 65 535 distinct
+    units, with a caption of more than 255 units, or on a CPU run it is left out and the log line says so;
   * save_result (dataset/utils.py:114-160): one JSON per rank, merged by rank 0; cal_metric (:240-298): predictions and references
     reduced to their CJK characters, one token per character, scored by pycocoevalcap's COCOEvalCap when that package is importable.
     It is not on this image: then BLEU-1..4 (corpus level, closest-reference brevity penalty) and ROUGE-L (beta 1.2, best reference)
-    are computed here as that package defines them, and METEOR / CIDEr are left out -- said in the log line, not guessed;
+    are computed here as that package defines them, CIDEr on the device (above), and METEOR is left out -- said in the log line,
+    not guessed;
   * main (:418-440, 446-470): `--evaluate_only` scores the validation split and writes one log line; training epochs do not
     evaluate (the reference has that block commented out)."""
+import argparse
 import json
 import math
 import os
@@ -290,7 +303,35 @@ def rouge_l(pairs, beta=1.2):
     return sum(scores) / max(len(scores), 1)
 
 
-def cal_metric(result_file):
+def corpus_cider(pairs, device):
+    """Corpus CIDEr of [(hypothesis units, [reference units, ...])] -- one hypothesis per clip, units any hashable tokens (CJK
+    characters here) -- as the reference project's scorer computes it: the units become ids in order of first appearance, the
+    document frequencies come from THESE references, one ops.caption_cider call scores every clip, -> the mean over clips.
+    ValueError: more than 65 535 distinct units, a caption of more than 255 units, a clip without references, no clip at all."""
+    from youku_mplug_amd import generation, ops
+    ids = {}
+    enc = lambda cap: [ids.setdefault(u, len(ids)) for u in cap]
+    hyps, refs = [enc(h) for h, _ in pairs], [[enc(r) for r in rs] for _, rs in pairs]
+    if not pairs or any(not rs for rs in refs):
+        raise ValueError("corpus CIDEr needs at least one clip, and references for every clip")
+    if len(ids) > generation.CiderStats.MAX_VOCAB:
+        raise ValueError(f"{len(ids)} distinct units do not fit the 16-bit key fields of the corpus table")
+    stats = generation.CiderStats(refs, max(len(ids), 1))
+    term = len(ids)                                                       # no unit has this id: it only pads
+    flat = [r for rs in refs for r in rs]
+
+    def table(caps):
+        w = max(max(len(c) for c in caps), 1)
+        return torch.tensor([c + [term] * (w - len(c)) for c in caps], dtype=torch.int64).to(device)
+    begin_b = [0]
+    for rs in refs:
+        begin_b.append(begin_b[-1] + len(rs))
+    _, score = ops.caption_cider(table(hyps), [0] * len(hyps), list(range(len(hyps) + 1)), table(flat), [0] * len(flat), begin_b,
+                                 term=term, stats=stats)
+    return float(score.mean().item())
+
+
+def cal_metric(result_file, device=None):
     """(:246-298) first prediction per video id; predictions and references normalised to CJK characters"""
     result_list = json.load(open(result_file, "r"))
     seen, preds, golds = set(), {}, {}
@@ -306,8 +347,16 @@ def cal_metric(result_file):
     except ImportError:
         pairs = [(preds[k].split(), [g.split() for g in golds[k]]) for k in preds]
         b = bleu_scores(pairs)
-        return {"Bleu_1": b[0], "Bleu_2": b[1], "Bleu_3": b[2], "Bleu_4": b[3], "ROUGE_L": rouge_l(pairs),
-                "scorer": "built-in BLEU / ROUGE-L (pycocoevalcap not installed: no METEOR / CIDEr)"}
+        stats = {"Bleu_1": b[0], "Bleu_2": b[1], "Bleu_3": b[2], "Bleu_4": b[3], "ROUGE_L": rouge_l(pairs)}
+        why = "a CPU run" if device is None or torch.device(device).type != "cuda" else None
+        if why is None:
+            try:
+                stats["CIDEr"] = corpus_cider(pairs, device)
+            except ValueError as e:
+                why = str(e)
+        if why is None:
+            return {**stats, "scorer": "built-in BLEU / ROUGE-L, CIDEr on the device (pycocoevalcap not installed: no METEOR)"}
+        return {**stats, "scorer": f"built-in BLEU / ROUGE-L (pycocoevalcap not installed: no METEOR / CIDEr; no device CIDEr: {why})"}
     stem = os.path.basename(result_file).replace(".json", "")
     pred_file, gt_file = "/tmp/%s_coco_format.json" % stem, "/tmp/%s_gt_file.json" % stem
     json.dump([{"image_id": k, "caption": v} for k, v in preds.items()], open(pred_file, "w"), ensure_ascii=False)
@@ -361,6 +410,9 @@ def main(args, config):
         video, text = batch
         return {"loss_generation": s.model(*make_training_batch(video, text, config["prompt"], s.tokenizer, s.device, args.max_length))}
 
+    if getattr(args, "scst", False) and not args.evaluate_only:
+        step_fn = scst_step_fn(args, config, s, data_loader)
+
     if args.evaluate_only:
         result = evaluation(s.model, val_loader, s.tokenizer, s.device, config, batched=getattr(args, "eval_batched_beam", False),
                             clips_per_search=getattr(args, "clips_per_search", 32), eval_sample=getattr(args, "eval_sample", 0),
@@ -378,7 +430,7 @@ def main(args, config):
                                if getattr(args, "eval_sample_consensus", 0) else {}),
                             **({"allowed_phrases": read_phrases(args.eval_allowed_phrases)} if getattr(args, "eval_allowed_phrases", None) else {}))
         final = save_result(result, args.result_dir, "val_caption_result")
-        val_stats = cal_metric(final)
+        val_stats = cal_metric(final, s.device)
         if getattr(args, "eval_score_gold", False):
             val_stats = {**val_stats, **gold_perplexity(json.load(open(final, "r")))}        # the merged file: every rank's clips
         print("* Validation Stats:", val_stats)
@@ -386,6 +438,55 @@ def main(args, config):
         ft.write_log(args, log_stats)
         return log_stats
     return ft.epoch_loop(args, s, step_fn, lambda epoch: {})
+
+
+def training_captions(data_loader):
+    """the training set's captions, one list per clip, without touching a video: the synthetic split's fields, or the `ann` list of
+    the reference's caption datasets (a string or a list of strings under "caption")"""
+    ds = data_loader.dataset
+    if hasattr(ds, "fields"):
+        return [[ds.fields(i)[0]] for i in range(ds.n)]
+    if hasattr(ds, "ann"):
+        return [list(a["caption"]) if isinstance(a["caption"], (list, tuple)) else [a["caption"]] for a in ds.ann]
+    raise ValueError("--scst: the training set exposes no captions (no `ann` list): pass --scst_stats FILE, a saved generation.CiderStats")
+
+
+def scst_step_fn(args, config, s, data_loader):
+    """`--scst`: the training step as self-critical sequence training.  The rewards' corpus statistics are loaded (--scst_stats) or
+    built here, once, from the training set's captions as the training pairs tokenise them (gold_tokens); a step is ONE forward_scst
+    call over the batch -- prompts of different lengths in a batch are refused there -- and a clip's reference is its own caption."""
+    from types import SimpleNamespace
+
+    from youku_mplug_amd import generation
+    module = getattr(s.model, "module", s.model)
+    vocab = generation._gen_config(module.text_decoder).vocab_size
+    prompt = config["prompt"]
+    if getattr(args, "scst_stats", None):
+        stats = generation.CiderStats.load(args.scst_stats)
+    else:
+        stats = generation.CiderStats([gold_tokens(s.tokenizer, prompt, caps, args.max_length) for caps in training_captions(data_loader)], vocab)
+    print(f"SCST: CIDEr statistics over {stats.clips} clips, {stats.entries} n-grams in {stats.capacity} slots")
+    kw = dict(cider=stats, num_samples=getattr(args, "scst_samples", 5), baseline=getattr(args, "scst_baseline", "mean_others"),
+              temperature=getattr(args, "scst_temperature", 1.0))
+
+    steps = [0]
+
+    def step_fn(batch):
+        video, text = batch
+        video, text_input = make_training_batch(video, text, prompt, s.tokenizer, s.device, args.max_length)
+        refs = [gold_tokens(s.tokenizer, prompt, [c], args.max_length) for c in text]
+        # the prompt of a rollout: bos + the prompt's tokens, what generate's prompt of mask.sum() - 1 tokens is at evaluation.  The
+        # tokenizer shortens the prompt of an over-long pair: a batch whose prompts then differ in length is refused by forward_scst
+        # (one backward per step: the backward kernels overwrite .grad, so a step cannot be the sum of several forward_scst calls)
+        col = torch.arange(text_input["input_ids"].shape[1], device=s.device)[None]
+        mask = (col <= text_input["prompt_lengths"].to(s.device)[:, None] + 1).to(text_input["attention_mask"].dtype)
+        loss, st = module.forward_scst(video, SimpleNamespace(input_ids=text_input["input_ids"], attention_mask=mask), refs, **kw)
+        if dist.get_rank() == 0 and steps[0] % 10 == 0:                  # the loop's own print frequency
+            print(f"SCST step {steps[0]}: reward {st['reward']:.4f} baseline {st['baseline']:.4f} length {st['length']:.2f} "
+                  f"terminated {st['terminated']:.2f}")
+        steps[0] += 1
+        return {"loss_scst": loss}
+    return step_fn
 
 
 def read_phrases(path):
@@ -470,7 +571,25 @@ def get_args(argv=None):
         p.add_argument("--eval_score_gold", action="store_true", default=False,
                        help="evaluation: also score every clip's gold captions against its query features (model.score_captions): "
                             "gold_logprob / gold_tokens in the result file, per-token NLL and perplexity in the log")
+        # self-critical training: absent from the namespace unless given (argparse.SUPPRESS), so a run without them is the run before them
+        p.add_argument("--scst", action="store_true", default=argparse.SUPPRESS,
+                       help="training: self-critical sequence training -- sample captions, reward them with CIDEr against the clip's own "
+                            "caption on the device, weight their log-likelihood by reward minus baseline (model.forward_scst)")
+        p.add_argument("--scst_samples", type=int, default=argparse.SUPPRESS, help="--scst: sampled captions per clip (default 5)")
+        p.add_argument("--scst_baseline", type=str, default=argparse.SUPPRESS, choices=("mean_others", "greedy"),
+                       help="--scst: the baseline of a sample's reward -- the mean reward of the clip's other samples (default), or the "
+                            "reward of one greedy caption")
+        p.add_argument("--scst_temperature", type=float, default=argparse.SUPPRESS, help="--scst: the sampling temperature (default 1.0)")
+        p.add_argument("--scst_stats", type=str, default=argparse.SUPPRESS, metavar="FILE",
+                       help="--scst: a saved generation.CiderStats (default: built at start-up from the training set's captions)")
     args, config = ft.get_args(argv, extra=extra)
+    given = [k for k in ("scst_samples", "scst_baseline", "scst_temperature", "scst_stats") if hasattr(args, k)]
+    if given and not getattr(args, "scst", False):
+        raise ValueError(f"--{' / --'.join(given)} need --scst")
+    if getattr(args, "scst_samples", 5) < 1 or (getattr(args, "scst_samples", 5) < 2 and getattr(args, "scst_baseline", "mean_others") == "mean_others"):
+        raise ValueError(f"--scst_samples must be at least 2 with --scst_baseline mean_others, at least 1 with greedy (got {args.scst_samples})")
+    if not (math.isfinite(getattr(args, "scst_temperature", 1.0)) and getattr(args, "scst_temperature", 1.0) > 0):
+        raise ValueError(f"--scst_temperature must be finite and positive (got {args.scst_temperature})")
     if args.eval_sample_best_of < 0:
         raise ValueError(f"--eval_sample_best_of must not be negative (got {args.eval_sample_best_of})")
     if args.eval_sample_consensus < 0:

@@ -986,6 +986,67 @@ typedef struct mpv_caption_overlap_desc {
 } mpv_caption_overlap_desc;
 int mpv_caption_overlap(const mpv_caption_overlap_desc* d, mpv_stream_t stream);
 /* ------------------------------------------------------------------------------------------
+ * CIDEr of caption candidates against references (generation.CiderStats; DistributedGPT3_Caption.forward_scst's reward and the
+ * caption entry point's corpus metric): the reference scorer's compute_cider over TOKEN IDS with corpus statistics from a table.
+ * Tables, starts, CSR offsets, pair order, candidate definition, host copies and the 255-token limit are mpv_caption_overlap's:
+ *   side a holds the candidates, side b the references, group g's nA_g x nB_g pairs lie row-major from pair_begin[g] on.
+ * Corpus table (device): table_keys uint64 [table_capacity], table_idf fp64 [table_capacity], open addressing with linear probing.
+ *   Key of an n-gram (n = 1 .. 4) of ids t_0 .. t_{n-1}: sum_i (t_i + 1) << (16 * i) -- exact for ids in [0, 65534], the order is
+ *   implied by the highest non-zero field, 0 is the empty slot.  table_capacity is a power of two; the slot of a key is the
+ *   splitmix64 finaliser of the key (x ^= x >> 30; x *= 0xbf58476d1ce4e5b9; x ^= x >> 27; x *= 0x94d049bb133111eb; x ^= x >> 31)
+ *   masked by table_capacity - 1 -- ONE function in the library, which the kernel's probe and the host entries at the end of this
+ *   section share --, then the following slots, wrapping, up to the first empty one.  table_idf[slot] = log_ref_len - log(max(1, df)), taken in fp64 on the host; a key that is not in
+ *   the table weighs log_ref_len (df = 0).  The device takes no logarithm.  A probe gives up after table_capacity slots: a table
+ *   without an empty slot cannot hang the kernel.
+ * Arithmetic, per pair (c, r) and order n, all in fp64: vec_x[g] = count_x(g) * idf(g) over the distinct n-grams g of x;
+ *   norm_x = sqrt(sum_g vec_x[g]^2); val = sum over the distinct g of c of min(vec_c[g], vec_r[g]) * vec_r[g]; val /= norm_c *
+ *   norm_r when both are non-zero; val *= exp(-(len_c - len_r)^2 / (2 sigma^2)).  The reference scorer measures a length in
+ *   bigrams (len - 1, and 0 for an empty caption): the difference is the same for all non-empty captions, and every value that
+ *   involves an empty caption is 0 whatever the penalty.
+ * Outputs (device, fp64): pair [pairs][4] = val of the orders 1 .. 4; score [rows_a] = 10 * mean_n(sum_r pair[c][r][n] / nB_g),
+ *   0.0 for the candidates of a group without references.
+ * Invariants: every value has one writer; no atomics; every sum runs in an order that is a function of the two captions alone (a
+ *   lane's positions ascending, then a fixed butterfly over the lanes; the references of a candidate ascending): a pair's four
+ *   values and a candidate's score are bit-identical whatever else is in the call.  No column at or beyond width_x is read.
+ * Workspace: mpv_caption_cider_workspace_size(d) bytes (read from the host copies: the rows' keys and weights per position and
+ *   order, their norms and lengths), 8-byte aligned.
+ * Refused with a negative code before any launch: what mpv_caption_overlap refuses; a NULL table or output; table_capacity that is
+ *   no power of two or below 2; a log_ref_len that is negative or not finite; sigma that is not positive and finite; a NULL,
+ *   misaligned or too small workspace. */
+#define MPV_CAPTION_CIDER_ORDERS 4
+typedef struct mpv_caption_cider_desc {
+  const int64_t* tok_a;
+  const int64_t* tok_b;
+  const int32_t* start_a;
+  const int32_t* start_b;
+  const int32_t* begin_a;
+  const int32_t* begin_b;
+  const int64_t* pair_begin;
+  const uint64_t* table_keys;
+  const double* table_idf;
+  double* pair;
+  double* score;
+  const int32_t* host_start_a;
+  const int32_t* host_start_b;
+  const int32_t* host_begin_a;
+  const int32_t* host_begin_b;
+  const int64_t* host_pair_begin;
+  int64_t ld_a;
+  int64_t ld_b;
+  int64_t term;
+  int64_t table_capacity;
+  double log_ref_len;
+  double sigma;
+  int rows_a, rows_b, width_a, width_b, groups;
+} mpv_caption_cider_desc;
+size_t mpv_caption_cider_workspace_size(const mpv_caption_cider_desc* d);
+int mpv_caption_cider(const mpv_caption_cider_desc* d, void* workspace, size_t workspace_bytes, mpv_stream_t stream);
+/* The corpus table on the HOST, with the slot rule above: fill inserts n distinct non-zero keys with their values into
+ * table_keys / table_idf (both zeroed here first; capacity a power of two > n) -> 0, or a negative code; lookup -> the slot of
+ * `key`, or -1 when it is absent (key 0 is never present). */
+int mpv_cider_table_fill(const uint64_t* keys, const double* idf, int64_t n, uint64_t* table_keys, double* table_idf, int64_t capacity);
+int64_t mpv_cider_table_lookup(const uint64_t* table_keys, int64_t capacity, uint64_t key);
+/* ------------------------------------------------------------------------------------------
  * Sequence scores of sampled generation in lockstep (generation.SampleScores): ONE launch, right after mpv_sample_advance, records
  * the model's log-probability of the token that call wrote into column `pos` -- log_softmax of the RAW logits the sampler read
  * (after mpv_logits_constrain edited them, if it did).  Temperature, top-k and top-p are ignored by design: the score is the

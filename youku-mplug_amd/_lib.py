@@ -150,6 +150,17 @@ class CaptionOverlapDesc(C.Structure):
 
 CAPTION_OVERLAP_MAX_LEN = 255   # include/mpv.h MPV_CAPTION_OVERLAP_MAX_LEN
 
+
+class CaptionCiderDesc(C.Structure):
+    _fields_ = [(n, c_void_p) for n in ("tok_a", "tok_b", "start_a", "start_b", "begin_a", "begin_b", "pair_begin", "table_keys", "table_idf",
+                                        "pair", "score", "host_start_a", "host_start_b", "host_begin_a", "host_begin_b", "host_pair_begin")] + \
+               [("ld_a", c_int64), ("ld_b", c_int64), ("term", c_int64), ("table_capacity", c_int64)] + \
+               [("log_ref_len", C.c_double), ("sigma", C.c_double)] + \
+               [(n, c_int) for n in ("rows_a", "rows_b", "width_a", "width_b", "groups")]
+
+
+CAPTION_CIDER_ORDERS = 4        # include/mpv.h MPV_CAPTION_CIDER_ORDERS
+
 _RM = [c_int, c_int, c_int]
 _SIGS = {
     "mpv_version": (c_int, []),
@@ -324,6 +335,10 @@ _SIGS.update({
     "mpv_logits_trie_mask_ragged": (c_int, [C.POINTER(LogitsTrieDesc), c_void_p]),
     "mpv_logits_trie_mask_steps": (c_int, [C.POINTER(LogitsTrieDesc), c_void_p, c_void_p]),
     "mpv_caption_overlap": (c_int, [C.POINTER(CaptionOverlapDesc), c_void_p]),
+    "mpv_caption_cider_workspace_size": (c_size_t, [C.POINTER(CaptionCiderDesc)]),
+    "mpv_caption_cider": (c_int, [C.POINTER(CaptionCiderDesc), c_void_p, c_size_t, c_void_p]),
+    "mpv_cider_table_fill": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64]),
+    "mpv_cider_table_lookup": (c_int64, [c_void_p, c_int64, c_uint64]),
 })
 
 EXPORTS = tuple(_SIGS)

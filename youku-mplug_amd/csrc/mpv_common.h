@@ -72,6 +72,16 @@ __host__ __device__ __forceinline__ uint32_t mpv_mix32(uint32_t x) {
   x ^= x >> 16;
   return x;
 }
+// The splitmix64 finaliser: the slot rule of the CIDEr corpus table (include/mpv.h: mpv_caption_cider), one function for the host
+// entries that build and probe the table and for the kernel that probes it.
+__host__ __device__ __forceinline__ uint64_t mpv_mix64(uint64_t x) {
+  x ^= x >> 30;
+  x *= 0xbf58476d1ce4e5b9ULL;
+  x ^= x >> 27;
+  x *= 0x94d049bb133111ebULL;
+  x ^= x >> 31;
+  return x;
+}
 // One hash serves TWO adjacent elements (16 random bits each): the 32-bit integer multiply is quarter rate on CDNA, so a
 // hash per element (two rounds, 4 multiplies) cost ~35 issue slots per element -- 10 us per 256x256 tile in a GEMM
 // epilogue.  `ctr` is the 64-bit index of the pair's FIRST element; every site pairs along its fastest dimension with

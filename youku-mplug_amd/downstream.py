@@ -53,8 +53,9 @@ def shared_prefix_split(ids: torch.Tensor, first_out: torch.Tensor, last_out: to
 
 class _GenClsFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, anchor, model, args):
-        (lc, lk), tape = model._forward_pipeline(*args)
+    def forward(ctx, anchor, model, args, pipeline=None):
+        """pipeline (default: model._forward_pipeline): what runs the forward -> ((loss_caption, loss_cls), the tape _backward_pipeline reads)"""
+        (lc, lk), tape = (model._forward_pipeline if pipeline is None else pipeline)(*args)
         ctx.model, ctx.tape = model, tape
         return lc, lk
 
@@ -62,7 +63,7 @@ class _GenClsFn(torch.autograd.Function):
     def backward(ctx, g_caption, g_cls):
         ctx.model._backward_pipeline(ctx.tape, g_caption.contiguous().float(), g_cls.contiguous().float())
         ctx.tape = None
-        return torch.zeros(1, device=g_caption.device), None, None
+        return torch.zeros(1, device=g_caption.device), None, None, None
 
 
 class _GenCls(DistributedGPT3_Pretrain):
@@ -332,6 +333,158 @@ class DistributedGPT3_Caption(_GenCls):
 
     def forward(self, image, text=None):
         return self._run(image, text, None, None, None, True)[0]                              # :768-789 returns loss_caption only
+
+    SCST_BASELINES = ("mean_others", "greedy")
+    SCST_MAX_OPERAND_BYTES = 0x7FFFFFF0          # mpv_gemm_bf16 refuses an operand of this many bytes or more
+
+    def forward_scst(self, image, text, references, *, cider, num_samples=5, baseline="mean_others", temperature=1.0, top_k=None, top_p=None,
+                     seed=None, max_new_tokens=None, termination_id=None, rollouts=None):
+        """Self-critical sequence training (not in the reference): one step's loss from the model's OWN sampled
+        captions, each weighted by its CIDEr against the clip's references minus a baseline.  text: the prompts as in generate, ONE prompt
+        length per call; references[b]: clip b's reference captions, a non-empty list of token lists; cider: the corpus statistics, a
+        generation.CiderStats.  In order:
+          1. the query features, once per clip, in the model's mode, on the tape;
+          2. under no_grad and with the decoder in eval mode (the decode path must see no dropout), num_samples = N captions per clip from
+             those features through the device sampler (text_decoder.sample_batched, kv="shared_prefix"; temperature / top_k / top_p as in
+             generate; seed None: derived from text_decoder.step_seed, so a resumed run repeats its rollouts; max_new_tokens None: the
+             decoder's tokens_to_generate); baseline="greedy" adds one top_k=1 caption per clip.  rollouts: an int64 table
+             [B * N, <= prompt + max_new_tokens] in the sampler's output layout (row b * N + s) that REPLACES the sampling;
+          3. the rewards r [B, N]: ONE ops.caption_cider call on the sampler's padded table against the references' table (one upload);
+          4. the advantages, fp32 on the device: "mean_others" A[b, n] = mean_{m != n}(r[b, n] - r[b, m]) (N >= 2), "greedy"
+             A[b, n] = r[b, n] - r_greedy[b];
+          5. ONE training pass of the frozen decoder over the B * N sequences [query slots | prompt | sample], the query rows repeated
+             (_expand; sequence s * B + b: the fold of _backward_pipeline then adds a clip's rows in sample order), the loss window from the
+             prompt's last position on, the weight of a generated position up to and including the terminating token A[b, n] / T with T
+             the number of such positions in the call, 0 elsewhere: loss = sum_t w_t CE_t, the weights handed to the CE kernel as they
+             are (signed: no normalisation by their sum, which is near zero);
+          6. backward through _GenClsFn / _backward_pipeline.
+        -> (loss, stats): stats = dict(reward, baseline, length, terminated), the means over the B * N samples, read from the device once."""
+        o = self._scst_options(SimpleNamespace(text=text, references=references, cider=cider, num_samples=num_samples, baseline=baseline,
+                                               temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, max_new_tokens=max_new_tokens,
+                                               termination_id=termination_id, rollouts=rollouts))      # every refusal comes first
+        holder = {}
+        args = (image, o, holder)
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            loss = _GenClsFn.apply(self._anchor, self, args, self._scst_pipeline)[0]
+        else:
+            loss = self._scst_pipeline(*args)[0][0]
+        reward, base, length, terminated = holder["stats"].tolist()                          # stats: one read, at the end
+        return loss, dict(reward=reward, baseline=base, length=length, terminated=terminated)
+
+    def _scst_options(self, o):
+        """forward_scst's arguments as a namespace -> the same namespace, checked and completed before anything is launched: B, N, pl (the
+        one prompt length), width (the token table's columns), term, seed, the references as host lists"""
+        if o.baseline not in self.SCST_BASELINES:
+            raise ValueError(f"baseline must be one of {self.SCST_BASELINES} (got {o.baseline!r})")
+        o.N = int(o.num_samples)
+        if o.N < 1:
+            raise ValueError(f"num_samples must be at least 1 (got {o.N})")
+        if o.baseline == "mean_others" and o.N < 2:
+            raise ValueError('baseline="mean_others" compares a sample with the clip\'s other samples: num_samples must be at least 2 (got 1)')
+        if not isinstance(o.cider, generation.CiderStats):
+            raise ValueError(f"cider must be a generation.CiderStats (got {type(o.cider).__name__})")
+        gc = generation._gen_config(self.text_decoder)
+        if gc.vocab_size > o.cider.vocab:                # the kernel packs id + 1 into 16 bits: a sampled id beyond the table's would alias
+            raise ValueError(f"cider was built for a vocabulary of {o.cider.vocab} ids, the decoder draws from {gc.vocab_size}: its keys "
+                             "would alias (CiderStats holds at most 65535 ids)")
+        ids, mask = o.text.input_ids, o.text.attention_mask
+        o.B = ids.shape[0]
+        if len(o.references) != o.B:
+            raise ValueError(f"{len(o.references)} reference lists for {o.B} clips")
+        o.refs = [[[int(t) for t in (r.tolist() if torch.is_tensor(r) else r)] for r in refs] for refs in o.references]
+        for b, refs in enumerate(o.refs):
+            if not refs:
+                raise ValueError(f"clip {b} has no references: a self-critical reward needs at least one per clip")
+        lengths = (mask.sum(-1) - 1).tolist()
+        if len(set(lengths)) != 1:
+            raise ValueError(f"forward_scst takes one prompt length per call (got {sorted(set(lengths))}): group the clips by prompt length")
+        o.pl = int(lengths[0])
+        if o.pl < 1:
+            raise ValueError("every clip needs a prompt of at least one token")
+        o.budget = gc.tokens_to_generate if o.max_new_tokens is None else int(o.max_new_tokens)
+        o.width = min(o.pl + o.budget, gc.max_position_embeddings)
+        if o.budget < 1 or o.width <= o.pl:
+            raise ValueError(f"no room to generate: prompt of {o.pl} tokens, max_new_tokens {o.budget}, {gc.max_position_embeddings} positions")
+        if o.width - o.pl > ops._lib.CAPTION_OVERLAP_MAX_LEN:
+            raise ValueError(f"a row of {o.width} columns behind a prompt of {o.pl} tokens can hold a caption of more than "
+                             f"{ops._lib.CAPTION_OVERLAP_MAX_LEN} tokens: lower max_new_tokens")
+        if max(len(r) for refs in o.refs for r in refs) > ops._lib.CAPTION_OVERLAP_MAX_LEN:
+            raise ValueError(f"a reference holds more than {ops._lib.CAPTION_OVERLAP_MAX_LEN} tokens")
+        # the training pass is ONE decoder pass over B * N sequences: its largest GEMM operands -- the MLP's [rows, ffn] activation and
+        # the loss window's [rows, vocab] logits, bf16 -- must stay under the GEMM entry's 2 GiB operand limit (include/mpv.h)
+        cfg = self.text_decoder.config
+        rows, wrows = o.B * o.N * (self.num_learnable_token + o.width), o.B * o.N * (o.width - o.pl)
+        worst = max(rows * cfg.ffn_hidden_size, wrows * cfg.vocab_size, rows * 3 * cfg.hidden_size) * 2
+        if worst >= self.SCST_MAX_OPERAND_BYTES:
+            raise ValueError(f"one training pass over {o.B} clips x {o.N} samples of {self.num_learnable_token + o.width} positions needs a "
+                             f"GEMM operand of {worst} bytes, larger than 2 GiB: pass fewer clips per forward_scst call")
+        o.termination_id, o.term = self._termination(o.termination_id)
+        if not 0 <= o.term < gc.vocab_size:                      # it pads the rollouts, which the training pass embeds
+            raise ValueError(f"termination_id = {o.term} is no token of the vocabulary [0, {gc.vocab_size})")
+        if o.rollouts is not None:
+            r = o.rollouts
+            if r.dtype != torch.int64 or r.ndim != 2 or r.shape[0] != o.B * o.N or not o.pl < r.shape[1] <= o.width:
+                raise ValueError(f"rollouts must be int64 [{o.B * o.N}, {o.pl + 1} .. {o.width}] (got {r.dtype} {tuple(r.shape)})")
+            if int(r.min()) < 0 or int(r.max()) >= gc.vocab_size:
+                raise ValueError(f"rollouts hold ids outside the vocabulary [0, {gc.vocab_size})")
+        if o.seed is None:
+            o.seed = (int(self.text_decoder.step_seed) ^ 0x5C57C1DE) & 0x3FFFFFFFFFFFFFFF
+        return o
+
+    def _scst_rollout(self, o, qf, N, **filt):
+        """N sampled captions per clip on the query features qf [B, Q, H] -> the padded device table [B * N, width], row b * N + s"""
+        toks = self.text_decoder.sample_batched(o.text.input_ids[:, :o.pl].contiguous(), query_embeds=qf, temperature=o.temperature,
+                                                num_samples=N, seed=o.seed, termination_id=o.termination_id, kv="shared_prefix",
+                                                prompt_length=torch.full((o.B,), o.pl, device=qf.device), tokens_to_generate=o.budget, **filt)
+        return generation.pad_after_termination(toks, o.pl, o.term, o.width, o.term)
+
+    def _scst_pipeline(self, video, o, holder):
+        """forward_scst's steps 1 - 5 -> ((loss, 0), the tape of _backward_pipeline); holder["stats"]: the four means, on the device"""
+        B, N, pl, W, term = o.B, o.N, o.pl, o.width, o.term
+        Q, Hh = self.num_learnable_token, self.text_width
+        tape = {"vit": {}, "pool": {}, "gpt": {}, "gpt2": {}}
+        qf = self._query_features(video, tape)                                               # 1. in the model's mode, on the tape
+        dev = qf.device
+        with torch.no_grad(), _eval_mode(self):                                              # 2. the decode path sees no dropout
+            q3 = qf.view(B, Q, Hh)
+            if o.rollouts is None:
+                table = self._scst_rollout(o, q3, N, top_k=o.top_k, top_p=o.top_p)
+            else:
+                table = generation.pad_after_termination(o.rollouts.to(dev), pl, term, W, term)
+            rows = table.view(B, N, W)
+            if o.baseline == "greedy":
+                rows = torch.cat([rows, self._scst_rollout(o, q3, 1, top_k=1).view(B, 1, W)], dim=1)
+        K = rows.shape[1]
+        flat = [r for refs in o.refs for r in refs]                                          # 3. the references: one table, one upload
+        Wr = max(max(len(r) for r in flat), 1)
+        ref_table = torch.tensor([r + [term] * (Wr - len(r)) for r in flat], dtype=torch.int64).to(dev)
+        ref_begin = [0]
+        for refs in o.refs:
+            ref_begin.append(ref_begin[-1] + len(refs))
+        _, score = ops.caption_cider(rows.reshape(B * K, W).contiguous(), [pl] * (B * K), list(range(0, B * K + 1, K)), ref_table,
+                                     [0] * len(flat), ref_begin, term=term, stats=o.cider)
+        r_all = score.view(B, K).to(torch.float32)
+        r = r_all[:, :N]
+        if o.baseline == "greedy":                                                           # 4. fp32, on the device
+            adv = r - r_all[:, N:]
+        else:                  # mean_{m != n}(r_n - r_m): the differences of equal rewards are exactly 0, whatever N
+            adv = (r[:, :, None] - r[:, None, :]).sum(dim=2) / (N - 1)
+        gen = table[:, pl:]                                                                  # [B * N, W - pl], row b * N + s
+        is_term = gen == term
+        live = (is_term.cumsum(dim=1) - is_term.to(torch.int64)) == 0                        # up to and including the terminating token
+        T = live.sum().to(torch.float32)
+        weights = adv.reshape(B * N, 1) * live.to(torch.float32) / T
+        ended = is_term.any(dim=1)
+        holder["stats"] = torch.stack([r.mean(), (r - adv).mean(), (live.sum(dim=1) - ended.to(torch.int64)).to(torch.float32).mean(),
+                                       ended.to(torch.float32).mean()])
+        # 5. sequence s * B + b: the first B rows are the clips' own, what _backward_pipeline's fold expects
+        order = lambda t: t.view(B, N, -1).transpose(0, 1).reshape(N * B, -1).contiguous()
+        src = list(range(B)) * N
+        wl = W - pl
+        out = self.text_decoder.forward_lm(self._expand(qf, src), order(table), None, None, tape["gpt"], loss_window=(Q + pl - 1, wl),
+                                           window_targets=(order(gen).view(-1), order(weights).view(-1)))
+        tape.update(src=src, Bv=B)
+        return (out["loss"], torch.zeros((), dtype=torch.float32, device=dev)), tape
 
     @torch.no_grad()
     def generate(self, image, text, termination_id=None, batched=False, clips_per_search=32, do_sample=False, num_samples=1, temperature=1.0,

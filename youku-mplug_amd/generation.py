@@ -1157,7 +1157,7 @@ class SampleScores:
 def sample_batched_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None, temperature=1.0, use_eod_token_for_early_termination=True,
                         stop_on_double_eol=False, stop_on_eol=False, termination_id=None, prompt_length=None, num_samples=1, seed=0,
                         streams=None, advance_fn=None, constraints: Optional["LogitsConstraints"] = None, constrain_fn=None,
-                        return_scores=False, score_fn=None, mixed_prompts=False, trie_fn=None):
+                        return_scores=False, score_fn=None, mixed_prompts=False, trie_fn=None, tokens_to_generate=None):
     """Sampled generation for B clips x num_samples sequences in lockstep, the whole of a step's sampling and bookkeeping in one
     launch: tokens [B, L], query_embeds [B, Q, H]; sequence j belongs to clip j // num_samples.  The prefill runs once per clip
     (state.prefill_fan_out) and fans out to the clip's samples; afterwards a step is state.step(st.next_tok) and _Sampler.step:
@@ -1192,8 +1192,11 @@ def sample_batched_loop(cfg, make_state, tokens: torch.Tensor, query_embeds=None
     along the trie, through trie_fn (the ops.logits_trie_mask* of the mode) with the same table, lengths, column, termination id and
     -inf: a banned token is never drawn, so every row is a phrase followed by the termination id (and then draws that id until the
     loop ends).  score_fn then records log-probabilities RENORMALISED over the allowed tokens.  Raised before the first launch: what
-    _active_trie refuses (min_new_tokens, stop_on_eol / stop_on_double_eol, a phrase with the termination id)."""
+    _active_trie refuses (min_new_tokens, stop_on_eol / stop_on_double_eol, a phrase with the termination id).
+    tokens_to_generate (default None: cfg.tokens_to_generate): the columns this call appends to the table."""
     B, dev, N = tokens.size(0), tokens.device, int(num_samples)
+    if tokens_to_generate is not None:
+        cfg = SimpleNamespace(**dict(vars(cfg), tokens_to_generate=int(tokens_to_generate)))
     sampler = _Sampler(cfg, dict(num_samples=num_samples), temperature, seed, termination_id, stop_on_double_eol, stop_on_eol, advance_fn,
                        constraints, constrain_fn, return_scores, score_fn, "sample_score", trie_fn)
     R = B * N
@@ -1653,6 +1656,127 @@ def consensus_order(U) -> list:
         order.append(pick)
         left.remove(pick)
     return order
+
+
+class CiderStats:
+    """The corpus statistics of CIDEr over TOKEN IDS, for ops.caption_cider (include/mpv.h: mpv_caption_cider).
+    reference_sets: one list of reference token lists per clip; vocab: ids lie in [0, vocab), vocab <= 65535.  Built on the host, once.
+    For every n-gram of the orders 1 .. n the document frequency df is the number of CLIPS with at least one reference that holds it
+    (once per clip, however often and in however many of its references); log_ref_len = log(number of clips).
+    An n-gram's key is exact: (id + 1) in 16 bits per token, the first token lowest, in one uint64 -- the order is implied and 0 is the
+    empty slot.  The table is open addressing with linear probing over `capacity` slots, a power of two of at least twice the entry
+    count (capacity= forces another power of two above the entry count): keys uint64 [capacity], idf float64 [capacity] =
+    log_ref_len - log(max(1, df)) in fp64; the slot of a key is the library's splitmix64 finaliser of it masked by capacity - 1, the same
+    function the kernel probes with.  A key that is not in the table weighs log_ref_len.
+    .arrays(device) -> (keys, idf, log_ref_len), uploaded once per device; .lookup(ngram) -> the n-gram's idf by the host probe;
+    .df(ngram) -> its document frequency; save(path) / CiderStats.load(path): plain tensors through torch.save;
+    CiderStats.from_token_table(tokens, start, begin, term, vocab): from the padded layout the kernel reads."""
+    MAX_VOCAB, ORDERS = 65535, 4
+
+    def __init__(self, reference_sets, vocab: int, n: int = 4, capacity: Optional[int] = None):
+        vocab, n = int(vocab), int(n)
+        if not 1 <= vocab <= self.MAX_VOCAB:
+            raise ValueError(f"CiderStats: vocab = {vocab} does not fit 16-bit key fields (ids + 1 <= {self.MAX_VOCAB})")
+        if n != self.ORDERS:
+            raise ValueError(f"CiderStats: the kernel counts the orders 1 .. {self.ORDERS} (got n = {n})")
+        df = {}
+        clips = 0
+        for refs in reference_sets:
+            clips += 1
+            seen = set()
+            for ref in refs:
+                ref = [int(t) for t in (ref.tolist() if torch.is_tensor(ref) else ref)]
+                if any(t < 0 or t >= vocab for t in ref):
+                    raise ValueError(f"CiderStats: a reference holds an id outside [0, {vocab})")
+                for k in range(1, n + 1):
+                    for i in range(len(ref) - k + 1):
+                        seen.add(self.key(ref[i:i + k]))
+            for key in seen:                                     # once per clip
+                df[key] = df.get(key, 0) + 1
+        if clips < 1:
+            raise ValueError("CiderStats: no clips")
+        self.vocab, self.n, self.clips = vocab, n, clips
+        self.log_ref_len = math.log(float(clips))
+        keys = sorted(df)
+        self._finish(keys, [df[k] for k in keys], capacity)
+
+    @staticmethod
+    def key(ngram) -> int:
+        """the packed key of an n-gram of 1 .. 4 ids"""
+        ngram = [int(t) for t in ngram]
+        if not 1 <= len(ngram) <= CiderStats.ORDERS or any(t < 0 or t >= CiderStats.MAX_VOCAB for t in ngram):
+            raise ValueError(f"CiderStats: an n-gram is 1 .. {CiderStats.ORDERS} ids in [0, {CiderStats.MAX_VOCAB}) (got {ngram})")
+        return sum((t + 1) << (16 * i) for i, t in enumerate(ngram))
+
+    def _finish(self, keys, dfs, capacity):
+        import numpy as np
+        entries = len(keys)
+        cap = 2
+        while cap < 2 * entries:
+            cap *= 2
+        if capacity is not None:
+            cap = int(capacity)
+            if cap < 2 or cap & (cap - 1) or cap <= entries:
+                raise ValueError(f"CiderStats: capacity = {cap} must be a power of two above the {entries} entries")
+        self.entries, self.capacity = entries, cap
+        self.entry_keys = torch.from_numpy(np.array(keys, dtype=np.uint64).view(np.int64))      # the bit patterns, ascending as unsigned
+        self.entry_df = torch.tensor(dfs, dtype=torch.int64)
+        idf = self.log_ref_len - torch.log(self.entry_df.clamp(min=1).to(torch.float64))
+        tk, ti = torch.zeros(cap, dtype=torch.int64), torch.zeros(cap, dtype=torch.float64)
+        _lib.check(_lib.lib().mpv_cider_table_fill(self.entry_keys.data_ptr(), idf.data_ptr(), entries, tk.data_ptr(), ti.data_ptr(), cap),
+                   "mpv_cider_table_fill")
+        self.keys, self.idf = tk.view(torch.uint64), ti
+        self._device = {}
+
+    def slot(self, ngram) -> int:
+        """the table slot that holds the n-gram, -1 when the corpus does not"""
+        return int(_lib.lib().mpv_cider_table_lookup(self.keys.data_ptr(), self.capacity, self.key(ngram)))
+
+    def lookup(self, ngram) -> float:
+        """idf of the n-gram by the host probe: log_ref_len for an n-gram the corpus does not hold"""
+        s = self.slot(ngram)
+        return self.log_ref_len if s < 0 else float(self.idf[s])
+
+    def df(self, ngram) -> int:
+        i = int(torch.searchsorted(self._unsigned_order(), self.key(ngram) - (1 << 63)))
+        ok = i < self.entries and int(self._unsigned_order()[i]) == self.key(ngram) - (1 << 63)
+        return int(self.entry_df[i]) if ok else 0
+
+    def _unsigned_order(self):
+        return self.entry_keys ^ torch.iinfo(torch.int64).min     # int64 that sorts as the uint64 keys do
+
+    def arrays(self, device):
+        """-> (keys uint64 [capacity], idf float64 [capacity], log_ref_len) with the tensors on `device`, uploaded once per device"""
+        key = str(torch.device(device))
+        hit = self._device.get(key)
+        if hit is None:
+            hit = self._device[key] = (self.keys.to(device), self.idf.to(device), self.log_ref_len)
+        return hit
+
+    def save(self, path):
+        torch.save(dict(entry_keys=self.entry_keys, entry_df=self.entry_df, clips=torch.tensor(self.clips), vocab=torch.tensor(self.vocab),
+                        n=torch.tensor(self.n), capacity=torch.tensor(self.capacity)), path)
+
+    @classmethod
+    def load(cls, path) -> "CiderStats":
+        sd = torch.load(path, map_location="cpu")
+        self = cls.__new__(cls)
+        self.vocab, self.n, self.clips = int(sd["vocab"]), int(sd["n"]), int(sd["clips"])
+        self.log_ref_len = math.log(float(self.clips))
+        import numpy as np
+        keys = sd["entry_keys"].numpy().view(np.uint64).tolist()
+        self._finish(keys, sd["entry_df"].tolist(), int(sd["capacity"]))
+        return self
+
+    @classmethod
+    def from_token_table(cls, tokens, start, begin, term: int, vocab: int, n: int = 4, capacity: Optional[int] = None) -> "CiderStats":
+        """tokens int64 [rows, width] (any device), start: the rows' first columns, begin: the clips' CSR offsets over the rows, term:
+        the id that ends a row -- the references' table as ops.caption_cider reads it"""
+        rows = tokens.cpu().tolist()
+        start = [int(s) for s in (start.tolist() if torch.is_tensor(start) else start)]
+        begin = [int(b) for b in (begin.tolist() if torch.is_tensor(begin) else begin)]
+        refs = [generated_part(row, s, int(term)) for row, s in zip(rows, start)]
+        return cls([refs[a:b] for a, b in zip(begin, begin[1:])], vocab, n, capacity)
 
 
 def _sampler_config(gpt, top_k=None, top_p=None):

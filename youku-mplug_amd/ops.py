@@ -1096,6 +1096,50 @@ def sample_score_steps(logits, st, sc, *, row_step, vocab=None, ld=None):
     return _sample_score("sample_score_steps", **locals())
 
 
+def _caption_sides(who, tok_a, start_a, begin_a, tok_b, start_b, begin_b, width_a, width_b):
+    """what caption_overlap and caption_cider check and lay out on the host before any launch (`who` names the caller in the
+    messages) -> (host: [start_a, begin_a, start_b, begin_b] as CPU int32 tensors, shape: (rows, width, row stride) per side, groups,
+    pair_begin int64 [groups + 1]: the running sums of nA_g * nB_g)"""
+    _need_cuda(tok_a, tok_b)
+    host, shape = [], []
+    for name, tok, start, begin, width in (("a", tok_a, start_a, begin_a, width_a), ("b", tok_b, start_b, begin_b, width_b)):
+        if tok.dtype != torch.int64 or tok.ndim != 2 or (tok.shape[0] > 1 and tok.shape[1] > 1 and tok.stride(1) != 1):
+            raise _lib.MpvError(f"{who}: tok_{name} must be int64 [rows, width] with unit column stride (got {tok.dtype} {tuple(tok.shape)})")
+        width = tok.shape[1] if width is None else int(width)
+        if width > tok.shape[1]:
+            raise ValueError(f"{who}: width_{name} = {width} for a table of {tok.shape[1]} columns")
+        start = torch.as_tensor(start, dtype=torch.int32, device="cpu").reshape(-1)
+        begin = torch.as_tensor(begin, dtype=torch.int32, device="cpu").reshape(-1)
+        if start.numel() != tok.shape[0]:
+            raise ValueError(f"{who}: {start.numel()} start_{name} for {tok.shape[0]} rows")
+        if start.numel() and width - int(start.min()) > _lib.CAPTION_OVERLAP_MAX_LEN:
+            raise ValueError(f"{who}: a row of table {name} can hold a candidate of {width - int(start.min())} tokens "
+                             f"(width {width}, start {int(start.min())}); at most {_lib.CAPTION_OVERLAP_MAX_LEN}")
+        host += [start, begin]
+        shape.append((tok.shape[0], width, tok.stride(0) if tok.shape[0] > 1 else max(width, 1)))
+    groups = host[1].numel() - 1
+    if groups != host[3].numel() - 1 or groups < 0:
+        raise ValueError(f"{who}: begin_a / begin_b describe {groups} and {host[3].numel() - 1} groups")
+    na, nb = host[1].to(torch.int64).diff(), host[3].to(torch.int64).diff()
+    pair_begin = torch.cat([torch.zeros(1, dtype=torch.int64), (na * nb).cumsum(0)])
+    return host, shape, groups, pair_begin
+
+
+def _caption_upload(d, host, pair_begin, dev):
+    """ONE upload of the pair offsets (int64) and the four int32 arrays; the descriptor's device and host pointers to them.  -> what
+    must stay alive until the call has been made"""
+    packed = torch.cat([pair_begin.view(torch.uint8)] + [h.contiguous().view(torch.uint8) for h in host])
+    up = packed.to(dev)
+    at, dptr, hptr = 0, [], []
+    for h in [pair_begin] + host:
+        dptr.append(up.data_ptr() + at)
+        hptr.append(packed.data_ptr() + at)
+        at += h.numel() * h.element_size()
+    d.pair_begin, d.start_a, d.begin_a, d.start_b, d.begin_b = dptr
+    d.host_pair_begin, d.host_start_a, d.host_begin_a, d.host_start_b, d.host_begin_b = hptr
+    return packed, up
+
+
 def caption_overlap(tok_a, start_a, begin_a, tok_b=None, start_b=None, begin_b=None, *, term, width_a=None, width_b=None):
     """Pairwise overlap counts between caption candidates on the current stream (include/mpv.h: mpv_caption_overlap).  tok_x: int64
     [rows_x, >= width_x] on the device with unit column stride (the row stride may exceed the width; width_x defaults to the column
@@ -1108,55 +1152,59 @@ def caption_overlap(tok_a, start_a, begin_a, tok_b=None, start_b=None, begin_b=N
         if start_b is not None or begin_b is not None or width_b is not None:
             raise ValueError("caption_overlap: start_b / begin_b / width_b without tok_b")
         tok_b, start_b, begin_b, width_b = tok_a, start_a, begin_a, width_a
-    _need_cuda(tok_a, tok_b)
-    host, shape = [], []
-    for name, tok, start, begin, width in (("a", tok_a, start_a, begin_a, width_a), ("b", tok_b, start_b, begin_b, width_b)):
-        if tok.dtype != torch.int64 or tok.ndim != 2 or (tok.shape[0] > 1 and tok.shape[1] > 1 and tok.stride(1) != 1):
-            raise _lib.MpvError(f"caption_overlap: tok_{name} must be int64 [rows, width] with unit column stride (got {tok.dtype} {tuple(tok.shape)})")
-        width = tok.shape[1] if width is None else int(width)
-        if width > tok.shape[1]:
-            raise ValueError(f"caption_overlap: width_{name} = {width} for a table of {tok.shape[1]} columns")
-        start = torch.as_tensor(start, dtype=torch.int32, device="cpu").reshape(-1)
-        begin = torch.as_tensor(begin, dtype=torch.int32, device="cpu").reshape(-1)
-        if start.numel() != tok.shape[0]:
-            raise ValueError(f"caption_overlap: {start.numel()} start_{name} for {tok.shape[0]} rows")
-        if start.numel() and width - int(start.min()) > _lib.CAPTION_OVERLAP_MAX_LEN:
-            raise ValueError(f"caption_overlap: a row of table {name} can hold a candidate of {width - int(start.min())} tokens "
-                             f"(width {width}, start {int(start.min())}); at most {_lib.CAPTION_OVERLAP_MAX_LEN}")
-        host += [start, begin]
-        shape.append((tok.shape[0], width, tok.stride(0) if tok.shape[0] > 1 else max(width, 1)))
-    groups = host[1].numel() - 1
-    if groups != host[3].numel() - 1 or groups < 0:
-        raise ValueError(f"caption_overlap: begin_a / begin_b describe {groups} and {host[3].numel() - 1} groups")
+    host, shape, groups, pair_begin = _caption_sides("caption_overlap", tok_a, start_a, begin_a, tok_b, start_b, begin_b, width_a, width_b)
     dev = tok_a.device
-    na, nb = host[1].to(torch.int64).diff(), host[3].to(torch.int64).diff()
-    pair_begin = torch.cat([torch.zeros(1, dtype=torch.int64), (na * nb).cumsum(0)])
     pairs = max(int(pair_begin[-1]), 0)
     len_a = torch.empty(shape[0][0], dtype=torch.int32, device=dev)
     len_b = len_a if same else torch.empty(shape[1][0], dtype=torch.int32, device=dev)
     counts = torch.empty((pairs, 5), dtype=torch.int32, device=dev)
     if groups == 0:
         return len_a, len_b, counts
-    # ONE upload: the pair offsets (int64) first, then the four int32 arrays
-    packed = torch.cat([pair_begin.view(torch.uint8)] + [h.contiguous().view(torch.uint8) for h in host])
-    up = packed.to(dev)
-    at, dptr, hptr = 0, [], []
-    for h in [pair_begin] + host:
-        dptr.append(up.data_ptr() + at)
-        hptr.append(packed.data_ptr() + at)
-        at += h.numel() * h.element_size()
+    d = _lib.CaptionOverlapDesc()
+    keep = _caption_upload(d, host, pair_begin, dev)
     some = torch.zeros(2, dtype=torch.int64, device=dev)               # what a side without rows, or a call without pairs, points at
     ptr = lambda t: t.data_ptr() if t.numel() else some.data_ptr()
-    d = _lib.CaptionOverlapDesc()
     d.tok_a, d.tok_b, d.len_a, d.len_b, d.counts = ptr(tok_a), ptr(tok_b), ptr(len_a), ptr(len_b), ptr(counts)
-    d.pair_begin, d.start_a, d.begin_a, d.start_b, d.begin_b = dptr
-    d.host_pair_begin, d.host_start_a, d.host_begin_a, d.host_start_b, d.host_begin_b = hptr
     (d.rows_a, d.width_a, d.ld_a), (d.rows_b, d.width_b, d.ld_b) = shape
     d.term, d.groups = int(term), groups
     if same:                                                            # one table: the library computes its lengths once
         d.start_b, d.begin_b = d.start_a, d.begin_a
     check(_lib.lib().mpv_caption_overlap(C.byref(d), _stream()), "mpv_caption_overlap")
     return len_a, len_b, counts
+
+
+def caption_cider(tok_a, start_a, begin_a, tok_b, start_b, begin_b, *, term, stats, sigma=6.0, width_a=None, width_b=None):
+    """CIDEr of caption candidates (side a) against references (side b) on the current stream (include/mpv.h: mpv_caption_cider).  The
+    tables, starts and CSR offsets are caption_overlap's; stats: the corpus statistics, a generation.CiderStats (or the tuple its
+    arrays(device) returns: (keys uint64 [cap], idf fp64 [cap], log_ref_len)).  -> (pair [pairs, 4], score [rows_a]) fp64 on the
+    device: per (candidate, reference) pair of a group, row-major, the similarity of the orders 1 .. 4 after the length penalty, and
+    per candidate 10 * mean_n(sum_r pair / R) (0.0 in a group without references).  Raises ValueError before any launch when a row
+    could hold a candidate of more than 255 tokens."""
+    host, shape, groups, pair_begin = _caption_sides("caption_cider", tok_a, start_a, begin_a, tok_b, start_b, begin_b, width_a, width_b)
+    dev = tok_a.device
+    keys, idf, log_ref_len = stats.arrays(dev) if hasattr(stats, "arrays") else stats
+    _need_cuda(keys, idf)
+    if keys.dtype != torch.uint64 or idf.dtype != torch.float64 or keys.ndim != 1 or keys.shape != idf.shape or not keys.is_contiguous() \
+            or not idf.is_contiguous() or keys.device != dev or idf.device != dev:
+        raise _lib.MpvError(f"caption_cider: the corpus table must be contiguous uint64 / float64 [capacity] on {dev} "
+                            f"(got {keys.dtype} {tuple(keys.shape)}, {idf.dtype} {tuple(idf.shape)})")
+    pairs = max(int(pair_begin[-1]), 0)
+    pair = torch.empty((pairs, _lib.CAPTION_CIDER_ORDERS), dtype=torch.float64, device=dev)
+    score = torch.empty(shape[0][0], dtype=torch.float64, device=dev)
+    if groups == 0:
+        return pair, score
+    d = _lib.CaptionCiderDesc()
+    keep = _caption_upload(d, host, pair_begin, dev)
+    some = torch.zeros(4, dtype=torch.float64, device=dev)             # what a side without rows, or a call without pairs, points at
+    ptr = lambda t: t.data_ptr() if t.numel() else some.data_ptr()
+    d.tok_a, d.tok_b, d.pair, d.score = ptr(tok_a), ptr(tok_b), ptr(pair), ptr(score)
+    d.table_keys, d.table_idf, d.table_capacity = keys.data_ptr(), idf.data_ptr(), keys.numel()
+    d.log_ref_len, d.sigma = float(log_ref_len), float(sigma)
+    (d.rows_a, d.width_a, d.ld_a), (d.rows_b, d.width_b, d.ld_b) = shape
+    d.term, d.groups = int(term), groups
+    ws = workspace(_lib.lib().mpv_caption_cider_workspace_size(C.byref(d)), dev)
+    check(_lib.lib().mpv_caption_cider(C.byref(d), ws.data_ptr(), ws.numel(), _stream()), "mpv_caption_cider")
+    return pair, score
 
 
 def sample_tokens(logits, *, temperature=1.0, top_k=0, top_p=0.0, seed=0, streams=None, vocab_size=None, vocab=None):
