@@ -69,7 +69,9 @@ What this entry point adds to downstream/finetune_common.py:
     weights its log-likelihood by reward minus baseline (`model.forward_scst`).  The corpus statistics are a
     saved `generation.CiderStats` (FILE) or, by default, built at start-up from the training set's captions (with
     `--synthetic_steps`, the synthetic ones); a step is one `forward_scst` call, and a batch whose prompts differ in length (the
-    tokenizer shortens the prompt of an over-long pair) is refused;
+    tokenizer shortens the prompt of an over-long pair) is refused.  `--scst_shared_prefix` (needs `--scst`, default off) runs the
+    step's training pass on a shared prefix, as the rollout already runs: every clip's query slots and prompt once, its samples as
+    packed continuations (`forward_scst(training_pass="shared_prefix")`, DESIGN.md section 32; that pass applies no decoder dropout);
   * corpus CIDEr in the evaluation's result dict ("CIDEr": the mean over clips of the scorer's 10 x mean-over-orders score): over the
     same CJK-character units as BLEU / ROUGE-L, the units mapped to ids in order of first appearance, df from this evaluation's own
     references as the reference project's scorer takes it, ONE `ops.caption_cider` call (`corpus_cider`).  Past 65 535 distinct
@@ -468,6 +470,8 @@ def scst_step_fn(args, config, s, data_loader):
     print(f"SCST: CIDEr statistics over {stats.clips} clips, {stats.entries} n-grams in {stats.capacity} slots")
     kw = dict(cider=stats, num_samples=getattr(args, "scst_samples", 5), baseline=getattr(args, "scst_baseline", "mean_others"),
               temperature=getattr(args, "scst_temperature", 1.0))
+    if getattr(args, "scst_shared_prefix", False):
+        kw["training_pass"] = "shared_prefix"
 
     steps = [0]
 
@@ -582,8 +586,11 @@ def get_args(argv=None):
         p.add_argument("--scst_temperature", type=float, default=argparse.SUPPRESS, help="--scst: the sampling temperature (default 1.0)")
         p.add_argument("--scst_stats", type=str, default=argparse.SUPPRESS, metavar="FILE",
                        help="--scst: a saved generation.CiderStats (default: built at start-up from the training set's captions)")
+        p.add_argument("--scst_shared_prefix", action="store_true", default=argparse.SUPPRESS,
+                       help="--scst: the training pass computes every clip's query slots and prompt once and its samples as packed "
+                            "continuations (forward_scst(training_pass='shared_prefix'); that pass applies no decoder dropout)")
     args, config = ft.get_args(argv, extra=extra)
-    given = [k for k in ("scst_samples", "scst_baseline", "scst_temperature", "scst_stats") if hasattr(args, k)]
+    given = [k for k in ("scst_samples", "scst_baseline", "scst_temperature", "scst_stats", "scst_shared_prefix") if hasattr(args, k)]
     if given and not getattr(args, "scst", False):
         raise ValueError(f"--{' / --'.join(given)} need --scst")
     if getattr(args, "scst_samples", 5) < 1 or (getattr(args, "scst_samples", 5) < 2 and getattr(args, "scst_baseline", "mean_others") == "mean_others"):

@@ -263,6 +263,46 @@ int mpv_attn_prefix_packed_fwd(const mpv_attn_prefix_packed_desc* d, mpv_stream_
 int mpv_attn_prefix_packed_layout(const int32_t* cont_len, int n_cont, const int32_t* conts_per_group, int n_groups,
                                   int32_t* seg_start_out, int32_t* group_row_out, int* rows_out, int* max_group_rows_out);
 
+/* The packed attention for TRAINING (self-critical caption training: the N sampled captions of a clip are continuations of one
+ * prefix, which is then computed once).
+ * mpv_attn_prefix_packed_fwd_lse is mpv_attn_prefix_packed_fwd that also stores lse, fp32 [heads][rows]: lse[h][r] = m + log(l) of
+ * row r's ONE softmax over [prefix | own visible keys], on the scaled scores.  o is mpv_attn_prefix_packed_fwd's bit for bit (the
+ * same kernel body: the same tiles in the same order).  The same refusals with the same codes; lse NULL is a null pointer
+ * (MPV_E_ARG), lse not 4-byte aligned MPV_E_ALIGN.  Nothing but o[0 .. rows) and lse[0 .. heads)[0 .. rows) is written. */
+int mpv_attn_prefix_packed_fwd_lse(const mpv_attn_prefix_packed_desc* d, float* lse, mpv_stream_t stream);
+/* The backward.  dO has o's strides, dq / dk / dv have q / k / v's, dpk / dpv have pk / pv's (group, head, row); all bf16.  lse is what
+ * the forward above stored; delta is fp32 scratch [heads][rows] (written, then read).  Per continuation over the keys [its group's
+ * prefix | its own rows], key kr visible to row r iff it is a prefix key or seg_start[r] <= kr <= r:
+ *   P = exp(scale s - lse) in fp32 (a masked pair: exactly 0),   delta = sum_d dO o from the bf16 o given,   dS = P (dO V^T - delta),
+ *   dS rounded to bf16 before the two products it enters, P rounded to bf16 before dV,
+ *   dq = scale dS K,   dk = scale dS^T q,   dv = P^T dO   (fp32 accumulation, one rounding to bf16),
+ * and a group's dpk / dpv are the sums of the prefix keys' dk / dv over ALL rows of the group.  accumulate_prefix == 0: dpk / dpv are
+ * overwritten; 1: they are read and the sum is added in fp32 before the one rounding (the prefix rows' own causal gradient and the
+ * continuations' contribution become one tensor).  No atomics: every output element is written by exactly one workgroup, and two
+ * runs agree bit for bit.  Nothing behind row `rows` is read; nothing but dq / dk / dv[0 .. rows), rows [0, prefix_len) of every group
+ * of dpk / dpv and delta is written; with prefix_len == 0, pk / pv / dpk / dpv may be NULL and are not touched.  group_row and
+ * seg_start are clamped to [0, rows] where an address is formed from them.  A continuation's dq / dk / dv and a group's dpk / dpv
+ * are functions of that group's prefix and rows only.
+ * Refused with a negative code before any launch, in mpv_attn_prefix_packed_fwd's order and wording where they coincide: NULL
+ * pointers; head_dim not 64 or 80; rows, n_groups or heads < 1; prefix_len < 0; max_group_rows outside [1, rows]; rows or prefix_len
+ * >= 2^30, n_groups > 65535 or heads > 65535; rows of any bf16 tensor not 16-byte aligned (strides or pointers), the index arrays,
+ * lse or delta not 4-byte (MPV_E_ALIGN); scale <= 0. */
+typedef struct mpv_attn_prefix_packed_bwd_desc {
+  const void *q, *k, *v, *o, *dO;    /* packed continuation rows */
+  const void *pk, *pv;               /* prefixes */
+  const float* lse;
+  float* delta;
+  void *dq, *dk, *dv;
+  void *dpk, *dpv;
+  const int32_t *seg_start, *group_row;
+  int64_t q_rs, q_hs, k_rs, k_hs, v_rs, v_hs, o_rs, o_hs;
+  int64_t pk_gs, pk_hs, pk_rs, pv_gs, pv_hs, pv_rs;
+  int rows, n_groups, heads, prefix_len, head_dim, max_group_rows;
+  int accumulate_prefix;
+  float scale;
+} mpv_attn_prefix_packed_bwd_desc;
+int mpv_attn_prefix_packed_bwd(const mpv_attn_prefix_packed_bwd_desc* d, mpv_stream_t stream);
+
 /* One decode step's attention for sequences that share a per-group prefix KV cache (lockstep beam search / sampling: the K
  * beams or samples of a clip share the visual prefix and the prompt).  n_seq sequences in groups of group_size consecutive
  * ones: sequence s belongs to group s / group_size (n_groups = ceil(n_seq / group_size); the last group may be short).  Every

@@ -74,6 +74,20 @@ class AttnPrefixPackedDesc(C.Structure):
     ]
 
 
+class AttnPrefixPackedBwdDesc(C.Structure):
+    _fields_ = [
+        ("q", c_void_p), ("k", c_void_p), ("v", c_void_p), ("o", c_void_p), ("dO", c_void_p), ("pk", c_void_p), ("pv", c_void_p),
+        ("lse", c_void_p), ("delta", c_void_p), ("dq", c_void_p), ("dk", c_void_p), ("dv", c_void_p), ("dpk", c_void_p), ("dpv", c_void_p),
+        ("seg_start", c_void_p), ("group_row", c_void_p),
+        ("q_rs", c_int64), ("q_hs", c_int64), ("k_rs", c_int64), ("k_hs", c_int64), ("v_rs", c_int64), ("v_hs", c_int64),
+        ("o_rs", c_int64), ("o_hs", c_int64),
+        ("pk_gs", c_int64), ("pk_hs", c_int64), ("pk_rs", c_int64),
+        ("pv_gs", c_int64), ("pv_hs", c_int64), ("pv_rs", c_int64),
+        ("rows", c_int), ("n_groups", c_int), ("heads", c_int), ("prefix_len", c_int), ("head_dim", c_int), ("max_group_rows", c_int),
+        ("accumulate_prefix", c_int), ("scale", c_float),
+    ]
+
+
 class AttnDecodeSharedDesc(C.Structure):
     _fields_ = [
         ("q", c_void_p), ("k", c_void_p), ("v", c_void_p), ("pk", c_void_p), ("pv", c_void_p), ("o", c_void_p),
@@ -186,6 +200,8 @@ _SIGS = {
     "mpv_temporal_attn_plan_describe": (c_int, [c_int] * 6 + [C.POINTER(AttnPlanInfo)]),
     "mpv_attn_prefix_fwd": (c_int, [C.POINTER(AttnPrefixDesc), c_void_p]),
     "mpv_attn_prefix_packed_fwd": (c_int, [C.POINTER(AttnPrefixPackedDesc), c_void_p]),
+    "mpv_attn_prefix_packed_fwd_lse": (c_int, [C.POINTER(AttnPrefixPackedDesc), c_void_p, c_void_p]),
+    "mpv_attn_prefix_packed_bwd": (c_int, [C.POINTER(AttnPrefixPackedBwdDesc), c_void_p]),
     "mpv_attn_prefix_packed_layout": (c_int, [C.POINTER(C.c_int32), c_int, C.POINTER(C.c_int32), c_int, C.POINTER(C.c_int32),
                                               C.POINTER(C.c_int32), C.POINTER(c_int), C.POINTER(c_int)]),
     "mpv_attn_decode_shared_fwd": (c_int, [C.POINTER(AttnDecodeSharedDesc), c_void_p]),

@@ -170,7 +170,10 @@ class _GenCls(DistributedGPT3_Pretrain):
     def _backward_pipeline(self, tape, g_caption, g_cls):
         Bv, src = tape["Bv"], tape["src"]
         Q, Hh, D = self.num_learnable_token, self.text_width, self.vision_width
-        dq_rows = self.text_decoder.backward_lm(tape["gpt"], g_caption)
+        if tape.get("shared_prefix"):      # forward_scst(training_pass="shared_prefix"): one prefix per clip, nothing to fold
+            dq_rows = self.text_decoder.backward_shared_prefix_lm(tape["gpt"], g_caption)
+        else:
+            dq_rows = self.text_decoder.backward_lm(tape["gpt"], g_caption)
         if self.use_cls:
             n, S, Cp, C = tape["n2"], tape["S2"], tape["Cp"], self.num_classes
             l0, l2 = self.cls_head[0], self.cls_head[2]
@@ -335,10 +338,11 @@ class DistributedGPT3_Caption(_GenCls):
         return self._run(image, text, None, None, None, True)[0]                              # :768-789 returns loss_caption only
 
     SCST_BASELINES = ("mean_others", "greedy")
+    SCST_TRAINING_PASSES = ("per_sequence", "shared_prefix")
     SCST_MAX_OPERAND_BYTES = 0x7FFFFFF0          # mpv_gemm_bf16 refuses an operand of this many bytes or more
 
     def forward_scst(self, image, text, references, *, cider, num_samples=5, baseline="mean_others", temperature=1.0, top_k=None, top_p=None,
-                     seed=None, max_new_tokens=None, termination_id=None, rollouts=None):
+                     seed=None, max_new_tokens=None, termination_id=None, rollouts=None, training_pass="per_sequence"):
         """Self-critical sequence training (not in the reference): one step's loss from the model's OWN sampled
         captions, each weighted by its CIDEr against the clip's references minus a baseline.  text: the prompts as in generate, ONE prompt
         length per call; references[b]: clip b's reference captions, a non-empty list of token lists; cider: the corpus statistics, a
@@ -357,11 +361,18 @@ class DistributedGPT3_Caption(_GenCls):
              prompt's last position on, the weight of a generated position up to and including the terminating token A[b, n] / T with T
              the number of such positions in the call, 0 elsewhere: loss = sum_t w_t CE_t, the weights handed to the CE kernel as they
              are (signed: no normalisation by their sum, which is near zero);
+             training_pass="shared_prefix" (default "per_sequence": the pass above) runs step 5 on a shared prefix instead, as the
+             rollout does: every clip's P = Q + prompt - 1 prefix rows ONCE and its N samples as packed, ragged
+             continuations [last prompt token, s_0 .. s_{T-2}] with targets [s_0 .. s_{T-1}] of its T live positions
+             (text_decoder.forward_shared_prefix_lm; one read of the B * N live counts builds the layout) -- the same targets and the
+             same weights A[b, n] / T on B P + sum T rows instead of B N (Q + width), no _expand and no fold.  That pass applies NO
+             decoder dropout (hidden or attention), whatever the model's mode; the visual tower and the abstractor stay in the model's mode;
           6. backward through _GenClsFn / _backward_pipeline.
         -> (loss, stats): stats = dict(reward, baseline, length, terminated), the means over the B * N samples, read from the device once."""
         o = self._scst_options(SimpleNamespace(text=text, references=references, cider=cider, num_samples=num_samples, baseline=baseline,
                                                temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, max_new_tokens=max_new_tokens,
-                                               termination_id=termination_id, rollouts=rollouts))      # every refusal comes first
+                                               termination_id=termination_id, rollouts=rollouts,
+                                               training_pass=training_pass))                           # every refusal comes first
         holder = {}
         args = (image, o, holder)
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
@@ -376,6 +387,8 @@ class DistributedGPT3_Caption(_GenCls):
         one prompt length), width (the token table's columns), term, seed, the references as host lists"""
         if o.baseline not in self.SCST_BASELINES:
             raise ValueError(f"baseline must be one of {self.SCST_BASELINES} (got {o.baseline!r})")
+        if o.training_pass not in self.SCST_TRAINING_PASSES:
+            raise ValueError(f"training_pass must be one of {self.SCST_TRAINING_PASSES} (got {o.training_pass!r})")
         o.N = int(o.num_samples)
         if o.N < 1:
             raise ValueError(f"num_samples must be at least 1 (got {o.N})")
@@ -414,6 +427,10 @@ class DistributedGPT3_Caption(_GenCls):
         # the loss window's [rows, vocab] logits, bf16 -- must stay under the GEMM entry's 2 GiB operand limit (include/mpv.h)
         cfg = self.text_decoder.config
         rows, wrows = o.B * o.N * (self.num_learnable_token + o.width), o.B * o.N * (o.width - o.pl)
+        if o.training_pass == "shared_prefix":      # this mode's rows: every prefix once, at most the budget per sample
+            P = self.num_learnable_token + o.pl - 1
+            self.text_decoder._shared_prefix_lm_check(P, o.width - o.pl)
+            rows = o.B * P + wrows
         worst = max(rows * cfg.ffn_hidden_size, wrows * cfg.vocab_size, rows * 3 * cfg.hidden_size) * 2
         if worst >= self.SCST_MAX_OPERAND_BYTES:
             raise ValueError(f"one training pass over {o.B} clips x {o.N} samples of {self.num_learnable_token + o.width} positions needs a "
@@ -477,6 +494,16 @@ class DistributedGPT3_Caption(_GenCls):
         ended = is_term.any(dim=1)
         holder["stats"] = torch.stack([r.mean(), (r - adv).mean(), (live.sum(dim=1) - ended.to(torch.int64)).to(torch.float32).mean(),
                                        ended.to(torch.float32).mean()])
+        if o.training_pass == "shared_prefix":
+            # 5. on a shared prefix: ONE read of the live counts; sample (b, n) is the packed continuation b * N + n of group b
+            counts = live.sum(dim=1).tolist()
+            layout = ops.PackedLayout(counts, [N] * B, device=dev)
+            at = torch.tensor([i * (W - pl) + t for i, T_i in enumerate(counts) for t in range(T_i)], dtype=torch.long).to(dev)
+            pick = lambda t: t.reshape(-1)[at].contiguous()
+            out = self.text_decoder.forward_shared_prefix_lm(qf, table.view(B, N, W)[:, 0, :pl - 1].contiguous(), pick(table[:, pl - 1:W - 1]),
+                                                             layout, (pick(gen), pick(weights)), tape["gpt"])
+            tape.update(src=list(range(B)), Bv=B, shared_prefix=True)
+            return (out["loss"], torch.zeros((), dtype=torch.float32, device=dev)), tape
         # 5. sequence s * B + b: the first B rows are the clips' own, what _backward_pipeline's fold expects
         order = lambda t: t.view(B, N, -1).transpose(0, 1).reshape(N * B, -1).contiguous()
         src = list(range(B)) * N

@@ -479,6 +479,136 @@ class DistributedGPT3(nn.Module):
         losses, _ = ops.cross_entropy(logits, labels.contiguous().view(-1), ones, R, V)
         return dict(token_logprob=-losses)
 
+    # -------------------------------------------------------------- training on a shared prefix
+    def _shared_prefix_lm_check(self, P: int, longest: int):
+        """forward_shared_prefix_lm's refusals, before any launch (forward_scst makes them before its rollout)"""
+        cfg = self.config
+        if self.trainable:
+            raise NotImplementedError("the shared-prefix training pass computes no decoder weight gradients: it needs freeze_text_decoder: true")
+        if not FP32_STREAM:
+            raise NotImplementedError("the shared-prefix training pass runs the fp32 residual stream only (MPV_DECODER_STREAM=bf16 is set)")
+        if cfg.kv_channels not in (64, 80):
+            raise NotImplementedError(f"the packed shared-prefix attention is built for head_dim 64 / 80 (got {cfg.kv_channels})")
+        n_pos = self.dist_model.language_model.embedding.position_embeddings.weight.shape[0]
+        if P + longest > n_pos:
+            raise ops._lib.MpvError(f"sequence of {P + longest} positions exceeds max_position_embeddings = {n_pos}")
+
+    def forward_shared_prefix_lm(self, query_features: torch.Tensor, prefix_ids: torch.Tensor, cont_ids: torch.Tensor, layout,
+                                 window_targets: tuple, tape: dict):
+        """The training pass of forward_lm for sequences that share a prefix per group, each prefix computed ONCE: query_features
+        [B*Q, H] and prefix_ids int64 [B, pl-1] (pl-1 may be 0) are the B prefixes [Q query slots | prompt[:-1]] of P = Q + pl - 1 rows;
+        cont_ids int64 [Rc] are the rows of the ragged continuations laid end to end as `layout` (an ops.PackedLayout with its device
+        arrays; group g continues prefix g), packed row r at position P + (r - seg_start[r]).  ONE token stream of Rp + Rc rows, Rp = B P:
+        LayerNorms and the four products of a layer run once on all rows, only the attention is two launches -- ops.attn_fwd (causal)
+        on the prefix block, ops.attn_prefix_packed_fwd_lse on the continuation rows against that layer's prefix K / V.  The loss
+        window is the continuation rows: the top layer's row-wise part, the final LayerNorm, the tied LM head and the CE run on those
+        Rc rows (row map (Rc, R, Rp)); window_targets = (labels int64 [Rc], weights fp32 [Rc]) as in forward_lm.
+        Frozen decoder, fp32 residual stream, head_dim 64 / 80 (anything else raises before any launch).  The pass applies NO decoder
+        dropout, neither hidden nor attention, whatever the module's mode: the packed attention has none, and one prefix cannot carry
+        the N independent masks of its N continuations.  -> dict(loss); backward_shared_prefix_lm(tape, grad_loss)."""
+        cfg = self.config
+        lm = self.dist_model.language_model
+        H, np_, hn, V = cfg.hidden_size, cfg.num_attention_heads, cfg.kv_channels, cfg.vocab_size
+        B, Lp = prefix_ids.shape
+        Q = query_features.shape[0] // B
+        P, Rc = Q + Lp, layout.rows
+        Rp = B * P
+        R = Rp + Rc
+        assert Q >= 1 and layout.n_groups == B and cont_ids.numel() == Rc and window_targets[0].numel() == Rc, \
+            f"{layout.n_groups} groups for {B} prefixes; {cont_ids.numel()} ids / {window_targets[0].numel()} labels for {Rc} packed rows"
+        self._shared_prefix_lm_check(P, max(layout.cont_len))
+        wte, wpe = lm.embedding.word_embeddings.weight, lm.embedding.position_embeddings.weight
+        ids_dev = prefix_ids.contiguous() if Lp > 0 else torch.zeros(1, dtype=torch.long, device=prefix_ids.device)
+        pos_host = [P + i for i in layout.pos_in_cont]
+        pos = (torch.arange(Rc, dtype=torch.int32, device=cont_ids.device) - layout.seg_start) + P
+        h = torch.cat([ops.gpt_embed_fwd(query_features, ids_dev, wte, wpe, B, Q, Lp, H),
+                       ops.gpt_embed_rows_fwd(cont_ids.contiguous(), pos, pos_host, wte, wpe, Rc, H)])
+        st3 = (P * 3 * H, 3 * hn, 3 * H)
+        lay = ops.AttnLayout(st3, st3, st3, (P * H, hn, H))
+        st = ((3 * H, 3 * hn),) * 3 + ((H, hn),)
+        scale = 1.0 / math.sqrt(hn)
+        tm = (Rc, R, Rp)                                      # the continuation rows of the [R, H] stream
+        nl = len(lm.encoder.layers)
+        layers = []
+        stream, pending = h, None
+        for li, layer in enumerate(lm.encoder.layers):
+            att, mlp = layer.self_attention, layer.mlp
+            l1, l2 = layer.input_layernorm, layer.post_attention_layernorm
+            x1, nxt, m1, r1 = ops.ln_stream_fwd(stream, pending, l1.weight, l1.bias, l1.eps, R, H)
+            stream = nxt if nxt is not None else stream
+            h_in = stream
+            qkv = ops.gemm(x1, att.query_key_value.weight, R, 3 * H, H, bias=att.query_key_value.bias, keep_output=True)
+            ctx = torch.empty((R, H), dtype=torch.bfloat16, device=h.device)
+            lse = ops.attn_fwd(qkv, qkv[:, hn:], qkv[:, 2 * hn:], ctx, lay, B, np_, P, P, hn, causal=True, scale=scale)
+            qc = qkv[Rp:]
+            lse_c = ops.attn_prefix_packed_fwd_lse(qc, qc[:, hn:], qc[:, 2 * hn:], qkv[:, hn:], qkv[:, 2 * hn:], ctx[Rp:], st, (st3, st3),
+                                                   layout, np_, P, hn, scale=scale)
+            top = li == nl - 1
+            rm = tm if top else ops.IDENT
+            Rl = Rc if top else R
+            a1 = ops.gemm(ctx, att.dense.weight, Rl, H, H, bias=att.dense.bias, amap=rm)
+            x2, h1, m2, r2 = ops.ln_stream_fwd(stream, a1, l2.weight, l2.bias, l2.eps, Rl, H, hmap=rm, h_rows=R)
+            F4 = mlp.dense_h_to_4h.out_features
+            z = torch.empty((Rl, F4), dtype=torch.bfloat16, device=h.device)
+            g = ops.gemm(x2, mlp.dense_h_to_4h.weight, Rl, F4, H, bias=mlp.dense_h_to_4h.bias, act=ACT_GELU_TANH, preact_out=z, preact_deriv=True)
+            pending = ops.gemm(g, mlp.dense_4h_to_h.weight, Rl, H, F4, bias=mlp.dense_4h_to_h.bias)
+            layers.append(dict(h=h_in, s1=(m1, r1), qkv=qkv, ctx=ctx, lse=lse, lse_c=lse_c, h1=h1, s2=(m2, r2), z=z, rows=tm if top else None))
+            stream = h1
+        fl = lm.encoder.final_layernorm
+        xf, h_last, mf, rf = ops.ln_stream_fwd(stream, pending, fl.weight, fl.bias, fl.eps, Rc, H, hmap=tm, h_rows=R)
+        logits = ops.gemm(xf, wte, Rc, V, H)                      # tied LM head on the continuation rows
+        _, loss = ops.cross_entropy(logits, window_targets[0], window_targets[1], Rc, V, dlogits=logits)
+        tape.update(B=B, Q=Q, L=Lp, P=P, Rp=Rp, Rc=Rc, layers=layers, h_last=h_last, sf=(mf, rf), dlogits=logits, lay=lay, st=st, scale=scale,
+                    layout=layout)
+        return dict(loss=loss)
+
+    def backward_shared_prefix_lm(self, tape: dict, grad_loss: Optional[torch.Tensor] = None):
+        """-> d(query_features) [B*Q, H] of forward_shared_prefix_lm (dgrad only: the decoder is frozen).  Per layer from the top: the
+        row-wise kernels of backward_lm's frozen branch on all rows (the top layer's on the continuation rows: the prefix rows' incoming
+        gradient is exactly zero there, their only gradient arrives through K and V); ops.attn_bwd on the prefix block writes dqkv[:Rp];
+        ops.attn_prefix_packed_bwd (accumulate_prefix) writes dqkv[Rp:] and adds the continuations' share into the K / V parts of
+        dqkv[:Rp]; then the qkv dgrad and LayerNorm 1 on all rows."""
+        cfg = self.config
+        lm = self.dist_model.language_model
+        H, np_, hn, V = cfg.hidden_size, cfg.num_attention_heads, cfg.kv_channels, cfg.vocab_size
+        B, Q, Lp, P, Rp, Rc = tape["B"], tape["Q"], tape["L"], tape["P"], tape["Rp"], tape["Rc"]
+        R = Rp + Rc
+        lay, st, scale, layout = tape["lay"], tape["st"], tape["scale"], tape["layout"]
+        st3 = lay.k
+        tm = (Rc, R, Rp)
+        fl = lm.encoder.final_layernorm
+        dxf = self._dgrad(tape["dlogits"], lm.embedding.word_embeddings.weight, Rc, H, V, alpha_dev=grad_loss)
+        tape["dlogits"] = None
+        dh = torch.empty((R, H), dtype=torch.bfloat16, device=dxf.device)      # only the continuation rows are read (top layer)
+        self._ln_bwd(dxf, tape["h_last"], fl.weight, *tape["sf"], Rc, H, dx=dh, xmap=tm)
+        for li in range(len(lm.encoder.layers) - 1, -1, -1):
+            layer, s = lm.encoder.layers[li], tape["layers"][li]
+            att, mlp = layer.self_attention, layer.mlp
+            F4 = mlp.dense_h_to_4h.out_features
+            if s["rows"] is not None:
+                dz = self._dgrad(dh, mlp.dense_4h_to_h.weight, Rc, F4, H, act_bwd_z=s["z"], act_bwd=ACT_GELU_TANH, z_is_deriv=True, amap=tm)
+                dx2 = self._dgrad(dz, mlp.dense_h_to_4h.weight, Rc, H, F4)
+                dh1, dctx = self._window_zero_pair(R, H, tm, dh.device)       # the prefix rows stay exact zeros
+                self._ln_bwd(dx2, s["h1"], layer.post_attention_layernorm.weight, *s["s2"], Rc, H, dres=dh, dx=dh1, xmap=tm)
+                self._dgrad(dh1, att.dense.weight, Rc, H, H, amap=tm, cmap=tm, out=dctx)
+            else:
+                dz = self._dgrad(dh, mlp.dense_4h_to_h.weight, R, F4, H, act_bwd_z=s["z"], act_bwd=ACT_GELU_TANH, z_is_deriv=True)
+                dx2 = self._dgrad(dz, mlp.dense_h_to_4h.weight, R, H, F4)
+                dh1 = self._ln_bwd(dx2, s["h1"], layer.post_attention_layernorm.weight, *s["s2"], R, H, dres=dh)
+                dctx = self._dgrad(dh1, att.dense.weight, R, H, H)
+            qkv = s["qkv"]
+            dqkv = torch.empty_like(qkv)
+            ops.attn_bwd(qkv, qkv[:, hn:], qkv[:, 2 * hn:], s["ctx"], s["lse"], dctx, dqkv, dqkv[:, hn:], dqkv[:, 2 * hn:], lay,
+                         B, np_, P, P, hn, causal=True, scale=scale)
+            qc, dqc = qkv[Rp:], dqkv[Rp:]
+            ops.attn_prefix_packed_bwd(qc, qc[:, hn:], qc[:, 2 * hn:], qkv[:, hn:], qkv[:, 2 * hn:], s["ctx"][Rp:], s["lse_c"], dctx[Rp:],
+                                       dqc, dqc[:, hn:], dqc[:, 2 * hn:], dqkv[:, hn:], dqkv[:, 2 * hn:], st, (st3, st3), layout, np_, P, hn,
+                                       scale=scale, accumulate_prefix=True)
+            dx1 = self._dgrad(dqkv, att.query_key_value.weight, R, H, 3 * H)
+            dh = self._ln_bwd(dx1, s["h"], layer.input_layernorm.weight, *s["s1"], R, H, dres=dh1)
+            tape["layers"][li] = None
+        return ops.gpt_embed_bwd(dh[:Rp], B, Q, Lp, H)           # the prefix block's rows: the front of forward_lm
+
     def _layers_bf16_stream(self, h, lay, scale, window, layers, seed, p_h, p_a, B, S, R, H, np_, hn, keep_inputs=False):
         """The layer stack with the reference's bf16 residual stream (residual adds in the GEMM epilogues): MPV_DECODER_STREAM=bf16,
         and always for a trainable decoder (keep_inputs: x1 / x2 / gelu(z) stay on the tape for the weight gradients, and the top layer

@@ -331,23 +331,58 @@ class PackedLayout:
             self.seg_start, self.group_row = both[:self.rows], both[self.rows:]
 
 
-def attn_prefix_packed_fwd(q, k, v, pk, pv, o, row_strides, prefix_lay: Tuple[Tuple[int, int, int], Tuple[int, int, int]],
-                           layout: PackedLayout, heads, prefix_len, hd, *, scale=1.0):
-    """Causal attention of the packed, ragged continuations of `layout` (packed row r of q/k/v/o strided (row, head) by row_strides
-    = (q, k, v, o) pairs) against the prefix_len-row prefix of their group (pk/pv strided (group, head, row) by prefix_lay = (k
-    strides, v strides)): query row r sees every prefix key of its group and its own keys seg_start[r] <= kr <= r.
-    include/mpv.h: mpv_attn_prefix_packed_fwd."""
-    _need_cuda(q, k, v, o, pk, pv, layout.seg_start, layout.group_row)
-    d = _lib.AttnPrefixPackedDesc()
-    d.q, d.k, d.v, d.o = q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr()
+def _prefix_packed_desc(d, q, k, v, pk, pv, row_strides, prefix_lay, layout: PackedLayout, heads, prefix_len, hd, scale, *more):
+    """what the packed entries share: the GPU-only check of every tensor and the operand, stride and shape fields of `d`"""
+    _need_cuda(q, k, v, pk, pv, layout.seg_start, layout.group_row, *more)
+    d.q, d.k, d.v = q.data_ptr(), k.data_ptr(), v.data_ptr()
     d.pk, d.pv = (_p(pk), _p(pv)) if prefix_len > 0 else (None, None)      # no prefix: nothing of pk / pv is read
     d.seg_start, d.group_row = _p(layout.seg_start), _p(layout.group_row)
     (d.q_rs, d.q_hs), (d.k_rs, d.k_hs), (d.v_rs, d.v_hs), (d.o_rs, d.o_hs) = row_strides
     (d.pk_gs, d.pk_hs, d.pk_rs), (d.pv_gs, d.pv_hs, d.pv_rs) = prefix_lay
     d.rows, d.n_groups, d.max_group_rows = layout.rows, layout.n_groups, layout.max_group_rows
     d.heads, d.prefix_len, d.head_dim, d.scale = heads, prefix_len, hd, scale
+    return d
+
+
+def attn_prefix_packed_fwd(q, k, v, pk, pv, o, row_strides, prefix_lay: Tuple[Tuple[int, int, int], Tuple[int, int, int]],
+                           layout: PackedLayout, heads, prefix_len, hd, *, scale=1.0):
+    """Causal attention of the packed, ragged continuations of `layout` (packed row r of q/k/v/o strided (row, head) by row_strides
+    = (q, k, v, o) pairs) against the prefix_len-row prefix of their group (pk/pv strided (group, head, row) by prefix_lay = (k
+    strides, v strides)): query row r sees every prefix key of its group and its own keys seg_start[r] <= kr <= r.
+    include/mpv.h: mpv_attn_prefix_packed_fwd."""
+    d = _prefix_packed_desc(_lib.AttnPrefixPackedDesc(), q, k, v, pk, pv, row_strides, prefix_lay, layout, heads, prefix_len, hd, scale, o)
+    d.o = o.data_ptr()
     check(_lib.lib().mpv_attn_prefix_packed_fwd(C.byref(d), _stream()), "mpv_attn_prefix_packed_fwd")
     return o
+
+
+def attn_prefix_packed_fwd_lse(q, k, v, pk, pv, o, row_strides, prefix_lay, layout: PackedLayout, heads, prefix_len, hd, *, scale=1.0,
+                               lse=None):
+    """attn_prefix_packed_fwd for training: the same o bit for bit, and -> lse, fp32 [heads, rows] (contiguous; a new tensor unless
+    given), the statistic of every row's one softmax that attn_prefix_packed_bwd needs.  include/mpv.h: mpv_attn_prefix_packed_fwd_lse."""
+    d = _prefix_packed_desc(_lib.AttnPrefixPackedDesc(), q, k, v, pk, pv, row_strides, prefix_lay, layout, heads, prefix_len, hd, scale, o,
+                            lse)
+    d.o = o.data_ptr()
+    if lse is None:
+        lse = torch.empty((heads, layout.rows), dtype=torch.float32, device=q.device)
+    check(_lib.lib().mpv_attn_prefix_packed_fwd_lse(C.byref(d), lse.data_ptr(), _stream()), "mpv_attn_prefix_packed_fwd_lse")
+    return lse
+
+
+def attn_prefix_packed_bwd(q, k, v, pk, pv, o, lse, do, dq, dk, dv, dpk, dpv, row_strides, prefix_lay, layout: PackedLayout, heads,
+                           prefix_len, hd, *, scale=1.0, accumulate_prefix=False):
+    """The backward of attn_prefix_packed_fwd_lse: dq / dk / dv of the packed rows (strided as q / k / v; do as o) and the groups' dpk /
+    dpv (strided as pk / pv), the sums over all rows of a group; accumulate_prefix adds them to what dpk / dpv hold (fp32 sum, one
+    rounding) instead of overwriting.  No atomics, deterministic.  include/mpv.h: mpv_attn_prefix_packed_bwd."""
+    d = _prefix_packed_desc(_lib.AttnPrefixPackedBwdDesc(), q, k, v, pk, pv, row_strides, prefix_lay, layout, heads, prefix_len, hd, scale,
+                            o, lse, do, dq, dk, dv, dpk, dpv)
+    d.o, d.dO, d.lse = o.data_ptr(), do.data_ptr(), lse.data_ptr()
+    d.dq, d.dk, d.dv = dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
+    d.dpk, d.dpv = (_p(dpk), _p(dpv)) if prefix_len > 0 else (None, None)
+    delta = torch.empty((heads, layout.rows), dtype=torch.float32, device=q.device)
+    d.delta = delta.data_ptr()
+    d.accumulate_prefix = int(bool(accumulate_prefix))
+    check(_lib.lib().mpv_attn_prefix_packed_bwd(C.byref(d), _stream()), "mpv_attn_prefix_packed_bwd")
 
 
 def attn_decode_shared_fwd(q, k, v, pk, pv, o, lay: AttnLayout, prefix_lay: Tuple[Tuple[int, int, int], Tuple[int, int, int]], n_seq,
