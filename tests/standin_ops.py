@@ -3,8 +3,8 @@ ONLY: they let the real host pipelines (vision.py / gpt3.py / pretrain.py: row m
 composed temporal-projection backward) run on CPU inside `-m "not gpu"` tests and be checked against the reference goldens.
 Each function restates the contract of its C entry point in include/mpv.h (same arguments as the ops.py wrapper, bf16
 storage, fp32 arithmetic, bf16 rounding at the points the kernels round) with plain indexing -- no attempt at speed, tiny
-shapes only.  Dropout is not modelled (the counter-hash masks live in the kernels): every stand-in asserts dropout_p == 0, except gemm and the
-LayerNorm entry points, which take their mask from the host replica of the hash in tests/ref_norm.py (_hash_dropout).
+shapes only.  Dropout is not modelled (the counter-hash masks live in the kernels): every stand-in asserts dropout_p == 0, except gemm, the
+LayerNorm entry points and the GPT embedding front, which take their mask from the host replica of the hash in tests/ref_norm.py (_hash_dropout).
 Nothing in the product imports this file; tests install it with `install(monkeypatch)`."""
 import math
 
@@ -54,6 +54,10 @@ GEMM_MUTATION = None
 # forward kernel's documented exception (residual added to the unrounded sum) is modelled.  False everywhere else: the host pipelines'
 # recorded traces and goldens were made without either
 GEMM_STRICT = False
+# tests/test_embed_glue_refs_cpu.py only: vit_embed_assemble_fwd to the letter of the kernel -- pos + temporal rounded to bf16 before the token
+# is added (elementwise.hip, embed_assemble_fwd_kernel).  False everywhere else: the host pipelines' gradient-distance gates were set on the
+# plain three-term fp32 sum
+EMBED_STRICT = False
 
 
 def _act(v, kind):
@@ -329,7 +333,8 @@ def vit_embed_assemble_fwd(patch, cls_token, pos_embed, temporal_embed, B, T, N,
     pos, tem = pos_embed.float().view(N + 1, D), temporal_embed.float().view(-1, D)[:T]
     x = torch.empty((B, T, N + 1, D), dtype=torch.float32)
     x[:, :, 0] = cls_token.float().view(1, 1, D) + pos[0]
-    x[:, :, 1:] = patch.float().view(B, T, N, D) + pos[1:][None, None] + tem[None, :, None]
+    pt = pos[1:][None, None] + tem[None, :, None]
+    x[:, :, 1:] = patch.float().view(B, T, N, D) + (_r16(pt) if EMBED_STRICT else pt)
     return x.view(-1, D).to(BF)
 
 
@@ -339,6 +344,24 @@ def vit_embed_assemble_bwd(dx, dpatch, dcls, dpos, dtemporal, B, T, N, D):
     dcls.view(-1).copy_(d[:, :, 0].sum((0, 1)).to(BF))
     dpos.view(N + 1, D).copy_(d.sum((0, 1)).to(BF))
     dtemporal.view(-1, D)[:T].copy_(d[:, :, 1:].sum((0, 2)).to(BF))
+
+
+def vit_cls_merge_fwd(xt, a, B, T, N1, D, out=None):
+    y = out if out is not None else torch.empty_like(xt)
+    xv, av = xt.float().view(B, T, N1, D), a.float().view(B, T, N1, D)
+    v = xv + av
+    v[:, :, 0] = xv[:, :, 0] + _r16(av[:, :, 0].mean(1, keepdim=True))      # torch.mean rounds to bf16 before the residual add
+    y.view(B, T, N1, D).copy_(v.to(BF))
+    return y
+
+
+def vit_cls_merge_bwd(dy, B, T, N1, D, out=None):
+    da = out if out is not None else torch.empty_like(dy)
+    dv = dy.view(B, T, N1, D)
+    o = da.view(B, T, N1, D)
+    o.copy_(dv)
+    o[:, :, 0] = dv[:, :, 0].float().mean(1, keepdim=True).to(BF).expand(B, T, D)
+    return da
 
 
 def vit_cls_fix_fwd(xt, tap, y, B, T, N1, D):
@@ -371,25 +394,33 @@ def colsum(x, rows, cols, *, out=None, ld=None, rmap=IDENT, accumulate=False):
 
 
 def gpt_embed_fwd(query, ids, wte, wpe, B, Q, L, H, dropout_p=0.0, seed=0, offset=0):
-    assert dropout_p == 0.0
     assert Q + L <= wpe.shape[0]
     h = torch.empty((B, Q + L, H), dtype=torch.float32)
     if Q:
         h[:, :Q] = query.float().view(B, Q, H)
     if L:
-        h[:, Q:] = wte.float()[ids.view(B, L)]
-    h = h + wpe.float()[:Q + L][None]
-    return h.view(-1, H).to(BF)
+        h[:, Q:] = wte.float()[ids.view(-1)[:B * L].view(B, L)]
+    h = (h + wpe.float()[:Q + L][None]).view(-1, H)
+    if dropout_p > 0.0:          # the sum is rounded to bf16 first, then masked and scaled
+        h = _hash_dropout(_r16(h), torch.arange(B * (Q + L)), H, dropout_p, seed, offset)
+    return h.to(BF)
+
+
+def gpt_embed_rows_fwd(ids, pos, pos_host, wte, wpe, rows, H):
+    """out[r] = wte[ids[r]] + wpe[pos[r]], the DEVICE positions clamped to wpe's rows (pos_host is what the wrapper checks)"""
+    assert len(pos_host) == rows and min(pos_host) >= 0 and max(pos_host) < wpe.shape[0]
+    p = pos.view(-1)[:rows].to(torch.int64).clamp(0, wpe.shape[0] - 1)
+    return (wte.float()[ids.view(-1)[:rows]] + wpe.float()[p]).to(BF)
 
 
 def gpt_embed_bwd(dh, B, Q, L, H, dropout_p=0.0, seed=0, offset=0):
-    assert dropout_p == 0.0
-    return dh.view(B, Q + L, H)[:, :Q].reshape(B * Q, H).clone()
+    return gpt_embed_bwd_full(dh, B * (Q + L), H, dropout_p, seed, offset).view(B, Q + L, H)[:, :Q].reshape(B * Q, H).clone()
 
 
 def gpt_embed_bwd_full(dh, rows, H, dropout_p=0.0, seed=0, offset=0):
-    assert dropout_p == 0.0
-    return dh.view(rows, H).clone()
+    if dropout_p == 0.0:
+        return dh.view(rows, H).clone()
+    return _hash_dropout(dh.view(rows, H).float(), torch.arange(rows), H, dropout_p, seed, offset).to(BF)
 
 
 def cross_entropy(logits, labels, weight, rows, vocab, *, ld=None, dlogits=None, want_losses=True):
@@ -426,6 +457,13 @@ def accum_f32(acc, g, first):
 def f32_to_bf16(src, dst):
     dst.copy_(src.to(BF))
     return dst
+
+
+def store_words(dst, words):
+    """dst (int32 / uint32 words) <- the 32-bit patterns of `words`"""
+    assert 1 <= len(words) <= 32
+    w = torch.tensor([v - (1 << 32) if v >= (1 << 31) else v for v in words], dtype=torch.int32)
+    _flat(dst.view(torch.int32))[:len(words)] = w
 
 
 def copy_segments(pairs):
@@ -506,11 +544,13 @@ def gather_rows_ld(src, idx, dst, rows, cols, lds, ldd):
 def logprob_topk(logits, k, add=None, rows=None, vocab=None, ld=None):
     rows = rows if rows is not None else logits.shape[0]
     vocab = vocab if vocab is not None else logits.shape[-1]
-    lp = torch.log_softmax(_rd(logits, torch.arange(rows), ld or vocab, vocab), dim=1)
+    lg = _rd(logits, torch.arange(rows), ld or vocab, vocab)
+    lp = torch.log_softmax(lg, dim=1)
     if add is not None:
         lp = lp + add.float().view(-1)[:rows, None]
-    val, idx = torch.sort(lp, dim=1, descending=True, stable=True)      # ties: the lower index first
-    return val[:, :k].contiguous(), idx[:, :k].contiguous()
+    # the order is that of the LOGITS (ties: the lower index first), also where `add` = -inf makes every value of a row equal
+    idx = torch.sort(lg, dim=1, descending=True, stable=True).indices[:, :k].contiguous()
+    return lp.gather(1, idx).contiguous(), idx
 
 
 def decode_step(self, tokens, query_embeds=None):

@@ -833,9 +833,9 @@ extern "C" int mpv_colsum(const void* in, void* out, int64_t rows, int64_t cols,
 }
 
 extern "C" int mpv_add(const void* a, const void* b, void* out, int64_t n, hipStream_t stream) {
-  MPV_REQUIRE(a && b && out, MPV_E_ARG, "mpv_add: null pointer");
   MPV_REQUIRE(n >= 0 && n % 4 == 0, MPV_E_SHAPE, "mpv_add: n must be a multiple of 4");
-  if (n == 0) return MPV_OK;
+  if (n == 0) return MPV_OK;      // (an empty tensor's address is null: nothing to do comes before the pointer check)
+  MPV_REQUIRE(a && b && out, MPV_E_ARG, "mpv_add: null pointer");
   hipLaunchKernelGGL(add_kernel, dim3(ew_grid(n / 4)), dim3(256), 0, stream, (const bf16*)a, (const bf16*)b, (bf16*)out,
                      (long long)(n / 4));
   return mpv_check_launch("mpv_add");

@@ -235,19 +235,19 @@ __global__ void store_words_kernel(uint32_t* __restrict__ dst, WordArgs a, int n
 }  // namespace
 
 extern "C" int mpv_accum_f32(float* acc, const void* g, int64_t n, int first, hipStream_t stream) {
-  MPV_REQUIRE(acc && g, MPV_E_ARG, "mpv_accum_f32: null pointer");
   MPV_REQUIRE(n >= 0 && n % 8 == 0, MPV_E_SHAPE, "mpv_accum_f32: n must be a multiple of 8");
+  if (n == 0) return MPV_OK;      // (an empty tensor's address is null: nothing to do comes before the pointer checks)
+  MPV_REQUIRE(acc && g, MPV_E_ARG, "mpv_accum_f32: null pointer");
   MPV_REQUIRE((((uintptr_t)acc & 31) | ((uintptr_t)g & 15)) == 0, MPV_E_ALIGN, "mpv_accum_f32: buffers must be 32- / 16-byte aligned");
-  if (n == 0) return MPV_OK;
   hipLaunchKernelGGL(accum_f32_kernel, dim3(stream_grid(n / 8)), dim3(256), 0, stream, acc, (const bf16*)g, (long long)(n / 8), first);
   return mpv_check_launch("mpv_accum_f32");
 }
 
 extern "C" int mpv_f32_to_bf16(const float* src, void* dst, int64_t n, hipStream_t stream) {
-  MPV_REQUIRE(src && dst, MPV_E_ARG, "mpv_f32_to_bf16: null pointer");
   MPV_REQUIRE(n >= 0 && n % 8 == 0, MPV_E_SHAPE, "mpv_f32_to_bf16: n must be a multiple of 8");
-  MPV_REQUIRE((((uintptr_t)src & 31) | ((uintptr_t)dst & 15)) == 0, MPV_E_ALIGN, "mpv_f32_to_bf16: buffers must be 32- / 16-byte aligned");
   if (n == 0) return MPV_OK;
+  MPV_REQUIRE(src && dst, MPV_E_ARG, "mpv_f32_to_bf16: null pointer");
+  MPV_REQUIRE((((uintptr_t)src & 31) | ((uintptr_t)dst & 15)) == 0, MPV_E_ALIGN, "mpv_f32_to_bf16: buffers must be 32- / 16-byte aligned");
   hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(stream_grid(n / 8)), dim3(256), 0, stream, src, (bf16*)dst, (long long)(n / 8));
   return mpv_check_launch("mpv_f32_to_bf16");
 }
@@ -266,7 +266,8 @@ extern "C" int mpv_copy_segments(const void* const* src, void* const* dst, const
     SegArgs a = {};
     const int m = n - base < SEG_MAX ? n - base : SEG_MAX;
     for (int i = 0; i < m; ++i) {
-      MPV_REQUIRE(src[base + i] && dst[base + i] && count[base + i] >= 0 && count[base + i] < (1LL << 31), MPV_E_ARG,
+      // (an empty segment may come with null addresses -- an empty tensor has one; the kernel's loops then run zero times)
+      MPV_REQUIRE(count[base + i] >= 0 && count[base + i] < (1LL << 31) && (count[base + i] == 0 || (src[base + i] && dst[base + i])), MPV_E_ARG,
                   "mpv_copy_segments: bad segment %d", base + i);
       a.src[i] = (const bf16*)src[base + i];
       a.dst[i] = (bf16*)dst[base + i];
