@@ -186,11 +186,12 @@ def _targets(lists, rows, device):
 
 
 @torch.no_grad()
-def evaluation_on_device(model, data_loader, tokenizer, device, config):
+def evaluation_on_device(model, data_loader, tokenizer, device, config, index_fp8=False):
     """-> (ranks_v2t int32 [videos], ranks_t2v int32 [texts]) as numpy arrays: `--eval_on_device`.  The features are those of
     `evaluation` (same towers, same chunking); they go into a text index and a video index and every query is ranked against the
     full gallery on the device (RetrievalIndex.rank) -- no score matrix on the device or the host.  Under a process group each
-    rank ranks its share of the queries and the rank vectors are all-gathered."""
+    rank ranks its share of the queries and the rank vectors are all-gathered.  index_fp8 (`--eval_index_fp8`): the galleries
+    are RetrievalIndex(storage="fp8")."""
     from youku_mplug_amd.retrieval import RetrievalIndex
     module = getattr(model, "module", model)
     module.eval()
@@ -198,16 +199,28 @@ def evaluation_on_device(model, data_loader, tokenizer, device, config):
     ds = data_loader.dataset
     texts = ds.text
     text_index = video_index = None
+    # --eval_index_fp8: the galleries are a second pair of indexes that keep e4m3 codes; the bf16 pair still supplies the queries
+    fp8 = bool(index_fp8)
+    text_gallery = video_gallery = None
     for i in range(0, len(texts), 32):
         text_input = tokenizer(texts[i:i + 32], padding="max_length", truncation=True, max_length=max(64, config["max_length"]),
                                return_tensors="pt").to(device)
         feat = module.extract_text_feature(text_input)
         text_index = text_index or RetrievalIndex(feat.shape[1], device=device)
         text_index.add(feat)
+        if fp8:
+            text_gallery = text_gallery or RetrievalIndex(feat.shape[1], device=device, storage="fp8")
+            text_gallery.add(feat)
     for video, _vid in data_loader:
         feat = module.extract_vision_feature(video.to(device).bfloat16())
         video_index = video_index or RetrievalIndex(feat.shape[1], device=device)
         video_index.add(feat)
+        if fp8:
+            video_gallery = video_gallery or RetrievalIndex(feat.shape[1], device=device, storage="fp8")
+            video_gallery.add(feat)
+    if not fp8:
+        text_gallery, video_gallery = text_index, video_index
+    print(f"index bytes: video {video_gallery.nbytes} ({video_gallery.storage}), text {text_gallery.nbytes} ({text_gallery.storage})")
     world, rank = (dist.get_world_size(), dist.get_rank()) if dist.is_available() and dist.is_initialized() else (1, 0)
 
     def ranks_of(queries, gallery, lists):
@@ -223,8 +236,8 @@ def evaluation_on_device(model, data_loader, tokenizer, device, config):
             out = torch.cat(parts)
         return out[:n].cpu().numpy()
 
-    ranks_v2t = ranks_of(video_index, text_index, ds.vid2txt)
-    ranks_t2v = ranks_of(text_index, video_index, ds.txt2vid)
+    ranks_v2t = ranks_of(video_index, text_gallery, ds.vid2txt)
+    ranks_t2v = ranks_of(text_index, video_gallery, ds.txt2vid)
     print("Evaluation time {}".format(str(datetime.timedelta(seconds=int(time.time() - t0)))))
     return ranks_v2t, ranks_t2v
 
@@ -297,7 +310,8 @@ def main(args, config):
 
     def evaluate(loader, name):
         if getattr(args, "eval_on_device", False):
-            result = recall_from_ranks(*evaluation_on_device(model, loader, tokenizer, device, config))
+            result = recall_from_ranks(*evaluation_on_device(model, loader, tokenizer, device, config,
+                                                              index_fp8=getattr(args, "eval_index_fp8", False)))
         else:
             v2t, t2v = evaluation(model, loader, tokenizer, device, config)
             result = itm_eval(v2t, t2v, loader.dataset.txt2vid, loader.dataset.vid2txt)
@@ -352,8 +366,14 @@ def get_args(argv=None):
                         "instead of building both fp32 score matrices and argsorting them on the host.  The towers emit bf16 "
                         "features, so the default path's .float() copies are exact and both paths score identical inputs; "
                         "ties are ranked by the lower gallery index")
+    p.add_argument("--eval_index_fp8", action="store_true", default=False,
+                   help="with --eval_on_device: rank against galleries kept as e4m3 codes with one scale per row (half the index bytes); "
+                        "the ranks are exactly those of bf16 galleries of the dequantised rows, so the run measures what the rounding "
+                        "does to recall")
     p.add_argument("--synthetic_steps", default=0, type=int, help="run on N synthetic batches per epoch instead of the dataset")
     args, _ = p.parse_known_args(argv)
+    if args.eval_index_fp8 and not args.eval_on_device:
+        p.error("--eval_index_fp8 needs --eval_on_device: only the on-device evaluation searches an index")
     config = yaml.load(open(args.config, "r"), Loader=_ConfigLoader)
     Path(args.output_dir).mkdir(parents=True, exist_ok=True)
     for section in ("optimizer", "schedular"):

@@ -1256,6 +1256,42 @@ int mpv_maxsim_rank(const mpv_maxsim_search_desc* d, const int64_t* target, int 
                     size_t workspace_bytes, mpv_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Searches over an FP8 gallery (opt-in; half the index bytes; csrc/search_common.h ScCodeStage).  The four searches above with
+ * the GALLERY stored as e4m3 codes.  Numeric contract:
+ *   format   OCP e4m3fn codes, one byte per element, and one fp32 scale per gallery ROW (g_scale: ng entries for mpv_sim_*_q8,
+ *            ng * g_group for mpv_maxsim_*_q8, row order) -- what mpv_quantize_rows_e4m3 writes ("FP8 decoder weights" above).
+ *   desc     the descriptors above, unchanged: d->gallery points to the codes, g_rs is counted in CODES, is a multiple of 16 and
+ *            at least dim, and the base pointer is 16-byte aligned (a 16-byte chunk is 16 codes).  Queries stay bf16.
+ *   score    s(row) = g_scale[row] * sum_k q[k] * deq(code[row][k]).  The sum is the bf16-MFMA / fp32 chain the bf16 entry runs on
+ *            that row (the codes become bf16 on the way into the LDS stage, deq is exact; same chunk order, same instruction,
+ *            accumulator zeroed at the same point); the product with the scale is taken in fp32 before any comparison and before
+ *            any max over a group; for top-k d->scale is applied after that, as above.
+ *   equality for scales that are powers of two every output -- values, indices, ranks, for every value of `slices` -- equals, bit
+ *            for bit, the matching bf16 entry called on the bf16 gallery deq(code) * g_scale (a bf16 number: the FP8 index IS a
+ *            bf16 index, kernel error and quantisation error are separate questions).  Domain: a multiplication by a power of
+ *            two commutes with fp32 addition as long as no partial sum is subnormal (or overflows), so the claim holds where the
+ *            partial sums of both chains stay normal or zero.  Rows of mpv_quantize_rows_e4m3 from unit-norm features have
+ *            exponents around -11; their partial sums are nowhere near 2^-126.
+ *   rules    order rule, tie rule, NaN rules and refusal style of the bf16 entries.  The codes 0x7F and 0xFF convert to NaN and
+ *            behave as a NaN bf16 element does there.
+ * Refused (negative code, *_q8_workspace_size 0, before any launch) beyond what the bf16 entries refuse: a null g_scale; a gallery
+ * that is not 16-byte aligned or a g_rs that is not a multiple of 16; for mpv_maxsim_*_q8 a q_group above 1 -- in that direction
+ * the gallery is the LDS-resident side and the index is titles, 512 bytes each at dim 256: out of scope, such indexes stay bf16.
+ * What the rounding to e4m3 does to rankings of TRAINED features has not been measured (no checkpoint or data set exists here). */
+size_t mpv_sim_topk_q8_workspace_size(const mpv_sim_search_desc* d, const float* g_scale);
+int mpv_sim_topk_q8(const mpv_sim_search_desc* d, const float* g_scale, float* vals, int64_t* idx, void* workspace,
+                    size_t workspace_bytes, mpv_stream_t stream);
+size_t mpv_sim_rank_q8_workspace_size(const mpv_sim_search_desc* d, const float* g_scale, int n_targets);
+int mpv_sim_rank_q8(const mpv_sim_search_desc* d, const float* g_scale, const int64_t* target, int n_targets, int32_t* rank,
+                    void* workspace, size_t workspace_bytes, mpv_stream_t stream);
+size_t mpv_maxsim_topk_q8_workspace_size(const mpv_maxsim_search_desc* d, const float* g_scale);
+int mpv_maxsim_topk_q8(const mpv_maxsim_search_desc* d, const float* g_scale, float* vals, int64_t* idx, void* workspace,
+                       size_t workspace_bytes, mpv_stream_t stream);
+size_t mpv_maxsim_rank_q8_workspace_size(const mpv_maxsim_search_desc* d, const float* g_scale, int n_targets);
+int mpv_maxsim_rank_q8(const mpv_maxsim_search_desc* d, const float* g_scale, const int64_t* target, int n_targets, int32_t* rank,
+                       void* workspace, size_t workspace_bytes, mpv_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Optimizer (DeepSpeed FusedAdam + global-norm clip, run_pretrain_distributed_gpt3.py:137;
  * math of optim/adamw.py:66-115; torch.nn.utils.clip_grad_norm_ semantics, utils.py:308).
  * sumsq (fp32 scalar, pre-zeroed) += sum g^2 over n bf16 gradients -- BIT-REPRODUCIBLE since round 6: per-workgroup partial sums in

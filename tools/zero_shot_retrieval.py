@@ -40,8 +40,10 @@ def _entry():
 
 
 @torch.no_grad()
-def build_indexes(model, split, tokenizer, device, max_length):
-    """-> (video index [clips, Q, E], text index [titles, E]) over the split, features extracted batch by batch"""
+def build_indexes(model, split, tokenizer, device, max_length, index_fp8=False):
+    """-> (video index [clips, Q, E], text index [titles, E]) over the split, features extracted batch by batch.  index_fp8: the video
+    index keeps e4m3 codes (half the bytes); the title index stays bf16 -- clips are searched against it with grouped queries, the
+    direction an fp8 index does not serve, and it is 1 / Q of the bytes anyway."""
     from youku_mplug_amd.retrieval import MaxSimIndex
     model.eval()
     texts = split.dataset.text
@@ -53,19 +55,27 @@ def build_indexes(model, split, tokenizer, device, max_length):
         text_index.add(feat)
     for video, _vid in split:
         feat = model.extract_vision_feature(video.to(device).bfloat16())
-        video_index = video_index or MaxSimIndex(feat.shape[2], feat.shape[1], device=device)
+        video_index = video_index or MaxSimIndex(feat.shape[2], feat.shape[1], device=device, storage="fp8" if index_fp8 else "bf16")
         video_index.add(feat)
     return video_index, text_index
 
 
 @torch.no_grad()
-def zero_shot_ranks(model, split, tokenizer, device, max_length):
-    """-> (ranks_v2t int32 [clips], ranks_t2v int32 [titles]) as numpy arrays, from MaxSimIndex.rank (ops.maxsim_rank)"""
+def zero_shot_ranks(model, split, tokenizer, device, max_length, index_fp8=False):
+    """-> (ranks_v2t int32 [clips], ranks_t2v int32 [titles]) as numpy arrays, from MaxSimIndex.rank (ops.maxsim_rank; with index_fp8
+    the title -> clip direction runs ops.maxsim_rank_q8 on the codes, and the clips that query the titles are the index's own
+    dequantised rows, 1024 clips at a time)"""
     entry = _entry()
-    video_index, text_index = build_indexes(model, split, tokenizer, device, max_length)
+    video_index, text_index = build_indexes(model, split, tokenizer, device, max_length, index_fp8)
+    print(f"index bytes: video {video_index.nbytes} ({video_index.storage}), text {text_index.nbytes} ({text_index.storage})")
     ds = split.dataset
     nv, nt = len(video_index), len(text_index)
-    ranks_v2t = text_index.rank(video_index.features, entry._targets(ds.vid2txt, range(nv), device))       # clip -> title: q_group = Q
+    if index_fp8:
+        ranks_v2t = torch.cat([text_index.rank((video_index.codes[i:i + 1024].view(torch.float8_e4m3fn).float()
+                                                * video_index.scales[i:i + 1024, :, None]).to(torch.bfloat16),
+                                               entry._targets(ds.vid2txt, range(i, min(i + 1024, nv)), device)) for i in range(0, nv, 1024)])
+    else:
+        ranks_v2t = text_index.rank(video_index.features, entry._targets(ds.vid2txt, range(nv), device))   # clip -> title: q_group = Q
     ranks_t2v = video_index.rank(text_index.features[:, 0], entry._targets(ds.txt2vid, range(nt), device))   # title -> clip: g_group = Q
     return ranks_v2t.cpu().numpy(), ranks_t2v.cpu().numpy()
 
@@ -115,6 +125,10 @@ def main(argv=None):
     ap.add_argument("--num_workers", type=int, default=4)
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--device", default="cuda")
+    ap.add_argument("--index_fp8", action="store_true",
+                    help="keep the video index as e4m3 codes with one scale per row (half the bytes); the title index stays bf16.  The "
+                         "search results are exactly those of a bf16 index of the dequantised rows; what the rounding does to recall on "
+                         "trained features has not been measured")
     args = ap.parse_args(argv)
     if not args.synthetic and not args.config:
         ap.error("give --config (and --checkpoint), or --synthetic N")
@@ -123,7 +137,7 @@ def main(argv=None):
         model, split, tokenizer, max_length = synthetic_setup(args.synthetic, args.batch_size, device, args.seed)
     else:
         model, split, tokenizer, max_length = real_setup(args, device)
-    result = _entry().recall_from_ranks(*zero_shot_ranks(model, split, tokenizer, device, max_length))
+    result = _entry().recall_from_ranks(*zero_shot_ranks(model, split, tokenizer, device, max_length, args.index_fp8))
     print(json.dumps(result))
     return result
 

@@ -275,6 +275,15 @@ _SIGS = {
     "mpv_maxsim_topk": (c_int, [C.POINTER(MaxSimSearchDesc), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mpv_maxsim_rank_workspace_size": (c_size_t, [C.POINTER(MaxSimSearchDesc), c_int]),
     "mpv_maxsim_rank": (c_int, [C.POINTER(MaxSimSearchDesc), c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # the searches over e4m3 codes: the same descriptors plus g_scale (fp32 per gallery row)
+    "mpv_sim_topk_q8_workspace_size": (c_size_t, [C.POINTER(SimSearchDesc), c_void_p]),
+    "mpv_sim_topk_q8": (c_int, [C.POINTER(SimSearchDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mpv_sim_rank_q8_workspace_size": (c_size_t, [C.POINTER(SimSearchDesc), c_void_p, c_int]),
+    "mpv_sim_rank_q8": (c_int, [C.POINTER(SimSearchDesc), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mpv_maxsim_topk_q8_workspace_size": (c_size_t, [C.POINTER(MaxSimSearchDesc), c_void_p]),
+    "mpv_maxsim_topk_q8": (c_int, [C.POINTER(MaxSimSearchDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mpv_maxsim_rank_q8_workspace_size": (c_size_t, [C.POINTER(MaxSimSearchDesc), c_void_p, c_int]),
+    "mpv_maxsim_rank_q8": (c_int, [C.POINTER(MaxSimSearchDesc), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mpv_grad_sumsq_workspace_size": (c_size_t, []),
     "mpv_grad_sumsq": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mpv_adamw_step": (c_int, [c_void_p] * 5 + [c_int64] + [c_float] * 5 + [c_int, c_float, c_void_p, c_float, c_void_p]),

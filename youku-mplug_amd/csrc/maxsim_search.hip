@@ -31,6 +31,11 @@
 // retrieval_search.hip's kernels for the same reason -- one definition of the tile walk -- and the max is over one element, so
 // mpv_maxsim_* equals mpv_sim_* bit for bit.  The slices are merged by sim_topk_merge_kernel and the ranks finished by
 // sim_rank_finish_kernel (retrieval_search.hip), which both files launch.
+//
+// mpv_maxsim_topk_q8 / mpv_maxsim_rank_q8 (include/mpv.h, "Searches over an FP8 gallery"): the gallery-grouped direction over e4m3
+// codes with one fp32 scale per row -- mxs_gallery_kernel's body and mode 3 of mxs_item_kernel's instantiated on the code stage of
+// search_common.h; the scale multiplies a row's score before the max over the group.  Grouped queries are refused there: the
+// gallery would be the resident side, which is bf16 only.
 #include "search_common.h"
 #include "../../include/mpv.h"
 
@@ -55,13 +60,16 @@ struct MxArgs {
   const int64_t* target;     // rank: [nq][n_t]
   const float* tscore;       // rank: [nq][n_t]
   int* counts;               // rank: [nq][n_t], zeroed
+  const float* s_scale;      // *_q8: S points to e4m3 codes, s_rs counts codes, one scale per streamed row
 };
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // Gallery grouped (or no group at all).  grid (query tiles, slices); wave w of slice s is unit 4 s + w and owns the items
 // unit * per_unit .. + per_unit - 1, i.e. a contiguous run of rows that starts on an item boundary.
-template <int MODE, int KMAX>        // MODE 0: top-k (k <= KMAX), 1: rank counts
-__global__ __launch_bounds__(64 * SC_WAVES) void mxs_gallery_kernel(MxArgs a) {
+// Written once over the streamed side's source type: bf16 rows (mxs_gallery_kernel) or e4m3 codes with row scales
+// (q8_gallery_kernel; search_common.h, ScCodeStage).
+template <int MODE, int KMAX, class Src>        // MODE 0: top-k (k <= KMAX), 1: rank counts
+__device__ __forceinline__ void mxs_gallery_body(const MxArgs& a, const Src S) {
   extern __shared__ __attribute__((aligned(16))) char mx_smem[];
   const int tid = threadIdx.x, lane = tid & 63, l32 = lane & 31, half = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -87,10 +95,10 @@ __global__ __launch_bounds__(64 * SC_WAVES) void mxs_gallery_kernel(MxArgs a) {
   const int nk = (D + SC_KC - 1) / SC_KC;
   const int nsteps = a.tiles * nk;                     // the same for every wave: the barriers below are uniform
   const bf16* rrow = rbuf + l32 * rpitch;
-  ScStage st;
+  typename ScSource<Src>::Stage st;
   long long trow = row_lo;                             // first row of the tile in flight
   auto rows = [&](long long r0) { return [=](int j) -> long long { return r0 + j < row_hi ? r0 + j : -1; }; };
-  sc_stage_load(st, a.S, a.s_rs, 0, D, rows(trow), lane);
+  sc_stage_load(st, S, a.s_rs, 0, D, rows(trow), lane);
   f32x16 acc = {};
   float run = __builtin_nanf("");                      // max over the rows seen so far of the item in progress
   int item = (int)it_lo, pos = 0;                      // that item, and how many of its rows have been seen
@@ -100,13 +108,14 @@ __global__ __launch_bounds__(64 * SC_WAVES) void mxs_gallery_kernel(MxArgs a) {
     __syncthreads();
     if (s + 1 < nsteps) {
       const bool wrap = kc + 1 == nk;
-      sc_stage_load(st, a.S, a.s_rs, wrap ? 0 : (kc + 1) * SC_KC, D, rows(wrap ? trow + SC_TILE : trow), lane);
+      sc_stage_load(st, S, a.s_rs, wrap ? 0 : (kc + 1) * SC_KC, D, rows(wrap ? trow + SC_TILE : trow), lane);
     }
     if (kc == 0) acc = f32x16{};
     const int kleft = D - kc * SC_KC;
     sc_tile_mma(acc, sbuf, rrow + kc * SC_KC, (kleft < SC_KC ? kleft : SC_KC) >> 4, lane);
     if (kc + 1 == nk) {
       // r[j] = score of tile row j: acc[i] of the lane with half h is row 8 (i / 4) + 4 h + i % 4
+      if constexpr (ScSource<Src>::scaled) sc_scale_acc(acc, sbuf, lane);
       float r[32];
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
@@ -204,13 +213,25 @@ __global__ __launch_bounds__(64 * SC_WAVES) void mxs_gallery_kernel(MxArgs a) {
   }
 }
 
+// The bf16 kernels keep the names and template heads the resource gate of the ISA test knows; the instances over codes are named
+// apart (retrieval_search.hip does the same).
+template <int MODE, int KMAX>
+__global__ __launch_bounds__(64 * SC_WAVES) void mxs_gallery_kernel(MxArgs a) {
+  mxs_gallery_body<MODE, KMAX>(a, a.S);
+}
+template <int MODE, int KMAX>
+__global__ __launch_bounds__(64 * SC_WAVES) void q8_gallery_kernel(MxArgs a) {
+  mxs_gallery_body<MODE, KMAX>(a, ScCodes{(const uint8_t*)a.S, a.s_scale});
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // One wave per streamed item.  MODE 0 / 1: top-k / rank counts of query item blockIdx.x * waves + wave over the resident tiles
 // of slice blockIdx.y (grid (ceil(nq / 4), slices), 4 waves).  MODE 2 / 3 (one wave): the target scores of mpv_maxsim_rank.
 //   2: queries grouped -- streamed item = query item blockIdx.x, resident row j = its target title j;  tscore[item][j].
 //   3: gallery grouped -- streamed item = target (blockIdx.y) of query blockIdx.x, resident row 0 = that query; tscore[q][t].
-template <int MODE>
-__global__ __launch_bounds__(64 * SC_WAVES) void mxs_item_kernel(MxArgs a, float* __restrict__ tscore_out) {
+// Over codes only MODE 3 exists (q8_item_kernel): with queries grouped the gallery is the resident side, which stays bf16.
+template <int MODE, class Src>
+__device__ __forceinline__ void mxs_item_body(const MxArgs& a, const Src S, float* __restrict__ tscore_out) {
   extern __shared__ __attribute__((aligned(16))) char mx_smem[];
   const int tid = threadIdx.x, lane = tid & 63, l32 = lane & 31, half = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nthreads = blockDim.x, nwaves = nthreads >> 6;
@@ -255,8 +276,8 @@ __global__ __launch_bounds__(64 * SC_WAVES) void mxs_item_kernel(MxArgs a, float
     } else {
       sc_load_resident(rbuf, a.R, a.r_rs, D, [&](int j) -> long long { return j == 0 ? (long long)blockIdx.x : -1; }, tid, nthreads);
     }
-    ScStage st;
-    sc_stage_load(st, a.S, a.s_rs, 0, D, rows(0), lane);
+    typename ScSource<Src>::Stage st;
+    sc_stage_load(st, S, a.s_rs, 0, D, rows(0), lane);
     f32x16 acc = {};
     float run = __builtin_nanf("");
     int kc = 0, tl = 0;
@@ -265,12 +286,13 @@ __global__ __launch_bounds__(64 * SC_WAVES) void mxs_item_kernel(MxArgs a, float
       __syncthreads();                                 // stage and resident tile visible
       if (s + 1 < nsteps) {
         const bool wrap = kc + 1 == nk;
-        sc_stage_load(st, a.S, a.s_rs, wrap ? 0 : (kc + 1) * SC_KC, D, rows(wrap ? tl + 1 : tl), lane);
+        sc_stage_load(st, S, a.s_rs, wrap ? 0 : (kc + 1) * SC_KC, D, rows(wrap ? tl + 1 : tl), lane);
       }
       if (kc == 0) acc = f32x16{};
       const int kleft = D - kc * SC_KC;
       sc_tile_mma(acc, sbuf, rrow + kc * SC_KC, (kleft < SC_KC ? kleft : SC_KC) >> 4, lane);
       if (kc + 1 == nk) {
+        if constexpr (ScSource<Src>::scaled) sc_scale_acc(acc, sbuf, lane);
 #pragma unroll
         for (int i = 0; i < 16; ++i)
           if (tl * SC_TILE + 8 * (i >> 2) + 4 * half + (i & 3) < G) run = mx_nanmax(run, acc[i]);
@@ -328,13 +350,22 @@ __global__ __launch_bounds__(64 * SC_WAVES) void mxs_item_kernel(MxArgs a, float
     a.ws_idx[o] = lg;
   }
 }
+template <int MODE>
+__global__ __launch_bounds__(64 * SC_WAVES) void mxs_item_kernel(MxArgs a, float* __restrict__ tscore_out) {
+  mxs_item_body<MODE>(a, a.S, tscore_out);
+}
+__global__ __launch_bounds__(64 * SC_WAVES) void q8_item_kernel(MxArgs a, float* __restrict__ tscore_out) {
+  mxs_item_body<3>(a, ScCodes{(const uint8_t*)a.S, a.s_scale}, tscore_out);
+}
 
 struct MxPlan {
   bool by_item;              // queries grouped: mxs_item_kernel
   int slices, per_unit, tiles;
 };
 
-int mx_plan(const mpv_maxsim_search_desc* d, MxPlan* p, const char* what, int topk_k = 0) {
+// `codes`: the gallery is e4m3 codes with the row scales g_scale (the *_q8 entries): sc_check_codes, and no grouped queries
+int mx_plan(const mpv_maxsim_search_desc* d, MxPlan* p, const char* what, int topk_k = 0, bool codes = false,
+            const float* g_scale = nullptr) {
   MPV_REQUIRE(d && d->queries && d->gallery, MPV_E_ARG, "%s: null pointer", what);
   MPV_REQUIRE(d->q_group >= 1 && d->q_group <= MX_MAX_GROUP && d->g_group >= 1 && d->g_group <= MX_MAX_GROUP, MPV_E_SHAPE,
               "%s: groups (%d, %d) must be in [1, %d]", what, d->q_group, d->g_group, MX_MAX_GROUP);
@@ -343,8 +374,12 @@ int mx_plan(const mpv_maxsim_search_desc* d, MxPlan* p, const char* what, int to
   MPV_REQUIRE(d->nq > 0 && d->ng > 0 && d->nq <= 0x7fffffffll / d->q_group && d->ng <= 0x7fffffffll / d->g_group, MPV_E_SHAPE,
               "%s: bad shape nq=%lld x %d ng=%lld x %d (rows per side <= 2^31 - 1)", what, (long long)d->nq, d->q_group, (long long)d->ng,
               d->g_group);
-  const int rc = sc_check_desc(what, d->queries, d->gallery, d->dim, d->q_rs, d->g_rs, d->slices);
+  int rc = sc_check_desc(what, d->queries, d->gallery, d->dim, d->q_rs, d->g_rs, d->slices);
+  if (rc == MPV_OK && codes) rc = sc_check_codes(what, d->gallery, d->g_rs, g_scale);
   if (rc != MPV_OK) return rc;
+  MPV_REQUIRE(!codes || d->q_group == 1, MPV_E_SHAPE,
+              "%s: q_group (%d) must be 1 over a gallery of codes (with grouped queries the gallery is the resident side: bf16 only)", what,
+              d->q_group);
   p->by_item = d->q_group > 1;
   long long s = d->slices;
   if (!p->by_item) {
@@ -379,7 +414,7 @@ int mx_plan(const mpv_maxsim_search_desc* d, MxPlan* p, const char* what, int to
   return MPV_OK;
 }
 
-MxArgs mx_args(const mpv_maxsim_search_desc* d, const MxPlan& p) {
+MxArgs mx_args(const mpv_maxsim_search_desc* d, const MxPlan& p, const float* g_scale) {
   MxArgs a = {};
   if (p.by_item) {
     a.S = (const bf16*)d->queries, a.s_rs = d->q_rs, a.ns = (int)d->nq, a.G = d->q_group;
@@ -393,29 +428,30 @@ MxArgs mx_args(const mpv_maxsim_search_desc* d, const MxPlan& p) {
   a.tiles = p.tiles;
   a.n_items_q = (int)d->nq;
   a.scale = 1.0f;
+  a.s_scale = g_scale;                                // codes are always the streamed side (mx_plan)
   return a;
 }
 
-}  // namespace
-
-extern "C" size_t mpv_maxsim_topk_workspace_size(const mpv_maxsim_search_desc* d) {
+// The entry points, each written once for both gallery types (`codes`: the *_q8 form).  `names`: the entry point, then its stages.
+size_t mx_topk_ws(const char* what, const mpv_maxsim_search_desc* d, bool codes, const float* g_scale) {
   MxPlan p;
-  if (!d || d->k < 1 || d->k > SC_MAX_K || mx_plan(d, &p, "mpv_maxsim_topk_workspace_size", d->k) != MPV_OK) return 0;
+  if (!d || d->k < 1 || d->k > SC_MAX_K || mx_plan(d, &p, what, d->k, codes, g_scale) != MPV_OK) return 0;
   return sc_ws_bytes((size_t)p.slices * (size_t)d->nq * d->k);
 }
 
-extern "C" int mpv_maxsim_topk(const mpv_maxsim_search_desc* d, float* vals, int64_t* idx, void* workspace, size_t workspace_bytes,
-                               hipStream_t stream) {
+int mx_topk(const char* const names[2], const mpv_maxsim_search_desc* d, bool codes, const float* g_scale, float* vals, int64_t* idx,
+            void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  const char* what = names[0];
   MxPlan p;
-  MPV_REQUIRE(d, MPV_E_ARG, "mpv_maxsim_topk: null descriptor");
-  MPV_REQUIRE(d->k >= 1 && d->k <= SC_MAX_K, MPV_E_ARG, "mpv_maxsim_topk: k (%d) must be in [1, %d]", d->k, SC_MAX_K);
-  int rc = mx_plan(d, &p, "mpv_maxsim_topk", d->k);
+  MPV_REQUIRE(d, MPV_E_ARG, "%s: null descriptor", what);
+  MPV_REQUIRE(d->k >= 1 && d->k <= SC_MAX_K, MPV_E_ARG, "%s: k (%d) must be in [1, %d]", what, d->k, SC_MAX_K);
+  int rc = mx_plan(d, &p, what, d->k, codes, g_scale);
   if (rc != MPV_OK) return rc;
-  MPV_REQUIRE(vals && idx && workspace, MPV_E_ARG, "mpv_maxsim_topk: null pointer");
+  MPV_REQUIRE(vals && idx && workspace, MPV_E_ARG, "%s: null pointer", what);
   const size_t n = (size_t)p.slices * (size_t)d->nq * d->k;
-  rc = sc_ws_check("mpv_maxsim_topk", workspace, workspace_bytes, n);
+  rc = sc_ws_check(what, workspace, workspace_bytes, n);
   if (rc != MPV_OK) return rc;
-  MxArgs a = mx_args(d, p);
+  MxArgs a = mx_args(d, p, g_scale);
   a.k = d->k;
   a.scale = d->scale;
   a.ws_val = (float*)workspace;
@@ -428,46 +464,47 @@ extern "C" int mpv_maxsim_topk(const mpv_maxsim_search_desc* d, float* vals, int
   } else {
     const size_t lds = sc_stream_lds(d->dim, SC_WAVES, (size_t)SC_WAVES * d->k * 32 * 8);
     auto kern = d->k <= 4 ? mxs_gallery_kernel<0, 4> : d->k <= 16 ? mxs_gallery_kernel<0, 16> : mxs_gallery_kernel<0, 32>;
+    if (codes) kern = d->k <= 4 ? q8_gallery_kernel<0, 4> : d->k <= 16 ? q8_gallery_kernel<0, 16> : q8_gallery_kernel<0, 32>;
     sc_allow_lds((const void*)kern, lds);
     hipLaunchKernelGGL(kern, dim3((unsigned)((d->nq + SC_TILE - 1) / SC_TILE), (unsigned)p.slices), dim3(64 * SC_WAVES), lds, stream, a);
   }
-  rc = mpv_check_launch("mpv_maxsim_topk");
+  rc = mpv_check_launch(what);
   if (rc != MPV_OK) return rc;
-  return sc_merge_slices("mpv_maxsim_topk (merge)", a.ws_val, a.ws_idx, vals, idx, (int)d->nq, a.k, p.slices, stream);
+  return sc_merge_slices(names[1], a.ws_val, a.ws_idx, vals, idx, (int)d->nq, a.k, p.slices, stream);
 }
 
-extern "C" size_t mpv_maxsim_rank_workspace_size(const mpv_maxsim_search_desc* d, int n_targets) {
+size_t mx_rank_ws(const char* what, const mpv_maxsim_search_desc* d, bool codes, const float* g_scale, int n_targets) {
   MxPlan p;
-  if (!d || n_targets < 1 || n_targets > SC_MAX_T || mx_plan(d, &p, "mpv_maxsim_rank_workspace_size") != MPV_OK) return 0;
+  if (!d || n_targets < 1 || n_targets > SC_MAX_T || mx_plan(d, &p, what, 0, codes, g_scale) != MPV_OK) return 0;
   return sc_ws_bytes((size_t)d->nq * n_targets);
 }
 
-extern "C" int mpv_maxsim_rank(const mpv_maxsim_search_desc* d, const int64_t* target, int n_targets, int32_t* rank, void* workspace,
-                               size_t workspace_bytes, hipStream_t stream) {
+int mx_rank(const char* const names[3], const mpv_maxsim_search_desc* d, bool codes, const float* g_scale, const int64_t* target,
+            int n_targets, int32_t* rank, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  const char* what = names[0];
   MxPlan p;
-  int rc = mx_plan(d, &p, "mpv_maxsim_rank");
+  int rc = mx_plan(d, &p, what, 0, codes, g_scale);
   if (rc != MPV_OK) return rc;
-  MPV_REQUIRE(target && rank && workspace, MPV_E_ARG, "mpv_maxsim_rank: null pointer");
-  MPV_REQUIRE(n_targets >= 1 && n_targets <= SC_MAX_T, MPV_E_ARG, "mpv_maxsim_rank: n_targets (%d) must be in [1, %d]", n_targets,
-              SC_MAX_T);
+  MPV_REQUIRE(target && rank && workspace, MPV_E_ARG, "%s: null pointer", what);
+  MPV_REQUIRE(n_targets >= 1 && n_targets <= SC_MAX_T, MPV_E_ARG, "%s: n_targets (%d) must be in [1, %d]", what, n_targets, SC_MAX_T);
   const size_t n = (size_t)d->nq * n_targets;
-  rc = sc_ws_check("mpv_maxsim_rank", workspace, workspace_bytes, n);
+  rc = sc_ws_check(what, workspace, workspace_bytes, n);
   if (rc != MPV_OK) return rc;
-  MxArgs a = mx_args(d, p);
+  MxArgs a = mx_args(d, p, g_scale);
   a.n_t = n_targets;
   a.target = target;
   float* tscore = (float*)workspace;
   a.tscore = tscore;
   a.counts = (int*)sc_ws_upper(workspace, n);
   if (hipMemsetAsync(a.counts, 0, n * 4, stream) != hipSuccess) {
-    mpv_set_error("mpv_maxsim_rank: hipMemsetAsync failed");
+    mpv_set_error("%s: hipMemsetAsync failed", what);
     return MPV_E_HIP;
   }
   const size_t lds_t = sc_stream_lds(d->dim, 1, 0);
   if (p.by_item) {
     sc_allow_lds((const void*)mxs_item_kernel<2>, lds_t);
     hipLaunchKernelGGL(mxs_item_kernel<2>, dim3((unsigned)d->nq), dim3(64), lds_t, stream, a, tscore);
-    rc = mpv_check_launch("mpv_maxsim_rank (target scores)");
+    rc = mpv_check_launch(names[1]);
     if (rc != MPV_OK) return rc;
     const size_t lds = sc_stream_lds(d->dim, SC_WAVES, 0);
     sc_allow_lds((const void*)mxs_item_kernel<1>, lds);
@@ -476,16 +513,55 @@ extern "C" int mpv_maxsim_rank(const mpv_maxsim_search_desc* d, const int64_t* t
   } else {
     MxArgs ta = a;                                    // one wave per (query, target): the target item's rows against that query
     ta.tiles = (d->g_group + SC_TILE - 1) / SC_TILE;
-    sc_allow_lds((const void*)mxs_item_kernel<3>, lds_t);
-    hipLaunchKernelGGL(mxs_item_kernel<3>, dim3((unsigned)d->nq, (unsigned)n_targets), dim3(64), lds_t, stream, ta, tscore);
-    rc = mpv_check_launch("mpv_maxsim_rank (target scores)");
+    auto tkern = codes ? q8_item_kernel : mxs_item_kernel<3>;
+    sc_allow_lds((const void*)tkern, lds_t);
+    hipLaunchKernelGGL(tkern, dim3((unsigned)d->nq, (unsigned)n_targets), dim3(64), lds_t, stream, ta, tscore);
+    rc = mpv_check_launch(names[1]);
     if (rc != MPV_OK) return rc;
     const size_t lds = sc_stream_lds(d->dim, SC_WAVES, (size_t)SC_TILE * n_targets * 12);
-    sc_allow_lds((const void*)mxs_gallery_kernel<1, 1>, lds);
-    hipLaunchKernelGGL((mxs_gallery_kernel<1, 1>), dim3((unsigned)((d->nq + SC_TILE - 1) / SC_TILE), (unsigned)p.slices), dim3(64 * SC_WAVES),
-                       lds, stream, a);
+    auto kern = codes ? q8_gallery_kernel<1, 1> : mxs_gallery_kernel<1, 1>;
+    sc_allow_lds((const void*)kern, lds);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((d->nq + SC_TILE - 1) / SC_TILE), (unsigned)p.slices), dim3(64 * SC_WAVES), lds, stream, a);
   }
-  rc = mpv_check_launch("mpv_maxsim_rank");
+  rc = mpv_check_launch(what);
   if (rc != MPV_OK) return rc;
-  return sc_rank_finish("mpv_maxsim_rank (finish)", target, tscore, a.counts, rank, (int)d->nq, n_targets, (int)d->ng, stream);
+  return sc_rank_finish(names[2], target, tscore, a.counts, rank, (int)d->nq, n_targets, (int)d->ng, stream);
+}
+
+const char* const MX_TOPK[2] = {"mpv_maxsim_topk", "mpv_maxsim_topk (merge)"};
+const char* const MX_TOPK_Q8[2] = {"mpv_maxsim_topk_q8", "mpv_maxsim_topk_q8 (merge)"};
+const char* const MX_RANK[3] = {"mpv_maxsim_rank", "mpv_maxsim_rank (target scores)", "mpv_maxsim_rank (finish)"};
+const char* const MX_RANK_Q8[3] = {"mpv_maxsim_rank_q8", "mpv_maxsim_rank_q8 (target scores)", "mpv_maxsim_rank_q8 (finish)"};
+
+}  // namespace
+
+extern "C" size_t mpv_maxsim_topk_workspace_size(const mpv_maxsim_search_desc* d) {
+  return mx_topk_ws("mpv_maxsim_topk_workspace_size", d, false, nullptr);
+}
+extern "C" int mpv_maxsim_topk(const mpv_maxsim_search_desc* d, float* vals, int64_t* idx, void* workspace, size_t workspace_bytes,
+                               hipStream_t stream) {
+  return mx_topk(MX_TOPK, d, false, nullptr, vals, idx, workspace, workspace_bytes, stream);
+}
+extern "C" size_t mpv_maxsim_rank_workspace_size(const mpv_maxsim_search_desc* d, int n_targets) {
+  return mx_rank_ws("mpv_maxsim_rank_workspace_size", d, false, nullptr, n_targets);
+}
+extern "C" int mpv_maxsim_rank(const mpv_maxsim_search_desc* d, const int64_t* target, int n_targets, int32_t* rank, void* workspace,
+                               size_t workspace_bytes, hipStream_t stream) {
+  return mx_rank(MX_RANK, d, false, nullptr, target, n_targets, rank, workspace, workspace_bytes, stream);
+}
+
+// ---- the same searches over e4m3 codes, gallery grouped or not (include/mpv.h, "Searches over an FP8 gallery") -------------------
+extern "C" size_t mpv_maxsim_topk_q8_workspace_size(const mpv_maxsim_search_desc* d, const float* g_scale) {
+  return mx_topk_ws("mpv_maxsim_topk_q8_workspace_size", d, true, g_scale);
+}
+extern "C" int mpv_maxsim_topk_q8(const mpv_maxsim_search_desc* d, const float* g_scale, float* vals, int64_t* idx, void* workspace,
+                                  size_t workspace_bytes, hipStream_t stream) {
+  return mx_topk(MX_TOPK_Q8, d, true, g_scale, vals, idx, workspace, workspace_bytes, stream);
+}
+extern "C" size_t mpv_maxsim_rank_q8_workspace_size(const mpv_maxsim_search_desc* d, const float* g_scale, int n_targets) {
+  return mx_rank_ws("mpv_maxsim_rank_q8_workspace_size", d, true, g_scale, n_targets);
+}
+extern "C" int mpv_maxsim_rank_q8(const mpv_maxsim_search_desc* d, const float* g_scale, const int64_t* target, int n_targets,
+                                  int32_t* rank, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  return mx_rank(MX_RANK_Q8, d, true, g_scale, target, n_targets, rank, workspace, workspace_bytes, stream);
 }

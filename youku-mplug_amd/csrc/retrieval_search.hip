@@ -30,6 +30,11 @@
 // of 128 ascending, 16 per MFMA), same instruction, accumulator zeroed at the same point -- and reads the diagonal of the
 // 32 x 32 tile.  An MFMA output element is a function of its A row, its B column and the accumulator only, so the score of
 // target row t is bit-identical to the score the stream computes when it meets row t.
+//
+// mpv_sim_topk_q8 / mpv_sim_rank_q8 (include/mpv.h, "Searches over an FP8 gallery") are the same two kernel bodies instantiated on
+// a gallery of e4m3 codes with one fp32 scale per row (search_common.h, ScCodes / ScCodeStage): the codes become bf16 on the way
+// into the LDS stage, so the accumulators are those of the bf16 kernel on deq(code), and the row scale multiplies a finished score
+// before anything compares it.
 #include "search_common.h"
 #include "../../include/mpv.h"
 
@@ -48,10 +53,13 @@ struct RsArgs {
   const int64_t* target;     // rank: [nq][n_t]
   const float* tscore;       // rank: [nq][n_t]
   int* counts;               // rank: [nq][n_t], zeroed
+  const float* g_scale;      // *_q8: G points to e4m3 codes, g_rs counts codes, one scale per gallery row
 };
 
-template <int MODE, int KMAX>        // MODE 0: top-k (k <= KMAX), 1: rank counts
-__global__ __launch_bounds__(64 * SC_WAVES) void sim_stream_kernel(RsArgs a) {
+// The stream, written once over the gallery's source type: bf16 rows (sim_stream_kernel) or e4m3 codes with row scales
+// (q8_stream_kernel), which differ in how a chunk reaches the LDS stage and in one fp32 multiplication per finished score.
+template <int MODE, int KMAX, class Src>        // MODE 0: top-k (k <= KMAX), 1: rank counts
+__device__ __forceinline__ void sim_stream_body(const RsArgs& a, const Src G) {
   extern __shared__ __attribute__((aligned(16))) char rs_smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l32 = lane & 31, half = lane >> 5;
   const int D = a.D, qpitch = D + 8;
@@ -76,10 +84,10 @@ __global__ __launch_bounds__(64 * SC_WAVES) void sim_stream_kernel(RsArgs a) {
   const int nk = (D + SC_KC - 1) / SC_KC;
   const int nsteps = n_super * nk;
   const bf16* qrow = qbuf + l32 * qpitch;
-  ScStage st;
+  typename ScSource<Src>::Stage st;
   long long row0 = s_row0 + wave * SC_TILE;
   auto rows = [&](long long r0) { return [=](int j) -> long long { return r0 + j < s_end ? r0 + j : -1; }; };
-  if (nsteps > 0) sc_stage_load(st, a.G, a.g_rs, 0, D, rows(row0), lane);
+  if (nsteps > 0) sc_stage_load(st, G, a.g_rs, 0, D, rows(row0), lane);
   f32x16 acc = {};
   int kc = 0;
   for (int s = 0; s < nsteps; ++s) {
@@ -87,7 +95,7 @@ __global__ __launch_bounds__(64 * SC_WAVES) void sim_stream_kernel(RsArgs a) {
     __syncthreads();                                 // stage (and, first time round, queries / targets) visible
     if (s + 1 < nsteps) {                            // next step's rows fly while this one computes
       const bool wrap = kc + 1 == nk;
-      sc_stage_load(st, a.G, a.g_rs, wrap ? 0 : (kc + 1) * SC_KC, D, rows(wrap ? row0 + RS_SUPER : row0), lane);
+      sc_stage_load(st, G, a.g_rs, wrap ? 0 : (kc + 1) * SC_KC, D, rows(wrap ? row0 + RS_SUPER : row0), lane);
     }
     if (kc == 0) acc = f32x16{};
     const int kleft = D - kc * SC_KC;
@@ -96,6 +104,7 @@ __global__ __launch_bounds__(64 * SC_WAVES) void sim_stream_kernel(RsArgs a) {
       // acc[i] is gallery row base + 8 (i / 4) + i % 4.  Unsigned: the last super-tile of a gallery of 2^31 - 1 rows runs
       // past INT_MAX; such rows fail g < uend and are never used as an index.
       const unsigned base = (unsigned)row0 + 4 * half;
+      if constexpr (ScSource<Src>::scaled) sc_scale_acc(acc, gbuf, lane);
       if (MODE == 0) {
         // one insertion site (the list code is 3 ops x KMAX slots): mark the scores that beat the list, then take them one by one
         unsigned m = 0;
@@ -181,9 +190,21 @@ __global__ __launch_bounds__(64 * SC_WAVES) void sim_stream_kernel(RsArgs a) {
   }
 }
 
+// The mangled names of the bf16 kernels are what the resource gate of the ISA test knows them by, so they keep their template
+// heads; the instances over codes are named apart.
+template <int MODE, int KMAX>
+__global__ __launch_bounds__(64 * SC_WAVES) void sim_stream_kernel(RsArgs a) {
+  sim_stream_body<MODE, KMAX>(a, a.G);
+}
+template <int MODE, int KMAX>
+__global__ __launch_bounds__(64 * SC_WAVES) void q8_stream_kernel(RsArgs a) {
+  sim_stream_body<MODE, KMAX>(a, ScCodes{(const uint8_t*)a.G, a.g_scale});
+}
+
 // Scores of the target rows, through the stream's staging and MFMA functions: one wave = 32 queries x target slot t, tile row j
 // is the target row of query j, the score is the tile's diagonal.
-__global__ __launch_bounds__(64) void sim_target_kernel(RsArgs a, float* __restrict__ tscore) {
+template <class Src>
+__device__ __forceinline__ void sim_target_body(const RsArgs& a, const Src G, float* __restrict__ tscore) {
   extern __shared__ __attribute__((aligned(16))) char rs_smem[];
   const int lane = threadIdx.x, l32 = lane & 31, half = lane >> 5;
   const int D = a.D, qpitch = D + 8;
@@ -198,9 +219,9 @@ __global__ __launch_bounds__(64) void sim_target_kernel(RsArgs a, float* __restr
   };
   const int nk = (D + SC_KC - 1) / SC_KC;
   f32x16 acc = {};
-  ScStage st;
+  typename ScSource<Src>::Stage st;
   for (int kc = 0; kc < nk; ++kc) {
-    sc_stage_load(st, a.G, a.g_rs, kc * SC_KC, D, rows, lane);
+    sc_stage_load(st, G, a.g_rs, kc * SC_KC, D, rows, lane);
     __syncthreads();                                 // the previous chunk has been consumed
     sc_stage_store(st, gbuf, lane);
     __syncthreads();
@@ -212,7 +233,12 @@ __global__ __launch_bounds__(64) void sim_target_kernel(RsArgs a, float* __restr
   float v = 0.f;
 #pragma unroll
   for (int i = 0; i < 16; ++i) v = i == want ? acc[i] : v;
+  if constexpr (ScSource<Src>::scaled) v *= sc_row_scale(gbuf, l32);
   if (half == ((l32 >> 2) & 1) && q0 + l32 < a.nq) tscore[(long long)(q0 + l32) * a.n_t + t] = v;
+}
+__global__ __launch_bounds__(64) void sim_target_kernel(RsArgs a, float* __restrict__ tscore) { sim_target_body(a, a.G, tscore); }
+__global__ __launch_bounds__(64) void q8_target_kernel(RsArgs a, float* __restrict__ tscore) {
+  sim_target_body(a, ScCodes{(const uint8_t*)a.G, a.g_scale}, tscore);
 }
 
 // One workgroup per query: k rounds; round j writes the best workspace entry that the entry written in round j - 1 beats.  The
@@ -306,11 +332,13 @@ struct RsPlan {
   int qtiles, slices, per_slice;
 };
 
-int rs_plan(const mpv_sim_search_desc* d, RsPlan* p, const char* what, int topk_k = 0) {
+// `codes`: the gallery is e4m3 codes with the row scales g_scale (the *_q8 entries), which adds sc_check_codes to the checks
+int rs_plan(const mpv_sim_search_desc* d, RsPlan* p, const char* what, int topk_k = 0, bool codes = false, const float* g_scale = nullptr) {
   MPV_REQUIRE(d && d->queries && d->gallery, MPV_E_ARG, "%s: null pointer", what);
   MPV_REQUIRE(d->nq > 0 && d->ng > 0 && d->nq <= 65535ll * SC_TILE /* grid.y */ && d->ng <= 0x7fffffffll, MPV_E_SHAPE,
               "%s: bad shape nq=%lld ng=%lld", what, (long long)d->nq, (long long)d->ng);
-  const int rc = sc_check_desc(what, d->queries, d->gallery, d->dim, d->q_rs, d->g_rs, d->slices);
+  int rc = sc_check_desc(what, d->queries, d->gallery, d->dim, d->q_rs, d->g_rs, d->slices);
+  if (rc == MPV_OK && codes) rc = sc_check_codes(what, d->gallery, d->g_rs, g_scale);
   if (rc != MPV_OK) return rc;
   const long long supers = (d->ng + RS_SUPER - 1) / RS_SUPER;
   p->qtiles = (int)((d->nq + SC_TILE - 1) / SC_TILE);
@@ -331,7 +359,7 @@ int rs_plan(const mpv_sim_search_desc* d, RsPlan* p, const char* what, int topk_
   return MPV_OK;
 }
 
-RsArgs rs_args(const mpv_sim_search_desc* d, const RsPlan& p) {
+RsArgs rs_args(const mpv_sim_search_desc* d, const RsPlan& p, const float* g_scale) {
   RsArgs a = {};
   a.Q = (const bf16*)d->queries;
   a.G = (const bf16*)d->gallery;
@@ -342,8 +370,85 @@ RsArgs rs_args(const mpv_sim_search_desc* d, const RsPlan& p) {
   a.D = d->dim;
   a.per_slice = p.per_slice;
   a.scale = 1.0f;
+  a.g_scale = g_scale;
   return a;
 }
+
+// The entry points, each written once for both gallery types (`codes`: the *_q8 form).  `names`: the entry point, then its stages.
+size_t rs_topk_ws(const char* what, const mpv_sim_search_desc* d, bool codes, const float* g_scale) {
+  RsPlan p;
+  if (!d || d->k < 1 || d->k > SC_MAX_K || rs_plan(d, &p, what, d->k, codes, g_scale) != MPV_OK) return 0;
+  return sc_ws_bytes((size_t)p.slices * (size_t)d->nq * d->k);
+}
+
+int rs_topk(const char* const names[2], const mpv_sim_search_desc* d, bool codes, const float* g_scale, float* vals, int64_t* idx,
+            void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  const char* what = names[0];
+  RsPlan p;
+  MPV_REQUIRE(d, MPV_E_ARG, "%s: null descriptor", what);
+  MPV_REQUIRE(d->k >= 1 && d->k <= SC_MAX_K, MPV_E_ARG, "%s: k (%d) must be in [1, %d]", what, d->k, SC_MAX_K);
+  int rc = rs_plan(d, &p, what, d->k, codes, g_scale);
+  if (rc != MPV_OK) return rc;
+  MPV_REQUIRE(vals && idx && workspace, MPV_E_ARG, "%s: null pointer", what);
+  const size_t n = (size_t)p.slices * (size_t)d->nq * d->k;
+  rc = sc_ws_check(what, workspace, workspace_bytes, n);
+  if (rc != MPV_OK) return rc;
+  RsArgs a = rs_args(d, p, g_scale);
+  a.k = d->k;
+  a.scale = d->scale;
+  a.ws_val = (float*)workspace;
+  a.ws_idx = (int*)sc_ws_upper(workspace, n);
+  const size_t lds = sc_stream_lds(d->dim, SC_WAVES, (size_t)SC_WAVES * d->k * 32 * 8);
+  auto kern = d->k <= 4 ? sim_stream_kernel<0, 4> : d->k <= 16 ? sim_stream_kernel<0, 16> : sim_stream_kernel<0, 32>;
+  if (codes) kern = d->k <= 4 ? q8_stream_kernel<0, 4> : d->k <= 16 ? q8_stream_kernel<0, 16> : q8_stream_kernel<0, 32>;
+  sc_allow_lds((const void*)kern, lds);
+  hipLaunchKernelGGL(kern, dim3((unsigned)p.slices, (unsigned)p.qtiles), dim3(64 * SC_WAVES), lds, stream, a);
+  rc = mpv_check_launch(what);
+  if (rc != MPV_OK) return rc;
+  return sc_merge_slices(names[1], a.ws_val, a.ws_idx, vals, idx, a.nq, a.k, p.slices, stream);
+}
+
+int rs_rank(const char* const names[3], const mpv_sim_search_desc* d, bool codes, const float* g_scale, const int64_t* target,
+            int n_targets, int32_t* rank, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  const char* what = names[0];
+  RsPlan p;
+  int rc = rs_plan(d, &p, what, 0, codes, g_scale);
+  if (rc != MPV_OK) return rc;
+  MPV_REQUIRE(target && rank && workspace, MPV_E_ARG, "%s: null pointer", what);
+  MPV_REQUIRE(n_targets >= 1 && n_targets <= SC_MAX_T, MPV_E_ARG, "%s: n_targets (%d) must be in [1, %d]", what, n_targets, SC_MAX_T);
+  const size_t n = (size_t)d->nq * n_targets;
+  rc = sc_ws_check(what, workspace, workspace_bytes, n);
+  if (rc != MPV_OK) return rc;
+  RsArgs a = rs_args(d, p, g_scale);
+  a.n_t = n_targets;
+  a.target = target;
+  float* tscore = (float*)workspace;
+  a.tscore = tscore;
+  a.counts = (int*)sc_ws_upper(workspace, n);
+  if (hipMemsetAsync(a.counts, 0, n * 4, stream) != hipSuccess) {
+    mpv_set_error("%s: hipMemsetAsync failed", what);
+    return MPV_E_HIP;
+  }
+  const size_t lds_t = sc_stream_lds(d->dim, 1, 0);
+  auto tkern = codes ? q8_target_kernel : sim_target_kernel;
+  sc_allow_lds((const void*)tkern, lds_t);
+  hipLaunchKernelGGL(tkern, dim3((unsigned)n_targets, (unsigned)p.qtiles), dim3(64), lds_t, stream, a, tscore);
+  rc = mpv_check_launch(names[1]);
+  if (rc != MPV_OK) return rc;
+  const size_t lds = sc_stream_lds(d->dim, SC_WAVES, (size_t)SC_TILE * n_targets * 12);
+  auto kern = codes ? q8_stream_kernel<1, 1> : sim_stream_kernel<1, 1>;
+  sc_allow_lds((const void*)kern, lds);
+  hipLaunchKernelGGL(kern, dim3((unsigned)p.slices, (unsigned)p.qtiles), dim3(64 * SC_WAVES), lds, stream, a);
+  rc = mpv_check_launch(what);
+  if (rc != MPV_OK) return rc;
+  // no target scores: a target whose score is NaN still counts as a target here (mpv_maxsim_rank skips it)
+  return sc_rank_finish(names[2], target, nullptr, a.counts, rank, a.nq, n_targets, a.ng, stream);
+}
+
+const char* const RS_TOPK[2] = {"mpv_sim_topk", "mpv_sim_topk (merge)"};
+const char* const RS_TOPK_Q8[2] = {"mpv_sim_topk_q8", "mpv_sim_topk_q8 (merge)"};
+const char* const RS_RANK[3] = {"mpv_sim_rank", "mpv_sim_rank (target scores)", "mpv_sim_rank (finish)"};
+const char* const RS_RANK_Q8[3] = {"mpv_sim_rank_q8", "mpv_sim_rank_q8 (target scores)", "mpv_sim_rank_q8 (finish)"};
 
 }  // namespace
 
@@ -362,71 +467,35 @@ int sc_rank_finish(const char* what, const int64_t* target, const float* tscore,
 }
 
 extern "C" size_t mpv_sim_topk_workspace_size(const mpv_sim_search_desc* d) {
-  RsPlan p;
-  if (!d || d->k < 1 || d->k > SC_MAX_K || rs_plan(d, &p, "mpv_sim_topk_workspace_size", d->k) != MPV_OK) return 0;
-  return sc_ws_bytes((size_t)p.slices * (size_t)d->nq * d->k);
+  return rs_topk_ws("mpv_sim_topk_workspace_size", d, false, nullptr);
 }
-
 extern "C" int mpv_sim_topk(const mpv_sim_search_desc* d, float* vals, int64_t* idx, void* workspace, size_t workspace_bytes,
                             hipStream_t stream) {
-  RsPlan p;
-  MPV_REQUIRE(d, MPV_E_ARG, "mpv_sim_topk: null descriptor");
-  MPV_REQUIRE(d->k >= 1 && d->k <= SC_MAX_K, MPV_E_ARG, "mpv_sim_topk: k (%d) must be in [1, %d]", d->k, SC_MAX_K);
-  int rc = rs_plan(d, &p, "mpv_sim_topk", d->k);
-  if (rc != MPV_OK) return rc;
-  MPV_REQUIRE(vals && idx && workspace, MPV_E_ARG, "mpv_sim_topk: null pointer");
-  const size_t n = (size_t)p.slices * (size_t)d->nq * d->k;
-  rc = sc_ws_check("mpv_sim_topk", workspace, workspace_bytes, n);
-  if (rc != MPV_OK) return rc;
-  RsArgs a = rs_args(d, p);
-  a.k = d->k;
-  a.scale = d->scale;
-  a.ws_val = (float*)workspace;
-  a.ws_idx = (int*)sc_ws_upper(workspace, n);
-  const size_t lds = sc_stream_lds(d->dim, SC_WAVES, (size_t)SC_WAVES * d->k * 32 * 8);
-  auto kern = d->k <= 4 ? sim_stream_kernel<0, 4> : d->k <= 16 ? sim_stream_kernel<0, 16> : sim_stream_kernel<0, 32>;
-  sc_allow_lds((const void*)kern, lds);
-  hipLaunchKernelGGL(kern, dim3((unsigned)p.slices, (unsigned)p.qtiles), dim3(64 * SC_WAVES), lds, stream, a);
-  rc = mpv_check_launch("mpv_sim_topk");
-  if (rc != MPV_OK) return rc;
-  return sc_merge_slices("mpv_sim_topk (merge)", a.ws_val, a.ws_idx, vals, idx, a.nq, a.k, p.slices, stream);
+  return rs_topk(RS_TOPK, d, false, nullptr, vals, idx, workspace, workspace_bytes, stream);
 }
-
 extern "C" size_t mpv_sim_rank_workspace_size(const mpv_sim_search_desc* d, int n_targets) {
   if (!d || d->nq <= 0 || n_targets < 1 || n_targets > SC_MAX_T) return 0;
   return sc_ws_bytes((size_t)d->nq * n_targets);
 }
-
 extern "C" int mpv_sim_rank(const mpv_sim_search_desc* d, const int64_t* target, int n_targets, int32_t* rank, void* workspace,
                             size_t workspace_bytes, hipStream_t stream) {
-  RsPlan p;
-  int rc = rs_plan(d, &p, "mpv_sim_rank");
-  if (rc != MPV_OK) return rc;
-  MPV_REQUIRE(target && rank && workspace, MPV_E_ARG, "mpv_sim_rank: null pointer");
-  MPV_REQUIRE(n_targets >= 1 && n_targets <= SC_MAX_T, MPV_E_ARG, "mpv_sim_rank: n_targets (%d) must be in [1, %d]", n_targets, SC_MAX_T);
-  const size_t n = (size_t)d->nq * n_targets;
-  rc = sc_ws_check("mpv_sim_rank", workspace, workspace_bytes, n);
-  if (rc != MPV_OK) return rc;
-  RsArgs a = rs_args(d, p);
-  a.n_t = n_targets;
-  a.target = target;
-  float* tscore = (float*)workspace;
-  a.tscore = tscore;
-  a.counts = (int*)sc_ws_upper(workspace, n);
-  if (hipMemsetAsync(a.counts, 0, n * 4, stream) != hipSuccess) {
-    mpv_set_error("mpv_sim_rank: hipMemsetAsync failed");
-    return MPV_E_HIP;
-  }
-  const size_t lds_t = sc_stream_lds(d->dim, 1, 0);
-  sc_allow_lds((const void*)sim_target_kernel, lds_t);
-  hipLaunchKernelGGL(sim_target_kernel, dim3((unsigned)n_targets, (unsigned)p.qtiles), dim3(64), lds_t, stream, a, tscore);
-  rc = mpv_check_launch("mpv_sim_rank (target scores)");
-  if (rc != MPV_OK) return rc;
-  const size_t lds = sc_stream_lds(d->dim, SC_WAVES, (size_t)SC_TILE * n_targets * 12);
-  sc_allow_lds((const void*)sim_stream_kernel<1, 1>, lds);
-  hipLaunchKernelGGL((sim_stream_kernel<1, 1>), dim3((unsigned)p.slices, (unsigned)p.qtiles), dim3(64 * SC_WAVES), lds, stream, a);
-  rc = mpv_check_launch("mpv_sim_rank");
-  if (rc != MPV_OK) return rc;
-  // no target scores: a target whose score is NaN still counts as a target here (mpv_maxsim_rank skips it)
-  return sc_rank_finish("mpv_sim_rank (finish)", target, nullptr, a.counts, rank, a.nq, n_targets, a.ng, stream);
+  return rs_rank(RS_RANK, d, false, nullptr, target, n_targets, rank, workspace, workspace_bytes, stream);
+}
+
+// ---- the same searches over e4m3 codes (include/mpv.h, "Searches over an FP8 gallery") ------------------------------------------
+extern "C" size_t mpv_sim_topk_q8_workspace_size(const mpv_sim_search_desc* d, const float* g_scale) {
+  return rs_topk_ws("mpv_sim_topk_q8_workspace_size", d, true, g_scale);
+}
+extern "C" int mpv_sim_topk_q8(const mpv_sim_search_desc* d, const float* g_scale, float* vals, int64_t* idx, void* workspace,
+                               size_t workspace_bytes, hipStream_t stream) {
+  return rs_topk(RS_TOPK_Q8, d, true, g_scale, vals, idx, workspace, workspace_bytes, stream);
+}
+extern "C" size_t mpv_sim_rank_q8_workspace_size(const mpv_sim_search_desc* d, const float* g_scale, int n_targets) {
+  RsPlan p;                                           // a descriptor the call would refuse: 0
+  if (n_targets < 1 || n_targets > SC_MAX_T || rs_plan(d, &p, "mpv_sim_rank_q8_workspace_size", 0, true, g_scale) != MPV_OK) return 0;
+  return sc_ws_bytes((size_t)d->nq * n_targets);
+}
+extern "C" int mpv_sim_rank_q8(const mpv_sim_search_desc* d, const float* g_scale, const int64_t* target, int n_targets, int32_t* rank,
+                               void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  return rs_rank(RS_RANK_Q8, d, true, g_scale, target, n_targets, rank, workspace, workspace_bytes, stream);
 }

@@ -7,6 +7,7 @@
 // rest on.  The host-side checks live once in search_common.hip, the slice merge and rank finish kernels in retrieval_search.hip.
 #pragma once
 #include "mpv_common.h"
+#include "fp8_deq.h"
 
 namespace {
 
@@ -46,6 +47,67 @@ __device__ __forceinline__ void sc_stage_store(const ScStage& st, bf16* buf, int
     const int u = j * 64 + lane;
     *(bf16x8*)(buf + (u >> 4) * SC_PITCH + (u & 15) * 8) = st.r[j];
   }
+}
+// ---- the streamed side as e4m3fn codes (the *_q8 entries; include/mpv.h, "Searches over an FP8 gallery") ----------------------
+// Only the way INTO the LDS stage differs: a lane loads 16-byte chunks of 16 codes (a 32 x 128 chunk is 4 units per lane, not 8)
+// and turns them into bf16 with the exact deq_pair on the way to the stage, so the stage holds what ScStage would have put there
+// for the bf16 gallery deq(code) -- same layout, same sc_tile_mma, bit-identical accumulators.  The fp32 scale of tile row j
+// travels with the chunk (lane j loads it) and is parked in the 16 spare bytes that SC_PITCH leaves behind row j's 128 elements,
+// which neither stage store nor sc_tile_mma touches: it is read back when the tile's scores are finished, after the register
+// stage has already moved on to the next tile.
+struct ScCodes {
+  const uint8_t* c;          // codes, row stride counted in codes (a multiple of 16)
+  const float* scale;        // one per row
+};
+struct ScCodeStage {
+  i32x4 r[SC_UNITS / 2];
+  float scale;               // of tile row lane & 31
+};
+template <class RowFn>
+__device__ __forceinline__ void sc_stage_load(ScCodeStage& st, ScCodes S, long long s_rs, int k0, int D, RowFn row_of, int lane) {
+#pragma unroll
+  for (int j = 0; j < SC_UNITS / 2; ++j) {
+    const int u = j * 64 + lane, row = u >> 3, k = k0 + (u & 7) * 16;
+    const long long gr = row_of(row);
+    i32x4 v = {};                                    // code 0 is +0.0
+    if (gr >= 0 && k < D) v = *(const i32x4*)(S.c + gr * s_rs + k);
+    st.r[j] = v;
+  }
+  const long long sr = row_of(lane & 31);
+  st.scale = sr >= 0 ? S.scale[sr] : 1.f;
+}
+__device__ __forceinline__ void sc_stage_store(const ScCodeStage& st, bf16* buf, int lane) {
+#pragma unroll
+  for (int j = 0; j < SC_UNITS / 2; ++j) {
+    const int u = j * 64 + lane;
+    Frag lo, hi;
+    deq_chunk(st.r[j], lo, hi);
+    bf16* p = buf + (u >> 3) * SC_PITCH + (u & 7) * 16;
+    *(bf16x8*)p = lo.b;
+    *(bf16x8*)(p + 8) = hi.b;
+  }
+  if (lane < SC_TILE) *(float*)(buf + lane * SC_PITCH + SC_KC) = st.scale;
+}
+// what a kernel stages a source through, and whether its scores carry a row scale
+template <class Src>
+struct ScSource;
+template <>
+struct ScSource<const bf16*> {
+  using Stage = ScStage;
+  static constexpr bool scaled = false;
+};
+template <>
+struct ScSource<ScCodes> {
+  using Stage = ScCodeStage;
+  static constexpr bool scaled = true;
+};
+// the scale parked with staged tile row `row`
+__device__ __forceinline__ float sc_row_scale(const bf16* sbuf, int row) { return *(const float*)(sbuf + row * SC_PITCH + SC_KC); }
+// acc[i] *= the scale of its row (sc_tile_mma below: row 8 (i / 4) + 4 (lane / 32) + i % 4), in fp32: the first thing a kernel
+// does with a finished tile of codes, before any comparison or max sees a score
+__device__ __forceinline__ void sc_scale_acc(f32x16& acc, const bf16* sbuf, int lane) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc[i] *= sc_row_scale(sbuf, 8 * (i >> 2) + 4 * (lane >> 5) + (i & 3));
 }
 // acc[i] += <staged row 8 (i / 4) + 4 (lane / 32) + i % 4, resident row lane & 31> over `ksteps` 16-wide steps
 __device__ __forceinline__ void sc_tile_mma(f32x16& acc, const bf16* sbuf, const bf16* rrow, int ksteps, int lane) {
@@ -139,6 +201,8 @@ __device__ __forceinline__ void sc_rank_flush(const int* cnt, int* counts, int q
 // dim, row strides, operand alignment and slice count of a search descriptor (`what` names the entry point in the error text)
 SC_HIDDEN int sc_check_desc(const char* what, const void* queries, const void* gallery, int dim, long long q_rs, long long g_rs,
                             int slices);
+// what a gallery of e4m3 codes adds to that: the scales exist, g_rs (in codes) is a multiple of 16, the base is 16-byte aligned
+SC_HIDDEN int sc_check_codes(const char* what, const void* gallery, long long g_rs, const float* g_scale);
 // The workspace of every entry point is two arrays of n 4-byte entries, each padded to 256 bytes.
 SC_HIDDEN size_t sc_ws_bytes(size_t n);
 SC_HIDDEN int sc_ws_check(const char* what, const void* ws, size_t ws_bytes, size_t n);      // size and alignment

@@ -18,6 +18,13 @@ int sc_check_desc(const char* what, const void* queries, const void* gallery, in
   return MPV_OK;
 }
 
+int sc_check_codes(const char* what, const void* gallery, long long g_rs, const float* g_scale) {
+  MPV_REQUIRE(g_scale, MPV_E_ARG, "%s: null g_scale", what);
+  MPV_REQUIRE(g_rs % 16 == 0 && ((uintptr_t)gallery & 15) == 0, MPV_E_ALIGN,
+              "%s: a gallery of codes must be 16-byte aligned with a row stride (%lld) that is a multiple of 16", what, g_rs);
+  return MPV_OK;
+}
+
 size_t sc_ws_bytes(size_t n) { return 2 * sc_align(n * 4); }
 
 int sc_ws_check(const char* what, const void* ws, size_t ws_bytes, size_t n) {

@@ -1294,12 +1294,13 @@ def smoothed_ce(sim, target, eps, scale, rows, cols, want_grad=True):
     return losses, dsim, dts
 
 
-def _sim_desc(q, g, k, scale, slices):
-    """mpv_sim_search_desc over bf16 feature rows q [Nq, D], g [Ng, D] (rows contiguous; a row stride is allowed)"""
+def _sim_desc(q, g, k, scale, slices, g_dtype=torch.bfloat16):
+    """mpv_sim_search_desc over bf16 feature rows q [Nq, D], g [Ng, D] (rows contiguous; a row stride is allowed); the *_q8 ops
+    pass g_dtype=torch.uint8: the gallery is e4m3 codes and its row stride counts codes"""
     _need_cuda(q, g)
-    for name, t in (("queries", q), ("gallery", g)):
-        if t.dtype != torch.bfloat16:
-            raise _lib.MpvError(f"sim search: {name} must be bfloat16 (got {t.dtype})")
+    for name, t, want in (("queries", q, torch.bfloat16), ("gallery", g, g_dtype)):
+        if t.dtype != want:
+            raise _lib.MpvError(f"sim search: {name} must be {want} (got {t.dtype})")
         if t.dim() != 2 or t.shape[0] == 0:
             raise _lib.MpvError(f"sim search: {name} must be a non-empty [rows, dim] matrix (got {tuple(t.shape)})")
         if t.stride(1) != 1:
@@ -1314,18 +1315,21 @@ def _sim_desc(q, g, k, scale, slices):
     return d
 
 
-def _search_topk(name, d, q, k):
-    """vals / idx [Nq, k] filled by mpv_<name> on descriptor d, with the workspace mpv_<name>_workspace_size asks for"""
+def _search_topk(name, d, q, k, g_scale=None):
+    """vals / idx [Nq, k] filled by mpv_<name> on descriptor d, with the workspace mpv_<name>_workspace_size asks for; g_scale: the
+    row scales that the *_q8 entries take after the descriptor"""
     vals = torch.empty((q.shape[0], k), dtype=torch.float32, device=q.device)
     idx = torch.empty((q.shape[0], k), dtype=torch.int64, device=q.device)
     lib = _lib.lib()
-    ws = workspace(max(getattr(lib, f"mpv_{name}_workspace_size")(C.byref(d)), 1), q.device)
-    check(getattr(lib, f"mpv_{name}")(C.byref(d), vals.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), f"mpv_{name}")
+    extra = () if g_scale is None else (g_scale.data_ptr(),)
+    ws = workspace(max(getattr(lib, f"mpv_{name}_workspace_size")(C.byref(d), *extra), 1), q.device)
+    check(getattr(lib, f"mpv_{name}")(C.byref(d), *extra, vals.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+          f"mpv_{name}")
     return vals, idx
 
 
-def _search_rank(name, d, q, target, queries="queries"):
-    """rank [Nq] filled by mpv_<name> on descriptor d for target int64 [Nq] or [Nq, n_t]"""
+def _search_rank(name, d, q, target, queries="queries", g_scale=None):
+    """rank [Nq] filled by mpv_<name> on descriptor d for target int64 [Nq] or [Nq, n_t]; g_scale as in _search_topk"""
     _need_cuda(target)
     if target.dtype != torch.int64:
         raise _lib.MpvError(f"{name}: target must be int64 (got {target.dtype})")
@@ -1335,8 +1339,9 @@ def _search_rank(name, d, q, target, queries="queries"):
     n_t = target.shape[1]
     rank = torch.empty(q.shape[0], dtype=torch.int32, device=q.device)
     lib = _lib.lib()
-    ws = workspace(max(getattr(lib, f"mpv_{name}_workspace_size")(C.byref(d), n_t), 1), q.device)
-    check(getattr(lib, f"mpv_{name}")(C.byref(d), target.data_ptr(), n_t, rank.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+    extra = () if g_scale is None else (g_scale.data_ptr(),)
+    ws = workspace(max(getattr(lib, f"mpv_{name}_workspace_size")(C.byref(d), *extra, n_t), 1), q.device)
+    check(getattr(lib, f"mpv_{name}")(C.byref(d), *extra, target.data_ptr(), n_t, rank.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
           f"mpv_{name}")
     return rank
 
@@ -1354,10 +1359,34 @@ def sim_rank(q, g, target, slices=0):
     return _search_rank("sim_rank", _sim_desc(q, g, 0, None, slices), q, target)
 
 
-def _maxsim_side(name, t):
-    """-> (rows per item, row stride in elements) of bf16 features [n, dim] (one row per item) or [n, group, dim]"""
-    if t.dtype != torch.bfloat16:
-        raise _lib.MpvError(f"maxsim search: {name} must be bfloat16 (got {t.dtype})")
+def _code_scales(what, codes, g_scale):
+    """the row scales of a gallery of codes: fp32, contiguous, one per row (codes [.., dim] -> g_scale [..])"""
+    _need_cuda(g_scale)
+    if g_scale.dtype != torch.float32 or tuple(g_scale.shape) != tuple(codes.shape[:-1]) or not g_scale.is_contiguous():
+        raise _lib.MpvError(f"{what}: g_scale must be a contiguous float32 tensor of shape {tuple(codes.shape[:-1])}, one scale per row of "
+                            f"codes (got {g_scale.dtype} {tuple(g_scale.shape)})")
+    return g_scale
+
+
+def sim_topk_q8(q, codes, g_scale, k, scale=None, slices=0):
+    """sim_topk over a gallery of e4m3 codes uint8 [Ng, D] (row pitch a multiple of 16) with g_scale fp32 [Ng], as
+    quantize_rows_e4m3 returns them: the score of row j is g_scale[j] * <q_i, deq(codes_j)>.  For power-of-two scales the result is
+    bit for bit sim_topk on the bf16 gallery deq(codes) * g_scale (include/mpv.h: mpv_sim_topk_q8)."""
+    d = _sim_desc(q, codes, k, scale, slices, g_dtype=torch.uint8)
+    return _search_topk("sim_topk_q8", d, q, k, g_scale=_code_scales("sim_topk_q8", codes, g_scale))
+
+
+def sim_rank_q8(q, codes, g_scale, target, slices=0):
+    """sim_rank over a gallery of e4m3 codes (sim_topk_q8; include/mpv.h: mpv_sim_rank_q8)"""
+    d = _sim_desc(q, codes, 0, None, slices, g_dtype=torch.uint8)
+    return _search_rank("sim_rank_q8", d, q, target, g_scale=_code_scales("sim_rank_q8", codes, g_scale))
+
+
+def _maxsim_side(name, t, dtype=torch.bfloat16):
+    """-> (rows per item, row stride in elements) of bf16 features [n, dim] (one row per item) or [n, group, dim]; dtype uint8: e4m3
+    codes, the stride counts codes"""
+    if t.dtype != dtype:
+        raise _lib.MpvError(f"maxsim search: {name} must be {dtype} (got {t.dtype})")
     if t.dim() not in (2, 3) or t.shape[0] == 0 or t.shape[-2] == 0:
         raise _lib.MpvError(f"maxsim search: {name} must be a non-empty [items, dim] or [items, group, dim] tensor (got {tuple(t.shape)})")
     if t.stride(-1) != 1:
@@ -1370,10 +1399,10 @@ def _maxsim_side(name, t):
     return t.shape[1], rs
 
 
-def _maxsim_desc(q, g, k, scale, slices):
+def _maxsim_desc(q, g, k, scale, slices, g_dtype=torch.bfloat16):
     """mpv_maxsim_search_desc over bf16 features; each side is [items, dim] or [items, group, dim], at most one side grouped > 1"""
     _need_cuda(q, g)
-    (qg, q_rs), (gg, g_rs) = _maxsim_side("queries", q), _maxsim_side("gallery", g)
+    (qg, q_rs), (gg, g_rs) = _maxsim_side("queries", q), _maxsim_side("gallery", g, g_dtype)
     if q.shape[-1] != g.shape[-1]:
         raise _lib.MpvError(f"maxsim search: feature widths differ ({q.shape[-1]} vs {g.shape[-1]})")
     d = _lib.MaxSimSearchDesc()
@@ -1394,3 +1423,17 @@ def maxsim_rank(q, g, target, slices=0):
     """-> rank int32 [Nq]: the best rank among the query item's target items (target int64 [Nq] or [Nq, n_t], -1 = unused slot) under
     the query-max score and the order rule of maxsim_topk; Ng for a query with no valid target (include/mpv.h: mpv_maxsim_rank)."""
     return _search_rank("maxsim_rank", _maxsim_desc(q, g, 0, None, slices), q, target, queries="query items")
+
+
+def maxsim_topk_q8(q, codes, g_scale, k, scale=None, slices=0):
+    """maxsim_topk over a gallery of e4m3 codes uint8 [Ng, group, D] or [Ng, D] with g_scale fp32 [Ng, group] or [Ng] (one per row,
+    applied before the max over the group); queries bf16 with one row per item -- grouped queries are refused, that direction stays
+    on bf16 indexes.  For power-of-two scales bit for bit maxsim_topk on deq(codes) * g_scale (include/mpv.h: mpv_maxsim_topk_q8)."""
+    d = _maxsim_desc(q, codes, k, scale, slices, g_dtype=torch.uint8)
+    return _search_topk("maxsim_topk_q8", d, q, k, g_scale=_code_scales("maxsim_topk_q8", codes, g_scale))
+
+
+def maxsim_rank_q8(q, codes, g_scale, target, slices=0):
+    """maxsim_rank over a gallery of e4m3 codes (maxsim_topk_q8; include/mpv.h: mpv_maxsim_rank_q8)"""
+    d = _maxsim_desc(q, codes, 0, None, slices, g_dtype=torch.uint8)
+    return _search_rank("maxsim_rank_q8", d, q, target, queries="query items", g_scale=_code_scales("maxsim_rank_q8", codes, g_scale))

@@ -232,11 +232,28 @@ def synthetic_retrieval_model(shapes, device="cuda", num_frames=None, embed_dim=
 
 
 class _FeatureIndex:
-    """Storage shared by the two indexes: items of shape `_item` appended in order into a buffer that grows geometrically."""
+    """Storage shared by the two indexes: items of shape `_item` appended in order into a buffer that grows geometrically.
+    storage="bf16" keeps the rows as they come.  storage="fp8" keeps e4m3 codes (one byte per element) and one power-of-two fp32
+    scale per row, quantised on the device by ops.quantize_rows_e4m3 as the rows are added: half the bytes, searched by the *_q8
+    ops, whose results are bit for bit those of the bf16 ops on dequantized() (include/mpv.h, "Searches over an FP8 gallery")."""
 
-    def _init_storage(self, item, device, capacity):
-        self._item, self.device, self.size = tuple(item), torch.device(device), 0
-        self._rows = torch.empty((max(int(capacity), 1),) + self._item, dtype=torch.bfloat16, device=self.device)
+    def _init_storage(self, item, device, capacity, storage="bf16"):
+        if storage not in ("bf16", "fp8"):
+            raise ops._lib.MpvError(f"{type(self).__name__}: storage must be 'bf16' or 'fp8' (got {storage!r})")
+        self._item, self.device, self.size, self.storage = tuple(item), torch.device(device), 0, storage
+        self._rows = self._scales = None
+        self._allocate(max(int(capacity), 1))
+
+    def _allocate(self, capacity):
+        """storage for `capacity` items, the first `size` of them copied over"""
+        dtype = torch.bfloat16 if self.storage == "bf16" else torch.uint8
+        rows = torch.empty((capacity,) + self._item, dtype=dtype, device=self.device)
+        scales = torch.empty((capacity,) + self._item[:-1], dtype=torch.float32, device=self.device) if self.storage == "fp8" else None
+        if self.size:
+            rows[:self.size].copy_(self._rows[:self.size])
+            if scales is not None:
+                scales[:self.size].copy_(self._scales[:self.size])
+        self._rows, self._scales = rows, scales
 
     def __len__(self):
         return self.size
@@ -248,15 +265,49 @@ class _FeatureIndex:
     @property
     def features(self):
         """the items added so far: a view of the storage, bf16 [size, *item shape]"""
+        if self.storage != "bf16":
+            raise ops._lib.MpvError(f"{type(self).__name__}.features: an fp8 index keeps codes and scales (.codes, .scales); "
+                                    "dequantized() builds the bf16 rows, at twice the index's bytes")
         return self._rows[:self.size]
+
+    def _fp8(self, what):
+        if self.storage != "fp8":
+            raise ops._lib.MpvError(f"{type(self).__name__}.{what}: only an index with storage='fp8' has it")
+
+    @property
+    def codes(self):
+        """fp8 storage: the e4m3 codes added so far, a view of the storage, uint8 [size, *item shape]"""
+        self._fp8("codes")
+        return self._rows[:self.size]
+
+    @property
+    def scales(self):
+        """fp8 storage: the row scales added so far, a view of the storage, fp32 [size] ([size, group] for grouped items)"""
+        self._fp8("scales")
+        return self._scales[:self.size]
+
+    def dequantized(self):
+        """fp8 storage: the bf16 rows the index stands for, deq(code) * scale (exact: the scales are powers of two) -- a new tensor of
+        twice the index's bytes, for checks and re-scoring, not for searching"""
+        self._fp8("dequantized()")
+        return (self.codes.view(torch.float8_e4m3fn).float() * self.scales[..., None]).to(torch.bfloat16)
+
+    @property
+    def nbytes(self):
+        """bytes of the items added so far (rows, and scales when there are any)"""
+        n = self._rows[:self.size].numel() * self._rows.element_size()
+        return n + (self._scales[:self.size].numel() * 4 if self._scales is not None else 0)
 
     def _append(self, features):
         n, first = features.shape[0], self.size
         if first + n > self.capacity:
-            grown = torch.empty((max(2 * self.capacity, first + n),) + self._item, dtype=torch.bfloat16, device=self.device)
-            grown[:first].copy_(self._rows[:first])
-            self._rows = grown
-        self._rows[first:first + n].copy_(features)
+            self._allocate(max(2 * self.capacity, first + n))
+        if self.storage == "bf16":
+            self._rows[first:first + n].copy_(features)
+        elif n:
+            codes, scale = ops.quantize_rows_e4m3(features.contiguous().reshape(-1, self._item[-1]))
+            self._rows[first:first + n].copy_(codes.view((n,) + self._item))
+            self._scales[first:first + n].copy_(scale.view((n,) + self._item[:-1]))
         self.size = first + n
         return first
 
@@ -275,11 +326,11 @@ class RetrievalIndex(_FeatureIndex):
     added in; row i of the index is the i-th feature ever added.  Storage grows geometrically, so `add` does not re-allocate
     per call.  Order rule of both searches: higher score first, equal scores by the lower row index (include/mpv.h)."""
 
-    def __init__(self, dim: int, device="cuda", capacity: int = 1024):
+    def __init__(self, dim: int, device="cuda", capacity: int = 1024, storage: str = "bf16"):
         if dim % 32 != 0 or not 32 <= dim <= 1024:
             raise ops._lib.MpvError(f"RetrievalIndex: dim ({dim}) must be a multiple of 32 in [32, 1024]")
         self.dim = dim
-        self._init_storage((dim,), device, capacity)
+        self._init_storage((dim,), device, capacity, storage)
 
     def _check(self, feats, what):
         if not torch.is_tensor(feats) or feats.dtype != torch.bfloat16:
@@ -300,6 +351,8 @@ class RetrievalIndex(_FeatureIndex):
             raise ops._lib.MpvError(f"RetrievalIndex.search: k ({k}) must be in [1, 32]")
         if self.size == 0:
             raise ops._lib.MpvError("RetrievalIndex.search: the index is empty")
+        if self.storage == "fp8":
+            return ops.sim_topk_q8(query_features.contiguous(), self.codes, self.scales, int(k), scale=scale)
         return ops.sim_topk(query_features.contiguous(), self.features, int(k), scale=scale)
 
     def rank(self, query_features, target):
@@ -307,7 +360,10 @@ class RetrievalIndex(_FeatureIndex):
         self._check(query_features, "rank")
         if self.size == 0:
             raise ops._lib.MpvError("RetrievalIndex.rank: the index is empty")
-        return ops.sim_rank(query_features.contiguous(), self.features, self._targets(target, query_features, "rows"))
+        target = self._targets(target, query_features, "rows")
+        if self.storage == "fp8":
+            return ops.sim_rank_q8(query_features.contiguous(), self.codes, self.scales, target)
+        return ops.sim_rank(query_features.contiguous(), self.features, target)
 
 
 class MaxSimIndex(_FeatureIndex):
@@ -317,13 +373,13 @@ class MaxSimIndex(_FeatureIndex):
     single-row queries [nq, dim]; a group == 1 index takes single-row queries or grouped ones [nq, Q, dim].  Neither the row
     products nor a [queries, items] matrix are built.  Surface, growth and order rule of RetrievalIndex."""
 
-    def __init__(self, dim: int, group: int = 1, device="cuda", capacity: int = 1024):
+    def __init__(self, dim: int, group: int = 1, device="cuda", capacity: int = 1024, storage: str = "bf16"):
         if dim % 32 != 0 or not 32 <= dim <= 1024:
             raise ops._lib.MpvError(f"MaxSimIndex: dim ({dim}) must be a multiple of 32 in [32, 1024]")
         if not 1 <= int(group) <= 1024:
             raise ops._lib.MpvError(f"MaxSimIndex: group ({group}) must be in [1, 1024]")
         self.dim, self.group = dim, int(group)
-        self._init_storage((self.group, dim), device, capacity)
+        self._init_storage((self.group, dim), device, capacity, storage)
 
     def _check(self, feats, what, groups):
         if not torch.is_tensor(feats) or feats.dtype != torch.bfloat16:
@@ -343,6 +399,9 @@ class MaxSimIndex(_FeatureIndex):
     def _query(self, query_features, what):
         # a grouped index is searched with one row per query; an index of single rows with single rows or with groups of any size
         q = self._check(query_features, what, (1,) if self.group > 1 else any)
+        if self.storage == "fp8" and q.shape[1] > 1:
+            raise ops._lib.MpvError(f"MaxSimIndex.{what}: grouped queries {tuple(q.shape)} against an fp8 index: in that direction the "
+                                    "index is the resident side of the search, which is bf16 only -- keep such (title) indexes in bf16")
         if self.size == 0:
             raise ops._lib.MpvError(f"MaxSimIndex.{what}: the index is empty")
         return q.contiguous()
@@ -352,9 +411,14 @@ class MaxSimIndex(_FeatureIndex):
         q = self._query(query_features, "search")
         if not 1 <= int(k) <= 32:
             raise ops._lib.MpvError(f"MaxSimIndex.search: k ({k}) must be in [1, 32]")
+        if self.storage == "fp8":
+            return ops.maxsim_topk_q8(q, self.codes, self.scales, int(k), scale=scale)
         return ops.maxsim_topk(q, self.features, int(k), scale=scale)
 
     def rank(self, query_features, target):
         """-> int32 [Nq]: the best rank (0 = first) among each query's target items; target int64 [Nq] or [Nq, n_t], -1 = unused"""
         q = self._query(query_features, "rank")
-        return ops.maxsim_rank(q, self.features, self._targets(target, q, "items"))
+        target = self._targets(target, q, "items")
+        if self.storage == "fp8":
+            return ops.maxsim_rank_q8(q, self.codes, self.scales, target)
+        return ops.maxsim_rank(q, self.features, target)
