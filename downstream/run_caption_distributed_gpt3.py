@@ -59,6 +59,13 @@ What this entry point adds to downstream/finetune_common.py:
     (`model.generate(..., do_sample=True, num_samples=N, consensus=METRIC)`); the chosen caption goes through the result path and the
     metrics above like `--eval_sample_best_of`'s, with which (as with `--eval_beam_groups` and `--eval_allowed_phrases`) it is
     refused; it combines with `--eval_shared_kv`, the constraints, `--eval_sample_mixed_prompts` and `--eval_sample_inflight`;
+  * `--eval_guidance_scale F` with `--eval_guidance_alpha F` (not in the reference, defaults 1.0 / 0.0 = off): the lockstep generation
+    calls of the evaluation are GUIDED (classifier-free guidance / contrastive decoding): every chunk decodes a second branch of the
+    same prompts behind the query features of an all-zero clip and each step continues from cond + (scale - 1) * (cond - uncond)
+    (`model.generate(..., guidance_scale=F)`; one more launch per step, twice the rows per chunk); the alpha -- a token below alpha
+    times the step's most likely one is banned -- acts on the sampling calls only (`guidance_alpha=F`; the beam search refuses it).
+    Needs one of the lockstep flags (`--eval_batched_beam`, `--eval_beam_groups`, `--eval_sample`, `--eval_sample_best_of`,
+    `--eval_sample_consensus`), is refused with `--eval_sample_inflight` and `--eval_beam_inflight`, and combines with the rest;
   * `--eval_score_gold` (not in the reference, default off): evaluation also scores every clip's `gold_caption` list, teacher-forced,
     against the query features computed once for that clip (`model.score_captions(..., query_features=)`: one packed pass per batch,
     no padding rows), adds "gold_logprob" / "gold_tokens" lists to the result entries and logs the corpus per-token NLL and perplexity;
@@ -109,7 +116,7 @@ def make_training_batch(video, text, prompt, tokenizer, device, max_length):
 def evaluation(model, data_loader, tokenizer, device, config, batched=False, clips_per_search=32, eval_sample=0, seed=0, shared_kv=False,
                constraints=None, best_of=0, score_gold=False, max_length=None, beam_groups=1, diversity_penalty=0.0, fp8_decode=False,
                mixed_prompts=False, sample_mixed_prompts=False, sample_inflight=False, beam_inflight=False, allowed_phrases=None,
-               consensus=0, consensus_metric="rouge_l"):
+               consensus=0, consensus_metric="rouge_l", guidance_scale=1.0, guidance_alpha=0.0):
     """-> [{video_id, pred_caption, gold_caption}] (:208-238); batched: `--eval_batched_beam`; eval_sample: `--eval_sample`;
     shared_kv: `--eval_shared_kv`, constraints: the keywords of `--eval_repetition_penalty` / `--eval_no_repeat_ngram` /
     `--eval_min_new_tokens` (the lockstep calls only); best_of: `--eval_sample_best_of` (the prediction is the best of that many
@@ -121,7 +128,14 @@ def evaluation(model, data_loader, tokenizer, device, config, batched=False, cli
     `--eval_sample_inflight` (the sampling calls only); beam_inflight: `--eval_beam_inflight` (the lockstep beam-search calls only);
     allowed_phrases: the strings of `--eval_allowed_phrases` (the lockstep beam search only; tokenised once, here); consensus /
     consensus_metric: `--eval_sample_consensus` / `--eval_consensus_metric` (the prediction is the consensus choice among that many
-    samples instead of the beam search's)"""
+    samples instead of the beam search's); guidance_scale / guidance_alpha: `--eval_guidance_scale` / `--eval_guidance_alpha` (the
+    lockstep calls only; the alpha reaches the sampling calls alone)"""
+    _check_guidance(guidance_scale, guidance_alpha, batched or beam_groups > 1, eval_sample or best_of or consensus, sample_inflight or beam_inflight)
+    if guidance_scale != 1.0 or guidance_alpha != 0.0:                       # flags absent: the calls below are unchanged
+        beam_guide = {"guidance_scale": guidance_scale} if guidance_scale != 1.0 else {}
+        sample_guide = dict(beam_guide, **({"guidance_alpha": guidance_alpha} if guidance_alpha else {}))
+    else:
+        beam_guide = sample_guide = {}
     module = getattr(model, "module", model)
     module.eval()
     trie = None
@@ -136,13 +150,13 @@ def evaluation(model, data_loader, tokenizer, device, config, batched=False, cli
     kvkw.update(constraints or {})
     if mixed_prompts and not (batched or beam_groups > 1):
         raise ValueError("--eval_mixed_prompts needs --eval_batched_beam or --eval_beam_groups: the per-clip search has one prompt per call")
-    mixkw = {"mixed_prompts": True} if mixed_prompts else {}                 # flag absent: the calls below are unchanged
+    mixkw = dict({"mixed_prompts": True} if mixed_prompts else {}, **beam_guide)    # flags absent: the calls below are unchanged
     if consensus and (best_of or beam_groups > 1 or allowed_phrases):
         raise ValueError("--eval_sample_consensus, --eval_sample_best_of, --eval_beam_groups and --eval_allowed_phrases all choose the "
                          "prediction: pass one of them")
     if sample_mixed_prompts and not ((eval_sample or best_of or consensus) and shared_kv):
         raise ValueError("--eval_sample_mixed_prompts needs --eval_sample or --eval_sample_best_of, and --eval_shared_kv")
-    smixkw = {"sample_mixed_prompts": True} if sample_mixed_prompts else {}  # flag absent: the calls below are unchanged
+    smixkw = dict({"sample_mixed_prompts": True} if sample_mixed_prompts else {}, **sample_guide)   # flags absent: the calls below are unchanged
     if sample_inflight and (sample_mixed_prompts or not ((eval_sample or best_of or consensus) and shared_kv)):
         raise ValueError("--eval_sample_inflight needs --eval_sample or --eval_sample_best_of, and --eval_shared_kv, without "
                          "--eval_sample_mixed_prompts")
@@ -205,6 +219,18 @@ def evaluation(model, data_loader, tokenizer, device, config, batched=False, cli
         if n == 0:
             print(result)
     return result
+
+
+def _check_guidance(scale, alpha, beams, sampling, inflight):
+    if not (math.isfinite(scale) and scale >= 0.0) or not 0.0 <= alpha < 1.0:
+        raise ValueError(f"--eval_guidance_scale must be finite and not negative, --eval_guidance_alpha in [0, 1) (got {scale}, {alpha})")
+    if scale == 1.0 and alpha == 0.0:
+        return
+    if not (beams or sampling) or inflight:
+        raise ValueError("--eval_guidance_scale / --eval_guidance_alpha need a lockstep call (--eval_batched_beam, --eval_beam_groups, "
+                         "--eval_sample, --eval_sample_best_of, --eval_sample_consensus), without --eval_sample_inflight and --eval_beam_inflight")
+    if alpha and not sampling:
+        raise ValueError("--eval_guidance_alpha acts on the sampling calls only (--eval_sample, --eval_sample_best_of, --eval_sample_consensus)")
 
 
 def _check_beam_inflight(batched, shared_kv, mixed_prompts, sampling):
@@ -430,6 +456,8 @@ def main(args, config):
                             **({"beam_inflight": True} if getattr(args, "eval_beam_inflight", False) else {}),
                             **({"consensus": args.eval_sample_consensus, "consensus_metric": args.eval_consensus_metric or "rouge_l"}
                                if getattr(args, "eval_sample_consensus", 0) else {}),
+                            **({"guidance_scale": args.eval_guidance_scale, "guidance_alpha": args.eval_guidance_alpha}
+                               if getattr(args, "eval_guidance_scale", 1.0) != 1.0 or getattr(args, "eval_guidance_alpha", 0.0) != 0.0 else {}),
                             **({"allowed_phrases": read_phrases(args.eval_allowed_phrases)} if getattr(args, "eval_allowed_phrases", None) else {}))
         final = save_result(result, args.result_dir, "val_caption_result")
         val_stats = cal_metric(final, s.device)
@@ -572,6 +600,12 @@ def get_args(argv=None):
         p.add_argument("--eval_allowed_phrases", type=str, default=None, metavar="FILE",
                        help="--eval_batched_beam: the captions are phrases of FILE (one per line), found by a beam search along their trie "
                             "(model.generate(batched=True, allowed_phrases=...)); pred_candidates lists the best with their scores")
+        p.add_argument("--eval_guidance_scale", type=float, default=1.0,
+                       help="evaluation: the lockstep generation calls are guided by a null-video branch, cond + (F - 1) * (cond - uncond) "
+                            "per step (model.generate(guidance_scale=F)); 1 = off")
+        p.add_argument("--eval_guidance_alpha", type=float, default=0.0,
+                       help="--eval_guidance_scale, sampling calls: ban the tokens whose probability is below F times the step's largest "
+                            "(model.generate(guidance_alpha=F)); 0 = off")
         p.add_argument("--eval_score_gold", action="store_true", default=False,
                        help="evaluation: also score every clip's gold captions against its query features (model.score_captions): "
                             "gold_logprob / gold_tokens in the result file, per-token NLL and perplexity in the log")
@@ -619,6 +653,8 @@ def get_args(argv=None):
                                       not ((args.eval_sample or args.eval_sample_best_of or args.eval_sample_consensus) and args.eval_shared_kv)):
         raise ValueError("--eval_sample_inflight needs --eval_sample N or --eval_sample_best_of N, and --eval_shared_kv, without "
                          "--eval_sample_mixed_prompts")
+    _check_guidance(args.eval_guidance_scale, args.eval_guidance_alpha, args.eval_batched_beam or args.eval_beam_groups > 1,
+                    args.eval_sample or args.eval_sample_best_of or args.eval_sample_consensus, args.eval_sample_inflight or args.eval_beam_inflight)
     if args.eval_beam_inflight:
         _check_beam_inflight(args.eval_batched_beam, args.eval_shared_kv, args.eval_mixed_prompts,
                              args.eval_sample or args.eval_sample_best_of or args.eval_sample_consensus or args.eval_sample_mixed_prompts or

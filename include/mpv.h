@@ -922,6 +922,40 @@ int mpv_logits_constrain_ragged(const mpv_logits_constrain_desc* d, mpv_stream_t
  * and mpv_logits_constrain on that row alone at pos = c_r.  Refused: as the ragged entry except d->pos, and a NULL row_step. */
 int mpv_logits_constrain_steps(const mpv_logits_constrain_desc* d, const int32_t* row_step, mpv_stream_t stream);
 /* ------------------------------------------------------------------------------------------
+ * Guided decoding (generation.Guidance; classifier-free guidance, also known as contrastive decoding): ONE launch rewrites one step's
+ * CONDITIONAL logits in place from the UNCONDITIONAL ones of a second branch that ran in lockstep behind a "null" video, before
+ * mpv_logits_constrain, mpv_logits_trie_mask, mpv_sample_advance, mpv_sample_score or mpv_logprob_topk sees them.
+ * Input: cond bf16 [rows][ld_c], edited in place; uncond bf16 [rows][ld_u], read only and left bit for bit (it may live in the same
+ *   allocation as cond, on other rows); both 16-byte aligned, the first `vocab` columns are the row; scale_m1 = float(guidance_scale
+ *   - 1), computed on the host; plaus_log = log(alpha) computed on the host, <= 0, -inf = off; ban_value, -inf or finite and negative,
+ *   stored rounded to bf16.  The inputs are the raw, finite logits.
+ * Row r: m_c = max_v float(cond[r][v]) and m_u = max_v float(uncond[r][v]) over v < vocab -- exact and order-free; a maximum that is a
+ *   zero counts as +0.  Then for every v < vocab
+ *     c = float(cond[r][v]) - m_c,  u = float(uncond[r][v]) - m_u,  g = c + scale_m1 * (c - u),  cond[r][v] = bf16_rne(g)
+ *   where each subtract, the multiply and the add is ONE IEEE fp32 operation: the multiply and the add are not contracted into a
+ *   fused one.  guidance_scale = 1 (scale_m1 = 0) therefore yields the centred conditional logits, guidance_scale = 0 the centred
+ *   unconditional ones up to rounding.
+ * Plausibility (plaus_log > -inf): a token with c < plaus_log -- p_cond(v) < alpha * max p_cond -- becomes ban_value instead.  The
+ *   arg-max of cond has c = 0 >= plaus_log and always survives.
+ * Columns >= vocab of either matrix are neither read nor written.  A row's result depends on its own two rows and the scalars only --
+ *   neither on `rows` nor on the row's place in the launch -- and every column has one writer: the result does not depend on thread
+ *   timing.  No atomics.  A non-finite element follows IEEE through the stated operations and is not otherwise defined; NaN is excluded.
+ * ban_value: -inf for mpv_sample_advance, the lowest finite bf16 in front of mpv_logprob_topk, as for mpv_logits_constrain.
+ * Refused with a negative code before any launch, logits untouched: what mpv_logits_constrain refuses about pointers, vocab, ld,
+ *   alignment and rows, applied to both matrices (a NULL cond / uncond; vocab not a multiple of 8 or outside [8, 65536]; ld_c or ld_u
+ *   < vocab or not a multiple of 8; cond or uncond not 16-byte aligned; rows < 1); a scale_m1 that is not finite or < -1; plaus_log > 0
+ *   or NaN; a ban_value that is NaN, +inf or >= 0.
+ * One workgroup per row; the row pair is loaded once in 16-byte chunks and kept in registers across the maximum, so the launch moves
+ *   3 * rows * vocab * 2 bytes. */
+typedef struct mpv_logits_guide_desc {
+  void* cond;
+  const void* uncond;
+  int64_t ld_c, ld_u;
+  int rows, vocab;
+  float scale_m1, plaus_log, ban_value;
+} mpv_logits_guide_desc;
+int mpv_logits_guide(const mpv_logits_guide_desc* d, mpv_stream_t stream);
+/* ------------------------------------------------------------------------------------------
  * Closed-vocabulary generation (generation.PhraseTrie, LogitsConstraints.allowed_phrases): ONE launch keeps, in one step's logits,
  * only the tokens that continue the row's generated history along a trie of allowed phrases, after mpv_logits_constrain (a ban
  * still wins) and before mpv_sample_advance or mpv_logprob_topk reads them.  The state of the walk is the loop's own token table.

@@ -144,6 +144,11 @@ class LogitsConstrainDesc(C.Structure):
                [("penalty", c_float), ("ban_value", c_float)]
 
 
+class LogitsGuideDesc(C.Structure):
+    _fields_ = [("cond", c_void_p), ("uncond", c_void_p), ("ld_c", c_int64), ("ld_u", c_int64), ("rows", c_int), ("vocab", c_int),
+                ("scale_m1", c_float), ("plaus_log", c_float), ("ban_value", c_float)]
+
+
 class LogitsTrieDesc(C.Structure):
     _fields_ = [(n, c_void_p) for n in ("logits", "tokens", "prompt_len", "eos_ids", "child_begin", "child_tok", "child_node", "terminal", "node_out")] + \
                [("ld", c_int64), ("prompt_len_all", c_int64)] + \
@@ -356,6 +361,7 @@ _SIGS.update({
     "mpv_sample_score_steps": (c_int, [C.POINTER(SampleScoreDesc), c_void_p, c_void_p]),
     "mpv_beam_advance_steps": (c_int, [C.POINTER(BeamAdvanceGroupsDesc), c_void_p, c_void_p, c_void_p]),
     "mpv_kv_suffix_reorder_steps": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "mpv_logits_guide": (c_int, [C.POINTER(LogitsGuideDesc), c_void_p]),
     "mpv_logits_trie_mask": (c_int, [C.POINTER(LogitsTrieDesc), c_void_p]),
     "mpv_logits_trie_mask_ragged": (c_int, [C.POINTER(LogitsTrieDesc), c_void_p]),
     "mpv_logits_trie_mask_steps": (c_int, [C.POINTER(LogitsTrieDesc), c_void_p, c_void_p]),

@@ -519,7 +519,7 @@ class DistributedGPT3_Caption(_GenCls):
                  banned_token_ids=None, constrain_prompt=False, return_scores=False, best_of=False, length_penalty=1.0, query_features=None,
                  beam_groups=1, diversity_penalty=0.0, rerank_by_logprob=False, decode_weights="bf16", mixed_prompts=False, sample_mixed_prompts=False,
                  inflight=False, max_new_tokens=None, refill_min=None, beam_inflight=False, allowed_phrases=None, consensus=None,
-                 rerank_by_consensus=None, **kw):
+                 rerank_by_consensus=None, guidance_scale=1.0, guidance_alpha=0.0, guidance_query_features=None, **kw):
         """One beam search per sample (:790-809): prompt = text.input_ids[i, :mask.sum()-1], prefix = its query features.
         batched=True (not in the reference, default off): the clips are grouped by prompt length and every group is searched in
         lockstep, `clips_per_search` clips at a time (generation.beam_search_batched_loop: the decoder's weights are read once per
@@ -631,12 +631,31 @@ class DistributedGPT3_Caption(_GenCls):
         rerank_by_consensus="rouge_l" | "ngram_f" (batched=True only; default None): -> (res, info).  Each clip's returned hypotheses
         are reordered by U descending, ties in search order (one ops.caption_overlap call over all the clips' rows: the clips may
         return different numbers of rows); info[i] holds consensus [n] fp64 and group [n] int64 in the new order.  Refused together
-        with rerank_by_logprob and with allowed_phrases."""
+        with rerank_by_logprob and with allowed_phrases.
+        guidance_scale / guidance_alpha / guidance_query_features (batched=True and do_sample=True only; defaults 1.0 / 0.0 / None: no
+        second branch, no launch, the call made before the feature existed): classifier-free guidance, also known as contrastive
+        decoding (generation.Guidance).  Every chunk decodes a second, "null-video" branch of the same prompts in
+        lockstep and each step continues from cond + (guidance_scale - 1) * (cond - uncond) on the max-centred logits (one launch,
+        ops.logits_guide, before the constraints, the trie, the sampler, the scores and the top-k): a scale above 1 pushes a frozen
+        decoder away from its language prior towards what the clip says.  guidance_alpha in (0, 1) (do_sample=True only) also bans
+        every token whose conditional probability is below alpha times the step's largest.  guidance_query_features: None -- the
+        query features of an all-zero normalised clip of this call's frame count and resolution, one batch-1 encode_video() per
+        call, broadcast to all clips and not cached across calls (the weights may have changed) -- or a tensor [Q, H] (broadcast) or
+        [B * Q, H] (one null clip per clip).  clips_per_search still counts CLIPS: a chunk's state holds 2 * clips * fan sequences,
+        so its KV memory doubles.  Scores under guidance (return_scores, best_of, the search's own) are log-probabilities of the
+        guided, renormalised distribution, not the model's likelihoods; rerank_by_logprob scores the unguided model.  It combines with
+        kv_cache, the constraints, allowed_phrases, beam_groups, the mixed-prompt modes and decode_weights="fp8" (refused when 2 * clips
+        * fan exceeds the 512 rows the FP8 step takes).  Refused: use with the per-clip search, with inflight / beam_inflight, alpha > 0
+        with the beam search, a negative or non-finite scale, alpha outside [0, 1), features of another shape."""
         o = self._generate_options(SimpleNamespace(**locals()))       # every refusal comes first: a refused call runs no ViT pass
         Q, Hh = self.num_learnable_token, self.text_width
         Bv = image.shape[0] if query_features is None else query_features.shape[0] // Q
         with _eval_mode(self):
             qf = (self._query_features(image, {"vit": {}, "pool": {}}) if query_features is None else query_features).view(Bv, Q, Hh)
+            if o.guided:
+                null = o.guidance_query_features                              # None: the zero clip's, one batch-1 pass per call
+                null = self.encode_video(torch.zeros((1,) + tuple(image.shape[1:]), dtype=image.dtype, device=image.device)) if null is None else null
+                o.null = null.view(-1, Q, Hh)                                 # [1, Q, H]: every clip's; [n, Q, H]: one per clip
             if do_sample:
                 return self._generate_samples(o, qf)
             if batched:
@@ -718,8 +737,44 @@ class DistributedGPT3_Caption(_GenCls):
             raise ValueError(f"clips_per_search must be at least 1 (got {o.clips_per_search})")
         if o.inflight or o.beam_inflight:
             kw.pop("kv", None)
+        o.guided = self._guidance_options(o, lockstep)
         o.kw = kw
         return o
+
+    @staticmethod
+    def _chunk_kw(o, sel):
+        """the keywords a lockstep chunk of the clips `sel` forwards to the decoder: o.kw, under guidance with the chunk's Guidance"""
+        if not o.guided:
+            return o.kw
+        null = o.null[0] if o.null.shape[0] == 1 else o.null[sel]
+        return dict(o.kw, guidance=generation.Guidance(o.guidance_scale, o.guidance_alpha, null))
+
+    def _guidance_options(self, o, lockstep) -> bool:
+        """the refusals of guidance_scale / guidance_alpha / guidance_query_features -> is the call guided?  (the Guidance itself is
+        built in generate, once the null features exist)"""
+        g = generation.Guidance(o.guidance_scale, o.guidance_alpha)           # scale and alpha: its own checks
+        if not g.active:
+            return False
+        if not lockstep:
+            raise ValueError("guidance_scale / guidance_alpha need batched=True or do_sample=True: the per-clip search has one branch")
+        if o.inflight or o.beam_inflight:
+            raise ValueError("guidance does not combine with inflight=True / beam_inflight=True: the in-flight states hold one branch per slot")
+        if g.alpha > 0.0 and not o.do_sample:
+            raise ValueError(f"guidance_alpha ({g.alpha}) needs do_sample=True: a banned token can enter the 2K candidates of a beam step")
+        Q, Hh = self.num_learnable_token, self.text_width
+        fan = o.N if o.do_sample else int(o.beam_groups) * int(o.kw.get("beam_size", 5))
+        rows = 2 * min(int(o.clips_per_search), o.n) * fan
+        if o.decode_weights == "fp8" and rows > ops._lib.W8_TILED_MAX_ROWS:
+            raise ValueError(f'guidance doubles a chunk to {rows} rows (2 x clips x fan); decode_weights="fp8" takes at most '
+                             f"{ops._lib.W8_TILED_MAX_ROWS}: lower clips_per_search")
+        nf = o.guidance_query_features
+        if nf is None:
+            if o.image is None:
+                raise ValueError("guidance needs `image` (the null clip takes its frame count and resolution) or guidance_query_features")
+        elif not torch.is_tensor(nf) or tuple(nf.shape) not in ((Q, Hh), (o.n * Q, Hh)):
+            raise ValueError(f"guidance_query_features must be [{Q}, {Hh}] or [{o.n * Q}, {Hh}] "
+                             f"(got {tuple(nf.shape) if torch.is_tensor(nf) else type(nf).__name__})")
+        return True
 
     # ------------------------------------------------------------------ the sampled family: three modes, one finish
     def _generate_samples(self, o, qf):
@@ -753,7 +808,8 @@ class DistributedGPT3_Caption(_GenCls):
             out = self.text_decoder.sample_batched(o.text.input_ids[sel], query_embeds=qf[sel].contiguous(), temperature=o.temperature,
                                                    num_samples=N, seed=o.seed, streams=streams, top_k=o.top_k, top_p=o.top_p,
                                                    termination_id=o.termination_id,
-                                                   prompt_length=pl if mixed else torch.full((len(sel),), pl, device=qf.device), **o.kw)
+                                                   prompt_length=pl if mixed else torch.full((len(sel),), pl, device=qf.device),
+                                                   **self._chunk_kw(o, sel))
             toks, sc = out if o.scored else (out, None)
             starts = [x for x in pl for _ in range(N)] if mixed else [pl] * (len(chunk) * N)
             yield generation.pad_after_termination(toks, starts if mixed else pl, o.term, o.width, o.term), sc, starts, chunk
@@ -804,7 +860,7 @@ class DistributedGPT3_Caption(_GenCls):
             for pl, chunk in _clip_chunks(o.lengths, o.clips_per_search, by_length=not o.mixed_prompts):
                 sel = torch.as_tensor(chunk, dtype=torch.long, device=qf.device)
                 collect(chunk, dec.beam_search_batched(o.text.input_ids[sel], query_embeds=qf[sel].contiguous(), stop_token=o.termination_id,
-                                                       prompt_length=pl, **o.kw))
+                                                       prompt_length=pl, **self._chunk_kw(o, sel)))
         if o.trie is not None:
             return res, info
         if o.rerank_by_consensus is not None:

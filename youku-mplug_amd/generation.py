@@ -22,6 +22,8 @@ sample_score_steps, a step per row).  decode_weights="fp8" (default "bf16") runs
 loops on e4m3 codes of the decoder's weights (DecodeWeightsQ8; mpv_gpt_decode_step_q8 / _shared_q8, csrc/gemm_w8.hip).
 LogitsConstraints(allowed_phrases=PhraseTrie) makes the lockstep and in-flight loops produce members of a closed set of phrases only:
 one more launch per step keeps the tokens that continue a row along the trie (ops.logits_trie_mask*, csrc/logits_trie.hip).
+Guidance (classifier-free guidance / contrastive decoding) runs a second branch behind a null video's query features in the same state
+(guided_state_fn: 2R rows, no loop change) and one launch per step rewrites the conditional logits (ops.logits_guide, csrc/logits_guide.hip).
 """
 from __future__ import annotations
 
@@ -1076,6 +1078,133 @@ def _active_trie(constraints, trie_fn, eos_ids, eol_stop=False):
     return trie
 
 
+# ---------------------------------------------------------------------------------------------- guided decoding
+@dataclasses.dataclass
+class Guidance:
+    """Classifier-free guidance (contrastive decoding) for the lockstep loops (include/mpv.h: mpv_logits_guide):
+    a second branch decodes the same prompts behind `query_embeds`, the query features of a "null" video, in lockstep, and every
+    step continues from cond + (scale - 1) * (cond - uncond) on the max-centred logits of the two branches.  scale >= 0 (1: the
+    conditional branch alone; above 1: away from what the language prior says without the clip); alpha in [0, 1): a token whose
+    conditional probability is below alpha times the step's largest is banned (0: off) -- sampling only.  query_embeds: [Q, H] (one
+    null clip for every clip of a call), [B * Q, H] or [B, Q, H].  scale == 1 with alpha == 0 is NO guidance: `active` is False, no
+    second branch runs and no launch is added.
+    The scores of a guided call -- SampleScores and beam scores alike -- are log-probabilities of the GUIDED distribution,
+    renormalised over the vocabulary (over the tokens the plausibility ban left), not the model's likelihoods: as with
+    LogitsConstraints(allowed_phrases=), log_softmax runs on the logits the step continued from."""
+    scale: float = 1.0
+    alpha: float = 0.0
+    query_embeds: Optional[torch.Tensor] = None
+
+    def __post_init__(self):
+        for name, ok, rule in (("scale", lambda v: v >= 0.0, "a finite number that is not negative"), ("alpha", lambda v: 0.0 <= v < 1.0, "in [0, 1)")):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or not ok(v):
+                raise ValueError(f"guidance {name} must be {rule} (got {v!r})")
+            setattr(self, name, float(v))
+        if self.query_embeds is not None and not isinstance(self.query_embeds, torch.Tensor):
+            raise ValueError(f"guidance query_embeds must be a tensor or None (got a {type(self.query_embeds).__name__})")
+
+    @property
+    def active(self) -> bool:
+        return self.scale != 1.0 or self.alpha != 0.0
+
+    def null_rows(self, query_embeds) -> torch.Tensor:
+        """the null branch's query features for a call with query_embeds [B, Q, H] -> [B, Q, H] (a broadcast view), on its device and in
+        its dtype; a missing tensor or a shape that is none of [Q, H], [B * Q, H], [B, Q, H] is refused"""
+        if query_embeds is None or query_embeds.dim() != 3:
+            raise ValueError("guidance needs the clips' query_embeds [B, Q, H]: the null branch replaces them")
+        B, Q, H = query_embeds.shape
+        n = self.query_embeds
+        if n is None:
+            raise ValueError(f"guidance needs query_embeds, the null video's query features [{Q}, {H}] or [{B * Q}, {H}]")
+        if tuple(n.shape) not in ((Q, H), (B * Q, H), (B, Q, H), (1, Q, H)):
+            raise ValueError(f"guidance query_embeds must be [{Q}, {H}], [{B * Q}, {H}] or [{B}, {Q}, {H}] (got {tuple(n.shape)})")
+        return n.to(device=query_embeds.device, dtype=query_embeds.dtype).reshape(-1, Q, H).expand(B, Q, H)
+
+
+class GuidedState:
+    """A decode state of R sequences under guidance, for the loops as they are: `inner` is a state of 2R sequences -- rows [0, R) the
+    clips, rows [R, 2R) the same prompts behind the null query features -- and every call is forwarded doubled: prefill_fan_out with
+    both tensors (and a prompt_len list) doubled, step with the tokens doubled, reorder with cat([idx, idx + R]), so that the null
+    branch follows the beams.  After each prefill or step guide_fn(logits[:R], logits[R:], scale=, alpha=, ban_value=) runs once
+    (ops.logits_guide: one launch) and the view logits[:R] is returned: every editor, sampler, top-k and scorer works on guided logits
+    unchanged.  Anything else (pos, kv_bytes, ...) is the inner state's."""
+
+    def __init__(self, inner, rows: int, guidance: Guidance, guide_fn, ban_value: float):
+        self.inner, self.rows, self.guidance, self.guide_fn, self.ban_value = inner, int(rows), guidance, guide_fn, float(ban_value)
+
+    def __getattr__(self, name):                     # (only what the wrapper itself does not have)
+        return getattr(self.__dict__["inner"], name)
+
+    def _guided(self, logits):
+        R = self.rows
+        self.guide_fn(logits[:R], logits[R:], scale=self.guidance.scale, alpha=self.guidance.alpha, ban_value=self.ban_value)
+        return logits[:R]
+
+    def _prefill(self, tokens, query_embeds, fan, **kw):
+        null = self.guidance.null_rows(query_embeds)
+        if kw.get("prompt_len") is not None:
+            kw["prompt_len"] = 2 * _int_list(kw["prompt_len"])
+        return self._guided(self.inner.prefill_fan_out(torch.cat([tokens, tokens], 0), torch.cat([query_embeds, null], 0), fan, **kw))
+
+    def prefill_fan_out(self, tokens, query_embeds, fan):
+        return self._prefill(tokens, query_embeds, fan)
+
+    def step(self, tokens):
+        return self._guided(self.inner.step(torch.cat([tokens, tokens], 0)))
+
+    def reorder(self, batch_idx, **kw):
+        return self.inner.reorder(torch.cat([batch_idx, batch_idx + self.rows], 0), **kw)
+
+
+class GuidedRaggedState(GuidedState):
+    """GuidedState over an inner state whose prefill takes a prompt length per clip: prefill_fan_out has prompt_len= exactly when the
+    inner state's has (_takes_prompt_len reads the signature)"""
+
+    def prefill_fan_out(self, tokens, query_embeds, fan, prompt_len=None):
+        return self._prefill(tokens, query_embeds, fan, **({} if prompt_len is None else dict(prompt_len=prompt_len)))
+
+
+def guided_state_fn(make_state, guidance: Optional[Guidance], guide_fn, ban_value: float):
+    """The make_state of a lockstep loop under `guidance`: (batch, max_len) -> a GuidedState around make_state(2 * batch, max_len).
+    guide_fn is ops.logits_guide (injectable, as the loops' *_fn are); ban_value is BAN_SAMPLING in front of the sampler and BAN_BEAM
+    in front of logprob_topk.  No guidance (None, or scale 1 with alpha 0): make_state itself is returned -- no second branch, no
+    launch, the call sequence of the unguided loop."""
+    if guidance is None or not guidance.active:
+        return make_state
+    if guide_fn is None:
+        raise ValueError("guidance needs a guide_fn (ops.logits_guide)")
+
+    def make(batch, max_len):
+        inner = make_state(2 * int(batch), max_len)
+        return (GuidedRaggedState if _takes_prompt_len(inner) else GuidedState)(inner, batch, guidance, guide_fn, ban_value)
+    return make
+
+
+def _guided_make_state(make_state, guidance, query_embeds, rows, weights, ban_value, who, beams=False):
+    """what sample_batched / beam_search_batched make of guidance=: every refusal before the first launch, then guided_state_fn"""
+    if guidance is None:
+        return make_state
+    if not isinstance(guidance, Guidance):
+        raise ValueError(f"{who}: guidance must be a generation.Guidance or None (got a {type(guidance).__name__})")
+    if not guidance.active:
+        return make_state
+    if beams and guidance.alpha > 0.0:
+        raise ValueError(f"{who}: guidance alpha ({guidance.alpha}) needs a sampler: a banned token can enter the 2K candidates of a beam "
+                         "step, and no exact host filter exists for it")
+    guidance.null_rows(query_embeds)                                                       # the shape check
+    if weights == "fp8" and 2 * int(rows) > _lib.W8_TILED_MAX_ROWS:
+        raise ValueError(f'{who}: guidance doubles the {int(rows)} rows of the step, and decode_weights="fp8" takes at most '
+                         f"{_lib.W8_TILED_MAX_ROWS}: the steps would run on the bf16 weights")
+    return guided_state_fn(make_state, guidance, ops.logits_guide, ban_value)
+
+
+def _no_inflight_guidance(guidance, who):
+    if guidance is not None and (not isinstance(guidance, Guidance) or guidance.active):
+        raise ValueError(f"{who} takes no guidance: the in-flight states hold one branch per slot (guided calls: sample_batched / "
+                         "beam_search_batched)")
+
+
 def _stop_behind_prompts(tokens, prompt_lens, stop_token):
     """tokens [B, L] -> a copy with the stop token in every column at and behind the clip's prompt length: a beam hypothesis is stored
     as its whole row, so with this its generated part is what generated_part() reads, whatever padding the caller's rows carried"""
@@ -1824,24 +1953,29 @@ def install(gpt_cls):
                                 topk_fn=lambda lg, k, add: ops.logprob_topk(lg, k, add=add))
 
     def beam_search_batched(self, tokens, query_embeds=None, beam_size=5, num_return_gen=1, stop_token=None, kv="per_sequence",
-                            constraints=None, beam_groups=1, diversity_penalty=0.0, decode_weights="bf16", **kw):
+                            constraints=None, beam_groups=1, diversity_penalty=0.0, decode_weights="bf16", guidance=None, **kw):
         """beam_search for tokens [B, L] / query_embeds [B, Q, H] with one prompt length (prompt_length an int) or one per clip
         (a sequence of B lengths: beam_search_batched_loop's mixed mode, kv="shared_prefix" only), B clips in lockstep -> a list of B results;
         kv="shared_prefix" keeps the visual prefix and the prompt once per clip (SharedPrefixDecodeState); constraints: a
         LogitsConstraints, applied on the device every step (with allowed_phrases: a closed set of phrases, the results carry
         phrase_index and renormalised scores); beam_groups = G > 1: diverse beam search, G groups of beam_size beams
         each with diversity_penalty between them (beam_search_batched_loop; ops.beam_advance_groups); decode_weights="fp8": the steps
-        run on the decoder's e4m3 codes (DecodeWeightsQ8)"""
+        run on the decoder's e4m3 codes (DecodeWeightsQ8); guidance: a Guidance with alpha 0 -- the state holds 2 * B * G * beam_size
+        sequences, the second half behind the null query features, and every step's logits are guided by one launch
+        (guided_state_fn, ops.logits_guide); the scores are then those of the guided distribution"""
         _no_sample_scores(kw.pop("return_scores", False), "beam_search_batched")
+        make_state = _guided_make_state(make_state_fn(self, kv, decode_weights), guidance, query_embeds,
+                                        tokens.size(0) * int(beam_groups) * int(beam_size), decode_weights, BAN_BEAM, "beam_search_batched", beams=True)
         groups = {} if int(beam_groups) == 1 else dict(beam_groups=beam_groups, diversity_penalty=diversity_penalty,
                                                        group_advance_fn=ops.beam_advance_groups)      # one group: none of the three keywords
-        return beam_search_batched_loop(_gen_config(self), make_state_fn(self, kv, decode_weights), tokens, query_embeds=query_embeds, beam_size=beam_size,
+        return beam_search_batched_loop(_gen_config(self), make_state, tokens, query_embeds=query_embeds, beam_size=beam_size,
                                         num_return_gen=num_return_gen, stop_token=stop_token, prompt_length=kw.pop("prompt_length", None),
                                         topk_fn=lambda lg, k, add: ops.logprob_topk(lg, k, add=add), advance_fn=ops.beam_advance,
                                         constraints=constraints, constrain_fn=ops.logits_constrain, **groups, **_trie_fn("uniform", constraints))
 
     def sample_batched(self, tokens, query_embeds=None, temperature=1.0, num_samples=1, seed=0, streams=None, top_k=None, top_p=None,
-                       kv="per_sequence", constraints=None, return_scores=False, decode_weights="bf16", mixed_prompts=False, **kw):
+                       kv="per_sequence", constraints=None, return_scores=False, decode_weights="bf16", mixed_prompts=False, guidance=None,
+                       **kw):
         """sample with the sampler on the device (sample_batched_loop): tokens [B, L] -> [B * num_samples, n]; top_k / top_p override
         the configuration's values; the draws are those of (seed, position, streams[row]) -- not torch's generator;
         kv="shared_prefix" keeps the visual prefix and the shortest prompt once per clip (SharedPrefixDecodeState); constraints: a
@@ -1850,22 +1984,29 @@ def install(gpt_cls):
         log-probability of every generated token, recorded on the device every step (ops.sample_score); decode_weights="fp8": the
         steps run on the decoder's e4m3 codes (DecodeWeightsQ8); mixed_prompts=True with prompt_length = B lengths and
         kv="shared_prefix": ONE loop over clips whose prompts differ in length, the table left-aligned and every row on its own
-        column (sample_batched_loop's mixed mode: ops.sample_advance_ragged / logits_constrain_ragged / sample_score_ragged)"""
+        column (sample_batched_loop's mixed mode: ops.sample_advance_ragged / logits_constrain_ragged / sample_score_ragged);
+        guidance: a Guidance -- the state holds 2 * B * num_samples sequences, the second half behind the null query features, and
+        every step's logits are guided by one launch before anything else reads them (guided_state_fn, ops.logits_guide); the
+        scores are then log-probabilities of the guided, renormalised distribution"""
         make_state = make_state_fn(self, kv, decode_weights)
         if mixed_prompts and kv != "shared_prefix":
             raise ValueError(f'mixed_prompts=True needs kv="shared_prefix" (got {kv!r}): only the shared-prefix decode step takes a '
                              "prefix length per clip")
+        make_state = _guided_make_state(make_state, guidance, query_embeds, tokens.size(0) * int(num_samples), decode_weights, BAN_SAMPLING,
+                                        "sample_batched")
         return sample_batched_loop(_sampler_config(self, top_k, top_p), make_state, tokens, query_embeds=query_embeds, temperature=temperature,
                                    num_samples=num_samples, seed=seed, streams=streams, constraints=constraints,
                                    mixed_prompts=bool(mixed_prompts), **_sampler_fns("ragged" if mixed_prompts else "uniform", return_scores),
                                    **_trie_fn("ragged" if mixed_prompts else "uniform", constraints), **kw)
 
     def sample_inflight(self, tokens, query_embeds=None, temperature=1.0, num_samples=1, slots=32, seed=0, streams=None, top_k=None, top_p=None,
-                        constraints=None, return_scores=False, decode_weights="bf16", max_new_tokens=None, refill_min=None, **kw):
+                        constraints=None, return_scores=False, decode_weights="bf16", max_new_tokens=None, refill_min=None, guidance=None,
+                        **kw):
         """sample_batched(mixed_prompts=True, kv="shared_prefix") over a whole data set with the finished clips' slots refilled in
         flight (sample_inflight_loop: continuous batching): tokens [n, L], prompt_length n lengths; `slots` clips x num_samples
         sequences stay resident; max_new_tokens: a budget per clip (None: tokens_to_generate); top_k=1 is a greedy captioner.
         -> a namespace: tokens [n * num_samples, final_len], written [n], scores (SampleScores or None), steps, prefills"""
+        _no_inflight_guidance(guidance, "sample_inflight")
         return sample_inflight_loop(_sampler_config(self, top_k, top_p), make_inflight_state_fn(self, decode_weights), tokens,
                                     query_embeds=query_embeds, temperature=temperature, num_samples=num_samples, slots=slots, seed=seed,
                                     streams=streams, max_new_tokens=max_new_tokens, refill_min=refill_min, constraints=constraints,
@@ -1873,11 +2014,12 @@ def install(gpt_cls):
 
     def beam_search_inflight(self, tokens, query_embeds=None, beam_size=5, num_return_gen=1, stop_token=None, prompt_length=None, slots=32,
                              max_new_tokens=None, refill_min=None, beam_groups=1, diversity_penalty=0.0, constraints=None,
-                             decode_weights="bf16", **kw):
+                             decode_weights="bf16", guidance=None, **kw):
         """beam_search_batched(kv="shared_prefix") over a whole data set with the finished clips' slots refilled in flight
         (beam_inflight_loop): tokens [n, L], prompt_length n lengths; `slots` clips x beam_groups * beam_size sequences stay resident;
         max_new_tokens: a budget per clip (None: the lockstep search's, up to the end of the table).  -> a namespace: results (the
         list of n results of beam_search_batched), steps, prefills"""
+        _no_inflight_guidance(guidance, "beam_search_inflight")
         return beam_inflight_loop(_gen_config(self), make_inflight_state_fn(self, decode_weights), tokens, query_embeds=query_embeds,
                                   beam_size=beam_size, num_return_gen=num_return_gen, stop_token=stop_token, prompt_length=prompt_length,
                                   slots=slots, max_new_tokens=max_new_tokens, refill_min=refill_min, beam_groups=beam_groups,
@@ -1904,6 +2046,8 @@ def install(gpt_cls):
             if kw.pop("constraints", None) is not None:
                 raise ValueError('constraints need a lockstep loop: do_sample=True with sampler="device", or beam_search_batched')
             _no_sample_scores(kw.pop("return_scores", False), "generate without do_sample=True and sampler=\"device\"")
+            if kw.pop("guidance", None) is not None:
+                raise ValueError('guidance needs a lockstep loop: do_sample=True with sampler="device", or beam_search_batched')
         was = self.training
         self.eval()
         try:

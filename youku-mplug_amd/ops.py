@@ -5,6 +5,7 @@ stream.  No CPU / eager fallback exists: non-CUDA tensors raise.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional, Tuple
 
 import os
@@ -1031,6 +1032,29 @@ def logits_constrain_steps(logits, tokens, *, row_step, constraints, prompt_len,
     device; row r's history ends in front of column prompt_len[r] + row_step[r] and row_step[r] tokens count as generated.  A row with
     a negative step, or whose column lies behind the table, is left alone.  -> logits"""
     return _logits_constrain("logits_constrain_steps", **locals())
+
+
+def logits_guide(cond, uncond, *, scale, alpha=0.0, ban_value=float("-inf"), vocab=None):
+    """One step's guidance, in place and in one launch (include/mpv.h: mpv_logits_guide): cond bf16 [rows, ld_c] becomes
+    bf16(c + (scale - 1) * (c - u)) on the max-centred rows c, u of cond and uncond bf16 [rows, ld_u] (read only; it may be other rows
+    of cond's allocation), over the first `vocab` columns.  alpha in (0, 1): a token whose conditional probability is below alpha times
+    the row's largest becomes ban_value (-inf for the sampler, the lowest finite bf16 in front of logprob_topk); 0: off.  scale - 1 and
+    log(alpha) are computed here, on the host, and passed as fp32.  -> cond"""
+    _need_cuda(cond, uncond)
+    for name, t in (("cond", cond), ("uncond", uncond)):
+        if t.dtype != torch.bfloat16 or t.ndim != 2 or t.stride(1) != 1:
+            raise _lib.MpvError(f"logits_guide: {name} must be bf16 [rows, ld] with unit column stride (got {t.dtype} {tuple(t.shape)})")
+    if uncond.shape[0] != cond.shape[0]:
+        raise _lib.MpvError(f"logits_guide: cond has {cond.shape[0]} rows, uncond {uncond.shape[0]}")
+    alpha = float(alpha)
+    if not 0.0 <= alpha <= 1.0:                           # (NaN fails both comparisons)
+        raise _lib.MpvError(f"logits_guide: alpha ({alpha}) must be in [0, 1]")
+    d = _lib.LogitsGuideDesc()
+    d.cond, d.uncond, d.ld_c, d.ld_u = _p(cond), _p(uncond), cond.stride(0), uncond.stride(0)
+    d.rows, d.vocab = cond.shape[0], int(vocab) if vocab is not None else min(cond.shape[-1], uncond.shape[-1])
+    d.scale_m1, d.plaus_log, d.ban_value = float(scale) - 1.0, math.log(alpha) if alpha > 0.0 else float("-inf"), float(ban_value)
+    check(_lib.lib().mpv_logits_guide(C.byref(d), _stream()), "mpv_logits_guide")
+    return cond
 
 
 def _logits_trie_mask(entry, logits, tokens, *, pos=None, step=None, row_step=None, trie, prompt_len, prompt_len_all=0, eos_ids, ban_value,
