@@ -19,6 +19,7 @@ package and tokenizer are imported from PYTHONPATH, untouched."""
 import argparse
 import datetime
 import json
+import math
 import os
 import random
 import sys
@@ -185,13 +186,31 @@ def _targets(lists, rows, device):
     return torch.tensor([l + [-1] * (width - len(l)) for l in lists], dtype=torch.long, device=device).reshape(len(lists), width)
 
 
+def load_eval_bank(path, dim):
+    """`--eval_bank FILE`: a .pt holding {"text": bf16 [n, dim], "video": bf16 [m, dim]}, query features of the training set (the
+    QB-Norm setting).  Anything else is refused here, before any search."""
+    bank = torch.load(path, map_location="cpu")
+    if not isinstance(bank, dict) or not {"text", "video"} <= set(bank):
+        raise ValueError(f"--eval_bank {path}: expected a dict with the keys 'text' and 'video'")
+    for side in ("text", "video"):
+        t = bank[side]
+        if not torch.is_tensor(t) or t.dtype != torch.bfloat16 or t.dim() != 2 or t.shape[0] == 0 or t.shape[1] != dim:
+            raise ValueError(f"--eval_bank {path}: '{side}' must be a non-empty bfloat16 [n, {dim}] tensor (got "
+                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))})")
+    return {"text": bank["text"], "video": bank["video"]}
+
+
 @torch.no_grad()
-def evaluation_on_device(model, data_loader, tokenizer, device, config, index_fp8=False):
+def evaluation_on_device(model, data_loader, tokenizer, device, config, index_fp8=False, inverted_softmax=None, bank=None):
     """-> (ranks_v2t int32 [videos], ranks_t2v int32 [texts]) as numpy arrays: `--eval_on_device`.  The features are those of
     `evaluation` (same towers, same chunking); they go into a text index and a video index and every query is ranked against the
     full gallery on the device (RetrievalIndex.rank) -- no score matrix on the device or the host.  Under a process group each
     rank ranks its share of the queries and the rank vectors are all-gathered.  index_fp8 (`--eval_index_fp8`): the galleries
-    are RetrievalIndex(storage="fp8")."""
+    are RetrievalIndex(storage="fp8").
+    inverted_softmax (`--eval_inverted_softmax BETA`): every gallery row g is normalised by lse[g] = log sum_b exp(BETA <b, g>) over a
+    bank of queries of the direction that searches it, and the ranks are those of BETA <q, g> - lse[g] (RetrievalIndex.
+    fit_normaliser).  bank None: the bank is the evaluation's own queries of that direction -- the dual-softmax setting, which
+    assumes that all test queries are known at once; bank {"text", "video"} (load_eval_bank): training queries, QB-Norm."""
     from youku_mplug_amd.retrieval import RetrievalIndex
     module = getattr(model, "module", model)
     module.eval()
@@ -221,6 +240,17 @@ def evaluation_on_device(model, data_loader, tokenizer, device, config, index_fp
     if not fp8:
         text_gallery, video_gallery = text_index, video_index
     print(f"index bytes: video {video_gallery.nbytes} ({video_gallery.storage}), text {text_gallery.nbytes} ({text_gallery.storage})")
+    if inverted_softmax is not None:
+        beta = float(inverted_softmax)
+        own = bank is None
+        text_bank = text_index.features if own else bank["text"].to(device)
+        video_bank = video_index.features if own else bank["video"].to(device)
+        text_gallery.fit_normaliser(video_bank, beta)          # titles are searched by clips
+        video_gallery.fit_normaliser(text_bank, beta)          # clips are searched by titles
+        print(f"inverted softmax, beta {beta:g}: " + (
+            f"the bank is the evaluation's own queries ({len(video_bank)} clips for the titles, {len(text_bank)} titles for the clips): "
+            "dual softmax, which assumes that all test queries are known at once" if own else
+            f"the bank is {len(video_bank)} clip and {len(text_bank)} title features of --eval_bank (QB-Norm)"))
     world, rank = (dist.get_world_size(), dist.get_rank()) if dist.is_available() and dist.is_initialized() else (1, 0)
 
     def ranks_of(queries, gallery, lists):
@@ -308,10 +338,15 @@ def main(args, config):
                                             warmup_steps=getattr(args, "warmup_steps", -1), sched_type=getattr(args, "lr_sched_type", "cos"))
     wd_values = mpv_engine.cosine_scheduler(args.weight_decay, args.weight_decay, args.epochs, steps_per_epoch)
 
+    eval_bank = None
+    if getattr(args, "eval_bank", None):
+        eval_bank = load_eval_bank(args.eval_bank, int(config.get("contrastive_embed_dim", 256)))
+
     def evaluate(loader, name):
         if getattr(args, "eval_on_device", False):
             result = recall_from_ranks(*evaluation_on_device(model, loader, tokenizer, device, config,
-                                                              index_fp8=getattr(args, "eval_index_fp8", False)))
+                                                              index_fp8=getattr(args, "eval_index_fp8", False),
+                                                              inverted_softmax=getattr(args, "eval_inverted_softmax", None), bank=eval_bank))
         else:
             v2t, t2v = evaluation(model, loader, tokenizer, device, config)
             result = itm_eval(v2t, t2v, loader.dataset.txt2vid, loader.dataset.vid2txt)
@@ -370,10 +405,24 @@ def get_args(argv=None):
                    help="with --eval_on_device: rank against galleries kept as e4m3 codes with one scale per row (half the index bytes); "
                         "the ranks are exactly those of bf16 galleries of the dequantised rows, so the run measures what the rounding "
                         "does to recall")
+    p.add_argument("--eval_inverted_softmax", default=None, type=float, metavar="BETA",
+                   help="with --eval_on_device: hubness correction (inverted softmax / QB-Norm).  Rank by BETA * <q, g> - log sum_b "
+                        "exp(BETA * <b, g>) over a bank of queries b.  Without --eval_bank the bank is the evaluation's own queries of "
+                        "each direction (dual softmax: assumes all test queries are known at once).  No recall figure on trained "
+                        "features exists for this path")
+    p.add_argument("--eval_bank", default=None, metavar="FILE",
+                   help="with --eval_inverted_softmax: a .pt holding {'text': bf16 [n, D], 'video': bf16 [m, D]}, query features of the "
+                        "training set, used as the bank instead of the test queries (the QB-Norm setting)")
     p.add_argument("--synthetic_steps", default=0, type=int, help="run on N synthetic batches per epoch instead of the dataset")
     args, _ = p.parse_known_args(argv)
     if args.eval_index_fp8 and not args.eval_on_device:
         p.error("--eval_index_fp8 needs --eval_on_device: only the on-device evaluation searches an index")
+    if args.eval_inverted_softmax is not None and not args.eval_on_device:
+        p.error("--eval_inverted_softmax needs --eval_on_device: the correction is a per-row term of the on-device search")
+    if args.eval_inverted_softmax is not None and not math.isfinite(args.eval_inverted_softmax):
+        p.error("--eval_inverted_softmax needs a finite BETA")
+    if args.eval_bank and args.eval_inverted_softmax is None:
+        p.error("--eval_bank needs --eval_inverted_softmax BETA")
     config = yaml.load(open(args.config, "r"), Loader=_ConfigLoader)
     Path(args.output_dir).mkdir(parents=True, exist_ok=True)
     for section in ("optimizer", "schedular"):

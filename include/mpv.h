@@ -1326,6 +1326,56 @@ int mpv_maxsim_rank_q8(const mpv_maxsim_search_desc* d, const float* g_scale, co
                        void* workspace, size_t workspace_bytes, mpv_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Searches with per-row priors (filtering, weighting, hubness correction; csrc/search_common.h ScPrior).  mpv_sim_topk / mpv_sim_rank
+ * and their *_q8 forms with one fp32 additive term per GALLERY row: g_prior, ng entries, 4-byte aligned.  The descriptor is unchanged;
+ * the q8 entries take g_scale, then g_prior.
+ *   score    s'(q, g) = fl(fl(scale * s(q, g)) + g_prior[g]).  s(q, g) is exactly what the plain entry computes (for codes,
+ *            fl(g_scale[g] * acc) first); the multiplication and the addition are two separately rounded fp32 operations, never a
+ *            fused multiply-add, so a plain fp32 restatement reproduces s' bit for bit from the accumulator.
+ *   rank     scale IS applied in mpv_sim_rank_prior*, unlike mpv_sim_rank: with an additive term the order depends on it.  The target
+ *            scores go through the stream's own code path, the multiply and the add included.
+ *   -inf     a row whose s' is NaN or -inf is not eligible: it is never returned, beats nothing, and as a target counts as no
+ *            target.  A term of -inf is therefore a filter.  A row with s' = +inf is ordinary (first, by index).  A query with fewer
+ *            than k eligible rows gets the (-inf, -1) tail.
+ *   rules    order rule, tie rule, `slices` independence, workspace conventions and refusal style of the plain entries; the q8
+ *            entries equal the bf16 ones on deq(code) * g_scale bit for bit under the conditions stated above.
+ * Refused (negative code, *_workspace_size 0, before any launch) beyond what the plain entry refuses: a null or misaligned g_prior.
+ *
+ * mpv_sim_bank_lse: lse fp32 [ng], lse[g] = log sum_{b < nb} exp(beta * <bank_b, gallery_g>), the products being the bf16-MFMA /
+ *   fp32 ones of the searches.  With g_prior = -lse and scale = beta the searches above return the inverted-softmax (QB-Norm; with
+ *   the test queries as the bank, dual-softmax) scores beta * s(q, g) - lse[g].  bank bf16 [nb][dim], gallery bf16 [ng][dim] (or
+ *   codes, for *_q8, with g_scale), row strides and alignment as in the search descriptors; nb, ng in [1, 2^31 - 1]; dim a
+ *   multiple of 32 in [32, 1024]; beta finite (any size: the sum is kept against a running max, nothing overflows).
+ *   lse[g] is a function of (bank, beta, gallery row g) alone, bit for bit: the same whether the row is scored alone or among
+ *   others, at whatever position, for whatever ng, however often.  No atomics; the bank is not cut into slices.  A NaN product
+ *   makes that row's lse NaN.  The q8 entry is bit for bit the bf16 entry on the rows bf16(deq(code) * g_scale).
+ *   The workspace is not used (its size is a nominal 256 bytes, 0 for a descriptor the call would refuse); it may be null. */
+size_t mpv_sim_topk_prior_workspace_size(const mpv_sim_search_desc* d, const float* g_prior);
+int mpv_sim_topk_prior(const mpv_sim_search_desc* d, const float* g_prior, float* vals, int64_t* idx, void* workspace,
+                       size_t workspace_bytes, mpv_stream_t stream);
+size_t mpv_sim_rank_prior_workspace_size(const mpv_sim_search_desc* d, const float* g_prior, int n_targets);
+int mpv_sim_rank_prior(const mpv_sim_search_desc* d, const float* g_prior, const int64_t* target, int n_targets, int32_t* rank,
+                       void* workspace, size_t workspace_bytes, mpv_stream_t stream);
+size_t mpv_sim_topk_prior_q8_workspace_size(const mpv_sim_search_desc* d, const float* g_scale, const float* g_prior);
+int mpv_sim_topk_prior_q8(const mpv_sim_search_desc* d, const float* g_scale, const float* g_prior, float* vals, int64_t* idx,
+                          void* workspace, size_t workspace_bytes, mpv_stream_t stream);
+size_t mpv_sim_rank_prior_q8_workspace_size(const mpv_sim_search_desc* d, const float* g_scale, const float* g_prior, int n_targets);
+int mpv_sim_rank_prior_q8(const mpv_sim_search_desc* d, const float* g_scale, const float* g_prior, const int64_t* target,
+                          int n_targets, int32_t* rank, void* workspace, size_t workspace_bytes, mpv_stream_t stream);
+typedef struct mpv_sim_bank_desc {
+  const void *bank, *gallery;
+  int64_t b_rs, g_rs;
+  int64_t nb, ng;
+  int dim;
+  float beta;
+} mpv_sim_bank_desc;
+size_t mpv_sim_bank_lse_workspace_size(const mpv_sim_bank_desc* d);
+int mpv_sim_bank_lse(const mpv_sim_bank_desc* d, float* lse, void* workspace, size_t workspace_bytes, mpv_stream_t stream);
+size_t mpv_sim_bank_lse_q8_workspace_size(const mpv_sim_bank_desc* d, const float* g_scale);
+int mpv_sim_bank_lse_q8(const mpv_sim_bank_desc* d, const float* g_scale, float* lse, void* workspace, size_t workspace_bytes,
+                        mpv_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Optimizer (DeepSpeed FusedAdam + global-norm clip, run_pretrain_distributed_gpt3.py:137;
  * math of optim/adamw.py:66-115; torch.nn.utils.clip_grad_norm_ semantics, utils.py:308).
  * sumsq (fp32 scalar, pre-zeroed) += sum g^2 over n bf16 gradients -- BIT-REPRODUCIBLE since round 6: per-workgroup partial sums in

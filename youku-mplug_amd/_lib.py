@@ -109,6 +109,13 @@ class SimSearchDesc(C.Structure):
     ]
 
 
+class SimBankDesc(C.Structure):
+    _fields_ = [
+        ("bank", c_void_p), ("gallery", c_void_p), ("b_rs", c_int64), ("g_rs", c_int64), ("nb", c_int64), ("ng", c_int64),
+        ("dim", c_int), ("beta", c_float),
+    ]
+
+
 class MaxSimSearchDesc(C.Structure):
     _fields_ = [
         ("queries", c_void_p), ("gallery", c_void_p), ("q_rs", c_int64), ("g_rs", c_int64), ("nq", c_int64), ("ng", c_int64),
@@ -289,6 +296,20 @@ _SIGS = {
     "mpv_maxsim_topk_q8": (c_int, [C.POINTER(MaxSimSearchDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mpv_maxsim_rank_q8_workspace_size": (c_size_t, [C.POINTER(MaxSimSearchDesc), c_void_p, c_int]),
     "mpv_maxsim_rank_q8": (c_int, [C.POINTER(MaxSimSearchDesc), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # searches with per-row priors, and the bank pass of the inverted-softmax correction
+    "mpv_sim_topk_prior_workspace_size": (c_size_t, [C.POINTER(SimSearchDesc), c_void_p]),
+    "mpv_sim_topk_prior": (c_int, [C.POINTER(SimSearchDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mpv_sim_rank_prior_workspace_size": (c_size_t, [C.POINTER(SimSearchDesc), c_void_p, c_int]),
+    "mpv_sim_rank_prior": (c_int, [C.POINTER(SimSearchDesc), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mpv_sim_topk_prior_q8_workspace_size": (c_size_t, [C.POINTER(SimSearchDesc), c_void_p, c_void_p]),
+    "mpv_sim_topk_prior_q8": (c_int, [C.POINTER(SimSearchDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mpv_sim_rank_prior_q8_workspace_size": (c_size_t, [C.POINTER(SimSearchDesc), c_void_p, c_void_p, c_int]),
+    "mpv_sim_rank_prior_q8": (c_int, [C.POINTER(SimSearchDesc), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t,
+                                      c_void_p]),
+    "mpv_sim_bank_lse_workspace_size": (c_size_t, [C.POINTER(SimBankDesc)]),
+    "mpv_sim_bank_lse": (c_int, [C.POINTER(SimBankDesc), c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mpv_sim_bank_lse_q8_workspace_size": (c_size_t, [C.POINTER(SimBankDesc), c_void_p]),
+    "mpv_sim_bank_lse_q8": (c_int, [C.POINTER(SimBankDesc), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mpv_grad_sumsq_workspace_size": (c_size_t, []),
     "mpv_grad_sumsq": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mpv_adamw_step": (c_int, [c_void_p] * 5 + [c_int64] + [c_float] * 5 + [c_int, c_float, c_void_p, c_float, c_void_p]),

@@ -54,6 +54,7 @@ struct RsArgs {
   const float* tscore;       // rank: [nq][n_t]
   int* counts;               // rank: [nq][n_t], zeroed
   const float* g_scale;      // *_q8: G points to e4m3 codes, g_rs counts codes, one scale per gallery row
+  const float* g_prior;      // *_prior: one additive term per gallery row; the score is fl(fl(scale * s) + g_prior[g])
 };
 
 // The stream, written once over the gallery's source type: bf16 rows (sim_stream_kernel) or e4m3 codes with row scales
@@ -105,14 +106,21 @@ __device__ __forceinline__ void sim_stream_body(const RsArgs& a, const Src G) {
       // past INT_MAX; such rows fail g < uend and are never used as an index.
       const unsigned base = (unsigned)row0 + 4 * half;
       if constexpr (ScSource<Src>::scaled) sc_scale_acc(acc, gbuf, lane);
+      // with a term the score of both modes is fl(fl(scale * s) + term), and a row that ends up at -inf (or NaN) is not there at all
+      auto with_prior = [&](float s, int i) { return sc_prior_score(s, a.scale, sc_row_prior(gbuf, 8 * (i >> 2) + 4 * half + (i & 3))); };
       if (MODE == 0) {
         // one insertion site (the list code is 3 ops x KMAX slots): mark the scores that beat the list, then take them one by one
         unsigned m = 0;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          acc[i] *= a.scale;
+          if constexpr (ScSource<Src>::prior)
+            acc[i] = with_prior(acc[i], i);
+          else
+            acc[i] *= a.scale;
           const unsigned g = base + 8 * (i >> 2) + (i & 3);
-          m |= (g < uend && top.beats(acc[i], (int)g)) ? 1u << i : 0u;
+          bool in = g < uend;
+          if constexpr (ScSource<Src>::prior) in = in && sc_eligible(acc[i]);      // (-inf, g) would beat the list's filler
+          m |= (in && top.beats(acc[i], (int)g)) ? 1u << i : 0u;
         }
         while (m) {                                  // rare once the list has settled
           const int i = __builtin_ctz(m);
@@ -124,6 +132,10 @@ __device__ __forceinline__ void sim_stream_body(const RsArgs& a, const Src G) {
           if (top.beats(v, g)) top.insert(v, g);          // the threshold may have risen since the marking
         }
       } else {
+        if constexpr (ScSource<Src>::prior) {
+#pragma unroll
+          for (int i = 0; i < 16; ++i) acc[i] = with_prior(acc[i], i);
+        }
         for (int t = 0; t < a.n_t; ++t) {
           const int tg = rk.ti[l32 * a.n_t + t];
           const float ts = rk.tv[l32 * a.n_t + t];
@@ -200,6 +212,15 @@ template <int MODE, int KMAX>
 __global__ __launch_bounds__(64 * SC_WAVES) void q8_stream_kernel(RsArgs a) {
   sim_stream_body<MODE, KMAX>(a, ScCodes{(const uint8_t*)a.G, a.g_scale});
 }
+// the instances with a per-row term (mpv_sim_*_prior, mpv_sim_*_prior_q8)
+template <int MODE, int KMAX>
+__global__ __launch_bounds__(64 * SC_WAVES) __attribute__((amdgpu_waves_per_eu(KMAX == 16 ? 3 : 1))) void pri_stream_kernel(RsArgs a) {
+  sim_stream_body<MODE, KMAX>(a, ScPrior<const bf16*>{a.G, a.g_prior});
+}
+template <int MODE, int KMAX>
+__global__ __launch_bounds__(64 * SC_WAVES) void pri8_stream_kernel(RsArgs a) {
+  sim_stream_body<MODE, KMAX>(a, ScPrior<ScCodes>{ScCodes{(const uint8_t*)a.G, a.g_scale}, a.g_prior});
+}
 
 // Scores of the target rows, through the stream's staging and MFMA functions: one wave = 32 queries x target slot t, tile row j
 // is the target row of query j, the score is the tile's diagonal.
@@ -234,11 +255,23 @@ __device__ __forceinline__ void sim_target_body(const RsArgs& a, const Src G, fl
 #pragma unroll
   for (int i = 0; i < 16; ++i) v = i == want ? acc[i] : v;
   if constexpr (ScSource<Src>::scaled) v *= sc_row_scale(gbuf, l32);
+  if constexpr (ScSource<Src>::prior) {
+    // the stream's own multiply and add; a target that is not eligible is written as NaN, which the stream never counts
+    // against and the finish kernel takes for "no target"
+    v = sc_prior_score(v, a.scale, sc_row_prior(gbuf, l32));
+    v = sc_eligible(v) ? v : __builtin_nanf("");
+  }
   if (half == ((l32 >> 2) & 1) && q0 + l32 < a.nq) tscore[(long long)(q0 + l32) * a.n_t + t] = v;
 }
 __global__ __launch_bounds__(64) void sim_target_kernel(RsArgs a, float* __restrict__ tscore) { sim_target_body(a, a.G, tscore); }
 __global__ __launch_bounds__(64) void q8_target_kernel(RsArgs a, float* __restrict__ tscore) {
   sim_target_body(a, ScCodes{(const uint8_t*)a.G, a.g_scale}, tscore);
+}
+__global__ __launch_bounds__(64) void pri_target_kernel(RsArgs a, float* __restrict__ tscore) {
+  sim_target_body(a, ScPrior<const bf16*>{a.G, a.g_prior}, tscore);
+}
+__global__ __launch_bounds__(64) void pri8_target_kernel(RsArgs a, float* __restrict__ tscore) {
+  sim_target_body(a, ScPrior<ScCodes>{ScCodes{(const uint8_t*)a.G, a.g_scale}, a.g_prior}, tscore);
 }
 
 // One workgroup per query: k rounds; round j writes the best workspace entry that the entry written in round j - 1 beats.  The
@@ -332,14 +365,28 @@ struct RsPlan {
   int qtiles, slices, per_slice;
 };
 
-// `codes`: the gallery is e4m3 codes with the row scales g_scale (the *_q8 entries), which adds sc_check_codes to the checks
-int rs_plan(const mpv_sim_search_desc* d, RsPlan* p, const char* what, int topk_k = 0, bool codes = false, const float* g_scale = nullptr) {
+// What a gallery is searched as: `codes`, e4m3 codes with the row scales g_scale (the *_q8 entries), which adds sc_check_codes to
+// the checks; `prior`, with the per-row terms g_prior (the *_prior entries), which have to exist and be 4-byte aligned.
+struct RsKind {
+  bool codes;
+  const float* g_scale;
+  bool prior;
+  const float* g_prior;
+};
+
+int rs_plan(const mpv_sim_search_desc* d, RsPlan* p, const char* what, int topk_k = 0, RsKind kind = {}) {
+  const bool codes = kind.codes;
+  const float* g_scale = kind.g_scale;
   MPV_REQUIRE(d && d->queries && d->gallery, MPV_E_ARG, "%s: null pointer", what);
   MPV_REQUIRE(d->nq > 0 && d->ng > 0 && d->nq <= 65535ll * SC_TILE /* grid.y */ && d->ng <= 0x7fffffffll, MPV_E_SHAPE,
               "%s: bad shape nq=%lld ng=%lld", what, (long long)d->nq, (long long)d->ng);
   int rc = sc_check_desc(what, d->queries, d->gallery, d->dim, d->q_rs, d->g_rs, d->slices);
   if (rc == MPV_OK && codes) rc = sc_check_codes(what, d->gallery, d->g_rs, g_scale);
   if (rc != MPV_OK) return rc;
+  if (kind.prior) {
+    MPV_REQUIRE(kind.g_prior, MPV_E_ARG, "%s: null g_prior", what);
+    MPV_REQUIRE(((uintptr_t)kind.g_prior & 3) == 0, MPV_E_ALIGN, "%s: g_prior must be 4-byte aligned", what);
+  }
   const long long supers = (d->ng + RS_SUPER - 1) / RS_SUPER;
   p->qtiles = (int)((d->nq + SC_TILE - 1) / SC_TILE);
   // 0 = choose: 3 workgroups per CU over the 256 CUs, at least 4 super-tiles (512 rows) each
@@ -359,7 +406,7 @@ int rs_plan(const mpv_sim_search_desc* d, RsPlan* p, const char* what, int topk_
   return MPV_OK;
 }
 
-RsArgs rs_args(const mpv_sim_search_desc* d, const RsPlan& p, const float* g_scale) {
+RsArgs rs_args(const mpv_sim_search_desc* d, const RsPlan& p, RsKind kind) {
   RsArgs a = {};
   a.Q = (const bf16*)d->queries;
   a.G = (const bf16*)d->gallery;
@@ -370,37 +417,44 @@ RsArgs rs_args(const mpv_sim_search_desc* d, const RsPlan& p, const float* g_sca
   a.D = d->dim;
   a.per_slice = p.per_slice;
   a.scale = 1.0f;
-  a.g_scale = g_scale;
+  a.g_scale = kind.g_scale;
+  a.g_prior = kind.g_prior;
   return a;
 }
 
 // The entry points, each written once for both gallery types (`codes`: the *_q8 form).  `names`: the entry point, then its stages.
-size_t rs_topk_ws(const char* what, const mpv_sim_search_desc* d, bool codes, const float* g_scale) {
+size_t rs_topk_ws(const char* what, const mpv_sim_search_desc* d, RsKind kind) {
   RsPlan p;
-  if (!d || d->k < 1 || d->k > SC_MAX_K || rs_plan(d, &p, what, d->k, codes, g_scale) != MPV_OK) return 0;
+  if (!d || d->k < 1 || d->k > SC_MAX_K || rs_plan(d, &p, what, d->k, kind) != MPV_OK) return 0;
   return sc_ws_bytes((size_t)p.slices * (size_t)d->nq * d->k);
 }
 
-int rs_topk(const char* const names[2], const mpv_sim_search_desc* d, bool codes, const float* g_scale, float* vals, int64_t* idx,
-            void* workspace, size_t workspace_bytes, hipStream_t stream) {
+// the top-k stream instance of a kind for list length KMAX
+template <int KMAX>
+void (*rs_topk_kernel(RsKind kind))(RsArgs) {
+  if (kind.prior) return kind.codes ? pri8_stream_kernel<0, KMAX> : pri_stream_kernel<0, KMAX>;
+  return kind.codes ? q8_stream_kernel<0, KMAX> : sim_stream_kernel<0, KMAX>;
+}
+
+int rs_topk(const char* const names[2], const mpv_sim_search_desc* d, RsKind kind, float* vals, int64_t* idx, void* workspace,
+            size_t workspace_bytes, hipStream_t stream) {
   const char* what = names[0];
   RsPlan p;
   MPV_REQUIRE(d, MPV_E_ARG, "%s: null descriptor", what);
   MPV_REQUIRE(d->k >= 1 && d->k <= SC_MAX_K, MPV_E_ARG, "%s: k (%d) must be in [1, %d]", what, d->k, SC_MAX_K);
-  int rc = rs_plan(d, &p, what, d->k, codes, g_scale);
+  int rc = rs_plan(d, &p, what, d->k, kind);
   if (rc != MPV_OK) return rc;
   MPV_REQUIRE(vals && idx && workspace, MPV_E_ARG, "%s: null pointer", what);
   const size_t n = (size_t)p.slices * (size_t)d->nq * d->k;
   rc = sc_ws_check(what, workspace, workspace_bytes, n);
   if (rc != MPV_OK) return rc;
-  RsArgs a = rs_args(d, p, g_scale);
+  RsArgs a = rs_args(d, p, kind);
   a.k = d->k;
   a.scale = d->scale;
   a.ws_val = (float*)workspace;
   a.ws_idx = (int*)sc_ws_upper(workspace, n);
   const size_t lds = sc_stream_lds(d->dim, SC_WAVES, (size_t)SC_WAVES * d->k * 32 * 8);
-  auto kern = d->k <= 4 ? sim_stream_kernel<0, 4> : d->k <= 16 ? sim_stream_kernel<0, 16> : sim_stream_kernel<0, 32>;
-  if (codes) kern = d->k <= 4 ? q8_stream_kernel<0, 4> : d->k <= 16 ? q8_stream_kernel<0, 16> : q8_stream_kernel<0, 32>;
+  auto kern = d->k <= 4 ? rs_topk_kernel<4>(kind) : d->k <= 16 ? rs_topk_kernel<16>(kind) : rs_topk_kernel<32>(kind);
   sc_allow_lds((const void*)kern, lds);
   hipLaunchKernelGGL(kern, dim3((unsigned)p.slices, (unsigned)p.qtiles), dim3(64 * SC_WAVES), lds, stream, a);
   rc = mpv_check_launch(what);
@@ -408,18 +462,19 @@ int rs_topk(const char* const names[2], const mpv_sim_search_desc* d, bool codes
   return sc_merge_slices(names[1], a.ws_val, a.ws_idx, vals, idx, a.nq, a.k, p.slices, stream);
 }
 
-int rs_rank(const char* const names[3], const mpv_sim_search_desc* d, bool codes, const float* g_scale, const int64_t* target,
-            int n_targets, int32_t* rank, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+int rs_rank(const char* const names[3], const mpv_sim_search_desc* d, RsKind kind, const int64_t* target, int n_targets, int32_t* rank,
+            void* workspace, size_t workspace_bytes, hipStream_t stream) {
   const char* what = names[0];
   RsPlan p;
-  int rc = rs_plan(d, &p, what, 0, codes, g_scale);
+  int rc = rs_plan(d, &p, what, 0, kind);
   if (rc != MPV_OK) return rc;
   MPV_REQUIRE(target && rank && workspace, MPV_E_ARG, "%s: null pointer", what);
   MPV_REQUIRE(n_targets >= 1 && n_targets <= SC_MAX_T, MPV_E_ARG, "%s: n_targets (%d) must be in [1, %d]", what, n_targets, SC_MAX_T);
   const size_t n = (size_t)d->nq * n_targets;
   rc = sc_ws_check(what, workspace, workspace_bytes, n);
   if (rc != MPV_OK) return rc;
-  RsArgs a = rs_args(d, p, g_scale);
+  RsArgs a = rs_args(d, p, kind);
+  if (kind.prior) a.scale = d->scale;                 // with an additive term the order depends on the scale
   a.n_t = n_targets;
   a.target = target;
   float* tscore = (float*)workspace;
@@ -430,25 +485,37 @@ int rs_rank(const char* const names[3], const mpv_sim_search_desc* d, bool codes
     return MPV_E_HIP;
   }
   const size_t lds_t = sc_stream_lds(d->dim, 1, 0);
-  auto tkern = codes ? q8_target_kernel : sim_target_kernel;
+  auto tkern = kind.prior ? (kind.codes ? pri8_target_kernel : pri_target_kernel) : (kind.codes ? q8_target_kernel : sim_target_kernel);
   sc_allow_lds((const void*)tkern, lds_t);
   hipLaunchKernelGGL(tkern, dim3((unsigned)n_targets, (unsigned)p.qtiles), dim3(64), lds_t, stream, a, tscore);
   rc = mpv_check_launch(names[1]);
   if (rc != MPV_OK) return rc;
   const size_t lds = sc_stream_lds(d->dim, SC_WAVES, (size_t)SC_TILE * n_targets * 12);
-  auto kern = codes ? q8_stream_kernel<1, 1> : sim_stream_kernel<1, 1>;
+  auto kern = kind.prior ? (kind.codes ? pri8_stream_kernel<1, 1> : pri_stream_kernel<1, 1>)
+                         : (kind.codes ? q8_stream_kernel<1, 1> : sim_stream_kernel<1, 1>);
   sc_allow_lds((const void*)kern, lds);
   hipLaunchKernelGGL(kern, dim3((unsigned)p.slices, (unsigned)p.qtiles), dim3(64 * SC_WAVES), lds, stream, a);
   rc = mpv_check_launch(what);
   if (rc != MPV_OK) return rc;
-  // no target scores: a target whose score is NaN still counts as a target here (mpv_maxsim_rank skips it)
-  return sc_rank_finish(names[2], target, nullptr, a.counts, rank, a.nq, n_targets, a.ng, stream);
+  // no target scores: a target whose score is NaN still counts as a target here (mpv_maxsim_rank skips it); with a term, a
+  // target that is not eligible carries a NaN score (pri_target_kernel) and is no target
+  return sc_rank_finish(names[2], target, kind.prior ? tscore : nullptr, a.counts, rank, a.nq, n_targets, a.ng, stream);
 }
 
 const char* const RS_TOPK[2] = {"mpv_sim_topk", "mpv_sim_topk (merge)"};
 const char* const RS_TOPK_Q8[2] = {"mpv_sim_topk_q8", "mpv_sim_topk_q8 (merge)"};
 const char* const RS_RANK[3] = {"mpv_sim_rank", "mpv_sim_rank (target scores)", "mpv_sim_rank (finish)"};
 const char* const RS_RANK_Q8[3] = {"mpv_sim_rank_q8", "mpv_sim_rank_q8 (target scores)", "mpv_sim_rank_q8 (finish)"};
+const char* const RS_TOPK_PRI[2] = {"mpv_sim_topk_prior", "mpv_sim_topk_prior (merge)"};
+const char* const RS_TOPK_PRI8[2] = {"mpv_sim_topk_prior_q8", "mpv_sim_topk_prior_q8 (merge)"};
+const char* const RS_RANK_PRI[3] = {"mpv_sim_rank_prior", "mpv_sim_rank_prior (target scores)", "mpv_sim_rank_prior (finish)"};
+const char* const RS_RANK_PRI8[3] = {"mpv_sim_rank_prior_q8", "mpv_sim_rank_prior_q8 (target scores)", "mpv_sim_rank_prior_q8 (finish)"};
+
+size_t rs_rank_ws(const char* what, const mpv_sim_search_desc* d, RsKind kind, int n_targets) {
+  RsPlan p;                                           // a descriptor the call would refuse: 0
+  if (n_targets < 1 || n_targets > SC_MAX_T || rs_plan(d, &p, what, 0, kind) != MPV_OK) return 0;
+  return sc_ws_bytes((size_t)d->nq * n_targets);
+}
 
 }  // namespace
 
@@ -467,11 +534,11 @@ int sc_rank_finish(const char* what, const int64_t* target, const float* tscore,
 }
 
 extern "C" size_t mpv_sim_topk_workspace_size(const mpv_sim_search_desc* d) {
-  return rs_topk_ws("mpv_sim_topk_workspace_size", d, false, nullptr);
+  return rs_topk_ws("mpv_sim_topk_workspace_size", d, RsKind{});
 }
 extern "C" int mpv_sim_topk(const mpv_sim_search_desc* d, float* vals, int64_t* idx, void* workspace, size_t workspace_bytes,
                             hipStream_t stream) {
-  return rs_topk(RS_TOPK, d, false, nullptr, vals, idx, workspace, workspace_bytes, stream);
+  return rs_topk(RS_TOPK, d, RsKind{}, vals, idx, workspace, workspace_bytes, stream);
 }
 extern "C" size_t mpv_sim_rank_workspace_size(const mpv_sim_search_desc* d, int n_targets) {
   if (!d || d->nq <= 0 || n_targets < 1 || n_targets > SC_MAX_T) return 0;
@@ -479,23 +546,52 @@ extern "C" size_t mpv_sim_rank_workspace_size(const mpv_sim_search_desc* d, int 
 }
 extern "C" int mpv_sim_rank(const mpv_sim_search_desc* d, const int64_t* target, int n_targets, int32_t* rank, void* workspace,
                             size_t workspace_bytes, hipStream_t stream) {
-  return rs_rank(RS_RANK, d, false, nullptr, target, n_targets, rank, workspace, workspace_bytes, stream);
+  return rs_rank(RS_RANK, d, RsKind{}, target, n_targets, rank, workspace, workspace_bytes, stream);
 }
 
 // ---- the same searches over e4m3 codes (include/mpv.h, "Searches over an FP8 gallery") ------------------------------------------
 extern "C" size_t mpv_sim_topk_q8_workspace_size(const mpv_sim_search_desc* d, const float* g_scale) {
-  return rs_topk_ws("mpv_sim_topk_q8_workspace_size", d, true, g_scale);
+  return rs_topk_ws("mpv_sim_topk_q8_workspace_size", d, RsKind{true, g_scale});
 }
 extern "C" int mpv_sim_topk_q8(const mpv_sim_search_desc* d, const float* g_scale, float* vals, int64_t* idx, void* workspace,
                                size_t workspace_bytes, hipStream_t stream) {
-  return rs_topk(RS_TOPK_Q8, d, true, g_scale, vals, idx, workspace, workspace_bytes, stream);
+  return rs_topk(RS_TOPK_Q8, d, RsKind{true, g_scale}, vals, idx, workspace, workspace_bytes, stream);
 }
 extern "C" size_t mpv_sim_rank_q8_workspace_size(const mpv_sim_search_desc* d, const float* g_scale, int n_targets) {
-  RsPlan p;                                           // a descriptor the call would refuse: 0
-  if (n_targets < 1 || n_targets > SC_MAX_T || rs_plan(d, &p, "mpv_sim_rank_q8_workspace_size", 0, true, g_scale) != MPV_OK) return 0;
-  return sc_ws_bytes((size_t)d->nq * n_targets);
+  return rs_rank_ws("mpv_sim_rank_q8_workspace_size", d, RsKind{true, g_scale}, n_targets);
 }
 extern "C" int mpv_sim_rank_q8(const mpv_sim_search_desc* d, const float* g_scale, const int64_t* target, int n_targets, int32_t* rank,
                                void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  return rs_rank(RS_RANK_Q8, d, true, g_scale, target, n_targets, rank, workspace, workspace_bytes, stream);
+  return rs_rank(RS_RANK_Q8, d, RsKind{true, g_scale}, target, n_targets, rank, workspace, workspace_bytes, stream);
+}
+
+// ---- the same searches with a per-row additive term (include/mpv.h, "Searches with per-row priors") ------------------------------
+extern "C" size_t mpv_sim_topk_prior_workspace_size(const mpv_sim_search_desc* d, const float* g_prior) {
+  return rs_topk_ws("mpv_sim_topk_prior_workspace_size", d, RsKind{false, nullptr, true, g_prior});
+}
+extern "C" int mpv_sim_topk_prior(const mpv_sim_search_desc* d, const float* g_prior, float* vals, int64_t* idx, void* workspace,
+                                  size_t workspace_bytes, hipStream_t stream) {
+  return rs_topk(RS_TOPK_PRI, d, RsKind{false, nullptr, true, g_prior}, vals, idx, workspace, workspace_bytes, stream);
+}
+extern "C" size_t mpv_sim_rank_prior_workspace_size(const mpv_sim_search_desc* d, const float* g_prior, int n_targets) {
+  return rs_rank_ws("mpv_sim_rank_prior_workspace_size", d, RsKind{false, nullptr, true, g_prior}, n_targets);
+}
+extern "C" int mpv_sim_rank_prior(const mpv_sim_search_desc* d, const float* g_prior, const int64_t* target, int n_targets,
+                                  int32_t* rank, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  return rs_rank(RS_RANK_PRI, d, RsKind{false, nullptr, true, g_prior}, target, n_targets, rank, workspace, workspace_bytes, stream);
+}
+extern "C" size_t mpv_sim_topk_prior_q8_workspace_size(const mpv_sim_search_desc* d, const float* g_scale, const float* g_prior) {
+  return rs_topk_ws("mpv_sim_topk_prior_q8_workspace_size", d, RsKind{true, g_scale, true, g_prior});
+}
+extern "C" int mpv_sim_topk_prior_q8(const mpv_sim_search_desc* d, const float* g_scale, const float* g_prior, float* vals,
+                                     int64_t* idx, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  return rs_topk(RS_TOPK_PRI8, d, RsKind{true, g_scale, true, g_prior}, vals, idx, workspace, workspace_bytes, stream);
+}
+extern "C" size_t mpv_sim_rank_prior_q8_workspace_size(const mpv_sim_search_desc* d, const float* g_scale, const float* g_prior,
+                                                       int n_targets) {
+  return rs_rank_ws("mpv_sim_rank_prior_q8_workspace_size", d, RsKind{true, g_scale, true, g_prior}, n_targets);
+}
+extern "C" int mpv_sim_rank_prior_q8(const mpv_sim_search_desc* d, const float* g_scale, const float* g_prior, const int64_t* target,
+                                     int n_targets, int32_t* rank, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  return rs_rank(RS_RANK_PRI8, d, RsKind{true, g_scale, true, g_prior}, target, n_targets, rank, workspace, workspace_bytes, stream);
 }

@@ -94,13 +94,54 @@ struct ScSource;
 template <>
 struct ScSource<const bf16*> {
   using Stage = ScStage;
-  static constexpr bool scaled = false;
+  static constexpr bool scaled = false, prior = false;
 };
 template <>
 struct ScSource<ScCodes> {
   using Stage = ScCodeStage;
-  static constexpr bool scaled = true;
+  static constexpr bool scaled = true, prior = false;
 };
+// ---- a streamed side with one fp32 additive term per row (the *_prior entries; include/mpv.h, "Searches with per-row priors") ----
+// Either source above plus `prior`: the term of tile row j travels with the chunk exactly as a code row's scale does (lane j loads
+// it) and is parked 4 bytes behind the scale's slot in the 16 spare bytes of the row's pitch.  A row of zeros has the term 0.
+template <class Src>
+struct ScPrior {
+  Src s;
+  const float* prior;        // one per row
+};
+template <class Stage>
+struct ScPriorStage {
+  Stage s;
+  float prior;               // of tile row lane & 31
+};
+template <class Src, class RowFn>
+__device__ __forceinline__ void sc_stage_load(ScPriorStage<typename ScSource<Src>::Stage>& st, ScPrior<Src> S, long long s_rs, int k0,
+                                              int D, RowFn row_of, int lane) {
+  sc_stage_load(st.s, S.s, s_rs, k0, D, row_of, lane);
+  const long long pr = row_of(lane & 31);
+  st.prior = pr >= 0 ? S.prior[pr] : 0.f;
+}
+template <class Stage>
+__device__ __forceinline__ void sc_stage_store(const ScPriorStage<Stage>& st, bf16* buf, int lane) {
+  sc_stage_store(st.s, buf, lane);
+  if (lane < SC_TILE) *(float*)(buf + lane * SC_PITCH + SC_KC + 2) = st.prior;
+}
+template <class Src>
+struct ScSource<ScPrior<Src>> {
+  using Stage = ScPriorStage<typename ScSource<Src>::Stage>;
+  static constexpr bool scaled = ScSource<Src>::scaled, prior = true;
+};
+// the term parked with staged tile row `row`
+__device__ __forceinline__ float sc_row_prior(const bf16* sbuf, int row) { return *(const float*)(sbuf + row * SC_PITCH + SC_KC + 2); }
+// fl(fl(scale * s) + prior): two separately rounded fp32 operations, never contracted into a fused multiply-add, so that a plain
+// fp32 restatement reproduces a score bit for bit from its accumulator
+__device__ __forceinline__ float sc_prior_score(float s, float scale, float prior) {
+#pragma clang fp contract(off)
+  const float m = s * scale;
+  return m + prior;
+}
+// A score with a term is eligible iff it is neither NaN nor -inf: -inf is how a row is left out.
+__device__ __forceinline__ bool sc_eligible(float v) { return v > -INFINITY; }
 // the scale parked with staged tile row `row`
 __device__ __forceinline__ float sc_row_scale(const bf16* sbuf, int row) { return *(const float*)(sbuf + row * SC_PITCH + SC_KC); }
 // acc[i] *= the scale of its row (sc_tile_mma below: row 8 (i / 4) + 4 (lane / 32) + i % 4), in fp32: the first thing a kernel
@@ -127,6 +168,26 @@ __device__ __forceinline__ void sc_load_resident(bf16* rbuf, const bf16* __restr
     bf16x8 v = {};
     if (gr >= 0) v = *(const bf16x8*)(R + gr * r_rs + c);
     *(bf16x8*)(rbuf + row * (D + 8) + c) = v;
+  }
+}
+// the same from codes: the resident tile holds the bf16 rows bf16(deq(code) * scale) (round to nearest even; exact for the
+// power-of-two scales of mpv_quantize_rows_e4m3), so whatever multiplies against it is what the bf16 entry computes on those rows
+template <class RowFn>
+__device__ __forceinline__ void sc_load_resident(bf16* rbuf, ScCodes R, long long r_rs, int D, RowFn row_of, int tid, int nthreads) {
+  const int upr = D >> 4;
+  for (int u = tid; u < SC_TILE * upr; u += nthreads) {
+    const int row = u / upr, c = (u - row * upr) * 16;
+    const long long gr = row_of(row);
+    i32x4 v = {};
+    float sc = 1.f;
+    if (gr >= 0) {
+      v = *(const i32x4*)(R.c + gr * r_rs + c);
+      sc = R.scale[gr];
+    }
+    Frag lo, hi;
+    deq_chunk(v, lo, hi);
+    *(bf16x8*)(rbuf + row * (D + 8) + c) = cvt8(cvt8(lo.b) * sc);
+    *(bf16x8*)(rbuf + row * (D + 8) + c + 8) = cvt8(cvt8(hi.b) * sc);
   }
 }
 

@@ -1339,13 +1339,20 @@ def _sim_desc(q, g, k, scale, slices, g_dtype=torch.bfloat16):
     return d
 
 
+def _row_pointers(g_scale):
+    """the per-row arguments between the descriptor and the outputs: none, the row scales, or a tuple of tensors in order"""
+    if g_scale is None:
+        return ()
+    return tuple(t.data_ptr() for t in (g_scale if isinstance(g_scale, tuple) else (g_scale,)))
+
+
 def _search_topk(name, d, q, k, g_scale=None):
     """vals / idx [Nq, k] filled by mpv_<name> on descriptor d, with the workspace mpv_<name>_workspace_size asks for; g_scale: the
-    row scales that the *_q8 entries take after the descriptor"""
+    row scales that the *_q8 entries take after the descriptor, or a tuple of per-row tensors in the entry's order (the *_prior entries)"""
     vals = torch.empty((q.shape[0], k), dtype=torch.float32, device=q.device)
     idx = torch.empty((q.shape[0], k), dtype=torch.int64, device=q.device)
     lib = _lib.lib()
-    extra = () if g_scale is None else (g_scale.data_ptr(),)
+    extra = _row_pointers(g_scale)
     ws = workspace(max(getattr(lib, f"mpv_{name}_workspace_size")(C.byref(d), *extra), 1), q.device)
     check(getattr(lib, f"mpv_{name}")(C.byref(d), *extra, vals.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
           f"mpv_{name}")
@@ -1363,7 +1370,7 @@ def _search_rank(name, d, q, target, queries="queries", g_scale=None):
     n_t = target.shape[1]
     rank = torch.empty(q.shape[0], dtype=torch.int32, device=q.device)
     lib = _lib.lib()
-    extra = () if g_scale is None else (g_scale.data_ptr(),)
+    extra = _row_pointers(g_scale)
     ws = workspace(max(getattr(lib, f"mpv_{name}_workspace_size")(C.byref(d), *extra, n_t), 1), q.device)
     check(getattr(lib, f"mpv_{name}")(C.byref(d), *extra, target.data_ptr(), n_t, rank.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
           f"mpv_{name}")
@@ -1404,6 +1411,75 @@ def sim_rank_q8(q, codes, g_scale, target, slices=0):
     """sim_rank over a gallery of e4m3 codes (sim_topk_q8; include/mpv.h: mpv_sim_rank_q8)"""
     d = _sim_desc(q, codes, 0, None, slices, g_dtype=torch.uint8)
     return _search_rank("sim_rank_q8", d, q, target, g_scale=_code_scales("sim_rank_q8", codes, g_scale))
+
+
+def _row_terms(what, g, prior):
+    """the per-row terms of a search with priors: fp32, contiguous, one per gallery row"""
+    _need_cuda(prior)
+    if prior.dtype != torch.float32 or tuple(prior.shape) != (g.shape[0],) or not prior.is_contiguous():
+        raise _lib.MpvError(f"{what}: prior must be a contiguous float32 tensor of shape ({g.shape[0]},), one term per gallery row "
+                            f"(got {prior.dtype} {tuple(prior.shape)})")
+    return prior
+
+
+def sim_topk_prior(q, g, prior, k, scale=None, slices=0):
+    """sim_topk with one fp32 additive term per gallery row: the score of row j is fl(fl(scale * <q_i, g_j>) + prior[j]) (two
+    roundings, no fused multiply-add).  A row whose score is -inf or NaN is left out altogether (prior[j] = -inf is a filter); a
+    query with fewer than k eligible rows gets the (-inf, -1) tail (include/mpv.h: mpv_sim_topk_prior)."""
+    d = _sim_desc(q, g, k, scale, slices)
+    return _search_topk("sim_topk_prior", d, q, k, g_scale=(_row_terms("sim_topk_prior", g, prior),))
+
+
+def sim_rank_prior(q, g, prior, target, scale=None, slices=0):
+    """sim_rank under the scores of sim_topk_prior -- `scale` IS applied here, the order depends on it.  A target that is not
+    eligible is no target; rows that are not eligible are never counted (include/mpv.h: mpv_sim_rank_prior)."""
+    d = _sim_desc(q, g, 0, scale, slices)
+    return _search_rank("sim_rank_prior", d, q, target, g_scale=(_row_terms("sim_rank_prior", g, prior),))
+
+
+def sim_topk_prior_q8(q, codes, g_scale, prior, k, scale=None, slices=0):
+    """sim_topk_prior over a gallery of e4m3 codes with row scales (sim_topk_q8; include/mpv.h: mpv_sim_topk_prior_q8)"""
+    d = _sim_desc(q, codes, k, scale, slices, g_dtype=torch.uint8)
+    extra = (_code_scales("sim_topk_prior_q8", codes, g_scale), _row_terms("sim_topk_prior_q8", codes, prior))
+    return _search_topk("sim_topk_prior_q8", d, q, k, g_scale=extra)
+
+
+def sim_rank_prior_q8(q, codes, g_scale, prior, target, scale=None, slices=0):
+    """sim_rank_prior over a gallery of e4m3 codes with row scales (include/mpv.h: mpv_sim_rank_prior_q8)"""
+    d = _sim_desc(q, codes, 0, scale, slices, g_dtype=torch.uint8)
+    extra = (_code_scales("sim_rank_prior_q8", codes, g_scale), _row_terms("sim_rank_prior_q8", codes, prior))
+    return _search_rank("sim_rank_prior_q8", d, q, target, g_scale=extra)
+
+
+def _bank_lse(name, bank, g, beta, g_dtype, g_scale=None):
+    _need_cuda(bank, g)
+    for what, t, want in (("bank", bank, torch.bfloat16), ("gallery", g, g_dtype)):
+        if t.dtype != want or t.dim() != 2 or t.shape[0] == 0 or t.stride(1) != 1:
+            raise _lib.MpvError(f"{name}: {what} must be a non-empty {want} [rows, dim] matrix with contiguous rows "
+                                f"(got {t.dtype} {tuple(t.shape)}, strides {t.stride()})")
+    if bank.shape[1] != g.shape[1]:
+        raise _lib.MpvError(f"{name}: feature widths differ ({bank.shape[1]} vs {g.shape[1]})")
+    d = _lib.SimBankDesc()
+    d.bank, d.gallery = bank.data_ptr(), g.data_ptr()
+    d.b_rs, d.g_rs = bank.stride(0) if bank.shape[0] > 1 else bank.shape[1], g.stride(0) if g.shape[0] > 1 else g.shape[1]
+    d.nb, d.ng, d.dim, d.beta = bank.shape[0], g.shape[0], g.shape[1], float(beta)
+    lse = torch.empty(g.shape[0], dtype=torch.float32, device=g.device)
+    extra = () if g_scale is None else (g_scale.data_ptr(),)
+    check(getattr(_lib.lib(), f"mpv_{name}")(C.byref(d), *extra, lse.data_ptr(), None, 0, _stream()), f"mpv_{name}")
+    return lse
+
+
+def sim_bank_lse(bank, g, beta):
+    """-> lse fp32 [Ng]: lse[j] = log sum_b exp(beta * <bank_b, g_j>) over the bank bf16 [Nb, D], kept against a running max (any
+    finite beta).  lse[j] depends on (bank, beta, row j) alone, bit for bit.  sim_topk_prior(q, g, -lse, k, scale=beta) is the
+    inverted-softmax (QB-Norm) search (include/mpv.h: mpv_sim_bank_lse)."""
+    return _bank_lse("sim_bank_lse", bank, g, beta, torch.bfloat16)
+
+
+def sim_bank_lse_q8(bank, codes, g_scale, beta):
+    """sim_bank_lse over a gallery of e4m3 codes with row scales: bit for bit sim_bank_lse on bf16(deq(codes) * g_scale)
+    (include/mpv.h: mpv_sim_bank_lse_q8)"""
+    return _bank_lse("sim_bank_lse_q8", bank, codes, beta, torch.uint8, g_scale=_code_scales("sim_bank_lse_q8", codes, g_scale))
 
 
 def _maxsim_side(name, t, dtype=torch.bfloat16):

@@ -146,14 +146,15 @@ class DistributedGPT3_Retrieval(nn.Module):
 
     # ------------------------------------------------------------------ search
     @torch.no_grad()
-    def search_videos(self, text, index: "RetrievalIndex", k: int):
-        """-> (scores fp32 [B, k], indices int64 [B, k]): the k best rows of a video-feature index for each tokenised title"""
-        return index.search(self.extract_text_feature(text), k)
+    def search_videos(self, text, index: "RetrievalIndex", k: int, **how):
+        """-> (scores fp32 [B, k], indices int64 [B, k]): the k best rows of a video-feature index for each tokenised title; `how`:
+        the keywords of RetrievalIndex.search (scale, use_prior, normalised)"""
+        return index.search(self.extract_text_feature(text), k, **how)
 
     @torch.no_grad()
-    def search_texts(self, video, index: "RetrievalIndex", k: int):
-        """-> (scores, indices): the k best rows of a text-feature index for each clip"""
-        return index.search(self.extract_vision_feature(video), k)
+    def search_texts(self, video, index: "RetrievalIndex", k: int, **how):
+        """-> (scores, indices): the k best rows of a text-feature index for each clip; `how` as in search_videos"""
+        return index.search(self.extract_vision_feature(video), k, **how)
 
     # ------------------------------------------------------------------ pipelines
     def _forward_pipeline(self, video, ids, mask, idx):
@@ -320,11 +321,27 @@ class _FeatureIndex:
         return target
 
 
+class _RowTerms:
+    """What a RetrievalIndex keeps per row once priors, exclusions or a normaliser are used (never before): each of `prior` (fp32),
+    `excluded` (bool) and `lse` (fp32, with the `bank` and `beta` it was fitted on) is storage of the index's capacity or None;
+    `cache` holds the effective terms built from them, per (use_prior, normalised), until one of the three changes."""
+
+    def __init__(self):
+        self.prior = self.excluded = self.lse = self.bank = self.beta = None
+        self.cache = {}
+
+
 class RetrievalIndex(_FeatureIndex):
     """Gallery of L2-normalised bf16 feature rows (what extract_vision_feature / extract_text_feature return) searched on the
     device by ops.sim_topk / ops.sim_rank: the [queries, gallery] score matrix is never built.  Rows keep the order they were
     added in; row i of the index is the i-th feature ever added.  Storage grows geometrically, so `add` does not re-allocate
-    per call.  Order rule of both searches: higher score first, equal scores by the lower row index (include/mpv.h)."""
+    per call.  Order rule of both searches: higher score first, equal scores by the lower row index (include/mpv.h).
+
+    Per-row terms (include/mpv.h, "Searches with per-row priors"): a prior added to a row's score (set_prior), rows left out
+    (exclude / include) and the inverted-softmax normaliser lse[g] = log sum_b exp(beta * <b, g>) over a bank of queries
+    (fit_normaliser; QB-Norm, or dual softmax when the bank is the test queries themselves).  A search then scores row g as
+    scale * <q, g> + prior[g] - lse[g], or not at all when it is excluded, through ops.sim_topk_prior / ops.sim_rank_prior.  An
+    index on which none of the three was ever used runs the plain ops and keeps nothing per row."""
 
     def __init__(self, dim: int, device="cuda", capacity: int = 1024, storage: str = "bf16"):
         if dim % 32 != 0 or not 32 <= dim <= 1024:
@@ -340,30 +357,198 @@ class RetrievalIndex(_FeatureIndex):
             raise ops._lib.MpvError(f"RetrievalIndex.{what}: features must be [rows, {self.dim}] (got {tuple(feats.shape)})")
 
     def add(self, features):
-        """append rows; -> the index of the first one"""
+        """append rows; -> the index of the first one.  With per-row terms in use the new rows get prior 0, are not excluded, and
+        get their normaliser from the bank that was fitted -- for the new rows only: lse[g] depends on row g alone, bit for bit."""
         self._check(features, "add")
-        return self._append(features)
+        first = self._append(features)
+        terms = getattr(self, "_terms", None)
+        if terms is not None and self.size > first:
+            new = slice(first, self.size)
+            if terms.prior is not None:
+                terms.prior[new] = 0
+            if terms.excluded is not None:
+                terms.excluded[new] = False
+            if terms.lse is not None:
+                terms.lse[new] = self._bank_lse(terms.bank, terms.beta, new)
+            terms.cache.clear()
+        return first
 
-    def search(self, query_features, k: int, scale=None):
-        """-> (scores fp32 [Nq, k], indices int64 [Nq, k]), best first; (-inf, -1) beyond the index size"""
+    # ------------------------------------------------------------------ per-row terms
+    def _allocate(self, capacity):
+        super()._allocate(capacity)
+        terms = getattr(self, "_terms", None)
+        if terms is not None:
+            for name in ("prior", "excluded", "lse"):
+                old = getattr(terms, name)
+                if old is not None:
+                    grown = torch.zeros(capacity, dtype=old.dtype, device=self.device)
+                    grown[:self.size].copy_(old[:self.size])
+                    setattr(terms, name, grown)
+
+    def _row_terms(self, name=None, dtype=torch.float32):
+        """the per-row state, created on first use; `name`: that array too, zeros of the index's capacity"""
+        terms = getattr(self, "_terms", None)
+        if terms is None:
+            terms = self._terms = _RowTerms()
+        if name is not None and getattr(terms, name) is None:
+            setattr(terms, name, torch.zeros(self.capacity, dtype=dtype, device=self.device))
+        terms.cache.clear()
+        return terms
+
+    def _rows_arg(self, rows, what):
+        rows = torch.as_tensor(rows, dtype=torch.int64, device=self.device).reshape(-1)
+        if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= self.size):
+            raise ops._lib.MpvError(f"RetrievalIndex.{what}: rows must be in [0, {self.size}) (got {int(rows.min())} .. {int(rows.max())})")
+        return rows
+
+    def set_prior(self, values, rows=None):
+        """prior[rows] = values (fp32; rows None: all rows, values a scalar or one per row).  -inf leaves a row out, as exclude does.
+        Rows added later get 0."""
+        values = torch.as_tensor(values, dtype=torch.float32, device=self.device)
+        if torch.isnan(values).any():
+            raise ops._lib.MpvError("RetrievalIndex.set_prior: a prior must not be NaN")
+        if rows is None:
+            if values.dim() > 0 and tuple(values.shape) != (self.size,):
+                raise ops._lib.MpvError(f"RetrievalIndex.set_prior: values must be a scalar or of shape ({self.size},) "
+                                        f"(got {tuple(values.shape)})")
+            self._row_terms("prior").prior[:self.size] = values
+        else:
+            rows = self._rows_arg(rows, "set_prior")
+            if values.dim() > 0 and values.numel() != rows.numel():
+                raise ops._lib.MpvError(f"RetrievalIndex.set_prior: {values.numel()} values for {rows.numel()} rows")
+            self._row_terms("prior").prior[rows] = values.reshape(-1) if values.dim() > 0 else values
+
+    @property
+    def prior(self):
+        """the priors of the rows added so far (a view, fp32 [size]), or None when none was ever set"""
+        terms = getattr(self, "_terms", None)
+        return None if terms is None or terms.prior is None else terms.prior[:self.size]
+
+    def clear_prior(self):
+        if self.prior is not None:
+            self._row_terms().prior = None
+
+    def exclude(self, rows):
+        """leave these rows out of every search and rank from now on (as results, as competitors and as targets)"""
+        rows = self._rows_arg(rows, "exclude")
+        self._row_terms("excluded", torch.bool).excluded[rows] = True
+
+    def include(self, rows):
+        """take rows back in that exclude() left out"""
+        rows = self._rows_arg(rows, "include")
+        if getattr(self, "_terms", None) is not None and self._terms.excluded is not None:
+            self._row_terms().excluded[rows] = False
+
+    @property
+    def excluded(self):
+        """bool [size]: the rows that are left out"""
+        terms = getattr(self, "_terms", None)
+        if terms is None or terms.excluded is None:
+            return torch.zeros(self.size, dtype=torch.bool, device=self.device)
+        return terms.excluded[:self.size]
+
+    def _bank_lse(self, bank, beta, rows):
+        if self.storage == "fp8":
+            return ops.sim_bank_lse_q8(bank, self._rows[rows], self._scales[rows].contiguous(), beta)
+        return ops.sim_bank_lse(bank, self._rows[rows], beta)
+
+    def fit_normaliser(self, bank_features, beta):
+        """inverted softmax over a bank of queries, bf16 [n, dim]: keeps the bank and beta, computes lse[g] = log sum_b
+        exp(beta * <b, g>) for the rows present (ops.sim_bank_lse); `add` computes it for new rows.  Searches are then normalised by
+        default: scores beta * <q, g> - lse[g]."""
+        self._check(bank_features, "fit_normaliser")
+        beta = float(beta)
+        if bank_features.shape[0] == 0 or beta != beta or beta in (float("inf"), float("-inf")):
+            raise ops._lib.MpvError(f"RetrievalIndex.fit_normaliser: a non-empty bank and a finite beta are needed (got "
+                                    f"{bank_features.shape[0]} rows, beta {beta})")
+        bank = bank_features.detach().to(self.device).contiguous().clone()
+        lse = self._bank_lse(bank, beta, slice(0, self.size)) if self.size else None
+        terms = self._row_terms("lse")
+        terms.bank, terms.beta = bank, beta
+        if lse is not None:
+            terms.lse[:self.size] = lse
+
+    @property
+    def normaliser(self):
+        """(bank bf16 [n, dim], beta, lse fp32 [size]) of fit_normaliser, or None"""
+        terms = getattr(self, "_terms", None)
+        return None if terms is None or terms.lse is None else (terms.bank, terms.beta, terms.lse[:self.size])
+
+    def clear_normaliser(self):
+        if self.normaliser is not None:
+            terms = self._row_terms()
+            terms.lse = terms.bank = terms.beta = None
+
+    def _effective(self, what, scale, use_prior, normalised, always=False):
+        """-> (term fp32 [size] or None, scale): the per-row term of this call, (prior) + (-lse) + (-inf where excluded), and the
+        scale that goes with it (beta when normalised).  None: nothing applies and the plain op serves (`always`: a term of zeros
+        instead, for a rank with a scale, which only the prior entry applies)."""
+        terms = getattr(self, "_terms", None)
+        has_prior = terms is not None and terms.prior is not None
+        has_norm = terms is not None and terms.lse is not None
+        for name, asked, has, how in (("use_prior", use_prior, has_prior, "set_prior"), ("normalised", normalised, has_norm, "fit_normaliser")):
+            if asked and not has:
+                raise ops._lib.MpvError(f"RetrievalIndex.{what}: {name}=True, but {how}() was never called on this index")
+        use_prior = has_prior if use_prior is None else bool(use_prior)
+        normalised = has_norm if normalised is None else bool(normalised)
+        if normalised:
+            if scale is not None:
+                raise ops._lib.MpvError(f"RetrievalIndex.{what}: a normalised search scores beta * <q, g> - lse[g] with the beta of "
+                                        f"fit_normaliser ({terms.beta}); pass no scale, or normalised=False")
+            scale = terms.beta
+        if not (use_prior or normalised or always or (terms is not None and terms.excluded is not None)):
+            return None, scale
+        if terms is None:
+            terms = self._row_terms()
+        key = (use_prior, normalised)
+        if key not in terms.cache:
+            term = torch.zeros(self.size, dtype=torch.float32, device=self.device)
+            if use_prior:
+                term += terms.prior[:self.size]
+            if normalised:
+                term -= terms.lse[:self.size]
+            if terms.excluded is not None:
+                term.masked_fill_(terms.excluded[:self.size], float("-inf"))
+            terms.cache[key] = term
+        return terms.cache[key], scale
+
+    def search(self, query_features, k: int, scale=None, use_prior=None, normalised=None):
+        """-> (scores fp32 [Nq, k], indices int64 [Nq, k]), best first; (-inf, -1) beyond the rows that can be returned.
+        use_prior / normalised: None = yes if a prior is set / a normaliser is fitted; True where there is none is refused.
+        normalised uses scale = beta (a scale passed as well is refused); the scores are then beta * s - lse[g] (+ prior[g]).
+        Excluded rows are never returned."""
         self._check(query_features, "search")
         if not 1 <= int(k) <= 32:
             raise ops._lib.MpvError(f"RetrievalIndex.search: k ({k}) must be in [1, 32]")
         if self.size == 0:
             raise ops._lib.MpvError("RetrievalIndex.search: the index is empty")
+        term, scale = self._effective("search", scale, use_prior, normalised)
+        q = query_features.contiguous()
+        if term is not None:
+            if self.storage == "fp8":
+                return ops.sim_topk_prior_q8(q, self.codes, self.scales, term, int(k), scale=scale)
+            return ops.sim_topk_prior(q, self.features, term, int(k), scale=scale)
         if self.storage == "fp8":
-            return ops.sim_topk_q8(query_features.contiguous(), self.codes, self.scales, int(k), scale=scale)
-        return ops.sim_topk(query_features.contiguous(), self.features, int(k), scale=scale)
+            return ops.sim_topk_q8(q, self.codes, self.scales, int(k), scale=scale)
+        return ops.sim_topk(q, self.features, int(k), scale=scale)
 
-    def rank(self, query_features, target):
-        """-> int32 [Nq]: the best rank (0 = first) among each query's target rows; target int64 [Nq] or [Nq, n_t], -1 = unused"""
+    def rank(self, query_features, target, scale=None, use_prior=None, normalised=None):
+        """-> int32 [Nq]: the best rank (0 = first) among each query's target rows; target int64 [Nq] or [Nq, n_t], -1 = unused.
+        scale, use_prior, normalised as in search: the ranks are those under the scores search returns.  An excluded target is no
+        target (the index size when a query has no other)."""
         self._check(query_features, "rank")
         if self.size == 0:
             raise ops._lib.MpvError("RetrievalIndex.rank: the index is empty")
         target = self._targets(target, query_features, "rows")
+        term, scale = self._effective("rank", scale, use_prior, normalised, always=scale is not None)
+        q = query_features.contiguous()
+        if term is not None:
+            if self.storage == "fp8":
+                return ops.sim_rank_prior_q8(q, self.codes, self.scales, term, target, scale=scale)
+            return ops.sim_rank_prior(q, self.features, term, target, scale=scale)
         if self.storage == "fp8":
-            return ops.sim_rank_q8(query_features.contiguous(), self.codes, self.scales, target)
-        return ops.sim_rank(query_features.contiguous(), self.features, target)
+            return ops.sim_rank_q8(q, self.codes, self.scales, target)
+        return ops.sim_rank(q, self.features, target)
 
 
 class MaxSimIndex(_FeatureIndex):
