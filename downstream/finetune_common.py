@@ -198,6 +198,45 @@ def load_resume_state(model, path):
     return msg
 
 
+# ---------------------------------------------------------------------------------------------- decoder LoRA adapters (no reference counterpart)
+def add_lora_args(p):
+    """the four flags every entry point shares: rank / alpha override the config's lora_rank / lora_alpha"""
+    p.add_argument("--lora_rank", type=int, default=None, help="LoRA adapters of this rank (8, 16, 32, 64) on the frozen decoder's q/k/v "
+                                                                 "projections; 0 = off; default: the config's lora_rank")
+    p.add_argument("--lora_alpha", type=float, default=None, help="--lora_rank: the adapters' scale is alpha / rank (default: the rank)")
+    p.add_argument("--lora_save", type=str, default=None, metavar="FILE", help="write the adapter-only state dict to FILE at the end of training")
+    p.add_argument("--lora_load", type=str, default=None, metavar="FILE", help="load an adapter-only state dict written by --lora_save")
+
+
+def apply_lora_args(args, config):
+    if getattr(args, "lora_rank", None) is not None:
+        config["lora_rank"] = args.lora_rank
+    if getattr(args, "lora_alpha", None) is not None:
+        config["lora_alpha"] = args.lora_alpha
+    if (getattr(args, "lora_save", None) or getattr(args, "lora_load", None)) and not config.get("lora_rank", 0):
+        raise ValueError("--lora_save / --lora_load need adapters: pass --lora_rank N (or set lora_rank in the config)")
+
+
+def load_lora(args, model):
+    """`--lora_load FILE` into the model's decoder, before the engine copies the parameters into its flat buffer"""
+    if getattr(args, "lora_load", None):
+        model.text_decoder.load_lora_state_dict(torch.load(args.lora_load, map_location="cpu"))
+        print("load adapters from %s" % args.lora_load)
+
+
+def save_lora(args, model):
+    """`--lora_save FILE`: the adapters alone (rank, alpha and two tensors per layer), written by rank 0"""
+    if getattr(args, "lora_save", None) and dist.get_rank() == 0:
+        torch.save(getattr(model, "module", model).text_decoder.lora_state_dict(), args.lora_save)
+        print("saved adapters to %s" % args.lora_save)
+
+
+def lora_merged_for_eval(model):
+    """context manager for evaluation code that leaves forward_lm (generation, score_captions, the shared-prefix scorers): the decoder's
+    adapters are merged into its weights inside and restored behind it; nothing happens on a model without adapters"""
+    return getattr(model, "module", model).text_decoder.lora_merged()
+
+
 def get_args(argv=None, extra=None, config_defaults=None):
     """The command line the four entry points share (:527-560) + `--synthetic_steps`; YAML `optimizer` / `schedular` sections fill
     the arguments the command line left unset (:572-581); the visual JSON's img_size / num_frames / clip_model go into the config
@@ -224,10 +263,12 @@ def get_args(argv=None, extra=None, config_defaults=None):
     p.add_argument("--zero_stage", default=1, type=int)
     p.add_argument("--evaluate_only", action="store_true", default=False)
     p.add_argument("--synthetic_steps", default=0, type=int, help="run on N synthetic batches per epoch instead of the dataset")
+    add_lora_args(p)
     if extra is not None:
         extra(p)
     args, _ = p.parse_known_args(argv)
     config = yaml.load(open(args.config, "r"), Loader=_ConfigLoader)
+    apply_lora_args(args, config)
     Path(args.output_dir).mkdir(parents=True, exist_ok=True)
     for section in ("optimizer", "schedular"):
         for name, val in (config.get(section) or {}).items():
@@ -278,6 +319,7 @@ def build_engine(args, config, model_cls, s):
     print("number of params (B):", s.n_parameters / 1e9)
     if args.resume:
         load_resume_state(model, args.resume)
+    load_lora(args, model)
     groups = mpv_engine.get_parameter_groups(model, config["optimizer"]["weight_decay"], model.no_weight_decay(),
                                              visual_backbone_scale=config.get("clip_model", False))
     s.model, s.optimizer, _, _ = mpv_engine.initialize(args=args, model=model, model_parameters=groups)
@@ -300,6 +342,7 @@ def epoch_loop(args, s, step_fn, after_epoch):
             s.model.save_checkpoint(save_dir=args.output_dir, tag=f"checkpoint-{epoch}", client_state={"epoch": epoch})
         log_stats = {**{f"train_{k}": v for k, v in train_stats.items()}, **after_epoch(epoch), "epoch": epoch, "n_parameters": s.n_parameters}
         write_log(args, log_stats)
+    save_lora(args, s.model)
     print("Training time {}".format(str(datetime.timedelta(seconds=int(time.time() - t_start)))))
     return log_stats
 

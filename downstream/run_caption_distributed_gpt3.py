@@ -441,8 +441,12 @@ def main(args, config):
     if getattr(args, "scst", False) and not args.evaluate_only:
         step_fn = scst_step_fn(args, config, s, data_loader)
 
+    def evaluate_merged(*a, **kw):                                # generation and score_captions leave forward_lm: adapters, if any, are merged
+        with ft.lora_merged_for_eval(s.model):
+            return evaluation(*a, **kw)
+
     if args.evaluate_only:
-        result = evaluation(s.model, val_loader, s.tokenizer, s.device, config, batched=getattr(args, "eval_batched_beam", False),
+        result = evaluate_merged(s.model, val_loader, s.tokenizer, s.device, config, batched=getattr(args, "eval_batched_beam", False),
                             clips_per_search=getattr(args, "clips_per_search", 32), eval_sample=getattr(args, "eval_sample", 0),
                             seed=getattr(args, "seed", 0) or 0, shared_kv=getattr(args, "eval_shared_kv", False),
                             constraints=constraint_keywords(args), best_of=getattr(args, "eval_sample_best_of", 0),

@@ -113,9 +113,10 @@ def main(args, config):
         return {"loss_generation": loss_generation, "loss_cls": loss_cls}
 
     def evaluate_both():
-        val = evaluation(s.model, val_loader, s.tokenizer, s.device, config, args.max_length, args.eval_shared_prefix)
-        print("Validation Performance:", val)
-        test = evaluation(s.model, test_loader, s.tokenizer, s.device, config, args.max_length, args.eval_shared_prefix)
+        with ft.lora_merged_for_eval(s.model):                       # --eval_shared_prefix leaves forward_lm: adapters, if any, are merged
+            val = evaluation(s.model, val_loader, s.tokenizer, s.device, config, args.max_length, args.eval_shared_prefix)
+            print("Validation Performance:", val)
+            test = evaluation(s.model, test_loader, s.tokenizer, s.device, config, args.max_length, args.eval_shared_prefix)
         print("Test Performance:", test)
         return {**{f"val_{k}": v for k, v in val.items()}, **{f"test_{k}": v for k, v in test.items()}}
 

@@ -330,6 +330,8 @@ def main(args, config):
     print("number of params (B):", n_parameters / 1e9)
     if args.resume:
         load_resume_state(model, args.resume)
+    import finetune_common as ft
+    ft.load_lora(args, model)
     groups = mpv_engine.get_parameter_groups(model, config["optimizer"]["weight_decay"], model.no_weight_decay(),
                                              visual_backbone_scale=config.get("clip_model", False))
     model, optimizer, _, _ = mpv_engine.initialize(args=args, model=model, model_parameters=groups)
@@ -370,6 +372,7 @@ def main(args, config):
         if args.output_dir and dist.get_rank() == 0:
             with open(os.path.join(args.output_dir, "log.txt"), "a", encoding="utf-8") as f:
                 f.write(json.dumps(log_stats) + "\n")
+    ft.save_lora(args, model)
     print("Training time {}".format(str(datetime.timedelta(seconds=int(time.time() - t_start)))))
     return log_stats
 
@@ -414,6 +417,8 @@ def get_args(argv=None):
                    help="with --eval_inverted_softmax: a .pt holding {'text': bf16 [n, D], 'video': bf16 [m, D]}, query features of the "
                         "training set, used as the bank instead of the test queries (the QB-Norm setting)")
     p.add_argument("--synthetic_steps", default=0, type=int, help="run on N synthetic batches per epoch instead of the dataset")
+    import finetune_common as ft                                        # (the LoRA flags and helpers the four fine-tuning entry points share)
+    ft.add_lora_args(p)
     args, _ = p.parse_known_args(argv)
     if args.eval_index_fp8 and not args.eval_on_device:
         p.error("--eval_index_fp8 needs --eval_on_device: only the on-device evaluation searches an index")
@@ -424,6 +429,7 @@ def get_args(argv=None):
     if args.eval_bank and args.eval_inverted_softmax is None:
         p.error("--eval_bank needs --eval_inverted_softmax BETA")
     config = yaml.load(open(args.config, "r"), Loader=_ConfigLoader)
+    ft.apply_lora_args(args, config)
     Path(args.output_dir).mkdir(parents=True, exist_ok=True)
     for section in ("optimizer", "schedular"):
         for name, val in (config.get(section) or {}).items():

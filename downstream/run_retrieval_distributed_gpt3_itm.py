@@ -143,8 +143,9 @@ def main(args, config):
         return {"loss_generation": loss_generation, "loss_cls": loss_cls}
 
     def evaluate(loader, name):
-        gen_v2t, gen_t2v, cls_v2t, cls_t2v = evaluation(s.model, loader, s.tokenizer, s.device, config, args.max_length,
-                                                        text_bs=args.eval_text_bs, shared_prefix=args.eval_shared_prefix)
+        with ft.lora_merged_for_eval(s.model):                  # --eval_shared_prefix leaves forward_lm: adapters, if any, are merged
+            gen_v2t, gen_t2v, cls_v2t, cls_t2v = evaluation(s.model, loader, s.tokenizer, s.device, config, args.max_length,
+                                                            text_bs=args.eval_text_bs, shared_prefix=args.eval_shared_prefix)
         ds = loader.dataset
         stats = {f"gen_{k}": v for k, v in itm_eval(gen_v2t, gen_t2v, ds.txt2vid, ds.vid2txt).items()}
         stats.update({f"cls_{k}": v for k, v in itm_eval(cls_v2t, cls_t2v, ds.txt2vid, ds.vid2txt).items()})

@@ -1410,6 +1410,30 @@ int mpv_adamw_step_grouped_dev(void* param_bf16, float* master, float* exp_avg, 
                                int64_t n, const uint8_t* tile_group, const float* hyper_dev, float beta1, float beta2, float eps,
                                float grad_scale, const float* sumsq, float max_norm, mpv_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * LoRA: the low-rank products of an adapter W + s B A on a frozen nn.Linear (lora_A [r, in], lora_B [out, r]); DESIGN.md section 36.
+ * The reference has no adapters: this is the middle setting between its freeze_text_decoder: true and false
+ * (models/distributed_gpt3.py:91-93).  bf16 operands, fp32 accumulation on the matrix cores, ONE bf16 rounding per output element.
+ * r is 8, 16, 32 or 64 (r = 8 is padded in registers, never in memory); C and N are multiples of 8; R >= 1 is any row count.
+ * Every leading dimension is given (multiples of 8, pointers 16-byte aligned): qkv and its slices are pitched.
+ * w(c, j) = w[j * ldw + c] when w_rank_major ([r, in]: lora_A), w[c * ldw + j] otherwise ([out, r]: lora_B); g likewise.
+ * All scalars by value, no host synchronisation, no allocation: the launches are capturable.
+ *
+ * mpv_lora_down:   t[i, j] = bf16(scale * sum_c x[i, c] w(c, j)), i < R, j < r.  Streams x once.
+ * mpv_lora_up_add: y[i, n] = bf16(fp32(y[i, n]) + scale * sum_j t[i, j] w(n, j)) in place, i < R, n < N; one read and one write
+ *                  of y, rows >= R and columns >= N are never touched.
+ * In both, the bits of row i do not depend on R (the reduction order of a row is a function of C / r alone).
+ * mpv_lora_wgrad:  g(c, j) = bf16(scale * sum_i t[i, j] x[i, c]), written [r, C] (g_rank_major) or [C, r].  Row slices are reduced
+ *                  through fp32 partials in the workspace (mpv_lora_wgrad_workspace_size bytes) in a fixed order, without
+ *                  floating-point atomics: two calls give the same bits. */
+int mpv_lora_down(const void* x, int64_t ldx, const void* w, int64_t ldw, int w_rank_major, void* t, int64_t ldt, int64_t R, int64_t C,
+                  int r, float scale, mpv_stream_t stream);
+int mpv_lora_up_add(const void* t, int64_t ldt, const void* w, int64_t ldw, int w_rank_major, void* y, int64_t ldy, int64_t R, int64_t N,
+                    int r, float scale, mpv_stream_t stream);
+size_t mpv_lora_wgrad_workspace_size(int64_t R, int64_t C, int r);
+int mpv_lora_wgrad(const void* t, int64_t ldt, const void* x, int64_t ldx, void* g, int64_t ldg, int g_rank_major, int64_t R, int64_t C,
+                   int r, float scale, void* workspace, size_t workspace_bytes, mpv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

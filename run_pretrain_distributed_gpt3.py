@@ -188,6 +188,8 @@ def main(args, config):
     model = DistributedGPT3_Pretrain(config=config, tokenizer=tokenizer, device=device)
     n_parameters = sum(p.numel() for p in model.parameters() if p.requires_grad)
     print("number of params (B):", n_parameters / 1e9)
+    if getattr(args, "lora_load", None):                  # before the engine copies the parameters into its flat buffer
+        model.text_decoder.load_lora_state_dict(torch.load(args.lora_load, map_location="cpu"))
     groups = mpv_engine.get_parameter_groups(model, config["optimizer"]["weight_decay"], model.no_weight_decay(),
                                              visual_backbone_scale=config.get("clip_model", False))
     model, optimizer, _, _ = mpv_engine.initialize(args=args, model=model, model_parameters=groups)
@@ -210,6 +212,8 @@ def main(args, config):
         if args.output_dir and dist.get_rank() == 0:
             with open(os.path.join(args.output_dir, "log.txt"), "a", encoding="utf-8") as f:
                 f.write(json.dumps({**{f"train_{k}": v for k, v in stats.items()}, "epoch": epoch, "n_parameters": n_parameters}) + "\n")
+    if getattr(args, "lora_save", None) and dist.get_rank() == 0:          # the adapters alone: rank, alpha, two tensors per layer
+        torch.save(getattr(model, "module", model).text_decoder.lora_state_dict(), args.lora_save)
     print("Training time {}".format(str(datetime.timedelta(seconds=int(time.time() - t_start)))))
     return stats
 
@@ -247,8 +251,20 @@ def get_args(argv=None):
     p.add_argument("--enable_deepspeed", action="store_true", default=False)
     p.add_argument("--zero_stage", default=1, type=int)
     p.add_argument("--synthetic_steps", default=0, type=int, help="run on N synthetic batches per epoch instead of the dataset")
+    # decoder LoRA adapters (no reference counterpart; the config keys lora_rank / lora_alpha, overridden here)
+    p.add_argument("--lora_rank", type=int, default=None, help="LoRA adapters of this rank (8, 16, 32, 64) on the frozen decoder's q/k/v "
+                                                                 "projections; 0 = off; default: the config's lora_rank")
+    p.add_argument("--lora_alpha", type=float, default=None, help="--lora_rank: the adapters' scale is alpha / rank (default: the rank)")
+    p.add_argument("--lora_save", type=str, default=None, metavar="FILE", help="write the adapter-only state dict to FILE at the end of training")
+    p.add_argument("--lora_load", type=str, default=None, metavar="FILE", help="load an adapter-only state dict written by --lora_save")
     args, _ = p.parse_known_args(argv)
     config = yaml.load(open(args.config, "r"), Loader=_ConfigLoader)
+    if args.lora_rank is not None:
+        config["lora_rank"] = args.lora_rank
+    if args.lora_alpha is not None:
+        config["lora_alpha"] = args.lora_alpha
+    if (args.lora_save or args.lora_load) and not config.get("lora_rank", 0):
+        raise ValueError("--lora_save / --lora_load need adapters: pass --lora_rank N (or set lora_rank in the config)")
     Path(args.output_dir).mkdir(parents=True, exist_ok=True)
     for section in ("optimizer", "schedular"):                         # YAML values fill whatever the command line left unset
         for name, val in (config.get(section) or {}).items():

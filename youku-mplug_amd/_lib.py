@@ -391,6 +391,12 @@ _SIGS.update({
     "mpv_caption_cider": (c_int, [C.POINTER(CaptionCiderDesc), c_void_p, c_size_t, c_void_p]),
     "mpv_cider_table_fill": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64]),
     "mpv_cider_table_lookup": (c_int64, [c_void_p, c_int64, c_uint64]),
+    # LoRA products (csrc/lora.hip)
+    "mpv_lora_down": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64, c_int64, c_int, c_float, c_void_p]),
+    "mpv_lora_up_add": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64, c_int64, c_int, c_float, c_void_p]),
+    "mpv_lora_wgrad_workspace_size": (c_size_t, [c_int64, c_int64, c_int]),
+    "mpv_lora_wgrad": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int64, c_int64, c_int, c_float,
+                               c_void_p, c_size_t, c_void_p]),
 })
 
 EXPORTS = tuple(_SIGS)

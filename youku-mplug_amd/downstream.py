@@ -189,7 +189,7 @@ class _GenCls(DistributedGPT3_Pretrain):
             dpooled = ops.gemm(dz, l0.weight, n, Hh, Hh, trans_b=True)
             dlh = torch.zeros((n * S, Hh), dtype=torch.bfloat16, device=dz.device)
             ops.scatter_rows(dpooled, tape["rows"], dlh, n, Hh)
-            dq2 = self.text_decoder.backward_lm(tape["gpt2"], None, d_last_hidden=dlh)
+            dq2 = self.text_decoder.backward_lm(tape["gpt2"], None, d_last_hidden=dlh, accumulate_lora=True)   # second pass of the step
             dq_rows = ops.add(dq_rows, dq2)
         # fold the expanded rows back onto the videos they came from, in row order (reproducible)
         per = Q * Hh
@@ -462,7 +462,8 @@ class DistributedGPT3_Caption(_GenCls):
         tape = {"vit": {}, "pool": {}, "gpt": {}, "gpt2": {}}
         qf = self._query_features(video, tape)                                               # 1. in the model's mode, on the tape
         dev = qf.device
-        with torch.no_grad(), _eval_mode(self):                                              # 2. the decode path sees no dropout
+        # 2. the decode path sees no dropout -- and no live adapters: the C decode drivers sample from the MERGED weights (a no-op without adapters)
+        with torch.no_grad(), _eval_mode(self), self.text_decoder.lora_merged():
             q3 = qf.view(B, Q, Hh)
             if o.rollouts is None:
                 table = self._scst_rollout(o, q3, N, top_k=o.top_k, top_p=o.top_p)

@@ -138,6 +138,7 @@ class DecodeState:
 
     def __init__(self, gpt, batch: int, max_len: int, weights: str = "bf16"):
         _check_weight_mode(weights)
+        gpt._refuse_live_lora("a decode state (the C decode drivers)")
         cfg = gpt.config
         self.gpt, self.batch, self.max_len = gpt, batch, max_len
         self.q8 = None                        # weights="fp8": the decoder's DecodeWeightsQ8 (re-quantised if a weight has moved)
@@ -190,6 +191,7 @@ class DecodeState:
     def _call(self, name: str, *tail):
         """The seam to the C step entries, also for the states built on a DecodeState: name(&weights, *tail), or, when the state holds
         an FP8 table, name_q8(&weights, &fp8 table, *tail) -- every step entry of include/mpv.h has both forms with the same tail."""
+        self.gpt._refuse_live_lora(name)      # (a state made while the adapters were merged, stepped after an unmerge)
         head = (C.byref(self._w),)
         if self.q8 is not None:
             name, head = name + "_q8", head + (C.byref(self._q8),)
@@ -322,8 +324,9 @@ class SharedPrefixDecodeState(_PrefixSuffixCaches):
 
     def __init__(self, gpt, batch: int, max_len: int, weights: str = "bf16"):
         _check_weight_mode(weights)
+        gpt._refuse_live_lora("a shared-prefix decode state (the C decode drivers)")
         self.gpt, self.batch, self.max_len, self.weights = gpt, batch, max_len, weights
-        self.fan = self.P = self.S = 0        # set, with prefix (the DecodeState of the prefill) and suffix, by prefill_fan_out
+        self.fan = self.P = self.S = 0       # set, with prefix (the DecodeState of the prefill) and suffix, by prefill_fan_out
         self.t = 0                            # suffix rows cached so far (per sequence)
         self.group_prefix_len = None          # ragged: int32 [G] on the device, Q + prompt_len
 

@@ -164,6 +164,14 @@ def _offset(layer: int, site: int) -> int:
     return (layer * 4 + site) << 36
 
 
+_LORA_SUFFIXES = ("query_key_value.lora_A", "query_key_value.lora_B")
+
+
+def _lora_keys_may_be_missing(module, incompatible_keys):
+    """load_state_dict post-hook of an adapted decoder: a base checkpoint has no adapter keys, and that is not an error"""
+    incompatible_keys.missing_keys[:] = [k for k in incompatible_keys.missing_keys if not k.endswith(_LORA_SUFFIXES)]
+
+
 class DistributedGPT3(nn.Module):
     """Drop-in for models/modeling_distributed_gpt3.py:1522 at TP=1 (checkpoint loading of
     `<model_dir>/model/mp_rank_00_model_states.pt['module']` :431-441 is kept)."""
@@ -189,6 +197,7 @@ class DistributedGPT3(nn.Module):
         """Quantises the layer products' weights and the tied embedding to e4m3 codes with per-row power-of-two scales, on the
         device, once, and keeps the result on the decoder (decode_weights="fp8" does this on first use, and again when a source
         parameter has been written to since).  -> the generation.DecodeWeightsQ8."""
+        self._refuse_live_lora("quantize_decode_weights")
         self._decode_weights_q8 = _generation.DecodeWeightsQ8(self)
         return self._decode_weights_q8
 
@@ -212,8 +221,158 @@ class DistributedGPT3(nn.Module):
 
     @property
     def trainable(self) -> bool:
-        """freeze_text_decoder: false (models/distributed_gpt3.py:91-93): the decoder's own parameters receive gradients"""
-        return any(p.requires_grad for p in self.parameters())
+        """freeze_text_decoder: false (models/distributed_gpt3.py:91-93): the decoder's own (BASE) parameters receive gradients.
+        LoRA adapters do not count: an adapted frozen decoder stays on the frozen (dgrad-only, fp32-stream) path."""
+        return any(p.requires_grad for n, p in self.named_parameters() if not n.endswith(_LORA_SUFFIXES))
+
+    # -------------------------------------------------------------- LoRA adapters on the fused q/k/v projection (DESIGN.md section 36)
+    def _qkv_linears(self):
+        return [layer.self_attention.query_key_value for layer in self.dist_model.language_model.encoder.layers]
+
+    def add_lora(self, rank: int, alpha: Optional[float] = None):
+        """Gives every layer's self_attention.query_key_value two trainable bf16 parameters, lora_A [rank, H] (std 0.02) and lora_B
+        [3H, rank] (zeros): qkv = x W^T + b + s (x A^T) B^T with s = alpha / rank (alpha defaults to rank).  The base stays frozen."""
+        if rank not in ops.LORA_RANKS:
+            raise ValueError(f"add_lora: rank {rank} is not one of {ops.LORA_RANKS}")
+        if self.__dict__.get("_lora") is not None:
+            raise RuntimeError("add_lora: this decoder already has adapters")
+        if self.trainable:
+            raise RuntimeError("add_lora: adapters go on a FROZEN decoder (freeze_text_decoder: true); this one's base parameters are trainable")
+        alpha = float(rank if alpha is None else alpha)
+        H = self.config.hidden_size
+        for lin in self._qkv_linears():
+            dev = lin.weight.device
+            lin.lora_A = _param(rank, H, std=0.02, device=dev)
+            lin.lora_B = _param(3 * H, rank, const=0.0, device=dev)
+        self._lora = dict(rank=int(rank), alpha=alpha, scale=alpha / rank, merged=False, saved=None)
+        # a BASE checkpoint loads with strict=True: only the adapter keys may be missing, and they stay as they are
+        self.register_load_state_dict_post_hook(_lora_keys_may_be_missing)
+        return self
+
+    def has_lora(self) -> bool:
+        return self.__dict__.get("_lora") is not None
+
+    def lora_live(self) -> bool:
+        """adapters present and not merged: forward_lm / backward_lm apply them; every other entry refuses"""
+        lo = self.__dict__.get("_lora")
+        return lo is not None and not lo["merged"]
+
+    def _refuse_live_lora(self, what: str):
+        if self.lora_live():
+            raise RuntimeError(f"{what} runs its own layer loop, which does not know the LoRA adapters: call merge_lora() first "
+                               "(or run it inside `with decoder.lora_merged():`)")
+
+    def _drop_weight_copies(self):
+        """the in-place merge writes the qkv weights through the kernels, which moves no tensor version: drop what is derived from them"""
+        cache = self.__dict__.get("_wt_cache")
+        if cache is not None:
+            for lin in self._qkv_linears():
+                cache.pop(id(lin.weight), None)
+        self.clear_decode_weights()
+
+    @torch.no_grad()
+    def merge_lora(self):
+        """W <- bf16(W + s B A) in place on every layer (ops.lora_up_add with t = B, w = A, y = W); keeps a bf16 copy of the original
+        weights and switches the adapters off.  Documented limit: the merge rounds W + dW to bf16, so what the delta contributes below
+        half a bf16 step of W is lost in the merged model (and only there)."""
+        lo = self.__dict__.get("_lora")
+        if lo is None:
+            raise RuntimeError("merge_lora: this decoder has no adapters")
+        if lo["merged"]:
+            raise RuntimeError("merge_lora: the adapters are already merged")
+        H, r = self.config.hidden_size, lo["rank"]
+        saved = []
+        for lin in self._qkv_linears():
+            saved.append(lin.weight.detach().clone())
+            ops.lora_up_add(lin.lora_B.detach(), lin.lora_A.detach(), lin.weight.detach(), 3 * H, H, r, w_rank_major=True, scale=lo["scale"])
+        lo.update(merged=True, saved=saved)
+        self._drop_weight_copies()
+
+    @torch.no_grad()
+    def unmerge_lora(self):
+        """restores the copy merge_lora kept, bit for bit, and switches the adapters back on"""
+        lo = self.__dict__.get("_lora")
+        if lo is None or not lo["merged"]:
+            raise RuntimeError("unmerge_lora: the adapters are not merged")
+        for lin, w in zip(self._qkv_linears(), lo["saved"]):
+            lin.weight.detach().copy_(w)
+        lo.update(merged=False, saved=None)
+        self._drop_weight_copies()
+
+    def lora_merged(self):
+        """context manager: merge_lora() on entry (unless already merged, which it then leaves alone), unmerge_lora() on exit.
+        Without adapters it does nothing."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def cm():
+            mine = self.lora_live()
+            if mine:
+                self.merge_lora()
+            try:
+                yield self
+            finally:
+                if mine:
+                    self.unmerge_lora()
+        return cm()
+
+    def merged_state_dict(self) -> dict:
+        """The state dict of the MERGED model under base names only (no adapter keys): loaded into an un-adapted stack it is the
+        merged model."""
+        with self.lora_merged():
+            return {k: v.detach().clone() for k, v in self.state_dict().items() if not k.endswith(_LORA_SUFFIXES)}
+
+    def lora_state_dict(self) -> dict:
+        """the adapters alone (state-dict keys of this module) plus their rank and alpha"""
+        lo = self.__dict__.get("_lora")
+        if lo is None:
+            raise RuntimeError("lora_state_dict: this decoder has no adapters")
+        sd = {k: v.detach().clone() for k, v in self.state_dict().items() if k.endswith(_LORA_SUFFIXES)}
+        sd["lora_rank"], sd["lora_alpha"] = lo["rank"], lo["alpha"]
+        return sd
+
+    @torch.no_grad()
+    def load_lora_state_dict(self, sd: dict):
+        lo = self.__dict__.get("_lora")
+        if lo is None:
+            raise RuntimeError("load_lora_state_dict: this decoder has no adapters (add_lora first)")
+        if lo["merged"]:
+            raise RuntimeError("load_lora_state_dict: the adapters are merged: unmerge_lora() first")
+        if int(sd["lora_rank"]) != lo["rank"] or float(sd["lora_alpha"]) != lo["alpha"]:
+            raise ValueError(f"load_lora_state_dict: file has rank {sd['lora_rank']} / alpha {sd['lora_alpha']}, the model "
+                             f"rank {lo['rank']} / alpha {lo['alpha']}")
+        own = {k: v for k, v in self.state_dict().items() if k.endswith(_LORA_SUFFIXES)}
+        given = {k: v for k, v in sd.items() if k not in ("lora_rank", "lora_alpha")}
+        if set(own) != set(given):
+            raise ValueError(f"load_lora_state_dict: keys differ: missing {sorted(set(own) - set(given))[:3]}, "
+                             f"unexpected {sorted(set(given) - set(own))[:3]}")
+        for k, v in given.items():
+            if tuple(v.shape) != tuple(own[k].shape):
+                raise ValueError(f"load_lora_state_dict: {k} has shape {tuple(v.shape)}, the model {tuple(own[k].shape)}")
+        for k, v in given.items():
+            own[k].copy_(v.to(own[k].dtype))
+
+    def _lora_forward(self, lin, x1, qkv, R):
+        """qkv += s (x1 A^T) B^T behind the frozen product; -> t = bf16(x1 A^T) [R, r] for the tape"""
+        lo = self._lora
+        H, r = self.config.hidden_size, lo["rank"]
+        t = ops.lora_down(x1, lin.lora_A, R, H, r, w_rank_major=True)
+        ops.lora_up_add(t, lin.lora_B, qkv, R, 3 * H, r, w_rank_major=False, scale=lo["scale"])
+        return t
+
+    def _lora_backward(self, lin, s, dqkv, R, accumulate):
+        """dB = s t^T dqkv -> grad_of(lora_B); dt = s dqkv B; dA = dt^T x1 -> grad_of(lora_A).  -> dt (the caller adds dt A to dx1).
+        accumulate: a later decoder pass of the same step adds to what the first one wrote."""
+        lo = self._lora
+        H, r = self.config.hidden_size, lo["rank"]
+        gB, gA = grad_of(lin.lora_B), grad_of(lin.lora_A)
+        dB = ops.lora_wgrad(s["t"], dqkv, R, 3 * H, r, g_rank_major=False, scale=lo["scale"], out=None if accumulate else gB)
+        dt = ops.lora_down(dqkv, lin.lora_B, R, 3 * H, r, w_rank_major=False, scale=lo["scale"])
+        dA = ops.lora_wgrad(dt, s["x1"], R, H, r, g_rank_major=True, out=None if accumulate else gA)
+        if accumulate:
+            ops.add(gB, dB, out=gB)
+            ops.add(gA, dA, out=gA)
+        return dt
 
     # -------------------------------------------------------------- explicit forward / backward
     def forward_lm(self, query_features: Optional[torch.Tensor], ids: torch.Tensor, labels: Optional[torch.Tensor],
@@ -257,6 +416,7 @@ class DistributedGPT3(nn.Module):
         nl = len(lm.encoder.layers)
         layers = []
         train_dec = self.trainable and not want_logits      # (autograd.Function.forward runs with grad mode off: not a usable signal)
+        lora = self.lora_live()
         if train_dec:
             # a trainable decoder runs the reference's own bf16 residual stream (the LayerNorm backward with parameter gradients reads
             # bf16 rows) on all rows of every layer, and keeps what the weight gradients need: the inputs of the four products
@@ -278,6 +438,7 @@ class DistributedGPT3(nn.Module):
                 stream = nxt if nxt is not None else stream
                 h_in = stream                                                   # x of LayerNorm 1 (for its backward)
                 qkv = ops.gemm(x1, att.query_key_value.weight, R, 3 * H, H, bias=att.query_key_value.bias, keep_output=True)
+                t_lora = self._lora_forward(att.query_key_value, x1, qkv, R) if lora else None
                 ctx = torch.empty((R, H), dtype=torch.bfloat16, device=h.device)
                 lse = ops.attn_fwd(qkv, qkv[:, hn:], qkv[:, 2 * hn:], ctx, lay, B, np_, S, S, hn, causal=True, scale=scale,
                                    dropout_p=p_a, seed=seed, offset=_offset(ln, _SITE_ATTN))
@@ -302,6 +463,8 @@ class DistributedGPT3(nn.Module):
                 ent = dict(h=h_in, s1=(m1, r1), qkv=qkv, ctx=ctx, lse=lse, h1=h1, s2=(m2, r2), z=z)
                 if top:
                     ent["rows"] = tm
+                if lora:
+                    ent.update(x1=x1, t=t_lora)
                 layers.append(ent)
                 stream, smap = h1, tm
             fl = lm.encoder.final_layernorm
@@ -367,6 +530,7 @@ class DistributedGPT3(nn.Module):
         loss_rows + labels -> losses fp32 [len(loss_rows)], the per-token CE of the tied LM head run on those rows only;
         hidden_rows -> hidden bf16 [len(hidden_rows), H], the final LayerNorm's output there."""
         assert not self.training, "shared-prefix scoring is an evaluation path (no dropout)"
+        self._refuse_live_lora("forward_continuation")
         cfg = self.config
         lm = self.dist_model.language_model
         n, Lc = ids.shape
@@ -451,6 +615,7 @@ class DistributedGPT3(nn.Module):
         row) and labels int64 [rows] are their targets.  -> dict(token_logprob fp32 [rows]): log softmax(logits[r])[labels[r]], the
         negated per-row loss of mpv_cross_entropy."""
         assert not self.training, "shared-prefix scoring is an evaluation path (no dropout)"
+        self._refuse_live_lora("forward_continuation_packed")
         cfg = self.config
         lm = self.dist_model.language_model
         P, ng = prefix["P"], prefix["B"]
@@ -483,6 +648,7 @@ class DistributedGPT3(nn.Module):
     def _shared_prefix_lm_check(self, P: int, longest: int):
         """forward_shared_prefix_lm's refusals, before any launch (forward_scst makes them before its rollout)"""
         cfg = self.config
+        self._refuse_live_lora("forward_shared_prefix_lm")
         if self.trainable:
             raise NotImplementedError("the shared-prefix training pass computes no decoder weight gradients: it needs freeze_text_decoder: true")
         if not FP32_STREAM:
@@ -506,6 +672,7 @@ class DistributedGPT3(nn.Module):
         Frozen decoder, fp32 residual stream, head_dim 64 / 80 (anything else raises before any launch).  The pass applies NO decoder
         dropout, neither hidden nor attention, whatever the module's mode: the packed attention has none, and one prefix cannot carry
         the N independent masks of its N continuations.  -> dict(loss); backward_shared_prefix_lm(tape, grad_loss)."""
+        self._refuse_live_lora("forward_shared_prefix_lm")
         cfg = self.config
         lm = self.dist_model.language_model
         H, np_, hn, V = cfg.hidden_size, cfg.num_attention_heads, cfg.kv_channels, cfg.vocab_size
@@ -616,11 +783,13 @@ class DistributedGPT3(nn.Module):
         lm = self.dist_model.language_model
         nl = len(lm.encoder.layers)
         trim_top = window is not None and not keep_inputs
+        lora = self.lora_live()
         for li, layer in enumerate(lm.encoder.layers):
             ln = li + 1
             att, mlp = layer.self_attention, layer.mlp
             x1, m1, r1 = ops.layernorm_fwd(h, layer.input_layernorm.weight, layer.input_layernorm.bias, layer.input_layernorm.eps, R, H)
             qkv = ops.gemm(x1, att.query_key_value.weight, R, 3 * H, H, bias=att.query_key_value.bias, keep_output=True)
+            t_lora = self._lora_forward(att.query_key_value, x1, qkv, R) if lora else None
             ctx = torch.empty((R, H), dtype=torch.bfloat16, device=h.device)
             lse = ops.attn_fwd(qkv, qkv[:, hn:], qkv[:, 2 * hn:], ctx, lay, B, np_, S, S, hn, causal=True, scale=scale,
                                dropout_p=p_a, seed=seed, offset=_offset(ln, _SITE_ATTN))
@@ -645,6 +814,8 @@ class DistributedGPT3(nn.Module):
                 ops.gemm(g, mlp.dense_4h_to_h.weight, Rw, H, F4, bias=mlp.dense_4h_to_h.bias, residual=h1, dropout_p=p_h,
                          seed=seed, offset=_offset(ln, _SITE_DROP2), cmap=tm, out=h2)
                 layers.append(dict(h=h, s1=(m1, r1), qkv=qkv, ctx=ctx, lse=lse, h1=h1, s2=(m2, r2), z=z, rows=tm))
+                if lora:
+                    layers[-1].update(x1=x1, t=t_lora)
                 h = h2
                 continue
             h1 = ops.gemm(ctx, att.dense.weight, R, H, H, bias=att.dense.bias, residual=h, dropout_p=p_h, seed=seed,
@@ -659,6 +830,8 @@ class DistributedGPT3(nn.Module):
             ent = dict(h=h, s1=(m1, r1), qkv=qkv, ctx=ctx, lse=lse, h1=h1, s2=(m2, r2), z=z)
             if keep_inputs:
                 ent.update(x1=x1, x2=x2, g=g)
+            if lora:
+                ent.update(x1=x1, t=t_lora)
             layers.append(ent)
             h = h2
         fl = lm.encoder.final_layernorm
@@ -699,9 +872,12 @@ class DistributedGPT3(nn.Module):
             return ops.ln_stream_bwd(dy, x, gamma, mean, rstd, rows, cols, **kw)
         return ops.layernorm_bwd(dy, x, gamma, mean, rstd, rows, cols, **kw)
 
-    def backward_lm(self, tape: dict, grad_loss: Optional[torch.Tensor] = None, d_last_hidden: Optional[torch.Tensor] = None):
+    def backward_lm(self, tape: dict, grad_loss: Optional[torch.Tensor] = None, d_last_hidden: Optional[torch.Tensor] = None,
+                    accumulate_lora: bool = False):
         """-> d(query_features) [B*Q, H] (dgrad only: the decoder is frozen).  The seed is the loss (grad_loss scales the
-        stored dlogits) and/or d_last_hidden [B*S, H], the gradient of the final-layernorm output."""
+        stored dlogits) and/or d_last_hidden [B*S, H], the gradient of the final-layernorm output.
+        A tape recorded with live LoRA adapters also writes their gradients into grad_of(lora_A / lora_B), overwriting them as the
+        decoder's other weight gradients do; accumulate_lora: this is a LATER decoder pass of the same step and adds to them."""
         cfg = self.config
         lm = self.dist_model.language_model
         B, Q, L, S = tape["B"], tape["Q"], tape["L"], tape["S"]
@@ -797,7 +973,10 @@ class DistributedGPT3(nn.Module):
             if td:      # fused q/k/v projection: dW = dqkv^T x1
                 ops.gemm(dqkv, s["x1"], 3 * H, H, R, trans_a=True, trans_b=True, out=grad_of(att.query_key_value.weight))
                 ops.colsum(dqkv, R, 3 * H, out=grad_of(att.query_key_value.bias))
+            dt_lora = self._lora_backward(att.query_key_value, s, dqkv, R, accumulate_lora) if s.get("t") is not None else None
             dx1 = self._dgrad(dqkv, att.query_key_value.weight, R, H, 3 * H)
+            if dt_lora is not None:      # the adapter's share of dx1: dx1 += dt A
+                ops.lora_up_add(dt_lora, att.query_key_value.lora_A, dx1, R, H, self._lora["rank"], w_rank_major=True)
             prev_off = _offset(li, _SITE_DROP2) if li > 0 else 0
             want_mask = drop and li > 0
             dh_m = torch.empty((R, H), dtype=torch.bfloat16, device=dh.device) if want_mask else None

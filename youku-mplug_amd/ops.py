@@ -1537,3 +1537,44 @@ def maxsim_rank_q8(q, codes, g_scale, target, slices=0):
     """maxsim_rank over a gallery of e4m3 codes (maxsim_topk_q8; include/mpv.h: mpv_maxsim_rank_q8)"""
     d = _maxsim_desc(q, codes, 0, None, slices, g_dtype=torch.uint8)
     return _search_rank("maxsim_rank_q8", d, q, target, queries="query items", g_scale=_code_scales("maxsim_rank_q8", codes, g_scale))
+
+
+# ---------------------------------------------------------------------------------------------- LoRA products (csrc/lora.hip)
+LORA_RANKS = (8, 16, 32, 64)
+
+
+def _ld(t, ld):
+    return int(ld) if ld is not None else int(t.stride(0))
+
+
+def lora_down(x, w, R, C, r, *, w_rank_major, scale=1.0, out=None, ldx=None, ldw=None, ldt=None):
+    """t[R, r] = bf16(scale * x[R, C] w(C, r)); w(c, j) = w[j, c] if w_rank_major ([r, C]: lora_A) else w[c, j] ([C, r]: lora_B).
+    Leading dimensions default to the tensors' row strides (include/mpv.h: mpv_lora_down)."""
+    _need_cuda(x, w, out)
+    if out is None:
+        out = torch.empty((R, r), dtype=torch.bfloat16, device=x.device)
+    check(_lib.lib().mpv_lora_down(x.data_ptr(), _ld(x, ldx), w.data_ptr(), _ld(w, ldw), int(w_rank_major), out.data_ptr(), _ld(out, ldt),
+                                   R, C, r, float(scale), _stream()), "mpv_lora_down")
+    return out
+
+
+def lora_up_add(t, w, y, R, N, r, *, w_rank_major, scale=1.0, ldt=None, ldw=None, ldy=None):
+    """y[R, N] = bf16(fp32(y) + scale * t[R, r] w(N, r)^T) in place; w(n, j) = w[j, n] if w_rank_major ([r, N]) else w[n, j] ([N, r])
+    (include/mpv.h: mpv_lora_up_add)."""
+    _need_cuda(t, w, y)
+    check(_lib.lib().mpv_lora_up_add(t.data_ptr(), _ld(t, ldt), w.data_ptr(), _ld(w, ldw), int(w_rank_major), y.data_ptr(), _ld(y, ldy),
+                                     R, N, r, float(scale), _stream()), "mpv_lora_up_add")
+    return y
+
+
+def lora_wgrad(t, x, R, C, r, *, g_rank_major, scale=1.0, out=None, ldt=None, ldx=None, ldg=None):
+    """g(C, r) = bf16(scale * t[R, r]^T x[R, C]), written [r, C] (g_rank_major) or [C, r]; fixed-order reduction, no atomics
+    (include/mpv.h: mpv_lora_wgrad)."""
+    _need_cuda(t, x, out)
+    if out is None:
+        out = torch.empty((r, C) if g_rank_major else (C, r), dtype=torch.bfloat16, device=x.device)
+    wsn = _lib.lib().mpv_lora_wgrad_workspace_size(R, C, r)
+    ws = workspace(wsn, x.device)
+    check(_lib.lib().mpv_lora_wgrad(t.data_ptr(), _ld(t, ldt), x.data_ptr(), _ld(x, ldx), out.data_ptr(), _ld(out, ldg), int(g_rank_major),
+                                    R, C, r, float(scale), ws.data_ptr(), ws.numel(), _stream()), "mpv_lora_wgrad")
+    return out

@@ -67,6 +67,12 @@ class DistributedGPT3_Pretrain(nn.Module):
         if config.get("freeze_text_decoder", True):                                       # :91-93 (every shipped recipe freezes it)
             for p in self.text_decoder.parameters():
                 p.requires_grad = False
+        # LoRA adapters on the frozen decoder's q/k/v projections (no reference counterpart): lora_rank 0 = off
+        lora_rank = int(config.get("lora_rank", 0) or 0)
+        if lora_rank:
+            if not config.get("freeze_text_decoder", True):
+                raise ValueError("lora_rank > 0 needs freeze_text_decoder: true: adapters go on a frozen decoder")
+            self.text_decoder.add_lora(lora_rank, config.get("lora_alpha", None))
         self.vision_width = visual_cfg["embed_dim"]
         self.text_width = self.text_decoder.config.hidden_size
         self.num_learnable_token = config.get("num_learnable_token", 256)                 # :102
@@ -139,7 +145,9 @@ class DistributedGPT3_Pretrain(nn.Module):
         Q, D, Hh, E = self.num_learnable_token, self.vision_width, self.text_width, self.vision_proj.out_features
         if B % 8:
             raise ValueError(f"use_contrastive: the per-rank batch ({B}) must be a multiple of 8 (operand rule of the head's GEMMs)")
-        pooled, tp, tf, tn = self._itc_text_features(ids, mask)
+        # live LoRA adapters: the text-only pass is no longer frozen below `pooled` -- keep its tape for _contrastive_backward
+        text_tape = {} if self.text_decoder.lora_live() else None
+        pooled, tp, tf, tn = self._itc_text_features(ids, mask, text_tape)
         iq = tape["image_query"]
         vp, vf, vn = self._itc_vision_features(iq, B)
         g = getattr(self, "process_group", None)
@@ -156,15 +164,19 @@ class DistributedGPT3_Pretrain(nn.Module):
         tape["loss_ita"] = (l1.sum() + l2.sum()) * scale
         tape["itc"] = dict(B=B, WB=WB, E=E, pooled=pooled, vp=vp, vn=vn, vf=vf, tp=tp, tn=tn, tf=tf, v_all=v_all, t_all=t_all,
                            arg1=arg1, arg2=arg2, ds1=ds1, ds2=ds2, dts=dt1.sum() + dt2.sum(), inv_temp=inv_temp)
+        if text_tape is not None:
+            tape["itc"].update(gpt_text=text_tape, L=L)
 
-    def _itc_text_features(self, ids, mask):
+    def _itc_text_features(self, ids, mask, gpt_tape=None):
         """-> (pooled [B, Hh], tp [B, E], tf = tp / |tp| bf16, tn): the title side of the head, shared by the loss and extract_text_feature"""
         B, L = ids.shape
         Hh, E = self.text_width, self.vision_proj.out_features
         # text-only pass of the frozen decoder (:169-176): hidden states after the final LayerNorm; its LM head / CE are unused in
         # the reference and skipped here.  pass_index 1: its dropout masks are not the caption pass's.
-        out = self.text_decoder.forward_lm(None, ids, None, None, {}, hidden_only=True, pass_index=1)
+        out = self.text_decoder.forward_lm(None, ids, None, None, {} if gpt_tape is None else gpt_tape, hidden_only=True, pass_index=1)
         rows = torch.arange(B, device=ids.device) * L + (mask.sum(dim=-1) - 1)                                  # :181
+        if gpt_tape is not None:
+            gpt_tape["pooled_rows"] = rows.contiguous()
         pooled = ops.gather_rows(out["last_hidden_state"].reshape(B * L, Hh), rows.contiguous(), B, Hh)
         tp = ops.gemm(pooled, self.text_proj.weight, B, E, Hh, bias=self.text_proj.bias)                       # :182
         tf, tn = ops.l2norm_fwd(tp, B, E)
@@ -229,6 +241,11 @@ class DistributedGPT3_Pretrain(nn.Module):
         dtp = ops.l2norm_bwd(dt, c["tp"], c["tn"], B, E)
         ops.colsum(dtp, B, E, out=grad_of(self.text_proj.bias))
         ops.gemm(dtp, c["pooled"], E, Hh, B, trans_a=True, trans_b=True, out=grad_of(self.text_proj.weight))
+        if "gpt_text" in c:             # live LoRA adapters: the text-only pass's backward, seeded at the pooled rows (first pass of the step)
+            dpooled = ops.gemm(dtp, self.text_proj.weight, B, Hh, E, trans_b=True)
+            dlh = torch.zeros((B * c["L"], Hh), dtype=torch.bfloat16, device=dtp.device)
+            ops.scatter_rows(dpooled, c["gpt_text"]["pooled_rows"], dlh, B, Hh)
+            self.text_decoder.backward_lm(c["gpt_text"], None, d_last_hidden=dlh)
         dvp = ops.l2norm_bwd(dv, c["vp"], c["vn"], B * Q, E)
         ops.colsum(dvp, B * Q, E, out=grad_of(self.vision_proj.bias))
         ops.gemm(dvp, tape["image_query"], E, D, B * Q, trans_a=True, trans_b=True, out=grad_of(self.vision_proj.weight))
@@ -279,7 +296,10 @@ class DistributedGPT3_Pretrain(nn.Module):
         diq_itc = None
         if "itc" in tape:               # every head gradient is complete before the "head" bucket is reported below
             diq_itc = self._contrastive_backward(tape, grad_ita if grad_ita is not None else torch.zeros((), device=grad_loss.device))
-        dqf = self.text_decoder.backward_lm(tape["gpt"], grad_loss)
+        if "itc" in tape and "gpt_text" in tape["itc"]:      # the adapters' gradients of the text-only pass are already in place
+            dqf = self.text_decoder.backward_lm(tape["gpt"], grad_loss, accumulate_lora=True)
+        else:
+            dqf = self.text_decoder.backward_lm(tape["gpt"], grad_loss)
         iq = tape["image_query"]
         if "qf_raw" in tape:
             vn = self.visual_norm

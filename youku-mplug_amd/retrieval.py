@@ -87,6 +87,9 @@ class DistributedGPT3_Retrieval(nn.Module):
                                       "(configs/retrieval/retrieval_gpt3_1.3B_youku_v0.yaml: freeze_text_decoder: true)")
         for p in self.text_decoder.parameters():
             p.requires_grad = False
+        lora_rank = int(config.get("lora_rank", 0) or 0)       # LoRA adapters on the frozen decoder: 0 = off
+        if lora_rank:
+            self.text_decoder.add_lora(lora_rank, config.get("lora_alpha", None))
         self.vision_width, self.text_width = visual_cfg["embed_dim"], self.text_decoder.config.hidden_size
         self.num_learnable_token = config.get("num_learnable_token", 256)
         # parameters that exist in the reference state-dict but are unused by the ITC forward (:942-945 commented out)
@@ -127,9 +130,12 @@ class DistributedGPT3_Retrieval(nn.Module):
     def _text_tower(self, ids, mask, tape):
         B, L = ids.shape
         H, E = self.text_width, self.text_proj.out_features
-        out = self.text_decoder.forward_lm(None, ids, None, None, {}, hidden_only=True)
+        gpt_tape = {}
+        out = self.text_decoder.forward_lm(None, ids, None, None, gpt_tape, hidden_only=True)
         last = mask.sum(dim=-1) - 1                                                                         # :958-959
         rows = torch.arange(B, device=ids.device) * L + last
+        if self.text_decoder.lora_live():       # the text tower is no longer frozen below `pooled`: keep the pass for _backward_pipeline
+            tape.update(gpt_text=gpt_tape, text_rows=rows.contiguous(), text_L=L)
         pooled = ops.gather_rows(out["last_hidden_state"].reshape(B * L, H), rows.contiguous(), B, H)
         tp = ops.gemm(pooled, self.text_proj.weight, B, E, H, bias=self.text_proj.bias)
         tf, tn = ops.l2norm_fwd(tp, B, E)
@@ -196,6 +202,11 @@ class DistributedGPT3_Retrieval(nn.Module):
         dtp = ops.l2norm_bwd(dt, tape["tp"], tape["tn"], B, E)
         ops.colsum(dtp, B, E, out=grad_of(self.text_proj.bias))
         ops.gemm(dtp, tape["pooled"], E, H, B, trans_a=True, trans_b=True, out=grad_of(self.text_proj.weight))
+        if "gpt_text" in tape:                  # live LoRA adapters: the text tower's backward, seeded at the pooled rows
+            dpooled = ops.gemm(dtp, self.text_proj.weight, B, H, E, trans_b=True)
+            dlh = torch.zeros((B * tape["text_L"], H), dtype=torch.bfloat16, device=dtp.device)
+            ops.scatter_rows(dpooled, tape["text_rows"], dlh, B, H)
+            self.text_decoder.backward_lm(tape["gpt_text"], None, d_last_hidden=dlh)
         # vision head
         dvp = ops.l2norm_bwd(dv, tape["vp"], tape["vn"], B, E)
         ops.colsum(dvp, B, E, out=grad_of(self.vision_proj.bias))
