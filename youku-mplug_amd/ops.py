@@ -15,7 +15,7 @@ import torch
 from . import _lib
 from ._lib import AttnDesc, GemmEpilogue, check
 
-ACT_NONE, ACT_GELU_ERF, ACT_GELU_TANH, ACT_RELU, ACT_DERIV = 0, 1, 2, 3, 4
+ACT_NONE, ACT_GELU_ERF, ACT_GELU_TANH, ACT_RELU, ACT_DERIV = (_lib.CONSTANTS["MPV_ACT_" + n] for n in ("NONE", "GELU_ERF", "GELU_TANH", "RELU", "DERIV"))
 # MPV_GELU_DERIV=0 (measurement knob): the MLPs park the pre-activation z and the dgrad epilogue evaluates GELU'(z), as until round 3.
 # Default: the forward epilogue parks GELU'(z) itself and the dgrad epilogue is one multiply (include/mpv.h: preact_deriv, MPV_ACT_DERIV).
 GELU_DERIV_FWD = os.environ.get("MPV_GELU_DERIV", "1") != "0"
@@ -131,7 +131,7 @@ def layernorm_fwd(x, gamma, beta, eps: float, rows: int, cols: int, *, out=None,
     return out, mean, rstd
 
 
-LN_DPARAM_DEFER = 2      # include/mpv.h: MPV_LN_DPARAM_DEFER
+LN_DPARAM_DEFER = _lib.CONSTANTS["MPV_LN_DPARAM_DEFER"]
 
 
 class LnDparamBatch:
